@@ -1,8 +1,8 @@
 """PNG -> ABGR texture words (host/TextureIO.h through libfyprt_host.so), the contract of the reference's
 Texture::Texture (Texture.cu:8-40, stb_image forced to 4 channels).  Pins: round trips through an independent encoder for
-every colour type / bit depth / filter type, hand-written expected words, rejection of what is not supported — and, when
-the reference tree is present (this container only, never on the GPU box), its own 2048x2048 texture assets decode and agree
-with an independent zlib + numpy unfilter."""
+every colour type / bit depth / filter type, hand-written expected words, rejection of what is not supported — and the
+reference's own 2048x2048 texture assets (their first 64 rows, stored verbatim as data fixtures under tests/golden/ by
+tools/make_texture_crops.py) decode and agree with an independent zlib + numpy unfilter."""
 import struct
 import zlib
 from pathlib import Path
@@ -12,7 +12,9 @@ import pytest
 
 from fypraytracer_amd import texture
 
-REF_ASSETS = Path("/root/reference/FYPRayTracer/Assets/3D Models/Test")
+GOLDEN = Path(__file__).resolve().parent / "golden"
+# the reference's texture assets (Assets/3D Models/Test/*.png), rows 0-63 with their filtered scanline bytes as stored
+ASSET_CROPS = {"bananaDiffuse.png": GOLDEN / "tex_bananaDiffuse_rows64.png", "toasterBaseColor.png": GOLDEN / "tex_toasterBaseColor_rows64.png"}
 
 
 def _abgr(r, g, b, a):
@@ -122,33 +124,11 @@ def _independent_decode(path):
     return _abgr(px[..., 0], px[..., 1], px[..., 2], px[..., 3])
 
 
-@pytest.mark.skipif(not REF_ASSETS.exists(), reason="reference assets are only present in the build container")
 @pytest.mark.parametrize("name", ["bananaDiffuse.png", "toasterBaseColor.png"])
 def test_reference_texture_assets_decode(name):
-    px = texture.load_png(REF_ASSETS / name)
-    assert px.shape == (2048, 2048)
-    rows = slice(0, 24)                                                     # the per-byte Python unfilter is slow: compare the first rows
-    want = _independent_decode_rows(REF_ASSETS / name, 24)
-    assert np.array_equal(px[rows], want)
-
-
-def _independent_decode_rows(path, nrows):
-    import io
-    raw = Path(path).read_bytes()
-    pos, idat, hdr = 8, b"", None
-    while pos < len(raw):
-        n, kind = struct.unpack(">I4s", raw[pos:pos + 8])
-        if kind == b"IHDR":
-            hdr = struct.unpack(">IIBBBBB", raw[pos + 8:pos + 21])
-        elif kind == b"IDAT":
-            idat += raw[pos + 8:pos + 8 + n]
-        pos += 12 + n
-    w, h, depth, ctype = hdr[:4]
-    ch = {2: 3, 6: 4}[ctype]
-    need = nrows * (1 + w * ch)
-    part = zlib.decompressobj().decompress(idat, need)
-    small = texture.encode_png(np.zeros((1, 1, ch), np.uint8), ctype)       # reuse the chunk writer for a cropped file
-    ihdr = struct.pack(">IIBBBBB", w, nrows, 8, ctype, 0, 0, 0)
-    tmp = b"\x89PNG\r\n\x1a\n" + texture._chunk(b"IHDR", ihdr) + texture._chunk(b"IDAT", zlib.compress(part[:need])) + texture._chunk(b"IEND", b"")
-    p = Path("/tmp/_crop.png"); p.write_bytes(tmp)
-    return _independent_decode(p)
+    path = ASSET_CROPS[name]
+    px = texture.load_png(path)
+    assert px.shape == (64, 2048)
+    assert np.array_equal(px, _independent_decode(path))
+    if name == "bananaDiffuse.png":                                         # the words config 2's data fixture holds for the whole asset
+        assert np.array_equal(px, np.load(GOLDEN / "banana_asset.npz")["texture"][:64])
