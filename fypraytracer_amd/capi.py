@@ -46,6 +46,10 @@ LT_NODE_DTYPE = np.dtype([("energy", "<f4"), ("numEmitters", "<u4"), ("left", "<
                           ("boxLo", "<f4", 3), ("boxHi", "<f4", 3), ("boxCentroid", "<f4", 3), ("_pad", "<u4")])
 assert VERTEX_DTYPE.itemsize == 32 and TRIANGLE_DTYPE.itemsize == 16 and MATERIAL_DTYPE.itemsize == 44
 assert MESH_DTYPE.itemsize == 12 and LT_NODE_DTYPE.itemsize == 80
+# batched ray queries (fyprt_trace_rays): fyprt_ray (32 B) and the two query kinds
+RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("tmin", "<f4"), ("direction", "<f4", 3), ("tmax", "<f4")])
+assert RAY_DTYPE.itemsize == 32
+QUERY_CLOSEST, QUERY_OCCLUDED = 0, 1
 BVH_NODE_DTYPE = np.dtype([("origin", "<f4", 3), ("ex", "u1", 3), ("meta", "u1"), ("child", "<i4", 4),
                            ("qlo", "u1", (3, 4)), ("qhi", "u1", (3, 4)), ("pad", "<u4", 2)])
 BVH_TRI_DTYPE = np.dtype([("v0", "<f4", 3), ("e1", "<f4", 3), ("e2", "<f4", 3), ("tri", "<u4"), ("pad", "<u4", 2)])
@@ -129,6 +133,7 @@ EXPORTED_SYMBOLS = [
     "fyprt_comm_gather", "fyprt_comm_destroy", "fyprt_render_part", "fyprt_balance_rows", "fyprt_last_frame_ms", "fyprt_halo_plan", "fyprt_comm_ops",
     "fyprt_set_object_vertices", "fyprt_update_transforms", "fyprt_compare_image",
     "fyprt_set_row_stripes", "fyprt_group_set_interleave", "fyprt_comm_set_interleave", "fyprt_selftest_math",
+    "fyprt_trace_rays", "fyprt_trace_rays_device",
 ]
 
 
@@ -181,6 +186,9 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.fyprt_set_object_vertices.argtypes = [vp, vp, u32, C.POINTER(u32)]
     lib.fyprt_update_transforms.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_float), u32]
     lib.fyprt_compare_image.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    if hasattr(lib, "fyprt_trace_rays"):     # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
+        lib.fyprt_trace_rays.argtypes = [vp, C.c_int, vp, u32, vp, C.POINTER(FrameStats)]
+        lib.fyprt_trace_rays_device.argtypes = [vp, C.c_int, vp, u32, vp]
     lib.fyprt_group_create.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(u32), C.POINTER(vp)]
     lib.fyprt_group_destroy.argtypes = [vp]
     lib.fyprt_group_destroy.restype = None
@@ -280,6 +288,7 @@ class Context:
         if rc != 0:
             raise FyprtError(f"fyprt_create({device}) failed: {self.lib.fyprt_last_error(None).decode()}")
         self.h = h
+        self.device = device
         self.width = self.height = 0
         self._keep = None
 
@@ -419,6 +428,53 @@ class Context:
         tris = np.empty(nt.value, dtype=BVH_TRI_DTYPE)
         self._check(self.lib.fyprt_export_bvh(self.h, _ptr(nodes), C.byref(nn), _ptr(tris), C.byref(nt), C.byref(root), C.byref(depth)))
         return {"nodes": nodes, "tris": tris, "root": root.value, "max_stack": depth.value, "stack_budget": self.get_tuning(8), "skip_dead_rays": self.get_tuning(18)}
+
+    def trace_rays(self, origins, directions, tmin=0.0, tmax=np.inf, occluded=False, with_stats=False):
+        """Batched ray query against the uploaded scene (fyprt_trace_rays, blocking).  `origins` / `directions`: (N, 3); `tmin` /
+        `tmax`: scalars or (N,) arrays.  Returns the PAYLOAD_DTYPE records of the closest hits, or (occluded=True) a bool array that
+        is True where any triangle lies in (tmin, tmax); with `with_stats` also the FrameStats of the launch."""
+        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError(f"trace_rays: {len(o)} origins but {len(d)} directions")
+        n = len(o)
+        rays = np.empty(n, dtype=RAY_DTYPE)
+        rays["origin"], rays["direction"] = o, d
+        rays["tmin"] = np.broadcast_to(np.asarray(tmin, dtype=np.float32), (n,))
+        rays["tmax"] = np.broadcast_to(np.asarray(tmax, dtype=np.float32), (n,))
+        out = np.empty(n, dtype=np.uint32 if occluded else PAYLOAD_DTYPE)
+        st = FrameStats()
+        self._check(self.lib.fyprt_trace_rays(self.h, QUERY_OCCLUDED if occluded else QUERY_CLOSEST, _ptr(rays), n, _ptr(out), C.byref(st)))
+        res = out.astype(bool) if occluded else out
+        return (res, st) if with_stats else res
+
+    def trace_rays_tensor(self, rays, occluded=False):
+        """Batched ray query on device tensors (fyprt_trace_rays_device).  `rays`: contiguous float32 (N, 8) tensor on this context's
+        GPU, one fyprt_ray per row (origin, tmin, direction, tmax).  Returns a float32 (N, 10) tensor of RayHitPayload records (column 9
+        holds the int32 bits of objectIndex: `out[:, 9].view(torch.int32)`), or (occluded=True) an int32 (N,) tensor of 0 / 1.
+        Ordered against torch's current stream on the device, without a host synchronisation: the context stream waits for torch's
+        current stream, the query is launched, torch's current stream waits for the context stream.
+        The process must have initialised torch's CUDA before the library was loaded (as bench.py does). Then the library binds to
+        torch's HIP runtime and the context stream is a stream of that runtime. In the other order torch loads a second runtime and
+        finds no GPU.
+        No record_stream: both tensors belong to torch's current stream, and the caching allocator hands their blocks out again only to
+        work on that stream, which is ordered after the query by the last wait.  record_stream would also make the allocator record an
+        event on the context stream when a tensor is freed, and a tensor that outlives the context would then record on a destroyed
+        stream."""
+        import torch
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
+            raise ValueError("trace_rays_tensor: rays must be a contiguous float32 (N, 8) tensor")
+        if rays.device.type != "cuda" or (rays.device.index if rays.device.index is not None else torch.cuda.current_device()) != self.device:
+            raise ValueError(f"trace_rays_tensor: rays must be on cuda:{self.device}, the context's GPU")
+        n = rays.shape[0]
+        out = torch.empty((n,) if occluded else (n, 10), dtype=torch.int32 if occluded else torch.float32, device=rays.device)
+        cur = torch.cuda.current_stream(rays.device)
+        ext = torch.cuda.ExternalStream(self.stream(), device=rays.device)
+        ext.wait_stream(cur)                                           # the rays are written and `out` is allocated before the query runs
+        self._check(self.lib.fyprt_trace_rays_device(self.h, QUERY_OCCLUDED if occluded else QUERY_CLOSEST, C.c_void_p(rays.data_ptr()), n,
+                                                     C.c_void_p(out.data_ptr())))
+        cur.wait_stream(ext)                                           # torch's later work (reads of `out`, reuse of either block) follows it
+        return out
 
     def export_lighttrees(self, mesh_count: int):
         tc, tr, bt = C.c_uint32(), C.c_uint32(), C.c_uint32()

@@ -13,6 +13,7 @@
 #include "rt_lbvh.h"
 #include "rt_refit.h"
 #include "rt_paths.h"
+#include "rt_query.h"
 
 using namespace rt;
 
@@ -98,6 +99,10 @@ struct fyprt_context {
     int gi2Occ = 0; size_t gi2OccLds = 0;       // ... of k_gi2_persistent
     DevBuf<uint32_t> refImage;                 // fyprt_compare_image's reference
     DevBuf<float4> shadowTasks; DevBuf<uint32_t> queueCounters, sortCounts, sortOffset, sortTotal, sortIndex; DevBuf<uint8_t> sortKeys; DevBuf<uint16_t> sortHist;
+    // batched ray queries (fyprt_trace_rays*, rt_query.h), all allocated on the first query: their own counters ([0..4] as a frame's
+    // launch, [5] low word = queue head of the persistent kernel), the host entry's staging buffers, its two timing events
+    DevBuf<unsigned long long> queryCounters; DevBuf<float4> queryRays; DevBuf<uint32_t> queryResults; hipEvent_t queryEv[2] = {};
+    int queryOcc[2] = {0, 0}; size_t queryOccLds[2] = {0, 0};     // cached residency of k_query_rays<kind, false>
 
     int fail(int code, const std::string& m) { err = m; return code; }
     int hip(hipError_t e, const char* what) {
@@ -186,6 +191,8 @@ void fyprt_destroy(fyprt_context* c) {
     for (int k = 0; k < 2; ++k) { c->wfRays[k].release(); c->wfHits[k].release(); }
     c->wfState.release(); c->wfPixels.release(); c->wfPixels2.release(); c->wfCounters.release();
     c->sortCounts.release(); c->sortOffset.release(); c->sortTotal.release(); c->sortIndex.release(); c->sortKeys.release(); c->sortHist.release();
+    c->queryCounters.release(); c->queryRays.release(); c->queryResults.release();
+    for (auto& e : c->queryEv) if (e) (void)hipEventDestroy(e);
     for (auto& row : c->ring) for (auto& e : row) if (e) (void)hipEventDestroy(e);
     for (int k = 0; k < 2; ++k) { if (c->evFront[k]) (void)hipEventDestroy(c->evFront[k]); if (c->evDone[k]) (void)hipEventDestroy(c->evDone[k]); }
     if (c->front) (void)hipStreamDestroy(c->front);
@@ -1258,6 +1265,98 @@ int fyprt_set_ray_counting(fyprt_context* c, int enabled) { if (!c) return FYPRT
 int fyprt_render_part(fyprt_context* c, const fyprt_settings* s, int part) {
     if (!c || !s || (part != 1 && part != 2)) return FYPRT_EINVAL;
     return enqueue_frame(c, s, true, part);
+}
+
+// ---- batched ray queries (rt_query.h).  A query reads the scene only and writes its own results and counters: no frame state moves.
+static int check_query(fyprt_context* c, int query, const void* rays, uint32_t count, const void* results, bool device) {
+    const char* who = device ? "fyprt_trace_rays_device" : "fyprt_trace_rays";
+    if (!c) return FYPRT_EINVAL;
+    if (query != FYPRT_QUERY_CLOSEST && query != FYPRT_QUERY_OCCLUDED) return c->fail(FYPRT_EINVAL, std::string(who) + ": unknown query kind");
+    if (count && (!rays || !results)) return c->fail(FYPRT_EINVAL, std::string(who) + ": NULL rays / results with a non-zero count");
+    if (device && (((uintptr_t)rays & 15u) || ((uintptr_t)results & 7u)))        // the kernels load rays as 16-byte quads, store 8-byte pairs
+        return c->fail(FYPRT_EINVAL, std::string(who) + ": rays must be 16-byte and results 8-byte aligned");
+    if (c->hostOnly) return c->fail(FYPRT_ESTATE, std::string(who) + ": host-only context (device -1) cannot trace");
+    if (!c->haveScene) return c->fail(FYPRT_ESTATE, std::string(who) + " before fyprt_upload_scene");
+    return FYPRT_OK;
+}
+// Enqueues one query launch on the context stream (rays / results: device memory, count > 0); `timed` brackets it with the query events.
+static int enqueue_query(fyprt_context* c, int query, const float4* rays, uint32_t count, void* results, bool timed) {
+    const bool occluded = query == FYPRT_QUERY_OCCLUDED;
+    if (!c->queryCounters.p) { HIPCHK(c, c->queryCounters.alloc(8)); }
+    HIPCHK(c, hipMemsetAsync(c->queryCounters.p, 0, 64, c->stream));
+    DevScene qs = c->dsc;                                         // a copy: the frame's descriptor stays as the last frame left it
+    const int budget = effective_stack_budget(c);
+    qs.stackBudget = budget;
+    qs.nodeQuorum = (uint32_t)c->tuning[6];                       // the path engine's ray kernels' quorum (incoherent rays in general)
+    qs.rayCounter = c->countRays ? c->queryCounters.p : nullptr;
+    qs.topCount = 0u;                                             // the query kernels stage no top nodes (not even in a -DRT_TOPCACHE build)
+    const size_t ldsBytes = (size_t)(budget + 1) * kBlock * sizeof(int32_t);      // the traversal stack of the path engine's ray kernels
+    QueryRays q{};
+    q.rays = rays; q.results = results; q.count = count; q.head = reinterpret_cast<uint32_t*>(c->queryCounters.p + 5);
+    q.chunk = (uint32_t)(c->tuning[4] > 0 ? c->tuning[4] : 128); q.refillLanes = (uint32_t)(c->tuning[5] > 0 ? c->tuning[5] : 24);
+    q.staticChunks = (uint32_t)(c->tuning[9] > 0 ? c->tuning[9] : 2); q.minChunk = (uint32_t)(c->tuning[10] > 0 ? c->tuning[10] : q.chunk);
+    const dim3 block(kBlock);
+    const uint32_t blocksForRays = (uint32_t)(((size_t)count + kBlock - 1) / kBlock);
+    // tuning key 15 as in the path engine: one thread per ray below 65 536 triangles, persistent waves above
+    const bool simple = c->tuning[15] == 2 || (c->tuning[15] == 0 && c->hostBvh.tris.size() < 65536u);
+    dim3 grid;
+    if (simple) grid = dim3(std::max(1u, std::min<uint32_t>((uint32_t)c->numCUs * 16u, blocksForRays)));
+    else {
+        if (c->queryOccLds[occluded] != ldsBytes) {
+            int n = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, occluded ? k_query_rays<true, false> : k_query_rays<false, false>, kBlock, ldsBytes) != hipSuccess || n <= 0) n = 4;
+            c->queryOcc[occluded] = n; c->queryOccLds[occluded] = ldsBytes;
+        }
+        const int perCU = c->tuning[2] > 0 ? c->tuning[2] : c->queryOcc[occluded];
+        grid = dim3(std::max(1u, std::min<uint32_t>((uint32_t)(c->numCUs * perCU), blocksForRays)));   // no more workgroups than the rays fill
+    }
+    if (timed) HIPCHK(c, hipEventRecord(c->queryEv[0], c->stream));
+    const int k = (occluded ? 2 : 0) + (c->countRays ? 1 : 0);
+    if (simple) {
+        static void (*const kSimple[4])(DevScene, QueryRays) = {k_query_rays_simple<false, false>, k_query_rays_simple<false, true>, k_query_rays_simple<true, false>, k_query_rays_simple<true, true>};
+        hipLaunchKernelGGL(kSimple[k], grid, block, ldsBytes, c->stream, qs, q);
+    } else {
+        static void (*const kPersistent[4])(DevScene, QueryRays) = {k_query_rays<false, false>, k_query_rays<false, true>, k_query_rays<true, false>, k_query_rays<true, true>};
+        hipLaunchKernelGGL(kPersistent[k], grid, block, ldsBytes, c->stream, qs, q);
+    }
+    HIPCHK(c, hipGetLastError());
+    if (timed) HIPCHK(c, hipEventRecord(c->queryEv[1], c->stream));
+    return FYPRT_OK;
+}
+
+int fyprt_trace_rays(fyprt_context* c, int query, const fyprt_ray* rays, uint32_t count, void* results, fyprt_frame_stats* stats) {
+    { const int rc = check_query(c, query, rays, count, results, false); if (rc != FYPRT_OK) return rc; }
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (count == 0) return FYPRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t rayBytes = (size_t)count * sizeof(fyprt_ray), resultBytes = (size_t)count * (query == FYPRT_QUERY_OCCLUDED ? 4u : 40u);
+    if (!c->queryEv[0]) { HIPCHK(c, hipEventCreate(&c->queryEv[0])); HIPCHK(c, hipEventCreate(&c->queryEv[1])); }
+    if (c->queryRays.n < (size_t)count * 2) { HIPCHK(c, c->queryRays.alloc((size_t)count * 2)); }        // staging grows, is kept
+    if (c->queryResults.bytes() < resultBytes) { HIPCHK(c, c->queryResults.alloc(resultBytes / 4)); }
+    HIPCHK(c, hipMemcpyAsync(c->queryRays.p, rays, rayBytes, hipMemcpyHostToDevice, c->stream));
+    { const int rc = enqueue_query(c, query, c->queryRays.p, count, c->queryResults.p, true); if (rc != FYPRT_OK) return rc; }
+    HIPCHK(c, hipMemcpyAsync(results, c->queryResults.p, resultBytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (stats) {
+        float ms = 0.0f;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->queryEv[0], c->queryEv[1]));
+        stats->kernel_ms = ms; stats->kernel_ms_part[0] = ms; stats->launches = 1;
+        if (c->countRays) {
+            unsigned long long r[5] = {0, 0, 0, 0, 0};
+            HIPCHK(c, hipMemcpy(r, c->queryCounters.p, sizeof r, hipMemcpyDeviceToHost));
+            stats->rays = stats->part_rays[0] = r[0]; stats->box_tests = stats->part_box_tests[0] = r[1];
+            stats->tri_tests = stats->part_tri_tests[0] = r[2]; stats->hits = stats->part_hits[0] = r[3];
+            stats->node_visits = stats->part_node_visits[0] = r[4];
+        }
+    }
+    return FYPRT_OK;
+}
+
+int fyprt_trace_rays_device(fyprt_context* c, int query, const void* rays, uint32_t count, void* results) {
+    { const int rc = check_query(c, query, rays, count, results, true); if (rc != FYPRT_OK) return rc; }
+    if (count == 0) return FYPRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    return enqueue_query(c, query, static_cast<const float4*>(rays), count, results, false);
 }
 
 #include "fyprt_multi.h"

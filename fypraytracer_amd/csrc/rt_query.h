@@ -1,0 +1,205 @@
+// Batched ray queries (fyprt_trace_rays / fyprt_trace_rays_device): the caller's rays traced against the uploaded scene, outside any frame.
+//
+//   ray record : 2 x float4 (32 B, 16-byte aligned) = origin | tmin, direction | tmax
+//   CLOSEST    : one 40-byte Payload per ray (make_hit / make_miss, the record a frame's primary kernel writes)
+//   OCCLUDED   : one uint32 per ray, 1 iff any triangle is accepted; traversal stops at the first one
+// A triangle is accepted at t when tri_test passes (the reference's Möller–Trumbore with its own t > 1e-4), t > tmin and t < tmax.
+// The closest-hit query starts from best = min(tmax, FLT_MAX) and culls boxes against best * 1.000001f: with tmin <= 1e-4 and
+// tmax = +inf that is trace_closest step for step, so the record equals the primary kernel's bit for bit (exact-t ties go to the first
+// triangle found, as there).  The occlusion query culls against tmax * 1.000001f; its answer does not depend on the visiting order.
+// A ray with a non-finite origin / direction component, a NaN bound or !(tmin < tmax) is answered as a miss (0) without traversal
+// and counted as a ray with no tests.
+//
+// Two kernels, chosen by the host like the path engine's ray kernels (tuning key 15):
+//   k_query_rays         persistent waves, one in-flight ray per lane, idle lanes refilled from the wave's claimed chunk (the
+//                        guided self-scheduling of trace_rays_body, tuning keys 4, 5, 9, 10); a refill is two 16-byte loads and
+//                        three reciprocals, a finished closest-hit ray one triShade gather (make_hit) and a 40-byte store.
+//   k_query_rays_simple  one thread per ray, for small trees where rays are too cheap for the refill machinery to pay.
+// The query kind is a template parameter: neither kernel carries the other kind's branches.  They only call the traversal core of
+// rt_device.h (node_step, tri_test, make_hit / make_miss, quorum_of, ray_not_finite); no frame kernel is touched.
+#pragma once
+#include "rt_wavefront.h"
+
+namespace rt {
+
+struct QueryRays {
+    const float4* rays; void* results; uint32_t count; uint32_t* head;
+    uint32_t chunk, refillLanes, staticChunks, minChunk;
+};
+
+RT_DEV bool query_invalid(f3 o, f3 d, float tmin, float tmax) { return ray_not_finite(o, d) || !(tmin < tmax); }   // (a NaN bound fails the compare)
+RT_DEV float query_start(float tmax) { return tmax < 3.402823466e+38f ? tmax : 3.402823466e+38f; }                   // min(tmax, FLT_MAX), tmax not NaN
+
+// 40 bytes as five 8-byte stores: the results array is only required to be 8-byte aligned
+RT_DEV void store_payload(Payload* dst, const Payload& p) {
+    float2* q = reinterpret_cast<float2*>(dst);
+    q[0] = make_float2(p.hitDistance, p.px); q[1] = make_float2(p.py, p.pz); q[2] = make_float2(p.nx, p.ny);
+    q[3] = make_float2(p.nz, p.u); q[4] = make_float2(p.v, __int_as_float(p.objectIndex));
+}
+
+template <bool OCCLUDED>
+RT_DEV void store_query_result(const DevScene& sc, const QueryRays& q, uint32_t i, f3 o, f3 d, float best, float hu, float hv, int32_t hitTri) {
+    if (OCCLUDED) { static_cast<uint32_t*>(q.results)[i] = hitTri >= 0 ? 1u : 0u; return; }
+    Hit h; h.t = best; h.u = hu; h.v = hv; h.tri = hitTri;
+    store_payload(static_cast<Payload*>(q.results) + i, hitTri < 0 ? make_miss() : make_hit(sc, o, d, h));
+}
+
+template <bool COUNT>
+RT_DEV void count_query_ray(const DevScene& sc, uint32_t nBox, uint32_t nTri, uint32_t nNode, bool hit) {
+    if (!COUNT) return;
+    atomicAdd(sc.rayCounter + 0, 1ull); atomicAdd(sc.rayCounter + 1, (unsigned long long)nBox);
+    atomicAdd(sc.rayCounter + 2, (unsigned long long)nTri); atomicAdd(sc.rayCounter + 3, hit ? 1ull : 0ull);
+    atomicAdd(sc.rayCounter + 4, (unsigned long long)nNode);
+}
+
+template <bool OCCLUDED, bool COUNT>
+RT_DEV void query_rays_body(const DevScene& sc, const QueryRays& q, int32_t* s_stack) {
+    int32_t* lds = s_stack + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t total = q.count;
+    // work distribution of trace_rays_body: static chunks per wave, then guided claims from the shared head
+    const uint32_t nWaves = gridDim.x * (uint32_t)(kBlock / 64), myWave = blockIdx.x * (uint32_t)(kBlock / 64) + (threadIdx.x >> 6);
+    const uint32_t share = (total + nWaves - 1u) / nWaves;
+    const uint32_t chunk = q.chunk, want1 = chunk * q.staticChunks;
+    const uint32_t first = share < want1 ? (share < 16u ? 16u : share) : want1;
+    const uint32_t dynBase = nWaves * first;
+    const bool hasDyn = dynBase < total;
+    // (the origin lives in pk only: a separate copy of it costs three registers across the loop, and the closest-hit kernel spills)
+    f3 d = splat3(0.0f); RayPk pk = make_raypk(d, 1.0f, 1.0f, 1.0f);
+    float tmin = 0.0f, best = 0.0f, cut = 0.0f, hu = 0.0f, hv = 0.0f; uint32_t task = 0; int32_t cur = kExit, hitTri = -1; int top = 0;
+    uint32_t nBox = 0, nTri = 0, nNode = 0;
+    bool active = false;
+    bool more = total != 0u;
+    uint32_t chunkNext = myWave * first < total ? myWave * first : total;
+    uint32_t chunkEnd = (myWave + 1u) * first < total ? (myWave + 1u) * first : total;
+    while (true) {
+        const unsigned long long idle = __ballot(!active);
+        if (more && (uint32_t)__popcll(idle) >= q.refillLanes) {
+            if (chunkNext >= chunkEnd && hasDyn) {
+                uint32_t base = 0;
+                uint32_t size = (total - chunkEnd) / nWaves;
+                size = size < q.minChunk ? q.minChunk : (size > chunk ? chunk : size);
+                if (lane == 0u) base = dynBase + atomicAdd(q.head, size);
+                base = (uint32_t)__shfl((int)base, 0);
+                chunkNext = base < total ? base : total;
+                chunkEnd = (base + size < total) ? base + size : total;
+            }
+            const uint32_t slot = chunkNext + (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
+            const uint32_t want = (uint32_t)__popcll(idle), avail = chunkEnd - chunkNext;
+            chunkNext += (want < avail) ? want : avail;
+            more = chunkNext < chunkEnd || (hasDyn && chunkEnd < total);
+            if (!active && slot < chunkEnd) {
+                task = slot;
+                const float4 r0 = q.rays[(size_t)task * 2], r1 = q.rays[(size_t)task * 2 + 1];
+                const f3 o = mk3(r0.x, r0.y, r0.z); d = mk3(r1.x, r1.y, r1.z); tmin = r0.w;
+                pk = make_raypk(o, safe_inv(d.x), safe_inv(d.y), safe_inv(d.z));
+                best = OCCLUDED ? r1.w : query_start(r1.w);
+                cut = best * 1.000001f;
+                hitTri = -1; hu = 0.0f; hv = 0.0f;
+                if (COUNT) { nBox = 0; nTri = 0; nNode = 0; }
+                top = 0; lane_push(lds, top, kExit);
+                cur = (sc.triCount == 0 || query_invalid(o, d, tmin, r1.w)) ? kExit : sc.rootRef;
+                active = true;
+            }
+        }
+        if (__ballot(active) == 0ull) { if (!more) break; else continue; }
+        while (true) {
+            bool walk = active && cur >= 0;
+            const uint32_t quorum = quorum_of(sc.nodeQuorum, (uint32_t)__popcll(__ballot(active)));
+            while (walk) {
+                { Stack st; st.lds = lds; st.top = top; cur = node_step<COUNT>(sc.nodes, sc.stackBudget, cur, pk, cut, st, nBox, nNode); top = st.top; }
+                walk = cur >= 0;
+                if ((uint32_t)__popcll(__ballot(walk)) < quorum) break;
+            }
+            if (active && cur < 0 && cur != kExit) {
+                const uint32_t code = (uint32_t)~cur, firstTri = code >> 2, cnt = (code & 3u) + 1u;
+                bool done = false;
+                for (uint32_t k = 0; k < cnt; ++k) {
+                    float t, u, v; uint32_t id;
+                    if (COUNT) nTri += 1;
+                    if (!tri_test(sc.leafTris + (size_t)(firstTri + k) * 3, mk3(pk.ox, pk.oy, pk.oz), d, t, u, v, id) || !(t > tmin) || !(t < best)) continue;
+                    hitTri = (int32_t)id;
+                    if (OCCLUDED) { done = true; break; }
+                    best = t; cut = t * 1.000001f; hu = u; hv = v;
+                }
+                cur = done ? kExit : lane_pop(lds, top);
+            }
+            if (active && cur == kExit) {
+                store_query_result<OCCLUDED>(sc, q, task, mk3(pk.ox, pk.oy, pk.oz), d, best, hu, hv, hitTri);
+                count_query_ray<COUNT>(sc, nBox, nTri, nNode, hitTri >= 0);
+                active = false;
+            }
+            const unsigned long long act = __ballot(active);
+            if (act == 0ull) break;
+            if (more && (64u - (uint32_t)__popcll(act)) >= q.refillLanes) break;
+        }
+    }
+}
+
+template <bool OCCLUDED, bool COUNT> __global__ void k_query_rays(DevScene sc, QueryRays q);
+template <> __global__ __launch_bounds__(kBlock) RT_TRACE_WAVES void k_query_rays<false, false>(DevScene sc, QueryRays q) {
+    extern __shared__ int32_t s_stack[];                         // (stackBudget + 1) entries x kBlock threads, sized at launch
+    query_rays_body<false, false>(sc, q, s_stack);
+}
+template <> __global__ __launch_bounds__(kBlock) RT_TRACE_WAVES void k_query_rays<true, false>(DevScene sc, QueryRays q) {
+    extern __shared__ int32_t s_stack[];
+    query_rays_body<true, false>(sc, q, s_stack);
+}
+template <> __global__ __launch_bounds__(kBlock) void k_query_rays<false, true>(DevScene sc, QueryRays q) {   // instrumented: no register cap
+    extern __shared__ int32_t s_stack[];
+    query_rays_body<false, true>(sc, q, s_stack);
+}
+template <> __global__ __launch_bounds__(kBlock) void k_query_rays<true, true>(DevScene sc, QueryRays q) {
+    extern __shared__ int32_t s_stack[];
+    query_rays_body<true, true>(sc, q, s_stack);
+}
+
+// One thread per ray: the interval form of trace_closest (or its any-hit variant), same traversal core.
+template <bool OCCLUDED, bool COUNT>
+RT_DEV void query_one(const DevScene& sc, const QueryRays& q, uint32_t i, int32_t* ldsBase) {
+    const float4 r0 = q.rays[(size_t)i * 2], r1 = q.rays[(size_t)i * 2 + 1];
+    const f3 o = mk3(r0.x, r0.y, r0.z), d = mk3(r1.x, r1.y, r1.z);
+    const float tmin = r0.w;
+    float best = OCCLUDED ? r1.w : query_start(r1.w), cut = best * 1.000001f, hu = 0.0f, hv = 0.0f;
+    int32_t hitTri = -1;
+    uint32_t nBox = 0, nTri = 0, nNode = 0;
+    if (!(sc.triCount == 0 || query_invalid(o, d, tmin, r1.w))) {
+        const RayPk pk = make_raypk(o, safe_inv(d.x), safe_inv(d.y), safe_inv(d.z));
+        Stack st; st.lds = ldsBase; st.top = 0; st.push(kExit);
+        int32_t cur = sc.rootRef;
+        bool done = false;
+        while (!done) {
+            bool walk = cur >= 0;
+            const uint32_t quorum = quorum_of(sc.nodeQuorum, (uint32_t)__popcll(__ballot(true)));
+            while (walk) {
+                cur = node_step<COUNT>(sc.nodes, sc.stackBudget, cur, pk, cut, st, nBox, nNode);
+                walk = cur >= 0;
+                if ((uint32_t)__popcll(__ballot(walk)) < quorum) break;
+            }
+            if (cur >= 0) continue;
+            if (cur == kExit) break;
+            const uint32_t code = (uint32_t)~cur, firstTri = code >> 2, cnt = (code & 3u) + 1u;
+            for (uint32_t k = 0; k < cnt; ++k) {
+                float t, u, v; uint32_t id;
+                if (COUNT) nTri += 1;
+                if (!tri_test(sc.leafTris + (size_t)(firstTri + k) * 3, o, d, t, u, v, id) || !(t > tmin) || !(t < best)) continue;
+                hitTri = (int32_t)id;
+                if (OCCLUDED) { done = true; break; }
+                best = t; cut = t * 1.000001f; hu = u; hv = v;
+            }
+            cur = st.pop();
+        }
+    }
+    store_query_result<OCCLUDED>(sc, q, i, o, d, best, hu, hv, hitTri);
+    count_query_ray<COUNT>(sc, nBox, nTri, nNode, hitTri >= 0);
+}
+template <bool OCCLUDED, bool COUNT>
+__global__ __launch_bounds__(kBlock) void k_query_rays_simple(DevScene sc, QueryRays q) {
+    extern __shared__ int32_t s_stack[];                         // (stackBudget + 1) entries x kBlock threads, sized at launch
+    for (uint32_t base = blockIdx.x * (uint32_t)kBlock; base < q.count; base += gridDim.x * (uint32_t)kBlock) {   // (block-uniform trips: node_step's ballots see whole waves)
+        const uint32_t j = base + threadIdx.x;
+        if (j < q.count) query_one<OCCLUDED, COUNT>(sc, q, j, s_stack + threadIdx.x);
+    }
+}
+
+}  // namespace rt

@@ -329,6 +329,33 @@ int fyprt_compare_image(fyprt_context* ctx, const uint32_t* reference_rgba8, int
  * in the order sqrt, reciprocal, reciprocal square root; all zero on a sound build.  New (no reference counterpart). */
 int fyprt_selftest_math(fyprt_context* ctx, uint64_t* mismatches3, uint32_t* first_bad3 /* may be NULL */);
 
+/* ================================================================================================= batched ray queries
+ * New (no reference counterpart): the caller's rays traced against the uploaded scene by the frames' traversal core, outside any frame —
+ * picking (the mesh under a viewport pixel), visibility probes, bakes, and timing traversal on a fixed ray set ("Batched ray queries").
+ * Acceptance: a triangle is accepted at distance t when the reference's Möller–Trumbore passes (including its own t > 1e-4), t > tmin
+ * and t < tmax.  Directions need not be normalised; t is in units of the direction.
+ *   FYPRT_QUERY_CLOSEST : one RayHitPayload (40 B, the FYPRT_BUF_PAYLOAD record) per ray — the nearest accepted triangle (exact-t ties:
+ *                         the first one found in traversal order, as in the frame kernels), or hitDistance -1 / objectIndex -1.  With
+ *                         tmin <= 1e-4 and tmax = +inf the record is bit-identical to the one a frame's primary kernel writes for the ray.
+ *   FYPRT_QUERY_OCCLUDED: one uint32 per ray, 1 if any triangle is accepted, else 0 (traversal stops at the first one).
+ * A ray with a non-finite origin / direction component, a NaN tmin / tmax or tmin >= tmax is answered as a miss (0) without traversal.
+ * Errors: FYPRT_EINVAL for a NULL context, an unknown query kind, NULL rays / results with count > 0 (and, device entry, rays not
+ * 16-byte or results not 8-byte aligned); FYPRT_ESTATE on a host-only context or before fyprt_upload_scene; count 0 returns FYPRT_OK
+ * and launches nothing.
+ * A query changes no frame state (frame index, accumulation, reservoirs, payload / image buffers, frame timings and counters): it has
+ * its own counters and queue head, and the host entry's staging buffers are allocated on the first query and kept.  Queries run on the
+ * context stream, after the geometry of the preceding upload / vertex / transform update.  The kernel (persistent waves with lane
+ * refill, or one thread per ray on trees below 65 536 triangles) follows tuning key 15 as the path engine's ray kernels do. */
+typedef struct fyprt_ray { float origin[3]; float tmin; float direction[3]; float tmax; } fyprt_ray;   /* 32 B, 16-B aligned on the device */
+enum fyprt_query { FYPRT_QUERY_CLOSEST = 0, FYPRT_QUERY_OCCLUDED = 1 };
+/* Host memory, blocking.  `results`: count x 40 B (closest) or count x uint32 (occluded).  `stats` may be NULL: kernel_ms = the hipEvent
+ * time of the query launch, launches = 1; with ray counting on (fyprt_set_ray_counting) rays / box_tests / tri_tests / hits /
+ * node_visits as a frame counts them, part_*[0] = the totals. */
+int fyprt_trace_rays(fyprt_context* ctx, int query /* enum fyprt_query */, const fyprt_ray* rays, uint32_t count, void* results,
+                     fyprt_frame_stats* stats);
+/* Device memory of the context's GPU (rays: count x fyprt_ray; results as above), asynchronous on the context stream (fyprt_stream). */
+int fyprt_trace_rays_device(fyprt_context* ctx, int query /* enum fyprt_query */, const void* rays, uint32_t count, void* results);
+
 /* ================================================================================================= multi-GPU
  * The reference renders on one GPU (Renderer.cu:13-284); there is no reference interface for this section.  It splits ONE
  * Renderer::Render call over several GPUs by image rows: every GPU holds the whole scene and renders a band;

@@ -1,0 +1,146 @@
+#!/usr/bin/env python3
+"""Rate of the batched ray queries (fyprt_trace_rays) on fixed ray sets of the bench hall (1M triangles, 1920x1080), GPU.
+  (a) camera rays, row-major, closest hit                 (b) cosine-hemisphere bounce rays from the camera hits, closest hit
+  (c) shadow segments from each hit to a seeded random point on a random emissive triangle, tmax = 0.999 x distance, occlusion
+  (d) set (a) on hall_small (11 k triangles: the one-thread-per-ray side of tuning key 15)
+One JSON line per set: rays, median hipEvent ms of the query launch over --calls calls after warm-up, Mrays/s, node visits per ray
+(one counted call).  The same run times ReSTIR DI Part 1 stand-alone (fyprt_render_part(..., 1)), which traces the camera rays of (a)
+and does its reservoir work on top.
+  usage: python tools/query_rate.py [--calls 20] [--out FILE.jsonl]"""
+import argparse
+import json
+import statistics
+import sys
+from pathlib import Path
+
+import numpy as np
+import torch  # noqa: E402  (torch's HIP runtime is initialised before the library's, as bench.py does: Part 1 is timed with torch events)
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tests"))
+from common import settings_for  # noqa: E402
+from fypraytracer_amd import capi, scenes  # noqa: E402
+
+F32 = np.float32
+
+
+def rate(ctx, name, scene, o, d, calls, tmin=0.0, tmax=np.inf, occluded=False):
+    for _ in range(3):
+        ctx.trace_rays(o, d, tmin, tmax, occluded=occluded)
+    ms = [ctx.trace_rays(o, d, tmin, tmax, occluded=occluded, with_stats=True)[1].kernel_ms for _ in range(calls)]
+    ctx.set_ray_counting(True)
+    res, st = ctx.trace_rays(o, d, tmin, tmax, occluded=occluded, with_stats=True)
+    ctx.set_ray_counting(False)
+    med = statistics.median(ms)
+    hits = int(res.sum()) if occluded else int((res["objectIndex"] >= 0).sum())
+    return {"set": name, "scene": scene, "query": "occluded" if occluded else "closest", "rays": len(o), "ms_median": round(med, 4),
+            "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4), "calls": calls, "mrays_per_s": round(len(o) / med / 1e3, 1),
+            "node_visits_per_ray": round(st.node_visits / st.rays, 3), "box_tests_per_ray": round(st.box_tests / st.rays, 3),
+            "tri_tests_per_ray": round(st.tri_tests / st.rays, 3), "hit_fraction": round(hits / len(o), 4)}, res
+
+
+def part1_ms(ctx, calls):
+    """ReSTIR DI Part 1 alone (fyprt_render_part(..., 1) runs on the context stream): device-event time of its launches."""
+    st = settings_for(capi.RESTIR_DI)
+    stream = torch.cuda.ExternalStream(ctx.stream())
+    ms = []
+    for f in range(calls + 3):
+        st.rand_seed = f + 1
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        ctx.render_part(st, 1)
+        e1.record(stream)
+        ctx.synchronize()
+        if f >= 3:
+            ms.append(e0.elapsed_time(e1))
+        ctx.render_part(st, 2)
+        ctx.synchronize()
+    return statistics.median(ms), min(ms), max(ms)
+
+
+def query_ms_torch_events(ctx, o, d, calls):
+    """The camera query of (a) timed like Part 1 (torch events on the context stream around fyprt_trace_rays_device): checks that this
+    way of timing agrees with the library's own hipEvents (kernel_ms of the host entry)."""
+    rays = torch.from_numpy(np.concatenate([o, np.zeros((len(o), 1), F32), d, np.full((len(o), 1), np.inf, F32)], 1)).cuda()
+    out = torch.empty((len(o), 10), dtype=torch.float32, device="cuda")
+    stream = torch.cuda.ExternalStream(ctx.stream())
+    torch.cuda.synchronize()
+    ms = []
+    for f in range(calls + 3):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        ctx._check(ctx.lib.fyprt_trace_rays_device(ctx.h, capi.QUERY_CLOSEST, rays.data_ptr(), len(o), out.data_ptr()))
+        e1.record(stream)
+        ctx.synchronize()
+        if f >= 3:
+            ms.append(e0.elapsed_time(e1))
+    return statistics.median(ms)
+
+
+def camera_rays(cam):
+    d = cam.ray_directions().reshape(-1, 3).astype(F32)           # row-major, row 0 first (the frame's pixel order)
+    o = np.broadcast_to(np.asarray(cam.position, F32), d.shape).copy()
+    return o, d
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("query_rate.py needs an MI355X")
+    torch.cuda.set_device(0)
+    W, H = 1920, 1080
+    rows = []
+    rng = np.random.default_rng(2024)
+    hall, cam = scenes.hall_scene(), scenes.hall_camera(W, H)
+    ctx = capi.Context(0)
+    ctx.resize(W, H)
+    ctx.upload_scene(hall)
+    ctx.set_camera(cam)
+    o, d = camera_rays(cam)
+    ra, res = rate(ctx, "a_camera", "hall_1M", o, d, a.calls)
+    rows.append(ra)
+    hit = res["objectIndex"] >= 0
+    p = res["worldPosition"][hit].astype(F32)
+    n = res["worldNormal"][hit].astype(F32)
+    n = np.where((np.einsum("ij,ij->i", n, d[hit]) > 0)[:, None], -n, n).astype(F32)   # facing the camera ray
+    # (b) cosine-weighted hemisphere about the shading normal
+    u1, u2 = rng.random(len(p)), rng.random(len(p))
+    r, phi = np.sqrt(u1), 2 * np.pi * u2
+    t = np.cross(n, np.where(np.abs(n[:, :1]) > 0.9, [[0.0, 1.0, 0.0]], [[1.0, 0.0, 0.0]]))
+    t /= np.linalg.norm(t, axis=1, keepdims=True)
+    b = np.cross(n, t)
+    bd = (t * (r * np.cos(phi))[:, None] + b * (r * np.sin(phi))[:, None] + n * np.sqrt(1 - u1)[:, None]).astype(F32)
+    rows.append(rate(ctx, "b_bounce", "hall_1M", p, bd, a.calls)[0])
+    # (c) shadow segments to a random point of a random emissive triangle
+    em = hall.init_scene_emissive_triangles()
+    pos = hall.world_vertices["position"]
+    tri = hall.triangles[em[rng.integers(0, len(em), len(p))]]
+    r1, r2 = rng.random(len(p)), rng.random(len(p))
+    s = np.sqrt(r1)
+    q = (1 - s)[:, None] * pos[tri["v0"]] + ((1 - r2) * s)[:, None] * pos[tri["v1"]] + (r2 * s)[:, None] * pos[tri["v2"]]
+    v = q - p
+    dist = np.linalg.norm(v, axis=1)
+    rows.append(rate(ctx, "c_shadow", "hall_1M", p, (v / dist[:, None]).astype(F32), a.calls, tmax=(0.999 * dist).astype(F32), occluded=True)[0])
+    p1 = part1_ms(ctx, a.calls)
+    rows.append({"set": "restir_di_part1", "scene": "hall_1M", "rays": W * H, "ms_median": round(p1[0], 4), "ms_min": round(p1[1], 4),
+                 "ms_max": round(p1[2], 4), "calls": a.calls, "camera_query_over_part1": round(ra["ms_median"] / p1[0], 3),
+                 "timing": "torch events on the context stream", "camera_query_ms_same_timing": round(query_ms_torch_events(ctx, o, d, a.calls), 4)})
+    ctx.close()
+    # (d) the camera rays of (a) on hall_small (one thread per ray under the default tuning key 15)
+    small = capi.Context(0)
+    small.upload_scene(scenes.hall_scene_small())
+    rows.append(rate(small, "d_camera_small", "hall_small", o, d, a.calls)[0])
+    small.close()
+    lines = [json.dumps(r) for r in rows]
+    print("\n".join(lines))
+    if a.out:
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
