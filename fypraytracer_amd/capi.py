@@ -50,6 +50,7 @@ assert MESH_DTYPE.itemsize == 12 and LT_NODE_DTYPE.itemsize == 80
 RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("tmin", "<f4"), ("direction", "<f4", 3), ("tmax", "<f4")])
 assert RAY_DTYPE.itemsize == 32
 QUERY_CLOSEST, QUERY_OCCLUDED = 0, 1
+RENDER_RAYS_CHUNK = 1 << 21      # FYPRT_RENDER_RAYS_CHUNK: rays per internal pass of fyprt_render_rays*
 BVH_NODE_DTYPE = np.dtype([("origin", "<f4", 3), ("ex", "u1", 3), ("meta", "u1"), ("child", "<i4", 4),
                            ("qlo", "u1", (3, 4)), ("qhi", "u1", (3, 4)), ("pad", "<u4", 2)])
 BVH_TRI_DTYPE = np.dtype([("v0", "<f4", 3), ("e1", "<f4", 3), ("e2", "<f4", 3), ("tri", "<u4"), ("pad", "<u4", 2)])
@@ -134,6 +135,7 @@ EXPORTED_SYMBOLS = [
     "fyprt_set_object_vertices", "fyprt_update_transforms", "fyprt_compare_image",
     "fyprt_set_row_stripes", "fyprt_group_set_interleave", "fyprt_comm_set_interleave", "fyprt_selftest_math",
     "fyprt_trace_rays", "fyprt_trace_rays_device",
+    "fyprt_render_rays", "fyprt_render_rays_device",
 ]
 
 
@@ -189,6 +191,9 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     if hasattr(lib, "fyprt_trace_rays"):     # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
         lib.fyprt_trace_rays.argtypes = [vp, C.c_int, vp, u32, vp, C.POINTER(FrameStats)]
         lib.fyprt_trace_rays_device.argtypes = [vp, C.c_int, vp, u32, vp]
+    if hasattr(lib, "fyprt_render_rays"):    # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
+        lib.fyprt_render_rays.argtypes = [vp, C.POINTER(Settings), u32, vp, vp, u32, u32, vp, vp, C.POINTER(FrameStats)]
+        lib.fyprt_render_rays_device.argtypes = [vp, C.POINTER(Settings), u32, vp, vp, u32, u32, vp, vp]
     lib.fyprt_group_create.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(u32), C.POINTER(vp)]
     lib.fyprt_group_destroy.argtypes = [vp]
     lib.fyprt_group_destroy.restype = None
@@ -475,6 +480,63 @@ class Context:
                                                      C.c_void_p(out.data_ptr())))
         cur.wait_stream(ext)                                           # torch's later work (reads of `out`, reuse of either block) follows it
         return out
+
+    def render_rays(self, origins, directions, settings: Settings, frame_index=1, first_index=0, pixel_indices=None, tmin=0.0, tmax=np.inf,
+                    want_payload=False, with_stats=False):
+        """Radiance query (fyprt_render_rays, blocking): the sample of technique `settings.technique` (0-6) for the caller's rays.
+        `origins` / `directions`: (N, 3), unit directions; `tmin` / `tmax`: scalars or (N,) arrays, the primary segment's interval.
+        Ray k uses the random sequence of pixel `pixel_indices[k]` (or `first_index + k`) in frame `frame_index`.  Returns float32
+        (N, 4): what a frame's epilogue would add to the accumulation; with `want_payload` also the PAYLOAD_DTYPE primary records, with
+        `with_stats` also the FrameStats of the call."""
+        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError(f"render_rays: {len(o)} origins but {len(d)} directions")
+        n = len(o)
+        idx = None
+        if pixel_indices is not None:
+            idx = np.ascontiguousarray(np.asarray(pixel_indices).astype(np.uint32, copy=False).reshape(-1))
+            if len(idx) != n:
+                raise ValueError(f"render_rays: {n} rays but {len(idx)} pixel indices")
+        rays = np.empty(n, dtype=RAY_DTYPE)
+        rays["origin"], rays["direction"] = o, d
+        rays["tmin"] = np.broadcast_to(np.asarray(tmin, dtype=np.float32), (n,))
+        rays["tmax"] = np.broadcast_to(np.asarray(tmax, dtype=np.float32), (n,))
+        rad = np.empty((n, 4), dtype=np.float32)
+        pay = np.empty(n, dtype=PAYLOAD_DTYPE) if want_payload else None
+        st = FrameStats()
+        self._check(self.lib.fyprt_render_rays(self.h, C.byref(settings), int(frame_index), _ptr(rays), _ptr(idx), int(first_index), n,
+                                               _ptr(rad), _ptr(pay), C.byref(st)))
+        out = (rad,) + ((pay,) if want_payload else ()) + ((st,) if with_stats else ())
+        return out[0] if len(out) == 1 else out
+
+    def render_rays_tensor(self, rays, settings: Settings, frame_index=1, first_index=0, pixel_indices=None, want_payload=False):
+        """Radiance query on device tensors (fyprt_render_rays_device).  `rays`: contiguous float32 (N, 8) tensor on this context's GPU,
+        one fyprt_ray per row; `pixel_indices`: None or a contiguous int32 (N,) tensor on the same GPU.  Returns a float32 (N, 4) tensor of
+        radiance, and with `want_payload` also a float32 (N, 10) tensor of primary records (as trace_rays_tensor).  Ordered against
+        torch's current stream as trace_rays_tensor is, without a host synchronisation and without record_stream."""
+        import torch
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
+            raise ValueError("render_rays_tensor: rays must be a contiguous float32 (N, 8) tensor")
+        if rays.device.type != "cuda" or (rays.device.index if rays.device.index is not None else torch.cuda.current_device()) != self.device:
+            raise ValueError(f"render_rays_tensor: rays must be on cuda:{self.device}, the context's GPU")
+        n = rays.shape[0]
+        if pixel_indices is not None:
+            if pixel_indices.dtype != torch.int32 or pixel_indices.dim() != 1 or pixel_indices.shape[0] != n or not pixel_indices.is_contiguous():
+                raise ValueError("render_rays_tensor: pixel_indices must be a contiguous int32 (N,) tensor, one per ray")
+            if pixel_indices.device != rays.device:
+                raise ValueError("render_rays_tensor: pixel_indices must be on the rays' GPU")
+        rad = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
+        pay = torch.empty((n, 10), dtype=torch.float32, device=rays.device) if want_payload else None
+        cur = torch.cuda.current_stream(rays.device)
+        ext = torch.cuda.ExternalStream(self.stream(), device=rays.device)
+        ext.wait_stream(cur)                                           # inputs written, outputs allocated before the query runs
+        self._check(self.lib.fyprt_render_rays_device(self.h, C.byref(settings), int(frame_index), C.c_void_p(rays.data_ptr()),
+                                                      C.c_void_p(pixel_indices.data_ptr()) if pixel_indices is not None else None,
+                                                      int(first_index), n, C.c_void_p(rad.data_ptr()),
+                                                      C.c_void_p(pay.data_ptr()) if pay is not None else None))
+        cur.wait_stream(ext)                                           # torch's later work follows the query
+        return (rad, pay) if want_payload else rad
 
     def export_lighttrees(self, mesh_count: int):
         tc, tr, bt = C.c_uint32(), C.c_uint32(), C.c_uint32()

@@ -103,6 +103,11 @@ struct fyprt_context {
     // launch, [5] low word = queue head of the persistent kernel), the host entry's staging buffers, its two timing events
     DevBuf<unsigned long long> queryCounters; DevBuf<float4> queryRays; DevBuf<uint32_t> queryResults; hipEvent_t queryEv[2] = {};
     int queryOcc[2] = {0, 0}; size_t queryOccLds[2] = {0, 0};     // cached residency of k_query_rays<kind, false>
+    // radiance queries (fyprt_render_rays*, rt_query.h: k_render_rays_primary + the path stages), allocated on first use for
+    // min(count, FYPRT_RENDER_RAYS_CHUNK) rays and kept: primary records, path state, ray / result lists, live lists, list counters + queue
+    // heads; the host entry's staging (rays, pixel indices, radiance) and its two timing events
+    DevBuf<Payload> rrPayload; DevBuf<float4> rrRays[2], rrHits[2], rrState; DevBuf<uint32_t> rrPixels, rrPixels2, rrCounters;
+    DevBuf<float4> rrIn, rrOut; DevBuf<uint32_t> rrIndices; hipEvent_t rrEv[2] = {};
 
     int fail(int code, const std::string& m) { err = m; return code; }
     int hip(hipError_t e, const char* what) {
@@ -193,6 +198,10 @@ void fyprt_destroy(fyprt_context* c) {
     c->sortCounts.release(); c->sortOffset.release(); c->sortTotal.release(); c->sortIndex.release(); c->sortKeys.release(); c->sortHist.release();
     c->queryCounters.release(); c->queryRays.release(); c->queryResults.release();
     for (auto& e : c->queryEv) if (e) (void)hipEventDestroy(e);
+    c->rrPayload.release(); for (int k = 0; k < 2; ++k) { c->rrRays[k].release(); c->rrHits[k].release(); }
+    c->rrState.release(); c->rrPixels.release(); c->rrPixels2.release(); c->rrCounters.release();
+    c->rrIn.release(); c->rrOut.release(); c->rrIndices.release();
+    for (auto& e : c->rrEv) if (e) (void)hipEventDestroy(e);
     for (auto& row : c->ring) for (auto& e : row) if (e) (void)hipEventDestroy(e);
     for (int k = 0; k < 2; ++k) { if (c->evFront[k]) (void)hipEventDestroy(c->evFront[k]); if (c->evDone[k]) (void)hipEventDestroy(c->evDone[k]); }
     if (c->front) (void)hipStreamDestroy(c->front);
@@ -707,14 +716,89 @@ static int ensure_paths(fyprt_context* c, size_t entries, uint32_t raysPer, uint
     return FYPRT_OK;
 }
 
-typedef void (*shade_kernel_t)(DevScene, DevCamera, DevFrame, DevSettings, PathIO);
-static shade_kernel_t shade_kernel(int stage) {
+extern "C++" {                                                   // (templates inside the C ABI file)
+template <class CAM> using shade_kernel_t = void (*)(DevScene, CAM, DevFrame, DevSettings, PathIO);
+template <class CAM> static shade_kernel_t<CAM> shade_kernel(int stage) {
     switch (stage) {
-        case T_BRUTE: return k_shade<T_BRUTE>; case T_UNIFORM: return k_shade<T_UNIFORM>; case T_COSINE: return k_shade<T_COSINE>;
-        case T_GGX: return k_shade<T_GGX>; case T_BRDF: return k_shade<T_BRDF>; case T_LIGHT: return k_shade<T_LIGHT>;
-        case T_NEE: return k_shade<T_NEE>; case T_GI1: return k_shade<T_GI1>; default: return k_shade<T_GI2>;
+        case T_BRUTE: return k_shade<T_BRUTE, CAM>; case T_UNIFORM: return k_shade<T_UNIFORM, CAM>; case T_COSINE: return k_shade<T_COSINE, CAM>;
+        case T_GGX: return k_shade<T_GGX, CAM>; case T_BRDF: return k_shade<T_BRDF, CAM>; case T_LIGHT: return k_shade<T_LIGHT, CAM>;
+        case T_NEE: return k_shade<T_NEE, CAM>;
     }
+    if constexpr (std::is_same<CAM, DevCamera>::value) return stage == T_GI1 ? k_shade<T_GI1> : k_shade<T_GI2>;      // (ReSTIR GI: frames only)
+    return nullptr;
 }
+
+// One pass of the wavefront path engine over a list of live paths (rt_paths.h): per step one shade launch (NEE: + MIS and emit
+// launches) and one trace launch.  Frames (CAM = DevCamera, the context's wf* buffers, counters at rayCounter + 8 x counterPart) and
+// radiance queries (CAM = RaySource, the query's own buffers and counters) share it.  `blocking`: the caller synchronises anyway, so
+// long sample x bounce products may poll the live-path count and stop early.  `launched` counts the kernel launches.
+struct StageRun { int stage; uint32_t steps, raysPer, stride; const uint32_t* pixelList; uint32_t* cnt; uint32_t* heads; uint32_t* part2List; uint32_t* part2Count; int counterPart; uint32_t* misCounts; size_t maxEntries; };
+struct StageBufs { float4* rays[2]; float4* hits[2]; float4* state; uint32_t* pixels; uint32_t* pixels2; unsigned long long* rayCounter; };
+template <class CAM>
+static int run_stage(fyprt_context* c, const StageRun& r, const StageBufs& b, const DevScene& sc, const CAM& cam, const DevFrame& fr, const DevSettings& st,
+                     size_t ldsBytes, bool blocking, int* launched) {
+    const shade_kernel_t<CAM> shade = shade_kernel<CAM>(r.stage);
+    const dim3 block(kBlock);
+    const dim3 shadeGrid((uint32_t)(c->numCUs * 8));
+    if (c->pathOccLds != ldsBytes) {
+        int n = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_trace_rays<false>, kBlock, ldsBytes) != hipSuccess || n <= 0) n = 4;
+        c->pathOcc = n; c->pathOccLds = ldsBytes;
+    }
+    const int perCU = c->tuning[2] > 0 ? c->tuning[2] : c->pathOcc;
+    DevScene tsc = sc;
+    tsc.nodeQuorum = (uint32_t)c->tuning[6];                 // incoherent rays: leave the node loop once few lanes remain in it
+    tsc.rayCounter = b.rayCounter ? b.rayCounter + 8 * r.counterPart : nullptr;
+    for (uint32_t it = 0; it <= r.steps; ++it) {
+        PathIO io{};
+        io.fusedOwner = kNotFused;
+        io.pixelList = r.pixelList; io.raysIn = b.rays[it & 1u]; io.hitsIn = b.hits[it & 1u]; io.countIn = r.cnt + it;
+        io.raysOut = b.rays[(it + 1u) & 1u]; io.countOut = r.cnt + it + 1; io.state = b.state; io.stateStride = r.stride;
+        io.iteration = it; io.raysPer = r.raysPer; io.part2List = r.part2List; io.part2Count = r.part2Count;
+        // NEE's MIS list reuses the primary kernel's pixel list, which only step 0 reads (and step 0 has no ray results, hence no MIS entries)
+        io.misList = b.pixels; io.misCount = r.misCounts ? r.misCounts + it : nullptr;
+        if (r.stage == T_GI2) {                                  // owner lists ping-pong between the Part-2 list's buffer and the (by now free) primary list's
+            io.ownersIn = (it & 1u) ? b.pixels : b.pixels2; io.ownersOut = (it & 1u) ? b.pixels2 : b.pixels;
+        }
+        hipLaunchKernelGGL(shade, shadeGrid, block, 0, c->stream, sc, cam, fr, st, io);
+        ++*launched;
+        if (r.stage == T_NEE && it > 0u) {                       // NEE: emitter-hit MIS for the few paths that need it (may add to the pick list)
+            hipLaunchKernelGGL(k_nee_mis<CAM>, dim3((uint32_t)c->numCUs), block, 0, c->stream, sc, cam, fr, st, (const uint32_t*)io.misList, (const uint32_t*)io.misCount,
+                               b.state, r.stride, r.part2List, io.countOut);
+            ++*launched;
+        }
+        if (it == r.steps) break;                                // the last step only consumes: every path has emitted all its rays
+        if (r.stage == T_NEE) {                                  // light pick + ray construction for the listed paths
+            hipLaunchKernelGGL(k_nee_emit, shadeGrid, block, 0, c->stream, sc, st, (const uint32_t*)r.part2List, (const uint32_t*)io.countOut, b.state, r.stride, io.raysOut, r.raysPer);
+            ++*launched;
+        }
+        TraceQueue q{};
+        q.rays = io.raysOut; q.hits = b.hits[(it + 1u) & 1u]; q.count = io.countOut; q.raysPer = r.raysPer; q.head = r.heads + it + 1;
+        q.chunk = (uint32_t)(c->tuning[4] > 0 ? c->tuning[4] : 128); q.refillLanes = (uint32_t)(c->tuning[5] > 0 ? c->tuning[5] : 24);
+        q.staticChunks = (uint32_t)(c->tuning[9] > 0 ? c->tuning[9] : 2); q.minChunk = (uint32_t)(c->tuning[10] > 0 ? c->tuning[10] : q.chunk);      // (auto: two static chunks per wave — config 3 3.13 -> 3.08 ms, profiles/README.md r03)
+        // small trees (cheap rays): one thread per ray; big ones: persistent waves with lane refill (tuning key 15: 0 = by tree size)
+        const bool simple = c->tuning[15] == 2 || (c->tuning[15] == 0 && c->hostBvh.tris.size() < 65536u);
+        if (simple) {
+            const uint32_t sg = (uint32_t)std::min<size_t>((size_t)c->numCUs * 16u, (r.maxEntries * r.raysPer + kBlock - 1) / kBlock);
+            if (tsc.rayCounter) hipLaunchKernelGGL(k_trace_rays_simple<true>, dim3(std::max(1u, sg)), block, ldsBytes, c->stream, tsc, q);
+            else hipLaunchKernelGGL(k_trace_rays_simple<false>, dim3(std::max(1u, sg)), block, ldsBytes, c->stream, tsc, q);
+        }
+        else if (tsc.rayCounter) hipLaunchKernelGGL(k_trace_rays<true>, dim3((uint32_t)(c->numCUs * perCU)), block, ldsBytes, c->stream, tsc, q);
+        else hipLaunchKernelGGL(k_trace_rays<false>, dim3((uint32_t)(c->numCUs * perCU)), block, ldsBytes, c->stream, tsc, q);
+        ++*launched;
+        // long sample x bounce products: stop once no path is alive any more.  Only inside a blocking call (fyprt_render, fyprt_render_rays)
+        // — an asynchronous call (fyprt_render_async, group / comm frames, fyprt_render_rays_device) must not wait on the device: there
+        // the remaining steps are launched and find empty lists (every kernel of a step returns at once on a count of zero)
+        if (blocking && r.steps > 8u && (it & 3u) == 3u) {
+            uint32_t alive = 0;
+            HIPCHK(c, hipMemcpyAsync(&alive, io.countOut, 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (alive == 0u) break;
+        }
+    }
+    return c->hip(hipGetLastError(), "path stage launch");
+}
+}  // extern "C++"
 
 // phase: 0 = the whole frame; 1 = ReSTIR Part 1 only (nothing of the frame's bookkeeping advances); 2 = the rest of the frame that a
 // phase-1 call started.  The split exists for the halo EXCHANGE of a multi-GPU frame (fyprt_multi.h): Part 1 on every band, the
@@ -816,62 +900,12 @@ static int enqueue_frame_impl(fyprt_context* c, const fyprt_settings* s, bool ti
     if (phase == 2) ei = 1;
     else if (timed) HIPCHK(c, hipEventRecord(c->ev[ei++], fs));
     int launches = 0;
-    // ---- wavefront path engine (rt_paths.h): primary kernel, then per step one shade launch + one persistent trace launch
-    struct StageRun { int stage; uint32_t steps, raysPer, stride; const uint32_t* pixelList; uint32_t* cnt; uint32_t* heads; uint32_t* part2List; uint32_t* part2Count; int counterPart; uint32_t* misCounts; size_t maxEntries; };
-    auto run_stage = [&](const StageRun& r) -> int {
-        const shade_kernel_t shade = shade_kernel(r.stage);
-        const dim3 shadeGrid((uint32_t)(c->numCUs * 8));
-        if (c->pathOccLds != ldsBytes) {
-            int n = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_trace_rays<false>, kBlock, ldsBytes) != hipSuccess || n <= 0) n = 4;
-            c->pathOcc = n; c->pathOccLds = ldsBytes;
-        }
-        const int perCU = c->tuning[2] > 0 ? c->tuning[2] : c->pathOcc;
-        DevScene tsc = c->dsc;
-        tsc.nodeQuorum = (uint32_t)c->tuning[6];                 // incoherent rays: leave the node loop once few lanes remain in it
-        tsc.rayCounter = c->countRays ? c->rayCounter.p + 8 * r.counterPart : nullptr;
-        for (uint32_t it = 0; it <= r.steps; ++it) {
-            PathIO io{};
-            io.fusedOwner = kNotFused;
-            io.pixelList = r.pixelList; io.raysIn = c->wfRays[it & 1u].p; io.hitsIn = c->wfHits[it & 1u].p; io.countIn = r.cnt + it;
-            io.raysOut = c->wfRays[(it + 1u) & 1u].p; io.countOut = r.cnt + it + 1; io.state = c->wfState.p; io.stateStride = r.stride;
-            io.iteration = it; io.raysPer = r.raysPer; io.part2List = r.part2List; io.part2Count = r.part2Count;
-            // NEE's MIS list reuses the primary kernel's pixel list, which only step 0 reads (and step 0 has no ray results, hence no MIS entries)
-            io.misList = c->wfPixels.p; io.misCount = r.misCounts ? r.misCounts + it : nullptr;
-            if (r.stage == T_GI2) {                                  // owner lists ping-pong between the Part-2 list's buffer and the (by now free) primary list's
-                io.ownersIn = (it & 1u) ? c->wfPixels.p : c->wfPixels2.p; io.ownersOut = (it & 1u) ? c->wfPixels2.p : c->wfPixels.p;
-            }
-            hipLaunchKernelGGL(shade, shadeGrid, block, 0, c->stream, c->dsc, c->dcam, fr, st, io);
-            if (r.stage == T_NEE && it > 0u)                         // NEE: emitter-hit MIS for the few paths that need it (may add to the pick list)
-                hipLaunchKernelGGL(k_nee_mis, dim3((uint32_t)c->numCUs), block, 0, c->stream, c->dsc, c->dcam, fr, st, (const uint32_t*)io.misList, (const uint32_t*)io.misCount,
-                                   c->wfState.p, r.stride, r.part2List, io.countOut);
-            if (it == r.steps) break;                                // the last step only consumes: every path has emitted all its rays
-            if (r.stage == T_NEE)                                    // light pick + ray construction for the listed paths
-                hipLaunchKernelGGL(k_nee_emit, shadeGrid, block, 0, c->stream, c->dsc, st, (const uint32_t*)r.part2List, (const uint32_t*)io.countOut, c->wfState.p, r.stride, io.raysOut, r.raysPer);
-            TraceQueue q{};
-            q.rays = io.raysOut; q.hits = c->wfHits[(it + 1u) & 1u].p; q.count = io.countOut; q.raysPer = r.raysPer; q.head = r.heads + it + 1;
-            q.chunk = (uint32_t)(c->tuning[4] > 0 ? c->tuning[4] : 128); q.refillLanes = (uint32_t)(c->tuning[5] > 0 ? c->tuning[5] : 24);
-            q.staticChunks = (uint32_t)(c->tuning[9] > 0 ? c->tuning[9] : 2); q.minChunk = (uint32_t)(c->tuning[10] > 0 ? c->tuning[10] : q.chunk);      // (auto: two static chunks per wave — config 3 3.13 -> 3.08 ms, profiles/README.md r03)
-            // small trees (cheap rays): one thread per ray; big ones: persistent waves with lane refill (tuning key 15: 0 = by tree size)
-            const bool simple = c->tuning[15] == 2 || (c->tuning[15] == 0 && c->hostBvh.tris.size() < 65536u);
-            if (simple) {
-                const uint32_t sg = (uint32_t)std::min<size_t>((size_t)c->numCUs * 16u, (r.maxEntries * r.raysPer + kBlock - 1) / kBlock);
-                if (c->countRays) hipLaunchKernelGGL(k_trace_rays_simple<true>, dim3(std::max(1u, sg)), block, ldsBytes, c->stream, tsc, q);
-                else hipLaunchKernelGGL(k_trace_rays_simple<false>, dim3(std::max(1u, sg)), block, ldsBytes, c->stream, tsc, q);
-            }
-            else if (c->countRays) hipLaunchKernelGGL(k_trace_rays<true>, dim3((uint32_t)(c->numCUs * perCU)), block, ldsBytes, c->stream, tsc, q);
-            else hipLaunchKernelGGL(k_trace_rays<false>, dim3((uint32_t)(c->numCUs * perCU)), block, ldsBytes, c->stream, tsc, q);
-            // long sample x bounce products: stop once no path is alive any more.  Only inside the blocking fyprt_render — an asynchronous
-            // call (fyprt_render_async, group / comm frames) must not wait on the device: there the remaining steps are launched and find
-            // empty lists (every kernel of a step returns at once on a count of zero)
-            if (c->blockingCall && r.steps > 8u && (it & 3u) == 3u) {
-                uint32_t alive = 0;
-                HIPCHK(c, hipMemcpyAsync(&alive, io.countOut, 4, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                if (alive == 0u) break;
-            }
-        }
-        return c->hip(hipGetLastError(), "path stage launch");
+    // ---- wavefront path engine (rt_paths.h): primary kernel, then per step one shade launch + one persistent trace launch (run_stage)
+    int stageLaunches = 0;                                       // (a frame reports its parts as launches, not its kernels)
+    auto run_stage = [&](const StageRun& r) -> int {             // (the wf* buffers as ensure_paths left them)
+        const StageBufs wf{{c->wfRays[0].p, c->wfRays[1].p}, {c->wfHits[0].p, c->wfHits[1].p}, c->wfState.p, c->wfPixels.p, c->wfPixels2.p,
+                           c->countRays ? c->rayCounter.p : nullptr};
+        return ::run_stage(c, r, wf, c->dsc, c->dcam, fr, st, ldsBytes, c->blockingCall, &stageLaunches);
     };
     switch (tech) {
         case FYPRT_BRUTE_FORCE: case FYPRT_UNIFORM_SAMPLING: case FYPRT_COSINE_WEIGHTED_SAMPLING: case FYPRT_GGX_SAMPLING: case FYPRT_BRDF_SAMPLING:
@@ -1357,6 +1391,133 @@ int fyprt_trace_rays_device(fyprt_context* c, int query, const void* rays, uint3
     if (count == 0) return FYPRT_OK;
     HIPCHK(c, hipSetDevice(c->device));
     return enqueue_query(c, query, static_cast<const float4*>(rays), count, results, false);
+}
+
+// ---- radiance queries (rt_query.h: k_render_rays_primary; rt_paths.h: the path stages with CAM = RaySource).  A frame's sample of
+// techniques 0-6 for the caller's rays: the closest-hit query kernels trace the primary segments into the query's own payload records,
+// k_render_rays_primary finishes what a frame's primary kernel finishes, run_stage runs the rest as it runs a frame's.  Everything it
+// writes is its own (rr* buffers, the query counters): no frame state moves.
+static int check_render_rays(fyprt_context* c, const fyprt_settings* s, uint32_t frameIndex, const void* rays, const void* indices, uint32_t count,
+                             const void* radiance, const void* payloads, bool device) {
+    const char* who = device ? "fyprt_render_rays_device" : "fyprt_render_rays";
+    if (!c) return FYPRT_EINVAL;
+    if (!s) return c->fail(FYPRT_EINVAL, std::string(who) + ": NULL settings");
+    if (s->technique < 0 || s->technique > FYPRT_NEE) return c->fail(FYPRT_EINVAL, std::string(who) + ": techniques 0-6 only (ReSTIR is defined over screen-space neighbours and history)");
+    if (frameIndex == 0) return c->fail(FYPRT_EINVAL, std::string(who) + ": frame_index must be >= 1");
+    if (count && (!rays || !radiance)) return c->fail(FYPRT_EINVAL, std::string(who) + ": NULL rays / radiance with a non-zero count");
+    if (device && (((uintptr_t)rays & 15u) || ((uintptr_t)radiance & 15u) || ((uintptr_t)payloads & 7u) || ((uintptr_t)indices & 3u)))
+        return c->fail(FYPRT_EINVAL, std::string(who) + ": rays and radiance must be 16-byte, payloads 8-byte and indices 4-byte aligned");
+    if (c->hostOnly) return c->fail(FYPRT_ESTATE, std::string(who) + ": host-only context (device -1) cannot render");
+    if (!c->haveScene) return c->fail(FYPRT_ESTATE, std::string(who) + " before fyprt_upload_scene");
+    if ((s->technique == FYPRT_LIGHT_SOURCE_SAMPLING || s->technique == FYPRT_NEE) && (c->dsc.emissiveCount == 0 || c->dsc.ltTlasCount == 0))
+        return c->fail(FYPRT_ENOLIGHT, std::string(who) + ": technique needs emissive triangles and a light tree");
+    return FYPRT_OK;
+}
+
+// Enqueues one chunk (count <= FYPRT_RENDER_RAYS_CHUNK, device memory): primary pass, then the stages.  Buffers grow to the chunk and are kept.
+static int enqueue_render_rays(fyprt_context* c, const fyprt_settings* s, uint32_t frameIndex, const float4* rays, const uint32_t* indices, uint32_t firstIndex,
+                               uint32_t count, float4* radiance, void* payloads, hipMemcpyKind payloadKind, bool blocking, int* launched) {
+    const int tech = s->technique;
+    DevSettings st{};                                            // what techniques 0-6 read, with the frame's casts (enqueue_frame_impl)
+    st.sky = f3{s->sky_color[0], s->sky_color[1], s->sky_color[2]};
+    st.maxBounces = (uint8_t)s->light_bounces; st.sampleCount = (uint8_t)s->sample_count;
+    st.skipDeadRays = c->tuning[18] ? 1u : 0u;
+    const uint32_t nSamples = (tech == FYPRT_BRUTE_FORCE) ? 1u : st.sampleCount;
+    const uint32_t steps = (tech == FYPRT_LIGHT_SOURCE_SAMPLING) ? nSamples : nSamples * st.maxBounces;
+    const uint32_t raysPer = (tech == FYPRT_NEE && st.maxBounces != 1u) ? 2u : 1u;
+    const uint32_t stride = (tech == FYPRT_NEE) ? 6u : 2u;
+    const size_t L = (size_t)steps + 2;
+    // buffers for the largest chunk so far, every technique (2 rays per entry, 6 quads of state); grown after the work that uses them
+    if (c->rrPayload.n < count) {
+        if (c->rrPayload.p) HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, c->rrPayload.alloc(count));
+        for (int k = 0; k < 2; ++k) { HIPCHK(c, c->rrRays[k].alloc((size_t)count * 2 * 3)); HIPCHK(c, c->rrHits[k].alloc((size_t)count * 2)); }
+        HIPCHK(c, c->rrState.alloc((size_t)count * 6)); HIPCHK(c, c->rrPixels.alloc(count)); HIPCHK(c, c->rrPixels2.alloc(count));
+    }
+    if (c->rrCounters.n < 3 * L) {
+        if (c->rrCounters.p) HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, c->rrCounters.alloc(3 * L));
+    }
+    HIPCHK(c, hipMemsetAsync(c->rrCounters.p, 0, 3 * L * sizeof(uint32_t), c->stream));
+    // primary segments: the closest-hit query (its own counters and queue head; ray counts of the whole call land there too)
+    { const int rc = enqueue_query(c, FYPRT_QUERY_CLOSEST, rays, count, c->rrPayload.p, false); if (rc != FYPRT_OK) return rc; }
+    ++*launched;
+    DevScene qs = c->dsc;                                        // as enqueue_query: the frame's descriptor is not touched
+    const int budget = effective_stack_budget(c);
+    qs.stackBudget = budget; qs.topCount = 0u; qs.rayCounter = nullptr;
+    const size_t ldsBytes = (size_t)(budget + 1) * kBlock * sizeof(int32_t);
+    DevFrame fr{};                                               // the step functions read the primary records and the frame index only
+    fr.payload = c->rrPayload.p; fr.frameIndex = frameIndex; fr.W = 1u; fr.H = 1u;
+    RaySource rs{rays, indices, firstIndex, radiance};
+    const uint32_t pg = (uint32_t)std::max<size_t>(1, std::min<size_t>((size_t)c->numCUs * 16u, ((size_t)count + kBlock - 1) / kBlock));
+    hipLaunchKernelGGL(k_render_rays_primary, dim3(pg), dim3(kBlock), 0, c->stream, qs, rs, fr, st, count, c->rrPixels.p, c->rrCounters.p);
+    ++*launched;
+    HIPCHK(c, hipGetLastError());
+    const StageBufs b{{c->rrRays[0].p, c->rrRays[1].p}, {c->rrHits[0].p, c->rrHits[1].p}, c->rrState.p, c->rrPixels.p, c->rrPixels2.p,
+                      c->countRays ? c->queryCounters.p : nullptr};
+    const StageRun r{tech, steps, raysPer, stride, c->rrPixels.p, c->rrCounters.p, c->rrCounters.p + L, (tech == FYPRT_NEE) ? c->rrPixels2.p : nullptr, nullptr, 0,
+                     (tech == FYPRT_NEE) ? c->rrCounters.p + 2 * L : nullptr, count};
+    { const int rc = run_stage(c, r, b, qs, rs, fr, st, ldsBytes, blocking, launched); if (rc != FYPRT_OK) return rc; }
+    if (payloads) HIPCHK(c, hipMemcpyAsync(payloads, c->rrPayload.p, (size_t)count * sizeof(Payload), payloadKind, c->stream));
+    return FYPRT_OK;
+}
+
+int fyprt_render_rays(fyprt_context* c, const fyprt_settings* s, uint32_t frame_index, const fyprt_ray* rays, const uint32_t* pixel_indices, uint32_t first_index,
+                      uint32_t count, float* radiance4, void* payloads, fyprt_frame_stats* stats) {
+    { const int rc = check_render_rays(c, s, frame_index, rays, pixel_indices, count, radiance4, payloads, false); if (rc != FYPRT_OK) return rc; }
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (count == 0) return FYPRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->rrEv[0]) { HIPCHK(c, hipEventCreate(&c->rrEv[0])); HIPCHK(c, hipEventCreate(&c->rrEv[1])); }
+    const uint32_t chunkMax = std::min<uint32_t>(count, FYPRT_RENDER_RAYS_CHUNK);
+    if (c->rrIn.n < (size_t)chunkMax * 2) { HIPCHK(c, c->rrIn.alloc((size_t)chunkMax * 2)); HIPCHK(c, c->rrOut.alloc(chunkMax)); }    // staging grows, is kept
+    if (pixel_indices && c->rrIndices.n < chunkMax) HIPCHK(c, c->rrIndices.alloc(chunkMax));
+    float ms = 0.0f; int launches = 0; unsigned long long totals[5] = {0, 0, 0, 0, 0};
+    for (uint32_t base = 0; base < count; base += FYPRT_RENDER_RAYS_CHUNK) {
+        const uint32_t n = std::min<uint32_t>(count - base, FYPRT_RENDER_RAYS_CHUNK);
+        HIPCHK(c, hipMemcpyAsync(c->rrIn.p, rays + base, (size_t)n * sizeof(fyprt_ray), hipMemcpyHostToDevice, c->stream));
+        if (pixel_indices) HIPCHK(c, hipMemcpyAsync(c->rrIndices.p, pixel_indices + base, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipEventRecord(c->rrEv[0], c->stream));
+        { const int rc = enqueue_render_rays(c, s, frame_index, c->rrIn.p, pixel_indices ? c->rrIndices.p : nullptr, first_index + base, n, c->rrOut.p,
+                                             payloads ? static_cast<char*>(payloads) + (size_t)base * sizeof(Payload) : nullptr, hipMemcpyDeviceToHost, true, &launches);
+          if (rc != FYPRT_OK) return rc; }
+        HIPCHK(c, hipEventRecord(c->rrEv[1], c->stream));
+        HIPCHK(c, hipMemcpyAsync(radiance4 + (size_t)base * 4, c->rrOut.p, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        float chunkMs = 0.0f;
+        HIPCHK(c, hipEventElapsedTime(&chunkMs, c->rrEv[0], c->rrEv[1]));
+        ms += chunkMs;
+        if (c->countRays) {
+            unsigned long long r[5] = {0, 0, 0, 0, 0};
+            HIPCHK(c, hipMemcpy(r, c->queryCounters.p, sizeof r, hipMemcpyDeviceToHost));
+            for (int k = 0; k < 5; ++k) totals[k] += r[k];
+        }
+    }
+    if (stats) {
+        stats->kernel_ms = ms; stats->kernel_ms_part[0] = ms; stats->launches = (uint32_t)launches;
+        if (c->countRays) {
+            stats->rays = stats->part_rays[0] = totals[0]; stats->box_tests = stats->part_box_tests[0] = totals[1];
+            stats->tri_tests = stats->part_tri_tests[0] = totals[2]; stats->hits = stats->part_hits[0] = totals[3];
+            stats->node_visits = stats->part_node_visits[0] = totals[4];
+        }
+    }
+    return FYPRT_OK;
+}
+
+int fyprt_render_rays_device(fyprt_context* c, const fyprt_settings* s, uint32_t frame_index, const void* rays, const uint32_t* pixel_indices, uint32_t first_index,
+                             uint32_t count, void* radiance4, void* payloads) {
+    { const int rc = check_render_rays(c, s, frame_index, rays, pixel_indices, count, radiance4, payloads, true); if (rc != FYPRT_OK) return rc; }
+    if (count == 0) return FYPRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    int launches = 0;
+    for (uint32_t base = 0; base < count; base += FYPRT_RENDER_RAYS_CHUNK) {
+        const uint32_t n = std::min<uint32_t>(count - base, FYPRT_RENDER_RAYS_CHUNK);
+        const int rc = enqueue_render_rays(c, s, frame_index, static_cast<const float4*>(rays) + (size_t)base * 2, pixel_indices ? pixel_indices + base : nullptr,
+                                           first_index + base, n, static_cast<float4*>(radiance4) + base,
+                                           payloads ? static_cast<char*>(payloads) + (size_t)base * sizeof(Payload) : nullptr, hipMemcpyDeviceToDevice, false, &launches);
+        if (rc != FYPRT_OK) return rc;
+    }
+    return FYPRT_OK;
 }
 
 #include "fyprt_multi.h"

@@ -76,6 +76,29 @@ RT_DEV uint32_t block_append(bool live, uint32_t* counter) {
     return slot;
 }
 
+// ============================================================ ray sources of techniques 0-6
+// A step knows its path by the owner `i` of the state record; the primary record is fr.payload[i] and the state io.state[i * stride].
+// Four things tie the owner to a camera: the primary direction, the seed index, and where the result goes.  A frame's owner is a pixel
+// of the camera (DevCamera): the camera's direction, the pixel index as seed index, the epilogue.  A radiance query's owner is the slot
+// k of the caller's ray (RaySource, fyprt_render_rays): the caller's direction, the ray's pixel index p_k, radiance[k] = what the
+// epilogue would add to the accumulation.  path_step, light_step, nee_consume / nee_next_sample, k_shade and k_nee_mis take the source as
+// the type of their `cam` argument; the frame's instantiations are the code they were before.
+struct RaySource {
+    const float4* rays;          // fyprt_ray records: origin | tmin, direction | tmax (2 x float4 per ray)
+    const uint32_t* pixels;      // p_k = pixels[k], or firstIndex + k when pixels is NULL
+    uint32_t firstIndex;
+    float4* radiance;
+};
+RT_DEV f3 primary_dir(const DevCamera& cam, const DevFrame& fr, uint32_t i) { return ray_direction(cam, i % fr.W, i / fr.W); }
+RT_DEV f3 primary_dir(const RaySource& rs, const DevFrame&, uint32_t k) { return xyz(rs.rays[(size_t)k * 2 + 1]); }
+RT_DEV uint32_t seed_index(const DevCamera&, uint32_t i) { return i; }
+RT_DEV uint32_t seed_index(const RaySource& rs, uint32_t k) { return rs.pixels ? rs.pixels[k] : rs.firstIndex + k; }
+RT_DEV void finish(const DevCamera&, const DevFrame& fr, uint32_t i, f4 c) { epilogue(fr, i, c); }
+RT_DEV void finish(const RaySource& rs, const DevFrame&, uint32_t k, f4 c) {
+    if (!(finitef(c.x) && finitef(c.y) && finitef(c.z) && finitef(c.w))) c = mk4(0.0f, 0.0f, 0.0f, 0.0f);      // the epilogue's rule
+    rs.radiance[k] = make_float4(c.x, c.y, c.z, c.w);
+}
+
 // ============================================================ primary rays of techniques 0-6
 // First lines of every PerPixel_* function (e.g. R.cu:565-600): primary ray, sky / directly visible emitter -> finished.
 template <bool COUNT>
@@ -112,14 +135,14 @@ RT_DEV uint32_t owner_of(const PathIO& io, uint32_t j) {
 // ============================================================ techniques 0-4 (Renderer.cu:565-1284): sample loop x bounce loop
 // state: S0 = throughput, seed | S1 = radiance, sample | bounce << 16
 // LOCAL (k_path_fused): state, ray and hit of the previous step are the thread's own six quads (PathIO::local) instead of records in memory
-template <int TECH, bool LOCAL = false>
-RT_DEV bool path_step(const DevScene& sc, const DevCamera& cam, const DevFrame& fr, const DevSettings& st, const PathIO& io, uint32_t j, RayRec& out) {
-    const uint32_t i = owner_of(io, j), x = i % fr.W, y = i / fr.W;
+template <int TECH, bool LOCAL = false, class CAM = DevCamera>
+RT_DEV bool path_step(const DevScene& sc, const CAM& cam, const DevFrame& fr, const DevSettings& st, const PathIO& io, uint32_t j, RayRec& out) {
+    const uint32_t i = owner_of(io, j);
     float4* S = LOCAL ? io.local : io.state + (size_t)i * io.stateStride;
     const int nSamples = (TECH == T_BRUTE) ? 1 : (int)st.sampleCount;
     uint32_t seed; int s = 0, b = 0; f3 T = splat3(1.0f), radiance = splat3(0.0f), ro = splat3(0.0f), rd = splat3(0.0f);
     bool open = false;                                                     // a sample's path is in flight and needs its next ray
-    if (io.iteration == 0u) seed = i * fr.frameIndex;
+    if (io.iteration == 0u) seed = seed_index(cam, i) * fr.frameIndex;
     else {
         const float4 s0 = S[0], s1 = S[1];
         T = xyz(s0); seed = (uint32_t)__float_as_int(s0.w); radiance = xyz(s1);
@@ -154,7 +177,7 @@ RT_DEV bool path_step(const DevScene& sc, const DevCamera& cam, const DevFrame& 
         const Payload pp = fr.payload[i];
         const Mat hm = load_mat(sc, tri_material(sc, pp.objectIndex));
         const f3 palbedo = sample_albedo(sc, hm, pp.u, pp.v);
-        const f3 pd = ray_direction(cam, x, y);
+        const f3 pd = primary_dir(cam, fr, i);
         for (; s < nSamples; ++s) {
             if (TECH != T_BRUTE) seed += (uint32_t)((s + 1) * 27);
             float pdf;
@@ -174,18 +197,18 @@ RT_DEV bool path_step(const DevScene& sc, const DevCamera& cam, const DevFrame& 
         return true;
     }
     if (TECH != T_BRUTE) radiance = radiance / (float)st.sampleCount;
-    epilogue(fr, i, rgb1(radiance));
+    finish(cam, fr, i, rgb1(radiance));
     return false;
 }
 
 // ============================================================ LIGHT_SOURCE_SAMPLING (Renderer.cu:1287-1408): one shadow ray per sample
 // state: S0 = pending contribution T, seed | S1 = radiance, sample
-template <bool LOCAL = false>
-RT_DEV bool light_step(const DevScene& sc, const DevCamera& cam, const DevFrame& fr, const DevSettings& st, const PathIO& io, uint32_t j, RayRec& out) {
-    const uint32_t i = owner_of(io, j), x = i % fr.W, y = i / fr.W;
+template <bool LOCAL = false, class CAM = DevCamera>
+RT_DEV bool light_step(const DevScene& sc, const CAM& cam, const DevFrame& fr, const DevSettings& st, const PathIO& io, uint32_t j, RayRec& out) {
+    const uint32_t i = owner_of(io, j);
     float4* S = LOCAL ? io.local : io.state + (size_t)i * io.stateStride;
     uint32_t seed; int s = 0; f3 radiance = splat3(0.0f);
-    if (io.iteration == 0u) seed = i * fr.frameIndex;
+    if (io.iteration == 0u) seed = seed_index(cam, i) * fr.frameIndex;
     else {
         const float4 s0 = S[0], s1 = S[1];
         const f3 T = xyz(s0); seed = (uint32_t)__float_as_int(s0.w); radiance = xyz(s1); s = __float_as_int(s1.w);
@@ -202,7 +225,7 @@ RT_DEV bool light_step(const DevScene& sc, const DevCamera& cam, const DevFrame&
         const Payload pp = fr.payload[i];
         const Mat hm = load_mat(sc, tri_material(sc, pp.objectIndex));
         const f3 albedo = sample_albedo(sc, hm, pp.u, pp.v);
-        const f3 pd = ray_direction(cam, x, y);
+        const f3 pd = primary_dir(cam, fr, i);
         seed += (uint32_t)((s + 1) * 27);
         const PickedLight pl = pick_light(sc, pos3(pp), seed);
         const TriGeom g = load_tri(sc, pl.tri);
@@ -221,7 +244,7 @@ RT_DEV bool light_step(const DevScene& sc, const DevCamera& cam, const DevFrame&
         return true;
     }
     radiance = radiance / (float)st.sampleCount;
-    epilogue(fr, i, rgb1(radiance));
+    finish(cam, fr, i, rgb1(radiance));
     return false;
 }
 
@@ -239,17 +262,19 @@ RT_DEV bool light_step(const DevScene& sc, const DevCamera& cam, const DevFrame&
 // state: S0 = throughput, seed | S1 = radiance, sample | bounce << 16 | S2 = pending direct contribution, pdfBRDF
 //        S3 = shading point, u | S4 = shading normal, v | S5 = incoming direction, triangle
 // next sample of a path that ended (restart from the primary hit), or false when all samples are done
-RT_DEV bool nee_next_sample(const DevCamera& cam, const DevFrame& fr, const DevSettings& st, uint32_t i, int s, uint32_t& seed, float4* S, f3 radiance) {
+template <class CAM>
+RT_DEV bool nee_next_sample(const CAM& cam, const DevFrame& fr, const DevSettings& st, uint32_t i, int s, uint32_t& seed, float4* S, f3 radiance) {
     if (!(s < (int)st.sampleCount && st.maxBounces > 0u)) return false;
     seed += (uint32_t)((s + 1) * 31);
     const Payload pp = fr.payload[i];
-    const f3 pd = ray_direction(cam, i % fr.W, i / fr.W);
+    const f3 pd = primary_dir(cam, fr, i);
     S[0] = f3w(splat3(1.0f), seed); S[1] = f3w(radiance, (uint32_t)s); S[2] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
     S[3] = make_float4(pp.px, pp.py, pp.pz, pp.u); S[4] = make_float4(pp.nx, pp.ny, pp.nz, pp.v); S[5] = f3w(pd, (uint32_t)pp.objectIndex);
     return true;
 }
 // returns 1: goes on (PICK list), 2: BRDF ray hit an emitter (MIS list), 0: pixel finished
-RT_DEV int nee_consume(const DevScene& sc, const DevCamera& cam, const DevFrame& fr, const DevSettings& st, const PathIO& io, uint32_t j, uint32_t& owner) {
+template <class CAM>
+RT_DEV int nee_consume(const DevScene& sc, const CAM& cam, const DevFrame& fr, const DevSettings& st, const PathIO& io, uint32_t j, uint32_t& owner) {
     const uint32_t i = owner_of(io, j);
     owner = i;
     float4* S = io.state + (size_t)i * io.stateStride;
@@ -257,7 +282,7 @@ RT_DEV int nee_consume(const DevScene& sc, const DevCamera& cam, const DevFrame&
     uint32_t seed; int s = 0; uint32_t bounce = 0; f3 T = splat3(1.0f), radiance = splat3(0.0f), rd = splat3(0.0f); float pdfBRDF = 1.0f;
     Payload hit;
     bool open = false;
-    if (io.iteration == 0u) seed = i * fr.frameIndex;
+    if (io.iteration == 0u) seed = seed_index(cam, i) * fr.frameIndex;
     else {
         const float4 s0 = S[0], s1 = S[1], s2 = S[2];
         T = xyz(s0); seed = (uint32_t)__float_as_int(s0.w); radiance = xyz(s1); pdfBRDF = s2.w;
@@ -291,12 +316,13 @@ RT_DEV int nee_consume(const DevScene& sc, const DevCamera& cam, const DevFrame&
         return 1;
     }
     if (nee_next_sample(cam, fr, st, i, s, seed, S, radiance)) return 1;
-    epilogue(fr, i, rgb1(radiance / (float)st.sampleCount));
+    finish(cam, fr, i, rgb1(radiance / (float)st.sampleCount));
     return 0;
 }
 
 // MIS weight of a BRDF-sampled emitter hit (R.cu:1588-1612) for the paths nee_consume listed; the sample ends with it
-__global__ __launch_bounds__(kBlock) void k_nee_mis(DevScene sc, DevCamera cam, DevFrame fr, DevSettings st, const uint32_t* misList, const uint32_t* misCount,
+template <class CAM = DevCamera>
+__global__ __launch_bounds__(kBlock) void k_nee_mis(DevScene sc, CAM cam, DevFrame fr, DevSettings st, const uint32_t* misList, const uint32_t* misCount,
                                                     float4* state, uint32_t stateStride, uint32_t* pickList, uint32_t* pickCount) {
     const uint32_t n = *misCount;
     for (uint32_t base = blockIdx.x * (uint32_t)kBlock; base < n; base += gridDim.x * (uint32_t)kBlock) {
@@ -325,7 +351,7 @@ __global__ __launch_bounds__(kBlock) void k_nee_mis(DevScene sc, DevCamera cam, 
             radiance = radiance + (wB * T) * emission(em);
             ++s;
             live = nee_next_sample(cam, fr, st, i, s, seed, S, radiance);
-            if (!live) epilogue(fr, i, rgb1(radiance / (float)st.sampleCount));
+            if (!live) finish(cam, fr, i, rgb1(radiance / (float)st.sampleCount));
         }
         const uint32_t slot = block_append(live, pickCount);
         if (live) pickList[slot] = i;
@@ -914,18 +940,18 @@ __global__ __launch_bounds__(kBlock) void k_path_fused(DevScene sc, DevCamera ca
 #endif
 // (register budgets of the shade kernels are the compiler's own — 81 to 121 VGPRs, none spills; forcing 5 waves per SIMD spills in all
 // but three of them: tools/kernel_resources.py -DRT_SHADE_WAVES=...)
-template <int TECH>
-__global__ __launch_bounds__(kBlock) RT_SHADE_WAVES void k_shade(DevScene sc, DevCamera cam, DevFrame fr, DevSettings st, PathIO io) {
+template <int TECH, class CAM = DevCamera>      // CAM: the ray source (DevCamera for a frame; RaySource for a radiance query, techniques 0-6 only)
+__global__ __launch_bounds__(kBlock) RT_SHADE_WAVES void k_shade(DevScene sc, CAM cam, DevFrame fr, DevSettings st, PathIO io) {
     const uint32_t count = *io.countIn;
     for (uint32_t base = blockIdx.x * (uint32_t)kBlock; base < count; base += gridDim.x * (uint32_t)kBlock) {
         const uint32_t j = base + threadIdx.x;
         bool live = false, toPart2 = false;
         RayRec r0; uint32_t owner = 0;
         if (j < count) {
-            if (TECH == T_LIGHT) live = light_step<false>(sc, cam, fr, st, io, j, r0);
-            else if (TECH == T_NEE) { const int k = nee_consume(sc, cam, fr, st, io, j, owner); live = k == 1; toPart2 = k == 2; }
-            else if (TECH == T_GI1) live = gi1_step(sc, cam, fr, st, io, j, r0, toPart2);
-            else if (TECH == T_GI2) live = gi2_step(sc, cam, fr, st, io, j, r0);
+            if constexpr (TECH == T_LIGHT) live = light_step<false>(sc, cam, fr, st, io, j, r0);
+            else if constexpr (TECH == T_NEE) { const int k = nee_consume(sc, cam, fr, st, io, j, owner); live = k == 1; toPart2 = k == 2; }
+            else if constexpr (TECH == T_GI1) live = gi1_step(sc, cam, fr, st, io, j, r0, toPart2);
+            else if constexpr (TECH == T_GI2) live = gi2_step(sc, cam, fr, st, io, j, r0);
             else live = path_step<(TECH <= T_BRDF ? TECH : T_BRUTE)>(sc, cam, fr, st, io, j, r0);
         }
         const uint32_t slot = block_append(live, io.countOut);

@@ -18,7 +18,7 @@
 // The query kind is a template parameter: neither kernel carries the other kind's branches.  They only call the traversal core of
 // rt_device.h (node_step, tri_test, make_hit / make_miss, quorum_of, ray_not_finite); no frame kernel is touched.
 #pragma once
-#include "rt_wavefront.h"
+#include "rt_paths.h"
 
 namespace rt {
 
@@ -199,6 +199,33 @@ __global__ __launch_bounds__(kBlock) void k_query_rays_simple(DevScene sc, Query
     for (uint32_t base = blockIdx.x * (uint32_t)kBlock; base < q.count; base += gridDim.x * (uint32_t)kBlock) {   // (block-uniform trips: node_step's ballots see whole waves)
         const uint32_t j = base + threadIdx.x;
         if (j < q.count) query_one<OCCLUDED, COUNT>(sc, q, j, s_stack + threadIdx.x);
+    }
+}
+
+// ============================================================ radiance queries (fyprt_render_rays*): the primary pass
+// The primary segments are traced by the closest-hit kernels above into the query's own payload records (the frame's primary record
+// for the same ray and the default interval).  This kernel, one thread per ray, does what the rest of k_primary does: an invalid ray
+// gives (0,0,0,0), a miss inside the interval (sky, 1), an emitter hit (emission, 1); every other ray is appended to the live list, where
+// the stages (k_shade<TECH, RaySource>, k_nee_mis<RaySource>) take it from the primary hit as they take a frame's pixel.
+__global__ __launch_bounds__(kBlock) void k_render_rays_primary(DevScene sc, RaySource rs, DevFrame fr, DevSettings st, uint32_t count,
+                                                                uint32_t* list, uint32_t* listCount) {
+    for (uint32_t base = blockIdx.x * (uint32_t)kBlock; base < count; base += gridDim.x * (uint32_t)kBlock) {   // (block-uniform trips: block_append)
+        const uint32_t k = base + threadIdx.x;
+        bool live = false;
+        if (k < count) {
+            const float4 r0 = rs.rays[(size_t)k * 2], r1 = rs.rays[(size_t)k * 2 + 1];
+            if (query_invalid(xyz(r0), xyz(r1), r0.w, r1.w)) rs.radiance[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            else {
+                const Payload pp = fr.payload[k];
+                if (pp.hitDistance < 0.0f) finish(rs, fr, k, rgb1(st.sky));
+                else {
+                    const Mat hm = load_mat(sc, tri_material(sc, pp.objectIndex));
+                    if (length(emission(hm)) > 0.0f) finish(rs, fr, k, rgb1(emission(hm))); else live = true;
+                }
+            }
+        }
+        const uint32_t slot = block_append(live, listCount);
+        if (live) list[slot] = k;
     }
 }
 

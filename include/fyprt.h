@@ -356,6 +356,43 @@ int fyprt_trace_rays(fyprt_context* ctx, int query /* enum fyprt_query */, const
 /* Device memory of the context's GPU (rays: count x fyprt_ray; results as above), asynchronous on the context stream (fyprt_stream). */
 int fyprt_trace_rays_device(fyprt_context* ctx, int query /* enum fyprt_query */, const void* rays, uint32_t count, void* results);
 
+/* ================================================================================================= radiance queries
+ * New (no reference counterpart): the renderer's sample of techniques 0-6 for the caller's own rays — other camera models, light probes,
+ * surface bakes, re-rendering a few pixels ("Radiance queries").  Only an uploaded scene is needed (no resize, no camera).
+ *   settings   : a frame's fyprt_settings; technique (0..6), light_bounces, sample_count and sky_color are read, with a frame's uint8
+ *                casts; every other field is ignored.
+ *   rays       : fyprt_ray records.  [tmin, tmax] applies to the PRIMARY segment only, with the FYPRT_QUERY_CLOSEST acceptance rule; bounce
+ *                and shadow rays behave as in a frame.  The direction is used as given (-direction is the view vector at the primary hit,
+ *                as the camera direction is in a frame): pass unit vectors.
+ *   seed       : ray k uses the random sequence of pixel p_k = pixel_indices ? pixel_indices[k] : first_index + k, seeded p_k x frame_index
+ *                as a frame seeds pixel x + y*W with its frame index (frame_index >= 1).
+ *   radiance4  : count x float4 = exactly what a frame's epilogue adds to the accumulation for this ray: (rgb, 1), or (0,0,0,0) if any
+ *                component is non-finite.  A primary miss inside the interval gives (sky, 1), an emitter hit (emission, 1), a ray that
+ *                the batched ray queries call invalid (0,0,0,0) and the miss record, without traversal.  So a W x H frame with frame index f
+ *                accumulates exactly accum + radiance4 of its camera rays in row-major order with first_index 0 and frame_index f.
+ *   payloads   : NULL, or count x 40 B: the primary record, bit-identical to FYPRT_QUERY_CLOSEST for the same ray and interval.
+ * Errors, in this order: FYPRT_EINVAL for a NULL context or settings, a technique outside 0..6 (ReSTIR DI / GI are defined over
+ * screen-space neighbours and history, not free rays), frame_index 0, NULL rays / radiance4 with count > 0, and (device entry) rays or
+ * radiance4 not 16-byte, payloads not 8-byte or pixel_indices not 4-byte aligned; FYPRT_ESTATE on a host-only context or before
+ * fyprt_upload_scene; FYPRT_ENOLIGHT for techniques 5 and 6 without emissive triangles or light tree.  count 0 returns FYPRT_OK and
+ * launches nothing.
+ * No frame state moves (frame index, accumulation, image, payload, depth, normals, reservoirs, frame timings and counters); a query
+ * between the two parts of a ReSTIR frame leaves it undisturbed.  The query has its own path state, ray lists, counters and queue heads,
+ * allocated on first use for min(count, FYPRT_RENDER_RAYS_CHUNK) rays and kept; larger batches run in chunks of that many rays, with the
+ * same results.  Tuning keys 4, 5, 6, 9, 10 and 15 act on its trace launches as on a frame's path stages (and key 18 on NEE's shadow rays).
+ * The caller's rays are not reordered.  For the closest-hit query alone, 8x8-tile-ordered camera rays measured faster than row-major
+ * ones; for a whole radiance query of 1080p camera rays, row-major order measured slightly faster. */
+#define FYPRT_RENDER_RAYS_CHUNK (1u << 21)   /* rays per internal pass; larger batches are split, results unchanged */
+/* Host memory, blocking.  `stats` may be NULL: kernel_ms = the hipEvent time over the call's kernels, launches = their number; with ray
+ * counting on, rays / box_tests / tri_tests / hits / node_visits are the totals, counted as a frame counts them, part_*[0] = the same. */
+int fyprt_render_rays(fyprt_context* ctx, const fyprt_settings* settings, uint32_t frame_index,
+                      const fyprt_ray* rays, const uint32_t* pixel_indices /* may be NULL */, uint32_t first_index, uint32_t count,
+                      float* radiance4, void* payloads /* may be NULL: count x 40 B */, fyprt_frame_stats* stats /* may be NULL */);
+/* Device memory of the context's GPU, asynchronous on the context stream (fyprt_stream); it never waits on the device. */
+int fyprt_render_rays_device(fyprt_context* ctx, const fyprt_settings* settings, uint32_t frame_index,
+                             const void* rays, const uint32_t* pixel_indices, uint32_t first_index, uint32_t count,
+                             void* radiance4, void* payloads);
+
 /* ================================================================================================= multi-GPU
  * The reference renders on one GPU (Renderer.cu:13-284); there is no reference interface for this section.  It splits ONE
  * Renderer::Render call over several GPUs by image rows: every GPU holds the whole scene and renders a band;
