@@ -21,6 +21,7 @@ TECHNIQUE_NAMES = ["BRUTE_FORCE", "UNIFORM_SAMPLING", "COSINE_WEIGHTED_SAMPLING"
                    "LIGHT_SOURCE_SAMPLING", "NEE", "RESTIR_DI", "RESTIR_GI"]
 
 BUF_ACCUM, BUF_IMAGE, BUF_PAYLOAD, BUF_DEPTH, BUF_NORMAL, BUF_DI, BUF_DI_PREV, BUF_GI, BUF_GI_PREV = range(9)
+BUF_ALBEDO = 9      # float4 per pixel: albedo of the primary hit, w = 1 filterable / 0 not; written by Context.denoise* (fyprt_denoise)
 
 # numpy views of the per-pixel records (Ray.h:13-22, ReSTIR_DI_Reservoir.cuh:9-16, ReSTIR_GI_Reservoir.cuh:9-27)
 PAYLOAD_DTYPE = np.dtype([("hitDistance", "<f4"), ("worldPosition", "<f4", 3), ("worldNormal", "<f4", 3),
@@ -33,7 +34,7 @@ GI_DTYPE = np.dtype([("visiblePoint", "<f4", 3), ("visibleNormal", "<f4", 2), ("
 assert PAYLOAD_DTYPE.itemsize == 40 and DI_DTYPE.itemsize == 20 and GI_DTYPE.itemsize == 72
 BUFFER_DTYPES = {BUF_ACCUM: np.dtype(("<f4", 4)), BUF_IMAGE: np.dtype("<u4"), BUF_PAYLOAD: PAYLOAD_DTYPE,
                  BUF_DEPTH: np.dtype("<f4"), BUF_NORMAL: np.dtype(("<f4", 2)), BUF_DI: DI_DTYPE, BUF_DI_PREV: DI_DTYPE,
-                 BUF_GI: GI_DTYPE, BUF_GI_PREV: GI_DTYPE}
+                 BUF_GI: GI_DTYPE, BUF_GI_PREV: GI_DTYPE, BUF_ALBEDO: np.dtype(("<f4", 4))}
 
 VERTEX_DTYPE = np.dtype([("position", "<f4", 3), ("normal", "<f4", 3), ("uv", "<f4", 2)])
 TRIANGLE_DTYPE = np.dtype([("v0", "<u4"), ("v1", "<u4"), ("v2", "<u4"), ("materialIndex", "<i4")])
@@ -123,6 +124,22 @@ class FrameStats(C.Structure):
                 ("launches", C.c_uint32), ("node_visits", C.c_uint64), ("part_node_visits", C.c_uint64 * 4)]
 
 
+class DenoiseParams(C.Structure):  # fyprt_denoise_params (20 B) with the library's defaults (fyprt_denoise_default_params)
+    _fields_ = [("iterations", C.c_uint32), ("sigma_luminance", C.c_float), ("sigma_plane", C.c_float),
+                ("normal_power_log2", C.c_uint32), ("demodulate_albedo", C.c_uint32)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        self.iterations, self.sigma_luminance, self.sigma_plane, self.normal_power_log2, self.demodulate_albedo = 5, 4.0, 0.01, 6, 1
+        for k, v in kw.items():
+            if not hasattr(self, k):
+                raise AttributeError(k)
+            setattr(self, k, v)
+
+
+assert C.sizeof(DenoiseParams) == 20
+
+
 EXPORTED_SYMBOLS = [
     "fyprt_create", "fyprt_destroy", "fyprt_last_error", "fyprt_resize", "fyprt_set_rows", "fyprt_upload_scene",
     "fyprt_set_camera", "fyprt_render", "fyprt_render_async", "fyprt_synchronize", "fyprt_readback",
@@ -136,6 +153,7 @@ EXPORTED_SYMBOLS = [
     "fyprt_set_row_stripes", "fyprt_group_set_interleave", "fyprt_comm_set_interleave", "fyprt_selftest_math",
     "fyprt_trace_rays", "fyprt_trace_rays_device",
     "fyprt_render_rays", "fyprt_render_rays_device",
+    "fyprt_denoise_default_params", "fyprt_denoise", "fyprt_denoise_device",
 ]
 
 
@@ -194,6 +212,10 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     if hasattr(lib, "fyprt_render_rays"):    # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
         lib.fyprt_render_rays.argtypes = [vp, C.POINTER(Settings), u32, vp, vp, u32, u32, vp, vp, C.POINTER(FrameStats)]
         lib.fyprt_render_rays_device.argtypes = [vp, C.POINTER(Settings), u32, vp, vp, u32, u32, vp, vp]
+    if hasattr(lib, "fyprt_denoise"):        # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
+        lib.fyprt_denoise_default_params.argtypes = [C.POINTER(DenoiseParams)]
+        lib.fyprt_denoise.argtypes = [vp, C.POINTER(DenoiseParams), vp, vp, C.POINTER(FrameStats)]
+        lib.fyprt_denoise_device.argtypes = [vp, C.POINTER(DenoiseParams), vp, vp]
     lib.fyprt_group_create.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(u32), C.POINTER(vp)]
     lib.fyprt_group_destroy.argtypes = [vp]
     lib.fyprt_group_destroy.restype = None
@@ -537,6 +559,43 @@ class Context:
                                                       C.c_void_p(pay.data_ptr()) if pay is not None else None))
         cur.wait_stream(ext)                                           # torch's later work follows the query
         return (rad, pay) if want_payload else rad
+
+    def denoise(self, params: DenoiseParams | None = None, want_radiance=True, with_stats=False):
+        """Edge-avoiding denoise of the frame rendered last (fyprt_denoise, blocking; defaults when `params` is None).  Returns
+        (image H x W uint32 ABGR8, radiance H x W x 4 float32 or None without `want_radiance`), with `with_stats` also the FrameStats of
+        the call.  No frame state moves; read_buffer(BUF_ALBEDO) afterwards gives the albedo guide of that frame."""
+        p = params if params is not None else DenoiseParams()
+        n = self.width * self.height
+        img = np.empty(n, dtype=np.uint32)
+        rad = np.empty((n, 4), dtype=np.float32) if want_radiance else None
+        st = FrameStats()
+        self._check(self.lib.fyprt_denoise(self.h, C.byref(p), _ptr(img), _ptr(rad), C.byref(st)))
+        out = (img.reshape(self.height, self.width), rad.reshape(self.height, self.width, 4) if want_radiance else None)
+        return out + (st,) if with_stats else out
+
+    def denoise_tensor(self, image_tensor, radiance_tensor, params: DenoiseParams | None = None):
+        """Denoise into device tensors (fyprt_denoise_device): `image_tensor` a contiguous int32 (H, W) tensor or None, `radiance_tensor`
+        a contiguous float32 (H, W, 4) tensor or None, on this context's GPU.  Ordered against torch's current stream as
+        trace_rays_tensor is, without a host synchronisation and without record_stream."""
+        import torch
+        p = params if params is not None else DenoiseParams()
+        if image_tensor is None and radiance_tensor is None:
+            raise ValueError("denoise_tensor: at least one output tensor is needed")
+        for t, dt, shape, name in ((image_tensor, torch.int32, (self.height, self.width), "image_tensor"),
+                                   (radiance_tensor, torch.float32, (self.height, self.width, 4), "radiance_tensor")):
+            if t is None:
+                continue
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"denoise_tensor: {name} must be a contiguous {dt} tensor of shape {shape}")
+            if t.device.type != "cuda" or (t.device.index if t.device.index is not None else torch.cuda.current_device()) != self.device:
+                raise ValueError(f"denoise_tensor: {name} must be on cuda:{self.device}, the context's GPU")
+        dev = (image_tensor if image_tensor is not None else radiance_tensor).device
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
+        ext.wait_stream(cur)                                           # the outputs are allocated (and their earlier uses done) before the kernels run
+        self._check(self.lib.fyprt_denoise_device(self.h, C.byref(p), C.c_void_p(image_tensor.data_ptr()) if image_tensor is not None else None,
+                                                  C.c_void_p(radiance_tensor.data_ptr()) if radiance_tensor is not None else None))
+        cur.wait_stream(ext)                                           # torch's later work follows the denoiser
 
     def export_lighttrees(self, mesh_count: int):
         tc, tr, bt = C.c_uint32(), C.c_uint32(), C.c_uint32()

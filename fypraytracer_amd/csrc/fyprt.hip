@@ -14,8 +14,16 @@
 #include "rt_refit.h"
 #include "rt_paths.h"
 #include "rt_query.h"
+#include "rt_denoise.h"
 
 using namespace rt;
+
+// Largest step of the denoiser's iterations that runs the LDS-staged kernel (rt_denoise.h: k_dn_iterate<1> ... <32>); larger steps
+// gather (iterations 7 and 8).  A build-time constant so that a variant library (tools/build_variant.sh) can time the other choice at
+// every step; there is no tuning key.
+#ifndef RT_DN_LDS_MAX_STEP
+#define RT_DN_LDS_MAX_STEP 32
+#endif
 
 namespace {
 
@@ -108,6 +116,14 @@ struct fyprt_context {
     // heads; the host entry's staging (rays, pixel indices, radiance) and its two timing events
     DevBuf<Payload> rrPayload; DevBuf<float4> rrRays[2], rrHits[2], rrState; DevBuf<uint32_t> rrPixels, rrPixels2, rrCounters;
     DevBuf<float4> rrIn, rrOut; DevBuf<uint32_t> rrIndices; hipEvent_t rrEv[2] = {};
+    // denoiser (fyprt_denoise*, rt_denoise.h), all allocated on the first call and dropped by fyprt_resize: guide records (2 quads per pixel),
+    // albedo (FYPRT_BUF_ALBEDO), two ping-pong colour buffers, the host entry's output staging; its timing events and the event the front
+    // stream waits for before the next pipelined frame's Part 1 overwrites the payload the denoiser reads
+    DevBuf<float4> dnGuide, dnAlbedo, dnCol[2], dnOutRad; DevBuf<uint32_t> dnOutImg; hipEvent_t dnEv[3] = {}, dnDone = nullptr;
+    bool frameComplete = false;                // a whole frame was rendered since the last resize / scene upload / geometry update
+    uint32_t lastFrameIndex = 0;               // the frame index that frame was rendered with (the divisor of its epilogue)
+    bool albedoValid = false;                  // FYPRT_BUF_ALBEDO holds the albedo of a denoised frame
+    void release_denoise() { dnGuide.release(); dnAlbedo.release(); dnCol[0].release(); dnCol[1].release(); dnOutRad.release(); dnOutImg.release(); albedoValid = false; }
 
     int fail(int code, const std::string& m) { err = m; return code; }
     int hip(hipError_t e, const char* what) {
@@ -202,6 +218,9 @@ void fyprt_destroy(fyprt_context* c) {
     c->rrState.release(); c->rrPixels.release(); c->rrPixels2.release(); c->rrCounters.release();
     c->rrIn.release(); c->rrOut.release(); c->rrIndices.release();
     for (auto& e : c->rrEv) if (e) (void)hipEventDestroy(e);
+    c->release_denoise();
+    for (auto& e : c->dnEv) if (e) (void)hipEventDestroy(e);
+    if (c->dnDone) (void)hipEventDestroy(c->dnDone);
     for (auto& row : c->ring) for (auto& e : row) if (e) (void)hipEventDestroy(e);
     for (int k = 0; k < 2; ++k) { if (c->evFront[k]) (void)hipEventDestroy(c->evFront[k]); if (c->evDone[k]) (void)hipEventDestroy(c->evDone[k]); }
     if (c->front) (void)hipStreamDestroy(c->front);
@@ -217,6 +236,7 @@ int fyprt_resize(fyprt_context* c, uint32_t w, uint32_t h) {
     if (c->hostOnly) return c->fail(FYPRT_ESTATE, "host-only context (device -1) has no device buffers");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, sync_all(c));
+    c->release_denoise(); c->frameComplete = false;
     const size_t n = (size_t)w * h;
     HIPCHK(c, c->accum.alloc(n)); HIPCHK(c, c->image.alloc(n)); HIPCHK(c, c->payload.alloc(n)); HIPCHK(c, c->depth.alloc(n));
     HIPCHK(c, c->normalA.alloc(n)); HIPCHK(c, c->normalB.alloc(n));
@@ -408,6 +428,7 @@ int fyprt_upload_scene(fyprt_context* c, const fyprt_scene_desc* s) {
         (s->material_count && !s->materials))
         return c->fail(FYPRT_EINVAL, "fyprt_upload_scene: NULL array with non-zero count");
     if (!c->hostOnly) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c)); }
+    c->frameComplete = false;                  // the payload's triangle indices belong to the scene they were traced in (fyprt_denoise)
     const uint8_t* tb = (const uint8_t*)s->triangles;
     auto tri = [&](uint32_t i) { return reinterpret_cast<const uint32_t*>(tb + (size_t)i * s->triangle_stride); };
     for (uint32_t i = 0; i < s->triangle_count; ++i) {
@@ -617,6 +638,7 @@ int fyprt_update_vertices(fyprt_context* c, const fyprt_vertex* vertices, uint32
     if (c->hostOnly) return c->fail(FYPRT_ESTATE, "fyprt_update_vertices needs a device (host-only context)");
     if (c->prebuiltLightTrees) return c->fail(FYPRT_ESTATE, "fyprt_update_vertices: the scene was uploaded with prebuilt light trees; upload it again instead");
     HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c));
+    c->frameComplete = false;                  // new vertices may carry new texture coordinates: the last frame can no longer be denoised
     const uint32_t nT = (uint32_t)(c->topoTris.size() / 4);
     if (upload(c, c->dverts.p, vertices, c->dverts.bytes())) return FYPRT_EHIP;
     c->hostVerts.assign(vertices, vertices + vertex_count);
@@ -661,6 +683,7 @@ int fyprt_update_transforms(fyprt_context* c, const uint32_t* mesh_indices, cons
     const uint32_t nM = (uint32_t)c->topoMeshes.size(), nT = (uint32_t)(c->topoTris.size() / 4);
     for (uint32_t k = 0; k < count; ++k) if (mesh_indices[k] >= nM) return c->fail(FYPRT_EINVAL, "fyprt_update_transforms: mesh index out of range");
     HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c));
+    c->frameComplete = false;                  // as fyprt_update_vertices
     std::vector<uint8_t> touched(nM, 0);
     bool lightsMoved = false;
     for (uint32_t k = 0; k < count; ++k) {
@@ -880,6 +903,7 @@ static int enqueue_frame_impl(fyprt_context* c, const fyprt_settings* s, bool ti
         HIPCHK(c, hipStreamWaitEvent(c->front, c->evDone[par], 0));                            // frame N-2 done: its queue is free
         if (!c->lastOverlapped) HIPCHK(c, hipStreamWaitEvent(c->front, c->evDone[par ^ 1], 0));   // frame N-1 ran on `stream` alone
     }
+    c->frameComplete = false;                  // from the first enqueued work until the frame is enqueued to its end (fyprt_denoise)
     if (c->countRays && phase != 2) HIPCHK(c, hipMemsetAsync(c->rayCounter.p, 0, 256, c->stream));
     // frame 1 (or toAccumulate == false): the accumulator starts from zero (Renderer.cu:50-51) — on `stream`, which owns it
     // (the whole buffer, as the reference does, not just this context's rows: a band moved later with fyprt_set_rows must not find the
@@ -1077,6 +1101,7 @@ static int enqueue_frame_impl(fyprt_context* c, const fyprt_settings* s, bool ti
     c->ringLaunches[c->frameSerial % fyprt_context::kRing] = timed ? launches : 0;
     c->ringSplit[c->frameSerial % fyprt_context::kRing] = overlap;
     c->frameSerial++;
+    c->frameComplete = true; c->lastFrameIndex = c->frameIndex;
     if (s->to_accumulate) c->frameIndex++; else c->frameIndex = 1;       // Renderer.cu:258-261
     return FYPRT_OK;
 }
@@ -1203,6 +1228,9 @@ int fyprt_read_buffer(fyprt_context* c, int which, void* dst, size_t bytes) {
         case FYPRT_BUF_DI_PREV: src = c->diPrev.p; n = c->diPrev.bytes(); break;
         case FYPRT_BUF_GI_RESERVOIR: src = c->gi.p; n = c->gi.bytes(); break;
         case FYPRT_BUF_GI_PREV: src = c->giPrev.p; n = c->giPrev.bytes(); break;
+        case FYPRT_BUF_ALBEDO:
+            if (!c->albedoValid) return c->fail(FYPRT_ESTATE, "fyprt_read_buffer: FYPRT_BUF_ALBEDO is written by fyprt_denoise");
+            src = c->dnAlbedo.p; n = c->dnAlbedo.bytes(); break;
         default: return c->fail(FYPRT_EINVAL, "fyprt_read_buffer: unknown buffer");
     }
     if (which == FYPRT_BUF_GI_RESERVOIR || which == FYPRT_BUF_GI_PREV) {
@@ -1518,6 +1546,109 @@ int fyprt_render_rays_device(fyprt_context* c, const fyprt_settings* s, uint32_t
         if (rc != FYPRT_OK) return rc;
     }
     return FYPRT_OK;
+}
+
+// ---- denoiser (rt_denoise.h; the contract is include/fyprt.h's).  Reads the last frame's accumulation and payload, writes its own
+// buffers and the caller's outputs: no frame state moves.
+int fyprt_denoise_default_params(fyprt_denoise_params* out) {
+    if (!out) return FYPRT_EINVAL;
+    out->iterations = 5; out->sigma_luminance = 4.0f; out->sigma_plane = 0.01f; out->normal_power_log2 = 6; out->demodulate_albedo = 1;
+    return FYPRT_OK;
+}
+
+static int check_denoise(fyprt_context* c, const fyprt_denoise_params* p, const void* rgba8, const void* radiance4, bool device) {
+    const char* who = device ? "fyprt_denoise_device" : "fyprt_denoise";
+    if (!c) return FYPRT_EINVAL;
+    if (!p) return c->fail(FYPRT_EINVAL, std::string(who) + ": NULL params");
+    if (p->iterations > 8u || p->normal_power_log2 > 7u || p->demodulate_albedo > 1u || !std::isfinite(p->sigma_luminance) ||
+        !std::isfinite(p->sigma_plane) || !(p->sigma_plane > 0.0f))
+        return c->fail(FYPRT_EINVAL, std::string(who) + ": iterations 0..8, normal_power_log2 0..7, demodulate_albedo 0 / 1, finite sigmas, sigma_plane > 0");
+    if (device && (((uintptr_t)rgba8 & 3u) || ((uintptr_t)radiance4 & 15u)))
+        return c->fail(FYPRT_EINVAL, std::string(who) + ": rgba8 must be 4-byte and radiance4 16-byte aligned");
+    if (!rgba8 && !radiance4) return c->fail(FYPRT_EINVAL, std::string(who) + ": both outputs are NULL");
+    if (c->hostOnly) return c->fail(FYPRT_ESTATE, std::string(who) + ": host-only context (device -1) has no frame");
+    if (c->W == 0 || !c->frameComplete || c->part1Pending)
+        return c->fail(FYPRT_ESTATE, std::string(who) + ": no complete frame since the last fyprt_resize / fyprt_upload_scene / fyprt_update_vertices / fyprt_update_transforms");
+    if (c->comm || c->rowBegin != 0 || c->rowEnd != c->H || c->stripeRows != 0)
+        return c->fail(FYPRT_ESTATE, std::string(who) + ": the context must render every row of the frame (no band, stripes, group or communicator)");
+    return FYPRT_OK;
+}
+
+// Enqueues prepare + iterations (+ finish) on the context stream, outputs in device memory.  ev: 3 timing events or null.
+static int enqueue_denoise(fyprt_context* c, const fyprt_denoise_params* p, uint32_t* rgba8, float4* radiance4, hipEvent_t* ev, int* launched) {
+    const size_t n = (size_t)c->W * c->H;
+    if (c->dnGuide.n != 2 * n) {
+        HIPCHK(c, c->dnGuide.alloc(2 * n)); HIPCHK(c, c->dnAlbedo.alloc(n)); HIPCHK(c, c->dnCol[0].alloc(n)); HIPCHK(c, c->dnCol[1].alloc(n));
+    }
+    if (!c->dnDone) HIPCHK(c, hipEventCreateWithFlags(&c->dnDone, hipEventDisableTiming));
+    DnFrame fr{};
+    fr.W = c->W; fr.H = c->H; fr.frameIndex = (float)c->lastFrameIndex; fr.demodulate = p->demodulate_albedo;
+    fr.accum = c->accum.p; fr.guide = c->dnGuide.p; fr.albedo = c->dnAlbedo.p; fr.rgba8 = rgba8; fr.radiance4 = radiance4;
+    DevScene sc = c->dsc; sc.rayCounter = nullptr;
+    const uint32_t linear = (uint32_t)((n + 255u) / 256u);
+    if (ev) HIPCHK(c, hipEventRecord(ev[0], c->stream));
+    hipLaunchKernelGGL(k_dn_prepare, dim3(linear), dim3(256), 0, c->stream, sc, fr, c->payload.p, c->dnCol[0].p);
+    ++*launched;
+    if (ev) HIPCHK(c, hipEventRecord(ev[1], c->stream));
+    for (uint32_t k = 0; k < p->iterations; ++k) {
+        DnIter it{};
+        it.step = 1 << k; it.sigmaL = p->sigma_luminance * (1.0f / (float)(1u << k)); it.lumOn = p->sigma_luminance > 0.0f ? 1u : 0u;
+        it.sigmaPlane = p->sigma_plane; it.normalPow = p->normal_power_log2; it.last = (k + 1 == p->iterations) ? 1u : 0u;
+        const float4* in = c->dnCol[k & 1u].p; float4* out = c->dnCol[(k + 1u) & 1u].p;
+#define DN_LAUNCH(STEP) hipLaunchKernelGGL(k_dn_iterate<STEP>, dim3(dn_grid<STEP>(c->W, c->H)), dim3(256), 0, c->stream, fr, it, in, out)
+        const int staged = it.step <= RT_DN_LDS_MAX_STEP ? it.step : 0;
+        switch (staged) {
+            case 1: DN_LAUNCH(1); break;
+            case 2: DN_LAUNCH(2); break;
+            case 4: DN_LAUNCH(4); break;
+            case 8: DN_LAUNCH(8); break;
+            case 16: DN_LAUNCH(16); break;
+            case 32: DN_LAUNCH(32); break;
+            default: DN_LAUNCH(0); break;
+        }
+#undef DN_LAUNCH
+        ++*launched;
+    }
+    if (p->iterations == 0) { hipLaunchKernelGGL(k_dn_finish, dim3(linear), dim3(256), 0, c->stream, fr, c->dnCol[0].p); ++*launched; }
+    HIPCHK(c, hipGetLastError());
+    if (ev) HIPCHK(c, hipEventRecord(ev[2], c->stream));
+    // a pipelined ReSTIR DI frame enqueued next runs its Part 1 on the front stream, which overwrites the payload: after the denoiser
+    HIPCHK(c, hipEventRecord(c->dnDone, c->stream));
+    if (c->front) HIPCHK(c, hipStreamWaitEvent(c->front, c->dnDone, 0));
+    c->albedoValid = true;
+    return FYPRT_OK;
+}
+
+int fyprt_denoise(fyprt_context* c, const fyprt_denoise_params* p, uint32_t* rgba8, float* radiance4, fyprt_frame_stats* stats) {
+    { const int rc = check_denoise(c, p, rgba8, radiance4, false); if (rc != FYPRT_OK) return rc; }
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, sync_all(c));                           // as fyprt_readback: the last frame is complete on both streams
+    for (auto& e : c->dnEv) if (!e) HIPCHK(c, hipEventCreate(&e));
+    const size_t n = (size_t)c->W * c->H;
+    if (rgba8 && c->dnOutImg.n != n) HIPCHK(c, c->dnOutImg.alloc(n));
+    if (radiance4 && c->dnOutRad.n != n) HIPCHK(c, c->dnOutRad.alloc(n));
+    int launches = 0;
+    { const int rc = enqueue_denoise(c, p, rgba8 ? c->dnOutImg.p : nullptr, radiance4 ? c->dnOutRad.p : nullptr, c->dnEv, &launches); if (rc != FYPRT_OK) return rc; }
+    if (rgba8) HIPCHK(c, hipMemcpyAsync(rgba8, c->dnOutImg.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (radiance4) HIPCHK(c, hipMemcpyAsync(radiance4, c->dnOutRad.p, n * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (stats) {
+        stats->launches = (uint32_t)launches;
+        HIPCHK(c, hipEventElapsedTime(&stats->kernel_ms_part[0], c->dnEv[0], c->dnEv[1]));      // prepare
+        HIPCHK(c, hipEventElapsedTime(&stats->kernel_ms_part[1], c->dnEv[1], c->dnEv[2]));      // the iterations (or the finish kernel)
+        stats->kernel_ms = stats->kernel_ms_part[0] + stats->kernel_ms_part[1];
+    }
+    return FYPRT_OK;
+}
+
+int fyprt_denoise_device(fyprt_context* c, const fyprt_denoise_params* p, void* rgba8, void* radiance4) {
+    { const int rc = check_denoise(c, p, rgba8, radiance4, true); if (rc != FYPRT_OK) return rc; }
+    HIPCHK(c, hipSetDevice(c->device));
+    // every frame completes on the context stream (a pipelined frame's trace kernel waits there for its front part), so work enqueued on
+    // it sees the last frame whole without a host wait
+    int launches = 0;
+    return enqueue_denoise(c, p, static_cast<uint32_t*>(rgba8), static_cast<float4*>(radiance4), nullptr, &launches);
 }
 
 #include "fyprt_multi.h"

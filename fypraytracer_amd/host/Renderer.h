@@ -78,6 +78,14 @@ public:
         if (m_Present) m_Present(m_RenderImageData.data(), m_Width, m_Height);                // :256 SetData
     }
 
+    // New (no reference counterpart): the edge-avoiding denoiser over the frame Render() just produced (fyprt_denoise; nullptr = the
+    // library's defaults) into `rgba8` (width x height ABGR8) — call it after Render, before presenting.  No renderer state moves.
+    bool Denoise(const fyprt_denoise_params* params, uint32_t* rgba8) {
+        fyprt_denoise_params p;
+        if (params) p = *params; else fyprt_denoise_default_params(&p);
+        return !report(fyprt_denoise(m_Ctx, &p, rgba8, nullptr, nullptr), "fyprt_denoise");
+    }
+
     void ResetFrameIndex() { fyprt_reset_frame_index(m_Ctx); }
     RenderingSettings& GetSettings() { return m_Settings; }
     uint32_t GetCurrentFrameIndex() const { return fyprt_frame_index(m_Ctx); }

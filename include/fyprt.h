@@ -161,7 +161,9 @@ enum fyprt_buffer {
     FYPRT_BUF_DI_RESERVOIR = 5, /* ReSTIR_DI_Reservoir 20 B, after Part 1 (Renderer.h:34)         */
     FYPRT_BUF_DI_PREV = 6,      /* ... written by Part 2       (Renderer.h:35)                    */
     FYPRT_BUF_GI_RESERVOIR = 7, /* ReSTIR_GI_Reservoir 72 B    (Renderer.h:38)                    */
-    FYPRT_BUF_GI_PREV = 8       /*                             (Renderer.h:39)                    */
+    FYPRT_BUF_GI_PREV = 8,      /*                             (Renderer.h:39)                    */
+    FYPRT_BUF_ALBEDO = 9        /* float4: rgb = albedo of the primary hit, w = 1 filterable / 0 not (rgb 0 there); written by
+                                   fyprt_denoise* for the frame it denoised, FYPRT_ESTATE before (new, no reference counterpart) */
 };
 
 /* ---- lifetime (the reference has none: Renderer owns raw pointers and never frees them,
@@ -392,6 +394,50 @@ int fyprt_render_rays(fyprt_context* ctx, const fyprt_settings* settings, uint32
 int fyprt_render_rays_device(fyprt_context* ctx, const fyprt_settings* settings, uint32_t frame_index,
                              const void* rays, const uint32_t* pixel_indices, uint32_t first_index, uint32_t count,
                              void* radiance4, void* payloads);
+
+/* ================================================================================================= denoiser
+ * New (no reference counterpart): an edge-avoiding a-trous wavelet filter over the frame the context rendered last, on the device, guided
+ * by what that frame left there — FYPRT_BUF_ACCUM, the frame index it was divided by, and FYPRT_BUF_PAYLOAD (the primary hit of every
+ * pixel, written by every technique).  Call it after a frame (Renderer::Render), before presenting ("Denoiser").
+ * The contract.  All arithmetic is binary32 without contraction, in the order written; every division is a true division; subnormals are
+ * kept; max(a, b) is (a < b) ? b : a.  n = the frame index the last frame was rendered with.  Per pixel p:
+ *   c_p = accum_p.rgb / n.   filterable_p: the payload records a hit (objectIndex >= 0) whose material does not emit
+ *   (length(emission) > 0 is the frames' own test).  Misses and directly seen emitters pass through and are never a tap.
+ *   a_p = the albedo of the primary hit (material colour or re-quantised bilinear texture sample, as the frames shade it);
+ *   d_p = max(a_p, 1e-3) per channel with demodulate_albedo, else 1;  e0_p = c_p / d_p.
+ *   Iteration k = 0 .. iterations-1: step s = 2^k, sigma_k = sigma_luminance * 2^-k, h = (1/16, 1/4, 3/8, 1/4, 1/16), taps
+ *   q = p + s * (dx, dy), dy outer, dx inner, both -2..2 increasing.  A tap outside the image or not filterable is skipped.  Else
+ *     w_n = max(0, (n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z), squared normal_power_log2 times;
+ *     g = |(n_p.x D.x + n_p.y D.y) + n_p.z D.z|, D = P_q - P_p;  x_z = g / (sigma_plane * t_p), t_p the primary hit distance;
+ *     w_z = 1 / (1 + x_z x_z);   L(e) = (0.2126 e.r + 0.7152 e.g) + 0.0722 e.b;  x_l = |L(e_q) - L(e_p)| / sigma_k;
+ *     w_l = 1 / (1 + x_l x_l), or 1 when sigma_luminance <= 0;   w = ((w_n w_z) w_l) (h_dy h_dx); the centre tap has w = 3/8 * 3/8;
+ *     e_p <- (sum e_q w) / (sum w), both sums sequential in tap order from +0, per channel.
+ *   out_p = e_p * d_p (filterable) or c_p;  radiance4 = (out, accum_p.w / n);  rgba8 = the frame epilogue's tonemap / clamp / pack of it.
+ *   So iterations = 0 with demodulate_albedo = 0 returns the frame's own image bit for bit.
+ * Errors, in this order: FYPRT_EINVAL for a NULL context / params, a parameter out of range or non-finite, (device entry) rgba8 not
+ * 4-byte or radiance4 not 16-byte aligned, both outputs NULL; FYPRT_ESTATE on a host-only context, when no complete frame was rendered
+ * since the last fyprt_resize, fyprt_upload_scene, fyprt_update_vertices or fyprt_update_transforms (each of them invalidates the frame
+ * for the denoiser: the payload's triangle indices and texture coordinates belong to the scene they were traced in; materials and
+ * textures change with fyprt_upload_scene only), between the two parts of a fyprt_render_part frame, and on a context that does not
+ * render every row (a fyprt_set_rows band, fyprt_set_row_stripes, a group or communicator member).  Multi-GPU denoising needs a halo of
+ * 2 * (2^iterations - 1) rows from the neighbouring bands and is out of scope.
+ * No frame state moves: accumulation, image (internal or external), payload, depth, normals, reservoirs, frame index, frame timings and
+ * ray counters are untouched, and the frames rendered afterwards are the frames that would have been rendered without the call.  The
+ * denoiser's buffers (guide records, albedo, two colour buffers, host staging: 96 B + up to 20 B per pixel) are allocated on the first
+ * call and dropped by fyprt_resize. */
+typedef struct fyprt_denoise_params {
+    uint32_t iterations;         /* 0..8, default 5 */
+    float    sigma_luminance;    /* default 4.0; <= 0 switches the luminance term off */
+    float    sigma_plane;        /* default 0.01 (of the hit distance); > 0 and finite */
+    uint32_t normal_power_log2;  /* 0..7, default 6 (n.n' to the 64th) */
+    uint32_t demodulate_albedo;  /* 0 / 1, default 1 */
+} fyprt_denoise_params;
+int fyprt_denoise_default_params(fyprt_denoise_params* out);
+/* Host memory, blocking; width x height uint32 / float4; either output may be NULL.  `stats` may be NULL: kernel_ms = the hipEvent time
+ * over the call's kernels, launches = their number, kernel_ms_part[0] = the prepare kernel, [1] = the iterations. */
+int fyprt_denoise(fyprt_context* ctx, const fyprt_denoise_params* params, uint32_t* rgba8, float* radiance4, fyprt_frame_stats* stats);
+/* Device memory of the context's GPU, asynchronous on the context stream (fyprt_stream); it never waits on the device. */
+int fyprt_denoise_device(fyprt_context* ctx, const fyprt_denoise_params* params, void* rgba8, void* radiance4);
 
 /* ================================================================================================= multi-GPU
  * The reference renders on one GPU (Renderer.cu:13-284); there is no reference interface for this section.  It splits ONE
