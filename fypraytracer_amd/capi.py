@@ -21,6 +21,7 @@ TECHNIQUE_NAMES = ["BRUTE_FORCE", "UNIFORM_SAMPLING", "COSINE_WEIGHTED_SAMPLING"
                    "LIGHT_SOURCE_SAMPLING", "NEE", "RESTIR_DI", "RESTIR_GI"]
 
 BUF_ACCUM, BUF_IMAGE, BUF_PAYLOAD, BUF_DEPTH, BUF_NORMAL, BUF_DI, BUF_DI_PREV, BUF_GI, BUF_GI_PREV = range(9)
+BUF_TEMPORAL = 10   # 64 B per pixel: the history record the last Context.denoise_temporal* call wrote (TEMPORAL_DTYPE)
 BUF_ALBEDO = 9      # float4 per pixel: albedo of the primary hit, w = 1 filterable / 0 not; written by Context.denoise* (fyprt_denoise)
 
 # numpy views of the per-pixel records (Ray.h:13-22, ReSTIR_DI_Reservoir.cuh:9-16, ReSTIR_GI_Reservoir.cuh:9-27)
@@ -32,9 +33,13 @@ GI_DTYPE = np.dtype([("visiblePoint", "<f4", 3), ("visibleNormal", "<f4", 2), ("
                      ("sampleNormal", "<f4", 2), ("Lo", "<f4", 3), ("randSeed", "<u4"), ("samplePDF", "<f4"),
                      ("weightSample", "<f4"), ("M", "<u4"), ("weightSum", "<f4")])
 assert PAYLOAD_DTYPE.itemsize == 40 and DI_DTYPE.itemsize == 20 and GI_DTYPE.itemsize == 72
+# the temporal denoiser's history record (include/fyprt.h, "temporal denoiser"; new, no reference counterpart)
+TEMPORAL_DTYPE = np.dtype([("worldPosition", "<f4", 3), ("hitDistance", "<f4"), ("worldNormal", "<f4", 3), ("filterable", "<f4"),
+                           ("colour", "<f4", 3), ("N", "<f4"), ("m1", "<f4"), ("m2", "<f4"), ("variance", "<f4"), ("pad", "<f4")])
+assert TEMPORAL_DTYPE.itemsize == 64
 BUFFER_DTYPES = {BUF_ACCUM: np.dtype(("<f4", 4)), BUF_IMAGE: np.dtype("<u4"), BUF_PAYLOAD: PAYLOAD_DTYPE,
                  BUF_DEPTH: np.dtype("<f4"), BUF_NORMAL: np.dtype(("<f4", 2)), BUF_DI: DI_DTYPE, BUF_DI_PREV: DI_DTYPE,
-                 BUF_GI: GI_DTYPE, BUF_GI_PREV: GI_DTYPE, BUF_ALBEDO: np.dtype(("<f4", 4))}
+                 BUF_GI: GI_DTYPE, BUF_GI_PREV: GI_DTYPE, BUF_ALBEDO: np.dtype(("<f4", 4)), BUF_TEMPORAL: TEMPORAL_DTYPE}
 
 VERTEX_DTYPE = np.dtype([("position", "<f4", 3), ("normal", "<f4", 3), ("uv", "<f4", 2)])
 TRIANGLE_DTYPE = np.dtype([("v0", "<u4"), ("v1", "<u4"), ("v2", "<u4"), ("materialIndex", "<i4")])
@@ -140,6 +145,27 @@ class DenoiseParams(C.Structure):  # fyprt_denoise_params (20 B) with the librar
 assert C.sizeof(DenoiseParams) == 20
 
 
+class TemporalParams(C.Structure):  # fyprt_temporal_params (36 B) with the library's defaults (fyprt_denoise_temporal_default_params)
+    _fields_ = [("spatial", DenoiseParams), ("history_limit", C.c_uint32), ("normal_min", C.c_float), ("plane_max", C.c_float),
+                ("feedback", C.c_uint32)]
+
+    def __init__(self, **kw):
+        """Keywords: the four fields of this struct, `spatial` (a DenoiseParams), or any field of DenoiseParams (set on `spatial`)."""
+        super().__init__()
+        self.spatial = DenoiseParams()
+        self.history_limit, self.normal_min, self.plane_max, self.feedback = 32, 0.9, 0.02, 1
+        for k, v in kw.items():
+            if hasattr(self, k):
+                setattr(self, k, v)
+            elif hasattr(self.spatial, k):
+                setattr(self.spatial, k, v)
+            else:
+                raise AttributeError(k)
+
+
+assert C.sizeof(TemporalParams) == 36
+
+
 EXPORTED_SYMBOLS = [
     "fyprt_create", "fyprt_destroy", "fyprt_last_error", "fyprt_resize", "fyprt_set_rows", "fyprt_upload_scene",
     "fyprt_set_camera", "fyprt_render", "fyprt_render_async", "fyprt_synchronize", "fyprt_readback",
@@ -154,6 +180,7 @@ EXPORTED_SYMBOLS = [
     "fyprt_trace_rays", "fyprt_trace_rays_device",
     "fyprt_render_rays", "fyprt_render_rays_device",
     "fyprt_denoise_default_params", "fyprt_denoise", "fyprt_denoise_device",
+    "fyprt_denoise_temporal_default_params", "fyprt_denoise_temporal", "fyprt_denoise_temporal_device", "fyprt_denoise_temporal_reset",
 ]
 
 
@@ -216,6 +243,11 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
         lib.fyprt_denoise_default_params.argtypes = [C.POINTER(DenoiseParams)]
         lib.fyprt_denoise.argtypes = [vp, C.POINTER(DenoiseParams), vp, vp, C.POINTER(FrameStats)]
         lib.fyprt_denoise_device.argtypes = [vp, C.POINTER(DenoiseParams), vp, vp]
+    if hasattr(lib, "fyprt_denoise_temporal"):   # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
+        lib.fyprt_denoise_temporal_default_params.argtypes = [C.POINTER(TemporalParams)]
+        lib.fyprt_denoise_temporal.argtypes = [vp, C.POINTER(TemporalParams), vp, vp, C.POINTER(FrameStats)]
+        lib.fyprt_denoise_temporal_device.argtypes = [vp, C.POINTER(TemporalParams), vp, vp]
+        lib.fyprt_denoise_temporal_reset.argtypes = [vp]
     lib.fyprt_group_create.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(u32), C.POINTER(vp)]
     lib.fyprt_group_destroy.argtypes = [vp]
     lib.fyprt_group_destroy.restype = None
@@ -596,6 +628,46 @@ class Context:
         self._check(self.lib.fyprt_denoise_device(self.h, C.byref(p), C.c_void_p(image_tensor.data_ptr()) if image_tensor is not None else None,
                                                   C.c_void_p(radiance_tensor.data_ptr()) if radiance_tensor is not None else None))
         cur.wait_stream(ext)                                           # torch's later work follows the denoiser
+
+    def denoise_temporal(self, params: TemporalParams | None = None, want_radiance=True, with_stats=False):
+        """Temporal denoise of the frame rendered last (fyprt_denoise_temporal, blocking; defaults when `params` is None): reprojected
+        history, per-pixel variance, variance-guided a-trous.  Returns as denoise() does.  No frame state moves; the context's history
+        advances (read_buffer(BUF_TEMPORAL) gives the record written, denoise_temporal_reset() drops it)."""
+        p = params if params is not None else TemporalParams()
+        n = self.width * self.height
+        img = np.empty(n, dtype=np.uint32)
+        rad = np.empty((n, 4), dtype=np.float32) if want_radiance else None
+        st = FrameStats()
+        self._check(self.lib.fyprt_denoise_temporal(self.h, C.byref(p), _ptr(img), _ptr(rad), C.byref(st)))
+        out = (img.reshape(self.height, self.width), rad.reshape(self.height, self.width, 4) if want_radiance else None)
+        return out + (st,) if with_stats else out
+
+    def denoise_temporal_tensor(self, image_tensor, radiance_tensor, params: TemporalParams | None = None):
+        """denoise_temporal into device tensors (fyprt_denoise_temporal_device); tensors and stream ordering exactly as denoise_tensor."""
+        import torch
+        p = params if params is not None else TemporalParams()
+        if image_tensor is None and radiance_tensor is None:
+            raise ValueError("denoise_temporal_tensor: at least one output tensor is needed")
+        for t, dt, shape, name in ((image_tensor, torch.int32, (self.height, self.width), "image_tensor"),
+                                   (radiance_tensor, torch.float32, (self.height, self.width, 4), "radiance_tensor")):
+            if t is None:
+                continue
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"denoise_temporal_tensor: {name} must be a contiguous {dt} tensor of shape {shape}")
+            if t.device.type != "cuda" or (t.device.index if t.device.index is not None else torch.cuda.current_device()) != self.device:
+                raise ValueError(f"denoise_temporal_tensor: {name} must be on cuda:{self.device}, the context's GPU")
+        dev = (image_tensor if image_tensor is not None else radiance_tensor).device
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
+        ext.wait_stream(cur)                                           # the outputs are allocated (and their earlier uses done) before the kernels run
+        self._check(self.lib.fyprt_denoise_temporal_device(self.h, C.byref(p),
+                                                           C.c_void_p(image_tensor.data_ptr()) if image_tensor is not None else None,
+                                                           C.c_void_p(radiance_tensor.data_ptr()) if radiance_tensor is not None else None))
+        cur.wait_stream(ext)                                           # torch's later work follows the denoiser
+
+    def denoise_temporal_reset(self):
+        """Drops the temporal history (fyprt_denoise_temporal_reset): the next denoise_temporal* call behaves as a first call."""
+        self._check(self.lib.fyprt_denoise_temporal_reset(self.h))
 
     def export_lighttrees(self, mesh_count: int):
         tc, tr, bt = C.c_uint32(), C.c_uint32(), C.c_uint32()

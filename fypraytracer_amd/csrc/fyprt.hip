@@ -15,6 +15,7 @@
 #include "rt_paths.h"
 #include "rt_query.h"
 #include "rt_denoise.h"
+#include "rt_temporal.h"
 
 using namespace rt;
 
@@ -123,6 +124,13 @@ struct fyprt_context {
     bool frameComplete = false;                // a whole frame was rendered since the last resize / scene upload / geometry update
     uint32_t lastFrameIndex = 0;               // the frame index that frame was rendered with (the divisor of its epilogue)
     bool albedoValid = false;                  // FYPRT_BUF_ALBEDO holds the albedo of a denoised frame
+    // temporal denoiser (fyprt_denoise_temporal*, rt_temporal.h), allocated on the first temporal call and dropped by fyprt_resize: two
+    // history buffers (4 quads per pixel; a call reads any pixel of the old one while it writes the new one) and two variance buffers.
+    // camPV = projection x view of the camera set last, framePV = that of the camera the last frame was enqueued with, dtPV = that of the
+    // frame the last temporal call denoised (what the next one reprojects with); dtValid: dtHist[dtCur] holds a history
+    DevBuf<float4> dtHist[2]; DevBuf<float> dtVar[2]; hipEvent_t dtEv[4] = {}; int dtCur = 0; bool dtValid = false;
+    float camPV[16] = {}, framePV[16] = {}, dtPV[16] = {};
+    void release_temporal() { for (int k = 0; k < 2; ++k) { dtHist[k].release(); dtVar[k].release(); } dtValid = false; }
     void release_denoise() { dnGuide.release(); dnAlbedo.release(); dnCol[0].release(); dnCol[1].release(); dnOutRad.release(); dnOutImg.release(); albedoValid = false; }
 
     int fail(int code, const std::string& m) { err = m; return code; }
@@ -220,6 +228,8 @@ void fyprt_destroy(fyprt_context* c) {
     for (auto& e : c->rrEv) if (e) (void)hipEventDestroy(e);
     c->release_denoise();
     for (auto& e : c->dnEv) if (e) (void)hipEventDestroy(e);
+    c->release_temporal();
+    for (auto& e : c->dtEv) if (e) (void)hipEventDestroy(e);
     if (c->dnDone) (void)hipEventDestroy(c->dnDone);
     for (auto& row : c->ring) for (auto& e : row) if (e) (void)hipEventDestroy(e);
     for (int k = 0; k < 2; ++k) { if (c->evFront[k]) (void)hipEventDestroy(c->evFront[k]); if (c->evDone[k]) (void)hipEventDestroy(c->evDone[k]); }
@@ -236,7 +246,7 @@ int fyprt_resize(fyprt_context* c, uint32_t w, uint32_t h) {
     if (c->hostOnly) return c->fail(FYPRT_ESTATE, "host-only context (device -1) has no device buffers");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, sync_all(c));
-    c->release_denoise(); c->frameComplete = false;
+    c->release_denoise(); c->release_temporal(); c->frameComplete = false;
     const size_t n = (size_t)w * h;
     HIPCHK(c, c->accum.alloc(n)); HIPCHK(c, c->image.alloc(n)); HIPCHK(c, c->payload.alloc(n)); HIPCHK(c, c->depth.alloc(n));
     HIPCHK(c, c->normalA.alloc(n)); HIPCHK(c, c->normalB.alloc(n));
@@ -429,6 +439,7 @@ int fyprt_upload_scene(fyprt_context* c, const fyprt_scene_desc* s) {
         return c->fail(FYPRT_EINVAL, "fyprt_upload_scene: NULL array with non-zero count");
     if (!c->hostOnly) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c)); }
     c->frameComplete = false;                  // the payload's triangle indices belong to the scene they were traced in (fyprt_denoise)
+    c->dtValid = false;                        // world positions of another scene are not comparable (fyprt_denoise_temporal)
     const uint8_t* tb = (const uint8_t*)s->triangles;
     auto tri = [&](uint32_t i) { return reinterpret_cast<const uint32_t*>(tb + (size_t)i * s->triangle_stride); };
     for (uint32_t i = 0; i < s->triangle_count; ++i) {
@@ -639,6 +650,7 @@ int fyprt_update_vertices(fyprt_context* c, const fyprt_vertex* vertices, uint32
     if (c->prebuiltLightTrees) return c->fail(FYPRT_ESTATE, "fyprt_update_vertices: the scene was uploaded with prebuilt light trees; upload it again instead");
     HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c));
     c->frameComplete = false;                  // new vertices may carry new texture coordinates: the last frame can no longer be denoised
+    c->dtValid = false;
     const uint32_t nT = (uint32_t)(c->topoTris.size() / 4);
     if (upload(c, c->dverts.p, vertices, c->dverts.bytes())) return FYPRT_EHIP;
     c->hostVerts.assign(vertices, vertices + vertex_count);
@@ -684,6 +696,7 @@ int fyprt_update_transforms(fyprt_context* c, const uint32_t* mesh_indices, cons
     for (uint32_t k = 0; k < count; ++k) if (mesh_indices[k] >= nM) return c->fail(FYPRT_EINVAL, "fyprt_update_transforms: mesh index out of range");
     HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c));
     c->frameComplete = false;                  // as fyprt_update_vertices
+    c->dtValid = false;
     std::vector<uint8_t> touched(nM, 0);
     bool lightsMoved = false;
     for (uint32_t k = 0; k < count; ++k) {
@@ -719,6 +732,7 @@ int fyprt_set_camera(fyprt_context* c, const fyprt_camera_desc* cam) {
     std::memcpy(&d.invProj, cam->inverse_projection, 64); std::memcpy(&d.invView, cam->inverse_view, 64);
     float pv[16]; matmul_cm(cam->prev_projection, cam->prev_view, pv);
     std::memcpy(&d.prevProjView, pv, 64);
+    matmul_cm(cam->projection, cam->view, c->camPV);           // what a frame rendered with this camera leaves for fyprt_denoise_temporal
     d.position = f3{cam->position[0], cam->position[1], cam->position[2]};
     d.W = cam->viewport_width; d.H = cam->viewport_height;
     c->haveCamera = true;
@@ -904,6 +918,7 @@ static int enqueue_frame_impl(fyprt_context* c, const fyprt_settings* s, bool ti
         if (!c->lastOverlapped) HIPCHK(c, hipStreamWaitEvent(c->front, c->evDone[par ^ 1], 0));   // frame N-1 ran on `stream` alone
     }
     c->frameComplete = false;                  // from the first enqueued work until the frame is enqueued to its end (fyprt_denoise)
+    if (phase != 2) std::memcpy(c->framePV, c->camPV, 64);    // the camera this frame is rendered with (fyprt_denoise_temporal)
     if (c->countRays && phase != 2) HIPCHK(c, hipMemsetAsync(c->rayCounter.p, 0, 256, c->stream));
     // frame 1 (or toAccumulate == false): the accumulator starts from zero (Renderer.cu:50-51) — on `stream`, which owns it
     // (the whole buffer, as the reference does, not just this context's rows: a band moved later with fyprt_set_rows must not find the
@@ -1231,6 +1246,9 @@ int fyprt_read_buffer(fyprt_context* c, int which, void* dst, size_t bytes) {
         case FYPRT_BUF_ALBEDO:
             if (!c->albedoValid) return c->fail(FYPRT_ESTATE, "fyprt_read_buffer: FYPRT_BUF_ALBEDO is written by fyprt_denoise");
             src = c->dnAlbedo.p; n = c->dnAlbedo.bytes(); break;
+        case FYPRT_BUF_TEMPORAL:
+            if (!c->dtValid) return c->fail(FYPRT_ESTATE, "fyprt_read_buffer: FYPRT_BUF_TEMPORAL is written by fyprt_denoise_temporal");
+            src = c->dtHist[c->dtCur].p; n = c->dtHist[c->dtCur].bytes(); break;
         default: return c->fail(FYPRT_EINVAL, "fyprt_read_buffer: unknown buffer");
     }
     if (which == FYPRT_BUF_GI_RESERVOIR || which == FYPRT_BUF_GI_PREV) {
@@ -1649,6 +1667,124 @@ int fyprt_denoise_device(fyprt_context* c, const fyprt_denoise_params* p, void* 
     // it sees the last frame whole without a host wait
     int launches = 0;
     return enqueue_denoise(c, p, static_cast<uint32_t*>(rgba8), static_cast<float4*>(radiance4), nullptr, &launches);
+}
+
+// ---- temporal denoiser (rt_temporal.h; the contract is include/fyprt.h's).  As the spatial one it reads the last frame's accumulation
+// and payload and moves no frame state; what it keeps between calls is its own history.
+int fyprt_denoise_temporal_default_params(fyprt_temporal_params* out) {
+    if (!out) return FYPRT_EINVAL;
+    fyprt_denoise_default_params(&out->spatial);
+    out->history_limit = 32; out->normal_min = 0.9f; out->plane_max = 0.02f; out->feedback = 1;
+    return FYPRT_OK;
+}
+
+static int check_temporal(fyprt_context* c, const fyprt_temporal_params* p, const void* rgba8, const void* radiance4, bool device) {
+    const char* who = device ? "fyprt_denoise_temporal_device" : "fyprt_denoise_temporal";
+    if (!c) return FYPRT_EINVAL;
+    if (!p) return c->fail(FYPRT_EINVAL, std::string(who) + ": NULL params");
+    if (p->history_limit < 1u || p->history_limit > 256u || p->feedback > 1u || !std::isfinite(p->normal_min) || !std::isfinite(p->plane_max) ||
+        !(p->plane_max > 0.0f))
+        return c->fail(FYPRT_EINVAL, std::string(who) + ": history_limit 1..256, feedback 0 / 1, finite normal_min, finite plane_max > 0");
+    const int rc = check_denoise(c, &p->spatial, rgba8, radiance4, device);
+    if (rc != FYPRT_OK) c->err = std::string(who) + " (as fyprt_denoise): " + c->err;
+    return rc;
+}
+
+// Enqueues prepare + reproject + iterations (+ finish) on the context stream.  ev: 4 timing events or null.
+static int enqueue_temporal(fyprt_context* c, const fyprt_temporal_params* p, uint32_t* rgba8, float4* radiance4, hipEvent_t* ev, int* launched) {
+    const fyprt_denoise_params& sp = p->spatial;
+    const size_t n = (size_t)c->W * c->H;
+    if (c->dnGuide.n != 2 * n) {
+        HIPCHK(c, c->dnGuide.alloc(2 * n)); HIPCHK(c, c->dnAlbedo.alloc(n)); HIPCHK(c, c->dnCol[0].alloc(n)); HIPCHK(c, c->dnCol[1].alloc(n));
+    }
+    if (c->dtHist[0].n != 4 * n) {
+        c->dtValid = false;
+        for (int k = 0; k < 2; ++k) { HIPCHK(c, c->dtHist[k].alloc(4 * n)); HIPCHK(c, c->dtVar[k].alloc(n)); }
+    }
+    if (!c->dnDone) HIPCHK(c, hipEventCreateWithFlags(&c->dnDone, hipEventDisableTiming));
+    DnFrame fr{};
+    fr.W = c->W; fr.H = c->H; fr.frameIndex = (float)c->lastFrameIndex; fr.demodulate = sp.demodulate_albedo;
+    fr.accum = c->accum.p; fr.guide = c->dnGuide.p; fr.albedo = c->dnAlbedo.p; fr.rgba8 = rgba8; fr.radiance4 = radiance4;
+    DevScene sc = c->dsc; sc.rayCounter = nullptr;
+    const uint32_t linear = (uint32_t)((n + 255u) / 256u);
+    if (ev) HIPCHK(c, hipEventRecord(ev[0], c->stream));
+    hipLaunchKernelGGL(k_dn_prepare, dim3(linear), dim3(256), 0, c->stream, sc, fr, c->payload.p, c->dnCol[0].p);
+    ++*launched;
+    if (ev) HIPCHK(c, hipEventRecord(ev[1], c->stream));
+    DtCall tc{};
+    std::memcpy(tc.m, c->dtPV, 64);
+    tc.haveHistory = c->dtValid ? 1u : 0u; tc.limit = (float)p->history_limit; tc.normalMin = p->normal_min; tc.planeMax = p->plane_max;
+    tc.sigmaPlane = sp.sigma_plane; tc.normalPow = sp.normal_power_log2;
+    const int next = c->dtCur ^ 1;
+    float4* hist = c->dtHist[next].p;
+    hipLaunchKernelGGL(k_dt_reproject, dim3(((c->W + 15u) / 16u) * ((c->H + 15u) / 16u)), dim3(256), 0, c->stream, fr, tc, c->dnCol[0].p,
+                       c->dtHist[c->dtCur].p, hist, c->dnCol[1].p, c->dtVar[0].p);
+    ++*launched;
+    if (ev) HIPCHK(c, hipEventRecord(ev[2], c->stream));
+    for (uint32_t k = 0; k < sp.iterations; ++k) {           // colour: dnCol[1] -> [0] -> [1] ...; variance: dtVar[0] -> [1] -> [0] ...
+        DnIter it{};
+        it.step = 1 << k; it.sigmaL = sp.sigma_luminance; it.lumOn = sp.sigma_luminance > 0.0f ? 1u : 0u;
+        it.sigmaPlane = sp.sigma_plane; it.normalPow = sp.normal_power_log2; it.last = (k + 1 == sp.iterations) ? 1u : 0u;
+        const float4* in = c->dnCol[(k + 1u) & 1u].p; float4* out = c->dnCol[k & 1u].p;
+        const float* vin = c->dtVar[k & 1u].p; float* vout = c->dtVar[(k + 1u) & 1u].p;
+        float4* fb = (k == 0 && p->feedback) ? hist : nullptr;
+#define DT_LAUNCH(STEP) hipLaunchKernelGGL(k_dt_iterate<STEP>, dim3(dn_grid<STEP>(c->W, c->H)), dim3(256), 0, c->stream, fr, it, in, out, vin, vout, fb)
+        const int staged = it.step <= RT_DN_LDS_MAX_STEP ? it.step : 0;
+        switch (staged) {
+            case 1: DT_LAUNCH(1); break;
+            case 2: DT_LAUNCH(2); break;
+            case 4: DT_LAUNCH(4); break;
+            case 8: DT_LAUNCH(8); break;
+            case 16: DT_LAUNCH(16); break;
+            case 32: DT_LAUNCH(32); break;
+            default: DT_LAUNCH(0); break;
+        }
+#undef DT_LAUNCH
+        ++*launched;
+    }
+    if (sp.iterations == 0) { hipLaunchKernelGGL(k_dn_finish, dim3(linear), dim3(256), 0, c->stream, fr, c->dnCol[1].p); ++*launched; }
+    HIPCHK(c, hipGetLastError());
+    if (ev) HIPCHK(c, hipEventRecord(ev[3], c->stream));
+    HIPCHK(c, hipEventRecord(c->dnDone, c->stream));           // as enqueue_denoise: the next pipelined frame's Part 1 overwrites the payload
+    if (c->front) HIPCHK(c, hipStreamWaitEvent(c->front, c->dnDone, 0));
+    c->albedoValid = true;
+    c->dtCur = next; c->dtValid = true; std::memcpy(c->dtPV, c->framePV, 64);
+    return FYPRT_OK;
+}
+
+int fyprt_denoise_temporal(fyprt_context* c, const fyprt_temporal_params* p, uint32_t* rgba8, float* radiance4, fyprt_frame_stats* stats) {
+    { const int rc = check_temporal(c, p, rgba8, radiance4, false); if (rc != FYPRT_OK) return rc; }
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, sync_all(c));
+    for (auto& e : c->dtEv) if (!e) HIPCHK(c, hipEventCreate(&e));
+    const size_t n = (size_t)c->W * c->H;
+    if (rgba8 && c->dnOutImg.n != n) HIPCHK(c, c->dnOutImg.alloc(n));
+    if (radiance4 && c->dnOutRad.n != n) HIPCHK(c, c->dnOutRad.alloc(n));
+    int launches = 0;
+    { const int rc = enqueue_temporal(c, p, rgba8 ? c->dnOutImg.p : nullptr, radiance4 ? c->dnOutRad.p : nullptr, c->dtEv, &launches); if (rc != FYPRT_OK) return rc; }
+    if (rgba8) HIPCHK(c, hipMemcpyAsync(rgba8, c->dnOutImg.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (radiance4) HIPCHK(c, hipMemcpyAsync(radiance4, c->dnOutRad.p, n * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (stats) {
+        stats->launches = (uint32_t)launches;
+        for (int k = 0; k < 3; ++k) HIPCHK(c, hipEventElapsedTime(&stats->kernel_ms_part[k], c->dtEv[k], c->dtEv[k + 1]));   // prepare, reproject, iterations
+        stats->kernel_ms = (stats->kernel_ms_part[0] + stats->kernel_ms_part[1]) + stats->kernel_ms_part[2];
+    }
+    return FYPRT_OK;
+}
+
+int fyprt_denoise_temporal_device(fyprt_context* c, const fyprt_temporal_params* p, void* rgba8, void* radiance4) {
+    { const int rc = check_temporal(c, p, rgba8, radiance4, true); if (rc != FYPRT_OK) return rc; }
+    HIPCHK(c, hipSetDevice(c->device));
+    int launches = 0;
+    return enqueue_temporal(c, p, static_cast<uint32_t*>(rgba8), static_cast<float4*>(radiance4), nullptr, &launches);
+}
+
+int fyprt_denoise_temporal_reset(fyprt_context* c) {
+    if (!c) return FYPRT_EINVAL;
+    c->dtValid = false;
+    return FYPRT_OK;
 }
 
 #include "fyprt_multi.h"

@@ -86,6 +86,16 @@ public:
         return !report(fyprt_denoise(m_Ctx, &p, rgba8, nullptr, nullptr), "fyprt_denoise");
     }
 
+    // New (no reference counterpart): the temporal denoiser over the frame Render() just produced (fyprt_denoise_temporal; nullptr = the
+    // library's defaults) — in place of Denoise for a moving camera that renders one-sample frames.  The context keeps the history;
+    // ResetDenoiseHistory() after a camera cut (scene uploads, geometry updates and resizes drop it themselves).
+    bool DenoiseTemporal(const fyprt_temporal_params* params, uint32_t* rgba8) {
+        fyprt_temporal_params p;
+        if (params) p = *params; else fyprt_denoise_temporal_default_params(&p);
+        return !report(fyprt_denoise_temporal(m_Ctx, &p, rgba8, nullptr, nullptr), "fyprt_denoise_temporal");
+    }
+    void ResetDenoiseHistory() { fyprt_denoise_temporal_reset(m_Ctx); }
+
     void ResetFrameIndex() { fyprt_reset_frame_index(m_Ctx); }
     RenderingSettings& GetSettings() { return m_Settings; }
     uint32_t GetCurrentFrameIndex() const { return fyprt_frame_index(m_Ctx); }

@@ -162,8 +162,11 @@ enum fyprt_buffer {
     FYPRT_BUF_DI_PREV = 6,      /* ... written by Part 2       (Renderer.h:35)                    */
     FYPRT_BUF_GI_RESERVOIR = 7, /* ReSTIR_GI_Reservoir 72 B    (Renderer.h:38)                    */
     FYPRT_BUF_GI_PREV = 8,      /*                             (Renderer.h:39)                    */
-    FYPRT_BUF_ALBEDO = 9        /* float4: rgb = albedo of the primary hit, w = 1 filterable / 0 not (rgb 0 there); written by
+    FYPRT_BUF_ALBEDO = 9,       /* float4: rgb = albedo of the primary hit, w = 1 filterable / 0 not (rgb 0 there); written by
                                    fyprt_denoise* for the frame it denoised, FYPRT_ESTATE before (new, no reference counterpart) */
+    FYPRT_BUF_TEMPORAL = 10     /* 64 B: P.xyz, t | n.xyz, filterable | colour.rgb, N | m1, m2, variance, 0 — the history record the last
+                                   fyprt_denoise_temporal* call wrote; FYPRT_ESTATE before the first call and after anything that drops the
+                                   history (new, no reference counterpart) */
 };
 
 /* ---- lifetime (the reference has none: Renderer owns raw pointers and never frees them,
@@ -438,6 +441,73 @@ int fyprt_denoise_default_params(fyprt_denoise_params* out);
 int fyprt_denoise(fyprt_context* ctx, const fyprt_denoise_params* params, uint32_t* rgba8, float* radiance4, fyprt_frame_stats* stats);
 /* Device memory of the context's GPU, asynchronous on the context stream (fyprt_stream); it never waits on the device. */
 int fyprt_denoise_device(fyprt_context* ctx, const fyprt_denoise_params* params, void* rgba8, void* radiance4);
+
+/* ================================================================================================= temporal denoiser
+ * New (no reference counterpart): the denoiser above with a memory (the SVGF structure; DESIGN.md §4, "Temporal denoiser").  The context
+ * keeps a history record per pixel.  A call reprojects every primary hit of the frame rendered last into the frame the previous call
+ * denoised, blends the frame's colour and two luminance moments into what it finds there, derives a per-pixel variance, and runs the
+ * a-trous iterations with a luminance stopping function scaled by that variance.  For a moving camera that renders one-sample frames
+ * (to_accumulate = 0): call it after every frame, before presenting, in place of fyprt_denoise.
+ * The contract.  Arithmetic as for fyprt_denoise: binary32 without contraction in the order written, true divisions, a correctly rounded
+ * square root, subnormals kept, max(a, b) = (a < b) ? b : a and min(a, b) = (b < a) ? b : a.  n, c_p, filterable_p, a_p, d_p, e0_p, L(.),
+ * P_p, n_p, t_p, h, w_n and w_z are fyprt_denoise's, with params->spatial.  L_p = L(e0_p).
+ *   1. Camera.  The library keeps M = projection x view (column j = ((A.c0 B.cj.x + A.c1 B.cj.y) + A.c2 B.cj.z) + A.c3 B.cj.w, as it
+ *      forms prev_projection x prev_view) of the camera each frame was rendered with, taken when the frame (its first part) is enqueued:
+ *      a fyprt_set_camera between the frame and the call changes nothing.  A call reprojects with the M of the frame the previous temporal
+ *      call denoised (frames rendered in between without a call do not count).  The caller's prev_* matrices are not used: they belong to
+ *      ReSTIR and to the application's own commit point.
+ *   2. Reprojection, per filterable pixel when a history exists.  For r in x, y, w:
+ *        clip.r = (M.c0.r P.x + M.c1.r P.y) + (M.c2.r P.z + M.c3.r);   history only if clip.w > 0;
+ *        sx = ((clip.x / clip.w) 0.5 + 0.5) W,  sy = ((clip.y / clip.w) 0.5 + 0.5) H  (W, H converted to binary32);
+ *        history only if -1 <= sx < W and -1 <= sy < H;   x0 = floor(sx), wx = sx - x0, y0 = floor(sy), wy = sy - y0.
+ *      Taps q in the order (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1) with b = (wx or 1 - wx) * (wy or 1 - wy).  A tap is valid when
+ *      it is inside the image, its history record is filterable with N >= 1, b > 0, (n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z >=
+ *      normal_min and |(n_p.x D.x + n_p.y D.y) + n_p.z D.z| <= plane_max * t_p, D = P_q - P_p (P_q, n_q of the history record).
+ *      Over the valid taps in that order, from +0: sw = sum b, sc = sum colour_q b (per channel), s1 = sum m1_q b, s2 = sum m2_q b;
+ *      N_hist = the largest N_q.
+ *   3. Integration.  With a valid tap: N = min(N_hist + 1, history_limit);  if N = 1 (history_limit = 1) the new sample alone is taken;
+ *      otherwise a = 1 / N, h = s / sw, x = h + (x_new - h) a for the colour channels (x_new = e0_p) and the two moments (x_new = L_p and
+ *      L_p L_p).  Without one: N = 1, colour e0_p, moments (L_p, L_p L_p).  A pixel that is not filterable: N = 0, the same colour and
+ *      moments, variance 0.
+ *   4. Variance.  N >= 4: v = max(0, m2 - m1 m1).  N < 4: over the taps q = p + (dx, dy), dy outer, dx inner, both -2..2 increasing,
+ *      inside the image and filterable, with w = w_n w_z:  S0 = 1 + sum w, S1 = L_p + sum L_q w, S2 = L_p L_p + sum (L_q L_q) w (the
+ *      centre comes first with weight 1 and is not a tap), M1 = S1 / S0, M2 = S2 / S0, v = max(0, M2 - M1 M1) * (4 / N).
+ *   5. Filter.  e = the integrated colour.  Iteration k = 0 .. iterations-1 is fyprt_denoise's (step 2^k, taps, order, w_n, w_z, h)
+ *      with: vbar_p = (sum v_q g) / (sum g) over q = p + (dx, dy), dy outer, dx inner, both -1..1, inside the image and filterable (the
+ *      centre among them), g = g_dy g_dx, g = (1/4, 1/2, 1/4), both sums from +0;  x_l = |L(e_q) - L(e_p)| / (sigma_luminance *
+ *      sqrt(vbar_p) + 1e-4) (w_l = 1 when sigma_luminance <= 0);  and the variance is filtered along: v_p <- (sum v_q (w w)) / ((sum w)
+ *      (sum w)), the centre tap first in its place of the tap order with w = 3/8 * 3/8 as for the colour.
+ *   6. History written (FYPRT_BUF_TEMPORAL): P_p, t_p | n_p, filterable_p (1.0 / 0.0) | colour, N | m1, m2, the variance of step 4, 0.
+ *      The colour is the output of iteration 0 when feedback = 1 and iterations >= 1, else the integrated colour.
+ *      Output: out_p = e_p * d_p (filterable) or c_p; radiance4.w and rgba8 as fyprt_denoise forms them.
+ *   So the first call after a reset with iterations = 0 and demodulate_albedo = 0 returns the frame's own image bit for bit, and
+ *   history_limit = 1 makes every call a first call.
+ * The history is dropped — the next call behaves as a first call — by fyprt_resize, fyprt_upload_scene, fyprt_update_vertices,
+ * fyprt_update_transforms (world positions of an edited scene are not comparable) and fyprt_denoise_temporal_reset.
+ * Errors, in this order: FYPRT_EINVAL for a NULL context / params, history_limit outside 1..256, feedback > 1, normal_min or plane_max
+ * not finite, plane_max <= 0; then everything fyprt_denoise refuses, in its order, with params->spatial (its FYPRT_EINVAL cases, then
+ * its FYPRT_ESTATE cases).  Multi-GPU bands are out of scope as there.
+ * No frame state moves, as for fyprt_denoise, and the two denoisers do not disturb each other: the history lives in buffers of its own
+ * (two of 64 B and two of 4 B per pixel, allocated on the first temporal call, dropped by fyprt_resize); the guide, albedo and colour
+ * buffers of fyprt_denoise are shared scratch, and FYPRT_BUF_ALBEDO is written by either.
+ * Static cameras: techniques 0-6 seed a pixel with pixel x frame index, and to_accumulate = 0 holds the frame index at 1, so a static
+ * camera then renders the same frame every time (the reference's seeding).  The temporal variance of identical frames is zero, the
+ * luminance term shuts and the result degrades towards the unfiltered frame; use a ReSTIR technique (its seeds move on) or accumulate. */
+typedef struct fyprt_temporal_params {
+    fyprt_denoise_params spatial;   /* iterations, sigma_luminance, sigma_plane, normal_power_log2, demodulate_albedo; defaults as there */
+    uint32_t history_limit;         /* 1..256, default 32: the blend factor is never below 1 / history_limit */
+    float    normal_min;            /* default 0.9; finite */
+    float    plane_max;             /* default 0.02 (of the hit distance); > 0 and finite */
+    uint32_t feedback;              /* 0 / 1, default 1 */
+} fyprt_temporal_params;
+int fyprt_denoise_temporal_default_params(fyprt_temporal_params* out);
+/* Host memory, blocking, as fyprt_denoise.  stats: kernel_ms_part[0] = prepare, [1] = reprojection + variance, [2] = the iterations. */
+int fyprt_denoise_temporal(fyprt_context* ctx, const fyprt_temporal_params* params, uint32_t* rgba8, float* radiance4, fyprt_frame_stats* stats);
+/* Device memory, asynchronous on the context stream, as fyprt_denoise_device. */
+int fyprt_denoise_temporal_device(fyprt_context* ctx, const fyprt_temporal_params* params, void* rgba8, void* radiance4);
+/* Drops the history: the next temporal call behaves as a first call.  Call it when the scene is replaced by other means than the above
+ * or the camera cuts. */
+int fyprt_denoise_temporal_reset(fyprt_context* ctx);
 
 /* ================================================================================================= multi-GPU
  * The reference renders on one GPU (Renderer.cu:13-284); there is no reference interface for this section.  It splits ONE
