@@ -181,6 +181,7 @@ EXPORTED_SYMBOLS = [
     "fyprt_render_rays", "fyprt_render_rays_device",
     "fyprt_denoise_default_params", "fyprt_denoise", "fyprt_denoise_device",
     "fyprt_denoise_temporal_default_params", "fyprt_denoise_temporal", "fyprt_denoise_temporal_device", "fyprt_denoise_temporal_reset",
+    "fyprt_live_device_bytes",
 ]
 
 
@@ -230,6 +231,9 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.fyprt_set_ray_counting.argtypes = [vp, C.c_int]
     lib.fyprt_set_tuning.argtypes = [vp, C.c_int, C.c_int]
     lib.fyprt_version.restype = C.c_char_p
+    if hasattr(lib, "fyprt_live_device_bytes"):   # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
+        lib.fyprt_live_device_bytes.argtypes = []
+        lib.fyprt_live_device_bytes.restype = C.c_uint64
     lib.fyprt_set_object_vertices.argtypes = [vp, vp, u32, C.POINTER(u32)]
     lib.fyprt_update_transforms.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_float), u32]
     lib.fyprt_compare_image.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -726,6 +730,11 @@ class Group:
         if getattr(self, "h", None):
             self.lib.fyprt_group_destroy(self.h)
             self.h = None
+
+
+def live_device_bytes(lib=None) -> int:
+    """fyprt_live_device_bytes: device bytes the library's buffers hold right now, over every context of the process."""
+    return int((lib or load_library()).fyprt_live_device_bytes())
 
 
 def balance_rows(row_bounds, band_ms, min_rows=16, max_shift=1 << 30, lib=None):

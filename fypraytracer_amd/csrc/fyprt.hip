@@ -3,6 +3,7 @@
 // frames (the reference re-allocates and round-trips ~100 MB over PCIe per 1080p frame,
 // Renderer.cu:37-53, :70, :244-283 — SURVEY.md §8 a14).
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -30,17 +31,62 @@ namespace {
 
 thread_local std::string g_createError;
 
-bool g_hostOnlyAlloc = false;   // set while a host-only context ingests a scene (no device allocations)
+std::atomic<uint64_t> g_liveDeviceBytes{0};     // device bytes held by every DevBuf of the process (fyprt_live_device_bytes)
+
+// Move-only owner of a device allocation.  A host-only context (device -1) records the size and allocates nothing.
 template <class T> struct DevBuf {
     T* p = nullptr; size_t n = 0;
-    hipError_t alloc(size_t count) {
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { release(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; } return *this; }
+    ~DevBuf() { release(); }
+    hipError_t alloc(size_t count, bool hostOnly = false) {
         release(); n = count;
-        if (count == 0 || g_hostOnlyAlloc) return hipSuccess;
-        return hipMalloc((void**)&p, count * sizeof(T));
+        if (count == 0 || hostOnly) return hipSuccess;
+        const hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
+        if (e == hipSuccess) g_liveDeviceBytes += bytes(); else { p = nullptr; n = 0; }
+        return e;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
+    void release() { if (p) { (void)hipFree(p); g_liveDeviceBytes -= bytes(); } p = nullptr; n = 0; }
     size_t bytes() const { return n * sizeof(T); }
 };
+
+// Move-only owner of an event / a stream (created by the caller into `h`); an empty one makes no HIP call.
+template <class H, hipError_t (*Destroy)(H)> struct DevHandle {
+    H h = nullptr;
+    DevHandle() = default;
+    DevHandle(DevHandle&& o) noexcept : h(o.h) { o.h = nullptr; }
+    DevHandle& operator=(DevHandle&& o) noexcept { if (this != &o) { reset(); h = o.h; o.h = nullptr; } return *this; }
+    ~DevHandle() { reset(); }
+    void reset() { if (h) (void)Destroy(h); h = nullptr; }
+    operator H() const { return h; }
+};
+using Event = DevHandle<hipEvent_t, hipEventDestroy>;
+using Stream = DevHandle<hipStream_t, hipStreamDestroy>;
+hipError_t create(Event& e, unsigned flags = hipEventDefault) { return e.h ? hipSuccess : hipEventCreateWithFlags(&e.h, flags); }
+
+// Cached residency (workgroups per CU) of one persistent kernel, asked from the runtime once per LDS size.
+struct OccCache {
+    int blocks = 0; size_t lds = 0;
+    template <class K> int get(K kernel, size_t ldsBytes, int fallback) {
+        if (lds != ldsBytes) {
+            int n = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, kBlock, ldsBytes) != hipSuccess || n <= 0) n = fallback;
+            blocks = n; lds = ldsBytes;
+        }
+        return blocks;
+    }
+};
+
+// Tuning keys (include/fyprt.h documents them by number): names, and {default, largest accepted value} per key; the smallest is 0.
+enum TuningKey {
+    K_TILE_ORDER = 0, K_DI_WAVEFRONT = 1, K_WG_PER_CU = 2, K_SORT_TASKS = 3, K_CHUNK = 4, K_REFILL_LANES = 5, K_QUORUM_SECONDARY = 6, K_QUORUM_PRIMARY = 7,
+    K_STACK_BUDGET = 8, K_STATIC_CHUNKS = 9, K_MIN_CHUNK = 10, K_PIPELINE = 11, K_BUILDER = 12, K_SKIP_HALO_PART1 = 13, K_SETUP_FETCH = 14, K_RAY_KERNEL = 15,
+    K_TOP_NODES = 16, K_FUSED_FRAME = 17, K_SKIP_DEAD_RAYS = 18, K_GI2_MODE = 19, K_GI2_REFILL_LANES = 20, /* 21..23 reserved */ K_COUNT = 24
+};
+constexpr struct { int def, max; } kTuning[K_COUNT] = {
+    {2, 2}, {1, 1}, {0, 16}, {0, 1}, {128, 65536}, {24, 64}, {24, 64}, {32, 64}, {0, 31}, {0, 4096}, {32, 65536}, {1, 1},
+    {0, 2}, {0, 1}, {0, 2}, {0, 2}, {0, 1024}, {0, 2}, {1, 1}, {2, 2}, {48, 64}, {0, 0}, {0, 0}, {0, 0}};
 
 // host mat4 product, same operation order as the device / glm (column j = ((a0*bj.x + a1*bj.y) + a2*bj.z) + a3*bj.w)
 void matmul_cm(const float* a, const float* b, float* out) {
@@ -60,12 +106,16 @@ struct ncclUniqueIdBytes { char b[128]; };        // == ncclUniqueId (rccl.h: 12
 struct fyprt_context {
     // multi-process multi-GPU (fyprt_comm_*, fyprt_multi.h): RCCL communicator of the ranks that share the frame, every rank's band
     void* comm = nullptr; int world = 1, rank = 0; std::vector<uint32_t> bounds; int commHaloMode = 0;
-    int device = 0; hipStream_t stream = nullptr; std::string err; bool hostOnly = false;
+    int device = 0; std::string err; bool hostOnly = false;
+    // Destruction order: members go in reverse order of declaration, so the two streams are declared before every buffer and event —
+    // they are destroyed last, after what was used on them.  fyprt_destroy makes the device current first; a host-only context holds
+    // only empty owners, so its destruction makes no HIP call.
+    Stream stream;
     // ReSTIR DI frames are pipelined over two streams: Part 1 + Part-2 setup of frame N+1 (front stream) run beside the
     // persistent trace kernel of frame N (`stream`, on which every frame COMPLETES and which fyprt_stream() hands out)
-    hipStream_t front = nullptr; hipEvent_t evFront[2] = {}, evDone[2] = {}; bool lastOverlapped = false; bool ringSplit[128] = {};
+    Stream front; Event evFront[2], evDone[2]; bool lastOverlapped = false; bool ringSplit[128] = {};
     static constexpr int kRing = 128;          // frames whose per-launch hipEvents are kept (fyprt_frame_timings)
-    hipEvent_t ring[kRing][5] = {}; int ringLaunches[kRing] = {}; unsigned long long frameSerial = 0; hipEvent_t* ev = nullptr;
+    Event ring[kRing][5]; int ringLaunches[kRing] = {}; unsigned long long frameSerial = 0; Event* ev = nullptr;
     uint32_t W = 0, H = 0, frameIndex = 1, rowBegin = 0, rowEnd = 0, halo = 0; bool rowsSet = false;
     uint32_t stripeRows = 0, stripeParts = 1, stripePart = 0;       // fyprt_set_row_stripes (per-pixel techniques only)
     uint32_t commStripeRows = 0, commLastStripeRows = 0; bool commLastStriped = false;
@@ -99,39 +149,38 @@ struct fyprt_context {
     int lastLaunches = 0;
     size_t queueStride = 0;                     // float4s per task queue
     size_t sortGroups = 0;                      // setup workgroups the sort scratch is sized for (per parity)
-    int traceOcc = 0; size_t traceOccLds = 0;   // cached residency of the persistent trace kernel
-    int tuning[24] = {2, 1, 0, 0, 128, 24, 24, /*7: node-loop quorum of the primary-ray kernels*/ 32, 0, /*9: static chunks, 0 = auto*/ 0, 32, 1, 0, 0, 0, 0, /*16: top nodes kept in LDS*/ 0, /*17: fused small-scene frame*/ 0, /*18: skip dead shadow rays*/ 1, /*19: ReSTIR GI Part 2 in one launch*/ 2, /*20: its service threshold*/ 48, 0, 0, 0};   // [0] tile order  [1] DI part 2: 0 one thread per pixel, 1 wavefront queue + persistent trace  [2] persistent workgroups per CU
+    OccCache traceOcc, pathOcc, gi2Occ, queryOcc[2];   // k_di_part2_trace, k_trace_rays, k_gi2_persistent, k_query_rays<kind, false>
+    int tuning[K_COUNT];                        // by TuningKey, defaults from kTuning
     int numCUs = 256;
     // wavefront path engine (rt_paths.h): two ray lists + results (ping-pong), per-pixel path state, pixel lists, list counters
     DevBuf<float4> wfRays[2], wfHits[2], wfState; DevBuf<uint32_t> wfPixels, wfPixels2, wfCounters;
-    int pathOcc = 0; size_t pathOccLds = 0;     // cached residency of k_trace_rays
-    int gi2Occ = 0; size_t gi2OccLds = 0;       // ... of k_gi2_persistent
     DevBuf<uint32_t> refImage;                 // fyprt_compare_image's reference
     DevBuf<float4> shadowTasks; DevBuf<uint32_t> queueCounters, sortCounts, sortOffset, sortTotal, sortIndex; DevBuf<uint8_t> sortKeys; DevBuf<uint16_t> sortHist;
     // batched ray queries (fyprt_trace_rays*, rt_query.h), all allocated on the first query: their own counters ([0..4] as a frame's
     // launch, [5] low word = queue head of the persistent kernel), the host entry's staging buffers, its two timing events
-    DevBuf<unsigned long long> queryCounters; DevBuf<float4> queryRays; DevBuf<uint32_t> queryResults; hipEvent_t queryEv[2] = {};
-    int queryOcc[2] = {0, 0}; size_t queryOccLds[2] = {0, 0};     // cached residency of k_query_rays<kind, false>
+    DevBuf<unsigned long long> queryCounters; DevBuf<float4> queryRays; DevBuf<uint32_t> queryResults; Event queryEv[2];
     // radiance queries (fyprt_render_rays*, rt_query.h: k_render_rays_primary + the path stages), allocated on first use for
     // min(count, FYPRT_RENDER_RAYS_CHUNK) rays and kept: primary records, path state, ray / result lists, live lists, list counters + queue
     // heads; the host entry's staging (rays, pixel indices, radiance) and its two timing events
     DevBuf<Payload> rrPayload; DevBuf<float4> rrRays[2], rrHits[2], rrState; DevBuf<uint32_t> rrPixels, rrPixels2, rrCounters;
-    DevBuf<float4> rrIn, rrOut; DevBuf<uint32_t> rrIndices; hipEvent_t rrEv[2] = {};
+    DevBuf<float4> rrIn, rrOut; DevBuf<uint32_t> rrIndices; Event rrEv[2];
     // denoiser (fyprt_denoise*, rt_denoise.h), all allocated on the first call and dropped by fyprt_resize: guide records (2 quads per pixel),
     // albedo (FYPRT_BUF_ALBEDO), two ping-pong colour buffers, the host entry's output staging; its timing events and the event the front
     // stream waits for before the next pipelined frame's Part 1 overwrites the payload the denoiser reads
-    DevBuf<float4> dnGuide, dnAlbedo, dnCol[2], dnOutRad; DevBuf<uint32_t> dnOutImg; hipEvent_t dnEv[3] = {}, dnDone = nullptr;
+    struct Denoise { DevBuf<float4> guide, albedo, col[2], outRad; DevBuf<uint32_t> outImg; } dn; Event dnEv[3], dnDone;
     bool frameComplete = false;                // a whole frame was rendered since the last resize / scene upload / geometry update
     uint32_t lastFrameIndex = 0;               // the frame index that frame was rendered with (the divisor of its epilogue)
     bool albedoValid = false;                  // FYPRT_BUF_ALBEDO holds the albedo of a denoised frame
     // temporal denoiser (fyprt_denoise_temporal*, rt_temporal.h), allocated on the first temporal call and dropped by fyprt_resize: two
     // history buffers (4 quads per pixel; a call reads any pixel of the old one while it writes the new one) and two variance buffers.
     // camPV = projection x view of the camera set last, framePV = that of the camera the last frame was enqueued with, dtPV = that of the
-    // frame the last temporal call denoised (what the next one reprojects with); dtValid: dtHist[dtCur] holds a history
-    DevBuf<float4> dtHist[2]; DevBuf<float> dtVar[2]; hipEvent_t dtEv[4] = {}; int dtCur = 0; bool dtValid = false;
+    // frame the last temporal call denoised (what the next one reprojects with); dtValid: dt.hist[dtCur] holds a history
+    struct Temporal { DevBuf<float4> hist[2]; DevBuf<float> var[2]; } dt; Event dtEv[4]; int dtCur = 0; bool dtValid = false;
     float camPV[16] = {}, framePV[16] = {}, dtPV[16] = {};
-    void release_temporal() { for (int k = 0; k < 2; ++k) { dtHist[k].release(); dtVar[k].release(); } dtValid = false; }
-    void release_denoise() { dnGuide.release(); dnAlbedo.release(); dnCol[0].release(); dnCol[1].release(); dnOutRad.release(); dnOutImg.release(); albedoValid = false; }
+    void release_temporal() { dt = Temporal(); dtValid = false; }
+    void release_denoise() { dn = Denoise(); albedoValid = false; }
+
+    fyprt_context() { for (int k = 0; k < K_COUNT; ++k) tuning[k] = kTuning[k].def; }
 
     int fail(int code, const std::string& m) { err = m; return code; }
     int hip(hipError_t e, const char* what) {
@@ -143,6 +192,7 @@ struct fyprt_context {
 };
 
 #define HIPCHK(ctx, call) do { int _rc = (ctx)->hip((call), #call); if (_rc != FYPRT_OK) return _rc; } while (0)
+#define TRY(call) do { const int _rc = (call); if (_rc != FYPRT_OK) return _rc; } while (0)      // a call that has reported its own error
 
 static hipError_t sync_all(fyprt_context* c) {      // both streams: the front one only ever runs ahead of `stream`
     hipError_t e = c->front ? hipStreamSynchronize(c->front) : hipSuccess;
@@ -156,16 +206,55 @@ static hipError_t sync_all(fyprt_context* c) {      // both streams: the front o
 // entries of slack above the level count remain.  Never below the level count (the induction needs it), never above 31.
 static int effective_stack_budget(const fyprt_context* c) {
     const int levels = (int)c->hostBvh.levels;
-    if (c->tuning[8] > 0) return std::min((int)rth::kStackBudget, std::max(levels, c->tuning[8]));
+    if (c->tuning[K_STACK_BUDGET] > 0) return std::min((int)rth::kStackBudget, std::max(levels, c->tuning[K_STACK_BUDGET]));
     static const int kSizes[6] = {16, 17, 20, 22, 26, 32};
     int entries = 32;
     for (int i = 5; i >= 0; --i) if (kSizes[i] <= std::max(levels + 9, 16) && kSizes[i] - 1 >= levels + 4) { entries = kSizes[i]; break; }
     return std::min((int)rth::kStackBudget, std::max(levels, entries - 1));
 }
 
+static int upload(fyprt_context* c, void* dst, const void* src, size_t bytes) {
+    if (bytes == 0 || c->hostOnly) return FYPRT_OK;
+    return c->hip(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice), "hipMemcpy H2D");
+}
+// (re)allocates `b` for `count` elements and fills it from host memory / with zeros (on the context stream)
+template <class T> static int alloc_upload(fyprt_context* c, DevBuf<T>& b, const void* src, size_t count) {
+    HIPCHK(c, b.alloc(count, c->hostOnly));
+    return upload(c, b.p, src, b.bytes());
+}
+template <class T> static int alloc_zeroed(fyprt_context* c, DevBuf<T>& b, size_t count) {
+    HIPCHK(c, b.alloc(count));
+    HIPCHK(c, hipMemsetAsync(b.p, 0, b.bytes(), c->stream));
+    return FYPRT_OK;
+}
+
+// glm::length2(GetEmission()) > 0 (Scene.cpp:216), in that operation order
+static bool is_emissive(const fyprt_material& m) {
+    const float ex = m.emission_color[0] * m.emission_power, ey = m.emission_color[1] * m.emission_power, ez = m.emission_color[2] * m.emission_power;
+    return ((ex * ex + ey * ey) + ez * ez) > 0.0f;
+}
+
+// The scheduling parameters every persistent queue shares (TraceQueue, GI2Queue, ShadowQueue, QueryRays); `refillKey`: K_REFILL_LANES
+// or, for k_gi2_persistent, K_GI2_REFILL_LANES.  Static chunks, auto: two per wave — config 3 3.13 -> 3.08 ms, profiles/README.md r03.
+template <class Q> static void set_queue_params(const fyprt_context* c, Q& q, int refillKey) {
+    const int* t = c->tuning;
+    q.chunk = (uint32_t)(t[K_CHUNK] > 0 ? t[K_CHUNK] : 128);
+    q.refillLanes = (uint32_t)(t[refillKey] > 0 ? t[refillKey] : (refillKey == K_GI2_REFILL_LANES ? 48 : 24));
+    q.staticChunks = (uint32_t)(t[K_STATIC_CHUNKS] > 0 ? t[K_STATIC_CHUNKS] : 2);
+    q.minChunk = (uint32_t)(t[K_MIN_CHUNK] > 0 ? t[K_MIN_CHUNK] : q.chunk);
+}
+
+// one launch's ray counters (rays, box tests, triangle tests, hits, node visits) into part `k` of the stats and into their totals
+static void add_ray_stats(fyprt_frame_stats* s, int k, const unsigned long long* r) {
+    s->part_rays[k] = r[0]; s->part_box_tests[k] = r[1]; s->part_tri_tests[k] = r[2]; s->part_hits[k] = r[3]; s->part_node_visits[k] = r[4];
+    s->rays += r[0]; s->box_tests += r[1]; s->tri_tests += r[2]; s->hits += r[3]; s->node_visits += r[4];
+}
+
 extern "C" {
 
 void fyprt_comm_destroy(fyprt_context* c);
+
+uint64_t fyprt_live_device_bytes(void) { return g_liveDeviceBytes.load(); }
 
 const char* fyprt_version(void) { return "fyprt 0.1.0 gfx950 (wave64, LDS traversal stack, fp-contract off)"; }
 
@@ -182,7 +271,7 @@ int fyprt_create(int device_ordinal, fyprt_context** out) {
     e = hipSetDevice(device_ordinal);
     if (e != hipSuccess) { g_createError = std::string("hipSetDevice: ") + hipGetErrorString(e); return FYPRT_EHIP; }
     auto* c = new fyprt_context(); c->device = device_ordinal;
-    e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+    e = hipStreamCreateWithFlags(&c->stream.h, hipStreamNonBlocking);
     if (e != hipSuccess) { g_createError = std::string("hipStreamCreate: ") + hipGetErrorString(e); delete c; return FYPRT_EHIP; }
     {   // The front stream is created at the LOWEST priority: HIP deals the streams of one priority level round-robin over a
         // few hardware queues (GPU_MAX_HW_QUEUES, default 4), and two streams that land on the same queue run strictly one
@@ -191,13 +280,13 @@ int fyprt_create(int device_ordinal, fyprt_context** out) {
         // GPU_MAX_HW_QUEUES=8 in the environment as well, 0.98 ms with or without the per-frame gather (profiles/README.md).
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-        e = hipStreamCreateWithPriority(&c->front, hipStreamNonBlocking, lo);
+        e = hipStreamCreateWithPriority(&c->front.h, hipStreamNonBlocking, lo);
     }
-    for (int k = 0; k < 2 && e == hipSuccess; ++k) { e = hipEventCreateWithFlags(&c->evFront[k], hipEventDisableTiming); if (e == hipSuccess) e = hipEventCreateWithFlags(&c->evDone[k], hipEventDisableTiming); }
+    for (int k = 0; k < 2 && e == hipSuccess; ++k) { e = create(c->evFront[k], hipEventDisableTiming); if (e == hipSuccess) e = create(c->evDone[k], hipEventDisableTiming); }
     if (e != hipSuccess) { g_createError = std::string("front stream / events: ") + hipGetErrorString(e); delete c; return FYPRT_EHIP; }
-    for (auto& row : c->ring) for (auto& e : row) (void)hipEventCreate(&e);
+    for (auto& row : c->ring) for (auto& e : row) (void)create(e);
     { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, device_ordinal) == hipSuccess && prop.multiProcessorCount > 0) c->numCUs = prop.multiProcessorCount; }
-    if (const char* e = std::getenv("FYPRT_TOP_NODES")) c->tuning[16] = std::min(1024, std::max(0, std::atoi(e)));
+    if (const char* e = std::getenv("FYPRT_TOP_NODES")) c->tuning[K_TOP_NODES] = std::min(1024, std::max(0, std::atoi(e)));
     (void)c->queueCounters.alloc(8);          // two queues (frame parity): tail, head, pad, pad each
     (void)c->rayCounter.alloc(32);            // 4 launches x (rays, box tests, triangle tests, hits, node visits, 3 unused)
     (void)hipMemset(c->rayCounter.p, 0, 256);
@@ -207,35 +296,8 @@ int fyprt_create(int device_ordinal, fyprt_context** out) {
 
 void fyprt_destroy(fyprt_context* c) {
     if (!c) return;
-    if (c->hostOnly) { delete c; return; }
-    (void)hipSetDevice(c->device);
-    (void)sync_all(c);
-    fyprt_comm_destroy(c);
-    c->accum.release(); c->image.release(); c->payload.release(); c->depth.release(); c->normalA.release(); c->normalB.release();
-    c->di.release(); c->diPrev.release(); c->gi.release(); c->giPrev.release(); c->giHot.release(); c->drec.release(); c->dprevA.release(); c->dprevB.release();
-    c->nodes.release(); c->leafTris.release(); c->triPos.release(); c->triShade.release(); c->mats.release(); c->texTable.release();
-    for (auto& t : c->texPixels) t.release();
-    c->emissive.release(); c->lightRecs.release(); c->ltTlas.release(); c->ltBlas.release(); c->ltFirst.release(); c->ltCount.release(); c->ltRoot.release(); c->ltLeafOfTri.release();
-    c->rayCounter.release(); c->shadowTasks.release(); c->queueCounters.release(); c->refImage.release(); c->objVerts.release();
-    for (int k = 0; k < 2; ++k) { c->wfRays[k].release(); c->wfHits[k].release(); }
-    c->wfState.release(); c->wfPixels.release(); c->wfPixels2.release(); c->wfCounters.release();
-    c->sortCounts.release(); c->sortOffset.release(); c->sortTotal.release(); c->sortIndex.release(); c->sortKeys.release(); c->sortHist.release();
-    c->queryCounters.release(); c->queryRays.release(); c->queryResults.release();
-    for (auto& e : c->queryEv) if (e) (void)hipEventDestroy(e);
-    c->rrPayload.release(); for (int k = 0; k < 2; ++k) { c->rrRays[k].release(); c->rrHits[k].release(); }
-    c->rrState.release(); c->rrPixels.release(); c->rrPixels2.release(); c->rrCounters.release();
-    c->rrIn.release(); c->rrOut.release(); c->rrIndices.release();
-    for (auto& e : c->rrEv) if (e) (void)hipEventDestroy(e);
-    c->release_denoise();
-    for (auto& e : c->dnEv) if (e) (void)hipEventDestroy(e);
-    c->release_temporal();
-    for (auto& e : c->dtEv) if (e) (void)hipEventDestroy(e);
-    if (c->dnDone) (void)hipEventDestroy(c->dnDone);
-    for (auto& row : c->ring) for (auto& e : row) if (e) (void)hipEventDestroy(e);
-    for (int k = 0; k < 2; ++k) { if (c->evFront[k]) (void)hipEventDestroy(c->evFront[k]); if (c->evDone[k]) (void)hipEventDestroy(c->evDone[k]); }
-    if (c->front) (void)hipStreamDestroy(c->front);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    if (!c->hostOnly) { (void)hipSetDevice(c->device); (void)sync_all(c); fyprt_comm_destroy(c); }
+    delete c;                                  // every buffer, event and stream releases itself (order: see fyprt_context)
 }
 
 const char* fyprt_last_error(const fyprt_context* c) { return c ? c->err.c_str() : g_createError.c_str(); }
@@ -248,13 +310,11 @@ int fyprt_resize(fyprt_context* c, uint32_t w, uint32_t h) {
     HIPCHK(c, sync_all(c));
     c->release_denoise(); c->release_temporal(); c->frameComplete = false;
     const size_t n = (size_t)w * h;
-    HIPCHK(c, c->accum.alloc(n)); HIPCHK(c, c->image.alloc(n)); HIPCHK(c, c->payload.alloc(n)); HIPCHK(c, c->depth.alloc(n));
-    HIPCHK(c, c->normalA.alloc(n)); HIPCHK(c, c->normalB.alloc(n));
-    HIPCHK(c, c->di.alloc(n)); HIPCHK(c, c->diPrev.alloc(n)); HIPCHK(c, c->gi.alloc(n)); HIPCHK(c, c->giPrev.alloc(n)); HIPCHK(c, c->giHot.alloc(n * 4));
-    HIPCHK(c, hipMemsetAsync(c->giHot.p, 0, c->giHot.bytes(), c->stream));
-    HIPCHK(c, c->drec.alloc(n)); HIPCHK(c, c->dprevA.alloc(n)); HIPCHK(c, c->dprevB.alloc(n));
-    HIPCHK(c, hipMemsetAsync(c->drec.p, 0, c->drec.bytes(), c->stream)); HIPCHK(c, hipMemsetAsync(c->dprevA.p, 0, c->dprevA.bytes(), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->dprevB.p, 0, c->dprevB.bytes(), c->stream));
+    // cudaMemset(…, 0, …) of every buffer: Renderer.cu:333-355, :372, :393, :414
+    TRY(alloc_zeroed(c, c->accum, n)); TRY(alloc_zeroed(c, c->image, n)); TRY(alloc_zeroed(c, c->payload, n)); TRY(alloc_zeroed(c, c->depth, n));
+    TRY(alloc_zeroed(c, c->normalA, n)); TRY(alloc_zeroed(c, c->normalB, n));
+    TRY(alloc_zeroed(c, c->di, n)); TRY(alloc_zeroed(c, c->diPrev, n)); TRY(alloc_zeroed(c, c->gi, n)); TRY(alloc_zeroed(c, c->giPrev, n)); TRY(alloc_zeroed(c, c->giHot, n * 4));
+    TRY(alloc_zeroed(c, c->drec, n)); TRY(alloc_zeroed(c, c->dprevA, n)); TRY(alloc_zeroed(c, c->dprevB, n));
     {   // shadow-task storage: 256 slots per setup workgroup (grid padded to whole groups of 8 tile rows), + the sort scratch
         const size_t tilesX = (w + 15u) / 16u, tilesY = (h + 15u) / 16u;
         const size_t maxGroups = std::max(tilesX * ((tilesY + 7u) / 8u) * 8u, ((tilesX * tilesY + 7u) / 8u) * 8u);
@@ -266,12 +326,6 @@ int fyprt_resize(fyprt_context* c, uint32_t w, uint32_t h) {
         HIPCHK(c, c->sortCounts.alloc(2 * maxGroups)); HIPCHK(c, c->sortKeys.alloc(2 * maxGroups * 256u)); HIPCHK(c, c->sortHist.alloc(2 * maxGroups * kSortBins));
         HIPCHK(c, c->sortOffset.alloc(2 * maxGroups * kSortBins)); HIPCHK(c, c->sortTotal.alloc(2 * kSortBins)); HIPCHK(c, c->sortIndex.alloc(2 * maxGroups * 256u));
     }
-    // cudaMemset(…, 0, …) of every buffer: Renderer.cu:333-355, :372, :393, :414
-    HIPCHK(c, hipMemsetAsync(c->accum.p, 0, c->accum.bytes(), c->stream)); HIPCHK(c, hipMemsetAsync(c->image.p, 0, c->image.bytes(), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->payload.p, 0, c->payload.bytes(), c->stream)); HIPCHK(c, hipMemsetAsync(c->depth.p, 0, c->depth.bytes(), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->normalA.p, 0, c->normalA.bytes(), c->stream)); HIPCHK(c, hipMemsetAsync(c->normalB.p, 0, c->normalB.bytes(), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->di.p, 0, c->di.bytes(), c->stream)); HIPCHK(c, hipMemsetAsync(c->diPrev.p, 0, c->diPrev.bytes(), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->gi.p, 0, c->gi.bytes(), c->stream)); HIPCHK(c, hipMemsetAsync(c->giPrev.p, 0, c->giPrev.bytes(), c->stream));
     HIPCHK(c, sync_all(c));
     c->part1Pending = false;
     c->stripeRows = 0; c->stripeParts = 1; c->stripePart = 0;
@@ -310,12 +364,6 @@ int fyprt_set_row_stripes(fyprt_context* c, uint32_t stripe_rows, uint32_t parts
     return FYPRT_OK;
 }
 
-static int upload(fyprt_context* c, void* dst, const void* src, size_t bytes) {
-    if (bytes == 0 || c->hostOnly) return FYPRT_OK;
-    return c->hip(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice), "hipMemcpy H2D");
-}
-
-
 // the node array back from the device, into HOST form (rt_host.h: inner references are indices on the host, byte offsets on the device)
 static int download_nodes(fyprt_context* c) {
     if (c->hostBvh.nodes.empty()) return FYPRT_OK;
@@ -346,18 +394,15 @@ static int build_device_lbvh(fyprt_context* c, const fyprt_vertex* verts, uint32
     float lo[3] = {3.402823466e+38f, 3.402823466e+38f, 3.402823466e+38f}, hi[3] = {-3.402823466e+38f, -3.402823466e+38f, -3.402823466e+38f};
     for (uint32_t i = 0; i < nV; ++i) for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], verts[i].position[a]); hi[a] = std::max(hi[a], verts[i].position[a]); }
     float3 l3 = make_float3(lo[0], lo[1], lo[2]), ie = make_float3(hi[0] > lo[0] ? 1.0f / (hi[0] - lo[0]) : 0.0f, hi[1] > lo[1] ? 1.0f / (hi[1] - lo[1]) : 0.0f, hi[2] > lo[2] ? 1.0f / (hi[2] - lo[2]) : 0.0f);
-    struct Temps {                      // scratch of the build, freed on every way out
-        DevBuf<unsigned long long> keysA, keysB; DevBuf<uint32_t> valsA, valsB, parentOfNode, parentOfLeaf, arrived; DevBuf<float> box; DevBuf<RadixNode> radix; DevBuf<CollapseItem> qA, qB; DevBuf<uint32_t> counters; DevBuf<float4> wide; DevBuf<uint8_t> temp;
-        DevBuf<uint32_t> clA, clB, nearest; DevBuf<uint8_t> keep, selTemp;                          // PLOC
-        ~Temps() { clA.release(); clB.release(); nearest.release(); keep.release(); selTemp.release(); keysA.release(); keysB.release(); valsA.release(); valsB.release(); parentOfNode.release(); parentOfLeaf.release(); arrived.release(); box.release(); radix.release(); qA.release(); qB.release(); counters.release(); wide.release(); temp.release(); }
-    } t;
-    auto &keysA = t.keysA, &keysB = t.keysB; auto &valsA = t.valsA, &valsB = t.valsB; auto& radix = t.radix;
+    // scratch of the build, freed on every way out
+    DevBuf<unsigned long long> keysA, keysB; DevBuf<uint32_t> valsA, valsB, parentOfNode, parentOfLeaf, arrived; DevBuf<float> box; DevBuf<RadixNode> radix; DevBuf<CollapseItem> qA, qB; DevBuf<uint32_t> counters; DevBuf<float4> wide; DevBuf<uint8_t> temp;
+    DevBuf<uint32_t> clA, clB, nearest; DevBuf<uint8_t> keep, selTemp;                          // PLOC
     if (!ploc) {
-        HIPCHK(c, t.parentOfNode.alloc(nT)); HIPCHK(c, t.parentOfLeaf.alloc(nT)); HIPCHK(c, t.arrived.alloc(nT)); HIPCHK(c, t.box.alloc((size_t)nT * 6));
-        HIPCHK(c, hipMemsetAsync(t.arrived.p, 0, (size_t)nT * 4, c->stream));
+        HIPCHK(c, parentOfNode.alloc(nT)); HIPCHK(c, parentOfLeaf.alloc(nT)); HIPCHK(c, arrived.alloc(nT)); HIPCHK(c, box.alloc((size_t)nT * 6));
+        HIPCHK(c, hipMemsetAsync(arrived.p, 0, (size_t)nT * 4, c->stream));
     } else {
-        HIPCHK(c, t.box.alloc((size_t)nT * 12)); HIPCHK(c, t.clA.alloc(nT)); HIPCHK(c, t.clB.alloc(nT)); HIPCHK(c, t.nearest.alloc(nT)); HIPCHK(c, t.keep.alloc(nT));
-    } auto &qA = t.qA, &qB = t.qB; auto& counters = t.counters; auto& wide = t.wide; auto& temp = t.temp;
+        HIPCHK(c, box.alloc((size_t)nT * 12)); HIPCHK(c, clA.alloc(nT)); HIPCHK(c, clB.alloc(nT)); HIPCHK(c, nearest.alloc(nT)); HIPCHK(c, keep.alloc(nT));
+    }
     HIPCHK(c, keysA.alloc(nT)); HIPCHK(c, keysB.alloc(nT)); HIPCHK(c, valsA.alloc(nT)); HIPCHK(c, valsB.alloc(nT)); HIPCHK(c, radix.alloc(nT)); HIPCHK(c, qA.alloc(nT)); HIPCHK(c, qB.alloc(nT));
     HIPCHK(c, counters.alloc(4)); HIPCHK(c, wide.alloc((size_t)nT * 4));
     hipLaunchKernelGGL(k_lbvh_keys, dim3((nT + 255u) / 256u), dim3(256), 0, c->stream, c->triPos.p, nT, l3, ie, keysA.p, valsA.p);
@@ -367,25 +412,25 @@ static int build_device_lbvh(fyprt_context* c, const fyprt_vertex* verts, uint32
     HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(temp.p, tempBytes, keysA.p, keysB.p, valsA.p, valsB.p, (int)nT, 0, 63, c->stream));
     uint32_t rootNode = 0;
     if (!ploc) {
-        hipLaunchKernelGGL(k_lbvh_radix, dim3((nT + 255u) / 256u), dim3(256), 0, c->stream, keysB.p, (int)nT, radix.p, t.parentOfNode.p, t.parentOfLeaf.p);
-        hipLaunchKernelGGL(k_lbvh_boxes, dim3((nT + 255u) / 256u), dim3(256), 0, c->stream, radix.p, t.parentOfNode.p, t.parentOfLeaf.p, valsB.p, c->triPos.p, nT, t.arrived.p, t.box.p);
+        hipLaunchKernelGGL(k_lbvh_radix, dim3((nT + 255u) / 256u), dim3(256), 0, c->stream, keysB.p, (int)nT, radix.p, parentOfNode.p, parentOfLeaf.p);
+        hipLaunchKernelGGL(k_lbvh_boxes, dim3((nT + 255u) / 256u), dim3(256), 0, c->stream, radix.p, parentOfNode.p, parentOfLeaf.p, valsB.p, c->triPos.p, nT, arrived.p, box.p);
     } else {
         // PLOC rounds over the sorted order (rt_lbvh.h).  Every round has at least one mutual pair (the pair of globally smallest
         // union), real scenes lose 20-35 % of their clusters per round (54 rounds for 1 M triangles).  A round over a LONG list
         // that loses less than 1/16 is followed by a forced one (neighbours i, i ^ 1 merge), which halves the list, so degenerate
         // input cannot take O(n) rounds of O(n) work; short lists (the top of the tree, where quality counts most) are never forced.
         const int radius = std::min(kPlocMaxRadius, std::max(1, env_int("FYPRT_PLOC_RADIUS", 16)));
-        hipLaunchKernelGGL(k_ploc_leaves, dim3((nT + 255u) / 256u), dim3(256), 0, c->stream, valsB.p, c->triPos.p, nT, t.box.p, t.clA.p);
+        hipLaunchKernelGGL(k_ploc_leaves, dim3((nT + 255u) / 256u), dim3(256), 0, c->stream, valsB.p, c->triPos.p, nT, box.p, clA.p);
         HIPCHK(c, hipMemsetAsync(counters.p + 2, 0, 8, c->stream));                     // [2] binary nodes allocated, [3] clusters kept by the compaction
         size_t selBytes = 0;
-        HIPCHK(c, hipcub::DeviceSelect::Flagged(nullptr, selBytes, t.clB.p, t.keep.p, t.clA.p, counters.p + 3, (int)nT, c->stream));
-        auto& selTemp = t.selTemp; HIPCHK(c, selTemp.alloc(selBytes));
-        uint32_t n = nT; uint32_t* cur = t.clA.p; uint32_t* merged = t.clB.p; int force = 0, rounds = 0;
+        HIPCHK(c, hipcub::DeviceSelect::Flagged(nullptr, selBytes, clB.p, keep.p, clA.p, counters.p + 3, (int)nT, c->stream));
+        HIPCHK(c, selTemp.alloc(selBytes));
+        uint32_t n = nT; uint32_t* cur = clA.p; uint32_t* merged = clB.p; int force = 0, rounds = 0;
         while (n > 1) {
             const dim3 g((n + kPlocBlock - 1) / kPlocBlock);
-            hipLaunchKernelGGL(k_ploc_nearest, g, dim3(kPlocBlock), 0, c->stream, (const uint32_t*)cur, n, (const float*)t.box.p, nT, radius, force, t.nearest.p);
-            hipLaunchKernelGGL(k_ploc_merge, g, dim3(kPlocBlock), 0, c->stream, (const uint32_t*)cur, (const uint32_t*)t.nearest.p, n, nT, radix.p, t.box.p, counters.p + 2, merged, t.keep.p);
-            hipError_t e = hipcub::DeviceSelect::Flagged(selTemp.p, selBytes, merged, t.keep.p, cur, counters.p + 3, (int)n, c->stream);     // back into `cur`, order kept
+            hipLaunchKernelGGL(k_ploc_nearest, g, dim3(kPlocBlock), 0, c->stream, (const uint32_t*)cur, n, (const float*)box.p, nT, radius, force, nearest.p);
+            hipLaunchKernelGGL(k_ploc_merge, g, dim3(kPlocBlock), 0, c->stream, (const uint32_t*)cur, (const uint32_t*)nearest.p, n, nT, radix.p, box.p, counters.p + 2, merged, keep.p);
+            hipError_t e = hipcub::DeviceSelect::Flagged(selTemp.p, selBytes, merged, keep.p, cur, counters.p + 3, (int)n, c->stream);     // back into `cur`, order kept
             uint32_t kept = 0;
             if (e == hipSuccess) e = hipMemcpyAsync(&kept, counters.p + 3, 4, hipMemcpyDeviceToHost, c->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -407,7 +452,7 @@ static int build_device_lbvh(fyprt_context* c, const fyprt_vertex* verts, uint32
     uint32_t nIn = 1, total = 1;
     CollapseItem *in = qA.p, *out = qB.p;
     while (nIn) {
-        hipLaunchKernelGGL(k_lbvh_collapse, dim3((nIn + 127u) / 128u), dim3(128), 0, c->stream, (const RadixNode*)radix.p, (const float*)t.box.p, (const uint32_t*)valsB.p, (const CollapseItem*)in, nIn, out, counters.p, wide.p, c->leafTris.p);
+        hipLaunchKernelGGL(k_lbvh_collapse, dim3((nIn + 127u) / 128u), dim3(128), 0, c->stream, (const RadixNode*)radix.p, (const float*)box.p, (const uint32_t*)valsB.p, (const CollapseItem*)in, nIn, out, counters.p, wide.p, c->leafTris.p);
         HIPCHK(c, hipMemcpyAsync(h_counters, counters.p, 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         levelFirst.push_back(total);
@@ -430,6 +475,32 @@ static int build_device_lbvh(fyprt_context* c, const fyprt_vertex* verts, uint32
     b.nodes.resize(total); b.tris.resize(nT); b.rootRef = 0; b.levels = nLevels;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return download_nodes(c);                                                                        // topology + meta: the level grouping needs it
+}
+
+// The host light trees (c->hostLt) onto the device, with the emitter -> TLAS-leaf table, and into the scene descriptor.
+static int upload_light_trees(fyprt_context* c, uint32_t nT, uint32_t nM) {
+    const rth::LightTrees& lt = c->hostLt;
+    static_assert(sizeof(DevLTNode) == sizeof(fyprt_lighttree_node), "light tree node layout");
+    TRY(alloc_upload(c, c->ltTlas, lt.tlas.data(), lt.tlas.size())); TRY(alloc_upload(c, c->ltBlas, lt.blas.data(), lt.blas.size()));
+    TRY(alloc_upload(c, c->ltFirst, lt.first.data(), nM)); TRY(alloc_upload(c, c->ltCount, lt.count.data(), nM)); TRY(alloc_upload(c, c->ltRoot, lt.root.data(), nM));
+    // ComputeDirectEmitterPMF (LightTree.cu:170-199) starts with a linear search for the first TLAS leaf whose mesh tree
+    // holds the emitter; the answer does not depend on the shading point, so it is tabled per triangle here (same search
+    // order: first match wins).
+    std::vector<uint32_t> leafOfTri(nT, ~0u);
+    for (uint32_t i = 0; i < (uint32_t)lt.tlas.size(); ++i) {
+        if (!lt.tlas[i].is_leaf) continue;
+        const uint32_t mesh = lt.tlas[i].right_or_emitter;
+        if (mesh >= nM) continue;
+        for (uint32_t j = 0; j < lt.count[mesh]; ++j) {
+            const fyprt_lighttree_node& n = lt.blas[lt.first[mesh] + j];
+            if (n.is_leaf && n.right_or_emitter < nT && leafOfTri[n.right_or_emitter] == ~0u) leafOfTri[n.right_or_emitter] = i;
+        }
+    }
+    TRY(alloc_upload(c, c->ltLeafOfTri, leafOfTri.data(), nT));
+    DevScene& d = c->dsc;
+    d.ltLeafOfTri = c->ltLeafOfTri.p; d.ltTlas = c->ltTlas.p; d.ltTlasCount = (uint32_t)lt.tlas.size(); d.ltTlasRoot = lt.tlasRoot;
+    d.ltBlas = c->ltBlas.p; d.ltFirst = c->ltFirst.p; d.ltCount = c->ltCount.p; d.ltRoot = c->ltRoot.p;
+    return FYPRT_OK;
 }
 
 int fyprt_upload_scene(fyprt_context* c, const fyprt_scene_desc* s) {
@@ -455,22 +526,20 @@ int fyprt_upload_scene(fyprt_context* c, const fyprt_scene_desc* s) {
         covered += me.triangle_count;
     }
     if (covered != s->triangle_count) return c->fail(FYPRT_EINVAL, "fyprt_upload_scene: meshes must partition the triangle list");
-    struct HostOnlyGuard { bool prev; explicit HostOnlyGuard(bool on) : prev(g_hostOnlyAlloc) { g_hostOnlyAlloc = on; } ~HostOnlyGuard() { g_hostOnlyAlloc = prev; } } guard(c->hostOnly);
     // acceleration structure (ours): built on the host (binned SAH + collapse, bvh_build.cpp) or, with tuning key 12, on the
     // device (LBVH + collapse, rt_lbvh.h — further down, once the per-triangle records are on the device)
-    bool deviceBuild = !c->hostOnly && c->tuning[12] != 0 && s->triangle_count > 4;
+    bool deviceBuild = !c->hostOnly && c->tuning[K_BUILDER] != 0 && s->triangle_count > 4;
     auto hostBuild = [&]() -> int {
         rth::BuildSceneBVH(s->vertices, tb, s->triangle_stride, s->meshes, s->mesh_count, c->hostBvh);
         if (c->hostBvh.levels > rth::kStackBudget || c->hostBvh.nodes.size() >= (size_t)rth::kMaxNodes)
             return c->fail(FYPRT_EINVAL, "fyprt_upload_scene: acceleration structure (" + std::to_string(c->hostBvh.levels) + " levels, " +
                            std::to_string(c->hostBvh.nodes.size()) + " nodes) exceeds the traversal stack / node index range");
-        HIPCHK(c, c->nodes.alloc(c->hostBvh.nodes.size() * 4)); HIPCHK(c, c->leafTris.alloc(c->hostBvh.tris.size() * 3));
         std::vector<rth::Node> dn;                                        // the array in device form (inner references = byte offsets)
         if (!c->hostOnly) { dn = c->hostBvh.nodes; rth::nodes_to_device_form(dn.data(), dn.size()); }
-        if (upload(c, c->nodes.p, dn.data(), c->nodes.bytes()) || upload(c, c->leafTris.p, c->hostBvh.tris.data(), c->leafTris.bytes())) return FYPRT_EHIP;
-        return FYPRT_OK;
+        TRY(alloc_upload(c, c->nodes, dn.data(), c->hostBvh.nodes.size() * 4));
+        return alloc_upload(c, c->leafTris, c->hostBvh.tris.data(), c->hostBvh.tris.size() * 3);
     };
-    if (!deviceBuild) { const int rc = hostBuild(); if (rc != FYPRT_OK) return rc; }
+    if (!deviceBuild) TRY(hostBuild());
     // per-triangle gather records
     const uint32_t nT = s->triangle_count;
     std::vector<float> pos((size_t)nT * 12), shade((size_t)nT * 16);
@@ -487,16 +556,15 @@ int fyprt_upload_scene(fyprt_context* c, const fyprt_scene_desc* s) {
         q[8] = cc.normal[0]; q[9] = cc.normal[1]; q[10] = cc.normal[2]; q[11] = b.uv[0];
         q[12] = b.uv[1]; q[13] = cc.uv[0]; q[14] = cc.uv[1]; q[15] = matBits;
     }
-    HIPCHK(c, c->triPos.alloc((size_t)nT * 3)); HIPCHK(c, c->triShade.alloc((size_t)nT * 4));
-    if (upload(c, c->triPos.p, pos.data(), c->triPos.bytes()) || upload(c, c->triShade.p, shade.data(), c->triShade.bytes())) return FYPRT_EHIP;
+    TRY(alloc_upload(c, c->triPos, pos.data(), (size_t)nT * 3)); TRY(alloc_upload(c, c->triShade, shade.data(), (size_t)nT * 4));
     // refit support: vertices + per-triangle indices on the device, nodes grouped by level (levels = 1 first)
     c->vertexCount = s->vertex_count; c->hostBvhStale = false;
     c->hostVerts.assign(s->vertices, s->vertices + s->vertex_count); c->objVerts.release(); c->meshFirstVertex.clear();
     c->topoTris.resize((size_t)nT * 4);
     for (uint32_t i = 0; i < nT; ++i) std::memcpy(&c->topoTris[(size_t)i * 4], tri(i), 16);
     if (deviceBuild) {
-        const int rc = build_device_lbvh(c, s->vertices, s->vertex_count, nT, c->tuning[12] == 2);
-        if (rc == kLbvhTooDeep) { deviceBuild = false; const int rc2 = hostBuild(); if (rc2 != FYPRT_OK) return rc2; }   // > 31 wide levels: the host builder bounds them
+        const int rc = build_device_lbvh(c, s->vertices, s->vertex_count, nT, c->tuning[K_BUILDER] == 2);
+        if (rc == kLbvhTooDeep) { deviceBuild = false; TRY(hostBuild()); }   // > 31 wide levels: the host builder bounds them
         else if (rc != FYPRT_OK) return rc;
     }
     c->topoMeshes.assign(s->meshes, s->meshes + s->mesh_count); c->topoMats.assign(s->materials, s->materials + s->material_count);
@@ -509,15 +577,13 @@ int fyprt_upload_scene(fyprt_context* c, const fyprt_scene_desc* s) {
         for (uint32_t l = 1; l <= L + 1; ++l) c->levelOffset[l] += c->levelOffset[l - 1];      // levelOffset[l] = first slot of level l (1-based levels)
         std::vector<uint32_t> order(hn.size()), fill(c->levelOffset.begin(), c->levelOffset.end());
         for (uint32_t i = 0; i < (uint32_t)hn.size(); ++i) order[fill[hn[i].meta >> 3]++] = i;
-        HIPCHK(c, c->dverts.alloc(s->vertex_count)); HIPCHK(c, c->triIdx.alloc(nT)); HIPCHK(c, c->levelNodes.alloc(order.size())); HIPCHK(c, c->nodeBox.alloc(hn.size() * 2));
-        if (upload(c, c->dverts.p, s->vertices, c->dverts.bytes()) || upload(c, c->triIdx.p, c->topoTris.data(), c->triIdx.bytes()) ||
-            upload(c, c->levelNodes.p, order.data(), c->levelNodes.bytes())) return FYPRT_EHIP;
+        TRY(alloc_upload(c, c->dverts, s->vertices, s->vertex_count)); TRY(alloc_upload(c, c->triIdx, c->topoTris.data(), nT));
+        TRY(alloc_upload(c, c->levelNodes, order.data(), order.size())); HIPCHK(c, c->nodeBox.alloc(hn.size() * 2, c->hostOnly));
     }
     if (deviceBuild) {                     // the device builder leaves boxes and quantisation to the refit pass
-        const int rc = run_refit(c);
-        if (rc != FYPRT_OK) return rc;
+        TRY(run_refit(c));
         HIPCHK(c, sync_all(c));
-        { const int rc2 = download_nodes(c); if (rc2 != FYPRT_OK) return rc2; }
+        TRY(download_nodes(c));
         HIPCHK(c, hipMemcpy(c->hostBvh.tris.data(), c->leafTris.p, c->hostBvh.tris.size() * 48, hipMemcpyDeviceToHost));
     }
     // materials (Material.cuh:7-16 -> 3 quads)
@@ -530,31 +596,25 @@ int fyprt_upload_scene(fyprt_context* c, const fyprt_scene_desc* s) {
         std::memcpy(&q[3], &info, 4);
         q[4] = m.roughness; q[5] = m.metallic; q[6] = m.emission_power;
         q[8] = m.emission_color[0]; q[9] = m.emission_color[1]; q[10] = m.emission_color[2];
-        const float ex = m.emission_color[0] * m.emission_power, ey = m.emission_color[1] * m.emission_power, ez = m.emission_color[2] * m.emission_power;
-        emissiveMat[i] = ((ex * ex + ey * ey) + ez * ez) > 0.0f;       // glm::length2(GetEmission()) > 0 (Scene.cpp:216)
+        emissiveMat[i] = is_emissive(m);
     }
-    HIPCHK(c, c->mats.alloc((size_t)s->material_count * 3));
-    if (upload(c, c->mats.p, mats.data(), c->mats.bytes())) return FYPRT_EHIP;
+    TRY(alloc_upload(c, c->mats, mats.data(), (size_t)s->material_count * 3));
     // textures
-    for (auto& t : c->texPixels) t.release();
-    c->texPixels.assign(s->texture_count, DevBuf<uint32_t>());
+    c->texPixels.clear(); c->texPixels.resize(s->texture_count);
     std::vector<DevTexture> tt(s->texture_count);
     for (uint32_t i = 0; i < s->texture_count; ++i) {
         const fyprt_texture& t = s->textures[i];
         if (!t.pixels || t.width == 0 || t.height == 0) return c->fail(FYPRT_EINVAL, "fyprt_upload_scene: empty texture");
-        HIPCHK(c, c->texPixels[i].alloc((size_t)t.width * t.height));
-        if (upload(c, c->texPixels[i].p, t.pixels, c->texPixels[i].bytes())) return FYPRT_EHIP;
+        TRY(alloc_upload(c, c->texPixels[i], t.pixels, (size_t)t.width * t.height));
         tt[i] = DevTexture{c->texPixels[i].p, t.width, t.height, 0};
     }
-    HIPCHK(c, c->texTable.alloc(s->texture_count));
-    if (upload(c, c->texTable.p, tt.data(), c->texTable.bytes())) return FYPRT_EHIP;
+    TRY(alloc_upload(c, c->texTable, tt.data(), s->texture_count));
     // emissive list (Scene::InitSceneEmissiveTriangles, Scene.cpp:209-221)
     std::vector<uint32_t> em;
     if (s->emissive_triangles) em.assign(s->emissive_triangles, s->emissive_triangles + s->emissive_count);
     else for (uint32_t i = 0; i < nT; ++i) if (emissiveMat[tri(i)[3]]) em.push_back(i);
     for (uint32_t e : em) if (e >= nT) return c->fail(FYPRT_EINVAL, "fyprt_upload_scene: emissive triangle index out of range");
-    HIPCHK(c, c->emissive.alloc(em.size()));
-    if (upload(c, c->emissive.p, em.data(), c->emissive.bytes())) return FYPRT_EHIP;
+    TRY(alloc_upload(c, c->emissive, em.data(), em.size()));
     // light trees: prebuilt (reference shape) or ours
     rth::LightTrees& lt = c->hostLt; lt = rth::LightTrees();
     c->meshCount = s->mesh_count;
@@ -568,37 +628,14 @@ int fyprt_upload_scene(fyprt_context* c, const fyprt_scene_desc* s) {
     } else {
         rth::BuildLightTrees(s->vertices, tb, s->triangle_stride, s->meshes, s->mesh_count, s->materials, lt);
     }
-    static_assert(sizeof(DevLTNode) == sizeof(fyprt_lighttree_node), "light tree node layout");
-    HIPCHK(c, c->ltTlas.alloc(lt.tlas.size())); HIPCHK(c, c->ltBlas.alloc(lt.blas.size()));
-    HIPCHK(c, c->ltFirst.alloc(s->mesh_count)); HIPCHK(c, c->ltCount.alloc(s->mesh_count)); HIPCHK(c, c->ltRoot.alloc(s->mesh_count));
-    if (upload(c, c->ltTlas.p, lt.tlas.data(), c->ltTlas.bytes()) || upload(c, c->ltBlas.p, lt.blas.data(), c->ltBlas.bytes()) ||
-        upload(c, c->ltFirst.p, lt.first.data(), c->ltFirst.bytes()) || upload(c, c->ltCount.p, lt.count.data(), c->ltCount.bytes()) ||
-        upload(c, c->ltRoot.p, lt.root.data(), c->ltRoot.bytes())) return FYPRT_EHIP;
-    // ComputeDirectEmitterPMF (LightTree.cu:170-199) starts with a linear search for the first TLAS leaf whose mesh tree
-    // holds the emitter; the answer does not depend on the shading point, so it is tabled per triangle here (same search
-    // order: first match wins).
-    std::vector<uint32_t> leafOfTri(nT, ~0u);
-    for (uint32_t i = 0; i < (uint32_t)lt.tlas.size(); ++i) {
-        if (!lt.tlas[i].is_leaf) continue;
-        const uint32_t mesh = lt.tlas[i].right_or_emitter;
-        if (mesh >= s->mesh_count) continue;
-        for (uint32_t j = 0; j < lt.count[mesh]; ++j) {
-            const fyprt_lighttree_node& n = lt.blas[lt.first[mesh] + j];
-            if (n.is_leaf && n.right_or_emitter < nT && leafOfTri[n.right_or_emitter] == ~0u) leafOfTri[n.right_or_emitter] = i;
-        }
-    }
-    HIPCHK(c, c->ltLeafOfTri.alloc(nT));
-    if (upload(c, c->ltLeafOfTri.p, leafOfTri.data(), c->ltLeafOfTri.bytes())) return FYPRT_EHIP;
+    TRY(upload_light_trees(c, nT, s->mesh_count));
     DevScene& d = c->dsc;
-    d.ltLeafOfTri = c->ltLeafOfTri.p;
     d.nodes = c->nodes.p; d.leafTris = c->leafTris.p; d.rootRef = rth::device_ref(c->hostBvh.rootRef); d.triCount = nT;
     d.triPos = c->triPos.p; d.triShade = c->triShade.p; d.mats = c->mats.p; d.textures = c->texTable.p; d.textureCount = s->texture_count;
     d.emissive = c->emissive.p; d.emissiveCount = (uint32_t)em.size();
-    d.ltTlas = c->ltTlas.p; d.ltTlasCount = (uint32_t)lt.tlas.size(); d.ltTlasRoot = lt.tlasRoot;
-    d.ltBlas = c->ltBlas.p; d.ltFirst = c->ltFirst.p; d.ltCount = c->ltCount.p; d.ltRoot = c->ltRoot.p;
     d.rayCounter = nullptr;
     // per-light records for ReSTIR DI, computed on the device with the kernels' own arithmetic
-    HIPCHK(c, c->lightRecs.alloc(em.size() * 3));
+    HIPCHK(c, c->lightRecs.alloc(em.size() * 3, c->hostOnly));
     d.lightRecs = c->lightRecs.p;
     if (!c->hostOnly && !em.empty()) {
         hipLaunchKernelGGL(k_build_light_records, dim3(((uint32_t)em.size() + 255u) / 256u), dim3(256), 0, c->stream, d, c->lightRecs.p);
@@ -616,27 +653,7 @@ static int rebuild_light_trees(fyprt_context* c, const fyprt_vertex* verts, cons
     if (!touched) lt = rth::LightTrees();
     const uint32_t nT = (uint32_t)(c->topoTris.size() / 4), nM = (uint32_t)c->topoMeshes.size();
     rth::BuildLightTrees(verts, (const uint8_t*)c->topoTris.data(), 16, c->topoMeshes.data(), nM, c->topoMats.data(), lt, touched);
-    HIPCHK(c, c->ltTlas.alloc(lt.tlas.size())); HIPCHK(c, c->ltBlas.alloc(lt.blas.size()));
-    HIPCHK(c, c->ltFirst.alloc(nM)); HIPCHK(c, c->ltCount.alloc(nM)); HIPCHK(c, c->ltRoot.alloc(nM));
-    if (upload(c, c->ltTlas.p, lt.tlas.data(), c->ltTlas.bytes()) || upload(c, c->ltBlas.p, lt.blas.data(), c->ltBlas.bytes()) ||
-        upload(c, c->ltFirst.p, lt.first.data(), c->ltFirst.bytes()) || upload(c, c->ltCount.p, lt.count.data(), c->ltCount.bytes()) ||
-        upload(c, c->ltRoot.p, lt.root.data(), c->ltRoot.bytes())) return FYPRT_EHIP;
-    std::vector<uint32_t> leafOfTri(nT, ~0u);
-    for (uint32_t i = 0; i < (uint32_t)lt.tlas.size(); ++i) {
-        if (!lt.tlas[i].is_leaf) continue;
-        const uint32_t mesh = lt.tlas[i].right_or_emitter;
-        if (mesh >= nM) continue;
-        for (uint32_t j = 0; j < lt.count[mesh]; ++j) {
-            const fyprt_lighttree_node& n = lt.blas[lt.first[mesh] + j];
-            if (n.is_leaf && n.right_or_emitter < nT && leafOfTri[n.right_or_emitter] == ~0u) leafOfTri[n.right_or_emitter] = i;
-        }
-    }
-    HIPCHK(c, c->ltLeafOfTri.alloc(nT));
-    if (upload(c, c->ltLeafOfTri.p, leafOfTri.data(), c->ltLeafOfTri.bytes())) return FYPRT_EHIP;
-    DevScene& d = c->dsc;
-    d.ltLeafOfTri = c->ltLeafOfTri.p; d.ltTlas = c->ltTlas.p; d.ltTlasCount = (uint32_t)lt.tlas.size(); d.ltTlasRoot = lt.tlasRoot;
-    d.ltBlas = c->ltBlas.p; d.ltFirst = c->ltFirst.p; d.ltCount = c->ltCount.p; d.ltRoot = c->ltRoot.p;
-    return FYPRT_OK;
+    return upload_light_trees(c, nT, nM);
 }
 
 // Scene geometry moved, topology unchanged (SceneManager::PerformAllSceneUpdates with a transform edit, SceneManager.cpp:24-66):
@@ -655,10 +672,9 @@ int fyprt_update_vertices(fyprt_context* c, const fyprt_vertex* vertices, uint32
     if (upload(c, c->dverts.p, vertices, c->dverts.bytes())) return FYPRT_EHIP;
     c->hostVerts.assign(vertices, vertices + vertex_count);
     if (nT) hipLaunchKernelGGL(k_refresh_triangles, dim3((nT + 255u) / 256u), dim3(256), 0, c->stream, c->dverts.p, c->triIdx.p, c->triPos.p, c->triShade.p, nT);
-    { const int rr = run_refit(c); if (rr != FYPRT_OK) return rr; }
+    TRY(run_refit(c));
     c->hostBvhStale = true;
-    int rc = rebuild_light_trees(c, vertices);
-    if (rc != FYPRT_OK) return rc;
+    TRY(rebuild_light_trees(c, vertices));
     if (c->dsc.emissiveCount) hipLaunchKernelGGL(k_build_light_records, dim3((c->dsc.emissiveCount + 255u) / 256u), dim3(256), 0, c->stream, c->dsc, c->lightRecs.p);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, sync_all(c));
@@ -678,8 +694,7 @@ int fyprt_set_object_vertices(fyprt_context* c, const fyprt_vertex* object_verti
         for (uint32_t t = c->topoMeshes[m].first_triangle; t < c->topoMeshes[m].first_triangle + c->topoMeshes[m].triangle_count; ++t)
             for (int k = 0; k < 3; ++k) { const uint32_t v = c->topoTris[(size_t)t * 4 + k]; if (v < mesh_first_vertex[m] || v >= mesh_first_vertex[m + 1]) return c->fail(FYPRT_EINVAL, "fyprt_set_object_vertices: triangle " + std::to_string(t) + " uses a vertex outside its mesh's range"); }
     HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c));
-    HIPCHK(c, c->objVerts.alloc(vertex_count));
-    if (upload(c, c->objVerts.p, object_vertices, c->objVerts.bytes())) return FYPRT_EHIP;
+    TRY(alloc_upload(c, c->objVerts, object_vertices, vertex_count));
     c->meshFirstVertex.assign(mesh_first_vertex, mesh_first_vertex + nM + 1);
     return FYPRT_OK;
 }
@@ -703,21 +718,18 @@ int fyprt_update_transforms(fyprt_context* c, const uint32_t* mesh_indices, cons
         const uint32_t m = mesh_indices[k], first = c->meshFirstVertex[m], n = c->meshFirstVertex[m + 1] - first;
         Mat4 M; std::memcpy(M.m, matrices16 + (size_t)k * 16, 64);
         if (n) hipLaunchKernelGGL(k_transform_vertices, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, c->objVerts.p, c->dverts.p, first, n, M);
-        const fyprt_material& mat = c->topoMats[c->topoMeshes[m].material_index];
-        const float ex = mat.emission_color[0] * mat.emission_power, ey = mat.emission_color[1] * mat.emission_power, ez = mat.emission_color[2] * mat.emission_power;
-        if (((ex * ex + ey * ey) + ez * ez) > 0.0f && n) {            // an emissive mesh moved: its light tree is rebuilt from its new vertices
+        if (is_emissive(c->topoMats[c->topoMeshes[m].material_index]) && n) {            // an emissive mesh moved: its light tree is rebuilt from its new vertices
             HIPCHK(c, hipMemcpyAsync(c->hostVerts.data() + first, c->dverts.p + first, (size_t)n * sizeof(fyprt_vertex), hipMemcpyDeviceToHost, c->stream));
             touched[m] = 1; lightsMoved = true;
         }
     }
     HIPCHK(c, hipGetLastError());
     if (nT) hipLaunchKernelGGL(k_refresh_triangles, dim3((nT + 255u) / 256u), dim3(256), 0, c->stream, c->dverts.p, c->triIdx.p, c->triPos.p, c->triShade.p, nT);
-    { const int rr = run_refit(c); if (rr != FYPRT_OK) return rr; }
+    TRY(run_refit(c));
     c->hostBvhStale = true; c->hostVertsStale = true;
     if (lightsMoved) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        const int rc = rebuild_light_trees(c, c->hostVerts.data(), touched.data());
-        if (rc != FYPRT_OK) return rc;
+        TRY(rebuild_light_trees(c, c->hostVerts.data(), touched.data()));
     }
     if (c->dsc.emissiveCount) hipLaunchKernelGGL(k_build_light_records, dim3((c->dsc.emissiveCount + 255u) / 256u), dim3(256), 0, c->stream, c->dsc, c->lightRecs.p);
     HIPCHK(c, hipGetLastError());
@@ -777,14 +789,9 @@ static int run_stage(fyprt_context* c, const StageRun& r, const StageBufs& b, co
     const shade_kernel_t<CAM> shade = shade_kernel<CAM>(r.stage);
     const dim3 block(kBlock);
     const dim3 shadeGrid((uint32_t)(c->numCUs * 8));
-    if (c->pathOccLds != ldsBytes) {
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_trace_rays<false>, kBlock, ldsBytes) != hipSuccess || n <= 0) n = 4;
-        c->pathOcc = n; c->pathOccLds = ldsBytes;
-    }
-    const int perCU = c->tuning[2] > 0 ? c->tuning[2] : c->pathOcc;
+    const int occ = c->pathOcc.get(k_trace_rays<false>, ldsBytes, 4), perCU = c->tuning[K_WG_PER_CU] > 0 ? c->tuning[K_WG_PER_CU] : occ;
     DevScene tsc = sc;
-    tsc.nodeQuorum = (uint32_t)c->tuning[6];                 // incoherent rays: leave the node loop once few lanes remain in it
+    tsc.nodeQuorum = (uint32_t)c->tuning[K_QUORUM_SECONDARY];                 // incoherent rays: leave the node loop once few lanes remain in it
     tsc.rayCounter = b.rayCounter ? b.rayCounter + 8 * r.counterPart : nullptr;
     for (uint32_t it = 0; it <= r.steps; ++it) {
         PathIO io{};
@@ -811,17 +818,14 @@ static int run_stage(fyprt_context* c, const StageRun& r, const StageBufs& b, co
         }
         TraceQueue q{};
         q.rays = io.raysOut; q.hits = b.hits[(it + 1u) & 1u]; q.count = io.countOut; q.raysPer = r.raysPer; q.head = r.heads + it + 1;
-        q.chunk = (uint32_t)(c->tuning[4] > 0 ? c->tuning[4] : 128); q.refillLanes = (uint32_t)(c->tuning[5] > 0 ? c->tuning[5] : 24);
-        q.staticChunks = (uint32_t)(c->tuning[9] > 0 ? c->tuning[9] : 2); q.minChunk = (uint32_t)(c->tuning[10] > 0 ? c->tuning[10] : q.chunk);      // (auto: two static chunks per wave — config 3 3.13 -> 3.08 ms, profiles/README.md r03)
+        set_queue_params(c, q, K_REFILL_LANES);
         // small trees (cheap rays): one thread per ray; big ones: persistent waves with lane refill (tuning key 15: 0 = by tree size)
-        const bool simple = c->tuning[15] == 2 || (c->tuning[15] == 0 && c->hostBvh.tris.size() < 65536u);
+        const bool simple = c->tuning[K_RAY_KERNEL] == 2 || (c->tuning[K_RAY_KERNEL] == 0 && c->hostBvh.tris.size() < 65536u);
         if (simple) {
             const uint32_t sg = (uint32_t)std::min<size_t>((size_t)c->numCUs * 16u, (r.maxEntries * r.raysPer + kBlock - 1) / kBlock);
-            if (tsc.rayCounter) hipLaunchKernelGGL(k_trace_rays_simple<true>, dim3(std::max(1u, sg)), block, ldsBytes, c->stream, tsc, q);
-            else hipLaunchKernelGGL(k_trace_rays_simple<false>, dim3(std::max(1u, sg)), block, ldsBytes, c->stream, tsc, q);
+            hipLaunchKernelGGL(tsc.rayCounter ? k_trace_rays_simple<true> : k_trace_rays_simple<false>, dim3(std::max(1u, sg)), block, ldsBytes, c->stream, tsc, q);
         }
-        else if (tsc.rayCounter) hipLaunchKernelGGL(k_trace_rays<true>, dim3((uint32_t)(c->numCUs * perCU)), block, ldsBytes, c->stream, tsc, q);
-        else hipLaunchKernelGGL(k_trace_rays<false>, dim3((uint32_t)(c->numCUs * perCU)), block, ldsBytes, c->stream, tsc, q);
+        else hipLaunchKernelGGL(tsc.rayCounter ? k_trace_rays<true> : k_trace_rays<false>, dim3((uint32_t)(c->numCUs * perCU)), block, ldsBytes, c->stream, tsc, q);
         ++*launched;
         // long sample x bounce products: stop once no path is alive any more.  Only inside a blocking call (fyprt_render, fyprt_render_rays)
         // — an asynchronous call (fyprt_render_async, group / comm frames, fyprt_render_rays_device) must not wait on the device: there
@@ -878,7 +882,7 @@ static int enqueue_frame_impl(fyprt_context* c, const fyprt_settings* s, bool ti
     st.candidateCount = (uint32_t)s->light_candidate_count; st.randSeed = s->rand_seed;
     st.useTemporal = s->use_temporal_reuse ? 1u : 0u; st.useSpatial = s->use_spatial_reuse ? 1u : 0u;
     st.historyLimit = (uint8_t)s->temporal_history_limit; st.numNeighbors = (uint8_t)s->spatial_neighbor_num; st.radius = (uint8_t)s->spatial_neighbor_radius;
-    st.skipDeadRays = c->tuning[18] ? 1u : 0u;
+    st.skipDeadRays = c->tuning[K_SKIP_DEAD_RAYS] ? 1u : 0u;
     DevFrame fr;
     fr.accum = c->accum.p; fr.image = c->externalImage ? c->externalImage : c->image.p; fr.payload = c->payload.p; fr.depth = c->depth.p;
     fr.normalPrev = c->normalFlip ? c->normalB.p : c->normalA.p; fr.normalCur = c->normalFlip ? c->normalA.p : c->normalB.p;
@@ -892,14 +896,14 @@ static int enqueue_frame_impl(fyprt_context* c, const fyprt_settings* s, bool ti
     c->dsc.rayCounter = c->countRays ? c->rayCounter.p : nullptr;
     // node-loop quorum of the fused per-pixel kernels (key 7): 0 = auto — 16 for the light-tree kernels (their shadow rays: NEE 5.2 -> 4.95 ms),
     // none elsewhere (path and ReSTIR GI kernels: neutral or slightly negative)
-    c->dsc.nodeQuorum = (uint32_t)c->tuning[7];
+    c->dsc.nodeQuorum = (uint32_t)c->tuning[K_QUORUM_PRIMARY];
     // traversal-stack budget (node_step's rule): never below the level count (the induction), never above the 31 the node
     // format records; by default a few entries above the level count, so the LDS stack is no larger than this tree needs
     // and more workgroups fit a CU (LDS is what limits residency: (budget + 1) KB per 256-thread workgroup)
     const int budget = effective_stack_budget(c);
     c->dsc.stackBudget = budget;
 #ifdef RT_TOPCACHE
-    c->dsc.topCount = (uint32_t)std::min<size_t>((size_t)std::max(0, c->tuning[16]), c->hostBvh.nodes.size());
+    c->dsc.topCount = (uint32_t)std::min<size_t>((size_t)std::max(0, c->tuning[K_TOP_NODES]), c->hostBvh.nodes.size());
 #else
     c->dsc.topCount = 0u;                      // tuning key 16 only acts in a -DRT_TOPCACHE build (rt_device.h: measured slower)
 #endif
@@ -910,8 +914,8 @@ static int enqueue_frame_impl(fyprt_context* c, const fyprt_settings* s, bool ti
     // frame order on `stream`; so frame N+1's front part may run beside frame N's trace kernel.  Any other frame runs on
     // `stream` alone, after everything before it.
     const int par = (int)(c->frameSerial & 1ull);
-    const bool wavefront = tech == FYPRT_RESTIR_DI && c->tuning[1] == 1;
-    const bool overlap = wavefront && c->tuning[11] != 0 && !c->countRays && phase == 0;
+    const bool wavefront = tech == FYPRT_RESTIR_DI && c->tuning[K_DI_WAVEFRONT] == 1;
+    const bool overlap = wavefront && c->tuning[K_PIPELINE] != 0 && !c->countRays && phase == 0;
     hipStream_t fs = overlap ? c->front : c->stream;             // where Part 1 + setup go
     if (overlap) {
         HIPCHK(c, hipStreamWaitEvent(c->front, c->evDone[par], 0));                            // frame N-2 done: its queue is free
@@ -925,11 +929,11 @@ static int enqueue_frame_impl(fyprt_context* c, const fyprt_settings* s, bool ti
     // sums of an earlier accumulation in its new rows)
     if (c->frameIndex == 1 && phase != 2) HIPCHK(c, hipMemsetAsync(c->accum.p, 0, c->accum.bytes(), c->stream));
     const uint32_t tilesX = (c->W + 15u) / 16u;
-    fr.tileOrder = (uint32_t)c->tuning[0];
+    fr.tileOrder = (uint32_t)c->tuning[K_TILE_ORDER];
     fr.p1Mode = wavefront ? 1u : 0u;
     auto gridFor = [&](uint32_t rb, uint32_t re) {
         const uint32_t tilesY = (re - rb + 15u) / 16u;
-        if (c->tuning[0] == 2) return dim3(tilesX * ((tilesY + 7u) / 8u) * 8u);
+        if (c->tuning[K_TILE_ORDER] == 2) return dim3(tilesX * ((tilesY + 7u) / 8u) * 8u);
         return dim3(((tilesX * tilesY + 7u) / 8u) * 8u);
     };
     const dim3 block(kBlock);
@@ -961,11 +965,11 @@ static int enqueue_frame_impl(fyprt_context* c, const fyprt_settings* s, bool ti
             }
             const size_t entries = (size_t)(fr.rowEnd - fr.rowBegin) * c->W, L = (size_t)steps + 2;
             const uint32_t stride = (tech == FYPRT_NEE) ? 6u : 2u;
-            { const int rc = ensure_paths(c, entries, raysPer, stride, 3 * L); if (rc != FYPRT_OK) return rc; }
+            TRY(ensure_paths(c, entries, raysPer, stride, 3 * L));
             HIPCHK(c, hipMemsetAsync(c->wfCounters.p, 0, 3 * L * sizeof(uint32_t), c->stream));
-            c->dsc.nodeQuorum = (uint32_t)c->tuning[7];             // coherent primary rays
+            c->dsc.nodeQuorum = (uint32_t)c->tuning[K_QUORUM_PRIMARY];             // coherent primary rays
             // small trees, techniques 0-5: the whole frame in one launch, one thread per pixel (rt_paths.h: k_path_fused; key 17: 0 = by tree size, 1 = never, 2 = always)
-            const bool fused = tech != FYPRT_NEE && (c->tuning[17] == 2 || (c->tuning[17] == 0 && c->hostBvh.tris.size() < 65536u));
+            const bool fused = tech != FYPRT_NEE && (c->tuning[K_FUSED_FRAME] == 2 || (c->tuning[K_FUSED_FRAME] == 0 && c->hostBvh.tris.size() < 65536u));
             if (fused) {
                 PathIO io{};
                 io.fusedOwner = kNotFused; io.raysIn = c->wfRays[0].p; io.raysOut = c->wfRays[0].p; io.hitsIn = c->wfHits[0].p; io.state = c->wfState.p; io.stateStride = stride; io.raysPer = 1u;
@@ -976,19 +980,18 @@ static int enqueue_frame_impl(fyprt_context* c, const fyprt_settings* s, bool ti
                 launches = 1;
                 break;
             }
-            if (c->countRays) hipLaunchKernelGGL(k_primary<true>, pgrid, block, ldsBytes, c->stream, c->dsc, c->dcam, fr, st, c->wfPixels.p, c->wfCounters.p);
-            else hipLaunchKernelGGL(k_primary<false>, pgrid, block, ldsBytes, c->stream, c->dsc, c->dcam, fr, st, c->wfPixels.p, c->wfCounters.p);
+            hipLaunchKernelGGL(c->countRays ? k_primary<true> : k_primary<false>, pgrid, block, ldsBytes, c->stream, c->dsc, c->dcam, fr, st, c->wfPixels.p, c->wfCounters.p);
             StageRun r{tech, steps, raysPer, stride, c->wfPixels.p, c->wfCounters.p, c->wfCounters.p + L, (tech == FYPRT_NEE) ? c->wfPixels2.p : nullptr, nullptr, 0, (tech == FYPRT_NEE) ? c->wfCounters.p + 2 * L : nullptr, entries};
-            { const int rc = run_stage(r); if (rc != FYPRT_OK) return rc; }
+            TRY(run_stage(r));
             launches = 1;
             break;
         }
         case FYPRT_RESTIR_DI: case FYPRT_RESTIR_GI: {
             // halo rows: Part 1 recomputed on them (default), or — exchange mode — left to the band that owns them and copied in between the parts
-            const uint32_t p1halo = (c->haloExchange || c->tuning[13]) ? 0u : c->halo;
+            const uint32_t p1halo = (c->haloExchange || c->tuning[K_SKIP_HALO_PART1]) ? 0u : c->halo;
             const uint32_t p1b = (c->rowBegin > p1halo) ? c->rowBegin - p1halo : 0u;
             const uint32_t p1e = (c->rowEnd + p1halo < c->H) ? c->rowEnd + p1halo : c->H;
-            c->dsc.nodeQuorum = (uint32_t)c->tuning[7];             // Part 1 traces coherent primary rays only
+            c->dsc.nodeQuorum = (uint32_t)c->tuning[K_QUORUM_PRIMARY];             // Part 1 traces coherent primary rays only
             // The reference's spatial-neighbour coordinate is computed in unsigned arithmetic (R.cu:1916-1917): an offset
             // above the first row wraps and clamps to the LAST row.  A band that owns rows < radius therefore also needs
             // Part 1 of row H-1 (one extra row of recompute) to stay bit-identical to a single-GPU frame.  It rides in the same
@@ -1001,73 +1004,63 @@ static int enqueue_frame_impl(fyprt_context* c, const fyprt_settings* s, bool ti
                 const size_t p1px = ((size_t)(p1e - p1b) + (extra ? 1u : 0u)) * c->W;
                 const uint32_t steps1 = st.maxBounces, steps2 = st.useSpatial ? st.numNeighbors : 0u;
                 const size_t L1 = (size_t)steps1 + 2, L2 = (size_t)steps2 + 2;
-                { const int rc = ensure_paths(c, p1px, 1, 5, 2 * L1 + 2 * L2); if (rc != FYPRT_OK) return rc; }
+                TRY(ensure_paths(c, p1px, 1, 5, 2 * L1 + 2 * L2));
                 uint32_t* cnt1 = c->wfCounters.p; uint32_t* cnt2 = cnt1 + 2 * L1;      // cnt2[0] = length of the Part-2 list
-                if (phase != 2) { const int rc = sync_restir_normals(c, tech, c->stream); if (rc != FYPRT_OK) return rc; }   // the last ReSTIR frame was a DI frame: its normals (in the history records) are this frame's "previous normals"
+                if (phase != 2) TRY(sync_restir_normals(c, tech, c->stream));   // the last ReSTIR frame was a DI frame: its normals (in the history records) are this frame's "previous normals"
                 if (phase != 2) {
                     HIPCHK(c, hipMemsetAsync(cnt1, 0, (2 * L1 + 2 * L2) * sizeof(uint32_t), c->stream));
-                    if (c->countRays) hipLaunchKernelGGL(k_gi_primary<true>, g1, block, ldsBytes, c->stream, c->dsc, c->dcam, fr, st, p1b, p1e, extraRow, c->wfPixels.p, cnt1);
-                    else hipLaunchKernelGGL(k_gi_primary<false>, g1, block, ldsBytes, c->stream, c->dsc, c->dcam, fr, st, p1b, p1e, extraRow, c->wfPixels.p, cnt1);
+                    hipLaunchKernelGGL(c->countRays ? k_gi_primary<true> : k_gi_primary<false>, g1, block, ldsBytes, c->stream, c->dsc, c->dcam, fr, st, p1b, p1e, extraRow, c->wfPixels.p, cnt1);
                     StageRun r1{T_GI1, steps1, 1u, 5u, c->wfPixels.p, cnt1, cnt1 + L1, c->wfPixels2.p, cnt2, 0, nullptr, p1px};
-                    { const int rc = run_stage(r1); if (rc != FYPRT_OK) return rc; }
+                    TRY(run_stage(r1));
                     if (timed) HIPCHK(c, hipEventRecord(c->ev[ei++], c->stream));
                     if (phase == 1) { c->part1Pending = true; return c->hip(hipGetLastError(), "ReSTIR GI part 1"); }
                 }
-                if (c->tuning[19] == 2) {
+                if (c->tuning[K_GI2_MODE] == 2) {
                     // Part 2 as one PERSISTENT launch (rt_paths.h: k_gi2_persistent): a lane owns a pixel of the list, lanes without a ray in flight are serviced together
                     DevScene tsc = c->dsc;
-                    tsc.nodeQuorum = (uint32_t)c->tuning[6];
+                    tsc.nodeQuorum = (uint32_t)c->tuning[K_QUORUM_SECONDARY];
                     tsc.rayCounter = c->countRays ? c->rayCounter.p + 8 : nullptr;
-                    if (c->gi2OccLds != ldsBytes) {
-                        int nb = 0;
-                        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_gi2_persistent<false>, kBlock, ldsBytes) != hipSuccess || nb <= 0) nb = 3;
-                        c->gi2Occ = nb; c->gi2OccLds = ldsBytes;
-                    }
-                    const int perCU = c->tuning[2] > 0 ? std::min(c->tuning[2], c->gi2Occ) : c->gi2Occ;
+                    const int occ = c->gi2Occ.get(k_gi2_persistent<false>, ldsBytes, 3), perCU = c->tuning[K_WG_PER_CU] > 0 ? std::min(c->tuning[K_WG_PER_CU], occ) : occ;
                     GI2Queue gq{};
                     gq.list = c->wfPixels2.p; gq.count = cnt2; gq.head = cnt2 + L2 + 1;
-                    gq.chunk = (uint32_t)(c->tuning[4] > 0 ? c->tuning[4] : 128); gq.refillLanes = (uint32_t)(c->tuning[20] > 0 ? c->tuning[20] : 48);
-                    gq.staticChunks = (uint32_t)(c->tuning[9] > 0 ? c->tuning[9] : 2); gq.minChunk = (uint32_t)(c->tuning[10] > 0 ? c->tuning[10] : gq.chunk);
-                    if (c->countRays) hipLaunchKernelGGL(k_gi2_persistent<true>, dim3((uint32_t)(c->numCUs * perCU)), block, ldsBytes, c->stream, tsc, c->dcam, fr, st, gq);
-                    else hipLaunchKernelGGL(k_gi2_persistent<false>, dim3((uint32_t)(c->numCUs * perCU)), block, ldsBytes, c->stream, tsc, c->dcam, fr, st, gq);
+                    set_queue_params(c, gq, K_GI2_REFILL_LANES);
+                    hipLaunchKernelGGL(c->countRays ? k_gi2_persistent<true> : k_gi2_persistent<false>, dim3((uint32_t)(c->numCUs * perCU)), block, ldsBytes, c->stream, tsc, c->dcam, fr, st, gq);
                     HIPCHK(c, hipGetLastError());
-                } else if (c->tuning[19] == 1) {
+                } else if (c->tuning[K_GI2_MODE] == 1) {
                     // Part 2 in one launch (rt_paths.h: k_gi2_fused): one thread per listed pixel for the whole neighbour loop, visibility rays traced in place
                     DevScene tsc = c->dsc;
-                    tsc.nodeQuorum = (uint32_t)c->tuning[6];
+                    tsc.nodeQuorum = (uint32_t)c->tuning[K_QUORUM_SECONDARY];
                     tsc.rayCounter = c->countRays ? c->rayCounter.p + 8 : nullptr;
                     const uint32_t fg = (uint32_t)std::max<size_t>(1, std::min<size_t>((size_t)c->numCUs * 64u, (p1px + kBlock - 1) / kBlock));
-                    if (c->countRays) hipLaunchKernelGGL(k_gi2_fused<true>, dim3(fg), block, ldsBytes, c->stream, tsc, c->dcam, fr, st, (const uint32_t*)c->wfPixels2.p, (const uint32_t*)cnt2);
-                    else hipLaunchKernelGGL(k_gi2_fused<false>, dim3(fg), block, ldsBytes, c->stream, tsc, c->dcam, fr, st, (const uint32_t*)c->wfPixels2.p, (const uint32_t*)cnt2);
+                    hipLaunchKernelGGL(c->countRays ? k_gi2_fused<true> : k_gi2_fused<false>, dim3(fg), block, ldsBytes, c->stream, tsc, c->dcam, fr, st, (const uint32_t*)c->wfPixels2.p, (const uint32_t*)cnt2);
                     HIPCHK(c, hipGetLastError());
                 } else {
                     StageRun r2{T_GI2, steps2, 1u, 5u, c->wfPixels2.p, cnt2, cnt2 + L2, nullptr, nullptr, 1, nullptr, p1px};
-                    const int rc = run_stage(r2); if (rc != FYPRT_OK) return rc;
+                    TRY(run_stage(r2));
                 }
                 launches = 2;
                 c->normalFlip = !c->normalFlip; c->histGI[0] = c->rowBegin; c->histGI[1] = c->rowEnd;
                 break;
             }
-            if (phase != 2) { const int rc = sync_restir_normals(c, tech, fs); if (rc != FYPRT_OK) return rc; }   // the last ReSTIR frame was a GI frame: its normals are this frame's "previous normals"
+            if (phase != 2) TRY(sync_restir_normals(c, tech, fs));   // the last ReSTIR frame was a GI frame: its normals are this frame's "previous normals"
             if (phase != 2) {
-                if (c->countRays) hipLaunchKernelGGL(k_di_part1<true>, g1, block, ldsBytes, fs, c->dsc, c->dcam, fr, st, p1b, p1e, extraRow);
-                else hipLaunchKernelGGL(k_di_part1<false>, g1, block, ldsBytes, fs, c->dsc, c->dcam, fr, st, p1b, p1e, extraRow);
+                hipLaunchKernelGGL(c->countRays ? k_di_part1<true> : k_di_part1<false>, g1, block, ldsBytes, fs, c->dsc, c->dcam, fr, st, p1b, p1e, extraRow);
                 if (timed) HIPCHK(c, hipEventRecord(c->ev[ei++], fs));
                 if (phase == 1) { c->part1Pending = true; return c->hip(hipGetLastError(), "ReSTIR DI part 1"); }
             }
-            c->dsc.nodeQuorum = (uint32_t)c->tuning[6];   // shadow-ray kernels of ReSTIR DI Part 2: measured 0.85 -> 0.68 ms
+            c->dsc.nodeQuorum = (uint32_t)c->tuning[K_QUORUM_SECONDARY];   // shadow-ray kernels of ReSTIR DI Part 2: measured 0.85 -> 0.68 ms
             if (c->countRays) c->dsc.rayCounter = c->rayCounter.p + 8;      // per-launch counters
             launches = 2;
-            if (tech == FYPRT_RESTIR_DI && c->tuning[1] == 1) {
+            if (tech == FYPRT_RESTIR_DI && c->tuning[K_DI_WAVEFRONT] == 1) {
                 ShadowQueue q{};
                 q.tasks = c->shadowTasks.p + (size_t)par * c->queueStride; q.counters = c->queueCounters.p + 4 * par;
-                q.chunk = (uint32_t)(c->tuning[4] > 0 ? c->tuning[4] : 128); q.refillLanes = (uint32_t)(c->tuning[5] > 0 ? c->tuning[5] : 24); q.staticChunks = (uint32_t)(c->tuning[9] > 0 ? c->tuning[9] : 2); q.minChunk = (uint32_t)(c->tuning[10] > 0 ? c->tuning[10] : q.chunk);
+                set_queue_params(c, q, K_REFILL_LANES);
                 const size_t sg = (size_t)par * c->sortGroups;
-                q.sortMode = c->tuning[3] ? 1u : 0u; q.numGroups = grid.x; q.counts = c->sortCounts.p + sg; q.keys = c->sortKeys.p + sg * 256u; q.hist = c->sortHist.p + sg * kSortBins;
+                q.sortMode = c->tuning[K_SORT_TASKS] ? 1u : 0u; q.numGroups = grid.x; q.counts = c->sortCounts.p + sg; q.keys = c->sortKeys.p + sg * 256u; q.hist = c->sortHist.p + sg * kSortBins;
                 q.binOffset = c->sortOffset.p + sg * kSortBins; q.binTotal = c->sortTotal.p + (size_t)par * kSortBins; q.sorted = c->sortIndex.p + sg * 256u;
                 HIPCHK(c, hipMemsetAsync(q.counters, 0, 16, fs));
-                if (c->tuning[14] == 1) hipLaunchKernelGGL(k_di_part2_setup<1>, grid, block, 0, fs, c->dsc, c->dcam, fr, st, q);
-                else if (c->tuning[14] == 2) hipLaunchKernelGGL(k_di_part2_setup<2>, grid, block, 0, fs, c->dsc, c->dcam, fr, st, q);
+                if (c->tuning[K_SETUP_FETCH] == 1) hipLaunchKernelGGL(k_di_part2_setup<1>, grid, block, 0, fs, c->dsc, c->dcam, fr, st, q);
+                else if (c->tuning[K_SETUP_FETCH] == 2) hipLaunchKernelGGL(k_di_part2_setup<2>, grid, block, 0, fs, c->dsc, c->dcam, fr, st, q);
                 else hipLaunchKernelGGL(k_di_part2_setup<0>, grid, block, 0, fs, c->dsc, c->dcam, fr, st, q);
                 if (q.sortMode) {
                     hipLaunchKernelGGL(k_di_sort_scan, dim3(kSortBins), block, 0, fs, q);
@@ -1080,14 +1073,9 @@ static int enqueue_frame_impl(fyprt_context* c, const fyprt_settings* s, bool ti
                     if (timed) HIPCHK(c, hipEventRecord(c->ev[4], c->stream));      // start of the trace kernel on its own stream
                 }
                 if (c->countRays) c->dsc.rayCounter = c->rayCounter.p + 16;
-                int perCU = c->tuning[2];
+                int perCU = c->tuning[K_WG_PER_CU];
                 if (perCU <= 0) {          // as many workgroups as registers + LDS let a CU hold (asked from the runtime once per stack size)
-                    if (c->traceOccLds != ldsBytes) {
-                        int n = 0;
-                        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_di_part2_trace<false>, kBlock, ldsBytes) != hipSuccess || n <= 0) n = 4;
-                        c->traceOcc = n; c->traceOccLds = ldsBytes;
-                    }
-                    perCU = c->traceOcc;
+                    perCU = c->traceOcc.get(k_di_part2_trace<false>, ldsBytes, 4);
                     // pipelined frames: the persistent grid shares the chip with Part 1 + setup of the NEXT frame; with every slot a CU has
                     // (6 workgroups) those start late and run in extra rounds — 4 per CU leave them room: an eighth of the frame (a multi-GPU
                     // band) renders in 0.228 instead of 0.252 ms, the whole frame in the same 0.888 ms (profiles/README.md r03)
@@ -1096,12 +1084,10 @@ static int enqueue_frame_impl(fyprt_context* c, const fyprt_settings* s, bool ti
                 // persistent grid: as many workgroups as the chip holds — but not more than the band has tasks for (one lane per task): a narrow
                 // multi-GPU band would otherwise park idle workgroups on the LDS / wave slots the next frame's Part 1 is waiting for
                 const uint32_t traceGrid = std::max(8u, std::min((uint32_t)(c->numCUs * perCU), grid.x));
-                if (c->countRays) hipLaunchKernelGGL(k_di_part2_trace<true>, dim3(traceGrid), block, ldsBytes, c->stream, c->dsc, fr, q);
-                else hipLaunchKernelGGL(k_di_part2_trace<false>, dim3(traceGrid), block, ldsBytes, c->stream, c->dsc, fr, q);
+                hipLaunchKernelGGL(c->countRays ? k_di_part2_trace<true> : k_di_part2_trace<false>, dim3(traceGrid), block, ldsBytes, c->stream, c->dsc, fr, q);
                 launches = 3;
             }
-            else if (c->countRays) hipLaunchKernelGGL(k_di_part2<true>, grid, block, ldsBytes, c->stream, c->dsc, c->dcam, fr, st);
-            else hipLaunchKernelGGL(k_di_part2<false>, grid, block, ldsBytes, c->stream, c->dsc, c->dcam, fr, st);
+            else hipLaunchKernelGGL(c->countRays ? k_di_part2<true> : k_di_part2<false>, grid, block, ldsBytes, c->stream, c->dsc, c->dcam, fr, st);
             c->dprevFlip = !c->dprevFlip; c->histDI[0] = c->rowBegin; c->histDI[1] = c->rowEnd;
             break;
         }
@@ -1140,11 +1126,7 @@ int fyprt_render(fyprt_context* c, const fyprt_settings* s, fyprt_frame_stats* s
         stats->kernel_ms = total;
         if (c->countRays) {
             unsigned long long r[32] = {0}; (void)hipMemcpy(r, c->rayCounter.p, 256, hipMemcpyDeviceToHost);
-            for (int k = 0; k < 4; ++k) {
-                stats->part_rays[k] = r[8 * k + 0]; stats->part_box_tests[k] = r[8 * k + 1]; stats->part_tri_tests[k] = r[8 * k + 2]; stats->part_hits[k] = r[8 * k + 3];
-                stats->part_node_visits[k] = r[8 * k + 4];
-                stats->rays += r[8 * k + 0]; stats->box_tests += r[8 * k + 1]; stats->tri_tests += r[8 * k + 2]; stats->hits += r[8 * k + 3]; stats->node_visits += r[8 * k + 4];
-            }
+            for (int k = 0; k < 4; ++k) add_ray_stats(stats, k, r + 8 * k);
         }
     }
     return FYPRT_OK;
@@ -1187,8 +1169,7 @@ int fyprt_selftest_math(fyprt_context* c, uint64_t* mismatches3, uint32_t* first
     if (!c || !mismatches3) return FYPRT_EINVAL;
     if (c->hostOnly) return c->fail(FYPRT_ESTATE, "fyprt_selftest_math needs a device");
     HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c));
-    struct Scratch { DevBuf<unsigned long long> counts; DevBuf<uint32_t> first; ~Scratch() { counts.release(); first.release(); } } scratch;
-    auto& counts = scratch.counts; auto& first = scratch.first;
+    DevBuf<unsigned long long> counts; DevBuf<uint32_t> first;
     HIPCHK(c, counts.alloc(3)); HIPCHK(c, first.alloc(3));
     hipError_t e = hipMemsetAsync(counts.p, 0, 24, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(first.p, 0xFF, 12, c->stream);
@@ -1210,7 +1191,7 @@ int fyprt_compare_image(fyprt_context* c, const uint32_t* reference_rgba8, int f
     HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c));
     const size_t n = (size_t)c->W * c->H;
     if (c->refImage.n != n) HIPCHK(c, c->refImage.alloc(n));
-    if (upload(c, c->refImage.p, reference_rgba8, n * 4)) return FYPRT_EHIP;
+    TRY(upload(c, c->refImage.p, reference_rgba8, n * 4));
     HIPCHK(c, hipMemsetAsync(c->rayCounter.p + 31, 0, 8, c->stream));            // (the last, unused counter word serves as the accumulator)
     const uint32_t* img = c->externalImage ? c->externalImage : c->image.p;
     hipLaunchKernelGGL(k_image_sqdiff, dim3((uint32_t)c->numCUs * 4u), dim3(256), 0, c->stream, img, c->refImage.p, c->W, c->H, c->rowBegin, c->rowEnd, flip_reference_rows ? 1 : 0, c->rayCounter.p + 31);
@@ -1245,10 +1226,10 @@ int fyprt_read_buffer(fyprt_context* c, int which, void* dst, size_t bytes) {
         case FYPRT_BUF_GI_PREV: src = c->giPrev.p; n = c->giPrev.bytes(); break;
         case FYPRT_BUF_ALBEDO:
             if (!c->albedoValid) return c->fail(FYPRT_ESTATE, "fyprt_read_buffer: FYPRT_BUF_ALBEDO is written by fyprt_denoise");
-            src = c->dnAlbedo.p; n = c->dnAlbedo.bytes(); break;
+            src = c->dn.albedo.p; n = c->dn.albedo.bytes(); break;
         case FYPRT_BUF_TEMPORAL:
             if (!c->dtValid) return c->fail(FYPRT_ESTATE, "fyprt_read_buffer: FYPRT_BUF_TEMPORAL is written by fyprt_denoise_temporal");
-            src = c->dtHist[c->dtCur].p; n = c->dtHist[c->dtCur].bytes(); break;
+            src = c->dt.hist[c->dtCur].p; n = c->dt.hist[c->dtCur].bytes(); break;
         default: return c->fail(FYPRT_EINVAL, "fyprt_read_buffer: unknown buffer");
     }
     if (which == FYPRT_BUF_GI_RESERVOIR || which == FYPRT_BUF_GI_PREV) {
@@ -1290,7 +1271,7 @@ int fyprt_export_bvh(fyprt_context* c, void* nodes64, uint32_t* node_count, void
     if (!c->haveScene) return c->fail(FYPRT_ESTATE, "fyprt_export_bvh before fyprt_upload_scene");
     if (c->hostBvhStale && !c->hostOnly) {              // the device refitted the tree: read it back
         HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c));
-        { const int rc = download_nodes(c); if (rc != FYPRT_OK) return rc; }
+        TRY(download_nodes(c));
         if (!c->hostBvh.tris.empty()) HIPCHK(c, hipMemcpy(c->hostBvh.tris.data(), c->leafTris.p, c->hostBvh.tris.size() * 48, hipMemcpyDeviceToHost));
         c->hostBvhStale = false;
     }
@@ -1321,19 +1302,17 @@ int fyprt_export_lighttrees(fyprt_context* c, fyprt_lighttree_node* tlas, uint32
 }
 
 int fyprt_get_tuning(fyprt_context* c, int key, int* value) {
-    if (!c || !value || key < 0 || key >= 24) return FYPRT_EINVAL;
-    *value = (key == 8) ? effective_stack_budget(c) : (key == 2 && c->tuning[2] <= 0) ? c->traceOcc : c->tuning[key];   // key 2: residency found at the last DI frame
+    if (!c || !value || key < 0 || key >= K_COUNT) return FYPRT_EINVAL;
+    *value = (key == K_STACK_BUDGET) ? effective_stack_budget(c) : (key == K_WG_PER_CU && c->tuning[K_WG_PER_CU] <= 0) ? c->traceOcc.blocks : c->tuning[key];   // key 2: residency found at the last DI frame
     return FYPRT_OK;
 }
 
 int fyprt_set_tuning(fyprt_context* c, int key, int value) {
-    if (!c || key < 0 || key >= 24) return FYPRT_EINVAL;
+    if (!c || key < 0 || key >= K_COUNT) return FYPRT_EINVAL;
     // ranges: a value outside them could hang the persistent kernels (refill threshold above the wave size: no lane is ever
     // refilled) or index past a buffer, so it is refused here instead of trusted
-    static const int lo[24] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    static const int hi[24] = {2, 1, 16, 1, 65536, 64, 64, 64, 31, 4096, 65536, 1, 2, 1, 2, 2, 1024, 2, 1, 2, 64, 0, 0, 0};
-    if (value < lo[key] || value > hi[key])
-        return c->fail(FYPRT_EINVAL, "fyprt_set_tuning: key " + std::to_string(key) + " accepts " + std::to_string(lo[key]) + ".." + std::to_string(hi[key]));
+    if (value < 0 || value > kTuning[key].max)
+        return c->fail(FYPRT_EINVAL, "fyprt_set_tuning: key " + std::to_string(key) + " accepts 0.." + std::to_string(kTuning[key].max));
     c->tuning[key] = value;
     return FYPRT_OK;
 }
@@ -1367,27 +1346,21 @@ static int enqueue_query(fyprt_context* c, int query, const float4* rays, uint32
     DevScene qs = c->dsc;                                         // a copy: the frame's descriptor stays as the last frame left it
     const int budget = effective_stack_budget(c);
     qs.stackBudget = budget;
-    qs.nodeQuorum = (uint32_t)c->tuning[6];                       // the path engine's ray kernels' quorum (incoherent rays in general)
+    qs.nodeQuorum = (uint32_t)c->tuning[K_QUORUM_SECONDARY];                       // the path engine's ray kernels' quorum (incoherent rays in general)
     qs.rayCounter = c->countRays ? c->queryCounters.p : nullptr;
     qs.topCount = 0u;                                             // the query kernels stage no top nodes (not even in a -DRT_TOPCACHE build)
     const size_t ldsBytes = (size_t)(budget + 1) * kBlock * sizeof(int32_t);      // the traversal stack of the path engine's ray kernels
     QueryRays q{};
     q.rays = rays; q.results = results; q.count = count; q.head = reinterpret_cast<uint32_t*>(c->queryCounters.p + 5);
-    q.chunk = (uint32_t)(c->tuning[4] > 0 ? c->tuning[4] : 128); q.refillLanes = (uint32_t)(c->tuning[5] > 0 ? c->tuning[5] : 24);
-    q.staticChunks = (uint32_t)(c->tuning[9] > 0 ? c->tuning[9] : 2); q.minChunk = (uint32_t)(c->tuning[10] > 0 ? c->tuning[10] : q.chunk);
+    set_queue_params(c, q, K_REFILL_LANES);
     const dim3 block(kBlock);
     const uint32_t blocksForRays = (uint32_t)(((size_t)count + kBlock - 1) / kBlock);
     // tuning key 15 as in the path engine: one thread per ray below 65 536 triangles, persistent waves above
-    const bool simple = c->tuning[15] == 2 || (c->tuning[15] == 0 && c->hostBvh.tris.size() < 65536u);
+    const bool simple = c->tuning[K_RAY_KERNEL] == 2 || (c->tuning[K_RAY_KERNEL] == 0 && c->hostBvh.tris.size() < 65536u);
     dim3 grid;
     if (simple) grid = dim3(std::max(1u, std::min<uint32_t>((uint32_t)c->numCUs * 16u, blocksForRays)));
     else {
-        if (c->queryOccLds[occluded] != ldsBytes) {
-            int n = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, occluded ? k_query_rays<true, false> : k_query_rays<false, false>, kBlock, ldsBytes) != hipSuccess || n <= 0) n = 4;
-            c->queryOcc[occluded] = n; c->queryOccLds[occluded] = ldsBytes;
-        }
-        const int perCU = c->tuning[2] > 0 ? c->tuning[2] : c->queryOcc[occluded];
+        const int occ = c->queryOcc[occluded].get(occluded ? k_query_rays<true, false> : k_query_rays<false, false>, ldsBytes, 4), perCU = c->tuning[K_WG_PER_CU] > 0 ? c->tuning[K_WG_PER_CU] : occ;
         grid = dim3(std::max(1u, std::min<uint32_t>((uint32_t)(c->numCUs * perCU), blocksForRays)));   // no more workgroups than the rays fill
     }
     if (timed) HIPCHK(c, hipEventRecord(c->queryEv[0], c->stream));
@@ -1405,16 +1378,16 @@ static int enqueue_query(fyprt_context* c, int query, const float4* rays, uint32
 }
 
 int fyprt_trace_rays(fyprt_context* c, int query, const fyprt_ray* rays, uint32_t count, void* results, fyprt_frame_stats* stats) {
-    { const int rc = check_query(c, query, rays, count, results, false); if (rc != FYPRT_OK) return rc; }
+    TRY(check_query(c, query, rays, count, results, false));
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (count == 0) return FYPRT_OK;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t rayBytes = (size_t)count * sizeof(fyprt_ray), resultBytes = (size_t)count * (query == FYPRT_QUERY_OCCLUDED ? 4u : 40u);
-    if (!c->queryEv[0]) { HIPCHK(c, hipEventCreate(&c->queryEv[0])); HIPCHK(c, hipEventCreate(&c->queryEv[1])); }
+    for (Event& e : c->queryEv) HIPCHK(c, create(e));
     if (c->queryRays.n < (size_t)count * 2) { HIPCHK(c, c->queryRays.alloc((size_t)count * 2)); }        // staging grows, is kept
     if (c->queryResults.bytes() < resultBytes) { HIPCHK(c, c->queryResults.alloc(resultBytes / 4)); }
     HIPCHK(c, hipMemcpyAsync(c->queryRays.p, rays, rayBytes, hipMemcpyHostToDevice, c->stream));
-    { const int rc = enqueue_query(c, query, c->queryRays.p, count, c->queryResults.p, true); if (rc != FYPRT_OK) return rc; }
+    TRY(enqueue_query(c, query, c->queryRays.p, count, c->queryResults.p, true));
     HIPCHK(c, hipMemcpyAsync(results, c->queryResults.p, resultBytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (stats) {
@@ -1424,16 +1397,14 @@ int fyprt_trace_rays(fyprt_context* c, int query, const fyprt_ray* rays, uint32_
         if (c->countRays) {
             unsigned long long r[5] = {0, 0, 0, 0, 0};
             HIPCHK(c, hipMemcpy(r, c->queryCounters.p, sizeof r, hipMemcpyDeviceToHost));
-            stats->rays = stats->part_rays[0] = r[0]; stats->box_tests = stats->part_box_tests[0] = r[1];
-            stats->tri_tests = stats->part_tri_tests[0] = r[2]; stats->hits = stats->part_hits[0] = r[3];
-            stats->node_visits = stats->part_node_visits[0] = r[4];
+            add_ray_stats(stats, 0, r);
         }
     }
     return FYPRT_OK;
 }
 
 int fyprt_trace_rays_device(fyprt_context* c, int query, const void* rays, uint32_t count, void* results) {
-    { const int rc = check_query(c, query, rays, count, results, true); if (rc != FYPRT_OK) return rc; }
+    TRY(check_query(c, query, rays, count, results, true));
     if (count == 0) return FYPRT_OK;
     HIPCHK(c, hipSetDevice(c->device));
     return enqueue_query(c, query, static_cast<const float4*>(rays), count, results, false);
@@ -1467,7 +1438,7 @@ static int enqueue_render_rays(fyprt_context* c, const fyprt_settings* s, uint32
     DevSettings st{};                                            // what techniques 0-6 read, with the frame's casts (enqueue_frame_impl)
     st.sky = f3{s->sky_color[0], s->sky_color[1], s->sky_color[2]};
     st.maxBounces = (uint8_t)s->light_bounces; st.sampleCount = (uint8_t)s->sample_count;
-    st.skipDeadRays = c->tuning[18] ? 1u : 0u;
+    st.skipDeadRays = c->tuning[K_SKIP_DEAD_RAYS] ? 1u : 0u;
     const uint32_t nSamples = (tech == FYPRT_BRUTE_FORCE) ? 1u : st.sampleCount;
     const uint32_t steps = (tech == FYPRT_LIGHT_SOURCE_SAMPLING) ? nSamples : nSamples * st.maxBounces;
     const uint32_t raysPer = (tech == FYPRT_NEE && st.maxBounces != 1u) ? 2u : 1u;
@@ -1486,7 +1457,7 @@ static int enqueue_render_rays(fyprt_context* c, const fyprt_settings* s, uint32
     }
     HIPCHK(c, hipMemsetAsync(c->rrCounters.p, 0, 3 * L * sizeof(uint32_t), c->stream));
     // primary segments: the closest-hit query (its own counters and queue head; ray counts of the whole call land there too)
-    { const int rc = enqueue_query(c, FYPRT_QUERY_CLOSEST, rays, count, c->rrPayload.p, false); if (rc != FYPRT_OK) return rc; }
+    TRY(enqueue_query(c, FYPRT_QUERY_CLOSEST, rays, count, c->rrPayload.p, false));
     ++*launched;
     DevScene qs = c->dsc;                                        // as enqueue_query: the frame's descriptor is not touched
     const int budget = effective_stack_budget(c);
@@ -1503,18 +1474,18 @@ static int enqueue_render_rays(fyprt_context* c, const fyprt_settings* s, uint32
                       c->countRays ? c->queryCounters.p : nullptr};
     const StageRun r{tech, steps, raysPer, stride, c->rrPixels.p, c->rrCounters.p, c->rrCounters.p + L, (tech == FYPRT_NEE) ? c->rrPixels2.p : nullptr, nullptr, 0,
                      (tech == FYPRT_NEE) ? c->rrCounters.p + 2 * L : nullptr, count};
-    { const int rc = run_stage(c, r, b, qs, rs, fr, st, ldsBytes, blocking, launched); if (rc != FYPRT_OK) return rc; }
+    TRY(run_stage(c, r, b, qs, rs, fr, st, ldsBytes, blocking, launched));
     if (payloads) HIPCHK(c, hipMemcpyAsync(payloads, c->rrPayload.p, (size_t)count * sizeof(Payload), payloadKind, c->stream));
     return FYPRT_OK;
 }
 
 int fyprt_render_rays(fyprt_context* c, const fyprt_settings* s, uint32_t frame_index, const fyprt_ray* rays, const uint32_t* pixel_indices, uint32_t first_index,
                       uint32_t count, float* radiance4, void* payloads, fyprt_frame_stats* stats) {
-    { const int rc = check_render_rays(c, s, frame_index, rays, pixel_indices, count, radiance4, payloads, false); if (rc != FYPRT_OK) return rc; }
+    TRY(check_render_rays(c, s, frame_index, rays, pixel_indices, count, radiance4, payloads, false));
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (count == 0) return FYPRT_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->rrEv[0]) { HIPCHK(c, hipEventCreate(&c->rrEv[0])); HIPCHK(c, hipEventCreate(&c->rrEv[1])); }
+    for (Event& e : c->rrEv) HIPCHK(c, create(e));
     const uint32_t chunkMax = std::min<uint32_t>(count, FYPRT_RENDER_RAYS_CHUNK);
     if (c->rrIn.n < (size_t)chunkMax * 2) { HIPCHK(c, c->rrIn.alloc((size_t)chunkMax * 2)); HIPCHK(c, c->rrOut.alloc(chunkMax)); }    // staging grows, is kept
     if (pixel_indices && c->rrIndices.n < chunkMax) HIPCHK(c, c->rrIndices.alloc(chunkMax));
@@ -1524,9 +1495,8 @@ int fyprt_render_rays(fyprt_context* c, const fyprt_settings* s, uint32_t frame_
         HIPCHK(c, hipMemcpyAsync(c->rrIn.p, rays + base, (size_t)n * sizeof(fyprt_ray), hipMemcpyHostToDevice, c->stream));
         if (pixel_indices) HIPCHK(c, hipMemcpyAsync(c->rrIndices.p, pixel_indices + base, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipEventRecord(c->rrEv[0], c->stream));
-        { const int rc = enqueue_render_rays(c, s, frame_index, c->rrIn.p, pixel_indices ? c->rrIndices.p : nullptr, first_index + base, n, c->rrOut.p,
-                                             payloads ? static_cast<char*>(payloads) + (size_t)base * sizeof(Payload) : nullptr, hipMemcpyDeviceToHost, true, &launches);
-          if (rc != FYPRT_OK) return rc; }
+        TRY(enqueue_render_rays(c, s, frame_index, c->rrIn.p, pixel_indices ? c->rrIndices.p : nullptr, first_index + base, n, c->rrOut.p,
+                                payloads ? static_cast<char*>(payloads) + (size_t)base * sizeof(Payload) : nullptr, hipMemcpyDeviceToHost, true, &launches));
         HIPCHK(c, hipEventRecord(c->rrEv[1], c->stream));
         HIPCHK(c, hipMemcpyAsync(radiance4 + (size_t)base * 4, c->rrOut.p, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1541,27 +1511,22 @@ int fyprt_render_rays(fyprt_context* c, const fyprt_settings* s, uint32_t frame_
     }
     if (stats) {
         stats->kernel_ms = ms; stats->kernel_ms_part[0] = ms; stats->launches = (uint32_t)launches;
-        if (c->countRays) {
-            stats->rays = stats->part_rays[0] = totals[0]; stats->box_tests = stats->part_box_tests[0] = totals[1];
-            stats->tri_tests = stats->part_tri_tests[0] = totals[2]; stats->hits = stats->part_hits[0] = totals[3];
-            stats->node_visits = stats->part_node_visits[0] = totals[4];
-        }
+        if (c->countRays) add_ray_stats(stats, 0, totals);
     }
     return FYPRT_OK;
 }
 
 int fyprt_render_rays_device(fyprt_context* c, const fyprt_settings* s, uint32_t frame_index, const void* rays, const uint32_t* pixel_indices, uint32_t first_index,
                              uint32_t count, void* radiance4, void* payloads) {
-    { const int rc = check_render_rays(c, s, frame_index, rays, pixel_indices, count, radiance4, payloads, true); if (rc != FYPRT_OK) return rc; }
+    TRY(check_render_rays(c, s, frame_index, rays, pixel_indices, count, radiance4, payloads, true));
     if (count == 0) return FYPRT_OK;
     HIPCHK(c, hipSetDevice(c->device));
     int launches = 0;
     for (uint32_t base = 0; base < count; base += FYPRT_RENDER_RAYS_CHUNK) {
         const uint32_t n = std::min<uint32_t>(count - base, FYPRT_RENDER_RAYS_CHUNK);
-        const int rc = enqueue_render_rays(c, s, frame_index, static_cast<const float4*>(rays) + (size_t)base * 2, pixel_indices ? pixel_indices + base : nullptr,
-                                           first_index + base, n, static_cast<float4*>(radiance4) + base,
-                                           payloads ? static_cast<char*>(payloads) + (size_t)base * sizeof(Payload) : nullptr, hipMemcpyDeviceToDevice, false, &launches);
-        if (rc != FYPRT_OK) return rc;
+        TRY(enqueue_render_rays(c, s, frame_index, static_cast<const float4*>(rays) + (size_t)base * 2, pixel_indices ? pixel_indices + base : nullptr,
+                                first_index + base, n, static_cast<float4*>(radiance4) + base,
+                                payloads ? static_cast<char*>(payloads) + (size_t)base * sizeof(Payload) : nullptr, hipMemcpyDeviceToDevice, false, &launches));
     }
     return FYPRT_OK;
 }
@@ -1592,76 +1557,99 @@ static int check_denoise(fyprt_context* c, const fyprt_denoise_params* p, const 
     return FYPRT_OK;
 }
 
-// Enqueues prepare + iterations (+ finish) on the context stream, outputs in device memory.  ev: 3 timing events or null.
-static int enqueue_denoise(fyprt_context* c, const fyprt_denoise_params* p, uint32_t* rgba8, float4* radiance4, hipEvent_t* ev, int* launched) {
-    const size_t n = (size_t)c->W * c->H;
-    if (c->dnGuide.n != 2 * n) {
-        HIPCHK(c, c->dnGuide.alloc(2 * n)); HIPCHK(c, c->dnAlbedo.alloc(n)); HIPCHK(c, c->dnCol[0].alloc(n)); HIPCHK(c, c->dnCol[1].alloc(n));
+extern "C++" {
+// The iteration kernel of a step size: steps up to RT_DN_LDS_MAX_STEP run their LDS-staged instantiation, larger ones gather (<0>).
+// `launch` is called with the instantiation's STEP as a std::integral_constant.
+template <class F> static void for_dn_step(int step, F&& launch) {
+    switch (step <= RT_DN_LDS_MAX_STEP ? step : 0) {
+        case 1: launch(std::integral_constant<int, 1>()); break;
+        case 2: launch(std::integral_constant<int, 2>()); break;
+        case 4: launch(std::integral_constant<int, 4>()); break;
+        case 8: launch(std::integral_constant<int, 8>()); break;
+        case 16: launch(std::integral_constant<int, 16>()); break;
+        case 32: launch(std::integral_constant<int, 32>()); break;
+        default: launch(std::integral_constant<int, 0>()); break;
     }
-    if (!c->dnDone) HIPCHK(c, hipEventCreateWithFlags(&c->dnDone, hipEventDisableTiming));
-    DnFrame fr{};
-    fr.W = c->W; fr.H = c->H; fr.frameIndex = (float)c->lastFrameIndex; fr.demodulate = p->demodulate_albedo;
-    fr.accum = c->accum.p; fr.guide = c->dnGuide.p; fr.albedo = c->dnAlbedo.p; fr.rgba8 = rgba8; fr.radiance4 = radiance4;
+}
+
+// The blocking form of either denoiser: outputs staged on the device, `enqueue(rgba8, radiance4, &launches)`, copied back; the stats'
+// parts are the times between the call's `nEv` timing events.
+template <class Enqueue> static int denoise_blocking(fyprt_context* c, uint32_t* rgba8, float* radiance4, fyprt_frame_stats* stats, Event* ev, int nEv, Enqueue&& enqueue) {
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, sync_all(c));                           // as fyprt_readback: the last frame is complete on both streams
+    for (int k = 0; k < nEv; ++k) HIPCHK(c, create(ev[k]));
+    const size_t n = (size_t)c->W * c->H;
+    if (rgba8 && c->dn.outImg.n != n) HIPCHK(c, c->dn.outImg.alloc(n));
+    if (radiance4 && c->dn.outRad.n != n) HIPCHK(c, c->dn.outRad.alloc(n));
+    int launches = 0;
+    TRY(enqueue(rgba8 ? c->dn.outImg.p : nullptr, radiance4 ? c->dn.outRad.p : nullptr, &launches));
+    if (rgba8) HIPCHK(c, hipMemcpyAsync(rgba8, c->dn.outImg.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (radiance4) HIPCHK(c, hipMemcpyAsync(radiance4, c->dn.outRad.p, n * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (stats) {
+        stats->launches = (uint32_t)launches;
+        for (int k = 0; k + 1 < nEv; ++k) { HIPCHK(c, hipEventElapsedTime(&stats->kernel_ms_part[k], ev[k], ev[k + 1])); stats->kernel_ms += stats->kernel_ms_part[k]; }
+    }
+    return FYPRT_OK;
+}
+}  // extern "C++"
+
+// What both denoisers start with: the shared buffers, the frame descriptor `fr`, the prepare launch (into dn.col[0]) between ev[0] and ev[1].
+static int begin_denoise(fyprt_context* c, const fyprt_denoise_params& sp, uint32_t* rgba8, float4* radiance4, const Event* ev, int* launched, DnFrame& fr) {
+    const size_t n = (size_t)c->W * c->H;
+    if (c->dn.guide.n != 2 * n) {
+        HIPCHK(c, c->dn.guide.alloc(2 * n)); HIPCHK(c, c->dn.albedo.alloc(n)); HIPCHK(c, c->dn.col[0].alloc(n)); HIPCHK(c, c->dn.col[1].alloc(n));
+    }
+    HIPCHK(c, create(c->dnDone, hipEventDisableTiming));
+    fr = DnFrame{};
+    fr.W = c->W; fr.H = c->H; fr.frameIndex = (float)c->lastFrameIndex; fr.demodulate = sp.demodulate_albedo;
+    fr.accum = c->accum.p; fr.guide = c->dn.guide.p; fr.albedo = c->dn.albedo.p; fr.rgba8 = rgba8; fr.radiance4 = radiance4;
     DevScene sc = c->dsc; sc.rayCounter = nullptr;
-    const uint32_t linear = (uint32_t)((n + 255u) / 256u);
     if (ev) HIPCHK(c, hipEventRecord(ev[0], c->stream));
-    hipLaunchKernelGGL(k_dn_prepare, dim3(linear), dim3(256), 0, c->stream, sc, fr, c->payload.p, c->dnCol[0].p);
+    hipLaunchKernelGGL(k_dn_prepare, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, c->stream, sc, fr, c->payload.p, c->dn.col[0].p);
     ++*launched;
     if (ev) HIPCHK(c, hipEventRecord(ev[1], c->stream));
-    for (uint32_t k = 0; k < p->iterations; ++k) {
-        DnIter it{};
-        it.step = 1 << k; it.sigmaL = p->sigma_luminance * (1.0f / (float)(1u << k)); it.lumOn = p->sigma_luminance > 0.0f ? 1u : 0u;
-        it.sigmaPlane = p->sigma_plane; it.normalPow = p->normal_power_log2; it.last = (k + 1 == p->iterations) ? 1u : 0u;
-        const float4* in = c->dnCol[k & 1u].p; float4* out = c->dnCol[(k + 1u) & 1u].p;
-#define DN_LAUNCH(STEP) hipLaunchKernelGGL(k_dn_iterate<STEP>, dim3(dn_grid<STEP>(c->W, c->H)), dim3(256), 0, c->stream, fr, it, in, out)
-        const int staged = it.step <= RT_DN_LDS_MAX_STEP ? it.step : 0;
-        switch (staged) {
-            case 1: DN_LAUNCH(1); break;
-            case 2: DN_LAUNCH(2); break;
-            case 4: DN_LAUNCH(4); break;
-            case 8: DN_LAUNCH(8); break;
-            case 16: DN_LAUNCH(16); break;
-            case 32: DN_LAUNCH(32); break;
-            default: DN_LAUNCH(0); break;
-        }
-#undef DN_LAUNCH
-        ++*launched;
-    }
-    if (p->iterations == 0) { hipLaunchKernelGGL(k_dn_finish, dim3(linear), dim3(256), 0, c->stream, fr, c->dnCol[0].p); ++*launched; }
+    return FYPRT_OK;
+}
+// ... and end with: the finish kernel on the unfiltered colour if no iteration ran, the last timing event, and dnDone — a pipelined
+// ReSTIR DI frame enqueued next runs its Part 1 on the front stream, which overwrites the payload: after the denoiser.
+static int end_denoise(fyprt_context* c, const DnFrame& fr, uint32_t iterations, const float4* unfiltered, const Event* evLast, int* launched) {
+    if (iterations == 0) { hipLaunchKernelGGL(k_dn_finish, dim3((uint32_t)(((size_t)c->W * c->H + 255u) / 256u)), dim3(256), 0, c->stream, fr, unfiltered); ++*launched; }
     HIPCHK(c, hipGetLastError());
-    if (ev) HIPCHK(c, hipEventRecord(ev[2], c->stream));
-    // a pipelined ReSTIR DI frame enqueued next runs its Part 1 on the front stream, which overwrites the payload: after the denoiser
+    if (evLast) HIPCHK(c, hipEventRecord(*evLast, c->stream));
     HIPCHK(c, hipEventRecord(c->dnDone, c->stream));
     if (c->front) HIPCHK(c, hipStreamWaitEvent(c->front, c->dnDone, 0));
     c->albedoValid = true;
     return FYPRT_OK;
 }
 
-int fyprt_denoise(fyprt_context* c, const fyprt_denoise_params* p, uint32_t* rgba8, float* radiance4, fyprt_frame_stats* stats) {
-    { const int rc = check_denoise(c, p, rgba8, radiance4, false); if (rc != FYPRT_OK) return rc; }
-    if (stats) std::memset(stats, 0, sizeof *stats);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, sync_all(c));                           // as fyprt_readback: the last frame is complete on both streams
-    for (auto& e : c->dnEv) if (!e) HIPCHK(c, hipEventCreate(&e));
-    const size_t n = (size_t)c->W * c->H;
-    if (rgba8 && c->dnOutImg.n != n) HIPCHK(c, c->dnOutImg.alloc(n));
-    if (radiance4 && c->dnOutRad.n != n) HIPCHK(c, c->dnOutRad.alloc(n));
-    int launches = 0;
-    { const int rc = enqueue_denoise(c, p, rgba8 ? c->dnOutImg.p : nullptr, radiance4 ? c->dnOutRad.p : nullptr, c->dnEv, &launches); if (rc != FYPRT_OK) return rc; }
-    if (rgba8) HIPCHK(c, hipMemcpyAsync(rgba8, c->dnOutImg.p, n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (radiance4) HIPCHK(c, hipMemcpyAsync(radiance4, c->dnOutRad.p, n * 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (stats) {
-        stats->launches = (uint32_t)launches;
-        HIPCHK(c, hipEventElapsedTime(&stats->kernel_ms_part[0], c->dnEv[0], c->dnEv[1]));      // prepare
-        HIPCHK(c, hipEventElapsedTime(&stats->kernel_ms_part[1], c->dnEv[1], c->dnEv[2]));      // the iterations (or the finish kernel)
-        stats->kernel_ms = stats->kernel_ms_part[0] + stats->kernel_ms_part[1];
+// Enqueues prepare + iterations (+ finish) on the context stream, outputs in device memory.  ev: 3 timing events or null.
+static int enqueue_denoise(fyprt_context* c, const fyprt_denoise_params* p, uint32_t* rgba8, float4* radiance4, const Event* ev, int* launched) {
+    DnFrame fr;
+    TRY(begin_denoise(c, *p, rgba8, radiance4, ev, launched, fr));
+    for (uint32_t k = 0; k < p->iterations; ++k) {
+        DnIter it{};
+        it.step = 1 << k; it.sigmaL = p->sigma_luminance * (1.0f / (float)(1u << k)); it.lumOn = p->sigma_luminance > 0.0f ? 1u : 0u;
+        it.sigmaPlane = p->sigma_plane; it.normalPow = p->normal_power_log2; it.last = (k + 1 == p->iterations) ? 1u : 0u;
+        const float4* in = c->dn.col[k & 1u].p; float4* out = c->dn.col[(k + 1u) & 1u].p;
+        for_dn_step(it.step, [&](auto S) {
+            constexpr int STEP = decltype(S)::value;
+            hipLaunchKernelGGL(k_dn_iterate<STEP>, dim3(dn_grid<STEP>(c->W, c->H)), dim3(256), 0, c->stream, fr, it, in, out);
+        });
+        ++*launched;
     }
-    return FYPRT_OK;
+    return end_denoise(c, fr, p->iterations, c->dn.col[0].p, ev ? ev + 2 : nullptr, launched);
+}
+
+int fyprt_denoise(fyprt_context* c, const fyprt_denoise_params* p, uint32_t* rgba8, float* radiance4, fyprt_frame_stats* stats) {
+    TRY(check_denoise(c, p, rgba8, radiance4, false));
+    return denoise_blocking(c, rgba8, radiance4, stats, c->dnEv, 3,      // parts: prepare, the iterations (or the finish kernel)
+                            [&](uint32_t* img, float4* rad, int* launched) { return enqueue_denoise(c, p, img, rad, c->dnEv, launched); });
 }
 
 int fyprt_denoise_device(fyprt_context* c, const fyprt_denoise_params* p, void* rgba8, void* radiance4) {
-    { const int rc = check_denoise(c, p, rgba8, radiance4, true); if (rc != FYPRT_OK) return rc; }
+    TRY(check_denoise(c, p, rgba8, radiance4, true));
     HIPCHK(c, hipSetDevice(c->device));
     // every frame completes on the context stream (a pipelined frame's trace kernel waits there for its front part), so work enqueued on
     // it sees the last frame whole without a host wait
@@ -1691,91 +1679,51 @@ static int check_temporal(fyprt_context* c, const fyprt_temporal_params* p, cons
 }
 
 // Enqueues prepare + reproject + iterations (+ finish) on the context stream.  ev: 4 timing events or null.
-static int enqueue_temporal(fyprt_context* c, const fyprt_temporal_params* p, uint32_t* rgba8, float4* radiance4, hipEvent_t* ev, int* launched) {
+static int enqueue_temporal(fyprt_context* c, const fyprt_temporal_params* p, uint32_t* rgba8, float4* radiance4, const Event* ev, int* launched) {
     const fyprt_denoise_params& sp = p->spatial;
     const size_t n = (size_t)c->W * c->H;
-    if (c->dnGuide.n != 2 * n) {
-        HIPCHK(c, c->dnGuide.alloc(2 * n)); HIPCHK(c, c->dnAlbedo.alloc(n)); HIPCHK(c, c->dnCol[0].alloc(n)); HIPCHK(c, c->dnCol[1].alloc(n));
-    }
-    if (c->dtHist[0].n != 4 * n) {
+    if (c->dt.hist[0].n != 4 * n) {
         c->dtValid = false;
-        for (int k = 0; k < 2; ++k) { HIPCHK(c, c->dtHist[k].alloc(4 * n)); HIPCHK(c, c->dtVar[k].alloc(n)); }
+        for (int k = 0; k < 2; ++k) { HIPCHK(c, c->dt.hist[k].alloc(4 * n)); HIPCHK(c, c->dt.var[k].alloc(n)); }
     }
-    if (!c->dnDone) HIPCHK(c, hipEventCreateWithFlags(&c->dnDone, hipEventDisableTiming));
-    DnFrame fr{};
-    fr.W = c->W; fr.H = c->H; fr.frameIndex = (float)c->lastFrameIndex; fr.demodulate = sp.demodulate_albedo;
-    fr.accum = c->accum.p; fr.guide = c->dnGuide.p; fr.albedo = c->dnAlbedo.p; fr.rgba8 = rgba8; fr.radiance4 = radiance4;
-    DevScene sc = c->dsc; sc.rayCounter = nullptr;
-    const uint32_t linear = (uint32_t)((n + 255u) / 256u);
-    if (ev) HIPCHK(c, hipEventRecord(ev[0], c->stream));
-    hipLaunchKernelGGL(k_dn_prepare, dim3(linear), dim3(256), 0, c->stream, sc, fr, c->payload.p, c->dnCol[0].p);
-    ++*launched;
-    if (ev) HIPCHK(c, hipEventRecord(ev[1], c->stream));
+    DnFrame fr;
+    TRY(begin_denoise(c, sp, rgba8, radiance4, ev, launched, fr));
     DtCall tc{};
     std::memcpy(tc.m, c->dtPV, 64);
     tc.haveHistory = c->dtValid ? 1u : 0u; tc.limit = (float)p->history_limit; tc.normalMin = p->normal_min; tc.planeMax = p->plane_max;
     tc.sigmaPlane = sp.sigma_plane; tc.normalPow = sp.normal_power_log2;
     const int next = c->dtCur ^ 1;
-    float4* hist = c->dtHist[next].p;
-    hipLaunchKernelGGL(k_dt_reproject, dim3(((c->W + 15u) / 16u) * ((c->H + 15u) / 16u)), dim3(256), 0, c->stream, fr, tc, c->dnCol[0].p,
-                       c->dtHist[c->dtCur].p, hist, c->dnCol[1].p, c->dtVar[0].p);
+    float4* hist = c->dt.hist[next].p;
+    hipLaunchKernelGGL(k_dt_reproject, dim3(((c->W + 15u) / 16u) * ((c->H + 15u) / 16u)), dim3(256), 0, c->stream, fr, tc, c->dn.col[0].p,
+                       c->dt.hist[c->dtCur].p, hist, c->dn.col[1].p, c->dt.var[0].p);
     ++*launched;
     if (ev) HIPCHK(c, hipEventRecord(ev[2], c->stream));
-    for (uint32_t k = 0; k < sp.iterations; ++k) {           // colour: dnCol[1] -> [0] -> [1] ...; variance: dtVar[0] -> [1] -> [0] ...
+    for (uint32_t k = 0; k < sp.iterations; ++k) {           // colour: dn.col[1] -> [0] -> [1] ...; variance: dt.var[0] -> [1] -> [0] ...
         DnIter it{};
         it.step = 1 << k; it.sigmaL = sp.sigma_luminance; it.lumOn = sp.sigma_luminance > 0.0f ? 1u : 0u;
         it.sigmaPlane = sp.sigma_plane; it.normalPow = sp.normal_power_log2; it.last = (k + 1 == sp.iterations) ? 1u : 0u;
-        const float4* in = c->dnCol[(k + 1u) & 1u].p; float4* out = c->dnCol[k & 1u].p;
-        const float* vin = c->dtVar[k & 1u].p; float* vout = c->dtVar[(k + 1u) & 1u].p;
+        const float4* in = c->dn.col[(k + 1u) & 1u].p; float4* out = c->dn.col[k & 1u].p;
+        const float* vin = c->dt.var[k & 1u].p; float* vout = c->dt.var[(k + 1u) & 1u].p;
         float4* fb = (k == 0 && p->feedback) ? hist : nullptr;
-#define DT_LAUNCH(STEP) hipLaunchKernelGGL(k_dt_iterate<STEP>, dim3(dn_grid<STEP>(c->W, c->H)), dim3(256), 0, c->stream, fr, it, in, out, vin, vout, fb)
-        const int staged = it.step <= RT_DN_LDS_MAX_STEP ? it.step : 0;
-        switch (staged) {
-            case 1: DT_LAUNCH(1); break;
-            case 2: DT_LAUNCH(2); break;
-            case 4: DT_LAUNCH(4); break;
-            case 8: DT_LAUNCH(8); break;
-            case 16: DT_LAUNCH(16); break;
-            case 32: DT_LAUNCH(32); break;
-            default: DT_LAUNCH(0); break;
-        }
-#undef DT_LAUNCH
+        for_dn_step(it.step, [&](auto S) {
+            constexpr int STEP = decltype(S)::value;
+            hipLaunchKernelGGL(k_dt_iterate<STEP>, dim3(dn_grid<STEP>(c->W, c->H)), dim3(256), 0, c->stream, fr, it, in, out, vin, vout, fb);
+        });
         ++*launched;
     }
-    if (sp.iterations == 0) { hipLaunchKernelGGL(k_dn_finish, dim3(linear), dim3(256), 0, c->stream, fr, c->dnCol[1].p); ++*launched; }
-    HIPCHK(c, hipGetLastError());
-    if (ev) HIPCHK(c, hipEventRecord(ev[3], c->stream));
-    HIPCHK(c, hipEventRecord(c->dnDone, c->stream));           // as enqueue_denoise: the next pipelined frame's Part 1 overwrites the payload
-    if (c->front) HIPCHK(c, hipStreamWaitEvent(c->front, c->dnDone, 0));
-    c->albedoValid = true;
+    TRY(end_denoise(c, fr, sp.iterations, c->dn.col[1].p, ev ? ev + 3 : nullptr, launched));
     c->dtCur = next; c->dtValid = true; std::memcpy(c->dtPV, c->framePV, 64);
     return FYPRT_OK;
 }
 
 int fyprt_denoise_temporal(fyprt_context* c, const fyprt_temporal_params* p, uint32_t* rgba8, float* radiance4, fyprt_frame_stats* stats) {
-    { const int rc = check_temporal(c, p, rgba8, radiance4, false); if (rc != FYPRT_OK) return rc; }
-    if (stats) std::memset(stats, 0, sizeof *stats);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, sync_all(c));
-    for (auto& e : c->dtEv) if (!e) HIPCHK(c, hipEventCreate(&e));
-    const size_t n = (size_t)c->W * c->H;
-    if (rgba8 && c->dnOutImg.n != n) HIPCHK(c, c->dnOutImg.alloc(n));
-    if (radiance4 && c->dnOutRad.n != n) HIPCHK(c, c->dnOutRad.alloc(n));
-    int launches = 0;
-    { const int rc = enqueue_temporal(c, p, rgba8 ? c->dnOutImg.p : nullptr, radiance4 ? c->dnOutRad.p : nullptr, c->dtEv, &launches); if (rc != FYPRT_OK) return rc; }
-    if (rgba8) HIPCHK(c, hipMemcpyAsync(rgba8, c->dnOutImg.p, n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (radiance4) HIPCHK(c, hipMemcpyAsync(radiance4, c->dnOutRad.p, n * 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (stats) {
-        stats->launches = (uint32_t)launches;
-        for (int k = 0; k < 3; ++k) HIPCHK(c, hipEventElapsedTime(&stats->kernel_ms_part[k], c->dtEv[k], c->dtEv[k + 1]));   // prepare, reproject, iterations
-        stats->kernel_ms = (stats->kernel_ms_part[0] + stats->kernel_ms_part[1]) + stats->kernel_ms_part[2];
-    }
-    return FYPRT_OK;
+    TRY(check_temporal(c, p, rgba8, radiance4, false));
+    return denoise_blocking(c, rgba8, radiance4, stats, c->dtEv, 4,      // parts: prepare, reproject, iterations
+                            [&](uint32_t* img, float4* rad, int* launched) { return enqueue_temporal(c, p, img, rad, c->dtEv, launched); });
 }
 
 int fyprt_denoise_temporal_device(fyprt_context* c, const fyprt_temporal_params* p, void* rgba8, void* radiance4) {
-    { const int rc = check_temporal(c, p, rgba8, radiance4, true); if (rc != FYPRT_OK) return rc; }
+    TRY(check_temporal(c, p, rgba8, radiance4, true));
     HIPCHK(c, hipSetDevice(c->device));
     int launches = 0;
     return enqueue_temporal(c, p, static_cast<uint32_t*>(rgba8), static_cast<float4*>(radiance4), nullptr, &launches);

@@ -145,7 +145,8 @@ std::vector<CommOp> comm_set_rows_ops(int rank, const std::vector<uint32_t>& old
 struct fyprt_group {
     std::vector<fyprt_context*> ctx; std::vector<uint32_t> bounds; int haloMode = 0;
     uint32_t stripeRows = 0, lastStripeRows = 0; bool lastStriped = false;      // interleaved split for the per-pixel techniques; whether (and with which stripes) the last frame used it
-    std::vector<hipEvent_t> evP1, evPulled, evFrame, evSync; hipEvent_t evGather = nullptr; bool gatherPending = false; std::string err;
+    struct BandEvents { Event p1, pulled, frame, sync; };      // per context: Part 1 done, halo pulled, frame done, history normals in step
+    std::vector<BandEvents> ev; Event evGather; bool gatherPending = false; std::string err;
 };
 
 int fyprt_group_synchronize(fyprt_group* g);
@@ -178,14 +179,13 @@ int fyprt_group_create(fyprt_context** ctxs, int n, const uint32_t* row_bounds, 
     if (row_bounds[0] != 0 || row_bounds[n] != ctxs[0]->H) return ctxs[0]->fail(FYPRT_EINVAL, "fyprt_group_create: the bands must partition rows 0..height");
     auto* g = new fyprt_group();
     g->ctx.assign(ctxs, ctxs + n); g->bounds.assign(row_bounds, row_bounds + n + 1);
-    g->evP1.resize(n); g->evPulled.resize(n); g->evFrame.resize(n); g->evSync.resize(n);
+    g->ev.resize(n);
     for (int i = 0; i < n; ++i) {
         (void)hipSetDevice(ctxs[i]->device);
-        (void)hipEventCreateWithFlags(&g->evP1[i], hipEventDisableTiming); (void)hipEventCreateWithFlags(&g->evPulled[i], hipEventDisableTiming);
-        (void)hipEventCreateWithFlags(&g->evFrame[i], hipEventDisableTiming); (void)hipEventCreateWithFlags(&g->evSync[i], hipEventDisableTiming);
+        for (Event* e : {&g->ev[i].p1, &g->ev[i].pulled, &g->ev[i].frame, &g->ev[i].sync}) (void)create(*e, hipEventDisableTiming);
     }
     (void)hipSetDevice(ctxs[0]->device);
-    (void)hipEventCreateWithFlags(&g->evGather, hipEventDisableTiming);
+    (void)create(g->evGather, hipEventDisableTiming);
     *out = g;
     return FYPRT_OK;
 }
@@ -193,10 +193,9 @@ void fyprt_group_destroy(fyprt_group* g) {
     if (!g) return;
     for (size_t i = 0; i < g->ctx.size(); ++i) {
         (void)hipSetDevice(g->ctx[i]->device); (void)sync_all(g->ctx[i]);
-        (void)hipEventDestroy(g->evP1[i]); (void)hipEventDestroy(g->evPulled[i]); (void)hipEventDestroy(g->evFrame[i]); (void)hipEventDestroy(g->evSync[i]);
+        g->ev[i] = fyprt_group::BandEvents();               // this band's events go while its device is current
         g->ctx[i]->haloExchange = false;
     }
-    if (g->evGather) (void)hipEventDestroy(g->evGather);
     delete g;
 }
 // New band boundaries (e.g. from fyprt_balance_rows).  Rows that change owner take their accumulation and their temporal history
@@ -268,20 +267,20 @@ int fyprt_group_render(fyprt_group* g, const fyprt_settings* s) {
             fyprt_context* c = g->ctx[i];
             const int rc = enqueue_frame(c, s, true);
             if (rc != FYPRT_OK) return rc;
-            HIPCHK(c, hipEventRecord(g->evFrame[i], c->stream));
+            HIPCHK(c, hipEventRecord(g->ev[i].frame, c->stream));
         }
         return FYPRT_OK;
     }
     const std::vector<HaloXfer> plan = halo_plan(g->bounds, halo, H, true), hplan = halo_plan(g->bounds, hhalo, H, false);
-    auto pull = [&](int i, const std::vector<HaloXfer>& pl, int kind, const std::vector<hipEvent_t>& ready) -> int {
+    auto pull = [&](int i, const std::vector<HaloXfer>& pl, int kind, Event fyprt_group::BandEvents::*ready) -> int {
         fyprt_context* c = g->ctx[i];
         HIPCHK(c, hipSetDevice(c->device));
         const std::vector<XBuf> mine = exchange_buffers(c, s->technique, kind);
         for (const HaloXfer& x : pl) {
             if (x.receiver != i) continue;
             fyprt_context* o = g->ctx[x.owner];
-            HIPCHK(c, hipStreamWaitEvent(c->stream, ready[x.owner], 0));
-            if (kind == 1) HIPCHK(c, hipStreamWaitEvent(c->stream, g->evSync[x.owner], 0));      // the owner's history is in step with the technique
+            HIPCHK(c, hipStreamWaitEvent(c->stream, g->ev[x.owner].*ready, 0));
+            if (kind == 1) HIPCHK(c, hipStreamWaitEvent(c->stream, g->ev[x.owner].sync, 0));      // the owner's history is in step with the technique
             const std::vector<XBuf> theirs = exchange_buffers(o, s->technique, kind);
             for (size_t b = 0; b < mine.size(); ++b) {
                 const size_t off = (size_t)x.r0 * W * mine[b].bytesPerPixel, bytes = (size_t)(x.r1 - x.r0) * W * mine[b].bytesPerPixel;
@@ -294,32 +293,32 @@ int fyprt_group_render(fyprt_group* g, const fyprt_settings* s) {
     for (int i = 0; i < n; ++i) {
         fyprt_context* c = g->ctx[i];
         HIPCHK(c, hipSetDevice(c->device));
-        { const int rc = sync_restir_normals(c, s->technique, c->stream); if (rc != FYPRT_OK) return rc; }
-        HIPCHK(c, hipEventRecord(g->evSync[i], c->stream));
+        TRY(sync_restir_normals(c, s->technique, c->stream));
+        HIPCHK(c, hipEventRecord(g->ev[i].sync, c->stream));
     }
     // 1. temporal history of the halo rows, then Part 1 on the band's own rows
     for (int i = 0; i < n; ++i) {
         fyprt_context* c = g->ctx[i];
         HIPCHK(c, hipSetDevice(c->device));
-        for (int j = 0; j < n; ++j) if (j != i) HIPCHK(c, hipStreamWaitEvent(c->stream, g->evPulled[j], 0));    // last frame's pulls FROM this band are done
-        if (s->use_temporal_reuse) { const int rc = pull(i, hplan, 1, g->evFrame); if (rc != FYPRT_OK) return rc; }
+        for (int j = 0; j < n; ++j) if (j != i) HIPCHK(c, hipStreamWaitEvent(c->stream, g->ev[j].pulled, 0));    // last frame's pulls FROM this band are done
+        if (s->use_temporal_reuse) TRY(pull(i, hplan, 1, &fyprt_group::BandEvents::frame));
         extend_history_rows(c, s->technique, hhalo);
         const int rc = enqueue_frame(c, s, true, 1);
         if (rc != FYPRT_OK) return rc;
-        HIPCHK(c, hipEventRecord(g->evP1[i], c->stream));
+        HIPCHK(c, hipEventRecord(g->ev[i].p1, c->stream));
     }
     // 2. the neighbours' Part-1 records of the halo rows, then Part 2
     for (int i = 0; i < n; ++i) {
         fyprt_context* c = g->ctx[i];
-        { const int rc = pull(i, plan, 0, g->evP1); if (rc != FYPRT_OK) return rc; }
-        HIPCHK(c, hipEventRecord(g->evPulled[i], c->stream));
+        TRY(pull(i, plan, 0, &fyprt_group::BandEvents::p1));
+        HIPCHK(c, hipEventRecord(g->ev[i].pulled, c->stream));
     }
     for (int i = 0; i < n; ++i) {
         fyprt_context* c = g->ctx[i];
         HIPCHK(c, hipSetDevice(c->device));
         const int rc = enqueue_frame(c, s, true, 2);
         if (rc != FYPRT_OK) return rc;
-        HIPCHK(c, hipEventRecord(g->evFrame[i], c->stream));
+        HIPCHK(c, hipEventRecord(g->ev[i].frame, c->stream));
     }
     return FYPRT_OK;
 }
@@ -332,7 +331,7 @@ int fyprt_group_gather(fyprt_group* g, int root) {
     for (int i = 0; i < (int)g->ctx.size(); ++i) {
         if (i == root) continue;
         fyprt_context* c = g->ctx[i];
-        HIPCHK(r, hipStreamWaitEvent(r->stream, g->evFrame[i], 0));
+        HIPCHK(r, hipStreamWaitEvent(r->stream, g->ev[i].frame, 0));
         const uint32_t* src = c->externalImage ? c->externalImage : c->image.p;
         hipError_t e = hipSuccess;
         auto rows = [&](uint32_t r0, uint32_t r1) {

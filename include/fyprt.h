@@ -309,7 +309,7 @@ int fyprt_set_ray_counting(fyprt_context* ctx, int enabled);
  *         pixel without refill (slower on a whole frame, kept for comparison).  Same pixels bit for bit, same ray counts in every mode.
  * key 20: k_gi2_persistent (key 19 = 2): lanes of a wave without a ray in flight before the wave services them together (default 48; 0 = default).
  * Values are range-checked (FYPRT_EINVAL): key 0: 0..2, keys 1, 3, 11, 13, 18: 0..1, keys 12, 14, 15, 17, 19: 0..2, key 2: 0..16, keys 5, 6, 7, 20: 0..64,
- * key 8: 0..31, key 16: 0..1024; keys 19..23 are reserved (0). */
+ * key 8: 0..31, key 16: 0..1024; keys 21..23 are reserved (0). */
 int fyprt_set_tuning(fyprt_context* ctx, int key, int value);
 /* The value in effect (key 8: the budget actually used for the uploaded scene, which an instrumented restatement of the
  * traversal must use too). */
@@ -565,6 +565,10 @@ int fyprt_comm_ops(int kind, const uint32_t* row_bounds, const uint32_t* new_bou
 
 /* Library / build identification ("fyprt <version> gfx950 ..."). */
 const char* fyprt_version(void);
+
+/* Bytes of device memory the library's buffers hold right now, over every context of the process: it returns to its earlier value
+ * once everything created since has been destroyed. */
+uint64_t fyprt_live_device_bytes(void);
 
 #ifdef __cplusplus
 }

@@ -53,6 +53,7 @@ def test_host_only_context_refuses_to_render_and_validates_scenes():
         ctx.resize(16, 16)
     sc = scenes.cornell_box()
     ctx.upload_scene(sc)
+    assert capi.live_device_bytes() == 0                              # a host-only context allocates nothing on a device
     with pytest.raises(capi.FyprtError):
         ctx.render(capi.Settings())
     bad = scenes.cornell_box()
@@ -65,6 +66,7 @@ def test_host_only_context_refuses_to_render_and_validates_scenes():
     with pytest.raises(capi.FyprtError, match="partition"):
         ctx.upload_scene(bad2)
     ctx.close()
+    assert capi.live_device_bytes() == 0
 
 
 @pytest.mark.parametrize("name", ["cornell", "hall_small"])
