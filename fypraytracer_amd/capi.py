@@ -182,6 +182,7 @@ EXPORTED_SYMBOLS = [
     "fyprt_denoise_default_params", "fyprt_denoise", "fyprt_denoise_device",
     "fyprt_denoise_temporal_default_params", "fyprt_denoise_temporal", "fyprt_denoise_temporal_device", "fyprt_denoise_temporal_reset",
     "fyprt_live_device_bytes",
+    "fyprt_update_materials", "fyprt_export_emissive",
 ]
 
 
@@ -237,6 +238,9 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.fyprt_set_object_vertices.argtypes = [vp, vp, u32, C.POINTER(u32)]
     lib.fyprt_update_transforms.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_float), u32]
     lib.fyprt_compare_image.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    if hasattr(lib, "fyprt_update_materials"):   # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
+        lib.fyprt_update_materials.argtypes = [vp, vp, u32, C.POINTER(u32), C.POINTER(i32), u32, vp, u32]
+        lib.fyprt_export_emissive.argtypes = [vp, vp, C.POINTER(u32)]
     if hasattr(lib, "fyprt_trace_rays"):     # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
         lib.fyprt_trace_rays.argtypes = [vp, C.c_int, vp, u32, vp, C.POINTER(FrameStats)]
         lib.fyprt_trace_rays_device.argtypes = [vp, C.c_int, vp, u32, vp]
@@ -471,6 +475,26 @@ class Context:
         mats = np.ascontiguousarray(np.stack([scene.mesh_matrix(m) for m in mesh_indices]).astype(np.float32).reshape(-1))
         idx = (C.c_uint32 * len(mesh_indices))(*[int(m) for m in mesh_indices])
         self._check(self.lib.fyprt_update_transforms(self.h, idx, mats.ctypes.data_as(C.POINTER(C.c_float)), len(mesh_indices)))
+
+    def update_materials(self, scene, meshes=(), emissive_triangles=None):
+        """A material edit applied on the device (fyprt_update_materials): the whole material table of `scene`, and for the listed
+        meshes their current material index (all their triangles follow).  `emissive_triangles`: None = derive, as upload_scene."""
+        m = np.ascontiguousarray(scene.materials_array(), dtype=MATERIAL_DTYPE)
+        meshes = [int(k) for k in meshes]
+        idx = (C.c_uint32 * max(1, len(meshes)))(*meshes)
+        mat = (C.c_int32 * max(1, len(meshes)))(*[int(scene.meshes[k][2]) for k in meshes])
+        em = None if emissive_triangles is None else np.ascontiguousarray(emissive_triangles, dtype=np.uint32)
+        self._check(self.lib.fyprt_update_materials(self.h, _ptr(m) if len(m) else None, len(m), idx, mat, len(meshes),
+                                                    None if em is None else (em.ctypes.data if len(em) else C.cast((C.c_uint32 * 1)(), C.c_void_p)),
+                                                    0 if em is None else len(em)))
+
+    def export_emissive(self) -> np.ndarray:
+        """The emissive-triangle list in effect (fyprt_export_emissive)."""
+        n = C.c_uint32()
+        self._check(self.lib.fyprt_export_emissive(self.h, None, C.byref(n)))
+        out = np.empty(n.value, dtype=np.uint32)
+        self._check(self.lib.fyprt_export_emissive(self.h, _ptr(out) if n.value else None, C.byref(n)))
+        return out
 
     def compare_image(self, reference, flip_reference_rows=False):
         """(MSE, PSNR) of the current frame against `reference` (uint32 ABGR8, H x W), reduced on the device (MisUtils::ComputeMSE)."""

@@ -13,6 +13,7 @@
 #include <hipcub/hipcub.hpp>
 #include "rt_lbvh.h"
 #include "rt_refit.h"
+#include "rt_materials.h"
 #include "rt_paths.h"
 #include "rt_query.h"
 #include "rt_denoise.h"
@@ -143,6 +144,11 @@ struct fyprt_context {
     bool hostVertsStale = false;                    // world vertices were recomputed on the device: the host copy only follows for emissive meshes
     DevBuf<float4> nodes, leafTris, triPos, triShade, mats; DevBuf<DevTexture> texTable; std::vector<DevBuf<uint32_t>> texPixels;
     DevBuf<uint32_t> emissive; DevBuf<float4> lightRecs; DevBuf<DevLTNode> ltTlas, ltBlas; DevBuf<uint32_t> ltFirst, ltCount, ltRoot, ltLeafOfTri;
+    // fyprt_update_materials: the emissive list as the host handed it over or derived it (host-only contexts answer fyprt_export_emissive
+    // from it; on a device the list a compaction wrote lives in `emissive` alone and the copy is empty), whether it was handed over, and
+    // the call's device scratch, grown on demand and kept (per-material flags, workgroup counts + offsets, reassigned triangle ranges)
+    std::vector<uint32_t> hostEmissive; bool emissiveExplicit = false;
+    DevBuf<uint32_t> matFlags, emCounts; DevBuf<uint4> matRanges;
     DevBuf<unsigned long long> rayCounter;
     DevScene dsc{}; DevCamera dcam{};
     rth::SceneBVH hostBvh; rth::LightTrees hostLt; uint32_t meshCount = 0;
@@ -232,6 +238,20 @@ template <class T> static int alloc_zeroed(fyprt_context* c, DevBuf<T>& b, size_
 static bool is_emissive(const fyprt_material& m) {
     const float ex = m.emission_color[0] * m.emission_power, ey = m.emission_color[1] * m.emission_power, ez = m.emission_color[2] * m.emission_power;
     return ((ex * ex + ey * ey) + ez * ez) > 0.0f;
+}
+
+// Material.cuh:7-16 -> the device's 3 quads per material, and is_emissive per material
+static void pack_materials(const fyprt_material* materials, uint32_t count, std::vector<float>& mats, std::vector<char>& emissiveMat) {
+    mats.assign((size_t)count * 12, 0.0f); emissiveMat.assign(count, 0);
+    for (uint32_t i = 0; i < count; ++i) {
+        const fyprt_material& m = materials[i]; float* q = &mats[(size_t)i * 12];
+        q[0] = m.albedo[0]; q[1] = m.albedo[1]; q[2] = m.albedo[2];
+        uint32_t info = ((m.is_use_albedo_map & 0xFFu) ? 0x80000000u : 0u) | (m.albedo_map_index > 0x7FFFFFFFu ? 0x7FFFFFFFu : m.albedo_map_index);
+        std::memcpy(&q[3], &info, 4);
+        q[4] = m.roughness; q[5] = m.metallic; q[6] = m.emission_power;
+        q[8] = m.emission_color[0]; q[9] = m.emission_color[1]; q[10] = m.emission_color[2];
+        emissiveMat[i] = is_emissive(m);
+    }
 }
 
 // The scheduling parameters every persistent queue shares (TraceQueue, GI2Queue, ShadowQueue, QueryRays); `refillKey`: K_REFILL_LANES
@@ -558,7 +578,7 @@ int fyprt_upload_scene(fyprt_context* c, const fyprt_scene_desc* s) {
     }
     TRY(alloc_upload(c, c->triPos, pos.data(), (size_t)nT * 3)); TRY(alloc_upload(c, c->triShade, shade.data(), (size_t)nT * 4));
     // refit support: vertices + per-triangle indices on the device, nodes grouped by level (levels = 1 first)
-    c->vertexCount = s->vertex_count; c->hostBvhStale = false;
+    c->vertexCount = s->vertex_count; c->hostBvhStale = false; c->hostVertsStale = false;
     c->hostVerts.assign(s->vertices, s->vertices + s->vertex_count); c->objVerts.release(); c->meshFirstVertex.clear();
     c->topoTris.resize((size_t)nT * 4);
     for (uint32_t i = 0; i < nT; ++i) std::memcpy(&c->topoTris[(size_t)i * 4], tri(i), 16);
@@ -587,17 +607,8 @@ int fyprt_upload_scene(fyprt_context* c, const fyprt_scene_desc* s) {
         HIPCHK(c, hipMemcpy(c->hostBvh.tris.data(), c->leafTris.p, c->hostBvh.tris.size() * 48, hipMemcpyDeviceToHost));
     }
     // materials (Material.cuh:7-16 -> 3 quads)
-    std::vector<float> mats((size_t)s->material_count * 12, 0.0f);
-    std::vector<char> emissiveMat(s->material_count, 0);
-    for (uint32_t i = 0; i < s->material_count; ++i) {
-        const fyprt_material& m = s->materials[i]; float* q = &mats[(size_t)i * 12];
-        q[0] = m.albedo[0]; q[1] = m.albedo[1]; q[2] = m.albedo[2];
-        uint32_t info = ((m.is_use_albedo_map & 0xFFu) ? 0x80000000u : 0u) | (m.albedo_map_index > 0x7FFFFFFFu ? 0x7FFFFFFFu : m.albedo_map_index);
-        std::memcpy(&q[3], &info, 4);
-        q[4] = m.roughness; q[5] = m.metallic; q[6] = m.emission_power;
-        q[8] = m.emission_color[0]; q[9] = m.emission_color[1]; q[10] = m.emission_color[2];
-        emissiveMat[i] = is_emissive(m);
-    }
+    std::vector<float> mats; std::vector<char> emissiveMat;
+    pack_materials(s->materials, s->material_count, mats, emissiveMat);
     TRY(alloc_upload(c, c->mats, mats.data(), (size_t)s->material_count * 3));
     // textures
     c->texPixels.clear(); c->texPixels.resize(s->texture_count);
@@ -615,6 +626,7 @@ int fyprt_upload_scene(fyprt_context* c, const fyprt_scene_desc* s) {
     else for (uint32_t i = 0; i < nT; ++i) if (emissiveMat[tri(i)[3]]) em.push_back(i);
     for (uint32_t e : em) if (e >= nT) return c->fail(FYPRT_EINVAL, "fyprt_upload_scene: emissive triangle index out of range");
     TRY(alloc_upload(c, c->emissive, em.data(), em.size()));
+    c->emissiveExplicit = s->emissive_triangles != nullptr;
     // light trees: prebuilt (reference shape) or ours
     rth::LightTrees& lt = c->hostLt; lt = rth::LightTrees();
     c->meshCount = s->mesh_count;
@@ -642,6 +654,7 @@ int fyprt_upload_scene(fyprt_context* c, const fyprt_scene_desc* s) {
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, sync_all(c));
     }
+    c->hostEmissive.swap(em);
     c->haveScene = true;
     return FYPRT_OK;
 }
@@ -670,7 +683,7 @@ int fyprt_update_vertices(fyprt_context* c, const fyprt_vertex* vertices, uint32
     c->dtValid = false;
     const uint32_t nT = (uint32_t)(c->topoTris.size() / 4);
     if (upload(c, c->dverts.p, vertices, c->dverts.bytes())) return FYPRT_EHIP;
-    c->hostVerts.assign(vertices, vertices + vertex_count);
+    c->hostVerts.assign(vertices, vertices + vertex_count); c->hostVertsStale = false;
     if (nT) hipLaunchKernelGGL(k_refresh_triangles, dim3((nT + 255u) / 256u), dim3(256), 0, c->stream, c->dverts.p, c->triIdx.p, c->triPos.p, c->triShade.p, nT);
     TRY(run_refit(c));
     c->hostBvhStale = true;
@@ -734,6 +747,191 @@ int fyprt_update_transforms(fyprt_context* c, const uint32_t* mesh_indices, cons
     if (c->dsc.emissiveCount) hipLaunchKernelGGL(k_build_light_records, dim3((c->dsc.emissiveCount + 255u) / 256u), dim3(256), 0, c->stream, c->dsc, c->lightRecs.p);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, sync_all(c));
+    return FYPRT_OK;
+}
+
+// The emissive list derived ON THE DEVICE from the per-material flags (rt_materials.h): count per workgroup, scan, scatter in ascending
+// triangle order.  Leaves c->emissive sized to the count, which comes back in one 4-byte read.
+static int derive_emissive_on_device(fyprt_context* c, const std::vector<char>& emissiveMat, uint32_t nT, uint32_t* count) {
+    const uint32_t nMat = (uint32_t)emissiveMat.size();
+    *count = 0;
+    if (nT == 0 || nMat == 0) { c->emissive.release(); return FYPRT_OK; }
+    const uint32_t groups = std::min<uint32_t>(kEmMaxGroups, (nT + kEmMinChunk - 1u) / kEmMinChunk);
+    const uint32_t perGroup = (((nT + groups - 1u) / groups + kBlock - 1u) / kBlock) * kBlock;     // whole tiles, groups * perGroup >= nT
+    std::vector<uint32_t> flags(emissiveMat.begin(), emissiveMat.end());
+    if (c->matFlags.n < nMat) HIPCHK(c, c->matFlags.alloc(nMat));
+    if (c->emCounts.n < 2u * kEmMaxGroups + 1u) HIPCHK(c, c->emCounts.alloc(2u * kEmMaxGroups + 1u));
+    TRY(upload(c, c->matFlags.p, flags.data(), (size_t)nMat * 4));
+    uint32_t* counts = c->emCounts.p; uint32_t* offsets = c->emCounts.p + kEmMaxGroups;
+    hipLaunchKernelGGL(k_emissive_count, dim3(groups), dim3(kBlock), 0, c->stream, c->triIdx.p, c->matFlags.p, nMat, nT, perGroup, counts);
+    hipLaunchKernelGGL(k_emissive_scan, dim3(1), dim3(kBlock), 0, c->stream, counts, groups, offsets);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(count, offsets + groups, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, c->emissive.alloc(*count));
+    if (*count) {
+        hipLaunchKernelGGL(k_emissive_scatter, dim3(groups), dim3(kBlock), 0, c->stream, c->triIdx.p, c->matFlags.p, nMat, nT, perGroup, offsets, c->emissive.p, *count);
+        HIPCHK(c, hipGetLastError());
+    }
+    return FYPRT_OK;
+}
+
+// A material edit (SceneManager::PerformAllSceneUpdates with materialsToUpdate / meshMatToBeUpdated, SceneManager.cpp:10-17, :69-85): the
+// whole material table is replaced, the listed meshes (and all their triangles) get another material, the emissive list is the given one
+// or derived again.  The context ends in the state fyprt_upload_scene reaches with the edited description — but the acceleration
+// structure is not touched, and nothing per triangle crosses the bus: table, reassignment and the ordered compaction of the emissive
+// list run on the device (rt_materials.h), the light records by their kernel, the light trees on the host.  An edit that moves no
+// emission (albedo, roughness, metallic, texture switch) stops after table and reassignment.
+int fyprt_update_materials(fyprt_context* c, const fyprt_material* materials, uint32_t material_count, const uint32_t* mesh_indices,
+                           const int32_t* mesh_materials, uint32_t mesh_count, const uint32_t* emissive_triangles, uint32_t emissive_count) {
+    if (!c) return FYPRT_EINVAL;
+    if (!materials && material_count) return c->fail(FYPRT_EINVAL, "fyprt_update_materials: NULL materials with a non-zero count");
+    if (mesh_count && (!mesh_indices || !mesh_materials)) return c->fail(FYPRT_EINVAL, "fyprt_update_materials: NULL mesh array with a non-zero count");
+    const uint32_t nM = (uint32_t)c->topoMeshes.size(), nT = (uint32_t)(c->topoTris.size() / 4), oldCount = (uint32_t)c->topoMats.size();
+    if (material_count < oldCount) return c->fail(FYPRT_EINVAL, "fyprt_update_materials: the material table must not shrink");
+    for (uint32_t k = 0; k < mesh_count; ++k) if (mesh_indices[k] >= nM) return c->fail(FYPRT_EINVAL, "fyprt_update_materials: mesh index out of range");
+    for (uint32_t k = 0; k < mesh_count; ++k) if (mesh_materials[k] < 0 || (uint32_t)mesh_materials[k] >= material_count) return c->fail(FYPRT_EINVAL, "fyprt_update_materials: material index out of range");
+    if (emissive_triangles) for (uint32_t k = 0; k < emissive_count; ++k) if (emissive_triangles[k] >= nT) return c->fail(FYPRT_EINVAL, "fyprt_update_materials: emissive triangle index out of range");
+    if (!c->haveScene) return c->fail(FYPRT_ESTATE, "fyprt_update_materials before fyprt_upload_scene");
+    if (c->prebuiltLightTrees) return c->fail(FYPRT_ESTATE, "fyprt_update_materials: the scene was uploaded with prebuilt light trees; upload it again instead");
+    if (!c->hostOnly) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c)); }
+    c->frameComplete = false;                  // the payload's triangles were shaded with the old materials (fyprt_denoise)
+    c->dtValid = false;
+
+    std::vector<float> mats; std::vector<char> emissiveMat;
+    pack_materials(materials, material_count, mats, emissiveMat);
+    // Does the edit move any emission?  A material whose emission colour or power changed bit-wise, or a reassigned mesh that has
+    // anything to do with an emitter (its old or new material, or the old material of any of its triangles).
+    bool emissionMoved = false;
+    for (uint32_t i = 0; i < oldCount && !emissionMoved; ++i)
+        emissionMoved = std::memcmp(materials[i].emission_color, c->topoMats[i].emission_color, 12) != 0 || std::memcmp(&materials[i].emission_power, &c->topoMats[i].emission_power, 4) != 0;
+    // the reassignment, de-duplicated (the last entry of a mesh wins, as a sequence of edits would have it)
+    std::vector<uint4> ranges;
+    if (mesh_count) {
+        std::vector<int32_t> newMat(nM, -1);
+        for (uint32_t k = 0; k < mesh_count; ++k) newMat[mesh_indices[k]] = mesh_materials[k];
+        for (uint32_t k = 0; k < mesh_count; ++k) {
+            const uint32_t m = mesh_indices[k];
+            if (newMat[m] < 0) continue;                                     // an earlier entry of this mesh has been taken
+            const fyprt_mesh& me = c->topoMeshes[m];
+            ranges.push_back(make_uint4(me.first_triangle, me.triangle_count, (uint32_t)newMat[m], m));
+            newMat[m] = -1;
+        }
+    }
+    // light trees hang on the MESH's material (lighttree_build.cpp): which meshes change their tree, and does any mesh start or stop
+    // being a light (then the node counts move and every tree is rebuilt)
+    std::vector<uint8_t> touched(nM, 0); std::vector<uint8_t> reassigned(nM, 0);
+    bool setChanged = false, anyTouched = false;
+    auto emissionBits = [](const fyprt_material& a, const fyprt_material& b) {
+        return std::memcmp(a.emission_color, b.emission_color, 12) == 0 && std::memcmp(&a.emission_power, &b.emission_power, 4) == 0;
+    };
+    for (const uint4& r : ranges) {
+        const fyprt_mesh& me = c->topoMeshes[r.w];
+        const fyprt_material& was = c->topoMats[me.material_index]; const fyprt_material& is = materials[r.z];
+        reassigned[r.w] = 1;
+        bool emits = is_emissive(was) || emissiveMat[r.z];
+        for (uint32_t t = me.first_triangle; t < me.first_triangle + me.triangle_count && !emits; ++t) emits = is_emissive(c->topoMats[c->topoTris[(size_t)t * 4 + 3]]);
+        if (emits) emissionMoved = true;
+        if (me.triangle_count && is_emissive(was) != (bool)emissiveMat[r.z]) setChanged = true;
+        else if (emissiveMat[r.z] && !emissionBits(was, is)) { touched[r.w] = 1; anyTouched = true; }
+    }
+    // the emissive list stays as it is when it is derived as before and no emission moved, or handed over unchanged
+    bool listSame = !emissionMoved;
+    if (listSame) {
+        if (emissive_triangles) listSame = c->emissiveExplicit && c->hostEmissive.size() == emissive_count && (emissive_count == 0 || std::memcmp(c->hostEmissive.data(), emissive_triangles, (size_t)emissive_count * 4) == 0);
+        else listSame = !c->emissiveExplicit;
+    }
+    if (!listSame || emissionMoved) {
+        for (uint32_t m = 0; m < nM; ++m) {
+            if (reassigned[m] || c->topoMeshes[m].triangle_count == 0) continue;
+            const uint32_t mi = (uint32_t)c->topoMeshes[m].material_index;             // < oldCount
+            if (is_emissive(c->topoMats[mi]) != (bool)emissiveMat[mi]) setChanged = true;
+            else if (emissiveMat[mi] && !emissionBits(c->topoMats[mi], materials[mi])) { touched[m] = 1; anyTouched = true; }
+        }
+    }
+
+    // 1. the table
+    if (material_count != oldCount) { HIPCHK(c, c->mats.alloc((size_t)material_count * 3, c->hostOnly)); c->dsc.mats = c->mats.p; }
+    TRY(upload(c, c->mats.p, mats.data(), mats.size() * 4));
+    c->topoMats.assign(materials, materials + material_count);
+    // 2. the reassigned meshes: their triangles on the device, the host's copy of those ranges
+    if (!ranges.empty()) {
+        for (const uint4& r : ranges) {
+            c->topoMeshes[r.w].material_index = (int32_t)r.z;
+            for (uint32_t t = r.x; t < r.x + r.y; ++t) c->topoTris[(size_t)t * 4 + 3] = r.z;
+        }
+        if (!c->hostOnly) {
+            if (c->matRanges.n < ranges.size()) HIPCHK(c, c->matRanges.alloc(ranges.size()));
+            TRY(upload(c, c->matRanges.p, ranges.data(), ranges.size() * sizeof(uint4)));
+            for (size_t first = 0; first < ranges.size(); first += 65535u) {            // blockIdx.y = the mesh
+                const uint32_t n = (uint32_t)std::min<size_t>(65535u, ranges.size() - first);
+                uint32_t longest = 0; for (uint32_t k = 0; k < n; ++k) longest = std::max(longest, ranges[first + k].y);
+                if (longest == 0) continue;
+                const uint32_t gx = std::min<uint32_t>(64u, (longest + kBlock - 1u) / kBlock);
+                hipLaunchKernelGGL(k_set_mesh_material, dim3(gx, n), dim3(kBlock), 0, c->stream, c->matRanges.p + first, c->triPos.p, c->triShade.p, c->triIdx.p, nT);
+            }
+            HIPCHK(c, hipGetLastError());
+        }
+    }
+    if (listSame && !emissionMoved) {           // albedo, roughness, metallic, texture switch: no light changes
+        if (!c->hostOnly) HIPCHK(c, sync_all(c));
+        return FYPRT_OK;
+    }
+    // 3. the emissive list
+    uint32_t nE = 0;
+    if (emissive_triangles) {
+        c->hostEmissive.assign(emissive_triangles, emissive_triangles + emissive_count);
+        TRY(alloc_upload(c, c->emissive, c->hostEmissive.data(), c->hostEmissive.size()));
+        nE = emissive_count;
+    } else if (c->hostOnly) {
+        c->hostEmissive.clear();
+        for (uint32_t i = 0; i < nT; ++i) if (emissiveMat[c->topoTris[(size_t)i * 4 + 3]]) c->hostEmissive.push_back(i);
+        nE = (uint32_t)c->hostEmissive.size();
+        HIPCHK(c, c->emissive.alloc(nE, true));
+    } else {
+        c->hostEmissive.clear();
+        TRY(derive_emissive_on_device(c, emissiveMat, nT, &nE));
+    }
+    c->emissiveExplicit = emissive_triangles != nullptr;
+    c->dsc.emissive = c->emissive.p; c->dsc.emissiveCount = nE;
+    // 4. the light records (they carry the emission)
+    HIPCHK(c, c->lightRecs.alloc((size_t)nE * 3, c->hostOnly));
+    c->dsc.lightRecs = c->lightRecs.p;
+    if (!c->hostOnly && nE) {
+        hipLaunchKernelGGL(k_build_light_records, dim3((nE + 255u) / 256u), dim3(256), 0, c->stream, c->dsc, c->lightRecs.p);
+        HIPCHK(c, hipGetLastError());
+    }
+    // 5. the light trees, on the host.  The partial rebuild replaces a mesh's tree in place, which needs every mesh to keep its node
+    // count: only when no mesh starts or stops being a light.  After device transform edits the host's vertices followed only the
+    // meshes that were lights when they moved: what the build will read (the meshes that are lights NOW) comes back first.
+    if (setChanged || anyTouched) {
+        if (setChanged && c->hostVertsStale && !c->hostOnly && !c->meshFirstVertex.empty()) {
+            for (uint32_t m = 0; m < nM; ++m) {
+                const uint32_t first = c->meshFirstVertex[m], n = c->meshFirstVertex[m + 1] - first;
+                if (n && is_emissive(c->topoMats[c->topoMeshes[m].material_index]))
+                    HIPCHK(c, hipMemcpyAsync(c->hostVerts.data() + first, c->dverts.p + first, (size_t)n * sizeof(fyprt_vertex), hipMemcpyDeviceToHost, c->stream));
+            }
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
+        TRY(rebuild_light_trees(c, c->hostVerts.data(), setChanged ? nullptr : touched.data()));
+    }
+    if (!c->hostOnly) HIPCHK(c, sync_all(c));
+    return FYPRT_OK;
+}
+
+// The emissive-triangle list in effect (NULL `triangles` = query the count).
+int fyprt_export_emissive(fyprt_context* c, uint32_t* triangles, uint32_t* count) {
+    if (!c) return FYPRT_EINVAL;
+    if (!c->haveScene) return c->fail(FYPRT_ESTATE, "fyprt_export_emissive before fyprt_upload_scene");
+    const uint32_t n = c->hostOnly ? (uint32_t)c->hostEmissive.size() : c->dsc.emissiveCount;
+    if (triangles && n) {
+        if (c->hostOnly) std::memcpy(triangles, c->hostEmissive.data(), (size_t)n * 4);
+        else {                                 // what the frames read
+            HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c));
+            HIPCHK(c, hipMemcpy(triangles, c->emissive.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+        }
+    }
+    if (count) *count = n;
     return FYPRT_OK;
 }
 

@@ -5,6 +5,8 @@
 #include "TextureIO.h"
 #include <cmath>
 #include <cstdint>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 namespace fyprt_host {
@@ -125,8 +127,16 @@ struct Scene {
     }
 };
 
+// A material edit is reported with the renderer's NoteMaterialEdit() (it moves no vertex: the facade applies it on the device); a
+// renderer type that has only the three older hooks gets NoteOtherSceneEdit() as before.
+template <class R, class = void> struct HasNoteMaterialEdit : std::false_type {};
+template <class R> struct HasNoteMaterialEdit<R, decltype(std::declval<R&>().NoteMaterialEdit(), void())> : std::true_type {};
+template <class RendererT> void NoteMaterialEdit(RendererT& renderer) {
+    if constexpr (HasNoteMaterialEdit<RendererT>::value) renderer.NoteMaterialEdit(); else renderer.NoteOtherSceneEdit();
+}
+
 template <class RendererT> void SceneManager::PerformAllSceneUpdates(Scene& scene, RendererT& renderer) {   // SceneManager.cpp:6-130
-    if (!materialsToUpdate.empty()) { renderer.SetSceneToBeUpdatedFlag(true); renderer.NoteOtherSceneEdit(); }
+    if (!materialsToUpdate.empty()) { renderer.SetSceneToBeUpdatedFlag(true); NoteMaterialEdit(renderer); }
     for (const MeshUpdateParam& u : meshesToUpdate) {
         if (!(u.meshTransformToBeUpdated || u.meshMatToBeUpdated)) continue;
         Mesh& mesh = scene.meshes[u.meshIndex];
@@ -141,7 +151,7 @@ template <class RendererT> void SceneManager::PerformAllSceneUpdates(Scene& scen
         }
         if (u.meshMatToBeUpdated) {
             for (uint32_t t = mesh.indexStart / 3; t < mesh.indexStart / 3 + mesh.indexCount / 3; ++t) scene.triangles[t].materialIndex = mesh.materialIndex;
-            renderer.SetSceneToBeUpdatedFlag(true); renderer.NoteOtherSceneEdit();
+            renderer.SetSceneToBeUpdatedFlag(true); NoteMaterialEdit(renderer);     // (the one line a maintainer adds to SceneManager.cpp:80)
         }
     }
     meshesToUpdate.clear(); materialsToUpdate.clear();

@@ -48,22 +48,40 @@ public:
 
     template <class SceneT, class CameraT> void Render(SceneT& scene, CameraT& camera) {   // Renderer.cu:13-284
         if (isSceneUpdated) {                                                                 // :61-69
-            // only vertices moved since the last upload (a transform edit): refit on the device instead of a full rebuild
-            const uint64_t sig = TopologySignature(scene);
-            // (a) nothing but mesh transforms changed and the SceneManager told us which (NoteMeshTransform): 64 bytes per mesh go to the
-            //     device, which recomputes the world vertices itself;  (b) same topology: every world vertex is uploaded, refit on the device
-            if (m_HaveScene && sig == m_TopologySig && !m_PendingTransforms.empty() && !m_OtherEdits &&
-                fyprt_update_transforms(m_Ctx, m_PendingMeshes.data(), m_PendingTransforms.data(), (uint32_t)m_PendingMeshes.size()) == FYPRT_OK) {
-                ++m_Refits; ++m_TransformUpdates;
-            } else if (m_HaveScene && sig == m_TopologySig &&
-                fyprt_update_vertices(m_Ctx, reinterpret_cast<const fyprt_vertex*>(scene.worldVertices.data()), (uint32_t)scene.worldVertices.size()) == FYPRT_OK) {
-                ++m_Refits;
-            } else if (UploadScene(scene)) {                 // remember the topology only of a scene the library really holds
-                m_TopologySig = sig; m_HaveScene = true; ++m_Uploads;
-            } else {
-                m_HaveScene = false;
+            // The scene's signature has two parts.  Structure (counts, triangle vertex indices, mesh ranges, texture identities): a change
+            // means a full upload.  Materials (table, per-triangle and per-mesh material index, emissive list): a change alone is applied
+            // on the device by fyprt_update_materials, and the acceleration structure is not touched.
+            const uint64_t ssig = StructureSignature(scene), msig = MaterialSignature(scene);
+            bool done = false;
+            if (m_HaveScene && ssig == m_StructureSig) {
+                // geometry — (a) nothing but mesh transforms moved vertices and the SceneManager told us which (NoteMeshTransform): 64 bytes
+                // per mesh go to the device, which recomputes the world vertices itself;  (b) an edit we know nothing about, or the flag
+                // alone: every world vertex is uploaded, refit on the device;  (c) a material edit alone moves no vertex
+                bool ok = true;
+                if (!m_PendingTransforms.empty() && !m_OtherEdits) {
+                    ok = fyprt_update_transforms(m_Ctx, m_PendingMeshes.data(), m_PendingTransforms.data(), (uint32_t)m_PendingMeshes.size()) == FYPRT_OK;
+                    if (ok) { ++m_Refits; ++m_TransformUpdates; }
+                }
+                if ((m_OtherEdits || !ok || (m_PendingTransforms.empty() && !m_MaterialEdits))) {
+                    ok = fyprt_update_vertices(m_Ctx, reinterpret_cast<const fyprt_vertex*>(scene.worldVertices.data()), (uint32_t)scene.worldVertices.size()) == FYPRT_OK;
+                    if (ok) ++m_Refits;
+                }
+                // materials — after the geometry, so that a tick with both edits does fyprt_update_transforms, then fyprt_update_materials
+                if (ok && msig != m_MaterialSig) {
+                    ok = UpdateMaterials(scene);
+                    if (ok) { m_MaterialSig = msig; ++m_MaterialUpdates; }
+                }
+                done = ok;
             }
-            isSceneUpdated = false; m_PendingMeshes.clear(); m_PendingTransforms.clear(); m_OtherEdits = false;
+            if (!done) {
+                if (UploadScene(scene)) {                    // remember the signature only of a scene the library really holds
+                    m_StructureSig = ssig; m_MaterialSig = msig; m_HaveScene = true; ++m_Uploads;
+                    KeepMaterialIndices(scene);
+                } else {
+                    m_HaveScene = false;
+                }
+            }
+            isSceneUpdated = false; m_PendingMeshes.clear(); m_PendingTransforms.clear(); m_OtherEdits = false; m_MaterialEdits = false;
         }
         fyprt_camera_desc c{};                                                                // :70 CameraToGPU
         std::memcpy(c.projection, &camera.GetProjection(), 64); std::memcpy(c.view, &camera.GetView(), 64);
@@ -110,30 +128,71 @@ public:
     void SetSceneToBeUpdatedFlag(bool flag) { isSceneUpdated = flag; }
     // Called by SceneManager::PerformAllSceneUpdates next to SetSceneToBeUpdatedFlag for a mesh whose transform changed (its
     // Mesh::worldTransformMatrix, column-major) — lets Render() send the matrix instead of the mesh's vertices.  Any other edit
-    // (material change, ...) is reported with NoteOtherSceneEdit() and takes the general path.
+    // that may have moved vertices is reported with NoteOtherSceneEdit() and takes the general path; a material edit (a material's fields, a
+    // mesh's material) with NoteMaterialEdit(): it moves no vertex, and Render() finds what changed by comparing with what it uploaded.
     void NoteMeshTransform(uint32_t meshIndex, const float* matrix16) { m_PendingMeshes.push_back(meshIndex); m_PendingTransforms.insert(m_PendingTransforms.end(), matrix16, matrix16 + 16); }
     void NoteOtherSceneEdit() { m_OtherEdits = true; }
+    void NoteMaterialEdit() { m_MaterialEdits = true; }
     uint32_t GetTransformUpdateCount() const { return m_TransformUpdates; }
     void SetPresenter(std::function<void(const uint32_t*, uint32_t, uint32_t)> p) { m_Present = std::move(p); }
     const fyprt_frame_stats& GetLastFrameStats() const { return m_LastStats; }
     fyprt_context* GetContext() const { return m_Ctx; }
     uint32_t GetSceneUploadCount() const { return m_Uploads; }
     uint32_t GetSceneRefitCount() const { return m_Refits; }
+    uint32_t GetMaterialUpdateCount() const { return m_MaterialUpdates; }
 
 private:
-    // FNV-1a over everything of the scene except vertex positions / normals: triangles (indices + material), meshes, materials,
-    // emissive list, texture identities, vertex count
-    template <class SceneT> static uint64_t TopologySignature(const SceneT& scene) {
+    // FNV-1a over everything of the scene except vertex positions / normals, in two parts.  Structure: vertex / triangle / mesh / texture
+    // counts, triangle vertex indices, mesh ranges, texture identities.  Materials: the table, the material index of every triangle and
+    // mesh, the emissive list.
+    struct Fnv {
         uint64_t h = 1469598103934665603ull;
-        auto mix = [&h](const void* p, size_t n) { const uint8_t* b = (const uint8_t*)p; for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; } };
-        const uint64_t counts[5] = {scene.worldVertices.size(), scene.triangles.size(), scene.meshes.size(), scene.materials.size(), scene.textures.size()};
-        mix(counts, sizeof counts);
-        for (const auto& t : scene.triangles) { const uint32_t v[4] = {t.v0, t.v1, t.v2, (uint32_t)t.materialIndex}; mix(v, sizeof v); }
-        for (const auto& m : scene.meshes) { const uint32_t v[3] = {m.indexStart, m.indexCount, (uint32_t)m.materialIndex}; mix(v, sizeof v); }
-        if (!scene.materials.empty()) mix(scene.materials.data(), scene.materials.size() * sizeof(scene.materials[0]));
-        if (!scene.emissiveTriangles.empty()) mix(scene.emissiveTriangles.data(), scene.emissiveTriangles.size() * 4);
-        for (const auto& t : scene.textures) { const uint64_t v[3] = {(uint64_t)(uintptr_t)t.pixels, t.width, t.height}; mix(v, sizeof v); }
-        return h;
+        void mix(const void* p, size_t n) { const uint8_t* b = (const uint8_t*)p; for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; } }
+    };
+    template <class SceneT> static uint64_t StructureSignature(const SceneT& scene) {
+        Fnv f;
+        const uint64_t counts[4] = {scene.worldVertices.size(), scene.triangles.size(), scene.meshes.size(), scene.textures.size()};
+        f.mix(counts, sizeof counts);
+        for (const auto& t : scene.triangles) { const uint32_t v[3] = {t.v0, t.v1, t.v2}; f.mix(v, sizeof v); }
+        for (const auto& m : scene.meshes) { const uint32_t v[2] = {m.indexStart, m.indexCount}; f.mix(v, sizeof v); }
+        for (const auto& t : scene.textures) { const uint64_t v[3] = {(uint64_t)(uintptr_t)t.pixels, t.width, t.height}; f.mix(v, sizeof v); }
+        return f.h;
+    }
+    template <class SceneT> static uint64_t MaterialSignature(const SceneT& scene) {
+        Fnv f;
+        const uint64_t counts[2] = {scene.materials.size(), scene.emissiveTriangles.size()};
+        f.mix(counts, sizeof counts);
+        for (const auto& t : scene.triangles) { const int32_t v = t.materialIndex; f.mix(&v, 4); }
+        for (const auto& m : scene.meshes) { const int32_t v = m.materialIndex; f.mix(&v, 4); }
+        if (!scene.materials.empty()) f.mix(scene.materials.data(), scene.materials.size() * sizeof(scene.materials[0]));
+        if (!scene.emissiveTriangles.empty()) f.mix(scene.emissiveTriangles.data(), scene.emissiveTriangles.size() * 4);
+        return f.h;
+    }
+    template <class SceneT> void KeepMaterialIndices(const SceneT& scene) {
+        m_TriMaterial.resize(scene.triangles.size()); m_MeshMaterial.resize(scene.meshes.size()); m_MaterialCount = scene.materials.size();
+        for (size_t i = 0; i < m_TriMaterial.size(); ++i) m_TriMaterial[i] = scene.triangles[i].materialIndex;
+        for (size_t i = 0; i < m_MeshMaterial.size(); ++i) m_MeshMaterial[i] = scene.meshes[i].materialIndex;
+    }
+    // The material part changed, the structure did not: fyprt_update_materials with the whole table, the meshes whose material index
+    // differs from what the library holds, and scene.emissiveTriangles exactly as UploadScene passes it.  The call can only say "every
+    // triangle of a mesh takes the mesh's material" (SceneManager.cpp:75-79): an edit it cannot express (a lone triangle's material, a
+    // shrunken table) returns false, and the scene is uploaded again.
+    template <class SceneT> bool UpdateMaterials(const SceneT& scene) {
+        if (scene.materials.size() < m_MaterialCount || m_TriMaterial.size() != scene.triangles.size() || m_MeshMaterial.size() != scene.meshes.size()) return false;
+        std::vector<uint32_t> meshes; std::vector<int32_t> materials;
+        for (size_t m = 0; m < scene.meshes.size(); ++m) {
+            const auto& me = scene.meshes[m];
+            const bool reassigned = me.materialIndex != m_MeshMaterial[m];
+            for (uint32_t t = me.indexStart / 3u; t < me.indexStart / 3u + me.indexCount / 3u; ++t)
+                if (scene.triangles[t].materialIndex != (reassigned ? me.materialIndex : m_TriMaterial[t])) return false;
+            if (reassigned) { meshes.push_back((uint32_t)m); materials.push_back(me.materialIndex); }
+        }
+        const int rc = fyprt_update_materials(m_Ctx, reinterpret_cast<const fyprt_material*>(scene.materials.data()), (uint32_t)scene.materials.size(),
+                                              meshes.data(), materials.data(), (uint32_t)meshes.size(),
+                                              scene.emissiveTriangles.empty() ? nullptr : scene.emissiveTriangles.data(), (uint32_t)scene.emissiveTriangles.size());
+        if (rc != FYPRT_OK) return false;
+        KeepMaterialIndices(scene);
+        return true;
     }
     template <class SceneT> bool UploadScene(SceneT& scene) {                                 // SceneToGPU, Scene_GPU.cpp:6-81
         fyprt_scene_desc d{};
@@ -172,8 +231,9 @@ private:
     std::vector<uint32_t> m_RenderImageData;
     std::vector<float> m_AccumulationData;
     bool isSceneUpdated = true;
-    bool m_HaveScene = false; uint64_t m_TopologySig = 0; uint32_t m_Uploads = 0, m_Refits = 0, m_TransformUpdates = 0;
-    std::vector<uint32_t> m_PendingMeshes; std::vector<float> m_PendingTransforms; bool m_OtherEdits = false;
+    bool m_HaveScene = false; uint64_t m_StructureSig = 0, m_MaterialSig = 0; uint32_t m_Uploads = 0, m_Refits = 0, m_TransformUpdates = 0, m_MaterialUpdates = 0;
+    std::vector<uint32_t> m_PendingMeshes; std::vector<float> m_PendingTransforms; bool m_OtherEdits = false, m_MaterialEdits = false;
+    std::vector<int32_t> m_TriMaterial, m_MeshMaterial; size_t m_MaterialCount = 0;     // what the library holds (UpdateMaterials)
     std::function<void(const uint32_t*, uint32_t, uint32_t)> m_Present;
     fyprt_frame_stats m_LastStats{};
 };

@@ -234,6 +234,30 @@ int fyprt_read_buffer(fyprt_context* ctx, int which /* enum fyprt_buffer */, voi
  * their kernel, the light trees on the host.  Not available for scenes uploaded with prebuilt light trees. */
 int fyprt_update_vertices(fyprt_context* ctx, const fyprt_vertex* vertices, uint32_t vertex_count);
 
+/* A material edit — SceneManager::PerformAllSceneUpdates with materialsToUpdate / meshMatToBeUpdated (SceneManager.cpp:10-17, :69-85),
+ * WalnutApp.cpp:702-723: a material's albedo, roughness, metallic, emission, texture switch or index changed, a mesh got another material,
+ * a material was created.  `materials` is the WHOLE table and replaces the uploaded one (material_count may be larger than the uploaded
+ * count, never smaller); every listed mesh gets material_index = mesh_materials[k], and so do ALL its triangles (SceneManager.cpp:75-79);
+ * `emissive_triangles` is read as the scene description's (NULL = derive).  Afterwards the context is in the state fyprt_upload_scene reaches
+ * with the edited description — every later frame, query, exported light tree and emissive list is bit-identical — except that the
+ * acceleration structure is NOT touched (fyprt_export_bvh returns the same bytes, a refitted tree included).  On the device: the 48-byte
+ * material records, the reassigned triangles' material index, the emissive list (an ordered compaction: ascending triangle order, as
+ * upload derives it) and the light records; the light trees are rebuilt on the host.  An edit that moves no emission (no material's
+ * emission colour or power changed bit-wise, no reassigned mesh with an emissive old or new material, the emissive list derived as
+ * before or handed over unchanged) only writes the table and the reassigned triangles.
+ * Frame index, accumulation, reservoirs and ReSTIR history are kept, as upload keeps them; the last frame is no longer denoisable and the
+ * temporal history is dropped.  Blocking: pipelined frames are waited for first, everything the call launches is complete on return.
+ * Errors, in this order: FYPRT_EINVAL for a NULL context, NULL materials with a non-zero count, a NULL mesh array with mesh_count > 0,
+ * material_count below the current count, a mesh index out of range, a material index < 0 or >= material_count, an emissive triangle
+ * index >= the triangle count; FYPRT_ESTATE before fyprt_upload_scene and on a scene uploaded with prebuilt light trees.  Host-only
+ * contexts are supported (everything but the device work).  A later render call answers FYPRT_ENOLIGHT as after an upload when the
+ * edit leaves no emitter.  The scene is per context: call it on every member of a group or communicator between frames. */
+int fyprt_update_materials(fyprt_context* ctx, const fyprt_material* materials, uint32_t material_count,
+                           const uint32_t* mesh_indices, const int32_t* mesh_materials, uint32_t mesh_count,
+                           const uint32_t* emissive_triangles, uint32_t emissive_count);
+/* The emissive-triangle list in effect (Scene::emissiveTriangles as uploaded, derived or updated).  NULL `triangles` queries the count. */
+int fyprt_export_emissive(fyprt_context* ctx, uint32_t* triangles, uint32_t* count);
+
 /* Renderer::ResetFrameIndex / GetCurrentFrameIndex (Renderer.h:47,49). */
 int fyprt_reset_frame_index(fyprt_context* ctx);
 uint32_t fyprt_frame_index(const fyprt_context* ctx);
@@ -419,9 +443,9 @@ int fyprt_render_rays_device(fyprt_context* ctx, const fyprt_settings* settings,
  *   So iterations = 0 with demodulate_albedo = 0 returns the frame's own image bit for bit.
  * Errors, in this order: FYPRT_EINVAL for a NULL context / params, a parameter out of range or non-finite, (device entry) rgba8 not
  * 4-byte or radiance4 not 16-byte aligned, both outputs NULL; FYPRT_ESTATE on a host-only context, when no complete frame was rendered
- * since the last fyprt_resize, fyprt_upload_scene, fyprt_update_vertices or fyprt_update_transforms (each of them invalidates the frame
- * for the denoiser: the payload's triangle indices and texture coordinates belong to the scene they were traced in; materials and
- * textures change with fyprt_upload_scene only), between the two parts of a fyprt_render_part frame, and on a context that does not
+ * since the last fyprt_resize, fyprt_upload_scene, fyprt_update_vertices, fyprt_update_transforms or fyprt_update_materials (each of
+ * them invalidates the frame for the denoiser: the payload's triangle indices and texture coordinates belong to the scene they were
+ * traced in, and its albedo to the materials it was shaded with; textures change with fyprt_upload_scene only), between the two parts of a fyprt_render_part frame, and on a context that does not
  * render every row (a fyprt_set_rows band, fyprt_set_row_stripes, a group or communicator member).  Multi-GPU denoising needs a halo of
  * 2 * (2^iterations - 1) rows from the neighbouring bands and is out of scope.
  * No frame state moves: accumulation, image (internal or external), payload, depth, normals, reservoirs, frame index, frame timings and
@@ -483,7 +507,8 @@ int fyprt_denoise_device(fyprt_context* ctx, const fyprt_denoise_params* params,
  *   So the first call after a reset with iterations = 0 and demodulate_albedo = 0 returns the frame's own image bit for bit, and
  *   history_limit = 1 makes every call a first call.
  * The history is dropped — the next call behaves as a first call — by fyprt_resize, fyprt_upload_scene, fyprt_update_vertices,
- * fyprt_update_transforms (world positions of an edited scene are not comparable) and fyprt_denoise_temporal_reset.
+ * fyprt_update_transforms (world positions of an edited scene are not comparable), fyprt_update_materials (nor are its colours) and
+ * fyprt_denoise_temporal_reset.
  * Errors, in this order: FYPRT_EINVAL for a NULL context / params, history_limit outside 1..256, feedback > 1, normal_min or plane_max
  * not finite, plane_max <= 0; then everything fyprt_denoise refuses, in its order, with params->spatial (its FYPRT_EINVAL cases, then
  * its FYPRT_ESTATE cases).  Multi-GPU bands are out of scope as there.
