@@ -183,6 +183,7 @@ EXPORTED_SYMBOLS = [
     "fyprt_denoise_temporal_default_params", "fyprt_denoise_temporal", "fyprt_denoise_temporal_device", "fyprt_denoise_temporal_reset",
     "fyprt_live_device_bytes",
     "fyprt_update_materials", "fyprt_export_emissive",
+    "fyprt_denoise_temporal_set_motion",
 ]
 
 
@@ -256,6 +257,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
         lib.fyprt_denoise_temporal.argtypes = [vp, C.POINTER(TemporalParams), vp, vp, C.POINTER(FrameStats)]
         lib.fyprt_denoise_temporal_device.argtypes = [vp, C.POINTER(TemporalParams), vp, vp]
         lib.fyprt_denoise_temporal_reset.argtypes = [vp]
+    if hasattr(lib, "fyprt_denoise_temporal_set_motion"):   # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
+        lib.fyprt_denoise_temporal_set_motion.argtypes = [vp, C.c_int]
     lib.fyprt_group_create.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(u32), C.POINTER(vp)]
     lib.fyprt_group_destroy.argtypes = [vp]
     lib.fyprt_group_destroy.restype = None
@@ -470,9 +473,14 @@ class Context:
         first = [tr["vertex_start"] for tr in scene.mesh_transforms] + [len(v)]
         self._check(self.lib.fyprt_set_object_vertices(self.h, v.ctypes.data, len(v), (C.c_uint32 * len(first))(*first)))
 
-    def update_transforms(self, scene, mesh_indices):
-        """A transform edit applied on the device: 64 bytes per mesh (Scene.mesh_matrix) instead of its vertices."""
-        mats = np.ascontiguousarray(np.stack([scene.mesh_matrix(m) for m in mesh_indices]).astype(np.float32).reshape(-1))
+    def update_transforms(self, scene, mesh_indices, matrices=None):
+        """A transform edit applied on the device: 64 bytes per mesh (Scene.mesh_matrix) instead of its vertices.  `matrices`: one
+        [col][row] matrix per listed mesh to apply instead of the scene's current ones (the host scene is then not read)."""
+        if matrices is None:
+            matrices = [scene.mesh_matrix(m) for m in mesh_indices]
+        if len(matrices) != len(mesh_indices):
+            raise ValueError("update_transforms: one matrix per mesh index")
+        mats = np.ascontiguousarray(np.stack([np.asarray(M, dtype=np.float32).reshape(4, 4) for M in matrices]).reshape(-1))
         idx = (C.c_uint32 * len(mesh_indices))(*[int(m) for m in mesh_indices])
         self._check(self.lib.fyprt_update_transforms(self.h, idx, mats.ctypes.data_as(C.POINTER(C.c_float)), len(mesh_indices)))
 
@@ -696,6 +704,12 @@ class Context:
     def denoise_temporal_reset(self):
         """Drops the temporal history (fyprt_denoise_temporal_reset): the next denoise_temporal* call behaves as a first call."""
         self._check(self.lib.fyprt_denoise_temporal_reset(self.h))
+
+    def denoise_temporal_set_motion(self, on: bool):
+        """Object motion for the temporal denoiser (fyprt_denoise_temporal_set_motion): with it on, update_vertices / update_transforms
+        keep the history and the next denoise_temporal* call reprojects through the geometry of the frame denoised before.  A change of
+        the mode drops the history."""
+        self._check(self.lib.fyprt_denoise_temporal_set_motion(self.h, 1 if on else 0))
 
     def export_lighttrees(self, mesh_count: int):
         tc, tr, bt = C.c_uint32(), C.c_uint32(), C.c_uint32()

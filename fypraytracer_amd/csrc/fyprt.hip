@@ -183,7 +183,15 @@ struct fyprt_context {
     // frame the last temporal call denoised (what the next one reprojects with); dtValid: dt.hist[dtCur] holds a history
     struct Temporal { DevBuf<float4> hist[2]; DevBuf<float> var[2]; } dt; Event dtEv[4]; int dtCur = 0; bool dtValid = false;
     float camPV[16] = {}, framePV[16] = {}, dtPV[16] = {};
-    void release_temporal() { dt = Temporal(); dtValid = false; }
+    // object motion (fyprt_denoise_temporal_set_motion): with the mode on a geometry edit keeps the history and copies the world vertices
+    // as the frame denoised last saw them into dtSnap (allocated at the first snapshot, with a moved flag per triangle).  dtSnapPending:
+    // from that copy until the next temporal call, which reprojects through it; [dtEditLo, dtEditHi): the triangles of the meshes edited
+    // since the copy — all others are bit-identical in both vertex sets, their flags stay at the zeros the snapshot left
+    bool dtMotion = false, dtSnapPending = false; uint32_t dtEditLo = 0, dtEditHi = 0;
+    DevBuf<DevVertex> dtSnap; DevBuf<uint8_t> dtMoved;
+    void drop_history() { dtValid = false; dtSnapPending = false; }
+    void release_temporal() { dt = Temporal(); drop_history(); }
+    void release_snapshot() { dtSnap.release(); dtMoved.release(); dtSnapPending = false; }
     void release_denoise() { dn = Denoise(); albedoValid = false; }
 
     fyprt_context() { for (int k = 0; k < K_COUNT; ++k) tuning[k] = kTuning[k].def; }
@@ -530,7 +538,7 @@ int fyprt_upload_scene(fyprt_context* c, const fyprt_scene_desc* s) {
         return c->fail(FYPRT_EINVAL, "fyprt_upload_scene: NULL array with non-zero count");
     if (!c->hostOnly) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c)); }
     c->frameComplete = false;                  // the payload's triangle indices belong to the scene they were traced in (fyprt_denoise)
-    c->dtValid = false;                        // world positions of another scene are not comparable (fyprt_denoise_temporal)
+    c->drop_history(); c->release_snapshot();  // world positions of another scene are not comparable (fyprt_denoise_temporal)
     const uint8_t* tb = (const uint8_t*)s->triangles;
     auto tri = [&](uint32_t i) { return reinterpret_cast<const uint32_t*>(tb + (size_t)i * s->triangle_stride); };
     for (uint32_t i = 0; i < s->triangle_count; ++i) {
@@ -669,6 +677,28 @@ static int rebuild_light_trees(fyprt_context* c, const fyprt_vertex* verts, cons
     return upload_light_trees(c, nT, nM);
 }
 
+// What a geometry edit means to the temporal denoiser (both streams idle).  Motion mode off: the history is dropped.  On: it is kept, and
+// the first edit after a temporal call copies the world vertices that call's frame was traced in: device to device on the context
+// stream, so ahead of whatever the edit enqueues there.  An edit that writes dverts any other way waits for the copy first.
+static int temporal_edit_begin(fyprt_context* c) {
+    if (!c->dtMotion) { c->dtValid = false; return FYPRT_OK; }
+    if (!c->dtValid || c->dtSnapPending) return FYPRT_OK;
+    const uint32_t nT = (uint32_t)(c->topoTris.size() / 4);
+    if (c->dtSnap.n != c->dverts.n) HIPCHK(c, c->dtSnap.alloc(c->dverts.n));
+    if (c->dtMoved.n != nT) HIPCHK(c, c->dtMoved.alloc(nT));
+    if (c->dverts.n) HIPCHK(c, hipMemcpyAsync(c->dtSnap.p, c->dverts.p, c->dverts.bytes(), hipMemcpyDeviceToDevice, c->stream));
+    if (nT) HIPCHK(c, hipMemsetAsync(c->dtMoved.p, 0, nT, c->stream));
+    c->dtSnapPending = true; c->dtEditLo = c->dtEditHi = 0;
+    return FYPRT_OK;
+}
+// ... and every edit widens the triangle range the next temporal call compares with the snapshot by [firstTri, firstTri + triCount)
+static void temporal_edit_range(fyprt_context* c, uint32_t firstTri, uint32_t triCount) {
+    if (!c->dtSnapPending || !triCount) return;
+    const bool empty = c->dtEditHi == c->dtEditLo;
+    c->dtEditLo = empty ? firstTri : std::min(c->dtEditLo, firstTri);
+    c->dtEditHi = empty ? firstTri + triCount : std::max(c->dtEditHi, firstTri + triCount);
+}
+
 // Scene geometry moved, topology unchanged (SceneManager::PerformAllSceneUpdates with a transform edit, SceneManager.cpp:24-66):
 // new world vertices -> per-triangle records, leaf triangles and the tree's boxes are refreshed ON THE DEVICE (rt_refit.h),
 // the per-light records are rebuilt by their kernel, the (small) light trees on the host.  The tree keeps its shape.
@@ -680,8 +710,10 @@ int fyprt_update_vertices(fyprt_context* c, const fyprt_vertex* vertices, uint32
     if (c->prebuiltLightTrees) return c->fail(FYPRT_ESTATE, "fyprt_update_vertices: the scene was uploaded with prebuilt light trees; upload it again instead");
     HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c));
     c->frameComplete = false;                  // new vertices may carry new texture coordinates: the last frame can no longer be denoised
-    c->dtValid = false;
     const uint32_t nT = (uint32_t)(c->topoTris.size() / 4);
+    TRY(temporal_edit_begin(c)); temporal_edit_range(c, 0, nT);
+    // the upload below is a blocking copy, which the non-blocking context stream does not order: the snapshot must have read dverts first
+    if (c->dtSnapPending) HIPCHK(c, hipStreamSynchronize(c->stream));
     if (upload(c, c->dverts.p, vertices, c->dverts.bytes())) return FYPRT_EHIP;
     c->hostVerts.assign(vertices, vertices + vertex_count); c->hostVertsStale = false;
     if (nT) hipLaunchKernelGGL(k_refresh_triangles, dim3((nT + 255u) / 256u), dim3(256), 0, c->stream, c->dverts.p, c->triIdx.p, c->triPos.p, c->triShade.p, nT);
@@ -724,7 +756,8 @@ int fyprt_update_transforms(fyprt_context* c, const uint32_t* mesh_indices, cons
     for (uint32_t k = 0; k < count; ++k) if (mesh_indices[k] >= nM) return c->fail(FYPRT_EINVAL, "fyprt_update_transforms: mesh index out of range");
     HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c));
     c->frameComplete = false;                  // as fyprt_update_vertices
-    c->dtValid = false;
+    TRY(temporal_edit_begin(c));
+    for (uint32_t k = 0; k < count; ++k) temporal_edit_range(c, c->topoMeshes[mesh_indices[k]].first_triangle, c->topoMeshes[mesh_indices[k]].triangle_count);
     std::vector<uint8_t> touched(nM, 0);
     bool lightsMoved = false;
     for (uint32_t k = 0; k < count; ++k) {
@@ -796,7 +829,7 @@ int fyprt_update_materials(fyprt_context* c, const fyprt_material* materials, ui
     if (c->prebuiltLightTrees) return c->fail(FYPRT_ESTATE, "fyprt_update_materials: the scene was uploaded with prebuilt light trees; upload it again instead");
     if (!c->hostOnly) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c)); }
     c->frameComplete = false;                  // the payload's triangles were shaded with the old materials (fyprt_denoise)
-    c->dtValid = false;
+    c->drop_history();
 
     std::vector<float> mats; std::vector<char> emissiveMat;
     pack_materials(materials, material_count, mats, emissiveMat);
@@ -1881,7 +1914,7 @@ static int enqueue_temporal(fyprt_context* c, const fyprt_temporal_params* p, ui
     const fyprt_denoise_params& sp = p->spatial;
     const size_t n = (size_t)c->W * c->H;
     if (c->dt.hist[0].n != 4 * n) {
-        c->dtValid = false;
+        c->drop_history();
         for (int k = 0; k < 2; ++k) { HIPCHK(c, c->dt.hist[k].alloc(4 * n)); HIPCHK(c, c->dt.var[k].alloc(n)); }
     }
     DnFrame fr;
@@ -1892,8 +1925,16 @@ static int enqueue_temporal(fyprt_context* c, const fyprt_temporal_params* p, ui
     tc.sigmaPlane = sp.sigma_plane; tc.normalPow = sp.normal_power_log2;
     const int next = c->dtCur ^ 1;
     float4* hist = c->dt.hist[next].p;
-    hipLaunchKernelGGL(k_dt_reproject, dim3(((c->W + 15u) / 16u) * ((c->H + 15u) / 16u)), dim3(256), 0, c->stream, fr, tc, c->dn.col[0].p,
-                       c->dt.hist[c->dtCur].p, hist, c->dn.col[1].p, c->dt.var[0].p);
+    const dim3 grid(((c->W + 15u) / 16u) * ((c->H + 15u) / 16u));
+    if (c->dtValid && c->dtSnapPending && c->dtEditHi > c->dtEditLo) {       // object motion: the flags of the edited range, then the motion form
+        const uint32_t count = c->dtEditHi - c->dtEditLo;
+        hipLaunchKernelGGL(k_dt_moved, dim3((count + 255u) / 256u), dim3(256), 0, c->stream, c->dverts.p, c->dtSnap.p, c->triIdx.p, c->dtMoved.p, c->dtEditLo, count);
+        ++*launched;
+        const DtMotion mo{c->payload.p, c->dtMoved.p, c->triIdx.p, c->triPos.p, c->dtSnap.p};
+        hipLaunchKernelGGL(k_dt_reproject_motion, grid, dim3(256), 0, c->stream, fr, tc, mo, c->dn.col[0].p, c->dt.hist[c->dtCur].p, hist, c->dn.col[1].p, c->dt.var[0].p);
+    } else {
+        hipLaunchKernelGGL(k_dt_reproject, grid, dim3(256), 0, c->stream, fr, tc, c->dn.col[0].p, c->dt.hist[c->dtCur].p, hist, c->dn.col[1].p, c->dt.var[0].p);
+    }
     ++*launched;
     if (ev) HIPCHK(c, hipEventRecord(ev[2], c->stream));
     for (uint32_t k = 0; k < sp.iterations; ++k) {           // colour: dn.col[1] -> [0] -> [1] ...; variance: dt.var[0] -> [1] -> [0] ...
@@ -1910,7 +1951,7 @@ static int enqueue_temporal(fyprt_context* c, const fyprt_temporal_params* p, ui
         ++*launched;
     }
     TRY(end_denoise(c, fr, sp.iterations, c->dn.col[1].p, ev ? ev + 3 : nullptr, launched));
-    c->dtCur = next; c->dtValid = true; std::memcpy(c->dtPV, c->framePV, 64);
+    c->dtCur = next; c->dtValid = true; c->dtSnapPending = false; std::memcpy(c->dtPV, c->framePV, 64);
     return FYPRT_OK;
 }
 
@@ -1929,7 +1970,17 @@ int fyprt_denoise_temporal_device(fyprt_context* c, const fyprt_temporal_params*
 
 int fyprt_denoise_temporal_reset(fyprt_context* c) {
     if (!c) return FYPRT_EINVAL;
-    c->dtValid = false;
+    c->drop_history();
+    return FYPRT_OK;
+}
+
+int fyprt_denoise_temporal_set_motion(fyprt_context* c, int enabled) {
+    if (!c) return FYPRT_EINVAL;
+    if (enabled != 0 && enabled != 1) return c->fail(FYPRT_EINVAL, "fyprt_denoise_temporal_set_motion: enabled must be 0 or 1");
+    if (c->dtMotion == (enabled == 1)) return FYPRT_OK;
+    if (!c->hostOnly && c->dtSnap.p) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c)); }     // a call in flight may read the snapshot
+    c->dtMotion = enabled == 1;
+    c->drop_history(); c->release_snapshot();
     return FYPRT_OK;
 }
 

@@ -15,10 +15,17 @@
 //                    memory, so the record stays 48 bytes and the LDS table and bank layout of DnTile hold as they are.  The 3 x 3
 //                    variance prefilter reads rows at distance 1, which a tile whose rows lie STEP apart does not hold: nine 4-byte
 //                    gathers per pixel.  Iteration 0 also writes its colour into the new history record (feedback).
+//   k_dt_moved / k_dt_reproject_motion : object motion (fyprt_denoise_temporal_set_motion), launched only while a vertex snapshot is
+//                    pending.  k_dt_moved: one thread per triangle of the edited range, a byte per triangle — do the 18 position and normal
+//                    floats of its vertices differ bit-wise between the snapshot and now.  The motion form of the reprojection loads that
+//                    byte per filterable pixel and, where it is set, rebuilds the hit's point and shading normal in the snapshot
+//                    geometry from its barycentrics in the current triangle (triIdx 16 B, triPos 48 B, three 32-byte snapshot vertices);
+//                    a wave that sees no moved triangle pays the byte alone.
 // Between the kernels the variance buffer holds -1 for a pixel that is not filterable (the record and the contract say 0 there): the
 // prefilter's taps then need no second load for the flag.
 #pragma once
 #include "rt_denoise.h"
+#include "rt_refit.h"
 
 namespace rt {
 
@@ -29,10 +36,36 @@ struct DtCall {                      // what k_dt_reproject needs about the call
     uint32_t normalPow;
 };
 
+struct DtMotion {                    // what the motion form needs beyond: the frame's payload, the moved flags, topology, both geometries
+    const Payload* payload; const uint8_t* moved; const uint4* triIdx; const float4* triPos; const DevVertex* snap;
+};
+
 RT_DEV float dt_g3(int d) { return d == 0 ? 0.5f : 0.25f; }
 
-__global__ void __launch_bounds__(256) k_dt_reproject(DnFrame fr, DtCall tc, const float4* __restrict__ col0, const float4* __restrict__ histIn,
-                                                      float4* __restrict__ histOut, float4* __restrict__ colOut, float* __restrict__ varOut) {
+// moved[t] for the triangles [first, first + count): any of the 18 position / normal floats of its vertices differs bit-wise
+__global__ void __launch_bounds__(256) k_dt_moved(const DevVertex* __restrict__ now, const DevVertex* __restrict__ snap, const uint4* __restrict__ triIdx,
+                                                  uint8_t* __restrict__ moved, uint32_t first, uint32_t count) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k >= count) return;
+    const uint32_t t = first + k;
+    const uint4 ix = triIdx[t];
+    const uint32_t v[3] = {ix.x, ix.y, ix.z};
+    uint32_t diff = 0;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const uint32_t* a = reinterpret_cast<const uint32_t*>(now + v[j]);
+        const uint32_t* b = reinterpret_cast<const uint32_t*>(snap + v[j]);
+#pragma unroll
+        for (int e = 0; e < 6; ++e) diff |= a[e] ^ b[e];
+    }
+    moved[t] = diff ? 1 : 0;
+}
+
+// The reprojection kernel's body.  MOTION: (Pq, nq) — the point and normal step 2 reprojects and tests with — are the hit's in the
+// snapshot geometry where its triangle moved; everything else, and every pixel of an unmoved triangle, is the plain form's arithmetic.
+template <bool MOTION>
+RT_DEV void dt_reproject(const DnFrame& fr, const DtCall& tc, const DtMotion& mo, const float4* __restrict__ col0, const float4* __restrict__ histIn,
+                         float4* __restrict__ histOut, float4* __restrict__ colOut, float* __restrict__ varOut) {
     const uint32_t tilesX = (fr.W + 15u) / 16u;
     const uint32_t bx = blockIdx.x % tilesX, by = blockIdx.x / tilesX;
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
@@ -44,11 +77,40 @@ __global__ void __launch_bounds__(256) k_dt_reproject(DnFrame fr, DtCall tc, con
     const bool filterable = g1.w != 0.0f;
     const float L = ce.w, LL = L * L;
     float cr = ce.x, cg = ce.y, cb = ce.z, m1 = L, m2 = LL, N = filterable ? 1.0f : 0.0f;
+    float Px = g0.x, Py = g0.y, Pz = g0.z, nx = g1.x, ny = g1.y, nz = g1.z;
+    if (MOTION) {
+        bool moved = false; uint32_t tri = 0;
+        if (filterable) {                    // (filterable: k_dn_prepare found the payload's triangle inside the scene)
+            tri = (uint32_t)reinterpret_cast<const int32_t*>(mo.payload + i)[9];
+            moved = mo.moved[tri] != 0;
+        }
+        if (moved) {
+            const float4* tp = mo.triPos + (size_t)tri * 3;
+            const float4 a = tp[0], b = tp[1], c = tp[2];
+            const uint4 ix = mo.triIdx[tri];
+            const float4* va = reinterpret_cast<const float4*>(mo.snap + ix.x);       // px py pz nx | ny nz u v
+            const float4* vb = reinterpret_cast<const float4*>(mo.snap + ix.y);
+            const float4* vc = reinterpret_cast<const float4*>(mo.snap + ix.z);
+            const float4 a0 = va[0], a1 = va[1], b0 = vb[0], b1 = vb[1], c0 = vc[0], c1 = vc[1];
+            const f3 e1 = mk3(b.x - a.x, b.y - a.y, b.z - a.z), e2 = mk3(c.x - a.x, c.y - a.y, c.z - a.z);
+            const f3 d = mk3(g0.x - a.x, g0.y - a.y, g0.z - a.z);
+            const float d11 = dot(e1, e1), d12 = dot(e1, e2), d22 = dot(e2, e2), p1 = dot(d, e1), p2 = dot(d, e2);
+            const float det = d11 * d22 - d12 * d12;
+            const float beta = (d22 * p1 - d12 * p2) / det, gamma = (d11 * p2 - d12 * p1) / det, alpha = (1.0f - beta) - gamma;
+            Px = (a0.x * alpha + b0.x * beta) + c0.x * gamma;
+            Py = (a0.y * alpha + b0.y * beta) + c0.y * gamma;
+            Pz = (a0.z * alpha + b0.z * beta) + c0.z * gamma;
+            const f3 mm = mk3((a0.w * alpha + b0.w * beta) + c0.w * gamma, (a1.x * alpha + b1.x * beta) + c1.x * gamma,
+                              (a1.y * alpha + b1.y * beta) + c1.y * gamma);
+            const f3 nn = normalize(mm);
+            nx = nn.x; ny = nn.y; nz = nn.z;
+        }
+    }
     if (filterable && tc.haveHistory) {
         const float* m = tc.m;
-        const float clipx = (m[0] * g0.x + m[4] * g0.y) + (m[8] * g0.z + m[12]);
-        const float clipy = (m[1] * g0.x + m[5] * g0.y) + (m[9] * g0.z + m[13]);
-        const float clipw = (m[3] * g0.x + m[7] * g0.y) + (m[11] * g0.z + m[15]);
+        const float clipx = (m[0] * Px + m[4] * Py) + (m[8] * Pz + m[12]);
+        const float clipy = (m[1] * Px + m[5] * Py) + (m[9] * Pz + m[13]);
+        const float clipw = (m[3] * Px + m[7] * Py) + (m[11] * Pz + m[15]);
         if (clipw > 0.0f) {
             const float sx = ((clipx / clipw) * 0.5f + 0.5f) * (float)fr.W, sy = ((clipy / clipw) * 0.5f + 0.5f) * (float)fr.H;
             if (sx >= -1.0f && sx < (float)fr.W && sy >= -1.0f && sy < (float)fr.H) {
@@ -66,9 +128,9 @@ __global__ void __launch_bounds__(256) k_dt_reproject(DnFrame fr, DtCall tc, con
                     const bool in = qx >= 0 && qy >= 0 && qx < W && qy < H;
                     const size_t j = in ? (size_t)qy * fr.W + (size_t)qx : i;          // (outside: the centre's own address, selected away)
                     const float4 h0 = histIn[4 * j], h1 = histIn[4 * j + 1], h2 = histIn[4 * j + 2], h3 = histIn[4 * j + 3];
-                    const float dn = (g1.x * h1.x + g1.y * h1.y) + g1.z * h1.z;
-                    const float ex = h0.x - g0.x, ey = h0.y - g0.y, ez = h0.z - g0.z;
-                    const float dp = __builtin_fabsf((g1.x * ex + g1.y * ey) + g1.z * ez);
+                    const float dn = (nx * h1.x + ny * h1.y) + nz * h1.z;
+                    const float ex = h0.x - Px, ey = h0.y - Py, ez = h0.z - Pz;
+                    const float dp = __builtin_fabsf((nx * ex + ny * ey) + nz * ez);
                     const bool valid = in && h1.w != 0.0f && h2.w >= 1.0f && b > 0.0f && dn >= tc.normalMin && dp <= planeT;
                     if (valid) {
                         sw = sw + b; sr = sr + h2.x * b; sg = sg + h2.y * b; sb = sb + h2.z * b; s1 = s1 + h3.x * b; s2 = s2 + h3.y * b;
@@ -122,6 +184,16 @@ __global__ void __launch_bounds__(256) k_dt_reproject(DnFrame fr, DtCall tc, con
     histOut[4 * i + 3] = make_float4(m1, m2, var, 0.0f);
     colOut[i] = make_float4(cr, cg, cb, dn_luminance(cr, cg, cb));
     varOut[i] = filterable ? var : -1.0f;
+}
+
+__global__ void __launch_bounds__(256) k_dt_reproject(DnFrame fr, DtCall tc, const float4* __restrict__ col0, const float4* __restrict__ histIn,
+                                                      float4* __restrict__ histOut, float4* __restrict__ colOut, float* __restrict__ varOut) {
+    dt_reproject<false>(fr, tc, DtMotion{}, col0, histIn, histOut, colOut, varOut);
+}
+__global__ void __launch_bounds__(256) k_dt_reproject_motion(DnFrame fr, DtCall tc, DtMotion mo, const float4* __restrict__ col0,
+                                                             const float4* __restrict__ histIn, float4* __restrict__ histOut,
+                                                             float4* __restrict__ colOut, float* __restrict__ varOut) {
+    dt_reproject<true>(fr, tc, mo, col0, histIn, histOut, colOut, varOut);
 }
 
 struct DtSums { float r, g, b, w, v; };

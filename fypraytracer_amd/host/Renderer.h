@@ -113,6 +113,9 @@ public:
         return !report(fyprt_denoise_temporal(m_Ctx, &p, rgba8, nullptr, nullptr), "fyprt_denoise_temporal");
     }
     void ResetDenoiseHistory() { fyprt_denoise_temporal_reset(m_Ctx); }
+    // Object motion (fyprt_denoise_temporal_set_motion): with it on, geometry updates keep the history and the next DenoiseTemporal
+    // reprojects every hit through the vertices of the frame denoised before — for dragging a mesh with the temporal denoiser on.
+    bool SetDenoiseMotion(bool on) { return !report(fyprt_denoise_temporal_set_motion(m_Ctx, on ? 1 : 0), "fyprt_denoise_temporal_set_motion"); }
 
     void ResetFrameIndex() { fyprt_reset_frame_index(m_Ctx); }
     RenderingSettings& GetSettings() { return m_Settings; }

@@ -508,7 +508,7 @@ int fyprt_denoise_device(fyprt_context* ctx, const fyprt_denoise_params* params,
  *   history_limit = 1 makes every call a first call.
  * The history is dropped — the next call behaves as a first call — by fyprt_resize, fyprt_upload_scene, fyprt_update_vertices,
  * fyprt_update_transforms (world positions of an edited scene are not comparable), fyprt_update_materials (nor are its colours) and
- * fyprt_denoise_temporal_reset.
+ * fyprt_denoise_temporal_reset.  (fyprt_denoise_temporal_set_motion, below, lets the history live through the two geometry edits.)
  * Errors, in this order: FYPRT_EINVAL for a NULL context / params, history_limit outside 1..256, feedback > 1, normal_min or plane_max
  * not finite, plane_max <= 0; then everything fyprt_denoise refuses, in its order, with params->spatial (its FYPRT_EINVAL cases, then
  * its FYPRT_ESTATE cases).  Multi-GPU bands are out of scope as there.
@@ -533,6 +533,37 @@ int fyprt_denoise_temporal_device(fyprt_context* ctx, const fyprt_temporal_param
 /* Drops the history: the next temporal call behaves as a first call.  Call it when the scene is replaced by other means than the above
  * or the camera cuts. */
 int fyprt_denoise_temporal_reset(fyprt_context* ctx);
+/* Object motion, opt-in: enabled = 1 keeps the history through fyprt_update_vertices and fyprt_update_transforms (dragging a mesh while the
+ * temporal denoiser runs), enabled = 0 (the default) is everything above unchanged, kernels included.  FYPRT_EINVAL for a NULL context or
+ * a value other than 0 / 1.  A call with the value in effect does nothing; a call that changes it drops the history as
+ * fyprt_denoise_temporal_reset does and releases the snapshot below.  Allowed on host-only contexts (the flag is stored; the temporal calls
+ * stay refused).
+ * With 1: the two geometry edits no longer drop the history.  If a history exists and no snapshot is pending, the edit first copies the
+ * world vertices (positions and normals) as they are on the device into a per-context snapshot buffer — device to device, on the context
+ * stream, after the call's own wait for both streams and complete before the edit writes a vertex.  The snapshot is pending from that
+ * copy until the next successful temporal call, which consumes it; further edits before that call leave it alone, frames rendered in
+ * between without a temporal call do not matter, so the snapshot is always the geometry of the frame the previous temporal call
+ * denoised.  fyprt_upload_scene, fyprt_update_materials, fyprt_resize, fyprt_denoise_temporal_reset and a change of the mode drop
+ * history and snapshot; a refused temporal call drops neither.
+ * The edits still invalidate the frame for both denoisers: render one before the next call.  The snapshot buffer (32 B per vertex and a
+ * byte per triangle) is allocated at the first snapshot and released by fyprt_upload_scene and by switching the mode off; a context that
+ * never switches the mode on allocates nothing.
+ * The contract: step 2 above when a snapshot is pending.  Arithmetic as everywhere in it; dot(x, y) = (x.x y.x + x.y y.y) + x.z y.z; no
+ * special cases (a comparison with a NaN is false).  For a filterable pixel p whose payload names triangle T: (a, b, c) = T's current world
+ * positions, (a', b', c') and (na', nb', nc') = T's positions and normals in the snapshot.  T is moved when any of the 18 position and
+ * normal floats of its three vertices differs bit-wise between snapshot and current.
+ *   T not moved: P' = P_p, n' = n_p — the pixel goes through the arithmetic above exactly.
+ *   T moved:     e1 = b - a, e2 = c - a, d = P_p - a;  d11 = dot(e1, e1), d12 = dot(e1, e2), d22 = dot(e2, e2), p1 = dot(d, e1),
+ *                p2 = dot(d, e2);  det = d11 d22 - d12 d12;  beta = (d22 p1 - d12 p2) / det, gamma = (d11 p2 - d12 p1) / det,
+ *                alpha = (1 - beta) - gamma;  P' = (a' alpha + b' beta) + c' gamma and m = (na' alpha + nb' beta) + nc' gamma per
+ *                component;  n' = m (1 / sqrt(dot(m, m))) (two roundings).
+ *   Step 2 with P', n': clip is formed from P'; a tap is valid when dot(n', n_q) >= normal_min and |dot(n', P_q - P')| <= plane_max t_p;
+ *   everything else of step 2 and steps 3 to 6 are unchanged — the history record written still holds the current P_p, n_p.  A degenerate
+ *   triangle gives a non-finite P' or n' and, through the comparisons, no history (N = 1) or an invalid tap.
+ * This is SVGF's motion vector, from the two vertex sets instead of a rasteriser.  The limit: a long history of a surface whose lighting
+ * changes as it moves lags behind it (fast drags look worse with the history kept than without); history_limit is the
+ * control.  ReSTIR's own temporal reuse is not touched. */
+int fyprt_denoise_temporal_set_motion(fyprt_context* ctx, int enabled);
 
 /* ================================================================================================= multi-GPU
  * The reference renders on one GPU (Renderer.cu:13-284); there is no reference interface for this section.  It splits ONE
