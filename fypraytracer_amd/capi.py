@@ -184,6 +184,7 @@ EXPORTED_SYMBOLS = [
     "fyprt_live_device_bytes",
     "fyprt_update_materials", "fyprt_export_emissive",
     "fyprt_denoise_temporal_set_motion",
+    "fyprt_group_denoise", "fyprt_group_denoise_device", "fyprt_group_denoise_plan",
 ]
 
 
@@ -285,6 +286,10 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.fyprt_halo_plan.argtypes = [C.POINTER(u32), C.c_int, u32, u32, C.c_int, C.POINTER(u32), C.c_int]
     if hasattr(lib, "fyprt_comm_ops"):       # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
         lib.fyprt_comm_ops.argtypes = [C.c_int, C.POINTER(u32), C.POINTER(u32), C.c_int, u32, u32, C.c_int, u32, C.c_int, C.POINTER(u32), C.c_int, C.POINTER(C.c_uint64), C.c_int]
+    if hasattr(lib, "fyprt_group_denoise"):  # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
+        lib.fyprt_group_denoise.argtypes = [vp, C.POINTER(DenoiseParams), vp, vp, vp]
+        lib.fyprt_group_denoise_device.argtypes = [vp, C.POINTER(DenoiseParams), C.c_int, vp, vp]
+        lib.fyprt_group_denoise_plan.argtypes = [C.POINTER(u32), C.c_int, u32, u32, C.POINTER(u32), C.c_int]
     alternative = path is not None or "FYPRT_LIB" in os.environ      # an older build loaded for an A/B run may lack the newest entry points
     for f in EXPORTED_SYMBOLS:
         if alternative and not hasattr(lib, f):
@@ -764,6 +769,46 @@ class Group:
     def synchronize(self):
         self._check(self.lib.fyprt_group_synchronize(self.h))
 
+    def denoise(self, params: DenoiseParams | None = None, want_radiance=True, with_band_ms=False):
+        """Context.denoise for the frame the group rendered last, every band filtered by its owner (fyprt_group_denoise, blocking;
+        defaults when `params` is None).  Returns (image H x W uint32 ABGR8, radiance H x W x 4 float32 or None without `want_radiance`)
+        of the WHOLE frame, bit for bit a single context's; with `with_band_ms` also the per-band milliseconds of the call."""
+        p = params if params is not None else DenoiseParams()
+        H, W = self.contexts[0].height, self.contexts[0].width
+        img = np.empty(W * H, dtype=np.uint32)
+        rad = np.empty((W * H, 4), dtype=np.float32) if want_radiance else None
+        ms = (C.c_float * len(self.contexts))()
+        self._check(self.lib.fyprt_group_denoise(self.h, C.byref(p), _ptr(img), _ptr(rad), ms if with_band_ms else None))
+        out = (img.reshape(H, W), rad.reshape(H, W, 4) if want_radiance else None)
+        return out + (list(ms),) if with_band_ms else out
+
+    def denoise_tensor(self, image_tensor, radiance_tensor, params: DenoiseParams | None = None, root=0):
+        """Context.denoise_tensor for the group (fyprt_group_denoise_device): the tensors live on the GPU of context `root`, and the call
+        is ordered against torch's current stream through that context's stream, without a host synchronisation."""
+        import torch
+        p = params if params is not None else DenoiseParams()
+        if not 0 <= root < len(self.contexts):
+            raise ValueError("denoise_tensor: root out of range")
+        ctx = self.contexts[root]
+        if image_tensor is None and radiance_tensor is None:
+            raise ValueError("denoise_tensor: at least one output tensor is needed")
+        for t, dt, shape, name in ((image_tensor, torch.int32, (ctx.height, ctx.width), "image_tensor"),
+                                   (radiance_tensor, torch.float32, (ctx.height, ctx.width, 4), "radiance_tensor")):
+            if t is None:
+                continue
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"denoise_tensor: {name} must be a contiguous {dt} tensor of shape {shape}")
+            if t.device.type != "cuda" or (t.device.index if t.device.index is not None else torch.cuda.current_device()) != ctx.device:
+                raise ValueError(f"denoise_tensor: {name} must be on cuda:{ctx.device}, the root context's GPU")
+        dev = (image_tensor if image_tensor is not None else radiance_tensor).device
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(ctx.stream(), device=dev)
+        ext.wait_stream(cur)                                           # the outputs are allocated (and their earlier uses done) before root writes them
+        self._check(self.lib.fyprt_group_denoise_device(self.h, C.byref(p), root,
+                                                        C.c_void_p(image_tensor.data_ptr()) if image_tensor is not None else None,
+                                                        C.c_void_p(radiance_tensor.data_ptr()) if radiance_tensor is not None else None))
+        cur.wait_stream(ext)                                           # torch's later work follows the collect
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.fyprt_group_destroy(self.h)
@@ -809,3 +854,15 @@ def halo_plan(row_bounds, halo, height, wrap_row=True, lib=None):
     out = (C.c_uint32 * (4 * max(cnt, 1)))()
     lib.fyprt_halo_plan(_u32_array(row_bounds), n, halo, height, 1 if wrap_row else 0, out, cnt)
     return [tuple(out[4 * k: 4 * k + 4]) for k in range(cnt)]
+
+
+def group_denoise_plan(row_bounds, height, iterations, lib=None):
+    """fyprt_group_denoise_plan: [(stage, receiver, owner, first row, end row), ...] of one Group.denoise call, in issue order."""
+    lib = lib or load_library()
+    n = len(row_bounds) - 1
+    cnt = lib.fyprt_group_denoise_plan(_u32_array(row_bounds), n, height, iterations, None, 0)
+    if cnt < 0:
+        raise FyprtError(f"fyprt_group_denoise_plan failed ({cnt})")
+    out = (C.c_uint32 * (5 * max(cnt, 1)))()
+    lib.fyprt_group_denoise_plan(_u32_array(row_bounds), n, height, iterations, out, cnt)
+    return [tuple(out[5 * k: 5 * k + 5]) for k in range(cnt)]

@@ -171,8 +171,9 @@ struct fyprt_context {
     DevBuf<Payload> rrPayload; DevBuf<float4> rrRays[2], rrHits[2], rrState; DevBuf<uint32_t> rrPixels, rrPixels2, rrCounters;
     DevBuf<float4> rrIn, rrOut; DevBuf<uint32_t> rrIndices; Event rrEv[2];
     // denoiser (fyprt_denoise*, rt_denoise.h), all allocated on the first call and dropped by fyprt_resize: guide records (2 quads per pixel),
-    // albedo (FYPRT_BUF_ALBEDO), two ping-pong colour buffers, the host entry's output staging; its timing events and the event the front
-    // stream waits for before the next pipelined frame's Part 1 overwrites the payload the denoiser reads
+    // albedo (FYPRT_BUF_ALBEDO), two ping-pong colour buffers, the host entry's output staging (for a group member, fyprt_group_denoise*: the
+    // staging of its band's output rows, which the root collects); its timing events and the event the front stream waits for before the
+    // next pipelined frame's Part 1 overwrites the payload the denoiser reads
     struct Denoise { DevBuf<float4> guide, albedo, col[2], outRad; DevBuf<uint32_t> outImg; } dn; Event dnEv[3], dnDone;
     bool frameComplete = false;                // a whole frame was rendered since the last resize / scene upload / geometry update
     uint32_t lastFrameIndex = 0;               // the frame index that frame was rendered with (the divisor of its epilogue)
@@ -1770,19 +1771,33 @@ int fyprt_denoise_default_params(fyprt_denoise_params* out) {
     return FYPRT_OK;
 }
 
-static int check_denoise(fyprt_context* c, const fyprt_denoise_params* p, const void* rgba8, const void* radiance4, bool device) {
-    const char* who = device ? "fyprt_denoise_device" : "fyprt_denoise";
-    if (!c) return FYPRT_EINVAL;
+// The checks of a denoise call in the header's order, in the pieces fyprt_group_denoise* (fyprt_multi.h) puts its own between:
+// the parameters, the outputs, the frame.
+static int check_denoise_params(fyprt_context* c, const char* who, const fyprt_denoise_params* p) {
     if (!p) return c->fail(FYPRT_EINVAL, std::string(who) + ": NULL params");
     if (p->iterations > 8u || p->normal_power_log2 > 7u || p->demodulate_albedo > 1u || !std::isfinite(p->sigma_luminance) ||
         !std::isfinite(p->sigma_plane) || !(p->sigma_plane > 0.0f))
         return c->fail(FYPRT_EINVAL, std::string(who) + ": iterations 0..8, normal_power_log2 0..7, demodulate_albedo 0 / 1, finite sigmas, sigma_plane > 0");
+    return FYPRT_OK;
+}
+static int check_denoise_outputs(fyprt_context* c, const char* who, const void* rgba8, const void* radiance4, bool device) {
     if (device && (((uintptr_t)rgba8 & 3u) || ((uintptr_t)radiance4 & 15u)))
         return c->fail(FYPRT_EINVAL, std::string(who) + ": rgba8 must be 4-byte and radiance4 16-byte aligned");
     if (!rgba8 && !radiance4) return c->fail(FYPRT_EINVAL, std::string(who) + ": both outputs are NULL");
+    return FYPRT_OK;
+}
+static int check_denoise_frame(fyprt_context* c, const char* who) {
     if (c->hostOnly) return c->fail(FYPRT_ESTATE, std::string(who) + ": host-only context (device -1) has no frame");
     if (c->W == 0 || !c->frameComplete || c->part1Pending)
         return c->fail(FYPRT_ESTATE, std::string(who) + ": no complete frame since the last fyprt_resize / fyprt_upload_scene / fyprt_update_vertices / fyprt_update_transforms");
+    return FYPRT_OK;
+}
+static int check_denoise(fyprt_context* c, const fyprt_denoise_params* p, const void* rgba8, const void* radiance4, bool device) {
+    const char* who = device ? "fyprt_denoise_device" : "fyprt_denoise";
+    if (!c) return FYPRT_EINVAL;
+    TRY(check_denoise_params(c, who, p));
+    TRY(check_denoise_outputs(c, who, rgba8, radiance4, device));
+    TRY(check_denoise_frame(c, who));
     if (c->comm || c->rowBegin != 0 || c->rowEnd != c->H || c->stripeRows != 0)
         return c->fail(FYPRT_ESTATE, std::string(who) + ": the context must render every row of the frame (no band, stripes, group or communicator)");
     return FYPRT_OK;

@@ -19,6 +19,7 @@
 //                   between the contexts' buffers, ordered with events — no collective library at all;
 //   fyprt_comm_*    one process per GPU (torch.distributed.run, MPI, ...): RCCL — grouped ncclSend / ncclRecv for the halos, grouped
 //                   ncclBroadcast (one per band, in place in the full-size image) for the gather.  librccl.so.1 is opened on first use.
+// fyprt_group_denoise* (below fyprt_group_synchronize): the a-trous denoiser on the same bands, by the same peer copies and events.
 #include <dlfcn.h>
 
 extern "C++" {
@@ -47,6 +48,20 @@ std::vector<HaloXfer> halo_plan(const std::vector<uint32_t>& bounds, uint32_t ha
                 if (a0 < a1) plan.push_back({r, j, a0, a1});
             }
     }
+    return plan;
+}
+
+// fyprt_group_denoise: every transfer of one call, in issue order.  Stage 0 = the guide records (32 B per pixel), halo 2^iterations rows
+// (the farthest tap of any iteration: 2 * 2^(iterations-1)); stage 1 + k = the colour | luminance buffer iteration k reads (16 B per
+// pixel), halo 2 * 2^k rows.  Clipped to the image, no wrap row; a halo higher than the neighbouring band has several owners.
+struct DnXfer { int stage; HaloXfer x; };
+constexpr size_t kDnGuideBytes = 2 * sizeof(float4), kDnColourBytes = sizeof(float4);
+std::vector<DnXfer> group_denoise_plan(const std::vector<uint32_t>& bounds, uint32_t H, uint32_t iterations) {
+    std::vector<DnXfer> plan;
+    if (iterations == 0) return plan;
+    for (const HaloXfer& x : halo_plan(bounds, 1u << iterations, H, false)) plan.push_back({0, x});
+    for (uint32_t k = 0; k < iterations; ++k)
+        for (const HaloXfer& x : halo_plan(bounds, 2u << k, H, false)) plan.push_back({1 + (int)k, x});
     return plan;
 }
 
@@ -147,6 +162,10 @@ struct fyprt_group {
     uint32_t stripeRows = 0, lastStripeRows = 0; bool lastStriped = false;      // interleaved split for the per-pixel techniques; whether (and with which stripes) the last frame used it
     struct BandEvents { Event p1, pulled, frame, sync; };      // per context: Part 1 done, halo pulled, frame done, history normals in step
     std::vector<BandEvents> ev; Event evGather; bool gatherPending = false; std::string err;
+    // fyprt_group_denoise*, per context: its latest stage (prepare / an iteration) done, its latest halo pulled, the collect it ran as
+    // root, the two timing events of the blocking entry; whether a call was enqueued before, and the root of the last one
+    struct DenoiseEvents { Event done, pulled, collect, first, last; };
+    std::vector<DenoiseEvents> dn; bool dnCalled = false; int dnRoot = -1;
 };
 
 int fyprt_group_synchronize(fyprt_group* g);
@@ -179,7 +198,7 @@ int fyprt_group_create(fyprt_context** ctxs, int n, const uint32_t* row_bounds, 
     if (row_bounds[0] != 0 || row_bounds[n] != ctxs[0]->H) return ctxs[0]->fail(FYPRT_EINVAL, "fyprt_group_create: the bands must partition rows 0..height");
     auto* g = new fyprt_group();
     g->ctx.assign(ctxs, ctxs + n); g->bounds.assign(row_bounds, row_bounds + n + 1);
-    g->ev.resize(n);
+    g->ev.resize(n); g->dn.resize(n);
     for (int i = 0; i < n; ++i) {
         (void)hipSetDevice(ctxs[i]->device);
         for (Event* e : {&g->ev[i].p1, &g->ev[i].pulled, &g->ev[i].frame, &g->ev[i].sync}) (void)create(*e, hipEventDisableTiming);
@@ -194,6 +213,7 @@ void fyprt_group_destroy(fyprt_group* g) {
     for (size_t i = 0; i < g->ctx.size(); ++i) {
         (void)hipSetDevice(g->ctx[i]->device); (void)sync_all(g->ctx[i]);
         g->ev[i] = fyprt_group::BandEvents();               // this band's events go while its device is current
+        g->dn[i] = fyprt_group::DenoiseEvents();
         g->ctx[i]->haloExchange = false;
     }
     delete g;
@@ -350,6 +370,206 @@ int fyprt_group_synchronize(fyprt_group* g) {
     if (!g) return FYPRT_EINVAL;
     for (fyprt_context* c : g->ctx) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c)); }
     return FYPRT_OK;
+}
+
+// ---- fyprt_group_denoise*: the a-trous denoiser (rt_denoise.h) on the group's bands.  Every pixel is filtered by the context that owns
+// its row, with the band forms of the kernels; what a tap beyond the band reads was pulled from the row's owner into the same place of
+// this context's full-size guide / colour buffers (group_denoise_plan).  The shared pixel code on the same inputs: the single-context
+// call's bits.  Nothing but the denoiser's own buffers and the caller's outputs is written.
+static int group_denoise_check(fyprt_group* g, const fyprt_denoise_params* p, int root, const void* rgba8, const void* radiance4, bool device) {
+    const char* who = device ? "fyprt_group_denoise_device" : "fyprt_group_denoise";
+    if (!g) return FYPRT_EINVAL;
+    const int n = (int)g->ctx.size();
+    TRY(check_denoise_params(g->ctx[0], who, p));
+    if (root < 0 || root >= n) return g->ctx[0]->fail(FYPRT_EINVAL, std::string(who) + ": root out of range");
+    TRY(check_denoise_outputs(g->ctx[root], who, rgba8, radiance4, device));
+    for (int i = 0; i < n; ++i) TRY(check_denoise_frame(g->ctx[i], who));
+    for (int i = 1; i < n; ++i)
+        if (g->ctx[i]->lastFrameIndex != g->ctx[0]->lastFrameIndex) return g->ctx[i]->fail(FYPRT_ESTATE, std::string(who) + ": the members' last frames differ in frame index");
+    if (g->lastStriped) return g->ctx[0]->fail(FYPRT_ESTATE, std::string(who) + ": the last group frame was striped (fyprt_group_set_interleave): the filter needs contiguous bands");
+    for (int i = 0; i < n; ++i) {
+        fyprt_context* c = g->ctx[i];
+        if (c->rowBegin != g->bounds[i] || c->rowEnd != g->bounds[i + 1] || c->stripeRows != 0)
+            return c->fail(FYPRT_ESTATE, std::string(who) + ": the member's rows are not its band of the group (fyprt_set_rows / fyprt_set_row_stripes behind the group)");
+    }
+    return FYPRT_OK;
+}
+
+// Enqueues one call on every band's stream and the collect on root's; no host wait (but before a staging buffer is reallocated).
+// rgba8 / radiance4: device memory of root's GPU.  Hazards, and the event that orders each:
+//   read after write   a pull of stage 1 + k reads the owner's rows of the colour buffer its iteration k - 1 wrote (its prepare for k = 0,
+//                      and for the guide records of stage 0): it waits for the owner's `done`, recorded after each of these launches;
+//   write after read   iteration k writes the ping-pong buffer the neighbours pulled from at stage k (before their iteration k - 1): it
+//                      waits for the `pulled` of every band that pulls from this one, as recorded after stage k;
+//   across calls       a later call (or the same call of the next frame of a pipelined sequence) may be enqueued while neighbours still
+//                      pull from this one: the first work of a call on a band waits for every other band's last `pulled` of the earlier
+//                      call; the kernel that writes the staging rows waits for the earlier root's `collect`; and the front stream
+//                      waits for the band's last kernel before the next pipelined frame's Part 1 overwrites the payload (dnDone, as
+//                      end_denoise does).
+static int group_denoise_enqueue(fyprt_group* g, const fyprt_denoise_params* p, int root, uint32_t* rgba8, float4* radiance4, bool timed) {
+    const int n = (int)g->ctx.size();
+    const uint32_t W = g->ctx[0]->W, H = g->ctx[0]->H;
+    const size_t npx = (size_t)W * H;
+    const std::vector<DnXfer> plan = group_denoise_plan(g->bounds, H, p->iterations);
+    std::vector<char> pullsFrom((size_t)n * n, 0);                // [owner * n + receiver]
+    for (const DnXfer& t : plan) pullsFrom[(size_t)t.x.owner * n + t.x.receiver] = 1;
+    std::vector<DnFrame> frames(n); std::vector<DnBand> bands(n);
+    for (int i = 0; i < n; ++i) {
+        fyprt_context* c = g->ctx[i];
+        HIPCHK(c, hipSetDevice(c->device));
+        if (c->dn.guide.n != 2 * npx) {
+            HIPCHK(c, c->dn.guide.alloc(2 * npx)); HIPCHK(c, c->dn.albedo.alloc(npx)); HIPCHK(c, c->dn.col[0].alloc(npx)); HIPCHK(c, c->dn.col[1].alloc(npx));
+        }
+        HIPCHK(c, create(c->dnDone, hipEventDisableTiming));
+        fyprt_group::DenoiseEvents& e = g->dn[i];
+        HIPCHK(c, create(e.done, hipEventDisableTiming)); HIPCHK(c, create(e.pulled, hipEventDisableTiming)); HIPCHK(c, create(e.collect, hipEventDisableTiming));
+        if (timed) { HIPCHK(c, create(e.first)); HIPCHK(c, create(e.last)); }
+        const uint32_t b = g->bounds[i], rows = g->bounds[i + 1] - b;
+        bands[i] = DnBand{b, g->bounds[i + 1]};
+        DnFrame& fr = frames[i];
+        fr = DnFrame{};
+        fr.W = W; fr.H = H; fr.frameIndex = (float)c->lastFrameIndex; fr.demodulate = p->demodulate_albedo;
+        fr.accum = c->accum.p; fr.guide = c->dn.guide.p; fr.albedo = c->dn.albedo.p;
+        if (i == root) { fr.rgba8 = rgba8; fr.radiance4 = radiance4; continue; }
+        // the band's output rows go to its staging (at least the band's size); the kernels index the whole frame, so they get the address
+        // row 0 would have.  A buffer the earlier root may still read is not freed under it.
+        const size_t need = (size_t)rows * W;
+        if ((rgba8 && c->dn.outImg.n < need) || (radiance4 && c->dn.outRad.n < need)) {
+            if (g->dnRoot >= 0) HIPCHK(c, hipEventSynchronize(g->dn[g->dnRoot].collect));
+            if (rgba8 && c->dn.outImg.n < need) HIPCHK(c, c->dn.outImg.alloc(need));
+            if (radiance4 && c->dn.outRad.n < need) HIPCHK(c, c->dn.outRad.alloc(need));
+        }
+        if (rgba8) fr.rgba8 = reinterpret_cast<uint32_t*>(reinterpret_cast<uintptr_t>(c->dn.outImg.p) - (size_t)b * W * sizeof(uint32_t));
+        if (radiance4) fr.radiance4 = reinterpret_cast<float4*>(reinterpret_cast<uintptr_t>(c->dn.outRad.p) - (size_t)b * W * sizeof(float4));
+    }
+    auto band_grid = [&](int i) { return dim3((uint32_t)(((size_t)(bands[i].rowEnd - bands[i].rowBegin) * W + 255u) / 256u)); };
+    auto pull = [&](int i, int stage) -> int {
+        fyprt_context* c = g->ctx[i];
+        HIPCHK(c, hipSetDevice(c->device));
+        for (const DnXfer& t : plan) {
+            if (t.stage != stage || t.x.receiver != i) continue;
+            fyprt_context* o = g->ctx[t.x.owner];
+            HIPCHK(c, hipStreamWaitEvent(c->stream, g->dn[t.x.owner].done, 0));
+            const size_t bpp = stage == 0 ? kDnGuideBytes : kDnColourBytes;
+            char* dst = stage == 0 ? (char*)c->dn.guide.p : (char*)c->dn.col[(stage - 1) & 1].p;
+            const char* src = stage == 0 ? (const char*)o->dn.guide.p : (const char*)o->dn.col[(stage - 1) & 1].p;
+            const size_t off = (size_t)t.x.r0 * W * bpp, bytes = (size_t)(t.x.r1 - t.x.r0) * W * bpp;
+            HIPCHK(c, hipMemcpyPeerAsync(dst + off, c->device, src + off, o->device, bytes, c->stream));
+        }
+        HIPCHK(c, hipEventRecord(g->dn[i].pulled, c->stream));
+        return FYPRT_OK;
+    };
+    auto before_output = [&](int i) -> int {                     // the earlier call's collect still reads this band's staging rows
+        fyprt_context* c = g->ctx[i];
+        if (i != root && g->dnRoot >= 0) HIPCHK(c, hipStreamWaitEvent(c->stream, g->dn[g->dnRoot].collect, 0));
+        return FYPRT_OK;
+    };
+    // 1. prepare on the band's rows, after the earlier call's pulls from this band
+    for (int i = 0; i < n; ++i) {
+        fyprt_context* c = g->ctx[i];
+        HIPCHK(c, hipSetDevice(c->device));
+        if (timed) HIPCHK(c, hipEventRecord(g->dn[i].first, c->stream));
+        if (g->dnCalled) for (int j = 0; j < n; ++j) if (j != i) HIPCHK(c, hipStreamWaitEvent(c->stream, g->dn[j].pulled, 0));
+        DevScene sc = c->dsc; sc.rayCounter = nullptr;
+        hipLaunchKernelGGL(k_dn_prepare_band, band_grid(i), dim3(256), 0, c->stream, sc, frames[i], bands[i], c->payload.p, c->dn.col[0].p);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(g->dn[i].done, c->stream));
+    }
+    // 2. the guide records of the halo rows
+    for (int i = 0; i < n; ++i) TRY(pull(i, 0));
+    // 3. per iteration: the colour halo it reads, then the iteration on the band's rows (one launch per band)
+    for (uint32_t k = 0; k < p->iterations; ++k) {
+        DnIter it{};
+        it.step = 1 << k; it.sigmaL = p->sigma_luminance * (1.0f / (float)(1u << k)); it.lumOn = p->sigma_luminance > 0.0f ? 1u : 0u;
+        it.sigmaPlane = p->sigma_plane; it.normalPow = p->normal_power_log2; it.last = (k + 1 == p->iterations) ? 1u : 0u;
+        if (k > 0)
+            for (int i = 0; i < n; ++i) {
+                fyprt_context* c = g->ctx[i];
+                HIPCHK(c, hipSetDevice(c->device));
+                for (int j = 0; j < n; ++j) if (pullsFrom[(size_t)i * n + j]) HIPCHK(c, hipStreamWaitEvent(c->stream, g->dn[j].pulled, 0));
+            }
+        for (int i = 0; i < n; ++i) TRY(pull(i, 1 + (int)k));
+        for (int i = 0; i < n; ++i) {
+            fyprt_context* c = g->ctx[i];
+            HIPCHK(c, hipSetDevice(c->device));
+            if (it.last) TRY(before_output(i));
+            const float4* in = c->dn.col[k & 1u].p; float4* out = c->dn.col[(k + 1u) & 1u].p;
+            const uint32_t rows = bands[i].rowEnd - bands[i].rowBegin;
+            for_dn_step(it.step, [&](auto S) {
+                constexpr int STEP = decltype(S)::value;
+                hipLaunchKernelGGL(k_dn_iterate_band<STEP>, dim3(dn_grid<STEP>(W, rows)), dim3(256), 0, c->stream, frames[i], it, bands[i], in, out);
+            });
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipEventRecord(g->dn[i].done, c->stream));
+        }
+    }
+    for (int i = 0; i < n; ++i) {
+        fyprt_context* c = g->ctx[i];
+        HIPCHK(c, hipSetDevice(c->device));
+        if (p->iterations == 0) {
+            TRY(before_output(i));
+            hipLaunchKernelGGL(k_dn_finish_band, band_grid(i), dim3(256), 0, c->stream, frames[i], bands[i], c->dn.col[0].p);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipEventRecord(g->dn[i].done, c->stream));
+        }
+        if (timed) HIPCHK(c, hipEventRecord(g->dn[i].last, c->stream));
+        HIPCHK(c, hipEventRecord(c->dnDone, c->stream));
+        if (c->front) HIPCHK(c, hipStreamWaitEvent(c->front, c->dnDone, 0));
+        c->albedoValid = true;
+    }
+    // 4. the other bands' output rows into the caller's buffers, on root's stream
+    fyprt_context* r = g->ctx[root];
+    HIPCHK(r, hipSetDevice(r->device));
+    for (int i = 0; i < n; ++i) {
+        if (i == root) continue;
+        fyprt_context* c = g->ctx[i];
+        HIPCHK(r, hipStreamWaitEvent(r->stream, g->dn[i].done, 0));
+        const size_t off = (size_t)bands[i].rowBegin * W, cnt = (size_t)(bands[i].rowEnd - bands[i].rowBegin) * W;
+        if (rgba8) HIPCHK(r, hipMemcpyPeerAsync(rgba8 + off, r->device, c->dn.outImg.p, c->device, cnt * sizeof(uint32_t), r->stream));
+        if (radiance4) HIPCHK(r, hipMemcpyPeerAsync(radiance4 + off, r->device, c->dn.outRad.p, c->device, cnt * sizeof(float4), r->stream));
+    }
+    HIPCHK(r, hipEventRecord(g->dn[root].collect, r->stream));
+    g->dnCalled = true; g->dnRoot = root;
+    return FYPRT_OK;
+}
+
+int fyprt_group_denoise(fyprt_group* g, const fyprt_denoise_params* p, uint32_t* rgba8, float* radiance4, float* band_ms) {
+    TRY(group_denoise_check(g, p, 0, rgba8, radiance4, false));
+    TRY(fyprt_group_synchronize(g));                               // as fyprt_denoise: the last frame is complete on every stream
+    fyprt_context* r = g->ctx[0];
+    HIPCHK(r, hipSetDevice(r->device));
+    const size_t npx = (size_t)r->W * r->H;
+    if (rgba8 && r->dn.outImg.n != npx) HIPCHK(r, r->dn.outImg.alloc(npx));
+    if (radiance4 && r->dn.outRad.n != npx) HIPCHK(r, r->dn.outRad.alloc(npx));
+    TRY(group_denoise_enqueue(g, p, 0, rgba8 ? r->dn.outImg.p : nullptr, radiance4 ? r->dn.outRad.p : nullptr, true));
+    HIPCHK(r, hipSetDevice(r->device));
+    if (rgba8) HIPCHK(r, hipMemcpyAsync(rgba8, r->dn.outImg.p, npx * 4, hipMemcpyDeviceToHost, r->stream));
+    if (radiance4) HIPCHK(r, hipMemcpyAsync(radiance4, r->dn.outRad.p, npx * 16, hipMemcpyDeviceToHost, r->stream));
+    HIPCHK(r, hipStreamSynchronize(r->stream));
+    for (size_t i = 0; i < g->ctx.size(); ++i) {
+        fyprt_context* c = g->ctx[i];
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipEventSynchronize(g->dn[i].last));
+        if (band_ms) HIPCHK(c, hipEventElapsedTime(&band_ms[i], g->dn[i].first, g->dn[i].last));
+    }
+    return FYPRT_OK;
+}
+
+int fyprt_group_denoise_device(fyprt_group* g, const fyprt_denoise_params* p, int root, void* rgba8, void* radiance4) {
+    TRY(group_denoise_check(g, p, root, rgba8, radiance4, true));
+    return group_denoise_enqueue(g, p, root, static_cast<uint32_t*>(rgba8), static_cast<float4*>(radiance4), false);
+}
+
+// The transfers of one fyprt_group_denoise* call in issue order: (stage, receiver, owner, first row, end row) per entry.
+int fyprt_group_denoise_plan(const uint32_t* row_bounds, int n, uint32_t height, uint32_t iterations, uint32_t* out5, int capacity) {
+    if (!row_bounds || n <= 0 || iterations > 8u || row_bounds[0] != 0 || row_bounds[n] != height) return FYPRT_EINVAL;
+    for (int i = 0; i < n; ++i) if (row_bounds[i] >= row_bounds[i + 1]) return FYPRT_EINVAL;
+    const std::vector<DnXfer> plan = group_denoise_plan(std::vector<uint32_t>(row_bounds, row_bounds + n + 1), height, iterations);
+    for (int k = 0; k < (int)plan.size() && k < capacity && out5; ++k) {
+        const HaloXfer& x = plan[k].x;
+        out5[5 * k] = (uint32_t)plan[k].stage; out5[5 * k + 1] = (uint32_t)x.receiver; out5[5 * k + 2] = (uint32_t)x.owner; out5[5 * k + 3] = x.r0; out5[5 * k + 4] = x.r1;
+    }
+    return (int)plan.size();
 }
 
 // Cost-balanced bands: new boundaries from the time each band took last frame, assuming a band's cost is spread evenly over its rows

@@ -446,8 +446,8 @@ int fyprt_render_rays_device(fyprt_context* ctx, const fyprt_settings* settings,
  * since the last fyprt_resize, fyprt_upload_scene, fyprt_update_vertices, fyprt_update_transforms or fyprt_update_materials (each of
  * them invalidates the frame for the denoiser: the payload's triangle indices and texture coordinates belong to the scene they were
  * traced in, and its albedo to the materials it was shaded with; textures change with fyprt_upload_scene only), between the two parts of a fyprt_render_part frame, and on a context that does not
- * render every row (a fyprt_set_rows band, fyprt_set_row_stripes, a group or communicator member).  Multi-GPU denoising needs a halo of
- * 2 * (2^iterations - 1) rows from the neighbouring bands and is out of scope.
+ * render every row (a fyprt_set_rows band, fyprt_set_row_stripes, a group or communicator member).  The bands of a group are denoised by fyprt_group_denoise
+ * (multi-GPU section); a communicator's are not.
  * No frame state moves: accumulation, image (internal or external), payload, depth, normals, reservoirs, frame index, frame timings and
  * ray counters are untouched, and the frames rendered afterwards are the frames that would have been rendered without the call.  The
  * denoiser's buffers (guide records, albedo, two colour buffers, host staging: 96 B + up to 20 B per pixel) are allocated on the first
@@ -511,7 +511,7 @@ int fyprt_denoise_device(fyprt_context* ctx, const fyprt_denoise_params* params,
  * fyprt_denoise_temporal_reset.  (fyprt_denoise_temporal_set_motion, below, lets the history live through the two geometry edits.)
  * Errors, in this order: FYPRT_EINVAL for a NULL context / params, history_limit outside 1..256, feedback > 1, normal_min or plane_max
  * not finite, plane_max <= 0; then everything fyprt_denoise refuses, in its order, with params->spatial (its FYPRT_EINVAL cases, then
- * its FYPRT_ESTATE cases).  Multi-GPU bands are out of scope as there.
+ * its FYPRT_ESTATE cases).  Multi-GPU bands are out of scope (fyprt_group_denoise has no temporal form).
  * No frame state moves, as for fyprt_denoise, and the two denoisers do not disturb each other: the history lives in buffers of its own
  * (two of 64 B and two of 4 B per pixel, allocated on the first temporal call, dropped by fyprt_resize); the guide, albedo and colour
  * buffers of fyprt_denoise are shared scratch, and FYPRT_BUF_ALBEDO is written by either.
@@ -592,6 +592,22 @@ int fyprt_group_set_interleave(fyprt_group* group, uint32_t stripe_rows);
 int fyprt_group_render(fyprt_group* group, const fyprt_settings* settings);   /* one frame on every band; asynchronous */
 int fyprt_group_gather(fyprt_group* group, int root);               /* all bands' RGBA8 rows into context `root`'s image; asynchronous */
 int fyprt_group_synchronize(fyprt_group* group);
+/* fyprt_denoise for the frame the group rendered last: every context filters its own band, the bands pull the rows either side that
+ * their taps reach from the contexts that own them, and the output rows are collected on one context.  The outputs are, bit for bit,
+ * what fyprt_denoise with the same parameters returns for a single context holding the same frame: the bands' accumulation and payload
+ * rows stitched together, and the same frame index.
+ * Errors, in this order: FYPRT_EINVAL for a NULL group / params, every parameter case of fyprt_denoise, `root` out of range, (device
+ * entry) misaligned outputs, both outputs NULL; FYPRT_ESTATE for a member without a complete frame (fyprt_denoise's conditions),
+ * members whose last frames differ in frame index, a last group frame that was striped (fyprt_group_set_interleave), a member whose
+ * rows are not its band of the group (fyprt_set_rows behind the group).  The message is the offending member's.
+ * No frame state moves on any member.  Afterwards FYPRT_BUF_ALBEDO is valid on every member for its own rows.  The buffers (those of
+ * fyprt_denoise, the staging being the band's rows) are allocated per member on first use and dropped by fyprt_resize.
+ * fyprt_denoise* on a group member stays refused. */
+/* Host memory, blocking; width x height uint32 / float4 of the WHOLE frame; either output may be NULL.  band_ms: NULL or one float per
+ * band, the hipEvent time from its first to its last enqueued operation on its own stream (waits for its neighbours included). */
+int fyprt_group_denoise(fyprt_group* group, const fyprt_denoise_params* params, uint32_t* rgba8, float* radiance4, float* band_ms);
+/* Device memory on context `root`'s GPU, asynchronous: complete on root's stream (fyprt_stream of that context); no host wait. */
+int fyprt_group_denoise_device(fyprt_group* group, const fyprt_denoise_params* params, int root, void* rgba8, void* radiance4);
 /* --- one process per GPU: RCCL over xGMI (librccl.so.1 is opened on first use).  Rank 0 calls fyprt_comm_unique_id and hands
  *     the 128 bytes to the other ranks (any transport); every rank then calls fyprt_comm_init_rank on its resized context. */
 int fyprt_comm_unique_id(void* id128);
@@ -612,6 +628,11 @@ int fyprt_balance_rows(const uint32_t* row_bounds, const float* band_ms, int n, 
 int fyprt_last_frame_ms(fyprt_context* ctx, float* ms);
 /* The transfers of one halo exchange: (receiver, owner, first row, end row) per entry; returns the number of entries. */
 int fyprt_halo_plan(const uint32_t* row_bounds, int n, uint32_t halo, uint32_t height, int wrap_row, uint32_t* out4, int capacity);
+/* The transfers of one fyprt_group_denoise* call in issue order: (stage, receiver, owner, first row, end row) per entry.  Stage 0: the
+ * guide records (32 B per pixel), 2^iterations rows either side of the band; stage 1 + k: the colour buffer iteration k reads (16 B per
+ * pixel), 2^(k+1) rows; clipped to the image.  Pure host arithmetic.  Returns the number of entries (also when `capacity` is smaller;
+ * nothing is written beyond it), FYPRT_EINVAL for a bad table or iterations > 8. */
+int fyprt_group_denoise_plan(const uint32_t* row_bounds, int n, uint32_t height, uint32_t iterations, uint32_t* out5, int capacity);
 /* The point-to-point operations rank `rank` issues inside ONE RCCL group section, in issue order — kind 0: a halo exchange over
  * `row_bounds`; kind 1: fyprt_comm_set_rows from `row_bounds` to `new_bounds`.  (is_recv, peer, buffer, byte offset, bytes) per
  * operation; returns their number.  Pure host arithmetic (no device, no RCCL): lets a test check that the two ends of every pair of
