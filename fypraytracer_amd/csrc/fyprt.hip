@@ -1841,33 +1841,64 @@ template <class Enqueue> static int denoise_blocking(fyprt_context* c, uint32_t*
 }
 }  // extern "C++"
 
-// What both denoisers start with: the shared buffers, the frame descriptor `fr`, the prepare launch (into dn.col[0]) between ev[0] and ev[1].
-static int begin_denoise(fyprt_context* c, const fyprt_denoise_params& sp, uint32_t* rgba8, float4* radiance4, const Event* ev, int* launched, DnFrame& fr) {
+// ---- what fyprt_denoise*, fyprt_denoise_temporal* and fyprt_group_denoise* (fyprt_multi.h) enqueue with.
+// Iteration k.  scaled: sigma_luminance / 2^k (spatial); otherwise sigma_luminance itself (temporal: the variance carries the scale).
+static DnIter make_dn_iter(const fyprt_denoise_params& p, uint32_t k, bool scaled) {
+    return DnIter{1 << k, scaled ? p.sigma_luminance * (1.0f / (float)(1u << k)) : p.sigma_luminance, p.sigma_luminance > 0.0f ? 1u : 0u,
+                  p.sigma_plane, p.normal_power_log2, (k + 1 == p.iterations) ? 1u : 0u};
+}
+// The full-size guide, albedo and ping-pong colour buffers of a context and its dnDone event; the frame descriptor over them.
+static int ensure_dn_buffers(fyprt_context* c) {
     const size_t n = (size_t)c->W * c->H;
     if (c->dn.guide.n != 2 * n) {
         HIPCHK(c, c->dn.guide.alloc(2 * n)); HIPCHK(c, c->dn.albedo.alloc(n)); HIPCHK(c, c->dn.col[0].alloc(n)); HIPCHK(c, c->dn.col[1].alloc(n));
     }
     HIPCHK(c, create(c->dnDone, hipEventDisableTiming));
-    fr = DnFrame{};
-    fr.W = c->W; fr.H = c->H; fr.frameIndex = (float)c->lastFrameIndex; fr.demodulate = sp.demodulate_albedo;
-    fr.accum = c->accum.p; fr.guide = c->dn.guide.p; fr.albedo = c->dn.albedo.p; fr.rgba8 = rgba8; fr.radiance4 = radiance4;
-    DevScene sc = c->dsc; sc.rayCounter = nullptr;
-    if (ev) HIPCHK(c, hipEventRecord(ev[0], c->stream));
-    hipLaunchKernelGGL(k_dn_prepare, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, c->stream, sc, fr, c->payload.p, c->dn.col[0].p);
-    ++*launched;
-    if (ev) HIPCHK(c, hipEventRecord(ev[1], c->stream));
     return FYPRT_OK;
 }
-// ... and end with: the finish kernel on the unfiltered colour if no iteration ran, the last timing event, and dnDone — a pipelined
-// ReSTIR DI frame enqueued next runs its Part 1 on the front stream, which overwrites the payload: after the denoiser.
-static int end_denoise(fyprt_context* c, const DnFrame& fr, uint32_t iterations, const float4* unfiltered, const Event* evLast, int* launched) {
-    if (iterations == 0) { hipLaunchKernelGGL(k_dn_finish, dim3((uint32_t)(((size_t)c->W * c->H + 255u) / 256u)), dim3(256), 0, c->stream, fr, unfiltered); ++*launched; }
-    HIPCHK(c, hipGetLastError());
-    if (evLast) HIPCHK(c, hipEventRecord(*evLast, c->stream));
+static DnFrame dn_frame(const fyprt_context* c, uint32_t demodulate, uint32_t* rgba8, float4* radiance4) {
+    return DnFrame{c->W, c->H, (float)c->lastFrameIndex, demodulate, c->accum.p, c->dn.guide.p, c->dn.albedo.p, rgba8, radiance4};
+}
+static dim3 dn_pixel_grid(const DnFrame& fr, DnBand band) { return dim3((uint32_t)(((size_t)(band.rowEnd - band.rowBegin) * fr.W + 255u) / 256u)); }
+// One launch each on the context stream, on the rows of `band` (the whole frame: {0, H}); prepare writes dn.col[0].
+static void launch_dn_prepare(fyprt_context* c, const DnFrame& fr, DnBand band) {
+    DevScene sc = c->dsc; sc.rayCounter = nullptr;
+    hipLaunchKernelGGL(k_dn_prepare, dn_pixel_grid(fr, band), dim3(256), 0, c->stream, sc, fr, band, c->payload.p, c->dn.col[0].p);
+}
+static void launch_dn_iterate(fyprt_context* c, const DnFrame& fr, const DnIter& it, DnBand band, const float4* in, float4* out) {
+    for_dn_step(it.step, [&](auto S) {
+        constexpr int STEP = decltype(S)::value;
+        hipLaunchKernelGGL(k_dn_iterate<STEP>, dim3(dn_grid<STEP>(fr.W, band.rowEnd - band.rowBegin)), dim3(256), 0, c->stream, fr, it, band, in, out);
+    });
+}
+static void launch_dn_finish(fyprt_context* c, const DnFrame& fr, DnBand band, const float4* col) {
+    hipLaunchKernelGGL(k_dn_finish, dn_pixel_grid(fr, band), dim3(256), 0, c->stream, fr, band, col);
+}
+// What every call ends with on a context, after its last kernel: dnDone — a pipelined ReSTIR DI frame enqueued next runs its Part 1 on
+// the front stream, which overwrites the payload: after the denoiser.
+static int dn_call_done(fyprt_context* c) {
     HIPCHK(c, hipEventRecord(c->dnDone, c->stream));
     if (c->front) HIPCHK(c, hipStreamWaitEvent(c->front, c->dnDone, 0));
     c->albedoValid = true;
     return FYPRT_OK;
+}
+
+// What both single-context denoisers start with: the shared buffers, the frame descriptor `fr`, the prepare launch (into dn.col[0]) between ev[0] and ev[1].
+static int begin_denoise(fyprt_context* c, const fyprt_denoise_params& sp, uint32_t* rgba8, float4* radiance4, const Event* ev, int* launched, DnFrame& fr) {
+    TRY(ensure_dn_buffers(c));
+    fr = dn_frame(c, sp.demodulate_albedo, rgba8, radiance4);
+    if (ev) HIPCHK(c, hipEventRecord(ev[0], c->stream));
+    launch_dn_prepare(c, fr, DnBand{0, c->H});
+    ++*launched;
+    if (ev) HIPCHK(c, hipEventRecord(ev[1], c->stream));
+    return FYPRT_OK;
+}
+// ... and end with: the finish kernel on the unfiltered colour if no iteration ran, the last timing event, and dn_call_done.
+static int end_denoise(fyprt_context* c, const DnFrame& fr, uint32_t iterations, const float4* unfiltered, const Event* evLast, int* launched) {
+    if (iterations == 0) { launch_dn_finish(c, fr, DnBand{0, c->H}, unfiltered); ++*launched; }
+    HIPCHK(c, hipGetLastError());
+    if (evLast) HIPCHK(c, hipEventRecord(*evLast, c->stream));
+    return dn_call_done(c);
 }
 
 // Enqueues prepare + iterations (+ finish) on the context stream, outputs in device memory.  ev: 3 timing events or null.
@@ -1875,14 +1906,7 @@ static int enqueue_denoise(fyprt_context* c, const fyprt_denoise_params* p, uint
     DnFrame fr;
     TRY(begin_denoise(c, *p, rgba8, radiance4, ev, launched, fr));
     for (uint32_t k = 0; k < p->iterations; ++k) {
-        DnIter it{};
-        it.step = 1 << k; it.sigmaL = p->sigma_luminance * (1.0f / (float)(1u << k)); it.lumOn = p->sigma_luminance > 0.0f ? 1u : 0u;
-        it.sigmaPlane = p->sigma_plane; it.normalPow = p->normal_power_log2; it.last = (k + 1 == p->iterations) ? 1u : 0u;
-        const float4* in = c->dn.col[k & 1u].p; float4* out = c->dn.col[(k + 1u) & 1u].p;
-        for_dn_step(it.step, [&](auto S) {
-            constexpr int STEP = decltype(S)::value;
-            hipLaunchKernelGGL(k_dn_iterate<STEP>, dim3(dn_grid<STEP>(c->W, c->H)), dim3(256), 0, c->stream, fr, it, in, out);
-        });
+        launch_dn_iterate(c, fr, make_dn_iter(*p, k, true), DnBand{0, c->H}, c->dn.col[k & 1u].p, c->dn.col[(k + 1u) & 1u].p);
         ++*launched;
     }
     return end_denoise(c, fr, p->iterations, c->dn.col[0].p, ev ? ev + 2 : nullptr, launched);
@@ -1953,9 +1977,7 @@ static int enqueue_temporal(fyprt_context* c, const fyprt_temporal_params* p, ui
     ++*launched;
     if (ev) HIPCHK(c, hipEventRecord(ev[2], c->stream));
     for (uint32_t k = 0; k < sp.iterations; ++k) {           // colour: dn.col[1] -> [0] -> [1] ...; variance: dt.var[0] -> [1] -> [0] ...
-        DnIter it{};
-        it.step = 1 << k; it.sigmaL = sp.sigma_luminance; it.lumOn = sp.sigma_luminance > 0.0f ? 1u : 0u;
-        it.sigmaPlane = sp.sigma_plane; it.normalPow = sp.normal_power_log2; it.last = (k + 1 == sp.iterations) ? 1u : 0u;
+        const DnIter it = make_dn_iter(sp, k, false);
         const float4* in = c->dn.col[(k + 1u) & 1u].p; float4* out = c->dn.col[k & 1u].p;
         const float* vin = c->dt.var[k & 1u].p; float* vout = c->dt.var[(k + 1u) & 1u].p;
         float4* fb = (k == 0 && p->feedback) ? hist : nullptr;

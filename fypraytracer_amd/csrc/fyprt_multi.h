@@ -373,7 +373,7 @@ int fyprt_group_synchronize(fyprt_group* g) {
 }
 
 // ---- fyprt_group_denoise*: the a-trous denoiser (rt_denoise.h) on the group's bands.  Every pixel is filtered by the context that owns
-// its row, with the band forms of the kernels; what a tap beyond the band reads was pulled from the row's owner into the same place of
+// its row, with its band as the kernels' DnBand; what a tap beyond the band reads was pulled from the row's owner into the same place of
 // this context's full-size guide / colour buffers (group_denoise_plan).  The shared pixel code on the same inputs: the single-context
 // call's bits.  Nothing but the denoiser's own buffers and the caller's outputs is written.
 static int group_denoise_check(fyprt_group* g, const fyprt_denoise_params* p, int root, const void* rgba8, const void* radiance4, bool device) {
@@ -404,12 +404,11 @@ static int group_denoise_check(fyprt_group* g, const fyprt_denoise_params* p, in
 //   across calls       a later call (or the same call of the next frame of a pipelined sequence) may be enqueued while neighbours still
 //                      pull from this one: the first work of a call on a band waits for every other band's last `pulled` of the earlier
 //                      call; the kernel that writes the staging rows waits for the earlier root's `collect`; and the front stream
-//                      waits for the band's last kernel before the next pipelined frame's Part 1 overwrites the payload (dnDone, as
-//                      end_denoise does).
+//                      waits for the band's last kernel before the next pipelined frame's Part 1 overwrites the payload
+//                      (dn_call_done).
 static int group_denoise_enqueue(fyprt_group* g, const fyprt_denoise_params* p, int root, uint32_t* rgba8, float4* radiance4, bool timed) {
     const int n = (int)g->ctx.size();
     const uint32_t W = g->ctx[0]->W, H = g->ctx[0]->H;
-    const size_t npx = (size_t)W * H;
     const std::vector<DnXfer> plan = group_denoise_plan(g->bounds, H, p->iterations);
     std::vector<char> pullsFrom((size_t)n * n, 0);                // [owner * n + receiver]
     for (const DnXfer& t : plan) pullsFrom[(size_t)t.x.owner * n + t.x.receiver] = 1;
@@ -417,20 +416,15 @@ static int group_denoise_enqueue(fyprt_group* g, const fyprt_denoise_params* p, 
     for (int i = 0; i < n; ++i) {
         fyprt_context* c = g->ctx[i];
         HIPCHK(c, hipSetDevice(c->device));
-        if (c->dn.guide.n != 2 * npx) {
-            HIPCHK(c, c->dn.guide.alloc(2 * npx)); HIPCHK(c, c->dn.albedo.alloc(npx)); HIPCHK(c, c->dn.col[0].alloc(npx)); HIPCHK(c, c->dn.col[1].alloc(npx));
-        }
-        HIPCHK(c, create(c->dnDone, hipEventDisableTiming));
+        TRY(ensure_dn_buffers(c));
         fyprt_group::DenoiseEvents& e = g->dn[i];
         HIPCHK(c, create(e.done, hipEventDisableTiming)); HIPCHK(c, create(e.pulled, hipEventDisableTiming)); HIPCHK(c, create(e.collect, hipEventDisableTiming));
         if (timed) { HIPCHK(c, create(e.first)); HIPCHK(c, create(e.last)); }
         const uint32_t b = g->bounds[i], rows = g->bounds[i + 1] - b;
         bands[i] = DnBand{b, g->bounds[i + 1]};
         DnFrame& fr = frames[i];
-        fr = DnFrame{};
-        fr.W = W; fr.H = H; fr.frameIndex = (float)c->lastFrameIndex; fr.demodulate = p->demodulate_albedo;
-        fr.accum = c->accum.p; fr.guide = c->dn.guide.p; fr.albedo = c->dn.albedo.p;
-        if (i == root) { fr.rgba8 = rgba8; fr.radiance4 = radiance4; continue; }
+        fr = dn_frame(c, p->demodulate_albedo, i == root ? rgba8 : nullptr, i == root ? radiance4 : nullptr);
+        if (i == root) continue;
         // the band's output rows go to its staging (at least the band's size); the kernels index the whole frame, so they get the address
         // row 0 would have.  A buffer the earlier root may still read is not freed under it.
         const size_t need = (size_t)rows * W;
@@ -442,7 +436,6 @@ static int group_denoise_enqueue(fyprt_group* g, const fyprt_denoise_params* p, 
         if (rgba8) fr.rgba8 = reinterpret_cast<uint32_t*>(reinterpret_cast<uintptr_t>(c->dn.outImg.p) - (size_t)b * W * sizeof(uint32_t));
         if (radiance4) fr.radiance4 = reinterpret_cast<float4*>(reinterpret_cast<uintptr_t>(c->dn.outRad.p) - (size_t)b * W * sizeof(float4));
     }
-    auto band_grid = [&](int i) { return dim3((uint32_t)(((size_t)(bands[i].rowEnd - bands[i].rowBegin) * W + 255u) / 256u)); };
     auto pull = [&](int i, int stage) -> int {
         fyprt_context* c = g->ctx[i];
         HIPCHK(c, hipSetDevice(c->device));
@@ -470,8 +463,7 @@ static int group_denoise_enqueue(fyprt_group* g, const fyprt_denoise_params* p, 
         HIPCHK(c, hipSetDevice(c->device));
         if (timed) HIPCHK(c, hipEventRecord(g->dn[i].first, c->stream));
         if (g->dnCalled) for (int j = 0; j < n; ++j) if (j != i) HIPCHK(c, hipStreamWaitEvent(c->stream, g->dn[j].pulled, 0));
-        DevScene sc = c->dsc; sc.rayCounter = nullptr;
-        hipLaunchKernelGGL(k_dn_prepare_band, band_grid(i), dim3(256), 0, c->stream, sc, frames[i], bands[i], c->payload.p, c->dn.col[0].p);
+        launch_dn_prepare(c, frames[i], bands[i]);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipEventRecord(g->dn[i].done, c->stream));
     }
@@ -479,9 +471,7 @@ static int group_denoise_enqueue(fyprt_group* g, const fyprt_denoise_params* p, 
     for (int i = 0; i < n; ++i) TRY(pull(i, 0));
     // 3. per iteration: the colour halo it reads, then the iteration on the band's rows (one launch per band)
     for (uint32_t k = 0; k < p->iterations; ++k) {
-        DnIter it{};
-        it.step = 1 << k; it.sigmaL = p->sigma_luminance * (1.0f / (float)(1u << k)); it.lumOn = p->sigma_luminance > 0.0f ? 1u : 0u;
-        it.sigmaPlane = p->sigma_plane; it.normalPow = p->normal_power_log2; it.last = (k + 1 == p->iterations) ? 1u : 0u;
+        const DnIter it = make_dn_iter(*p, k, true);
         if (k > 0)
             for (int i = 0; i < n; ++i) {
                 fyprt_context* c = g->ctx[i];
@@ -493,12 +483,7 @@ static int group_denoise_enqueue(fyprt_group* g, const fyprt_denoise_params* p, 
             fyprt_context* c = g->ctx[i];
             HIPCHK(c, hipSetDevice(c->device));
             if (it.last) TRY(before_output(i));
-            const float4* in = c->dn.col[k & 1u].p; float4* out = c->dn.col[(k + 1u) & 1u].p;
-            const uint32_t rows = bands[i].rowEnd - bands[i].rowBegin;
-            for_dn_step(it.step, [&](auto S) {
-                constexpr int STEP = decltype(S)::value;
-                hipLaunchKernelGGL(k_dn_iterate_band<STEP>, dim3(dn_grid<STEP>(W, rows)), dim3(256), 0, c->stream, frames[i], it, bands[i], in, out);
-            });
+            launch_dn_iterate(c, frames[i], it, bands[i], c->dn.col[k & 1u].p, c->dn.col[(k + 1u) & 1u].p);
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, hipEventRecord(g->dn[i].done, c->stream));
         }
@@ -508,14 +493,12 @@ static int group_denoise_enqueue(fyprt_group* g, const fyprt_denoise_params* p, 
         HIPCHK(c, hipSetDevice(c->device));
         if (p->iterations == 0) {
             TRY(before_output(i));
-            hipLaunchKernelGGL(k_dn_finish_band, band_grid(i), dim3(256), 0, c->stream, frames[i], bands[i], c->dn.col[0].p);
+            launch_dn_finish(c, frames[i], bands[i], c->dn.col[0].p);
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, hipEventRecord(g->dn[i].done, c->stream));
         }
         if (timed) HIPCHK(c, hipEventRecord(g->dn[i].last, c->stream));
-        HIPCHK(c, hipEventRecord(c->dnDone, c->stream));
-        if (c->front) HIPCHK(c, hipStreamWaitEvent(c->front, c->dnDone, 0));
-        c->albedoValid = true;
+        TRY(dn_call_done(c));
     }
     // 4. the other bands' output rows into the caller's buffers, on root's stream
     fyprt_context* r = g->ctx[root];

@@ -14,10 +14,10 @@
 //                  correctness anchor).  The sums run in the contract's tap order in both forms.
 //                  The last iteration remodulates, tonemaps and packs instead of writing the colour buffer.
 //   k_dn_finish  : the same epilogue alone, for iterations == 0.
-// Band forms (k_dn_prepare_band, k_dn_iterate_band<STEP>, k_dn_finish_band; fyprt_group_denoise, fyprt_multi.h): the same arithmetic
-// (dn_prepare_pixel, dn_tap, dn_output) for the rows [rowBegin, rowEnd) of a frame split over several contexts.  The buffers stay
-// full-size: the taps beyond the band read the halo rows where the host's peer copies put them.  The full-frame kernels are kept as
-// separate kernels (the iteration as its own text: routed through a shared tile function its step-16 form compiles to other registers).
+// Every kernel computes the rows [rowBegin, rowEnd) of a DnBand: the full frame is the band [0, H) (fyprt_denoise*), a frame split over
+// several contexts one band each (fyprt_group_denoise, fyprt_multi.h).  The buffers stay full-size: the taps beyond a band read the halo
+// rows where the host's peer copies put them.  dn_tile_pos and dn_stage — the thread-to-pixel mapping and the LDS staging of a tile —
+// are shared with the temporal denoiser's iteration (rt_temporal.h: k_dt_iterate).
 #pragma once
 #include "rt_device.h"
 
@@ -67,7 +67,7 @@ RT_DEV void dn_output(const DnFrame& fr, uint32_t i, f3 e, bool filterable) {
     }
 }
 
-// one pixel of k_dn_prepare / k_dn_prepare_band
+// one pixel of k_dn_prepare
 RT_DEV void dn_prepare_pixel(const DevScene& sc, const DnFrame& fr, const Payload* __restrict__ payload, float4* __restrict__ col0, uint32_t i) {
     const float2* q = reinterpret_cast<const float2*>(payload + i);          // 40-byte records: 8-byte aligned
     const float2 p0 = q[0], p1 = q[1], p2 = q[2], p3 = q[3], p4 = q[4];      // t px | py pz | nx ny | nz u | v objectIndex
@@ -86,14 +86,9 @@ RT_DEV void dn_prepare_pixel(const DevScene& sc, const DnFrame& fr, const Payloa
     fr.albedo[i] = make_float4(a.x, a.y, a.z, flag);
     col0[i] = make_float4(c.x, c.y, c.z, dn_luminance(c.x, c.y, c.z));
 }
-__global__ void __launch_bounds__(256) k_dn_prepare(DevScene sc, DnFrame fr, const Payload* __restrict__ payload, float4* __restrict__ col0) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= fr.W * fr.H) return;
-    dn_prepare_pixel(sc, fr, payload, col0, i);
-}
-// rows [rowBegin, rowEnd) of a frame whose other rows belong to other contexts (the band forms; rowBegin < rowEnd <= H)
+// rows [rowBegin, rowEnd) of a frame: all of them, or those of a context whose other rows belong to other contexts (rowBegin < rowEnd <= H)
 struct DnBand { uint32_t rowBegin, rowEnd; };
-__global__ void __launch_bounds__(256) k_dn_prepare_band(DevScene sc, DnFrame fr, DnBand band, const Payload* __restrict__ payload, float4* __restrict__ col0) {
+__global__ void __launch_bounds__(256) k_dn_prepare(DevScene sc, DnFrame fr, DnBand band, const Payload* __restrict__ payload, float4* __restrict__ col0) {
     const uint32_t i = band.rowBegin * fr.W + blockIdx.x * 256u + threadIdx.x;
     if (i >= band.rowEnd * fr.W) return;
     dn_prepare_pixel(sc, fr, payload, col0, i);
@@ -116,92 +111,52 @@ RT_DEV void dn_tap(const DnIter& it, const float4& c0, const float4& c1, float s
 }
 RT_DEV float dn_h(int d) { return d == 0 ? 0.375f : ((d == 1 || d == -1) ? 0.25f : 0.0625f); }
 
-// STEP 0: taps gathered from memory at the run-time step it.step; STEP > 0: tile + halo staged in LDS.
-// Grid: tiles across x groups of TY * S rows x S row phases (dn_grid).
-template <int STEP>
-__global__ void __launch_bounds__(256) k_dn_iterate(DnFrame fr, DnIter it, const float4* __restrict__ colIn, float4* __restrict__ colOut) {
+// Where a thread of workgroup blockIdx.x stands: the tile's first column and row (xBase, yBase), the thread's place in the tile (lx, ly)
+// and its pixel (x, y).  Grid: tiles across x groups of TY * S rows x S row phases (dn_grid), counted from firstRow.  16 x 16 tiles: one
+// 8 x 8 quad per wave; 64 x 4 tiles: one row per wave.
+struct DnTilePos { int xBase, yBase, lx, ly, x, y; };
+template <int STEP> RT_DEV DnTilePos dn_tile_pos(uint32_t W, int firstRow) {
     using T = DnTile<STEP>;
-    __shared__ float4 sG0[T::RECORDS], sG1[T::RECORDS], sC[T::RECORDS];
-    const uint32_t tilesX = (fr.W + (T::TX - 1)) / T::TX;
+    const uint32_t tilesX = (W + (T::TX - 1)) / T::TX;
     const uint32_t bx = blockIdx.x % tilesX, rest = blockIdx.x / tilesX;
-    const int xBase = (int)bx * T::TX, yBase = (int)(rest / T::S) * (T::TY * T::S) + (int)(rest % T::S);   // the tile's first column, first row
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const int lx = T::TX == 64 ? (int)lane : (int)(((wave & 1u) << 3) + (lane & 7u));
-    const int ly = T::TX == 64 ? (int)wave : (int)(((wave >> 1) << 3) + (lane >> 3));
-    const int x = xBase + lx, y = yBase + ly * T::S;
-    if (STEP) {
-        for (int k = (int)threadIdx.x; k < T::RW * T::RH; k += 256) {
-            const int rx = k % T::RW, ry = k / T::RW, gx = xBase - 2 * T::S + rx, gy = yBase + (ry - 2) * T::S;
-            const bool in = gx >= 0 && gy >= 0 && gx < (int)fr.W && gy < (int)fr.H;
-            const size_t j = in ? (size_t)gy * fr.W + (size_t)gx : 0;          // (outside the image: any valid address, the record is flagged unusable)
-            float4 g1 = fr.guide[2 * j + 1];
-            if (!in) g1.w = 0.0f;
-            sG0[ry * T::STRIDE + rx] = fr.guide[2 * j]; sG1[ry * T::STRIDE + rx] = g1; sC[ry * T::STRIDE + rx] = colIn[j];
-        }
-        __syncthreads();
-    }
-    if (x >= (int)fr.W || y >= (int)fr.H) return;
-    const uint32_t i = (uint32_t)y * fr.W + (uint32_t)x;
-    const int lc = (ly + 2) * T::STRIDE + lx + 2 * T::S;                        // this pixel inside the staged region
-    const float4 c0 = STEP ? sG0[lc] : fr.guide[2 * (size_t)i];
-    const float4 c1 = STEP ? sG1[lc] : fr.guide[2 * (size_t)i + 1];
-    const float4 cp = STEP ? sC[lc] : colIn[i];
-    const bool filterable = c1.w != 0.0f;
-    f3 e = mk3(cp.x, cp.y, cp.z);
-    if (filterable) {
-        const float sigmaPlaneT = it.sigmaPlane * c0.w;
-        DnSums s{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int dy = -2; dy <= 2; ++dy) {
-#pragma unroll
-            for (int dx = -2; dx <= 2; ++dx) {
-                const float hh = dn_h(dy) * dn_h(dx);
-                if (dx == 0 && dy == 0) { s.r = s.r + cp.x * hh; s.g = s.g + cp.y * hh; s.b = s.b + cp.z * hh; s.w = s.w + hh; continue; }
-                if (STEP) {
-                    const int k = lc + dy * T::STRIDE + dx * T::S;
-                    const float4 g1 = sG1[k];
-                    dn_tap(it, c0, c1, sigmaPlaneT, cp.w, sG0[k], g1, sC[k], g1.w != 0.0f, hh, s);
-                } else {
-                    const int qx = x + dx * it.step, qy = y + dy * it.step;
-                    const bool in = qx >= 0 && qy >= 0 && qx < (int)fr.W && qy < (int)fr.H;
-                    const size_t j = in ? (size_t)qy * fr.W + (size_t)qx : (size_t)i;   // (outside: the centre's own address, selected away)
-                    const float4 g1 = fr.guide[2 * j + 1];
-                    dn_tap(it, c0, c1, sigmaPlaneT, cp.w, fr.guide[2 * j], g1, colIn[j], in && g1.w != 0.0f, hh, s);
-                }
-            }
-        }
-        e = mk3(s.r / s.w, s.g / s.w, s.b / s.w);
-    }
-    if (it.last) dn_output(fr, i, e, filterable);
-    else colOut[i] = make_float4(e.x, e.y, e.z, dn_luminance(e.x, e.y, e.z));
+    DnTilePos p;
+    p.xBase = (int)bx * T::TX; p.yBase = firstRow + (int)(rest / T::S) * (T::TY * T::S) + (int)(rest % T::S);
+    p.lx = T::TX == 64 ? (int)lane : (int)(((wave & 1u) << 3) + (lane & 7u));
+    p.ly = T::TX == 64 ? (int)wave : (int)(((wave >> 1) << 3) + (lane >> 3));
+    p.x = p.xBase + p.lx; p.y = p.yBase + p.ly * T::S;
+    return p;
 }
-// The band form of k_dn_iterate, the same statements: the tiles start at band.rowBegin and the row phase counts from there (grid: dn_grid
-// of the band's height), pixels below band.rowEnd leave.  A tap is valid wherever it lies inside the image and is filterable: rows beyond
-// the band were copied from their owners into this context's guide and colour buffers.  A band lower than the tile's span (TY * S rows:
-// 128 at step 32) has workgroups whose first row already lies below it.
+// Stages the tile at (xBase, yBase) and its halo: guide records into sG0 / sG1, colour | luminance into sC, and waits for the workgroup.
+// A record outside the image is flagged unusable (sG1.w = 0).  g0w(g0, j): what the caller keeps in sG0.w of pixel j.
+template <int STEP, class G0W>
+RT_DEV void dn_stage(const DnFrame& fr, const float4* __restrict__ colIn, int xBase, int yBase, float4* sG0, float4* sG1, float4* sC, G0W g0w) {
+    using T = DnTile<STEP>;
+    for (int k = (int)threadIdx.x; k < T::RW * T::RH; k += 256) {
+        const int rx = k % T::RW, ry = k / T::RW, gx = xBase - 2 * T::S + rx, gy = yBase + (ry - 2) * T::S;
+        const bool in = gx >= 0 && gy >= 0 && gx < (int)fr.W && gy < (int)fr.H;
+        const size_t j = in ? (size_t)gy * fr.W + (size_t)gx : 0;          // (outside the image: any valid address, the record is flagged unusable)
+        float4 g0 = fr.guide[2 * j], g1 = fr.guide[2 * j + 1];
+        g0w(g0, j);
+        if (!in) g1.w = 0.0f;
+        sG0[ry * T::STRIDE + rx] = g0; sG1[ry * T::STRIDE + rx] = g1; sC[ry * T::STRIDE + rx] = colIn[j];
+    }
+    __syncthreads();
+}
+
+// STEP 0: taps gathered from memory at the run-time step it.step; STEP > 0: tile + halo staged in LDS.
+// The tiles start at band.rowBegin and the row phase counts from there (grid: dn_grid of the band's height), pixels below band.rowEnd
+// leave.  A tap is valid wherever it lies inside the image and is filterable: rows beyond a context's band were copied from their
+// owners into its guide and colour buffers.  A band lower than the tile's span (TY * S rows: 128 at step 32) has workgroups whose first
+// row already lies below it.
 template <int STEP>
-__global__ void __launch_bounds__(256) k_dn_iterate_band(DnFrame fr, DnIter it, DnBand band, const float4* __restrict__ colIn, float4* __restrict__ colOut) {
+__global__ void __launch_bounds__(256) k_dn_iterate(DnFrame fr, DnIter it, DnBand band, const float4* __restrict__ colIn, float4* __restrict__ colOut) {
     using T = DnTile<STEP>;
     __shared__ float4 sG0[T::RECORDS], sG1[T::RECORDS], sC[T::RECORDS];
-    const uint32_t tilesX = (fr.W + (T::TX - 1)) / T::TX;
-    const uint32_t bx = blockIdx.x % tilesX, rest = blockIdx.x / tilesX;
-    const int xBase = (int)bx * T::TX, yBase = (int)band.rowBegin + (int)(rest / T::S) * (T::TY * T::S) + (int)(rest % T::S);
-    if (yBase >= (int)band.rowEnd) return;                                       // (the whole workgroup: before anything is staged)
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const int lx = T::TX == 64 ? (int)lane : (int)(((wave & 1u) << 3) + (lane & 7u));
-    const int ly = T::TX == 64 ? (int)wave : (int)(((wave >> 1) << 3) + (lane >> 3));
-    const int x = xBase + lx, y = yBase + ly * T::S;
-    if (STEP) {
-        for (int k = (int)threadIdx.x; k < T::RW * T::RH; k += 256) {
-            const int rx = k % T::RW, ry = k / T::RW, gx = xBase - 2 * T::S + rx, gy = yBase + (ry - 2) * T::S;
-            const bool in = gx >= 0 && gy >= 0 && gx < (int)fr.W && gy < (int)fr.H;
-            const size_t j = in ? (size_t)gy * fr.W + (size_t)gx : 0;          // (outside the image: any valid address, the record is flagged unusable)
-            float4 g1 = fr.guide[2 * j + 1];
-            if (!in) g1.w = 0.0f;
-            sG0[ry * T::STRIDE + rx] = fr.guide[2 * j]; sG1[ry * T::STRIDE + rx] = g1; sC[ry * T::STRIDE + rx] = colIn[j];
-        }
-        __syncthreads();
-    }
+    const DnTilePos tp = dn_tile_pos<STEP>(fr.W, (int)band.rowBegin);
+    if (tp.yBase >= (int)band.rowEnd) return;                                    // (the whole workgroup: before anything is staged)
+    const int lx = tp.lx, ly = tp.ly, x = tp.x, y = tp.y;
+    if (STEP) dn_stage<STEP>(fr, colIn, tp.xBase, tp.yBase, sG0, sG1, sC, [](float4&, size_t) {});
     if (x >= (int)fr.W || y >= (int)band.rowEnd) return;
     const uint32_t i = (uint32_t)y * fr.W + (uint32_t)x;
     const int lc = (ly + 2) * T::STRIDE + lx + 2 * T::S;                        // this pixel inside the staged region
@@ -237,18 +192,12 @@ __global__ void __launch_bounds__(256) k_dn_iterate_band(DnFrame fr, DnIter it, 
     if (it.last) dn_output(fr, i, e, filterable);
     else colOut[i] = make_float4(e.x, e.y, e.z, dn_luminance(e.x, e.y, e.z));
 }
-template <int STEP> inline uint32_t dn_grid(uint32_t W, uint32_t H) {
+template <int STEP> inline uint32_t dn_grid(uint32_t W, uint32_t rows) {
     using T = DnTile<STEP>;
-    return ((W + (T::TX - 1)) / T::TX) * ((H + (T::TY * T::S - 1)) / (T::TY * T::S)) * (uint32_t)T::S;
+    return ((W + (T::TX - 1)) / T::TX) * ((rows + (T::TY * T::S - 1)) / (T::TY * T::S)) * (uint32_t)T::S;
 }
 
-__global__ void __launch_bounds__(256) k_dn_finish(DnFrame fr, const float4* __restrict__ colIn) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= fr.W * fr.H) return;
-    const float4 c = colIn[i];
-    dn_output(fr, i, mk3(c.x, c.y, c.z), fr.albedo[i].w != 0.0f);
-}
-__global__ void __launch_bounds__(256) k_dn_finish_band(DnFrame fr, DnBand band, const float4* __restrict__ colIn) {
+__global__ void __launch_bounds__(256) k_dn_finish(DnFrame fr, DnBand band, const float4* __restrict__ colIn) {
     const uint32_t i = band.rowBegin * fr.W + blockIdx.x * 256u + threadIdx.x;
     if (i >= band.rowEnd * fr.W) return;
     const float4 c = colIn[i];

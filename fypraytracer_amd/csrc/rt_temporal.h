@@ -5,14 +5,15 @@
 // filter it along.  No reference counterpart; the contract is the header's, binary32 + - * / sqrt and selections in the order written
 // there, and tests/temporal_ref.py restates it in numpy bit for bit.
 //
-//   k_dn_prepare   : unchanged (rt_denoise.h) — guide record, albedo, e0 | L(e0).
+//   k_dn_prepare   : the spatial denoiser's (rt_denoise.h), on the band [0, H) — guide record, albedo, e0 | L(e0).
 //   k_dt_reproject : one thread per pixel, a wave = an 8 x 8 pixel quad (the four history taps of a wave stay within a few lines).
 //                    Gathers up to four 64-byte history records (DtRecord: P.xyz t | n.xyz filterable | colour.rgb N | m1 m2 variance 0),
 //                    integrates colour and moments, takes the temporal variance where N >= 4 and, behind a wave-uniform test, the 5 x 5
 //                    spatial estimate where N < 4; writes the new history record, the integrated colour | its luminance and the variance.
-//   k_dt_iterate   : k_dn_iterate's two forms (STEP > 0: tile + halo staged in LDS, STEP == 0: gathered) with the variance in the staged
-//                    record — it takes the place of the hit distance in the first quad, which only the centre needs and reads from
-//                    memory, so the record stays 48 bytes and the LDS table and bank layout of DnTile hold as they are.  The 3 x 3
+//   k_dt_iterate   : k_dn_iterate's two forms (STEP > 0: tile + halo staged in LDS, STEP == 0: gathered) on its tile skeleton — dn_tile_pos
+//                    from row 0 and dn_stage (rt_denoise.h) — with the variance in the staged record: dn_stage's hook puts it in the place
+//                    of the hit distance in the first quad, which only the centre needs and reads from memory, so the record stays
+//                    48 bytes and the LDS table and bank layout of DnTile hold as they are.  The tap loop is its own (dt_tap).  The 3 x 3
 //                    variance prefilter reads rows at distance 1, which a tile whose rows lie STEP apart does not hold: nine 4-byte
 //                    gathers per pixel.  Iteration 0 also writes its colour into the new history record (feedback).
 //   k_dt_moved / k_dt_reproject_motion : object motion (fyprt_denoise_temporal_set_motion), launched only while a vertex snapshot is
@@ -212,32 +213,16 @@ RT_DEV void dt_tap(const DnIter& it, const float4& c0, const float4& c1, float s
     if (use) { s.r = s.r + cq.x * w; s.g = s.g + cq.y * w; s.b = s.b + cq.z * w; s.w = s.w + w; s.v = s.v + vq * (w * w); }
 }
 
-// Grid and tiles as k_dn_iterate<STEP> (dn_grid, DnTile).  it.sigmaL = sigma_luminance itself (the variance carries the scale).
-// histOut: the new history, or null — iteration 0 of a call with feedback writes its colour there.
+// Grid, tiles and staging as k_dn_iterate<STEP> (dn_grid, DnTile, dn_tile_pos, dn_stage), the whole frame.  it.sigmaL = sigma_luminance
+// itself (the variance carries the scale).  histOut: the new history, or null — iteration 0 of a call with feedback writes its colour there.
 template <int STEP>
 __global__ void __launch_bounds__(256) k_dt_iterate(DnFrame fr, DnIter it, const float4* __restrict__ colIn, float4* __restrict__ colOut,
                                                     const float* __restrict__ varIn, float* __restrict__ varOut, float4* __restrict__ histOut) {
     using T = DnTile<STEP>;
     __shared__ float4 sG0[T::RECORDS], sG1[T::RECORDS], sC[T::RECORDS];     // sG0.w = the variance (not the hit distance)
-    const uint32_t tilesX = (fr.W + (T::TX - 1)) / T::TX;
-    const uint32_t bx = blockIdx.x % tilesX, rest = blockIdx.x / tilesX;
-    const int xBase = (int)bx * T::TX, yBase = (int)(rest / T::S) * (T::TY * T::S) + (int)(rest % T::S);
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const int lx = T::TX == 64 ? (int)lane : (int)(((wave & 1u) << 3) + (lane & 7u));
-    const int ly = T::TX == 64 ? (int)wave : (int)(((wave >> 1) << 3) + (lane >> 3));
-    const int x = xBase + lx, y = yBase + ly * T::S;
-    if (STEP) {
-        for (int k = (int)threadIdx.x; k < T::RW * T::RH; k += 256) {
-            const int rx = k % T::RW, ry = k / T::RW, gx = xBase - 2 * T::S + rx, gy = yBase + (ry - 2) * T::S;
-            const bool in = gx >= 0 && gy >= 0 && gx < (int)fr.W && gy < (int)fr.H;
-            const size_t j = in ? (size_t)gy * fr.W + (size_t)gx : 0;          // (outside the image: any valid address, the record is flagged unusable)
-            float4 g0 = fr.guide[2 * j], g1 = fr.guide[2 * j + 1];
-            g0.w = varIn[j];
-            if (!in) g1.w = 0.0f;
-            sG0[ry * T::STRIDE + rx] = g0; sG1[ry * T::STRIDE + rx] = g1; sC[ry * T::STRIDE + rx] = colIn[j];
-        }
-        __syncthreads();
-    }
+    const DnTilePos tp = dn_tile_pos<STEP>(fr.W, 0);
+    const int lx = tp.lx, ly = tp.ly, x = tp.x, y = tp.y;
+    if (STEP) dn_stage<STEP>(fr, colIn, tp.xBase, tp.yBase, sG0, sG1, sC, [&](float4& g0, size_t j) { g0.w = varIn[j]; });
     if (x >= (int)fr.W || y >= (int)fr.H) return;
     const uint32_t i = (uint32_t)y * fr.W + (uint32_t)x;
     const int lc = (ly + 2) * T::STRIDE + lx + 2 * T::S;

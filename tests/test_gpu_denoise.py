@@ -1,8 +1,8 @@
 """The denoiser (fyprt_denoise / fyprt_denoise_device) on the GPU against the numpy restatement of its contract (tests/denoise_ref.py),
 fed with the context's own accumulation, payload, albedo and frame index.  "Equal" is bitwise (NaN-aware) on every pixel of radiance4
-and rgba8: scenes x techniques x accumulation states, a parameter sweep, sizes that are no multiple of the tile; the albedo buffer
-itself; the identity configuration; no frame state moves; the torch path; the state errors; quality on the device; the 1M-triangle hall
-at 1920 x 1080."""
+and rgba8: scenes x techniques x accumulation states, a parameter sweep, sizes that are no multiple of the tile, the full frame
+as the band [0, H) beside a one-band group; the albedo buffer itself; the identity configuration; no frame state moves; the torch
+path; the state errors; quality on the device; the 1M-triangle hall at 1920 x 1080."""
 import numpy as np
 import pytest
 
@@ -99,6 +99,31 @@ def test_denoise_sizes_off_the_tile(scene_name, tech, size):
         _check(ctx, n, f"{scene_name} {size}", iterations=it)
     _check(ctx, n, f"{scene_name} {size}", iterations=6, sigma_luminance=1.0, normal_power_log2=7)
     _check(ctx, n, f"{scene_name} {size}", iterations=3, sigma_luminance=16.0, normal_power_log2=0, demodulate_albedo=0)
+    ctx.close()
+
+
+def test_full_frame_is_the_band_0_H():
+    """The full frame runs the kernels as the band [0, H): cornell 97 x 61 (no multiple of any tile span), NEE, one frame, iterations
+    0..8 — the finish kernel, the staged steps 1..32 and the gather form at steps 64 and 128, every one clipped by rowEnd = 61 (at step 32
+    a tile spans 128 rows: its tile rows 2 and 3 lie below the image in every row phase, tile row 1 in phases 29..31).  Each equals
+    denoise_ref, and a one-band group [0, 61] on the same frame gives the same bits.  (Workgroups whose first row lies below the frame
+    need H mod the tile span < STEP: the 24 x 20, 16 x 16 and 33 x 5 frames of test_denoise_sizes_off_the_tile.)"""
+    assert_numpy_keeps_subnormals()
+    W, H = 97, 61
+    ctx, sc = _context("cornell", W, H)
+    member, _ = _context("cornell", W, H, sc)
+    grp = capi.Group([member], [0, H])
+    st = settings_for(capi.NEE)
+    n = _frame(ctx, st, 1)
+    grp.render(st)
+    grp.synchronize()
+    assert bits_equal(member.read_buffer(capi.BUF_ACCUM), ctx.read_buffer(capi.BUF_ACCUM)).all()      # the same frame
+    for it in range(9):
+        img, rad, _ = _check(ctx, n, "band [0, H)", iterations=it)
+        g_img, g_rad = grp.denoise(capi.DenoiseParams(**dict(DEFAULTS, iterations=it)))
+        assert bits_equal(g_rad, rad).all() and (g_img == img).all(), f"iterations {it}: the one-band group differs from the context"
+    grp.close()
+    member.close()
     ctx.close()
 
 

@@ -138,7 +138,7 @@ def hall_five():
 
 @pytest.mark.parametrize("iterations", range(9))
 def test_iteration_sweep(hall_five, iterations):
-    """0: k_dn_finish_band alone; 1..6: the staged steps 1..32; 7, 8: the gather form at steps 64 and 128, whose halos (up to 256 rows)
+    """0: k_dn_finish alone; 1..6: the staged steps 1..32; 7, 8: the gather form at steps 64 and 128, whose halos (up to 256 rows)
     clip at the image and cross every band."""
     grp, ctxs, frame = hall_five
     _check(grp, ctxs, FIVE, 1, "sweep", frame, iterations=iterations)
