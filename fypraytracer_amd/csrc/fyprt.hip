@@ -116,7 +116,7 @@ struct fyprt_context {
     // persistent trace kernel of frame N (`stream`, on which every frame COMPLETES and which fyprt_stream() hands out)
     Stream front; Event evFront[2], evDone[2]; bool lastOverlapped = false; bool ringSplit[128] = {};
     static constexpr int kRing = 128;          // frames whose per-launch hipEvents are kept (fyprt_frame_timings)
-    Event ring[kRing][5]; int ringLaunches[kRing] = {}; unsigned long long frameSerial = 0; Event* ev = nullptr;
+    Event ring[kRing][5]; int ringLaunches[kRing] = {}; unsigned long long frameSerial = 0;
     uint32_t W = 0, H = 0, frameIndex = 1, rowBegin = 0, rowEnd = 0, halo = 0; bool rowsSet = false;
     uint32_t stripeRows = 0, stripeParts = 1, stripePart = 0;       // fyprt_set_row_stripes (per-pixel techniques only)
     uint32_t commStripeRows = 0, commLastStripeRows = 0; bool commLastStriped = false;
@@ -227,6 +227,23 @@ static int effective_stack_budget(const fyprt_context* c) {
     for (int i = 5; i >= 0; --i) if (kSizes[i] <= std::max(levels + 9, 16) && kSizes[i] - 1 >= levels + 4) { entries = kSizes[i]; break; }
     return std::min((int)rth::kStackBudget, std::max(levels, entries - 1));
 }
+// ... and what a traversing launch takes from it: the budget for its scene descriptor and a workgroup's dynamic LDS, the stack
+// ((budget + 1) entries per thread: LDS is what limits residency) + `topCount` staged top nodes (a -DRT_TOPCACHE build only)
+struct StackLds { int budget; size_t bytes; };
+static StackLds stack_lds(const fyprt_context* c, uint32_t topCount) { const int b = effective_stack_budget(c); return {b, (size_t)(b + 1) * kBlock * sizeof(int32_t) + (size_t)topCount * 64u}; }
+// Ray kernels of the path engine and the batched queries (tuning key 15: 0 = by tree size): small trees (cheap rays) one thread per ray, big ones persistent waves with lane refill
+static bool simple_ray_kernel(const fyprt_context* c) { return c->tuning[K_RAY_KERNEL] == 2 || (c->tuning[K_RAY_KERNEL] == 0 && c->hostBvh.tris.size() < 65536u); }
+// fyprt_settings as the kernels read them, with the reference's uint8_t casts (Renderer.cu:2444, :2480-2481)
+static DevSettings dev_settings(const fyprt_context* c, const fyprt_settings* s) {
+    DevSettings st; st.sky = f3{s->sky_color[0], s->sky_color[1], s->sky_color[2]}; st.maxBounces = (uint8_t)s->light_bounces; st.sampleCount = (uint8_t)s->sample_count;
+    st.candidateCount = (uint32_t)s->light_candidate_count; st.randSeed = s->rand_seed;
+    st.useTemporal = s->use_temporal_reuse ? 1u : 0u; st.useSpatial = s->use_spatial_reuse ? 1u : 0u;
+    st.historyLimit = (uint8_t)s->temporal_history_limit; st.numNeighbors = (uint8_t)s->spatial_neighbor_num; st.radius = (uint8_t)s->spatial_neighbor_radius;
+    st.skipDeadRays = c->tuning[K_SKIP_DEAD_RAYS] ? 1u : 0u;
+    return st;
+}
+// The descriptor of a launch that traces incoherent rays: the node-loop quorum of its kind, its own block of ray counters (or none)
+static DevScene secondary_scene(DevScene sc, uint32_t quorum, unsigned long long* counters) { sc.nodeQuorum = quorum; sc.rayCounter = counters; return sc; }
 
 static int upload(fyprt_context* c, void* dst, const void* src, size_t bytes) {
     if (bytes == 0 || c->hostOnly) return FYPRT_OK;
@@ -654,7 +671,7 @@ int fyprt_upload_scene(fyprt_context* c, const fyprt_scene_desc* s) {
     d.nodes = c->nodes.p; d.leafTris = c->leafTris.p; d.rootRef = rth::device_ref(c->hostBvh.rootRef); d.triCount = nT;
     d.triPos = c->triPos.p; d.triShade = c->triShade.p; d.mats = c->mats.p; d.textures = c->texTable.p; d.textureCount = s->texture_count;
     d.emissive = c->emissive.p; d.emissiveCount = (uint32_t)em.size();
-    d.rayCounter = nullptr;
+    d.rayCounter = nullptr; d.topCount = 0u; d.stackBudget = 0; d.nodeQuorum = 0u;     // per launch: every launch sets them on its own copy
     // per-light records for ReSTIR DI, computed on the device with the kernels' own arithmetic
     HIPCHK(c, c->lightRecs.alloc(em.size() * 3, c->hostOnly));
     d.lightRecs = c->lightRecs.p;
@@ -667,7 +684,6 @@ int fyprt_upload_scene(fyprt_context* c, const fyprt_scene_desc* s) {
     c->haveScene = true;
     return FYPRT_OK;
 }
-
 
 // (Re)build the light trees from the given vertices with the stored topology and upload them (+ the emitter -> TLAS-leaf table).
 static int rebuild_light_trees(fyprt_context* c, const fyprt_vertex* verts, const uint8_t* touched = nullptr) {
@@ -1022,9 +1038,9 @@ static int run_stage(fyprt_context* c, const StageRun& r, const StageBufs& b, co
     const dim3 block(kBlock);
     const dim3 shadeGrid((uint32_t)(c->numCUs * 8));
     const int occ = c->pathOcc.get(k_trace_rays<false>, ldsBytes, 4), perCU = c->tuning[K_WG_PER_CU] > 0 ? c->tuning[K_WG_PER_CU] : occ;
-    DevScene tsc = sc;
-    tsc.nodeQuorum = (uint32_t)c->tuning[K_QUORUM_SECONDARY];                 // incoherent rays: leave the node loop once few lanes remain in it
-    tsc.rayCounter = b.rayCounter ? b.rayCounter + 8 * r.counterPart : nullptr;
+    // incoherent rays: leave the node loop once few lanes remain in it
+    const DevScene tsc = secondary_scene(sc, (uint32_t)c->tuning[K_QUORUM_SECONDARY], b.rayCounter ? b.rayCounter + 8 * r.counterPart : nullptr);
+    const bool simple = simple_ray_kernel(c);
     for (uint32_t it = 0; it <= r.steps; ++it) {
         PathIO io{};
         io.fusedOwner = kNotFused;
@@ -1051,8 +1067,6 @@ static int run_stage(fyprt_context* c, const StageRun& r, const StageBufs& b, co
         TraceQueue q{};
         q.rays = io.raysOut; q.hits = b.hits[(it + 1u) & 1u]; q.count = io.countOut; q.raysPer = r.raysPer; q.head = r.heads + it + 1;
         set_queue_params(c, q, K_REFILL_LANES);
-        // small trees (cheap rays): one thread per ray; big ones: persistent waves with lane refill (tuning key 15: 0 = by tree size)
-        const bool simple = c->tuning[K_RAY_KERNEL] == 2 || (c->tuning[K_RAY_KERNEL] == 0 && c->hostBvh.tris.size() < 65536u);
         if (simple) {
             const uint32_t sg = (uint32_t)std::min<size_t>((size_t)c->numCUs * 16u, (r.maxEntries * r.raysPer + kBlock - 1) / kBlock);
             hipLaunchKernelGGL(tsc.rayCounter ? k_trace_rays_simple<true> : k_trace_rays_simple<false>, dim3(std::max(1u, sg)), block, ldsBytes, c->stream, tsc, q);
@@ -1073,9 +1087,19 @@ static int run_stage(fyprt_context* c, const StageRun& r, const StageBufs& b, co
 }
 }  // extern "C++"
 
-// phase: 0 = the whole frame; 1 = ReSTIR Part 1 only (nothing of the frame's bookkeeping advances); 2 = the rest of the frame that a
-// phase-1 call started.  The split exists for the halo EXCHANGE of a multi-GPU frame (fyprt_multi.h): Part 1 on every band, the
-// bands' Part-1 records of each other's halo rows copied across, Part 2 on every band.
+// The shape of a path technique's (0-6) sample: rays a pixel emits one after the other = trace passes `steps`, rays per path and step,
+// float4s of per-path state, and L = the length of each of its counter arrays (list counts, queue heads, NEE: MIS counts)
+struct PathShape { uint32_t steps, raysPer, stride; size_t L; };
+static PathShape path_shape(int tech, const DevSettings& st) {
+    const uint32_t nSamples = (tech == FYPRT_BRUTE_FORCE) ? 1u : st.sampleCount;
+    const uint32_t steps = (tech == FYPRT_LIGHT_SOURCE_SAMPLING) ? nSamples : nSamples * st.maxBounces;
+    return {steps, (tech == FYPRT_NEE && st.maxBounces != 1u) ? 2u : 1u, (tech == FYPRT_NEE) ? 6u : 2u, (size_t)steps + 2};
+}
+// ... and its stage over the `entries` paths the primary kernel listed in `pixels`; `counters`: 3 L zeroed words, NEE's pick list: `pixels2`
+static StageRun path_stage(int tech, const PathShape& p, uint32_t* pixels, uint32_t* pixels2, uint32_t* counters, size_t entries) {
+    return StageRun{tech, p.steps, p.raysPer, p.stride, pixels, counters, counters + p.L, tech == FYPRT_NEE ? pixels2 : nullptr, nullptr, 0, tech == FYPRT_NEE ? counters + 2 * p.L : nullptr, entries};
+}
+
 // The "previous normals" of a ReSTIR frame are the last ReSTIR frame's, whichever of the two techniques rendered it (the reference keeps
 // one pair of normal buffers for both; rt_refit.h: k_sync_history_normals).  Called before Part 1 — by the multi-GPU layer before the
 // halo rows' history is fetched from their owners, so that what travels is already in step.
@@ -1089,254 +1113,245 @@ static int sync_restir_normals(fyprt_context* c, int tech, hipStream_t stream) {
     return c->hip(hipGetLastError(), "k_sync_history_normals");
 }
 
-static int enqueue_frame_impl(fyprt_context* c, const fyprt_settings* s, bool timed, int phase);
-static int enqueue_frame(fyprt_context* c, const fyprt_settings* s, bool timed, int phase = 0) {
-    const int rc = enqueue_frame_impl(c, s, timed, phase);
-    if (rc != FYPRT_OK && rc != FYPRT_ESTATE) c->part1Pending = false;      // a frame that failed half-way is abandoned, not left pending
-    return rc;
+// ---- a frame's host path: check_frame, begin_frame, one function per technique family, end_frame.  FrameRun carries what they share.
+// sc: the frame's own copy of c->dsc — the four per-launch fields are set here, never in the context; ldsBytes: traversal stack (+ top nodes) of its
+// traversing launches; par: queue / event parity; wavefront: ReSTIR DI Part 2 over a task queue; overlap: pipelined over two streams; fs: where Part 1 +
+// setup go; grid: tiles of the context's rows; ev, ei: its slot of the timing ring, the next event to record; launches: the parts it reports (not its
+// kernels); part1Only: phase 1 — Part 1 is enqueued, the frame stops there
+struct FrameRun {
+    fyprt_context* c; const fyprt_settings* s; int tech, phase; bool timed;
+    DevSettings st; DevFrame fr; DevScene sc; size_t ldsBytes;
+    int par; bool wavefront, overlap, striped; hipStream_t fs; dim3 grid;
+    Event* ev; int ei, launches, stageLaunches; bool part1Only;
+};
+static bool stripes_set(const fyprt_context* c) { return c->stripeRows != 0 && c->stripeRows < c->H && c->stripeParts > 1; }
+static dim3 tile_grid(const fyprt_context* c, uint32_t rowBegin, uint32_t rowEnd) {
+    const uint32_t tilesX = (c->W + 15u) / 16u, tilesY = (rowEnd - rowBegin + 15u) / 16u;
+    return dim3(c->tuning[K_TILE_ORDER] == 2 ? tilesX * ((tilesY + 7u) / 8u) * 8u : ((tilesX * tilesY + 7u) / 8u) * 8u);
 }
-static int enqueue_frame_impl(fyprt_context* c, const fyprt_settings* s, bool timed, int phase) {
+static unsigned long long* frame_counters(const fyprt_context* c, int part) { return c->countRays ? c->rayCounter.p + 8 * part : nullptr; }   // of the frame's launch `part`
+// Every refusal of a frame; nothing is enqueued or modified before it passes.
+static int check_frame(fyprt_context* c, const fyprt_settings* s, int phase) {
     if (c->hostOnly) return c->fail(FYPRT_ESTATE, "host-only context (device -1) cannot render");
     if (!c->haveScene || !c->haveCamera || c->W == 0) return c->fail(FYPRT_ESTATE, "fyprt_render: resize, upload_scene and set_camera must precede render");
     if (c->dcam.W != c->W || c->dcam.H != c->H) return c->fail(FYPRT_ESTATE, "fyprt_render: camera viewport differs from the render size");
-    const int tech = s->technique;
+    const int tech = s->technique; const bool restir = tech == FYPRT_RESTIR_DI || tech == FYPRT_RESTIR_GI;
     if (tech < 0 || tech > 8) return c->fail(FYPRT_EINVAL, "fyprt_render: unknown technique");
-    if (phase != 0 && tech != FYPRT_RESTIR_DI && tech != FYPRT_RESTIR_GI) return c->fail(FYPRT_EINVAL, "fyprt_render_part: only the ReSTIR techniques have two parts");
+    if (phase != 0 && !restir) return c->fail(FYPRT_EINVAL, "fyprt_render_part: only the ReSTIR techniques have two parts");
     if (phase == 2 && !c->part1Pending) return c->fail(FYPRT_ESTATE, "fyprt_render_part(2) without a preceding part 1");
     if (phase != 2 && c->part1Pending) return c->fail(FYPRT_ESTATE, "a frame's part 1 is pending: call fyprt_render_part(ctx, settings, 2) first");
     if ((tech == FYPRT_LIGHT_SOURCE_SAMPLING || tech == FYPRT_NEE) && (c->dsc.emissiveCount == 0 || c->dsc.ltTlasCount == 0))
         return c->fail(FYPRT_ENOLIGHT, "fyprt_render: technique needs emissive triangles and a light tree");
     if (tech == FYPRT_RESTIR_DI && c->dsc.emissiveCount == 0) return c->fail(FYPRT_ENOLIGHT, "fyprt_render: ReSTIR DI needs emissive triangles");
+    if (restir && stripes_set(c)) return c->fail(FYPRT_ESTATE, "ReSTIR frames need contiguous rows: clear fyprt_set_row_stripes first");
+    return FYPRT_OK;
+}
+// The descriptors, the pipelining decision, the memsets a new frame starts with and its slot of the timing ring.
+static int begin_frame(FrameRun& f) {
+    fyprt_context* c = f.c; DevFrame& fr = f.fr;
     HIPCHK(c, hipSetDevice(c->device));
-    DevSettings st;
-    st.sky = f3{s->sky_color[0], s->sky_color[1], s->sky_color[2]};
-    st.maxBounces = (uint8_t)s->light_bounces; st.sampleCount = (uint8_t)s->sample_count;       // Renderer.cu:2444, :2480-2481
-    st.candidateCount = (uint32_t)s->light_candidate_count; st.randSeed = s->rand_seed;
-    st.useTemporal = s->use_temporal_reuse ? 1u : 0u; st.useSpatial = s->use_spatial_reuse ? 1u : 0u;
-    st.historyLimit = (uint8_t)s->temporal_history_limit; st.numNeighbors = (uint8_t)s->spatial_neighbor_num; st.radius = (uint8_t)s->spatial_neighbor_radius;
-    st.skipDeadRays = c->tuning[K_SKIP_DEAD_RAYS] ? 1u : 0u;
-    DevFrame fr;
+    f.st = dev_settings(c, f.s);
     fr.accum = c->accum.p; fr.image = c->externalImage ? c->externalImage : c->image.p; fr.payload = c->payload.p; fr.depth = c->depth.p;
     fr.normalPrev = c->normalFlip ? c->normalB.p : c->normalA.p; fr.normalCur = c->normalFlip ? c->normalA.p : c->normalB.p;
     fr.di = c->di.p; fr.diPrev = c->diPrev.p; fr.gi = c->gi.p; fr.giPrev = c->giPrev.p; fr.giHot = c->giHot.p;
     fr.drec = c->drec.p; fr.dprevRead = c->dprevFlip ? c->dprevB.p : c->dprevA.p; fr.dprevWrite = c->dprevFlip ? c->dprevA.p : c->dprevB.p;
     fr.W = c->W; fr.H = c->H; fr.frameIndex = c->frameIndex; fr.rowBegin = c->rowBegin; fr.rowEnd = c->rowEnd;
-    fr.stripeRows = 0; fr.stripeParts = 1; fr.stripePart = 0;
-    const bool striped = c->stripeRows != 0 && c->stripeRows < c->H && c->stripeParts > 1;
-    if (striped && (tech == FYPRT_RESTIR_DI || tech == FYPRT_RESTIR_GI)) return c->fail(FYPRT_ESTATE, "ReSTIR frames need contiguous rows: clear fyprt_set_row_stripes first");
-    fr.histBegin = (tech == FYPRT_RESTIR_GI) ? c->histGI[0] : c->histDI[0]; fr.histEnd = (tech == FYPRT_RESTIR_GI) ? c->histGI[1] : c->histDI[1];
-    c->dsc.rayCounter = c->countRays ? c->rayCounter.p : nullptr;
-    // node-loop quorum of the fused per-pixel kernels (key 7): 0 = auto — 16 for the light-tree kernels (their shadow rays: NEE 5.2 -> 4.95 ms),
-    // none elsewhere (path and ReSTIR GI kernels: neutral or slightly negative)
-    c->dsc.nodeQuorum = (uint32_t)c->tuning[K_QUORUM_PRIMARY];
-    // traversal-stack budget (node_step's rule): never below the level count (the induction), never above the 31 the node
-    // format records; by default a few entries above the level count, so the LDS stack is no larger than this tree needs
-    // and more workgroups fit a CU (LDS is what limits residency: (budget + 1) KB per 256-thread workgroup)
-    const int budget = effective_stack_budget(c);
-    c->dsc.stackBudget = budget;
+    fr.stripeRows = 0; fr.stripeParts = 1; fr.stripePart = 0; f.striped = stripes_set(c);
+    fr.histBegin = (f.tech == FYPRT_RESTIR_GI) ? c->histGI[0] : c->histDI[0]; fr.histEnd = (f.tech == FYPRT_RESTIR_GI) ? c->histGI[1] : c->histDI[1];
+    // The scene as the frame's first launches read it: counters of part 0; the node-loop quorum of the fused per-pixel kernels and of coherent primary rays (key 7:
+    // 0 = auto — 16 for the light-tree kernels (their shadow rays: NEE 5.2 -> 4.95 ms), none elsewhere (path and ReSTIR GI kernels: neutral or slightly negative))
 #ifdef RT_TOPCACHE
-    c->dsc.topCount = (uint32_t)std::min<size_t>((size_t)std::max(0, c->tuning[K_TOP_NODES]), c->hostBvh.nodes.size());
+    const uint32_t topCount = (uint32_t)std::min<size_t>((size_t)std::max(0, c->tuning[K_TOP_NODES]), c->hostBvh.nodes.size());
 #else
-    c->dsc.topCount = 0u;                      // tuning key 16 only acts in a -DRT_TOPCACHE build (rt_device.h: measured slower)
+    const uint32_t topCount = 0u;              // tuning key 16 only acts in a -DRT_TOPCACHE build (rt_device.h: measured slower)
 #endif
-    const size_t ldsBytes = (size_t)(budget + 1) * kBlock * sizeof(int32_t) + (size_t)c->dsc.topCount * 64u;
-    // Pipelining (tuning key 11): a wavefront ReSTIR DI frame runs Part 1 + setup on the front stream and the trace kernel on
-    // `stream`.  Nothing the front part writes is read or written by a trace kernel (payload, records, history, depth, its own
-    // task queue — two queues alternate), and image + accumulation are touched by trace kernels only (p1Mode 1), which stay in
-    // frame order on `stream`; so frame N+1's front part may run beside frame N's trace kernel.  Any other frame runs on
-    // `stream` alone, after everything before it.
-    const int par = (int)(c->frameSerial & 1ull);
-    const bool wavefront = tech == FYPRT_RESTIR_DI && c->tuning[K_DI_WAVEFRONT] == 1;
-    const bool overlap = wavefront && c->tuning[K_PIPELINE] != 0 && !c->countRays && phase == 0;
-    hipStream_t fs = overlap ? c->front : c->stream;             // where Part 1 + setup go
-    if (overlap) {
-        HIPCHK(c, hipStreamWaitEvent(c->front, c->evDone[par], 0));                            // frame N-2 done: its queue is free
-        if (!c->lastOverlapped) HIPCHK(c, hipStreamWaitEvent(c->front, c->evDone[par ^ 1], 0));   // frame N-1 ran on `stream` alone
+    const StackLds stack = stack_lds(c, topCount);
+    f.sc = secondary_scene(c->dsc, (uint32_t)c->tuning[K_QUORUM_PRIMARY], frame_counters(c, 0));
+    f.sc.stackBudget = stack.budget; f.sc.topCount = topCount; f.ldsBytes = stack.bytes;
+    // Pipelining (tuning key 11): a wavefront ReSTIR DI frame runs Part 1 + setup on the front stream and the trace kernel on `stream`.  Nothing the
+    // front part writes is read or written by a trace kernel (payload, records, history, depth, its own task queue — two queues alternate), and image +
+    // accumulation are touched by trace kernels only (p1Mode 1), which stay in frame order on `stream`; so frame N+1's front part may run beside frame
+    // N's trace kernel.  Any other frame runs on `stream` alone, after everything before it.
+    f.par = (int)(c->frameSerial & 1ull); f.wavefront = f.tech == FYPRT_RESTIR_DI && c->tuning[K_DI_WAVEFRONT] == 1;
+    f.overlap = f.wavefront && c->tuning[K_PIPELINE] != 0 && !c->countRays && f.phase == 0;
+    f.fs = f.overlap ? c->front : c->stream;
+    if (f.overlap) {
+        HIPCHK(c, hipStreamWaitEvent(c->front, c->evDone[f.par], 0));                            // frame N-2 done: its queue is free
+        if (!c->lastOverlapped) HIPCHK(c, hipStreamWaitEvent(c->front, c->evDone[f.par ^ 1], 0));   // frame N-1 ran on `stream` alone
     }
     c->frameComplete = false;                  // from the first enqueued work until the frame is enqueued to its end (fyprt_denoise)
-    if (phase != 2) std::memcpy(c->framePV, c->camPV, 64);    // the camera this frame is rendered with (fyprt_denoise_temporal)
-    if (c->countRays && phase != 2) HIPCHK(c, hipMemsetAsync(c->rayCounter.p, 0, 256, c->stream));
-    // frame 1 (or toAccumulate == false): the accumulator starts from zero (Renderer.cu:50-51) — on `stream`, which owns it
-    // (the whole buffer, as the reference does, not just this context's rows: a band moved later with fyprt_set_rows must not find the
-    // sums of an earlier accumulation in its new rows)
-    if (c->frameIndex == 1 && phase != 2) HIPCHK(c, hipMemsetAsync(c->accum.p, 0, c->accum.bytes(), c->stream));
-    const uint32_t tilesX = (c->W + 15u) / 16u;
-    fr.tileOrder = (uint32_t)c->tuning[K_TILE_ORDER];
-    fr.p1Mode = wavefront ? 1u : 0u;
-    auto gridFor = [&](uint32_t rb, uint32_t re) {
-        const uint32_t tilesY = (re - rb + 15u) / 16u;
-        if (c->tuning[K_TILE_ORDER] == 2) return dim3(tilesX * ((tilesY + 7u) / 8u) * 8u);
-        return dim3(((tilesX * tilesY + 7u) / 8u) * 8u);
-    };
-    const dim3 block(kBlock);
-    const dim3 grid = gridFor(c->rowBegin, c->rowEnd);
-    int ei = 0;
-    c->ev = c->ring[c->frameSerial % fyprt_context::kRing];
-    if (phase == 2) ei = 1;
-    else if (timed) HIPCHK(c, hipEventRecord(c->ev[ei++], fs));
-    int launches = 0;
-    // ---- wavefront path engine (rt_paths.h): primary kernel, then per step one shade launch + one persistent trace launch (run_stage)
-    int stageLaunches = 0;                                       // (a frame reports its parts as launches, not its kernels)
-    auto run_stage = [&](const StageRun& r) -> int {             // (the wf* buffers as ensure_paths left them)
-        const StageBufs wf{{c->wfRays[0].p, c->wfRays[1].p}, {c->wfHits[0].p, c->wfHits[1].p}, c->wfState.p, c->wfPixels.p, c->wfPixels2.p,
-                           c->countRays ? c->rayCounter.p : nullptr};
-        return ::run_stage(c, r, wf, c->dsc, c->dcam, fr, st, ldsBytes, c->blockingCall, &stageLaunches);
-    };
-    switch (tech) {
-        case FYPRT_BRUTE_FORCE: case FYPRT_UNIFORM_SAMPLING: case FYPRT_COSINE_WEIGHTED_SAMPLING: case FYPRT_GGX_SAMPLING: case FYPRT_BRDF_SAMPLING:
-        case FYPRT_LIGHT_SOURCE_SAMPLING: case FYPRT_NEE: {
-            // rays a pixel emits one after the other = trace passes of the frame
-            const uint32_t nSamples = (tech == FYPRT_BRUTE_FORCE) ? 1u : st.sampleCount;
-            const uint32_t steps = (tech == FYPRT_LIGHT_SOURCE_SAMPLING) ? nSamples : nSamples * st.maxBounces;
-            const uint32_t raysPer = (tech == FYPRT_NEE && st.maxBounces != 1u) ? 2u : 1u;
-            dim3 pgrid = grid;
-            if (striped) {                                           // k_primary maps the local rows [0, n) onto this context's stripes
-                fr.stripeRows = c->stripeRows; fr.stripeParts = c->stripeParts; fr.stripePart = c->stripePart;
-                fr.rowBegin = 0; fr.rowEnd = stripe_row_count(c->H, c->stripeRows, c->stripeParts, c->stripePart);
-                pgrid = gridFor(fr.rowBegin, fr.rowEnd);
-            }
-            const size_t entries = (size_t)(fr.rowEnd - fr.rowBegin) * c->W, L = (size_t)steps + 2;
-            const uint32_t stride = (tech == FYPRT_NEE) ? 6u : 2u;
-            TRY(ensure_paths(c, entries, raysPer, stride, 3 * L));
-            HIPCHK(c, hipMemsetAsync(c->wfCounters.p, 0, 3 * L * sizeof(uint32_t), c->stream));
-            c->dsc.nodeQuorum = (uint32_t)c->tuning[K_QUORUM_PRIMARY];             // coherent primary rays
-            // small trees, techniques 0-5: the whole frame in one launch, one thread per pixel (rt_paths.h: k_path_fused; key 17: 0 = by tree size, 1 = never, 2 = always)
-            const bool fused = tech != FYPRT_NEE && (c->tuning[K_FUSED_FRAME] == 2 || (c->tuning[K_FUSED_FRAME] == 0 && c->hostBvh.tris.size() < 65536u));
-            if (fused) {
-                PathIO io{};
-                io.fusedOwner = kNotFused; io.raysIn = c->wfRays[0].p; io.raysOut = c->wfRays[0].p; io.hitsIn = c->wfHits[0].p; io.state = c->wfState.p; io.stateStride = stride; io.raysPer = 1u;
-                typedef void (*fused_kernel_t)(DevScene, DevCamera, DevFrame, DevSettings, PathIO, uint32_t);
-                static const fused_kernel_t kFused[2][6] = {{k_path_fused<T_BRUTE, false>, k_path_fused<T_UNIFORM, false>, k_path_fused<T_COSINE, false>, k_path_fused<T_GGX, false>, k_path_fused<T_BRDF, false>, k_path_fused<T_LIGHT, false>},
-                                                            {k_path_fused<T_BRUTE, true>, k_path_fused<T_UNIFORM, true>, k_path_fused<T_COSINE, true>, k_path_fused<T_GGX, true>, k_path_fused<T_BRDF, true>, k_path_fused<T_LIGHT, true>}};
-                hipLaunchKernelGGL(kFused[c->countRays ? 1 : 0][tech], pgrid, block, ldsBytes, c->stream, c->dsc, c->dcam, fr, st, io, steps);
-                launches = 1;
-                break;
-            }
-            hipLaunchKernelGGL(c->countRays ? k_primary<true> : k_primary<false>, pgrid, block, ldsBytes, c->stream, c->dsc, c->dcam, fr, st, c->wfPixels.p, c->wfCounters.p);
-            StageRun r{tech, steps, raysPer, stride, c->wfPixels.p, c->wfCounters.p, c->wfCounters.p + L, (tech == FYPRT_NEE) ? c->wfPixels2.p : nullptr, nullptr, 0, (tech == FYPRT_NEE) ? c->wfCounters.p + 2 * L : nullptr, entries};
-            TRY(run_stage(r));
-            launches = 1;
-            break;
-        }
-        case FYPRT_RESTIR_DI: case FYPRT_RESTIR_GI: {
-            // halo rows: Part 1 recomputed on them (default), or — exchange mode — left to the band that owns them and copied in between the parts
-            const uint32_t p1halo = (c->haloExchange || c->tuning[K_SKIP_HALO_PART1]) ? 0u : c->halo;
-            const uint32_t p1b = (c->rowBegin > p1halo) ? c->rowBegin - p1halo : 0u;
-            const uint32_t p1e = (c->rowEnd + p1halo < c->H) ? c->rowEnd + p1halo : c->H;
-            c->dsc.nodeQuorum = (uint32_t)c->tuning[K_QUORUM_PRIMARY];             // Part 1 traces coherent primary rays only
-            // The reference's spatial-neighbour coordinate is computed in unsigned arithmetic (R.cu:1916-1917): an offset
-            // above the first row wraps and clamps to the LAST row.  A band that owns rows < radius therefore also needs
-            // Part 1 of row H-1 (one extra row of recompute) to stay bit-identical to a single-GPU frame.  It rides in the same
-            // launch as one more row of tiles (a separate one-row launch is all latency: ~0.09 ms on a 135-row band).
-            const bool extra = p1halo > 0 && c->rowBegin < p1halo && p1e < c->H;
-            const uint32_t extraRow = extra ? c->H - 1u : 0xFFFFFFFFu;
-            const dim3 g1 = gridFor(p1b, extra ? p1e + 16u : p1e);
-            if (tech == FYPRT_RESTIR_GI) {
-                // Part 1 = primary kernel + bounce-loop steps (they build the Part-2 list as paths complete); Part 2 = neighbour-loop steps
-                const size_t p1px = ((size_t)(p1e - p1b) + (extra ? 1u : 0u)) * c->W;
-                const uint32_t steps1 = st.maxBounces, steps2 = st.useSpatial ? st.numNeighbors : 0u;
-                const size_t L1 = (size_t)steps1 + 2, L2 = (size_t)steps2 + 2;
-                TRY(ensure_paths(c, p1px, 1, 5, 2 * L1 + 2 * L2));
-                uint32_t* cnt1 = c->wfCounters.p; uint32_t* cnt2 = cnt1 + 2 * L1;      // cnt2[0] = length of the Part-2 list
-                if (phase != 2) TRY(sync_restir_normals(c, tech, c->stream));   // the last ReSTIR frame was a DI frame: its normals (in the history records) are this frame's "previous normals"
-                if (phase != 2) {
-                    HIPCHK(c, hipMemsetAsync(cnt1, 0, (2 * L1 + 2 * L2) * sizeof(uint32_t), c->stream));
-                    hipLaunchKernelGGL(c->countRays ? k_gi_primary<true> : k_gi_primary<false>, g1, block, ldsBytes, c->stream, c->dsc, c->dcam, fr, st, p1b, p1e, extraRow, c->wfPixels.p, cnt1);
-                    StageRun r1{T_GI1, steps1, 1u, 5u, c->wfPixels.p, cnt1, cnt1 + L1, c->wfPixels2.p, cnt2, 0, nullptr, p1px};
-                    TRY(run_stage(r1));
-                    if (timed) HIPCHK(c, hipEventRecord(c->ev[ei++], c->stream));
-                    if (phase == 1) { c->part1Pending = true; return c->hip(hipGetLastError(), "ReSTIR GI part 1"); }
-                }
-                if (c->tuning[K_GI2_MODE] == 2) {
-                    // Part 2 as one PERSISTENT launch (rt_paths.h: k_gi2_persistent): a lane owns a pixel of the list, lanes without a ray in flight are serviced together
-                    DevScene tsc = c->dsc;
-                    tsc.nodeQuorum = (uint32_t)c->tuning[K_QUORUM_SECONDARY];
-                    tsc.rayCounter = c->countRays ? c->rayCounter.p + 8 : nullptr;
-                    const int occ = c->gi2Occ.get(k_gi2_persistent<false>, ldsBytes, 3), perCU = c->tuning[K_WG_PER_CU] > 0 ? std::min(c->tuning[K_WG_PER_CU], occ) : occ;
-                    GI2Queue gq{};
-                    gq.list = c->wfPixels2.p; gq.count = cnt2; gq.head = cnt2 + L2 + 1;
-                    set_queue_params(c, gq, K_GI2_REFILL_LANES);
-                    hipLaunchKernelGGL(c->countRays ? k_gi2_persistent<true> : k_gi2_persistent<false>, dim3((uint32_t)(c->numCUs * perCU)), block, ldsBytes, c->stream, tsc, c->dcam, fr, st, gq);
-                    HIPCHK(c, hipGetLastError());
-                } else if (c->tuning[K_GI2_MODE] == 1) {
-                    // Part 2 in one launch (rt_paths.h: k_gi2_fused): one thread per listed pixel for the whole neighbour loop, visibility rays traced in place
-                    DevScene tsc = c->dsc;
-                    tsc.nodeQuorum = (uint32_t)c->tuning[K_QUORUM_SECONDARY];
-                    tsc.rayCounter = c->countRays ? c->rayCounter.p + 8 : nullptr;
-                    const uint32_t fg = (uint32_t)std::max<size_t>(1, std::min<size_t>((size_t)c->numCUs * 64u, (p1px + kBlock - 1) / kBlock));
-                    hipLaunchKernelGGL(c->countRays ? k_gi2_fused<true> : k_gi2_fused<false>, dim3(fg), block, ldsBytes, c->stream, tsc, c->dcam, fr, st, (const uint32_t*)c->wfPixels2.p, (const uint32_t*)cnt2);
-                    HIPCHK(c, hipGetLastError());
-                } else {
-                    StageRun r2{T_GI2, steps2, 1u, 5u, c->wfPixels2.p, cnt2, cnt2 + L2, nullptr, nullptr, 1, nullptr, p1px};
-                    TRY(run_stage(r2));
-                }
-                launches = 2;
-                c->normalFlip = !c->normalFlip; c->histGI[0] = c->rowBegin; c->histGI[1] = c->rowEnd;
-                break;
-            }
-            if (phase != 2) TRY(sync_restir_normals(c, tech, fs));   // the last ReSTIR frame was a GI frame: its normals are this frame's "previous normals"
-            if (phase != 2) {
-                hipLaunchKernelGGL(c->countRays ? k_di_part1<true> : k_di_part1<false>, g1, block, ldsBytes, fs, c->dsc, c->dcam, fr, st, p1b, p1e, extraRow);
-                if (timed) HIPCHK(c, hipEventRecord(c->ev[ei++], fs));
-                if (phase == 1) { c->part1Pending = true; return c->hip(hipGetLastError(), "ReSTIR DI part 1"); }
-            }
-            c->dsc.nodeQuorum = (uint32_t)c->tuning[K_QUORUM_SECONDARY];   // shadow-ray kernels of ReSTIR DI Part 2: measured 0.85 -> 0.68 ms
-            if (c->countRays) c->dsc.rayCounter = c->rayCounter.p + 8;      // per-launch counters
-            launches = 2;
-            if (tech == FYPRT_RESTIR_DI && c->tuning[K_DI_WAVEFRONT] == 1) {
-                ShadowQueue q{};
-                q.tasks = c->shadowTasks.p + (size_t)par * c->queueStride; q.counters = c->queueCounters.p + 4 * par;
-                set_queue_params(c, q, K_REFILL_LANES);
-                const size_t sg = (size_t)par * c->sortGroups;
-                q.sortMode = c->tuning[K_SORT_TASKS] ? 1u : 0u; q.numGroups = grid.x; q.counts = c->sortCounts.p + sg; q.keys = c->sortKeys.p + sg * 256u; q.hist = c->sortHist.p + sg * kSortBins;
-                q.binOffset = c->sortOffset.p + sg * kSortBins; q.binTotal = c->sortTotal.p + (size_t)par * kSortBins; q.sorted = c->sortIndex.p + sg * 256u;
-                HIPCHK(c, hipMemsetAsync(q.counters, 0, 16, fs));
-                if (c->tuning[K_SETUP_FETCH] == 1) hipLaunchKernelGGL(k_di_part2_setup<1>, grid, block, 0, fs, c->dsc, c->dcam, fr, st, q);
-                else if (c->tuning[K_SETUP_FETCH] == 2) hipLaunchKernelGGL(k_di_part2_setup<2>, grid, block, 0, fs, c->dsc, c->dcam, fr, st, q);
-                else hipLaunchKernelGGL(k_di_part2_setup<0>, grid, block, 0, fs, c->dsc, c->dcam, fr, st, q);
-                if (q.sortMode) {
-                    hipLaunchKernelGGL(k_di_sort_scan, dim3(kSortBins), block, 0, fs, q);
-                    hipLaunchKernelGGL(k_di_sort_scatter, grid, block, 0, fs, q);
-                }
-                if (timed) HIPCHK(c, hipEventRecord(c->ev[ei++], fs));
-                if (overlap) {                                   // the trace kernel waits for this frame's front part only
-                    HIPCHK(c, hipEventRecord(c->evFront[par], c->front));
-                    HIPCHK(c, hipStreamWaitEvent(c->stream, c->evFront[par], 0));
-                    if (timed) HIPCHK(c, hipEventRecord(c->ev[4], c->stream));      // start of the trace kernel on its own stream
-                }
-                if (c->countRays) c->dsc.rayCounter = c->rayCounter.p + 16;
-                int perCU = c->tuning[K_WG_PER_CU];
-                if (perCU <= 0) {          // as many workgroups as registers + LDS let a CU hold (asked from the runtime once per stack size)
-                    perCU = c->traceOcc.get(k_di_part2_trace<false>, ldsBytes, 4);
-                    // pipelined frames: the persistent grid shares the chip with Part 1 + setup of the NEXT frame; with every slot a CU has
-                    // (6 workgroups) those start late and run in extra rounds — 4 per CU leave them room: an eighth of the frame (a multi-GPU
-                    // band) renders in 0.228 instead of 0.252 ms, the whole frame in the same 0.888 ms (profiles/README.md r03)
-                    if (overlap && perCU > 4) perCU = 4;
-                }
-                // persistent grid: as many workgroups as the chip holds — but not more than the band has tasks for (one lane per task): a narrow
-                // multi-GPU band would otherwise park idle workgroups on the LDS / wave slots the next frame's Part 1 is waiting for
-                const uint32_t traceGrid = std::max(8u, std::min((uint32_t)(c->numCUs * perCU), grid.x));
-                hipLaunchKernelGGL(c->countRays ? k_di_part2_trace<true> : k_di_part2_trace<false>, dim3(traceGrid), block, ldsBytes, c->stream, c->dsc, fr, q);
-                launches = 3;
-            }
-            else hipLaunchKernelGGL(c->countRays ? k_di_part2<true> : k_di_part2<false>, grid, block, ldsBytes, c->stream, c->dsc, c->dcam, fr, st);
-            c->dprevFlip = !c->dprevFlip; c->histDI[0] = c->rowBegin; c->histDI[1] = c->rowEnd;
-            break;
-        }
+    fr.tileOrder = (uint32_t)c->tuning[K_TILE_ORDER]; fr.p1Mode = f.wavefront ? 1u : 0u;
+    f.grid = tile_grid(c, c->rowBegin, c->rowEnd); f.ev = c->ring[c->frameSerial % fyprt_context::kRing];
+    if (f.phase == 2) { f.ei = 2; return FYPRT_OK; }          // part 1 recorded its start and its end
+    std::memcpy(c->framePV, c->camPV, 64);     // the camera this frame is rendered with (fyprt_denoise_temporal)
+    if (c->countRays) HIPCHK(c, hipMemsetAsync(c->rayCounter.p, 0, 256, c->stream));
+    // frame 1 (or toAccumulate == false): the accumulator starts from zero (Renderer.cu:50-51) — on `stream`, which owns it (the whole buffer, as the
+    // reference does, not just this context's rows: a band moved later with fyprt_set_rows must not find the sums of an earlier accumulation in its new rows)
+    if (c->frameIndex == 1) HIPCHK(c, hipMemsetAsync(c->accum.p, 0, c->accum.bytes(), c->stream));
+    if (f.timed) HIPCHK(c, hipEventRecord(f.ev[f.ei++], f.fs));
+    return FYPRT_OK;
+}
+// One stage of the wavefront path engine (rt_paths.h) on the frame's scene, with the wf* buffers as ensure_paths left them
+static int run_frame_stage(FrameRun& f, const StageRun& r) {
+    fyprt_context* c = f.c;
+    const StageBufs wf{{c->wfRays[0].p, c->wfRays[1].p}, {c->wfHits[0].p, c->wfHits[1].p}, c->wfState.p, c->wfPixels.p, c->wfPixels2.p, frame_counters(c, 0)};
+    return run_stage(c, r, wf, f.sc, c->dcam, f.fr, f.st, f.ldsBytes, c->blockingCall, &f.stageLaunches);
+}
+// Techniques 0-6: the primary kernel, then per step one shade launch + one trace launch (run_stage) — or, small trees, the whole frame in one launch.
+static int enqueue_path_frame(FrameRun& f) {
+    fyprt_context* c = f.c; DevFrame& fr = f.fr; const int tech = f.tech;
+    const PathShape p = path_shape(tech, f.st);
+    dim3 pgrid = f.grid;
+    if (f.striped) {                                           // k_primary maps the local rows [0, n) onto this context's stripes
+        fr.stripeRows = c->stripeRows; fr.stripeParts = c->stripeParts; fr.stripePart = c->stripePart;
+        fr.rowBegin = 0; fr.rowEnd = stripe_row_count(c->H, c->stripeRows, c->stripeParts, c->stripePart);
+        pgrid = tile_grid(c, fr.rowBegin, fr.rowEnd);
     }
+    const size_t entries = (size_t)(fr.rowEnd - fr.rowBegin) * c->W;
+    TRY(ensure_paths(c, entries, p.raysPer, p.stride, 3 * p.L));
+    HIPCHK(c, hipMemsetAsync(c->wfCounters.p, 0, 3 * p.L * sizeof(uint32_t), c->stream));
+    f.launches = 1;                                            // (a frame reports its parts as launches, not its kernels)
+    // small trees, techniques 0-5: the whole frame in one launch, one thread per pixel (rt_paths.h: k_path_fused; key 17: 0 = by tree size, 1 = never, 2 = always)
+    const bool fused = tech != FYPRT_NEE && (c->tuning[K_FUSED_FRAME] == 2 || (c->tuning[K_FUSED_FRAME] == 0 && c->hostBvh.tris.size() < 65536u));
+    if (fused) {
+        PathIO io{};
+        io.fusedOwner = kNotFused; io.raysIn = c->wfRays[0].p; io.raysOut = c->wfRays[0].p; io.hitsIn = c->wfHits[0].p; io.state = c->wfState.p; io.stateStride = p.stride; io.raysPer = 1u;
+        static void (*const kFused[2][6])(DevScene, DevCamera, DevFrame, DevSettings, PathIO, uint32_t) = {{k_path_fused<T_BRUTE, false>, k_path_fused<T_UNIFORM, false>, k_path_fused<T_COSINE, false>, k_path_fused<T_GGX, false>, k_path_fused<T_BRDF, false>, k_path_fused<T_LIGHT, false>},
+                                                    {k_path_fused<T_BRUTE, true>, k_path_fused<T_UNIFORM, true>, k_path_fused<T_COSINE, true>, k_path_fused<T_GGX, true>, k_path_fused<T_BRDF, true>, k_path_fused<T_LIGHT, true>}};
+        hipLaunchKernelGGL(kFused[c->countRays ? 1 : 0][tech], pgrid, dim3(kBlock), f.ldsBytes, c->stream, f.sc, c->dcam, fr, f.st, io, p.steps);
+        return FYPRT_OK;
+    }
+    hipLaunchKernelGGL(c->countRays ? k_primary<true> : k_primary<false>, pgrid, dim3(kBlock), f.ldsBytes, c->stream, f.sc, c->dcam, fr, f.st, c->wfPixels.p, c->wfCounters.p);
+    return run_frame_stage(f, path_stage(tech, p, c->wfPixels.p, c->wfPixels2.p, c->wfCounters.p, entries));
+}
+// The rows Part 1 of a ReSTIR frame runs on, and its grid.  Halo rows: Part 1 recomputed on them (default), or — exchange mode — left to the band that
+// owns them and copied in between the parts.  The reference's spatial-neighbour coordinate is computed in unsigned arithmetic (R.cu:1916-1917): an offset
+// above the first row wraps and clamps to the LAST row.  A band that owns rows < radius therefore also needs Part 1 of row H-1 (one extra row of
+// recompute) to stay bit-identical to a single-GPU frame.  It rides in the same launch as one more row of tiles (a separate one-row launch is all
+// latency: ~0.09 ms on a 135-row band).
+struct Part1Rows { uint32_t begin, end, extraRow; size_t pixels; dim3 grid; };
+static Part1Rows part1_rows(const fyprt_context* c) {
+    const uint32_t halo = (c->haloExchange || c->tuning[K_SKIP_HALO_PART1]) ? 0u : c->halo;
+    const uint32_t b = (c->rowBegin > halo) ? c->rowBegin - halo : 0u, e = (c->rowEnd + halo < c->H) ? c->rowEnd + halo : c->H;
+    const bool extra = halo > 0 && c->rowBegin < halo && e < c->H;
+    return {b, e, extra ? c->H - 1u : 0xFFFFFFFFu, ((size_t)(e - b) + (extra ? 1u : 0u)) * c->W, tile_grid(c, b, extra ? e + 16u : e)};
+}
+// ReSTIR GI.  Part 1 = primary kernel + bounce-loop steps (they build the Part-2 list as paths complete); Part 2 = the neighbour loop over that
+// list (wfPixels2, cnt2[0] = its length): as stages (tuning key 19 = 0) or in one launch.
+static int enqueue_gi_frame(FrameRun& f) {
+    fyprt_context* c = f.c; const Part1Rows p1 = part1_rows(c);
+    const uint32_t steps1 = f.st.maxBounces, steps2 = f.st.useSpatial ? f.st.numNeighbors : 0u;
+    const size_t L1 = (size_t)steps1 + 2, L2 = (size_t)steps2 + 2;
+    TRY(ensure_paths(c, p1.pixels, 1, 5, 2 * L1 + 2 * L2));
+    uint32_t* cnt1 = c->wfCounters.p; uint32_t* cnt2 = cnt1 + 2 * L1;
+    if (f.phase != 2) {
+        TRY(sync_restir_normals(c, f.tech, c->stream));   // the last ReSTIR frame was a DI frame: its normals (in the history records) are this frame's "previous normals"
+        HIPCHK(c, hipMemsetAsync(cnt1, 0, (2 * L1 + 2 * L2) * sizeof(uint32_t), c->stream));
+        hipLaunchKernelGGL(c->countRays ? k_gi_primary<true> : k_gi_primary<false>, p1.grid, dim3(kBlock), f.ldsBytes, c->stream, f.sc, c->dcam, f.fr, f.st, p1.begin, p1.end, p1.extraRow, c->wfPixels.p, cnt1);
+        TRY(run_frame_stage(f, StageRun{T_GI1, steps1, 1u, 5u, c->wfPixels.p, cnt1, cnt1 + L1, c->wfPixels2.p, cnt2, 0, nullptr, p1.pixels}));
+        if (f.timed) HIPCHK(c, hipEventRecord(f.ev[f.ei++], c->stream));
+        if (f.phase == 1) { f.part1Only = true; return c->hip(hipGetLastError(), "ReSTIR GI part 1"); }
+    }
+    const DevScene tsc = secondary_scene(f.sc, (uint32_t)c->tuning[K_QUORUM_SECONDARY], frame_counters(c, 1));      // of the one-launch forms
+    if (c->tuning[K_GI2_MODE] == 2) {
+        // one PERSISTENT launch (rt_paths.h: k_gi2_persistent): a lane owns a pixel of the list, lanes without a ray in flight are serviced together
+        const int occ = c->gi2Occ.get(k_gi2_persistent<false>, f.ldsBytes, 3), perCU = c->tuning[K_WG_PER_CU] > 0 ? std::min(c->tuning[K_WG_PER_CU], occ) : occ;
+        GI2Queue gq{c->wfPixels2.p, cnt2, cnt2 + L2 + 1};
+        set_queue_params(c, gq, K_GI2_REFILL_LANES);
+        hipLaunchKernelGGL(c->countRays ? k_gi2_persistent<true> : k_gi2_persistent<false>, dim3((uint32_t)(c->numCUs * perCU)), dim3(kBlock), f.ldsBytes, c->stream, tsc, c->dcam, f.fr, f.st, gq);
+    } else if (c->tuning[K_GI2_MODE] == 1) {
+        // one launch (rt_paths.h: k_gi2_fused): one thread per listed pixel for the whole neighbour loop, visibility rays traced in place
+        const uint32_t fg = (uint32_t)std::max<size_t>(1, std::min<size_t>((size_t)c->numCUs * 64u, (p1.pixels + kBlock - 1) / kBlock));
+        hipLaunchKernelGGL(c->countRays ? k_gi2_fused<true> : k_gi2_fused<false>, dim3(fg), dim3(kBlock), f.ldsBytes, c->stream, tsc, c->dcam, f.fr, f.st, (const uint32_t*)c->wfPixels2.p, (const uint32_t*)cnt2);
+    } else TRY(run_frame_stage(f, StageRun{T_GI2, steps2, 1u, 5u, c->wfPixels2.p, cnt2, cnt2 + L2, nullptr, nullptr, 1, nullptr, p1.pixels}));
+    f.launches = 2; c->normalFlip = !c->normalFlip; c->histGI[0] = c->rowBegin; c->histGI[1] = c->rowEnd;
+    return FYPRT_OK;
+}
+// ReSTIR DI Part 2 as a wavefront: the setup kernel queues the frame's shadow rays as tasks (optionally sorted by light), one persistent
+// kernel traces them.  Setup and sort go where Part 1 went (f.fs), the trace kernel on the context stream.
+static int enqueue_di_wavefront_part2(FrameRun& f) {
+    fyprt_context* c = f.c; const int par = f.par; const dim3 grid = f.grid; hipStream_t fs = f.fs;
+    const dim3 block(kBlock);
+    ShadowQueue q{};
+    q.tasks = c->shadowTasks.p + (size_t)par * c->queueStride; q.counters = c->queueCounters.p + 4 * par;
+    set_queue_params(c, q, K_REFILL_LANES);
+    const size_t sg = (size_t)par * c->sortGroups;
+    q.sortMode = c->tuning[K_SORT_TASKS] ? 1u : 0u; q.numGroups = grid.x; q.counts = c->sortCounts.p + sg; q.keys = c->sortKeys.p + sg * 256u; q.hist = c->sortHist.p + sg * kSortBins;
+    q.binOffset = c->sortOffset.p + sg * kSortBins; q.binTotal = c->sortTotal.p + (size_t)par * kSortBins; q.sorted = c->sortIndex.p + sg * 256u;
+    HIPCHK(c, hipMemsetAsync(q.counters, 0, 16, fs));
+    static void (*const kSetup[3])(DevScene, DevCamera, DevFrame, DevSettings, ShadowQueue) = {k_di_part2_setup<0>, k_di_part2_setup<1>, k_di_part2_setup<2>};
+    hipLaunchKernelGGL(kSetup[c->tuning[K_SETUP_FETCH]], grid, block, 0, fs, f.sc, c->dcam, f.fr, f.st, q);
+    if (q.sortMode) {
+        hipLaunchKernelGGL(k_di_sort_scan, dim3(kSortBins), block, 0, fs, q);
+        hipLaunchKernelGGL(k_di_sort_scatter, grid, block, 0, fs, q);
+    }
+    if (f.timed) HIPCHK(c, hipEventRecord(f.ev[f.ei++], fs));
+    if (f.overlap) {                                   // the trace kernel waits for this frame's front part only
+        HIPCHK(c, hipEventRecord(c->evFront[par], c->front));
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->evFront[par], 0));
+        if (f.timed) HIPCHK(c, hipEventRecord(f.ev[4], c->stream));      // start of the trace kernel on its own stream
+    }
+    f.sc.rayCounter = frame_counters(c, 2);
+    int perCU = c->tuning[K_WG_PER_CU];
+    if (perCU <= 0) {          // as many workgroups as registers + LDS let a CU hold (asked from the runtime once per stack size)
+        perCU = c->traceOcc.get(k_di_part2_trace<false>, f.ldsBytes, 4);
+        // pipelined frames: the persistent grid shares the chip with Part 1 + setup of the NEXT frame; with every slot a CU has (6 workgroups) those start late and run in
+        // extra rounds — 4 per CU leave them room: an eighth of the frame (a multi-GPU band) renders in 0.228 instead of 0.252 ms, the whole frame in the same 0.888 ms (profiles/README.md r03)
+        if (f.overlap && perCU > 4) perCU = 4;
+    }
+    // persistent grid: as many workgroups as the chip holds — but not more than the band has tasks for (one lane per task): a narrow
+    // multi-GPU band would otherwise park idle workgroups on the LDS / wave slots the next frame's Part 1 is waiting for
+    const uint32_t traceGrid = std::max(8u, std::min((uint32_t)(c->numCUs * perCU), grid.x));
+    hipLaunchKernelGGL(c->countRays ? k_di_part2_trace<true> : k_di_part2_trace<false>, dim3(traceGrid), block, f.ldsBytes, c->stream, f.sc, f.fr, q);
+    f.launches = 3;
+    return FYPRT_OK;
+}
+// ReSTIR DI.  Part 1: candidates + temporal reuse per pixel; Part 2: spatial reuse + shadow rays, as a wavefront (tuning key 1) or per pixel.
+static int enqueue_di_frame(FrameRun& f) {
+    fyprt_context* c = f.c;
+    if (f.phase != 2) {
+        const Part1Rows p1 = part1_rows(c);
+        TRY(sync_restir_normals(c, f.tech, f.fs));   // the last ReSTIR frame was a GI frame: its normals are this frame's "previous normals"
+        hipLaunchKernelGGL(c->countRays ? k_di_part1<true> : k_di_part1<false>, p1.grid, dim3(kBlock), f.ldsBytes, f.fs, f.sc, c->dcam, f.fr, f.st, p1.begin, p1.end, p1.extraRow);
+        if (f.timed) HIPCHK(c, hipEventRecord(f.ev[f.ei++], f.fs));
+        if (f.phase == 1) { f.part1Only = true; return c->hip(hipGetLastError(), "ReSTIR DI part 1"); }
+    }
+    // shadow-ray kernels of Part 2: the secondary quorum (measured 0.85 -> 0.68 ms), counters of their own
+    f.sc = secondary_scene(f.sc, (uint32_t)c->tuning[K_QUORUM_SECONDARY], frame_counters(c, 1)); f.launches = 2;
+    if (f.wavefront) TRY(enqueue_di_wavefront_part2(f));
+    else hipLaunchKernelGGL(c->countRays ? k_di_part2<true> : k_di_part2<false>, f.grid, dim3(kBlock), f.ldsBytes, c->stream, f.sc, c->dcam, f.fr, f.st);
+    c->dprevFlip = !c->dprevFlip; c->histDI[0] = c->rowBegin; c->histDI[1] = c->rowEnd;
+    return FYPRT_OK;
+}
+// The frame is enqueued to its end: its last timing event, evDone, the ring's and the context's bookkeeping.
+static int end_frame(FrameRun& f) {
+    fyprt_context* c = f.c; const unsigned long long slot = c->frameSerial % fyprt_context::kRing;
     HIPCHK(c, hipGetLastError());
     c->part1Pending = false;
-    if (timed) HIPCHK(c, hipEventRecord(c->ev[ei++], c->stream));
-    HIPCHK(c, hipEventRecord(c->evDone[par], c->stream));                // the frame is complete (and its task queue free again)
-    c->lastOverlapped = overlap;
-    c->lastLaunches = launches; c->lastTech = tech;
-    if (tech == FYPRT_RESTIR_DI || tech == FYPRT_RESTIR_GI) c->lastRestir = tech;
-    c->ringLaunches[c->frameSerial % fyprt_context::kRing] = timed ? launches : 0;
-    c->ringSplit[c->frameSerial % fyprt_context::kRing] = overlap;
-    c->frameSerial++;
-    c->frameComplete = true; c->lastFrameIndex = c->frameIndex;
-    if (s->to_accumulate) c->frameIndex++; else c->frameIndex = 1;       // Renderer.cu:258-261
+    if (f.timed) HIPCHK(c, hipEventRecord(f.ev[f.ei++], c->stream));
+    HIPCHK(c, hipEventRecord(c->evDone[f.par], c->stream));                // the frame is complete (and its task queue free again)
+    c->lastOverlapped = f.overlap; c->lastLaunches = f.launches; c->lastTech = f.tech;
+    if (f.tech == FYPRT_RESTIR_DI || f.tech == FYPRT_RESTIR_GI) c->lastRestir = f.tech;
+    c->ringLaunches[slot] = f.timed ? f.launches : 0; c->ringSplit[slot] = f.overlap;
+    c->frameSerial++; c->frameComplete = true; c->lastFrameIndex = c->frameIndex;
+    if (f.s->to_accumulate) c->frameIndex++; else c->frameIndex = 1;       // Renderer.cu:258-261
     return FYPRT_OK;
+}
+// phase: 0 = the whole frame; 1 = ReSTIR Part 1 only (nothing of the frame's bookkeeping advances); 2 = the rest of the frame that a
+// phase-1 call started.  The split exists for the halo EXCHANGE of a multi-GPU frame (fyprt_multi.h): Part 1 on every band, the
+// bands' Part-1 records of each other's halo rows copied across, Part 2 on every band.
+static int enqueue_frame(fyprt_context* c, const fyprt_settings* s, bool timed, int phase = 0) {
+    FrameRun f{}; f.c = c; f.s = s; f.tech = s->technique; f.phase = phase; f.timed = timed;
+    int rc = check_frame(c, s, phase);
+    if (rc == FYPRT_OK) rc = begin_frame(f);
+    if (rc == FYPRT_OK) rc = f.tech == FYPRT_RESTIR_DI ? enqueue_di_frame(f) : f.tech == FYPRT_RESTIR_GI ? enqueue_gi_frame(f) : enqueue_path_frame(f);
+    if (rc == FYPRT_OK) { if (f.part1Only) c->part1Pending = true; else rc = end_frame(f); }
+    if (rc != FYPRT_OK && rc != FYPRT_ESTATE) c->part1Pending = false;      // a frame that failed half-way is abandoned, not left pending
+    return rc;
+}
+// Time of part `k` of the frame in ring slot `slot`, between its timing events; the trace kernel of a split (pipelined) frame has its own start event
+static hipError_t part_elapsed(fyprt_context* c, unsigned long long slot, int k, float* ms) {
+    return hipEventElapsedTime(ms, c->ring[slot][(c->ringSplit[slot] && k == 2) ? 4 : k], c->ring[slot][k + 1]);
 }
 
 int fyprt_render(fyprt_context* c, const fyprt_settings* s, fyprt_frame_stats* stats) {
@@ -1350,9 +1365,8 @@ int fyprt_render(fyprt_context* c, const fyprt_settings* s, fyprt_frame_stats* s
         std::memset(stats, 0, sizeof *stats);
         stats->launches = (uint32_t)c->lastLaunches;
         float total = 0.0f;
-        const bool split = c->ringSplit[(c->frameSerial - 1ull) % fyprt_context::kRing];
         for (int k = 0; k < c->lastLaunches; ++k) {
-            float ms = 0.0f; (void)hipEventElapsedTime(&ms, (split && k == 2) ? c->ev[4] : c->ev[k], c->ev[k + 1]);   // split frame: the trace kernel has its own start event
+            float ms = 0.0f; (void)part_elapsed(c, (c->frameSerial - 1ull) % fyprt_context::kRing, k, &ms);
             stats->kernel_ms_part[k] = ms; total += ms;
         }
         stats->kernel_ms = total;
@@ -1374,7 +1388,7 @@ int fyprt_frame_timings(fyprt_context* c, uint32_t frames_back, float* kernel_ms
     for (int k = 0; k < 4; ++k) kernel_ms_part4[k] = 0.0f;
     for (int k = 0; k < n && k < 4; ++k) {
         float ms = 0.0f;
-        hipError_t e = hipEventElapsedTime(&ms, (c->ringSplit[slot] && k == 2) ? c->ring[slot][4] : c->ring[slot][k], c->ring[slot][k + 1]);
+        const hipError_t e = part_elapsed(c, slot, k, &ms);
         if (e != hipSuccess) return c->hip(e, "hipEventElapsedTime (synchronize the context first)");
         kernel_ms_part4[k] = ms;
     }
@@ -1535,7 +1549,7 @@ int fyprt_export_lighttrees(fyprt_context* c, fyprt_lighttree_node* tlas, uint32
 
 int fyprt_get_tuning(fyprt_context* c, int key, int* value) {
     if (!c || !value || key < 0 || key >= K_COUNT) return FYPRT_EINVAL;
-    *value = (key == K_STACK_BUDGET) ? effective_stack_budget(c) : (key == K_WG_PER_CU && c->tuning[K_WG_PER_CU] <= 0) ? c->traceOcc.blocks : c->tuning[key];   // key 2: residency found at the last DI frame
+    *value = (key == K_STACK_BUDGET) ? stack_lds(c, 0u).budget : (key == K_WG_PER_CU && c->tuning[K_WG_PER_CU] <= 0) ? c->traceOcc.blocks : c->tuning[key];   // key 2: residency found at the last DI frame
     return FYPRT_OK;
 }
 
@@ -1575,20 +1589,17 @@ static int enqueue_query(fyprt_context* c, int query, const float4* rays, uint32
     const bool occluded = query == FYPRT_QUERY_OCCLUDED;
     if (!c->queryCounters.p) { HIPCHK(c, c->queryCounters.alloc(8)); }
     HIPCHK(c, hipMemsetAsync(c->queryCounters.p, 0, 64, c->stream));
-    DevScene qs = c->dsc;                                         // a copy: the frame's descriptor stays as the last frame left it
-    const int budget = effective_stack_budget(c);
-    qs.stackBudget = budget;
-    qs.nodeQuorum = (uint32_t)c->tuning[K_QUORUM_SECONDARY];                       // the path engine's ray kernels' quorum (incoherent rays in general)
-    qs.rayCounter = c->countRays ? c->queryCounters.p : nullptr;
-    qs.topCount = 0u;                                             // the query kernels stage no top nodes (not even in a -DRT_TOPCACHE build)
-    const size_t ldsBytes = (size_t)(budget + 1) * kBlock * sizeof(int32_t);      // the traversal stack of the path engine's ray kernels
+    const StackLds stack = stack_lds(c, 0u);                      // the query kernels stage no top nodes (not even in a -DRT_TOPCACHE build)
+    // the path engine's ray kernels' quorum (incoherent rays in general), the query's own counters
+    DevScene qs = secondary_scene(c->dsc, (uint32_t)c->tuning[K_QUORUM_SECONDARY], c->countRays ? c->queryCounters.p : nullptr);
+    qs.stackBudget = stack.budget;
+    const size_t ldsBytes = stack.bytes;
     QueryRays q{};
     q.rays = rays; q.results = results; q.count = count; q.head = reinterpret_cast<uint32_t*>(c->queryCounters.p + 5);
     set_queue_params(c, q, K_REFILL_LANES);
     const dim3 block(kBlock);
     const uint32_t blocksForRays = (uint32_t)(((size_t)count + kBlock - 1) / kBlock);
-    // tuning key 15 as in the path engine: one thread per ray below 65 536 triangles, persistent waves above
-    const bool simple = c->tuning[K_RAY_KERNEL] == 2 || (c->tuning[K_RAY_KERNEL] == 0 && c->hostBvh.tris.size() < 65536u);
+    const bool simple = simple_ray_kernel(c);                     // tuning key 15 as in the path engine
     dim3 grid;
     if (simple) grid = dim3(std::max(1u, std::min<uint32_t>((uint32_t)c->numCUs * 16u, blocksForRays)));
     else {
@@ -1597,13 +1608,9 @@ static int enqueue_query(fyprt_context* c, int query, const float4* rays, uint32
     }
     if (timed) HIPCHK(c, hipEventRecord(c->queryEv[0], c->stream));
     const int k = (occluded ? 2 : 0) + (c->countRays ? 1 : 0);
-    if (simple) {
-        static void (*const kSimple[4])(DevScene, QueryRays) = {k_query_rays_simple<false, false>, k_query_rays_simple<false, true>, k_query_rays_simple<true, false>, k_query_rays_simple<true, true>};
-        hipLaunchKernelGGL(kSimple[k], grid, block, ldsBytes, c->stream, qs, q);
-    } else {
-        static void (*const kPersistent[4])(DevScene, QueryRays) = {k_query_rays<false, false>, k_query_rays<false, true>, k_query_rays<true, false>, k_query_rays<true, true>};
-        hipLaunchKernelGGL(kPersistent[k], grid, block, ldsBytes, c->stream, qs, q);
-    }
+    static void (*const kQuery[2][4])(DevScene, QueryRays) = {{k_query_rays<false, false>, k_query_rays<false, true>, k_query_rays<true, false>, k_query_rays<true, true>},
+        {k_query_rays_simple<false, false>, k_query_rays_simple<false, true>, k_query_rays_simple<true, false>, k_query_rays_simple<true, true>}};
+    hipLaunchKernelGGL(kQuery[simple ? 1 : 0][k], grid, block, ldsBytes, c->stream, qs, q);
     HIPCHK(c, hipGetLastError());
     if (timed) HIPCHK(c, hipEventRecord(c->queryEv[1], c->stream));
     return FYPRT_OK;
@@ -1667,15 +1674,8 @@ static int check_render_rays(fyprt_context* c, const fyprt_settings* s, uint32_t
 static int enqueue_render_rays(fyprt_context* c, const fyprt_settings* s, uint32_t frameIndex, const float4* rays, const uint32_t* indices, uint32_t firstIndex,
                                uint32_t count, float4* radiance, void* payloads, hipMemcpyKind payloadKind, bool blocking, int* launched) {
     const int tech = s->technique;
-    DevSettings st{};                                            // what techniques 0-6 read, with the frame's casts (enqueue_frame_impl)
-    st.sky = f3{s->sky_color[0], s->sky_color[1], s->sky_color[2]};
-    st.maxBounces = (uint8_t)s->light_bounces; st.sampleCount = (uint8_t)s->sample_count;
-    st.skipDeadRays = c->tuning[K_SKIP_DEAD_RAYS] ? 1u : 0u;
-    const uint32_t nSamples = (tech == FYPRT_BRUTE_FORCE) ? 1u : st.sampleCount;
-    const uint32_t steps = (tech == FYPRT_LIGHT_SOURCE_SAMPLING) ? nSamples : nSamples * st.maxBounces;
-    const uint32_t raysPer = (tech == FYPRT_NEE && st.maxBounces != 1u) ? 2u : 1u;
-    const uint32_t stride = (tech == FYPRT_NEE) ? 6u : 2u;
-    const size_t L = (size_t)steps + 2;
+    const DevSettings st = dev_settings(c, s);                   // as a frame's (techniques 0-6 read sky, bounces, samples and skipDeadRays only)
+    const PathShape p = path_shape(tech, st);
     // buffers for the largest chunk so far, every technique (2 rays per entry, 6 quads of state); grown after the work that uses them
     if (c->rrPayload.n < count) {
         if (c->rrPayload.p) HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1683,18 +1683,16 @@ static int enqueue_render_rays(fyprt_context* c, const fyprt_settings* s, uint32
         for (int k = 0; k < 2; ++k) { HIPCHK(c, c->rrRays[k].alloc((size_t)count * 2 * 3)); HIPCHK(c, c->rrHits[k].alloc((size_t)count * 2)); }
         HIPCHK(c, c->rrState.alloc((size_t)count * 6)); HIPCHK(c, c->rrPixels.alloc(count)); HIPCHK(c, c->rrPixels2.alloc(count));
     }
-    if (c->rrCounters.n < 3 * L) {
+    if (c->rrCounters.n < 3 * p.L) {
         if (c->rrCounters.p) HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, c->rrCounters.alloc(3 * L));
+        HIPCHK(c, c->rrCounters.alloc(3 * p.L));
     }
-    HIPCHK(c, hipMemsetAsync(c->rrCounters.p, 0, 3 * L * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->rrCounters.p, 0, 3 * p.L * sizeof(uint32_t), c->stream));
     // primary segments: the closest-hit query (its own counters and queue head; ray counts of the whole call land there too)
     TRY(enqueue_query(c, FYPRT_QUERY_CLOSEST, rays, count, c->rrPayload.p, false));
     ++*launched;
-    DevScene qs = c->dsc;                                        // as enqueue_query: the frame's descriptor is not touched
-    const int budget = effective_stack_budget(c);
-    qs.stackBudget = budget; qs.topCount = 0u; qs.rayCounter = nullptr;
-    const size_t ldsBytes = (size_t)(budget + 1) * kBlock * sizeof(int32_t);
+    const StackLds stack = stack_lds(c, 0u);
+    DevScene qs = c->dsc; qs.stackBudget = stack.budget;        // (run_stage sets quorum and counters of its trace launches)
     DevFrame fr{};                                               // the step functions read the primary records and the frame index only
     fr.payload = c->rrPayload.p; fr.frameIndex = frameIndex; fr.W = 1u; fr.H = 1u;
     RaySource rs{rays, indices, firstIndex, radiance};
@@ -1704,9 +1702,7 @@ static int enqueue_render_rays(fyprt_context* c, const fyprt_settings* s, uint32
     HIPCHK(c, hipGetLastError());
     const StageBufs b{{c->rrRays[0].p, c->rrRays[1].p}, {c->rrHits[0].p, c->rrHits[1].p}, c->rrState.p, c->rrPixels.p, c->rrPixels2.p,
                       c->countRays ? c->queryCounters.p : nullptr};
-    const StageRun r{tech, steps, raysPer, stride, c->rrPixels.p, c->rrCounters.p, c->rrCounters.p + L, (tech == FYPRT_NEE) ? c->rrPixels2.p : nullptr, nullptr, 0,
-                     (tech == FYPRT_NEE) ? c->rrCounters.p + 2 * L : nullptr, count};
-    TRY(run_stage(c, r, b, qs, rs, fr, st, ldsBytes, blocking, launched));
+    TRY(run_stage(c, path_stage(tech, p, c->rrPixels.p, c->rrPixels2.p, c->rrCounters.p, count), b, qs, rs, fr, st, stack.bytes, blocking, launched));
     if (payloads) HIPCHK(c, hipMemcpyAsync(payloads, c->rrPayload.p, (size_t)count * sizeof(Payload), payloadKind, c->stream));
     return FYPRT_OK;
 }

@@ -227,7 +227,7 @@ int fyprt_group_set_rows(fyprt_group* g, const uint32_t* row_bounds) {
     const uint32_t W = g->ctx[0]->W;
     if (row_bounds[0] != 0 || row_bounds[n] != g->ctx[0]->H) return g->ctx[0]->fail(FYPRT_EINVAL, "fyprt_group_set_rows: the bands must partition rows 0..height");
     for (int i = 0; i < n; ++i) if (row_bounds[i] >= row_bounds[i + 1]) return g->ctx[i]->fail(FYPRT_EINVAL, "fyprt_group_set_rows: empty or unordered band");
-    { const int rc = fyprt_group_synchronize(g); if (rc != FYPRT_OK) return rc; }
+    TRY(fyprt_group_synchronize(g));
     for (int k = 0; k < n; ++k) {
         fyprt_context* c = g->ctx[k];
         HIPCHK(c, hipSetDevice(c->device));
@@ -244,7 +244,7 @@ int fyprt_group_set_rows(fyprt_group* g, const uint32_t* row_bounds) {
             HIPCHK(c, move(c->normalFlip ? c->normalB.p : c->normalA.p, o->normalFlip ? o->normalB.p : o->normalA.p, sizeof(f2)));
         }
     }
-    { const int rc = fyprt_group_synchronize(g); if (rc != FYPRT_OK) return rc; }
+    TRY(fyprt_group_synchronize(g));
     g->bounds.assign(row_bounds, row_bounds + n + 1);
     for (int k = 0; k < n; ++k) {
         fyprt_context* c = g->ctx[k];
@@ -276,7 +276,7 @@ int fyprt_group_render(fyprt_group* g, const fyprt_settings* s) {
     for (int i = 0; i < n; ++i) {
         fyprt_context* c = g->ctx[i];
         c->rowBegin = g->bounds[i]; c->rowEnd = g->bounds[i + 1]; c->halo = halo; c->rowsSet = true; c->haloExchange = exchange;
-        if (striped) { const int rc = fyprt_set_row_stripes(c, g->stripeRows, (uint32_t)n, (uint32_t)i); if (rc != FYPRT_OK) return rc; }
+        if (striped) TRY(fyprt_set_row_stripes(c, g->stripeRows, (uint32_t)n, (uint32_t)i));
         else c->stripeRows = 0;
         // the previous frame's gather still reads this band's image rows on the root's stream: the new frame's epilogues wait for it
         if (g->gatherPending) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, hipStreamWaitEvent(c->stream, g->evGather, 0)); }
@@ -285,8 +285,7 @@ int fyprt_group_render(fyprt_group* g, const fyprt_settings* s) {
     if (!exchange) {
         for (int i = 0; i < n; ++i) {
             fyprt_context* c = g->ctx[i];
-            const int rc = enqueue_frame(c, s, true);
-            if (rc != FYPRT_OK) return rc;
+            TRY(enqueue_frame(c, s, true));
             HIPCHK(c, hipEventRecord(g->ev[i].frame, c->stream));
         }
         return FYPRT_OK;
@@ -323,8 +322,7 @@ int fyprt_group_render(fyprt_group* g, const fyprt_settings* s) {
         for (int j = 0; j < n; ++j) if (j != i) HIPCHK(c, hipStreamWaitEvent(c->stream, g->ev[j].pulled, 0));    // last frame's pulls FROM this band are done
         if (s->use_temporal_reuse) TRY(pull(i, hplan, 1, &fyprt_group::BandEvents::frame));
         extend_history_rows(c, s->technique, hhalo);
-        const int rc = enqueue_frame(c, s, true, 1);
-        if (rc != FYPRT_OK) return rc;
+        TRY(enqueue_frame(c, s, true, 1));
         HIPCHK(c, hipEventRecord(g->ev[i].p1, c->stream));
     }
     // 2. the neighbours' Part-1 records of the halo rows, then Part 2
@@ -336,8 +334,7 @@ int fyprt_group_render(fyprt_group* g, const fyprt_settings* s) {
     for (int i = 0; i < n; ++i) {
         fyprt_context* c = g->ctx[i];
         HIPCHK(c, hipSetDevice(c->device));
-        const int rc = enqueue_frame(c, s, true, 2);
-        if (rc != FYPRT_OK) return rc;
+        TRY(enqueue_frame(c, s, true, 2));
         HIPCHK(c, hipEventRecord(g->ev[i].frame, c->stream));
     }
     return FYPRT_OK;
@@ -586,8 +583,7 @@ int fyprt_last_frame_ms(fyprt_context* c, float* ms) {
     if (!c || !ms) return FYPRT_EINVAL;
     float part[4]; uint32_t n = 0;
     HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c));
-    const int rc = fyprt_frame_timings(c, 0, part, &n);
-    if (rc != FYPRT_OK) return rc;
+    TRY(fyprt_frame_timings(c, 0, part, &n));
     *ms = part[0] + part[1] + part[2] + part[3];
     return FYPRT_OK;
 }
@@ -630,7 +626,7 @@ int fyprt_comm_set_rows(fyprt_context* c, const uint32_t* row_bounds) {
     base.push_back(c->dprevFlip ? (void*)c->dprevB.p : (void*)c->dprevA.p); bpp.push_back(sizeof(DIRec));
     base.push_back(c->giPrev.p); bpp.push_back(sizeof(GIRes));
     base.push_back(c->normalFlip ? (void*)c->normalB.p : (void*)c->normalA.p); bpp.push_back(sizeof(f2));
-    { const int rc = comm_issue(c, comm_set_rows_ops(c->rank, c->bounds, std::vector<uint32_t>(row_bounds, row_bounds + c->world + 1), bpp, c->W), base); if (rc != FYPRT_OK) return rc; }
+    TRY(comm_issue(c, comm_set_rows_ops(c->rank, c->bounds, std::vector<uint32_t>(row_bounds, row_bounds + c->world + 1), bpp, c->W), base));
     HIPCHK(c, sync_all(c));
     c->bounds.assign(row_bounds, row_bounds + c->world + 1);
     c->rowBegin = c->bounds[c->rank]; c->rowEnd = c->bounds[c->rank + 1];
@@ -661,15 +657,15 @@ int fyprt_comm_render(fyprt_context* c, const fyprt_settings* s) {
     const bool exchange = c->commHaloMode == 1 && (halo > 0 || hhalo > 0);
     c->rowBegin = c->bounds[c->rank]; c->rowEnd = c->bounds[c->rank + 1]; c->halo = halo; c->rowsSet = true; c->haloExchange = exchange;
     c->commLastStriped = c->commStripeRows != 0 && c->world > 1 && !is_restir(s); c->commLastStripeRows = c->commStripeRows;
-    if (c->commLastStriped) { const int rc = fyprt_set_row_stripes(c, c->commStripeRows, (uint32_t)c->world, (uint32_t)c->rank); if (rc != FYPRT_OK) return rc; }
+    if (c->commLastStriped) TRY(fyprt_set_row_stripes(c, c->commStripeRows, (uint32_t)c->world, (uint32_t)c->rank));
     else c->stripeRows = 0;
     if (!exchange) return enqueue_frame(c, s, true);
     HIPCHK(c, hipSetDevice(c->device));
-    { const int rc = sync_restir_normals(c, s->technique, c->stream); if (rc != FYPRT_OK) return rc; }      // before the history travels
-    if (s->use_temporal_reuse) { const int rc = comm_exchange(c, s->technique, halo_plan(c->bounds, hhalo, c->H, false), 1); if (rc != FYPRT_OK) return rc; }
+    TRY(sync_restir_normals(c, s->technique, c->stream));      // before the history travels
+    if (s->use_temporal_reuse) TRY(comm_exchange(c, s->technique, halo_plan(c->bounds, hhalo, c->H, false), 1));
     extend_history_rows(c, s->technique, hhalo);
-    { const int rc = enqueue_frame(c, s, true, 1); if (rc != FYPRT_OK) return rc; }
-    { const int rc = comm_exchange(c, s->technique, halo_plan(c->bounds, halo, c->H, true), 0); if (rc != FYPRT_OK) return rc; }
+    TRY(enqueue_frame(c, s, true, 1));
+    TRY(comm_exchange(c, s->technique, halo_plan(c->bounds, halo, c->H, true), 0));
     return enqueue_frame(c, s, true, 2);
 }
 // The image gather of the north-star design: every band's RGBA8 rows, in place in the full-size image (the context's own or the

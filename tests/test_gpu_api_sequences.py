@@ -266,3 +266,61 @@ def test_band_moved_between_accumulated_frames(oracle_built):
         m.frame(_settings(capi.BRDF_SAMPLING, rand_seed=4), asynchronous=False)
     finally:
         m.close()
+
+
+def _refused(code, call, *args):
+    """`call(*args)` must raise capi.FyprtError carrying `code` in its "fyprt error <code>" text"""
+    import re
+    with pytest.raises(capi.FyprtError) as e:
+        call(*args)
+    got = int(re.search(r"fyprt error (-?\d+)", str(e.value)).group(1))
+    assert got == code, f"{call.__name__}{args[1:]}: fyprt error {got}, expected {code}: {e.value}"
+
+
+@pytest.mark.parametrize("tech", [capi.RESTIR_DI, capi.RESTIR_GI], ids=["restir_di", "restir_gi"])
+def test_a_refused_frame_leaves_no_trace(tech):
+    """The refusals of the two-part frame state machine (part 2 without part 1, two parts of a one-part technique, ReSTIR on a striped
+    context, a frame or another part 1 while a part 1 is pending) change nothing: six frames with the refused calls in between are byte
+    for byte the six frames without them, and the last frame (a two-part one) reports the same launch count.  48 x 40: partial tiles in
+    both directions."""
+    from common import settings_for
+    EINVAL, ESTATE = -1, -3
+    W, H = 48, 40
+    mk_scene, mk_cam = SCENES["cornell"]
+    sc, cam = mk_scene(), mk_cam(W, H)
+    bufs = [capi.BUF_DEPTH] + ([capi.BUF_DI, capi.BUF_DI_PREV] if tech == capi.RESTIR_DI else [capi.BUF_GI, capi.BUF_GI_PREV])
+
+    def run(refusals):
+        ctx = capi.Context(0)
+        try:
+            ctx.resize(W, H); ctx.upload_scene(sc); ctx.set_camera(cam)
+            for f in range(6):
+                st = settings_for(tech, rand_seed=f + 1)
+                if refusals and f == 0:
+                    _refused(ESTATE, ctx.render_part, st, 2)
+                    _refused(EINVAL, ctx.render_part, settings_for(capi.COSINE_WEIGHTED_SAMPLING), 1)
+                if refusals and f == 1:
+                    ctx.set_row_stripes(16, 2, 1)
+                    _refused(ESTATE, ctx.render, st)
+                    ctx.set_row_stripes(0)
+                if f < 3:
+                    ctx.render(st)
+                else:
+                    ctx.render_part(st, 1)
+                    if refusals and f == 4:
+                        _refused(ESTATE, ctx.render, st)
+                        _refused(ESTATE, ctx.render_part, st, 1)
+                    ctx.render_part(st, 2)
+            ctx.synchronize()
+            img, acc = ctx.readback()
+            return img, acc, [ctx.read_buffer(b) for b in bufs], ctx.frame_timings(0)[1]
+        finally:
+            ctx.close()
+
+    img_a, acc_a, bufs_a, launches_a = run(False)
+    img_b, acc_b, bufs_b, launches_b = run(True)
+    assert np.array_equal(img_a, img_b)
+    assert np.array_equal(acc_a, acc_b, equal_nan=True)
+    for which, a, b in zip(bufs, bufs_a, bufs_b):
+        assert a.tobytes() == b.tobytes(), f"buffer {which} differs"
+    assert launches_a == launches_b
