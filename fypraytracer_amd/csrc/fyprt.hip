@@ -27,6 +27,11 @@ using namespace rt;
 #ifndef RT_DN_LDS_MAX_STEP
 #define RT_DN_LDS_MAX_STEP 32
 #endif
+// Priority levels of the context's three streams (fyprt_create), likewise a build-time constant for a variant library: 0 = primary-ray stream
+// lowest, context stream default, front stream highest; 1 = lowest / front default / context highest; 2 = front lowest, context default, primary highest.
+#ifndef FYPRT_PRIORITY_ORDER
+#define FYPRT_PRIORITY_ORDER 0
+#endif
 
 namespace {
 
@@ -83,11 +88,11 @@ struct OccCache {
 enum TuningKey {
     K_TILE_ORDER = 0, K_DI_WAVEFRONT = 1, K_WG_PER_CU = 2, K_SORT_TASKS = 3, K_CHUNK = 4, K_REFILL_LANES = 5, K_QUORUM_SECONDARY = 6, K_QUORUM_PRIMARY = 7,
     K_STACK_BUDGET = 8, K_STATIC_CHUNKS = 9, K_MIN_CHUNK = 10, K_PIPELINE = 11, K_BUILDER = 12, K_SKIP_HALO_PART1 = 13, K_SETUP_FETCH = 14, K_RAY_KERNEL = 15,
-    K_TOP_NODES = 16, K_FUSED_FRAME = 17, K_SKIP_DEAD_RAYS = 18, K_GI2_MODE = 19, K_GI2_REFILL_LANES = 20, /* 21..23 reserved */ K_COUNT = 24
+    K_TOP_NODES = 16, K_FUSED_FRAME = 17, K_SKIP_DEAD_RAYS = 18, K_GI2_MODE = 19, K_GI2_REFILL_LANES = 20, K_DI_SPLIT = 21, /* 22..23 reserved */ K_COUNT = 24
 };
 constexpr struct { int def, max; } kTuning[K_COUNT] = {
     {2, 2}, {1, 1}, {0, 16}, {0, 1}, {128, 65536}, {24, 64}, {24, 64}, {32, 64}, {0, 31}, {0, 4096}, {32, 65536}, {1, 1},
-    {0, 2}, {0, 1}, {0, 2}, {0, 2}, {0, 1024}, {0, 2}, {1, 1}, {2, 2}, {48, 64}, {0, 0}, {0, 0}, {0, 0}};
+    {0, 2}, {0, 1}, {0, 2}, {0, 2}, {0, 1024}, {0, 2}, {1, 1}, {2, 2}, {48, 64}, {1, 1}, {0, 0}, {0, 0}};
 
 // host mat4 product, same operation order as the device / glm (column j = ((a0*bj.x + a1*bj.y) + a2*bj.z) + a3*bj.w)
 void matmul_cm(const float* a, const float* b, float* out) {
@@ -108,15 +113,20 @@ struct fyprt_context {
     // multi-process multi-GPU (fyprt_comm_*, fyprt_multi.h): RCCL communicator of the ranks that share the frame, every rank's band
     void* comm = nullptr; int world = 1, rank = 0; std::vector<uint32_t> bounds; int commHaloMode = 0;
     int device = 0; std::string err; bool hostOnly = false;
-    // Destruction order: members go in reverse order of declaration, so the two streams are declared before every buffer and event —
+    // Destruction order: members go in reverse order of declaration, so the three streams are declared before every buffer and event —
     // they are destroyed last, after what was used on them.  fyprt_destroy makes the device current first; a host-only context holds
     // only empty owners, so its destruction makes no HIP call.
     Stream stream;
     // ReSTIR DI frames are pipelined over two streams: Part 1 + Part-2 setup of frame N+1 (front stream) run beside the
     // persistent trace kernel of frame N (`stream`, on which every frame COMPLETES and which fyprt_stream() hands out)
-    Stream front; Event evFront[2], evDone[2]; bool lastOverlapped = false; bool ringSplit[128] = {};
+    Stream front; Event evFront[2], evDone[2]; bool lastOverlapped = false;
+    // ... and, with tuning key 21, over a third: the history-free half of Part 1 of frame N+1 (k_di_part1_primary, `prim`) runs beside the
+    // setup kernel of frame N as well and hands its pixels to k_di_part1_temporal on the front stream through the staging set of the frame's
+    // parity.  evPrim: the primary kernel is done; evTemp: the temporal kernel is done, the staging set free for the frame after next
+    Stream prim; Event evPrim[2], evTemp[2];
     static constexpr int kRing = 128;          // frames whose per-launch hipEvents are kept (fyprt_frame_timings)
-    Event ring[kRing][5]; int ringLaunches[kRing] = {}; unsigned long long frameSerial = 0;
+    uint8_t ringSplit[kRing] = {};             // 0: the parts ran one after the other; 1: pipelined (the trace kernel starts at event 4); 2: Part 1 split as well (the front part starts at event 5)
+    Event ring[kRing][6]; int ringLaunches[kRing] = {}; unsigned long long frameSerial = 0;
     uint32_t W = 0, H = 0, frameIndex = 1, rowBegin = 0, rowEnd = 0, halo = 0; bool rowsSet = false;
     uint32_t stripeRows = 0, stripeParts = 1, stripePart = 0;       // fyprt_set_row_stripes (per-pixel techniques only)
     uint32_t commStripeRows = 0, commLastStripeRows = 0; bool commLastStriped = false;
@@ -130,6 +140,7 @@ struct fyprt_context {
     DevBuf<float4> accum; DevBuf<uint32_t> image; DevBuf<Payload> payload; DevBuf<float> depth; DevBuf<f2> normalA, normalB;
     DevBuf<DIRes> di, diPrev; DevBuf<GIRes> gi, giPrev; DevBuf<float4> giHot; bool normalFlip = false;
     DevBuf<DIRec> drec, dprevA, dprevB; bool dprevFlip = false; int lastTech = -1;
+    DevBuf<Payload> stagePayload; DevBuf<DIRec> stageRec;             // the split Part 1's staging sets, one per frame parity (written before they are read: not zeroed)
     int lastRestir = -1;                                              // technique of the last ReSTIR frame (-1: none since the buffers were zeroed): k_sync_history_normals
     uint32_t* externalImage = nullptr;
     // scene
@@ -209,10 +220,11 @@ struct fyprt_context {
 #define HIPCHK(ctx, call) do { int _rc = (ctx)->hip((call), #call); if (_rc != FYPRT_OK) return _rc; } while (0)
 #define TRY(call) do { const int _rc = (call); if (_rc != FYPRT_OK) return _rc; } while (0)      // a call that has reported its own error
 
-static hipError_t sync_all(fyprt_context* c) {      // both streams: the front one only ever runs ahead of `stream`
-    hipError_t e = c->front ? hipStreamSynchronize(c->front) : hipSuccess;
+static hipError_t sync_all(fyprt_context* c) {      // all three streams: `prim` only ever runs ahead of the front one, and that one ahead of `stream`
+    hipError_t e = c->prim ? hipStreamSynchronize(c->prim) : hipSuccess;
+    const hipError_t e1 = c->front ? hipStreamSynchronize(c->front) : hipSuccess;
     const hipError_t e2 = hipStreamSynchronize(c->stream);
-    return e != hipSuccess ? e : e2;
+    return e != hipSuccess ? e : e1 != hipSuccess ? e1 : e2;
 }
 
 // Effective pending-entry budget of node_step's stack rule for the uploaded tree: tuning key 8 if set; otherwise a few entries
@@ -317,19 +329,30 @@ int fyprt_create(int device_ordinal, fyprt_context** out) {
     e = hipSetDevice(device_ordinal);
     if (e != hipSuccess) { g_createError = std::string("hipSetDevice: ") + hipGetErrorString(e); return FYPRT_EHIP; }
     auto* c = new fyprt_context(); c->device = device_ordinal;
-    e = hipStreamCreateWithFlags(&c->stream.h, hipStreamNonBlocking);
-    if (e != hipSuccess) { g_createError = std::string("hipStreamCreate: ") + hipGetErrorString(e); delete c; return FYPRT_EHIP; }
-    {   // The front stream is created at the LOWEST priority: HIP deals the streams of one priority level round-robin over a
+    {   // The three streams sit on three different priority levels: HIP deals the streams of one priority level round-robin over a
         // few hardware queues (GPU_MAX_HW_QUEUES, default 4), and two streams that land on the same queue run strictly one
-        // after the other.  With torch + RCCL streams in the process both of ours shared a queue and nothing overlapped
-        // (1.12 instead of 0.99 ms per frame); a different priority level uses a different set of queues (1.00 ms), and with
-        // GPU_MAX_HW_QUEUES=8 in the environment as well, 0.98 ms with or without the per-frame gather (profiles/README.md).
+        // after the other.  With torch + RCCL streams in the process two of ours at one level shared a queue and nothing overlapped
+        // (1.12 instead of 0.99 ms per frame); a different priority level uses a different set of queues (profiles/README.md r01).
+        // `prim` is the lowest: its kernel soaks up the issue slots the others leave; the front stream, the frame's critical path, the
+        // highest (against lowest measured neutral in r03, before there was a third stream); the context stream keeps the default.
+        // -DFYPRT_PRIORITY_ORDER=1 / 2 build the other two assignments measured in profiles/README.md (di_split).
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-        e = hipStreamCreateWithPriority(&c->front.h, hipStreamNonBlocking, lo);
+        const int mid = (lo + hi) / 2;
+#if FYPRT_PRIORITY_ORDER == 1
+        const int pStream = hi, pFront = mid, pPrim = lo;
+#elif FYPRT_PRIORITY_ORDER == 2
+        const int pStream = mid, pFront = lo, pPrim = hi;
+#else
+        const int pStream = mid, pFront = hi, pPrim = lo;
+#endif
+        e = hipStreamCreateWithPriority(&c->stream.h, hipStreamNonBlocking, pStream);
+        if (e == hipSuccess) e = hipStreamCreateWithPriority(&c->front.h, hipStreamNonBlocking, pFront);
+        if (e == hipSuccess) e = hipStreamCreateWithPriority(&c->prim.h, hipStreamNonBlocking, pPrim);
     }
-    for (int k = 0; k < 2 && e == hipSuccess; ++k) { e = create(c->evFront[k], hipEventDisableTiming); if (e == hipSuccess) e = create(c->evDone[k], hipEventDisableTiming); }
-    if (e != hipSuccess) { g_createError = std::string("front stream / events: ") + hipGetErrorString(e); delete c; return FYPRT_EHIP; }
+    for (int k = 0; k < 2 && e == hipSuccess; ++k)
+        for (Event* ev : {&c->evFront[k], &c->evDone[k], &c->evPrim[k], &c->evTemp[k]}) if (e == hipSuccess) e = create(*ev, hipEventDisableTiming);
+    if (e != hipSuccess) { g_createError = std::string("streams / events: ") + hipGetErrorString(e); delete c; return FYPRT_EHIP; }
     for (auto& row : c->ring) for (auto& e : row) (void)create(e);
     { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, device_ordinal) == hipSuccess && prop.multiProcessorCount > 0) c->numCUs = prop.multiProcessorCount; }
     if (const char* e = std::getenv("FYPRT_TOP_NODES")) c->tuning[K_TOP_NODES] = std::min(1024, std::max(0, std::atoi(e)));
@@ -361,6 +384,7 @@ int fyprt_resize(fyprt_context* c, uint32_t w, uint32_t h) {
     TRY(alloc_zeroed(c, c->normalA, n)); TRY(alloc_zeroed(c, c->normalB, n));
     TRY(alloc_zeroed(c, c->di, n)); TRY(alloc_zeroed(c, c->diPrev, n)); TRY(alloc_zeroed(c, c->gi, n)); TRY(alloc_zeroed(c, c->giPrev, n)); TRY(alloc_zeroed(c, c->giHot, n * 4));
     TRY(alloc_zeroed(c, c->drec, n)); TRY(alloc_zeroed(c, c->dprevA, n)); TRY(alloc_zeroed(c, c->dprevB, n));
+    HIPCHK(c, c->stagePayload.alloc(2 * n)); HIPCHK(c, c->stageRec.alloc(2 * n));
     {   // shadow-task storage: 256 slots per setup workgroup (grid padded to whole groups of 8 tile rows), + the sort scratch
         const size_t tilesX = (w + 15u) / 16u, tilesY = (h + 15u) / 16u;
         const size_t maxGroups = std::max(tilesX * ((tilesY + 7u) / 8u) * 8u, ((tilesX * tilesY + 7u) / 8u) * 8u);
@@ -694,7 +718,7 @@ static int rebuild_light_trees(fyprt_context* c, const fyprt_vertex* verts, cons
     return upload_light_trees(c, nT, nM);
 }
 
-// What a geometry edit means to the temporal denoiser (both streams idle).  Motion mode off: the history is dropped.  On: it is kept, and
+// What a geometry edit means to the temporal denoiser (all streams idle).  Motion mode off: the history is dropped.  On: it is kept, and
 // the first edit after a temporal call copies the world vertices that call's frame was traced in: device to device on the context
 // stream, so ahead of whatever the edit enqueues there.  An edit that writes dverts any other way waits for the copy first.
 static int temporal_edit_begin(fyprt_context* c) {
@@ -1115,13 +1139,13 @@ static int sync_restir_normals(fyprt_context* c, int tech, hipStream_t stream) {
 
 // ---- a frame's host path: check_frame, begin_frame, one function per technique family, end_frame.  FrameRun carries what they share.
 // sc: the frame's own copy of c->dsc — the four per-launch fields are set here, never in the context; ldsBytes: traversal stack (+ top nodes) of its
-// traversing launches; par: queue / event parity; wavefront: ReSTIR DI Part 2 over a task queue; overlap: pipelined over two streams; fs: where Part 1 +
-// setup go; grid: tiles of the context's rows; ev, ei: its slot of the timing ring, the next event to record; launches: the parts it reports (not its
-// kernels); part1Only: phase 1 — Part 1 is enqueued, the frame stops there
+// traversing launches; par: queue / event parity; wavefront: ReSTIR DI Part 2 over a task queue; overlap: pipelined over two streams; split: ... and the
+// history-free half of Part 1 on a third; fs: where Part 1 (split: its history half) + setup go; grid: tiles of the context's rows; ev, ei: its slot of
+// the timing ring, the next event to record; launches: the parts it reports (not its kernels); part1Only: phase 1 — Part 1 is enqueued, the frame stops there
 struct FrameRun {
     fyprt_context* c; const fyprt_settings* s; int tech, phase; bool timed;
     DevSettings st; DevFrame fr; DevScene sc; size_t ldsBytes;
-    int par; bool wavefront, overlap, striped; hipStream_t fs; dim3 grid;
+    int par; bool wavefront, overlap, split, striped; hipStream_t fs; dim3 grid;
     Event* ev; int ei, launches, stageLaunches; bool part1Only;
 };
 static bool stripes_set(const fyprt_context* c) { return c->stripeRows != 0 && c->stripeRows < c->H && c->stripeParts > 1; }
@@ -1175,10 +1199,17 @@ static int begin_frame(FrameRun& f) {
     f.par = (int)(c->frameSerial & 1ull); f.wavefront = f.tech == FYPRT_RESTIR_DI && c->tuning[K_DI_WAVEFRONT] == 1;
     f.overlap = f.wavefront && c->tuning[K_PIPELINE] != 0 && !c->countRays && f.phase == 0;
     f.fs = f.overlap ? c->front : c->stream;
+    // Split Part 1 (tuning key 21, asynchronous pipelined frames): everything of Part 1 up to the candidate reservoir needs the scene, the camera, the
+    // frame index and the seed only — k_di_part1_primary computes it on `prim` into the staging set of the frame's parity, which nothing else reads,
+    // while the front stream is still busy with frame N's setup kernel (which writes the history Part 1 merges); k_di_part1_temporal on the front
+    // stream does the rest, and writes every public buffer where k_di_part1 did.  The API calls that edit the scene or reallocate wait for all three
+    // streams first (sync_all), so `prim` itself waits for one thing: the temporal kernel that read this staging set, two frames ago.
+    f.split = f.overlap && c->tuning[K_DI_SPLIT] != 0 && !c->blockingCall;
     if (f.overlap) {
         HIPCHK(c, hipStreamWaitEvent(c->front, c->evDone[f.par], 0));                            // frame N-2 done: its queue is free
         if (!c->lastOverlapped) HIPCHK(c, hipStreamWaitEvent(c->front, c->evDone[f.par ^ 1], 0));   // frame N-1 ran on `stream` alone
     }
+    if (f.split) HIPCHK(c, hipStreamWaitEvent(c->prim, c->evTemp[f.par], 0));
     c->frameComplete = false;                  // from the first enqueued work until the frame is enqueued to its end (fyprt_denoise)
     fr.tileOrder = (uint32_t)c->tuning[K_TILE_ORDER]; fr.p1Mode = f.wavefront ? 1u : 0u;
     f.grid = tile_grid(c, c->rowBegin, c->rowEnd); f.ev = c->ring[c->frameSerial % fyprt_context::kRing];
@@ -1188,7 +1219,7 @@ static int begin_frame(FrameRun& f) {
     // frame 1 (or toAccumulate == false): the accumulator starts from zero (Renderer.cu:50-51) — on `stream`, which owns it (the whole buffer, as the
     // reference does, not just this context's rows: a band moved later with fyprt_set_rows must not find the sums of an earlier accumulation in its new rows)
     if (c->frameIndex == 1) HIPCHK(c, hipMemsetAsync(c->accum.p, 0, c->accum.bytes(), c->stream));
-    if (f.timed) HIPCHK(c, hipEventRecord(f.ev[f.ei++], f.fs));
+    if (f.timed) HIPCHK(c, hipEventRecord(f.ev[f.ei++], f.split ? c->prim.h : f.fs));
     return FYPRT_OK;
 }
 // One stage of the wavefront path engine (rt_paths.h) on the frame's scene, with the wf* buffers as ensure_paths left them
@@ -1311,9 +1342,22 @@ static int enqueue_di_frame(FrameRun& f) {
     fyprt_context* c = f.c;
     if (f.phase != 2) {
         const Part1Rows p1 = part1_rows(c);
-        TRY(sync_restir_normals(c, f.tech, f.fs));   // the last ReSTIR frame was a GI frame: its normals are this frame's "previous normals"
-        hipLaunchKernelGGL(c->countRays ? k_di_part1<true> : k_di_part1<false>, p1.grid, dim3(kBlock), f.ldsBytes, f.fs, f.sc, c->dcam, f.fr, f.st, p1.begin, p1.end, p1.extraRow);
-        if (f.timed) HIPCHK(c, hipEventRecord(f.ev[f.ei++], f.fs));
+        if (f.split) {               // part 0 of the frame's timings: the primary kernel, between its own events on `prim`
+            const size_t npx = (size_t)c->W * c->H;
+            const DIStage sg{c->stagePayload.p + (size_t)f.par * npx, c->stageRec.p + (size_t)f.par * npx};
+            hipLaunchKernelGGL(k_di_part1_primary<false>, p1.grid, dim3(kBlock), f.ldsBytes, c->prim, f.sc, c->dcam, f.fr, f.st, p1.begin, p1.end, p1.extraRow, sg);
+            if (f.timed) HIPCHK(c, hipEventRecord(f.ev[f.ei++], c->prim));
+            HIPCHK(c, hipEventRecord(c->evPrim[f.par], c->prim));
+            HIPCHK(c, hipStreamWaitEvent(c->front, c->evPrim[f.par], 0));
+            TRY(sync_restir_normals(c, f.tech, f.fs));
+            if (f.timed) HIPCHK(c, hipEventRecord(f.ev[5], c->front));   // part 1: temporal + setup, from here to the event behind the setup kernel
+            hipLaunchKernelGGL(k_di_part1_temporal, p1.grid, dim3(kBlock), 0, c->front, f.sc, c->dcam, f.fr, f.st, p1.begin, p1.end, p1.extraRow, sg);
+            HIPCHK(c, hipEventRecord(c->evTemp[f.par], c->front));
+        } else {
+            TRY(sync_restir_normals(c, f.tech, f.fs));   // the last ReSTIR frame was a GI frame: its normals are this frame's "previous normals"
+            hipLaunchKernelGGL(c->countRays ? k_di_part1<true> : k_di_part1<false>, p1.grid, dim3(kBlock), f.ldsBytes, f.fs, f.sc, c->dcam, f.fr, f.st, p1.begin, p1.end, p1.extraRow);
+            if (f.timed) HIPCHK(c, hipEventRecord(f.ev[f.ei++], f.fs));
+        }
         if (f.phase == 1) { f.part1Only = true; return c->hip(hipGetLastError(), "ReSTIR DI part 1"); }
     }
     // shadow-ray kernels of Part 2: the secondary quorum (measured 0.85 -> 0.68 ms), counters of their own
@@ -1332,7 +1376,7 @@ static int end_frame(FrameRun& f) {
     HIPCHK(c, hipEventRecord(c->evDone[f.par], c->stream));                // the frame is complete (and its task queue free again)
     c->lastOverlapped = f.overlap; c->lastLaunches = f.launches; c->lastTech = f.tech;
     if (f.tech == FYPRT_RESTIR_DI || f.tech == FYPRT_RESTIR_GI) c->lastRestir = f.tech;
-    c->ringLaunches[slot] = f.timed ? f.launches : 0; c->ringSplit[slot] = f.overlap;
+    c->ringLaunches[slot] = f.timed ? f.launches : 0; c->ringSplit[slot] = f.split ? 2 : f.overlap ? 1 : 0;
     c->frameSerial++; c->frameComplete = true; c->lastFrameIndex = c->frameIndex;
     if (f.s->to_accumulate) c->frameIndex++; else c->frameIndex = 1;       // Renderer.cu:258-261
     return FYPRT_OK;
@@ -1349,9 +1393,11 @@ static int enqueue_frame(fyprt_context* c, const fyprt_settings* s, bool timed, 
     if (rc != FYPRT_OK && rc != FYPRT_ESTATE) c->part1Pending = false;      // a frame that failed half-way is abandoned, not left pending
     return rc;
 }
-// Time of part `k` of the frame in ring slot `slot`, between its timing events; the trace kernel of a split (pipelined) frame has its own start event
+// Time of part `k` of the frame in ring slot `slot`, between its timing events; the trace kernel of a pipelined frame has its own start event, and
+// so has the front part (temporal + setup) of a frame whose Part 1 was split
 static hipError_t part_elapsed(fyprt_context* c, unsigned long long slot, int k, float* ms) {
-    return hipEventElapsedTime(ms, c->ring[slot][(c->ringSplit[slot] && k == 2) ? 4 : k], c->ring[slot][k + 1]);
+    const int mode = c->ringSplit[slot], start = (mode && k == 2) ? 4 : (mode == 2 && k == 1) ? 5 : k;
+    return hipEventElapsedTime(ms, c->ring[slot][start], c->ring[slot][k + 1]);
 }
 
 int fyprt_render(fyprt_context* c, const fyprt_settings* s, fyprt_frame_stats* stats) {
@@ -1819,7 +1865,7 @@ template <class F> static void for_dn_step(int step, F&& launch) {
 template <class Enqueue> static int denoise_blocking(fyprt_context* c, uint32_t* rgba8, float* radiance4, fyprt_frame_stats* stats, Event* ev, int nEv, Enqueue&& enqueue) {
     if (stats) std::memset(stats, 0, sizeof *stats);
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, sync_all(c));                           // as fyprt_readback: the last frame is complete on both streams
+    HIPCHK(c, sync_all(c));                           // as fyprt_readback: the last frame is complete on every stream
     for (int k = 0; k < nEv; ++k) HIPCHK(c, create(ev[k]));
     const size_t n = (size_t)c->W * c->H;
     if (rgba8 && c->dn.outImg.n != n) HIPCHK(c, c->dn.outImg.alloc(n));

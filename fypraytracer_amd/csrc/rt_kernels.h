@@ -250,47 +250,55 @@ RT_DEV uint32_t neighbor_index(const DevCamera& cam, uint32_t W, uint32_t x, uin
     return (uint32_t)ox + (uint32_t)oy * W;
 }
 
-// Part 1 rows: [p1Begin, p1End) (band + halo); finished pixels (sky / emitter) go through the
-// epilogue only inside the band proper so halo rows never touch accumulation.
-template <bool COUNT>
-__global__ __launch_bounds__(kBlock) void k_di_part1(DevScene sc, DevCamera cam, DevFrame fr, DevSettings st, uint32_t p1Begin, uint32_t p1End, uint32_t extraRow) {
-    extern __shared__ int32_t s_stack[];                         // (stackBudget + 1) entries x kBlock threads, sized at launch, + the top-node copy
-    const float4* top4 = stage_top_nodes(sc.nodes, sc.topCount, sc.stackBudget, s_stack);
-    uint32_t x, y;
-    if (!p1_pixel_of_thread(fr, p1Begin, p1End, extraRow, x, y)) return;
-    int32_t* stk = s_stack + threadIdx.x;
-    const uint32_t i = x + y * fr.W;
-    const bool inBand = (y >= fr.rowBegin && y < fr.rowEnd);
-    uint32_t seed = i * (fr.frameIndex + 1u + st.randSeed);
-    const f3 pd = ray_direction(cam, x, y);
-    const Payload pp = trace_ray<COUNT>(sc, cam.position, pd, stk, top4);
-    fr.payload[i] = pp;
-    const f2 ncur = oct_encode(nrm3(pp));
-    DIRes R = di_empty();
-    bool finished = false; f3 finalColor = splat3(0.0f);
-    Mat hm;
-    if (pp.hitDistance < 0.0f) { finished = true; finalColor = st.sky; }
+// Part 1 is written as two halves, in the order of the reference's kernel.  k_di_part1 runs one after the other in one thread; a pipelined
+// frame runs them as two kernels (k_di_part1_primary on a stream of its own, k_di_part1_temporal on the front stream) with a DIPixel
+// handed over through staging memory — the same operations in the same order on the same values, so the same bits.
+struct DIPixel { Payload pp; f3 pd; f2 ncur; Mat hm; f3 albedo, finalColor; DIRes R; uint32_t seed; bool finished; };
+// A pixel whose primary ray left the scene or hit an emitter is finished in Part 1 (Renderer.cu:1650-1668); loads the hit's material otherwise
+RT_DEV void di_finished(const DevScene& sc, const DevSettings& st, DIPixel& p) {
+    p.finished = false; p.finalColor = splat3(0.0f);
+    if (p.pp.hitDistance < 0.0f) { p.finished = true; p.finalColor = st.sky; }
     else {
-        hm = load_mat(sc, tri_material(sc, pp.objectIndex));
-        if (length(emission(hm)) > 0.0f) { finished = true; finalColor = emission(hm); }
+        p.hm = load_mat(sc, tri_material(sc, p.pp.objectIndex));
+        if (length(emission(p.hm)) > 0.0f) { p.finished = true; p.finalColor = emission(p.hm); }
     }
-    if (finished) {
-        store_rec(fr.drec + i, pp.hitDistance, ncur, R);
-        // history for the next frame: this frame's normal, the previous reservoir carried over unchanged (the
-        // reference never writes di_prev_reservoirs for pixels finished in Part 1)
-        store_rec(fr.dprevWrite + i, pp.hitDistance, ncur, rec_reservoir(load_rec(fr.dprevRead + i)));
-        fr.depth[i] = pp.hitDistance;
-        if (inBand && fr.p1Mode == 0u) epilogue(fr, i, rgb1(finalColor));
-        return;
-    }
-    const f3 albedo = sample_albedo(sc, hm, pp.u, pp.v);
+}
+// The half that depends on nothing from earlier frames: primary ray, material, albedo, the light candidates and R.W.  Reads the scene,
+// the camera, frameIndex and randSeed; writes the payload to `payloadOut` and nothing else.
+template <bool COUNT>
+RT_DEV void di_part1_candidates(const DevScene& sc, const DevCamera& cam, const DevFrame& fr, const DevSettings& st, uint32_t x, uint32_t y,
+                                int32_t* stk, const float4* top4, Payload* payloadOut, DIPixel& p) {
+    const uint32_t i = x + y * fr.W;
+    p.seed = i * (fr.frameIndex + 1u + st.randSeed);
+    p.pd = ray_direction(cam, x, y);
+    p.pp = trace_ray<COUNT>(sc, cam.position, p.pd, stk, top4);
+    *payloadOut = p.pp;
+    p.ncur = oct_encode(nrm3(p.pp));
+    p.R = di_empty();
+    di_finished(sc, st, p);
+    if (p.finished) return;
+    p.albedo = sample_albedo(sc, p.hm, p.pp.u, p.pp.v);
     const uint32_t nE = sc.emissiveCount;
     for (uint32_t k = 0; k < st.candidateCount; ++k) {
-        const uint32_t e = (uint32_t)__builtin_roundf((float)(nE - 1u) * rnd(seed));
-        const float pdf = di_target(sc, e, pp, pd, hm, albedo);
-        di_update(R, e, pdf * (float)nE, 1u, pdf, seed);
+        const uint32_t e = (uint32_t)__builtin_roundf((float)(nE - 1u) * rnd(p.seed));
+        const float pdf = di_target(sc, e, p.pp, p.pd, p.hm, p.albedo);
+        di_update(p.R, e, pdf * (float)nE, 1u, pdf, p.seed);
     }
-    R.W = R.pdf > 0.0f ? ((1.0f / R.pdf) * R.wSum) / (float)R.M : 0.0f;
+    p.R.W = p.R.pdf > 0.0f ? ((1.0f / p.R.pdf) * p.R.wSum) / (float)p.R.M : 0.0f;
+}
+// The half that reads and writes history: the records of a finished pixel, or the temporal merge and this frame's record
+RT_DEV void di_part1_temporal(const DevScene& sc, const DevCamera& cam, const DevFrame& fr, const DevSettings& st, uint32_t i, bool inBand, DIPixel& p) {
+    const Payload& pp = p.pp; DIRes& R = p.R;
+    if (p.finished) {
+        store_rec(fr.drec + i, pp.hitDistance, p.ncur, R);
+        // history for the next frame: this frame's normal, the previous reservoir carried over unchanged (the
+        // reference never writes di_prev_reservoirs for pixels finished in Part 1)
+        store_rec(fr.dprevWrite + i, pp.hitDistance, p.ncur, rec_reservoir(load_rec(fr.dprevRead + i)));
+        fr.depth[i] = pp.hitDistance;
+        if (inBand && fr.p1Mode == 0u) epilogue(fr, i, rgb1(p.finalColor));
+        return;
+    }
+    const uint32_t nE = sc.emissiveCount;
     if (st.useTemporal) {
         uint32_t prow;
         const uint32_t prevIdx = prev_pixel(cam, pos3(pp), prow);
@@ -305,17 +313,71 @@ __global__ __launch_bounds__(kBlock) void k_di_part1(DevScene sc, DevCamera cam,
             const uint32_t lim = st.historyLimit * R.M;
             prev.M = (lim < prev.M) ? lim : prev.M;
             DIRes Tm = di_empty(); uint32_t Z = 0;
-            { const float pdf = R.pdf; di_update(Tm, R.index, (pdf * R.W) * (float)R.M, R.M, pdf, seed); Z += pdf > 0.0f ? R.M : 0u; }
-            const float pdf = di_target(sc, prev.index, pp, pd, hm, albedo);
-            di_update(Tm, prev.index, (pdf * prev.W) * (float)prev.M, prev.M, pdf, seed);
+            { const float pdf = R.pdf; di_update(Tm, R.index, (pdf * R.W) * (float)R.M, R.M, pdf, p.seed); Z += pdf > 0.0f ? R.M : 0u; }
+            const float pdf = di_target(sc, prev.index, pp, p.pd, p.hm, p.albedo);
+            di_update(Tm, prev.index, (pdf * prev.W) * (float)prev.M, prev.M, pdf, p.seed);
             Z += pdf > 0.0f ? prev.M : 0u;
             const float m = 1.0f / (float)Z;
             Tm.W = Tm.pdf > 0.0f ? (1.0f / Tm.pdf) * (m * Tm.wSum) : 0.0f;
             R = Tm;
         }
     }
-    store_rec(fr.drec + i, pp.hitDistance, ncur, R);
+    store_rec(fr.drec + i, pp.hitDistance, p.ncur, R);
     if (inBand && fr.p1Mode == 0u) fr.image[i] = 0u;     // sentinel: ConvertToRGBA(vec4(0)) (Renderer.cu:2746-2750)
+}
+
+// Part 1 rows: [p1Begin, p1End) (band + halo); finished pixels (sky / emitter) go through the
+// epilogue only inside the band proper so halo rows never touch accumulation.
+template <bool COUNT>
+__global__ __launch_bounds__(kBlock) void k_di_part1(DevScene sc, DevCamera cam, DevFrame fr, DevSettings st, uint32_t p1Begin, uint32_t p1End, uint32_t extraRow) {
+    extern __shared__ int32_t s_stack[];                         // (stackBudget + 1) entries x kBlock threads, sized at launch, + the top-node copy
+    const float4* top4 = stage_top_nodes(sc.nodes, sc.topCount, sc.stackBudget, s_stack);
+    uint32_t x, y;
+    if (!p1_pixel_of_thread(fr, p1Begin, p1End, extraRow, x, y)) return;
+    const uint32_t i = x + y * fr.W;
+    const bool inBand = (y >= fr.rowBegin && y < fr.rowEnd);
+    DIPixel p;
+    di_part1_candidates<COUNT>(sc, cam, fr, st, x, y, s_stack + threadIdx.x, top4, fr.payload + i, p);
+    di_part1_temporal(sc, cam, fr, st, i, inBand, p);
+}
+
+// Part 1 of a pipelined frame, history-free half: the same rows, the payload and the candidate record (hit distance, octahedral normal, the
+// candidate reservoir with W and wSum) into the frame parity's private staging set.  No API call and no other kernel reads what it writes
+// but k_di_part1_temporal of the same frame, so it may run while the previous frame's setup kernel still writes the history.
+struct DIStage { Payload* payload; DIRec* rec; };
+template <bool COUNT>
+__global__ __launch_bounds__(kBlock) void k_di_part1_primary(DevScene sc, DevCamera cam, DevFrame fr, DevSettings st, uint32_t p1Begin, uint32_t p1End, uint32_t extraRow, DIStage sg) {
+    extern __shared__ int32_t s_stack[];                         // as k_di_part1
+    const float4* top4 = stage_top_nodes(sc.nodes, sc.topCount, sc.stackBudget, s_stack);
+    uint32_t x, y;
+    if (!p1_pixel_of_thread(fr, p1Begin, p1End, extraRow, x, y)) return;
+    const uint32_t i = x + y * fr.W;
+    DIPixel p;
+    di_part1_candidates<COUNT>(sc, cam, fr, st, x, y, s_stack + threadIdx.x, top4, sg.payload + i, p);
+    store_rec(sg.rec + i, p.pp.hitDistance, p.ncur, p.R);
+}
+// ... and the history half, one thread per Part-1 pixel, no traversal: payload and candidate record from the staging set, view direction,
+// material and albedo recomputed from the payload as the setup kernel does, the RNG state after the candidates re-derived (every candidate
+// draws twice: its light and its reservoir update, so the state is pcg_hash applied 2 x candidateCount times to the pixel's initial seed).
+// Writes the public payload and what Part 1 writes of records, history and depth.  A pipelined frame has p1Mode 1: no epilogue, no sentinel.
+__global__ __launch_bounds__(kBlock) void k_di_part1_temporal(DevScene sc, DevCamera cam, DevFrame fr, DevSettings st, uint32_t p1Begin, uint32_t p1End, uint32_t extraRow, DIStage sg) {
+    uint32_t x, y;
+    if (!p1_pixel_of_thread(fr, p1Begin, p1End, extraRow, x, y)) return;
+    const uint32_t i = x + y * fr.W;
+    fr.p1Mode = 1u;
+    DIPixel p;
+    p.pp = sg.payload[i];
+    fr.payload[i] = p.pp;
+    const DIRec rec = load_rec(sg.rec + i);
+    p.ncur.x = rec.nx; p.ncur.y = rec.ny; p.R = rec_reservoir(rec);
+    p.pd = ray_direction(cam, x, y);
+    di_finished(sc, st, p);
+    if (!p.finished) {
+        p.albedo = sample_albedo(sc, p.hm, p.pp.u, p.pp.v);
+        p.seed = i * (fr.frameIndex + 1u + st.randSeed);
+        for (uint32_t k = 0; k < 2u * st.candidateCount; ++k) p.seed = pcg_hash(p.seed);
+    }
+    di_part1_temporal(sc, cam, fr, st, i, y >= fr.rowBegin && y < fr.rowEnd, p);
 }
 
 template <bool COUNT>

@@ -210,7 +210,11 @@ int fyprt_render(fyprt_context* ctx, const fyprt_settings* settings, fyprt_frame
 int fyprt_render_async(fyprt_context* ctx, const fyprt_settings* settings);
 int fyprt_synchronize(fyprt_context* ctx);
 /* Per-launch hipEvent times (ms) of the frame enqueued `frames_back` frames ago (0 = the last one; the last 128 frames
- * are kept).  The events are recorded on the context's stream by both render variants; call after fyprt_synchronize. */
+ * are kept).  The events are recorded on the context's streams by both render variants; call after fyprt_synchronize.
+ * A ReSTIR DI frame reports three parts (launches == 3).  Pipelined with Part 1 split (tuning key 21, asynchronous frames): part 0 =
+ * the primary kernel (primary rays + light candidates, between its own events on its own stream), part 1 = the temporal kernel + the
+ * setup kernel on the front stream, part 2 = the trace kernel.  Otherwise: part 0 = Part 1, part 1 = setup, part 2 = trace.  The parts of
+ * a pipelined frame run beside parts of its neighbours: their sum is not the frame's time. */
 int fyprt_frame_timings(fyprt_context* ctx, uint32_t frames_back, float* kernel_ms_part4, uint32_t* launches);
 
 /* The D2H copies at Renderer.cu:244-250: rgba8 = m_RenderImageData (ABGR8, row 0 = NDC y -1),
@@ -302,7 +306,7 @@ int fyprt_set_ray_counting(fyprt_context* ctx, int enabled);
  *        0.833 -> 0.820 ms, config 3 3.13 -> 3.08 ms against 1; on queues shorter than the grid the static part is an even share and no atomic is issued at all).
  * key 10: smallest chunk of the guided self-scheduling of the shared part: claims shrink from key 4 towards this value as
  *        the queue runs out (default 32).
- * key 11: 1 (default) = wavefront ReSTIR DI frames are pipelined over two streams: Part 1 + setup of frame N+1 run beside the
+ * key 11: 1 (default) = wavefront ReSTIR DI frames are pipelined over two streams (three with key 21): Part 1 + setup of frame N+1 run beside the
  *        trace kernel of frame N (asynchronous frames only overlap, of course; a blocking fyprt_render waits for its frame).
  * key 12: builder of the acceleration structure for the NEXT fyprt_upload_scene: 0 (default) host binned SAH + SAH-optimal
  *        collapse; 1 device LBVH (Morton sort, Karras radix tree, collapse, refit) — milliseconds instead of a fraction of a
@@ -332,8 +336,12 @@ int fyprt_set_ray_counting(fyprt_context* ctx, int enabled);
  *         0 = the stages (2 x neighbours + 1 launches; state, ray and result records move through memory).  1 = one launch, one thread per
  *         pixel without refill (slower on a whole frame, kept for comparison).  Same pixels bit for bit, same ray counts in every mode.
  * key 20: k_gi2_persistent (key 19 = 2): lanes of a wave without a ray in flight before the wave services them together (default 48; 0 = default).
- * Values are range-checked (FYPRT_EINVAL): key 0: 0..2, keys 1, 3, 11, 13, 18: 0..1, keys 12, 14, 15, 17, 19: 0..2, key 2: 0..16, keys 5, 6, 7, 20: 0..64,
- * key 8: 0..31, key 16: 0..1024; keys 21..23 are reserved (0). */
+ * key 21: 1 (default) = Part 1 of a pipelined ReSTIR DI frame (key 11, asynchronous frames) runs as two kernels: its history-free half (primary ray,
+ *         material, light candidates) on a third stream — beside the previous frame's setup kernel, which writes the history — and the temporal
+ *         merge on the front stream, fed through a private staging set per frame parity (72 B per pixel and parity).  0 = one kernel on the front
+ *         stream.  Same results bit for bit; blocking, instrumented and two-call frames always take the one kernel.
+ * Values are range-checked (FYPRT_EINVAL): key 0: 0..2, keys 1, 3, 11, 13, 18, 21: 0..1, keys 12, 14, 15, 17, 19: 0..2, key 2: 0..16, keys 5, 6, 7, 20: 0..64,
+ * key 8: 0..31, key 16: 0..1024; keys 22..23 are reserved (0). */
 int fyprt_set_tuning(fyprt_context* ctx, int key, int value);
 /* The value in effect (key 8: the budget actually used for the uploaded scene, which an instrumented restatement of the
  * traversal must use too). */
@@ -540,7 +548,7 @@ int fyprt_denoise_temporal_reset(fyprt_context* ctx);
  * stay refused).
  * With 1: the two geometry edits no longer drop the history.  If a history exists and no snapshot is pending, the edit first copies the
  * world vertices (positions and normals) as they are on the device into a per-context snapshot buffer — device to device, on the context
- * stream, after the call's own wait for both streams and complete before the edit writes a vertex.  The snapshot is pending from that
+ * stream, after the call's own wait for the context's streams and complete before the edit writes a vertex.  The snapshot is pending from that
  * copy until the next successful temporal call, which consumes it; further edits before that call leave it alone, frames rendered in
  * between without a temporal call do not matter, so the snapshot is always the geometry of the frame the previous temporal call
  * denoised.  fyprt_upload_scene, fyprt_update_materials, fyprt_resize, fyprt_denoise_temporal_reset and a change of the mode drop
