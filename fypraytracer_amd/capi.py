@@ -185,6 +185,7 @@ EXPORTED_SYMBOLS = [
     "fyprt_update_materials", "fyprt_export_emissive",
     "fyprt_denoise_temporal_set_motion",
     "fyprt_group_denoise", "fyprt_group_denoise_device", "fyprt_group_denoise_plan",
+    "fyprt_append_meshes", "fyprt_append_textures",
 ]
 
 
@@ -290,6 +291,9 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
         lib.fyprt_group_denoise.argtypes = [vp, C.POINTER(DenoiseParams), vp, vp, vp]
         lib.fyprt_group_denoise_device.argtypes = [vp, C.POINTER(DenoiseParams), C.c_int, vp, vp]
         lib.fyprt_group_denoise_plan.argtypes = [C.POINTER(u32), C.c_int, u32, u32, C.POINTER(u32), C.c_int]
+    if hasattr(lib, "fyprt_append_meshes"):  # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
+        lib.fyprt_append_meshes.argtypes = [vp, vp, u32, vp, u32, u32, vp, u32, vp, C.POINTER(u32)]
+        lib.fyprt_append_textures.argtypes = [vp, C.POINTER(Texture), u32]
     alternative = path is not None or "FYPRT_LIB" in os.environ      # an older build loaded for an A/B run may lack the newest entry points
     for f in EXPORTED_SYMBOLS:
         if alternative and not hasattr(lib, f):
@@ -402,6 +406,7 @@ class Context:
     def upload_scene(self, scene, light_trees=None):
         d, keep = make_scene_desc(scene, light_trees)
         self._check(self.lib.fyprt_upload_scene(self.h, C.byref(d)))
+        self._has_object_vertices = False                         # an upload drops the object-space copy
 
     def set_camera(self, cam):
         c = make_camera_desc(cam)
@@ -477,6 +482,7 @@ class Context:
         v = np.ascontiguousarray(scene.vertices)
         first = [tr["vertex_start"] for tr in scene.mesh_transforms] + [len(v)]
         self._check(self.lib.fyprt_set_object_vertices(self.h, v.ctypes.data, len(v), (C.c_uint32 * len(first))(*first)))
+        self._has_object_vertices = True                          # append_meshes passes the new meshes' object-space vertices along
 
     def update_transforms(self, scene, mesh_indices, matrices=None):
         """A transform edit applied on the device: 64 bytes per mesh (Scene.mesh_matrix) instead of its vertices.  `matrices`: one
@@ -500,6 +506,34 @@ class Context:
         self._check(self.lib.fyprt_update_materials(self.h, _ptr(m) if len(m) else None, len(m), idx, mat, len(meshes),
                                                     None if em is None else (em.ctypes.data if len(em) else C.cast((C.c_uint32 * 1)(), C.c_void_p)),
                                                     0 if em is None else len(em)))
+
+    def append_meshes(self, scene, first_new_mesh, with_object_vertices=None):
+        """An import applied on the device (fyprt_append_meshes): the tails of a `scene` that add_new_mesh_to_scene extended by the
+        meshes [first_new_mesh, len(scene.meshes)) — their triangles, and the vertices from the first of them on.  The object-space
+        vertices go along when the context holds a copy (set_object_vertices on this wrapper); `with_object_vertices` overrides that."""
+        first_new_mesh = int(first_new_mesh)
+        ms = np.ascontiguousarray(scene.meshes_array()[first_new_mesh:], dtype=MESH_DTYPE)
+        t0 = int(scene.meshes[first_new_mesh][0]) if first_new_mesh < len(scene.meshes) else len(scene.triangles)
+        v0 = int(scene.mesh_transforms[first_new_mesh]["vertex_start"]) if first_new_mesh < len(scene.mesh_transforms) else len(scene.world_vertices)
+        v = np.ascontiguousarray(scene.world_vertices[v0:], dtype=VERTEX_DTYPE)
+        t = np.ascontiguousarray(scene.triangles[t0:], dtype=TRIANGLE_DTYPE)
+        with_object = getattr(self, "_has_object_vertices", False) if with_object_vertices is None else bool(with_object_vertices)
+        ov = first = None
+        if with_object:
+            ov = np.ascontiguousarray(scene.vertices[v0:], dtype=VERTEX_DTYPE)
+            starts = [tr["vertex_start"] for tr in scene.mesh_transforms[first_new_mesh:]] + [len(scene.world_vertices)]
+            first = (C.c_uint32 * len(starts))(*starts)
+        self._check(self.lib.fyprt_append_meshes(self.h, _ptr(v) if len(v) else None, len(v), _ptr(t) if len(t) else None, len(t), TRIANGLE_DTYPE.itemsize,
+                                                 _ptr(ms) if len(ms) else None, len(ms), None if ov is None else (ov.ctypes.data if len(ov) else C.cast((C.c_uint32 * 8)(), C.c_void_p)), first))
+        self._has_object_vertices = with_object
+
+    def append_textures(self, textures):
+        """New textures behind the uploaded ones (fyprt_append_textures); each a uint32 [H][W] ABGR8 array."""
+        px = [np.ascontiguousarray(t, dtype=np.uint32) for t in textures]
+        texs = (Texture * max(1, len(px)))()
+        for i, a in enumerate(px):
+            texs[i].pixels, texs[i].height, texs[i].width = _ptr(a), a.shape[0], a.shape[1]
+        self._check(self.lib.fyprt_append_textures(self.h, C.cast(texs, C.POINTER(Texture)) if px else None, len(px)))
 
     def export_emissive(self) -> np.ndarray:
         """The emissive-triangle list in effect (fyprt_export_emissive)."""

@@ -375,6 +375,12 @@ static void BuildWithDepthBound(const fyprt_vertex* verts, const uint8_t* tris, 
     }
 }
 
+void QuantiseNode(Node& n, const ChildBox* boxes, int count) {
+    Collapser::Child ch[4];
+    for (int i = 0; i < count && i < 4; ++i) { ch[i].ref = 0; std::memcpy(ch[i].b.lo, boxes[i].lo, 12); std::memcpy(ch[i].b.hi, boxes[i].hi, 12); }
+    Collapser::quantise(n, ch, std::min(count, 4));
+}
+
 void BuildSceneBVH(const fyprt_vertex* verts, const uint8_t* tris, uint32_t triStride, const fyprt_mesh* meshes,
                    uint32_t meshCount, SceneBVH& out) {
     BuildWithDepthBound(verts, tris, triStride, meshes, meshCount, kMaxDepthRelaxed, out);

@@ -39,21 +39,22 @@ thread_local std::string g_createError;
 
 std::atomic<uint64_t> g_liveDeviceBytes{0};     // device bytes held by every DevBuf of the process (fyprt_live_device_bytes)
 
-// Move-only owner of a device allocation.  A host-only context (device -1) records the size and allocates nothing.
+// Move-only owner of a device allocation.  A host-only context (device -1) records the size and allocates nothing.  `n` elements are in
+// use out of `cap` allocated ones: the two differ only for a scene array that an append grew (grow_buffer).
 template <class T> struct DevBuf {
-    T* p = nullptr; size_t n = 0;
+    T* p = nullptr; size_t n = 0, cap = 0;
     DevBuf() = default;
-    DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
-    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { release(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; } return *this; }
+    DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n), cap(o.cap) { o.p = nullptr; o.n = o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { release(); p = o.p; n = o.n; cap = o.cap; o.p = nullptr; o.n = o.cap = 0; } return *this; }
     ~DevBuf() { release(); }
     hipError_t alloc(size_t count, bool hostOnly = false) {
-        release(); n = count;
+        release(); n = cap = count;
         if (count == 0 || hostOnly) return hipSuccess;
         const hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
-        if (e == hipSuccess) g_liveDeviceBytes += bytes(); else { p = nullptr; n = 0; }
+        if (e == hipSuccess) g_liveDeviceBytes += cap * sizeof(T); else { p = nullptr; n = cap = 0; }
         return e;
     }
-    void release() { if (p) { (void)hipFree(p); g_liveDeviceBytes -= bytes(); } p = nullptr; n = 0; }
+    void release() { if (p) { (void)hipFree(p); g_liveDeviceBytes -= cap * sizeof(T); } p = nullptr; n = cap = 0; }
     size_t bytes() const { return n * sizeof(T); }
 };
 
@@ -152,6 +153,7 @@ struct fyprt_context {
     DevBuf<DevVertex> objVerts; std::vector<uint32_t> meshFirstVertex; std::vector<fyprt_vertex> hostVerts;
     std::vector<uint32_t> topoTris; std::vector<fyprt_mesh> topoMeshes; std::vector<fyprt_material> topoMats; uint32_t vertexCount = 0; bool prebuiltLightTrees = false;
     bool hostBvhStale = false;                      // the device tree was refitted: fyprt_export_bvh reads it back first
+    bool nodeBoxValid = false;                      // nodeBox holds every node's exact box (a refit pass wrote it; a host-built tree has none yet)
     bool hostVertsStale = false;                    // world vertices were recomputed on the device: the host copy only follows for emissive meshes
     DevBuf<float4> nodes, leafTris, triPos, triShade, mats; DevBuf<DevTexture> texTable; std::vector<DevBuf<uint32_t>> texPixels;
     DevBuf<uint32_t> emissive; DevBuf<float4> lightRecs; DevBuf<DevLTNode> ltTlas, ltBlas; DevBuf<uint32_t> ltFirst, ltCount, ltRoot, ltLeafOfTri;
@@ -160,6 +162,9 @@ struct fyprt_context {
     // the call's device scratch, grown on demand and kept (per-material flags, workgroup counts + offsets, reassigned triangle ranges)
     std::vector<uint32_t> hostEmissive; bool emissiveExplicit = false;
     DevBuf<uint32_t> matFlags, emCounts; DevBuf<uint4> matRanges;
+    // fyprt_append_meshes / fyprt_append_textures: the scene arrays grow in place (DevBuf::cap, grow_buffer); the nodes a graft refits
+    // (rt_graft.h), grown on demand and kept; the texture table as uploaded, which a longer one starts from
+    DevBuf<uint32_t> graftList; std::vector<DevTexture> texHost;
     DevBuf<unsigned long long> rayCounter;
     DevScene dsc{}; DevCamera dcam{};
     rth::SceneBVH hostBvh; rth::LightTrees hostLt; uint32_t meshCount = 0;
@@ -269,6 +274,19 @@ template <class T> static int alloc_upload(fyprt_context* c, DevBuf<T>& b, const
 template <class T> static int alloc_zeroed(fyprt_context* c, DevBuf<T>& b, size_t count) {
     HIPCHK(c, b.alloc(count));
     HIPCHK(c, hipMemsetAsync(b.p, 0, b.bytes(), c->stream));
+    return FYPRT_OK;
+}
+
+// `b` grown to `count` elements for an append (fyprt_append_meshes): within the capacity nothing moves; beyond it the capacity at least
+// doubles and (`move`) the old contents move device to device.  All streams are idle; complete on return.
+template <class T> static int grow_buffer(fyprt_context* c, DevBuf<T>& b, size_t count, bool move = true) {
+    if (c->hostOnly) { b.n = b.cap = count; return FYPRT_OK; }
+    if (count <= b.cap) { b.n = count; return FYPRT_OK; }
+    DevBuf<T> nb;
+    HIPCHK(c, nb.alloc(std::max(count, 2 * b.cap)));
+    if (move && b.n) { HIPCHK(c, hipMemcpyAsync(nb.p, b.p, b.bytes(), hipMemcpyDeviceToDevice, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream)); }
+    nb.n = count;
+    b = std::move(nb);
     return FYPRT_OK;
 }
 
@@ -452,20 +470,25 @@ static int run_refit(fyprt_context* c) {
         if (count) hipLaunchKernelGGL(k_refit_level, dim3((count + 127u) / 128u), dim3(128), 0, c->stream, c->nodes.p, c->levelNodes.p + first, count, c->leafTris.p, c->triPos.p, c->nodeBox.p);
     }
     HIPCHK(c, hipGetLastError());
+    c->nodeBoxValid = true;
     return FYPRT_OK;
 }
 
 // Device builder (tuning key 12, rt_lbvh.h): Morton keys -> radix sort -> Karras radix tree -> BFS collapse into 4-wide nodes ->
-// level counts.  Leaves c->nodes (topology only), c->leafTris (triangle indices in sorted order) and the host copy of the
-// topology (for export and the level grouping); boxes come from run_refit.  kLbvhTooDeep: more than 31 wide levels.
+// level counts, over the triangle range [firstTri, firstTri + nT) — the whole scene for an upload, the appended triangles for
+// fyprt_append_meshes; `verts` span the range's Morton grid.  Destination: the leaf records (triangle indices in sorted order) go to
+// c->leafTris from record `leafBase` on, where the caller has made room for nT of them; the nodes (topology only, references relative
+// to the tree: node 0 is its root, leaf record 0 is record leafBase) are left in the scratch `wide`, from where the caller takes
+// them.  Boxes come from the refit pass.  kLbvhTooDeep: more than 31 wide levels.
 constexpr int kLbvhTooDeep = -1000;
+struct LbvhTree { uint32_t nodes = 0, levels = 0; };
 static int env_int(const char* name, int fallback) { const char* v = std::getenv(name); return (v && *v) ? std::atoi(v) : fallback; }
-static int build_device_lbvh(fyprt_context* c, const fyprt_vertex* verts, uint32_t nV, uint32_t nT, bool ploc) {
+static int build_device_lbvh(fyprt_context* c, const fyprt_vertex* verts, uint32_t nV, uint32_t firstTri, uint32_t nT, bool ploc, size_t leafBase, DevBuf<float4>& wide, LbvhTree* tree) {
     float lo[3] = {3.402823466e+38f, 3.402823466e+38f, 3.402823466e+38f}, hi[3] = {-3.402823466e+38f, -3.402823466e+38f, -3.402823466e+38f};
     for (uint32_t i = 0; i < nV; ++i) for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], verts[i].position[a]); hi[a] = std::max(hi[a], verts[i].position[a]); }
     float3 l3 = make_float3(lo[0], lo[1], lo[2]), ie = make_float3(hi[0] > lo[0] ? 1.0f / (hi[0] - lo[0]) : 0.0f, hi[1] > lo[1] ? 1.0f / (hi[1] - lo[1]) : 0.0f, hi[2] > lo[2] ? 1.0f / (hi[2] - lo[2]) : 0.0f);
     // scratch of the build, freed on every way out
-    DevBuf<unsigned long long> keysA, keysB; DevBuf<uint32_t> valsA, valsB, parentOfNode, parentOfLeaf, arrived; DevBuf<float> box; DevBuf<RadixNode> radix; DevBuf<CollapseItem> qA, qB; DevBuf<uint32_t> counters; DevBuf<float4> wide; DevBuf<uint8_t> temp;
+    DevBuf<unsigned long long> keysA, keysB; DevBuf<uint32_t> valsA, valsB, parentOfNode, parentOfLeaf, arrived; DevBuf<float> box; DevBuf<RadixNode> radix; DevBuf<CollapseItem> qA, qB; DevBuf<uint32_t> counters; DevBuf<uint8_t> temp;
     DevBuf<uint32_t> clA, clB, nearest; DevBuf<uint8_t> keep, selTemp;                          // PLOC
     if (!ploc) {
         HIPCHK(c, parentOfNode.alloc(nT)); HIPCHK(c, parentOfLeaf.alloc(nT)); HIPCHK(c, arrived.alloc(nT)); HIPCHK(c, box.alloc((size_t)nT * 6));
@@ -475,7 +498,7 @@ static int build_device_lbvh(fyprt_context* c, const fyprt_vertex* verts, uint32
     }
     HIPCHK(c, keysA.alloc(nT)); HIPCHK(c, keysB.alloc(nT)); HIPCHK(c, valsA.alloc(nT)); HIPCHK(c, valsB.alloc(nT)); HIPCHK(c, radix.alloc(nT)); HIPCHK(c, qA.alloc(nT)); HIPCHK(c, qB.alloc(nT));
     HIPCHK(c, counters.alloc(4)); HIPCHK(c, wide.alloc((size_t)nT * 4));
-    hipLaunchKernelGGL(k_lbvh_keys, dim3((nT + 255u) / 256u), dim3(256), 0, c->stream, c->triPos.p, nT, l3, ie, keysA.p, valsA.p);
+    hipLaunchKernelGGL(k_lbvh_keys, dim3((nT + 255u) / 256u), dim3(256), 0, c->stream, c->triPos.p, firstTri, nT, l3, ie, keysA.p, valsA.p);
     size_t tempBytes = 0;
     HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(nullptr, tempBytes, keysA.p, keysB.p, valsA.p, valsB.p, (int)nT, 0, 63, c->stream));
     HIPCHK(c, temp.alloc(tempBytes));
@@ -512,7 +535,6 @@ static int build_device_lbvh(fyprt_context* c, const fyprt_vertex* verts, uint32
         HIPCHK(c, hipMemcpy(&rootNode, cur, 4, hipMemcpyDeviceToHost));
         c->lastBuildRounds = rounds;
     }
-    HIPCHK(c, c->leafTris.alloc((size_t)nT * 3));
     // BFS collapse, one launch per level; the nodes of a level are contiguous: [levelFirst[l], levelFirst[l + 1])
     const CollapseItem rootItem{rootNode, 0u, 0u};
     uint32_t h_counters[2] = {1u, 0u};
@@ -522,7 +544,7 @@ static int build_device_lbvh(fyprt_context* c, const fyprt_vertex* verts, uint32
     uint32_t nIn = 1, total = 1;
     CollapseItem *in = qA.p, *out = qB.p;
     while (nIn) {
-        hipLaunchKernelGGL(k_lbvh_collapse, dim3((nIn + 127u) / 128u), dim3(128), 0, c->stream, (const RadixNode*)radix.p, (const float*)box.p, (const uint32_t*)valsB.p, (const CollapseItem*)in, nIn, out, counters.p, wide.p, c->leafTris.p);
+        hipLaunchKernelGGL(k_lbvh_collapse, dim3((nIn + 127u) / 128u), dim3(128), 0, c->stream, (const RadixNode*)radix.p, (const float*)box.p, (const uint32_t*)valsB.p, (const CollapseItem*)in, nIn, out, counters.p, wide.p, c->leafTris.p + leafBase * 3);
         HIPCHK(c, hipMemcpyAsync(h_counters, counters.p, 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         levelFirst.push_back(total);
@@ -538,13 +560,9 @@ static int build_device_lbvh(fyprt_context* c, const fyprt_vertex* verts, uint32
         if (count) hipLaunchKernelGGL(k_lbvh_levels, dim3((count + 127u) / 128u), dim3(128), 0, c->stream, wide.p, first, count);
     }
     HIPCHK(c, hipGetLastError());
-    if (total >= rth::kMaxNodes) return c->fail(FYPRT_EINVAL, "fyprt_upload_scene: too many nodes for the node reference range");
-    HIPCHK(c, c->nodes.alloc((size_t)total * 4));
-    HIPCHK(c, hipMemcpyAsync(c->nodes.p, wide.p, (size_t)total * 64, hipMemcpyDeviceToDevice, c->stream));
-    rth::SceneBVH& b = c->hostBvh; b = rth::SceneBVH();
-    b.nodes.resize(total); b.tris.resize(nT); b.rootRef = 0; b.levels = nLevels;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return download_nodes(c);                                                                        // topology + meta: the level grouping needs it
+    if (total >= rth::kMaxNodes) return c->fail(FYPRT_EINVAL, "device builder: too many nodes for the node reference range");
+    tree->nodes = total; tree->levels = nLevels;
+    return FYPRT_OK;
 }
 
 // The host light trees (c->hostLt) onto the device, with the emitter -> TLAS-leaf table, and into the scene descriptor.
@@ -573,6 +591,63 @@ static int upload_light_trees(fyprt_context* c, uint32_t nT, uint32_t nM) {
     return FYPRT_OK;
 }
 
+// The nodes of the host's copy of the tree grouped by level (levels = 1 first) for the refit pass: c->levelOffset and, on the device,
+// c->levelNodes — 4 bytes per node.  `keep`: the buffer grows within its capacity (an append) instead of being allocated to size.
+static int upload_level_grouping(fyprt_context* c, bool keep) {
+    const std::vector<rth::Node>& hn = c->hostBvh.nodes;
+    const uint32_t L = c->hostBvh.levels;
+    c->levelOffset.assign(L + 2, 0);
+    for (const rth::Node& n : hn) c->levelOffset[(n.meta >> 3) + 1]++;
+    for (uint32_t l = 1; l <= L + 1; ++l) c->levelOffset[l] += c->levelOffset[l - 1];      // levelOffset[l] = first slot of level l (1-based levels)
+    std::vector<uint32_t> order(hn.size()), fill(c->levelOffset.begin(), c->levelOffset.end());
+    for (uint32_t i = 0; i < (uint32_t)hn.size(); ++i) order[fill[hn[i].meta >> 3]++] = i;
+    if (!keep) return alloc_upload(c, c->levelNodes, order.data(), order.size());
+    TRY(grow_buffer(c, c->levelNodes, order.size(), false));
+    return upload(c, c->levelNodes.p, order.data(), c->levelNodes.bytes());
+}
+
+// The acceleration structure of the scene whose per-triangle records are on the device (c->triPos): built on the host (binned SAH +
+// collapse, bvh_build.cpp) or, with tuning key 12, on the device (LBVH / PLOC + collapse, rt_lbvh.h, boxes by the refit pass).  Leaves
+// c->nodes, c->leafTris, the level grouping, c->nodeBox and the host's copy c->hostBvh.  `what`: the caller's name for error texts.
+static int build_scene_tree(fyprt_context* c, const char* what, const fyprt_vertex* verts, uint32_t nV, const uint8_t* tb, uint32_t stride, const fyprt_mesh* meshes, uint32_t nM, uint32_t nT) {
+    bool deviceBuild = !c->hostOnly && c->tuning[K_BUILDER] != 0 && nT > 4;
+    if (deviceBuild) {
+        DevBuf<float4> wide; LbvhTree tree;
+        HIPCHK(c, c->leafTris.alloc((size_t)nT * 3));
+        const int rc = build_device_lbvh(c, verts, nV, 0, nT, c->tuning[K_BUILDER] == 2, 0, wide, &tree);
+        if (rc == kLbvhTooDeep) deviceBuild = false;                      // > 31 wide levels: the host builder bounds them
+        else if (rc != FYPRT_OK) return rc;
+        else {
+            HIPCHK(c, c->nodes.alloc((size_t)tree.nodes * 4));
+            HIPCHK(c, hipMemcpyAsync(c->nodes.p, wide.p, (size_t)tree.nodes * 64, hipMemcpyDeviceToDevice, c->stream));
+            rth::SceneBVH& b = c->hostBvh; b = rth::SceneBVH();
+            b.nodes.resize(tree.nodes); b.tris.resize(nT); b.rootRef = 0; b.levels = tree.levels;
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            TRY(download_nodes(c));                                        // topology + meta: the level grouping needs it
+        }
+    }
+    if (!deviceBuild) {
+        rth::BuildSceneBVH(verts, tb, stride, meshes, nM, c->hostBvh);
+        if (c->hostBvh.levels > rth::kStackBudget || c->hostBvh.nodes.size() >= (size_t)rth::kMaxNodes)
+            return c->fail(FYPRT_EINVAL, std::string(what) + ": acceleration structure (" + std::to_string(c->hostBvh.levels) + " levels, " +
+                           std::to_string(c->hostBvh.nodes.size()) + " nodes) exceeds the traversal stack / node index range");
+        std::vector<rth::Node> dn;                                        // the array in device form (inner references = byte offsets)
+        if (!c->hostOnly) { dn = c->hostBvh.nodes; rth::nodes_to_device_form(dn.data(), dn.size()); }
+        TRY(alloc_upload(c, c->nodes, dn.data(), c->hostBvh.nodes.size() * 4));
+        TRY(alloc_upload(c, c->leafTris, c->hostBvh.tris.data(), c->hostBvh.tris.size() * 3));
+    }
+    // refit support: the nodes grouped by level, a box per node
+    TRY(upload_level_grouping(c, false)); HIPCHK(c, c->nodeBox.alloc(c->hostBvh.nodes.size() * 2, c->hostOnly));
+    c->hostBvhStale = false; c->nodeBoxValid = deviceBuild;
+    if (deviceBuild) {                     // the device builder leaves boxes and quantisation to the refit pass
+        TRY(run_refit(c));
+        HIPCHK(c, sync_all(c));
+        TRY(download_nodes(c));
+        HIPCHK(c, hipMemcpy(c->hostBvh.tris.data(), c->leafTris.p, c->hostBvh.tris.size() * 48, hipMemcpyDeviceToHost));
+    }
+    return FYPRT_OK;
+}
+
 int fyprt_upload_scene(fyprt_context* c, const fyprt_scene_desc* s) {
     if (!c || !s) return FYPRT_EINVAL;
     if ((s->triangle_count && (!s->triangles || !s->vertices || s->triangle_stride < 16)) || (s->mesh_count && !s->meshes) ||
@@ -596,20 +671,6 @@ int fyprt_upload_scene(fyprt_context* c, const fyprt_scene_desc* s) {
         covered += me.triangle_count;
     }
     if (covered != s->triangle_count) return c->fail(FYPRT_EINVAL, "fyprt_upload_scene: meshes must partition the triangle list");
-    // acceleration structure (ours): built on the host (binned SAH + collapse, bvh_build.cpp) or, with tuning key 12, on the
-    // device (LBVH + collapse, rt_lbvh.h — further down, once the per-triangle records are on the device)
-    bool deviceBuild = !c->hostOnly && c->tuning[K_BUILDER] != 0 && s->triangle_count > 4;
-    auto hostBuild = [&]() -> int {
-        rth::BuildSceneBVH(s->vertices, tb, s->triangle_stride, s->meshes, s->mesh_count, c->hostBvh);
-        if (c->hostBvh.levels > rth::kStackBudget || c->hostBvh.nodes.size() >= (size_t)rth::kMaxNodes)
-            return c->fail(FYPRT_EINVAL, "fyprt_upload_scene: acceleration structure (" + std::to_string(c->hostBvh.levels) + " levels, " +
-                           std::to_string(c->hostBvh.nodes.size()) + " nodes) exceeds the traversal stack / node index range");
-        std::vector<rth::Node> dn;                                        // the array in device form (inner references = byte offsets)
-        if (!c->hostOnly) { dn = c->hostBvh.nodes; rth::nodes_to_device_form(dn.data(), dn.size()); }
-        TRY(alloc_upload(c, c->nodes, dn.data(), c->hostBvh.nodes.size() * 4));
-        return alloc_upload(c, c->leafTris, c->hostBvh.tris.data(), c->hostBvh.tris.size() * 3);
-    };
-    if (!deviceBuild) TRY(hostBuild());
     // per-triangle gather records
     const uint32_t nT = s->triangle_count;
     std::vector<float> pos((size_t)nT * 12), shade((size_t)nT * 16);
@@ -627,35 +688,16 @@ int fyprt_upload_scene(fyprt_context* c, const fyprt_scene_desc* s) {
         q[12] = b.uv[1]; q[13] = cc.uv[0]; q[14] = cc.uv[1]; q[15] = matBits;
     }
     TRY(alloc_upload(c, c->triPos, pos.data(), (size_t)nT * 3)); TRY(alloc_upload(c, c->triShade, shade.data(), (size_t)nT * 4));
-    // refit support: vertices + per-triangle indices on the device, nodes grouped by level (levels = 1 first)
-    c->vertexCount = s->vertex_count; c->hostBvhStale = false; c->hostVertsStale = false;
+    // acceleration structure (ours), on the host or, with tuning key 12, on the device from the records above
+    TRY(build_scene_tree(c, "fyprt_upload_scene", s->vertices, s->vertex_count, tb, s->triangle_stride, s->meshes, s->mesh_count, nT));
+    // refit support: vertices + per-triangle indices on the device
+    c->vertexCount = s->vertex_count; c->hostVertsStale = false;
     c->hostVerts.assign(s->vertices, s->vertices + s->vertex_count); c->objVerts.release(); c->meshFirstVertex.clear();
     c->topoTris.resize((size_t)nT * 4);
     for (uint32_t i = 0; i < nT; ++i) std::memcpy(&c->topoTris[(size_t)i * 4], tri(i), 16);
-    if (deviceBuild) {
-        const int rc = build_device_lbvh(c, s->vertices, s->vertex_count, nT, c->tuning[K_BUILDER] == 2);
-        if (rc == kLbvhTooDeep) { deviceBuild = false; TRY(hostBuild()); }   // > 31 wide levels: the host builder bounds them
-        else if (rc != FYPRT_OK) return rc;
-    }
     c->topoMeshes.assign(s->meshes, s->meshes + s->mesh_count); c->topoMats.assign(s->materials, s->materials + s->material_count);
     c->prebuiltLightTrees = s->light_trees && s->light_trees->tlas_nodes;
-    {
-        const std::vector<rth::Node>& hn = c->hostBvh.nodes;
-        const uint32_t L = c->hostBvh.levels;
-        c->levelOffset.assign(L + 2, 0);
-        for (const rth::Node& n : hn) c->levelOffset[(n.meta >> 3) + 1]++;
-        for (uint32_t l = 1; l <= L + 1; ++l) c->levelOffset[l] += c->levelOffset[l - 1];      // levelOffset[l] = first slot of level l (1-based levels)
-        std::vector<uint32_t> order(hn.size()), fill(c->levelOffset.begin(), c->levelOffset.end());
-        for (uint32_t i = 0; i < (uint32_t)hn.size(); ++i) order[fill[hn[i].meta >> 3]++] = i;
-        TRY(alloc_upload(c, c->dverts, s->vertices, s->vertex_count)); TRY(alloc_upload(c, c->triIdx, c->topoTris.data(), nT));
-        TRY(alloc_upload(c, c->levelNodes, order.data(), order.size())); HIPCHK(c, c->nodeBox.alloc(hn.size() * 2, c->hostOnly));
-    }
-    if (deviceBuild) {                     // the device builder leaves boxes and quantisation to the refit pass
-        TRY(run_refit(c));
-        HIPCHK(c, sync_all(c));
-        TRY(download_nodes(c));
-        HIPCHK(c, hipMemcpy(c->hostBvh.tris.data(), c->leafTris.p, c->hostBvh.tris.size() * 48, hipMemcpyDeviceToHost));
-    }
+    TRY(alloc_upload(c, c->dverts, s->vertices, s->vertex_count)); TRY(alloc_upload(c, c->triIdx, c->topoTris.data(), nT));
     // materials (Material.cuh:7-16 -> 3 quads)
     std::vector<float> mats; std::vector<char> emissiveMat;
     pack_materials(s->materials, s->material_count, mats, emissiveMat);
@@ -670,6 +712,7 @@ int fyprt_upload_scene(fyprt_context* c, const fyprt_scene_desc* s) {
         tt[i] = DevTexture{c->texPixels[i].p, t.width, t.height, 0};
     }
     TRY(alloc_upload(c, c->texTable, tt.data(), s->texture_count));
+    c->texHost.swap(tt);
     // emissive list (Scene::InitSceneEmissiveTriangles, Scene.cpp:209-221)
     std::vector<uint32_t> em;
     if (s->emissive_triangles) em.assign(s->emissive_triangles, s->emissive_triangles + s->emissive_count);
@@ -824,27 +867,29 @@ int fyprt_update_transforms(fyprt_context* c, const uint32_t* mesh_indices, cons
     return FYPRT_OK;
 }
 
-// The emissive list derived ON THE DEVICE from the per-material flags (rt_materials.h): count per workgroup, scan, scatter in ascending
-// triangle order.  Leaves c->emissive sized to the count, which comes back in one 4-byte read.
-static int derive_emissive_on_device(fyprt_context* c, const std::vector<char>& emissiveMat, uint32_t nT, uint32_t* count) {
-    const uint32_t nMat = (uint32_t)emissiveMat.size();
+// The emissive list derived ON THE DEVICE from the per-material flags (rt_materials.h) over the triangles [first, nT): count per
+// workgroup, scan, scatter in ascending triangle order.  `keep` = 0: the list is the range's (a material edit: first = 0) and c->emissive
+// is sized to the count; otherwise the range's emitters follow the first `keep` entries of the list (an append).  `count`: the range's
+// emitters, which come back in one 4-byte read.
+static int derive_emissive_on_device(fyprt_context* c, const std::vector<char>& emissiveMat, uint32_t first, uint32_t nT, uint32_t keep, uint32_t* count) {
+    const uint32_t nMat = (uint32_t)emissiveMat.size(), n = nT - first;
     *count = 0;
-    if (nT == 0 || nMat == 0) { c->emissive.release(); return FYPRT_OK; }
-    const uint32_t groups = std::min<uint32_t>(kEmMaxGroups, (nT + kEmMinChunk - 1u) / kEmMinChunk);
-    const uint32_t perGroup = (((nT + groups - 1u) / groups + kBlock - 1u) / kBlock) * kBlock;     // whole tiles, groups * perGroup >= nT
+    if (n == 0 || nMat == 0) { if (!keep) c->emissive.release(); return FYPRT_OK; }
+    const uint32_t groups = std::min<uint32_t>(kEmMaxGroups, (n + kEmMinChunk - 1u) / kEmMinChunk);
+    const uint32_t perGroup = (((n + groups - 1u) / groups + kBlock - 1u) / kBlock) * kBlock;     // whole tiles, groups * perGroup >= n
     std::vector<uint32_t> flags(emissiveMat.begin(), emissiveMat.end());
     if (c->matFlags.n < nMat) HIPCHK(c, c->matFlags.alloc(nMat));
     if (c->emCounts.n < 2u * kEmMaxGroups + 1u) HIPCHK(c, c->emCounts.alloc(2u * kEmMaxGroups + 1u));
     TRY(upload(c, c->matFlags.p, flags.data(), (size_t)nMat * 4));
     uint32_t* counts = c->emCounts.p; uint32_t* offsets = c->emCounts.p + kEmMaxGroups;
-    hipLaunchKernelGGL(k_emissive_count, dim3(groups), dim3(kBlock), 0, c->stream, c->triIdx.p, c->matFlags.p, nMat, nT, perGroup, counts);
+    hipLaunchKernelGGL(k_emissive_count, dim3(groups), dim3(kBlock), 0, c->stream, c->triIdx.p, c->matFlags.p, nMat, first, nT, perGroup, counts);
     hipLaunchKernelGGL(k_emissive_scan, dim3(1), dim3(kBlock), 0, c->stream, counts, groups, offsets);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(count, offsets + groups, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, c->emissive.alloc(*count));
+    if (keep) TRY(grow_buffer(c, c->emissive, (size_t)keep + *count)); else HIPCHK(c, c->emissive.alloc(*count));
     if (*count) {
-        hipLaunchKernelGGL(k_emissive_scatter, dim3(groups), dim3(kBlock), 0, c->stream, c->triIdx.p, c->matFlags.p, nMat, nT, perGroup, offsets, c->emissive.p, *count);
+        hipLaunchKernelGGL(k_emissive_scatter, dim3(groups), dim3(kBlock), 0, c->stream, c->triIdx.p, c->matFlags.p, nMat, first, nT, perGroup, offsets, c->emissive.p + keep, *count);
         HIPCHK(c, hipGetLastError());
     }
     return FYPRT_OK;
@@ -964,7 +1009,7 @@ int fyprt_update_materials(fyprt_context* c, const fyprt_material* materials, ui
         HIPCHK(c, c->emissive.alloc(nE, true));
     } else {
         c->hostEmissive.clear();
-        TRY(derive_emissive_on_device(c, emissiveMat, nT, &nE));
+        TRY(derive_emissive_on_device(c, emissiveMat, 0, nT, 0, &nE));
     }
     c->emissiveExplicit = emissive_triangles != nullptr;
     c->dsc.emissive = c->emissive.p; c->dsc.emissiveCount = nE;
@@ -990,6 +1035,161 @@ int fyprt_update_materials(fyprt_context* c, const fyprt_material* materials, ui
         TRY(rebuild_light_trees(c, c->hostVerts.data(), setChanged ? nullptr : touched.data()));
     }
     if (!c->hostOnly) HIPCHK(c, sync_all(c));
+    return FYPRT_OK;
+}
+
+// "Import Mesh" (WalnutApp.cpp:668-693 -> Scene::CreateNewMeshInScene, Scene.cpp:241-290, on Scene::AddNewMeshToScene, Scene.cpp:9-92):
+// vertices, triangles and meshes are appended, nothing that exists moves.  The context ends in the state fyprt_upload_scene reaches
+// with the combined description, except for the acceleration structure, which takes a sub-tree over the new triangles at its root
+// (rt_graft.h).  Of the old scene nothing crosses the bus but the level grouping (4 bytes per node): the scene arrays grow in place
+// or move device to device, the appended range goes through k_refresh_triangles, the emissive list is extended by the ordered
+// compaction over the range, the light records are rebuilt by their kernel, and the host builds the new meshes' light trees + the TLAS.
+#include "rt_graft.h"
+
+int fyprt_append_meshes(fyprt_context* c, const fyprt_vertex* vertices, uint32_t vertex_count, const void* triangles, uint32_t triangle_count, uint32_t triangle_stride,
+                        const fyprt_mesh* meshes, uint32_t mesh_count, const fyprt_vertex* object_vertices, const uint32_t* mesh_first_vertex) {
+    if (!c) return FYPRT_EINVAL;
+    if ((vertex_count && !vertices) || (triangle_count && !triangles) || (mesh_count && !meshes) || (object_vertices && !mesh_first_vertex))
+        return c->fail(FYPRT_EINVAL, "fyprt_append_meshes: NULL array with non-zero count");
+    if (triangle_count && triangle_stride < 16) return c->fail(FYPRT_EINVAL, "fyprt_append_meshes: triangle stride below 16");
+    const uint32_t V0 = c->vertexCount, T0 = (uint32_t)(c->topoTris.size() / 4), M0 = (uint32_t)c->topoMeshes.size(), nMat = (uint32_t)c->topoMats.size();
+    const uint64_t V64 = (uint64_t)V0 + vertex_count, T64 = (uint64_t)T0 + triangle_count;
+    if (V64 > 0xFFFFFFFFull || T64 > 0x3FFFFFFFull) return c->fail(FYPRT_EINVAL, "fyprt_append_meshes: too many vertices / triangles");
+    const uint32_t V = (uint32_t)V64, T = (uint32_t)T64, M = M0 + mesh_count;
+    const uint8_t* tb = (const uint8_t*)triangles;
+    auto tri = [&](uint32_t i) { return reinterpret_cast<const uint32_t*>(tb + (size_t)i * triangle_stride); };
+    for (uint32_t i = 0; i < triangle_count; ++i)
+        if (tri(i)[0] >= V || tri(i)[1] >= V || tri(i)[2] >= V) return c->fail(FYPRT_EINVAL, "fyprt_append_meshes: triangle " + std::to_string(i) + " references a vertex out of range");
+    for (uint32_t i = 0; i < triangle_count; ++i)
+        if ((int32_t)tri(i)[3] < 0 || tri(i)[3] >= nMat) return c->fail(FYPRT_EINVAL, "fyprt_append_meshes: triangle " + std::to_string(i) + " references a material outside the table");
+    for (uint32_t m = 0; m < mesh_count; ++m)
+        if (meshes[m].material_index < 0 || (uint32_t)meshes[m].material_index >= nMat) return c->fail(FYPRT_EINVAL, "fyprt_append_meshes: mesh " + std::to_string(m) + " references a material outside the table");
+    {
+        uint64_t next = T0;
+        for (uint32_t m = 0; m < mesh_count; ++m) {
+            if (meshes[m].first_triangle != next) return c->fail(FYPRT_EINVAL, "fyprt_append_meshes: the meshes must partition the appended triangle range in order");
+            next += meshes[m].triangle_count;
+        }
+        if (next != T64) return c->fail(FYPRT_EINVAL, "fyprt_append_meshes: the meshes must partition the appended triangle range in order");
+    }
+    if (object_vertices) {
+        if (mesh_first_vertex[0] != V0 || mesh_first_vertex[mesh_count] != V) return c->fail(FYPRT_EINVAL, "fyprt_append_meshes: mesh vertex ranges must span the appended vertices");
+        for (uint32_t m = 0; m < mesh_count; ++m) if (mesh_first_vertex[m] > mesh_first_vertex[m + 1]) return c->fail(FYPRT_EINVAL, "fyprt_append_meshes: mesh vertex ranges out of order");
+        for (uint32_t m = 0; m < mesh_count; ++m)
+            for (uint32_t t = meshes[m].first_triangle - T0; t < meshes[m].first_triangle - T0 + meshes[m].triangle_count; ++t)
+                for (int k = 0; k < 3; ++k) if (tri(t)[k] < mesh_first_vertex[m] || tri(t)[k] >= mesh_first_vertex[m + 1]) return c->fail(FYPRT_EINVAL, "fyprt_append_meshes: triangle " + std::to_string(t) + " uses a vertex outside its mesh's range");
+    }
+    if (!c->haveScene) return c->fail(FYPRT_ESTATE, "fyprt_append_meshes before fyprt_upload_scene");
+    if (c->prebuiltLightTrees) return c->fail(FYPRT_ESTATE, "fyprt_append_meshes: the scene was uploaded with prebuilt light trees; upload it again instead");
+    if (triangle_count == 0 && mesh_count == 0) return FYPRT_OK;
+    if (!c->hostOnly) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c)); }
+    c->frameComplete = false;                  // as fyprt_upload_scene
+    c->drop_history(); c->release_snapshot();
+
+    // 1. the host's copies: vertices, topology.  The sub-tree's host builder and the new meshes' light trees read the vertices the new
+    // triangles use: after device transform edits the old ones come back first if any is among them.
+    bool usesOld = false;
+    for (uint32_t i = 0; i < triangle_count && !usesOld; ++i) usesOld = tri(i)[0] < V0 || tri(i)[1] < V0 || tri(i)[2] < V0;
+    if (usesOld && c->hostVertsStale && !c->hostOnly && V0) {
+        HIPCHK(c, hipMemcpy(c->hostVerts.data(), c->dverts.p, (size_t)V0 * sizeof(fyprt_vertex), hipMemcpyDeviceToHost));
+        c->hostVertsStale = false;
+    }
+    c->hostVerts.insert(c->hostVerts.end(), vertices, vertices + vertex_count);
+    c->topoTris.resize((size_t)T * 4);
+    for (uint32_t i = 0; i < triangle_count; ++i) std::memcpy(&c->topoTris[(size_t)(T0 + i) * 4], tri(i), 16);
+    c->topoMeshes.insert(c->topoMeshes.end(), meshes, meshes + mesh_count);
+    c->vertexCount = V; c->meshCount = M;
+    // 2. the device's: vertices and triangle indices cross the bus, the per-triangle records are computed there
+    static_assert(sizeof(DevVertex) == sizeof(fyprt_vertex), "vertex layout");
+    TRY(grow_buffer(c, c->dverts, V)); TRY(grow_buffer(c, c->triIdx, T)); TRY(grow_buffer(c, c->triPos, (size_t)T * 3)); TRY(grow_buffer(c, c->triShade, (size_t)T * 4));
+    if (!c->hostOnly) {
+        TRY(upload(c, c->dverts.p + V0, vertices, (size_t)vertex_count * sizeof(fyprt_vertex)));
+        TRY(upload(c, c->triIdx.p + T0, c->topoTris.data() + (size_t)T0 * 4, (size_t)triangle_count * 16));
+        if (triangle_count) hipLaunchKernelGGL(k_refresh_triangles, dim3((triangle_count + 255u) / 256u), dim3(256), 0, c->stream, c->dverts.p, c->triIdx.p + T0, c->triPos.p + (size_t)T0 * 3, c->triShade.p + (size_t)T0 * 4, triangle_count);
+        HIPCHK(c, hipGetLastError());
+    }
+    // 3. object-space vertices: extended with the copy the context holds; without new ones the copy goes, as an upload drops it
+    if (object_vertices && !c->meshFirstVertex.empty()) {
+        TRY(grow_buffer(c, c->objVerts, V));
+        TRY(upload(c, c->objVerts.p + V0, object_vertices, (size_t)vertex_count * sizeof(fyprt_vertex)));
+        c->meshFirstVertex.insert(c->meshFirstVertex.end(), mesh_first_vertex + 1, mesh_first_vertex + mesh_count + 1);
+    } else if (!object_vertices) { c->objVerts.release(); c->meshFirstVertex.clear(); }
+    // 4. the acceleration structure: the graft, or the tree of the combined scene when the graft would be too deep / too large
+    if (triangle_count) {
+        int rc = graft_append(c, vertices, vertex_count, T0, triangle_count, meshes, mesh_count);
+        if (rc == kGraftRebuild) {
+            if (c->hostVertsStale && !c->hostOnly && V0) {             // the host builder reads every vertex
+                HIPCHK(c, hipStreamSynchronize(c->stream));
+                HIPCHK(c, hipMemcpy(c->hostVerts.data(), c->dverts.p, (size_t)V0 * sizeof(fyprt_vertex), hipMemcpyDeviceToHost));
+                c->hostVertsStale = false;
+            }
+            rc = build_scene_tree(c, "fyprt_append_meshes", c->hostVerts.data(), V, (const uint8_t*)c->topoTris.data(), 16, c->topoMeshes.data(), M, T);
+        }
+        if (rc != FYPRT_OK) return rc;
+    }
+    DevScene& d = c->dsc;
+    d.nodes = c->nodes.p; d.leafTris = c->leafTris.p; d.rootRef = rth::device_ref(c->hostBvh.rootRef); d.triCount = T;
+    d.triPos = c->triPos.p; d.triShade = c->triShade.p;
+    // 5. lights.  The emissive list: the old one followed by the appended triangles whose material emits, in ascending order
+    std::vector<char> emissiveMat(nMat);
+    for (uint32_t i = 0; i < nMat; ++i) emissiveMat[i] = is_emissive(c->topoMats[i]);
+    std::vector<uint32_t> tail;
+    for (uint32_t i = 0; i < triangle_count; ++i) if (emissiveMat[tri(i)[3]]) tail.push_back(T0 + i);
+    const uint32_t nE0 = c->hostOnly ? (uint32_t)c->hostEmissive.size() : d.emissiveCount;
+    if (c->hostEmissive.size() == nE0) c->hostEmissive.insert(c->hostEmissive.end(), tail.begin(), tail.end());   // (a device context keeps the copy of a list it was handed only)
+    if (!tail.empty()) {
+        const uint32_t nE = nE0 + (uint32_t)tail.size();
+        if (c->hostOnly) HIPCHK(c, c->emissive.alloc(nE, true));
+        else {
+            uint32_t found = 0;
+            TRY(derive_emissive_on_device(c, emissiveMat, T0, T, nE0, &found));
+            if (found != tail.size()) return c->fail(FYPRT_EHIP, "fyprt_append_meshes: the device's emissive list disagrees with the host's");
+        }
+        d.emissive = c->emissive.p; d.emissiveCount = nE;
+        HIPCHK(c, c->lightRecs.alloc((size_t)nE * 3, c->hostOnly));
+        d.lightRecs = c->lightRecs.p;
+        if (!c->hostOnly) { hipLaunchKernelGGL(k_build_light_records, dim3((nE + 255u) / 256u), dim3(256), 0, c->stream, d, c->lightRecs.p); HIPCHK(c, hipGetLastError()); }
+    }
+    // ... and the light trees, which hang on the MESH's material: the new meshes' trees behind the old ones, then the TLAS
+    {
+        rth::LightTrees& lt = c->hostLt;
+        std::vector<uint8_t> touched(M, 0);
+        bool newLight = false;
+        for (uint32_t m = M0; m < M; ++m) {
+            const fyprt_mesh& me = c->topoMeshes[m];
+            lt.first.push_back((uint32_t)lt.blas.size()); lt.count.push_back(0u); lt.root.push_back(~0u);
+            if (!emissiveMat[me.material_index] || me.triangle_count == 0) continue;
+            lt.blas.resize(lt.blas.size() + 2u * (size_t)me.triangle_count - 1u);         // a mesh's tree has 2n - 1 nodes
+            touched[m] = 1; newLight = true;
+        }
+        if (newLight) TRY(rebuild_light_trees(c, c->hostVerts.data(), touched.data()));
+        else if (!tail.empty()) TRY(upload_light_trees(c, T, M));                          // the emitter -> TLAS-leaf table covers the new triangles
+    }
+    if (!c->hostOnly) HIPCHK(c, sync_all(c));
+    return FYPRT_OK;
+}
+
+// "Import Texture" (WalnutApp.cpp:739-754 -> Scene::CreateNewTextureInScene, Scene.cpp:228-239): the new pixel arrays are uploaded and the
+// table is extended; old pixel buffers stay where they are.
+int fyprt_append_textures(fyprt_context* c, const fyprt_texture* textures, uint32_t count) {
+    if (!c) return FYPRT_EINVAL;
+    if (count && !textures) return c->fail(FYPRT_EINVAL, "fyprt_append_textures: NULL textures with a non-zero count");
+    for (uint32_t i = 0; i < count; ++i) if (!textures[i].pixels || textures[i].width == 0 || textures[i].height == 0) return c->fail(FYPRT_EINVAL, "fyprt_append_textures: empty texture");
+    if (!c->haveScene) return c->fail(FYPRT_ESTATE, "fyprt_append_textures before fyprt_upload_scene");
+    if (count == 0) return FYPRT_OK;
+    if (!c->hostOnly) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c)); }
+    const uint32_t old = (uint32_t)c->texHost.size();
+    // a material that already pointed at one of the new slots shaded as solid colour so far: the edit changes its pixels, as a material edit does
+    for (const fyprt_material& m : c->topoMats)
+        if ((m.is_use_albedo_map & 0xFFu) && m.albedo_map_index >= old && (uint64_t)m.albedo_map_index < (uint64_t)old + count) { c->frameComplete = false; c->drop_history(); }
+    for (uint32_t i = 0; i < count; ++i) {
+        const fyprt_texture& t = textures[i];
+        c->texPixels.emplace_back();
+        TRY(alloc_upload(c, c->texPixels.back(), t.pixels, (size_t)t.width * t.height));
+        c->texHost.push_back(DevTexture{c->texPixels.back().p, t.width, t.height, 0});
+    }
+    TRY(alloc_upload(c, c->texTable, c->texHost.data(), c->texHost.size()));
+    c->dsc.textures = c->texTable.p; c->dsc.textureCount = (uint32_t)c->texHost.size();
     return FYPRT_OK;
 }
 

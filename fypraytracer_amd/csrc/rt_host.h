@@ -49,6 +49,12 @@ inline void nodes_to_host_form(Node* n, size_t count) { for (size_t i = 0; i < c
 void BuildSceneBVH(const fyprt_vertex* verts, const uint8_t* tris, uint32_t triStride, const fyprt_mesh* meshes,
                    uint32_t meshCount, SceneBVH& out);
 
+// The builder's quantiser (Collapser::quantise) for a caller's child boxes — the graft of fyprt_append_meshes on a host-only context:
+// origin, grid exponents, child planes and the child count of `n` from `count` (2..4) boxes.  The node is cleared first: child
+// references and the level count are the caller's to fill in.
+struct ChildBox { float lo[3], hi[3]; };
+void QuantiseNode(Node& n, const ChildBox* boxes, int count);
+
 struct LightTrees {
     std::vector<fyprt_lighttree_node> tlas; uint32_t tlasRoot = ~0u;
     std::vector<fyprt_lighttree_node> blas; std::vector<uint32_t> first, count, root;

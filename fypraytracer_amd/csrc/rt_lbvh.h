@@ -35,16 +35,18 @@ RT_DEV unsigned long long expand_bits21(unsigned long long v) {   // 21 bits -> 
     return v;
 }
 
-__global__ void k_lbvh_keys(const float4* triPos, uint32_t nT, float3 lo, float3 invExt, unsigned long long* keys, uint32_t* vals) {
+// The builders work on the triangle range [firstTri, firstTri + nT) of the scene (a whole-scene build: firstTri = 0): keys and values are
+// indexed by the position in the range, the VALUES are absolute triangle indices, which is all the later kernels read of the range.
+__global__ void k_lbvh_keys(const float4* triPos, uint32_t firstTri, uint32_t nT, float3 lo, float3 invExt, unsigned long long* keys, uint32_t* vals) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nT) return;
-    const float4* p = triPos + (size_t)t * 3;
+    const float4* p = triPos + (size_t)(firstTri + t) * 3;
     const float4 a = p[0], b = p[1], c = p[2];
     const float cx = ((a.x + b.x + c.x) * (1.0f / 3.0f) - lo.x) * invExt.x, cy = ((a.y + b.y + c.y) * (1.0f / 3.0f) - lo.y) * invExt.y,
                 cz = ((a.z + b.z + c.z) * (1.0f / 3.0f) - lo.z) * invExt.z;
     auto q = [](float v) { v = v * 2097152.0f; v = v < 0.0f ? 0.0f : (v > 2097151.0f ? 2097151.0f : v); return (unsigned long long)(uint32_t)v; };   // NaN -> 0
     keys[t] = (expand_bits21(q(cx)) << 2) | (expand_bits21(q(cy)) << 1) | expand_bits21(q(cz));
-    vals[t] = t;
+    vals[t] = firstTri + t;
 }
 
 // internal node i of the radix tree: range [first, last] of sorted leaves, children (bit 31 set = leaf index)

@@ -4,6 +4,8 @@
 //   k_emissive_count       } the emissive-triangle list (Scene::InitSceneEmissiveTriangles, Scene.cpp:209-221) as an ORDERED stream
 //   k_emissive_scan        } compaction: ReSTIR DI draws a candidate as an index into the list, so the list must be the one an upload
 //   k_emissive_scatter     } derives — ascending triangle order, the same on every run.  Positions come from a scan, never from atomics.
+// The stream is the triangle range [first, nT) — the whole scene for a material edit, the appended triangles for fyprt_append_meshes, whose
+// list is the old one followed by the range's emitters.
 // Every workgroup owns one contiguous chunk of triangles (a multiple of the block size, the same in count and scatter):
 //   count:   flags of the chunk -> one count per workgroup
 //   scan:    exclusive prefix of the (at most kEmMaxGroups) counts in one workgroup; entry [groups] = the total, the host's 4-byte read
@@ -35,10 +37,10 @@ RT_DEV bool tri_emits(const uint4* triIdx, const uint32_t* matFlag, uint32_t mat
     return m < matCount && matFlag[m] != 0u;
 }
 
-__global__ void __launch_bounds__(kBlock) k_emissive_count(const uint4* triIdx, const uint32_t* matFlag, uint32_t matCount, uint32_t nT, uint32_t perGroup, uint32_t* counts) {
+__global__ void __launch_bounds__(kBlock) k_emissive_count(const uint4* triIdx, const uint32_t* matFlag, uint32_t matCount, uint32_t first, uint32_t nT, uint32_t perGroup, uint32_t* counts) {
     __shared__ uint32_t s_count[kBlock / 64];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t begin = blockIdx.x * perGroup;
+    const uint32_t begin = first + blockIdx.x * perGroup;
     uint32_t n = 0;
     for (uint32_t tile = 0; tile < perGroup; tile += kBlock)
         n += (uint32_t)__popcll(__ballot(tri_emits(triIdx, matFlag, matCount, begin + tile + threadIdx.x, nT)));
@@ -66,11 +68,11 @@ __global__ void __launch_bounds__(kBlock) k_emissive_scan(const uint32_t* counts
     if (threadIdx.x == (uint32_t)kBlock - 1u) offsets[groups] = s_sum[threadIdx.x];
 }
 
-__global__ void __launch_bounds__(kBlock) k_emissive_scatter(const uint4* triIdx, const uint32_t* matFlag, uint32_t matCount, uint32_t nT, uint32_t perGroup,
+__global__ void __launch_bounds__(kBlock) k_emissive_scatter(const uint4* triIdx, const uint32_t* matFlag, uint32_t matCount, uint32_t first, uint32_t nT, uint32_t perGroup,
                                                              const uint32_t* offsets, uint32_t* out, uint32_t outCount) {
     __shared__ uint32_t s_count[2][kBlock / 64];   // double-buffered: one barrier per tile
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t begin = blockIdx.x * perGroup;
+    const uint32_t begin = first + blockIdx.x * perGroup;
     uint32_t base = offsets[blockIdx.x];
     for (uint32_t tile = 0, par = 0; tile < perGroup; tile += kBlock, par ^= 1u) {
         const uint32_t t = begin + tile + threadIdx.x;

@@ -87,21 +87,14 @@ RT_DEV void rbox_grow(RBox& b, float x, float y, float z) {
     b.hi[0] = __builtin_fmaxf(b.hi[0], x); b.hi[1] = __builtin_fmaxf(b.hi[1], y); b.hi[2] = __builtin_fmaxf(b.hi[2], z);
 }
 
-// nodeBox: 2 float4 per node (lo.xyz, hi.xyz), written for every node processed
-__global__ __launch_bounds__(128) void k_refit_level(float4* nodes, const uint32_t* levelNodes, uint32_t count, const float4* leafTris, const float4* triPos, float4* nodeBox) {
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= count) return;
-    const uint32_t node = levelNodes[k];
-    float4* n = nodes + (size_t)node * 4;
-    const float4 q0 = n[0], q1 = n[1];
-    const uint32_t ex = (uint32_t)__float_as_int(q0.w), cnt = (ex >> 24) & 7u;
-    const int32_t child[4] = {__float_as_int(q1.x), __float_as_int(q1.y), __float_as_int(q1.z), __float_as_int(q1.w)};
-    RBox cb[4]; RBox nb;
+// Exact boxes of a node's children (cb[i], the inverted box for the unused slots) and their union nb: a leaf child's from the triangles
+// of its leaf records, an inner child's from nodeBox, which the child's own level wrote before.
+// (every loop over the four child slots and the three axes is fully unrolled and predicated on `i < cnt`: the per-child boxes are
+// then indexed by constants and live in registers — indexed dynamically they were 112 bytes of scratch per lane)
+RT_DEV void refit_child_boxes(uint32_t cnt, const int32_t (&child)[4], const float4* leafTris, const float4* triPos, const float4* nodeBox, RBox (&cb)[4], RBox& nb) {
     const float big = 3.402823466e+38f;
 #pragma unroll
     for (int a = 0; a < 3; ++a) { nb.lo[a] = big; nb.hi[a] = -big; }
-    // (every loop over the four child slots and the three axes is fully unrolled and predicated on `i < cnt`: the per-child boxes are
-    // then indexed by constants and live in registers — indexed dynamically they were 112 bytes of scratch per lane)
 #pragma unroll
     for (uint32_t i = 0; i < 4; ++i) {
         RBox b;
@@ -125,6 +118,19 @@ __global__ __launch_bounds__(128) void k_refit_level(float4* nodes, const uint32
 #pragma unroll
         for (int a = 0; a < 3; ++a) { nb.lo[a] = __builtin_fminf(nb.lo[a], b.lo[a]); nb.hi[a] = __builtin_fmaxf(nb.hi[a], b.hi[a]); }
     }
+}
+
+// nodeBox: 2 float4 per node (lo.xyz, hi.xyz), written for every node processed
+__global__ __launch_bounds__(128) void k_refit_level(float4* nodes, const uint32_t* levelNodes, uint32_t count, const float4* leafTris, const float4* triPos, float4* nodeBox) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= count) return;
+    const uint32_t node = levelNodes[k];
+    float4* n = nodes + (size_t)node * 4;
+    const float4 q0 = n[0], q1 = n[1];
+    const uint32_t ex = (uint32_t)__float_as_int(q0.w), cnt = (ex >> 24) & 7u;
+    const int32_t child[4] = {__float_as_int(q1.x), __float_as_int(q1.y), __float_as_int(q1.z), __float_as_int(q1.w)};
+    RBox cb[4]; RBox nb;
+    refit_child_boxes(cnt, child, leafTris, triPos, nodeBox, cb, nb);
     uint32_t exps = ex & 0xFF000000u, qlo[3] = {0, 0, 0}, qhi[3] = {0, 0, 0};
 #pragma unroll
     for (int a = 0; a < 3; ++a) {

@@ -49,20 +49,25 @@ public:
     template <class SceneT, class CameraT> void Render(SceneT& scene, CameraT& camera) {   // Renderer.cu:13-284
         if (isSceneUpdated) {                                                                 // :61-69
             // The scene's signature has two parts.  Structure (counts, triangle vertex indices, mesh ranges, texture identities): a change
-            // means a full upload.  Materials (table, per-triangle and per-mesh material index, emissive list): a change alone is applied
-            // on the device by fyprt_update_materials, and the acceleration structure is not touched.
-            const uint64_t ssig = StructureSignature(scene), msig = MaterialSignature(scene);
+            // means a full upload, unless only tails grew (an import, below).  Materials (table, per-triangle and per-mesh material index,
+            // emissive list): a change alone is applied on the device by fyprt_update_materials, and the acceleration structure is not touched.
+            const uint64_t ssig = StructureSignature(scene, CountsOf(scene)), msig = MaterialSignature(scene);
             bool done = false;
+            // an import — "Import Mesh" / "Import Texture" (WalnutApp.cpp:668-693, :739-754) only push onto the end of the scene's arrays: when
+            // the structure the library holds is unchanged and only tails grew, the tails go to fyprt_append_textures / fyprt_append_meshes.
+            // The material part always differs then (new triangles, a longer emissive list): the material path below follows.
+            bool appended = false;
+            if (m_HaveScene && ssig != m_StructureSig && m_PendingTransforms.empty() && !m_OtherEdits && AppendTails(scene)) { m_StructureSig = ssig; ++m_Appends; appended = true; }
             if (m_HaveScene && ssig == m_StructureSig) {
                 // geometry — (a) nothing but mesh transforms moved vertices and the SceneManager told us which (NoteMeshTransform): 64 bytes
                 // per mesh go to the device, which recomputes the world vertices itself;  (b) an edit we know nothing about, or the flag
                 // alone: every world vertex is uploaded, refit on the device;  (c) a material edit alone moves no vertex
                 bool ok = true;
-                if (!m_PendingTransforms.empty() && !m_OtherEdits) {
+                if (!appended && !m_PendingTransforms.empty() && !m_OtherEdits) {
                     ok = fyprt_update_transforms(m_Ctx, m_PendingMeshes.data(), m_PendingTransforms.data(), (uint32_t)m_PendingMeshes.size()) == FYPRT_OK;
                     if (ok) { ++m_Refits; ++m_TransformUpdates; }
                 }
-                if ((m_OtherEdits || !ok || (m_PendingTransforms.empty() && !m_MaterialEdits))) {
+                if (!appended && (m_OtherEdits || !ok || (m_PendingTransforms.empty() && !m_MaterialEdits))) {
                     ok = fyprt_update_vertices(m_Ctx, reinterpret_cast<const fyprt_vertex*>(scene.worldVertices.data()), (uint32_t)scene.worldVertices.size()) == FYPRT_OK;
                     if (ok) ++m_Refits;
                 }
@@ -76,7 +81,7 @@ public:
             if (!done) {
                 if (UploadScene(scene)) {                    // remember the signature only of a scene the library really holds
                     m_StructureSig = ssig; m_MaterialSig = msig; m_HaveScene = true; ++m_Uploads;
-                    KeepMaterialIndices(scene);
+                    KeepMaterialIndices(scene); m_Counts = CountsOf(scene);
                 } else {
                     m_HaveScene = false;
                 }
@@ -143,6 +148,7 @@ public:
     uint32_t GetSceneUploadCount() const { return m_Uploads; }
     uint32_t GetSceneRefitCount() const { return m_Refits; }
     uint32_t GetMaterialUpdateCount() const { return m_MaterialUpdates; }
+    uint32_t GetSceneAppendCount() const { return m_Appends; }
 
 private:
     // FNV-1a over everything of the scene except vertex positions / normals, in two parts.  Structure: vertex / triangle / mesh / texture
@@ -152,14 +158,49 @@ private:
         uint64_t h = 1469598103934665603ull;
         void mix(const void* p, size_t n) { const uint8_t* b = (const uint8_t*)p; for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; } }
     };
-    template <class SceneT> static uint64_t StructureSignature(const SceneT& scene) {
+    // (of the scene restricted to `n`: its first n.vertices vertices, n.triangles triangles, ... — the whole scene with CountsOf(scene))
+    struct Counts { uint64_t vertices = 0, triangles = 0, meshes = 0, textures = 0; };
+    template <class SceneT> static Counts CountsOf(const SceneT& scene) { return Counts{scene.worldVertices.size(), scene.triangles.size(), scene.meshes.size(), scene.textures.size()}; }
+    template <class SceneT> static uint64_t StructureSignature(const SceneT& scene, const Counts& n) {
         Fnv f;
-        const uint64_t counts[4] = {scene.worldVertices.size(), scene.triangles.size(), scene.meshes.size(), scene.textures.size()};
+        const uint64_t counts[4] = {n.vertices, n.triangles, n.meshes, n.textures};
         f.mix(counts, sizeof counts);
-        for (const auto& t : scene.triangles) { const uint32_t v[3] = {t.v0, t.v1, t.v2}; f.mix(v, sizeof v); }
-        for (const auto& m : scene.meshes) { const uint32_t v[2] = {m.indexStart, m.indexCount}; f.mix(v, sizeof v); }
-        for (const auto& t : scene.textures) { const uint64_t v[3] = {(uint64_t)(uintptr_t)t.pixels, t.width, t.height}; f.mix(v, sizeof v); }
+        for (size_t i = 0; i < n.triangles; ++i) { const auto& t = scene.triangles[i]; const uint32_t v[3] = {t.v0, t.v1, t.v2}; f.mix(v, sizeof v); }
+        for (size_t i = 0; i < n.meshes; ++i) { const auto& m = scene.meshes[i]; const uint32_t v[2] = {m.indexStart, m.indexCount}; f.mix(v, sizeof v); }
+        for (size_t i = 0; i < n.textures; ++i) { const auto& t = scene.textures[i]; const uint64_t v[3] = {(uint64_t)(uintptr_t)t.pixels, t.width, t.height}; f.mix(v, sizeof v); }
         return f.h;
+    }
+    // Only tails grew on the structure the library holds: the new textures, then the new vertices / triangles / meshes (with their
+    // object-space vertices when the upload passed them), and the remembered material indices follow.  false: nothing an append can
+    // express, or the library refused — the scene is uploaded again.
+    template <class SceneT> bool AppendTails(const SceneT& scene) {
+        const Counts now = CountsOf(scene), was = m_Counts;
+        if (now.vertices < was.vertices || now.triangles < was.triangles || now.meshes < was.meshes || now.textures < was.textures) return false;
+        if (StructureSignature(scene, was) != m_StructureSig) return false;
+        if (now.textures > was.textures) {
+            std::vector<fyprt_texture> tex;
+            for (size_t i = was.textures; i < now.textures; ++i) tex.push_back(fyprt_texture{scene.textures[i].pixels, scene.textures[i].width, scene.textures[i].height});
+            if (fyprt_append_textures(m_Ctx, tex.data(), (uint32_t)tex.size()) != FYPRT_OK) return false;
+        }
+        if (now.meshes > was.meshes || now.triangles > was.triangles || now.vertices > was.vertices) {
+            std::vector<fyprt_mesh> meshes; std::vector<uint32_t> first;
+            for (size_t i = was.meshes; i < now.meshes; ++i) {
+                meshes.push_back(fyprt_mesh{scene.meshes[i].indexStart / 3u, scene.meshes[i].indexCount / 3u, scene.meshes[i].materialIndex});
+                first.push_back(scene.meshes[i].vertexStart);
+            }
+            first.push_back((uint32_t)now.vertices);
+            const bool object = m_ObjectVertices && scene.vertices.size() == scene.worldVertices.size();
+            const int rc = fyprt_append_meshes(m_Ctx, reinterpret_cast<const fyprt_vertex*>(scene.worldVertices.data()) + was.vertices, (uint32_t)(now.vertices - was.vertices),
+                                               scene.triangles.data() + was.triangles, (uint32_t)(now.triangles - was.triangles), (uint32_t)sizeof(scene.triangles[0]),
+                                               meshes.data(), (uint32_t)meshes.size(),
+                                               object ? reinterpret_cast<const fyprt_vertex*>(scene.vertices.data()) + was.vertices : nullptr, object ? first.data() : nullptr);
+            if (rc != FYPRT_OK) return false;
+            m_ObjectVertices = object;
+            for (size_t i = was.triangles; i < now.triangles; ++i) m_TriMaterial.push_back(scene.triangles[i].materialIndex);
+            for (size_t i = was.meshes; i < now.meshes; ++i) m_MeshMaterial.push_back(scene.meshes[i].materialIndex);
+        }
+        m_Counts = now;
+        return true;
     }
     template <class SceneT> static uint64_t MaterialSignature(const SceneT& scene) {
         Fnv f;
@@ -215,10 +256,11 @@ private:
         d.light_trees = nullptr;                      // the library builds them (LightTree.cpp restated)
         if (report(fyprt_upload_scene(m_Ctx, &d), "fyprt_upload_scene")) return false;
         // object-space vertices + mesh vertex ranges: what fyprt_update_transforms needs (Scene::vertices, Mesh::vertexStart / vertexCount)
+        m_ObjectVertices = false;
         if (scene.vertices.size() == scene.worldVertices.size()) {
             std::vector<uint32_t> first(scene.meshes.size() + 1, (uint32_t)scene.vertices.size());
             for (size_t i = 0; i < scene.meshes.size(); ++i) first[i] = scene.meshes[i].vertexStart;
-            fyprt_set_object_vertices(m_Ctx, reinterpret_cast<const fyprt_vertex*>(scene.vertices.data()), (uint32_t)scene.vertices.size(), first.data());
+            m_ObjectVertices = fyprt_set_object_vertices(m_Ctx, reinterpret_cast<const fyprt_vertex*>(scene.vertices.data()), (uint32_t)scene.vertices.size(), first.data()) == FYPRT_OK;
         }
         return true;
     }
@@ -234,7 +276,8 @@ private:
     std::vector<uint32_t> m_RenderImageData;
     std::vector<float> m_AccumulationData;
     bool isSceneUpdated = true;
-    bool m_HaveScene = false; uint64_t m_StructureSig = 0, m_MaterialSig = 0; uint32_t m_Uploads = 0, m_Refits = 0, m_TransformUpdates = 0, m_MaterialUpdates = 0;
+    bool m_HaveScene = false; uint64_t m_StructureSig = 0, m_MaterialSig = 0; uint32_t m_Uploads = 0, m_Refits = 0, m_TransformUpdates = 0, m_MaterialUpdates = 0, m_Appends = 0;
+    Counts m_Counts; bool m_ObjectVertices = false;                                         // what was uploaded: the counts an append starts from; with object-space vertices
     std::vector<uint32_t> m_PendingMeshes; std::vector<float> m_PendingTransforms; bool m_OtherEdits = false, m_MaterialEdits = false;
     std::vector<int32_t> m_TriMaterial, m_MeshMaterial; size_t m_MaterialCount = 0;     // what the library holds (UpdateMaterials)
     std::function<void(const uint32_t*, uint32_t, uint32_t)> m_Present;

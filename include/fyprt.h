@@ -259,6 +259,53 @@ int fyprt_update_vertices(fyprt_context* ctx, const fyprt_vertex* vertices, uint
 int fyprt_update_materials(fyprt_context* ctx, const fyprt_material* materials, uint32_t material_count,
                            const uint32_t* mesh_indices, const int32_t* mesh_materials, uint32_t mesh_count,
                            const uint32_t* emissive_triangles, uint32_t emissive_count);
+/* "Import Mesh" — WalnutApp.cpp:668-693 -> Scene::CreateNewMeshInScene (Scene.cpp:241-290) on Scene::AddNewMeshToScene (Scene.cpp:9-92):
+ * vertices, triangles and mesh records are pushed onto the end of the scene's arrays, nothing that exists moves.  `vertices` are the NEW world
+ * vertices, which follow the uploaded ones; `triangles` the NEW triangles (records as in fyprt_scene_desc), whose vertex indices are ABSOLUTE,
+ * into the combined vertex array, as AddNewMeshToScene offsets them by vertexStart; `meshes` the NEW meshes with ABSOLUTE first_triangle,
+ * which must partition the triangle range [T_old, T_old + triangle_count) in order.  `object_vertices`: NULL, or vertex_count object-space
+ * vertices with `mesh_first_vertex`, mesh_count + 1 ABSOLUTE entries from V_old to V_old + vertex_count: the object-space copy and the mesh
+ * vertex ranges of fyprt_set_object_vertices are extended under its checks, so fyprt_update_transforms works on old and new meshes (a
+ * context that holds no copy ignores them); with NULL a copy the context holds is released, as fyprt_upload_scene releases it.
+ * Afterwards the context is in the state fyprt_upload_scene reaches with the combined description, bit for bit — every per-triangle record,
+ * the material table (untouched), the exported light trees and emissive list, the light records, every later frame, ray query and radiance
+ * query (checked by an oracle that walks the exported tree) — except for the acceleration structure.  The emissive list is the old list,
+ * explicit or derived, followed by the appended triangles whose material emits, in ascending order: for a derived list exactly what upload
+ * derives for the combined scene.  Frame index, accumulation, reservoirs and ReSTIR history are kept, as upload keeps them; the last frame is no
+ * longer denoisable; the temporal history and the motion snapshot are dropped, as upload drops them.
+ * Acceleration structure — the graft: a sub-tree is built over the appended triangles only, with the builder of tuning key 12 (0: the host
+ * builder over the new meshes; 1, 2: the device LBVH / PLOC builder over the triangle range from five triangles on, otherwise the host
+ * builder); its nodes are appended to the node array and its leaf records to the leaf-triangle array.  With S the sub-tree's root (a leaf
+ * code when the append has few triangles) and R the current root: an inner R with fewer than four children takes S as child[count];
+ * otherwise (R is full, or a leaf code) a new two-child node (R, S) is appended as the LAST node and becomes the root; an empty tree
+ * becomes S.  The level count of R / the new root stays exact.  Apart from R when it takes the child (its grid is quantised again), every
+ * old node and every old leaf record keeps its index and its bytes.  Boxes and quantisation of the new nodes and of R / the new root come
+ * from the refit pass run over those nodes only; a host-only context quantises R / the new root with the host builder's quantiser from R's
+ * grid origin and its conservative upper planes.  The tree grows by one level about every third append; when the result would exceed 31
+ * levels or the node index range, the call rebuilds the tree of the combined scene as fyprt_upload_scene would.
+ * Cost: of the old scene only the per-node level grouping (4 bytes per node) crosses the bus; the scene's device arrays have a capacity that at
+ * least doubles when exceeded and move device to device (fyprt_live_device_bytes counts the capacity); per-triangle records, emissive list
+ * (an ordered compaction over the appended range), light records and the refit run on the device; the light trees of the new emissive meshes
+ * and the TLAS are built on the host.  An append without an emitter leaves the lights alone.
+ * Blocking: pipelined frames are waited for first, everything the call launches is complete on return.  Errors, in this order: FYPRT_EINVAL
+ * for a NULL context, a NULL array with a non-zero count (or object_vertices without mesh_first_vertex), triangle_stride < 16, a vertex index
+ * >= the combined vertex count, a material index outside the current table, meshes that do not partition the appended range in order,
+ * mesh_first_vertex out of order or not spanning [V_old, V_old + vertex_count], a triangle outside its mesh's vertex range (with
+ * object_vertices only); FYPRT_ESTATE before fyprt_upload_scene and on a scene uploaded with prebuilt light trees.  triangle_count == 0 &&
+ * mesh_count == 0 returns FYPRT_OK and changes nothing.  Host-only contexts are supported (everything but the device work).  The scene is
+ * per context: call it on every member of a group or communicator between frames. */
+int fyprt_append_meshes(fyprt_context* ctx,
+                        const fyprt_vertex* vertices, uint32_t vertex_count,
+                        const void* triangles, uint32_t triangle_count, uint32_t triangle_stride,
+                        const fyprt_mesh* meshes, uint32_t mesh_count,
+                        const fyprt_vertex* object_vertices, const uint32_t* mesh_first_vertex);
+/* "Import Texture" — WalnutApp.cpp:739-754 -> Scene::CreateNewTextureInScene (Scene.cpp:228-239): the new pixel arrays are uploaded and the
+ * texture table is extended; old pixel buffers stay where they are.  The context is then, bit for bit, one that uploaded the scene with the
+ * longer list.  Acceleration structure, frame state and temporal history are untouched and the last frame stays denoisable — unless a
+ * material's albedo_map_index already pointed at one of the new slots (indices beyond the table shade as solid colour): then the last frame
+ * is no longer denoisable and the temporal history is dropped, as after fyprt_update_materials.  Blocking.  Errors: FYPRT_EINVAL for a NULL
+ * context, NULL textures with a non-zero count, an empty or NULL texture; FYPRT_ESTATE before fyprt_upload_scene.  count == 0 changes nothing. */
+int fyprt_append_textures(fyprt_context* ctx, const fyprt_texture* textures, uint32_t count);
 /* The emissive-triangle list in effect (Scene::emissiveTriangles as uploaded, derived or updated).  NULL `triangles` queries the count. */
 int fyprt_export_emissive(fyprt_context* ctx, uint32_t* triangles, uint32_t* count);
 
