@@ -186,7 +186,10 @@ EXPORTED_SYMBOLS = [
     "fyprt_denoise_temporal_set_motion",
     "fyprt_group_denoise", "fyprt_group_denoise_device", "fyprt_group_denoise_plan",
     "fyprt_append_meshes", "fyprt_append_textures",
+    "fyprt_group_denoise_temporal", "fyprt_group_denoise_temporal_device", "fyprt_group_denoise_temporal_reset",
+    "fyprt_group_denoise_temporal_plan",
 ]
+GROUP_HISTORY_ROWS = 32   # FYPRT_GROUP_HISTORY_ROWS: the default history window of Group.denoise_temporal, rows either side of a band
 
 
 class FyprtError(RuntimeError):
@@ -291,6 +294,11 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
         lib.fyprt_group_denoise.argtypes = [vp, C.POINTER(DenoiseParams), vp, vp, vp]
         lib.fyprt_group_denoise_device.argtypes = [vp, C.POINTER(DenoiseParams), C.c_int, vp, vp]
         lib.fyprt_group_denoise_plan.argtypes = [C.POINTER(u32), C.c_int, u32, u32, C.POINTER(u32), C.c_int]
+    if hasattr(lib, "fyprt_group_denoise_temporal"):  # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
+        lib.fyprt_group_denoise_temporal.argtypes = [vp, C.POINTER(TemporalParams), u32, vp, vp, vp]
+        lib.fyprt_group_denoise_temporal_device.argtypes = [vp, C.POINTER(TemporalParams), u32, C.c_int, vp, vp]
+        lib.fyprt_group_denoise_temporal_reset.argtypes = [vp]
+        lib.fyprt_group_denoise_temporal_plan.argtypes = [C.POINTER(u32), C.c_int, u32, u32, u32, C.POINTER(u32), C.c_int]
     if hasattr(lib, "fyprt_append_meshes"):  # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
         lib.fyprt_append_meshes.argtypes = [vp, vp, u32, vp, u32, u32, vp, u32, vp, C.POINTER(u32)]
         lib.fyprt_append_textures.argtypes = [vp, C.POINTER(Texture), u32]
@@ -843,6 +851,50 @@ class Group:
                                                         C.c_void_p(radiance_tensor.data_ptr()) if radiance_tensor is not None else None))
         cur.wait_stream(ext)                                           # torch's later work follows the collect
 
+    def denoise_temporal(self, params: TemporalParams | None = None, history_rows=GROUP_HISTORY_ROWS, want_radiance=True, with_band_ms=False):
+        """Context.denoise_temporal for the frame the group rendered last (fyprt_group_denoise_temporal, blocking; defaults when `params`
+        is None): every band reprojects into the group's history — its own rows and `history_rows` rows either side, the band's history
+        window — and filters its rows.  Returns as denoise() does.  With history_rows >= height the sequence is a single context's."""
+        p = params if params is not None else TemporalParams()
+        H, W = self.contexts[0].height, self.contexts[0].width
+        img = np.empty(W * H, dtype=np.uint32)
+        rad = np.empty((W * H, 4), dtype=np.float32) if want_radiance else None
+        ms = (C.c_float * len(self.contexts))()
+        self._check(self.lib.fyprt_group_denoise_temporal(self.h, C.byref(p), int(history_rows), _ptr(img), _ptr(rad), ms if with_band_ms else None))
+        out = (img.reshape(H, W), rad.reshape(H, W, 4) if want_radiance else None)
+        return out + (list(ms),) if with_band_ms else out
+
+    def denoise_temporal_tensor(self, image_tensor, radiance_tensor, params: TemporalParams | None = None, history_rows=GROUP_HISTORY_ROWS, root=0):
+        """denoise_temporal into device tensors on the GPU of context `root` (fyprt_group_denoise_temporal_device); tensors and stream
+        ordering exactly as denoise_tensor."""
+        import torch
+        p = params if params is not None else TemporalParams()
+        if not 0 <= root < len(self.contexts):
+            raise ValueError("denoise_temporal_tensor: root out of range")
+        ctx = self.contexts[root]
+        if image_tensor is None and radiance_tensor is None:
+            raise ValueError("denoise_temporal_tensor: at least one output tensor is needed")
+        for t, dt, shape, name in ((image_tensor, torch.int32, (ctx.height, ctx.width), "image_tensor"),
+                                   (radiance_tensor, torch.float32, (ctx.height, ctx.width, 4), "radiance_tensor")):
+            if t is None:
+                continue
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"denoise_temporal_tensor: {name} must be a contiguous {dt} tensor of shape {shape}")
+            if t.device.type != "cuda" or (t.device.index if t.device.index is not None else torch.cuda.current_device()) != ctx.device:
+                raise ValueError(f"denoise_temporal_tensor: {name} must be on cuda:{ctx.device}, the root context's GPU")
+        dev = (image_tensor if image_tensor is not None else radiance_tensor).device
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(ctx.stream(), device=dev)
+        ext.wait_stream(cur)                                           # the outputs are allocated (and their earlier uses done) before root writes them
+        self._check(self.lib.fyprt_group_denoise_temporal_device(self.h, C.byref(p), int(history_rows), root,
+                                                                 C.c_void_p(image_tensor.data_ptr()) if image_tensor is not None else None,
+                                                                 C.c_void_p(radiance_tensor.data_ptr()) if radiance_tensor is not None else None))
+        cur.wait_stream(ext)                                           # torch's later work follows the collect
+
+    def denoise_temporal_reset(self):
+        """Drops every member's temporal history (fyprt_group_denoise_temporal_reset): the next denoise_temporal* call is a first call."""
+        self._check(self.lib.fyprt_group_denoise_temporal_reset(self.h))
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.fyprt_group_destroy(self.h)
@@ -899,4 +951,17 @@ def group_denoise_plan(row_bounds, height, iterations, lib=None):
         raise FyprtError(f"fyprt_group_denoise_plan failed ({cnt})")
     out = (C.c_uint32 * (5 * max(cnt, 1)))()
     lib.fyprt_group_denoise_plan(_u32_array(row_bounds), n, height, iterations, out, cnt)
+    return [tuple(out[5 * k: 5 * k + 5]) for k in range(cnt)]
+
+
+def group_denoise_temporal_plan(row_bounds, height, iterations, history_rows=GROUP_HISTORY_ROWS, lib=None):
+    """fyprt_group_denoise_temporal_plan: [(stage, receiver, owner, first row, end row), ...] of one Group.denoise_temporal call that finds a
+    history, in issue order (stage 0 guides, 1 prepared colour, 2 history, 3 + k colour and variance of iteration k)."""
+    lib = lib or load_library()
+    n = len(row_bounds) - 1
+    cnt = lib.fyprt_group_denoise_temporal_plan(_u32_array(row_bounds), n, height, iterations, history_rows, None, 0)
+    if cnt < 0:
+        raise FyprtError(f"fyprt_group_denoise_temporal_plan failed ({cnt})")
+    out = (C.c_uint32 * (5 * max(cnt, 1)))()
+    lib.fyprt_group_denoise_temporal_plan(_u32_array(row_bounds), n, height, iterations, history_rows, out, cnt)
     return [tuple(out[5 * k: 5 * k + 5]) for k in range(cnt)]

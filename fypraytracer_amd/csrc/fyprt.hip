@@ -199,6 +199,7 @@ struct fyprt_context {
     // camPV = projection x view of the camera set last, framePV = that of the camera the last frame was enqueued with, dtPV = that of the
     // frame the last temporal call denoised (what the next one reprojects with); dtValid: dt.hist[dtCur] holds a history
     struct Temporal { DevBuf<float4> hist[2]; DevBuf<float> var[2]; } dt; Event dtEv[4]; int dtCur = 0; bool dtValid = false;
+    uint64_t dtGroup = 0;                      // who wrote that history: 0 = a single-context call, else the group's serial (fyprt_group_denoise_temporal*)
     float camPV[16] = {}, framePV[16] = {}, dtPV[16] = {};
     // object motion (fyprt_denoise_temporal_set_motion): with the mode on a geometry edit keeps the history and copies the world vertices
     // as the frame denoised last saw them into dtSnap (allocated at the first snapshot, with a moved flag per triangle).  dtSnapPending:
@@ -2178,43 +2179,69 @@ int fyprt_denoise_temporal_default_params(fyprt_temporal_params* out) {
     return FYPRT_OK;
 }
 
-static int check_temporal(fyprt_context* c, const fyprt_temporal_params* p, const void* rgba8, const void* radiance4, bool device) {
-    const char* who = device ? "fyprt_denoise_temporal_device" : "fyprt_denoise_temporal";
-    if (!c) return FYPRT_EINVAL;
+// The temporal part of the parameters (the spatial part: check_denoise_params); fyprt_group_denoise_temporal* (fyprt_multi.h) shares it.
+static int check_temporal_params(fyprt_context* c, const char* who, const fyprt_temporal_params* p) {
     if (!p) return c->fail(FYPRT_EINVAL, std::string(who) + ": NULL params");
     if (p->history_limit < 1u || p->history_limit > 256u || p->feedback > 1u || !std::isfinite(p->normal_min) || !std::isfinite(p->plane_max) ||
         !(p->plane_max > 0.0f))
         return c->fail(FYPRT_EINVAL, std::string(who) + ": history_limit 1..256, feedback 0 / 1, finite normal_min, finite plane_max > 0");
+    return FYPRT_OK;
+}
+static int check_temporal(fyprt_context* c, const fyprt_temporal_params* p, const void* rgba8, const void* radiance4, bool device) {
+    const char* who = device ? "fyprt_denoise_temporal_device" : "fyprt_denoise_temporal";
+    if (!c) return FYPRT_EINVAL;
+    TRY(check_temporal_params(c, who, p));
     const int rc = check_denoise(c, &p->spatial, rgba8, radiance4, device);
     if (rc != FYPRT_OK) c->err = std::string(who) + " (as fyprt_denoise): " + c->err;
     return rc;
 }
 
-// Enqueues prepare + reproject + iterations (+ finish) on the context stream.  ev: 4 timing events or null.
-static int enqueue_temporal(fyprt_context* c, const fyprt_temporal_params* p, uint32_t* rgba8, float4* radiance4, const Event* ev, int* launched) {
-    const fyprt_denoise_params& sp = p->spatial;
+// One iteration of the temporal form on the rows of `band`, on the context stream
+static void launch_dt_iterate(fyprt_context* c, const DnFrame& fr, const DnIter& it, DnBand band, const float4* in, float4* out, const float* vin,
+                              float* vout, float4* fb) {
+    for_dn_step(it.step, [&](auto S) {
+        constexpr int STEP = decltype(S)::value;
+        hipLaunchKernelGGL(k_dt_iterate<STEP>, dim3(dn_grid<STEP>(fr.W, band.rowEnd - band.rowBegin)), dim3(256), 0, c->stream, fr, it, band, in, out, vin, vout, fb);
+    });
+}
+// The history and variance buffers of a context (a new size drops the history)
+static int ensure_dt_buffers(fyprt_context* c) {
     const size_t n = (size_t)c->W * c->H;
     if (c->dt.hist[0].n != 4 * n) {
         c->drop_history();
         for (int k = 0; k < 2; ++k) { HIPCHK(c, c->dt.hist[k].alloc(4 * n)); HIPCHK(c, c->dt.var[k].alloc(n)); }
     }
-    DnFrame fr;
-    TRY(begin_denoise(c, sp, rgba8, radiance4, ev, launched, fr));
+    return FYPRT_OK;
+}
+
+static DtCall make_dt_call(const fyprt_context* c, const fyprt_temporal_params& p, bool haveHistory) {
     DtCall tc{};
     std::memcpy(tc.m, c->dtPV, 64);
-    tc.haveHistory = c->dtValid ? 1u : 0u; tc.limit = (float)p->history_limit; tc.normalMin = p->normal_min; tc.planeMax = p->plane_max;
-    tc.sigmaPlane = sp.sigma_plane; tc.normalPow = sp.normal_power_log2;
+    tc.haveHistory = haveHistory ? 1u : 0u; tc.limit = (float)p.history_limit; tc.normalMin = p.normal_min; tc.planeMax = p.plane_max;
+    tc.sigmaPlane = p.spatial.sigma_plane; tc.normalPow = p.spatial.normal_power_log2;
+    return tc;
+}
+
+// Enqueues prepare + reproject + iterations (+ finish) on the context stream.  ev: 4 timing events or null.
+static int enqueue_temporal(fyprt_context* c, const fyprt_temporal_params* p, uint32_t* rgba8, float4* radiance4, const Event* ev, int* launched) {
+    const fyprt_denoise_params& sp = p->spatial;
+    TRY(ensure_dt_buffers(c));
+    if (c->dtGroup != 0) c->drop_history();      // a history a group wrote (fyprt_group_denoise_temporal*) covers the rows the context owned there
+    DnFrame fr;
+    TRY(begin_denoise(c, sp, rgba8, radiance4, ev, launched, fr));
+    const DtCall tc = make_dt_call(c, *p, c->dtValid);
     const int next = c->dtCur ^ 1;
     float4* hist = c->dt.hist[next].p;
-    const dim3 grid(((c->W + 15u) / 16u) * ((c->H + 15u) / 16u));
+    const DnBand all{0, c->H};
+    const dim3 grid(dt_reproject_grid(c->W, c->H));
     if (c->dtValid && c->dtSnapPending && c->dtEditHi > c->dtEditLo) {       // object motion: the flags of the edited range, then the motion form
         const uint32_t count = c->dtEditHi - c->dtEditLo;
         hipLaunchKernelGGL(k_dt_moved, dim3((count + 255u) / 256u), dim3(256), 0, c->stream, c->dverts.p, c->dtSnap.p, c->triIdx.p, c->dtMoved.p, c->dtEditLo, count);
         ++*launched;
         const DtMotion mo{c->payload.p, c->dtMoved.p, c->triIdx.p, c->triPos.p, c->dtSnap.p};
-        hipLaunchKernelGGL(k_dt_reproject_motion, grid, dim3(256), 0, c->stream, fr, tc, mo, c->dn.col[0].p, c->dt.hist[c->dtCur].p, hist, c->dn.col[1].p, c->dt.var[0].p);
+        hipLaunchKernelGGL(k_dt_reproject_motion, grid, dim3(256), 0, c->stream, fr, tc, mo, all, all, c->dn.col[0].p, c->dt.hist[c->dtCur].p, hist, c->dn.col[1].p, c->dt.var[0].p);
     } else {
-        hipLaunchKernelGGL(k_dt_reproject, grid, dim3(256), 0, c->stream, fr, tc, c->dn.col[0].p, c->dt.hist[c->dtCur].p, hist, c->dn.col[1].p, c->dt.var[0].p);
+        hipLaunchKernelGGL(k_dt_reproject, grid, dim3(256), 0, c->stream, fr, tc, all, all, c->dn.col[0].p, c->dt.hist[c->dtCur].p, hist, c->dn.col[1].p, c->dt.var[0].p);
     }
     ++*launched;
     if (ev) HIPCHK(c, hipEventRecord(ev[2], c->stream));
@@ -2223,14 +2250,11 @@ static int enqueue_temporal(fyprt_context* c, const fyprt_temporal_params* p, ui
         const float4* in = c->dn.col[(k + 1u) & 1u].p; float4* out = c->dn.col[k & 1u].p;
         const float* vin = c->dt.var[k & 1u].p; float* vout = c->dt.var[(k + 1u) & 1u].p;
         float4* fb = (k == 0 && p->feedback) ? hist : nullptr;
-        for_dn_step(it.step, [&](auto S) {
-            constexpr int STEP = decltype(S)::value;
-            hipLaunchKernelGGL(k_dt_iterate<STEP>, dim3(dn_grid<STEP>(c->W, c->H)), dim3(256), 0, c->stream, fr, it, in, out, vin, vout, fb);
-        });
+        launch_dt_iterate(c, fr, it, all, in, out, vin, vout, fb);
         ++*launched;
     }
     TRY(end_denoise(c, fr, sp.iterations, c->dn.col[1].p, ev ? ev + 3 : nullptr, launched));
-    c->dtCur = next; c->dtValid = true; c->dtSnapPending = false; std::memcpy(c->dtPV, c->framePV, 64);
+    c->dtCur = next; c->dtValid = true; c->dtGroup = 0; c->dtSnapPending = false; std::memcpy(c->dtPV, c->framePV, 64);
     return FYPRT_OK;
 }
 

@@ -20,6 +20,8 @@
 //   fyprt_comm_*    one process per GPU (torch.distributed.run, MPI, ...): RCCL — grouped ncclSend / ncclRecv for the halos, grouped
 //                   ncclBroadcast (one per band, in place in the full-size image) for the gather.  librccl.so.1 is opened on first use.
 // fyprt_group_denoise* (below fyprt_group_synchronize): the a-trous denoiser on the same bands, by the same peer copies and events.
+// fyprt_group_denoise_temporal* (below it): the temporal denoiser on the same bands; the history stays with the rows' owners, a band reads
+// it inside its history window, and fyprt_group_set_rows moves it with the rows.
 #include <dlfcn.h>
 
 extern "C++" {
@@ -62,6 +64,21 @@ std::vector<DnXfer> group_denoise_plan(const std::vector<uint32_t>& bounds, uint
     for (const HaloXfer& x : halo_plan(bounds, 1u << iterations, H, false)) plan.push_back({0, x});
     for (uint32_t k = 0; k < iterations; ++k)
         for (const HaloXfer& x : halo_plan(bounds, 2u << k, H, false)) plan.push_back({1 + (int)k, x});
+    return plan;
+}
+
+// fyprt_group_denoise_temporal: every transfer of one call, in issue order, each sized by what the kernel after it reads.  Stage 0 = the
+// guide records, max(2, 2^iterations) rows (the 5 x 5 variance estimate of k_dt_reproject reads 2 rows whatever the iterations); stage 1
+// = the prepared colour e0 | L that estimate reads, 2 rows; stage 2 = the history records (64 B per pixel), min(historyRows, H) rows:
+// the band's history window; stage 3 + k = the colour | luminance and the variance (4 B per pixel) iteration k reads, 2 * 2^k rows.
+constexpr size_t kDtHistoryBytes = 4 * sizeof(float4), kDtVarianceBytes = sizeof(float);
+std::vector<DnXfer> group_temporal_plan(const std::vector<uint32_t>& bounds, uint32_t H, uint32_t iterations, uint32_t historyRows) {
+    std::vector<DnXfer> plan;
+    for (const HaloXfer& x : halo_plan(bounds, std::max(2u, 1u << iterations), H, false)) plan.push_back({0, x});
+    for (const HaloXfer& x : halo_plan(bounds, 2u, H, false)) plan.push_back({1, x});
+    for (const HaloXfer& x : halo_plan(bounds, std::min(historyRows, H), H, false)) plan.push_back({2, x});
+    for (uint32_t k = 0; k < iterations; ++k)
+        for (const HaloXfer& x : halo_plan(bounds, 2u << k, H, false)) plan.push_back({3 + (int)k, x});
     return plan;
 }
 
@@ -166,7 +183,18 @@ struct fyprt_group {
     // root, the two timing events of the blocking entry; whether a call was enqueued before, and the root of the last one
     struct DenoiseEvents { Event done, pulled, collect, first, last; };
     std::vector<DenoiseEvents> dn; bool dnCalled = false; int dnRoot = -1;
+    // fyprt_group_denoise_temporal*: the serial a member's history carries (fyprt_context::dtGroup) while this group wrote it
+    uint64_t id = 0;
 };
+static uint64_t g_groupSerial = 0;
+// The group holds a temporal history: every member's was written by this group's last temporal call (or moved by fyprt_group_set_rows
+// since), for the same camera matrix.
+static bool group_has_history(const fyprt_group* g) {
+    const fyprt_context* c0 = g->ctx[0];
+    for (const fyprt_context* c : g->ctx)
+        if (!c->dtValid || c->dtGroup != g->id || c->dt.hist[0].n != 4 * (size_t)c->W * c->H || std::memcmp(c->dtPV, c0->dtPV, 64) != 0) return false;
+    return true;
+}
 
 int fyprt_group_synchronize(fyprt_group* g);
 #define NCCLCHK(c, call) do { const int _r = (call); if (_r != 0) return (c)->fail(FYPRT_EHIP, std::string(#call) + ": " + g_rccl.GetErrorString(_r)); } while (0)
@@ -198,7 +226,7 @@ int fyprt_group_create(fyprt_context** ctxs, int n, const uint32_t* row_bounds, 
     if (row_bounds[0] != 0 || row_bounds[n] != ctxs[0]->H) return ctxs[0]->fail(FYPRT_EINVAL, "fyprt_group_create: the bands must partition rows 0..height");
     auto* g = new fyprt_group();
     g->ctx.assign(ctxs, ctxs + n); g->bounds.assign(row_bounds, row_bounds + n + 1);
-    g->ev.resize(n); g->dn.resize(n);
+    g->ev.resize(n); g->dn.resize(n); g->id = ++g_groupSerial;
     for (int i = 0; i < n; ++i) {
         (void)hipSetDevice(ctxs[i]->device);
         for (Event* e : {&g->ev[i].p1, &g->ev[i].pulled, &g->ev[i].frame, &g->ev[i].sync}) (void)create(*e, hipEventDisableTiming);
@@ -220,7 +248,7 @@ void fyprt_group_destroy(fyprt_group* g) {
 }
 // New band boundaries (e.g. from fyprt_balance_rows).  Rows that change owner take their accumulation and their temporal history
 // (ReSTIR DI records, ReSTIR GI reservoirs + normals) with them — peer copies from the old owner, between two frames — so a sequence
-// with moving borders stays what it was.  Synchronises the group.
+// with moving borders stays what it was; and, while the group holds one, the temporal denoiser's history records.  Synchronises the group.
 int fyprt_group_set_rows(fyprt_group* g, const uint32_t* row_bounds) {
     if (!g || !row_bounds) return FYPRT_EINVAL;
     const int n = (int)g->ctx.size();
@@ -228,6 +256,7 @@ int fyprt_group_set_rows(fyprt_group* g, const uint32_t* row_bounds) {
     if (row_bounds[0] != 0 || row_bounds[n] != g->ctx[0]->H) return g->ctx[0]->fail(FYPRT_EINVAL, "fyprt_group_set_rows: the bands must partition rows 0..height");
     for (int i = 0; i < n; ++i) if (row_bounds[i] >= row_bounds[i + 1]) return g->ctx[i]->fail(FYPRT_EINVAL, "fyprt_group_set_rows: empty or unordered band");
     TRY(fyprt_group_synchronize(g));
+    const bool history = group_has_history(g);
     for (int k = 0; k < n; ++k) {
         fyprt_context* c = g->ctx[k];
         HIPCHK(c, hipSetDevice(c->device));
@@ -242,6 +271,7 @@ int fyprt_group_set_rows(fyprt_group* g, const uint32_t* row_bounds) {
             HIPCHK(c, move(c->dprevFlip ? c->dprevB.p : c->dprevA.p, o->dprevFlip ? o->dprevB.p : o->dprevA.p, sizeof(DIRec)));
             HIPCHK(c, move(c->giPrev.p, o->giPrev.p, sizeof(GIRes)));
             HIPCHK(c, move(c->normalFlip ? c->normalB.p : c->normalA.p, o->normalFlip ? o->normalB.p : o->normalA.p, sizeof(f2)));
+            if (history) HIPCHK(c, move(c->dt.hist[c->dtCur].p, o->dt.hist[o->dtCur].p, kDtHistoryBytes));
         }
     }
     TRY(fyprt_group_synchronize(g));
@@ -373,11 +403,9 @@ int fyprt_group_synchronize(fyprt_group* g) {
 // its row, with its band as the kernels' DnBand; what a tap beyond the band reads was pulled from the row's owner into the same place of
 // this context's full-size guide / colour buffers (group_denoise_plan).  The shared pixel code on the same inputs: the single-context
 // call's bits.  Nothing but the denoiser's own buffers and the caller's outputs is written.
-static int group_denoise_check(fyprt_group* g, const fyprt_denoise_params* p, int root, const void* rgba8, const void* radiance4, bool device) {
-    const char* who = device ? "fyprt_group_denoise_device" : "fyprt_group_denoise";
-    if (!g) return FYPRT_EINVAL;
+// everything fyprt_group_denoise* checks after the parameters, in the header's order (fyprt_group_denoise_temporal* shares it)
+static int group_denoise_check_call(fyprt_group* g, const char* who, int root, const void* rgba8, const void* radiance4, bool device) {
     const int n = (int)g->ctx.size();
-    TRY(check_denoise_params(g->ctx[0], who, p));
     if (root < 0 || root >= n) return g->ctx[0]->fail(FYPRT_EINVAL, std::string(who) + ": root out of range");
     TRY(check_denoise_outputs(g->ctx[root], who, rgba8, radiance4, device));
     for (int i = 0; i < n; ++i) TRY(check_denoise_frame(g->ctx[i], who));
@@ -390,6 +418,12 @@ static int group_denoise_check(fyprt_group* g, const fyprt_denoise_params* p, in
             return c->fail(FYPRT_ESTATE, std::string(who) + ": the member's rows are not its band of the group (fyprt_set_rows / fyprt_set_row_stripes behind the group)");
     }
     return FYPRT_OK;
+}
+static int group_denoise_check(fyprt_group* g, const fyprt_denoise_params* p, int root, const void* rgba8, const void* radiance4, bool device) {
+    const char* who = device ? "fyprt_group_denoise_device" : "fyprt_group_denoise";
+    if (!g) return FYPRT_EINVAL;
+    TRY(check_denoise_params(g->ctx[0], who, p));
+    return group_denoise_check_call(g, who, root, rgba8, radiance4, device);
 }
 
 // Enqueues one call on every band's stream and the collect on root's; no host wait (but before a staging buffer is reallocated).
@@ -545,6 +579,252 @@ int fyprt_group_denoise_plan(const uint32_t* row_bounds, int n, uint32_t height,
     if (!row_bounds || n <= 0 || iterations > 8u || row_bounds[0] != 0 || row_bounds[n] != height) return FYPRT_EINVAL;
     for (int i = 0; i < n; ++i) if (row_bounds[i] >= row_bounds[i + 1]) return FYPRT_EINVAL;
     const std::vector<DnXfer> plan = group_denoise_plan(std::vector<uint32_t>(row_bounds, row_bounds + n + 1), height, iterations);
+    for (int k = 0; k < (int)plan.size() && k < capacity && out5; ++k) {
+        const HaloXfer& x = plan[k].x;
+        out5[5 * k] = (uint32_t)plan[k].stage; out5[5 * k + 1] = (uint32_t)x.receiver; out5[5 * k + 2] = (uint32_t)x.owner; out5[5 * k + 3] = x.r0; out5[5 * k + 4] = x.r1;
+    }
+    return (int)plan.size();
+}
+
+// ---- fyprt_group_denoise_temporal*: the temporal denoiser (rt_temporal.h) on the group's bands, as fyprt_group_denoise* above: the band
+// as the kernels' DnBand, its history window as the reprojection's second DnBand, and what a kernel reads beyond the band pulled from
+// the rows' owners into the same place of this context's full-size buffers (group_temporal_plan).  Every member keeps the history of
+// its own rows in its own ping-pong pair; dt.hist[dtCur] of a member also holds the window rows the last call pulled, which nothing
+// reads again.
+static int group_temporal_check(fyprt_group* g, const fyprt_temporal_params* p, int root, const void* rgba8, const void* radiance4, bool device) {
+    const char* who = device ? "fyprt_group_denoise_temporal_device" : "fyprt_group_denoise_temporal";
+    if (!g) return FYPRT_EINVAL;
+    fyprt_context* c0 = g->ctx[0];
+    TRY(check_temporal_params(c0, who, p));
+    TRY(check_denoise_params(c0, who, &p->spatial));
+    TRY(group_denoise_check_call(g, who, root, rgba8, radiance4, device));
+    for (fyprt_context* c : g->ctx)
+        if (std::memcmp(c->framePV, c0->framePV, 64) != 0) return c->fail(FYPRT_ESTATE, std::string(who) + ": the members' last frames differ in camera matrix");
+    const bool history = group_has_history(g);
+    for (fyprt_context* c : g->ctx)
+        if (c->dtMotion != c0->dtMotion || (history && c->dtSnapPending != c0->dtSnapPending))
+            return c->fail(FYPRT_ESTATE, std::string(who) + ": the members differ in motion mode (fyprt_denoise_temporal_set_motion) or in having a geometry edit pending");
+    return FYPRT_OK;
+}
+
+// Enqueues one call on every band's stream and the collect on root's, as group_denoise_enqueue, with its events.  Per band: prepare;
+// the pulls of stages 0 and 1; k_dt_moved if a snapshot is pending; the pull of stage 2; reproject; per iteration the pull of stage
+// 3 + k and the iteration; the finish kernel without iterations.  Hazards, and the event that orders each:
+//   read after write   a pull reads rows the owner's latest kernel wrote (prepare: guide and e0 | L; the previous call: the history;
+//                      reproject / iteration k - 1: colour and variance): it waits for the owner's `done`, recorded after each launch;
+//   write after read   iteration k overwrites the colour and variance buffers iteration k - 1 read, which the neighbours pulled from at
+//                      stage 3 + k - 1 (iteration 0: the prepared colour of stage 1): it waits for the last `pulled` of every band that
+//                      pulls from this one, as recorded after that stage or a later one;
+//   the history        ping-pongs per member: this call writes dt.hist[dtCur ^ 1], the buffer the neighbours' stage 2 of the call before
+//                      pulled from.  The first work of a call on a band waits for every other band's last `pulled` of the earlier call
+//                      — recorded after that call's last stage, so after its stage 2 — which also covers the colour, variance and guide
+//                      buffers;
+//   across calls       the staging rows wait for the earlier root's `collect`, and dn_call_done holds the front stream, as there.
+// The members' bookkeeping (dtCur, dtValid, dtGroup, dtPV, dtSnapPending) advances only once everything is enqueued.
+static int group_temporal_enqueue_all(fyprt_group* g, const fyprt_temporal_params* p, uint32_t historyRows, int root, uint32_t* rgba8, float4* radiance4, bool timed) {
+    const fyprt_denoise_params& sp = p->spatial;
+    const int n = (int)g->ctx.size();
+    const uint32_t W = g->ctx[0]->W, H = g->ctx[0]->H, R = std::min(historyRows, H);
+    for (int i = 0; i < n; ++i) {
+        fyprt_context* c = g->ctx[i];
+        HIPCHK(c, hipSetDevice(c->device));
+        TRY(ensure_dn_buffers(c));
+        TRY(ensure_dt_buffers(c));
+    }
+    const bool history = group_has_history(g);
+    std::vector<DnXfer> plan;
+    for (const DnXfer& t : group_temporal_plan(g->bounds, H, sp.iterations, R)) if (t.stage != 2 || history) plan.push_back(t);
+    std::vector<char> pullsFrom((size_t)n * n, 0);                // [owner * n + receiver]
+    for (const DnXfer& t : plan) pullsFrom[(size_t)t.x.owner * n + t.x.receiver] = 1;
+    std::vector<DnFrame> frames(n); std::vector<DnBand> bands(n);
+    for (int i = 0; i < n; ++i) {
+        fyprt_context* c = g->ctx[i];
+        HIPCHK(c, hipSetDevice(c->device));
+        fyprt_group::DenoiseEvents& e = g->dn[i];
+        HIPCHK(c, create(e.done, hipEventDisableTiming)); HIPCHK(c, create(e.pulled, hipEventDisableTiming)); HIPCHK(c, create(e.collect, hipEventDisableTiming));
+        if (timed) { HIPCHK(c, create(e.first)); HIPCHK(c, create(e.last)); }
+        const uint32_t b = g->bounds[i], rows = g->bounds[i + 1] - b;
+        bands[i] = DnBand{b, g->bounds[i + 1]};
+        DnFrame& fr = frames[i];
+        fr = dn_frame(c, sp.demodulate_albedo, i == root ? rgba8 : nullptr, i == root ? radiance4 : nullptr);
+        if (i == root) continue;
+        const size_t need = (size_t)rows * W;                     // the band's staging, as group_denoise_enqueue
+        if ((rgba8 && c->dn.outImg.n < need) || (radiance4 && c->dn.outRad.n < need)) {
+            if (g->dnRoot >= 0) HIPCHK(c, hipEventSynchronize(g->dn[g->dnRoot].collect));
+            if (rgba8 && c->dn.outImg.n < need) HIPCHK(c, c->dn.outImg.alloc(need));
+            if (radiance4 && c->dn.outRad.n < need) HIPCHK(c, c->dn.outRad.alloc(need));
+        }
+        if (rgba8) fr.rgba8 = reinterpret_cast<uint32_t*>(reinterpret_cast<uintptr_t>(c->dn.outImg.p) - (size_t)b * W * sizeof(uint32_t));
+        if (radiance4) fr.radiance4 = reinterpret_cast<float4*>(reinterpret_cast<uintptr_t>(c->dn.outRad.p) - (size_t)b * W * sizeof(float4));
+    }
+    auto pull = [&](int i, int stage) -> int {
+        fyprt_context* c = g->ctx[i];
+        HIPCHK(c, hipSetDevice(c->device));
+        for (const DnXfer& t : plan) {
+            if (t.stage != stage || t.x.receiver != i) continue;
+            fyprt_context* o = g->ctx[t.x.owner];
+            HIPCHK(c, hipStreamWaitEvent(c->stream, g->dn[t.x.owner].done, 0));
+            const uint32_t k = stage >= 3 ? (uint32_t)(stage - 3) : 0u;
+            struct { void* dst; const void* src; size_t bpp; } what[2] = {};
+            int cnt = 1;
+            if (stage == 0) what[0] = {c->dn.guide.p, o->dn.guide.p, kDnGuideBytes};
+            else if (stage == 1) what[0] = {c->dn.col[0].p, o->dn.col[0].p, kDnColourBytes};
+            else if (stage == 2) what[0] = {c->dt.hist[c->dtCur].p, o->dt.hist[o->dtCur].p, kDtHistoryBytes};
+            else {
+                what[0] = {c->dn.col[(k + 1u) & 1u].p, o->dn.col[(k + 1u) & 1u].p, kDnColourBytes};
+                what[1] = {c->dt.var[k & 1u].p, o->dt.var[k & 1u].p, kDtVarianceBytes}; cnt = 2;
+            }
+            for (int w = 0; w < cnt; ++w) {
+                const size_t off = (size_t)t.x.r0 * W * what[w].bpp, bytes = (size_t)(t.x.r1 - t.x.r0) * W * what[w].bpp;
+                HIPCHK(c, hipMemcpyPeerAsync((char*)what[w].dst + off, c->device, (const char*)what[w].src + off, o->device, bytes, c->stream));
+            }
+        }
+        HIPCHK(c, hipEventRecord(g->dn[i].pulled, c->stream));
+        return FYPRT_OK;
+    };
+    auto before_output = [&](int i) -> int {                     // the earlier call's collect still reads this band's staging rows
+        fyprt_context* c = g->ctx[i];
+        if (i != root && g->dnRoot >= 0) HIPCHK(c, hipStreamWaitEvent(c->stream, g->dn[g->dnRoot].collect, 0));
+        return FYPRT_OK;
+    };
+    auto wait_pullers = [&](int i) -> int {                      // every band that pulls from band i has pulled what it last asked for
+        fyprt_context* c = g->ctx[i];
+        HIPCHK(c, hipSetDevice(c->device));
+        for (int j = 0; j < n; ++j) if (pullsFrom[(size_t)i * n + j]) HIPCHK(c, hipStreamWaitEvent(c->stream, g->dn[j].pulled, 0));
+        return FYPRT_OK;
+    };
+    // 1. prepare on the band's rows, after the earlier call's pulls from this band
+    for (int i = 0; i < n; ++i) {
+        fyprt_context* c = g->ctx[i];
+        HIPCHK(c, hipSetDevice(c->device));
+        if (timed) HIPCHK(c, hipEventRecord(g->dn[i].first, c->stream));
+        if (g->dnCalled) for (int j = 0; j < n; ++j) if (j != i) HIPCHK(c, hipStreamWaitEvent(c->stream, g->dn[j].pulled, 0));
+        launch_dn_prepare(c, frames[i], bands[i]);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(g->dn[i].done, c->stream));
+    }
+    // 2. guide records and prepared colour of the rows the variance estimate and the taps reach
+    for (int i = 0; i < n; ++i) TRY(pull(i, 0));
+    for (int i = 0; i < n; ++i) TRY(pull(i, 1));
+    // 3. the moved flags, the history window, the reprojection.  `done` is not recorded after k_dt_moved: nothing pulls what it writes,
+    // and the owner's `done` a stage-2 pull waits for is its prepare's — the history itself is the call before's, which the stream orders.
+    for (int i = 0; i < n; ++i) {
+        fyprt_context* c = g->ctx[i];
+        HIPCHK(c, hipSetDevice(c->device));
+        const bool motion = history && c->dtSnapPending && c->dtEditHi > c->dtEditLo;
+        if (motion) {
+            const uint32_t count = c->dtEditHi - c->dtEditLo;
+            hipLaunchKernelGGL(k_dt_moved, dim3((count + 255u) / 256u), dim3(256), 0, c->stream, c->dverts.p, c->dtSnap.p, c->triIdx.p, c->dtMoved.p, c->dtEditLo, count);
+        }
+        if (history) TRY(pull(i, 2));
+    }
+    for (int i = 0; i < n; ++i) {
+        fyprt_context* c = g->ctx[i];
+        HIPCHK(c, hipSetDevice(c->device));
+        const bool motion = history && c->dtSnapPending && c->dtEditHi > c->dtEditLo;
+        const DtCall tc = make_dt_call(c, *p, history);
+        const DnBand win{bands[i].rowBegin > R ? bands[i].rowBegin - R : 0u, std::min(H, bands[i].rowEnd + R)};
+        const dim3 grid(dt_reproject_grid(W, bands[i].rowEnd - bands[i].rowBegin));
+        const float4* histIn = c->dt.hist[c->dtCur].p; float4* histOut = c->dt.hist[c->dtCur ^ 1].p;
+        if (motion) {
+            const DtMotion mo{c->payload.p, c->dtMoved.p, c->triIdx.p, c->triPos.p, c->dtSnap.p};
+            hipLaunchKernelGGL(k_dt_reproject_motion, grid, dim3(256), 0, c->stream, frames[i], tc, mo, bands[i], win, c->dn.col[0].p, histIn, histOut, c->dn.col[1].p, c->dt.var[0].p);
+        } else {
+            hipLaunchKernelGGL(k_dt_reproject, grid, dim3(256), 0, c->stream, frames[i], tc, bands[i], win, c->dn.col[0].p, histIn, histOut, c->dn.col[1].p, c->dt.var[0].p);
+        }
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(g->dn[i].done, c->stream));
+    }
+    // 4. per iteration: colour and variance of the rows it reads, then the iteration on the band's rows
+    for (uint32_t k = 0; k < sp.iterations; ++k) {              // colour: dn.col[1] -> [0] -> [1] ...; variance: dt.var[0] -> [1] -> [0] ...
+        const DnIter it = make_dn_iter(sp, k, false);
+        for (int i = 0; i < n; ++i) TRY(wait_pullers(i));
+        for (int i = 0; i < n; ++i) TRY(pull(i, 3 + (int)k));
+        for (int i = 0; i < n; ++i) {
+            fyprt_context* c = g->ctx[i];
+            HIPCHK(c, hipSetDevice(c->device));
+            if (it.last) TRY(before_output(i));
+            float4* fb = (k == 0 && p->feedback) ? c->dt.hist[c->dtCur ^ 1].p : nullptr;
+            launch_dt_iterate(c, frames[i], it, bands[i], c->dn.col[(k + 1u) & 1u].p, c->dn.col[k & 1u].p, c->dt.var[k & 1u].p, c->dt.var[(k + 1u) & 1u].p, fb);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipEventRecord(g->dn[i].done, c->stream));
+        }
+    }
+    for (int i = 0; i < n; ++i) {
+        fyprt_context* c = g->ctx[i];
+        HIPCHK(c, hipSetDevice(c->device));
+        if (sp.iterations == 0) {
+            TRY(before_output(i));
+            launch_dn_finish(c, frames[i], bands[i], c->dn.col[1].p);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipEventRecord(g->dn[i].done, c->stream));
+        }
+        if (timed) HIPCHK(c, hipEventRecord(g->dn[i].last, c->stream));
+        TRY(dn_call_done(c));
+    }
+    // 5. the other bands' output rows into the caller's buffers, on root's stream
+    fyprt_context* r = g->ctx[root];
+    HIPCHK(r, hipSetDevice(r->device));
+    for (int i = 0; i < n; ++i) {
+        if (i == root) continue;
+        fyprt_context* c = g->ctx[i];
+        HIPCHK(r, hipStreamWaitEvent(r->stream, g->dn[i].done, 0));
+        const size_t off = (size_t)bands[i].rowBegin * W, cnt = (size_t)(bands[i].rowEnd - bands[i].rowBegin) * W;
+        if (rgba8) HIPCHK(r, hipMemcpyPeerAsync(rgba8 + off, r->device, c->dn.outImg.p, c->device, cnt * sizeof(uint32_t), r->stream));
+        if (radiance4) HIPCHK(r, hipMemcpyPeerAsync(radiance4 + off, r->device, c->dn.outRad.p, c->device, cnt * sizeof(float4), r->stream));
+    }
+    HIPCHK(r, hipEventRecord(g->dn[root].collect, r->stream));
+    g->dnCalled = true; g->dnRoot = root;
+    for (fyprt_context* c : g->ctx) {
+        c->dtCur ^= 1; c->dtValid = true; c->dtGroup = g->id; c->dtSnapPending = false; std::memcpy(c->dtPV, c->framePV, 64);
+    }
+    return FYPRT_OK;
+}
+// A failed enqueue leaves some bands' new history written and others' not: the group's history is dropped instead.
+static int group_temporal_enqueue(fyprt_group* g, const fyprt_temporal_params* p, uint32_t historyRows, int root, uint32_t* rgba8, float4* radiance4, bool timed) {
+    const int rc = group_temporal_enqueue_all(g, p, historyRows, root, rgba8, radiance4, timed);
+    if (rc != FYPRT_OK) for (fyprt_context* c : g->ctx) c->drop_history();
+    return rc;
+}
+
+int fyprt_group_denoise_temporal(fyprt_group* g, const fyprt_temporal_params* p, uint32_t history_rows, uint32_t* rgba8, float* radiance4, float* band_ms) {
+    TRY(group_temporal_check(g, p, 0, rgba8, radiance4, false));
+    TRY(fyprt_group_synchronize(g));                               // as fyprt_group_denoise
+    fyprt_context* r = g->ctx[0];
+    HIPCHK(r, hipSetDevice(r->device));
+    const size_t npx = (size_t)r->W * r->H;
+    if (rgba8 && r->dn.outImg.n != npx) HIPCHK(r, r->dn.outImg.alloc(npx));
+    if (radiance4 && r->dn.outRad.n != npx) HIPCHK(r, r->dn.outRad.alloc(npx));
+    TRY(group_temporal_enqueue(g, p, history_rows, 0, rgba8 ? r->dn.outImg.p : nullptr, radiance4 ? r->dn.outRad.p : nullptr, true));
+    HIPCHK(r, hipSetDevice(r->device));
+    if (rgba8) HIPCHK(r, hipMemcpyAsync(rgba8, r->dn.outImg.p, npx * 4, hipMemcpyDeviceToHost, r->stream));
+    if (radiance4) HIPCHK(r, hipMemcpyAsync(radiance4, r->dn.outRad.p, npx * 16, hipMemcpyDeviceToHost, r->stream));
+    HIPCHK(r, hipStreamSynchronize(r->stream));
+    for (size_t i = 0; i < g->ctx.size(); ++i) {
+        fyprt_context* c = g->ctx[i];
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipEventSynchronize(g->dn[i].last));
+        if (band_ms) HIPCHK(c, hipEventElapsedTime(&band_ms[i], g->dn[i].first, g->dn[i].last));
+    }
+    return FYPRT_OK;
+}
+
+int fyprt_group_denoise_temporal_device(fyprt_group* g, const fyprt_temporal_params* p, uint32_t history_rows, int root, void* rgba8, void* radiance4) {
+    TRY(group_temporal_check(g, p, root, rgba8, radiance4, true));
+    return group_temporal_enqueue(g, p, history_rows, root, static_cast<uint32_t*>(rgba8), static_cast<float4*>(radiance4), false);
+}
+
+int fyprt_group_denoise_temporal_reset(fyprt_group* g) {
+    if (!g) return FYPRT_EINVAL;
+    for (fyprt_context* c : g->ctx) c->drop_history();
+    return FYPRT_OK;
+}
+
+// The transfers of one fyprt_group_denoise_temporal* call in issue order, entries as fyprt_group_denoise_plan's.
+int fyprt_group_denoise_temporal_plan(const uint32_t* row_bounds, int n, uint32_t height, uint32_t iterations, uint32_t history_rows, uint32_t* out5, int capacity) {
+    if (!row_bounds || n <= 0 || iterations > 8u || row_bounds[0] != 0 || row_bounds[n] != height) return FYPRT_EINVAL;
+    for (int i = 0; i < n; ++i) if (row_bounds[i] >= row_bounds[i + 1]) return FYPRT_EINVAL;
+    const std::vector<DnXfer> plan = group_temporal_plan(std::vector<uint32_t>(row_bounds, row_bounds + n + 1), height, iterations, history_rows);
     for (int k = 0; k < (int)plan.size() && k < capacity && out5; ++k) {
         const HaloXfer& x = plan[k].x;
         out5[5 * k] = (uint32_t)plan[k].stage; out5[5 * k + 1] = (uint32_t)x.receiver; out5[5 * k + 2] = (uint32_t)x.owner; out5[5 * k + 3] = x.r0; out5[5 * k + 4] = x.r1;

@@ -11,7 +11,7 @@
 //                    integrates colour and moments, takes the temporal variance where N >= 4 and, behind a wave-uniform test, the 5 x 5
 //                    spatial estimate where N < 4; writes the new history record, the integrated colour | its luminance and the variance.
 //   k_dt_iterate   : k_dn_iterate's two forms (STEP > 0: tile + halo staged in LDS, STEP == 0: gathered) on its tile skeleton — dn_tile_pos
-//                    from row 0 and dn_stage (rt_denoise.h) — with the variance in the staged record: dn_stage's hook puts it in the place
+//                    from the band's first row and dn_stage (rt_denoise.h) — with the variance in the staged record: dn_stage's hook puts it in the place
 //                    of the hit distance in the first quad, which only the centre needs and reads from memory, so the record stays
 //                    48 bytes and the LDS table and bank layout of DnTile hold as they are.  The tap loop is its own (dt_tap).  The 3 x 3
 //                    variance prefilter reads rows at distance 1, which a tile whose rows lie STEP apart does not hold: nine 4-byte
@@ -24,6 +24,8 @@
 //                    a wave that sees no moved triangle pays the byte alone.
 // Between the kernels the variance buffer holds -1 for a pixel that is not filterable (the record and the contract say 0 there): the
 // prefilter's taps then need no second load for the flag.
+// k_dt_reproject* and k_dt_iterate compute the rows of a DnBand as the a-trous set does (rt_denoise.h): the full frame is the band
+// [0, H) (fyprt_denoise_temporal*), a group's frame one band per context (fyprt_group_denoise_temporal*, fyprt_multi.h).
 #pragma once
 #include "rt_denoise.h"
 #include "rt_refit.h"
@@ -64,15 +66,20 @@ __global__ void __launch_bounds__(256) k_dt_moved(const DevVertex* __restrict__ 
 
 // The reprojection kernel's body.  MOTION: (Pq, nq) — the point and normal step 2 reprojects and tests with — are the hit's in the
 // snapshot geometry where its triangle moved; everything else, and every pixel of an unmoved triangle, is the plain form's arithmetic.
+// Computes the rows of `band` (the 16 x 16 tiles count from its first row; the grid covers its height) and takes history taps from the
+// rows of `win` only — the band's history window (include/fyprt.h, fyprt_group_denoise_temporal): two wave-uniform bounds in the place
+// of the image's.  The single context is the band [0, H) with the window [0, H).  Every buffer is full-size and indexed by the frame's
+// pixel; the 5 x 5 estimate reads guide and colour rows beyond the band where the host's peer copies put them.
 template <bool MOTION>
-RT_DEV void dt_reproject(const DnFrame& fr, const DtCall& tc, const DtMotion& mo, const float4* __restrict__ col0, const float4* __restrict__ histIn,
-                         float4* __restrict__ histOut, float4* __restrict__ colOut, float* __restrict__ varOut) {
+RT_DEV void dt_reproject(const DnFrame& fr, const DtCall& tc, const DtMotion& mo, DnBand band, DnBand win, const float4* __restrict__ col0,
+                         const float4* __restrict__ histIn, float4* __restrict__ histOut, float4* __restrict__ colOut, float* __restrict__ varOut) {
     const uint32_t tilesX = (fr.W + 15u) / 16u;
     const uint32_t bx = blockIdx.x % tilesX, by = blockIdx.x / tilesX;
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const int x = (int)(bx * 16u + ((wave & 1u) << 3) + (lane & 7u)), y = (int)(by * 16u + ((wave >> 1) << 3) + (lane >> 3));
-    if (x >= (int)fr.W || y >= (int)fr.H) return;
+    const int x = (int)(bx * 16u + ((wave & 1u) << 3) + (lane & 7u)), y = (int)(band.rowBegin + by * 16u + ((wave >> 1) << 3) + (lane >> 3));
+    if (x >= (int)fr.W || y >= (int)band.rowEnd) return;
     const int W = (int)fr.W, H = (int)fr.H;
+    const int winLo = (int)win.rowBegin, winHi = (int)win.rowEnd;
     const size_t i = (size_t)y * fr.W + (size_t)x;
     const float4 g0 = fr.guide[2 * i], g1 = fr.guide[2 * i + 1], ce = col0[i];
     const bool filterable = g1.w != 0.0f;
@@ -126,8 +133,8 @@ RT_DEV void dt_reproject(const DnFrame& fr, const DtCall& tc, const DtMotion& mo
                     const int dx = k & 1, dy = k >> 1;
                     const float b = (dx ? wx : 1.0f - wx) * (dy ? wy : 1.0f - wy);
                     const int qx = x0 + dx, qy = y0 + dy;
-                    const bool in = qx >= 0 && qy >= 0 && qx < W && qy < H;
-                    const size_t j = in ? (size_t)qy * fr.W + (size_t)qx : i;          // (outside: the centre's own address, selected away)
+                    const bool in = qx >= 0 && qy >= winLo && qx < W && qy < winHi;
+                    const size_t j = in ? (size_t)qy * fr.W + (size_t)qx : i;          // (outside the image or the window: the centre's own address, selected away)
                     const float4 h0 = histIn[4 * j], h1 = histIn[4 * j + 1], h2 = histIn[4 * j + 2], h3 = histIn[4 * j + 3];
                     const float dn = (nx * h1.x + ny * h1.y) + nz * h1.z;
                     const float ex = h0.x - Px, ey = h0.y - Py, ez = h0.z - Pz;
@@ -187,15 +194,17 @@ RT_DEV void dt_reproject(const DnFrame& fr, const DtCall& tc, const DtMotion& mo
     varOut[i] = filterable ? var : -1.0f;
 }
 
-__global__ void __launch_bounds__(256) k_dt_reproject(DnFrame fr, DtCall tc, const float4* __restrict__ col0, const float4* __restrict__ histIn,
-                                                      float4* __restrict__ histOut, float4* __restrict__ colOut, float* __restrict__ varOut) {
-    dt_reproject<false>(fr, tc, DtMotion{}, col0, histIn, histOut, colOut, varOut);
+__global__ void __launch_bounds__(256) k_dt_reproject(DnFrame fr, DtCall tc, DnBand band, DnBand win, const float4* __restrict__ col0,
+                                                      const float4* __restrict__ histIn, float4* __restrict__ histOut,
+                                                      float4* __restrict__ colOut, float* __restrict__ varOut) {
+    dt_reproject<false>(fr, tc, DtMotion{}, band, win, col0, histIn, histOut, colOut, varOut);
 }
-__global__ void __launch_bounds__(256) k_dt_reproject_motion(DnFrame fr, DtCall tc, DtMotion mo, const float4* __restrict__ col0,
+__global__ void __launch_bounds__(256) k_dt_reproject_motion(DnFrame fr, DtCall tc, DtMotion mo, DnBand band, DnBand win, const float4* __restrict__ col0,
                                                              const float4* __restrict__ histIn, float4* __restrict__ histOut,
                                                              float4* __restrict__ colOut, float* __restrict__ varOut) {
-    dt_reproject<true>(fr, tc, mo, col0, histIn, histOut, colOut, varOut);
+    dt_reproject<true>(fr, tc, mo, band, win, col0, histIn, histOut, colOut, varOut);
 }
+inline uint32_t dt_reproject_grid(uint32_t W, uint32_t rows) { return ((W + 15u) / 16u) * ((rows + 15u) / 16u); }
 
 struct DtSums { float r, g, b, w, v; };
 // dn_tap with the centre's own luminance scale and the variance sum; vq = the tap's variance
@@ -213,17 +222,20 @@ RT_DEV void dt_tap(const DnIter& it, const float4& c0, const float4& c1, float s
     if (use) { s.r = s.r + cq.x * w; s.g = s.g + cq.y * w; s.b = s.b + cq.z * w; s.w = s.w + w; s.v = s.v + vq * (w * w); }
 }
 
-// Grid, tiles and staging as k_dn_iterate<STEP> (dn_grid, DnTile, dn_tile_pos, dn_stage), the whole frame.  it.sigmaL = sigma_luminance
+// Grid, tiles, staging and the band as k_dn_iterate<STEP> (dn_grid of the band's height, DnTile, dn_tile_pos from band.rowBegin, dn_stage):
+// pixels below band.rowEnd leave, and so does the feedback write; taps, and the prefilter's, read the colour, variance (-1 = not
+// filterable, as its owner wrote it) and guide rows beyond the band where the host's peer copies put them.  it.sigmaL = sigma_luminance
 // itself (the variance carries the scale).  histOut: the new history, or null — iteration 0 of a call with feedback writes its colour there.
 template <int STEP>
-__global__ void __launch_bounds__(256) k_dt_iterate(DnFrame fr, DnIter it, const float4* __restrict__ colIn, float4* __restrict__ colOut,
+__global__ void __launch_bounds__(256) k_dt_iterate(DnFrame fr, DnIter it, DnBand band, const float4* __restrict__ colIn, float4* __restrict__ colOut,
                                                     const float* __restrict__ varIn, float* __restrict__ varOut, float4* __restrict__ histOut) {
     using T = DnTile<STEP>;
     __shared__ float4 sG0[T::RECORDS], sG1[T::RECORDS], sC[T::RECORDS];     // sG0.w = the variance (not the hit distance)
-    const DnTilePos tp = dn_tile_pos<STEP>(fr.W, 0);
+    const DnTilePos tp = dn_tile_pos<STEP>(fr.W, (int)band.rowBegin);
+    if (tp.yBase >= (int)band.rowEnd) return;                                    // (the whole workgroup: before anything is staged)
     const int lx = tp.lx, ly = tp.ly, x = tp.x, y = tp.y;
     if (STEP) dn_stage<STEP>(fr, colIn, tp.xBase, tp.yBase, sG0, sG1, sC, [&](float4& g0, size_t j) { g0.w = varIn[j]; });
-    if (x >= (int)fr.W || y >= (int)fr.H) return;
+    if (x >= (int)fr.W || y >= (int)band.rowEnd) return;
     const uint32_t i = (uint32_t)y * fr.W + (uint32_t)x;
     const int lc = (ly + 2) * T::STRIDE + lx + 2 * T::S;
     const float4 c0 = STEP ? sG0[lc] : fr.guide[2 * (size_t)i];

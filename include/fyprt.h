@@ -566,7 +566,8 @@ int fyprt_denoise_device(fyprt_context* ctx, const fyprt_denoise_params* params,
  * fyprt_denoise_temporal_reset.  (fyprt_denoise_temporal_set_motion, below, lets the history live through the two geometry edits.)
  * Errors, in this order: FYPRT_EINVAL for a NULL context / params, history_limit outside 1..256, feedback > 1, normal_min or plane_max
  * not finite, plane_max <= 0; then everything fyprt_denoise refuses, in its order, with params->spatial (its FYPRT_EINVAL cases, then
- * its FYPRT_ESTATE cases).  Multi-GPU bands are out of scope (fyprt_group_denoise has no temporal form).
+ * its FYPRT_ESTATE cases).  The bands of a group are denoised by fyprt_group_denoise_temporal (multi-GPU section), whose contract is this
+ * one with one more term, the band's history window.
  * No frame state moves, as for fyprt_denoise, and the two denoisers do not disturb each other: the history lives in buffers of its own
  * (two of 64 B and two of 4 B per pixel, allocated on the first temporal call, dropped by fyprt_resize); the guide, albedo and colour
  * buffers of fyprt_denoise are shared scratch, and FYPRT_BUF_ALBEDO is written by either.
@@ -663,6 +664,48 @@ int fyprt_group_synchronize(fyprt_group* group);
 int fyprt_group_denoise(fyprt_group* group, const fyprt_denoise_params* params, uint32_t* rgba8, float* radiance4, float* band_ms);
 /* Device memory on context `root`'s GPU, asynchronous: complete on root's stream (fyprt_stream of that context); no host wait. */
 int fyprt_group_denoise_device(fyprt_group* group, const fyprt_denoise_params* params, int root, void* rgba8, void* radiance4);
+/* fyprt_denoise_temporal for the frames the group renders: every context keeps the history of its own rows, reprojects and filters its
+ * band, and pulls what its kernels read beyond the band from the rows' owners.  A history tap may lie anywhere the camera motion points,
+ * so the rows of history a band can see are bounded, and the bound is part of the contract.
+ * The contract.  Band k owns the rows [b, e); R = min(history_rows, height); its HISTORY WINDOW is the rows [max(0, b - R), min(height,
+ * e + R)).  The output rows and the history records of band k are fyprt_denoise_temporal's contract, steps 1 to 6, evaluated on the
+ * stitched frame (every band's accumulation, payload and history rows taken from their owners, the same frame index n), with one
+ * addition in step 2: a tap q of a pixel p is valid only if its row also lies inside the history window of the band that owns p.  For
+ * its own pixels the band sees a history in which every record outside its window is not filterable.  Nothing else changes: the 5 x 5
+ * estimate of step 4, the 3 x 3 variance prefilter and the a-trous taps of step 5 read the real neighbours across band borders — a
+ * neighbour in another band enters them as its owner computed it, under that band's window.
+ *   So: if every otherwise valid tap of every pixel lies inside its band's window, the outputs and the stitched FYPRT_BUF_TEMPORAL are, bit
+ *   for bit, those of fyprt_denoise_temporal on a single context running the same sequence; history_rows >= height guarantees it
+ *   unconditionally.  A pixel whose reprojection leaves the window starts over with N = 1, as a disocclusion does; history_rows is the
+ *   control.  FYPRT_GROUP_HISTORY_ROWS is derived, not measured: at 64 B per pixel, 32 rows are the bytes the spatial call already pulls
+ *   per band side at its default 5 iterations (32 rows of 32 B guide records + 62 rows of 16 B colour: 3.9 MB at 1080p), so the temporal
+ *   call at most doubles the traffic per side.
+ * Whose history.  The history belongs to the group.  A call finds one only if every member holds a history written by this group's
+ * previous successful temporal call (or moved by fyprt_group_set_rows since) and all members keep the same projection x view, bit for
+ * bit, for the frame that call denoised.  Otherwise the call is a first call on every member: whatever drops one member's history
+ * (fyprt_resize, fyprt_upload_scene, the edits, fyprt_denoise_temporal_reset, a change of the motion mode) or replaces it (a
+ * single-context temporal call before the context joined the group) makes the next group call a first call for the whole group.
+ * fyprt_group_denoise_temporal_reset drops every member's history.  After a call FYPRT_BUF_TEMPORAL is valid on every member for its
+ * own rows, FYPRT_BUF_ALBEDO as after fyprt_group_denoise.  fyprt_denoise_temporal* on a group member stays refused.
+ * Rows that change owner.  While the group holds a history, fyprt_group_set_rows also moves the 64-byte history records of the rows
+ * that change owner, from the old owner's current history buffer into the new owner's, beside the accumulation and the ReSTIR records.
+ * With history_rows >= height a sequence with moving borders therefore stays the single-context sequence.  A group without a temporal
+ * history moves exactly what it moved before.
+ * Object motion.  fyprt_denoise_temporal_set_motion stays per context (and so does the scene: the caller applies every edit to every
+ * member).  A group call requires every member in the same mode and the same snapshot state (pending or not).  With a snapshot pending
+ * every band runs the motion form on its rows, and every member consumes its snapshot.
+ * Errors, in this order: FYPRT_EINVAL for a NULL group / params; fyprt_denoise_temporal's parameter cases (its own, then the spatial
+ * part's); fyprt_group_denoise's remaining FYPRT_EINVAL cases (root, alignment, both outputs NULL); FYPRT_ESTATE for
+ * fyprt_group_denoise's state cases in its order; for members whose last frames differ in camera matrix; for members that differ in
+ * motion mode or snapshot state.  The message is the offending member's.  A refused call drops nothing.
+ * Outputs, root, band_ms, alignment and "no frame state moves on any member" are exactly fyprt_group_denoise's.  The history and
+ * variance buffers are those of fyprt_denoise_temporal, full-size per member.
+ * Out of scope: an RCCL transport (fyprt_comm_*), striped frames (refused, as by fyprt_group_denoise), and a window that sizes itself
+ * from the camera motion (it would need a host wait). */
+#define FYPRT_GROUP_HISTORY_ROWS 32u
+int fyprt_group_denoise_temporal(fyprt_group* group, const fyprt_temporal_params* params, uint32_t history_rows, uint32_t* rgba8, float* radiance4, float* band_ms);
+int fyprt_group_denoise_temporal_device(fyprt_group* group, const fyprt_temporal_params* params, uint32_t history_rows, int root, void* rgba8, void* radiance4);
+int fyprt_group_denoise_temporal_reset(fyprt_group* group);
 /* --- one process per GPU: RCCL over xGMI (librccl.so.1 is opened on first use).  Rank 0 calls fyprt_comm_unique_id and hands
  *     the 128 bytes to the other ranks (any transport); every rank then calls fyprt_comm_init_rank on its resized context. */
 int fyprt_comm_unique_id(void* id128);
@@ -688,6 +731,12 @@ int fyprt_halo_plan(const uint32_t* row_bounds, int n, uint32_t halo, uint32_t h
  * pixel), 2^(k+1) rows; clipped to the image.  Pure host arithmetic.  Returns the number of entries (also when `capacity` is smaller;
  * nothing is written beyond it), FYPRT_EINVAL for a bad table or iterations > 8. */
 int fyprt_group_denoise_plan(const uint32_t* row_bounds, int n, uint32_t height, uint32_t iterations, uint32_t* out5, int capacity);
+/* The transfers of one fyprt_group_denoise_temporal* call in issue order, entries as above, sized by what each kernel reads.  Stage 0:
+ * the guide records (32 B), max(2, 2^iterations) rows — the 5 x 5 estimate of step 4 reads 2 rows even without an iteration; stage 1: the
+ * prepared colour e0 | L (16 B), 2 rows (step 4's L_q); stage 2: the history (64 B), min(history_rows, height) rows — listed for the
+ * history_rows given, a call without a history skips it; stage 3 + k: the colour (16 B) and the variance (4 B) iteration k reads,
+ * 2^(k+1) rows.  Pure host arithmetic; returns and errors as fyprt_group_denoise_plan. */
+int fyprt_group_denoise_temporal_plan(const uint32_t* row_bounds, int n, uint32_t height, uint32_t iterations, uint32_t history_rows, uint32_t* out5, int capacity);
 /* The point-to-point operations rank `rank` issues inside ONE RCCL group section, in issue order — kind 0: a halo exchange over
  * `row_bounds`; kind 1: fyprt_comm_set_rows from `row_bounds` to `new_bounds`.  (is_recv, peer, buffer, byte offset, bytes) per
  * operation; returns their number.  Pure host arithmetic (no device, no RCCL): lets a test check that the two ends of every pair of
