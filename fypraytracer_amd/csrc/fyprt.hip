@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 #include "rt_host.h"
@@ -2204,6 +2205,25 @@ static void launch_dt_iterate(fyprt_context* c, const DnFrame& fr, const DnIter&
         hipLaunchKernelGGL(k_dt_iterate<STEP>, dim3(dn_grid<STEP>(fr.W, band.rowEnd - band.rowBegin)), dim3(256), 0, c->stream, fr, it, band, in, out, vin, vout, fb);
     });
 }
+// Object motion is at work in a call: there is a history to reproject, and a vertex snapshot with an edited range is pending.
+static bool dt_motion_pending(const fyprt_context* c, bool history) { return history && c->dtSnapPending && c->dtEditHi > c->dtEditLo; }
+// The moved flags of the edited range (only while dt_motion_pending), on the context stream
+static void launch_dt_moved(fyprt_context* c) {
+    const uint32_t count = c->dtEditHi - c->dtEditLo;
+    hipLaunchKernelGGL(k_dt_moved, dim3((count + 255u) / 256u), dim3(256), 0, c->stream, c->dverts.p, c->dtSnap.p, c->triIdx.p, c->dtMoved.p, c->dtEditLo, count);
+}
+// The reprojection on the rows of `band`, its history taps within `window` (the whole frame: both {0, H}), in its motion form after
+// launch_dt_moved: dn.col[0] and dt.hist[dtCur] -> dt.hist[dtCur ^ 1], dn.col[1], dt.var[0]
+static void launch_dt_reproject(fyprt_context* c, const DnFrame& fr, const DtCall& tc, DnBand band, DnBand window, bool motion) {
+    const dim3 grid(dt_reproject_grid(fr.W, band.rowEnd - band.rowBegin));
+    const float4* histIn = c->dt.hist[c->dtCur].p; float4* histOut = c->dt.hist[c->dtCur ^ 1].p;
+    if (motion) {
+        const DtMotion mo{c->payload.p, c->dtMoved.p, c->triIdx.p, c->triPos.p, c->dtSnap.p};
+        hipLaunchKernelGGL(k_dt_reproject_motion, grid, dim3(256), 0, c->stream, fr, tc, mo, band, window, c->dn.col[0].p, histIn, histOut, c->dn.col[1].p, c->dt.var[0].p);
+    } else {
+        hipLaunchKernelGGL(k_dt_reproject, grid, dim3(256), 0, c->stream, fr, tc, band, window, c->dn.col[0].p, histIn, histOut, c->dn.col[1].p, c->dt.var[0].p);
+    }
+}
 // The history and variance buffers of a context (a new size drops the history)
 static int ensure_dt_buffers(fyprt_context* c) {
     const size_t n = (size_t)c->W * c->H;
@@ -2233,16 +2253,9 @@ static int enqueue_temporal(fyprt_context* c, const fyprt_temporal_params* p, ui
     const int next = c->dtCur ^ 1;
     float4* hist = c->dt.hist[next].p;
     const DnBand all{0, c->H};
-    const dim3 grid(dt_reproject_grid(c->W, c->H));
-    if (c->dtValid && c->dtSnapPending && c->dtEditHi > c->dtEditLo) {       // object motion: the flags of the edited range, then the motion form
-        const uint32_t count = c->dtEditHi - c->dtEditLo;
-        hipLaunchKernelGGL(k_dt_moved, dim3((count + 255u) / 256u), dim3(256), 0, c->stream, c->dverts.p, c->dtSnap.p, c->triIdx.p, c->dtMoved.p, c->dtEditLo, count);
-        ++*launched;
-        const DtMotion mo{c->payload.p, c->dtMoved.p, c->triIdx.p, c->triPos.p, c->dtSnap.p};
-        hipLaunchKernelGGL(k_dt_reproject_motion, grid, dim3(256), 0, c->stream, fr, tc, mo, all, all, c->dn.col[0].p, c->dt.hist[c->dtCur].p, hist, c->dn.col[1].p, c->dt.var[0].p);
-    } else {
-        hipLaunchKernelGGL(k_dt_reproject, grid, dim3(256), 0, c->stream, fr, tc, all, all, c->dn.col[0].p, c->dt.hist[c->dtCur].p, hist, c->dn.col[1].p, c->dt.var[0].p);
-    }
+    const bool motion = dt_motion_pending(c, c->dtValid);      // object motion: the flags of the edited range, then the motion form
+    if (motion) { launch_dt_moved(c); ++*launched; }
+    launch_dt_reproject(c, fr, tc, all, all, motion);
     ++*launched;
     if (ev) HIPCHK(c, hipEventRecord(ev[2], c->stream));
     for (uint32_t k = 0; k < sp.iterations; ++k) {           // colour: dn.col[1] -> [0] -> [1] ...; variance: dt.var[0] -> [1] -> [0] ...

@@ -19,9 +19,9 @@
 //                   between the contexts' buffers, ordered with events — no collective library at all;
 //   fyprt_comm_*    one process per GPU (torch.distributed.run, MPI, ...): RCCL — grouped ncclSend / ncclRecv for the halos, grouped
 //                   ncclBroadcast (one per band, in place in the full-size image) for the gather.  librccl.so.1 is opened on first use.
-// fyprt_group_denoise* (below fyprt_group_synchronize): the a-trous denoiser on the same bands, by the same peer copies and events.
-// fyprt_group_denoise_temporal* (below it): the temporal denoiser on the same bands; the history stays with the rows' owners, a band reads
-// it inside its history window, and fyprt_group_set_rows moves it with the rows.
+// fyprt_group_denoise* and fyprt_group_denoise_temporal* (below fyprt_group_synchronize): the a-trous and the temporal denoiser on the same
+// bands, by the same peer copies and events — two lists of steps for one schedule, group_filter_enqueue.  The temporal history stays with
+// the rows' owners, a band reads it inside its history window, and fyprt_group_set_rows moves it with the rows.
 #include <dlfcn.h>
 
 extern "C++" {
@@ -81,6 +81,14 @@ std::vector<DnXfer> group_temporal_plan(const std::vector<uint32_t>& bounds, uin
         for (const HaloXfer& x : halo_plan(bounds, 2u << k, H, false)) plan.push_back({3 + (int)k, x});
     return plan;
 }
+// a plan as the _plan entries hand it out: (stage, receiver, owner, first row, end row) per entry; returns the number of entries
+int export_plan(const std::vector<DnXfer>& plan, uint32_t* out5, int capacity) {
+    for (int k = 0; k < (int)plan.size() && k < capacity && out5; ++k) {
+        const HaloXfer& x = plan[k].x;
+        out5[5 * k] = (uint32_t)plan[k].stage; out5[5 * k + 1] = (uint32_t)x.receiver; out5[5 * k + 2] = (uint32_t)x.owner; out5[5 * k + 3] = x.r0; out5[5 * k + 4] = x.r1;
+    }
+    return (int)plan.size();
+}
 
 struct XBuf { void* p; size_t bytesPerPixel; };
 // what crosses between Part 1 and Part 2 (kind 0) / before Part 1 (kind 1: temporal history), for the technique
@@ -99,6 +107,32 @@ std::vector<XBuf> exchange_buffers(fyprt_context* c, int tech, int kind) {
         }
     }
     return v;
+}
+// what a row takes with it when it changes owner (fyprt_group_set_rows, fyprt_comm_set_rows): its accumulation — unless the last frame was
+// interleaved: that accumulation lives in stripes, not in bands, and every context keeps its stripes — and its temporal history: the
+// ReSTIR DI records, the ReSTIR GI reservoirs and the previous normals
+std::vector<XBuf> row_buffers(fyprt_context* c, bool lastStriped) {
+    std::vector<XBuf> v;
+    if (!lastStriped) v.push_back({c->accum.p, sizeof(float4)});
+    v.push_back({c->dprevFlip ? (void*)c->dprevB.p : (void*)c->dprevA.p, sizeof(DIRec)});
+    v.push_back({c->giPrev.p, sizeof(GIRes)});
+    v.push_back({c->normalFlip ? (void*)c->normalB.p : (void*)c->normalA.p, sizeof(f2)});
+    return v;
+}
+// rows [r0, r1) of a full-size buffer (W pixels of bytesPerPixel a row) of context `o` into the same rows of context `c`'s, on `stream`
+hipError_t copy_rows(const fyprt_context* c, void* dst, const fyprt_context* o, const void* src, uint32_t r0, uint32_t r1, uint32_t W, size_t bytesPerPixel, hipStream_t stream) {
+    const size_t off = (size_t)r0 * W * bytesPerPixel;
+    return hipMemcpyPeerAsync((char*)dst + off, c->device, (const char*)src + off, o->device, (size_t)(r1 - r0) * W * bytesPerPixel, stream);
+}
+// The check of a band table, for every entry that takes one: its ends are rows 0 and H, and no band is empty or out of order.  Each
+// returns the text of what is wrong, or null; bad_bands looks at the ends first, then at every band, and says in `at` whose fault it is.
+const char* bad_ends(const uint32_t* b, int n, uint32_t H) { return (b[0] != 0 || b[n] != H) ? ": the bands must partition rows 0..height" : nullptr; }
+const char* bad_band(const uint32_t* b, int i) { return b[i] >= b[i + 1] ? ": empty or unordered band" : nullptr; }
+const char* bad_bands(const uint32_t* b, int n, uint32_t H, int* at) {
+    *at = 0;
+    if (const char* t = bad_ends(b, n, H)) return t;
+    for (; *at < n; ++*at) if (const char* t = bad_band(b, *at)) return t;
+    return nullptr;
 }
 bool is_restir(const fyprt_settings* s) { return s->technique == FYPRT_RESTIR_DI || s->technique == FYPRT_RESTIR_GI; }
 // stripes of part `part` of an interleaved split, as (first row, end row) — the same walk as stripe_row_count
@@ -221,9 +255,9 @@ int fyprt_group_create(fyprt_context** ctxs, int n, const uint32_t* row_bounds, 
     for (int i = 0; i < n; ++i) {
         if (!ctxs[i] || ctxs[i]->hostOnly || ctxs[i]->H == 0) return FYPRT_EINVAL;
         if (ctxs[i]->W != ctxs[0]->W || ctxs[i]->H != ctxs[0]->H) return ctxs[i]->fail(FYPRT_EINVAL, "fyprt_group_create: contexts differ in size");
-        if (row_bounds[i] >= row_bounds[i + 1]) return ctxs[i]->fail(FYPRT_EINVAL, "fyprt_group_create: empty or unordered band");
+        if (const char* bad = bad_band(row_bounds, i)) return ctxs[i]->fail(FYPRT_EINVAL, std::string("fyprt_group_create") + bad);
     }
-    if (row_bounds[0] != 0 || row_bounds[n] != ctxs[0]->H) return ctxs[0]->fail(FYPRT_EINVAL, "fyprt_group_create: the bands must partition rows 0..height");
+    if (const char* bad = bad_ends(row_bounds, n, ctxs[0]->H)) return ctxs[0]->fail(FYPRT_EINVAL, std::string("fyprt_group_create") + bad);
     auto* g = new fyprt_group();
     g->ctx.assign(ctxs, ctxs + n); g->bounds.assign(row_bounds, row_bounds + n + 1);
     g->ev.resize(n); g->dn.resize(n); g->id = ++g_groupSerial;
@@ -253,25 +287,25 @@ int fyprt_group_set_rows(fyprt_group* g, const uint32_t* row_bounds) {
     if (!g || !row_bounds) return FYPRT_EINVAL;
     const int n = (int)g->ctx.size();
     const uint32_t W = g->ctx[0]->W;
-    if (row_bounds[0] != 0 || row_bounds[n] != g->ctx[0]->H) return g->ctx[0]->fail(FYPRT_EINVAL, "fyprt_group_set_rows: the bands must partition rows 0..height");
-    for (int i = 0; i < n; ++i) if (row_bounds[i] >= row_bounds[i + 1]) return g->ctx[i]->fail(FYPRT_EINVAL, "fyprt_group_set_rows: empty or unordered band");
+    int at;
+    if (const char* bad = bad_bands(row_bounds, n, g->ctx[0]->H, &at)) return g->ctx[at]->fail(FYPRT_EINVAL, std::string("fyprt_group_set_rows") + bad);
     TRY(fyprt_group_synchronize(g));
     const bool history = group_has_history(g);
+    auto moving = [&](fyprt_context* c) {                             // per context: the flips of its ping-pong buffers are its own
+        std::vector<XBuf> v = row_buffers(c, g->lastStriped);
+        if (history) v.push_back({c->dt.hist[c->dtCur].p, kDtHistoryBytes});
+        return v;
+    };
     for (int k = 0; k < n; ++k) {
         fyprt_context* c = g->ctx[k];
         HIPCHK(c, hipSetDevice(c->device));
+        const std::vector<XBuf> mine = moving(c);
         for (int j = 0; j < n; ++j) {
             if (j == k) continue;
             const uint32_t r0 = std::max(row_bounds[k], g->bounds[j]), r1 = std::min(row_bounds[k + 1], g->bounds[j + 1]);
             if (r0 >= r1) continue;                                   // rows [r0, r1): owned by j so far, by k from now on
-            fyprt_context* o = g->ctx[j];
-            auto move = [&](void* dst, const void* src, size_t bpp) { return hipMemcpyPeerAsync((char*)dst + (size_t)r0 * W * bpp, c->device, (const char*)src + (size_t)r0 * W * bpp, o->device, (size_t)(r1 - r0) * W * bpp, c->stream); };
-            // (the accumulation of an interleaved frame lives in stripes, not in bands: nothing to move — every context keeps its stripes)
-            if (!g->lastStriped) HIPCHK(c, move(c->accum.p, o->accum.p, sizeof(float4)));
-            HIPCHK(c, move(c->dprevFlip ? c->dprevB.p : c->dprevA.p, o->dprevFlip ? o->dprevB.p : o->dprevA.p, sizeof(DIRec)));
-            HIPCHK(c, move(c->giPrev.p, o->giPrev.p, sizeof(GIRes)));
-            HIPCHK(c, move(c->normalFlip ? c->normalB.p : c->normalA.p, o->normalFlip ? o->normalB.p : o->normalA.p, sizeof(f2)));
-            if (history) HIPCHK(c, move(c->dt.hist[c->dtCur].p, o->dt.hist[o->dtCur].p, kDtHistoryBytes));
+            const std::vector<XBuf> theirs = moving(g->ctx[j]);
+            for (size_t b = 0; b < mine.size(); ++b) HIPCHK(c, copy_rows(c, mine[b].p, g->ctx[j], theirs[b].p, r0, r1, W, mine[b].bytesPerPixel, c->stream));
         }
     }
     TRY(fyprt_group_synchronize(g));
@@ -331,10 +365,7 @@ int fyprt_group_render(fyprt_group* g, const fyprt_settings* s) {
             HIPCHK(c, hipStreamWaitEvent(c->stream, g->ev[x.owner].*ready, 0));
             if (kind == 1) HIPCHK(c, hipStreamWaitEvent(c->stream, g->ev[x.owner].sync, 0));      // the owner's history is in step with the technique
             const std::vector<XBuf> theirs = exchange_buffers(o, s->technique, kind);
-            for (size_t b = 0; b < mine.size(); ++b) {
-                const size_t off = (size_t)x.r0 * W * mine[b].bytesPerPixel, bytes = (size_t)(x.r1 - x.r0) * W * mine[b].bytesPerPixel;
-                HIPCHK(c, hipMemcpyPeerAsync((char*)mine[b].p + off, c->device, (const char*)theirs[b].p + off, o->device, bytes, c->stream));
-            }
+            for (size_t b = 0; b < mine.size(); ++b) HIPCHK(c, copy_rows(c, mine[b].p, o, theirs[b].p, x.r0, x.r1, W, mine[b].bytesPerPixel, c->stream));
         }
         return FYPRT_OK;
     };
@@ -381,10 +412,7 @@ int fyprt_group_gather(fyprt_group* g, int root) {
         HIPCHK(r, hipStreamWaitEvent(r->stream, g->ev[i].frame, 0));
         const uint32_t* src = c->externalImage ? c->externalImage : c->image.p;
         hipError_t e = hipSuccess;
-        auto rows = [&](uint32_t r0, uint32_t r1) {
-            const size_t off = (size_t)r0 * r->W, cnt = (size_t)(r1 - r0) * r->W;
-            if (e == hipSuccess) e = hipMemcpyPeerAsync(dst + off, r->device, src + off, c->device, cnt * 4, r->stream);
-        };
+        auto rows = [&](uint32_t r0, uint32_t r1) { if (e == hipSuccess) e = copy_rows(r, dst, c, src, r0, r1, r->W, sizeof(uint32_t), r->stream); };
         if (g->lastStriped) for_each_stripe(r->H, g->lastStripeRows, (uint32_t)g->ctx.size(), (uint32_t)i, rows);
         else rows(g->bounds[i], g->bounds[i + 1]);
         HIPCHK(r, e);
@@ -426,21 +454,48 @@ static int group_denoise_check(fyprt_group* g, const fyprt_denoise_params* p, in
     return group_denoise_check_call(g, who, root, rgba8, radiance4, device);
 }
 
-// Enqueues one call on every band's stream and the collect on root's; no host wait (but before a staging buffer is reallocated).
-// rgba8 / radiance4: device memory of root's GPU.  Hazards, and the event that orders each:
-//   read after write   a pull of stage 1 + k reads the owner's rows of the colour buffer its iteration k - 1 wrote (its prepare for k = 0,
-//                      and for the guide records of stage 0): it waits for the owner's `done`, recorded after each of these launches;
-//   write after read   iteration k writes the ping-pong buffer the neighbours pulled from at stage k (before their iteration k - 1): it
-//                      waits for the `pulled` of every band that pulls from this one, as recorded after stage k;
-//   across calls       a later call (or the same call of the next frame of a pipelined sequence) may be enqueued while neighbours still
-//                      pull from this one: the first work of a call on a band waits for every other band's last `pulled` of the earlier
-//                      call; the kernel that writes the staging rows waits for the earlier root's `collect`; and the front stream
-//                      waits for the band's last kernel before the next pipelined frame's Part 1 overwrites the payload
-//                      (dn_call_done).
-static int group_denoise_enqueue(fyprt_group* g, const fyprt_denoise_params* p, int root, uint32_t* rgba8, float4* radiance4, bool timed) {
+// ---- group_filter_enqueue: one filter call on the group's bands, which both denoisers enqueue with.  A call is a plan — which rows a
+// band pulls from which owner at which stage — and a list of steps; the engine below runs the steps in order, each on every band
+// before the next on any (the waits of a step resolve to the records of the step before, so the host's issue order is part of it):
+//   1. if the step's launch overwrites rows that neighbours pulled earlier: every band waits for the `pulled` of the bands that pull from it;
+//   2. if the step pulls a plan stage: every band copies that stage's rows from their owners, after the owner's `done`, and records `pulled`
+//      (also when it had nothing to pull);
+//   3. if the step launches: every band launches and, unless the step says otherwise, records `done`.
+// Around them: the members' buffers, events and output rows (a non-root band writes a staging buffer of its size; the kernels index the
+// whole frame, so they get the address row 0 would have), the first work of the call, the end of a band, and the collect of the staging
+// rows on root's stream.  No host wait but before a staging buffer is reallocated.  rgba8 / radiance4: device memory of root's GPU.
+// Hazards, and the event that orders each:
+//   read after write   a pull reads rows the owner's latest kernel wrote — the prepared colour and the guide records (prepare), the colour
+//                      (and, temporal, the variance) the iteration before or the reprojection wrote, the history the call before wrote
+//                      (which the owner's stream orders before its prepare): it waits for the owner's `done`, recorded after each of
+//                      these launches.  A launch nothing pulls from (k_dt_moved) records none, and the `done` a pull after it waits
+//                      for is the owner's latest earlier one;
+//   write after read   an iteration writes the ping-pong buffers the iteration before read, which the neighbours pulled from one stage
+//                      earlier (spatial: iteration k > 0 writes what stage k moved, and iteration 0 writes dn.col[1], which nothing pulled
+//                      in this call; temporal: iteration k overwrites colour and variance of stage 3 + k - 1, and iteration 0 the
+//                      prepared colour of stage 1): it waits for the last `pulled` of every band that pulls from this one, as recorded
+//                      after that stage or a later one;
+//   the history        ping-pongs per member: a temporal call writes dt.hist[dtCur ^ 1], the buffer the neighbours' stage 2 of the call
+//                      before pulled from.  The first work of a call on a band waits for every other band's last `pulled` of the earlier
+//                      call — recorded after that call's last stage, so after its stage 2 — which also covers the colour, variance and
+//                      guide buffers;
+//   across calls       a later call of either denoiser (or the same call of the next frame of a pipelined sequence) may be enqueued
+//                      while neighbours still pull from this band: the first-work wait above; the kernel that writes the staging rows
+//                      waits for the earlier root's `collect`, which may still read them; and the front stream waits for the band's last
+//                      kernel before the next pipelined frame's Part 1 overwrites the payload (dn_call_done).
+struct BandStep {
+    int pulls;                                                        // the plan stage every band pulls before the launch, or -1,
+    std::function<std::vector<XBuf>(fyprt_context*)> moved;           // and the buffers it moves: the receiver's and, in the same order, the owner's
+    bool overwritesPulled;                                            // the launch overwrites rows the neighbours pulled earlier
+    bool writesOutput;                                                // the launch writes the output rows
+    std::function<void(fyprt_context*, const DnFrame&, DnBand)> launch;      // on a band's rows, on its context's stream; empty: the step only pulls
+    bool recordsDone;                                                 // `done` is recorded after the launch: a pull reads what it wrote
+};
+// The first step must not pull: the first-work wait goes with its launch (both denoisers start with prepare).
+static int group_filter_enqueue(fyprt_group* g, const std::vector<DnXfer>& plan, const std::vector<BandStep>& steps, uint32_t demodulate, int root,
+                                uint32_t* rgba8, float4* radiance4, bool timed) {
     const int n = (int)g->ctx.size();
-    const uint32_t W = g->ctx[0]->W, H = g->ctx[0]->H;
-    const std::vector<DnXfer> plan = group_denoise_plan(g->bounds, H, p->iterations);
+    const uint32_t W = g->ctx[0]->W;
     std::vector<char> pullsFrom((size_t)n * n, 0);                // [owner * n + receiver]
     for (const DnXfer& t : plan) pullsFrom[(size_t)t.x.owner * n + t.x.receiver] = 1;
     std::vector<DnFrame> frames(n); std::vector<DnBand> bands(n);
@@ -454,10 +509,10 @@ static int group_denoise_enqueue(fyprt_group* g, const fyprt_denoise_params* p, 
         const uint32_t b = g->bounds[i], rows = g->bounds[i + 1] - b;
         bands[i] = DnBand{b, g->bounds[i + 1]};
         DnFrame& fr = frames[i];
-        fr = dn_frame(c, p->demodulate_albedo, i == root ? rgba8 : nullptr, i == root ? radiance4 : nullptr);
+        fr = dn_frame(c, demodulate, i == root ? rgba8 : nullptr, i == root ? radiance4 : nullptr);
         if (i == root) continue;
-        // the band's output rows go to its staging (at least the band's size); the kernels index the whole frame, so they get the address
-        // row 0 would have.  A buffer the earlier root may still read is not freed under it.
+        // the band's output rows go to its staging (at least the band's size), biased to row 0.  A buffer the earlier root may still read
+        // is not freed under it.
         const size_t need = (size_t)rows * W;
         if ((rgba8 && c->dn.outImg.n < need) || (radiance4 && c->dn.outRad.n < need)) {
             if (g->dnRoot >= 0) HIPCHK(c, hipEventSynchronize(g->dn[g->dnRoot].collect));
@@ -467,95 +522,83 @@ static int group_denoise_enqueue(fyprt_group* g, const fyprt_denoise_params* p, 
         if (rgba8) fr.rgba8 = reinterpret_cast<uint32_t*>(reinterpret_cast<uintptr_t>(c->dn.outImg.p) - (size_t)b * W * sizeof(uint32_t));
         if (radiance4) fr.radiance4 = reinterpret_cast<float4*>(reinterpret_cast<uintptr_t>(c->dn.outRad.p) - (size_t)b * W * sizeof(float4));
     }
-    auto pull = [&](int i, int stage) -> int {
-        fyprt_context* c = g->ctx[i];
-        HIPCHK(c, hipSetDevice(c->device));
-        for (const DnXfer& t : plan) {
-            if (t.stage != stage || t.x.receiver != i) continue;
-            fyprt_context* o = g->ctx[t.x.owner];
-            HIPCHK(c, hipStreamWaitEvent(c->stream, g->dn[t.x.owner].done, 0));
-            const size_t bpp = stage == 0 ? kDnGuideBytes : kDnColourBytes;
-            char* dst = stage == 0 ? (char*)c->dn.guide.p : (char*)c->dn.col[(stage - 1) & 1].p;
-            const char* src = stage == 0 ? (const char*)o->dn.guide.p : (const char*)o->dn.col[(stage - 1) & 1].p;
-            const size_t off = (size_t)t.x.r0 * W * bpp, bytes = (size_t)(t.x.r1 - t.x.r0) * W * bpp;
-            HIPCHK(c, hipMemcpyPeerAsync(dst + off, c->device, src + off, o->device, bytes, c->stream));
-        }
-        HIPCHK(c, hipEventRecord(g->dn[i].pulled, c->stream));
-        return FYPRT_OK;
-    };
-    auto before_output = [&](int i) -> int {                     // the earlier call's collect still reads this band's staging rows
-        fyprt_context* c = g->ctx[i];
-        if (i != root && g->dnRoot >= 0) HIPCHK(c, hipStreamWaitEvent(c->stream, g->dn[g->dnRoot].collect, 0));
-        return FYPRT_OK;
-    };
-    // 1. prepare on the band's rows, after the earlier call's pulls from this band
-    for (int i = 0; i < n; ++i) {
-        fyprt_context* c = g->ctx[i];
-        HIPCHK(c, hipSetDevice(c->device));
-        if (timed) HIPCHK(c, hipEventRecord(g->dn[i].first, c->stream));
-        if (g->dnCalled) for (int j = 0; j < n; ++j) if (j != i) HIPCHK(c, hipStreamWaitEvent(c->stream, g->dn[j].pulled, 0));
-        launch_dn_prepare(c, frames[i], bands[i]);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipEventRecord(g->dn[i].done, c->stream));
-    }
-    // 2. the guide records of the halo rows
-    for (int i = 0; i < n; ++i) TRY(pull(i, 0));
-    // 3. per iteration: the colour halo it reads, then the iteration on the band's rows (one launch per band)
-    for (uint32_t k = 0; k < p->iterations; ++k) {
-        const DnIter it = make_dn_iter(*p, k, true);
-        if (k > 0)
+    std::vector<std::vector<XBuf>> moved(n);
+    for (const BandStep& st : steps) {
+        if (st.overwritesPulled)                                  // every band that pulls from band i has pulled what it last asked for
             for (int i = 0; i < n; ++i) {
                 fyprt_context* c = g->ctx[i];
                 HIPCHK(c, hipSetDevice(c->device));
                 for (int j = 0; j < n; ++j) if (pullsFrom[(size_t)i * n + j]) HIPCHK(c, hipStreamWaitEvent(c->stream, g->dn[j].pulled, 0));
             }
-        for (int i = 0; i < n; ++i) TRY(pull(i, 1 + (int)k));
+        if (st.pulls >= 0) {
+            for (int i = 0; i < n; ++i) moved[i] = st.moved(g->ctx[i]);
+            for (int i = 0; i < n; ++i) {
+                fyprt_context* c = g->ctx[i];
+                HIPCHK(c, hipSetDevice(c->device));
+                for (const DnXfer& t : plan) {
+                    if (t.stage != st.pulls || t.x.receiver != i) continue;
+                    const int o = t.x.owner;
+                    HIPCHK(c, hipStreamWaitEvent(c->stream, g->dn[o].done, 0));
+                    for (size_t b = 0; b < moved[i].size(); ++b)
+                        HIPCHK(c, copy_rows(c, moved[i][b].p, g->ctx[o], moved[o][b].p, t.x.r0, t.x.r1, W, moved[i][b].bytesPerPixel, c->stream));
+                }
+                HIPCHK(c, hipEventRecord(g->dn[i].pulled, c->stream));
+            }
+        }
+        if (!st.launch) continue;
         for (int i = 0; i < n; ++i) {
             fyprt_context* c = g->ctx[i];
             HIPCHK(c, hipSetDevice(c->device));
-            if (it.last) TRY(before_output(i));
-            launch_dn_iterate(c, frames[i], it, bands[i], c->dn.col[k & 1u].p, c->dn.col[(k + 1u) & 1u].p);
+            if (&st == &steps.front()) {                          // the first work of the call: after the earlier call's pulls from this band
+                if (timed) HIPCHK(c, hipEventRecord(g->dn[i].first, c->stream));
+                if (g->dnCalled) for (int j = 0; j < n; ++j) if (j != i) HIPCHK(c, hipStreamWaitEvent(c->stream, g->dn[j].pulled, 0));
+            }
+            // the earlier call's collect still reads this band's staging rows
+            if (st.writesOutput && i != root && g->dnRoot >= 0) HIPCHK(c, hipStreamWaitEvent(c->stream, g->dn[g->dnRoot].collect, 0));
+            st.launch(c, frames[i], bands[i]);
             HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipEventRecord(g->dn[i].done, c->stream));
+            if (st.recordsDone) HIPCHK(c, hipEventRecord(g->dn[i].done, c->stream));
         }
     }
-    for (int i = 0; i < n; ++i) {
+    for (int i = 0; i < n; ++i) {                                 // the end of a band
         fyprt_context* c = g->ctx[i];
         HIPCHK(c, hipSetDevice(c->device));
-        if (p->iterations == 0) {
-            TRY(before_output(i));
-            launch_dn_finish(c, frames[i], bands[i], c->dn.col[0].p);
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipEventRecord(g->dn[i].done, c->stream));
-        }
         if (timed) HIPCHK(c, hipEventRecord(g->dn[i].last, c->stream));
         TRY(dn_call_done(c));
     }
-    // 4. the other bands' output rows into the caller's buffers, on root's stream
+    // the other bands' output rows into the caller's buffers, on root's stream
     fyprt_context* r = g->ctx[root];
     HIPCHK(r, hipSetDevice(r->device));
     for (int i = 0; i < n; ++i) {
         if (i == root) continue;
-        fyprt_context* c = g->ctx[i];
         HIPCHK(r, hipStreamWaitEvent(r->stream, g->dn[i].done, 0));
-        const size_t off = (size_t)bands[i].rowBegin * W, cnt = (size_t)(bands[i].rowEnd - bands[i].rowBegin) * W;
-        if (rgba8) HIPCHK(r, hipMemcpyPeerAsync(rgba8 + off, r->device, c->dn.outImg.p, c->device, cnt * sizeof(uint32_t), r->stream));
-        if (radiance4) HIPCHK(r, hipMemcpyPeerAsync(radiance4 + off, r->device, c->dn.outRad.p, c->device, cnt * sizeof(float4), r->stream));
+        if (rgba8) HIPCHK(r, copy_rows(r, rgba8, g->ctx[i], frames[i].rgba8, bands[i].rowBegin, bands[i].rowEnd, W, sizeof(uint32_t), r->stream));
+        if (radiance4) HIPCHK(r, copy_rows(r, radiance4, g->ctx[i], frames[i].radiance4, bands[i].rowBegin, bands[i].rowEnd, W, sizeof(float4), r->stream));
     }
     HIPCHK(r, hipEventRecord(g->dn[root].collect, r->stream));
     g->dnCalled = true; g->dnRoot = root;
     return FYPRT_OK;
 }
-
-int fyprt_group_denoise(fyprt_group* g, const fyprt_denoise_params* p, uint32_t* rgba8, float* radiance4, float* band_ms) {
-    TRY(group_denoise_check(g, p, 0, rgba8, radiance4, false));
-    TRY(fyprt_group_synchronize(g));                               // as fyprt_denoise: the last frame is complete on every stream
+// What both lists of steps start with: prepare on the band's rows (into dn.col[0]), then the guide records of the halo rows (stage 0) ...
+static std::vector<BandStep> first_band_steps() {
+    return {{-1, nullptr, false, false, [](fyprt_context* c, const DnFrame& fr, DnBand band) { launch_dn_prepare(c, fr, band); }, true},
+            {0, [](fyprt_context* c) { return std::vector<XBuf>{{c->dn.guide.p, kDnGuideBytes}}; }, false, false, nullptr, false}};
+}
+// ... and, without iterations, end with: the finish kernel on the unfiltered colour dn.col[col]
+static BandStep finish_band_step(int col) {
+    return {-1, nullptr, false, true, [col](fyprt_context* c, const DnFrame& fr, DnBand band) { launch_dn_finish(c, fr, band, c->dn.col[col].p); }, true};
+}
+// The blocking form of either group call, as denoise_blocking is of a context's: the group synchronised (the last frame is complete on
+// every stream), the outputs staged at full size on member 0, `enqueue(rgba8, radiance4)` with member 0 as root and timed, copied back;
+// band_ms from every member's timing events.
+static int group_denoise_blocking(fyprt_group* g, uint32_t* rgba8, float* radiance4, float* band_ms, const std::function<int(uint32_t*, float4*)>& enqueue) {
+    TRY(fyprt_group_synchronize(g));
     fyprt_context* r = g->ctx[0];
     HIPCHK(r, hipSetDevice(r->device));
     const size_t npx = (size_t)r->W * r->H;
     if (rgba8 && r->dn.outImg.n != npx) HIPCHK(r, r->dn.outImg.alloc(npx));
     if (radiance4 && r->dn.outRad.n != npx) HIPCHK(r, r->dn.outRad.alloc(npx));
-    TRY(group_denoise_enqueue(g, p, 0, rgba8 ? r->dn.outImg.p : nullptr, radiance4 ? r->dn.outRad.p : nullptr, true));
+    TRY(enqueue(rgba8 ? r->dn.outImg.p : nullptr, radiance4 ? r->dn.outRad.p : nullptr));
     HIPCHK(r, hipSetDevice(r->device));
     if (rgba8) HIPCHK(r, hipMemcpyAsync(rgba8, r->dn.outImg.p, npx * 4, hipMemcpyDeviceToHost, r->stream));
     if (radiance4) HIPCHK(r, hipMemcpyAsync(radiance4, r->dn.outRad.p, npx * 16, hipMemcpyDeviceToHost, r->stream));
@@ -569,21 +612,34 @@ int fyprt_group_denoise(fyprt_group* g, const fyprt_denoise_params* p, uint32_t*
     return FYPRT_OK;
 }
 
+// The spatial call (group_denoise_plan): prepare; the guides; per iteration k the colour halo it reads (stage 1 + k: dn.col[k & 1]) and
+// the iteration dn.col[k & 1] -> dn.col[(k + 1) & 1].  Iteration 0 waits for no puller: it writes dn.col[1], which nothing pulled yet.
+static int group_spatial_call(fyprt_group* g, const fyprt_denoise_params* p, int root, uint32_t* rgba8, float4* radiance4, bool timed) {
+    std::vector<BandStep> steps = first_band_steps();
+    for (uint32_t k = 0; k < p->iterations; ++k) {
+        const DnIter it = make_dn_iter(*p, k, true);
+        steps.push_back({1 + (int)k, [k](fyprt_context* c) { return std::vector<XBuf>{{c->dn.col[k & 1u].p, kDnColourBytes}}; }, k > 0, it.last != 0,
+                         [k, it](fyprt_context* c, const DnFrame& fr, DnBand band) { launch_dn_iterate(c, fr, it, band, c->dn.col[k & 1u].p, c->dn.col[(k + 1u) & 1u].p); }, true});
+    }
+    if (p->iterations == 0) steps.push_back(finish_band_step(0));
+    return group_filter_enqueue(g, group_denoise_plan(g->bounds, g->ctx[0]->H, p->iterations), steps, p->demodulate_albedo, root, rgba8, radiance4, timed);
+}
+
+int fyprt_group_denoise(fyprt_group* g, const fyprt_denoise_params* p, uint32_t* rgba8, float* radiance4, float* band_ms) {
+    TRY(group_denoise_check(g, p, 0, rgba8, radiance4, false));
+    return group_denoise_blocking(g, rgba8, radiance4, band_ms, [&](uint32_t* img, float4* rad) { return group_spatial_call(g, p, 0, img, rad, true); });
+}
+
 int fyprt_group_denoise_device(fyprt_group* g, const fyprt_denoise_params* p, int root, void* rgba8, void* radiance4) {
     TRY(group_denoise_check(g, p, root, rgba8, radiance4, true));
-    return group_denoise_enqueue(g, p, root, static_cast<uint32_t*>(rgba8), static_cast<float4*>(radiance4), false);
+    return group_spatial_call(g, p, root, static_cast<uint32_t*>(rgba8), static_cast<float4*>(radiance4), false);
 }
 
 // The transfers of one fyprt_group_denoise* call in issue order: (stage, receiver, owner, first row, end row) per entry.
 int fyprt_group_denoise_plan(const uint32_t* row_bounds, int n, uint32_t height, uint32_t iterations, uint32_t* out5, int capacity) {
-    if (!row_bounds || n <= 0 || iterations > 8u || row_bounds[0] != 0 || row_bounds[n] != height) return FYPRT_EINVAL;
-    for (int i = 0; i < n; ++i) if (row_bounds[i] >= row_bounds[i + 1]) return FYPRT_EINVAL;
-    const std::vector<DnXfer> plan = group_denoise_plan(std::vector<uint32_t>(row_bounds, row_bounds + n + 1), height, iterations);
-    for (int k = 0; k < (int)plan.size() && k < capacity && out5; ++k) {
-        const HaloXfer& x = plan[k].x;
-        out5[5 * k] = (uint32_t)plan[k].stage; out5[5 * k + 1] = (uint32_t)x.receiver; out5[5 * k + 2] = (uint32_t)x.owner; out5[5 * k + 3] = x.r0; out5[5 * k + 4] = x.r1;
-    }
-    return (int)plan.size();
+    int at;
+    if (!row_bounds || n <= 0 || iterations > 8u || bad_bands(row_bounds, n, height, &at)) return FYPRT_EINVAL;
+    return export_plan(group_denoise_plan(std::vector<uint32_t>(row_bounds, row_bounds + n + 1), height, iterations), out5, capacity);
 }
 
 // ---- fyprt_group_denoise_temporal*: the temporal denoiser (rt_temporal.h) on the group's bands, as fyprt_group_denoise* above: the band
@@ -607,211 +663,60 @@ static int group_temporal_check(fyprt_group* g, const fyprt_temporal_params* p, 
     return FYPRT_OK;
 }
 
-// Enqueues one call on every band's stream and the collect on root's, as group_denoise_enqueue, with its events.  Per band: prepare;
-// the pulls of stages 0 and 1; k_dt_moved if a snapshot is pending; the pull of stage 2; reproject; per iteration the pull of stage
-// 3 + k and the iteration; the finish kernel without iterations.  Hazards, and the event that orders each:
-//   read after write   a pull reads rows the owner's latest kernel wrote (prepare: guide and e0 | L; the previous call: the history;
-//                      reproject / iteration k - 1: colour and variance): it waits for the owner's `done`, recorded after each launch;
-//   write after read   iteration k overwrites the colour and variance buffers iteration k - 1 read, which the neighbours pulled from at
-//                      stage 3 + k - 1 (iteration 0: the prepared colour of stage 1): it waits for the last `pulled` of every band that
-//                      pulls from this one, as recorded after that stage or a later one;
-//   the history        ping-pongs per member: this call writes dt.hist[dtCur ^ 1], the buffer the neighbours' stage 2 of the call before
-//                      pulled from.  The first work of a call on a band waits for every other band's last `pulled` of the earlier call
-//                      — recorded after that call's last stage, so after its stage 2 — which also covers the colour, variance and guide
-//                      buffers;
-//   across calls       the staging rows wait for the earlier root's `collect`, and dn_call_done holds the front stream, as there.
-// The members' bookkeeping (dtCur, dtValid, dtGroup, dtPV, dtSnapPending) advances only once everything is enqueued.
-static int group_temporal_enqueue_all(fyprt_group* g, const fyprt_temporal_params* p, uint32_t historyRows, int root, uint32_t* rgba8, float4* radiance4, bool timed) {
+// The temporal call (group_temporal_plan, without stage 2 while the group holds no history): prepare; the guides; the prepared colour
+// the variance estimate reads (stage 1); with a history the moved flags of a pending edit — nothing pulls what they are, so no `done` —
+// and the history window (stage 2: dt.hist[dtCur]); the reprojection, its taps within the band plus min(historyRows, H) rows either
+// side; per iteration k the colour and variance it reads (stage 3 + k) and the iteration, colour dn.col[1] -> [0] -> [1] ..., variance
+// dt.var[0] -> [1] -> [0] ..., iteration 0 feeding dt.hist[dtCur ^ 1] back.  Every iteration waits for its pullers: iteration 0
+// overwrites the prepared colour of stage 1.  The members' bookkeeping (dtCur, dtValid, dtGroup, dtPV, dtSnapPending) advances only
+// once everything is enqueued.
+static int group_temporal_call(fyprt_group* g, const fyprt_temporal_params* p, uint32_t historyRows, int root, uint32_t* rgba8, float4* radiance4, bool timed) {
     const fyprt_denoise_params& sp = p->spatial;
-    const int n = (int)g->ctx.size();
-    const uint32_t W = g->ctx[0]->W, H = g->ctx[0]->H, R = std::min(historyRows, H);
-    for (int i = 0; i < n; ++i) {
-        fyprt_context* c = g->ctx[i];
-        HIPCHK(c, hipSetDevice(c->device));
-        TRY(ensure_dn_buffers(c));
-        TRY(ensure_dt_buffers(c));
-    }
+    const uint32_t H = g->ctx[0]->H, R = std::min(historyRows, H);
+    for (fyprt_context* c : g->ctx) { HIPCHK(c, hipSetDevice(c->device)); TRY(ensure_dt_buffers(c)); }      // (may drop the history)
     const bool history = group_has_history(g);
     std::vector<DnXfer> plan;
     for (const DnXfer& t : group_temporal_plan(g->bounds, H, sp.iterations, R)) if (t.stage != 2 || history) plan.push_back(t);
-    std::vector<char> pullsFrom((size_t)n * n, 0);                // [owner * n + receiver]
-    for (const DnXfer& t : plan) pullsFrom[(size_t)t.x.owner * n + t.x.receiver] = 1;
-    std::vector<DnFrame> frames(n); std::vector<DnBand> bands(n);
-    for (int i = 0; i < n; ++i) {
-        fyprt_context* c = g->ctx[i];
-        HIPCHK(c, hipSetDevice(c->device));
-        fyprt_group::DenoiseEvents& e = g->dn[i];
-        HIPCHK(c, create(e.done, hipEventDisableTiming)); HIPCHK(c, create(e.pulled, hipEventDisableTiming)); HIPCHK(c, create(e.collect, hipEventDisableTiming));
-        if (timed) { HIPCHK(c, create(e.first)); HIPCHK(c, create(e.last)); }
-        const uint32_t b = g->bounds[i], rows = g->bounds[i + 1] - b;
-        bands[i] = DnBand{b, g->bounds[i + 1]};
-        DnFrame& fr = frames[i];
-        fr = dn_frame(c, sp.demodulate_albedo, i == root ? rgba8 : nullptr, i == root ? radiance4 : nullptr);
-        if (i == root) continue;
-        const size_t need = (size_t)rows * W;                     // the band's staging, as group_denoise_enqueue
-        if ((rgba8 && c->dn.outImg.n < need) || (radiance4 && c->dn.outRad.n < need)) {
-            if (g->dnRoot >= 0) HIPCHK(c, hipEventSynchronize(g->dn[g->dnRoot].collect));
-            if (rgba8 && c->dn.outImg.n < need) HIPCHK(c, c->dn.outImg.alloc(need));
-            if (radiance4 && c->dn.outRad.n < need) HIPCHK(c, c->dn.outRad.alloc(need));
-        }
-        if (rgba8) fr.rgba8 = reinterpret_cast<uint32_t*>(reinterpret_cast<uintptr_t>(c->dn.outImg.p) - (size_t)b * W * sizeof(uint32_t));
-        if (radiance4) fr.radiance4 = reinterpret_cast<float4*>(reinterpret_cast<uintptr_t>(c->dn.outRad.p) - (size_t)b * W * sizeof(float4));
+    std::vector<BandStep> steps = first_band_steps();
+    steps.push_back({1, [](fyprt_context* c) { return std::vector<XBuf>{{c->dn.col[0].p, kDnColourBytes}}; }, false, false, nullptr, false});
+    if (history) {
+        steps.push_back({-1, nullptr, false, false, [](fyprt_context* c, const DnFrame&, DnBand) { if (dt_motion_pending(c, true)) launch_dt_moved(c); }, false});
+        steps.push_back({2, [](fyprt_context* c) { return std::vector<XBuf>{{c->dt.hist[c->dtCur].p, kDtHistoryBytes}}; }, false, false, nullptr, false});
     }
-    auto pull = [&](int i, int stage) -> int {
-        fyprt_context* c = g->ctx[i];
-        HIPCHK(c, hipSetDevice(c->device));
-        for (const DnXfer& t : plan) {
-            if (t.stage != stage || t.x.receiver != i) continue;
-            fyprt_context* o = g->ctx[t.x.owner];
-            HIPCHK(c, hipStreamWaitEvent(c->stream, g->dn[t.x.owner].done, 0));
-            const uint32_t k = stage >= 3 ? (uint32_t)(stage - 3) : 0u;
-            struct { void* dst; const void* src; size_t bpp; } what[2] = {};
-            int cnt = 1;
-            if (stage == 0) what[0] = {c->dn.guide.p, o->dn.guide.p, kDnGuideBytes};
-            else if (stage == 1) what[0] = {c->dn.col[0].p, o->dn.col[0].p, kDnColourBytes};
-            else if (stage == 2) what[0] = {c->dt.hist[c->dtCur].p, o->dt.hist[o->dtCur].p, kDtHistoryBytes};
-            else {
-                what[0] = {c->dn.col[(k + 1u) & 1u].p, o->dn.col[(k + 1u) & 1u].p, kDnColourBytes};
-                what[1] = {c->dt.var[k & 1u].p, o->dt.var[k & 1u].p, kDtVarianceBytes}; cnt = 2;
-            }
-            for (int w = 0; w < cnt; ++w) {
-                const size_t off = (size_t)t.x.r0 * W * what[w].bpp, bytes = (size_t)(t.x.r1 - t.x.r0) * W * what[w].bpp;
-                HIPCHK(c, hipMemcpyPeerAsync((char*)what[w].dst + off, c->device, (const char*)what[w].src + off, o->device, bytes, c->stream));
-            }
-        }
-        HIPCHK(c, hipEventRecord(g->dn[i].pulled, c->stream));
-        return FYPRT_OK;
-    };
-    auto before_output = [&](int i) -> int {                     // the earlier call's collect still reads this band's staging rows
-        fyprt_context* c = g->ctx[i];
-        if (i != root && g->dnRoot >= 0) HIPCHK(c, hipStreamWaitEvent(c->stream, g->dn[g->dnRoot].collect, 0));
-        return FYPRT_OK;
-    };
-    auto wait_pullers = [&](int i) -> int {                      // every band that pulls from band i has pulled what it last asked for
-        fyprt_context* c = g->ctx[i];
-        HIPCHK(c, hipSetDevice(c->device));
-        for (int j = 0; j < n; ++j) if (pullsFrom[(size_t)i * n + j]) HIPCHK(c, hipStreamWaitEvent(c->stream, g->dn[j].pulled, 0));
-        return FYPRT_OK;
-    };
-    // 1. prepare on the band's rows, after the earlier call's pulls from this band
-    for (int i = 0; i < n; ++i) {
-        fyprt_context* c = g->ctx[i];
-        HIPCHK(c, hipSetDevice(c->device));
-        if (timed) HIPCHK(c, hipEventRecord(g->dn[i].first, c->stream));
-        if (g->dnCalled) for (int j = 0; j < n; ++j) if (j != i) HIPCHK(c, hipStreamWaitEvent(c->stream, g->dn[j].pulled, 0));
-        launch_dn_prepare(c, frames[i], bands[i]);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipEventRecord(g->dn[i].done, c->stream));
-    }
-    // 2. guide records and prepared colour of the rows the variance estimate and the taps reach
-    for (int i = 0; i < n; ++i) TRY(pull(i, 0));
-    for (int i = 0; i < n; ++i) TRY(pull(i, 1));
-    // 3. the moved flags, the history window, the reprojection.  `done` is not recorded after k_dt_moved: nothing pulls what it writes,
-    // and the owner's `done` a stage-2 pull waits for is its prepare's — the history itself is the call before's, which the stream orders.
-    for (int i = 0; i < n; ++i) {
-        fyprt_context* c = g->ctx[i];
-        HIPCHK(c, hipSetDevice(c->device));
-        const bool motion = history && c->dtSnapPending && c->dtEditHi > c->dtEditLo;
-        if (motion) {
-            const uint32_t count = c->dtEditHi - c->dtEditLo;
-            hipLaunchKernelGGL(k_dt_moved, dim3((count + 255u) / 256u), dim3(256), 0, c->stream, c->dverts.p, c->dtSnap.p, c->triIdx.p, c->dtMoved.p, c->dtEditLo, count);
-        }
-        if (history) TRY(pull(i, 2));
-    }
-    for (int i = 0; i < n; ++i) {
-        fyprt_context* c = g->ctx[i];
-        HIPCHK(c, hipSetDevice(c->device));
-        const bool motion = history && c->dtSnapPending && c->dtEditHi > c->dtEditLo;
-        const DtCall tc = make_dt_call(c, *p, history);
-        const DnBand win{bands[i].rowBegin > R ? bands[i].rowBegin - R : 0u, std::min(H, bands[i].rowEnd + R)};
-        const dim3 grid(dt_reproject_grid(W, bands[i].rowEnd - bands[i].rowBegin));
-        const float4* histIn = c->dt.hist[c->dtCur].p; float4* histOut = c->dt.hist[c->dtCur ^ 1].p;
-        if (motion) {
-            const DtMotion mo{c->payload.p, c->dtMoved.p, c->triIdx.p, c->triPos.p, c->dtSnap.p};
-            hipLaunchKernelGGL(k_dt_reproject_motion, grid, dim3(256), 0, c->stream, frames[i], tc, mo, bands[i], win, c->dn.col[0].p, histIn, histOut, c->dn.col[1].p, c->dt.var[0].p);
-        } else {
-            hipLaunchKernelGGL(k_dt_reproject, grid, dim3(256), 0, c->stream, frames[i], tc, bands[i], win, c->dn.col[0].p, histIn, histOut, c->dn.col[1].p, c->dt.var[0].p);
-        }
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipEventRecord(g->dn[i].done, c->stream));
-    }
-    // 4. per iteration: colour and variance of the rows it reads, then the iteration on the band's rows
-    for (uint32_t k = 0; k < sp.iterations; ++k) {              // colour: dn.col[1] -> [0] -> [1] ...; variance: dt.var[0] -> [1] -> [0] ...
+    steps.push_back({-1, nullptr, false, false, [=](fyprt_context* c, const DnFrame& fr, DnBand band) {
+        const DnBand window{band.rowBegin > R ? band.rowBegin - R : 0u, std::min(H, band.rowEnd + R)};
+        launch_dt_reproject(c, fr, make_dt_call(c, *p, history), band, window, dt_motion_pending(c, history));
+    }, true});
+    for (uint32_t k = 0; k < sp.iterations; ++k) {
         const DnIter it = make_dn_iter(sp, k, false);
-        for (int i = 0; i < n; ++i) TRY(wait_pullers(i));
-        for (int i = 0; i < n; ++i) TRY(pull(i, 3 + (int)k));
-        for (int i = 0; i < n; ++i) {
-            fyprt_context* c = g->ctx[i];
-            HIPCHK(c, hipSetDevice(c->device));
-            if (it.last) TRY(before_output(i));
-            float4* fb = (k == 0 && p->feedback) ? c->dt.hist[c->dtCur ^ 1].p : nullptr;
-            launch_dt_iterate(c, frames[i], it, bands[i], c->dn.col[(k + 1u) & 1u].p, c->dn.col[k & 1u].p, c->dt.var[k & 1u].p, c->dt.var[(k + 1u) & 1u].p, fb);
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipEventRecord(g->dn[i].done, c->stream));
-        }
+        const bool feedback = k == 0 && p->feedback;
+        steps.push_back({3 + (int)k, [k](fyprt_context* c) { return std::vector<XBuf>{{c->dn.col[(k + 1u) & 1u].p, kDnColourBytes}, {c->dt.var[k & 1u].p, kDtVarianceBytes}}; }, true, it.last != 0,
+                         [k, it, feedback](fyprt_context* c, const DnFrame& fr, DnBand band) {
+                             launch_dt_iterate(c, fr, it, band, c->dn.col[(k + 1u) & 1u].p, c->dn.col[k & 1u].p, c->dt.var[k & 1u].p, c->dt.var[(k + 1u) & 1u].p, feedback ? c->dt.hist[c->dtCur ^ 1].p : nullptr);
+                         }, true});
     }
-    for (int i = 0; i < n; ++i) {
-        fyprt_context* c = g->ctx[i];
-        HIPCHK(c, hipSetDevice(c->device));
-        if (sp.iterations == 0) {
-            TRY(before_output(i));
-            launch_dn_finish(c, frames[i], bands[i], c->dn.col[1].p);
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipEventRecord(g->dn[i].done, c->stream));
-        }
-        if (timed) HIPCHK(c, hipEventRecord(g->dn[i].last, c->stream));
-        TRY(dn_call_done(c));
-    }
-    // 5. the other bands' output rows into the caller's buffers, on root's stream
-    fyprt_context* r = g->ctx[root];
-    HIPCHK(r, hipSetDevice(r->device));
-    for (int i = 0; i < n; ++i) {
-        if (i == root) continue;
-        fyprt_context* c = g->ctx[i];
-        HIPCHK(r, hipStreamWaitEvent(r->stream, g->dn[i].done, 0));
-        const size_t off = (size_t)bands[i].rowBegin * W, cnt = (size_t)(bands[i].rowEnd - bands[i].rowBegin) * W;
-        if (rgba8) HIPCHK(r, hipMemcpyPeerAsync(rgba8 + off, r->device, c->dn.outImg.p, c->device, cnt * sizeof(uint32_t), r->stream));
-        if (radiance4) HIPCHK(r, hipMemcpyPeerAsync(radiance4 + off, r->device, c->dn.outRad.p, c->device, cnt * sizeof(float4), r->stream));
-    }
-    HIPCHK(r, hipEventRecord(g->dn[root].collect, r->stream));
-    g->dnCalled = true; g->dnRoot = root;
+    if (sp.iterations == 0) steps.push_back(finish_band_step(1));
+    TRY(group_filter_enqueue(g, plan, steps, sp.demodulate_albedo, root, rgba8, radiance4, timed));
     for (fyprt_context* c : g->ctx) {
         c->dtCur ^= 1; c->dtValid = true; c->dtGroup = g->id; c->dtSnapPending = false; std::memcpy(c->dtPV, c->framePV, 64);
     }
     return FYPRT_OK;
 }
 // A failed enqueue leaves some bands' new history written and others' not: the group's history is dropped instead.
-static int group_temporal_enqueue(fyprt_group* g, const fyprt_temporal_params* p, uint32_t historyRows, int root, uint32_t* rgba8, float4* radiance4, bool timed) {
-    const int rc = group_temporal_enqueue_all(g, p, historyRows, root, rgba8, radiance4, timed);
+static int group_temporal_call_or_drop(fyprt_group* g, const fyprt_temporal_params* p, uint32_t historyRows, int root, uint32_t* rgba8, float4* radiance4, bool timed) {
+    const int rc = group_temporal_call(g, p, historyRows, root, rgba8, radiance4, timed);
     if (rc != FYPRT_OK) for (fyprt_context* c : g->ctx) c->drop_history();
     return rc;
 }
 
 int fyprt_group_denoise_temporal(fyprt_group* g, const fyprt_temporal_params* p, uint32_t history_rows, uint32_t* rgba8, float* radiance4, float* band_ms) {
     TRY(group_temporal_check(g, p, 0, rgba8, radiance4, false));
-    TRY(fyprt_group_synchronize(g));                               // as fyprt_group_denoise
-    fyprt_context* r = g->ctx[0];
-    HIPCHK(r, hipSetDevice(r->device));
-    const size_t npx = (size_t)r->W * r->H;
-    if (rgba8 && r->dn.outImg.n != npx) HIPCHK(r, r->dn.outImg.alloc(npx));
-    if (radiance4 && r->dn.outRad.n != npx) HIPCHK(r, r->dn.outRad.alloc(npx));
-    TRY(group_temporal_enqueue(g, p, history_rows, 0, rgba8 ? r->dn.outImg.p : nullptr, radiance4 ? r->dn.outRad.p : nullptr, true));
-    HIPCHK(r, hipSetDevice(r->device));
-    if (rgba8) HIPCHK(r, hipMemcpyAsync(rgba8, r->dn.outImg.p, npx * 4, hipMemcpyDeviceToHost, r->stream));
-    if (radiance4) HIPCHK(r, hipMemcpyAsync(radiance4, r->dn.outRad.p, npx * 16, hipMemcpyDeviceToHost, r->stream));
-    HIPCHK(r, hipStreamSynchronize(r->stream));
-    for (size_t i = 0; i < g->ctx.size(); ++i) {
-        fyprt_context* c = g->ctx[i];
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipEventSynchronize(g->dn[i].last));
-        if (band_ms) HIPCHK(c, hipEventElapsedTime(&band_ms[i], g->dn[i].first, g->dn[i].last));
-    }
-    return FYPRT_OK;
+    return group_denoise_blocking(g, rgba8, radiance4, band_ms, [&](uint32_t* img, float4* rad) { return group_temporal_call_or_drop(g, p, history_rows, 0, img, rad, true); });
 }
 
 int fyprt_group_denoise_temporal_device(fyprt_group* g, const fyprt_temporal_params* p, uint32_t history_rows, int root, void* rgba8, void* radiance4) {
     TRY(group_temporal_check(g, p, root, rgba8, radiance4, true));
-    return group_temporal_enqueue(g, p, history_rows, root, static_cast<uint32_t*>(rgba8), static_cast<float4*>(radiance4), false);
+    return group_temporal_call_or_drop(g, p, history_rows, root, static_cast<uint32_t*>(rgba8), static_cast<float4*>(radiance4), false);
 }
 
 int fyprt_group_denoise_temporal_reset(fyprt_group* g) {
@@ -822,14 +727,9 @@ int fyprt_group_denoise_temporal_reset(fyprt_group* g) {
 
 // The transfers of one fyprt_group_denoise_temporal* call in issue order, entries as fyprt_group_denoise_plan's.
 int fyprt_group_denoise_temporal_plan(const uint32_t* row_bounds, int n, uint32_t height, uint32_t iterations, uint32_t history_rows, uint32_t* out5, int capacity) {
-    if (!row_bounds || n <= 0 || iterations > 8u || row_bounds[0] != 0 || row_bounds[n] != height) return FYPRT_EINVAL;
-    for (int i = 0; i < n; ++i) if (row_bounds[i] >= row_bounds[i + 1]) return FYPRT_EINVAL;
-    const std::vector<DnXfer> plan = group_temporal_plan(std::vector<uint32_t>(row_bounds, row_bounds + n + 1), height, iterations, history_rows);
-    for (int k = 0; k < (int)plan.size() && k < capacity && out5; ++k) {
-        const HaloXfer& x = plan[k].x;
-        out5[5 * k] = (uint32_t)plan[k].stage; out5[5 * k + 1] = (uint32_t)x.receiver; out5[5 * k + 2] = (uint32_t)x.owner; out5[5 * k + 3] = x.r0; out5[5 * k + 4] = x.r1;
-    }
-    return (int)plan.size();
+    int at;
+    if (!row_bounds || n <= 0 || iterations > 8u || bad_bands(row_bounds, n, height, &at)) return FYPRT_EINVAL;
+    return export_plan(group_temporal_plan(std::vector<uint32_t>(row_bounds, row_bounds + n + 1), height, iterations, history_rows), out5, capacity);
 }
 
 // Cost-balanced bands: new boundaries from the time each band took last frame, assuming a band's cost is spread evenly over its rows
@@ -879,8 +779,8 @@ int fyprt_comm_unique_id(void* id128) {
 int fyprt_comm_init_rank(fyprt_context* c, int world, int rank, const void* id128, const uint32_t* row_bounds) {
     if (!c || !id128 || !row_bounds || world <= 0 || rank < 0 || rank >= world) return FYPRT_EINVAL;
     if (c->hostOnly || c->H == 0) return c->fail(FYPRT_ESTATE, "fyprt_comm_init_rank: resize the context first");
-    if (row_bounds[0] != 0 || row_bounds[world] != c->H) return c->fail(FYPRT_EINVAL, "fyprt_comm_init_rank: the bands must partition rows 0..height");
-    for (int i = 0; i < world; ++i) if (row_bounds[i] >= row_bounds[i + 1]) return c->fail(FYPRT_EINVAL, "fyprt_comm_init_rank: empty or unordered band");
+    int at;
+    if (const char* bad = bad_bands(row_bounds, world, c->H, &at)) return c->fail(FYPRT_EINVAL, std::string("fyprt_comm_init_rank") + bad);
     if (!g_rccl.load()) return c->fail(FYPRT_EHIP, g_rccl.err);
     HIPCHK(c, hipSetDevice(c->device));
     if (c->comm) { (void)g_rccl.CommDestroy(c->comm); c->comm = nullptr; }
@@ -894,18 +794,15 @@ int fyprt_comm_init_rank(fyprt_context* c, int world, int rank, const void* id12
 // owner take their accumulation and temporal history along (grouped ncclSend / ncclRecv), as fyprt_group_set_rows does with peer copies.
 int fyprt_comm_set_rows(fyprt_context* c, const uint32_t* row_bounds) {
     if (!c || !row_bounds || !c->comm) return FYPRT_EINVAL;
-    if (row_bounds[0] != 0 || row_bounds[c->world] != c->H) return c->fail(FYPRT_EINVAL, "fyprt_comm_set_rows: the bands must partition rows 0..height");
-    for (int i = 0; i < c->world; ++i) if (row_bounds[i] >= row_bounds[i + 1]) return c->fail(FYPRT_EINVAL, "fyprt_comm_set_rows: empty or unordered band");
+    int at;
+    if (const char* bad = bad_bands(row_bounds, c->world, c->H, &at)) return c->fail(FYPRT_EINVAL, std::string("fyprt_comm_set_rows") + bad);
     HIPCHK(c, hipSetDevice(c->device));
     // Between two frames for real: a pipelined ReSTIR DI frame still has Part 1 + setup of the NEXT frame in flight on the front stream,
     // and they read and write the very history rows that move here.  Everything of this context drains first, and the call returns only
     // once the rows have arrived — exactly what fyprt_group_set_rows does around its peer copies.
     HIPCHK(c, sync_all(c));
     std::vector<void*> base; std::vector<size_t> bpp;
-    if (!c->commLastStriped) { base.push_back(c->accum.p); bpp.push_back(sizeof(float4)); }     // an interleaved frame's accumulation lives in stripes: nothing to move
-    base.push_back(c->dprevFlip ? (void*)c->dprevB.p : (void*)c->dprevA.p); bpp.push_back(sizeof(DIRec));
-    base.push_back(c->giPrev.p); bpp.push_back(sizeof(GIRes));
-    base.push_back(c->normalFlip ? (void*)c->normalB.p : (void*)c->normalA.p); bpp.push_back(sizeof(f2));
+    for (const XBuf& b : row_buffers(c, c->commLastStriped)) { base.push_back(b.p); bpp.push_back(b.bytesPerPixel); }
     TRY(comm_issue(c, comm_set_rows_ops(c->rank, c->bounds, std::vector<uint32_t>(row_bounds, row_bounds + c->world + 1), bpp, c->W), base));
     HIPCHK(c, sync_all(c));
     c->bounds.assign(row_bounds, row_bounds + c->world + 1);

@@ -7,7 +7,7 @@ hipEvent kernel time, the per-band hipEvent times (band_ms, waits for the neighb
 other per call (fyprt_group_denoise_plan).  Medians, one JSON line per split.
 With fewer GPUs than bands the bands share a device and run one after the other: the figures then show the overhead of the split
 (more launches, the pulls, the collect), not scaling.
-  usage: python tools/group_denoise_rate.py [--reps 20] [--splits 1,2,4,8] [--out profiles/denoise/group_denoise_rate.jsonl]"""
+  usage: python tools/group_denoise_rate.py [--reps 20] [--splits 1,2,4,8] [--lib PATH --label NAME] [--out profiles/denoise/group_denoise_rate.jsonl]"""
 import argparse
 import json
 import statistics
@@ -31,11 +31,11 @@ def med(v):
     return round(statistics.median(v), 4)
 
 
-def gpu_count(limit):
+def gpu_count(limit, lib):
     n = 0
     while n < limit:
         try:
-            capi.Context(n).close()
+            capi.Context(n, lib=lib).close()
         except capi.FyprtError:
             break
         n += 1
@@ -49,14 +49,17 @@ def main():
     ap.add_argument("--splits", default="1,2,4,8")
     ap.add_argument("--size", default="1920x1080")
     ap.add_argument("--out", default=str(ROOT / "profiles" / "denoise" / "group_denoise_rate.jsonl"))
+    ap.add_argument("--lib", default=None, help="an alternative libfyprt.so to measure instead of the built one (before / after runs)")
+    ap.add_argument("--label", default="default", help="the `library` field of the lines")
     a = ap.parse_args()
+    lib = capi.load_library(a.lib) if a.lib else capi.load_library()
     W, H = (int(x) for x in a.size.split("x"))
     splits = [int(x) for x in a.splits.split(",")]
-    gpus = gpu_count(max(splits))
+    gpus = gpu_count(max(splits), lib)
     sc, cam, st, par = scenes.hall_scene(), scenes.hall_camera(W, H), bench_settings(), capi.DenoiseParams()
 
     def context(device):
-        c = capi.Context(device)
+        c = capi.Context(device, lib=lib)
         c.resize(W, H)
         c.upload_scene(sc)
         c.set_camera(cam)
@@ -73,7 +76,7 @@ def main():
         grp = capi.Group(members[:n], bounds, halo_mode=1)
         grp.render(st)
         grp.synchronize()
-        plan = capi.group_denoise_plan(bounds, H, par.iterations)
+        plan = capi.group_denoise_plan(bounds, H, par.iterations, lib=lib)
         pulled = sum((r1 - r0) * W * (GUIDE_BYTES if stage == 0 else COLOUR_BYTES) for stage, _, _, r0, r1 in plan)
         wall_s, wall_g, kern_s, band = [], [], [], []
         same = None
@@ -87,7 +90,7 @@ def main():
                 same = bool((img_s == img_g).all())
             if rep >= a.warmup:
                 wall_s.append((t1 - t0) * 1e3); wall_g.append((t2 - t1) * 1e3); kern_s.append(stats.kernel_ms); band.append(ms)
-        line = {"what": "group_denoise", "size": a.size, "iterations": par.iterations, "bands": n, "gpus": min(gpus, n), "bands_share_a_gpu": gpus < n,
+        line = {"what": "group_denoise", "library": a.label, "size": a.size, "iterations": par.iterations, "bands": n, "gpus": min(gpus, n), "bands_share_a_gpu": gpus < n,
                 "reps": a.reps, "equal_to_single": same, "single_wall_ms": med(wall_s), "single_kernel_ms": med(kern_s),
                 "group_wall_ms": med(wall_g), "group_wall_ms_min": round(min(wall_g), 4), "group_wall_ms_max": round(max(wall_g), 4),
                 "band_ms": [med([b[k] for b in band]) for k in range(n)], "transfers": len(plan), "pulled_MB": round(pulled / 1e6, 2)}
