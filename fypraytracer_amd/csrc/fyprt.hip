@@ -376,7 +376,7 @@ int fyprt_create(int device_ordinal, fyprt_context** out) {
     for (auto& row : c->ring) for (auto& e : row) (void)create(e);
     { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, device_ordinal) == hipSuccess && prop.multiProcessorCount > 0) c->numCUs = prop.multiProcessorCount; }
     if (const char* e = std::getenv("FYPRT_TOP_NODES")) c->tuning[K_TOP_NODES] = std::min(1024, std::max(0, std::atoi(e)));
-    (void)c->queueCounters.alloc(8);          // two queues (frame parity): tail, head, pad, pad each
+    (void)c->queueCounters.alloc(8);          // two queues (frame parity): ray tail, ray-less count, head, pad each
     (void)c->rayCounter.alloc(32);            // 4 launches x (rays, box tests, triangle tests, hits, node visits, 3 unused)
     (void)hipMemset(c->rayCounter.p, 0, 256);
     *out = c;
@@ -413,7 +413,7 @@ int fyprt_resize(fyprt_context* c, uint32_t w, uint32_t h) {
         // the sort scratch alternates with the frame parity like the queues: frame N+1's setup / scan / scatter (front stream) run
         // beside frame N's trace kernel, which still reads its `sorted` index
         c->sortGroups = maxGroups;
-        HIPCHK(c, c->sortCounts.alloc(2 * maxGroups)); HIPCHK(c, c->sortKeys.alloc(2 * maxGroups * 256u)); HIPCHK(c, c->sortHist.alloc(2 * maxGroups * kSortBins));
+        HIPCHK(c, c->sortCounts.alloc(4 * maxGroups)); HIPCHK(c, c->sortKeys.alloc(2 * maxGroups * 256u)); HIPCHK(c, c->sortHist.alloc(2 * maxGroups * kSortBins));
         HIPCHK(c, c->sortOffset.alloc(2 * maxGroups * kSortBins)); HIPCHK(c, c->sortTotal.alloc(2 * kSortBins)); HIPCHK(c, c->sortIndex.alloc(2 * maxGroups * 256u));
     }
     HIPCHK(c, sync_all(c));
@@ -1506,10 +1506,10 @@ static int enqueue_di_wavefront_part2(FrameRun& f) {
     fyprt_context* c = f.c; const int par = f.par; const dim3 grid = f.grid; hipStream_t fs = f.fs;
     const dim3 block(kBlock);
     ShadowQueue q{};
-    q.tasks = c->shadowTasks.p + (size_t)par * c->queueStride; q.counters = c->queueCounters.p + 4 * par;
+    q.tasks = c->shadowTasks.p + (size_t)par * c->queueStride; q.rayless = q.tasks + c->queueStride; q.counters = c->queueCounters.p + 4 * par;
     set_queue_params(c, q, K_REFILL_LANES);
     const size_t sg = (size_t)par * c->sortGroups;
-    q.sortMode = c->tuning[K_SORT_TASKS] ? 1u : 0u; q.numGroups = grid.x; q.counts = c->sortCounts.p + sg; q.keys = c->sortKeys.p + sg * 256u; q.hist = c->sortHist.p + sg * kSortBins;
+    q.sortMode = c->tuning[K_SORT_TASKS] ? 1u : 0u; q.numGroups = grid.x; q.counts = c->sortCounts.p + 2 * sg; q.bases = q.counts + c->sortGroups; q.keys = c->sortKeys.p + sg * 256u; q.hist = c->sortHist.p + sg * kSortBins;
     q.binOffset = c->sortOffset.p + sg * kSortBins; q.binTotal = c->sortTotal.p + (size_t)par * kSortBins; q.sorted = c->sortIndex.p + sg * 256u;
     HIPCHK(c, hipMemsetAsync(q.counters, 0, 16, fs));
     static void (*const kSetup[3])(DevScene, DevCamera, DevFrame, DevSettings, ShadowQueue) = {k_di_part2_setup<0>, k_di_part2_setup<1>, k_di_part2_setup<2>};

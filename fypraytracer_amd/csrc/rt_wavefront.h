@@ -3,15 +3,15 @@
 //
 //   k_di_part2_setup  one thread per pixel: spatial reuse, light-point sample, BRDF — everything of
 //                     PerPixel_ReSTIR_DI_Part2 (R.cu:1875-2007, :2033-2038) except the shadow ray; every pixel of the band
-//                     appends one 64-byte task to a queue (wave ballot + prefix popcount, LDS prefix over the 4 waves, ONE
-//                     atomic per workgroup): a shadow task, or — for a pixel Part 1 finished (sky / emitter) — a task
-//                     without a ray that only carries the pixel's colour to the epilogue.
+//                     with a shadow ray appends one 64-byte task to a queue (wave ballot + prefix popcount, LDS prefix over
+//                     the 4 waves, ONE atomic per workgroup); a pixel without one — Part 1 finished it (sky / emitter), or
+//                     its ray is dead — appends 16 bytes, colour and pixel index, to a list of its own (ShadowQueue).
 //   k_di_part2_trace  persistent waves: every lane owns one in-flight shadow ray; when >= refillLanes lanes of a wave are
 //                     idle, the wave runs their fused epilogues together (visibility select, accumulate, tonemap, pack)
 //                     and refills exactly those lanes from its claimed chunk of the queue, so SIMD lanes stay busy although
 //                     shadow rays differ 10x in length (lane utilisation of the one-thread-per-pixel Part 2: 35 %).
 //                     Chunks: the first one of every wave is static, the rest are stolen from a shared head and shrink
-//                     towards the end of the queue (see the kernel).
+//                     towards the end of the queue (see the kernel).  The ray-less list's epilogues run first, at full width.
 //
 // All epilogues of a wavefront frame run in the trace kernel, and Part 1 touches neither image nor accumulation
 // (DevFrame::p1Mode): that is what lets the host run Part 1 + setup of the next frame on a second stream beside it.
@@ -25,12 +25,16 @@ namespace rt {
 
 struct ShadowQueue {
     float4* tasks; uint32_t* counters; uint32_t chunk, refillLanes, staticChunks, minChunk;
-    // light-sorted mode (tuning key 3): tasks are slotted per setup workgroup, a counting sort over kSortBins light bins
-    // produces `sorted` (task slots in bin order) without a single global atomic
-    uint32_t sortMode, numGroups; uint32_t* counts; uint8_t* keys; uint16_t* hist; uint32_t* binOffset; uint32_t* binTotal; uint32_t* sorted;
+    // Pixels without a shadow ray (sky, emitter, dead ray) never enter the ray queue: each is one float4 (colour | pixel index) of a list
+    // that grows DOWN from the end of the same buffer, entry k at rayless[-1 - k].  Rays grow up from the front, and
+    // 64 x rays + 16 x ray-less <= 64 x pixels = the buffer, so the two never meet.
+    float4* rayless;
+    // light-sorted mode (tuning key 3): a counting sort over kSortBins light bins produces `sorted` (task slots in bin order); a setup
+    // workgroup's tasks are the slots [bases[g], bases[g] + counts[g])
+    uint32_t sortMode, numGroups; uint32_t* counts; uint32_t* bases; uint8_t* keys; uint16_t* hist; uint32_t* binOffset; uint32_t* binTotal; uint32_t* sorted;
 };
-constexpr uint32_t kNoRayTask = 0xFFFFFFFFu;   // light-triangle field of a task that carries only a finished pixel's colour
-constexpr uint32_t kSortBins = 64;   // counters[0] = tail (tasks appended), [1] = head (tasks taken)
+constexpr uint32_t kNoRayTask = 0xFFFFFFFFu;   // light triangle of a live pixel whose ray is dead (black whatever it finds): the pixel joins the ray-less list
+constexpr uint32_t kSortBins = 64;   // counters[0] = ray tail (tasks appended), [1] = ray-less entries appended, [2] = head (tasks taken)
 constexpr int kRefillLanes = 16;
 
 // ---- spatial reuse with SPECULATIVE neighbour gathers (R.cu:1913-1941).
@@ -218,41 +222,44 @@ __global__ __launch_bounds__(kBlock) RT_SETUP_WAVES void k_di_part2_setup(DevSce
         fr.depth[i] = pp.hitDistance;
         { f2 on; on.x = own.nx; on.y = own.ny; store_rec(fr.dprevWrite + i, pp.hitDistance, on, R); }
     }
-    // ---- compaction of the live lanes: ballot + prefix popcount inside a wave, a 4-entry LDS prefix across the waves
+    // ---- compaction of the lanes with a ray and of those without: two ballots + prefix popcounts inside a wave, ONE 4-entry LDS prefix
+    // across the waves — both counts (<= 256 each) travel in one word, rays in the low half, ray-less pixels in the high half
     __shared__ uint32_t s_count[kBlock / 64];
-    __shared__ uint32_t s_base;
+    __shared__ unsigned long long s_base;
     __shared__ uint32_t s_hist[kSortBins];
-    const bool queued = live || noRay;
-    const unsigned long long mask = __ballot(queued);
+    const bool hasRay = live && ti != kNoRayTask, rayless = (live || noRay) && !hasRay;
+    const unsigned long long mask = __ballot(hasRay), emptyMask = __ballot(rayless);
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (lane == 0u) s_count[wave] = (uint32_t)__popcll(mask);
+    if (lane == 0u) s_count[wave] = (uint32_t)__popcll(mask) | ((uint32_t)__popcll(emptyMask) << 16);
     if (q.sortMode && threadIdx.x < kSortBins) s_hist[threadIdx.x] = 0u;
     __syncthreads();
-    const uint32_t nLive = s_count[0] + s_count[1] + s_count[2] + s_count[3];
-    uint32_t rank = (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+    const uint32_t nBoth = s_count[0] + s_count[1] + s_count[2] + s_count[3], nRays = nBoth & 0xFFFFu, nEmpty = nBoth >> 16;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    uint32_t rank = (uint32_t)__popcll(mask & below) | ((uint32_t)__popcll(emptyMask & below) << 16);
     for (uint32_t k = 0; k < wave; ++k) rank += s_count[k];
-    uint32_t slot;
+    // ONE atomic per workgroup for both lists: ray tail and ray-less count are adjacent words (a single counter word saturates near
+    // 88 atomics/us: one per wave = 34 560 per 1080p frame cost 0.4 ms).  The ray tail stays below 2^32, so nothing carries into the count.
+    if (threadIdx.x == 0u) s_base = nBoth ? atomicAdd(reinterpret_cast<unsigned long long*>(q.counters), (unsigned long long)nRays | ((unsigned long long)nEmpty << 32)) : 0ull;
+    __syncthreads();
+    const uint32_t slot = (uint32_t)s_base + (rank & 0xFFFFu);
     if (q.sortMode) {
-        // slotted storage (256 slots per workgroup, no global atomic) + this workgroup's row of the light histogram
-        slot = blockIdx.x * (uint32_t)kBlock + rank;
+        // this workgroup's row of the light histogram, its range of slots for the scatter.  (Slots are compact in sorted mode too: with 256
+        // slots per workgroup a last workgroup full of rays would leave the ray-less list no room at the end of the buffer.)
         const uint32_t key = (uint32_t)(((unsigned long long)lightSlot * kSortBins) / (sc.emissiveCount ? sc.emissiveCount : 1u));
-        if (queued) { atomicAdd(&s_hist[key], 1u); q.keys[slot] = (uint8_t)key; }
+        if (hasRay) { atomicAdd(&s_hist[key], 1u); q.keys[slot] = (uint8_t)key; }
         __syncthreads();
         if (threadIdx.x < kSortBins) q.hist[(size_t)blockIdx.x * kSortBins + threadIdx.x] = (uint16_t)s_hist[threadIdx.x];
-        if (threadIdx.x == 0u) q.counts[blockIdx.x] = nLive;
-    } else {
-        // compact queue: ONE atomic per workgroup on the tail (a single counter word saturates near 88 atomics/us:
-        // one per wave = 34 560 per 1080p frame cost 0.4 ms)
-        if (threadIdx.x == 0u) s_base = nLive ? atomicAdd(q.counters + 0, nLive) : 0u;
-        __syncthreads();
-        slot = s_base + rank;
+        if (threadIdx.x == 0u) { q.counts[blockIdx.x] = nRays; q.bases[blockIdx.x] = (uint32_t)s_base; }
     }
-    if (queued) {
+    if (hasRay) {
         float4* t = q.tasks + (size_t)slot * 4;
         t[0] = make_float4(ro.x, ro.y, ro.z, tLight);
         t[1] = make_float4(rd.x, rd.y, rd.z, __int_as_float((int)ti));
         t[2] = make_float4(Lvis.x, Lvis.y, Lvis.z, __int_as_float((int)i));      // the pixel travels with both candidate radiances:
         t[3] = make_float4(Lsky.x, Lsky.y, Lsky.z, __int_as_float((int)i));      // the epilogue loads exactly one of them
+    } else if (rayless) {
+        const size_t k = (size_t)(uint32_t)(s_base >> 32) + (rank >> 16);
+        q.rayless[-1 - (ptrdiff_t)k] = make_float4(Lvis.x, Lvis.y, Lvis.z, __int_as_float((int)i));   // a finished pixel's colour (dead ray: black)
     }
 }
 
@@ -284,12 +291,11 @@ __global__ __launch_bounds__(kBlock) void k_di_sort_scatter(ShadowQueue q) {
     if (t < kSortBins) s_rank[t] = 0u;
     if (t == 0u) {
         uint32_t run = 0;
-        for (uint32_t b = 0; b < kSortBins; ++b) { s_start[b] = run; run += q.binTotal[b]; }
-        if (g == 0u) q.counters[0] = run;                           // total number of tasks (queue tail)
+        for (uint32_t b = 0; b < kSortBins; ++b) { s_start[b] = run; run += q.binTotal[b]; }     // (run ends at the queue tail the setup kernel counted)
     }
     __syncthreads();
     if (t < q.counts[g]) {
-        const uint32_t slot = g * (uint32_t)kBlock + t, key = q.keys[slot];
+        const uint32_t slot = q.bases[g] + t, key = q.keys[slot];
         const uint32_t r = atomicAdd(&s_rank[key], 1u);
         q.sorted[s_start[key] + q.binOffset[(size_t)g * kSortBins + key] + r] = slot;
     }
@@ -315,7 +321,7 @@ RT_DEV void di_part2_trace_body(const DevScene& sc, const DevFrame& fr, const Sh
     int32_t* lds = s_stack + threadIdx.x;
     const float4* top4 = stage_top_nodes(sc.nodes, sc.topCount, sc.stackBudget, s_stack);
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t total = q.counters[0];
+    const uint32_t total = q.counters[0];                          // rays queued
     // Work distribution: every wave owns the first `first` tasks of its own slice statically (wave w: [w * first, (w + 1) * first)),
     // further chunks are stolen from a shared head that starts behind the static slices.  `first` is key 9 x chunk when there is
     // plenty of work and an even share when the queue is shorter than that (a narrow multi-GPU band): then no atomic is
@@ -329,6 +335,12 @@ RT_DEV void di_part2_trace_body(const DevScene& sc, const DevFrame& fr, const Sh
     const uint32_t first = share < want1 ? (share < 16u ? 16u : share) : want1;
     const uint32_t dynBase = nWaves * first;
     const bool hasDyn = dynBase < total;                           // otherwise the static chunks cover the whole queue: no atomics at all
+    // Pixels without a ray first: every wave runs the epilogues of its share of the ray-less list at full width (nothing of a ray is live
+    // yet).  Image and accumulation stay this kernel's alone, which the pipelining of frames relies on.
+    for (uint32_t k = myWave * 64u + lane, nEmpty = q.counters[1]; k < nEmpty; k += nWaves * 64u) {
+        const float4 L = q.rayless[-1 - (ptrdiff_t)k];
+        epilogue(fr, (uint32_t)__float_as_int(L.w), rgb1(mk3(L.x, L.y, L.z)));
+    }
     LaneRay r; r.cur = kExit; r.top = 0; r.nBox = 0; r.nTri = 0; r.nNode = 0;
     bool active = false;                                           // lane owns a ray that is still being traced
     bool pending = false;                                          // lane's ray is finished, its pixel epilogue not yet run
@@ -357,7 +369,7 @@ RT_DEV void di_part2_trace_body(const DevScene& sc, const DevFrame& fr, const Sh
                 // previous claim, so no extra access to the head word is needed
                 uint32_t size = (total - chunkEnd) / nWaves;
                 size = size < q.minChunk ? q.minChunk : (size > chunk ? chunk : size);
-                if (lane == 0u) base = dynBase + atomicAdd(q.counters + 1, size);
+                if (lane == 0u) base = dynBase + atomicAdd(q.counters + 2, size);
                 base = (uint32_t)__shfl((int)base, 0);
                 chunkNext = base < total ? base : total;
                 chunkEnd = (base + size < total) ? base + size : total;
@@ -372,8 +384,6 @@ RT_DEV void di_part2_trace_body(const DevScene& sc, const DevFrame& fr, const Sh
                 const float4 t0 = t[0], t1 = t[1];
                 r.o = mk3(t0.x, t0.y, t0.z);
                 r.d = mk3(t1.x, t1.y, t1.z); r.lightTri = (uint32_t)__float_as_int(t1.w);
-                if (r.lightTri == kNoRayTask) { pending = true; outcome = 1u; }          // a finished pixel: straight to the epilogue with its colour (t[2])
-                else {
                 r.pk = make_raypk(r.o, safe_inv(r.d.x), safe_inv(r.d.y), safe_inv(r.d.z));
                 const float tL = t0.w;                                  // distance to the light triangle, from the setup kernel
                 r.closestMode = !(tL > 0.0f);
@@ -384,10 +394,9 @@ RT_DEV void di_part2_trace_body(const DevScene& sc, const DevFrame& fr, const Sh
                 r.top = 0; lane_push(lds, r.top, kExit);
                 r.cur = (sc.triCount == 0 || ray_not_finite(r.o, r.d)) ? kExit : sc.rootRef;   // (a non-finite ray also fails the light test above: closest mode, miss)
                 active = true;
-                }
             }
         }
-        if (__ballot(active) == 0ull) { if (!more && __ballot(pending) == 0ull) break; else continue; }   // (tasks without a ray leave lanes pending but not active)
+        if (__ballot(active) == 0ull) { if (!more) break; else continue; }   // (no ray in flight: every epilogue has run above)
         // ---------------- traverse until enough lanes have finished to make a refill worthwhile
         while (true) {
             // inner nodes

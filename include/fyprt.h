@@ -335,8 +335,8 @@ int fyprt_set_ray_counting(fyprt_context* ctx, int enabled);
  * key 0: tile order — 0 linear, 1 one contiguous eighth of the tiles per XCD, 2 every 8th tile row per XCD.
  * key 1: ReSTIR DI Part 2 — 0 one thread per pixel, 1 setup kernel + shadow-task queue + persistent trace waves.
  * key 2: persistent workgroups per CU for the trace kernel (default 0 = as many as LDS and registers allow: 6 today).
- * key 3: 1 = counting-sort the shadow tasks by light bin before tracing (slotted tasks + histogram matrix + column scan +
- *        scatter, no global atomics).  Default 0: measured +0.04 ms for the sort and no faster trace — shadow-ray cost is
+ * key 3: 1 = counting-sort the shadow tasks by light bin before tracing (histogram matrix + column scan + scatter; one
+ *        global atomic per setup workgroup, as without the sort).  Default 0: measured +0.04 ms for the sort and no faster trace — shadow-ray cost is
  *        dominated by the geometry around the ray ORIGIN, which the unsorted tile order already keeps coherent.
  * key 4: tasks a persistent wave claims per queue-head atomic (default 128).
  * key 5: idle lanes that trigger a refill of a persistent wave (default 24).
