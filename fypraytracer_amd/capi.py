@@ -22,6 +22,8 @@ TECHNIQUE_NAMES = ["BRUTE_FORCE", "UNIFORM_SAMPLING", "COSINE_WEIGHTED_SAMPLING"
 
 BUF_ACCUM, BUF_IMAGE, BUF_PAYLOAD, BUF_DEPTH, BUF_NORMAL, BUF_DI, BUF_DI_PREV, BUF_GI, BUF_GI_PREV = range(9)
 BUF_TEMPORAL = 10   # 64 B per pixel: the history record the last Context.denoise_temporal* call wrote (TEMPORAL_DTYPE)
+BUF_UPSCALE_GUIDE = 11    # 32 B per HI-RES pixel: the guide record of the hi-res primary hit (UPSCALE_GUIDE_DTYPE); Context.denoise_upscale*
+BUF_UPSCALE_ALBEDO = 12   # float4 per hi-res pixel: albedo | 1 (filterable) or pass-through colour | 0
 BUF_ALBEDO = 9      # float4 per pixel: albedo of the primary hit, w = 1 filterable / 0 not; written by Context.denoise* (fyprt_denoise)
 
 # numpy views of the per-pixel records (Ray.h:13-22, ReSTIR_DI_Reservoir.cuh:9-16, ReSTIR_GI_Reservoir.cuh:9-27)
@@ -37,9 +39,13 @@ assert PAYLOAD_DTYPE.itemsize == 40 and DI_DTYPE.itemsize == 20 and GI_DTYPE.ite
 TEMPORAL_DTYPE = np.dtype([("worldPosition", "<f4", 3), ("hitDistance", "<f4"), ("worldNormal", "<f4", 3), ("filterable", "<f4"),
                            ("colour", "<f4", 3), ("N", "<f4"), ("m1", "<f4"), ("m2", "<f4"), ("variance", "<f4"), ("pad", "<f4")])
 assert TEMPORAL_DTYPE.itemsize == 64
+# the upscaler's hi-res guide record (include/fyprt.h, "upscaler"; new, no reference counterpart)
+UPSCALE_GUIDE_DTYPE = np.dtype([("worldPosition", "<f4", 3), ("hitDistance", "<f4"), ("worldNormal", "<f4", 3), ("filterable", "<f4")])
+assert UPSCALE_GUIDE_DTYPE.itemsize == 32
 BUFFER_DTYPES = {BUF_ACCUM: np.dtype(("<f4", 4)), BUF_IMAGE: np.dtype("<u4"), BUF_PAYLOAD: PAYLOAD_DTYPE,
                  BUF_DEPTH: np.dtype("<f4"), BUF_NORMAL: np.dtype(("<f4", 2)), BUF_DI: DI_DTYPE, BUF_DI_PREV: DI_DTYPE,
-                 BUF_GI: GI_DTYPE, BUF_GI_PREV: GI_DTYPE, BUF_ALBEDO: np.dtype(("<f4", 4)), BUF_TEMPORAL: TEMPORAL_DTYPE}
+                 BUF_GI: GI_DTYPE, BUF_GI_PREV: GI_DTYPE, BUF_ALBEDO: np.dtype(("<f4", 4)), BUF_TEMPORAL: TEMPORAL_DTYPE,
+                 BUF_UPSCALE_GUIDE: UPSCALE_GUIDE_DTYPE, BUF_UPSCALE_ALBEDO: np.dtype(("<f4", 4))}
 
 VERTEX_DTYPE = np.dtype([("position", "<f4", 3), ("normal", "<f4", 3), ("uv", "<f4", 2)])
 TRIANGLE_DTYPE = np.dtype([("v0", "<u4"), ("v1", "<u4"), ("v2", "<u4"), ("materialIndex", "<i4")])
@@ -166,6 +172,28 @@ class TemporalParams(C.Structure):  # fyprt_temporal_params (36 B) with the libr
 assert C.sizeof(TemporalParams) == 36
 
 
+class UpscaleParams(C.Structure):  # fyprt_upscale_params (44 B) with the library's defaults (fyprt_upscale_default_params)
+    _fields_ = [("scale", C.c_uint32), ("temporal", C.c_uint32), ("filter", TemporalParams)]
+
+    def __init__(self, **kw):
+        """Keywords: `scale`, `temporal`, `filter` (a TemporalParams), or any keyword of TemporalParams (set on `filter`)."""
+        super().__init__()
+        self.scale, self.temporal = 2, 0
+        self.filter = TemporalParams()
+        for k, v in kw.items():
+            if hasattr(self, k):
+                setattr(self, k, v)
+            elif hasattr(self.filter, k):
+                setattr(self.filter, k, v)
+            elif hasattr(self.filter.spatial, k):
+                setattr(self.filter.spatial, k, v)
+            else:
+                raise AttributeError(k)
+
+
+assert C.sizeof(UpscaleParams) == 44
+
+
 EXPORTED_SYMBOLS = [
     "fyprt_create", "fyprt_destroy", "fyprt_last_error", "fyprt_resize", "fyprt_set_rows", "fyprt_upload_scene",
     "fyprt_set_camera", "fyprt_render", "fyprt_render_async", "fyprt_synchronize", "fyprt_readback",
@@ -188,6 +216,7 @@ EXPORTED_SYMBOLS = [
     "fyprt_append_meshes", "fyprt_append_textures",
     "fyprt_group_denoise_temporal", "fyprt_group_denoise_temporal_device", "fyprt_group_denoise_temporal_reset",
     "fyprt_group_denoise_temporal_plan",
+    "fyprt_upscale_default_params", "fyprt_denoise_upscale", "fyprt_denoise_upscale_device",
 ]
 GROUP_HISTORY_ROWS = 32   # FYPRT_GROUP_HISTORY_ROWS: the default history window of Group.denoise_temporal, rows either side of a band
 
@@ -262,6 +291,10 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
         lib.fyprt_denoise_temporal.argtypes = [vp, C.POINTER(TemporalParams), vp, vp, C.POINTER(FrameStats)]
         lib.fyprt_denoise_temporal_device.argtypes = [vp, C.POINTER(TemporalParams), vp, vp]
         lib.fyprt_denoise_temporal_reset.argtypes = [vp]
+    if hasattr(lib, "fyprt_denoise_upscale"):    # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
+        lib.fyprt_upscale_default_params.argtypes = [C.POINTER(UpscaleParams)]
+        lib.fyprt_denoise_upscale.argtypes = [vp, C.POINTER(UpscaleParams), vp, vp, C.POINTER(FrameStats)]
+        lib.fyprt_denoise_upscale_device.argtypes = [vp, C.POINTER(UpscaleParams), vp, vp]
     if hasattr(lib, "fyprt_denoise_temporal_set_motion"):   # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
         lib.fyprt_denoise_temporal_set_motion.argtypes = [vp, C.c_int]
     lib.fyprt_group_create.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(u32), C.POINTER(vp)]
@@ -377,6 +410,7 @@ class Context:
         self.h = h
         self.device = device
         self.width = self.height = 0
+        self._upscale = 1        # the scale of the last denoise_upscale* call: read_buffer sizes the two BUF_UPSCALE_* buffers by it
         self._keep = None
 
     def _check(self, rc):
@@ -397,6 +431,7 @@ class Context:
     def resize(self, width, height):
         self._check(self.lib.fyprt_resize(self.h, width, height))
         self.width, self.height = width, height
+        self._upscale = 1
 
     def set_rows(self, row_begin, row_end, halo_rows=0):
         self._check(self.lib.fyprt_set_rows(self.h, row_begin, row_end, halo_rows))
@@ -450,7 +485,8 @@ class Context:
 
     def read_buffer(self, which) -> np.ndarray:
         dt = BUFFER_DTYPES[which]
-        out = np.empty(self.width * self.height, dtype=dt)
+        s = self._upscale if which in (BUF_UPSCALE_GUIDE, BUF_UPSCALE_ALBEDO) else 1       # (flat, as every buffer: s*height rows of s*width)
+        out = np.empty(self.width * s * self.height * s, dtype=dt)
         self._check(self.lib.fyprt_read_buffer(self.h, which, _ptr(out), out.nbytes))
         return out
 
@@ -747,6 +783,49 @@ class Context:
                                                            C.c_void_p(image_tensor.data_ptr()) if image_tensor is not None else None,
                                                            C.c_void_p(radiance_tensor.data_ptr()) if radiance_tensor is not None else None))
         cur.wait_stream(ext)                                           # torch's later work follows the denoiser
+
+    def denoise_upscale(self, params: UpscaleParams | None = None, want_radiance=True, with_stats=False):
+        """Denoise the frame rendered last at its own size and present it at scale x that size (fyprt_denoise_upscale, blocking; defaults
+        when `params` is None): the low-res stage of denoise() or, with params.temporal, of denoise_temporal() — the history then advances
+        as in that call — hi-res primary rays, and a resolve guided by them.  Returns (image sH x sW uint32 ABGR8, radiance sH x sW x 4
+        float32 or None), with `with_stats` also the FrameStats.  read_buffer(BUF_UPSCALE_GUIDE / BUF_UPSCALE_ALBEDO) afterwards gives the
+        hi-res records (sH * sW of them)."""
+        p = params if params is not None else UpscaleParams()
+        s = int(p.scale)
+        h, w = self.height * s, self.width * s
+        img = np.empty(max(h * w, 1), dtype=np.uint32)
+        rad = np.empty((max(h * w, 1), 4), dtype=np.float32) if want_radiance else None
+        st = FrameStats()
+        self._check(self.lib.fyprt_denoise_upscale(self.h, C.byref(p), _ptr(img), _ptr(rad), C.byref(st)))
+        self._upscale = s
+        out = (img.reshape(h, w), rad.reshape(h, w, 4) if want_radiance else None)
+        return out + (st,) if with_stats else out
+
+    def denoise_upscale_tensor(self, image_tensor, radiance_tensor, params: UpscaleParams | None = None):
+        """denoise_upscale into device tensors of the hi-res size (fyprt_denoise_upscale_device): int32 (sH, sW) / float32 (sH, sW, 4);
+        stream ordering exactly as denoise_tensor."""
+        import torch
+        p = params if params is not None else UpscaleParams()
+        s = int(p.scale)
+        if image_tensor is None and radiance_tensor is None:
+            raise ValueError("denoise_upscale_tensor: at least one output tensor is needed")
+        for t, dt, shape, name in ((image_tensor, torch.int32, (self.height * s, self.width * s), "image_tensor"),
+                                   (radiance_tensor, torch.float32, (self.height * s, self.width * s, 4), "radiance_tensor")):
+            if t is None:
+                continue
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"denoise_upscale_tensor: {name} must be a contiguous {dt} tensor of shape {shape}")
+            if t.device.type != "cuda" or (t.device.index if t.device.index is not None else torch.cuda.current_device()) != self.device:
+                raise ValueError(f"denoise_upscale_tensor: {name} must be on cuda:{self.device}, the context's GPU")
+        dev = (image_tensor if image_tensor is not None else radiance_tensor).device
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
+        ext.wait_stream(cur)                                           # the outputs are allocated (and their earlier uses done) before the kernels run
+        self._check(self.lib.fyprt_denoise_upscale_device(self.h, C.byref(p),
+                                                          C.c_void_p(image_tensor.data_ptr()) if image_tensor is not None else None,
+                                                          C.c_void_p(radiance_tensor.data_ptr()) if radiance_tensor is not None else None))
+        self._upscale = s
+        cur.wait_stream(ext)                                           # torch's later work follows the upscaler
 
     def denoise_temporal_reset(self):
         """Drops the temporal history (fyprt_denoise_temporal_reset): the next denoise_temporal* call behaves as a first call."""

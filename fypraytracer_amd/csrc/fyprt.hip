@@ -19,6 +19,7 @@
 #include "rt_query.h"
 #include "rt_denoise.h"
 #include "rt_temporal.h"
+#include "rt_upscale.h"
 
 using namespace rt;
 
@@ -212,6 +213,14 @@ struct fyprt_context {
     void release_temporal() { dt = Temporal(); drop_history(); }
     void release_snapshot() { dtSnap.release(); dtMoved.release(); dtSnapPending = false; }
     void release_denoise() { dn = Denoise(); albedoValid = false; }
+    // upscaler (fyprt_denoise_upscale*, rt_upscale.h): the hi-res guide records (2 quads per hi-res pixel) and albedo | pass-through colour
+    // (FYPRT_BUF_UPSCALE_GUIDE / _ALBEDO) and the host entry's hi-res output staging, allocated on the first call for its scale, reallocated
+    // when the scale changes, dropped by fyprt_resize; its timing events.  frameCam / frameSky: the camera and the sky colour the last
+    // frame was enqueued with (taken where framePV is) — what the hi-res primary rays are formed and the misses coloured with
+    struct Upscale { DevBuf<float4> guide, albedo, outRad; DevBuf<uint32_t> outImg; } up; Event upEv[4];
+    uint32_t upScale = 0; bool upValid = false;      // the scale the hi-res buffers are sized for (0: none); they hold a call's records
+    DevCamera frameCam{}; f3 frameSky{};
+    void release_upscale() { up = Upscale(); upScale = 0; upValid = false; }
 
     fyprt_context() { for (int k = 0; k < K_COUNT; ++k) tuning[k] = kTuning[k].def; }
 
@@ -397,7 +406,7 @@ int fyprt_resize(fyprt_context* c, uint32_t w, uint32_t h) {
     if (c->hostOnly) return c->fail(FYPRT_ESTATE, "host-only context (device -1) has no device buffers");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, sync_all(c));
-    c->release_denoise(); c->release_temporal(); c->frameComplete = false;
+    c->release_denoise(); c->release_temporal(); c->release_upscale(); c->frameComplete = false;
     const size_t n = (size_t)w * h;
     // cudaMemset(…, 0, …) of every buffer: Renderer.cu:333-355, :372, :393, :414
     TRY(alloc_zeroed(c, c->accum, n)); TRY(alloc_zeroed(c, c->image, n)); TRY(alloc_zeroed(c, c->payload, n)); TRY(alloc_zeroed(c, c->depth, n));
@@ -1417,6 +1426,7 @@ static int begin_frame(FrameRun& f) {
     f.grid = tile_grid(c, c->rowBegin, c->rowEnd); f.ev = c->ring[c->frameSerial % fyprt_context::kRing];
     if (f.phase == 2) { f.ei = 2; return FYPRT_OK; }          // part 1 recorded its start and its end
     std::memcpy(c->framePV, c->camPV, 64);     // the camera this frame is rendered with (fyprt_denoise_temporal)
+    c->frameCam = c->dcam; c->frameSky = f.st.sky;   // ... and what fyprt_denoise_upscale traces and colours its hi-res primary rays with
     if (c->countRays) HIPCHK(c, hipMemsetAsync(c->rayCounter.p, 0, 256, c->stream));
     // frame 1 (or toAccumulate == false): the accumulator starts from zero (Renderer.cu:50-51) — on `stream`, which owns it (the whole buffer, as the
     // reference does, not just this context's rows: a band moved later with fyprt_set_rows must not find the sums of an earlier accumulation in its new rows)
@@ -1724,6 +1734,10 @@ int fyprt_read_buffer(fyprt_context* c, int which, void* dst, size_t bytes) {
         case FYPRT_BUF_TEMPORAL:
             if (!c->dtValid) return c->fail(FYPRT_ESTATE, "fyprt_read_buffer: FYPRT_BUF_TEMPORAL is written by fyprt_denoise_temporal");
             src = c->dt.hist[c->dtCur].p; n = c->dt.hist[c->dtCur].bytes(); break;
+        case FYPRT_BUF_UPSCALE_GUIDE: case FYPRT_BUF_UPSCALE_ALBEDO:
+            if (!c->upValid) return c->fail(FYPRT_ESTATE, "fyprt_read_buffer: FYPRT_BUF_UPSCALE_* are written by fyprt_denoise_upscale");
+            src = which == FYPRT_BUF_UPSCALE_GUIDE ? c->up.guide.p : c->up.albedo.p;
+            n = which == FYPRT_BUF_UPSCALE_GUIDE ? c->up.guide.bytes() : c->up.albedo.bytes(); break;
         default: return c->fail(FYPRT_EINVAL, "fyprt_read_buffer: unknown buffer");
     }
     if (which == FYPRT_BUF_GI_RESERVOIR || which == FYPRT_BUF_GI_PREV) {
@@ -2036,15 +2050,18 @@ static int check_denoise_frame(fyprt_context* c, const char* who) {
         return c->fail(FYPRT_ESTATE, std::string(who) + ": no complete frame since the last fyprt_resize / fyprt_upload_scene / fyprt_update_vertices / fyprt_update_transforms");
     return FYPRT_OK;
 }
+static int check_denoise_rows(fyprt_context* c, const char* who) {
+    if (c->comm || c->rowBegin != 0 || c->rowEnd != c->H || c->stripeRows != 0)
+        return c->fail(FYPRT_ESTATE, std::string(who) + ": the context must render every row of the frame (no band, stripes, group or communicator)");
+    return FYPRT_OK;
+}
 static int check_denoise(fyprt_context* c, const fyprt_denoise_params* p, const void* rgba8, const void* radiance4, bool device) {
     const char* who = device ? "fyprt_denoise_device" : "fyprt_denoise";
     if (!c) return FYPRT_EINVAL;
     TRY(check_denoise_params(c, who, p));
     TRY(check_denoise_outputs(c, who, rgba8, radiance4, device));
     TRY(check_denoise_frame(c, who));
-    if (c->comm || c->rowBegin != 0 || c->rowEnd != c->H || c->stripeRows != 0)
-        return c->fail(FYPRT_ESTATE, std::string(who) + ": the context must render every row of the frame (no band, stripes, group or communicator)");
-    return FYPRT_OK;
+    return check_denoise_rows(c, who);
 }
 
 extern "C++" {
@@ -2062,26 +2079,30 @@ template <class F> static void for_dn_step(int step, F&& launch) {
     }
 }
 
-// The blocking form of either denoiser: outputs staged on the device, `enqueue(rgba8, radiance4, &launches)`, copied back; the stats'
-// parts are the times between the call's `nEv` timing events.
-template <class Enqueue> static int denoise_blocking(fyprt_context* c, uint32_t* rgba8, float* radiance4, fyprt_frame_stats* stats, Event* ev, int nEv, Enqueue&& enqueue) {
+// The blocking form of a denoiser call: `n` output pixels staged on the device in outImg / outRad, `enqueue(rgba8, radiance4, &launches)`,
+// copied back; the stats' parts are the times between the call's `nEv` timing events.
+template <class Enqueue> static int staged_blocking(fyprt_context* c, size_t n, DevBuf<uint32_t>& outImg, DevBuf<float4>& outRad, uint32_t* rgba8, float* radiance4,
+                                                    fyprt_frame_stats* stats, Event* ev, int nEv, Enqueue&& enqueue) {
     if (stats) std::memset(stats, 0, sizeof *stats);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, sync_all(c));                           // as fyprt_readback: the last frame is complete on every stream
     for (int k = 0; k < nEv; ++k) HIPCHK(c, create(ev[k]));
-    const size_t n = (size_t)c->W * c->H;
-    if (rgba8 && c->dn.outImg.n != n) HIPCHK(c, c->dn.outImg.alloc(n));
-    if (radiance4 && c->dn.outRad.n != n) HIPCHK(c, c->dn.outRad.alloc(n));
+    if (rgba8 && outImg.n != n) HIPCHK(c, outImg.alloc(n));
+    if (radiance4 && outRad.n != n) HIPCHK(c, outRad.alloc(n));
     int launches = 0;
-    TRY(enqueue(rgba8 ? c->dn.outImg.p : nullptr, radiance4 ? c->dn.outRad.p : nullptr, &launches));
-    if (rgba8) HIPCHK(c, hipMemcpyAsync(rgba8, c->dn.outImg.p, n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (radiance4) HIPCHK(c, hipMemcpyAsync(radiance4, c->dn.outRad.p, n * 16, hipMemcpyDeviceToHost, c->stream));
+    TRY(enqueue(rgba8 ? outImg.p : nullptr, radiance4 ? outRad.p : nullptr, &launches));
+    if (rgba8) HIPCHK(c, hipMemcpyAsync(rgba8, outImg.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (radiance4) HIPCHK(c, hipMemcpyAsync(radiance4, outRad.p, n * 16, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (stats) {
         stats->launches = (uint32_t)launches;
         for (int k = 0; k + 1 < nEv; ++k) { HIPCHK(c, hipEventElapsedTime(&stats->kernel_ms_part[k], ev[k], ev[k + 1])); stats->kernel_ms += stats->kernel_ms_part[k]; }
     }
     return FYPRT_OK;
+}
+// ... of either denoiser at the rendered size: width x height pixels through the denoiser's own staging
+template <class Enqueue> static int denoise_blocking(fyprt_context* c, uint32_t* rgba8, float* radiance4, fyprt_frame_stats* stats, Event* ev, int nEv, Enqueue&& enqueue) {
+    return staged_blocking(c, (size_t)c->W * c->H, c->dn.outImg, c->dn.outRad, rgba8, radiance4, stats, ev, nEv, enqueue);
 }
 }  // extern "C++"
 
@@ -2146,13 +2167,19 @@ static int end_denoise(fyprt_context* c, const DnFrame& fr, uint32_t iterations,
 }
 
 // Enqueues prepare + iterations (+ finish) on the context stream, outputs in device memory.  ev: 3 timing events or null.
-static int enqueue_denoise(fyprt_context* c, const fyprt_denoise_params* p, uint32_t* rgba8, float4* radiance4, const Event* ev, int* launched) {
+// keep (fyprt_denoise_upscale*: its low-res stage): the call stops before the output — the last iteration writes its colour buffer as every
+// other one does (DnIter::last = 0), no finish kernel, no dn_call_done — and *keep is the buffer that holds e.
+static int enqueue_denoise(fyprt_context* c, const fyprt_denoise_params* p, uint32_t* rgba8, float4* radiance4, const Event* ev, int* launched,
+                           const float4** keep = nullptr) {
     DnFrame fr;
     TRY(begin_denoise(c, *p, rgba8, radiance4, ev, launched, fr));
     for (uint32_t k = 0; k < p->iterations; ++k) {
-        launch_dn_iterate(c, fr, make_dn_iter(*p, k, true), DnBand{0, c->H}, c->dn.col[k & 1u].p, c->dn.col[(k + 1u) & 1u].p);
+        DnIter it = make_dn_iter(*p, k, true);
+        if (keep) it.last = 0u;
+        launch_dn_iterate(c, fr, it, DnBand{0, c->H}, c->dn.col[k & 1u].p, c->dn.col[(k + 1u) & 1u].p);
         ++*launched;
     }
+    if (keep) { *keep = c->dn.col[p->iterations & 1u].p; return FYPRT_OK; }
     return end_denoise(c, fr, p->iterations, c->dn.col[0].p, ev ? ev + 2 : nullptr, launched);
 }
 
@@ -2242,8 +2269,10 @@ static DtCall make_dt_call(const fyprt_context* c, const fyprt_temporal_params& 
     return tc;
 }
 
-// Enqueues prepare + reproject + iterations (+ finish) on the context stream.  ev: 4 timing events or null.
-static int enqueue_temporal(fyprt_context* c, const fyprt_temporal_params* p, uint32_t* rgba8, float4* radiance4, const Event* ev, int* launched) {
+// Enqueues prepare + reproject + iterations (+ finish) on the context stream.  ev: 4 timing events or null.  keep: as enqueue_denoise's —
+// the history advances as in any temporal call.
+static int enqueue_temporal(fyprt_context* c, const fyprt_temporal_params* p, uint32_t* rgba8, float4* radiance4, const Event* ev, int* launched,
+                            const float4** keep = nullptr) {
     const fyprt_denoise_params& sp = p->spatial;
     TRY(ensure_dt_buffers(c));
     if (c->dtGroup != 0) c->drop_history();      // a history a group wrote (fyprt_group_denoise_temporal*) covers the rows the context owned there
@@ -2259,14 +2288,16 @@ static int enqueue_temporal(fyprt_context* c, const fyprt_temporal_params* p, ui
     ++*launched;
     if (ev) HIPCHK(c, hipEventRecord(ev[2], c->stream));
     for (uint32_t k = 0; k < sp.iterations; ++k) {           // colour: dn.col[1] -> [0] -> [1] ...; variance: dt.var[0] -> [1] -> [0] ...
-        const DnIter it = make_dn_iter(sp, k, false);
+        DnIter it = make_dn_iter(sp, k, false);
+        if (keep) it.last = 0u;
         const float4* in = c->dn.col[(k + 1u) & 1u].p; float4* out = c->dn.col[k & 1u].p;
         const float* vin = c->dt.var[k & 1u].p; float* vout = c->dt.var[(k + 1u) & 1u].p;
         float4* fb = (k == 0 && p->feedback) ? hist : nullptr;
         launch_dt_iterate(c, fr, it, all, in, out, vin, vout, fb);
         ++*launched;
     }
-    TRY(end_denoise(c, fr, sp.iterations, c->dn.col[1].p, ev ? ev + 3 : nullptr, launched));
+    if (keep) { *keep = c->dn.col[(sp.iterations + 1u) & 1u].p; HIPCHK(c, hipGetLastError()); }      // (iteration k writes col[k & 1]; none: the integrated colour in col[1])
+    else TRY(end_denoise(c, fr, sp.iterations, c->dn.col[1].p, ev ? ev + 3 : nullptr, launched));
     c->dtCur = next; c->dtValid = true; c->dtGroup = 0; c->dtSnapPending = false; std::memcpy(c->dtPV, c->framePV, 64);
     return FYPRT_OK;
 }
@@ -2298,6 +2329,91 @@ int fyprt_denoise_temporal_set_motion(fyprt_context* c, int enabled) {
     c->dtMotion = enabled == 1;
     c->drop_history(); c->release_snapshot();
     return FYPRT_OK;
+}
+
+// ---- upscaler (rt_upscale.h; the contract is include/fyprt.h's).  The low-res stage of either denoiser, hi-res primary rays, the resolve.
+int fyprt_upscale_default_params(fyprt_upscale_params* out) {
+    if (!out) return FYPRT_EINVAL;
+    out->scale = 2; out->temporal = 0;
+    return fyprt_denoise_temporal_default_params(&out->filter);
+}
+
+static int check_upscale(fyprt_context* c, const fyprt_upscale_params* p, const void* rgba8, const void* radiance4, bool device) {
+    const char* who = device ? "fyprt_denoise_upscale_device" : "fyprt_denoise_upscale";
+    if (!c) return FYPRT_EINVAL;
+    if (!p) return c->fail(FYPRT_EINVAL, std::string(who) + ": NULL params");
+    if (p->scale < 2u || p->scale > 4u || p->temporal > 1u) return c->fail(FYPRT_EINVAL, std::string(who) + ": scale 2..4, temporal 0 / 1");
+    if (p->temporal) TRY(check_temporal_params(c, who, &p->filter));
+    if ((uint64_t)c->W * p->scale * ((uint64_t)c->H * p->scale) > (1ull << 31))
+        return c->fail(FYPRT_EINVAL, std::string(who) + ": scale*width x scale*height is beyond what fyprt_resize accepts");
+    TRY(check_denoise_params(c, who, &p->filter.spatial));
+    TRY(check_denoise_outputs(c, who, rgba8, radiance4, device));
+    TRY(check_denoise_frame(c, who));
+    return check_denoise_rows(c, who);
+}
+
+// The hi-res buffers for scale s.  Another scale than the last call's: that call may still be writing the old ones on the context stream
+static int ensure_up_buffers(fyprt_context* c, uint32_t s) {
+    const size_t n = (size_t)c->W * s * ((size_t)c->H * s);
+    if (c->upScale != s || c->up.albedo.n != n) {
+        if (c->up.albedo.p) HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->release_upscale();
+        HIPCHK(c, c->up.guide.alloc(2 * n)); HIPCHK(c, c->up.albedo.alloc(n));
+        c->upScale = s;
+    }
+    return FYPRT_OK;
+}
+
+// Enqueues the low-res stage, k_up_primary and k_up_resolve on the context stream (after ensure_up_buffers).  ev: 4 timing events or null.
+static int enqueue_upscale(fyprt_context* c, const fyprt_upscale_params* p, uint32_t* rgba8, float4* radiance4, const Event* ev, int* launched) {
+    const uint32_t s = p->scale, upW = c->W * s, upH = c->H * s;
+    const fyprt_denoise_params& sp = p->filter.spatial;
+    if (ev) HIPCHK(c, hipEventRecord(ev[0], c->stream));
+    const float4* e = nullptr;
+    if (p->temporal) TRY(enqueue_temporal(c, &p->filter, nullptr, nullptr, nullptr, launched, &e));
+    else TRY(enqueue_denoise(c, &sp, nullptr, nullptr, nullptr, launched, &e));
+    if (ev) HIPCHK(c, hipEventRecord(ev[1], c->stream));
+    {   // the frame's camera on the hi-res viewport; the scene as a frame's primary rays read it (key 7's quorum, the tree's stack budget), no ray counters
+        DevCamera cam = c->frameCam; cam.W = upW; cam.H = upH;
+        const StackLds stack = stack_lds(c, 0u);
+        DevScene sc = secondary_scene(c->dsc, (uint32_t)c->tuning[K_QUORUM_PRIMARY], nullptr);
+        sc.stackBudget = stack.budget; sc.topCount = 0u;
+        const uint32_t tilesX = (upW + 15u) / 16u, tilesY = (upH + 15u) / 16u;      // (tile_grid at the hi-res size)
+        const dim3 grid(c->tuning[K_TILE_ORDER] == 2 ? tilesX * ((tilesY + 7u) / 8u) * 8u : ((tilesX * tilesY + 7u) / 8u) * 8u);
+        hipLaunchKernelGGL(k_up_primary, grid, dim3(kBlock), stack.bytes, c->stream, sc, cam, (uint32_t)c->tuning[K_TILE_ORDER], c->frameSky, c->up.guide.p, c->up.albedo.p);
+        ++*launched;
+    }
+    if (ev) HIPCHK(c, hipEventRecord(ev[2], c->stream));
+    const UpFrame fr{c->W, c->H, (float)c->lastFrameIndex, sp.demodulate_albedo, sp.sigma_plane, sp.normal_power_log2, c->accum.p, c->dn.guide.p,
+                     c->dn.albedo.p, e, c->up.guide.p, c->up.albedo.p, rgba8, radiance4};
+    const dim3 rgrid(up_resolve_grid(upW, upH));
+    switch (s) {
+        case 2: hipLaunchKernelGGL(k_up_resolve<2>, rgrid, dim3(256), 0, c->stream, fr); break;
+        case 3: hipLaunchKernelGGL(k_up_resolve<3>, rgrid, dim3(256), 0, c->stream, fr); break;
+        default: hipLaunchKernelGGL(k_up_resolve<4>, rgrid, dim3(256), 0, c->stream, fr); break;
+    }
+    ++*launched;
+    HIPCHK(c, hipGetLastError());
+    if (ev) HIPCHK(c, hipEventRecord(ev[3], c->stream));
+    c->upValid = true;
+    return dn_call_done(c);
+}
+
+int fyprt_denoise_upscale(fyprt_context* c, const fyprt_upscale_params* p, uint32_t* rgba8, float* radiance4, fyprt_frame_stats* stats) {
+    TRY(check_upscale(c, p, rgba8, radiance4, false));
+    HIPCHK(c, hipSetDevice(c->device));
+    TRY(ensure_up_buffers(c, p->scale));
+    const size_t n = (size_t)c->W * p->scale * ((size_t)c->H * p->scale);
+    return staged_blocking(c, n, c->up.outImg, c->up.outRad, rgba8, radiance4, stats, c->upEv, 4,      // parts: the low-res stage, the hi-res primary rays, the resolve
+                           [&](uint32_t* img, float4* rad, int* launched) { return enqueue_upscale(c, p, img, rad, c->upEv, launched); });
+}
+
+int fyprt_denoise_upscale_device(fyprt_context* c, const fyprt_upscale_params* p, void* rgba8, void* radiance4) {
+    TRY(check_upscale(c, p, rgba8, radiance4, true));
+    HIPCHK(c, hipSetDevice(c->device));
+    TRY(ensure_up_buffers(c, p->scale));
+    int launches = 0;
+    return enqueue_upscale(c, p, static_cast<uint32_t*>(rgba8), static_cast<float4*>(radiance4), nullptr, &launches);
 }
 
 #include "fyprt_multi.h"

@@ -121,6 +121,14 @@ public:
     // Object motion (fyprt_denoise_temporal_set_motion): with it on, geometry updates keep the history and the next DenoiseTemporal
     // reprojects every hit through the vertices of the frame denoised before — for dragging a mesh with the temporal denoiser on.
     bool SetDenoiseMotion(bool on) { return !report(fyprt_denoise_temporal_set_motion(m_Ctx, on ? 1 : 0), "fyprt_denoise_temporal_set_motion"); }
+    // New (no reference counterpart): denoise the frame Render() just produced at its own size and present it at scale x that size
+    // (fyprt_denoise_upscale; nullptr = the library's defaults, scale 2 over the spatial denoiser).  `rgba8` holds scale*width x
+    // scale*height pixels.  With params->temporal = 1 the call is the DenoiseTemporal of this frame as well: call one or the other.
+    bool DenoiseUpscale(const fyprt_upscale_params* params, uint32_t* rgba8) {
+        fyprt_upscale_params p;
+        if (params) p = *params; else fyprt_upscale_default_params(&p);
+        return !report(fyprt_denoise_upscale(m_Ctx, &p, rgba8, nullptr, nullptr), "fyprt_denoise_upscale");
+    }
 
     void ResetFrameIndex() { fyprt_reset_frame_index(m_Ctx); }
     RenderingSettings& GetSettings() { return m_Settings; }

@@ -164,9 +164,14 @@ enum fyprt_buffer {
     FYPRT_BUF_GI_PREV = 8,      /*                             (Renderer.h:39)                    */
     FYPRT_BUF_ALBEDO = 9,       /* float4: rgb = albedo of the primary hit, w = 1 filterable / 0 not (rgb 0 there); written by
                                    fyprt_denoise* for the frame it denoised, FYPRT_ESTATE before (new, no reference counterpart) */
-    FYPRT_BUF_TEMPORAL = 10     /* 64 B: P.xyz, t | n.xyz, filterable | colour.rgb, N | m1, m2, variance, 0 — the history record the last
+    FYPRT_BUF_TEMPORAL = 10,    /* 64 B: P.xyz, t | n.xyz, filterable | colour.rgb, N | m1, m2, variance, 0 — the history record the last
                                    fyprt_denoise_temporal* call wrote; FYPRT_ESTATE before the first call and after anything that drops the
                                    history (new, no reference counterpart) */
+    FYPRT_BUF_UPSCALE_GUIDE = 11,  /* 32 B per HI-RES pixel (scale*width x scale*height of the last fyprt_denoise_upscale* call): P.xyz, t |
+                                   n.xyz, filterable (1.0 / 0.0) — the denoiser's guide record of the hi-res primary hit; FYPRT_ESTATE
+                                   before the first successful call and after fyprt_resize (new, no reference counterpart) */
+    FYPRT_BUF_UPSCALE_ALBEDO = 12  /* float4 per hi-res pixel, valid as the guide: rgb = albedo, w = 1 for a filterable pixel; rgb = the
+                                   pass-through colour (sky / emission), w = 0 otherwise */
 };
 
 /* ---- lifetime (the reference has none: Renderer owns raw pointers and never frees them,
@@ -620,6 +625,60 @@ int fyprt_denoise_temporal_reset(fyprt_context* ctx);
  * changes as it moves lags behind it (fast drags look worse with the history kept than without); history_limit is the
  * control.  ReSTIR's own temporal reuse is not touched. */
 int fyprt_denoise_temporal_set_motion(fyprt_context* ctx, int enabled);
+
+/* ================================================================================================= upscaler
+ * New (no reference counterpart): denoise at the rendered size W x H, present at sW x sH, s = 2, 3 or 4 ("Upscaler").  The
+ * call runs the low-res stage of either denoiser, traces primary rays only at sW x sH, interpolates the demodulated colour under the
+ * hi-res guide records and multiplies by the hi-res albedo: geometric edges and texture detail arrive at the presented size, lighting at
+ * the rendered one.  Camera::RecalculateRayDirections forms (float)x / (float)width, and (float)(s x) / (float)(s W) is the correctly
+ * rounded value of the same rational: hi-res pixel (s x, s y) has bit for bit the ray of low-res pixel (x, y), so the rendered samples sit
+ * exactly on every s-th hi-res pixel.
+ * The contract.  Arithmetic as for fyprt_denoise.  W, H, n, c_p, filterable_p, a_p, d_p, P_p, n_p, t_p, w_n and w_z are fyprt_denoise's,
+ * with params->filter.spatial.  Capital letters name hi-res pixels Q = (X, Y), X < sW, Y < sH.
+ *   1. Low-res stage.  temporal = 0: fyprt_denoise up to its last iteration.  temporal = 1: steps 1 to 6 of fyprt_denoise_temporal with
+ *      params->filter — the history record, the consumed motion snapshot and FYPRT_BUF_TEMPORAL are exactly what that call would leave.
+ *      e_p = the colour after the last iteration (iterations = 0: e0_p, or the integrated colour; never the feedback colour).
+ *      out_p = e_p * d_p (filterable) or c_p: the pixel either denoiser would have output.
+ *   2. Hi-res guides.  The primary ray of Q is Camera::RecalculateRayDirections for a viewport sW x sH with the inverse matrices and the
+ *      position of the camera the frame was enqueued with (taken where the temporal denoiser's M is taken: a fyprt_set_camera between
+ *      frame and call changes nothing).  The primary record of Q is, bit for bit, the FYPRT_BUF_PAYLOAD record a context resized to
+ *      sW x sH with that camera and scene writes; hence the record of (s x, s y) is the low-res pixel's.  filterable_Q, a_Q, d_Q, P_Q, n_Q,
+ *      t_Q are derived from it as fyprt_denoise derives them.  Pass-through colour of a Q that is not filterable: a miss takes the sky
+ *      colour of the settings the frame was rendered with (taken with the camera), a directly seen emitter the material's emission as the
+ *      frames form it (emission_color * emission_power).
+ *   3. Resolve.  x0 = X div s, y0 = Y div s, fx = X - s x0, fy = Y - s y0.
+ *      Aligned (fx = fy = 0): out_Q = out_(x0, y0), no arithmetic.   Not aligned, Q not filterable: out_Q = the pass-through colour.
+ *      Not aligned, Q filterable: tx = (float)fx / (float)s, ty likewise; taps q = (x0 + dx, y0 + dy), dy outer, dx inner, both 0..1;
+ *        b = (dx ? tx : 1 - tx) * (dy ? ty : 1 - ty).  A tap is usable when it is inside the W x H image, filterable_q holds and b > 0.
+ *        w_n = max(0, dot(n_Q, n_q)) squared normal_power_log2 times;  x_z = |dot(n_Q, P_q - P_Q)| / (sigma_plane * t_Q),
+ *        w_z = 1 / (1 + x_z x_z);  w = (w_n w_z) b   (dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z).
+ *        Over the usable taps in order, from +0: S = sum w, C = sum e_q w, B = sum b, D = sum e_q b (per channel).
+ *        E_Q = C / S if S > 0; otherwise E_Q = D / B if a usable tap exists; otherwise out_Q = out_(x0, y0).
+ *        With an E_Q: out_Q = E_Q * d_Q (d_Q = 1 without demodulate_albedo).
+ *      radiance4 = (out_Q, accum_(x0, y0).w / n);  rgba8 = the frame epilogue's tonemap / clamp / pack of it.
+ *      There is no luminance term: no hi-res colour exists to compare.
+ *   So out[::s, ::s] of a call is, bit for bit, the output of fyprt_denoise / fyprt_denoise_temporal with the same parameters.
+ * Errors, in this order: FYPRT_EINVAL for a NULL context / params, scale outside 2..4 or temporal > 1, with temporal = 1 the parameter
+ * cases of fyprt_denoise_temporal (with 0 only filter.spatial is read), sW * sH beyond what fyprt_resize accepts, then everything
+ * fyprt_denoise refuses with FYPRT_EINVAL (parameter, alignment, both outputs NULL); then its FYPRT_ESTATE cases in its order (host-only
+ * context, no complete frame, between the two parts of a frame, bands / stripes / group and communicator members).
+ * No frame state moves.  With temporal = 0 the temporal history is untouched; with 1 the call IS a temporal call.  FYPRT_BUF_ALBEDO is
+ * written as by either denoiser.  Afterwards FYPRT_BUF_UPSCALE_GUIDE and FYPRT_BUF_UPSCALE_ALBEDO hold the hi-res records of step 2.  The
+ * hi-res buffers (48 B per hi-res pixel, plus up to 20 B of host-entry staging) are allocated on the first call, reallocated when scale
+ * changes (that call first waits for the context stream: an earlier call may still write the old ones) and dropped by fyprt_resize and
+ * fyprt_destroy. */
+typedef struct fyprt_upscale_params {
+    uint32_t scale;                 /* 2..4, default 2: the output is scale*W x scale*H */
+    uint32_t temporal;              /* 0 (default): the low-res stage is fyprt_denoise with filter.spatial;
+                                       1: it is fyprt_denoise_temporal with filter, and the call IS a temporal call */
+    fyprt_temporal_params filter;   /* defaults of fyprt_denoise_temporal_default_params */
+} fyprt_upscale_params;
+int fyprt_upscale_default_params(fyprt_upscale_params* out);
+/* Host memory, blocking; scale*width x scale*height uint32 / float4; either output may be NULL.  `stats` may be NULL: kernel_ms_part[0] =
+ * the low-res stage (prepare through the last iteration), [1] = the hi-res primary kernel, [2] = the resolve kernel, launches = their number. */
+int fyprt_denoise_upscale(fyprt_context* ctx, const fyprt_upscale_params* params, uint32_t* rgba8, float* radiance4, fyprt_frame_stats* stats);
+/* Device memory of the context's GPU, asynchronous on the context stream, as fyprt_denoise_device. */
+int fyprt_denoise_upscale_device(fyprt_context* ctx, const fyprt_upscale_params* params, void* rgba8, void* radiance4);
 
 /* ================================================================================================= multi-GPU
  * The reference renders on one GPU (Renderer.cu:13-284); there is no reference interface for this section.  It splits ONE
