@@ -217,7 +217,14 @@ EXPORTED_SYMBOLS = [
     "fyprt_group_denoise_temporal", "fyprt_group_denoise_temporal_device", "fyprt_group_denoise_temporal_reset",
     "fyprt_group_denoise_temporal_plan",
     "fyprt_upscale_default_params", "fyprt_denoise_upscale", "fyprt_denoise_upscale_device",
+    "fyprt_selftest_functions",
 ]
+# enum fyprt_probe (fyprt_selftest_functions) and the 32-bit words of one input / output record of each probe
+(PROBE_SINCOS, PROBE_ACOS, PROBE_POW5, PROBE_RND, PROBE_OCT_ENCODE, PROBE_OCT_DECODE, PROBE_PACK_ABGR, PROBE_UNPACK_ABGR, PROBE_EVAL_BRDF,
+ PROBE_PDF_BRDF, PROBE_PDF_GGX, PROBE_SAMPLE_UNIFORM, PROBE_SAMPLE_COSINE, PROBE_SAMPLE_GGX, PROBE_SAMPLE_BRDF, PROBE_DI_UPDATE,
+ PROBE_SAMPLE_ALBEDO, PROBE_CLUSTER_IMPORTANCE, PROBE_CLUSTER_IMPORTANCE_GENERAL, PROBE_ASIN_KERNEL) = range(20)
+PROBE_IN_WORDS = (1, 1, 1, 1, 3, 2, 4, 1, 16, 16, 16, 16, 16, 16, 16, 4, 3, 23, 23, 2)
+PROBE_OUT_WORDS = (2, 1, 1, 2, 2, 3, 1, 4, 3, 1, 1, 5, 5, 5, 5, 7, 3, 1, 1, 2)
 GROUP_HISTORY_ROWS = 32   # FYPRT_GROUP_HISTORY_ROWS: the default history window of Group.denoise_temporal, rows either side of a band
 
 
@@ -306,6 +313,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.fyprt_comm_set_interleave.argtypes = [vp, u32]
     lib.fyprt_set_row_stripes.argtypes = [vp, u32, u32, u32]
     lib.fyprt_selftest_math.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(u32)]
+    if hasattr(lib, "fyprt_selftest_functions"):   # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
+        lib.fyprt_selftest_functions.argtypes = [vp, C.c_int, vp, u32, vp]
     lib.fyprt_group_render.argtypes = [vp, C.POINTER(Settings)]
     lib.fyprt_group_gather.argtypes = [vp, C.c_int]
     lib.fyprt_group_synchronize.argtypes = [vp]
@@ -441,6 +450,17 @@ class Context:
         n, f = (C.c_uint64 * 3)(), (C.c_uint32 * 3)()
         self._check(self.lib.fyprt_selftest_math(self.h, n, f))
         return list(n), list(f)
+
+    def selftest_functions(self, probe, records):
+        """Shading function `probe` (PROBE_*) on the device for every row of `records`, a (count, PROBE_IN_WORDS[probe]) array of
+        32-bit words (uint32 or float32; include/fyprt.h lists the layouts).  Returns the (count, PROBE_OUT_WORDS[probe]) uint32 result words."""
+        a = np.ascontiguousarray(records)
+        if not (0 <= probe < len(PROBE_IN_WORDS)):
+            self._check(self.lib.fyprt_selftest_functions(self.h, probe, None, 0, None))
+        assert a.dtype.itemsize == 4 and a.ndim == 2 and a.shape[1] == PROBE_IN_WORDS[probe], (a.dtype, a.shape)
+        out = np.zeros((a.shape[0], PROBE_OUT_WORDS[probe]), dtype=np.uint32)
+        self._check(self.lib.fyprt_selftest_functions(self.h, probe, _ptr(a) if len(a) else None, len(a), _ptr(out) if len(a) else None))
+        return out
 
     def set_row_stripes(self, stripe_rows, parts=1, part=0):
         """Interleaved split of the per-pixel techniques: this context renders stripes part, part + parts, ... (0 rows = off)."""

@@ -20,6 +20,7 @@
 #include "rt_denoise.h"
 #include "rt_temporal.h"
 #include "rt_upscale.h"
+#include "rt_probe.h"
 
 using namespace rt;
 
@@ -1684,6 +1685,32 @@ int fyprt_selftest_math(fyprt_context* c, uint64_t* mismatches3, uint32_t* first
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     HIPCHK(c, e);
     for (int w = 0; w < 3; ++w) { mismatches3[w] = hc[w]; if (first_bad3) first_bad3[w] = hf[w]; }
+    return FYPRT_OK;
+}
+
+// One shading function (`probe`, enum fyprt_probe) evaluated on `count` caller-supplied argument records by the inline functions the frame
+// kernels call (rt_probe.h); include/fyprt.h documents the records.  Touches no frame state: its buffers live for the call only.
+int fyprt_selftest_functions(fyprt_context* c, int probe, const void* in, uint32_t count, void* out) {
+    static_assert((int)P_COUNT == (int)FYPRT_PROBE_COUNT && (int)P_ASIN_KERNEL == (int)FYPRT_PROBE_ASIN_KERNEL, "enum fyprt_probe");
+    if (!c) return FYPRT_EINVAL;
+    if (probe < 0 || probe >= (int)P_COUNT) return c->fail(FYPRT_EINVAL, "fyprt_selftest_functions: unknown probe");
+    if (count && (!in || !out)) return c->fail(FYPRT_EINVAL, "fyprt_selftest_functions: NULL records with a non-zero count");
+    if (c->hostOnly) return c->fail(FYPRT_ESTATE, "fyprt_selftest_functions needs a device");
+    if (probe == (int)P_SAMPLE_ALBEDO && !c->haveScene) return c->fail(FYPRT_ESTATE, "fyprt_selftest_functions: the sample_albedo probe reads the uploaded scene's textures (before fyprt_upload_scene)");
+    if (count == 0) return FYPRT_OK;
+    HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c));
+    const uint32_t inWords = kProbeIn[probe], outWords = kProbeOut[probe];
+    DevBuf<uint32_t> din, dout;
+    HIPCHK(c, din.alloc((size_t)count * inWords)); HIPCHK(c, dout.alloc((size_t)count * outWords));
+    hipError_t e = hipMemcpyAsync(din.p, in, din.bytes(), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        const uint32_t blocks = std::min((count + (uint32_t)kBlock - 1u) / (uint32_t)kBlock, (uint32_t)c->numCUs * 16u);
+        hipLaunchKernelGGL(k_probe_functions, dim3(blocks), dim3(kBlock), 0, c->stream, probe, c->dsc, din.p, inWords, dout.p, outWords, count);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout.p, dout.bytes(), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);      // also after a failed enqueue: the buffers are freed on return
+    HIPCHK(c, e != hipSuccess ? e : es);
     return FYPRT_OK;
 }
 

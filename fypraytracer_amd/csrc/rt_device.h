@@ -439,7 +439,7 @@ RT_DEV f3 sample_albedo(const DevScene& sc, const Mat& m, float u, float v) {
         u = (u < 0.0f) ? 0.0f : (u > 1.0f ? 1.0f : u);
         v = (v < 0.0f) ? 0.0f : (v > 1.0f ? 1.0f : v);
         const float x = u * (float)(t.width - 1), y = v * (float)(t.height - 1);
-        const int x0 = (int)x, y0 = (int)y;
+        const int x0 = f2i_sat(x), y0 = f2i_sat(y);      // a NaN uv (a mesh with a NaN texture coordinate) indexes texel 0, not an undefined one (and shades black: NaN packs to 0)
         const int x1 = (x0 + 1 < (int)t.width) ? x0 + 1 : x0, y1 = (y0 + 1 < (int)t.height) ? y0 + 1 : y0;
         const float tx = x - (float)x0, ty = y - (float)y0;
         const f4 c00 = unpack_abgr(t.pixels[y0 * t.width + x0]), c10 = unpack_abgr(t.pixels[y0 * t.width + x1]);

@@ -228,7 +228,6 @@ RT_DEV float di_target(const DevScene& sc, uint32_t emissiveSlot, const Payload&
     const f3 Lr = (((brdf * cx) * cy) / sa) * mk3(l2.x, l2.y, l2.z);
     return length(Lr);
 }
-RT_DEV int f2i_sat(float f) { if (!(f == f)) return 0; if (f >= 2147483520.0f) return 2147483647; if (f <= -2147483648.0f) return (-2147483647 - 1); return (int)f; }
 // `row` = the reprojected pixel's row: a row band only holds history of the rows it rendered last frame (DevFrame::histBegin/End)
 RT_DEV uint32_t prev_pixel(const DevCamera& cam, f3 wp, uint32_t& row) {                    // Renderer.cu:1750-1763
     const f4 clip = mul(cam.prevProjView, mk4(wp.x, wp.y, wp.z, 1.0f));

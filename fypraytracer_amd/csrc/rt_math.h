@@ -77,6 +77,8 @@ RT_DEV f3 normalize(f3 a) { float inv = rsqrt_exact(dot(a, a)); return a * inv; 
 RT_DEV f3 reflect(f3 I, f3 N) { return I - N * dot(N, I) * 2.0f; }
 RT_DEV f3 mix(f3 a, f3 b, float t) { return a * (1.0f - t) + b * t; }
 RT_DEV bool finitef(float x) { return __builtin_fabsf(x) <= 3.402823466e+38f; }   // false for NaN / inf
+// float -> int with every argument defined: NaN -> 0, out of range -> the nearest int (C++ leaves both undefined)
+RT_DEV int f2i_sat(float f) { if (!(f == f)) return 0; if (f >= 2147483520.0f) return 2147483647; if (f <= -2147483648.0f) return (-2147483647 - 1); return (int)f; }
 
 RT_DEV f4 mk4(float x, float y, float z, float w) { f4 r; r.x = x; r.y = y; r.z = z; r.w = w; return r; }
 RT_DEV f4 operator+(f4 a, f4 b) { return mk4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }

@@ -418,6 +418,43 @@ int fyprt_compare_image(fyprt_context* ctx, const uint32_t* reference_rgba8, int
  * in the order sqrt, reciprocal, reciprocal square root; all zero on a sound build.  New (no reference counterpart). */
 int fyprt_selftest_math(fyprt_context* ctx, uint64_t* mismatches3, uint32_t* first_bad3 /* may be NULL */);
 
+/* Self-test of the arithmetic contract, function by function: shading function `probe` evaluated on the device for `count` argument
+ * records at `in`, one result record each to `out` (host memory both) — by the very inline functions the frame kernels call, so a test
+ * can compare each with the CPU oracle bit for bit at arguments no rendered picture reaches.  New (no reference counterpart).
+ * A record is an array of 32-bit words (f = binary32, u = uint32), tightly packed, record i at word i * words:
+ *   probe                          input words                                         output words
+ *   SINCOS                         1: x (f; valid for 0 <= x <= 2*pi + eps)            2: sin, cos
+ *   ACOS, POW5                     1: x (f)                                            1: result (f)
+ *   RND                            1: seed (u)                                         2: value (f), seed after (u)
+ *   OCT_ENCODE                     3: v (f)                                            2: e (f)
+ *   OCT_DECODE                     2: e (f)                                            3: v (f)
+ *   PACK_ABGR                      4: r g b a (f)                                      1: ABGR word (u)
+ *   UNPACK_ABGR                    1: ABGR word (u)                                    4: r g b a (f)
+ *   EVAL_BRDF                      16: surface record (below)                          3: rgb (f)
+ *   PDF_BRDF, PDF_GGX              16: surface record                                  1: pdf (f)
+ *   SAMPLE_UNIFORM / _COSINE /     16: surface record (L unused)                       5: direction (3 f), pdf (f), seed after (u)
+ *     _GGX / _BRDF
+ *   DI_UPDATE                      4: candidate (u), w (f), pdf (f), seed (u)          7: the 20-byte reservoir after one update of an empty one
+ *                                                                                         (index u, W f, pdf f, weightSum f, M u), accepted (u), seed after (u)
+ *   SAMPLE_ALBEDO                  3: u (f), v (f), texture index (u)                  3: rgb (f); (-1, -1, -1) for an index past the scene's textures
+ *   CLUSTER_IMPORTANCE,            23: shading point (3 f), one fyprt_lighttree_node   1: importance (f)
+ *     CLUSTER_IMPORTANCE_GENERAL       (20 words)
+ *   ASIN_KERNEL                    2: z (one binary64, low word first; 0 <= z <= 0.25)  2: the polynomial under acos (one binary64)
+ * Surface record: N (3 f), V (3 f), L (3 f), albedo (3 f), metallic (f), roughness (f), seed (u), one unused word.
+ * SAMPLE_ALBEDO reads the textures of the uploaded scene (fyprt_upload_scene / fyprt_append_textures; FYPRT_ESTATE without a scene).
+ * CLUSTER_IMPORTANCE is the form the light-tree walk calls: it takes a shorter path when the boxes of all 64 records a wave holds
+ * (records 64k .. 64k+63) have no extent along one axis; CLUSTER_IMPORTANCE_GENERAL is the all-corners path whatever the boxes.
+ * FYPRT_EINVAL: unknown probe, NULL `in` / `out` with count > 0.  FYPRT_ESTATE: host-only context.  count == 0 launches nothing.
+ * Waits for the context's pending work first; touches no frame state. */
+enum fyprt_probe {
+    FYPRT_PROBE_SINCOS = 0, FYPRT_PROBE_ACOS = 1, FYPRT_PROBE_POW5 = 2, FYPRT_PROBE_RND = 3, FYPRT_PROBE_OCT_ENCODE = 4, FYPRT_PROBE_OCT_DECODE = 5,
+    FYPRT_PROBE_PACK_ABGR = 6, FYPRT_PROBE_UNPACK_ABGR = 7, FYPRT_PROBE_EVAL_BRDF = 8, FYPRT_PROBE_PDF_BRDF = 9, FYPRT_PROBE_PDF_GGX = 10,
+    FYPRT_PROBE_SAMPLE_UNIFORM = 11, FYPRT_PROBE_SAMPLE_COSINE = 12, FYPRT_PROBE_SAMPLE_GGX = 13, FYPRT_PROBE_SAMPLE_BRDF = 14,
+    FYPRT_PROBE_DI_UPDATE = 15, FYPRT_PROBE_SAMPLE_ALBEDO = 16, FYPRT_PROBE_CLUSTER_IMPORTANCE = 17, FYPRT_PROBE_CLUSTER_IMPORTANCE_GENERAL = 18,
+    FYPRT_PROBE_ASIN_KERNEL = 19, FYPRT_PROBE_COUNT = 20
+};
+int fyprt_selftest_functions(fyprt_context* ctx, int probe, const void* in, uint32_t count, void* out);
+
 /* ================================================================================================= batched ray queries
  * New (no reference counterpart): the caller's rays traced against the uploaded scene by the frames' traversal core, outside any frame —
  * picking (the mesh under a viewport pixel), visibility probes, bakes, and timing traversal on a fixed ray set ("Batched ray queries").

@@ -231,5 +231,64 @@ void orc_di_reset_update(uint32_t cand, float w, float pdf, uint32_t* seed, void
     DIReservoir r; DI_Reset(r); *accepted = DI_Update(r, cand, w, 1, pdf, *seed) ? 1 : 0; std::memcpy(out20, &r, 20);
 }
 uint32_t orc_sample_bilinear(const uint32_t* pixels, uint32_t w, uint32_t hh, float u, float v) { return SampleBilinear(Texture{pixels, w, hh}, u, v); }
+void orc_unpack_abgr(uint32_t p, float* c4) { vec4 c = UnpackABGR(p); c4[0] = c.x; c4[1] = c.y; c4[2] = c.z; c4[3] = c.w; }
+float orc_pdf_ggx(const float* N, const float* V, const float* L, float roughness) {
+    return GGXHemispherePDF(v3(N[0], N[1], N[2]), v3(V[0], V[1], V[2]), v3(L[0], L[1], L[2]), roughness);
+}
+float orc_pdf_brdf(const float* N, const float* V, const float* L, const float* albedo, float metallic, float roughness) {
+    return BRDFHemispherePDF(v3(N[0], N[1], N[2]), v3(V[0], V[1], V[2]), v3(L[0], L[1], L[2]), v3(albedo[0], albedo[1], albedo[2]), metallic, roughness);
+}
+// LightTreeNode importance (LightTree.cuh:91-117) of one cluster, given in the exported node format, seen from `sp3`
+float orc_cluster_importance(const float* sp3, const orc_lt_node* n) {
+    LTNode c; c.energy = n->energy;
+    c.bounds_o.axis = v3(n->cone_axis[0], n->cone_axis[1], n->cone_axis[2]); c.bounds_o.theta_o = n->theta_o; c.bounds_o.theta_e = n->theta_e;
+    c.bounds_w.lo = v3(n->box_lo[0], n->box_lo[1], n->box_lo[2]); c.bounds_w.hi = v3(n->box_hi[0], n->box_hi[1], n->box_hi[2]);
+    c.bounds_w.centroid = v3(n->box_centroid[0], n->box_centroid[1], n->box_centroid[2]);
+    return ClusterImportance(ShadingPoint{v3(sp3[0], sp3[1], sp3[2]), v3(0.0f)}, c);
+}
+
+// the binary64 polynomial under t_acos, (asin(sqrt z) / sqrt z - 1) / z on [0, 0.25]: its coefficients' last bits do not show in binary32 results
+#ifdef ORC_USE_LIBM
+double orc_asin_kernel(double z) { const double s = sqrt(z); return z > 0.0 ? (asin(s) / s - 1.0) / z : 1.0 / 6.0; }
+#else
+double orc_asin_kernel(double z) { return t_asin_kernel(z); }
+#endif
+
+// ---- array form of the hooks above: `count` records of 32-bit words in the layouts of fyprt_selftest_functions (include/fyprt.h,
+// enum fyprt_probe), each record through the scalar hook.  One difference: SAMPLE_ALBEDO writes ONE word per record, SampleBilinear's
+// ABGR word (what the reference's function returns); the caller unpacks it.  Returns 0, or -1 for an unknown probe / a texture index
+// past `texture_count`.
+int orc_probe(int probe, const void* in, uint32_t count, void* out, const orc_texture* textures, uint32_t texture_count) {
+    static const uint32_t kIn[20] = {1, 1, 1, 1, 3, 2, 4, 1, 16, 16, 16, 16, 16, 16, 16, 4, 3, 23, 23, 2};
+    static const uint32_t kOut[20] = {2, 1, 1, 2, 2, 3, 1, 4, 3, 1, 1, 5, 5, 5, 5, 7, 1, 1, 1, 2};
+    if (probe < 0 || probe >= 20) return -1;
+    static_assert(sizeof(orc_lt_node) == 80, "layout");
+    const uint32_t nin = kIn[probe], nout = kOut[probe];
+    int bad = 0;
+#pragma omp parallel for schedule(static) reduction(| : bad)
+    for (int64_t i = 0; i < (int64_t)count; ++i) {
+        const uint32_t* w = (const uint32_t*)in + (size_t)i * nin; const float* f = (const float*)w;
+        uint32_t* o = (uint32_t*)out + (size_t)i * nout; float* g = (float*)o;
+        switch (probe) {
+            case 0: g[0] = orc_sin(f[0]); g[1] = orc_cos(f[0]); break;
+            case 1: g[0] = orc_acos(f[0]); break;
+            case 2: g[0] = orc_pow5(f[0]); break;
+            case 3: { uint32_t s = w[0]; g[0] = orc_random_float(&s); o[1] = s; break; }
+            case 4: orc_encode_oct(f, g); break;
+            case 5: orc_decode_oct(f, g); break;
+            case 6: o[0] = orc_convert_rgba(f); break;
+            case 7: orc_unpack_abgr(w[0], g); break;
+            case 8: orc_brdf(f, f + 3, f + 6, f + 9, f[12], f[13], g); break;
+            case 9: g[0] = orc_pdf_brdf(f, f + 3, f + 6, f + 9, f[12], f[13]); break;
+            case 10: g[0] = orc_pdf_ggx(f, f + 3, f + 6, f[13]); break;
+            case 11: case 12: case 13: case 14: { uint32_t s = w[14]; orc_sample(probe - 11, f, f + 3, f + 9, f[12], f[13], &s, g); o[4] = s; break; }
+            case 15: { uint32_t s = w[3]; int acc = 0; orc_di_reset_update(w[0], f[1], f[2], &s, o, &acc); o[5] = (uint32_t)acc; o[6] = s; break; }
+            case 16: if (w[2] < texture_count) o[0] = orc_sample_bilinear(textures[w[2]].pixels, textures[w[2]].width, textures[w[2]].height, f[0], f[1]); else bad |= 1; break;
+            case 19: { double z, r; std::memcpy(&z, w, 8); r = orc_asin_kernel(z); std::memcpy(o, &r, 8); break; }
+            default: g[0] = orc_cluster_importance(f, (const orc_lt_node*)(w + 3)); break;
+        }
+    }
+    return bad ? -1 : 0;
+}
 
 }  // extern "C"

@@ -509,8 +509,7 @@ struct Renderer {
         vec2 uvPrev = GetUVFromNDC(cam.prevProjection, cam.prevView, worldPos);
         vec2 viewport{(float)cam.width, (float)cam.height};
         vec2 sp = uvPrev * viewport;
-        auto toInt = [](float f) -> int { if (!(f == f)) return 0; if (f >= 2147483520.0f) return 2147483647; if (f <= -2147483648.0f) return (-2147483647 - 1); return (int)f; };
-        int px = iclamp(toInt(floorf(sp.x)), 0, (int)cam.width - 1), py = iclamp(toInt(floorf(sp.y)), 0, (int)cam.height - 1);
+        int px = iclamp(f2i_sat(floorf(sp.x)), 0, (int)cam.width - 1), py = iclamp(f2i_sat(floorf(sp.y)), 0, (int)cam.height - 1);
         row = (uint32_t)py;
         return (uint32_t)py * cam.width + (uint32_t)px;
     }

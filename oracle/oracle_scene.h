@@ -57,11 +57,12 @@ static inline vec3 TriNormal(vec3 n0, vec3 n1, vec3 n2) { return normalize((n0 +
 static inline float TriArea(vec3 p0, vec3 p1, vec3 p2) { return 0.5f * length(cross(p1 - p0, p2 - p0)); }
 
 // ---- Texture::SampleBilinear (Texture.cu:103-139)
+static inline int f2i_sat(float f) { if (!(f == f)) return 0; if (f >= 2147483520.0f) return 2147483647; if (f <= -2147483648.0f) return (-2147483647 - 1); return (int)f; }
 static inline uint32_t SampleBilinear(const Texture& t, float u, float v) {
     u = (u < 0.0f) ? 0.0f : (u > 1.0f ? 1.0f : u);
     v = (v < 0.0f) ? 0.0f : (v > 1.0f ? 1.0f : v);
     float x = u * (float)(t.width - 1), y = v * (float)(t.height - 1);
-    int x0 = (int)x, y0 = (int)y;
+    int x0 = f2i_sat(x), y0 = f2i_sat(y);        // NaN uv -> texel index 0 (the reference's (int)NaN is undefined: INT_MIN on x86, far outside the texture)
     int x1 = (x0 + 1 < (int)t.width) ? x0 + 1 : x0, y1 = (y0 + 1 < (int)t.height) ? y0 + 1 : y0;
     float tx = x - (float)x0, ty = y - (float)y0;
     vec4 c00 = UnpackABGR(t.pixels[y0 * t.width + x0]), c10 = UnpackABGR(t.pixels[y0 * t.width + x1]);

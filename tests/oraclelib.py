@@ -69,6 +69,17 @@ def _load(name):
     lib.orc_di_reset_update.argtypes = [u32, C.c_float, C.c_float, C.POINTER(u32), vp, C.POINTER(C.c_int)]
     lib.orc_sample_bilinear.argtypes = [vp, u32, u32, C.c_float, C.c_float]
     lib.orc_sample_bilinear.restype = u32
+    lib.orc_unpack_abgr.argtypes = [u32, vp]
+    lib.orc_pdf_ggx.argtypes = [vp, vp, vp, C.c_float]
+    lib.orc_pdf_ggx.restype = C.c_float
+    lib.orc_pdf_brdf.argtypes = [vp, vp, vp, vp, C.c_float, C.c_float]
+    lib.orc_pdf_brdf.restype = C.c_float
+    lib.orc_cluster_importance.argtypes = [vp, vp]
+    lib.orc_cluster_importance.restype = C.c_float
+    lib.orc_asin_kernel.argtypes = [C.c_double]
+    lib.orc_asin_kernel.restype = C.c_double
+    lib.orc_probe.argtypes = [C.c_int, vp, u32, vp, vp, u32]
+    lib.orc_probe.restype = C.c_int
     return lib
 
 
@@ -80,6 +91,23 @@ def lib(libm=False):
     if name not in _libs:
         _libs[name] = _load(name)
     return _libs[name]
+
+
+def probe(which, records, textures=()):
+    """Array form of the per-function hooks: `records` as for capi.Context.selftest_functions (same layouts), `textures` the 2-D uint32
+    pixel arrays PROBE_SAMPLE_ALBEDO indexes.  Returns the result words; PROBE_SAMPLE_ALBEDO yields one ABGR word per record
+    (SampleBilinear's own result), every other probe the layout of the device call."""
+    a = np.ascontiguousarray(records)
+    assert a.dtype.itemsize == 4 and a.ndim == 2 and a.shape[1] == capi.PROBE_IN_WORDS[which], (a.dtype, a.shape)
+    nout = 1 if which == capi.PROBE_SAMPLE_ALBEDO else capi.PROBE_OUT_WORDS[which]
+    out = np.zeros((a.shape[0], nout), dtype=np.uint32)
+    px = [np.ascontiguousarray(t, dtype=np.uint32) for t in textures]
+    texs = (capi.Texture * max(1, len(px)))()
+    for i, t in enumerate(px):
+        texs[i].pixels, texs[i].height, texs[i].width = t.ctypes.data_as(C.c_void_p), t.shape[0], t.shape[1]
+    rc = lib().orc_probe(which, a.ctypes.data, len(a), out.ctypes.data, C.cast(texs, C.c_void_p), len(px))
+    assert rc == 0, f"orc_probe({which}) failed"
+    return out
 
 
 class Oracle:
