@@ -218,6 +218,7 @@ EXPORTED_SYMBOLS = [
     "fyprt_group_denoise_temporal_plan",
     "fyprt_upscale_default_params", "fyprt_denoise_upscale", "fyprt_denoise_upscale_device",
     "fyprt_selftest_functions",
+    "fyprt_group_denoise_upscale", "fyprt_group_denoise_upscale_device", "fyprt_group_denoise_upscale_plan",
 ]
 # enum fyprt_probe (fyprt_selftest_functions) and the 32-bit words of one input / output record of each probe
 (PROBE_SINCOS, PROBE_ACOS, PROBE_POW5, PROBE_RND, PROBE_OCT_ENCODE, PROBE_OCT_DECODE, PROBE_PACK_ABGR, PROBE_UNPACK_ABGR, PROBE_EVAL_BRDF,
@@ -341,6 +342,10 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
         lib.fyprt_group_denoise_temporal_device.argtypes = [vp, C.POINTER(TemporalParams), u32, C.c_int, vp, vp]
         lib.fyprt_group_denoise_temporal_reset.argtypes = [vp]
         lib.fyprt_group_denoise_temporal_plan.argtypes = [C.POINTER(u32), C.c_int, u32, u32, u32, C.POINTER(u32), C.c_int]
+    if hasattr(lib, "fyprt_group_denoise_upscale"):  # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
+        lib.fyprt_group_denoise_upscale.argtypes = [vp, C.POINTER(UpscaleParams), u32, vp, vp, vp]
+        lib.fyprt_group_denoise_upscale_device.argtypes = [vp, C.POINTER(UpscaleParams), u32, C.c_int, vp, vp]
+        lib.fyprt_group_denoise_upscale_plan.argtypes = [C.POINTER(u32), C.c_int, u32, u32, u32, u32, C.POINTER(u32), C.c_int]
     if hasattr(lib, "fyprt_append_meshes"):  # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
         lib.fyprt_append_meshes.argtypes = [vp, vp, u32, vp, u32, u32, vp, u32, vp, C.POINTER(u32)]
         lib.fyprt_append_textures.argtypes = [vp, C.POINTER(Texture), u32]
@@ -990,6 +995,54 @@ class Group:
                                                                  C.c_void_p(radiance_tensor.data_ptr()) if radiance_tensor is not None else None))
         cur.wait_stream(ext)                                           # torch's later work follows the collect
 
+    def denoise_upscale(self, params: UpscaleParams | None = None, history_rows=GROUP_HISTORY_ROWS, want_radiance=True, with_band_ms=False):
+        """Context.denoise_upscale for the frame the group rendered last (fyprt_group_denoise_upscale, blocking; defaults when `params` is
+        None): the low-res stage of denoise() or, with params.temporal, of denoise_temporal() with `history_rows` on the bands, then every
+        band traces and resolves its own hi-res rows.  Returns (image sH x sW uint32 ABGR8, radiance sH x sW x 4 float32 or None) of the
+        WHOLE frame, with `with_band_ms` also the per-band milliseconds.  Afterwards read_buffer(BUF_UPSCALE_GUIDE / BUF_UPSCALE_ALBEDO)
+        of a member gives its hi-res records, valid in the hi-res rows of its band."""
+        p = params if params is not None else UpscaleParams()
+        s = int(p.scale)
+        H, W = self.contexts[0].height * s, self.contexts[0].width * s
+        img = np.empty(max(W * H, 1), dtype=np.uint32)
+        rad = np.empty((max(W * H, 1), 4), dtype=np.float32) if want_radiance else None
+        ms = (C.c_float * len(self.contexts))()
+        self._check(self.lib.fyprt_group_denoise_upscale(self.h, C.byref(p), int(history_rows), _ptr(img), _ptr(rad), ms if with_band_ms else None))
+        for c in self.contexts:
+            c._upscale = s
+        out = (img.reshape(H, W), rad.reshape(H, W, 4) if want_radiance else None)
+        return out + (list(ms),) if with_band_ms else out
+
+    def denoise_upscale_tensor(self, image_tensor, radiance_tensor, params: UpscaleParams | None = None, history_rows=GROUP_HISTORY_ROWS, root=0):
+        """denoise_upscale into device tensors of the hi-res size on the GPU of context `root` (fyprt_group_denoise_upscale_device): int32
+        (sH, sW) / float32 (sH, sW, 4); stream ordering exactly as denoise_tensor."""
+        import torch
+        p = params if params is not None else UpscaleParams()
+        s = int(p.scale)
+        if not 0 <= root < len(self.contexts):
+            raise ValueError("denoise_upscale_tensor: root out of range")
+        ctx = self.contexts[root]
+        if image_tensor is None and radiance_tensor is None:
+            raise ValueError("denoise_upscale_tensor: at least one output tensor is needed")
+        for t, dt, shape, name in ((image_tensor, torch.int32, (ctx.height * s, ctx.width * s), "image_tensor"),
+                                   (radiance_tensor, torch.float32, (ctx.height * s, ctx.width * s, 4), "radiance_tensor")):
+            if t is None:
+                continue
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"denoise_upscale_tensor: {name} must be a contiguous {dt} tensor of shape {shape}")
+            if t.device.type != "cuda" or (t.device.index if t.device.index is not None else torch.cuda.current_device()) != ctx.device:
+                raise ValueError(f"denoise_upscale_tensor: {name} must be on cuda:{ctx.device}, the root context's GPU")
+        dev = (image_tensor if image_tensor is not None else radiance_tensor).device
+        cur = torch.cuda.current_stream(dev)
+        ext = torch.cuda.ExternalStream(ctx.stream(), device=dev)
+        ext.wait_stream(cur)                                           # the outputs are allocated (and their earlier uses done) before root writes them
+        self._check(self.lib.fyprt_group_denoise_upscale_device(self.h, C.byref(p), int(history_rows), root,
+                                                                C.c_void_p(image_tensor.data_ptr()) if image_tensor is not None else None,
+                                                                C.c_void_p(radiance_tensor.data_ptr()) if radiance_tensor is not None else None))
+        for c in self.contexts:
+            c._upscale = s
+        cur.wait_stream(ext)                                           # torch's later work follows the collect
+
     def denoise_temporal_reset(self):
         """Drops every member's temporal history (fyprt_group_denoise_temporal_reset): the next denoise_temporal* call is a first call."""
         self._check(self.lib.fyprt_group_denoise_temporal_reset(self.h))
@@ -1063,4 +1116,19 @@ def group_denoise_temporal_plan(row_bounds, height, iterations, history_rows=GRO
         raise FyprtError(f"fyprt_group_denoise_temporal_plan failed ({cnt})")
     out = (C.c_uint32 * (5 * max(cnt, 1)))()
     lib.fyprt_group_denoise_temporal_plan(_u32_array(row_bounds), n, height, iterations, history_rows, out, cnt)
+    return [tuple(out[5 * k: 5 * k + 5]) for k in range(cnt)]
+
+
+def group_denoise_upscale_plan(row_bounds, height, iterations, temporal=False, history_rows=GROUP_HISTORY_ROWS, lib=None):
+    """fyprt_group_denoise_upscale_plan: [(stage, receiver, owner, first row, end row), ...] of one Group.denoise_upscale call, in issue
+    order: the plan of the low-res stage (group_denoise_plan, or with `temporal` group_denoise_temporal_plan), then the stage that brings
+    every band but the last the colour row below it."""
+    lib = lib or load_library()
+    n = len(row_bounds) - 1
+    args = (_u32_array(row_bounds), n, height, iterations, 1 if temporal else 0, history_rows)
+    cnt = lib.fyprt_group_denoise_upscale_plan(*args, None, 0)
+    if cnt < 0:
+        raise FyprtError(f"fyprt_group_denoise_upscale_plan failed ({cnt})")
+    out = (C.c_uint32 * (5 * max(cnt, 1)))()
+    lib.fyprt_group_denoise_upscale_plan(*args, out, cnt)
     return [tuple(out[5 * k: 5 * k + 5]) for k in range(cnt)]

@@ -215,7 +215,8 @@ struct fyprt_context {
     void release_snapshot() { dtSnap.release(); dtMoved.release(); dtSnapPending = false; }
     void release_denoise() { dn = Denoise(); albedoValid = false; }
     // upscaler (fyprt_denoise_upscale*, rt_upscale.h): the hi-res guide records (2 quads per hi-res pixel) and albedo | pass-through colour
-    // (FYPRT_BUF_UPSCALE_GUIDE / _ALBEDO) and the host entry's hi-res output staging, allocated on the first call for its scale, reallocated
+    // (FYPRT_BUF_UPSCALE_GUIDE / _ALBEDO) and the host entry's hi-res output staging (for a group member, fyprt_group_denoise_upscale*: full-size
+    // records of which its band's hi-res rows are valid, and the staging of those rows), allocated on the first call for its scale, reallocated
     // when the scale changes, dropped by fyprt_resize; its timing events.  frameCam / frameSky: the camera and the sky colour the last
     // frame was enqueued with (taken where framePV is) — what the hi-res primary rays are formed and the misses coloured with
     struct Upscale { DevBuf<float4> guide, albedo, outRad; DevBuf<uint32_t> outImg; } up; Event upEv[4];
@@ -2365,15 +2366,19 @@ int fyprt_upscale_default_params(fyprt_upscale_params* out) {
     return fyprt_denoise_temporal_default_params(&out->filter);
 }
 
-static int check_upscale(fyprt_context* c, const fyprt_upscale_params* p, const void* rgba8, const void* radiance4, bool device) {
-    const char* who = device ? "fyprt_denoise_upscale_device" : "fyprt_denoise_upscale";
-    if (!c) return FYPRT_EINVAL;
+// The parameter cases of an upscale call in the header's order; fyprt_group_denoise_upscale* (fyprt_multi.h) shares them.
+static int check_upscale_params(fyprt_context* c, const char* who, const fyprt_upscale_params* p) {
     if (!p) return c->fail(FYPRT_EINVAL, std::string(who) + ": NULL params");
     if (p->scale < 2u || p->scale > 4u || p->temporal > 1u) return c->fail(FYPRT_EINVAL, std::string(who) + ": scale 2..4, temporal 0 / 1");
     if (p->temporal) TRY(check_temporal_params(c, who, &p->filter));
     if ((uint64_t)c->W * p->scale * ((uint64_t)c->H * p->scale) > (1ull << 31))
         return c->fail(FYPRT_EINVAL, std::string(who) + ": scale*width x scale*height is beyond what fyprt_resize accepts");
-    TRY(check_denoise_params(c, who, &p->filter.spatial));
+    return check_denoise_params(c, who, &p->filter.spatial);
+}
+static int check_upscale(fyprt_context* c, const fyprt_upscale_params* p, const void* rgba8, const void* radiance4, bool device) {
+    const char* who = device ? "fyprt_denoise_upscale_device" : "fyprt_denoise_upscale";
+    if (!c) return FYPRT_EINVAL;
+    TRY(check_upscale_params(c, who, p));
     TRY(check_denoise_outputs(c, who, rgba8, radiance4, device));
     TRY(check_denoise_frame(c, who));
     return check_denoise_rows(c, who);
@@ -2391,34 +2396,43 @@ static int ensure_up_buffers(fyprt_context* c, uint32_t s) {
     return FYPRT_OK;
 }
 
+// One launch each on the context stream, on the hi-res rows of `band` (the whole frame: {0, s H}).  k_up_primary: the frame's camera on
+// the hi-res viewport; the scene as a frame's primary rays read it (key 7's quorum, the tree's stack budget), no ray counters.
+static void launch_up_primary(fyprt_context* c, uint32_t s, DnBand band) {
+    DevCamera cam = c->frameCam; cam.W = c->W * s; cam.H = c->H * s;
+    const StackLds stack = stack_lds(c, 0u);
+    DevScene sc = secondary_scene(c->dsc, (uint32_t)c->tuning[K_QUORUM_PRIMARY], nullptr);
+    sc.stackBudget = stack.budget; sc.topCount = 0u;
+    const uint32_t order = (uint32_t)c->tuning[K_TILE_ORDER];
+    hipLaunchKernelGGL(k_up_primary, dim3(up_primary_grid(cam.W, band.rowEnd - band.rowBegin, order)), dim3(kBlock), stack.bytes, c->stream, sc, cam, order, c->frameSky,
+                       band, c->up.guide.p, c->up.albedo.p);
+}
+// k_up_resolve: e = the low-res colour buffer after the last iteration; rgba8 / radiance4 = where row 0 of the hi-res outputs is (or would be)
+static void launch_up_resolve(fyprt_context* c, const fyprt_denoise_params& sp, uint32_t s, const float4* e, uint32_t* rgba8, float4* radiance4, DnBand band) {
+    const UpFrame fr{c->W, c->H, (float)c->lastFrameIndex, sp.demodulate_albedo, sp.sigma_plane, sp.normal_power_log2, c->accum.p, c->dn.guide.p,
+                     c->dn.albedo.p, e, c->up.guide.p, c->up.albedo.p, rgba8, radiance4};
+    const dim3 rgrid(up_resolve_grid(c->W * s, band.rowEnd - band.rowBegin));
+    switch (s) {
+        case 2: hipLaunchKernelGGL(k_up_resolve<2>, rgrid, dim3(256), 0, c->stream, fr, band); break;
+        case 3: hipLaunchKernelGGL(k_up_resolve<3>, rgrid, dim3(256), 0, c->stream, fr, band); break;
+        default: hipLaunchKernelGGL(k_up_resolve<4>, rgrid, dim3(256), 0, c->stream, fr, band); break;
+    }
+}
+
 // Enqueues the low-res stage, k_up_primary and k_up_resolve on the context stream (after ensure_up_buffers).  ev: 4 timing events or null.
 static int enqueue_upscale(fyprt_context* c, const fyprt_upscale_params* p, uint32_t* rgba8, float4* radiance4, const Event* ev, int* launched) {
-    const uint32_t s = p->scale, upW = c->W * s, upH = c->H * s;
+    const uint32_t s = p->scale;
     const fyprt_denoise_params& sp = p->filter.spatial;
+    const DnBand all{0u, c->H * s};
     if (ev) HIPCHK(c, hipEventRecord(ev[0], c->stream));
     const float4* e = nullptr;
     if (p->temporal) TRY(enqueue_temporal(c, &p->filter, nullptr, nullptr, nullptr, launched, &e));
     else TRY(enqueue_denoise(c, &sp, nullptr, nullptr, nullptr, launched, &e));
     if (ev) HIPCHK(c, hipEventRecord(ev[1], c->stream));
-    {   // the frame's camera on the hi-res viewport; the scene as a frame's primary rays read it (key 7's quorum, the tree's stack budget), no ray counters
-        DevCamera cam = c->frameCam; cam.W = upW; cam.H = upH;
-        const StackLds stack = stack_lds(c, 0u);
-        DevScene sc = secondary_scene(c->dsc, (uint32_t)c->tuning[K_QUORUM_PRIMARY], nullptr);
-        sc.stackBudget = stack.budget; sc.topCount = 0u;
-        const uint32_t tilesX = (upW + 15u) / 16u, tilesY = (upH + 15u) / 16u;      // (tile_grid at the hi-res size)
-        const dim3 grid(c->tuning[K_TILE_ORDER] == 2 ? tilesX * ((tilesY + 7u) / 8u) * 8u : ((tilesX * tilesY + 7u) / 8u) * 8u);
-        hipLaunchKernelGGL(k_up_primary, grid, dim3(kBlock), stack.bytes, c->stream, sc, cam, (uint32_t)c->tuning[K_TILE_ORDER], c->frameSky, c->up.guide.p, c->up.albedo.p);
-        ++*launched;
-    }
+    launch_up_primary(c, s, all);
+    ++*launched;
     if (ev) HIPCHK(c, hipEventRecord(ev[2], c->stream));
-    const UpFrame fr{c->W, c->H, (float)c->lastFrameIndex, sp.demodulate_albedo, sp.sigma_plane, sp.normal_power_log2, c->accum.p, c->dn.guide.p,
-                     c->dn.albedo.p, e, c->up.guide.p, c->up.albedo.p, rgba8, radiance4};
-    const dim3 rgrid(up_resolve_grid(upW, upH));
-    switch (s) {
-        case 2: hipLaunchKernelGGL(k_up_resolve<2>, rgrid, dim3(256), 0, c->stream, fr); break;
-        case 3: hipLaunchKernelGGL(k_up_resolve<3>, rgrid, dim3(256), 0, c->stream, fr); break;
-        default: hipLaunchKernelGGL(k_up_resolve<4>, rgrid, dim3(256), 0, c->stream, fr); break;
-    }
+    launch_up_resolve(c, sp, s, e, rgba8, radiance4, all);
     ++*launched;
     HIPCHK(c, hipGetLastError());
     if (ev) HIPCHK(c, hipEventRecord(ev[3], c->stream));

@@ -81,6 +81,17 @@ std::vector<DnXfer> group_temporal_plan(const std::vector<uint32_t>& bounds, uin
         for (const HaloXfer& x : halo_plan(bounds, 2u << k, H, false)) plan.push_back({3 + (int)k, x});
     return plan;
 }
+// fyprt_group_denoise_upscale: the plan of its low-res stage, then one more stage, numbered after the last iteration's: every band but the
+// last pulls the one low-res row below it, e_k, from its owner — the colour buffer that holds e after the last iteration (16 B per pixel).
+// The resolve of the last s - 1 hi-res rows of a band taps that row.  Its guide record needs no entry: stage 0 already brings at least one
+// guide row below the band (2^iterations >= 1 rows, temporal max(2, ...)) — except that the spatial plan has no stage 0 at all without an
+// iteration, and the call then moves the guide record of the row with its colour (48 B per pixel; group_upscale_steps).
+std::vector<DnXfer> group_upscale_plan(const std::vector<uint32_t>& bounds, uint32_t H, uint32_t iterations, bool temporal, uint32_t historyRows) {
+    std::vector<DnXfer> plan = temporal ? group_temporal_plan(bounds, H, iterations, historyRows) : group_denoise_plan(bounds, H, iterations);
+    const int n = (int)bounds.size() - 1, stage = (temporal ? 3 : 1) + (int)iterations;
+    for (int k = 0; k + 1 < n; ++k) plan.push_back({stage, HaloXfer{k, k + 1, bounds[k + 1], bounds[k + 1] + 1u}});      // (no band is empty: row e_k is band k + 1's first)
+    return plan;
+}
 // a plan as the _plan entries hand it out: (stage, receiver, owner, first row, end row) per entry; returns the number of entries
 int export_plan(const std::vector<DnXfer>& plan, uint32_t* out5, int capacity) {
     for (int k = 0; k < (int)plan.size() && k < capacity && out5; ++k) {
@@ -483,6 +494,18 @@ static int group_denoise_check(fyprt_group* g, const fyprt_denoise_params* p, in
 //                      while neighbours still pull from this band: the first-work wait above; the kernel that writes the staging rows
 //                      waits for the earlier root's `collect`, which may still read them; and the front stream waits for the band's last
 //                      kernel before the next pipelined frame's Part 1 overwrites the payload (dn_call_done).
+// The upscale call (fyprt_group_denoise_upscale*) runs on the same engine with an output scale s: the output rows of band [b, e) are the
+// hi-res rows [s b, s e) at width s W, in the members' upscale staging (up.outImg / up.outRad) instead of the denoiser's — sizes, bias,
+// collect and the blocking wrapper's staging all follow `scale`; with 1 everything is as above.  What its last stage adds:
+//   read after write   the pull of row e reads the owner's colour buffer after its last iteration: the owner's `done`, which that iteration
+//                      recorded — without an iteration the `done` of prepare (spatial: e0) or of the reprojection (temporal: the
+//                      integrated colour).  k_up_primary records none and nothing pulls what it writes;
+//   write after read   the next call's first kernel (prepare) may overwrite that buffer while a neighbour still pulls the row: the
+//                      first-work wait on every other band's last `pulled`, which is now the one recorded after this stage.  Within the
+//                      call nothing writes a colour buffer after the last iteration;
+//   the staging        the resolve writes the band's hi-res staging rows, which the earlier root's `collect` may still read: the
+//                      writesOutput wait, as for the low-res staging.  A staging or hi-res buffer reallocated for another scale is first
+//                      waited for on the host (group_ensure_up_buffers).
 struct BandStep {
     int pulls;                                                        // the plan stage every band pulls before the launch, or -1,
     std::function<std::vector<XBuf>(fyprt_context*)> moved;           // and the buffers it moves: the receiver's and, in the same order, the owner's
@@ -493,9 +516,9 @@ struct BandStep {
 };
 // The first step must not pull: the first-work wait goes with its launch (both denoisers start with prepare).
 static int group_filter_enqueue(fyprt_group* g, const std::vector<DnXfer>& plan, const std::vector<BandStep>& steps, uint32_t demodulate, int root,
-                                uint32_t* rgba8, float4* radiance4, bool timed) {
+                                uint32_t* rgba8, float4* radiance4, bool timed, uint32_t scale = 1u) {
     const int n = (int)g->ctx.size();
-    const uint32_t W = g->ctx[0]->W;
+    const uint32_t W = g->ctx[0]->W, outW = W * scale;
     std::vector<char> pullsFrom((size_t)n * n, 0);                // [owner * n + receiver]
     for (const DnXfer& t : plan) pullsFrom[(size_t)t.x.owner * n + t.x.receiver] = 1;
     std::vector<DnFrame> frames(n); std::vector<DnBand> bands(n);
@@ -513,14 +536,16 @@ static int group_filter_enqueue(fyprt_group* g, const std::vector<DnXfer>& plan,
         if (i == root) continue;
         // the band's output rows go to its staging (at least the band's size), biased to row 0.  A buffer the earlier root may still read
         // is not freed under it.
-        const size_t need = (size_t)rows * W;
-        if ((rgba8 && c->dn.outImg.n < need) || (radiance4 && c->dn.outRad.n < need)) {
+        DevBuf<uint32_t>& outImg = scale > 1u ? c->up.outImg : c->dn.outImg;
+        DevBuf<float4>& outRad = scale > 1u ? c->up.outRad : c->dn.outRad;
+        const size_t need = (size_t)rows * scale * outW, bias = (size_t)b * scale * outW;
+        if ((rgba8 && outImg.n < need) || (radiance4 && outRad.n < need)) {
             if (g->dnRoot >= 0) HIPCHK(c, hipEventSynchronize(g->dn[g->dnRoot].collect));
-            if (rgba8 && c->dn.outImg.n < need) HIPCHK(c, c->dn.outImg.alloc(need));
-            if (radiance4 && c->dn.outRad.n < need) HIPCHK(c, c->dn.outRad.alloc(need));
+            if (rgba8 && outImg.n < need) HIPCHK(c, outImg.alloc(need));
+            if (radiance4 && outRad.n < need) HIPCHK(c, outRad.alloc(need));
         }
-        if (rgba8) fr.rgba8 = reinterpret_cast<uint32_t*>(reinterpret_cast<uintptr_t>(c->dn.outImg.p) - (size_t)b * W * sizeof(uint32_t));
-        if (radiance4) fr.radiance4 = reinterpret_cast<float4*>(reinterpret_cast<uintptr_t>(c->dn.outRad.p) - (size_t)b * W * sizeof(float4));
+        if (rgba8) fr.rgba8 = reinterpret_cast<uint32_t*>(reinterpret_cast<uintptr_t>(outImg.p) - bias * sizeof(uint32_t));
+        if (radiance4) fr.radiance4 = reinterpret_cast<float4*>(reinterpret_cast<uintptr_t>(outRad.p) - bias * sizeof(float4));
     }
     std::vector<std::vector<XBuf>> moved(n);
     for (const BandStep& st : steps) {
@@ -572,8 +597,9 @@ static int group_filter_enqueue(fyprt_group* g, const std::vector<DnXfer>& plan,
     for (int i = 0; i < n; ++i) {
         if (i == root) continue;
         HIPCHK(r, hipStreamWaitEvent(r->stream, g->dn[i].done, 0));
-        if (rgba8) HIPCHK(r, copy_rows(r, rgba8, g->ctx[i], frames[i].rgba8, bands[i].rowBegin, bands[i].rowEnd, W, sizeof(uint32_t), r->stream));
-        if (radiance4) HIPCHK(r, copy_rows(r, radiance4, g->ctx[i], frames[i].radiance4, bands[i].rowBegin, bands[i].rowEnd, W, sizeof(float4), r->stream));
+        const uint32_t r0 = bands[i].rowBegin * scale, r1 = bands[i].rowEnd * scale;
+        if (rgba8) HIPCHK(r, copy_rows(r, rgba8, g->ctx[i], frames[i].rgba8, r0, r1, outW, sizeof(uint32_t), r->stream));
+        if (radiance4) HIPCHK(r, copy_rows(r, radiance4, g->ctx[i], frames[i].radiance4, r0, r1, outW, sizeof(float4), r->stream));
     }
     HIPCHK(r, hipEventRecord(g->dn[root].collect, r->stream));
     g->dnCalled = true; g->dnRoot = root;
@@ -590,18 +616,23 @@ static BandStep finish_band_step(int col) {
 }
 // The blocking form of either group call, as denoise_blocking is of a context's: the group synchronised (the last frame is complete on
 // every stream), the outputs staged at full size on member 0, `enqueue(rgba8, radiance4)` with member 0 as root and timed, copied back;
-// band_ms from every member's timing events.
-static int group_denoise_blocking(fyprt_group* g, uint32_t* rgba8, float* radiance4, float* band_ms, const std::function<int(uint32_t*, float4*)>& enqueue) {
+// band_ms from every member's timing events.  scale > 1 (the upscale call): scale*W x scale*H pixels through member 0's upscale staging,
+// after `prepare` — the hi-res buffers of the members, which a change of scale drops together with that staging.
+static int group_denoise_blocking(fyprt_group* g, uint32_t* rgba8, float* radiance4, float* band_ms, const std::function<int(uint32_t*, float4*)>& enqueue,
+                                  uint32_t scale = 1u, const std::function<int()>& prepare = nullptr) {
     TRY(fyprt_group_synchronize(g));
+    if (prepare) TRY(prepare());
     fyprt_context* r = g->ctx[0];
     HIPCHK(r, hipSetDevice(r->device));
-    const size_t npx = (size_t)r->W * r->H;
-    if (rgba8 && r->dn.outImg.n != npx) HIPCHK(r, r->dn.outImg.alloc(npx));
-    if (radiance4 && r->dn.outRad.n != npx) HIPCHK(r, r->dn.outRad.alloc(npx));
-    TRY(enqueue(rgba8 ? r->dn.outImg.p : nullptr, radiance4 ? r->dn.outRad.p : nullptr));
+    DevBuf<uint32_t>& outImg = scale > 1u ? r->up.outImg : r->dn.outImg;
+    DevBuf<float4>& outRad = scale > 1u ? r->up.outRad : r->dn.outRad;
+    const size_t npx = (size_t)r->W * scale * ((size_t)r->H * scale);
+    if (rgba8 && outImg.n != npx) HIPCHK(r, outImg.alloc(npx));
+    if (radiance4 && outRad.n != npx) HIPCHK(r, outRad.alloc(npx));
+    TRY(enqueue(rgba8 ? outImg.p : nullptr, radiance4 ? outRad.p : nullptr));
     HIPCHK(r, hipSetDevice(r->device));
-    if (rgba8) HIPCHK(r, hipMemcpyAsync(rgba8, r->dn.outImg.p, npx * 4, hipMemcpyDeviceToHost, r->stream));
-    if (radiance4) HIPCHK(r, hipMemcpyAsync(radiance4, r->dn.outRad.p, npx * 16, hipMemcpyDeviceToHost, r->stream));
+    if (rgba8) HIPCHK(r, hipMemcpyAsync(rgba8, outImg.p, npx * 4, hipMemcpyDeviceToHost, r->stream));
+    if (radiance4) HIPCHK(r, hipMemcpyAsync(radiance4, outRad.p, npx * 16, hipMemcpyDeviceToHost, r->stream));
     HIPCHK(r, hipStreamSynchronize(r->stream));
     for (size_t i = 0; i < g->ctx.size(); ++i) {
         fyprt_context* c = g->ctx[i];
@@ -612,14 +643,46 @@ static int group_denoise_blocking(fyprt_group* g, uint32_t* rgba8, float* radian
     return FYPRT_OK;
 }
 
+// What the upscale call (scale s > 1) makes of a list of low-res steps in "keep" form (the last iteration as every other one, no finish
+// step: the colour e stays in dn.col[col]):
+//   k_up_primary on the band's hi-res rows after the last iteration.  It reads the scene and the frame's camera only, so it may stand
+//   anywhere before the resolve; there it runs while the neighbour below finishes its last iteration, whose `done` the pull after it
+//   waits for — the one wait of the call that nothing else of the band's own could fill.  Directly after prepare (FYPRT_UP_PRIMARY_EARLY)
+//   it was slower with 2, 4 and 8 bands sharing one GPU (profiles/upscale/group_upscale_rate.jsonl).  A launch-only step: it pulls
+//   nothing and records no `done`, because nothing pulls from it;
+//   then the pull of the plan's last stage `stage` — row e of dn.col[col], and its guide record where the plan has no stage 0
+//   (`withGuide`) — and k_up_resolve on the band's hi-res rows, which writes the output rows and records `done` for the collect.
+#ifndef FYPRT_UP_PRIMARY_EARLY
+#define FYPRT_UP_PRIMARY_EARLY 0     // 1: k_up_primary directly after prepare instead (the placement it was timed against)
+#endif
+static void group_upscale_steps(std::vector<BandStep>& steps, const fyprt_denoise_params& sp, uint32_t s, int stage, int col, bool withGuide) {
+    steps.insert(FYPRT_UP_PRIMARY_EARLY ? steps.begin() + 1 : steps.end(), BandStep{-1, nullptr, false, false, [s](fyprt_context* c, const DnFrame&, DnBand band) {
+        launch_up_primary(c, s, DnBand{band.rowBegin * s, band.rowEnd * s});
+    }, false});
+    steps.push_back({stage, [col, withGuide](fyprt_context* c) {
+        std::vector<XBuf> v{{c->dn.col[col].p, kDnColourBytes}};
+        if (withGuide) v.push_back({c->dn.guide.p, kDnGuideBytes});
+        return v;
+    }, false, true, [sp, s, col](fyprt_context* c, const DnFrame& fr, DnBand band) {
+        launch_up_resolve(c, sp, s, c->dn.col[col].p, fr.rgba8, fr.radiance4, DnBand{band.rowBegin * s, band.rowEnd * s});
+    }, true});
+}
+
 // The spatial call (group_denoise_plan): prepare; the guides; per iteration k the colour halo it reads (stage 1 + k: dn.col[k & 1]) and
 // the iteration dn.col[k & 1] -> dn.col[(k + 1) & 1].  Iteration 0 waits for no puller: it writes dn.col[1], which nothing pulled yet.
-static int group_spatial_call(fyprt_group* g, const fyprt_denoise_params* p, int root, uint32_t* rgba8, float4* radiance4, bool timed) {
+// scale > 1: the low-res stage of fyprt_group_denoise_upscale* (group_upscale_plan, group_upscale_steps), e in dn.col[iterations & 1].
+static int group_spatial_call(fyprt_group* g, const fyprt_denoise_params* p, int root, uint32_t* rgba8, float4* radiance4, bool timed, uint32_t scale = 1u) {
     std::vector<BandStep> steps = first_band_steps();
+    const bool keep = scale > 1u;
     for (uint32_t k = 0; k < p->iterations; ++k) {
-        const DnIter it = make_dn_iter(*p, k, true);
+        DnIter it = make_dn_iter(*p, k, true);
+        if (keep) it.last = 0u;
         steps.push_back({1 + (int)k, [k](fyprt_context* c) { return std::vector<XBuf>{{c->dn.col[k & 1u].p, kDnColourBytes}}; }, k > 0, it.last != 0,
                          [k, it](fyprt_context* c, const DnFrame& fr, DnBand band) { launch_dn_iterate(c, fr, it, band, c->dn.col[k & 1u].p, c->dn.col[(k + 1u) & 1u].p); }, true});
+    }
+    if (keep) {
+        group_upscale_steps(steps, *p, scale, 1 + (int)p->iterations, (int)(p->iterations & 1u), p->iterations == 0);
+        return group_filter_enqueue(g, group_upscale_plan(g->bounds, g->ctx[0]->H, p->iterations, false, 0u), steps, p->demodulate_albedo, root, rgba8, radiance4, timed, scale);
     }
     if (p->iterations == 0) steps.push_back(finish_band_step(0));
     return group_filter_enqueue(g, group_denoise_plan(g->bounds, g->ctx[0]->H, p->iterations), steps, p->demodulate_albedo, root, rgba8, radiance4, timed);
@@ -647,13 +710,9 @@ int fyprt_group_denoise_plan(const uint32_t* row_bounds, int n, uint32_t height,
 // the rows' owners into the same place of this context's full-size buffers (group_temporal_plan).  Every member keeps the history of
 // its own rows in its own ping-pong pair; dt.hist[dtCur] of a member also holds the window rows the last call pulled, which nothing
 // reads again.
-static int group_temporal_check(fyprt_group* g, const fyprt_temporal_params* p, int root, const void* rgba8, const void* radiance4, bool device) {
-    const char* who = device ? "fyprt_group_denoise_temporal_device" : "fyprt_group_denoise_temporal";
-    if (!g) return FYPRT_EINVAL;
+// the state cases a temporal call adds to group_denoise_check_call's (fyprt_group_denoise_upscale* with temporal = 1 shares them)
+static int group_temporal_check_state(fyprt_group* g, const char* who) {
     fyprt_context* c0 = g->ctx[0];
-    TRY(check_temporal_params(c0, who, p));
-    TRY(check_denoise_params(c0, who, &p->spatial));
-    TRY(group_denoise_check_call(g, who, root, rgba8, radiance4, device));
     for (fyprt_context* c : g->ctx)
         if (std::memcmp(c->framePV, c0->framePV, 64) != 0) return c->fail(FYPRT_ESTATE, std::string(who) + ": the members' last frames differ in camera matrix");
     const bool history = group_has_history(g);
@@ -661,6 +720,15 @@ static int group_temporal_check(fyprt_group* g, const fyprt_temporal_params* p, 
         if (c->dtMotion != c0->dtMotion || (history && c->dtSnapPending != c0->dtSnapPending))
             return c->fail(FYPRT_ESTATE, std::string(who) + ": the members differ in motion mode (fyprt_denoise_temporal_set_motion) or in having a geometry edit pending");
     return FYPRT_OK;
+}
+static int group_temporal_check(fyprt_group* g, const fyprt_temporal_params* p, int root, const void* rgba8, const void* radiance4, bool device) {
+    const char* who = device ? "fyprt_group_denoise_temporal_device" : "fyprt_group_denoise_temporal";
+    if (!g) return FYPRT_EINVAL;
+    fyprt_context* c0 = g->ctx[0];
+    TRY(check_temporal_params(c0, who, p));
+    TRY(check_denoise_params(c0, who, &p->spatial));
+    TRY(group_denoise_check_call(g, who, root, rgba8, radiance4, device));
+    return group_temporal_check_state(g, who);
 }
 
 // The temporal call (group_temporal_plan, without stage 2 while the group holds no history): prepare; the guides; the prepared colour
@@ -670,13 +738,16 @@ static int group_temporal_check(fyprt_group* g, const fyprt_temporal_params* p, 
 // dt.var[0] -> [1] -> [0] ..., iteration 0 feeding dt.hist[dtCur ^ 1] back.  Every iteration waits for its pullers: iteration 0
 // overwrites the prepared colour of stage 1.  The members' bookkeeping (dtCur, dtValid, dtGroup, dtPV, dtSnapPending) advances only
 // once everything is enqueued.
-static int group_temporal_call(fyprt_group* g, const fyprt_temporal_params* p, uint32_t historyRows, int root, uint32_t* rgba8, float4* radiance4, bool timed) {
+// scale > 1: the low-res stage of fyprt_group_denoise_upscale* (group_upscale_plan, group_upscale_steps), e in dn.col[(iterations + 1) & 1].
+static int group_temporal_call(fyprt_group* g, const fyprt_temporal_params* p, uint32_t historyRows, int root, uint32_t* rgba8, float4* radiance4, bool timed,
+                               uint32_t scale = 1u) {
     const fyprt_denoise_params& sp = p->spatial;
     const uint32_t H = g->ctx[0]->H, R = std::min(historyRows, H);
     for (fyprt_context* c : g->ctx) { HIPCHK(c, hipSetDevice(c->device)); TRY(ensure_dt_buffers(c)); }      // (may drop the history)
-    const bool history = group_has_history(g);
+    const bool history = group_has_history(g), keep = scale > 1u;
     std::vector<DnXfer> plan;
-    for (const DnXfer& t : group_temporal_plan(g->bounds, H, sp.iterations, R)) if (t.stage != 2 || history) plan.push_back(t);
+    for (const DnXfer& t : keep ? group_upscale_plan(g->bounds, H, sp.iterations, true, R) : group_temporal_plan(g->bounds, H, sp.iterations, R))
+        if (t.stage != 2 || history) plan.push_back(t);
     std::vector<BandStep> steps = first_band_steps();
     steps.push_back({1, [](fyprt_context* c) { return std::vector<XBuf>{{c->dn.col[0].p, kDnColourBytes}}; }, false, false, nullptr, false});
     if (history) {
@@ -688,23 +759,26 @@ static int group_temporal_call(fyprt_group* g, const fyprt_temporal_params* p, u
         launch_dt_reproject(c, fr, make_dt_call(c, *p, history), band, window, dt_motion_pending(c, history));
     }, true});
     for (uint32_t k = 0; k < sp.iterations; ++k) {
-        const DnIter it = make_dn_iter(sp, k, false);
+        DnIter it = make_dn_iter(sp, k, false);
+        if (keep) it.last = 0u;
         const bool feedback = k == 0 && p->feedback;
         steps.push_back({3 + (int)k, [k](fyprt_context* c) { return std::vector<XBuf>{{c->dn.col[(k + 1u) & 1u].p, kDnColourBytes}, {c->dt.var[k & 1u].p, kDtVarianceBytes}}; }, true, it.last != 0,
                          [k, it, feedback](fyprt_context* c, const DnFrame& fr, DnBand band) {
                              launch_dt_iterate(c, fr, it, band, c->dn.col[(k + 1u) & 1u].p, c->dn.col[k & 1u].p, c->dt.var[k & 1u].p, c->dt.var[(k + 1u) & 1u].p, feedback ? c->dt.hist[c->dtCur ^ 1].p : nullptr);
                          }, true});
     }
-    if (sp.iterations == 0) steps.push_back(finish_band_step(1));
-    TRY(group_filter_enqueue(g, plan, steps, sp.demodulate_albedo, root, rgba8, radiance4, timed));
+    if (keep) group_upscale_steps(steps, sp, scale, 3 + (int)sp.iterations, (int)((sp.iterations + 1u) & 1u), false);
+    else if (sp.iterations == 0) steps.push_back(finish_band_step(1));
+    TRY(group_filter_enqueue(g, plan, steps, sp.demodulate_albedo, root, rgba8, radiance4, timed, scale));
     for (fyprt_context* c : g->ctx) {
         c->dtCur ^= 1; c->dtValid = true; c->dtGroup = g->id; c->dtSnapPending = false; std::memcpy(c->dtPV, c->framePV, 64);
     }
     return FYPRT_OK;
 }
 // A failed enqueue leaves some bands' new history written and others' not: the group's history is dropped instead.
-static int group_temporal_call_or_drop(fyprt_group* g, const fyprt_temporal_params* p, uint32_t historyRows, int root, uint32_t* rgba8, float4* radiance4, bool timed) {
-    const int rc = group_temporal_call(g, p, historyRows, root, rgba8, radiance4, timed);
+static int group_temporal_call_or_drop(fyprt_group* g, const fyprt_temporal_params* p, uint32_t historyRows, int root, uint32_t* rgba8, float4* radiance4, bool timed,
+                                       uint32_t scale = 1u) {
+    const int rc = group_temporal_call(g, p, historyRows, root, rgba8, radiance4, timed, scale);
     if (rc != FYPRT_OK) for (fyprt_context* c : g->ctx) c->drop_history();
     return rc;
 }
@@ -730,6 +804,61 @@ int fyprt_group_denoise_temporal_plan(const uint32_t* row_bounds, int n, uint32_
     int at;
     if (!row_bounds || n <= 0 || iterations > 8u || bad_bands(row_bounds, n, height, &at)) return FYPRT_EINVAL;
     return export_plan(group_temporal_plan(std::vector<uint32_t>(row_bounds, row_bounds + n + 1), height, iterations, history_rows), out5, capacity);
+}
+
+// ---- fyprt_group_denoise_upscale*: the guided upscaler (rt_upscale.h) on the group's bands.  The low-res stage is the group's (either call
+// above in its keep form); band [b, e) then traces and resolves the hi-res rows [s b, s e) itself, after pulling the one low-res row below
+// it.  The hi-res guide and albedo buffers are full size on every member (48 B per hi-res pixel), as every other group buffer is.
+static int group_upscale_check(fyprt_group* g, const fyprt_upscale_params* p, int root, const void* rgba8, const void* radiance4, bool device) {
+    const char* who = device ? "fyprt_group_denoise_upscale_device" : "fyprt_group_denoise_upscale";
+    if (!g) return FYPRT_EINVAL;
+    fyprt_context* c0 = g->ctx[0];
+    TRY(check_upscale_params(c0, who, p));
+    TRY(group_denoise_check_call(g, who, root, rgba8, radiance4, device));
+    for (fyprt_context* c : g->ctx) {                         // the bands would otherwise trace different hi-res frames
+        const DevCamera &a = c->frameCam, &b = c0->frameCam;
+        if (std::memcmp(&a.invProj, &b.invProj, sizeof a.invProj) != 0 || std::memcmp(&a.invView, &b.invView, sizeof a.invView) != 0 ||
+            std::memcmp(&a.position, &b.position, sizeof a.position) != 0 || std::memcmp(&c->frameSky, &c0->frameSky, sizeof c->frameSky) != 0)
+            return c->fail(FYPRT_ESTATE, std::string(who) + ": the members' last frames differ in camera or sky colour");
+    }
+    return p->temporal ? group_temporal_check_state(g, who) : FYPRT_OK;
+}
+// The members' hi-res buffers for scale s.  Another scale drops a member's old ones together with its hi-res staging: the member's own
+// stream may still write them (ensure_up_buffers waits for it), and the earlier root's collect may still read the staging.
+static int group_ensure_up_buffers(fyprt_group* g, uint32_t s) {
+    for (fyprt_context* c : g->ctx) {
+        HIPCHK(c, hipSetDevice(c->device));
+        if ((c->upScale != s || c->up.albedo.n != (size_t)c->W * s * ((size_t)c->H * s)) && (c->up.outImg.p || c->up.outRad.p) && g->dnRoot >= 0)
+            HIPCHK(c, hipEventSynchronize(g->dn[g->dnRoot].collect));
+        TRY(ensure_up_buffers(c, s));
+    }
+    return FYPRT_OK;
+}
+static int group_upscale_call(fyprt_group* g, const fyprt_upscale_params* p, uint32_t historyRows, int root, uint32_t* rgba8, float4* radiance4, bool timed) {
+    const int rc = p->temporal ? group_temporal_call_or_drop(g, &p->filter, historyRows, root, rgba8, radiance4, timed, p->scale)
+                               : group_spatial_call(g, &p->filter.spatial, root, rgba8, radiance4, timed, p->scale);
+    if (rc == FYPRT_OK) for (fyprt_context* c : g->ctx) c->upValid = true;
+    return rc;
+}
+
+int fyprt_group_denoise_upscale(fyprt_group* g, const fyprt_upscale_params* p, uint32_t history_rows, uint32_t* rgba8, float* radiance4, float* band_ms) {
+    TRY(group_upscale_check(g, p, 0, rgba8, radiance4, false));
+    return group_denoise_blocking(g, rgba8, radiance4, band_ms, [&](uint32_t* img, float4* rad) { return group_upscale_call(g, p, history_rows, 0, img, rad, true); },
+                                  p->scale, [&]() { return group_ensure_up_buffers(g, p->scale); });
+}
+
+int fyprt_group_denoise_upscale_device(fyprt_group* g, const fyprt_upscale_params* p, uint32_t history_rows, int root, void* rgba8, void* radiance4) {
+    TRY(group_upscale_check(g, p, root, rgba8, radiance4, true));
+    TRY(group_ensure_up_buffers(g, p->scale));
+    return group_upscale_call(g, p, history_rows, root, static_cast<uint32_t*>(rgba8), static_cast<float4*>(radiance4), false);
+}
+
+// The transfers of one fyprt_group_denoise_upscale* call in issue order, entries as fyprt_group_denoise_plan's.
+int fyprt_group_denoise_upscale_plan(const uint32_t* row_bounds, int n, uint32_t height, uint32_t iterations, uint32_t temporal, uint32_t history_rows, uint32_t* out5,
+                                     int capacity) {
+    int at;
+    if (!row_bounds || n <= 0 || iterations > 8u || bad_bands(row_bounds, n, height, &at)) return FYPRT_EINVAL;
+    return export_plan(group_upscale_plan(std::vector<uint32_t>(row_bounds, row_bounds + n + 1), height, iterations, temporal != 0, history_rows), out5, capacity);
 }
 
 // Cost-balanced bands: new boundaries from the time each band took last frame, assuming a band's cost is spread evenly over its rows

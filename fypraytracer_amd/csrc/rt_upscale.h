@@ -14,6 +14,9 @@
 //   k_up_resolve<S>   : one thread per hi-res pixel, 16 x 16 tiles as dn_tile_pos lays them out.  The tile's low-res footprint (at most
 //                       9 x 9 pixels: 16 / S columns and their right neighbour) is staged in LDS as 48-byte records (guide | e) in the
 //                       way dn_stage does it; the four taps are ds_read_b128.  Own guide and albedo: 16-byte global loads.
+// Both hi-res kernels work on a band of hi-res rows, as k_dn_iterate does on low-res ones: the full frame is the band [0, sH), and a group
+// member (fyprt_group_denoise_upscale*, fyprt_multi.h) that owns the low-res rows [b, e) runs them on [s b, s e).  The records and the
+// outputs keep their place in the full-size hi-res buffers; the band bounds are kernel arguments, so they stay in scalar registers.
 #pragma once
 #include "rt_denoise.h"
 #include "rt_kernels.h"
@@ -34,13 +37,14 @@ struct UpFrame {                     // what the resolve kernel reads about the 
     uint32_t* rgba8; float4* radiance4;   // the call's outputs, S W x S H (device memory; either may be null)
 };
 
-// cam: the frame's camera with W, H = the hi-res viewport.  sky: the sky colour the frame was rendered with.
-__global__ __launch_bounds__(kBlock) void k_up_primary(DevScene sc, DevCamera cam, uint32_t tileOrder, f3 sky, float4* __restrict__ guide,
+// cam: the frame's camera with W, H = the hi-res viewport.  sky: the sky colour the frame was rendered with.  band: the hi-res rows the
+// tiles cover, counted from band.rowBegin (grid: up_primary_grid of the band's height).
+__global__ __launch_bounds__(kBlock) void k_up_primary(DevScene sc, DevCamera cam, uint32_t tileOrder, f3 sky, DnBand band, float4* __restrict__ guide,
                                                         float4* __restrict__ albedo) {
     extern __shared__ int32_t s_stack[];                         // (stackBudget + 1) entries x kBlock threads, sized at launch
     DevFrame fr{}; fr.W = cam.W; fr.H = cam.H; fr.tileOrder = tileOrder;
     uint32_t x, y;
-    if (!pixel_of_thread(fr, 0u, cam.H, x, y)) return;
+    if (!pixel_of_thread(fr, band.rowBegin, band.rowEnd, x, y)) return;
     const size_t i = (size_t)y * cam.W + x;
     const f3 pd = ray_direction(cam, x, y);
     const Payload pp = trace_ray<false>(sc, cam.position, pd, s_stack + threadIdx.x);
@@ -53,6 +57,11 @@ __global__ __launch_bounds__(kBlock) void k_up_primary(DevScene sc, DevCamera ca
     guide[2 * i] = make_float4(pp.px, pp.py, pp.pz, pp.hitDistance);
     guide[2 * i + 1] = make_float4(pp.nx, pp.ny, pp.nz, flag);
     albedo[i] = make_float4(a.x, a.y, a.z, flag);
+}
+// tile_grid for `rows` hi-res rows: padded so that every XCD owns the same number of workgroups
+inline uint32_t up_primary_grid(uint32_t upW, uint32_t rows, uint32_t tileOrder) {
+    const uint32_t tilesX = (upW + 15u) / 16u, tilesY = (rows + 15u) / 16u;
+    return tileOrder == 2u ? tilesX * ((tilesY + 7u) / 8u) * 8u : ((tilesX * tilesY + 7u) / 8u) * 8u;
 }
 
 // Staged low-res region of a 16 x 16 hi-res tile: R x R records from (xBase / S, yBase / S).  16 consecutive hi-res columns from a
@@ -75,13 +84,17 @@ RT_DEV void up_output(const UpFrame& fr, size_t i, f3 out, float alpha) {
 
 // (A form that gathers the four taps from memory instead of staging them was timed beside this one and is gone: 0.149 against 0.126 ms
 // at 1920 x 1080 -> 3840 x 2160, profiles/upscale/upscale_rate.jsonl.)
+// band: the hi-res rows [S b, S e) of a band of low-res rows [b, e) — the tiles start at band.rowBegin (a multiple of S, so the low-res
+// row of a hi-res row is the same division as in the full frame), pixels at or below band.rowEnd leave.  The last S - 1 rows of a band
+// read the low-res row e: a group member finds it in its own guide and colour buffers, where the pull from the row's owner put it, and row
+// H is outside the image as before.  Staged rows beyond e are read (any address inside the full-size buffers) and used by no pixel.
 template <int S>
-__global__ void __launch_bounds__(256) k_up_resolve(UpFrame fr) {
+__global__ void __launch_bounds__(256) k_up_resolve(UpFrame fr, DnBand band) {
     using T = UpTile<S>;
     __shared__ float4 sG0[T::RECORDS], sG1[T::RECORDS], sC[T::RECORDS];
-    const uint32_t upW = fr.W * (uint32_t)S, upH = fr.H * (uint32_t)S;
-    const DnTilePos tp = dn_tile_pos<0>(upW, 0);
-    if (tp.yBase >= (int)upH) return;                                            // (the whole workgroup: before anything is staged)
+    const uint32_t upW = fr.W * (uint32_t)S;
+    const DnTilePos tp = dn_tile_pos<0>(upW, (int)band.rowBegin);
+    if (tp.yBase >= (int)band.rowEnd) return;                                          // (the whole workgroup: before anything is staged)
     const int bx = tp.xBase / S, by = tp.yBase / S;
     for (int k = (int)threadIdx.x; k < T::R * T::R; k += 256) {
         const int rx = k % T::R, ry = k / T::R, gx = bx + rx, gy = by + ry;
@@ -93,7 +106,7 @@ __global__ void __launch_bounds__(256) k_up_resolve(UpFrame fr) {
     }
     __syncthreads();
     const int X = tp.x, Y = tp.y;
-    if (X >= (int)upW || Y >= (int)upH) return;
+    if (X >= (int)upW || Y >= (int)band.rowEnd) return;
     const size_t i = (size_t)Y * upW + (size_t)X;
     const int x0 = X / S, y0 = Y / S, fx = X - S * x0, fy = Y - S * y0;
     const size_t p = (size_t)y0 * fr.W + (size_t)x0;
@@ -146,6 +159,6 @@ __global__ void __launch_bounds__(256) k_up_resolve(UpFrame fr) {
     }
     up_output(fr, i, out, alpha);
 }
-inline uint32_t up_resolve_grid(uint32_t upW, uint32_t upH) { return dn_grid<0>(upW, upH); }
+inline uint32_t up_resolve_grid(uint32_t upW, uint32_t rows) { return dn_grid<0>(upW, rows); }
 
 }  // namespace rt

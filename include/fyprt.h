@@ -802,6 +802,38 @@ int fyprt_group_denoise_device(fyprt_group* group, const fyprt_denoise_params* p
 int fyprt_group_denoise_temporal(fyprt_group* group, const fyprt_temporal_params* params, uint32_t history_rows, uint32_t* rgba8, float* radiance4, float* band_ms);
 int fyprt_group_denoise_temporal_device(fyprt_group* group, const fyprt_temporal_params* params, uint32_t history_rows, int root, void* rgba8, void* radiance4);
 int fyprt_group_denoise_temporal_reset(fyprt_group* group);
+/* fyprt_denoise_upscale for the frame the group rendered last: every context runs the low-res stage on its band, traces the hi-res primary
+ * rays of its own hi-res rows and resolves them; the hi-res output rows are collected on one context.
+ * The contract is fyprt_denoise_upscale's, steps 1 to 3, evaluated on the stitched frame, with the low-res stage replaced by the group's:
+ *   temporal = 0: fyprt_group_denoise up to its last iteration.
+ *   temporal = 1: steps 1 to 6 of fyprt_group_denoise_temporal with params->filter and `history_rows` (read only in this mode), history
+ *     window included, and the call IS a group temporal call: the group's history is found or not found as that call finds it, written
+ *     as it writes it, moved by fyprt_group_set_rows as before, and the motion snapshot is consumed on every member.
+ * Band k = the low-res rows [b, e) owns the hi-res rows [s b, s e).  It traces their primary rays itself (step 2) with its own copy of the
+ * camera and sky colour the frame was enqueued with, and resolves them itself (step 3).  The resolve of hi-res row Y reads the low-res
+ * rows y0 = Y div s and y0 + 1; for the last s - 1 hi-res rows of a band y0 + 1 = e belongs to the next band, and that row's guide record
+ * and its colour e after the last iteration come from its owner.  Row `height` is outside the image, as in the single call.
+ *   So: with temporal = 0 the outputs are, bit for bit, fyprt_denoise_upscale's for a single context holding the same frame; with
+ *   temporal = 1 the same holds wherever fyprt_group_denoise_temporal equals the single context — always with history_rows >= height.
+ *   out[::s, ::s] is the output of the matching group denoiser call.
+ * Afterwards FYPRT_BUF_UPSCALE_GUIDE and FYPRT_BUF_UPSCALE_ALBEDO are valid on every member for its own hi-res rows, as FYPRT_BUF_ALBEDO
+ * is after fyprt_group_denoise; FYPRT_BUF_ALBEDO and FYPRT_BUF_TEMPORAL are left as after the matching group denoiser call.  No frame
+ * state moves on any member.  fyprt_denoise_upscale* on a group member stays refused.
+ * Errors, in this order: FYPRT_EINVAL for a NULL group / params; fyprt_denoise_upscale's parameter cases in its order (scale / temporal
+ * out of range, with temporal = 1 the temporal parameter cases, the hi-res size limit, the spatial parameter cases); fyprt_group_denoise's
+ * remaining FYPRT_EINVAL cases (root, alignment of the hi-res outputs on root's context, both outputs NULL); FYPRT_ESTATE for
+ * fyprt_group_denoise's state cases in its order; for members whose last frames differ bit-wise in camera (inverse projection, inverse
+ * view, position) or sky colour — the bands would trace different hi-res frames; with temporal = 1 fyprt_group_denoise_temporal's
+ * camera-matrix and motion-mode cases.  The message is the offending member's.  A refused call drops nothing and allocates nothing.
+ * Memory: the hi-res guide and albedo buffers are FULL SIZE on every member (48 B per hi-res pixel: 400 MB per member at 3840 x 2160), as
+ * every other group buffer and as fyprt_read_buffer expects; the staging is the band's hi-res rows.  They are allocated on the first call,
+ * reallocated when scale changes (that call first waits for the member's stream and for the earlier root's collect), dropped by
+ * fyprt_resize and counted by fyprt_live_device_bytes.  Band-sized hi-res buffers are out of scope, as are an RCCL transport and striped
+ * frames.
+ * Outputs: scale*width x scale*height uint32 / float4 of the WHOLE frame; root, band_ms, alignment and "either output may be NULL, not
+ * both" are exactly fyprt_group_denoise's. */
+int fyprt_group_denoise_upscale(fyprt_group* group, const fyprt_upscale_params* params, uint32_t history_rows, uint32_t* rgba8, float* radiance4, float* band_ms);
+int fyprt_group_denoise_upscale_device(fyprt_group* group, const fyprt_upscale_params* params, uint32_t history_rows, int root, void* rgba8, void* radiance4);
 /* --- one process per GPU: RCCL over xGMI (librccl.so.1 is opened on first use).  Rank 0 calls fyprt_comm_unique_id and hands
  *     the 128 bytes to the other ranks (any transport); every rank then calls fyprt_comm_init_rank on its resized context. */
 int fyprt_comm_unique_id(void* id128);
@@ -833,6 +865,15 @@ int fyprt_group_denoise_plan(const uint32_t* row_bounds, int n, uint32_t height,
  * history_rows given, a call without a history skips it; stage 3 + k: the colour (16 B) and the variance (4 B) iteration k reads,
  * 2^(k+1) rows.  Pure host arithmetic; returns and errors as fyprt_group_denoise_plan. */
 int fyprt_group_denoise_temporal_plan(const uint32_t* row_bounds, int n, uint32_t height, uint32_t iterations, uint32_t history_rows, uint32_t* out5, int capacity);
+/* The transfers of one fyprt_group_denoise_upscale* call in issue order, entries as above: the plan of the low-res stage
+ * (fyprt_group_denoise_plan, or with temporal != 0 fyprt_group_denoise_temporal_plan for `history_rows`), then one more stage, numbered
+ * 1 + iterations (spatial) or 3 + iterations (temporal): for every band k but the last one entry (k, owner of row e_k, e_k, e_k + 1) — the
+ * colour buffer that holds e after the last iteration (16 B per pixel), the low-res row the band's last hi-res rows tap.  The row's guide
+ * record needs no entry: stage 0 already brings at least one guide row below the band (2^iterations >= 1 rows; temporal max(2, ...)).
+ * The spatial plan without an iteration has no stage 0, and the call then moves the guide record with the colour (48 B per pixel).  Pure
+ * host arithmetic; returns and errors as fyprt_group_denoise_plan. */
+int fyprt_group_denoise_upscale_plan(const uint32_t* row_bounds, int n, uint32_t height, uint32_t iterations, uint32_t temporal, uint32_t history_rows,
+                                     uint32_t* out5, int capacity);
 /* The point-to-point operations rank `rank` issues inside ONE RCCL group section, in issue order — kind 0: a halo exchange over
  * `row_bounds`; kind 1: fyprt_comm_set_rows from `row_bounds` to `new_bounds`.  (is_recv, peer, buffer, byte offset, bytes) per
  * operation; returns their number.  Pure host arithmetic (no device, no RCCL): lets a test check that the two ends of every pair of
