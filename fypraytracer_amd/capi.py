@@ -213,7 +213,7 @@ EXPORTED_SYMBOLS = [
     "fyprt_update_materials", "fyprt_export_emissive",
     "fyprt_denoise_temporal_set_motion",
     "fyprt_group_denoise", "fyprt_group_denoise_device", "fyprt_group_denoise_plan",
-    "fyprt_append_meshes", "fyprt_append_textures",
+    "fyprt_append_meshes", "fyprt_append_textures", "fyprt_remove_meshes",
     "fyprt_group_denoise_temporal", "fyprt_group_denoise_temporal_device", "fyprt_group_denoise_temporal_reset",
     "fyprt_group_denoise_temporal_plan",
     "fyprt_upscale_default_params", "fyprt_denoise_upscale", "fyprt_denoise_upscale_device",
@@ -349,6 +349,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     if hasattr(lib, "fyprt_append_meshes"):  # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
         lib.fyprt_append_meshes.argtypes = [vp, vp, u32, vp, u32, u32, vp, u32, vp, C.POINTER(u32)]
         lib.fyprt_append_textures.argtypes = [vp, C.POINTER(Texture), u32]
+    if hasattr(lib, "fyprt_remove_meshes"):  # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
+        lib.fyprt_remove_meshes.argtypes = [vp, C.POINTER(u32), u32, C.POINTER(u32)]
     alternative = path is not None or "FYPRT_LIB" in os.environ      # an older build loaded for an A/B run may lack the newest entry points
     for f in EXPORTED_SYMBOLS:
         if alternative and not hasattr(lib, f):
@@ -595,6 +597,17 @@ class Context:
         self._check(self.lib.fyprt_append_meshes(self.h, _ptr(v) if len(v) else None, len(v), _ptr(t) if len(t) else None, len(t), TRIANGLE_DTYPE.itemsize,
                                                  _ptr(ms) if len(ms) else None, len(ms), None if ov is None else (ov.ctypes.data if len(ov) else C.cast((C.c_uint32 * 8)(), C.c_void_p)), first))
         self._has_object_vertices = with_object
+
+    def remove_meshes(self, removed, with_vertex_ranges=True):
+        """A deletion applied on the device (fyprt_remove_meshes): `removed` is the record Scene.remove_meshes_from_scene returned
+        (mesh indices and their vertex ranges before the edit).  Without `with_vertex_ranges` the library takes the meshes' own ranges
+        from the object-space copy it holds, or removes no vertex when it holds none."""
+        ms = [int(m) for m in removed["meshes"]]
+        idx = (C.c_uint32 * max(1, len(ms)))(*ms)
+        vr = None
+        if with_vertex_ranges:
+            vr = (C.c_uint32 * max(2, 2 * len(ms)))(*[int(x) for r in removed["vertex_ranges"] for x in r])
+        self._check(self.lib.fyprt_remove_meshes(self.h, idx, len(ms), vr))
 
     def append_textures(self, textures):
         """New textures behind the uploaded ones (fyprt_append_textures); each a uint32 [H][W] ABGR8 array."""

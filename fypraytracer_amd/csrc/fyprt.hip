@@ -1182,6 +1182,56 @@ int fyprt_append_meshes(fyprt_context* c, const fyprt_vertex* vertices, uint32_t
     return FYPRT_OK;
 }
 
+// Mesh removal (new, no reference counterpart): the listed meshes, their triangle ranges and the given vertex ranges leave the scene.  The
+// context ends in the state fyprt_upload_scene reaches with the reduced description, except for the acceleration structure, which is the
+// old tree pruned bottom-up (rt_prune.h).  Every array is compacted on the device into a buffer of the same capacity; 4 bytes per leaf
+// record come back (the dead counts the host repeats the node pass with), tables, refit list and level grouping go up.
+#include "rt_prune.h"
+
+int fyprt_remove_meshes(fyprt_context* c, const uint32_t* mesh_indices, uint32_t mesh_count, const uint32_t* vertex_ranges) {
+    if (!c) return FYPRT_EINVAL;
+    if (mesh_count && !mesh_indices) return c->fail(FYPRT_EINVAL, "fyprt_remove_meshes: NULL mesh_indices with a non-zero count");
+    const uint32_t M0 = (uint32_t)c->topoMeshes.size(), T0 = (uint32_t)(c->topoTris.size() / 4), V0 = c->vertexCount;
+    for (uint32_t k = 0; k < mesh_count; ++k) if (mesh_indices[k] >= M0) return c->fail(FYPRT_EINVAL, "fyprt_remove_meshes: mesh index out of range");
+    std::vector<uint8_t> gone(M0, 0);
+    for (uint32_t k = 0; k < mesh_count; ++k) {
+        if (gone[mesh_indices[k]]) return c->fail(FYPRT_EINVAL, "fyprt_remove_meshes: mesh " + std::to_string(mesh_indices[k]) + " is listed twice");
+        gone[mesh_indices[k]] = 1;
+    }
+    const bool copy = !c->meshFirstVertex.empty();
+    std::vector<std::pair<uint32_t, uint32_t>> vr, tr;
+    if (vertex_ranges) {
+        for (uint32_t k = 0; k < mesh_count; ++k) {
+            if ((uint64_t)vertex_ranges[2 * k] + vertex_ranges[2 * k + 1] > V0) return c->fail(FYPRT_EINVAL, "fyprt_remove_meshes: vertex range beyond the vertex count");
+            if (vertex_ranges[2 * k + 1]) vr.push_back({vertex_ranges[2 * k], vertex_ranges[2 * k + 1]});
+        }
+        std::sort(vr.begin(), vr.end());
+        for (size_t i = 1; i < vr.size(); ++i) if (vr[i - 1].first + vr[i - 1].second > vr[i].first) return c->fail(FYPRT_EINVAL, "fyprt_remove_meshes: vertex ranges overlap");
+        if (copy) for (uint32_t k = 0; k < mesh_count; ++k) {
+            const uint32_t m = mesh_indices[k];
+            if (vertex_ranges[2 * k] != c->meshFirstVertex[m] || vertex_ranges[2 * k + 1] != c->meshFirstVertex[m + 1] - c->meshFirstVertex[m])
+                return c->fail(FYPRT_EINVAL, "fyprt_remove_meshes: the vertex range of mesh " + std::to_string(m) + " is not the mesh's own");
+        }
+    } else if (copy) {
+        for (uint32_t k = 0; k < mesh_count; ++k) { const uint32_t m = mesh_indices[k]; vr.push_back({c->meshFirstVertex[m], c->meshFirstVertex[m + 1] - c->meshFirstVertex[m]}); }
+    }
+    for (uint32_t k = 0; k < mesh_count; ++k) tr.push_back({c->topoMeshes[mesh_indices[k]].first_triangle, c->topoMeshes[mesh_indices[k]].triangle_count});
+    PruneTable tris, verts;
+    tris.build(tr); verts.build(vr);
+    if (verts.removed) for (uint32_t t = 0; t < T0; ++t) {
+        uint32_t shift;
+        if (tris.dead(t, shift)) continue;
+        for (int k = 0; k < 3; ++k) if (verts.dead(c->topoTris[(size_t)t * 4 + k], shift)) return c->fail(FYPRT_EINVAL, "fyprt_remove_meshes: surviving triangle " + std::to_string(t) + " uses a removed vertex");
+    }
+    if (!c->haveScene) return c->fail(FYPRT_ESTATE, "fyprt_remove_meshes before fyprt_upload_scene");
+    if (c->prebuiltLightTrees) return c->fail(FYPRT_ESTATE, "fyprt_remove_meshes: the scene was uploaded with prebuilt light trees; upload it again instead");
+    if (mesh_count == 0) return FYPRT_OK;
+    if (!c->hostOnly) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c)); }
+    c->frameComplete = false;                  // as fyprt_append_meshes
+    c->drop_history(); c->release_snapshot();
+    return prune_remove(c, tris, verts, gone);
+}
+
 // "Import Texture" (WalnutApp.cpp:739-754 -> Scene::CreateNewTextureInScene, Scene.cpp:228-239): the new pixel arrays are uploaded and the
 // table is extended; old pixel buffers stay where they are.
 int fyprt_append_textures(fyprt_context* c, const fyprt_texture* textures, uint32_t count) {

@@ -3,6 +3,7 @@
 // Byte layouts equal the reference's (Vertex 32, Triangle 52, Material 44).
 #pragma once
 #include "TextureIO.h"
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <type_traits>
@@ -116,6 +117,38 @@ struct Scene {
             t.materialIndex = materialIndex; triangles.push_back(t);
         }
         meshes.push_back(mesh); return &meshes.back();
+    }
+    // New (no reference counterpart): the edit fyprt_remove_meshes applies.  The listed meshes leave with their triangle ranges and their
+    // own vertex ranges; survivors keep their order, triangle and vertex indices shift down, emissiveTriangles is remapped.  Returns what
+    // was removed, in the numbering before the edit: the sorted mesh indices and (first, count) of their vertex ranges.
+    struct Removed { std::vector<uint32_t> meshes, vertexRanges; };
+    Removed RemoveMeshesFromScene(std::vector<uint32_t> indices) {
+        std::sort(indices.begin(), indices.end());
+        indices.erase(std::unique(indices.begin(), indices.end()), indices.end());
+        Removed r;
+        std::vector<uint8_t> deadT(triangles.size(), 0), deadV(worldVertices.size(), 0), gone(meshes.size(), 0);
+        for (uint32_t m : indices) {
+            if (m >= meshes.size()) continue;
+            const Mesh& me = meshes[m];
+            gone[m] = 1; r.meshes.push_back(m); r.vertexRanges.push_back(me.vertexStart); r.vertexRanges.push_back(me.vertexCount);
+            for (uint32_t t = me.indexStart / 3u; t < me.indexStart / 3u + me.indexCount / 3u; ++t) deadT[t] = 1;
+            for (uint32_t v = me.vertexStart; v < me.vertexStart + me.vertexCount; ++v) deadV[v] = 1;
+        }
+        std::vector<uint32_t> newT(triangles.size() + 1, 0), newV(worldVertices.size() + 1, 0);    // new index = survivors before
+        for (size_t t = 0; t < triangles.size(); ++t) newT[t + 1] = newT[t] + (deadT[t] ? 0u : 1u);
+        for (size_t v = 0; v < worldVertices.size(); ++v) newV[v + 1] = newV[v] + (deadV[v] ? 0u : 1u);
+        const bool object = vertices.size() == worldVertices.size();
+        for (size_t v = 0; v < worldVertices.size(); ++v) if (!deadV[v]) { worldVertices[newV[v]] = worldVertices[v]; if (object) vertices[newV[v]] = vertices[v]; }
+        worldVertices.resize(newV.back()); if (object) vertices.resize(newV.back());
+        for (size_t t = 0; t < triangles.size(); ++t) if (!deadT[t]) { Triangle x = triangles[t]; x.v0 = newV[x.v0]; x.v1 = newV[x.v1]; x.v2 = newV[x.v2]; triangles[newT[t]] = x; }
+        triangles.resize(newT.back());
+        size_t w = 0;
+        for (uint32_t e : emissiveTriangles) if (!deadT[e]) emissiveTriangles[w++] = newT[e];
+        emissiveTriangles.resize(w);
+        w = 0;
+        for (size_t m = 0; m < meshes.size(); ++m) if (!gone[m]) { Mesh me = meshes[m]; me.indexStart = newT[me.indexStart / 3u] * 3u; me.vertexStart = newV[me.vertexStart]; meshes[w++] = me; }
+        meshes.resize(w);
+        return r;
     }
     void InitSceneEmissiveTriangles() {               // Scene.cpp:209-221
         emissiveTriangles.clear();

@@ -130,6 +130,21 @@ public:
         return !report(fyprt_denoise_upscale(m_Ctx, &p, rgba8, nullptr, nullptr), "fyprt_denoise_upscale");
     }
 
+    // New (no reference counterpart): "Delete Mesh".  Edits the scene (Scene::RemoveMeshesFromScene) and applies the same edit on the device
+    // with fyprt_remove_meshes, then stamps the signatures of the reduced scene, so that the next Render() does not upload it.  A removal
+    // is not found by comparing signatures: call this instead of editing the arrays.  Before the first upload, or when the library
+    // refuses, the scene is edited all the same and the next Render() uploads it.
+    template <class SceneT> bool RemoveMeshes(SceneT& scene, const std::vector<uint32_t>& indices) {
+        const auto removed = scene.RemoveMeshesFromScene(indices);
+        if (!m_HaveScene || isSceneUpdated) { isSceneUpdated = true; m_HaveScene = false; return false; }
+        const int rc = fyprt_remove_meshes(m_Ctx, removed.meshes.data(), (uint32_t)removed.meshes.size(), removed.vertexRanges.data());
+        if (report(rc, "fyprt_remove_meshes")) { isSceneUpdated = true; m_HaveScene = false; return false; }
+        m_StructureSig = StructureSignature(scene, CountsOf(scene)); m_MaterialSig = MaterialSignature(scene);
+        KeepMaterialIndices(scene); m_Counts = CountsOf(scene); ++m_Removes;
+        return true;
+    }
+    uint32_t GetSceneRemoveCount() const { return m_Removes; }
+
     void ResetFrameIndex() { fyprt_reset_frame_index(m_Ctx); }
     RenderingSettings& GetSettings() { return m_Settings; }
     uint32_t GetCurrentFrameIndex() const { return fyprt_frame_index(m_Ctx); }
@@ -284,7 +299,7 @@ private:
     std::vector<uint32_t> m_RenderImageData;
     std::vector<float> m_AccumulationData;
     bool isSceneUpdated = true;
-    bool m_HaveScene = false; uint64_t m_StructureSig = 0, m_MaterialSig = 0; uint32_t m_Uploads = 0, m_Refits = 0, m_TransformUpdates = 0, m_MaterialUpdates = 0, m_Appends = 0;
+    bool m_HaveScene = false; uint64_t m_StructureSig = 0, m_MaterialSig = 0; uint32_t m_Uploads = 0, m_Refits = 0, m_TransformUpdates = 0, m_MaterialUpdates = 0, m_Appends = 0, m_Removes = 0;
     Counts m_Counts; bool m_ObjectVertices = false;                                         // what was uploaded: the counts an append starts from; with object-space vertices
     std::vector<uint32_t> m_PendingMeshes; std::vector<float> m_PendingTransforms; bool m_OtherEdits = false, m_MaterialEdits = false;
     std::vector<int32_t> m_TriMaterial, m_MeshMaterial; size_t m_MaterialCount = 0;     // what the library holds (UpdateMaterials)

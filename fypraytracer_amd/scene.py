@@ -238,6 +238,43 @@ class Scene:
         self.mesh_transforms.append({"pos": tuple(pos), "rotation": tuple(rotation), "scale": tuple(scale_), "vertex_start": vstart, "vertex_count": len(positions)})
         return len(self.meshes) - 1
 
+    def remove_meshes_from_scene(self, mesh_indices):
+        """The edit fyprt_remove_meshes applies (no reference counterpart): the listed meshes leave with their triangle ranges and their
+        own vertex ranges; survivors keep their order, triangle and vertex indices shift down, an explicit `emissive_triangles` is
+        remapped.  Returns the record Context.remove_meshes takes: the sorted mesh indices and their (first, count) vertex ranges
+        in the numbering before the edit."""
+        gone = sorted({int(m) for m in mesh_indices})
+        if len(gone) != len(list(mesh_indices)) or (gone and (gone[0] < 0 or gone[-1] >= len(self.meshes))):
+            raise ValueError("remove_meshes_from_scene: mesh indices must be distinct and in range")
+        ranges = [(int(self.mesh_transforms[m]["vertex_start"]), int(self.mesh_transforms[m]["vertex_count"])) for m in gone]
+        keep_t = np.ones(len(self.triangles), dtype=bool)
+        keep_v = np.ones(len(self.world_vertices), dtype=bool)
+        for m, (a, n) in zip(gone, ranges):
+            first, count, _ = self.meshes[m]
+            keep_t[first:first + count] = False
+            keep_v[a:a + n] = False
+        new_t = (np.cumsum(keep_t) - keep_t).astype(np.uint32)           # new index of a surviving triangle / vertex
+        new_v = (np.cumsum(keep_v) - keep_v).astype(np.uint32)
+        tris = self.triangles[keep_t].copy()
+        for k in ("v0", "v1", "v2"):
+            if len(tris) and not keep_v[tris[k]].all():
+                raise ValueError("remove_meshes_from_scene: a surviving triangle uses a removed vertex")
+            tris[k] = new_v[tris[k]]
+        em = np.asarray(self.emissive_triangles, dtype=np.uint32)
+        self.emissive_triangles = new_t[em[keep_t[em]]] if len(em) else em
+        removed_t_before = (np.cumsum(~keep_t) - ~keep_t).astype(np.int64)   # removed triangles below an index
+        removed_v_before = (np.cumsum(~keep_v) - ~keep_v).astype(np.int64)
+        meshes, transforms = [], []
+        for m, ((first, count, mi), tr) in enumerate(zip(self.meshes, self.mesh_transforms)):
+            if m in gone:
+                continue
+            meshes.append((int(first - (removed_t_before[first] if first < len(keep_t) else (~keep_t).sum())), count, mi))
+            a = tr["vertex_start"]
+            transforms.append({**tr, "vertex_start": int(a - (removed_v_before[a] if a < len(keep_v) else (~keep_v).sum()))})
+        self.triangles, self.meshes, self.mesh_transforms = tris, meshes, transforms
+        self.world_vertices, self.vertices = self.world_vertices[keep_v].copy(), self.vertices[keep_v].copy()
+        return {"meshes": gone, "vertex_ranges": ranges}
+
     def manager(self):
         if self.scene_manager is None:
             self.scene_manager = SceneManager()

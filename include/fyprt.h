@@ -304,6 +304,48 @@ int fyprt_append_meshes(fyprt_context* ctx,
                         const void* triangles, uint32_t triangle_count, uint32_t triangle_stride,
                         const fyprt_mesh* meshes, uint32_t mesh_count,
                         const fyprt_vertex* object_vertices, const uint32_t* mesh_first_vertex);
+/* Mesh removal, applied ON THE DEVICE.  New (no reference counterpart: the reference can import a mesh but not delete one).  The meshes
+ * `mesh_indices` (mesh_count distinct indices, any order) leave the scene.  Reduced description: the listed mesh records are gone and later
+ * meshes move down; their triangle ranges are gone, surviving triangles keep their relative order (new index = old index - removed triangles
+ * before it) and surviving meshes' first_triangle shifts likewise; the vertex ranges given are gone, surviving vertices keep their order and
+ * surviving triangles' vertex indices shift likewise.  `vertex_ranges`: NULL, or 2 * mesh_count words, (first, count) per listed mesh.  With
+ * NULL a context that holds the object-space copy (fyprt_set_object_vertices / an append with object vertices) removes each listed mesh's
+ * own range [mesh_first_vertex[m], mesh_first_vertex[m + 1]); a context without the copy removes no vertex, and the orphaned vertices stay
+ * part of the description.  Given ranges on a context that holds the copy must be exactly the meshes' own.  The object-space copy and
+ * mesh_first_vertex are compacted with the rest, so fyprt_update_transforms and fyprt_update_vertices go on working with the reduced arrays.
+ * Materials and textures are untouched.
+ * Afterwards the context is in the state fyprt_upload_scene reaches with the reduced description, bit for bit — every per-triangle record,
+ * the exported light trees and emissive list, the light records, every later frame, ray query and radiance query (checked by an oracle that
+ * walks the exported tree) — except for the acceleration structure.  The emissive list is the old one, explicit or derived, minus the removed
+ * triangles, remapped and kept in order: for a derived list exactly what upload derives.  Frame index, accumulation, reservoirs and ReSTIR
+ * history are kept, as upload keeps them (a history light index beyond the shorter list is rejected by the temporal pass); the last frame is
+ * no longer denoisable; the temporal history and the motion snapshot are dropped, as an append drops them.  A later light-based render
+ * answers FYPRT_ENOLIGHT when no emitter is left; removing every mesh leaves the state of an upload of a scene without triangles.
+ * Acceleration structure — the prune rule: the tree is pruned bottom-up, never rebuilt (a removal cannot deepen it).
+ *   Leaf records: a record whose triangle is removed is dead; the array is compacted stably; survivors keep every byte except the triangle
+ *     index, which is remapped.  One record per triangle holds again.
+ *   Leaf codes: (first, n) becomes (first - dead records before first, survivors in the range); with no survivor the child is dead.
+ *   Nodes, by level, levels = 1 first: a node's surviving children — remapped leaf codes and the replacements of inner children — are
+ *     compacted stably (slot order is kept, so exact-t ties resolve as before).  No survivor: the node is dead.  Exactly one: the node is
+ *     dead and is replaced in its parent by that survivor (a splice; chains collapse).  Two or more: the node lives with the new count and
+ *     levels = 1 + max(levels of its inner children).  The root follows the same rule: it may become a leaf code, or empty.
+ *   Node array: compacted stably (the area ordering survives), inner references rebased; node boxes and the level grouping follow.
+ *   Boxes: a node that lost no triangle anywhere below it keeps all bytes except rebased references.  Every other surviving node gets its
+ *     box and quantisation from the refit pass run over just those nodes, lowest level first (after exact boxes for a tree no refit has run
+ *     on); a host-only context quantises them with the host builder's quantiser from the children's exact lower corners and conservative
+ *     upper planes and exact leaf boxes.
+ * Cost: nothing per triangle crosses the bus.  Every stream is compacted on the device into a buffer of the same capacity (capacities are
+ * kept: a removal never grows fyprt_live_device_bytes beyond its value before the call, and a later append of the same size fits without
+ * growing); 4 bytes per leaf record come back (the dead counts, from which the host repeats the node pass on its topology copy), the range
+ * tables, the refit list and the level grouping (4 bytes per node) go up; light records by their kernel, light trees on the host.
+ * Blocking: pipelined frames are waited for first, everything the call launches is complete on return.  Errors, in this order: FYPRT_EINVAL
+ * for a NULL context, NULL mesh_indices with a non-zero count, a mesh index out of range, a mesh listed twice, a vertex range beyond the
+ * vertex count, two vertex ranges that overlap, with an object-space copy held a range that is not the mesh's own, a surviving triangle that
+ * uses a removed vertex; FYPRT_ESTATE before fyprt_upload_scene and on a scene uploaded with prebuilt light trees.  A failed call changes
+ * nothing.  mesh_count == 0 returns FYPRT_OK and changes nothing.  Host-only contexts are supported (everything but the device work).  The
+ * scene is per context: call it on every member of a group or communicator between frames. */
+int fyprt_remove_meshes(fyprt_context* ctx, const uint32_t* mesh_indices, uint32_t mesh_count,
+                        const uint32_t* vertex_ranges /* NULL, or 2 * mesh_count: (first, count) per listed mesh */);
 /* "Import Texture" — WalnutApp.cpp:739-754 -> Scene::CreateNewTextureInScene (Scene.cpp:228-239): the new pixel arrays are uploaded and the
  * texture table is extended; old pixel buffers stay where they are.  The context is then, bit for bit, one that uploaded the scene with the
  * longer list.  Acceleration structure, frame state and temporal history are untouched and the last frame stays denoisable — unless a
