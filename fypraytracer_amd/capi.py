@@ -135,6 +135,11 @@ class FrameStats(C.Structure):
                 ("launches", C.c_uint32), ("node_visits", C.c_uint64), ("part_node_visits", C.c_uint64 * 4)]
 
 
+class EditStats(C.Structure):  # fyprt_edit_stats: what the last geometry edit covered (fyprt_last_edit_stats)
+    _fields_ = [("partial", C.c_uint32), ("triangles_refreshed", C.c_uint32), ("leaf_records_refreshed", C.c_uint32),
+                ("nodes_refit", C.c_uint32), ("level_launches", C.c_uint32)]
+
+
 class DenoiseParams(C.Structure):  # fyprt_denoise_params (20 B) with the library's defaults (fyprt_denoise_default_params)
     _fields_ = [("iterations", C.c_uint32), ("sigma_luminance", C.c_float), ("sigma_plane", C.c_float),
                 ("normal_power_log2", C.c_uint32), ("demodulate_albedo", C.c_uint32)]
@@ -219,6 +224,7 @@ EXPORTED_SYMBOLS = [
     "fyprt_upscale_default_params", "fyprt_denoise_upscale", "fyprt_denoise_upscale_device",
     "fyprt_selftest_functions",
     "fyprt_group_denoise_upscale", "fyprt_group_denoise_upscale_device", "fyprt_group_denoise_upscale_plan",
+    "fyprt_update_mesh_vertices", "fyprt_last_edit_stats",
 ]
 # enum fyprt_probe (fyprt_selftest_functions) and the 32-bit words of one input / output record of each probe
 (PROBE_SINCOS, PROBE_ACOS, PROBE_POW5, PROBE_RND, PROBE_OCT_ENCODE, PROBE_OCT_DECODE, PROBE_PACK_ABGR, PROBE_UNPACK_ABGR, PROBE_EVAL_BRDF,
@@ -280,6 +286,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
         lib.fyprt_live_device_bytes.restype = C.c_uint64
     lib.fyprt_set_object_vertices.argtypes = [vp, vp, u32, C.POINTER(u32)]
     lib.fyprt_update_transforms.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_float), u32]
+    lib.fyprt_update_mesh_vertices.argtypes = [vp, C.POINTER(u32), u32, vp, u32]
+    lib.fyprt_last_edit_stats.argtypes = [vp, C.POINTER(EditStats)]
     lib.fyprt_compare_image.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     if hasattr(lib, "fyprt_update_materials"):   # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
         lib.fyprt_update_materials.argtypes = [vp, vp, u32, C.POINTER(u32), C.POINTER(i32), u32, vp, u32]
@@ -565,6 +573,22 @@ class Context:
         mats = np.ascontiguousarray(np.stack([np.asarray(M, dtype=np.float32).reshape(4, 4) for M in matrices]).reshape(-1))
         idx = (C.c_uint32 * len(mesh_indices))(*[int(m) for m in mesh_indices])
         self._check(self.lib.fyprt_update_transforms(self.h, idx, mats.ctypes.data_as(C.POINTER(C.c_float)), len(mesh_indices)))
+
+    def update_mesh_vertices(self, scene, mesh_indices):
+        """New world vertices of the listed meshes only (fyprt_update_mesh_vertices): their slices of scene.world_vertices, by the
+        vertex ranges of scene.mesh_transforms, cross the bus; records and tree are refitted for what moved (partial refit)."""
+        mesh_indices = [int(m) for m in mesh_indices]
+        starts = [tr["vertex_start"] for tr in scene.mesh_transforms] + [len(scene.world_vertices)]
+        parts = [scene.world_vertices[starts[m]:starts[m + 1]] for m in mesh_indices if 0 <= m < len(starts) - 1]
+        v = np.ascontiguousarray(np.concatenate(parts) if parts else scene.world_vertices[:0], dtype=VERTEX_DTYPE)
+        idx = (C.c_uint32 * max(1, len(mesh_indices)))(*mesh_indices)
+        self._check(self.lib.fyprt_update_mesh_vertices(self.h, idx, len(mesh_indices), v.ctypes.data if len(v) else None, len(v)))
+
+    def last_edit_stats(self) -> EditStats:
+        """What the last update_vertices / update_transforms / update_mesh_vertices covered (fyprt_last_edit_stats)."""
+        st = EditStats()
+        self._check(self.lib.fyprt_last_edit_stats(self.h, C.byref(st)))
+        return st
 
     def update_materials(self, scene, meshes=(), emissive_triangles=None):
         """A material edit applied on the device (fyprt_update_materials): the whole material table of `scene`, and for the listed

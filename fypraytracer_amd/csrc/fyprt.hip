@@ -71,6 +71,15 @@ template <class H, hipError_t (*Destroy)(H)> struct DevHandle {
     void reset() { if (h) (void)Destroy(h); h = nullptr; }
     operator H() const { return h; }
 };
+// Move-only owner of a few words of page-locked host memory, the target of a small read-back that must not stall the stream
+struct PinnedWords {
+    uint32_t* p = nullptr;
+    PinnedWords() = default;
+    PinnedWords(const PinnedWords&) = delete;
+    PinnedWords& operator=(const PinnedWords&) = delete;
+    ~PinnedWords() { if (p) (void)hipHostFree(p); }
+    hipError_t alloc(size_t words) { return p ? hipSuccess : hipHostMalloc((void**)&p, words * sizeof(uint32_t), hipHostMallocDefault); }
+};
 using Event = DevHandle<hipEvent_t, hipEventDestroy>;
 using Stream = DevHandle<hipStream_t, hipStreamDestroy>;
 hipError_t create(Event& e, unsigned flags = hipEventDefault) { return e.h ? hipSuccess : hipEventCreateWithFlags(&e.h, flags); }
@@ -92,11 +101,11 @@ struct OccCache {
 enum TuningKey {
     K_TILE_ORDER = 0, K_DI_WAVEFRONT = 1, K_WG_PER_CU = 2, K_SORT_TASKS = 3, K_CHUNK = 4, K_REFILL_LANES = 5, K_QUORUM_SECONDARY = 6, K_QUORUM_PRIMARY = 7,
     K_STACK_BUDGET = 8, K_STATIC_CHUNKS = 9, K_MIN_CHUNK = 10, K_PIPELINE = 11, K_BUILDER = 12, K_SKIP_HALO_PART1 = 13, K_SETUP_FETCH = 14, K_RAY_KERNEL = 15,
-    K_TOP_NODES = 16, K_FUSED_FRAME = 17, K_SKIP_DEAD_RAYS = 18, K_GI2_MODE = 19, K_GI2_REFILL_LANES = 20, K_DI_SPLIT = 21, /* 22..23 reserved */ K_COUNT = 24
+    K_TOP_NODES = 16, K_FUSED_FRAME = 17, K_SKIP_DEAD_RAYS = 18, K_GI2_MODE = 19, K_GI2_REFILL_LANES = 20, K_DI_SPLIT = 21, K_PARTIAL_REFIT = 22, /* 23 reserved */ K_COUNT = 24
 };
 constexpr struct { int def, max; } kTuning[K_COUNT] = {
     {2, 2}, {1, 1}, {0, 16}, {0, 1}, {128, 65536}, {24, 64}, {24, 64}, {32, 64}, {0, 31}, {0, 4096}, {32, 65536}, {1, 1},
-    {0, 2}, {0, 1}, {0, 2}, {0, 2}, {0, 1024}, {0, 2}, {1, 1}, {2, 2}, {48, 64}, {1, 1}, {0, 0}, {0, 0}};
+    {0, 2}, {0, 1}, {0, 2}, {0, 2}, {0, 1024}, {0, 2}, {1, 1}, {2, 2}, {48, 64}, {1, 1}, {0, 1}, {0, 0}};
 
 // host mat4 product, same operation order as the device / glm (column j = ((a0*bj.x + a1*bj.y) + a2*bj.z) + a3*bj.w)
 void matmul_cm(const float* a, const float* b, float* out) {
@@ -168,6 +177,12 @@ struct fyprt_context {
     // fyprt_append_meshes / fyprt_append_textures: the scene arrays grow in place (DevBuf::cap, grow_buffer); the nodes a graft refits
     // (rt_graft.h), grown on demand and kept; the texture table as uploaded, which a longer one starts from
     DevBuf<uint32_t> graftList; std::vector<DevTexture> texHost;
+    // partial refit (rt_partial.h), all allocated on the first partial edit: the way up from a triangle (its leaf record, the record's
+    // node, a node's parent) and the walk's scratch (per-level lists of dirty nodes, a flag per node, the list counts).  linksValid: the
+    // maps describe the tree as it is — whatever changes the topology (upload, append, removal) clears it, the next partial edit rebuilds
+    // them.  editStats: what the last geometry edit covered (fyprt_last_edit_stats)
+    DevBuf<uint32_t> nodeParent, leafParent, leafOfTri, partialLists, partialDirty, partialCounters; bool linksValid = false;
+    fyprt_edit_stats editStats{}; bool haveEditStats = false; PinnedWords partialCountsHost; bool partialCountsPending = false;
     DevBuf<unsigned long long> rayCounter;
     DevScene dsc{}; DevCamera dcam{};
     rth::SceneBVH hostBvh; rth::LightTrees hostLt; uint32_t meshCount = 0;
@@ -624,6 +639,7 @@ static int upload_level_grouping(fyprt_context* c, bool keep) {
 // c->nodes, c->leafTris, the level grouping, c->nodeBox and the host's copy c->hostBvh.  `what`: the caller's name for error texts.
 static int build_scene_tree(fyprt_context* c, const char* what, const fyprt_vertex* verts, uint32_t nV, const uint8_t* tb, uint32_t stride, const fyprt_mesh* meshes, uint32_t nM, uint32_t nT) {
     bool deviceBuild = !c->hostOnly && c->tuning[K_BUILDER] != 0 && nT > 4;
+    c->linksValid = false;                     // another tree: the partial refit's maps go with the old one
     if (deviceBuild) {
         DevBuf<float4> wide; LbvhTree tree;
         HIPCHK(c, c->leafTris.alloc((size_t)nT * 3));
@@ -796,6 +812,8 @@ static void temporal_edit_range(fyprt_context* c, uint32_t firstTri, uint32_t tr
     c->dtEditHi = empty ? firstTri + triCount : std::max(c->dtEditHi, firstTri + triCount);
 }
 
+static void full_edit_stats(fyprt_context* c);        // rt_partial.h
+
 // Scene geometry moved, topology unchanged (SceneManager::PerformAllSceneUpdates with a transform edit, SceneManager.cpp:24-66):
 // new world vertices -> per-triangle records, leaf triangles and the tree's boxes are refreshed ON THE DEVICE (rt_refit.h),
 // the per-light records are rebuilt by their kernel, the (small) light trees on the host.  The tree keeps its shape.
@@ -815,6 +833,7 @@ int fyprt_update_vertices(fyprt_context* c, const fyprt_vertex* vertices, uint32
     c->hostVerts.assign(vertices, vertices + vertex_count); c->hostVertsStale = false;
     if (nT) hipLaunchKernelGGL(k_refresh_triangles, dim3((nT + 255u) / 256u), dim3(256), 0, c->stream, c->dverts.p, c->triIdx.p, c->triPos.p, c->triShade.p, nT);
     TRY(run_refit(c));
+    full_edit_stats(c);
     c->hostBvhStale = true;
     TRY(rebuild_light_trees(c, vertices));
     if (c->dsc.emissiveCount) hipLaunchKernelGGL(k_build_light_records, dim3((c->dsc.emissiveCount + 255u) / 256u), dim3(256), 0, c->stream, c->dsc, c->lightRecs.p);
@@ -841,10 +860,14 @@ int fyprt_set_object_vertices(fyprt_context* c, const fyprt_vertex* object_verti
     return FYPRT_OK;
 }
 
+// Geometry edits at the cost of what moved: the walk from the moved triangles up to the root
+#include "rt_partial.h"
+
 // A transform edit of `count` meshes (SceneManager::PerformAllSceneUpdates with meshTransformToBeUpdated, SceneManager.cpp:24-66): 64
 // bytes per mesh cross the bus; the world vertices are recomputed on the device (k_transform_vertices), per-triangle records, leaf
 // triangles, tree boxes and light records refreshed there, and only the moved EMISSIVE meshes' light trees are rebuilt on the host
 // (their vertices read back) + the small TLAS.  Same result as fyprt_update_vertices with host-computed world vertices.
+// Tuning key 22 = 1: records and tree by the partial walk over the listed meshes (rt_partial.h) instead of the full passes.
 int fyprt_update_transforms(fyprt_context* c, const uint32_t* mesh_indices, const float* matrices16, uint32_t count) {
     if (!c || (count && (!mesh_indices || !matrices16))) return FYPRT_EINVAL;
     if (!c->haveScene || c->meshFirstVertex.empty()) return c->fail(FYPRT_ESTATE, "fyprt_update_transforms before fyprt_upload_scene + fyprt_set_object_vertices");
@@ -867,8 +890,15 @@ int fyprt_update_transforms(fyprt_context* c, const uint32_t* mesh_indices, cons
         }
     }
     HIPCHK(c, hipGetLastError());
-    if (nT) hipLaunchKernelGGL(k_refresh_triangles, dim3((nT + 255u) / 256u), dim3(256), 0, c->stream, c->dverts.p, c->triIdx.p, c->triPos.p, c->triShade.p, nT);
-    TRY(run_refit(c));
+    if (c->tuning[K_PARTIAL_REFIT]) {
+        std::vector<uint32_t> distinct; std::vector<uint8_t> listed(nM, 0);       // a mesh may be listed twice: its last matrix holds, it is walked once
+        for (uint32_t k = 0; k < count; ++k) if (!listed[mesh_indices[k]]) { listed[mesh_indices[k]] = 1; distinct.push_back(mesh_indices[k]); }
+        TRY(run_partial_refit(c, distinct));
+    } else {
+        if (nT) hipLaunchKernelGGL(k_refresh_triangles, dim3((nT + 255u) / 256u), dim3(256), 0, c->stream, c->dverts.p, c->triIdx.p, c->triPos.p, c->triShade.p, nT);
+        TRY(run_refit(c));
+        full_edit_stats(c);
+    }
     c->hostBvhStale = true; c->hostVertsStale = true;
     if (lightsMoved) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -877,6 +907,59 @@ int fyprt_update_transforms(fyprt_context* c, const uint32_t* mesh_indices, cons
     if (c->dsc.emissiveCount) hipLaunchKernelGGL(k_build_light_records, dim3((c->dsc.emissiveCount + 255u) / 256u), dim3(256), 0, c->stream, c->dsc, c->lightRecs.p);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, sync_all(c));
+    partial_finish_stats(c);
+    return FYPRT_OK;
+}
+
+// New world vertices for the listed meshes only: the state fyprt_update_vertices reaches with the full array (the given vertices in
+// place, every other vertex as it is on the device), by the partial walk.  Only the listed ranges cross the bus.
+int fyprt_update_mesh_vertices(fyprt_context* c, const uint32_t* mesh_indices, uint32_t mesh_count, const fyprt_vertex* vertices, uint32_t vertex_count) {
+    if (!c) return FYPRT_EINVAL;
+    if ((mesh_count && !mesh_indices) || (vertex_count && !vertices)) return c->fail(FYPRT_EINVAL, "fyprt_update_mesh_vertices: NULL array with a non-zero count");
+    if (!c->haveScene) return c->fail(FYPRT_ESTATE, "fyprt_update_mesh_vertices before fyprt_upload_scene");
+    if (c->meshFirstVertex.empty()) return c->fail(FYPRT_ESTATE, "fyprt_update_mesh_vertices needs the mesh vertex ranges of fyprt_set_object_vertices");
+    if (c->prebuiltLightTrees) return c->fail(FYPRT_ESTATE, "fyprt_update_mesh_vertices: the scene was uploaded with prebuilt light trees; upload it again instead");
+    if (c->hostOnly) return c->fail(FYPRT_ESTATE, "fyprt_update_mesh_vertices needs a device (host-only context)");
+    const uint32_t nM = (uint32_t)c->topoMeshes.size();
+    for (uint32_t k = 0; k < mesh_count; ++k) if (mesh_indices[k] >= nM) return c->fail(FYPRT_EINVAL, "fyprt_update_mesh_vertices: mesh index out of range");
+    std::vector<uint8_t> listed(nM, 0);
+    uint64_t sum = 0;
+    for (uint32_t k = 0; k < mesh_count; ++k) {
+        const uint32_t m = mesh_indices[k];
+        if (listed[m]) return c->fail(FYPRT_EINVAL, "fyprt_update_mesh_vertices: mesh " + std::to_string(m) + " is listed twice");
+        listed[m] = 1; sum += c->meshFirstVertex[m + 1] - c->meshFirstVertex[m];
+    }
+    if (sum != vertex_count) return c->fail(FYPRT_EINVAL, "fyprt_update_mesh_vertices: vertex_count is not the sum of the listed meshes' vertex ranges");
+    if (mesh_count == 0) return FYPRT_OK;
+    HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c));
+    c->frameComplete = false;                  // as fyprt_update_vertices
+    TRY(temporal_edit_begin(c));
+    for (uint32_t k = 0; k < mesh_count; ++k) temporal_edit_range(c, c->topoMeshes[mesh_indices[k]].first_triangle, c->topoMeshes[mesh_indices[k]].triangle_count);
+    if (c->dtSnapPending) HIPCHK(c, hipStreamSynchronize(c->stream));          // blocking copies below: the snapshot must have read dverts first
+    std::vector<uint8_t> touched(nM, 0);
+    bool lightsMoved = false;
+    const fyprt_vertex* src = vertices;
+    for (uint32_t k = 0; k < mesh_count; ++k) {
+        const uint32_t m = mesh_indices[k], first = c->meshFirstVertex[m], n = c->meshFirstVertex[m + 1] - first;
+        TRY(upload(c, c->dverts.p + first, src, (size_t)n * sizeof(fyprt_vertex)));
+        if (n) std::memcpy(c->hostVerts.data() + first, src, (size_t)n * sizeof(fyprt_vertex));
+        if (n && is_emissive(c->topoMats[c->topoMeshes[m].material_index])) { touched[m] = 1; lightsMoved = true; }
+        src += n;
+    }
+    TRY(run_partial_refit(c, std::vector<uint32_t>(mesh_indices, mesh_indices + mesh_count)));
+    c->hostBvhStale = true;
+    if (lightsMoved) TRY(rebuild_light_trees(c, c->hostVerts.data(), touched.data()));
+    if (c->dsc.emissiveCount) hipLaunchKernelGGL(k_build_light_records, dim3((c->dsc.emissiveCount + 255u) / 256u), dim3(256), 0, c->stream, c->dsc, c->lightRecs.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, sync_all(c));
+    partial_finish_stats(c);
+    return FYPRT_OK;
+}
+
+int fyprt_last_edit_stats(fyprt_context* c, fyprt_edit_stats* out) {
+    if (!c || !out) return FYPRT_EINVAL;
+    if (!c->haveEditStats) return c->fail(FYPRT_ESTATE, "fyprt_last_edit_stats before the first geometry edit");
+    *out = c->editStats;
     return FYPRT_OK;
 }
 

@@ -107,6 +107,7 @@ static rth::ChildBox graft_host_box(const fyprt_context* c, int32_t ref) {
 static int graft_append(fyprt_context* c, const fyprt_vertex* newVerts, uint32_t nV, uint32_t firstTri, uint32_t nT, const fyprt_mesh* meshes, uint32_t meshCount) {
     rth::SceneBVH& hb = c->hostBvh;
     const size_t leafBase = hb.tris.size(), nodeBase = hb.nodes.size();
+    c->linksValid = false;                     // new nodes, new records, maybe a new root: the partial refit's maps are rebuilt
     // 1. the sub-tree: S (relative to the sub-tree), its node count and levels
     bool onDevice = !c->hostOnly && c->tuning[K_BUILDER] != 0 && nT > 4;
     DevBuf<float4> wide; LbvhTree tree; rth::SceneBVH sub;

@@ -297,6 +297,7 @@ static int prune_remove(fyprt_context* c, const PruneTable& tris, const PruneTab
     const uint32_t T = T0 - tris.removed, V = V0 - verts.removed;
     const uint32_t nLeaf = (uint32_t)hb.tris.size(), nNodes = (uint32_t)hb.nodes.size();
     const bool dev = !c->hostOnly;
+    c->linksValid = false;                     // nodes, records and triangles are renumbered: the partial refit's maps are rebuilt
     // device scratch of the call, freed on every way out: the two tables, the compactions' counts + offsets, the node pass's arrays
     DevBuf<uint2> dTab, dVtab; DevBuf<uint32_t> counts, deadBeforeDev, alive, newIndex, refitList; DevBuf<int32_t> repl;
     if (dev) {

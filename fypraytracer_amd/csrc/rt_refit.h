@@ -49,9 +49,8 @@ __global__ void k_transform_vertices(const DevVertex* obj, DevVertex* world, uin
     world[first + k] = o;
 }
 
-__global__ void k_refresh_leaf_tris(const float4* triPos, float4* leafTris, uint32_t nLeaf) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= nLeaf) return;
+// (v0, e1, e2) of leaf record j from the positions of its triangle; the record's triangle index and padding stay
+RT_DEV void refresh_leaf_record(const float4* triPos, float4* leafTris, uint32_t j) {
     float4* r = leafTris + (size_t)j * 3;
     const float4 c = r[2];
     const uint32_t tri = (uint32_t)__float_as_int(c.y);
@@ -60,6 +59,11 @@ __global__ void k_refresh_leaf_tris(const float4* triPos, float4* leafTris, uint
     r[0] = make_float4(a.x, a.y, a.z, b.x - a.x);
     r[1] = make_float4(b.y - a.y, b.z - a.z, d.x - a.x, d.y - a.y);
     r[2] = make_float4(d.z - a.z, c.y, c.z, c.w);
+}
+__global__ void k_refresh_leaf_tris(const float4* triPos, float4* leafTris, uint32_t nLeaf) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= nLeaf) return;
+    refresh_leaf_record(triPos, leafTris, j);
 }
 
 // Sum of squared RGB differences of two ABGR8 images over rows [rowBegin, rowEnd) — MisUtils::ComputeMSE (MisUtils.cpp:118-147) as a
@@ -120,11 +124,9 @@ RT_DEV void refit_child_boxes(uint32_t cnt, const int32_t (&child)[4], const flo
     }
 }
 
-// nodeBox: 2 float4 per node (lo.xyz, hi.xyz), written for every node processed
-__global__ __launch_bounds__(128) void k_refit_level(float4* nodes, const uint32_t* levelNodes, uint32_t count, const float4* leafTris, const float4* triPos, float4* nodeBox) {
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= count) return;
-    const uint32_t node = levelNodes[k];
+// One node's refit: exact child boxes, then the node's origin, grid exponents and child planes, and its own exact box into nodeBox
+// (2 float4 per node: lo.xyz, hi.xyz).  Shared by the pass over whole levels and the partial one over dirty nodes (rt_partial.h).
+RT_DEV void refit_node(float4* nodes, uint32_t node, const float4* leafTris, const float4* triPos, float4* nodeBox) {
     float4* n = nodes + (size_t)node * 4;
     const float4 q0 = n[0], q1 = n[1];
     const uint32_t ex = (uint32_t)__float_as_int(q0.w), cnt = (ex >> 24) & 7u;
@@ -164,6 +166,13 @@ __global__ __launch_bounds__(128) void k_refit_level(float4* nodes, const uint32
     n[3] = make_float4(__int_as_float((int)qhi[1]), __int_as_float((int)qhi[2]), 0.0f, 0.0f);
     nodeBox[(size_t)node * 2] = make_float4(nb.lo[0], nb.lo[1], nb.lo[2], 0.0f);
     nodeBox[(size_t)node * 2 + 1] = make_float4(nb.hi[0], nb.hi[1], nb.hi[2], 0.0f);
+}
+
+// nodeBox is written for every node processed
+__global__ __launch_bounds__(128) void k_refit_level(float4* nodes, const uint32_t* levelNodes, uint32_t count, const float4* leafTris, const float4* triPos, float4* nodeBox) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= count) return;
+    refit_node(nodes, levelNodes[k], leafTris, triPos, nodeBox);
 }
 
 // The reference keeps ONE pair of octahedral-normal buffers for both ReSTIRs (R.cu: normalBuffers prev / cur, swapped after every ReSTIR

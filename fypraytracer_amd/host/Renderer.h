@@ -164,6 +164,8 @@ public:
     void NoteMeshTransform(uint32_t meshIndex, const float* matrix16) { m_PendingMeshes.push_back(meshIndex); m_PendingTransforms.insert(m_PendingTransforms.end(), matrix16, matrix16 + 16); }
     void NoteOtherSceneEdit() { m_OtherEdits = true; }
     void NoteMaterialEdit() { m_MaterialEdits = true; }
+    // Transform edits refit what moved only (tuning key 22 of the context) instead of the whole scene.  Edit detection is unchanged.
+    bool SetPartialRefit(bool on) { return m_Ctx && fyprt_set_tuning(m_Ctx, 22, on ? 1 : 0) == FYPRT_OK; }
     uint32_t GetTransformUpdateCount() const { return m_TransformUpdates; }
     void SetPresenter(std::function<void(const uint32_t*, uint32_t, uint32_t)> p) { m_Present = std::move(p); }
     const fyprt_frame_stats& GetLastFrameStats() const { return m_LastStats; }

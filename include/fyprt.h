@@ -434,8 +434,11 @@ int fyprt_set_ray_counting(fyprt_context* ctx, int enabled);
  *         material, light candidates) on a third stream — beside the previous frame's setup kernel, which writes the history — and the temporal
  *         merge on the front stream, fed through a private staging set per frame parity (72 B per pixel and parity).  0 = one kernel on the front
  *         stream.  Same results bit for bit; blocking, instrumented and two-call frames always take the one kernel.
- * Values are range-checked (FYPRT_EINVAL): key 0: 0..2, keys 1, 3, 11, 13, 18, 21: 0..1, keys 12, 14, 15, 17, 19: 0..2, key 2: 0..16, keys 5, 6, 7, 20: 0..64,
- * key 8: 0..31, key 16: 0..1024; keys 22..23 are reserved (0). */
+ * key 22: path of fyprt_update_transforms: 0 (default) = the full passes (every per-triangle record, every leaf record, every node of every
+ *         level); 1 = the partial refit (below, fyprt_update_mesh_vertices): records and nodes of the listed meshes only.  Same state
+ *         on a tree a full refit has run on; otherwise nodes and records nothing moved under keep their bytes.
+ * Values are range-checked (FYPRT_EINVAL): key 0: 0..2, keys 1, 3, 11, 13, 18, 21, 22: 0..1, keys 12, 14, 15, 17, 19: 0..2, key 2: 0..16, keys 5, 6, 7, 20: 0..64,
+ * key 8: 0..31, key 16: 0..1024; key 23 is reserved (0). */
 int fyprt_set_tuning(fyprt_context* ctx, int key, int value);
 /* The value in effect (key 8: the budget actually used for the uploaded scene, which an instrumented restatement of the
  * traversal must use too). */
@@ -450,6 +453,31 @@ int fyprt_set_object_vertices(fyprt_context* ctx, const fyprt_vertex* object_ver
  * vertices, per-triangle records, tree boxes and light records are refreshed on the device, the light trees of the moved emissive
  * meshes (+ the TLAS) on the host.  Same result as fyprt_update_vertices with the host-computed world vertices. */
 int fyprt_update_transforms(fyprt_context* ctx, const uint32_t* mesh_indices, const float* matrices16, uint32_t count);
+
+/* Partial refit: new world vertices for the listed meshes only.  `vertices`: the meshes' own vertex ranges [mesh_first_vertex[m],
+ * mesh_first_vertex[m+1]) (fyprt_set_object_vertices) concatenated in the order listed; vertex_count = their sum.  Afterwards the context
+ * is in the state fyprt_update_vertices reaches with the full array (the given vertices in place, every other vertex as it is on the
+ * device): world vertices, per-triangle records, leaf records, light records, exported light trees, every later frame and query are equal
+ * bit for bit.  Tree: every node with a moved triangle anywhere below it has the bytes (and the exact box) the full refit writes; every
+ * other node and leaf record keeps its bytes — so on a tree a full refit has run on, fyprt_export_bvh is byte for byte the full update's.
+ * Cost: the listed vertex ranges cross the bus; on the device the listed meshes' triangles, their leaf records and the nodes above them
+ * are rewritten (a walk from the moved triangles to the root, level by level), nothing else is read or written.  The object-space copy is
+ * not touched: a later transform of the mesh starts from it again, as after fyprt_update_vertices.  Frame, denoiser and motion-snapshot
+ * state follow fyprt_update_transforms; the light trees of listed emissive meshes (+ the TLAS) are rebuilt on the host.  Blocking.
+ * Memory: the first partial edit after an upload, append or removal builds the way up the tree — 4 bytes per node, per leaf record and
+ * per triangle — and the walk's scratch — 8 bytes per node + 128 bytes; both are kept (fyprt_live_device_bytes counts them) until the
+ * topology changes again.  A tree no refit has run on also gets one pass that fills every node's exact box first.
+ * Errors, in this order: FYPRT_EINVAL: NULL context, NULL array with a non-zero count.  FYPRT_ESTATE: before fyprt_upload_scene; without
+ * the mesh vertex ranges of fyprt_set_object_vertices; scene with prebuilt light trees; host-only context.  FYPRT_EINVAL: mesh index out
+ * of range; mesh listed twice; vertex_count not the sum of the ranges.  A failed call changes nothing; mesh_count == 0 returns FYPRT_OK
+ * and changes nothing. */
+int fyprt_update_mesh_vertices(fyprt_context* ctx, const uint32_t* mesh_indices, uint32_t mesh_count, const fyprt_vertex* vertices, uint32_t vertex_count);
+
+/* What the last fyprt_update_vertices / fyprt_update_transforms / fyprt_update_mesh_vertices covered.  partial: 0 = the full passes
+ * (the counts are the scene's triangles, leaf records and nodes, and the tree's levels), 1 = the partial refit (distinct triangles,
+ * leaf records and nodes rewritten, and the level launches made).  FYPRT_ESTATE before the first geometry edit. */
+typedef struct fyprt_edit_stats { uint32_t partial, triangles_refreshed, leaf_records_refreshed, nodes_refit, level_launches; } fyprt_edit_stats;
+int fyprt_last_edit_stats(fyprt_context* ctx, fyprt_edit_stats* out);
 
 /* MisUtils::ComputeMSE / ComputePSNR (MisUtils.cpp:118-157) of the current frame against a host reference image, reduced on the
  * device (exact integer sums: equals the host routine bit for bit); `flip_reference_rows` reads the reference vertically flipped as
