@@ -140,6 +140,11 @@ class EditStats(C.Structure):  # fyprt_edit_stats: what the last geometry edit c
                 ("nodes_refit", C.c_uint32), ("level_launches", C.c_uint32)]
 
 
+class AppendPlacement(C.Structure):  # fyprt_append_placement: where the last append linked its sub-tree (fyprt_last_append_placement)
+    _fields_ = [("mode", C.c_uint32), ("kind", C.c_uint32), ("node", C.c_uint32), ("slot", C.c_uint32), ("depth", C.c_uint32),
+                ("cost_bits", C.c_uint32), ("levels_before", C.c_uint32), ("levels_after", C.c_uint32), ("candidates", C.c_uint32)]
+
+
 class DenoiseParams(C.Structure):  # fyprt_denoise_params (20 B) with the library's defaults (fyprt_denoise_default_params)
     _fields_ = [("iterations", C.c_uint32), ("sigma_luminance", C.c_float), ("sigma_plane", C.c_float),
                 ("normal_power_log2", C.c_uint32), ("demodulate_albedo", C.c_uint32)]
@@ -225,6 +230,7 @@ EXPORTED_SYMBOLS = [
     "fyprt_selftest_functions",
     "fyprt_group_denoise_upscale", "fyprt_group_denoise_upscale_device", "fyprt_group_denoise_upscale_plan",
     "fyprt_update_mesh_vertices", "fyprt_last_edit_stats",
+    "fyprt_set_append_placement", "fyprt_last_append_placement",
 ]
 # enum fyprt_probe (fyprt_selftest_functions) and the 32-bit words of one input / output record of each probe
 (PROBE_SINCOS, PROBE_ACOS, PROBE_POW5, PROBE_RND, PROBE_OCT_ENCODE, PROBE_OCT_DECODE, PROBE_PACK_ABGR, PROBE_UNPACK_ABGR, PROBE_EVAL_BRDF,
@@ -288,6 +294,9 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.fyprt_update_transforms.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_float), u32]
     lib.fyprt_update_mesh_vertices.argtypes = [vp, C.POINTER(u32), u32, vp, u32]
     lib.fyprt_last_edit_stats.argtypes = [vp, C.POINTER(EditStats)]
+    if hasattr(lib, "fyprt_set_append_placement"):  # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
+        lib.fyprt_set_append_placement.argtypes = [vp, C.c_int]
+        lib.fyprt_last_append_placement.argtypes = [vp, C.POINTER(AppendPlacement)]
     lib.fyprt_compare_image.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     if hasattr(lib, "fyprt_update_materials"):   # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
         lib.fyprt_update_materials.argtypes = [vp, vp, u32, C.POINTER(u32), C.POINTER(i32), u32, vp, u32]
@@ -621,6 +630,17 @@ class Context:
         self._check(self.lib.fyprt_append_meshes(self.h, _ptr(v) if len(v) else None, len(v), _ptr(t) if len(t) else None, len(t), TRIANGLE_DTYPE.itemsize,
                                                  _ptr(ms) if len(ms) else None, len(ms), None if ov is None else (ov.ctypes.data if len(ov) else C.cast((C.c_uint32 * 8)(), C.c_void_p)), first))
         self._has_object_vertices = with_object
+
+    def set_append_placement(self, mode):
+        """Where append_meshes links the sub-tree (fyprt_set_append_placement): 0 at the root (default), 1 at the cheapest place by
+        the surface-area rule of include/fyprt.h."""
+        self._check(self.lib.fyprt_set_append_placement(self.h, int(mode)))
+
+    def last_append_placement(self) -> AppendPlacement:
+        """Where the last append with triangles linked its sub-tree (fyprt_last_append_placement)."""
+        pl = AppendPlacement()
+        self._check(self.lib.fyprt_last_append_placement(self.h, C.byref(pl)))
+        return pl
 
     def remove_meshes(self, removed, with_vertex_ranges=True):
         """A deletion applied on the device (fyprt_remove_meshes): `removed` is the record Scene.remove_meshes_from_scene returned

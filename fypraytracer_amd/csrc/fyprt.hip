@@ -177,6 +177,9 @@ struct fyprt_context {
     // fyprt_append_meshes / fyprt_append_textures: the scene arrays grow in place (DevBuf::cap, grow_buffer); the nodes a graft refits
     // (rt_graft.h), grown on demand and kept; the texture table as uploaded, which a longer one starts from
     DevBuf<uint32_t> graftList; std::vector<DevTexture> texHost;
+    // fyprt_set_append_placement: the mode, the report of the last append with triangles (fyprt_last_append_placement), and the search's
+    // two result words (best key, candidate count), allocated by the first search and kept
+    int appendPlacement = 0; fyprt_append_placement placement{}; bool havePlacement = false; DevBuf<unsigned long long> placeOut;
     // partial refit (rt_partial.h), all allocated on the first partial edit: the way up from a triangle (its leaf record, the record's
     // node, a node's parent) and the walk's scratch (per-level lists of dirty nodes, a flag per node, the list counts).  linksValid: the
     // maps describe the tree as it is — whatever changes the topology (upload, append, removal) clears it, the next partial edit rebuilds
@@ -1220,8 +1223,11 @@ int fyprt_append_meshes(fyprt_context* c, const fyprt_vertex* vertices, uint32_t
                 c->hostVertsStale = false;
             }
             rc = build_scene_tree(c, "fyprt_append_meshes", c->hostVerts.data(), V, (const uint8_t*)c->topoTris.data(), 16, c->topoMeshes.data(), M, T);
+            c->placement.kind = 4u; c->placement.node = c->placement.slot = c->placement.depth = c->placement.cost_bits = c->placement.candidates = 0u;
+            c->placement.levels_after = c->hostBvh.levels;
         }
         if (rc != FYPRT_OK) return rc;
+        c->havePlacement = true;
     }
     DevScene& d = c->dsc;
     d.nodes = c->nodes.p; d.leafTris = c->leafTris.p; d.rootRef = rth::device_ref(c->hostBvh.rootRef); d.triCount = T;
@@ -1262,6 +1268,20 @@ int fyprt_append_meshes(fyprt_context* c, const fyprt_vertex* vertices, uint32_t
         else if (!tail.empty()) TRY(upload_light_trees(c, T, M));                          // the emitter -> TLAS-leaf table covers the new triangles
     }
     if (!c->hostOnly) HIPCHK(c, sync_all(c));
+    return FYPRT_OK;
+}
+
+int fyprt_set_append_placement(fyprt_context* c, int mode) {
+    if (!c) return FYPRT_EINVAL;
+    if (mode != 0 && mode != 1) return c->fail(FYPRT_EINVAL, "fyprt_set_append_placement: mode must be 0 or 1");
+    c->appendPlacement = mode;
+    return FYPRT_OK;
+}
+
+int fyprt_last_append_placement(fyprt_context* c, fyprt_append_placement* out) {
+    if (!c || !out) return FYPRT_EINVAL;
+    if (!c->havePlacement) return c->fail(FYPRT_ESTATE, "fyprt_last_append_placement before the first append with triangles");
+    *out = c->placement;
     return FYPRT_OK;
 }
 

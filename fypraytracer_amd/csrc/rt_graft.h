@@ -10,9 +10,13 @@
 //                         a new two-child node (R, S) behind all others becomes the root; the level counts stay exact
 //   k_graft_node_boxes    exact node boxes of a tree no refit pass has run on yet (a host-built one): what k_refit_level reads of the
 //                         children of the nodes it is run on
-//   k_refit_level (rt_refit.h) over the new nodes, lowest level first, then over R / the new root: one box and quantisation rule
-//                         on the device whichever builder made the sub-tree
-// The tree grows by one level about every third append (two more children for a full root's successor, then a new root again); a
+//   k_refit_level (rt_refit.h) over the new nodes, lowest level first: one box and quantisation rule on the device whichever builder
+//                         made the sub-tree
+//   k_graft_place         fyprt_set_append_placement(ctx, 1): the cheapest place for S by the surface-area rule of include/fyprt.h instead
+//                         of the root — one thread per old inner node over the partial refit's parent links (rt_partial.h) and nodeBox
+//   k_graft_path          the nodes whose children changed (a new pair node, the node that took S, its ancestors; just R / the new root in
+//                         mode 0): their meta bytes, then refit_node on each, lowest first, by ONE thread in one launch
+// In mode 0 the tree grows by one level about every third append (two more children for a full root's successor, then a new root again); a
 // result deeper than the traversal stack allows is rebuilt as an upload builds it (fyprt.hip: fyprt_append_meshes).
 // This header is part of fyprt.hip (it uses the context and its helpers) and is included there once.
 #pragma once
@@ -35,8 +39,8 @@ __global__ void k_graft_rebase(float4* nodes, uint32_t count, int32_t nodeBase, 
     n[1] = make_float4(__int_as_float(child[0]), __int_as_float(child[1]), __int_as_float(child[2]), __int_as_float(child[3]));
 }
 
-// One thread.  fresh = 0: `ref1` becomes child `slot` of `node`, whose meta byte (count | levels << 3) becomes `meta`.  fresh = 1:
-// `node` becomes a new node of the children (ref0, ref1).  Boxes, exponents and planes are k_refit_level's.  References in device form.
+// One thread.  fresh = 0: `ref1` becomes child `slot` of `node` (one more child, or a new pair node in place of the child that was
+// there), whose meta byte (count | levels << 3) becomes `meta`.  fresh = 1: `node` becomes a new node of the children (ref0, ref1).  Boxes, exponents and planes are k_refit_level's.  References in device form.
 __global__ void k_graft_link(float4* nodes, uint32_t node, uint32_t slot, int32_t ref0, int32_t ref1, uint32_t meta, int fresh) {
     if (blockIdx.x != 0u || threadIdx.x != 0u) return;
     float4* n = nodes + (size_t)node * 4;
@@ -66,6 +70,102 @@ __global__ __launch_bounds__(128) void k_graft_node_boxes(const float4* nodes, c
     refit_child_boxes(cnt, child, leafTris, triPos, nodeBox, cb, nb);
     nodeBox[(size_t)node * 2] = make_float4(nb.lo[0], nb.lo[1], nb.lo[2], 0.0f);
     nodeBox[(size_t)node * 2 + 1] = make_float4(nb.hi[0], nb.hi[1], nb.hi[2], 0.0f);
+}
+
+
+// ---- placement by surface-area cost (fyprt_set_append_placement(ctx, 1); the rule: include/fyprt.h).  Plain binary32 expressions, every
+// operation rounded on its own (the build sets -ffp-contract=off for host and device alike); the same functions serve the kernel and the
+// host-only search.
+#define RT_HD __host__ __device__ __forceinline__
+RT_HD float place_area(const RBox& b) {
+    const float dx = b.hi[0] - b.lo[0], dy = b.hi[1] - b.lo[1], dz = b.hi[2] - b.lo[2];
+    const float xy = dx * dy, yz = dy * dz, zx = dz * dx;
+    const float s = xy + yz;
+    return s + zx;
+}
+RT_HD float place_union_area(const RBox& a, const RBox& b) {
+    RBox u;
+    for (int k = 0; k < 3; ++k) { u.lo[k] = a.lo[k] < b.lo[k] ? a.lo[k] : b.lo[k]; u.hi[k] = a.hi[k] > b.hi[k] ? a.hi[k] : b.hi[k]; }
+    return place_area(u);
+}
+RT_HD float place_growth(const RBox& y, const RBox& B) { const float u = place_union_area(y, B), a = place_area(y); return u - a; }
+// one candidate offered to a thread's best key ((cost bits << 32) | id) and candidate count; costs are >= +0, so their bits order as they do
+RT_HD void place_offer(bool feasible, float cost, uint32_t id, unsigned long long& best, uint32_t& found) {
+    uint32_t bits;
+#if defined(__HIP_DEVICE_COMPILE__)
+    bits = __float_as_uint(cost);
+#else
+    std::memcpy(&bits, &cost, 4);
+#endif
+    if (!feasible || (bits & 0x7FFFFFFFu) >= 0x7F800000u) return;
+    const unsigned long long key = ((unsigned long long)bits << 32) | id;
+    best = key < best ? key : best; ++found;
+}
+// What the host knows before the search: the appended box, the sub-tree's level count, which kinds the node range still allows, and
+// whether the root pair is feasible (its new root levels <= 31)
+struct PlaceParams { RBox B; uint32_t subLevels, slotOk, pairOk, rootPairOk, root; };
+// The (up to five) candidates at node X and, at the root, the root pair.  acc = P(X), depth = d(X), levelsX / childLevels from the meta
+// bytes, cb / nb = the exact boxes of X's children / of X.
+RT_HD void place_candidates(const PlaceParams& pp, uint32_t X, uint32_t cnt, uint32_t levelsX, const uint32_t (&childLevels)[4], const RBox (&cb)[4], const RBox& nb,
+                            float acc, uint32_t depth, unsigned long long& best, uint32_t& found) {
+    const uint32_t h = pp.subLevels;
+    if (cnt < 4u) { const uint32_t hX = levelsX > h + 1u ? levelsX : h + 1u; place_offer(pp.slotOk && depth + hX <= 31u, acc, X * 8u + 4u, best, found); }
+#pragma unroll
+    for (uint32_t i = 0; i < 4; ++i) {                // (unrolled: the child boxes stay in registers, as in refit_child_boxes)
+        if (i >= cnt) continue;
+        const uint32_t hN = 1u + (childLevels[i] > h ? childLevels[i] : h), hX = levelsX > hN + 1u ? levelsX : hN + 1u;
+        const float u = place_union_area(cb[i], pp.B);
+        place_offer(pp.pairOk && depth + hX <= 31u, acc + u, X * 8u + i, best, found);
+    }
+    if (X == pp.root) place_offer(pp.rootPairOk != 0u, place_union_area(nb, pp.B), 0xFFFFFFFFu, best, found);
+}
+
+// One thread per old inner node X: its children's exact boxes, the walk up the parent links for P(X) and d(X), its candidates; the best key
+// of a wave by shuffles, then one 64-bit atomicMin (and one add of the candidate count) per wave: out[0] = best key, out[1] = candidates.
+__global__ __launch_bounds__(256) void k_graft_place(const float4* nodes, uint32_t nNodes, const float4* leafTris, const float4* triPos, const float4* nodeBox,
+                                                     const uint32_t* nodeParent, PlaceParams pp, unsigned long long* out) {
+    const uint32_t X = blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long best = ~0ull; uint32_t found = 0;
+    if (X < nNodes) {
+        const float4* n = nodes + (size_t)X * 4;
+        const float4 q0 = n[0], q1 = n[1];
+        const uint32_t w = (uint32_t)__float_as_int(q0.w), cnt = (w >> 24) & 7u, levelsX = w >> 27;
+        const int32_t child[4] = {__float_as_int(q1.x), __float_as_int(q1.y), __float_as_int(q1.z), __float_as_int(q1.w)};
+        RBox cb[4]; RBox nb;
+        refit_child_boxes(cnt, child, leafTris, triPos, nodeBox, cb, nb);
+        uint32_t childLevels[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i) {
+            const uint32_t ci = (uint32_t)child[i] >> 6;
+            if (i < cnt && child[i] >= 0 && ci < nNodes) childLevels[i] = (uint32_t)__float_as_int(nodes[(size_t)ci * 4].w) >> 27;
+        }
+        float acc = place_growth(nb, pp.B);
+        uint32_t depth = 0;
+        for (uint32_t p = nodeParent[X]; p < nNodes && depth < 64u; p = nodeParent[p]) {
+            const float4 l = nodeBox[(size_t)p * 2], hgh = nodeBox[(size_t)p * 2 + 1];
+            RBox y; y.lo[0] = l.x; y.lo[1] = l.y; y.lo[2] = l.z; y.hi[0] = hgh.x; y.hi[1] = hgh.y; y.hi[2] = hgh.z;
+            acc = acc + place_growth(y, pp.B);
+            ++depth;
+        }
+        place_candidates(pp, X, cnt, levelsX, childLevels, cb, nb, acc, depth, best, found);
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_down(best, off); const uint32_t f = __shfl_down(found, off);
+        best = o < best ? o : best; found += f;
+    }
+    if ((threadIdx.x & 63u) == 0u && found) { atomicMin(out, best); atomicAdd(out + 1, (unsigned long long)found); }
+}
+
+// One thread: the meta bytes (count | levels << 3) of the `count` listed nodes, then their refit in list order, lowest first, each
+// reading what the one before wrote: the new pair node, the node that took the sub-tree and its ancestors up to the root.
+__global__ void k_graft_path(float4* nodes, const uint32_t* list, const uint32_t* metas, uint32_t count, const float4* leafTris, const float4* triPos, float4* nodeBox) {
+    if (blockIdx.x != 0u || threadIdx.x != 0u) return;
+    for (uint32_t k = 0; k < count; ++k) {
+        float4* n = nodes + (size_t)list[k] * 4;
+        const float w = n[0].w;
+        n[0].w = __int_as_float((int)(((uint32_t)__float_as_int(w) & 0x00FFFFFFu) | (metas[k] << 24)));
+    }
+    for (uint32_t k = 0; k < count; ++k) refit_node(nodes, list[k], leafTris, triPos, nodeBox);
 }
 
 }  // namespace rt
@@ -100,6 +200,48 @@ static rth::ChildBox graft_host_box(const fyprt_context* c, int32_t ref) {
     return b;
 }
 
+static int partial_ensure_links(fyprt_context* c);      // rt_partial.h: the parent links (and exact boxes) of the tree as it is
+
+// parent[i] of the tree's inner nodes (the root keeps ~0u)
+static void graft_parents(const rth::SceneBVH& hb, std::vector<uint32_t>& parent) {
+    parent.assign(hb.nodes.size(), ~0u);
+    for (uint32_t i = 0; i < (uint32_t)hb.nodes.size(); ++i)
+        for (uint32_t k = 0; k < (hb.nodes[i].meta & 7u); ++k) if (hb.nodes[i].child[k] >= 0) parent[(size_t)hb.nodes[i].child[k]] = i;
+}
+// The placement search of a host-only context: k_graft_place's arithmetic in its order, node by node.  Exact boxes bottom-up from the
+// vertices (the host's copy of the tree holds quantised planes only).  res[0] = the best key, res[1] = the candidates.
+static void graft_place_host(const fyprt_context* c, const PlaceParams& pp, std::vector<uint32_t>& parent, unsigned long long (&res)[2]) {
+    const std::vector<rth::Node>& hn = c->hostBvh.nodes;
+    const uint32_t n = (uint32_t)hn.size();
+    graft_parents(c->hostBvh, parent);
+    std::vector<uint32_t> order(n);
+    for (uint32_t i = 0; i < n; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return (hn[a].meta >> 3) < (hn[b].meta >> 3); });
+    std::vector<RBox> box(n);
+    auto child_box = [&](int32_t ref) {
+        if (ref >= 0) return box[(size_t)ref];
+        const rth::ChildBox cb = graft_host_box(c, ref);
+        RBox b; for (int a = 0; a < 3; ++a) { b.lo[a] = cb.lo[a]; b.hi[a] = cb.hi[a]; }
+        return b;
+    };
+    for (uint32_t X : order) {
+        RBox nb; for (int a = 0; a < 3; ++a) { nb.lo[a] = 3.402823466e+38f; nb.hi[a] = -3.402823466e+38f; }
+        for (uint32_t i = 0; i < (hn[X].meta & 7u); ++i) { const RBox b = child_box(hn[X].child[i]); for (int a = 0; a < 3; ++a) { nb.lo[a] = std::min(nb.lo[a], b.lo[a]); nb.hi[a] = std::max(nb.hi[a], b.hi[a]); } }
+        box[X] = nb;
+    }
+    unsigned long long best = ~0ull; uint32_t found = 0;
+    for (uint32_t X = 0; X < n; ++X) {
+        const uint32_t cnt = hn[X].meta & 7u;
+        RBox cb[4]; uint32_t childLevels[4] = {0, 0, 0, 0};
+        for (uint32_t i = 0; i < 4 && i < cnt; ++i) { cb[i] = child_box(hn[X].child[i]); if (hn[X].child[i] >= 0) childLevels[i] = hn[(size_t)hn[X].child[i]].meta >> 3; }
+        float acc = place_growth(box[X], pp.B);
+        uint32_t depth = 0;
+        for (uint32_t p = parent[X]; p != ~0u; p = parent[p]) { acc = acc + place_growth(box[p], pp.B); ++depth; }
+        place_candidates(pp, X, cnt, hn[X].meta >> 3, childLevels, cb, box[X], acc, depth, best, found);
+    }
+    res[0] = best; res[1] = found;
+}
+
 // The sub-tree over the appended triangles [firstTri, firstTri + nT) = the meshes `meshes` (first_triangle absolute), built and grafted
 // into the tree of c.  The per-triangle records of the range are on the device, the host's topology (c->topoTris) and vertices
 // (c->hostVerts, valid for every vertex the range uses) hold the combined scene; `newVerts`: the appended vertices (the Morton grid of a
@@ -107,7 +249,6 @@ static rth::ChildBox graft_host_box(const fyprt_context* c, int32_t ref) {
 static int graft_append(fyprt_context* c, const fyprt_vertex* newVerts, uint32_t nV, uint32_t firstTri, uint32_t nT, const fyprt_mesh* meshes, uint32_t meshCount) {
     rth::SceneBVH& hb = c->hostBvh;
     const size_t leafBase = hb.tris.size(), nodeBase = hb.nodes.size();
-    c->linksValid = false;                     // new nodes, new records, maybe a new root: the partial refit's maps are rebuilt
     // 1. the sub-tree: S (relative to the sub-tree), its node count and levels
     bool onDevice = !c->hostOnly && c->tuning[K_BUILDER] != 0 && nT > 4;
     DevBuf<float4> wide; LbvhTree tree; rth::SceneBVH sub;
@@ -121,13 +262,57 @@ static int graft_append(fyprt_context* c, const fyprt_vertex* newVerts, uint32_t
     const uint32_t subNodes = onDevice ? tree.nodes : (uint32_t)sub.nodes.size(), subLevels = onDevice ? tree.levels : sub.levels;
     auto rebased = [&](int32_t ref) { return ref >= 0 ? ref + (int32_t)nodeBase : ~(int32_t)((uint32_t)~ref + ((uint32_t)leafBase << 2)); };
     const int32_t S = rebased(onDevice ? 0 : sub.rootRef);
-    // 2. where it goes
+    // 2. where it goes: the root (mode 0, an empty tree, a leaf-code root) or the cheapest place (mode 1)
     const int32_t R = hb.rootRef;
-    const bool empty = leafBase == 0, attach = !empty && R >= 0 && (hb.nodes[(size_t)R].meta & 7u) < 4u, newRoot = !empty && !attach;
+    const bool empty = leafBase == 0, search = c->appendPlacement == 1 && !empty && R >= 0;
     const uint32_t rLevels = (!empty && R >= 0) ? (uint32_t)(hb.nodes[(size_t)R].meta >> 3) : 0u;
-    const uint32_t levels = empty ? subLevels : attach ? std::max(rLevels, subLevels + 1u) : 1u + std::max(rLevels, subLevels);
-    const size_t total = nodeBase + subNodes + (newRoot ? 1u : 0u);
-    if (levels > rth::kStackBudget || total >= (size_t)rth::kMaxNodes) { c->leafTris.n = leafBase * 3; return kGraftRebuild; }
+    if (!search) c->linksValid = false;        // new nodes, new records, maybe a new root: the partial refit's maps are rebuilt (a search reads them first)
+    fyprt_append_placement& rep = c->placement;
+    rep = fyprt_append_placement{(uint32_t)c->appendPlacement, 0u, 0u, 0u, 0u, 0u, hb.levels, 0u, 0u};
+    enum : uint32_t { kFirst = 0, kSlot = 1, kPair = 2, kRootPair = 3 };
+    uint32_t kind = kFirst, X = 0, slot = 0;
+    std::vector<uint32_t> parent;               // of the old nodes, when the place may lie below the root
+    if (search) {
+        PlaceParams pp;
+        for (int a = 0; a < 3; ++a) { pp.B.lo[a] = 3.402823466e+38f; pp.B.hi[a] = -3.402823466e+38f; }
+        for (uint32_t t = firstTri; t < firstTri + nT; ++t)
+            for (int k = 0; k < 3; ++k) for (int a = 0; a < 3; ++a) {
+                const float v = c->hostVerts[c->topoTris[(size_t)t * 4 + k]].position[a];
+                pp.B.lo[a] = std::min(pp.B.lo[a], v); pp.B.hi[a] = std::max(pp.B.hi[a], v);
+            }
+        pp.subLevels = subLevels; pp.root = (uint32_t)R;
+        pp.slotOk = nodeBase + subNodes < (size_t)rth::kMaxNodes ? 1u : 0u; pp.pairOk = nodeBase + subNodes + 1u < (size_t)rth::kMaxNodes ? 1u : 0u;
+        pp.rootPairOk = pp.pairOk && 1u + std::max(rLevels, subLevels) <= rth::kStackBudget ? 1u : 0u;
+        unsigned long long res[2] = {~0ull, 0ull};
+        if (c->hostOnly) graft_place_host(c, pp, parent, res);
+        else {
+            TRY(partial_ensure_links(c));          // parent links and exact boxes of the old tree (the sub-tree is not linked yet)
+            if (c->placeOut.n != 2) HIPCHK(c, c->placeOut.alloc(2));
+            HIPCHK(c, hipMemsetAsync(c->placeOut.p, 0xFF, 8, c->stream)); HIPCHK(c, hipMemsetAsync(c->placeOut.p + 1, 0, 8, c->stream));
+            hipLaunchKernelGGL(k_graft_place, dim3(((uint32_t)nodeBase + 255u) / 256u), dim3(256), 0, c->stream, (const float4*)c->nodes.p, (uint32_t)nodeBase, (const float4*)c->leafTris.p,
+                               (const float4*)c->triPos.p, (const float4*)c->nodeBox.p, (const uint32_t*)c->nodeParent.p, pp, c->placeOut.p);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipMemcpyAsync(res, c->placeOut.p, 16, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
+        c->linksValid = false;
+        if (res[0] == ~0ull) { c->leafTris.n = leafBase * 3; return kGraftRebuild; }
+        const uint32_t id = (uint32_t)res[0];
+        rep.cost_bits = (uint32_t)(res[0] >> 32); rep.candidates = (uint32_t)res[1];
+        if (id == 0xFFFFFFFFu) kind = kRootPair;
+        else { X = id >> 3; kind = (id & 7u) == 4u ? kSlot : kPair; slot = kind == kSlot ? (uint32_t)(hb.nodes[X].meta & 7u) : (id & 7u); }
+        if (kind != kRootPair && (X >= nodeBase || slot >= 4u)) return c->fail(FYPRT_EHIP, "fyprt_append_meshes: the placement search returned no node of the tree");
+        if (kind != kRootPair && X != (uint32_t)R && parent.empty()) graft_parents(hb, parent);
+    } else if (!empty) {
+        const bool attach = R >= 0 && (hb.nodes[(size_t)R].meta & 7u) < 4u;
+        kind = attach ? kSlot : kRootPair;
+        if (attach) { X = (uint32_t)R; slot = hb.nodes[X].meta & 7u; }
+        const uint32_t levels = attach ? std::max(rLevels, subLevels + 1u) : 1u + std::max(rLevels, subLevels);
+        if (levels > rth::kStackBudget || nodeBase + subNodes + (attach ? 0u : 1u) >= (size_t)rth::kMaxNodes) { c->leafTris.n = leafBase * 3; return kGraftRebuild; }
+    }
+    const bool fresh = kind == kPair || kind == kRootPair;
+    const size_t total = nodeBase + subNodes + (fresh ? 1u : 0u);
+    if (kind == kFirst && (subLevels > rth::kStackBudget || total >= (size_t)rth::kMaxNodes)) { c->leafTris.n = leafBase * 3; return kGraftRebuild; }
     // 3. the sub-tree's nodes and leaf records behind the old ones, on the device and in the host's copy
     TRY(grow_buffer(c, c->nodes, total * 4)); TRY(grow_buffer(c, c->nodeBox, total * 2));
     hb.nodes.resize(total); hb.tris.resize(leafBase + nT);
@@ -161,46 +346,68 @@ static int graft_append(fyprt_context* c, const fyprt_vertex* newVerts, uint32_t
             if (count) hipLaunchKernelGGL(k_graft_node_boxes, dim3((count + 127u) / 128u), dim3(128), 0, c->stream, (const float4*)c->nodes.p, (const uint32_t*)(c->levelNodes.p + first), count, (const float4*)c->leafTris.p, (const float4*)c->triPos.p, c->nodeBox.p);
         }
     }
-    // 4. the link, in the host's copy (topology and level counts; on a host-only context the planes too) and on the device
-    const uint32_t linked = empty ? ~0u : attach ? (uint32_t)R : (uint32_t)(total - 1);        // the node that is refitted last
-    if (attach) {
-        rth::Node& r = hb.nodes[(size_t)R];
-        const uint32_t k = r.meta & 7u;
-        if (c->hostOnly) {
-            rth::ChildBox boxes[4]; int32_t child[4];
-            for (uint32_t i = 0; i < k; ++i) { boxes[i] = graft_plane_box(r, (int)i); child[i] = r.child[i]; }
-            boxes[k] = graft_host_box(c, S);
-            rth::QuantiseNode(r, boxes, (int)k + 1);
-            for (uint32_t i = 0; i < 4; ++i) r.child[i] = i < k ? child[i] : INT32_MIN;
-        }
-        r.child[k] = S; r.meta = (uint8_t)((k + 1u) | (levels << 3));
-        if (!c->hostOnly) hipLaunchKernelGGL(k_graft_link, dim3(1), dim3(64), 0, c->stream, c->nodes.p, (uint32_t)R, k, 0, rth::device_ref(S), (uint32_t)r.meta, 0);
-    } else if (newRoot) {
-        rth::Node& r = hb.nodes[total - 1];
-        std::memset(&r, 0, sizeof r);
-        if (c->hostOnly) { const rth::ChildBox boxes[2] = {graft_host_box(c, R), graft_host_box(c, S)}; rth::QuantiseNode(r, boxes, 2); }
-        r.child[0] = R; r.child[1] = S; r.child[2] = r.child[3] = INT32_MIN; r.meta = (uint8_t)(2u | (levels << 3));
-        if (!c->hostOnly) hipLaunchKernelGGL(k_graft_link, dim3(1), dim3(64), 0, c->stream, c->nodes.p, (uint32_t)(total - 1), 0u, rth::device_ref(R), rth::device_ref(S), (uint32_t)r.meta, 1);
+    // 4. the link, in the host's copy (topology and level counts; on a host-only context the planes too) and on the device.  `path`: the
+    // nodes whose children changed, lowest first — the new pair node, the node that took the sub-tree, its ancestors up to the root
+    const uint32_t N = (uint32_t)(total - 1);
+    std::vector<uint32_t> path;
+    if (fresh) {
+        rth::Node& n = hb.nodes[N];
+        std::memset(&n, 0, sizeof n);
+        n.child[0] = kind == kPair ? hb.nodes[X].child[slot] : R; n.child[1] = S; n.child[2] = n.child[3] = INT32_MIN; n.meta = 2u;
+        if (!c->hostOnly) hipLaunchKernelGGL(k_graft_link, dim3(1), dim3(64), 0, c->stream, c->nodes.p, N, 0u, rth::device_ref(n.child[0]), rth::device_ref(S), 2u, 1);
+        path.push_back(N);
     }
-    // 5. boxes and quantisation of the new nodes, then of the linked one
+    const bool legacy = c->hostOnly && !search && kind == kSlot;     // mode 0 keeps R's old children on R's own planes, byte for byte
+    rth::ChildBox legacyBoxes[4];
+    if (legacy) for (uint32_t i = 0; i < slot; ++i) legacyBoxes[i] = graft_plane_box(hb.nodes[X], (int)i);
+    if (kind == kSlot || kind == kPair) {
+        rth::Node& x = hb.nodes[X];
+        x.child[slot] = kind == kPair ? (int32_t)N : S;
+        if (kind == kSlot) x.meta = (uint8_t)((x.meta & 0xF8u) | (slot + 1u));
+        for (uint32_t p = X; p != ~0u; p = p == (uint32_t)R ? ~0u : parent[p]) path.push_back(p);
+        rep.depth = (uint32_t)path.size() - (fresh ? 2u : 1u);
+    }
+    std::vector<uint32_t> metas(path.size());
+    for (size_t k = 0; k < path.size(); ++k) {
+        rth::Node& n = hb.nodes[path[k]];
+        uint32_t lv = 0;
+        for (uint32_t i = 0; i < (n.meta & 7u); ++i) if (n.child[i] >= 0) lv = std::max(lv, (uint32_t)(hb.nodes[(size_t)n.child[i]].meta >> 3));
+        n.meta = (uint8_t)((n.meta & 7u) | ((lv + 1u) << 3));
+        metas[k] = n.meta;
+        if (c->hostOnly) {                                           // quantised as the prune does it: the children's boxes from what the tree holds
+            const uint32_t cnt = n.meta & 7u; const uint8_t meta = n.meta;
+            rth::ChildBox boxes[4]; int32_t child[4];
+            for (uint32_t i = 0; i < 4; ++i) { child[i] = n.child[i]; if (i < cnt) boxes[i] = legacy && i < slot ? legacyBoxes[i] : graft_host_box(c, n.child[i]); }
+            rth::QuantiseNode(n, boxes, (int)cnt);
+            for (uint32_t i = 0; i < 4; ++i) n.child[i] = i < cnt ? child[i] : INT32_MIN;
+            n.meta = meta;
+        }
+    }
+    if (!c->hostOnly && (kind == kSlot || kind == kPair))
+        hipLaunchKernelGGL(k_graft_link, dim3(1), dim3(64), 0, c->stream, c->nodes.p, X, slot, 0, rth::device_ref(hb.nodes[X].child[slot]), (uint32_t)hb.nodes[X].meta, 0);
+    // 5. boxes and quantisation of the new nodes, level by level, then of the path in one launch
     if (!c->hostOnly) {
         std::vector<uint32_t> byLevel(rth::kStackBudget + 2u, 0u);
         for (uint32_t i = 0; i < subNodes; ++i) byLevel[(hb.nodes[nodeBase + i].meta >> 3) + 1u]++;
         for (size_t l = 1; l < byLevel.size(); ++l) byLevel[l] += byLevel[l - 1];
-        std::vector<uint32_t> list(subNodes + 1u), fill(byLevel);
+        std::vector<uint32_t> list(subNodes + 2u * path.size()), fill(byLevel);
         for (uint32_t i = 0; i < subNodes; ++i) list[fill[hb.nodes[nodeBase + i].meta >> 3]++] = (uint32_t)nodeBase + i;
-        list[subNodes] = linked;
+        std::copy(path.begin(), path.end(), list.begin() + subNodes); std::copy(metas.begin(), metas.end(), list.begin() + subNodes + path.size());
         if (c->graftList.n < list.size()) HIPCHK(c, c->graftList.alloc(std::max(list.size(), 2 * c->graftList.n)));
         TRY(upload(c, c->graftList.p, list.data(), list.size() * 4));
         for (size_t l = 1; l + 1 < byLevel.size(); ++l) {
             const uint32_t first = byLevel[l], count = byLevel[l + 1] - first;
             if (count) hipLaunchKernelGGL(k_refit_level, dim3((count + 127u) / 128u), dim3(128), 0, c->stream, c->nodes.p, (const uint32_t*)(c->graftList.p + first), count, (const float4*)c->leafTris.p, (const float4*)c->triPos.p, c->nodeBox.p);
         }
-        if (linked != ~0u) hipLaunchKernelGGL(k_refit_level, dim3(1), dim3(128), 0, c->stream, c->nodes.p, (const uint32_t*)(c->graftList.p + subNodes), 1u, (const float4*)c->leafTris.p, (const float4*)c->triPos.p, c->nodeBox.p);
+        if (!path.empty()) hipLaunchKernelGGL(k_graft_path, dim3(1), dim3(64), 0, c->stream, c->nodes.p, (const uint32_t*)(c->graftList.p + subNodes), (const uint32_t*)(c->graftList.p + subNodes + path.size()),
+                                              (uint32_t)path.size(), (const float4*)c->leafTris.p, (const float4*)c->triPos.p, c->nodeBox.p);
         HIPCHK(c, hipGetLastError());
         c->nodeBoxValid = true; c->hostBvhStale = true;       // the boxes of the new nodes live on the device: an export reads the tree back
     }
-    hb.rootRef = empty ? S : attach ? R : (int32_t)(total - 1); hb.levels = levels;
+    hb.rootRef = kind == kFirst ? S : kind == kRootPair ? (int32_t)N : R;
+    hb.levels = hb.rootRef >= 0 ? (uint32_t)(hb.nodes[(size_t)hb.rootRef].meta >> 3) : 0u;
+    rep.kind = kind; rep.node = kind == kSlot || kind == kPair ? X : 0u; rep.slot = kind == kSlot || kind == kPair ? slot : 0u; rep.levels_after = hb.levels;
+    c->linksValid = false;                     // new nodes, new records, maybe a new root: the partial refit's maps are rebuilt
     // 6. the level grouping, regrouped on the host: 4 bytes per node cross the bus (once the launches above have read the old one)
     if (!c->hostOnly) HIPCHK(c, hipStreamSynchronize(c->stream));
     return upload_level_grouping(c, true);

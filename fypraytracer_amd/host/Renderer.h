@@ -166,6 +166,8 @@ public:
     void NoteMaterialEdit() { m_MaterialEdits = true; }
     // Transform edits refit what moved only (tuning key 22 of the context) instead of the whole scene.  Edit detection is unchanged.
     bool SetPartialRefit(bool on) { return m_Ctx && fyprt_set_tuning(m_Ctx, 22, on ? 1 : 0) == FYPRT_OK; }
+    // Where an import links its sub-tree (fyprt_set_append_placement): 0 at the root, 1 at the cheapest place by the surface-area rule.
+    bool SetAppendPlacement(int mode) { return m_Ctx && fyprt_set_append_placement(m_Ctx, mode) == FYPRT_OK; }
     uint32_t GetTransformUpdateCount() const { return m_TransformUpdates; }
     void SetPresenter(std::function<void(const uint32_t*, uint32_t, uint32_t)> p) { m_Present = std::move(p); }
     const fyprt_frame_stats& GetLastFrameStats() const { return m_LastStats; }

@@ -6,6 +6,7 @@
 // and renders the same frame.  The two acceleration structures differ (A's took a sub-tree at its root), so the frames agree except
 // where two triangles are hit at exactly the same distance: the share of identical pixels is printed and must pass the bar of the
 // refit test for a differently built tree.  History-free settings (no accumulation).  Exit status 1 below the bar.
+// A third argument sets A's placement mode (Renderer::SetAppendPlacement, default 0); the kind of place the import took is printed.
 #include <cmath>
 #include <cstdlib>
 #include "HostTypes.h"
@@ -52,6 +53,7 @@ static void settings(Renderer& r, int tech, uint32_t seed) {
 
 int main(int argc, char** argv) {
     const uint32_t W = argc > 1 ? std::atoi(argv[1]) : 128, H = argc > 2 ? std::atoi(argv[2]) : 80;
+    const int placement = argc > 3 ? std::atoi(argv[3]) : 0;
     const double bar = 0.97;                                              // identical pixels for a differently built tree
     std::vector<uint32_t> pixels(8 * 8);
     for (size_t i = 0; i < pixels.size(); ++i) pixels[i] = 0xFF000000u | (uint32_t)(i * 0x030507u);
@@ -63,6 +65,7 @@ int main(int argc, char** argv) {
         camera.OnResize(W, H); camera.SetPosition({0, 0, 3.4f});
         Renderer a(0);
         a.OnResize(W, H);
+        if (!a.SetAppendPlacement(placement)) { std::printf("placement mode %d refused\n", placement); return 1; }
         scene.sceneManager.PerformAllSceneUpdates(scene, a);          // drains the 20 default queue entries
         settings(a, tech, 2); a.Render(scene, camera);
         // the import, as the UI does it: a texture, a mesh, the emissive list again, the scene-updated flag
@@ -82,7 +85,10 @@ int main(int argc, char** argv) {
         const bool pass = b.GetSceneUploadCount() == 1 && a.GetSceneUploadCount() == 1 && a.GetSceneAppendCount() == 1 && share > bar;
         std::printf("%s scene uploads (A): %u\n%s scene appends (A): %u\n%s material updates (A): %u\n%s triangles: %zu\n%s identical pixels: %.4f\n",
                     name, a.GetSceneUploadCount(), name, a.GetSceneAppendCount(), name, a.GetMaterialUpdateCount(), name, scene.triangles.size(), name, share);
-        allPass = allPass && pass;
+        fyprt_append_placement pl{};
+        const bool reported = fyprt_last_append_placement(a.GetContext(), &pl) == FYPRT_OK && pl.mode == (uint32_t)placement;
+        std::printf("%s placement mode: %u\n%s placement kind: %u\n%s levels after: %u\n", name, pl.mode, name, pl.kind, name, pl.levels_after);
+        allPass = allPass && pass && reported;
     }
     return allPass ? 0 : 1;
 }

@@ -288,6 +288,7 @@ int fyprt_update_materials(fyprt_context* ctx, const fyprt_material* materials, 
  * from the refit pass run over those nodes only; a host-only context quantises R / the new root with the host builder's quantiser from R's
  * grid origin and its conservative upper planes.  The tree grows by one level about every third append; when the result would exceed 31
  * levels or the node index range, the call rebuilds the tree of the combined scene as fyprt_upload_scene would.
+ * fyprt_set_append_placement(ctx, 1) links S at the cheapest place by a surface-area cost instead of the root (below).
  * Cost: of the old scene only the per-node level grouping (4 bytes per node) crosses the bus; the scene's device arrays have a capacity that at
  * least doubles when exceeded and move device to device (fyprt_live_device_bytes counts the capacity); per-triangle records, emissive list
  * (an ordered compaction over the appended range), light records and the refit run on the device; the light trees of the new emissive meshes
@@ -304,6 +305,51 @@ int fyprt_append_meshes(fyprt_context* ctx,
                         const void* triangles, uint32_t triangle_count, uint32_t triangle_stride,
                         const fyprt_mesh* meshes, uint32_t mesh_count,
                         const fyprt_vertex* object_vertices, const uint32_t* mesh_first_vertex);
+/* Where fyprt_append_meshes links the sub-tree.  New (no reference counterpart).  mode 0 (default): at the root, the graft above, byte for
+ * byte.  mode 1: at the cheapest place by a surface-area cost.  A graft at the root makes every ray test the import's box, and every third
+ * import puts a level on top of the whole scene; mode 1 puts a small import next to what it lies in.
+ * The placement rule.  All arithmetic is IEEE binary32, every operation rounded on its own, no fma contraction, on the device and on the host.
+ *   B       exact box of the appended triangles' world vertices
+ *   b(Y)    exact box of inner node Y (the union of its triangles' vertices); a leaf child's exact box likewise
+ *   A(b)    with d = hi - lo per axis: (d.x*d.y + d.y*d.z) + d.z*d.x
+ *   U(a,b)  per-axis min and max
+ *   g(Y)    A(U(b(Y), B)) - A(b(Y))                                      (>= 0 exactly: rounding is monotone)
+ *   P(X)    acc = g(X); acc = acc + g(parent); acc = acc + g(grandparent); ... up to the root, in that order
+ *   d(X)    number of ancestors of X;   h = level count of the sub-tree's root S (0 when S is a leaf code)
+ * Candidates, for every inner node X of the old tree:
+ *   slot              count(X) < 4     cost P(X)                          hX = max(levels(X), h + 1)
+ *   pair with child i i < count(X)     cost P(X) + A(U(b(child_i), B))    hX = max(levels(X), hN + 1), hN = 1 + max(levels(child_i), h),
+ *                                                                         levels 0 for a leaf child
+ *   root pair         once per tree    cost A(U(b(R), B))                 new root levels 1 + max(levels(R), h)
+ * A slot or pair candidate is feasible iff d(X) + hX <= 31, the root pair iff its new root levels are <= 31; the node total must stay below
+ * 2^24; a candidate whose cost is not finite is skipped.  The winner is the minimum of the 64-bit key (cost bits << 32) | id, with
+ * id = node * 8 + i for a pair, node * 8 + 4 for a slot, 0xFFFFFFFF for the root pair: a cost tie goes to the lowest id, the root pair loses
+ * every tie.  No feasible candidate: the rebuild fall-back of mode 0.  An empty tree or a root that is a leaf code follows mode 0's rule.
+ * Link: the sub-tree's nodes and leaf records go behind the old ones as in mode 0.  A pair's new node N is the LAST node, its children
+ * (old child, S) in that order.  In X only the one slot changes; the slot order of the other children is kept (exact-t ties depend on it).
+ * The level counts of N, X and every ancestor stay exact (1 + max over the inner children); they get box and quantisation from the refit of
+ * one node, lowest first (a host-only context quantises them as a removal does).  Every other old node and every old leaf record keeps its
+ * index and its bytes.  Apart from the acceleration structure the state equals fyprt_upload_scene of the combined scene bit for bit, as
+ * mode 0 promises.
+ * Cost over mode 0: the parent links of the tree are built (as the first partial refit builds them; the append invalidates them again), one
+ * search launch with one thread per inner node, 16 bytes back (the key and the candidate count), and the path's refit in one launch.  The
+ * search's scratch (16 bytes) is counted by fyprt_live_device_bytes.
+ * Errors: FYPRT_EINVAL for a NULL context or a mode other than 0 or 1. */
+int fyprt_set_append_placement(fyprt_context* ctx, int mode);
+typedef struct fyprt_append_placement {
+    uint32_t mode;          /* mode in effect for that append */
+    uint32_t kind;          /* 0 first (tree was empty or a leaf code: mode 0's rule)
+                               1 slot: S is child[count] of node
+                               2 pair: new last node (child[slot] of node, S) replaces that child
+                               3 root pair: new last node (R, S) is the root
+                               4 rebuilt: no feasible place, tree rebuilt as upload builds it */
+    uint32_t node, slot, depth;      /* depth = ancestors of node; all 0 for kinds 0, 3, 4 */
+    uint32_t cost_bits;              /* the winning cost as binary32 bits; 0 in mode 0, for kinds 0 and 4 and for a leaf-code root */
+    uint32_t levels_before, levels_after, candidates;   /* candidates = feasible, finite ones (0 where no search ran) */
+} fyprt_append_placement;
+/* The report of the last successful fyprt_append_meshes with triangles, in either mode (mode 0: kinds 0, 1 at the root, 3 and 4).  Errors, in
+ * this order: FYPRT_EINVAL for NULL arguments; FYPRT_ESTATE before the first such append. */
+int fyprt_last_append_placement(fyprt_context* ctx, fyprt_append_placement* out);
 /* Mesh removal, applied ON THE DEVICE.  New (no reference counterpart: the reference can import a mesh but not delete one).  The meshes
  * `mesh_indices` (mesh_count distinct indices, any order) leave the scene.  Reduced description: the listed mesh records are gone and later
  * meshes move down; their triangle ranges are gone, surviving triangles keep their relative order (new index = old index - removed triangles
