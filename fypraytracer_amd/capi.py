@@ -145,6 +145,14 @@ class AppendPlacement(C.Structure):  # fyprt_append_placement: where the last ap
                 ("cost_bits", C.c_uint32), ("levels_before", C.c_uint32), ("levels_after", C.c_uint32), ("candidates", C.c_uint32)]
 
 
+class TreeCost(C.Structure):  # fyprt_tree_cost_sums (40 B): the surface-area cost of the tree as it is (fyprt_tree_cost)
+    _fields_ = [("root_area", C.c_double), ("inner_area", C.c_double), ("leaf_area", C.c_double),
+                ("nodes", C.c_uint32), ("leaf_children", C.c_uint32), ("leaf_records", C.c_uint32), ("levels", C.c_uint32)]
+
+
+assert C.sizeof(TreeCost) == 40
+
+
 class DenoiseParams(C.Structure):  # fyprt_denoise_params (20 B) with the library's defaults (fyprt_denoise_default_params)
     _fields_ = [("iterations", C.c_uint32), ("sigma_luminance", C.c_float), ("sigma_plane", C.c_float),
                 ("normal_power_log2", C.c_uint32), ("demodulate_albedo", C.c_uint32)]
@@ -231,6 +239,7 @@ EXPORTED_SYMBOLS = [
     "fyprt_group_denoise_upscale", "fyprt_group_denoise_upscale_device", "fyprt_group_denoise_upscale_plan",
     "fyprt_update_mesh_vertices", "fyprt_last_edit_stats",
     "fyprt_set_append_placement", "fyprt_last_append_placement",
+    "fyprt_regraft_meshes", "fyprt_tree_cost",
 ]
 # enum fyprt_probe (fyprt_selftest_functions) and the 32-bit words of one input / output record of each probe
 (PROBE_SINCOS, PROBE_ACOS, PROBE_POW5, PROBE_RND, PROBE_OCT_ENCODE, PROBE_OCT_DECODE, PROBE_PACK_ABGR, PROBE_UNPACK_ABGR, PROBE_EVAL_BRDF,
@@ -368,6 +377,9 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
         lib.fyprt_append_textures.argtypes = [vp, C.POINTER(Texture), u32]
     if hasattr(lib, "fyprt_remove_meshes"):  # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
         lib.fyprt_remove_meshes.argtypes = [vp, C.POINTER(u32), u32, C.POINTER(u32)]
+    if hasattr(lib, "fyprt_regraft_meshes"):  # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
+        lib.fyprt_regraft_meshes.argtypes = [vp, C.POINTER(u32), u32, C.POINTER(AppendPlacement)]
+        lib.fyprt_tree_cost.argtypes = [vp, C.POINTER(TreeCost)]
     alternative = path is not None or "FYPRT_LIB" in os.environ      # an older build loaded for an A/B run may lack the newest entry points
     for f in EXPORTED_SYMBOLS:
         if alternative and not hasattr(lib, f):
@@ -652,6 +664,21 @@ class Context:
         if with_vertex_ranges:
             vr = (C.c_uint32 * max(2, 2 * len(ms)))(*[int(x) for r in removed["vertex_ranges"] for x in r])
         self._check(self.lib.fyprt_remove_meshes(self.h, idx, len(ms), vr))
+
+    def regraft_meshes(self, mesh_indices):
+        """The listed meshes taken out of the tree and linked in again where they lie now (fyprt_regraft_meshes): nothing but the
+        tree moves.  Returns one AppendPlacement per listed mesh, the report of its graft."""
+        ms = [int(m) for m in mesh_indices]
+        idx = (C.c_uint32 * max(1, len(ms)))(*ms)
+        reports = (AppendPlacement * max(1, len(ms)))()
+        self._check(self.lib.fyprt_regraft_meshes(self.h, idx, len(ms), reports))
+        return [reports[k] for k in range(len(ms))]
+
+    def tree_cost(self) -> TreeCost:
+        """The surface-area cost of the tree as it is (fyprt_tree_cost); (inner_area + leaf_area) / root_area is the SAH estimate."""
+        out = TreeCost()
+        self._check(self.lib.fyprt_tree_cost(self.h, C.byref(out)))
+        return out
 
     def append_textures(self, textures):
         """New textures behind the uploaded ones (fyprt_append_textures); each a uint32 [H][W] ABGR8 array."""

@@ -180,6 +180,8 @@ struct fyprt_context {
     // fyprt_set_append_placement: the mode, the report of the last append with triangles (fyprt_last_append_placement), and the search's
     // two result words (best key, candidate count), allocated by the first search and kept
     int appendPlacement = 0; fyprt_append_placement placement{}; bool havePlacement = false; DevBuf<unsigned long long> placeOut;
+    // fyprt_tree_cost (rt_treecost.h): the root's area and one (inner, leaf) pair of sums per workgroup, grown on demand and kept
+    DevBuf<double> costPartials;
     // partial refit (rt_partial.h), all allocated on the first partial edit: the way up from a triangle (its leaf record, the record's
     // node, a node's parent) and the walk's scratch (per-level lists of dirty nodes, a flag per node, the list counts).  linksValid: the
     // maps describe the tree as it is — whatever changes the topology (upload, append, removal) clears it, the next partial edit rebuilds
@@ -1333,6 +1335,102 @@ int fyprt_remove_meshes(fyprt_context* c, const uint32_t* mesh_indices, uint32_t
     c->frameComplete = false;                  // as fyprt_append_meshes
     c->drop_history(); c->release_snapshot();
     return prune_remove(c, tris, verts, gone);
+}
+
+// Regraft (new, no reference counterpart): the listed meshes' leaf records leave the tree by the prune of a removal, then every listed
+// mesh gets the graft of an append over its own triangle range.  Only the tree moves: no scene stream, light or frame state is touched.
+// The body, after every check, all streams idle; `reports`: NULL or one entry per listed mesh, preset by the caller.
+static int regraft_meshes(fyprt_context* c, const uint32_t* mesh_indices, uint32_t mesh_count, fyprt_append_placement* reports) {
+    const uint32_t V = c->vertexCount, T = (uint32_t)(c->topoTris.size() / 4), M = (uint32_t)c->topoMeshes.size();
+    if (c->hostVertsStale && !c->hostOnly && V) {                     // the builders and the placement rule read the meshes' world vertices
+        HIPCHK(c, hipMemcpy(c->hostVerts.data(), c->dverts.p, (size_t)V * sizeof(fyprt_vertex), hipMemcpyDeviceToHost));
+        c->hostVertsStale = false;
+    }
+    // 1. the prune of a removal on the tree alone: no triangle leaves the scene, so no record is renumbered and no stream moves
+    {
+        std::vector<std::pair<uint32_t, uint32_t>> tr;
+        for (uint32_t k = 0; k < mesh_count; ++k) tr.push_back({c->topoMeshes[mesh_indices[k]].first_triangle, c->topoMeshes[mesh_indices[k]].triangle_count});
+        PruneTable tris; tris.build(tr);
+        DevBuf<uint2> dTab; DevBuf<uint32_t> counts;                  // scratch of the prune, freed on every way out
+        if (!c->hostOnly) { TRY(alloc_upload(c, dTab, tris.tab.data(), tris.tab.size())); HIPCHK(c, counts.alloc(2u * kEmMaxGroups + 1u)); }
+        std::vector<uint32_t> refit, refitLevel;
+        TRY(prune_tree(c, "fyprt_regraft_meshes", tris, false, dTab.p, counts, refit, refitLevel));
+        TRY(prune_refit(c, refit, refitLevel));                       // (with the level grouping the placement search builds its parent links from)
+    }
+    // 2. one graft per listed mesh, in the order listed, as if the mesh had just been appended
+    bool rebuilt = false;
+    for (uint32_t k = 0; k < mesh_count; ++k) {
+        const fyprt_mesh me = c->topoMeshes[mesh_indices[k]];
+        if (!me.triangle_count) continue;
+        if (!rebuilt) {
+            // the device builders' Morton grid: the exact box of the mesh's triangles, handed over as its two corners
+            fyprt_vertex corner[2] = {};
+            for (int a = 0; a < 3; ++a) { corner[0].position[a] = 3.402823466e+38f; corner[1].position[a] = -3.402823466e+38f; }
+            for (uint32_t t = me.first_triangle; t < me.first_triangle + me.triangle_count; ++t)
+                for (int i = 0; i < 3; ++i) for (int a = 0; a < 3; ++a) {
+                    const float v = c->hostVerts[c->topoTris[(size_t)t * 4 + i]].position[a];
+                    corner[0].position[a] = std::min(corner[0].position[a], v); corner[1].position[a] = std::max(corner[1].position[a], v);
+                }
+            int rc = graft_append(c, corner, 2, me.first_triangle, me.triangle_count, &me, 1);
+            if (rc == kGraftRebuild) {
+                rc = build_scene_tree(c, "fyprt_regraft_meshes", c->hostVerts.data(), V, (const uint8_t*)c->topoTris.data(), 16, c->topoMeshes.data(), M, T);
+                c->placement.kind = 4u; c->placement.node = c->placement.slot = c->placement.depth = c->placement.cost_bits = c->placement.candidates = 0u;
+                c->placement.levels_after = c->hostBvh.levels;
+                rebuilt = true;
+            }
+            if (rc != FYPRT_OK) return rc;
+            if (reports) reports[k] = c->placement;
+        } else if (reports) {                                         // the rebuilt tree holds this mesh already
+            reports[k].kind = 4u; reports[k].levels_before = reports[k].levels_after = c->hostBvh.levels;
+        }
+    }
+    DevScene& d = c->dsc;
+    d.nodes = c->nodes.p; d.leafTris = c->leafTris.p; d.rootRef = rth::device_ref(c->hostBvh.rootRef);
+    if (!c->hostOnly) HIPCHK(c, sync_all(c));
+    return FYPRT_OK;
+}
+
+int fyprt_regraft_meshes(fyprt_context* c, const uint32_t* mesh_indices, uint32_t mesh_count, fyprt_append_placement* reports) {
+    if (!c) return FYPRT_EINVAL;
+    if (mesh_count && !mesh_indices) return c->fail(FYPRT_EINVAL, "fyprt_regraft_meshes: NULL mesh_indices with a non-zero count");
+    const uint32_t M = (uint32_t)c->topoMeshes.size();
+    for (uint32_t k = 0; k < mesh_count; ++k) if (mesh_indices[k] >= M) return c->fail(FYPRT_EINVAL, "fyprt_regraft_meshes: mesh index out of range");
+    std::vector<uint8_t> listed(M, 0);
+    uint64_t moved = 0;
+    for (uint32_t k = 0; k < mesh_count; ++k) {
+        if (listed[mesh_indices[k]]) return c->fail(FYPRT_EINVAL, "fyprt_regraft_meshes: mesh " + std::to_string(mesh_indices[k]) + " is listed twice");
+        listed[mesh_indices[k]] = 1; moved += c->topoMeshes[mesh_indices[k]].triangle_count;
+    }
+    if (!c->haveScene) return c->fail(FYPRT_ESTATE, "fyprt_regraft_meshes before fyprt_upload_scene");
+    if (mesh_count == 0) return FYPRT_OK;
+    if (!c->hostOnly) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c)); }
+    const fyprt_append_placement blank{(uint32_t)c->appendPlacement, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    if (reports) for (uint32_t k = 0; k < mesh_count; ++k) reports[k] = blank;
+    if (!moved) return FYPRT_OK;
+    // what the call leaves as it found it, whichever way it ends: the report of the last append, and the sizes of the kept scratch an append
+    // or a placement search allocates (parent links, walk scratch, search result, graft list) — their contents describe the old tree and are
+    // rebuilt by whoever needs them next, so only fyprt_live_device_bytes sees the difference
+    const fyprt_append_placement saved = c->placement;
+    DevBuf<uint32_t>* kept[] = {&c->nodeParent, &c->leafParent, &c->leafOfTri, &c->partialLists, &c->partialDirty, &c->partialCounters, &c->graftList};
+    size_t keptSize[7]; for (int i = 0; i < 7; ++i) keptSize[i] = kept[i]->n;
+    const size_t placeOutSize = c->placeOut.n;
+    const int rc = regraft_meshes(c, mesh_indices, mesh_count, reports);
+    c->placement = saved; c->linksValid = false;
+    if (!c->hostOnly) {
+        for (int i = 0; i < 7; ++i) if (kept[i]->n != keptSize[i]) HIPCHK(c, kept[i]->alloc(keptSize[i]));
+        if (c->placeOut.n != placeOutSize) HIPCHK(c, c->placeOut.alloc(placeOutSize));
+    }
+    return rc;
+}
+
+// The surface-area cost of the tree as it is
+#include "rt_treecost.h"
+
+int fyprt_tree_cost(fyprt_context* c, fyprt_tree_cost_sums* out) {
+    if (!c || !out) return FYPRT_EINVAL;
+    if (!c->haveScene) return c->fail(FYPRT_ESTATE, "fyprt_tree_cost before fyprt_upload_scene");
+    if (!c->hostOnly) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c)); }
+    return tree_cost(c, out);
 }
 
 // "Import Texture" (WalnutApp.cpp:739-754 -> Scene::CreateNewTextureInScene, Scene.cpp:228-239): the new pixel arrays are uploaded and the

@@ -71,11 +71,12 @@ __global__ __launch_bounds__(kBlock) void k_prune_stream(const float4* src, floa
 
 // Entry j of an ordered compaction: does it survive, and (kinds 0, 1) the triangle it names and that triangle's shift.
 //   KIND 0  leaf records (src = the 48-byte records)      KIND 1  the emissive list (src = triangle indices)      KIND 2  alive flags
+//   KIND 3  leaf records whose triangles stay in the scene (fyprt_regraft_meshes): as kind 0, the triangle index is not remapped
 template <int KIND> RT_DEV bool prune_alive(const void* src, uint32_t j, uint32_t n, const uint2* tab, uint32_t K, uint32_t& tri, uint32_t& shift) {
     tri = 0u; shift = 0u;
     if (j >= n) return false;
     if (KIND == 2) return ((const uint32_t*)src)[j] != 0u;
-    tri = KIND == 0 ? (uint32_t)__float_as_int(((const float4*)src)[(size_t)j * 3 + 2].y) : ((const uint32_t*)src)[j];
+    tri = KIND == 0 || KIND == 3 ? (uint32_t)__float_as_int(((const float4*)src)[(size_t)j * 3 + 2].y) : ((const uint32_t*)src)[j];
     return !prune_lookup(tab, K, tri, shift);
 }
 
@@ -95,6 +96,7 @@ __global__ __launch_bounds__(kBlock) void k_prune_count(const void* src, uint32_
 
 // Survivor j goes to position p = survivors before it (the scan's offset of the workgroup + the tiles before + the rank in the tile).
 //   KIND 0  out = leaf records: record p = record j with its triangle index shifted; aux[j] = j - p = dead records before j, j in [0, n]
+//   KIND 3  the same, every byte of record j kept
 //   KIND 1  out[p] = the shifted triangle index                     KIND 2  aux[j] = p for EVERY j < n (a dead node's is never read)
 template <int KIND>
 __global__ __launch_bounds__(kBlock) void k_prune_scatter(const void* src, uint32_t n, uint32_t perGroup, const uint2* tab, uint32_t K, const uint32_t* offsets, void* out, uint32_t outCount, uint32_t* aux) {
@@ -112,11 +114,11 @@ __global__ __launch_bounds__(kBlock) void k_prune_scatter(const void* src, uint3
         __syncthreads();
         uint32_t p = base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
         for (uint32_t k = 0; k < wave; ++k) p += s_count[par][k];
-        if (KIND == 0) {
+        if (KIND == 0 || KIND == 3) {
             if (j < n) { aux[j] = j - p; if (j + 1u == n) aux[n] = n - p - (alive ? 1u : 0u); }
             if (alive && p < outCount) {
                 const float4* r = (const float4*)src + (size_t)j * 3; float4* w = (float4*)out + (size_t)p * 3;
-                float4 c2 = r[2]; c2.y = __int_as_float((int)(tri - shift));
+                float4 c2 = r[2]; if (KIND == 0) c2.y = __int_as_float((int)(tri - shift));
                 w[0] = r[0]; w[1] = r[1]; w[2] = c2;
             }
         } else if (KIND == 1) {
@@ -290,19 +292,19 @@ template <int QUADS, bool REMAP, class T> static int prune_stream(fyprt_context*
     return FYPRT_OK;
 }
 
-// The removal proper, after every check: `tris` / `verts` the removed triangle and vertex intervals, `gone[m]` the listed meshes.
-static int prune_remove(fyprt_context* c, const PruneTable& tris, const PruneTable& verts, const std::vector<uint8_t>& gone) {
+// The tree's part of a removal, shared with fyprt_regraft_meshes (`who`: the caller's name for error texts): the leaf records whose triangle
+// lies in `tris` leave the tree, the nodes follow by the prune rule.  `renumber`: the triangles leave the scene as well, so the surviving
+// records' triangle indices are remapped (a removal); otherwise survivors keep every byte (a regraft).  `dTab`: the table on the device,
+// `counts`: the compactions' counts + offsets.  Leaves the compacted leaf records and node array (old boxes and planes) on the device and
+// in the host's copy, and in `refit` / `refitLevel` what prune_refit is to run on once the per-triangle streams are in place.
+static int prune_tree(fyprt_context* c, const char* who, const PruneTable& tris, bool renumber, const uint2* dTab, DevBuf<uint32_t>& counts,
+                      std::vector<uint32_t>& refit, std::vector<uint32_t>& refitLevel) {
     rth::SceneBVH& hb = c->hostBvh;
-    const uint32_t T0 = (uint32_t)(c->topoTris.size() / 4), V0 = c->vertexCount, M0 = (uint32_t)c->topoMeshes.size();
-    const uint32_t T = T0 - tris.removed, V = V0 - verts.removed;
-    const uint32_t nLeaf = (uint32_t)hb.tris.size(), nNodes = (uint32_t)hb.nodes.size();
+    const uint32_t nLeaf = (uint32_t)hb.tris.size(), nNodes = (uint32_t)hb.nodes.size(), T = nLeaf - tris.removed;
     const bool dev = !c->hostOnly;
-    c->linksValid = false;                     // nodes, records and triangles are renumbered: the partial refit's maps are rebuilt
-    // device scratch of the call, freed on every way out: the two tables, the compactions' counts + offsets, the node pass's arrays
-    DevBuf<uint2> dTab, dVtab; DevBuf<uint32_t> counts, deadBeforeDev, alive, newIndex, refitList; DevBuf<int32_t> repl;
+    c->linksValid = false;                     // nodes and records are renumbered: the partial refit's maps are rebuilt
+    DevBuf<uint32_t> deadBeforeDev, alive, newIndex; DevBuf<int32_t> repl;      // the node pass's arrays, freed on every way out
     if (dev) {
-        TRY(alloc_upload(c, dTab, tris.tab.data(), tris.tab.size())); TRY(alloc_upload(c, dVtab, verts.tab.data(), verts.tab.size()));
-        HIPCHK(c, counts.alloc(2u * kEmMaxGroups + 1u));
         // exact boxes of a tree no refit pass has run on (the old grouping describes it): what k_refit_level reads of untouched children
         if (!c->nodeBoxValid && nNodes) {
             for (uint32_t l = 1; l + 1u < (uint32_t)c->levelOffset.size(); ++l) {
@@ -318,9 +320,10 @@ static int prune_remove(fyprt_context* c, const PruneTable& tris, const PruneTab
         DevBuf<float4> nl;
         HIPCHK(c, nl.alloc(c->leafTris.cap)); HIPCHK(c, deadBeforeDev.alloc((size_t)nLeaf + 1u));
         uint32_t kept = 0;
-        TRY(prune_compact<0>(c, c->leafTris.p, nLeaf, dTab.p, tris.K, nl.p, (uint32_t)(nl.cap / 3), deadBeforeDev.p, counts, &kept));
+        if (renumber) TRY(prune_compact<0>(c, c->leafTris.p, nLeaf, dTab, tris.K, nl.p, (uint32_t)(nl.cap / 3), deadBeforeDev.p, counts, &kept));
+        else TRY(prune_compact<3>(c, c->leafTris.p, nLeaf, dTab, tris.K, nl.p, (uint32_t)(nl.cap / 3), deadBeforeDev.p, counts, &kept));
         if (nLeaf) HIPCHK(c, hipMemcpy(deadBefore.data(), deadBeforeDev.p, ((size_t)nLeaf + 1u) * 4, hipMemcpyDeviceToHost));
-        if (kept != T || deadBefore[nLeaf] != tris.removed) return c->fail(FYPRT_EHIP, "fyprt_remove_meshes: the device's leaf records disagree with the host's triangle ranges");
+        if (kept != T || deadBefore[nLeaf] != tris.removed) return c->fail(FYPRT_EHIP, std::string(who) + ": the device's leaf records disagree with the host's triangle ranges");
         // 2. the node pass on the old array, level by level, then the alive scan and the move
         if (nNodes) {
             HIPCHK(c, repl.alloc(nNodes)); HIPCHK(c, alive.alloc(nNodes)); HIPCHK(c, newIndex.alloc(nNodes));
@@ -337,12 +340,11 @@ static int prune_remove(fyprt_context* c, const PruneTable& tris, const PruneTab
         for (uint32_t j = 0; j < nLeaf; ++j) {
             uint32_t shift; deadBefore[j] = j - w;
             if (tris.dead(hb.tris[j].tri, shift)) continue;
-            rth::Tri t = hb.tris[j]; t.tri -= shift; hb.tris[w++] = t;
+            rth::Tri t = hb.tris[j]; if (renumber) t.tri -= shift; hb.tris[w++] = t;
         }
         deadBefore[nLeaf] = nLeaf - w;
         c->leafTris.n = c->leafTris.cap = (size_t)w * 3;
     }
-    std::vector<uint32_t> refit, refitLevel;
     prune_host_tree(hb, deadBefore, refit, refitLevel);
     hb.tris.resize(T);
     const uint32_t nNew = (uint32_t)hb.nodes.size();
@@ -351,13 +353,61 @@ static int prune_remove(fyprt_context* c, const PruneTable& tris, const PruneTab
         HIPCHK(c, nn.alloc(c->nodes.cap)); HIPCHK(c, nbx.alloc(c->nodeBox.cap));
         uint32_t keptNodes = 0;
         TRY(prune_compact<2>(c, alive.p, nNodes, nullptr, 0u, nullptr, 0u, newIndex.p, counts, &keptNodes));
-        if (keptNodes != nNew) return c->fail(FYPRT_EHIP, "fyprt_remove_meshes: the device's node pass disagrees with the host's");
+        if (keptNodes != nNew) return c->fail(FYPRT_EHIP, std::string(who) + ": the device's node pass disagrees with the host's");
         hipLaunchKernelGGL(k_prune_move, dim3((nNodes * 4u + kBlock - 1u) / kBlock), dim3(kBlock), 0, c->stream, (const float4*)c->nodes.p, nn.p, (const float4*)c->nodeBox.p, nbx.p, (const uint32_t*)alive.p, (const uint32_t*)newIndex.p, nNodes);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
         nn.n = (size_t)nNew * 4; nbx.n = (size_t)nNew * 2;
         c->nodes = std::move(nn); c->nodeBox = std::move(nbx);
     } else if (!dev) { c->nodes.n = c->nodes.cap = (size_t)nNew * 4; c->nodeBox.n = c->nodeBox.cap = (size_t)nNew * 2; }
+    return FYPRT_OK;
+}
+
+// ... and its last step, once the surviving records' triangles are where the records say: boxes and quantisation of the surviving nodes
+// that lost a triangle below them, lowest level first, then the level grouping of the pruned tree.  Complete on return.
+static int prune_refit(fyprt_context* c, const std::vector<uint32_t>& refit, const std::vector<uint32_t>& refitLevel) {
+    rth::SceneBVH& hb = c->hostBvh;
+    if (!c->hostOnly) {
+        DevBuf<uint32_t> refitList;
+        if (!refit.empty()) {
+            TRY(alloc_upload(c, refitList, refit.data(), refit.size()));
+            for (size_t l = 1; l + 1 < refitLevel.size(); ++l) {
+                const uint32_t first = refitLevel[l], count = refitLevel[l + 1] - first;
+                if (count) hipLaunchKernelGGL(k_refit_level, dim3((count + 127u) / 128u), dim3(128), 0, c->stream, c->nodes.p, (const uint32_t*)(refitList.p + first), count, (const float4*)c->leafTris.p, (const float4*)c->triPos.p, c->nodeBox.p);
+            }
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipStreamSynchronize(c->stream));                  // the list is scratch of this step
+        }
+        c->nodeBoxValid = true; c->hostBvhStale = true;               // planes and leaf records live on the device: an export reads them back
+    } else {
+        for (uint32_t i : refit) {
+            rth::Node& n = hb.nodes[i];
+            const uint32_t k = n.meta & 7u; const uint8_t meta = n.meta;
+            rth::ChildBox boxes[4]; int32_t child[4];
+            for (uint32_t s = 0; s < 4; ++s) { child[s] = n.child[s]; if (s < k) boxes[s] = graft_host_box(c, n.child[s]); }
+            rth::QuantiseNode(n, boxes, (int)k);
+            for (uint32_t s = 0; s < 4; ++s) n.child[s] = s < k ? child[s] : INT32_MIN;
+            n.meta = meta;
+        }
+    }
+    return upload_level_grouping(c, true);
+}
+
+// The removal proper, after every check: `tris` / `verts` the removed triangle and vertex intervals, `gone[m]` the listed meshes.
+static int prune_remove(fyprt_context* c, const PruneTable& tris, const PruneTable& verts, const std::vector<uint8_t>& gone) {
+    rth::SceneBVH& hb = c->hostBvh;
+    const uint32_t T0 = (uint32_t)(c->topoTris.size() / 4), V0 = c->vertexCount, M0 = (uint32_t)c->topoMeshes.size();
+    const uint32_t T = T0 - tris.removed, V = V0 - verts.removed;
+    const bool dev = !c->hostOnly;
+    // device scratch of the call, freed on every way out: the two tables, the compactions' counts + offsets
+    DevBuf<uint2> dTab, dVtab; DevBuf<uint32_t> counts;
+    if (dev) {
+        TRY(alloc_upload(c, dTab, tris.tab.data(), tris.tab.size())); TRY(alloc_upload(c, dVtab, verts.tab.data(), verts.tab.size()));
+        HIPCHK(c, counts.alloc(2u * kEmMaxGroups + 1u));
+    }
+    // 1. leaf records and 2. the node pass
+    std::vector<uint32_t> refit, refitLevel;
+    TRY(prune_tree(c, "fyprt_remove_meshes", tris, true, dTab.p, counts, refit, refitLevel));
     // 3. the per-triangle and per-vertex streams
     TRY((prune_stream<1, true>(c, c->triIdx, T0, T, dTab.p, tris.K, dVtab.p, verts.K)));
     TRY((prune_stream<3, false>(c, c->triPos, T0, T, dTab.p, tris.K, nullptr, 0u)));
@@ -396,28 +446,7 @@ static int prune_remove(fyprt_context* c, const PruneTable& tris, const PruneTab
         c->vertexCount = V; c->meshCount = w;
     }
     // 5. boxes and quantisation of the surviving nodes that lost a triangle below them, lowest level first
-    if (dev) {
-        if (!refit.empty()) {
-            TRY(alloc_upload(c, refitList, refit.data(), refit.size()));
-            for (size_t l = 1; l + 1 < refitLevel.size(); ++l) {
-                const uint32_t first = refitLevel[l], count = refitLevel[l + 1] - first;
-                if (count) hipLaunchKernelGGL(k_refit_level, dim3((count + 127u) / 128u), dim3(128), 0, c->stream, c->nodes.p, (const uint32_t*)(refitList.p + first), count, (const float4*)c->leafTris.p, (const float4*)c->triPos.p, c->nodeBox.p);
-            }
-            HIPCHK(c, hipGetLastError());
-        }
-        c->nodeBoxValid = true; c->hostBvhStale = true;               // planes and leaf records live on the device: an export reads them back
-    } else {
-        for (uint32_t i : refit) {
-            rth::Node& n = hb.nodes[i];
-            const uint32_t k = n.meta & 7u; const uint8_t meta = n.meta;
-            rth::ChildBox boxes[4]; int32_t child[4];
-            for (uint32_t s = 0; s < 4; ++s) { child[s] = n.child[s]; if (s < k) boxes[s] = graft_host_box(c, n.child[s]); }
-            rth::QuantiseNode(n, boxes, (int)k);
-            for (uint32_t s = 0; s < 4; ++s) n.child[s] = s < k ? child[s] : INT32_MIN;
-            n.meta = meta;
-        }
-    }
-    TRY(upload_level_grouping(c, true));
+    TRY(prune_refit(c, refit, refitLevel));
     DevScene& d = c->dsc;
     d.nodes = c->nodes.p; d.leafTris = c->leafTris.p; d.rootRef = rth::device_ref(hb.rootRef); d.triCount = T;
     d.triPos = c->triPos.p; d.triShade = c->triShade.p;

@@ -145,6 +145,21 @@ public:
     }
     uint32_t GetSceneRemoveCount() const { return m_Removes; }
 
+    // New (no reference counterpart): meshes that were moved far are taken out of the tree and linked in again where they lie now
+    // (fyprt_regraft_meshes) — call it after the Render() that applied their transform edits.  Only the tree moves: the scene, its
+    // signatures and the frame state stay as they are.  Returns one report per listed mesh; empty when the library refuses or no scene
+    // is on the device yet.  TreeCost() is what tells when it pays: (inner_area + leaf_area) / root_area rises as the tree degrades.
+    std::vector<fyprt_append_placement> RegraftMeshes(const std::vector<uint32_t>& indices) {
+        std::vector<fyprt_append_placement> reports(indices.size());
+        if (!m_HaveScene || report(fyprt_regraft_meshes(m_Ctx, indices.data(), (uint32_t)indices.size(), reports.data()), "fyprt_regraft_meshes")) reports.clear();
+        return reports;
+    }
+    fyprt_tree_cost_sums TreeCost() {
+        fyprt_tree_cost_sums cost{};
+        if (m_HaveScene) report(fyprt_tree_cost(m_Ctx, &cost), "fyprt_tree_cost");
+        return cost;
+    }
+
     void ResetFrameIndex() { fyprt_reset_frame_index(m_Ctx); }
     RenderingSettings& GetSettings() { return m_Settings; }
     uint32_t GetCurrentFrameIndex() const { return fyprt_frame_index(m_Ctx); }

@@ -392,6 +392,63 @@ int fyprt_last_append_placement(fyprt_context* ctx, fyprt_append_placement* out)
  * scene is per context: call it on every member of a group or communicator between frames. */
 int fyprt_remove_meshes(fyprt_context* ctx, const uint32_t* mesh_indices, uint32_t mesh_count,
                         const uint32_t* vertex_ranges /* NULL, or 2 * mesh_count: (first, count) per listed mesh */);
+/* Regraft: the listed meshes are taken out of the tree and linked in again where they lie NOW.  New (no reference counterpart).  The
+ * geometry edits (fyprt_update_transforms, fyprt_update_vertices, fyprt_update_mesh_vertices) refit boxes only: a mesh that was moved across
+ * the scene keeps its leaf records under the nodes of its old neighbourhood, every ancestor's box spans both places and every ray through
+ * the gap visits them.  This call repairs the tree without fyprt_upload_scene: nothing but the tree moves.  `mesh_indices`: mesh_count
+ * distinct mesh indices; `reports`: NULL, or mesh_count entries.
+ * 1. Tree-only prune.  The prune rule of fyprt_remove_meshes, exactly as stated there, with this dead set: every leaf record whose triangle
+ *    lies in a listed mesh's range [first_triangle, first_triangle + triangle_count).  No triangle leaves the scene, so no triangle is
+ *    renumbered: surviving leaf records keep EVERY byte.  Leaf codes, the node pass by level, splices, the stable compaction of the node array,
+ *    rebased references, the refit of just the nodes that lost something and the level grouping are a removal's.
+ * 2. One graft per listed mesh, in the order listed: the graft of fyprt_append_meshes for that mesh's triangle range, as if the mesh had
+ *    just been appended.  Sub-tree by the builder of tuning key 12 (the device builders from five triangles on, otherwise the host builder);
+ *    the device builders' Morton grid is the exact box B of the mesh's triangles (the box of the vertices an append would have passed when the
+ *    mesh uses all of its vertices).  The sub-tree's nodes go behind the old nodes, its leaf records behind the old records (the record array
+ *    ends at the triangle count again), linked by the placement mode in effect (fyprt_set_append_placement: 0 at the root, 1 at the cheapest
+ *    place); the new nodes and the path are refitted as in an append.  reports[k] is the fyprt_append_placement of the graft of
+ *    mesh_indices[k].  A graft that answers "rebuild" (too deep, node range) rebuilds the whole tree as fyprt_upload_scene builds it: this
+ *    and every remaining report then say kind 4.  A listed mesh without triangles is skipped, its report is zero apart from `mode`.  After
+ *    device transform edits the host's vertex copy is refreshed from the device first, as fyprt_append_meshes refreshes it.
+ * 3. Nothing else moves: the per-triangle and per-vertex streams, materials, the emissive list, light records and light trees, the
+ *    object-space copy, frame index, accumulation, reservoirs and ReSTIR history, fyprt_last_append_placement and fyprt_last_edit_stats are
+ *    untouched.  The last frame stays denoisable; the temporal history and a pending motion snapshot are kept (the payload's triangle indices
+ *    and every world position are what they were).  Only the partial refit's parent links are invalidated.  Every later frame and query
+ *    equals the one before the call bit for bit, except where two triangles are hit at exactly the same t — the promise of any valid tree.
+ * Consequence: the tree after the call is the tree of a twin context that removed the listed meshes in ONE fyprt_remove_meshes and appended
+ * them again, one call each in the listed order, under the same tuning key 12 and placement mode: nodes64 equal byte for byte, tris48 equal
+ * in every byte except triangleIndex, which maps through the twin's renumbering, and reports[k] equal to the twin's
+ * fyprt_last_append_placement after its k-th append.  (The device builders hand out node indices by atomic counters, so two builds of one
+ * tree differ in the numbering of their nodes and leaf records: with tuning key 12 = 1 or 2 "equal" is up to that numbering.)
+ * Memory: the prune compacts into buffers of the same capacity and frees its scratch; the kept scratch of an append (graft list, parent
+ * links, search result) is left at the size it had.  fyprt_live_device_bytes returns to its value before the call unless the regrafted
+ * tree has more nodes than the node arrays' capacity, which then at least doubles as in an append.
+ * Blocking: pipelined frames are waited for first, everything the call launches is complete on return.  Errors, in this order: FYPRT_EINVAL
+ * for a NULL context, NULL mesh_indices with a non-zero count, a mesh index out of range, a mesh listed twice; FYPRT_ESTATE before
+ * fyprt_upload_scene.  Scenes with prebuilt light trees are allowed (the light trees are not touched).  A failed check changes nothing.
+ * mesh_count == 0 returns FYPRT_OK and changes nothing.  Host-only contexts are supported (everything but the device work).  The scene is
+ * per context: regraft the members of a group or communicator one by one between frames. */
+int fyprt_regraft_meshes(fyprt_context* ctx, const uint32_t* mesh_indices, uint32_t mesh_count,
+                         fyprt_append_placement* reports /* NULL, or mesh_count entries */);
+/* Surface-area cost of the tree as it is.  New (no reference counterpart).  Reads the tree, changes nothing: what tells an application that
+ * a moved mesh should be regrafted.  A, b(Y) and the exact leaf boxes are those of the placement rule above: A in binary32, every operation
+ * rounded on its own, no contraction; exact boxes from the triangles' world vertices.  Each term is converted to binary64 and summed in
+ * binary64.  (inner_area + leaf_area) / root_area is the usual SAH estimate; the caller forms it.
+ * On a device one thread per node computes the terms, workgroups reduce them in a fixed order into one pair of sums each, and the host adds
+ * the pairs in workgroup order: no floating-point atomics, so two calls on the same tree return the same bits.  A host-only context adds the
+ * same terms in node order; the two agree within 2^-26 relative (at most 2^26 non-negative terms: any summation order is within
+ * (n - 1) * 2^-53 <= 2^-27 relative of the exact sum).  The partial sums' buffer (16 bytes per 256 nodes) is kept and counted by
+ * fyprt_live_device_bytes; a tree no refit has run on gets the pass that fills every node's exact box first.
+ * Blocking: pipelined frames are waited for first.  Errors, in this order: FYPRT_EINVAL for NULL arguments; FYPRT_ESTATE before
+ * fyprt_upload_scene. */
+typedef struct fyprt_tree_cost_sums {
+    double root_area;      /* (double) A(b(R)); of a leaf-code root its exact leaf box; 0 for an empty tree */
+    double inner_area;     /* sum over inner nodes Y of (double) A(b(Y)) */
+    double leaf_area;      /* sum over leaf children (first, n) of n * (double) A(exact box of those n triangles); a leaf-code root counts
+                              as the one leaf child */
+    uint32_t nodes, leaf_children, leaf_records, levels;
+} fyprt_tree_cost_sums;
+int fyprt_tree_cost(fyprt_context* ctx, fyprt_tree_cost_sums* out);
 /* "Import Texture" — WalnutApp.cpp:739-754 -> Scene::CreateNewTextureInScene (Scene.cpp:228-239): the new pixel arrays are uploaded and the
  * texture table is extended; old pixel buffers stay where they are.  The context is then, bit for bit, one that uploaded the scene with the
  * longer list.  Acceleration structure, frame state and temporal history are untouched and the last frame stays denoisable — unless a
