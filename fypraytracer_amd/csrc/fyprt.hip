@@ -493,15 +493,18 @@ static int download_nodes(fyprt_context* c) {
     return FYPRT_OK;
 }
 
+}  // extern "C"
+// what the builders below and the tree edits share
+#include "rt_tree_host.h"
+extern "C" {
 // the refit pass over the whole tree (rt_refit.h): leaf triangles from the per-triangle positions, then boxes + quantisation
-// level by level, bottom level first
+// level by level, bottom level first (the grouping's levels are the tree's: upload_level_grouping)
 static int run_refit(fyprt_context* c) {
-    const uint32_t nLeaf = (uint32_t)c->hostBvh.tris.size(), nNodes = (uint32_t)c->hostBvh.nodes.size();
+    const uint32_t nLeaf = (uint32_t)c->hostBvh.tris.size();
     if (nLeaf) hipLaunchKernelGGL(k_refresh_leaf_tris, dim3((nLeaf + 255u) / 256u), dim3(256), 0, c->stream, c->triPos.p, c->leafTris.p, nLeaf);
-    for (uint32_t l = 1; nNodes && l <= c->hostBvh.levels; ++l) {
-        const uint32_t first = c->levelOffset[l], count = c->levelOffset[l + 1] - first;
-        if (count) hipLaunchKernelGGL(k_refit_level, dim3((count + 127u) / 128u), dim3(128), 0, c->stream, c->nodes.p, c->levelNodes.p + first, count, c->leafTris.p, c->triPos.p, c->nodeBox.p);
-    }
+    for_each_level(c->levelOffset, [&](uint32_t first, uint32_t count, dim3 grid) {
+        hipLaunchKernelGGL(k_refit_level, grid, dim3(kLevelBlock), 0, c->stream, c->nodes.p, c->levelNodes.p + first, count, c->leafTris.p, c->triPos.p, c->nodeBox.p);
+    });
     HIPCHK(c, hipGetLastError());
     c->nodeBoxValid = true;
     return FYPRT_OK;
@@ -517,8 +520,9 @@ constexpr int kLbvhTooDeep = -1000;
 struct LbvhTree { uint32_t nodes = 0, levels = 0; };
 static int env_int(const char* name, int fallback) { const char* v = std::getenv(name); return (v && *v) ? std::atoi(v) : fallback; }
 static int build_device_lbvh(fyprt_context* c, const fyprt_vertex* verts, uint32_t nV, uint32_t firstTri, uint32_t nT, bool ploc, size_t leafBase, DevBuf<float4>& wide, LbvhTree* tree) {
-    float lo[3] = {3.402823466e+38f, 3.402823466e+38f, 3.402823466e+38f}, hi[3] = {-3.402823466e+38f, -3.402823466e+38f, -3.402823466e+38f};
-    for (uint32_t i = 0; i < nV; ++i) for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], verts[i].position[a]); hi[a] = std::max(hi[a], verts[i].position[a]); }
+    rth::HostBox grid;
+    for (uint32_t i = 0; i < nV; ++i) grid.grow(verts[i].position);
+    const float *lo = grid.lo, *hi = grid.hi;
     float3 l3 = make_float3(lo[0], lo[1], lo[2]), ie = make_float3(hi[0] > lo[0] ? 1.0f / (hi[0] - lo[0]) : 0.0f, hi[1] > lo[1] ? 1.0f / (hi[1] - lo[1]) : 0.0f, hi[2] > lo[2] ? 1.0f / (hi[2] - lo[2]) : 0.0f);
     // scratch of the build, freed on every way out
     DevBuf<unsigned long long> keysA, keysB; DevBuf<uint32_t> valsA, valsB, parentOfNode, parentOfLeaf, arrived; DevBuf<float> box; DevBuf<RadixNode> radix; DevBuf<CollapseItem> qA, qB; DevBuf<uint32_t> counters; DevBuf<uint8_t> temp;
@@ -622,21 +626,6 @@ static int upload_light_trees(fyprt_context* c, uint32_t nT, uint32_t nM) {
     d.ltLeafOfTri = c->ltLeafOfTri.p; d.ltTlas = c->ltTlas.p; d.ltTlasCount = (uint32_t)lt.tlas.size(); d.ltTlasRoot = lt.tlasRoot;
     d.ltBlas = c->ltBlas.p; d.ltFirst = c->ltFirst.p; d.ltCount = c->ltCount.p; d.ltRoot = c->ltRoot.p;
     return FYPRT_OK;
-}
-
-// The nodes of the host's copy of the tree grouped by level (levels = 1 first) for the refit pass: c->levelOffset and, on the device,
-// c->levelNodes — 4 bytes per node.  `keep`: the buffer grows within its capacity (an append) instead of being allocated to size.
-static int upload_level_grouping(fyprt_context* c, bool keep) {
-    const std::vector<rth::Node>& hn = c->hostBvh.nodes;
-    const uint32_t L = c->hostBvh.levels;
-    c->levelOffset.assign(L + 2, 0);
-    for (const rth::Node& n : hn) c->levelOffset[(n.meta >> 3) + 1]++;
-    for (uint32_t l = 1; l <= L + 1; ++l) c->levelOffset[l] += c->levelOffset[l - 1];      // levelOffset[l] = first slot of level l (1-based levels)
-    std::vector<uint32_t> order(hn.size()), fill(c->levelOffset.begin(), c->levelOffset.end());
-    for (uint32_t i = 0; i < (uint32_t)hn.size(); ++i) order[fill[hn[i].meta >> 3]++] = i;
-    if (!keep) return alloc_upload(c, c->levelNodes, order.data(), order.size());
-    TRY(grow_buffer(c, c->levelNodes, order.size(), false));
-    return upload(c, c->levelNodes.p, order.data(), c->levelNodes.bytes());
 }
 
 // The acceleration structure of the scene whose per-triangle records are on the device (c->triPos): built on the host (binned SAH +
@@ -769,18 +758,15 @@ int fyprt_upload_scene(fyprt_context* c, const fyprt_scene_desc* s) {
     }
     TRY(upload_light_trees(c, nT, s->mesh_count));
     DevScene& d = c->dsc;
-    d.nodes = c->nodes.p; d.leafTris = c->leafTris.p; d.rootRef = rth::device_ref(c->hostBvh.rootRef); d.triCount = nT;
-    d.triPos = c->triPos.p; d.triShade = c->triShade.p; d.mats = c->mats.p; d.textures = c->texTable.p; d.textureCount = s->texture_count;
+    set_scene_triangles(c, nT);
+    d.mats = c->mats.p; d.textures = c->texTable.p; d.textureCount = s->texture_count;
     d.emissive = c->emissive.p; d.emissiveCount = (uint32_t)em.size();
     d.rayCounter = nullptr; d.topCount = 0u; d.stackBudget = 0; d.nodeQuorum = 0u;     // per launch: every launch sets them on its own copy
     // per-light records for ReSTIR DI, computed on the device with the kernels' own arithmetic
     HIPCHK(c, c->lightRecs.alloc(em.size() * 3, c->hostOnly));
     d.lightRecs = c->lightRecs.p;
-    if (!c->hostOnly && !em.empty()) {
-        hipLaunchKernelGGL(k_build_light_records, dim3(((uint32_t)em.size() + 255u) / 256u), dim3(256), 0, c->stream, d, c->lightRecs.p);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, sync_all(c));
-    }
+    TRY(launch_light_records(c));
+    if (!c->hostOnly && !em.empty()) HIPCHK(c, sync_all(c));
     c->hostEmissive.swap(em);
     c->haveScene = true;
     return FYPRT_OK;
@@ -817,32 +803,89 @@ static void temporal_edit_range(fyprt_context* c, uint32_t firstTri, uint32_t tr
     c->dtEditHi = empty ? firstTri + triCount : std::max(c->dtEditHi, firstTri + triCount);
 }
 
-static void full_edit_stats(fyprt_context* c);        // rt_partial.h
+}  // extern "C"
+// the tree's part of the scene edits: graft (append, regraft), partial refit (geometry edits), prune (removal, regraft), surface-area cost
+#include "rt_partial.h"
+#include "rt_graft.h"
+#include "rt_prune.h"
+#include "rt_treecost.h"
+extern "C" {
+
+// ---- what the edit entry points below share
+// The state an edit needs, asked for flag by flag and checked in this order; `who`: the entry point's name, which starts every text.
+// Argument checks stay with the entry points, each of which keeps its own order of the two kinds.
+enum : unsigned { kNeedScene = 1u, kNeedSceneAndRanges = 2u, kNeedRanges = 4u, kNeedOwnLightTrees = 8u, kNeedDevice = 16u };
+static int edit_check_state(fyprt_context* c, const char* who, unsigned needs) {
+    auto refuse = [&](const char* why) { return c->fail(FYPRT_ESTATE, std::string(who) + why); };
+    if ((needs & kNeedScene) && !c->haveScene) return refuse(" before fyprt_upload_scene");
+    if ((needs & kNeedSceneAndRanges) && (!c->haveScene || c->meshFirstVertex.empty())) return refuse(" before fyprt_upload_scene + fyprt_set_object_vertices");
+    if ((needs & kNeedRanges) && c->meshFirstVertex.empty()) return refuse(" needs the mesh vertex ranges of fyprt_set_object_vertices");
+    if ((needs & kNeedOwnLightTrees) && c->prebuiltLightTrees) return refuse(": the scene was uploaded with prebuilt light trees; upload it again instead");
+    if ((needs & kNeedDevice) && c->hostOnly) return refuse(" needs a device (host-only context)");
+    return FYPRT_OK;
+}
+// An edit begins, every check passed: all streams idle, and what the edit means to the last frame and to the temporal denoiser's history.
+// kEditGeometry: the history stays under motion (temporal_edit_begin); kEditShading: it goes; kEditTopology: it goes with the snapshot;
+// kEditTreeOnly: neither the frame nor the history is touched (the tree moves, what it holds does not).
+enum EditKind { kEditGeometry, kEditShading, kEditTopology, kEditTreeOnly };
+static int edit_begin(fyprt_context* c, EditKind kind) {
+    if (!c->hostOnly) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c)); }
+    if (kind == kEditTreeOnly) return FYPRT_OK;
+    c->frameComplete = false;                  // the payload's triangles, texture coordinates and materials are the old scene's (fyprt_denoise)
+    if (kind == kEditGeometry) return temporal_edit_begin(c);
+    c->drop_history(); if (kind == kEditTopology) c->release_snapshot();
+    return FYPRT_OK;
+}
+// A list of `n` mesh indices: every index in range, and (`distinct` == NULL) no mesh listed twice.  `listed`: NULL or a mark per mesh
+// of the scene; `distinct`: NULL or the listed meshes once each, in the order of their first entry.
+static int check_mesh_list(fyprt_context* c, const char* who, const uint32_t* indices, uint32_t n, std::vector<uint8_t>* listed, std::vector<uint32_t>* distinct = nullptr) {
+    const uint32_t nM = (uint32_t)c->topoMeshes.size();
+    for (uint32_t k = 0; k < n; ++k) if (indices[k] >= nM) return c->fail(FYPRT_EINVAL, std::string(who) + ": mesh index out of range");
+    if (!listed) return FYPRT_OK;
+    listed->assign(nM, 0);
+    for (uint32_t k = 0; k < n; ++k) {
+        uint8_t& mark = (*listed)[indices[k]];
+        if (mark && !distinct) return c->fail(FYPRT_EINVAL, std::string(who) + ": mesh " + std::to_string(indices[k]) + " is listed twice");
+        if (!mark && distinct) distinct->push_back(indices[k]);
+        mark = 1;
+    }
+    return FYPRT_OK;
+}
+// The tail of a geometry edit whose records and tree are enqueued: the light trees of the emissive meshes that moved (`touched`, a mark
+// per mesh; NULL: all of them) from the host's vertices — `waitForReadback`: which the context stream is still bringing back —, the light
+// records, and the edit complete on return.
+static int finish_geometry_edit(fyprt_context* c, const uint8_t* touched, bool lightsMoved, bool waitForReadback) {
+    c->hostBvhStale = true;
+    if (lightsMoved && waitForReadback) HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (lightsMoved) TRY(rebuild_light_trees(c, c->hostVerts.data(), touched));
+    TRY(launch_light_records(c));
+    HIPCHK(c, sync_all(c));
+    partial_finish_stats(c);
+    return FYPRT_OK;
+}
 
 // Scene geometry moved, topology unchanged (SceneManager::PerformAllSceneUpdates with a transform edit, SceneManager.cpp:24-66):
 // new world vertices -> per-triangle records, leaf triangles and the tree's boxes are refreshed ON THE DEVICE (rt_refit.h),
 // the per-light records are rebuilt by their kernel, the (small) light trees on the host.  The tree keeps its shape.
 int fyprt_update_vertices(fyprt_context* c, const fyprt_vertex* vertices, uint32_t vertex_count) {
     if (!c || !vertices) return FYPRT_EINVAL;
-    if (!c->haveScene) return c->fail(FYPRT_ESTATE, "fyprt_update_vertices before fyprt_upload_scene");
+    TRY(edit_check_state(c, "fyprt_update_vertices", kNeedScene));
     if (vertex_count != c->vertexCount) return c->fail(FYPRT_EINVAL, "fyprt_update_vertices: vertex count differs from the uploaded scene");
-    if (c->hostOnly) return c->fail(FYPRT_ESTATE, "fyprt_update_vertices needs a device (host-only context)");
-    if (c->prebuiltLightTrees) return c->fail(FYPRT_ESTATE, "fyprt_update_vertices: the scene was uploaded with prebuilt light trees; upload it again instead");
-    HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c));
-    c->frameComplete = false;                  // new vertices may carry new texture coordinates: the last frame can no longer be denoised
+    TRY(edit_check_state(c, "fyprt_update_vertices", kNeedDevice));
+    TRY(edit_check_state(c, "fyprt_update_vertices", kNeedOwnLightTrees));
+    TRY(edit_begin(c, kEditGeometry));
     const uint32_t nT = (uint32_t)(c->topoTris.size() / 4);
-    TRY(temporal_edit_begin(c)); temporal_edit_range(c, 0, nT);
+    temporal_edit_range(c, 0, nT);
     // the upload below is a blocking copy, which the non-blocking context stream does not order: the snapshot must have read dverts first
     if (c->dtSnapPending) HIPCHK(c, hipStreamSynchronize(c->stream));
     if (upload(c, c->dverts.p, vertices, c->dverts.bytes())) return FYPRT_EHIP;
     c->hostVerts.assign(vertices, vertices + vertex_count); c->hostVertsStale = false;
-    if (nT) hipLaunchKernelGGL(k_refresh_triangles, dim3((nT + 255u) / 256u), dim3(256), 0, c->stream, c->dverts.p, c->triIdx.p, c->triPos.p, c->triShade.p, nT);
+    TRY(launch_refresh_triangles(c, 0, nT));
     TRY(run_refit(c));
     full_edit_stats(c);
     c->hostBvhStale = true;
-    TRY(rebuild_light_trees(c, vertices));
-    if (c->dsc.emissiveCount) hipLaunchKernelGGL(k_build_light_records, dim3((c->dsc.emissiveCount + 255u) / 256u), dim3(256), 0, c->stream, c->dsc, c->lightRecs.p);
-    HIPCHK(c, hipGetLastError());
+    TRY(rebuild_light_trees(c, vertices));                      // every light tree, from the caller's array
+    TRY(launch_light_records(c));
     HIPCHK(c, sync_all(c));
     return FYPRT_OK;
 }
@@ -850,8 +893,7 @@ int fyprt_update_vertices(fyprt_context* c, const fyprt_vertex* vertices, uint32
 // Object-space vertices (Scene::vertices) and the meshes' vertex ranges, kept on the device so that a transform edit can be applied there.
 int fyprt_set_object_vertices(fyprt_context* c, const fyprt_vertex* object_vertices, uint32_t vertex_count, const uint32_t* mesh_first_vertex) {
     if (!c || !object_vertices || !mesh_first_vertex) return FYPRT_EINVAL;
-    if (!c->haveScene) return c->fail(FYPRT_ESTATE, "fyprt_set_object_vertices before fyprt_upload_scene");
-    if (c->hostOnly) return c->fail(FYPRT_ESTATE, "fyprt_set_object_vertices needs a device (host-only context)");
+    TRY(edit_check_state(c, "fyprt_set_object_vertices", kNeedScene | kNeedDevice));
     if (vertex_count != c->vertexCount) return c->fail(FYPRT_EINVAL, "fyprt_set_object_vertices: vertex count differs from the uploaded scene");
     const uint32_t nM = (uint32_t)c->topoMeshes.size();
     for (uint32_t m = 0; m < nM; ++m) if (mesh_first_vertex[m] > mesh_first_vertex[m + 1] || mesh_first_vertex[m + 1] > vertex_count) return c->fail(FYPRT_EINVAL, "fyprt_set_object_vertices: mesh vertex ranges out of order / out of range");
@@ -865,9 +907,6 @@ int fyprt_set_object_vertices(fyprt_context* c, const fyprt_vertex* object_verti
     return FYPRT_OK;
 }
 
-// Geometry edits at the cost of what moved: the walk from the moved triangles up to the root
-#include "rt_partial.h"
-
 // A transform edit of `count` meshes (SceneManager::PerformAllSceneUpdates with meshTransformToBeUpdated, SceneManager.cpp:24-66): 64
 // bytes per mesh cross the bus; the world vertices are recomputed on the device (k_transform_vertices), per-triangle records, leaf
 // triangles, tree boxes and light records refreshed there, and only the moved EMISSIVE meshes' light trees are rebuilt on the host
@@ -875,45 +914,33 @@ int fyprt_set_object_vertices(fyprt_context* c, const fyprt_vertex* object_verti
 // Tuning key 22 = 1: records and tree by the partial walk over the listed meshes (rt_partial.h) instead of the full passes.
 int fyprt_update_transforms(fyprt_context* c, const uint32_t* mesh_indices, const float* matrices16, uint32_t count) {
     if (!c || (count && (!mesh_indices || !matrices16))) return FYPRT_EINVAL;
-    if (!c->haveScene || c->meshFirstVertex.empty()) return c->fail(FYPRT_ESTATE, "fyprt_update_transforms before fyprt_upload_scene + fyprt_set_object_vertices");
-    if (c->prebuiltLightTrees) return c->fail(FYPRT_ESTATE, "fyprt_update_transforms: the scene was uploaded with prebuilt light trees; upload it again instead");
-    const uint32_t nM = (uint32_t)c->topoMeshes.size(), nT = (uint32_t)(c->topoTris.size() / 4);
-    for (uint32_t k = 0; k < count; ++k) if (mesh_indices[k] >= nM) return c->fail(FYPRT_EINVAL, "fyprt_update_transforms: mesh index out of range");
-    HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c));
-    c->frameComplete = false;                  // as fyprt_update_vertices
-    TRY(temporal_edit_begin(c));
+    TRY(edit_check_state(c, "fyprt_update_transforms", kNeedSceneAndRanges | kNeedOwnLightTrees));
+    TRY(check_mesh_list(c, "fyprt_update_transforms", mesh_indices, count, nullptr));
+    TRY(edit_begin(c, kEditGeometry));
     for (uint32_t k = 0; k < count; ++k) temporal_edit_range(c, c->topoMeshes[mesh_indices[k]].first_triangle, c->topoMeshes[mesh_indices[k]].triangle_count);
-    std::vector<uint8_t> touched(nM, 0);
+    std::vector<uint8_t> touched(c->topoMeshes.size(), 0);
     bool lightsMoved = false;
     for (uint32_t k = 0; k < count; ++k) {
         const uint32_t m = mesh_indices[k], first = c->meshFirstVertex[m], n = c->meshFirstVertex[m + 1] - first;
         Mat4 M; std::memcpy(M.m, matrices16 + (size_t)k * 16, 64);
         if (n) hipLaunchKernelGGL(k_transform_vertices, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, c->objVerts.p, c->dverts.p, first, n, M);
         if (is_emissive(c->topoMats[c->topoMeshes[m].material_index]) && n) {            // an emissive mesh moved: its light tree is rebuilt from its new vertices
-            HIPCHK(c, hipMemcpyAsync(c->hostVerts.data() + first, c->dverts.p + first, (size_t)n * sizeof(fyprt_vertex), hipMemcpyDeviceToHost, c->stream));
+            TRY(read_back_mesh_verts(c, m));
             touched[m] = 1; lightsMoved = true;
         }
     }
     HIPCHK(c, hipGetLastError());
     if (c->tuning[K_PARTIAL_REFIT]) {
-        std::vector<uint32_t> distinct; std::vector<uint8_t> listed(nM, 0);       // a mesh may be listed twice: its last matrix holds, it is walked once
-        for (uint32_t k = 0; k < count; ++k) if (!listed[mesh_indices[k]]) { listed[mesh_indices[k]] = 1; distinct.push_back(mesh_indices[k]); }
+        std::vector<uint8_t> listed; std::vector<uint32_t> distinct;              // a mesh may be listed twice: its last matrix holds, it is walked once
+        TRY(check_mesh_list(c, "fyprt_update_transforms", mesh_indices, count, &listed, &distinct));
         TRY(run_partial_refit(c, distinct));
     } else {
-        if (nT) hipLaunchKernelGGL(k_refresh_triangles, dim3((nT + 255u) / 256u), dim3(256), 0, c->stream, c->dverts.p, c->triIdx.p, c->triPos.p, c->triShade.p, nT);
+        TRY(launch_refresh_triangles(c, 0, (uint32_t)(c->topoTris.size() / 4)));
         TRY(run_refit(c));
         full_edit_stats(c);
     }
-    c->hostBvhStale = true; c->hostVertsStale = true;
-    if (lightsMoved) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        TRY(rebuild_light_trees(c, c->hostVerts.data(), touched.data()));
-    }
-    if (c->dsc.emissiveCount) hipLaunchKernelGGL(k_build_light_records, dim3((c->dsc.emissiveCount + 255u) / 256u), dim3(256), 0, c->stream, c->dsc, c->lightRecs.p);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, sync_all(c));
-    partial_finish_stats(c);
-    return FYPRT_OK;
+    c->hostVertsStale = true;
+    return finish_geometry_edit(c, touched.data(), lightsMoved, true);
 }
 
 // New world vertices for the listed meshes only: the state fyprt_update_vertices reaches with the full array (the given vertices in
@@ -921,27 +948,17 @@ int fyprt_update_transforms(fyprt_context* c, const uint32_t* mesh_indices, cons
 int fyprt_update_mesh_vertices(fyprt_context* c, const uint32_t* mesh_indices, uint32_t mesh_count, const fyprt_vertex* vertices, uint32_t vertex_count) {
     if (!c) return FYPRT_EINVAL;
     if ((mesh_count && !mesh_indices) || (vertex_count && !vertices)) return c->fail(FYPRT_EINVAL, "fyprt_update_mesh_vertices: NULL array with a non-zero count");
-    if (!c->haveScene) return c->fail(FYPRT_ESTATE, "fyprt_update_mesh_vertices before fyprt_upload_scene");
-    if (c->meshFirstVertex.empty()) return c->fail(FYPRT_ESTATE, "fyprt_update_mesh_vertices needs the mesh vertex ranges of fyprt_set_object_vertices");
-    if (c->prebuiltLightTrees) return c->fail(FYPRT_ESTATE, "fyprt_update_mesh_vertices: the scene was uploaded with prebuilt light trees; upload it again instead");
-    if (c->hostOnly) return c->fail(FYPRT_ESTATE, "fyprt_update_mesh_vertices needs a device (host-only context)");
-    const uint32_t nM = (uint32_t)c->topoMeshes.size();
-    for (uint32_t k = 0; k < mesh_count; ++k) if (mesh_indices[k] >= nM) return c->fail(FYPRT_EINVAL, "fyprt_update_mesh_vertices: mesh index out of range");
-    std::vector<uint8_t> listed(nM, 0);
+    TRY(edit_check_state(c, "fyprt_update_mesh_vertices", kNeedScene | kNeedRanges | kNeedOwnLightTrees | kNeedDevice));
+    std::vector<uint8_t> listed;
+    TRY(check_mesh_list(c, "fyprt_update_mesh_vertices", mesh_indices, mesh_count, &listed));
     uint64_t sum = 0;
-    for (uint32_t k = 0; k < mesh_count; ++k) {
-        const uint32_t m = mesh_indices[k];
-        if (listed[m]) return c->fail(FYPRT_EINVAL, "fyprt_update_mesh_vertices: mesh " + std::to_string(m) + " is listed twice");
-        listed[m] = 1; sum += c->meshFirstVertex[m + 1] - c->meshFirstVertex[m];
-    }
+    for (uint32_t k = 0; k < mesh_count; ++k) sum += c->meshFirstVertex[mesh_indices[k] + 1] - c->meshFirstVertex[mesh_indices[k]];
     if (sum != vertex_count) return c->fail(FYPRT_EINVAL, "fyprt_update_mesh_vertices: vertex_count is not the sum of the listed meshes' vertex ranges");
     if (mesh_count == 0) return FYPRT_OK;
-    HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c));
-    c->frameComplete = false;                  // as fyprt_update_vertices
-    TRY(temporal_edit_begin(c));
+    TRY(edit_begin(c, kEditGeometry));
     for (uint32_t k = 0; k < mesh_count; ++k) temporal_edit_range(c, c->topoMeshes[mesh_indices[k]].first_triangle, c->topoMeshes[mesh_indices[k]].triangle_count);
     if (c->dtSnapPending) HIPCHK(c, hipStreamSynchronize(c->stream));          // blocking copies below: the snapshot must have read dverts first
-    std::vector<uint8_t> touched(nM, 0);
+    std::vector<uint8_t> touched(c->topoMeshes.size(), 0);
     bool lightsMoved = false;
     const fyprt_vertex* src = vertices;
     for (uint32_t k = 0; k < mesh_count; ++k) {
@@ -952,13 +969,7 @@ int fyprt_update_mesh_vertices(fyprt_context* c, const uint32_t* mesh_indices, u
         src += n;
     }
     TRY(run_partial_refit(c, std::vector<uint32_t>(mesh_indices, mesh_indices + mesh_count)));
-    c->hostBvhStale = true;
-    if (lightsMoved) TRY(rebuild_light_trees(c, c->hostVerts.data(), touched.data()));
-    if (c->dsc.emissiveCount) hipLaunchKernelGGL(k_build_light_records, dim3((c->dsc.emissiveCount + 255u) / 256u), dim3(256), 0, c->stream, c->dsc, c->lightRecs.p);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, sync_all(c));
-    partial_finish_stats(c);
-    return FYPRT_OK;
+    return finish_geometry_edit(c, touched.data(), lightsMoved, false);
 }
 
 int fyprt_last_edit_stats(fyprt_context* c, fyprt_edit_stats* out) {
@@ -996,6 +1007,81 @@ static int derive_emissive_on_device(fyprt_context* c, const std::vector<char>& 
     return FYPRT_OK;
 }
 
+// What a material edit means, worked out before anything changes: the packed table and which materials emit; the reassignment as (first
+// triangle, count, material, mesh); does emission move, does the list stay; the meshes whose light tree changes, and does the set of lights
+struct MaterialEdit {
+    std::vector<float> mats; std::vector<char> emissiveMat; std::vector<uint4> ranges; std::vector<uint8_t> touched;
+    bool emissionMoved = false, listSame = false, setChanged = false, anyTouched = false;
+};
+static MaterialEdit plan_material_edit(const fyprt_context* c, const fyprt_material* materials, uint32_t material_count, const uint32_t* mesh_indices, const int32_t* mesh_materials,
+                                       uint32_t mesh_count, const uint32_t* emissive_triangles, uint32_t emissive_count) {
+    MaterialEdit e;
+    const uint32_t nM = (uint32_t)c->topoMeshes.size(), oldCount = (uint32_t)c->topoMats.size();
+    pack_materials(materials, material_count, e.mats, e.emissiveMat);
+    // Does the edit move any emission?  A material whose emission colour or power changed bit-wise, or a reassigned mesh that has
+    // anything to do with an emitter (its old or new material, or the old material of any of its triangles).
+    for (uint32_t i = 0; i < oldCount && !e.emissionMoved; ++i)
+        e.emissionMoved = std::memcmp(materials[i].emission_color, c->topoMats[i].emission_color, 12) != 0 || std::memcmp(&materials[i].emission_power, &c->topoMats[i].emission_power, 4) != 0;
+    // the reassignment, de-duplicated (the last entry of a mesh wins, as a sequence of edits would have it)
+    if (mesh_count) {
+        std::vector<int32_t> newMat(nM, -1);
+        for (uint32_t k = 0; k < mesh_count; ++k) newMat[mesh_indices[k]] = mesh_materials[k];
+        for (uint32_t k = 0; k < mesh_count; ++k) {
+            const uint32_t m = mesh_indices[k];
+            if (newMat[m] < 0) continue;                                     // an earlier entry of this mesh has been taken
+            const fyprt_mesh& me = c->topoMeshes[m];
+            e.ranges.push_back(make_uint4(me.first_triangle, me.triangle_count, (uint32_t)newMat[m], m));
+            newMat[m] = -1;
+        }
+    }
+    // light trees hang on the MESH's material (lighttree_build.cpp): which meshes change their tree, and does any mesh start or stop
+    // being a light (then the node counts move and every tree is rebuilt)
+    e.touched.assign(nM, 0); std::vector<uint8_t> reassigned(nM, 0);
+    auto emissionBits = [](const fyprt_material& a, const fyprt_material& b) {
+        return std::memcmp(a.emission_color, b.emission_color, 12) == 0 && std::memcmp(&a.emission_power, &b.emission_power, 4) == 0;
+    };
+    for (const uint4& r : e.ranges) {
+        const fyprt_mesh& me = c->topoMeshes[r.w];
+        const fyprt_material& was = c->topoMats[me.material_index]; const fyprt_material& is = materials[r.z];
+        reassigned[r.w] = 1;
+        bool emits = is_emissive(was) || e.emissiveMat[r.z];
+        for (uint32_t t = me.first_triangle; t < me.first_triangle + me.triangle_count && !emits; ++t) emits = is_emissive(c->topoMats[c->topoTris[(size_t)t * 4 + 3]]);
+        if (emits) e.emissionMoved = true;
+        if (me.triangle_count && is_emissive(was) != (bool)e.emissiveMat[r.z]) e.setChanged = true;
+        else if (e.emissiveMat[r.z] && !emissionBits(was, is)) { e.touched[r.w] = 1; e.anyTouched = true; }
+    }
+    // the emissive list stays as it is when it is derived as before and no emission moved, or handed over unchanged
+    e.listSame = !e.emissionMoved;
+    if (e.listSame) {
+        if (emissive_triangles) e.listSame = c->emissiveExplicit && c->hostEmissive.size() == emissive_count && (emissive_count == 0 || std::memcmp(c->hostEmissive.data(), emissive_triangles, (size_t)emissive_count * 4) == 0);
+        else e.listSame = !c->emissiveExplicit;
+    }
+    if (!e.listSame || e.emissionMoved) {
+        for (uint32_t m = 0; m < nM; ++m) {
+            if (reassigned[m] || c->topoMeshes[m].triangle_count == 0) continue;
+            const uint32_t mi = (uint32_t)c->topoMeshes[m].material_index;             // < oldCount
+            if (is_emissive(c->topoMats[mi]) != (bool)e.emissiveMat[mi]) e.setChanged = true;
+            else if (e.emissiveMat[mi] && !emissionBits(c->topoMats[mi], materials[mi])) { e.touched[m] = 1; e.anyTouched = true; }
+        }
+    }
+    return e;
+}
+// the reassigned ranges' triangles on the device (k_set_mesh_material: blockIdx.y = the range); the table is scratch the context keeps
+static int launch_set_mesh_materials(fyprt_context* c, const std::vector<uint4>& ranges) {
+    if (c->hostOnly || ranges.empty()) return FYPRT_OK;
+    if (c->matRanges.n < ranges.size()) HIPCHK(c, c->matRanges.alloc(ranges.size()));
+    TRY(upload(c, c->matRanges.p, ranges.data(), ranges.size() * sizeof(uint4)));
+    for (size_t first = 0; first < ranges.size(); first += 65535u) {
+        const uint32_t n = (uint32_t)std::min<size_t>(65535u, ranges.size() - first);
+        uint32_t longest = 0; for (uint32_t k = 0; k < n; ++k) longest = std::max(longest, ranges[first + k].y);
+        if (longest == 0) continue;
+        const uint32_t gx = std::min<uint32_t>(64u, (longest + kBlock - 1u) / kBlock);
+        hipLaunchKernelGGL(k_set_mesh_material, dim3(gx, n), dim3(kBlock), 0, c->stream, c->matRanges.p + first, c->triPos.p, c->triShade.p, c->triIdx.p, (uint32_t)(c->topoTris.size() / 4));
+    }
+    HIPCHK(c, hipGetLastError());
+    return FYPRT_OK;
+}
+
 // A material edit (SceneManager::PerformAllSceneUpdates with materialsToUpdate / meshMatToBeUpdated, SceneManager.cpp:10-17, :69-85): the
 // whole material table is replaced, the listed meshes (and all their triangles) get another material, the emissive list is the given one
 // or derived again.  The context ends in the state fyprt_upload_scene reaches with the edited description — but the acceleration
@@ -1009,131 +1095,54 @@ int fyprt_update_materials(fyprt_context* c, const fyprt_material* materials, ui
     if (mesh_count && (!mesh_indices || !mesh_materials)) return c->fail(FYPRT_EINVAL, "fyprt_update_materials: NULL mesh array with a non-zero count");
     const uint32_t nM = (uint32_t)c->topoMeshes.size(), nT = (uint32_t)(c->topoTris.size() / 4), oldCount = (uint32_t)c->topoMats.size();
     if (material_count < oldCount) return c->fail(FYPRT_EINVAL, "fyprt_update_materials: the material table must not shrink");
-    for (uint32_t k = 0; k < mesh_count; ++k) if (mesh_indices[k] >= nM) return c->fail(FYPRT_EINVAL, "fyprt_update_materials: mesh index out of range");
+    TRY(check_mesh_list(c, "fyprt_update_materials", mesh_indices, mesh_count, nullptr));
     for (uint32_t k = 0; k < mesh_count; ++k) if (mesh_materials[k] < 0 || (uint32_t)mesh_materials[k] >= material_count) return c->fail(FYPRT_EINVAL, "fyprt_update_materials: material index out of range");
     if (emissive_triangles) for (uint32_t k = 0; k < emissive_count; ++k) if (emissive_triangles[k] >= nT) return c->fail(FYPRT_EINVAL, "fyprt_update_materials: emissive triangle index out of range");
-    if (!c->haveScene) return c->fail(FYPRT_ESTATE, "fyprt_update_materials before fyprt_upload_scene");
-    if (c->prebuiltLightTrees) return c->fail(FYPRT_ESTATE, "fyprt_update_materials: the scene was uploaded with prebuilt light trees; upload it again instead");
-    if (!c->hostOnly) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c)); }
-    c->frameComplete = false;                  // the payload's triangles were shaded with the old materials (fyprt_denoise)
-    c->drop_history();
+    TRY(edit_check_state(c, "fyprt_update_materials", kNeedScene | kNeedOwnLightTrees));
+    TRY(edit_begin(c, kEditShading));
 
-    std::vector<float> mats; std::vector<char> emissiveMat;
-    pack_materials(materials, material_count, mats, emissiveMat);
-    // Does the edit move any emission?  A material whose emission colour or power changed bit-wise, or a reassigned mesh that has
-    // anything to do with an emitter (its old or new material, or the old material of any of its triangles).
-    bool emissionMoved = false;
-    for (uint32_t i = 0; i < oldCount && !emissionMoved; ++i)
-        emissionMoved = std::memcmp(materials[i].emission_color, c->topoMats[i].emission_color, 12) != 0 || std::memcmp(&materials[i].emission_power, &c->topoMats[i].emission_power, 4) != 0;
-    // the reassignment, de-duplicated (the last entry of a mesh wins, as a sequence of edits would have it)
-    std::vector<uint4> ranges;
-    if (mesh_count) {
-        std::vector<int32_t> newMat(nM, -1);
-        for (uint32_t k = 0; k < mesh_count; ++k) newMat[mesh_indices[k]] = mesh_materials[k];
-        for (uint32_t k = 0; k < mesh_count; ++k) {
-            const uint32_t m = mesh_indices[k];
-            if (newMat[m] < 0) continue;                                     // an earlier entry of this mesh has been taken
-            const fyprt_mesh& me = c->topoMeshes[m];
-            ranges.push_back(make_uint4(me.first_triangle, me.triangle_count, (uint32_t)newMat[m], m));
-            newMat[m] = -1;
-        }
-    }
-    // light trees hang on the MESH's material (lighttree_build.cpp): which meshes change their tree, and does any mesh start or stop
-    // being a light (then the node counts move and every tree is rebuilt)
-    std::vector<uint8_t> touched(nM, 0); std::vector<uint8_t> reassigned(nM, 0);
-    bool setChanged = false, anyTouched = false;
-    auto emissionBits = [](const fyprt_material& a, const fyprt_material& b) {
-        return std::memcmp(a.emission_color, b.emission_color, 12) == 0 && std::memcmp(&a.emission_power, &b.emission_power, 4) == 0;
-    };
-    for (const uint4& r : ranges) {
-        const fyprt_mesh& me = c->topoMeshes[r.w];
-        const fyprt_material& was = c->topoMats[me.material_index]; const fyprt_material& is = materials[r.z];
-        reassigned[r.w] = 1;
-        bool emits = is_emissive(was) || emissiveMat[r.z];
-        for (uint32_t t = me.first_triangle; t < me.first_triangle + me.triangle_count && !emits; ++t) emits = is_emissive(c->topoMats[c->topoTris[(size_t)t * 4 + 3]]);
-        if (emits) emissionMoved = true;
-        if (me.triangle_count && is_emissive(was) != (bool)emissiveMat[r.z]) setChanged = true;
-        else if (emissiveMat[r.z] && !emissionBits(was, is)) { touched[r.w] = 1; anyTouched = true; }
-    }
-    // the emissive list stays as it is when it is derived as before and no emission moved, or handed over unchanged
-    bool listSame = !emissionMoved;
-    if (listSame) {
-        if (emissive_triangles) listSame = c->emissiveExplicit && c->hostEmissive.size() == emissive_count && (emissive_count == 0 || std::memcmp(c->hostEmissive.data(), emissive_triangles, (size_t)emissive_count * 4) == 0);
-        else listSame = !c->emissiveExplicit;
-    }
-    if (!listSame || emissionMoved) {
-        for (uint32_t m = 0; m < nM; ++m) {
-            if (reassigned[m] || c->topoMeshes[m].triangle_count == 0) continue;
-            const uint32_t mi = (uint32_t)c->topoMeshes[m].material_index;             // < oldCount
-            if (is_emissive(c->topoMats[mi]) != (bool)emissiveMat[mi]) setChanged = true;
-            else if (emissiveMat[mi] && !emissionBits(c->topoMats[mi], materials[mi])) { touched[m] = 1; anyTouched = true; }
-        }
-    }
-
+    const MaterialEdit e = plan_material_edit(c, materials, material_count, mesh_indices, mesh_materials, mesh_count, emissive_triangles, emissive_count);
     // 1. the table
     if (material_count != oldCount) { HIPCHK(c, c->mats.alloc((size_t)material_count * 3, c->hostOnly)); c->dsc.mats = c->mats.p; }
-    TRY(upload(c, c->mats.p, mats.data(), mats.size() * 4));
+    TRY(upload(c, c->mats.p, e.mats.data(), e.mats.size() * 4));
     c->topoMats.assign(materials, materials + material_count);
-    // 2. the reassigned meshes: their triangles on the device, the host's copy of those ranges
-    if (!ranges.empty()) {
-        for (const uint4& r : ranges) {
-            c->topoMeshes[r.w].material_index = (int32_t)r.z;
-            for (uint32_t t = r.x; t < r.x + r.y; ++t) c->topoTris[(size_t)t * 4 + 3] = r.z;
-        }
-        if (!c->hostOnly) {
-            if (c->matRanges.n < ranges.size()) HIPCHK(c, c->matRanges.alloc(ranges.size()));
-            TRY(upload(c, c->matRanges.p, ranges.data(), ranges.size() * sizeof(uint4)));
-            for (size_t first = 0; first < ranges.size(); first += 65535u) {            // blockIdx.y = the mesh
-                const uint32_t n = (uint32_t)std::min<size_t>(65535u, ranges.size() - first);
-                uint32_t longest = 0; for (uint32_t k = 0; k < n; ++k) longest = std::max(longest, ranges[first + k].y);
-                if (longest == 0) continue;
-                const uint32_t gx = std::min<uint32_t>(64u, (longest + kBlock - 1u) / kBlock);
-                hipLaunchKernelGGL(k_set_mesh_material, dim3(gx, n), dim3(kBlock), 0, c->stream, c->matRanges.p + first, c->triPos.p, c->triShade.p, c->triIdx.p, nT);
-            }
-            HIPCHK(c, hipGetLastError());
-        }
+    // 2. the reassigned meshes: the host's copy of their ranges, their triangles on the device
+    for (const uint4& r : e.ranges) {
+        c->topoMeshes[r.w].material_index = (int32_t)r.z;
+        for (uint32_t t = r.x; t < r.x + r.y; ++t) c->topoTris[(size_t)t * 4 + 3] = r.z;
     }
-    if (listSame && !emissionMoved) {           // albedo, roughness, metallic, texture switch: no light changes
+    TRY(launch_set_mesh_materials(c, e.ranges));
+    if (e.listSame && !e.emissionMoved) {       // albedo, roughness, metallic, texture switch: no light changes
         if (!c->hostOnly) HIPCHK(c, sync_all(c));
         return FYPRT_OK;
     }
-    // 3. the emissive list
+    // 3. the emissive list: handed over, or derived again from the materials that emit now
     uint32_t nE = 0;
+    c->hostEmissive.clear();
     if (emissive_triangles) {
         c->hostEmissive.assign(emissive_triangles, emissive_triangles + emissive_count);
         TRY(alloc_upload(c, c->emissive, c->hostEmissive.data(), c->hostEmissive.size()));
         nE = emissive_count;
     } else if (c->hostOnly) {
-        c->hostEmissive.clear();
-        for (uint32_t i = 0; i < nT; ++i) if (emissiveMat[c->topoTris[(size_t)i * 4 + 3]]) c->hostEmissive.push_back(i);
+        for (uint32_t i = 0; i < nT; ++i) if (e.emissiveMat[c->topoTris[(size_t)i * 4 + 3]]) c->hostEmissive.push_back(i);
         nE = (uint32_t)c->hostEmissive.size();
         HIPCHK(c, c->emissive.alloc(nE, true));
-    } else {
-        c->hostEmissive.clear();
-        TRY(derive_emissive_on_device(c, emissiveMat, 0, nT, 0, &nE));
-    }
+    } else TRY(derive_emissive_on_device(c, e.emissiveMat, 0, nT, 0, &nE));
     c->emissiveExplicit = emissive_triangles != nullptr;
     c->dsc.emissive = c->emissive.p; c->dsc.emissiveCount = nE;
     // 4. the light records (they carry the emission)
     HIPCHK(c, c->lightRecs.alloc((size_t)nE * 3, c->hostOnly));
     c->dsc.lightRecs = c->lightRecs.p;
-    if (!c->hostOnly && nE) {
-        hipLaunchKernelGGL(k_build_light_records, dim3((nE + 255u) / 256u), dim3(256), 0, c->stream, c->dsc, c->lightRecs.p);
-        HIPCHK(c, hipGetLastError());
-    }
+    TRY(launch_light_records(c));
     // 5. the light trees, on the host.  The partial rebuild replaces a mesh's tree in place, which needs every mesh to keep its node
     // count: only when no mesh starts or stops being a light.  After device transform edits the host's vertices followed only the
     // meshes that were lights when they moved: what the build will read (the meshes that are lights NOW) comes back first.
-    if (setChanged || anyTouched) {
-        if (setChanged && c->hostVertsStale && !c->hostOnly && !c->meshFirstVertex.empty()) {
-            for (uint32_t m = 0; m < nM; ++m) {
-                const uint32_t first = c->meshFirstVertex[m], n = c->meshFirstVertex[m + 1] - first;
-                if (n && is_emissive(c->topoMats[c->topoMeshes[m].material_index]))
-                    HIPCHK(c, hipMemcpyAsync(c->hostVerts.data() + first, c->dverts.p + first, (size_t)n * sizeof(fyprt_vertex), hipMemcpyDeviceToHost, c->stream));
-            }
+    if (e.setChanged || e.anyTouched) {
+        if (e.setChanged && c->hostVertsStale && !c->hostOnly && !c->meshFirstVertex.empty()) {
+            for (uint32_t m = 0; m < nM; ++m) if (is_emissive(c->topoMats[c->topoMeshes[m].material_index])) TRY(read_back_mesh_verts(c, m));
             HIPCHK(c, hipStreamSynchronize(c->stream));
         }
-        TRY(rebuild_light_trees(c, c->hostVerts.data(), setChanged ? nullptr : touched.data()));
+        TRY(rebuild_light_trees(c, c->hostVerts.data(), e.setChanged ? nullptr : e.touched.data()));
     }
     if (!c->hostOnly) HIPCHK(c, sync_all(c));
     return FYPRT_OK;
@@ -1145,8 +1154,6 @@ int fyprt_update_materials(fyprt_context* c, const fyprt_material* materials, ui
 // (rt_graft.h).  Of the old scene nothing crosses the bus but the level grouping (4 bytes per node): the scene arrays grow in place
 // or move device to device, the appended range goes through k_refresh_triangles, the emissive list is extended by the ordered
 // compaction over the range, the light records are rebuilt by their kernel, and the host builds the new meshes' light trees + the TLAS.
-#include "rt_graft.h"
-
 int fyprt_append_meshes(fyprt_context* c, const fyprt_vertex* vertices, uint32_t vertex_count, const void* triangles, uint32_t triangle_count, uint32_t triangle_stride,
                         const fyprt_mesh* meshes, uint32_t mesh_count, const fyprt_vertex* object_vertices, const uint32_t* mesh_first_vertex) {
     if (!c) return FYPRT_EINVAL;
@@ -1180,21 +1187,15 @@ int fyprt_append_meshes(fyprt_context* c, const fyprt_vertex* vertices, uint32_t
             for (uint32_t t = meshes[m].first_triangle - T0; t < meshes[m].first_triangle - T0 + meshes[m].triangle_count; ++t)
                 for (int k = 0; k < 3; ++k) if (tri(t)[k] < mesh_first_vertex[m] || tri(t)[k] >= mesh_first_vertex[m + 1]) return c->fail(FYPRT_EINVAL, "fyprt_append_meshes: triangle " + std::to_string(t) + " uses a vertex outside its mesh's range");
     }
-    if (!c->haveScene) return c->fail(FYPRT_ESTATE, "fyprt_append_meshes before fyprt_upload_scene");
-    if (c->prebuiltLightTrees) return c->fail(FYPRT_ESTATE, "fyprt_append_meshes: the scene was uploaded with prebuilt light trees; upload it again instead");
+    TRY(edit_check_state(c, "fyprt_append_meshes", kNeedScene | kNeedOwnLightTrees));
     if (triangle_count == 0 && mesh_count == 0) return FYPRT_OK;
-    if (!c->hostOnly) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c)); }
-    c->frameComplete = false;                  // as fyprt_upload_scene
-    c->drop_history(); c->release_snapshot();
+    TRY(edit_begin(c, kEditTopology));
 
     // 1. the host's copies: vertices, topology.  The sub-tree's host builder and the new meshes' light trees read the vertices the new
     // triangles use: after device transform edits the old ones come back first if any is among them.
     bool usesOld = false;
     for (uint32_t i = 0; i < triangle_count && !usesOld; ++i) usesOld = tri(i)[0] < V0 || tri(i)[1] < V0 || tri(i)[2] < V0;
-    if (usesOld && c->hostVertsStale && !c->hostOnly && V0) {
-        HIPCHK(c, hipMemcpy(c->hostVerts.data(), c->dverts.p, (size_t)V0 * sizeof(fyprt_vertex), hipMemcpyDeviceToHost));
-        c->hostVertsStale = false;
-    }
+    if (usesOld) TRY(ensure_host_verts(c, V0));
     c->hostVerts.insert(c->hostVerts.end(), vertices, vertices + vertex_count);
     c->topoTris.resize((size_t)T * 4);
     for (uint32_t i = 0; i < triangle_count; ++i) std::memcpy(&c->topoTris[(size_t)(T0 + i) * 4], tri(i), 16);
@@ -1206,8 +1207,7 @@ int fyprt_append_meshes(fyprt_context* c, const fyprt_vertex* vertices, uint32_t
     if (!c->hostOnly) {
         TRY(upload(c, c->dverts.p + V0, vertices, (size_t)vertex_count * sizeof(fyprt_vertex)));
         TRY(upload(c, c->triIdx.p + T0, c->topoTris.data() + (size_t)T0 * 4, (size_t)triangle_count * 16));
-        if (triangle_count) hipLaunchKernelGGL(k_refresh_triangles, dim3((triangle_count + 255u) / 256u), dim3(256), 0, c->stream, c->dverts.p, c->triIdx.p + T0, c->triPos.p + (size_t)T0 * 3, c->triShade.p + (size_t)T0 * 4, triangle_count);
-        HIPCHK(c, hipGetLastError());
+        TRY(launch_refresh_triangles(c, T0, triangle_count));
     }
     // 3. object-space vertices: extended with the copy the context holds; without new ones the copy goes, as an upload drops it
     if (object_vertices && !c->meshFirstVertex.empty()) {
@@ -1217,23 +1217,11 @@ int fyprt_append_meshes(fyprt_context* c, const fyprt_vertex* vertices, uint32_t
     } else if (!object_vertices) { c->objVerts.release(); c->meshFirstVertex.clear(); }
     // 4. the acceleration structure: the graft, or the tree of the combined scene when the graft would be too deep / too large
     if (triangle_count) {
-        int rc = graft_append(c, vertices, vertex_count, T0, triangle_count, meshes, mesh_count);
-        if (rc == kGraftRebuild) {
-            if (c->hostVertsStale && !c->hostOnly && V0) {             // the host builder reads every vertex
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                HIPCHK(c, hipMemcpy(c->hostVerts.data(), c->dverts.p, (size_t)V0 * sizeof(fyprt_vertex), hipMemcpyDeviceToHost));
-                c->hostVertsStale = false;
-            }
-            rc = build_scene_tree(c, "fyprt_append_meshes", c->hostVerts.data(), V, (const uint8_t*)c->topoTris.data(), 16, c->topoMeshes.data(), M, T);
-            c->placement.kind = 4u; c->placement.node = c->placement.slot = c->placement.depth = c->placement.cost_bits = c->placement.candidates = 0u;
-            c->placement.levels_after = c->hostBvh.levels;
-        }
-        if (rc != FYPRT_OK) return rc;
+        TRY(graft_or_rebuild(c, "fyprt_append_meshes", vertices, vertex_count, T0, triangle_count, meshes, mesh_count, V0));
         c->havePlacement = true;
     }
+    set_scene_triangles(c, T);
     DevScene& d = c->dsc;
-    d.nodes = c->nodes.p; d.leafTris = c->leafTris.p; d.rootRef = rth::device_ref(c->hostBvh.rootRef); d.triCount = T;
-    d.triPos = c->triPos.p; d.triShade = c->triShade.p;
     // 5. lights.  The emissive list: the old one followed by the appended triangles whose material emits, in ascending order
     std::vector<char> emissiveMat(nMat);
     for (uint32_t i = 0; i < nMat; ++i) emissiveMat[i] = is_emissive(c->topoMats[i]);
@@ -1252,7 +1240,7 @@ int fyprt_append_meshes(fyprt_context* c, const fyprt_vertex* vertices, uint32_t
         d.emissive = c->emissive.p; d.emissiveCount = nE;
         HIPCHK(c, c->lightRecs.alloc((size_t)nE * 3, c->hostOnly));
         d.lightRecs = c->lightRecs.p;
-        if (!c->hostOnly) { hipLaunchKernelGGL(k_build_light_records, dim3((nE + 255u) / 256u), dim3(256), 0, c->stream, d, c->lightRecs.p); HIPCHK(c, hipGetLastError()); }
+        TRY(launch_light_records(c));
     }
     // ... and the light trees, which hang on the MESH's material: the new meshes' trees behind the old ones, then the TLAS
     {
@@ -1291,18 +1279,12 @@ int fyprt_last_append_placement(fyprt_context* c, fyprt_append_placement* out) {
 // context ends in the state fyprt_upload_scene reaches with the reduced description, except for the acceleration structure, which is the
 // old tree pruned bottom-up (rt_prune.h).  Every array is compacted on the device into a buffer of the same capacity; 4 bytes per leaf
 // record come back (the dead counts the host repeats the node pass with), tables, refit list and level grouping go up.
-#include "rt_prune.h"
-
 int fyprt_remove_meshes(fyprt_context* c, const uint32_t* mesh_indices, uint32_t mesh_count, const uint32_t* vertex_ranges) {
     if (!c) return FYPRT_EINVAL;
     if (mesh_count && !mesh_indices) return c->fail(FYPRT_EINVAL, "fyprt_remove_meshes: NULL mesh_indices with a non-zero count");
-    const uint32_t M0 = (uint32_t)c->topoMeshes.size(), T0 = (uint32_t)(c->topoTris.size() / 4), V0 = c->vertexCount;
-    for (uint32_t k = 0; k < mesh_count; ++k) if (mesh_indices[k] >= M0) return c->fail(FYPRT_EINVAL, "fyprt_remove_meshes: mesh index out of range");
-    std::vector<uint8_t> gone(M0, 0);
-    for (uint32_t k = 0; k < mesh_count; ++k) {
-        if (gone[mesh_indices[k]]) return c->fail(FYPRT_EINVAL, "fyprt_remove_meshes: mesh " + std::to_string(mesh_indices[k]) + " is listed twice");
-        gone[mesh_indices[k]] = 1;
-    }
+    const uint32_t T0 = (uint32_t)(c->topoTris.size() / 4), V0 = c->vertexCount;
+    std::vector<uint8_t> gone;
+    TRY(check_mesh_list(c, "fyprt_remove_meshes", mesh_indices, mesh_count, &gone));
     const bool copy = !c->meshFirstVertex.empty();
     std::vector<std::pair<uint32_t, uint32_t>> vr, tr;
     if (vertex_ranges) {
@@ -1328,12 +1310,9 @@ int fyprt_remove_meshes(fyprt_context* c, const uint32_t* mesh_indices, uint32_t
         if (tris.dead(t, shift)) continue;
         for (int k = 0; k < 3; ++k) if (verts.dead(c->topoTris[(size_t)t * 4 + k], shift)) return c->fail(FYPRT_EINVAL, "fyprt_remove_meshes: surviving triangle " + std::to_string(t) + " uses a removed vertex");
     }
-    if (!c->haveScene) return c->fail(FYPRT_ESTATE, "fyprt_remove_meshes before fyprt_upload_scene");
-    if (c->prebuiltLightTrees) return c->fail(FYPRT_ESTATE, "fyprt_remove_meshes: the scene was uploaded with prebuilt light trees; upload it again instead");
+    TRY(edit_check_state(c, "fyprt_remove_meshes", kNeedScene | kNeedOwnLightTrees));
     if (mesh_count == 0) return FYPRT_OK;
-    if (!c->hostOnly) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c)); }
-    c->frameComplete = false;                  // as fyprt_append_meshes
-    c->drop_history(); c->release_snapshot();
+    TRY(edit_begin(c, kEditTopology));
     return prune_remove(c, tris, verts, gone);
 }
 
@@ -1341,11 +1320,7 @@ int fyprt_remove_meshes(fyprt_context* c, const uint32_t* mesh_indices, uint32_t
 // mesh gets the graft of an append over its own triangle range.  Only the tree moves: no scene stream, light or frame state is touched.
 // The body, after every check, all streams idle; `reports`: NULL or one entry per listed mesh, preset by the caller.
 static int regraft_meshes(fyprt_context* c, const uint32_t* mesh_indices, uint32_t mesh_count, fyprt_append_placement* reports) {
-    const uint32_t V = c->vertexCount, T = (uint32_t)(c->topoTris.size() / 4), M = (uint32_t)c->topoMeshes.size();
-    if (c->hostVertsStale && !c->hostOnly && V) {                     // the builders and the placement rule read the meshes' world vertices
-        HIPCHK(c, hipMemcpy(c->hostVerts.data(), c->dverts.p, (size_t)V * sizeof(fyprt_vertex), hipMemcpyDeviceToHost));
-        c->hostVertsStale = false;
-    }
+    TRY(ensure_host_verts(c, c->vertexCount));                         // the builders and the placement rule read the meshes' world vertices
     // 1. the prune of a removal on the tree alone: no triangle leaves the scene, so no record is renumbered and no stream moves
     {
         std::vector<std::pair<uint32_t, uint32_t>> tr;
@@ -1364,28 +1339,16 @@ static int regraft_meshes(fyprt_context* c, const uint32_t* mesh_indices, uint32
         if (!me.triangle_count) continue;
         if (!rebuilt) {
             // the device builders' Morton grid: the exact box of the mesh's triangles, handed over as its two corners
+            const rth::HostBox box = tri_range_box(c, me.first_triangle, me.triangle_count);
             fyprt_vertex corner[2] = {};
-            for (int a = 0; a < 3; ++a) { corner[0].position[a] = 3.402823466e+38f; corner[1].position[a] = -3.402823466e+38f; }
-            for (uint32_t t = me.first_triangle; t < me.first_triangle + me.triangle_count; ++t)
-                for (int i = 0; i < 3; ++i) for (int a = 0; a < 3; ++a) {
-                    const float v = c->hostVerts[c->topoTris[(size_t)t * 4 + i]].position[a];
-                    corner[0].position[a] = std::min(corner[0].position[a], v); corner[1].position[a] = std::max(corner[1].position[a], v);
-                }
-            int rc = graft_append(c, corner, 2, me.first_triangle, me.triangle_count, &me, 1);
-            if (rc == kGraftRebuild) {
-                rc = build_scene_tree(c, "fyprt_regraft_meshes", c->hostVerts.data(), V, (const uint8_t*)c->topoTris.data(), 16, c->topoMeshes.data(), M, T);
-                c->placement.kind = 4u; c->placement.node = c->placement.slot = c->placement.depth = c->placement.cost_bits = c->placement.candidates = 0u;
-                c->placement.levels_after = c->hostBvh.levels;
-                rebuilt = true;
-            }
-            if (rc != FYPRT_OK) return rc;
+            for (int a = 0; a < 3; ++a) { corner[0].position[a] = box.lo[a]; corner[1].position[a] = box.hi[a]; }
+            TRY(graft_or_rebuild(c, "fyprt_regraft_meshes", corner, 2, me.first_triangle, me.triangle_count, &me, 1, 0u, &rebuilt));
             if (reports) reports[k] = c->placement;
         } else if (reports) {                                         // the rebuilt tree holds this mesh already
             reports[k].kind = 4u; reports[k].levels_before = reports[k].levels_after = c->hostBvh.levels;
         }
     }
-    DevScene& d = c->dsc;
-    d.nodes = c->nodes.p; d.leafTris = c->leafTris.p; d.rootRef = rth::device_ref(c->hostBvh.rootRef);
+    set_scene_tree(c);
     if (!c->hostOnly) HIPCHK(c, sync_all(c));
     return FYPRT_OK;
 }
@@ -1393,17 +1356,13 @@ static int regraft_meshes(fyprt_context* c, const uint32_t* mesh_indices, uint32
 int fyprt_regraft_meshes(fyprt_context* c, const uint32_t* mesh_indices, uint32_t mesh_count, fyprt_append_placement* reports) {
     if (!c) return FYPRT_EINVAL;
     if (mesh_count && !mesh_indices) return c->fail(FYPRT_EINVAL, "fyprt_regraft_meshes: NULL mesh_indices with a non-zero count");
-    const uint32_t M = (uint32_t)c->topoMeshes.size();
-    for (uint32_t k = 0; k < mesh_count; ++k) if (mesh_indices[k] >= M) return c->fail(FYPRT_EINVAL, "fyprt_regraft_meshes: mesh index out of range");
-    std::vector<uint8_t> listed(M, 0);
+    std::vector<uint8_t> listed;
+    TRY(check_mesh_list(c, "fyprt_regraft_meshes", mesh_indices, mesh_count, &listed));
     uint64_t moved = 0;
-    for (uint32_t k = 0; k < mesh_count; ++k) {
-        if (listed[mesh_indices[k]]) return c->fail(FYPRT_EINVAL, "fyprt_regraft_meshes: mesh " + std::to_string(mesh_indices[k]) + " is listed twice");
-        listed[mesh_indices[k]] = 1; moved += c->topoMeshes[mesh_indices[k]].triangle_count;
-    }
-    if (!c->haveScene) return c->fail(FYPRT_ESTATE, "fyprt_regraft_meshes before fyprt_upload_scene");
+    for (uint32_t k = 0; k < mesh_count; ++k) moved += c->topoMeshes[mesh_indices[k]].triangle_count;
+    TRY(edit_check_state(c, "fyprt_regraft_meshes", kNeedScene));
     if (mesh_count == 0) return FYPRT_OK;
-    if (!c->hostOnly) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c)); }
+    TRY(edit_begin(c, kEditTreeOnly));
     const fyprt_append_placement blank{(uint32_t)c->appendPlacement, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
     if (reports) for (uint32_t k = 0; k < mesh_count; ++k) reports[k] = blank;
     if (!moved) return FYPRT_OK;
@@ -1424,12 +1383,10 @@ int fyprt_regraft_meshes(fyprt_context* c, const uint32_t* mesh_indices, uint32_
 }
 
 // The surface-area cost of the tree as it is
-#include "rt_treecost.h"
-
 int fyprt_tree_cost(fyprt_context* c, fyprt_tree_cost_sums* out) {
     if (!c || !out) return FYPRT_EINVAL;
-    if (!c->haveScene) return c->fail(FYPRT_ESTATE, "fyprt_tree_cost before fyprt_upload_scene");
-    if (!c->hostOnly) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c)); }
+    TRY(edit_check_state(c, "fyprt_tree_cost", kNeedScene));
+    TRY(edit_begin(c, kEditTreeOnly));
     return tree_cost(c, out);
 }
 

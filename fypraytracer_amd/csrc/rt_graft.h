@@ -8,7 +8,7 @@
 //                         numbering (node 0, leaf record 0) to their place in the arrays
 //   k_graft_link          the sub-tree root S and the old root R: S becomes one more child of an R that has a free slot, otherwise
 //                         a new two-child node (R, S) behind all others becomes the root; the level counts stay exact
-//   k_graft_node_boxes    exact node boxes of a tree no refit pass has run on yet (a host-built one): what k_refit_level reads of the
+//   k_graft_node_boxes (rt_refit.h, run by ensure_node_boxes) exact node boxes of a tree no refit pass has run on yet (a host-built one): what k_refit_level reads of the
 //                         children of the nodes it is run on
 //   k_refit_level (rt_refit.h) over the new nodes, lowest level first: one box and quantisation rule on the device whichever builder
 //                         made the sub-tree
@@ -18,11 +18,11 @@
 //                         mode 0): their meta bytes, then refit_node on each, lowest first, by ONE thread in one launch
 // In mode 0 the tree grows by one level about every third append (two more children for a full root's successor, then a new root again); a
 // result deeper than the traversal stack allows is rebuilt as an upload builds it (fyprt.hip: fyprt_append_meshes).
-// This header is part of fyprt.hip (it uses the context and its helpers) and is included there once.
+// This header is part of fyprt.hip (it uses the context and its helpers, rt_tree_host.h among them) and is included there once.
 #pragma once
 #include "rt_refit.h"
+#include "rt_partial.h"      // partial_ensure_links: the parent links the placement search walks
 
-extern "C++" {
 namespace rt {
 
 // nodes [0, count) of a device-built sub-tree at `nodes`: inner references + nodeBase (a byte offset), leaf codes + leafBase records
@@ -56,22 +56,6 @@ __global__ void k_graft_link(float4* nodes, uint32_t node, uint32_t slot, int32_
     if (slot == 0u) q1.x = r; else if (slot == 1u) q1.y = r; else if (slot == 2u) q1.z = r; else q1.w = r;
     n[0] = q0; n[1] = q1;
 }
-
-// nodeBox of the listed nodes of one level (levels = 1 first), nothing else written: the box half of k_refit_level
-__global__ __launch_bounds__(128) void k_graft_node_boxes(const float4* nodes, const uint32_t* levelNodes, uint32_t count, const float4* leafTris, const float4* triPos, float4* nodeBox) {
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= count) return;
-    const uint32_t node = levelNodes[k];
-    const float4* n = nodes + (size_t)node * 4;
-    const float4 q0 = n[0], q1 = n[1];
-    const uint32_t cnt = ((uint32_t)__float_as_int(q0.w) >> 24) & 7u;
-    const int32_t child[4] = {__float_as_int(q1.x), __float_as_int(q1.y), __float_as_int(q1.z), __float_as_int(q1.w)};
-    RBox cb[4]; RBox nb;
-    refit_child_boxes(cnt, child, leafTris, triPos, nodeBox, cb, nb);
-    nodeBox[(size_t)node * 2] = make_float4(nb.lo[0], nb.lo[1], nb.lo[2], 0.0f);
-    nodeBox[(size_t)node * 2 + 1] = make_float4(nb.hi[0], nb.hi[1], nb.hi[2], 0.0f);
-}
-
 
 // ---- placement by surface-area cost (fyprt_set_append_placement(ctx, 1); the rule: include/fyprt.h).  Plain binary32 expressions, every
 // operation rounded on its own (the build sets -ffp-contract=off for host and device alike); the same functions serve the kernel and the
@@ -171,36 +155,8 @@ __global__ void k_graft_path(float4* nodes, const uint32_t* list, const uint32_t
 }  // namespace rt
 
 // ---- host side
+
 constexpr int kGraftRebuild = -1001;        // the grafted tree would exceed the traversal stack or the node range: rebuild it
-
-// Host-only contexts quantise with the builder's own quantiser from what the tree itself holds: a node's box is its exact lower corner
-// (the grid origin) and its conservative upper planes; a leaf's box is exact, from the vertices.
-static rth::ChildBox graft_plane_box(const rth::Node& n, int i) {       // child i of n, from its planes
-    rth::ChildBox b;
-    for (int a = 0; a < 3; ++a) {
-        const float s = std::ldexp(1.0f, (int)n.ex[a] - 127);
-        b.lo[a] = std::fmaf((float)n.qlo[a][i], s, n.origin[a]); b.hi[a] = std::fmaf((float)n.qhi[a][i], s, n.origin[a]);
-    }
-    return b;
-}
-static rth::ChildBox graft_host_box(const fyprt_context* c, int32_t ref) {
-    rth::ChildBox b;
-    for (int a = 0; a < 3; ++a) { b.lo[a] = 3.402823466e+38f; b.hi[a] = -3.402823466e+38f; }
-    if (ref >= 0) {
-        const rth::Node& n = c->hostBvh.nodes[(size_t)ref];
-        for (int i = 0; i < (int)(n.meta & 7u); ++i) { const rth::ChildBox cb = graft_plane_box(n, i); for (int a = 0; a < 3; ++a) b.hi[a] = std::max(b.hi[a], cb.hi[a]); }
-        for (int a = 0; a < 3; ++a) b.lo[a] = n.origin[a];
-        return b;
-    }
-    const uint32_t code = (uint32_t)~ref, first = code >> 2, m = (code & 3u) + 1u;
-    for (uint32_t j = 0; j < m; ++j) {
-        const uint32_t* t = &c->topoTris[(size_t)c->hostBvh.tris[first + j].tri * 4];
-        for (int k = 0; k < 3; ++k) for (int a = 0; a < 3; ++a) { const float v = c->hostVerts[t[k]].position[a]; b.lo[a] = std::min(b.lo[a], v); b.hi[a] = std::max(b.hi[a], v); }
-    }
-    return b;
-}
-
-static int partial_ensure_links(fyprt_context* c);      // rt_partial.h: the parent links (and exact boxes) of the tree as it is
 
 // parent[i] of the tree's inner nodes (the root keeps ~0u)
 static void graft_parents(const rth::SceneBVH& hb, std::vector<uint32_t>& parent) {
@@ -214,26 +170,12 @@ static void graft_place_host(const fyprt_context* c, const PlaceParams& pp, std:
     const std::vector<rth::Node>& hn = c->hostBvh.nodes;
     const uint32_t n = (uint32_t)hn.size();
     graft_parents(c->hostBvh, parent);
-    std::vector<uint32_t> order(n);
-    for (uint32_t i = 0; i < n; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return (hn[a].meta >> 3) < (hn[b].meta >> 3); });
-    std::vector<RBox> box(n);
-    auto child_box = [&](int32_t ref) {
-        if (ref >= 0) return box[(size_t)ref];
-        const rth::ChildBox cb = graft_host_box(c, ref);
-        RBox b; for (int a = 0; a < 3; ++a) { b.lo[a] = cb.lo[a]; b.hi[a] = cb.hi[a]; }
-        return b;
-    };
-    for (uint32_t X : order) {
-        RBox nb; for (int a = 0; a < 3; ++a) { nb.lo[a] = 3.402823466e+38f; nb.hi[a] = -3.402823466e+38f; }
-        for (uint32_t i = 0; i < (hn[X].meta & 7u); ++i) { const RBox b = child_box(hn[X].child[i]); for (int a = 0; a < 3; ++a) { nb.lo[a] = std::min(nb.lo[a], b.lo[a]); nb.hi[a] = std::max(nb.hi[a], b.hi[a]); } }
-        box[X] = nb;
-    }
+    const std::vector<RBox> box = host_exact_boxes(c);
     unsigned long long best = ~0ull; uint32_t found = 0;
     for (uint32_t X = 0; X < n; ++X) {
         const uint32_t cnt = hn[X].meta & 7u;
         RBox cb[4]; uint32_t childLevels[4] = {0, 0, 0, 0};
-        for (uint32_t i = 0; i < 4 && i < cnt; ++i) { cb[i] = child_box(hn[X].child[i]); if (hn[X].child[i] >= 0) childLevels[i] = hn[(size_t)hn[X].child[i]].meta >> 3; }
+        for (uint32_t i = 0; i < 4 && i < cnt; ++i) { cb[i] = host_child_box(c, box, hn[X].child[i]); if (hn[X].child[i] >= 0) childLevels[i] = hn[(size_t)hn[X].child[i]].meta >> 3; }
         float acc = place_growth(box[X], pp.B);
         uint32_t depth = 0;
         for (uint32_t p = parent[X]; p != ~0u; p = parent[p]) { acc = acc + place_growth(box[p], pp.B); ++depth; }
@@ -274,12 +216,7 @@ static int graft_append(fyprt_context* c, const fyprt_vertex* newVerts, uint32_t
     std::vector<uint32_t> parent;               // of the old nodes, when the place may lie below the root
     if (search) {
         PlaceParams pp;
-        for (int a = 0; a < 3; ++a) { pp.B.lo[a] = 3.402823466e+38f; pp.B.hi[a] = -3.402823466e+38f; }
-        for (uint32_t t = firstTri; t < firstTri + nT; ++t)
-            for (int k = 0; k < 3; ++k) for (int a = 0; a < 3; ++a) {
-                const float v = c->hostVerts[c->topoTris[(size_t)t * 4 + k]].position[a];
-                pp.B.lo[a] = std::min(pp.B.lo[a], v); pp.B.hi[a] = std::max(pp.B.hi[a], v);
-            }
+        pp.B = to_rbox(tri_range_box(c, firstTri, nT));
         pp.subLevels = subLevels; pp.root = (uint32_t)R;
         pp.slotOk = nodeBase + subNodes < (size_t)rth::kMaxNodes ? 1u : 0u; pp.pairOk = nodeBase + subNodes + 1u < (size_t)rth::kMaxNodes ? 1u : 0u;
         pp.rootPairOk = pp.pairOk && 1u + std::max(rLevels, subLevels) <= rth::kStackBudget ? 1u : 0u;
@@ -340,12 +277,7 @@ static int graft_append(fyprt_context* c, const fyprt_vertex* newVerts, uint32_t
         } else c->leafTris.n = c->leafTris.cap = (leafBase + nT) * 3;
     }
     // (a tree no refit pass has run on: the exact boxes of the old nodes first, once — the old grouping still describes them)
-    if (!c->hostOnly && !c->nodeBoxValid && !empty) {
-        for (uint32_t l = 1; l < (uint32_t)c->levelOffset.size() - 1u; ++l) {
-            const uint32_t first = c->levelOffset[l], count = c->levelOffset[l + 1] - first;
-            if (count) hipLaunchKernelGGL(k_graft_node_boxes, dim3((count + 127u) / 128u), dim3(128), 0, c->stream, (const float4*)c->nodes.p, (const uint32_t*)(c->levelNodes.p + first), count, (const float4*)c->leafTris.p, (const float4*)c->triPos.p, c->nodeBox.p);
-        }
-    }
+    TRY(ensure_node_boxes(c));
     // 4. the link, in the host's copy (topology and level counts; on a host-only context the planes too) and on the device.  `path`: the
     // nodes whose children changed, lowest first — the new pair node, the node that took the sub-tree, its ancestors up to the root
     const uint32_t N = (uint32_t)(total - 1);
@@ -374,31 +306,21 @@ static int graft_append(fyprt_context* c, const fyprt_vertex* newVerts, uint32_t
         for (uint32_t i = 0; i < (n.meta & 7u); ++i) if (n.child[i] >= 0) lv = std::max(lv, (uint32_t)(hb.nodes[(size_t)n.child[i]].meta >> 3));
         n.meta = (uint8_t)((n.meta & 7u) | ((lv + 1u) << 3));
         metas[k] = n.meta;
-        if (c->hostOnly) {                                           // quantised as the prune does it: the children's boxes from what the tree holds
-            const uint32_t cnt = n.meta & 7u; const uint8_t meta = n.meta;
-            rth::ChildBox boxes[4]; int32_t child[4];
-            for (uint32_t i = 0; i < 4; ++i) { child[i] = n.child[i]; if (i < cnt) boxes[i] = legacy && i < slot ? legacyBoxes[i] : graft_host_box(c, n.child[i]); }
-            rth::QuantiseNode(n, boxes, (int)cnt);
-            for (uint32_t i = 0; i < 4; ++i) n.child[i] = i < cnt ? child[i] : INT32_MIN;
-            n.meta = meta;
-        }
+        if (c->hostOnly) host_requantise(c, path[k], legacyBoxes, legacy ? slot : 0u);     // as the prune does it: the children's boxes from what the tree holds
     }
     if (!c->hostOnly && (kind == kSlot || kind == kPair))
         hipLaunchKernelGGL(k_graft_link, dim3(1), dim3(64), 0, c->stream, c->nodes.p, X, slot, 0, rth::device_ref(hb.nodes[X].child[slot]), (uint32_t)hb.nodes[X].meta, 0);
     // 5. boxes and quantisation of the new nodes, level by level, then of the path in one launch
     if (!c->hostOnly) {
-        std::vector<uint32_t> byLevel(rth::kStackBudget + 2u, 0u);
-        for (uint32_t i = 0; i < subNodes; ++i) byLevel[(hb.nodes[nodeBase + i].meta >> 3) + 1u]++;
-        for (size_t l = 1; l < byLevel.size(); ++l) byLevel[l] += byLevel[l - 1];
-        std::vector<uint32_t> list(subNodes + 2u * path.size()), fill(byLevel);
-        for (uint32_t i = 0; i < subNodes; ++i) list[fill[hb.nodes[nodeBase + i].meta >> 3]++] = (uint32_t)nodeBase + i;
-        std::copy(path.begin(), path.end(), list.begin() + subNodes); std::copy(metas.begin(), metas.end(), list.begin() + subNodes + path.size());
+        LevelGroups sub = group_by_level(hb.nodes.data() + nodeBase, subNodes, rth::kStackBudget, kEveryNode);
+        std::vector<uint32_t>& list = sub.order;                      // the new nodes by level, then the path, then the path's meta bytes
+        for (uint32_t& i : list) i += (uint32_t)nodeBase;
+        list.insert(list.end(), path.begin(), path.end()); list.insert(list.end(), metas.begin(), metas.end());
         if (c->graftList.n < list.size()) HIPCHK(c, c->graftList.alloc(std::max(list.size(), 2 * c->graftList.n)));
         TRY(upload(c, c->graftList.p, list.data(), list.size() * 4));
-        for (size_t l = 1; l + 1 < byLevel.size(); ++l) {
-            const uint32_t first = byLevel[l], count = byLevel[l + 1] - first;
-            if (count) hipLaunchKernelGGL(k_refit_level, dim3((count + 127u) / 128u), dim3(128), 0, c->stream, c->nodes.p, (const uint32_t*)(c->graftList.p + first), count, (const float4*)c->leafTris.p, (const float4*)c->triPos.p, c->nodeBox.p);
-        }
+        for_each_level(sub.offsets, [&](uint32_t first, uint32_t count, dim3 grid) {
+            hipLaunchKernelGGL(k_refit_level, grid, dim3(kLevelBlock), 0, c->stream, c->nodes.p, (const uint32_t*)(c->graftList.p + first), count, (const float4*)c->leafTris.p, (const float4*)c->triPos.p, c->nodeBox.p);
+        });
         if (!path.empty()) hipLaunchKernelGGL(k_graft_path, dim3(1), dim3(64), 0, c->stream, c->nodes.p, (const uint32_t*)(c->graftList.p + subNodes), (const uint32_t*)(c->graftList.p + subNodes + path.size()),
                                               (uint32_t)path.size(), (const float4*)c->leafTris.p, (const float4*)c->triPos.p, c->nodeBox.p);
         HIPCHK(c, hipGetLastError());
@@ -413,4 +335,17 @@ static int graft_append(fyprt_context* c, const fyprt_vertex* newVerts, uint32_t
     return upload_level_grouping(c, true);
 }
 
-}  // extern "C++"
+// graft_append, or, where the graft would be too deep or too large, the tree of the whole scene as an upload builds it (`who`: the
+// caller's name for its error texts), reported as kind 4.  The host builder reads every vertex: the first `staleVerts` of the host's
+// copy come back first if device edits left them behind.  `rebuilt`: NULL, or set when the tree was rebuilt.
+static int graft_or_rebuild(fyprt_context* c, const char* who, const fyprt_vertex* newVerts, uint32_t nV, uint32_t firstTri, uint32_t nT, const fyprt_mesh* meshes, uint32_t meshCount,
+                            uint32_t staleVerts, bool* rebuilt = nullptr) {
+    int rc = graft_append(c, newVerts, nV, firstTri, nT, meshes, meshCount);
+    if (rc != kGraftRebuild) return rc;
+    TRY(ensure_host_verts(c, staleVerts, true));
+    rc = build_scene_tree(c, who, c->hostVerts.data(), c->vertexCount, (const uint8_t*)c->topoTris.data(), 16, c->topoMeshes.data(), (uint32_t)c->topoMeshes.size(), (uint32_t)(c->topoTris.size() / 4));
+    c->placement.kind = 4u; c->placement.node = c->placement.slot = c->placement.depth = c->placement.cost_bits = c->placement.candidates = 0u;
+    c->placement.levels_after = c->hostBvh.levels;
+    if (rebuilt) *rebuilt = true;
+    return rc;
+}

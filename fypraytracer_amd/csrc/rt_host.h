@@ -1,6 +1,7 @@
 // Host-side data contracts of libfyprt: the acceleration-structure layout that is uploaded
 // to HBM and the builders' entry points.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <vector>
 #include "../../include/fyprt.h"
@@ -53,6 +54,13 @@ void BuildSceneBVH(const fyprt_vertex* verts, const uint8_t* tris, uint32_t triS
 // origin, grid exponents, child planes and the child count of `n` from `count` (2..4) boxes.  The node is cleared first: child
 // references and the level count are the caller's to fill in.
 struct ChildBox { float lo[3], hi[3]; };
+// ... and the box the host accumulates one: empty until the first point; binary32 min / max per axis, the box so far as first argument
+struct HostBox : ChildBox {
+    HostBox() { empty(); }
+    void empty() { for (int a = 0; a < 3; ++a) { lo[a] = 3.402823466e+38f; hi[a] = -3.402823466e+38f; } }
+    void grow(const float* p) { for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], p[a]); hi[a] = std::max(hi[a], p[a]); } }
+    template <class Box> void merge(const Box& b) { for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], b.lo[a]); hi[a] = std::max(hi[a], b.hi[a]); } }
+};
 void QuantiseNode(Node& n, const ChildBox* boxes, int count);
 
 struct LightTrees {

@@ -17,11 +17,10 @@
 // record of an unmoved triangle keeps its bytes.  Flags are cleared by the nodes themselves and the (at most 32) list counts by a
 // 128-byte memset: once the links exist, no launch runs over all triangles, all records or all nodes.
 // Flags and counts are plain words in global memory, touched inside a launch by agent-scope vector atomics only.
-// This header is part of fyprt.hip (it uses the context and its helpers) and is included there once.
+// This header is part of fyprt.hip (it uses the context and its helpers, rt_tree_host.h among them) and is included there once.
 #pragma once
-#include "rt_graft.h"
+#include "rt_refit.h"
 
-extern "C++" {
 namespace rt {
 
 constexpr uint32_t kPartialLevels = 32;         // list counts: [l] = dirty nodes of level l (1..31), [0] = leaf records rewritten
@@ -150,17 +149,6 @@ __global__ __launch_bounds__(256) void k_partial_refit_tail(float4* nodes, uint3
 
 // ---- host side
 
-// nodeBox of every node of a tree no refit pass has run on (a host-built one), level by level: what the graft does before it refits
-static int partial_node_boxes(fyprt_context* c) {
-    for (uint32_t l = 1; l + 1u < (uint32_t)c->levelOffset.size(); ++l) {
-        const uint32_t first = c->levelOffset[l], count = c->levelOffset[l + 1] - first;
-        if (count) hipLaunchKernelGGL(k_graft_node_boxes, dim3((count + 127u) / 128u), dim3(128), 0, c->stream, (const float4*)c->nodes.p, (const uint32_t*)(c->levelNodes.p + first), count, (const float4*)c->leafTris.p, (const float4*)c->triPos.p, c->nodeBox.p);
-    }
-    HIPCHK(c, hipGetLastError());
-    c->nodeBoxValid = true;
-    return FYPRT_OK;
-}
-
 // The three maps and the scratch of the walk, (re)built for the tree as it is: 4 bytes per node, leaf record and triangle for the maps,
 // 8 bytes per node (lists, flags) + 128 bytes (counts) for the scratch.  Kept until the topology changes (fyprt_context::linksValid).
 static int partial_ensure_links(fyprt_context* c) {
@@ -182,8 +170,7 @@ static int partial_ensure_links(fyprt_context* c) {
         }
         c->linksValid = true;
     }
-    if (!c->nodeBoxValid && nNodes) TRY(partial_node_boxes(c));
-    return FYPRT_OK;
+    return ensure_node_boxes(c);
 }
 
 // The walk for the listed meshes (distinct), whose new world vertices the context stream has written or will have written by now:
@@ -203,7 +190,7 @@ static int run_partial_refit(fyprt_context* c, const std::vector<uint32_t>& mesh
     for (uint32_t m : meshes) {
         const uint32_t first = c->topoMeshes[m].first_triangle, n = c->topoMeshes[m].triangle_count;
         if (!n) continue;
-        hipLaunchKernelGGL(k_refresh_triangles, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, c->dverts.p, c->triIdx.p + first, c->triPos.p + (size_t)first * 3, c->triShade.p + (size_t)first * 4, n);
+        TRY(launch_refresh_triangles(c, first, n));
         hipLaunchKernelGGL(k_partial_seed, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, first, n, (const float4*)c->triPos.p, c->leafTris.p, nLeaf, (const uint32_t*)c->leafOfTri.p,
                            (const uint32_t*)c->leafParent.p, (const float4*)c->nodes.p, nNodes, c->partialDirty.p, c->partialLists.p, c->partialCounters.p, lv);
     }
@@ -244,8 +231,6 @@ static void partial_finish_stats(fyprt_context* c) {
 static void full_edit_stats(fyprt_context* c) {
     fyprt_edit_stats& st = c->editStats;
     st = fyprt_edit_stats{0u, (uint32_t)(c->topoTris.size() / 4), (uint32_t)c->hostBvh.tris.size(), (uint32_t)c->hostBvh.nodes.size(), 0u};
-    for (uint32_t l = 1; l + 1u < (uint32_t)c->levelOffset.size() && l <= c->hostBvh.levels; ++l) st.level_launches += c->levelOffset[l + 1] > c->levelOffset[l] ? 1u : 0u;
+    for_each_level(c->levelOffset, [&](uint32_t, uint32_t, dim3) { ++st.level_launches; });
     c->haveEditStats = true;
 }
-
-}  // extern "C++"

@@ -24,7 +24,6 @@
 #include "rt_graft.h"
 #include "rt_materials.h"
 
-extern "C++" {
 namespace rt {
 
 constexpr uint32_t kPruneLds = 1024;                  // table entries kept in LDS; a longer table is searched in global memory
@@ -212,11 +211,7 @@ struct PruneTable {
 // surviving nodes that lost a triangle below them, lowest level first; `refitLevel` = where each level's nodes begin in it.
 static void prune_host_tree(rth::SceneBVH& hb, const std::vector<uint32_t>& deadBefore, std::vector<uint32_t>& refit, std::vector<uint32_t>& refitLevel) {
     const size_t nN = hb.nodes.size();
-    std::vector<uint32_t> first(rth::kStackBudget + 3u, 0u);
-    for (const rth::Node& n : hb.nodes) first[(n.meta >> 3) + 1u]++;
-    for (size_t l = 1; l < first.size(); ++l) first[l] += first[l - 1];
-    std::vector<uint32_t> order(nN), fill(first);
-    for (uint32_t i = 0; i < (uint32_t)nN; ++i) order[fill[hb.nodes[i].meta >> 3]++] = i;
+    const std::vector<uint32_t> order = group_by_level(hb.nodes.data(), nN, rth::kStackBudget, kEveryNode).order;
     std::vector<int32_t> repl(nN, rt::kPruneDead); std::vector<uint8_t> alive(nN, 0), lost(nN, 0);
     bool rootLost = false;
     auto resolve = [&](int32_t child, bool& lostAny) -> int32_t {
@@ -244,11 +239,9 @@ static void prune_host_tree(rth::SceneBVH& hb, const std::vector<uint32_t>& dead
     const int32_t root = deadBefore.size() <= 1 ? rt::kPruneDead : resolve(hb.rootRef, rootLost);
     std::vector<uint32_t> newIndex(nN, 0); uint32_t nAlive = 0;
     for (size_t i = 0; i < nN; ++i) { newIndex[i] = nAlive; nAlive += alive[i]; }
-    std::vector<uint32_t> count(rth::kStackBudget + 3u, 0u);
-    for (size_t i = 0; i < nN; ++i) if (alive[i] && lost[i]) count[(hb.nodes[i].meta >> 3) + 1u]++;
-    for (size_t l = 1; l < count.size(); ++l) count[l] += count[l - 1];
-    refitLevel = count; refit.assign(count.back(), 0u); fill = count;
-    for (size_t i = 0; i < nN; ++i) if (alive[i] && lost[i]) refit[fill[hb.nodes[i].meta >> 3]++] = newIndex[i];
+    LevelGroups g = group_by_level(hb.nodes.data(), nN, rth::kStackBudget, [&](uint32_t i) { return alive[i] && lost[i]; });
+    refitLevel.swap(g.offsets); refit.swap(g.order);
+    for (uint32_t& i : refit) i = newIndex[i];
     for (size_t i = 0; i < nN; ++i) {
         if (!alive[i]) continue;
         rth::Node n = hb.nodes[i];
@@ -304,16 +297,7 @@ static int prune_tree(fyprt_context* c, const char* who, const PruneTable& tris,
     const bool dev = !c->hostOnly;
     c->linksValid = false;                     // nodes and records are renumbered: the partial refit's maps are rebuilt
     DevBuf<uint32_t> deadBeforeDev, alive, newIndex; DevBuf<int32_t> repl;      // the node pass's arrays, freed on every way out
-    if (dev) {
-        // exact boxes of a tree no refit pass has run on (the old grouping describes it): what k_refit_level reads of untouched children
-        if (!c->nodeBoxValid && nNodes) {
-            for (uint32_t l = 1; l + 1u < (uint32_t)c->levelOffset.size(); ++l) {
-                const uint32_t first = c->levelOffset[l], count = c->levelOffset[l + 1] - first;
-                if (count) hipLaunchKernelGGL(k_graft_node_boxes, dim3((count + 127u) / 128u), dim3(128), 0, c->stream, (const float4*)c->nodes.p, (const uint32_t*)(c->levelNodes.p + first), count, (const float4*)c->leafTris.p, (const float4*)c->triPos.p, c->nodeBox.p);
-            }
-            HIPCHK(c, hipGetLastError());
-        }
-    }
+    TRY(ensure_node_boxes(c));                 // (the old grouping describes the tree: what k_refit_level reads of untouched children)
     // 1. leaf records: compacted, their triangle indices remapped; the dead counts go to the node pass here and on the host
     std::vector<uint32_t> deadBefore((size_t)nLeaf + 1u, 0u);
     if (dev) {
@@ -327,10 +311,9 @@ static int prune_tree(fyprt_context* c, const char* who, const PruneTable& tris,
         // 2. the node pass on the old array, level by level, then the alive scan and the move
         if (nNodes) {
             HIPCHK(c, repl.alloc(nNodes)); HIPCHK(c, alive.alloc(nNodes)); HIPCHK(c, newIndex.alloc(nNodes));
-            for (uint32_t l = 1; l + 1u < (uint32_t)c->levelOffset.size(); ++l) {
-                const uint32_t first = c->levelOffset[l], count = c->levelOffset[l + 1] - first;
-                if (count) hipLaunchKernelGGL(k_prune_level, dim3((count + 127u) / 128u), dim3(128), 0, c->stream, c->nodes.p, (const uint32_t*)(c->levelNodes.p + first), count, (const uint32_t*)deadBeforeDev.p, repl.p, alive.p);
-            }
+            for_each_level(c->levelOffset, [&](uint32_t first, uint32_t count, dim3 grid) {
+                hipLaunchKernelGGL(k_prune_level, grid, dim3(kLevelBlock), 0, c->stream, c->nodes.p, (const uint32_t*)(c->levelNodes.p + first), count, (const uint32_t*)deadBeforeDev.p, repl.p, alive.p);
+            });
             HIPCHK(c, hipGetLastError());
         }
         nl.n = (size_t)T * 3;
@@ -366,36 +349,23 @@ static int prune_tree(fyprt_context* c, const char* who, const PruneTable& tris,
 // ... and its last step, once the surviving records' triangles are where the records say: boxes and quantisation of the surviving nodes
 // that lost a triangle below them, lowest level first, then the level grouping of the pruned tree.  Complete on return.
 static int prune_refit(fyprt_context* c, const std::vector<uint32_t>& refit, const std::vector<uint32_t>& refitLevel) {
-    rth::SceneBVH& hb = c->hostBvh;
     if (!c->hostOnly) {
         DevBuf<uint32_t> refitList;
         if (!refit.empty()) {
             TRY(alloc_upload(c, refitList, refit.data(), refit.size()));
-            for (size_t l = 1; l + 1 < refitLevel.size(); ++l) {
-                const uint32_t first = refitLevel[l], count = refitLevel[l + 1] - first;
-                if (count) hipLaunchKernelGGL(k_refit_level, dim3((count + 127u) / 128u), dim3(128), 0, c->stream, c->nodes.p, (const uint32_t*)(refitList.p + first), count, (const float4*)c->leafTris.p, (const float4*)c->triPos.p, c->nodeBox.p);
-            }
+            for_each_level(refitLevel, [&](uint32_t first, uint32_t count, dim3 grid) {
+                hipLaunchKernelGGL(k_refit_level, grid, dim3(kLevelBlock), 0, c->stream, c->nodes.p, (const uint32_t*)(refitList.p + first), count, (const float4*)c->leafTris.p, (const float4*)c->triPos.p, c->nodeBox.p);
+            });
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, hipStreamSynchronize(c->stream));                  // the list is scratch of this step
         }
         c->nodeBoxValid = true; c->hostBvhStale = true;               // planes and leaf records live on the device: an export reads them back
-    } else {
-        for (uint32_t i : refit) {
-            rth::Node& n = hb.nodes[i];
-            const uint32_t k = n.meta & 7u; const uint8_t meta = n.meta;
-            rth::ChildBox boxes[4]; int32_t child[4];
-            for (uint32_t s = 0; s < 4; ++s) { child[s] = n.child[s]; if (s < k) boxes[s] = graft_host_box(c, n.child[s]); }
-            rth::QuantiseNode(n, boxes, (int)k);
-            for (uint32_t s = 0; s < 4; ++s) n.child[s] = s < k ? child[s] : INT32_MIN;
-            n.meta = meta;
-        }
-    }
+    } else for (uint32_t i : refit) host_requantise(c, i);
     return upload_level_grouping(c, true);
 }
 
 // The removal proper, after every check: `tris` / `verts` the removed triangle and vertex intervals, `gone[m]` the listed meshes.
 static int prune_remove(fyprt_context* c, const PruneTable& tris, const PruneTable& verts, const std::vector<uint8_t>& gone) {
-    rth::SceneBVH& hb = c->hostBvh;
     const uint32_t T0 = (uint32_t)(c->topoTris.size() / 4), V0 = c->vertexCount, M0 = (uint32_t)c->topoMeshes.size();
     const uint32_t T = T0 - tris.removed, V = V0 - verts.removed;
     const bool dev = !c->hostOnly;
@@ -447,9 +417,8 @@ static int prune_remove(fyprt_context* c, const PruneTable& tris, const PruneTab
     }
     // 5. boxes and quantisation of the surviving nodes that lost a triangle below them, lowest level first
     TRY(prune_refit(c, refit, refitLevel));
+    set_scene_triangles(c, T);
     DevScene& d = c->dsc;
-    d.nodes = c->nodes.p; d.leafTris = c->leafTris.p; d.rootRef = rth::device_ref(hb.rootRef); d.triCount = T;
-    d.triPos = c->triPos.p; d.triShade = c->triShade.p;
     // 6. lights.  The emissive list: the old one, explicit or derived, without the removed triangles, remapped, in order
     const uint32_t nE0 = dev ? d.emissiveCount : (uint32_t)c->hostEmissive.size();
     uint32_t nE = 0;
@@ -470,11 +439,9 @@ static int prune_remove(fyprt_context* c, const PruneTable& tris, const PruneTab
     } else if (!dev) c->emissive.n = c->emissive.cap = nE;
     c->lightRecs.n = (size_t)nE * 3; if (!dev) c->lightRecs.cap = c->lightRecs.n;
     d.emissive = c->emissive.p; d.emissiveCount = nE; d.lightRecs = c->lightRecs.p;
-    if (dev && nE) { hipLaunchKernelGGL(k_build_light_records, dim3((nE + 255u) / 256u), dim3(256), 0, c->stream, d, c->lightRecs.p); HIPCHK(c, hipGetLastError()); }
+    TRY(launch_light_records(c));
     // ... and the light trees of the meshes that stayed + the TLAS, on the host, with the emitter -> TLAS-leaf table of the shorter list
     TRY(rebuild_light_trees(c, c->hostVerts.data()));
     if (dev) HIPCHK(c, sync_all(c));
     return FYPRT_OK;
 }
-
-}  // extern "C++"

@@ -175,6 +175,21 @@ __global__ __launch_bounds__(128) void k_refit_level(float4* nodes, const uint32
     refit_node(nodes, levelNodes[k], leafTris, triPos, nodeBox);
 }
 
+// nodeBox of the listed nodes of one level (levels = 1 first), nothing else written: the box half of k_refit_level
+__global__ __launch_bounds__(128) void k_graft_node_boxes(const float4* nodes, const uint32_t* levelNodes, uint32_t count, const float4* leafTris, const float4* triPos, float4* nodeBox) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= count) return;
+    const uint32_t node = levelNodes[k];
+    const float4* n = nodes + (size_t)node * 4;
+    const float4 q0 = n[0], q1 = n[1];
+    const uint32_t cnt = ((uint32_t)__float_as_int(q0.w) >> 24) & 7u;
+    const int32_t child[4] = {__float_as_int(q1.x), __float_as_int(q1.y), __float_as_int(q1.z), __float_as_int(q1.w)};
+    RBox cb[4]; RBox nb;
+    refit_child_boxes(cnt, child, leafTris, triPos, nodeBox, cb, nb);
+    nodeBox[(size_t)node * 2] = make_float4(nb.lo[0], nb.lo[1], nb.lo[2], 0.0f);
+    nodeBox[(size_t)node * 2 + 1] = make_float4(nb.hi[0], nb.hi[1], nb.hi[2], 0.0f);
+}
+
 // The reference keeps ONE pair of octahedral-normal buffers for both ReSTIRs (R.cu: normalBuffers prev / cur, swapped after every ReSTIR
 // frame), so the "previous normal" a ReSTIR DI frame tests its history against is the last ReSTIR frame's — also when that was a GI
 // frame — and vice versa.  Here the DI history carries its normal inside the 32-byte record and GI has its own normal buffers; when

@@ -16,7 +16,6 @@
 #pragma once
 #include "rt_graft.h"
 
-extern "C++" {
 namespace rt {
 
 constexpr uint32_t kCostBlock = 256;
@@ -66,28 +65,18 @@ static void tree_cost_host(const fyprt_context* c, fyprt_tree_cost_sums* out) {
     const rth::SceneBVH& hb = c->hostBvh;
     const std::vector<rth::Node>& hn = hb.nodes;
     const uint32_t n = (uint32_t)hn.size();
-    auto leaf_box = [&](int32_t ref) { const rth::ChildBox cb = graft_host_box(c, ref); RBox b; for (int a = 0; a < 3; ++a) { b.lo[a] = cb.lo[a]; b.hi[a] = cb.hi[a]; } return b; };
+    auto leaf_term = [&](int32_t ref) { return (double)(((uint32_t)~ref & 3u) + 1u) * (double)place_area(to_rbox(graft_host_box(c, ref))); };
     if (n == 0) {                                        // a leaf-code root: the one leaf child
-        const RBox b = leaf_box(hb.rootRef);
-        out->root_area = (double)place_area(b);
-        out->leaf_area = (double)(((uint32_t)~hb.rootRef & 3u) + 1u) * (double)place_area(b);
+        out->root_area = (double)place_area(to_rbox(graft_host_box(c, hb.rootRef)));
+        out->leaf_area = leaf_term(hb.rootRef);
         return;
     }
-    std::vector<uint32_t> order(n);
-    for (uint32_t i = 0; i < n; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return (hn[a].meta >> 3) < (hn[b].meta >> 3); });
-    std::vector<RBox> box(n); std::vector<double> leaf(n, 0.0);
-    for (uint32_t X : order) {
-        RBox nb; for (int a = 0; a < 3; ++a) { nb.lo[a] = 3.402823466e+38f; nb.hi[a] = -3.402823466e+38f; }
-        for (uint32_t i = 0; i < (hn[X].meta & 7u); ++i) {
-            const int32_t ref = hn[X].child[i];
-            const RBox b = ref >= 0 ? box[(size_t)ref] : leaf_box(ref);
-            if (ref < 0) leaf[X] = leaf[X] + (double)(((uint32_t)~ref & 3u) + 1u) * (double)place_area(b);
-            for (int a = 0; a < 3; ++a) { nb.lo[a] = std::min(nb.lo[a], b.lo[a]); nb.hi[a] = std::max(nb.hi[a], b.hi[a]); }
-        }
-        box[X] = nb;
+    const std::vector<RBox> box = host_exact_boxes(c);
+    for (uint32_t X = 0; X < n; ++X) {
+        double leaf = 0.0;
+        for (uint32_t i = 0; i < (hn[X].meta & 7u); ++i) if (hn[X].child[i] < 0) leaf = leaf + leaf_term(hn[X].child[i]);
+        out->inner_area += (double)place_area(box[X]); out->leaf_area += leaf;
     }
-    for (uint32_t X = 0; X < n; ++X) { out->inner_area += (double)place_area(box[X]); out->leaf_area += leaf[X]; }
     out->root_area = (double)place_area(box[(size_t)hb.rootRef]);
 }
 
@@ -102,7 +91,7 @@ static int tree_cost(fyprt_context* c, fyprt_tree_cost_sums* out) {
     const uint32_t nNodes = out->nodes, blocks = std::max(1u, (nNodes + kCostBlock - 1u) / kCostBlock);
     const size_t words = 2u + 2u * (size_t)blocks;
     if (c->costPartials.n < words) HIPCHK(c, c->costPartials.alloc(std::max(words, 2 * c->costPartials.n)));
-    if (!c->nodeBoxValid && nNodes) TRY(partial_node_boxes(c));
+    TRY(ensure_node_boxes(c));
     hipLaunchKernelGGL(k_tree_cost, dim3(blocks), dim3(kCostBlock), 0, c->stream, (const float4*)c->nodes.p, nNodes, rth::device_ref(hb.rootRef), (const float4*)c->leafTris.p,
                        (const float4*)c->triPos.p, (const float4*)c->nodeBox.p, c->costPartials.p);
     HIPCHK(c, hipGetLastError());
@@ -113,5 +102,3 @@ static int tree_cost(fyprt_context* c, fyprt_tree_cost_sums* out) {
     for (uint32_t b = 0; b < blocks; ++b) { out->inner_area += part[2 + 2 * (size_t)b]; out->leaf_area += part[3 + 2 * (size_t)b]; }
     return FYPRT_OK;
 }
-
-}  // extern "C++"
