@@ -603,11 +603,18 @@ static int build_device_lbvh(fyprt_context* c, const fyprt_vertex* verts, uint32
 }
 
 // The host light trees (c->hostLt) onto the device, with the emitter -> TLAS-leaf table, and into the scene descriptor.
-static int upload_light_trees(fyprt_context* c, uint32_t nT, uint32_t nM) {
+// `keep` (a removal): the per-mesh and per-triangle tables are written into the buffers they have (the scene shrank: they fit), so their
+// capacity stays, as the capacity of the scene's arrays does, and a later append of the removed size fits without growing
+static int upload_light_table(fyprt_context* c, DevBuf<uint32_t>& b, const uint32_t* src, size_t count, bool keep) {
+    if (!keep || c->hostOnly || count > b.cap) return alloc_upload(c, b, src, count);
+    b.n = count;
+    return upload(c, b.p, src, b.bytes());
+}
+static int upload_light_trees(fyprt_context* c, uint32_t nT, uint32_t nM, bool keep = false) {
     const rth::LightTrees& lt = c->hostLt;
     static_assert(sizeof(DevLTNode) == sizeof(fyprt_lighttree_node), "light tree node layout");
     TRY(alloc_upload(c, c->ltTlas, lt.tlas.data(), lt.tlas.size())); TRY(alloc_upload(c, c->ltBlas, lt.blas.data(), lt.blas.size()));
-    TRY(alloc_upload(c, c->ltFirst, lt.first.data(), nM)); TRY(alloc_upload(c, c->ltCount, lt.count.data(), nM)); TRY(alloc_upload(c, c->ltRoot, lt.root.data(), nM));
+    TRY(upload_light_table(c, c->ltFirst, lt.first.data(), nM, keep)); TRY(upload_light_table(c, c->ltCount, lt.count.data(), nM, keep)); TRY(upload_light_table(c, c->ltRoot, lt.root.data(), nM, keep));
     // ComputeDirectEmitterPMF (LightTree.cu:170-199) starts with a linear search for the first TLAS leaf whose mesh tree
     // holds the emitter; the answer does not depend on the shading point, so it is tabled per triangle here (same search
     // order: first match wins).
@@ -621,10 +628,31 @@ static int upload_light_trees(fyprt_context* c, uint32_t nT, uint32_t nM) {
             if (n.is_leaf && n.right_or_emitter < nT && leafOfTri[n.right_or_emitter] == ~0u) leafOfTri[n.right_or_emitter] = i;
         }
     }
-    TRY(alloc_upload(c, c->ltLeafOfTri, leafOfTri.data(), nT));
+    TRY(upload_light_table(c, c->ltLeafOfTri, leafOfTri.data(), nT, keep));
     DevScene& d = c->dsc;
     d.ltLeafOfTri = c->ltLeafOfTri.p; d.ltTlas = c->ltTlas.p; d.ltTlasCount = (uint32_t)lt.tlas.size(); d.ltTlasRoot = lt.tlasRoot;
     d.ltBlas = c->ltBlas.p; d.ltFirst = c->ltFirst.p; d.ltCount = c->ltCount.p; d.ltRoot = c->ltRoot.p;
+    return FYPRT_OK;
+}
+
+// An append that brings no emitter changes no light tree, but the per-triangle and per-mesh tables must cover the combined scene as
+// upload_light_trees leaves them: a removal sizes its tables by the scene it finds, and fyprt_remove_meshes promises never to grow the
+// device memory.  The tables grow like the scene's arrays (grow_buffer) and move device to device; the new triangles lie in no TLAS leaf
+// and the new meshes have no tree (their entries of c->hostLt go up: 12 bytes per new mesh).  All streams are idle.
+static int extend_light_tables(fyprt_context* c, uint32_t nT, uint32_t nM) {
+    const rth::LightTrees& lt = c->hostLt;
+    const size_t t0 = c->ltLeafOfTri.n, m0 = c->ltFirst.n;
+    if (nT < t0 || nM < m0 || lt.first.size() < nM) return c->fail(FYPRT_EHIP, "fyprt_append_meshes: the light tables do not cover the scene before the append");
+    TRY(grow_buffer(c, c->ltLeafOfTri, nT)); TRY(grow_buffer(c, c->ltFirst, nM)); TRY(grow_buffer(c, c->ltCount, nM)); TRY(grow_buffer(c, c->ltRoot, nM));
+    if (c->hostOnly) return FYPRT_OK;
+    if (nT > t0) HIPCHK(c, hipMemsetAsync(c->ltLeafOfTri.p + t0, 0xFF, (nT - t0) * sizeof(uint32_t), c->stream));
+    if (nM > m0) {
+        TRY(upload(c, c->ltFirst.p + m0, lt.first.data() + m0, (nM - m0) * sizeof(uint32_t)));
+        TRY(upload(c, c->ltCount.p + m0, lt.count.data() + m0, (nM - m0) * sizeof(uint32_t)));
+        TRY(upload(c, c->ltRoot.p + m0, lt.root.data() + m0, (nM - m0) * sizeof(uint32_t)));
+    }
+    DevScene& d = c->dsc;
+    d.ltLeafOfTri = c->ltLeafOfTri.p; d.ltFirst = c->ltFirst.p; d.ltCount = c->ltCount.p; d.ltRoot = c->ltRoot.p;
     return FYPRT_OK;
 }
 
@@ -773,12 +801,12 @@ int fyprt_upload_scene(fyprt_context* c, const fyprt_scene_desc* s) {
 }
 
 // (Re)build the light trees from the given vertices with the stored topology and upload them (+ the emitter -> TLAS-leaf table).
-static int rebuild_light_trees(fyprt_context* c, const fyprt_vertex* verts, const uint8_t* touched = nullptr) {
+static int rebuild_light_trees(fyprt_context* c, const fyprt_vertex* verts, const uint8_t* touched = nullptr, bool keep = false) {
     rth::LightTrees& lt = c->hostLt;
     if (!touched) lt = rth::LightTrees();
     const uint32_t nT = (uint32_t)(c->topoTris.size() / 4), nM = (uint32_t)c->topoMeshes.size();
     rth::BuildLightTrees(verts, (const uint8_t*)c->topoTris.data(), 16, c->topoMeshes.data(), nM, c->topoMats.data(), lt, touched);
-    return upload_light_trees(c, nT, nM);
+    return upload_light_trees(c, nT, nM, keep);
 }
 
 // What a geometry edit means to the temporal denoiser (all streams idle).  Motion mode off: the history is dropped.  On: it is kept, and
@@ -1256,6 +1284,7 @@ int fyprt_append_meshes(fyprt_context* c, const fyprt_vertex* vertices, uint32_t
         }
         if (newLight) TRY(rebuild_light_trees(c, c->hostVerts.data(), touched.data()));
         else if (!tail.empty()) TRY(upload_light_trees(c, T, M));                          // the emitter -> TLAS-leaf table covers the new triangles
+        else TRY(extend_light_tables(c, T, M));                                            // no emitter came: the tables grow on the device
     }
     if (!c->hostOnly) HIPCHK(c, sync_all(c));
     return FYPRT_OK;

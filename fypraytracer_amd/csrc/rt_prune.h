@@ -441,7 +441,7 @@ static int prune_remove(fyprt_context* c, const PruneTable& tris, const PruneTab
     d.emissive = c->emissive.p; d.emissiveCount = nE; d.lightRecs = c->lightRecs.p;
     TRY(launch_light_records(c));
     // ... and the light trees of the meshes that stayed + the TLAS, on the host, with the emitter -> TLAS-leaf table of the shorter list
-    TRY(rebuild_light_trees(c, c->hostVerts.data()));
+    TRY(rebuild_light_trees(c, c->hostVerts.data(), nullptr, true));   // (the tables keep their capacity)
     if (dev) HIPCHK(c, sync_all(c));
     return FYPRT_OK;
 }

@@ -292,7 +292,8 @@ int fyprt_update_materials(fyprt_context* ctx, const fyprt_material* materials, 
  * Cost: of the old scene only the per-node level grouping (4 bytes per node) crosses the bus; the scene's device arrays have a capacity that at
  * least doubles when exceeded and move device to device (fyprt_live_device_bytes counts the capacity); per-triangle records, emissive list
  * (an ordered compaction over the appended range), light records and the refit run on the device; the light trees of the new emissive meshes
- * and the TLAS are built on the host.  An append without an emitter leaves the lights alone.
+ * and the TLAS are built on the host.  An append without an emitter leaves the lights alone; its per-triangle and per-mesh light tables grow
+ * on the device like the scene's arrays, so that they cover the combined scene (a removal writes them in place and keeps their capacity).
  * Blocking: pipelined frames are waited for first, everything the call launches is complete on return.  Errors, in this order: FYPRT_EINVAL
  * for a NULL context, a NULL array with a non-zero count (or object_vertices without mesh_first_vertex), triangle_stride < 16, a vertex index
  * >= the combined vertex count, a material index outside the current table, meshes that do not partition the appended range in order,

@@ -10,7 +10,8 @@ import pytest
 
 import placement_ref as pr
 from append_common import SIZES, add_emitter_material, append_patch, check_graft
-from common import SCENES, check_bvh_invariants, struct_equal
+from common import SCENES, check_bvh_invariants
+from edit_sequences import same_exports as same_light_exports
 from fypraytracer_amd import capi
 from fypraytracer_amd.scene import Scene
 from remove_common import check_prune, removed_triangles
@@ -21,17 +22,6 @@ EINVAL, ESTATE = -1, -3
 # the first and a free slot two levels down for the second; hall_small takes pairs three levels down.
 SHIFTS = {"cornell": ((0.0, 0.0, 0.0), (0.3, -0.7, 0.8)), "hall_small": ((0.0, 0.0, 0.0), (-4.0, 0.5, -3.0))}
 CASES = [(name, n, k) for name in ("cornell", "hall_small") for n in (SIZES[0], SIZES[2], SIZES[3]) for k in (0, 1)]
-
-
-def same_light_exports(a, b, n_meshes):
-    """(same_exports of test_gpu_materials.py)"""
-    la, lb = a.export_lighttrees(n_meshes), b.export_lighttrees(n_meshes)
-    for k in ("tlas", "blas"):
-        assert len(la[k]) == len(lb[k]) and struct_equal(la[k], lb[k]).all(), k
-    assert la["tlas_root"] == lb["tlas_root"]
-    for k in ("blas_first", "blas_count", "blas_root"):
-        assert np.array_equal(la[k], lb[k]), k
-    assert np.array_equal(a.export_emissive(), b.export_emissive())
 
 
 def host(sc, mode=None):

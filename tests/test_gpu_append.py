@@ -14,6 +14,7 @@ import pytest
 
 from append_common import SIZES, add_emitter_material, append_patch, check_graft
 from common import SCENES, bits_equal, check_bvh_invariants, settings_for, struct_equal
+from edit_sequences import same_exports
 from fypraytracer_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -55,16 +56,6 @@ def _frames_equal(ctx, orc, tech, seeds, tag):
         if tech == capi.RESTIR_DI:
             for buf in (capi.BUF_DI, capi.BUF_DI_PREV):
                 assert struct_equal(ctx.read_buffer(buf), orc.read_buffer(buf)).all(), (tag, seed, buf)
-
-
-def same_exports(a, b, n_meshes):
-    la, lb = a.export_lighttrees(n_meshes), b.export_lighttrees(n_meshes)
-    for k in ("tlas", "blas"):
-        assert len(la[k]) == len(lb[k]) and struct_equal(la[k], lb[k]).all(), k
-    assert la["tlas_root"] == lb["tlas_root"]
-    for k in ("blas_first", "blas_count", "blas_root"):
-        assert np.array_equal(la[k], lb[k]), k
-    assert np.array_equal(a.export_emissive(), b.export_emissive())
 
 
 # ---- A

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from common import SCENES, bits_equal, settings_for, struct_equal
+from edit_sequences import same_exports
 from fypraytracer_amd import capi
 from fypraytracer_amd.scene import Material, Scene
 
@@ -28,16 +29,6 @@ def _ctx(sc, cam):
     ctx.upload_scene(sc)
     ctx.set_camera(cam)
     return ctx
-
-
-def same_exports(a, b, n_meshes):
-    la, lb = a.export_lighttrees(n_meshes), b.export_lighttrees(n_meshes)
-    for k in ("tlas", "blas"):
-        assert len(la[k]) == len(lb[k]) and struct_equal(la[k], lb[k]).all(), k
-    assert la["tlas_root"] == lb["tlas_root"]
-    for k in ("blas_first", "blas_count", "blas_root"):
-        assert np.array_equal(la[k], lb[k]), k
-    assert np.array_equal(a.export_emissive(), b.export_emissive())
 
 
 def same_frames(a, b, techs=TECHS, seed0=10):

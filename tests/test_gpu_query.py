@@ -10,6 +10,7 @@ import pytest
 
 import bruteforce
 from common import SCENES, bits_equal, settings_for
+from edit_sequences import _scene_bvh
 from fypraytracer_amd import capi, scenes
 
 pytestmark = pytest.mark.gpu
@@ -250,16 +251,6 @@ def test_invalid_rays_empty_and_misaligned_calls():
     assert ctx.lib.fyprt_trace_rays_device(ctx.h, capi.QUERY_CLOSEST, img + 4, 1, img + 64) == -1
     assert ctx.lib.fyprt_trace_rays_device(ctx.h, capi.QUERY_CLOSEST, img, 1, img + 36) == -1
     ctx.close()
-
-
-def _scene_bvh(sc):
-    """Leaf records straight from the scene's world vertices (what the device must hold after an edit), in export_bvh's shape."""
-    pos = sc.world_vertices["position"].astype(F32)
-    t = sc.triangles
-    tris = np.zeros(len(t), dtype=capi.BVH_TRI_DTYPE)
-    tris["v0"], tris["e1"], tris["e2"] = pos[t["v0"]], pos[t["v1"]] - pos[t["v0"]], pos[t["v2"]] - pos[t["v0"]]
-    tris["tri"] = np.arange(len(t), dtype=np.uint32)
-    return {"tris": tris}
 
 
 def test_queries_see_current_geometry(oracle_built):

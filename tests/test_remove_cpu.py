@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 
 from append_common import add_emitter_material, append_patch, check_graft
-from common import SCENES, check_bvh_invariants, struct_equal
+from common import SCENES, check_bvh_invariants
+from edit_sequences import same_exports as same_light_exports
 from fypraytracer_amd import capi
 from fypraytracer_amd.scene import Scene
 from remove_common import BRANCHES, LOSES, check_prune, removed_triangles
@@ -18,17 +19,6 @@ from remove_common import BRANCHES, LOSES, check_prune, removed_triangles
 W, H = 128, 80
 EINVAL, ESTATE = -1, -3
 MET = set()                        # the branches of the prune rule the tests of this module met, in file order
-
-
-def same_light_exports(a, b, n_meshes):
-    """(same_exports of test_gpu_materials.py)"""
-    la, lb = a.export_lighttrees(n_meshes), b.export_lighttrees(n_meshes)
-    for k in ("tlas", "blas"):
-        assert len(la[k]) == len(lb[k]) and struct_equal(la[k], lb[k]).all(), k
-    assert la["tlas_root"] == lb["tlas_root"]
-    for k in ("blas_first", "blas_count", "blas_root"):
-        assert np.array_equal(la[k], lb[k]), k
-    assert np.array_equal(a.export_emissive(), b.export_emissive())
 
 
 def fresh_host(sc):
