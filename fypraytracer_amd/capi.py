@@ -240,6 +240,7 @@ EXPORTED_SYMBOLS = [
     "fyprt_update_mesh_vertices", "fyprt_last_edit_stats",
     "fyprt_set_append_placement", "fyprt_last_append_placement",
     "fyprt_regraft_meshes", "fyprt_tree_cost",
+    "fyprt_kept_primary_frames",
 ]
 # enum fyprt_probe (fyprt_selftest_functions) and the 32-bit words of one input / output record of each probe
 (PROBE_SINCOS, PROBE_ACOS, PROBE_POW5, PROBE_RND, PROBE_OCT_ENCODE, PROBE_OCT_DECODE, PROBE_PACK_ABGR, PROBE_UNPACK_ABGR, PROBE_EVAL_BRDF,
@@ -306,6 +307,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     if hasattr(lib, "fyprt_set_append_placement"):  # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
         lib.fyprt_set_append_placement.argtypes = [vp, C.c_int]
         lib.fyprt_last_append_placement.argtypes = [vp, C.POINTER(AppendPlacement)]
+    if hasattr(lib, "fyprt_kept_primary_frames"):   # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
+        lib.fyprt_kept_primary_frames.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.fyprt_compare_image.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     if hasattr(lib, "fyprt_update_materials"):   # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
         lib.fyprt_update_materials.argtypes = [vp, vp, u32, C.POINTER(u32), C.POINTER(i32), u32, vp, u32]
@@ -702,6 +705,12 @@ class Context:
         mse, psnr = C.c_double(), C.c_double()
         self._check(self.lib.fyprt_compare_image(self.h, ref.ctypes.data, 1 if flip_reference_rows else 0, C.byref(mse), C.byref(psnr)))
         return mse.value, psnr.value
+
+    def kept_primary_frames(self) -> int:
+        """ReSTIR DI frames since creation that reused the kept primary hits (tuning key 25; fyprt_kept_primary_frames)."""
+        n = C.c_uint64()
+        self._check(self.lib.fyprt_kept_primary_frames(self.h, C.byref(n)))
+        return n.value
 
     def get_tuning(self, key: int) -> int:
         v = C.c_int()

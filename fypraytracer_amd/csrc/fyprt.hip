@@ -101,11 +101,11 @@ struct OccCache {
 enum TuningKey {
     K_TILE_ORDER = 0, K_DI_WAVEFRONT = 1, K_WG_PER_CU = 2, K_SORT_TASKS = 3, K_CHUNK = 4, K_REFILL_LANES = 5, K_QUORUM_SECONDARY = 6, K_QUORUM_PRIMARY = 7,
     K_STACK_BUDGET = 8, K_STATIC_CHUNKS = 9, K_MIN_CHUNK = 10, K_PIPELINE = 11, K_BUILDER = 12, K_SKIP_HALO_PART1 = 13, K_SETUP_FETCH = 14, K_RAY_KERNEL = 15,
-    K_TOP_NODES = 16, K_FUSED_FRAME = 17, K_SKIP_DEAD_RAYS = 18, K_GI2_MODE = 19, K_GI2_REFILL_LANES = 20, K_DI_SPLIT = 21, K_PARTIAL_REFIT = 22, /* 23 reserved */ K_COUNT = 24
+    K_TOP_NODES = 16, K_FUSED_FRAME = 17, K_SKIP_DEAD_RAYS = 18, K_GI2_MODE = 19, K_GI2_REFILL_LANES = 20, K_DI_SPLIT = 21, K_PARTIAL_REFIT = 22, /* 23 reserved, 24 not assigned */ K_KEEP_PRIMARY = 25, K_COUNT = 26
 };
 constexpr struct { int def, max; } kTuning[K_COUNT] = {
     {2, 2}, {1, 1}, {0, 16}, {0, 1}, {128, 65536}, {24, 64}, {24, 64}, {32, 64}, {0, 31}, {0, 4096}, {32, 65536}, {1, 1},
-    {0, 2}, {0, 1}, {0, 2}, {0, 2}, {0, 1024}, {0, 2}, {1, 1}, {2, 2}, {48, 64}, {1, 1}, {0, 1}, {0, 0}};
+    {0, 2}, {0, 1}, {0, 2}, {0, 2}, {0, 1024}, {0, 2}, {1, 1}, {2, 2}, {48, 64}, {1, 1}, {0, 1}, {0, 0}, {0, -1}, {1, 1}};
 
 // host mat4 product, same operation order as the device / glm (column j = ((a0*bj.x + a1*bj.y) + a2*bj.z) + a3*bj.w)
 void matmul_cm(const float* a, const float* b, float* out) {
@@ -137,6 +137,25 @@ struct fyprt_context {
     // setup kernel of frame N as well and hands its pixels to k_di_part1_temporal on the front stream through the staging set of the frame's
     // parity.  evPrim: the primary kernel is done; evTemp: the temporal kernel is done, the staging set free for the frame after next
     Stream prim; Event evPrim[2], evTemp[2];
+    // Kept primary hits (tuning key 25).  A pixel's payload is a function of five camera fields and the geometry: ray_direction has no
+    // jitter, no seed, and materials, textures, frameIndex and history do not enter trace_ray.  While both stand still — the converging
+    // still frame frameIndex counts — a ReSTIR DI frame reads the payload an earlier DI frame traced instead of tracing it again.
+    //   established by every ReSTIR DI frame that traced (split, unsplit, blocking, instrumented: the same trace_ray bits), at enqueue time,
+    //               with its Part-1 rows and camera; evPayload is recorded behind the kernel that wrote c->payload, on `writer`
+    //   used        by a DI frame that counts no rays, on exactly these rows with byte-equal camera fields (kept_primary_usable).  The band
+    //               is compared as well: a moved band traces once even where band + halo, cut at the frame's edges, come out as the same
+    //               Part-1 rows — one rule for every row change, at the price of one traced frame per change
+    //   dropped     by whatever moves or renumbers geometry or the tree (edit_begin, set_scene_tree, fyprt_upload_scene, fyprt_resize,
+    //               fyprt_set_object_vertices), by a changed tuning value (keys 7, 8 and 16 shape the traversal), and by every frame
+    //               of another technique (k_primary, k_gi_primary and k_path_fused write the same buffer).  fyprt_update_materials and
+    //               fyprt_append_textures keep it: a Payload holds distance, position, normal, uv and triangle index, the material is
+    //               looked up from the triangle by every kernel that wants it (di_finished, k_di_part2_setup).
+    struct KeptPrimary {
+        bool valid = false; uint32_t begin = 0, end = 0, extraRow = 0, rowBegin = 0, rowEnd = 0;   // Part1Rows, and the band they were formed for
+        m4 invProj{}, invView{}; f3 position{}; uint32_t W = 0, H = 0;
+        hipStream_t writer = nullptr;
+    } kept; Event evPayload; uint64_t keptFrames = 0;       // keptFrames: frames that reused the payload (fyprt_kept_primary_frames)
+    void drop_kept_primary() { kept.valid = false; }
     static constexpr int kRing = 128;          // frames whose per-launch hipEvents are kept (fyprt_frame_timings)
     uint8_t ringSplit[kRing] = {};             // 0: the parts ran one after the other; 1: pipelined (the trace kernel starts at event 4); 2: Part 1 split as well (the front part starts at event 5)
     Event ring[kRing][6]; int ringLaunches[kRing] = {}; unsigned long long frameSerial = 0;
@@ -403,6 +422,7 @@ int fyprt_create(int device_ordinal, fyprt_context** out) {
     }
     for (int k = 0; k < 2 && e == hipSuccess; ++k)
         for (Event* ev : {&c->evFront[k], &c->evDone[k], &c->evPrim[k], &c->evTemp[k]}) if (e == hipSuccess) e = create(*ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = create(c->evPayload, hipEventDisableTiming);
     if (e != hipSuccess) { g_createError = std::string("streams / events: ") + hipGetErrorString(e); delete c; return FYPRT_EHIP; }
     for (auto& row : c->ring) for (auto& e : row) (void)create(e);
     { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, device_ordinal) == hipSuccess && prop.multiProcessorCount > 0) c->numCUs = prop.multiProcessorCount; }
@@ -428,7 +448,7 @@ int fyprt_resize(fyprt_context* c, uint32_t w, uint32_t h) {
     if (c->hostOnly) return c->fail(FYPRT_ESTATE, "host-only context (device -1) has no device buffers");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, sync_all(c));
-    c->release_denoise(); c->release_temporal(); c->release_upscale(); c->frameComplete = false;
+    c->release_denoise(); c->release_temporal(); c->release_upscale(); c->frameComplete = false; c->drop_kept_primary();
     const size_t n = (size_t)w * h;
     // cudaMemset(…, 0, …) of every buffer: Renderer.cu:333-355, :372, :393, :414
     TRY(alloc_zeroed(c, c->accum, n)); TRY(alloc_zeroed(c, c->image, n)); TRY(alloc_zeroed(c, c->payload, n)); TRY(alloc_zeroed(c, c->depth, n));
@@ -706,6 +726,7 @@ int fyprt_upload_scene(fyprt_context* c, const fyprt_scene_desc* s) {
         return c->fail(FYPRT_EINVAL, "fyprt_upload_scene: NULL array with non-zero count");
     if (!c->hostOnly) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c)); }
     c->frameComplete = false;                  // the payload's triangle indices belong to the scene they were traced in (fyprt_denoise)
+    c->drop_kept_primary();
     c->drop_history(); c->release_snapshot();  // world positions of another scene are not comparable (fyprt_denoise_temporal)
     const uint8_t* tb = (const uint8_t*)s->triangles;
     auto tri = [&](uint32_t i) { return reinterpret_cast<const uint32_t*>(tb + (size_t)i * s->triangle_stride); };
@@ -858,8 +879,9 @@ static int edit_check_state(fyprt_context* c, const char* who, unsigned needs) {
 enum EditKind { kEditGeometry, kEditShading, kEditTopology, kEditTreeOnly };
 static int edit_begin(fyprt_context* c, EditKind kind) {
     if (!c->hostOnly) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c)); }
-    if (kind == kEditTreeOnly) return FYPRT_OK;
+    if (kind == kEditTreeOnly) return FYPRT_OK;         // (a call that changes the tree re-points the descriptor: set_scene_tree drops the kept primary hits)
     c->frameComplete = false;                  // the payload's triangles, texture coordinates and materials are the old scene's (fyprt_denoise)
+    if (kind != kEditShading) c->drop_kept_primary();   // ... but the hits themselves outlive a shading edit: no material in a Payload (fyprt_context::KeptPrimary)
     if (kind == kEditGeometry) return temporal_edit_begin(c);
     c->drop_history(); if (kind == kEditTopology) c->release_snapshot();
     return FYPRT_OK;
@@ -930,6 +952,7 @@ int fyprt_set_object_vertices(fyprt_context* c, const fyprt_vertex* object_verti
         for (uint32_t t = c->topoMeshes[m].first_triangle; t < c->topoMeshes[m].first_triangle + c->topoMeshes[m].triangle_count; ++t)
             for (int k = 0; k < 3; ++k) { const uint32_t v = c->topoTris[(size_t)t * 4 + k]; if (v < mesh_first_vertex[m] || v >= mesh_first_vertex[m + 1]) return c->fail(FYPRT_EINVAL, "fyprt_set_object_vertices: triangle " + std::to_string(t) + " uses a vertex outside its mesh's range"); }
     HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, sync_all(c));
+    c->drop_kept_primary();                    // the vertices the next transform edit starts from
     TRY(alloc_upload(c, c->objVerts, object_vertices, vertex_count));
     c->meshFirstVertex.assign(mesh_first_vertex, mesh_first_vertex + nM + 1);
     return FYPRT_OK;
@@ -1402,6 +1425,7 @@ int fyprt_regraft_meshes(fyprt_context* c, const uint32_t* mesh_indices, uint32_
     DevBuf<uint32_t>* kept[] = {&c->nodeParent, &c->leafParent, &c->leafOfTri, &c->partialLists, &c->partialDirty, &c->partialCounters, &c->graftList};
     size_t keptSize[7]; for (int i = 0; i < 7; ++i) keptSize[i] = kept[i]->n;
     const size_t placeOutSize = c->placeOut.n;
+    c->drop_kept_primary();                    // hits at equal distance go by the tree's order — also of a tree a failed call leaves half moved
     const int rc = regraft_meshes(c, mesh_indices, mesh_count, reports);
     c->placement = saved; c->linksValid = false;
     if (!c->hostOnly) {
@@ -1661,6 +1685,7 @@ static int begin_frame(FrameRun& f) {
     }
     if (f.split) HIPCHK(c, hipStreamWaitEvent(c->prim, c->evTemp[f.par], 0));
     c->frameComplete = false;                  // from the first enqueued work until the frame is enqueued to its end (fyprt_denoise)
+    if (f.tech != FYPRT_RESTIR_DI) c->drop_kept_primary();   // k_primary, k_gi_primary and k_path_fused write the payload too, and keep nothing
     fr.tileOrder = (uint32_t)c->tuning[K_TILE_ORDER]; fr.p1Mode = f.wavefront ? 1u : 0u;
     f.grid = tile_grid(c, c->rowBegin, c->rowEnd); f.ev = c->ring[c->frameSerial % fyprt_context::kRing];
     if (f.phase == 2) { f.ei = 2; return FYPRT_OK; }          // part 1 recorded its start and its end
@@ -1788,25 +1813,62 @@ static int enqueue_di_wavefront_part2(FrameRun& f) {
     f.launches = 3;
     return FYPRT_OK;
 }
+// Kept primary hits (fyprt_context::KeptPrimary).  May this frame read the payload instead of tracing it: it counts no rays, and the payload
+// in place was traced for exactly its band and Part-1 rows with the five camera fields ray_direction and trace_ray read, byte for byte (compared
+// here, at frame time: fyprt_set_camera with the same matrices, or with other prev_* matrices, keeps it; fyprt_set_rows, the halo mode
+// and key 13 need no hook)
+static bool kept_primary_usable(const fyprt_context* c, const Part1Rows& p1) {
+    const fyprt_context::KeptPrimary& k = c->kept; const DevCamera& d = c->dcam;
+    return k.valid && !c->countRays && c->tuning[K_KEEP_PRIMARY] != 0 && k.begin == p1.begin && k.end == p1.end && k.extraRow == p1.extraRow && k.rowBegin == c->rowBegin && k.rowEnd == c->rowEnd && k.W == d.W && k.H == d.H &&
+           !std::memcmp(&k.invProj, &d.invProj, sizeof d.invProj) && !std::memcmp(&k.invView, &d.invView, sizeof d.invView) && !std::memcmp(&k.position, &d.position, sizeof d.position);
+}
+// ... and a frame that traced leaves it: `writer` is the stream whose last launch wrote c->payload
+static int establish_kept_primary(fyprt_context* c, const Part1Rows& p1, hipStream_t writer) {
+    fyprt_context::KeptPrimary& k = c->kept; const DevCamera& d = c->dcam;
+    k.valid = true; k.begin = p1.begin; k.end = p1.end; k.extraRow = p1.extraRow; k.rowBegin = c->rowBegin; k.rowEnd = c->rowEnd; k.invProj = d.invProj; k.invView = d.invView; k.position = d.position; k.W = d.W; k.H = d.H; k.writer = writer;
+    HIPCHK(c, hipEventRecord(c->evPayload, writer));
+    return FYPRT_OK;
+}
 // ReSTIR DI.  Part 1: candidates + temporal reuse per pixel; Part 2: spatial reuse + shadow rays, as a wavefront (tuning key 1) or per pixel.
+// Who touches c->payload in Part 1, and why no two of them meet:
+//   a tracing frame  writes it in k_di_part1_temporal<false> on `front` (split) or in k_di_part1<.., false> on f.fs, and records evPayload behind it;
+//   a kept frame     writes it nowhere and reads it in k_di_part1_primary<false, true> on `prim` and k_di_part1_temporal<true> on `front`, or in
+//                    k_di_part1<false, true> on f.fs — each behind evPayload where the stream is not the writer's own.
+//   A tracing split frame after kept ones writes on `front` behind its own evPrim, and `prim` runs in order: every earlier kept primary kernel
+//   is done.  A tracing unsplit frame has no evPrim of its own and waits for both parities' — the later one covers every kept primary kernel.
+//   The setup kernel and the denoisers read the payload as before (dn_call_done's dnDone wait stays: a tracing frame may follow any call).
 static int enqueue_di_frame(FrameRun& f) {
     fyprt_context* c = f.c;
     if (f.phase != 2) {
         const Part1Rows p1 = part1_rows(c);
+        const bool kept = kept_primary_usable(c, p1);
+        if (kept) c->keptFrames++;
         if (f.split) {               // part 0 of the frame's timings: the primary kernel, between its own events on `prim`
             const size_t npx = (size_t)c->W * c->H;
-            const DIStage sg{c->stagePayload.p + (size_t)f.par * npx, c->stageRec.p + (size_t)f.par * npx};
-            hipLaunchKernelGGL(k_di_part1_primary<false>, p1.grid, dim3(kBlock), f.ldsBytes, c->prim, f.sc, c->dcam, f.fr, f.st, p1.begin, p1.end, p1.extraRow, sg);
+            const DIStage sg{kept ? nullptr : c->stagePayload.p + (size_t)f.par * npx, c->stageRec.p + (size_t)f.par * npx};
+            if (kept) {
+                HIPCHK(c, hipStreamWaitEvent(c->prim, c->evPayload, 0));      // long signalled in steady state
+                hipLaunchKernelGGL((k_di_part1_primary<false, true>), p1.grid, dim3(kBlock), 0, c->prim, f.sc, c->dcam, f.fr, f.st, p1.begin, p1.end, p1.extraRow, sg);
+            } else hipLaunchKernelGGL((k_di_part1_primary<false, false>), p1.grid, dim3(kBlock), f.ldsBytes, c->prim, f.sc, c->dcam, f.fr, f.st, p1.begin, p1.end, p1.extraRow, sg);
             if (f.timed) HIPCHK(c, hipEventRecord(f.ev[f.ei++], c->prim));
             HIPCHK(c, hipEventRecord(c->evPrim[f.par], c->prim));
             HIPCHK(c, hipStreamWaitEvent(c->front, c->evPrim[f.par], 0));
             TRY(sync_restir_normals(c, f.tech, f.fs));
             if (f.timed) HIPCHK(c, hipEventRecord(f.ev[5], c->front));   // part 1: temporal + setup, from here to the event behind the setup kernel
-            hipLaunchKernelGGL(k_di_part1_temporal, p1.grid, dim3(kBlock), 0, c->front, f.sc, c->dcam, f.fr, f.st, p1.begin, p1.end, p1.extraRow, sg);
+            if (kept && c->kept.writer != c->front.h) HIPCHK(c, hipStreamWaitEvent(c->front, c->evPayload, 0));
+            hipLaunchKernelGGL(kept ? k_di_part1_temporal<true> : k_di_part1_temporal<false>, p1.grid, dim3(kBlock), 0, c->front, f.sc, c->dcam, f.fr, f.st, p1.begin, p1.end, p1.extraRow, sg);
             HIPCHK(c, hipEventRecord(c->evTemp[f.par], c->front));
+            if (!kept) TRY(establish_kept_primary(c, p1, c->front));
         } else {
             TRY(sync_restir_normals(c, f.tech, f.fs));   // the last ReSTIR frame was a GI frame: its normals are this frame's "previous normals"
-            hipLaunchKernelGGL(c->countRays ? k_di_part1<true> : k_di_part1<false>, p1.grid, dim3(kBlock), f.ldsBytes, f.fs, f.sc, c->dcam, f.fr, f.st, p1.begin, p1.end, p1.extraRow);
+            if (kept) {
+                if (c->kept.writer != f.fs) HIPCHK(c, hipStreamWaitEvent(f.fs, c->evPayload, 0));
+                hipLaunchKernelGGL((k_di_part1<false, true>), p1.grid, dim3(kBlock), 0, f.fs, f.sc, c->dcam, f.fr, f.st, p1.begin, p1.end, p1.extraRow);
+            } else {
+                for (int k = 0; k < 2; ++k) HIPCHK(c, hipStreamWaitEvent(f.fs, c->evPrim[k], 0));
+                hipLaunchKernelGGL((c->countRays ? k_di_part1<true, false> : k_di_part1<false, false>), p1.grid, dim3(kBlock), f.ldsBytes, f.fs, f.sc, c->dcam, f.fr, f.st, p1.begin, p1.end, p1.extraRow);
+                TRY(establish_kept_primary(c, p1, f.fs));
+            }
             if (f.timed) HIPCHK(c, hipEventRecord(f.ev[f.ei++], f.fs));
         }
         if (f.phase == 1) { f.part1Only = true; return c->hip(hipGetLastError(), "ReSTIR DI part 1"); }
@@ -2084,12 +2146,15 @@ int fyprt_set_tuning(fyprt_context* c, int key, int value) {
     if (!c || key < 0 || key >= K_COUNT) return FYPRT_EINVAL;
     // ranges: a value outside them could hang the persistent kernels (refill threshold above the wave size: no lane is ever
     // refilled) or index past a buffer, so it is refused here instead of trusted
+    if (kTuning[key].max < 0) return c->fail(FYPRT_EINVAL, "fyprt_set_tuning: key " + std::to_string(key) + " is not assigned");
     if (value < 0 || value > kTuning[key].max)
         return c->fail(FYPRT_EINVAL, "fyprt_set_tuning: key " + std::to_string(key) + " accepts 0.." + std::to_string(kTuning[key].max));
+    if (c->tuning[key] != value) c->drop_kept_primary();     // keys 7, 8 and 16 shape the traversal; no key changes in a still frame's steady state
     c->tuning[key] = value;
     return FYPRT_OK;
 }
 
+int fyprt_kept_primary_frames(fyprt_context* c, uint64_t* frames) { if (!c || !frames) return FYPRT_EINVAL; *frames = c->keptFrames; return FYPRT_OK; }
 int fyprt_set_ray_counting(fyprt_context* c, int enabled) { if (!c) return FYPRT_EINVAL; c->countRays = enabled != 0; return FYPRT_OK; }
 
 // The two parts of a ReSTIR frame as separate calls, for a host that moves the halo rows between the bands itself (part 1, then its

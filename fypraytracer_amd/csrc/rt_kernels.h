@@ -264,14 +264,21 @@ RT_DEV void di_finished(const DevScene& sc, const DevSettings& st, DIPixel& p) {
 }
 // The half that depends on nothing from earlier frames: primary ray, material, albedo, the light candidates and R.W.  Reads the scene,
 // the camera, frameIndex and randSeed; writes the payload to `payloadOut` and nothing else.
-template <bool COUNT>
+// KEPT: the pixel's payload is a function of the camera and the geometry alone (ray_direction has no jitter), so while both stand still
+// the one an earlier frame traced IS this frame's (the host decides: fyprt.hip, KeptPrimary) — it is loaded from fr.payload instead of
+// traced, and not stored again; no stack, no top nodes.  Everything after it is the same operations on the same values.
+template <bool COUNT, bool KEPT>
 RT_DEV void di_part1_candidates(const DevScene& sc, const DevCamera& cam, const DevFrame& fr, const DevSettings& st, uint32_t x, uint32_t y,
                                 int32_t* stk, const float4* top4, Payload* payloadOut, DIPixel& p) {
+    static_assert(!(COUNT && KEPT), "an instrumented frame always traces");
     const uint32_t i = x + y * fr.W;
     p.seed = i * (fr.frameIndex + 1u + st.randSeed);
     p.pd = ray_direction(cam, x, y);
-    p.pp = trace_ray<COUNT>(sc, cam.position, p.pd, stk, top4);
-    *payloadOut = p.pp;
+    if constexpr (KEPT) p.pp = fr.payload[i];
+    else {
+        p.pp = trace_ray<COUNT>(sc, cam.position, p.pd, stk, top4);
+        *payloadOut = p.pp;
+    }
     p.ncur = oct_encode(nrm3(p.pp));
     p.R = di_empty();
     di_finished(sc, st, p);
@@ -327,46 +334,59 @@ RT_DEV void di_part1_temporal(const DevScene& sc, const DevCamera& cam, const De
 
 // Part 1 rows: [p1Begin, p1End) (band + halo); finished pixels (sky / emitter) go through the
 // epilogue only inside the band proper so halo rows never touch accumulation.
-template <bool COUNT>
+// The traversal stack of a tracing Part-1 kernel: (stackBudget + 1) entries x kBlock threads, sized at launch, + the top-node copy.  A
+// KEPT kernel has neither (launched with 0 bytes of dynamic LDS).
+struct Part1Lds { int32_t* stk; const float4* top4; };
+template <bool KEPT>
+RT_DEV Part1Lds part1_lds(const DevScene& sc) {
+    if constexpr (KEPT) return {nullptr, nullptr};
+    else {
+        extern __shared__ int32_t s_stack[];
+        const float4* top4 = stage_top_nodes(sc.nodes, sc.topCount, sc.stackBudget, s_stack);
+        return {s_stack + threadIdx.x, top4};
+    }
+}
+template <bool COUNT, bool KEPT>
 __global__ __launch_bounds__(kBlock) void k_di_part1(DevScene sc, DevCamera cam, DevFrame fr, DevSettings st, uint32_t p1Begin, uint32_t p1End, uint32_t extraRow) {
-    extern __shared__ int32_t s_stack[];                         // (stackBudget + 1) entries x kBlock threads, sized at launch, + the top-node copy
-    const float4* top4 = stage_top_nodes(sc.nodes, sc.topCount, sc.stackBudget, s_stack);
+    const Part1Lds lds = part1_lds<KEPT>(sc);
     uint32_t x, y;
     if (!p1_pixel_of_thread(fr, p1Begin, p1End, extraRow, x, y)) return;
     const uint32_t i = x + y * fr.W;
     const bool inBand = (y >= fr.rowBegin && y < fr.rowEnd);
     DIPixel p;
-    di_part1_candidates<COUNT>(sc, cam, fr, st, x, y, s_stack + threadIdx.x, top4, fr.payload + i, p);
+    di_part1_candidates<COUNT, KEPT>(sc, cam, fr, st, x, y, lds.stk, lds.top4, fr.payload + i, p);
     di_part1_temporal(sc, cam, fr, st, i, inBand, p);
 }
 
 // Part 1 of a pipelined frame, history-free half: the same rows, the payload and the candidate record (hit distance, octahedral normal, the
 // candidate reservoir with W and wSum) into the frame parity's private staging set.  No API call and no other kernel reads what it writes
 // but k_di_part1_temporal of the same frame, so it may run while the previous frame's setup kernel still writes the history.
+// A KEPT frame stages the record alone: sg.payload is NULL, both halves read the public payload, which no kernel of the frame writes.
 struct DIStage { Payload* payload; DIRec* rec; };
-template <bool COUNT>
+template <bool COUNT, bool KEPT>
 __global__ __launch_bounds__(kBlock) void k_di_part1_primary(DevScene sc, DevCamera cam, DevFrame fr, DevSettings st, uint32_t p1Begin, uint32_t p1End, uint32_t extraRow, DIStage sg) {
-    extern __shared__ int32_t s_stack[];                         // as k_di_part1
-    const float4* top4 = stage_top_nodes(sc.nodes, sc.topCount, sc.stackBudget, s_stack);
+    const Part1Lds lds = part1_lds<KEPT>(sc);
     uint32_t x, y;
     if (!p1_pixel_of_thread(fr, p1Begin, p1End, extraRow, x, y)) return;
     const uint32_t i = x + y * fr.W;
     DIPixel p;
-    di_part1_candidates<COUNT>(sc, cam, fr, st, x, y, s_stack + threadIdx.x, top4, sg.payload + i, p);
+    di_part1_candidates<COUNT, KEPT>(sc, cam, fr, st, x, y, lds.stk, lds.top4, KEPT ? nullptr : sg.payload + i, p);
     store_rec(sg.rec + i, p.pp.hitDistance, p.ncur, p.R);
 }
 // ... and the history half, one thread per Part-1 pixel, no traversal: payload and candidate record from the staging set, view direction,
 // material and albedo recomputed from the payload as the setup kernel does, the RNG state after the candidates re-derived (every candidate
 // draws twice: its light and its reservoir update, so the state is pcg_hash applied 2 x candidateCount times to the pixel's initial seed).
-// Writes the public payload and what Part 1 writes of records, history and depth.  A pipelined frame has p1Mode 1: no epilogue, no sentinel.
+// Writes the public payload (KEPT: reads it; the 40 B + 40 B copy is gone) and what Part 1 writes of records, history and depth.  A
+// pipelined frame has p1Mode 1: no epilogue, no sentinel.
+template <bool KEPT>
 __global__ __launch_bounds__(kBlock) void k_di_part1_temporal(DevScene sc, DevCamera cam, DevFrame fr, DevSettings st, uint32_t p1Begin, uint32_t p1End, uint32_t extraRow, DIStage sg) {
     uint32_t x, y;
     if (!p1_pixel_of_thread(fr, p1Begin, p1End, extraRow, x, y)) return;
     const uint32_t i = x + y * fr.W;
     fr.p1Mode = 1u;
     DIPixel p;
-    p.pp = sg.payload[i];
-    fr.payload[i] = p.pp;
+    if constexpr (KEPT) p.pp = fr.payload[i];
+    else { p.pp = sg.payload[i]; fr.payload[i] = p.pp; }
     const DIRec rec = load_rec(sg.rec + i);
     p.ncur.x = rec.nx; p.ncur.y = rec.ny; p.R = rec_reservoir(rec);
     p.pd = ray_direction(cam, x, y);

@@ -122,8 +122,10 @@ static int read_back_mesh_verts(fyprt_context* c, uint32_t m) {
     return FYPRT_OK;
 }
 
-// ---- the scene descriptor's tree fields, and with them those of the per-triangle records of a scene of T triangles
-static void set_scene_tree(fyprt_context* c) { c->dsc.nodes = c->nodes.p; c->dsc.leafTris = c->leafTris.p; c->dsc.rootRef = rth::device_ref(c->hostBvh.rootRef); }
+// ---- the scene descriptor's tree fields, and with them those of the per-triangle records of a scene of T triangles.  Every call that
+// builds, grafts, prunes or regrafts ends here, so here the kept primary hits go (fyprt_context::KeptPrimary): another tree visits the
+// triangles in another order, and hits at equal distance go by that order.
+static void set_scene_tree(fyprt_context* c) { c->drop_kept_primary(); c->dsc.nodes = c->nodes.p; c->dsc.leafTris = c->leafTris.p; c->dsc.rootRef = rth::device_ref(c->hostBvh.rootRef); }
 static void set_scene_triangles(fyprt_context* c, uint32_t T) { set_scene_tree(c); c->dsc.triCount = T; c->dsc.triPos = c->triPos.p; c->dsc.triShade = c->triShade.p; }
 
 // ---- launches on the context stream

@@ -541,12 +541,21 @@ int fyprt_set_ray_counting(fyprt_context* ctx, int enabled);
  * key 22: path of fyprt_update_transforms: 0 (default) = the full passes (every per-triangle record, every leaf record, every node of every
  *         level); 1 = the partial refit (below, fyprt_update_mesh_vertices): records and nodes of the listed meshes only.  Same state
  *         on a tree a full refit has run on; otherwise nodes and records nothing moved under keep their bytes.
- * Values are range-checked (FYPRT_EINVAL): key 0: 0..2, keys 1, 3, 11, 13, 18, 21, 22: 0..1, keys 12, 14, 15, 17, 19: 0..2, key 2: 0..16, keys 5, 6, 7, 20: 0..64,
- * key 8: 0..31, key 16: 0..1024; key 23 is reserved (0). */
+ * key 25: 1 (default) = a ReSTIR DI frame keeps the primary hits while camera and geometry stand still: a pixel's primary payload depends on the
+ *         camera's inverse projection, inverse view, position and viewport and on the geometry alone (no jitter, no seed, no material), so a
+ *         frame whose rows (fyprt_set_rows: band, and band + halo) and camera fields equal, byte for byte, those of the ReSTIR DI frame that traced the payload in place reads it
+ *         instead of tracing 1 ray per pixel again.  Every geometry, transform, topology or tree edit, fyprt_upload_scene, fyprt_resize, a changed
+ *         tuning value and a frame of any other technique drop it (the next ReSTIR DI frame traces); material and texture edits keep it.
+ *         Instrumented frames (fyprt_set_ray_counting) always trace, and count as ever.  0 = every frame traces.  Same results bit for bit;
+ *         fyprt_kept_primary_frames counts the frames that reused the payload.  Changing ANY key's value drops the kept hits once.
+ * Values are range-checked (FYPRT_EINVAL): key 0: 0..2, keys 1, 3, 11, 13, 18, 21, 22, 25: 0..1, keys 12, 14, 15, 17, 19: 0..2, key 2: 0..16, keys 5, 6, 7, 20: 0..64,
+ * key 8: 0..31, key 16: 0..1024; key 23 is reserved (0), key 24 is not assigned (every value is refused). */
 int fyprt_set_tuning(fyprt_context* ctx, int key, int value);
 /* The value in effect (key 8: the budget actually used for the uploaded scene, which an instrumented restatement of the
  * traversal must use too). */
 int fyprt_get_tuning(fyprt_context* ctx, int key, int* value);
+/* ReSTIR DI frames since fyprt_create that read the kept primary hits instead of tracing them (tuning key 25); 0 on a host-only context. */
+int fyprt_kept_primary_frames(fyprt_context* ctx, uint64_t* frames);
 
 /* Scene::vertices (object space) + every mesh's vertex range [mesh_first_vertex[m], mesh_first_vertex[m+1]) (Mesh::vertexStart /
  * vertexCount), kept on the device so that fyprt_update_transforms can apply a transform edit there.  After fyprt_upload_scene. */
