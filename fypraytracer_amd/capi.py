@@ -62,6 +62,10 @@ assert MESH_DTYPE.itemsize == 12 and LT_NODE_DTYPE.itemsize == 80
 RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("tmin", "<f4"), ("direction", "<f4", 3), ("tmax", "<f4")])
 assert RAY_DTYPE.itemsize == 32
 QUERY_CLOSEST, QUERY_OCCLUDED = 0, 1
+# multi-hit queries (fyprt_trace_ray_hits): fyprt_ray_hit (16 B); the unused record is (-1, 0xFFFFFFFF, 0, 0)
+RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("triangle", "<u4"), ("u", "<f4"), ("v", "<f4")])
+assert RAY_HIT_DTYPE.itemsize == 16
+QUERY_MAX_HITS = 8               # FYPRT_QUERY_MAX_HITS
 RENDER_RAYS_CHUNK = 1 << 21      # FYPRT_RENDER_RAYS_CHUNK: rays per internal pass of fyprt_render_rays*
 BVH_NODE_DTYPE = np.dtype([("origin", "<f4", 3), ("ex", "u1", 3), ("meta", "u1"), ("child", "<i4", 4),
                            ("qlo", "u1", (3, 4)), ("qhi", "u1", (3, 4)), ("pad", "<u4", 2)])
@@ -224,6 +228,7 @@ EXPORTED_SYMBOLS = [
     "fyprt_set_object_vertices", "fyprt_update_transforms", "fyprt_compare_image",
     "fyprt_set_row_stripes", "fyprt_group_set_interleave", "fyprt_comm_set_interleave", "fyprt_selftest_math",
     "fyprt_trace_rays", "fyprt_trace_rays_device",
+    "fyprt_trace_ray_hits", "fyprt_trace_ray_hits_device",
     "fyprt_render_rays", "fyprt_render_rays_device",
     "fyprt_denoise_default_params", "fyprt_denoise", "fyprt_denoise_device",
     "fyprt_denoise_temporal_default_params", "fyprt_denoise_temporal", "fyprt_denoise_temporal_device", "fyprt_denoise_temporal_reset",
@@ -316,6 +321,9 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     if hasattr(lib, "fyprt_trace_rays"):     # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
         lib.fyprt_trace_rays.argtypes = [vp, C.c_int, vp, u32, vp, C.POINTER(FrameStats)]
         lib.fyprt_trace_rays_device.argtypes = [vp, C.c_int, vp, u32, vp]
+    if hasattr(lib, "fyprt_trace_ray_hits"):
+        lib.fyprt_trace_ray_hits.argtypes = [vp, vp, vp, u32, u32, vp, vp, C.POINTER(FrameStats)]
+        lib.fyprt_trace_ray_hits_device.argtypes = [vp, vp, vp, u32, u32, vp, vp]
     if hasattr(lib, "fyprt_render_rays"):    # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
         lib.fyprt_render_rays.argtypes = [vp, C.POINTER(Settings), u32, vp, vp, u32, u32, vp, vp, C.POINTER(FrameStats)]
         lib.fyprt_render_rays_device.argtypes = [vp, C.POINTER(Settings), u32, vp, vp, u32, u32, vp, vp]
@@ -771,6 +779,93 @@ class Context:
                                                      C.c_void_p(out.data_ptr())))
         cur.wait_stream(ext)                                           # torch's later work (reads of `out`, reuse of either block) follows it
         return out
+
+    @staticmethod
+    def _check_max_hits(who, max_hits):
+        if not isinstance(max_hits, (int, np.integer)) or isinstance(max_hits, bool) or not 1 <= int(max_hits) <= QUERY_MAX_HITS:
+            raise ValueError(f"{who}: max_hits must be an integer in 1..{QUERY_MAX_HITS}, got {max_hits!r}")
+        return int(max_hits)
+
+    def trace_ray_hits(self, origins, directions, tmin=0.0, tmax=np.inf, max_hits=QUERY_MAX_HITS, after=None, with_stats=False):
+        """Ordered multi-hit query (fyprt_trace_ray_hits, blocking): the `max_hits` nearest accepted triangles per ray, ascending by
+        (t, triangle).  `origins` / `directions`: (N, 3); `tmin` / `tmax`: scalars or (N,) arrays; `after`: None or N RAY_HIT_DTYPE
+        records — only hits beyond after[i] in that order are returned, and a record with t < 0 (the unused record) finishes the ray.
+        Returns (hits (N, K) RAY_HIT_DTYPE, counts (N,) uint32); unused records are (-1, 0xFFFFFFFF, 0, 0); with `with_stats` also
+        the FrameStats of the launch."""
+        k = self._check_max_hits("trace_ray_hits", max_hits)
+        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError(f"trace_ray_hits: {len(o)} origins but {len(d)} directions")
+        n = len(o)
+        aft = None
+        if after is not None:
+            aft = np.asarray(after)
+            if aft.dtype != RAY_HIT_DTYPE or aft.size != n:
+                raise ValueError(f"trace_ray_hits: after must be {n} RAY_HIT_DTYPE records")
+            aft = np.ascontiguousarray(aft.reshape(-1))
+        rays = np.empty(n, dtype=RAY_DTYPE)
+        rays["origin"], rays["direction"] = o, d
+        rays["tmin"] = np.broadcast_to(np.asarray(tmin, dtype=np.float32), (n,))
+        rays["tmax"] = np.broadcast_to(np.asarray(tmax, dtype=np.float32), (n,))
+        hits = np.empty((n, k), dtype=RAY_HIT_DTYPE)
+        counts = np.empty(n, dtype=np.uint32)
+        st = FrameStats()
+        self._check(self.lib.fyprt_trace_ray_hits(self.h, _ptr(rays), _ptr(aft), n, k, _ptr(hits), _ptr(counts), C.byref(st)))
+        return (hits, counts, st) if with_stats else (hits, counts)
+
+    def trace_ray_hits_tensor(self, rays, max_hits, after=None):
+        """Multi-hit query on device tensors (fyprt_trace_ray_hits_device).  `rays`: contiguous float32 (N, 8) tensor on this context's
+        GPU, one fyprt_ray per row; `after`: None or a contiguous float32 (N, 4) tensor of hit records (the last column of records of an
+        earlier call: `hits[:, -1].contiguous()`).  Returns a float32 (N, K, 4) tensor of records (t, triangle bits, u, v: the index is
+        `hits[..., 1].contiguous().view(torch.int32)`) and an int32 (N,) tensor of counts.  Ordered against torch's current stream
+        exactly as trace_rays_tensor is, without a host synchronisation and without record_stream."""
+        import torch
+        k = self._check_max_hits("trace_ray_hits_tensor", max_hits)
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
+            raise ValueError("trace_ray_hits_tensor: rays must be a contiguous float32 (N, 8) tensor")
+        if rays.device.type != "cuda" or (rays.device.index if rays.device.index is not None else torch.cuda.current_device()) != self.device:
+            raise ValueError(f"trace_ray_hits_tensor: rays must be on cuda:{self.device}, the context's GPU")
+        n = rays.shape[0]
+        if after is not None and (after.dtype != torch.float32 or tuple(after.shape) != (n, 4) or not after.is_contiguous() or after.device != rays.device):
+            raise ValueError("trace_ray_hits_tensor: after must be a contiguous float32 (N, 4) tensor on the rays' device")
+        hits = torch.empty((n, k, 4), dtype=torch.float32, device=rays.device)
+        counts = torch.empty((n,), dtype=torch.int32, device=rays.device)
+        cur = torch.cuda.current_stream(rays.device)
+        ext = torch.cuda.ExternalStream(self.stream(), device=rays.device)
+        ext.wait_stream(cur)                                           # rays / after are written, the outputs allocated before the query runs
+        self._check(self.lib.fyprt_trace_ray_hits_device(self.h, C.c_void_p(rays.data_ptr()), C.c_void_p(after.data_ptr()) if after is not None else None,
+                                                         n, k, C.c_void_p(hits.data_ptr()), C.c_void_p(counts.data_ptr())))
+        cur.wait_stream(ext)                                           # torch's later work follows it
+        return hits, counts
+
+    def trace_all_hits(self, origins, directions, tmin=0.0, tmax=np.inf, max_hits=QUERY_MAX_HITS):
+        """Every accepted hit of every ray, in order: continuation passes of trace_ray_hits (each pass's last record per ray passed
+        back in as `after`) until every ray is finished.  Returns (records, offsets): flat RAY_HIT_DTYPE records, ray i's in
+        records[offsets[i]:offsets[i + 1]], offsets int64 (N + 1,)."""
+        k = self._check_max_hits("trace_all_hits", max_hits)
+        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError(f"trace_all_hits: {len(o)} origins but {len(d)} directions")
+        n = len(o)
+        lo = np.broadcast_to(np.asarray(tmin, dtype=np.float32), (n,))
+        hi = np.broadcast_to(np.asarray(tmax, dtype=np.float32), (n,))
+        live = np.arange(n)                                            # rays not finished yet; only they are traced again
+        after = None
+        parts = [[] for _ in range(n)]
+        while len(live):
+            hits, counts = self.trace_ray_hits(o[live], d[live], lo[live], hi[live], k, after)
+            for j, i in enumerate(live):
+                if counts[j]:
+                    parts[i].append(hits[j, :counts[j]])
+            go = counts == k                                           # a ray with a short list has no further hit
+            live, after = live[go], np.ascontiguousarray(hits[go, k - 1])
+        total = np.array([sum(len(p) for p in ps) for ps in parts], dtype=np.int64)
+        offsets = np.concatenate([[0], np.cumsum(total)]).astype(np.int64)
+        flat = [p for ps in parts for p in ps]
+        records = np.concatenate(flat) if flat else np.empty(0, dtype=RAY_HIT_DTYPE)
+        return records, offsets
 
     def render_rays(self, origins, directions, settings: Settings, frame_index=1, first_index=0, pixel_indices=None, tmin=0.0, tmax=np.inf,
                     want_payload=False, with_stats=False):

@@ -213,7 +213,7 @@ struct fyprt_context {
     int lastLaunches = 0;
     size_t queueStride = 0;                     // float4s per task queue
     size_t sortGroups = 0;                      // setup workgroups the sort scratch is sized for (per parity)
-    OccCache traceOcc, pathOcc, gi2Occ, queryOcc[2];   // k_di_part2_trace, k_trace_rays, k_gi2_persistent, k_query_rays<kind, false>
+    OccCache traceOcc, pathOcc, gi2Occ, queryOcc[2], hitsOcc;   // k_di_part2_trace, k_trace_rays, k_gi2_persistent, k_query_rays<kind, false>, k_query_hits<false>
     int tuning[K_COUNT];                        // by TuningKey, defaults from kTuning
     int numCUs = 256;
     // wavefront path engine (rt_paths.h): two ray lists + results (ping-pong), per-pixel path state, pixel lists, list counters
@@ -223,6 +223,9 @@ struct fyprt_context {
     // batched ray queries (fyprt_trace_rays*, rt_query.h), all allocated on the first query: their own counters ([0..4] as a frame's
     // launch, [5] low word = queue head of the persistent kernel), the host entry's staging buffers, its two timing events
     DevBuf<unsigned long long> queryCounters; DevBuf<float4> queryRays; DevBuf<uint32_t> queryResults; Event queryEv[2];
+    // multi-hit queries (fyprt_trace_ray_hits*, rt_query.h), allocated on the first one: their own counters (laid out as the batched
+    // queries'), the host entry's staging (rays, `after` records, hit records, counts), grown on demand and kept, its two timing events
+    DevBuf<unsigned long long> hitsCounters; DevBuf<float4> hitsRays, hitsAfter, hitsOut; DevBuf<uint32_t> hitsCounts; Event hitsEv[2];
     // radiance queries (fyprt_render_rays*, rt_query.h: k_render_rays_primary + the path stages), allocated on first use for
     // min(count, FYPRT_RENDER_RAYS_CHUNK) rays and kept: primary records, path state, ray / result lists, live lists, list counters + queue
     // heads; the host entry's staging (rays, pixel indices, radiance) and its two timing events
@@ -2239,6 +2242,88 @@ int fyprt_trace_rays_device(fyprt_context* c, int query, const void* rays, uint3
     if (count == 0) return FYPRT_OK;
     HIPCHK(c, hipSetDevice(c->device));
     return enqueue_query(c, query, static_cast<const float4*>(rays), count, results, false);
+}
+
+// ---- multi-hit queries (rt_query.h: k_query_hits / k_query_hits_simple).  As the batched queries: the scene is read, the query's own
+// results and counters are written, no frame state moves.
+static int check_ray_hits(fyprt_context* c, const void* rays, const void* after, uint32_t count, uint32_t maxHits, const void* hits, const void* hitCounts, bool device) {
+    const char* who = device ? "fyprt_trace_ray_hits_device" : "fyprt_trace_ray_hits";
+    if (!c) return FYPRT_EINVAL;
+    if (maxHits == 0 || maxHits > FYPRT_QUERY_MAX_HITS) return c->fail(FYPRT_EINVAL, std::string(who) + ": max_hits must be 1.." + std::to_string(FYPRT_QUERY_MAX_HITS));
+    if (count && (!rays || !hits)) return c->fail(FYPRT_EINVAL, std::string(who) + ": NULL rays / hits with a non-zero count");
+    if (device && (((uintptr_t)rays & 15u) || ((uintptr_t)after & 15u) || ((uintptr_t)hits & 15u) || ((uintptr_t)hitCounts & 3u)))   // 16-byte loads and stores, 4-byte counts
+        return c->fail(FYPRT_EINVAL, std::string(who) + ": rays, after and hits must be 16-byte and hit_counts 4-byte aligned");
+    if (c->hostOnly) return c->fail(FYPRT_ESTATE, std::string(who) + ": host-only context (device -1) cannot trace");
+    if (!c->haveScene) return c->fail(FYPRT_ESTATE, std::string(who) + " before fyprt_upload_scene");
+    return FYPRT_OK;
+}
+// Enqueues one multi-hit launch on the context stream (device memory, count > 0, after / counts may be NULL); `timed` brackets it with
+// the query's events.  A workgroup's LDS is the stack plus 16 bytes per thread and list entry: the list is sized by this call's max_hits.
+static int enqueue_ray_hits(fyprt_context* c, const float4* rays, const float4* after, uint32_t count, uint32_t maxHits, float4* hits, uint32_t* counts, bool timed) {
+    if (!c->hitsCounters.p) { HIPCHK(c, c->hitsCounters.alloc(8)); }
+    HIPCHK(c, hipMemsetAsync(c->hitsCounters.p, 0, 64, c->stream));
+    const StackLds stack = stack_lds(c, 0u);
+    DevScene qs = secondary_scene(c->dsc, (uint32_t)c->tuning[K_QUORUM_SECONDARY], c->countRays ? c->hitsCounters.p : nullptr);
+    qs.stackBudget = stack.budget;
+    const size_t ldsBytes = stack.bytes + (size_t)maxHits * 16u * kBlock;        // <= 32 KB + 32 KB
+    QueryHits q{};
+    q.rays = rays; q.after = after; q.hits = hits; q.counts = counts; q.count = count; q.maxHits = maxHits;
+    q.head = reinterpret_cast<uint32_t*>(c->hitsCounters.p + 5);
+    set_queue_params(c, q, K_REFILL_LANES);
+    const dim3 block(kBlock);
+    const uint32_t blocksForRays = (uint32_t)(((size_t)count + kBlock - 1) / kBlock);
+    const bool simple = simple_ray_kernel(c);                     // tuning key 15 as for the other queries
+    dim3 grid;
+    if (simple) grid = dim3(std::max(1u, std::min<uint32_t>((uint32_t)c->numCUs * 16u, blocksForRays)));
+    else {
+        const int occ = c->hitsOcc.get(k_query_hits<false>, ldsBytes, 2), perCU = c->tuning[K_WG_PER_CU] > 0 ? std::min(c->tuning[K_WG_PER_CU], occ) : occ;
+        grid = dim3(std::max(1u, std::min<uint32_t>((uint32_t)(c->numCUs * perCU), blocksForRays)));
+    }
+    if (timed) HIPCHK(c, hipEventRecord(c->hitsEv[0], c->stream));
+    static void (*const kHits[2][2])(DevScene, QueryHits) = {{k_query_hits<false>, k_query_hits<true>}, {k_query_hits_simple<false>, k_query_hits_simple<true>}};
+    hipLaunchKernelGGL(kHits[simple ? 1 : 0][c->countRays ? 1 : 0], grid, block, ldsBytes, c->stream, qs, q);
+    HIPCHK(c, hipGetLastError());
+    if (timed) HIPCHK(c, hipEventRecord(c->hitsEv[1], c->stream));
+    return FYPRT_OK;
+}
+
+int fyprt_trace_ray_hits(fyprt_context* c, const fyprt_ray* rays, const fyprt_ray_hit* after, uint32_t count, uint32_t max_hits, fyprt_ray_hit* hits,
+                         uint32_t* hit_counts, fyprt_frame_stats* stats) {
+    TRY(check_ray_hits(c, rays, after, count, max_hits, hits, hit_counts, false));
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (count == 0) return FYPRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t rayBytes = (size_t)count * sizeof(fyprt_ray), afterBytes = (size_t)count * sizeof(fyprt_ray_hit), hitBytes = afterBytes * max_hits;
+    for (Event& e : c->hitsEv) HIPCHK(c, create(e));
+    if (c->hitsRays.n < (size_t)count * 2) { HIPCHK(c, c->hitsRays.alloc((size_t)count * 2)); }          // staging grows, is kept
+    if (after && c->hitsAfter.n < (size_t)count) { HIPCHK(c, c->hitsAfter.alloc(count)); }
+    if (c->hitsOut.n < (size_t)count * max_hits) { HIPCHK(c, c->hitsOut.alloc((size_t)count * max_hits)); }
+    if (c->hitsCounts.n < (size_t)count) { HIPCHK(c, c->hitsCounts.alloc(count)); }
+    HIPCHK(c, hipMemcpyAsync(c->hitsRays.p, rays, rayBytes, hipMemcpyHostToDevice, c->stream));
+    if (after) HIPCHK(c, hipMemcpyAsync(c->hitsAfter.p, after, afterBytes, hipMemcpyHostToDevice, c->stream));
+    TRY(enqueue_ray_hits(c, c->hitsRays.p, after ? c->hitsAfter.p : nullptr, count, max_hits, c->hitsOut.p, c->hitsCounts.p, true));
+    HIPCHK(c, hipMemcpyAsync(hits, c->hitsOut.p, hitBytes, hipMemcpyDeviceToHost, c->stream));
+    if (hit_counts) HIPCHK(c, hipMemcpyAsync(hit_counts, c->hitsCounts.p, (size_t)count * 4u, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (stats) {
+        float ms = 0.0f;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->hitsEv[0], c->hitsEv[1]));
+        stats->kernel_ms = ms; stats->kernel_ms_part[0] = ms; stats->launches = 1;
+        if (c->countRays) {
+            unsigned long long r[5] = {0, 0, 0, 0, 0};
+            HIPCHK(c, hipMemcpy(r, c->hitsCounters.p, sizeof r, hipMemcpyDeviceToHost));
+            add_ray_stats(stats, 0, r);
+        }
+    }
+    return FYPRT_OK;
+}
+
+int fyprt_trace_ray_hits_device(fyprt_context* c, const void* rays, const void* after, uint32_t count, uint32_t max_hits, void* hits, void* hit_counts) {
+    TRY(check_ray_hits(c, rays, after, count, max_hits, hits, hit_counts, true));
+    if (count == 0) return FYPRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    return enqueue_ray_hits(c, static_cast<const float4*>(rays), static_cast<const float4*>(after), count, max_hits, static_cast<float4*>(hits),
+                            static_cast<uint32_t*>(hit_counts), false);
 }
 
 // ---- radiance queries (rt_query.h: k_render_rays_primary; rt_paths.h: the path stages with CAM = RaySource).  A frame's sample of

@@ -17,6 +17,8 @@
 //   k_query_rays_simple  one thread per ray, for small trees where rays are too cheap for the refill machinery to pay.
 // The query kind is a template parameter: neither kernel carries the other kind's branches.  They only call the traversal core of
 // rt_device.h (node_step, tri_test, make_hit / make_miss, quorum_of, ray_not_finite); no frame kernel is touched.
+// The multi-hit query (fyprt_trace_ray_hits*: the K nearest hits per ray in order) has the same two forms, k_query_hits and
+// k_query_hits_simple, further down.
 #pragma once
 #include "rt_paths.h"
 
@@ -199,6 +201,222 @@ __global__ __launch_bounds__(kBlock) void k_query_rays_simple(DevScene sc, Query
     for (uint32_t base = blockIdx.x * (uint32_t)kBlock; base < q.count; base += gridDim.x * (uint32_t)kBlock) {   // (block-uniform trips: node_step's ballots see whole waves)
         const uint32_t j = base + threadIdx.x;
         if (j < q.count) query_one<OCCLUDED, COUNT>(sc, q, j, s_stack + threadIdx.x);
+    }
+}
+
+// ============================================================ multi-hit queries (fyprt_trace_ray_hits*): the K nearest hits per ray
+// Every accepted hit (the closest-hit query's acceptance rule) has the 64-bit key (bits(t) << 32) | triangle: t > 1e-4, so the bit
+// pattern orders as the value (the key construction of k_graft_place).  The answer is the `maxHits` smallest keys above the key of
+// `after[i]` (0 without `after`), ascending — a function of the triangles alone, not of the tree or the visiting order.
+//   hit record : one float4 (16 B) = t | triangle (bits) | u | v, tri_test's values; unused = -1 | 0xFFFFFFFF | 0 | 0
+// The per-lane list is kept sorted in LDS behind the traversal stack, lane-strided like it: a plane of 64-bit keys and a plane of
+// (u, v) pairs, maxHits entries x kBlock threads each, read and written as 8-byte quantities (a lane's entries are 8 B apart in a
+// plane row: conflict-free for ds_read_b64 / ds_write_b64).  Its length and its worst key live in registers — `worst` is all ones
+// while the list is not full, so one 64-bit compare rejects a candidate without touching LDS.  Boxes are culled against
+// min(tmax, FLT_MAX) * 1.000001f until the list is full, then against t_worst * 1.000001f: a box entered at exactly t_worst is still
+// visited, a tie with a lower triangle index displaces the worst entry.
+struct QueryHits {
+    const float4* rays; const float4* after; float4* hits; uint32_t* counts; uint32_t count, maxHits; uint32_t* head;
+    uint32_t chunk, refillLanes, staticChunks, minChunk;
+};
+struct HitList {
+    unsigned long long* keys; float2* uv;       // &plane[threadIdx.x]; entry s at [s * kBlock]
+};
+constexpr unsigned long long kNoWorstKey = ~0ull;
+
+RT_DEV HitList hit_list(int32_t* s_stack, int32_t budget, uint32_t maxHits) {
+    HitList l;
+    l.keys = reinterpret_cast<unsigned long long*>(s_stack + (size_t)(budget + 1) * kBlock) + threadIdx.x;      // (the stack is a multiple of 1 KB: 8-byte aligned)
+    l.uv = reinterpret_cast<float2*>(l.keys + (size_t)maxHits * kBlock);
+    return l;
+}
+RT_DEV unsigned long long hit_key(float t, uint32_t tri) { return ((unsigned long long)__float_as_uint(t) << 32) | (unsigned long long)tri; }
+// The ray's start: the key every answer must exceed and whether the ray is to be traced at all (an `after` record with t < 0 is the
+// unused record of an earlier pass: the ray is finished)
+RT_DEV bool hits_start(const QueryHits& q, uint32_t i, unsigned long long& afterKey) {
+    afterKey = 0ull;
+    if (!q.after) return true;
+    const float4 a = q.after[i];
+    if (a.x < 0.0f) return false;
+    afterKey = hit_key(a.x, __float_as_uint(a.y));
+    return true;
+}
+// Inserts (key, u, v) with afterKey < key < worst into the sorted list of n <= maxHits entries; a key the list holds already is dropped
+// (no visit order may duplicate a hit).  Find the place from the tail, then shift from the tail; a full list loses its last entry.
+RT_DEV void hit_insert(const HitList& l, uint32_t maxHits, uint32_t& n, unsigned long long& worst, unsigned long long key, float u, float v) {
+    uint32_t pos = n;
+    while (pos > 0u) {
+        const unsigned long long k = l.keys[(size_t)(pos - 1u) * kBlock];
+        if (k == key) return;
+        if (k < key) break;
+        --pos;
+    }
+    for (uint32_t j = n < maxHits ? n : maxHits - 1u; j > pos; --j) {
+        l.keys[(size_t)j * kBlock] = l.keys[(size_t)(j - 1u) * kBlock];
+        l.uv[(size_t)j * kBlock] = l.uv[(size_t)(j - 1u) * kBlock];
+    }
+    l.keys[(size_t)pos * kBlock] = key; l.uv[(size_t)pos * kBlock] = make_float2(u, v);
+    if (n < maxHits) ++n;
+    if (n == maxHits) worst = l.keys[(size_t)(maxHits - 1u) * kBlock];
+}
+// One leaf's triangles against the list; returns the box cut that holds afterwards
+RT_DEV float hits_leaf(const DevScene& sc, const HitList& l, uint32_t maxHits, int32_t cur, f3 o, f3 d, float tmin, float hi, unsigned long long afterKey,
+                       uint32_t& n, unsigned long long& worst, float cut, uint32_t& nTri, bool count) {
+    const uint32_t code = (uint32_t)~cur, firstTri = code >> 2, cnt = (code & 3u) + 1u;
+    for (uint32_t k = 0; k < cnt; ++k) {
+        float t, u, v; uint32_t id;
+        if (count) nTri += 1;
+        if (!tri_test(sc.leafTris + (size_t)(firstTri + k) * 3, o, d, t, u, v, id) || !(t > tmin) || !(t < hi)) continue;
+        const unsigned long long key = hit_key(t, id);
+        if (key <= afterKey || key >= worst) continue;
+        hit_insert(l, maxHits, n, worst, key, u, v);
+        if (n == maxHits) cut = __uint_as_float((uint32_t)(worst >> 32)) * 1.000001f;
+    }
+    return cut;
+}
+// The finished ray's maxHits records as 16-byte stores, then its count
+RT_DEV void store_hits(const QueryHits& q, const HitList& l, uint32_t i, uint32_t n) {
+    float4* dst = q.hits + (size_t)i * q.maxHits;
+    for (uint32_t s = 0; s < q.maxHits; ++s) {
+        float4 r = make_float4(-1.0f, __uint_as_float(0xFFFFFFFFu), 0.0f, 0.0f);
+        if (s < n) {
+            const unsigned long long k = l.keys[(size_t)s * kBlock]; const float2 uv = l.uv[(size_t)s * kBlock];
+            r = make_float4(__uint_as_float((uint32_t)(k >> 32)), __uint_as_float((uint32_t)k), uv.x, uv.y);
+        }
+        dst[s] = r;
+    }
+    if (q.counts) q.counts[i] = n;
+}
+
+// Persistent waves: the scheduling of query_rays_body (refill, guided claims, node-loop quorum), the per-ray state of the list instead
+// of the closest hit's.
+template <bool COUNT>
+RT_DEV void query_hits_body(const DevScene& sc, const QueryHits& q, int32_t* s_stack) {
+    int32_t* lds = s_stack + threadIdx.x;
+    const HitList list = hit_list(s_stack, sc.stackBudget, q.maxHits);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t total = q.count;
+    const uint32_t nWaves = gridDim.x * (uint32_t)(kBlock / 64), myWave = blockIdx.x * (uint32_t)(kBlock / 64) + (threadIdx.x >> 6);
+    const uint32_t share = (total + nWaves - 1u) / nWaves;
+    const uint32_t chunk = q.chunk, want1 = chunk * q.staticChunks;
+    const uint32_t first = share < want1 ? (share < 16u ? 16u : share) : want1;
+    const uint32_t dynBase = nWaves * first;
+    const bool hasDyn = dynBase < total;
+    f3 d = splat3(0.0f); RayPk pk = make_raypk(d, 1.0f, 1.0f, 1.0f);
+    float tmin = 0.0f, hi = 0.0f, cut = 0.0f; uint32_t task = 0, n = 0; int32_t cur = kExit; int top = 0;
+    unsigned long long worst = kNoWorstKey, afterKey = 0ull;
+    uint32_t nBox = 0, nTri = 0, nNode = 0;
+    bool active = false;
+    bool more = total != 0u;
+    uint32_t chunkNext = myWave * first < total ? myWave * first : total;
+    uint32_t chunkEnd = (myWave + 1u) * first < total ? (myWave + 1u) * first : total;
+    while (true) {
+        const unsigned long long idle = __ballot(!active);
+        if (more && (uint32_t)__popcll(idle) >= q.refillLanes) {
+            if (chunkNext >= chunkEnd && hasDyn) {
+                uint32_t base = 0;
+                uint32_t size = (total - chunkEnd) / nWaves;
+                size = size < q.minChunk ? q.minChunk : (size > chunk ? chunk : size);
+                if (lane == 0u) base = dynBase + atomicAdd(q.head, size);
+                base = (uint32_t)__shfl((int)base, 0);
+                chunkNext = base < total ? base : total;
+                chunkEnd = (base + size < total) ? base + size : total;
+            }
+            const uint32_t slot = chunkNext + (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
+            const uint32_t want = (uint32_t)__popcll(idle), avail = chunkEnd - chunkNext;
+            chunkNext += (want < avail) ? want : avail;
+            more = chunkNext < chunkEnd || (hasDyn && chunkEnd < total);
+            if (!active && slot < chunkEnd) {
+                task = slot;
+                const float4 r0 = q.rays[(size_t)task * 2], r1 = q.rays[(size_t)task * 2 + 1];
+                const f3 o = mk3(r0.x, r0.y, r0.z); d = mk3(r1.x, r1.y, r1.z); tmin = r0.w;
+                pk = make_raypk(o, safe_inv(d.x), safe_inv(d.y), safe_inv(d.z));
+                hi = query_start(r1.w);
+                cut = hi * 1.000001f;
+                n = 0; worst = kNoWorstKey;
+                if (COUNT) { nBox = 0; nTri = 0; nNode = 0; }
+                top = 0; lane_push(lds, top, kExit);
+                const bool wanted = hits_start(q, task, afterKey);
+                cur = (sc.triCount == 0 || !wanted || query_invalid(o, d, tmin, r1.w)) ? kExit : sc.rootRef;
+                active = true;
+            }
+        }
+        if (__ballot(active) == 0ull) { if (!more) break; else continue; }
+        while (true) {
+            bool walk = active && cur >= 0;
+            const uint32_t quorum = quorum_of(sc.nodeQuorum, (uint32_t)__popcll(__ballot(active)));
+            while (walk) {
+                { Stack st; st.lds = lds; st.top = top; cur = node_step<COUNT>(sc.nodes, sc.stackBudget, cur, pk, cut, st, nBox, nNode); top = st.top; }
+                walk = cur >= 0;
+                if ((uint32_t)__popcll(__ballot(walk)) < quorum) break;
+            }
+            if (active && cur < 0 && cur != kExit) {
+                cut = hits_leaf(sc, list, q.maxHits, cur, mk3(pk.ox, pk.oy, pk.oz), d, tmin, hi, afterKey, n, worst, cut, nTri, COUNT);
+                cur = lane_pop(lds, top);
+            }
+            if (active && cur == kExit) {
+                store_hits(q, list, task, n);
+                count_query_ray<COUNT>(sc, nBox, nTri, nNode, n != 0u);
+                active = false;
+            }
+            const unsigned long long act = __ballot(active);
+            if (act == 0ull) break;
+            if (more && (64u - (uint32_t)__popcll(act)) >= q.refillLanes) break;
+        }
+    }
+}
+
+template <bool COUNT> __global__ void k_query_hits(DevScene sc, QueryHits q);
+// Compiled for 5 waves per SIMD (96 VGPRs, 12 B of scratch as k_query_rays<false, false>), not the 6 of RT_TRACE_WAVES (80 VGPRs, 20 B: the
+// list's length, its worst key and the `after` key are five more live registers): the list's LDS leaves room for no more than 5
+// workgroups per CU from a 26-entry stack on (26 x 4 + 16 B per thread = 30 KB), so the sixth wave would be bought for small trees only.
+template <> __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5))) void k_query_hits<false>(DevScene sc, QueryHits q) {
+    extern __shared__ int32_t s_stack[];                         // (stackBudget + 1) x 4 B + maxHits x 16 B per thread, sized at launch
+    query_hits_body<false>(sc, q, s_stack);
+}
+template <> __global__ __launch_bounds__(kBlock) void k_query_hits<true>(DevScene sc, QueryHits q) {          // instrumented: no register cap
+    extern __shared__ int32_t s_stack[];
+    query_hits_body<true>(sc, q, s_stack);
+}
+
+// One thread per ray, as query_one
+template <bool COUNT>
+RT_DEV void query_hits_one(const DevScene& sc, const QueryHits& q, uint32_t i, int32_t* ldsBase, const HitList& list) {
+    const float4 r0 = q.rays[(size_t)i * 2], r1 = q.rays[(size_t)i * 2 + 1];
+    const f3 o = mk3(r0.x, r0.y, r0.z), d = mk3(r1.x, r1.y, r1.z);
+    const float tmin = r0.w, hi = query_start(r1.w);
+    float cut = hi * 1.000001f;
+    uint32_t n = 0; unsigned long long worst = kNoWorstKey, afterKey;
+    uint32_t nBox = 0, nTri = 0, nNode = 0;
+    const bool wanted = hits_start(q, i, afterKey);
+    if (!(sc.triCount == 0 || !wanted || query_invalid(o, d, tmin, r1.w))) {
+        const RayPk pk = make_raypk(o, safe_inv(d.x), safe_inv(d.y), safe_inv(d.z));
+        Stack st; st.lds = ldsBase; st.top = 0; st.push(kExit);
+        int32_t cur = sc.rootRef;
+        while (true) {
+            bool walk = cur >= 0;
+            const uint32_t quorum = quorum_of(sc.nodeQuorum, (uint32_t)__popcll(__ballot(true)));
+            while (walk) {
+                cur = node_step<COUNT>(sc.nodes, sc.stackBudget, cur, pk, cut, st, nBox, nNode);
+                walk = cur >= 0;
+                if ((uint32_t)__popcll(__ballot(walk)) < quorum) break;
+            }
+            if (cur >= 0) continue;
+            if (cur == kExit) break;
+            cut = hits_leaf(sc, list, q.maxHits, cur, o, d, tmin, hi, afterKey, n, worst, cut, nTri, COUNT);
+            cur = st.pop();
+        }
+    }
+    store_hits(q, list, i, n);
+    count_query_ray<COUNT>(sc, nBox, nTri, nNode, n != 0u);
+}
+template <bool COUNT>
+__global__ __launch_bounds__(kBlock) void k_query_hits_simple(DevScene sc, QueryHits q) {
+    extern __shared__ int32_t s_stack[];                         // (stackBudget + 1) x 4 B + maxHits x 16 B per thread, sized at launch
+    const HitList list = hit_list(s_stack, sc.stackBudget, q.maxHits);
+    for (uint32_t base = blockIdx.x * (uint32_t)kBlock; base < q.count; base += gridDim.x * (uint32_t)kBlock) {   // (block-uniform trips: node_step's ballots see whole waves)
+        const uint32_t j = base + threadIdx.x;
+        if (j < q.count) query_hits_one<COUNT>(sc, q, j, s_stack + threadIdx.x, list);
     }
 }
 

@@ -665,6 +665,38 @@ int fyprt_trace_rays(fyprt_context* ctx, int query /* enum fyprt_query */, const
 /* Device memory of the context's GPU (rays: count x fyprt_ray; results as above), asynchronous on the context stream (fyprt_stream). */
 int fyprt_trace_rays_device(fyprt_context* ctx, int query /* enum fyprt_query */, const void* rays, uint32_t count, void* results);
 
+/* Ordered multi-hit query: the max_hits nearest accepted triangles per ray, in order ("Multi-hit queries") — picking through
+ * an occluder, thickness and penetration probes, ordered layers, crossing counts.
+ *   Acceptance  : as FYPRT_QUERY_CLOSEST — the Möller–Trumbore passes, t > tmin and t < min(tmax, FLT_MAX).
+ *   Order       : every accepted hit has the 64-bit key (bits(t) << 32) | triangle; t > 1e-4, so the bit pattern of t orders as its value.
+ *                 The answer for a ray is its max_hits smallest keys in ascending order: exact-t ties go to the lower triangle index.  The
+ *                 answer does not depend on the tree, the builder or the visiting order.
+ *   Record      : t, u, v as the ray/triangle test returns them (u, v: the barycentrics, not the payload's texture coordinates);
+ *                 triangle: the scene triangle index (the payload's objectIndex).  Unused records are {-1.0f, 0xFFFFFFFF, 0, 0};
+ *                 hit_counts[i] = the number of used records of ray i (hit_counts may be NULL).
+ *   Continuation: with `after` (count records), a hit is accepted only if its key is greater than the key of after[i] (its u, v are
+ *                 ignored); an after[i] with t < 0 — the unused record — means "this ray is finished": zero hits, no traversal.  So
+ *                 passing each pass's LAST record per ray back in until every count is 0 enumerates all hits: none is skipped or
+ *                 repeated, exact ties included (which tracing again with tmin = t cannot give: t > tmin skips a second triangle at that t).
+ *   Invalid rays: as above — zero hits without traversal, counted as a ray with no tests.
+ * Errors, in this order: FYPRT_EINVAL for a NULL context, max_hits 0 or above FYPRT_QUERY_MAX_HITS, NULL rays / hits with count > 0, and
+ * (device entry) rays, after or hits not 16-byte or hit_counts not 4-byte aligned; FYPRT_ESTATE on a host-only context or before
+ * fyprt_upload_scene; count 0 returns FYPRT_OK and launches nothing.
+ * No frame state moves, as for fyprt_trace_rays: the query has its own counters and queue head, and the host entry's staging buffers
+ * grow on demand and are kept.  The kernel follows tuning key 15 (and keys 4, 5, 6, 9, 10) as the other queries'; each lane keeps its
+ * sorted list in LDS behind the traversal stack, 16 bytes per entry — with the deepest stack, 8 entries fill the 64 KB a workgroup may
+ * have, which is why the cap is 8. */
+#define FYPRT_QUERY_MAX_HITS 8
+typedef struct fyprt_ray_hit { float t; uint32_t triangle; float u, v; } fyprt_ray_hit;   /* 16 B, 16-B aligned on the device */
+/* Host memory, blocking.  `hits`: count x max_hits records, ray-major.  `stats` may be NULL; it is filled as fyprt_trace_rays fills it,
+ * `hits` counting the rays with at least one record. */
+int fyprt_trace_ray_hits(fyprt_context* ctx, const fyprt_ray* rays, const fyprt_ray_hit* after /* NULL or count */, uint32_t count,
+                         uint32_t max_hits, fyprt_ray_hit* hits /* count x max_hits */, uint32_t* hit_counts /* NULL or count */,
+                         fyprt_frame_stats* stats /* may be NULL */);
+/* Device memory of the context's GPU, asynchronous on the context stream (fyprt_stream). */
+int fyprt_trace_ray_hits_device(fyprt_context* ctx, const void* rays, const void* after, uint32_t count, uint32_t max_hits, void* hits,
+                                void* hit_counts);
+
 /* ================================================================================================= radiance queries
  * New (no reference counterpart): the renderer's sample of techniques 0-6 for the caller's own rays — other camera models, light probes,
  * surface bakes, re-rendering a few pixels ("Radiance queries").  Only an uploaded scene is needed (no resize, no camera).

@@ -6,7 +6,12 @@
 One JSON line per set: rays, median hipEvent ms of the query launch over --calls calls after warm-up, Mrays/s, node visits per ray
 (one counted call).  The same run times ReSTIR DI Part 1 stand-alone (fyprt_render_part(..., 1)), which traces the camera rays of (a)
 and does its reservoir work on top.
-  usage: python tools/query_rate.py [--calls 20] [--out FILE.jsonl]"""
+  usage: python tools/query_rate.py [--calls 20] [--out FILE.jsonl]
+With --hits K [K ...]: the multi-hit query (fyprt_trace_ray_hits) instead, on sets (a), (b) and (c) (the shadow segments as rays with
+their tmax): per set one line for FYPRT_QUERY_CLOSEST and one per K, timed in the same run on the same rays — median, minimum and
+maximum hipEvent ms over --calls calls after warm-up, Mrays/s, records (hits) per second, and the ratio to the closest-hit query.
+Written to profiles/query/hits_rate.jsonl unless --out names another file.
+  usage: python tools/query_rate.py --hits 1 2 4 8 [--calls 20] [--out FILE.jsonl]"""
 import argparse
 import json
 import statistics
@@ -84,25 +89,9 @@ def camera_rays(cam):
     return o, d
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--calls", type=int, default=20)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("query_rate.py needs an MI355X")
-    torch.cuda.set_device(0)
-    W, H = 1920, 1080
-    rows = []
-    rng = np.random.default_rng(2024)
-    hall, cam = scenes.hall_scene(), scenes.hall_camera(W, H)
-    ctx = capi.Context(0)
-    ctx.resize(W, H)
-    ctx.upload_scene(hall)
-    ctx.set_camera(cam)
-    o, d = camera_rays(cam)
-    ra, res = rate(ctx, "a_camera", "hall_1M", o, d, a.calls)
-    rows.append(ra)
+def hall_ray_sets(hall, d, rng, camera_hits):
+    """The sets (b) and (c) derived from the camera hits of (a): (bounce origins, bounce directions), (shadow directions, tmax)."""
+    res = camera_hits
     hit = res["objectIndex"] >= 0
     p = res["worldPosition"][hit].astype(F32)
     n = res["worldNormal"][hit].astype(F32)
@@ -114,7 +103,6 @@ def main():
     t /= np.linalg.norm(t, axis=1, keepdims=True)
     b = np.cross(n, t)
     bd = (t * (r * np.cos(phi))[:, None] + b * (r * np.sin(phi))[:, None] + n * np.sqrt(1 - u1)[:, None]).astype(F32)
-    rows.append(rate(ctx, "b_bounce", "hall_1M", p, bd, a.calls)[0])
     # (c) shadow segments to a random point of a random emissive triangle
     em = hall.init_scene_emissive_triangles()
     pos = hall.world_vertices["position"]
@@ -124,7 +112,78 @@ def main():
     q = (1 - s)[:, None] * pos[tri["v0"]] + ((1 - r2) * s)[:, None] * pos[tri["v1"]] + (r2 * s)[:, None] * pos[tri["v2"]]
     v = q - p
     dist = np.linalg.norm(v, axis=1)
-    rows.append(rate(ctx, "c_shadow", "hall_1M", p, (v / dist[:, None]).astype(F32), a.calls, tmax=(0.999 * dist).astype(F32), occluded=True)[0])
+    return p, bd, (v / dist[:, None]).astype(F32), (0.999 * dist).astype(F32)
+
+
+def hits_rate(ctx, name, o, d, tmax, ks, calls):
+    """One ray set: the closest-hit query, then the multi-hit query per K, each warmed up and timed over `calls` calls."""
+    rows = []
+
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        ms = [fn().kernel_ms for _ in range(calls)]
+        return statistics.median(ms), min(ms), max(ms)
+    med0, lo0, hi0 = timed(lambda: ctx.trace_rays(o, d, 0.0, tmax, with_stats=True)[1])
+    rows.append({"set": name, "scene": "hall_1M", "query": "closest", "rays": len(o), "ms_median": round(med0, 4), "ms_min": round(lo0, 4),
+                 "ms_max": round(hi0, 4), "calls": calls, "mrays_per_s": round(len(o) / med0 / 1e3, 1)})
+    for k in ks:
+        med, lo, hi = timed(lambda: ctx.trace_ray_hits(o, d, 0.0, tmax, max_hits=k, with_stats=True)[2])
+        counts = ctx.trace_ray_hits(o, d, 0.0, tmax, max_hits=k)[1]
+        records = int(counts.sum())
+        rows.append({"set": name, "scene": "hall_1M", "query": "hits", "max_hits": k, "rays": len(o), "ms_median": round(med, 4),
+                     "ms_min": round(lo, 4), "ms_max": round(hi, 4), "calls": calls, "mrays_per_s": round(len(o) / med / 1e3, 1),
+                     "records": records, "mhits_per_s": round(records / med / 1e3, 1), "records_per_ray": round(records / len(o), 3),
+                     "ms_over_closest": round(med / med0, 3)})
+    return rows
+
+
+def main_hits(a):
+    W, H = 1920, 1080
+    rng = np.random.default_rng(2024)
+    hall, cam = scenes.hall_scene(), scenes.hall_camera(W, H)
+    ctx = capi.Context(0)
+    ctx.upload_scene(hall)
+    o, d = camera_rays(cam)
+    p, bd, sd, smax = hall_ray_sets(hall, d, rng, ctx.trace_rays(o, d))
+    rows = hits_rate(ctx, "a_camera", o, d, np.inf, a.hits, a.calls)
+    rows += hits_rate(ctx, "b_bounce", p, bd, np.inf, a.hits, a.calls)
+    rows += hits_rate(ctx, "c_shadow", p, sd, smax, a.hits, a.calls)
+    ctx.close()
+    lines = [json.dumps(r) for r in rows]
+    print("\n".join(lines))
+    out = Path(a.out) if a.out else ROOT / "profiles" / "query" / "hits_rate.jsonl"
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text("\n".join(lines) + "\n")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--hits", type=int, nargs="+", default=None, metavar="K", help="time the multi-hit query at these max_hits instead")
+    a = ap.parse_args()
+    if a.hits and not all(1 <= k <= capi.QUERY_MAX_HITS for k in a.hits):
+        raise SystemExit(f"--hits takes values in 1..{capi.QUERY_MAX_HITS}")
+    if not torch.cuda.is_available():
+        raise SystemExit("query_rate.py needs an MI355X")
+    torch.cuda.set_device(0)
+    if a.hits:
+        return main_hits(a)
+    W, H = 1920, 1080
+    rows = []
+    rng = np.random.default_rng(2024)
+    hall, cam = scenes.hall_scene(), scenes.hall_camera(W, H)
+    ctx = capi.Context(0)
+    ctx.resize(W, H)
+    ctx.upload_scene(hall)
+    ctx.set_camera(cam)
+    o, d = camera_rays(cam)
+    ra, res = rate(ctx, "a_camera", "hall_1M", o, d, a.calls)
+    rows.append(ra)
+    p, bd, sd, smax = hall_ray_sets(hall, d, rng, res)
+    rows.append(rate(ctx, "b_bounce", "hall_1M", p, bd, a.calls)[0])
+    rows.append(rate(ctx, "c_shadow", "hall_1M", p, sd, a.calls, tmax=smax, occluded=True)[0])
     p1 = part1_ms(ctx, a.calls)
     rows.append({"set": "restir_di_part1", "scene": "hall_1M", "rays": W * H, "ms_median": round(p1[0], 4), "ms_min": round(p1[1], 4),
                  "ms_max": round(p1[2], 4), "calls": a.calls, "camera_query_over_part1": round(ra["ms_median"] / p1[0], 3),
