@@ -26,6 +26,19 @@ def struct_equal(a, b):
     return ok
 
 
+def _compare_buffers(ctx, orc, tech, rows=None):
+    y0, y1 = rows if rows else (0, ctx.height)
+    sl = slice(y0 * ctx.width, y1 * ctx.width)
+    bufs = [capi.BUF_PAYLOAD, capi.BUF_DEPTH] + ([capi.BUF_DI_PREV] if tech == capi.RESTIR_DI else [capi.BUF_GI_PREV])
+    if rows is None:
+        bufs += [capi.BUF_NORMAL, capi.BUF_DI if tech == capi.RESTIR_DI else capi.BUF_GI]
+    for b in bufs:
+        g, o = ctx.read_buffer(b)[sl], orc.read_buffer(b)[sl]
+        ok = struct_equal(g, o) if g.dtype.names else bits_equal(g, o)
+        ok = ok.all(axis=-1) if ok.ndim > 1 else ok
+        assert ok.all(), f"buffer {b}: {(~ok).sum()} records differ"
+
+
 SCENES = {
     "cornell": (lambda: scenes.cornell_box(), scenes.cornell_camera),
     "hall_small": (lambda: scenes.hall_scene_small(), scenes.hall_camera),

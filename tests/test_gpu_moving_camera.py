@@ -12,7 +12,7 @@ reprojects outside the band must read as "none" (DESIGN.md §5 R7)."""
 import numpy as np
 import pytest
 
-from common import SCENES, bits_equal, settings_for, struct_equal
+from common import SCENES, _compare_buffers, bits_equal, settings_for
 from fypraytracer_amd import capi, multigpu
 
 pytestmark = pytest.mark.gpu
@@ -26,19 +26,6 @@ REF_NEW_PER_FRAME = {"cornell": 0.025, "hall_small": 0.004}     # pixels newly t
 def _pose(cam, f):
     keys, mouse = MOVES[f % len(MOVES)]
     cam.on_update(0.05, keys, mouse)
-
-
-def _compare_buffers(ctx, orc, tech, rows=None):
-    y0, y1 = rows if rows else (0, ctx.height)
-    sl = slice(y0 * ctx.width, y1 * ctx.width)
-    bufs = [capi.BUF_PAYLOAD, capi.BUF_DEPTH] + ([capi.BUF_DI_PREV] if tech == capi.RESTIR_DI else [capi.BUF_GI_PREV])
-    if rows is None:
-        bufs += [capi.BUF_NORMAL, capi.BUF_DI if tech == capi.RESTIR_DI else capi.BUF_GI]
-    for b in bufs:
-        g, o = ctx.read_buffer(b)[sl], orc.read_buffer(b)[sl]
-        ok = struct_equal(g, o) if g.dtype.names else bits_equal(g, o)
-        ok = ok.all(axis=-1) if ok.ndim > 1 else ok
-        assert ok.all(), f"buffer {b}: {(~ok).sum()} records differ"
 
 
 def _reprojection_moves(ctx, cam):
