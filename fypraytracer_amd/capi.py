@@ -66,6 +66,10 @@ QUERY_CLOSEST, QUERY_OCCLUDED = 0, 1
 RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("triangle", "<u4"), ("u", "<f4"), ("v", "<f4")])
 assert RAY_HIT_DTYPE.itemsize == 16
 QUERY_MAX_HITS = 8               # FYPRT_QUERY_MAX_HITS
+# nearest-point queries (fyprt_nearest_points): fyprt_point and fyprt_point_hit (16 B each); the unused record as above
+POINT_DTYPE = np.dtype([("position", "<f4", (3,)), ("max_distance", "<f4")])
+POINT_HIT_DTYPE = np.dtype([("distance2", "<f4"), ("triangle", "<u4"), ("u", "<f4"), ("v", "<f4")])
+assert POINT_DTYPE.itemsize == 16 and POINT_HIT_DTYPE.itemsize == 16
 RENDER_RAYS_CHUNK = 1 << 21      # FYPRT_RENDER_RAYS_CHUNK: rays per internal pass of fyprt_render_rays*
 BVH_NODE_DTYPE = np.dtype([("origin", "<f4", 3), ("ex", "u1", 3), ("meta", "u1"), ("child", "<i4", 4),
                            ("qlo", "u1", (3, 4)), ("qhi", "u1", (3, 4)), ("pad", "<u4", 2)])
@@ -246,6 +250,7 @@ EXPORTED_SYMBOLS = [
     "fyprt_set_append_placement", "fyprt_last_append_placement",
     "fyprt_regraft_meshes", "fyprt_tree_cost",
     "fyprt_kept_primary_frames",
+    "fyprt_nearest_points", "fyprt_nearest_points_device",
 ]
 # enum fyprt_probe (fyprt_selftest_functions) and the 32-bit words of one input / output record of each probe
 (PROBE_SINCOS, PROBE_ACOS, PROBE_POW5, PROBE_RND, PROBE_OCT_ENCODE, PROBE_OCT_DECODE, PROBE_PACK_ABGR, PROBE_UNPACK_ABGR, PROBE_EVAL_BRDF,
@@ -324,6 +329,9 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     if hasattr(lib, "fyprt_trace_ray_hits"):
         lib.fyprt_trace_ray_hits.argtypes = [vp, vp, vp, u32, u32, vp, vp, C.POINTER(FrameStats)]
         lib.fyprt_trace_ray_hits_device.argtypes = [vp, vp, vp, u32, u32, vp, vp]
+    if hasattr(lib, "fyprt_nearest_points"):   # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
+        lib.fyprt_nearest_points.argtypes = [vp, vp, vp, u32, u32, vp, vp, C.POINTER(FrameStats)]
+        lib.fyprt_nearest_points_device.argtypes = [vp, vp, vp, u32, u32, vp, vp]
     if hasattr(lib, "fyprt_render_rays"):    # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
         lib.fyprt_render_rays.argtypes = [vp, C.POINTER(Settings), u32, vp, vp, u32, u32, vp, vp, C.POINTER(FrameStats)]
         lib.fyprt_render_rays_device.argtypes = [vp, C.POINTER(Settings), u32, vp, vp, u32, u32, vp, vp]
@@ -865,6 +873,88 @@ class Context:
         offsets = np.concatenate([[0], np.cumsum(total)]).astype(np.int64)
         flat = [p for ps in parts for p in ps]
         records = np.concatenate(flat) if flat else np.empty(0, dtype=RAY_HIT_DTYPE)
+        return records, offsets
+
+    @staticmethod
+    def _point_records(who, points, max_distance):
+        p = np.asarray(points, dtype=np.float32)
+        if p.ndim == 0 or p.size % 3 or (p.ndim > 1 and p.shape[-1] != 3):
+            raise ValueError(f"{who}: points must be (N, 3), got shape {p.shape}")
+        p = p.reshape(-1, 3)
+        n = len(p)
+        md = np.asarray(max_distance, dtype=np.float32)
+        if md.ndim > 1 or (md.ndim == 1 and len(md) != n):
+            raise ValueError(f"{who}: max_distance must be a scalar or {n} values")
+        rec = np.empty(n, dtype=POINT_DTYPE)
+        rec["position"], rec["max_distance"] = p, np.broadcast_to(md, (n,))
+        return rec
+
+    def nearest_points(self, points, max_distance=np.inf, max_hits=1, after=None, with_stats=False):
+        """Nearest-point query (fyprt_nearest_points, blocking): the `max_hits` closest triangles to each point, ascending by
+        (distance2, triangle).  `points`: (N, 3); `max_distance`: a scalar or (N,) array, only triangles within it are answered;
+        `after`: None or N POINT_HIT_DTYPE records — only triangles beyond after[i] in that order are returned, and a record with
+        distance2 < 0 (the unused record) finishes the point.  Returns (hits (N, K) POINT_HIT_DTYPE, counts (N,) uint32); unused
+        records are (-1, 0xFFFFFFFF, 0, 0); with `with_stats` also the FrameStats of the launch."""
+        k = self._check_max_hits("nearest_points", max_hits)
+        rec = self._point_records("nearest_points", points, max_distance)
+        n = len(rec)
+        aft = None
+        if after is not None:
+            aft = np.asarray(after)
+            if aft.dtype != POINT_HIT_DTYPE or aft.size != n:
+                raise ValueError(f"nearest_points: after must be {n} POINT_HIT_DTYPE records")
+            aft = np.ascontiguousarray(aft.reshape(-1))
+        hits = np.empty((n, k), dtype=POINT_HIT_DTYPE)
+        counts = np.empty(n, dtype=np.uint32)
+        st = FrameStats()
+        self._check(self.lib.fyprt_nearest_points(self.h, _ptr(rec), _ptr(aft), n, k, _ptr(hits), _ptr(counts), C.byref(st)))
+        return (hits, counts, st) if with_stats else (hits, counts)
+
+    def nearest_points_tensor(self, points, max_hits, after=None):
+        """Nearest-point query on device tensors (fyprt_nearest_points_device).  `points`: contiguous float32 (N, 4) tensor on this
+        context's GPU, one fyprt_point per row (position, max_distance); `after`: None or a contiguous float32 (N, 4) tensor of hit
+        records.  Returns a float32 (N, K, 4) tensor of records (distance2, triangle bits, u, v) and an int32 (N,) tensor of counts.
+        Ordered against torch's current stream exactly as trace_ray_hits_tensor is."""
+        import torch
+        k = self._check_max_hits("nearest_points_tensor", max_hits)
+        if not isinstance(points, torch.Tensor) or points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous():
+            raise ValueError("nearest_points_tensor: points must be a contiguous float32 (N, 4) tensor")
+        if points.device.type != "cuda" or (points.device.index if points.device.index is not None else torch.cuda.current_device()) != self.device:
+            raise ValueError(f"nearest_points_tensor: points must be on cuda:{self.device}, the context's GPU")
+        n = points.shape[0]
+        if after is not None and (after.dtype != torch.float32 or tuple(after.shape) != (n, 4) or not after.is_contiguous() or after.device != points.device):
+            raise ValueError("nearest_points_tensor: after must be a contiguous float32 (N, 4) tensor on the points' device")
+        hits = torch.empty((n, k, 4), dtype=torch.float32, device=points.device)
+        counts = torch.empty((n,), dtype=torch.int32, device=points.device)
+        cur = torch.cuda.current_stream(points.device)
+        ext = torch.cuda.ExternalStream(self.stream(), device=points.device)
+        ext.wait_stream(cur)                                           # points / after are written, the outputs allocated before the query runs
+        self._check(self.lib.fyprt_nearest_points_device(self.h, C.c_void_p(points.data_ptr()), C.c_void_p(after.data_ptr()) if after is not None else None,
+                                                         n, k, C.c_void_p(hits.data_ptr()), C.c_void_p(counts.data_ptr())))
+        cur.wait_stream(ext)                                           # torch's later work follows it
+        return hits, counts
+
+    def triangles_within(self, points, radius, max_hits=QUERY_MAX_HITS):
+        """Every triangle within `radius` (a scalar or (N,) array) of every point, nearest first: continuation passes of nearest_points
+        until every point is finished.  Returns (records, offsets) shaped as trace_all_hits': flat POINT_HIT_DTYPE records, point i's in
+        records[offsets[i]:offsets[i + 1]], offsets int64 (N + 1,)."""
+        k = self._check_max_hits("triangles_within", max_hits)
+        rec = self._point_records("triangles_within", points, radius)
+        n = len(rec)
+        live = np.arange(n)                                            # points not finished yet; only they are asked again
+        after = None
+        parts = [[] for _ in range(n)]
+        while len(live):
+            hits, counts = self.nearest_points(rec["position"][live], rec["max_distance"][live], k, after)
+            for j, i in enumerate(live):
+                if counts[j]:
+                    parts[i].append(hits[j, :counts[j]])
+            go = counts == k                                           # a point with a short list has no further triangle
+            live, after = live[go], np.ascontiguousarray(hits[go, k - 1])
+        total = np.array([sum(len(p) for p in ps) for ps in parts], dtype=np.int64)
+        offsets = np.concatenate([[0], np.cumsum(total)]).astype(np.int64)
+        flat = [p for ps in parts for p in ps]
+        records = np.concatenate(flat) if flat else np.empty(0, dtype=POINT_HIT_DTYPE)
         return records, offsets
 
     def render_rays(self, origins, directions, settings: Settings, frame_index=1, first_index=0, pixel_indices=None, tmin=0.0, tmax=np.inf,

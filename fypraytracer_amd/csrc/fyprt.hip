@@ -17,6 +17,7 @@
 #include "rt_materials.h"
 #include "rt_paths.h"
 #include "rt_query.h"
+#include "rt_points.h"
 #include "rt_denoise.h"
 #include "rt_temporal.h"
 #include "rt_upscale.h"
@@ -213,7 +214,7 @@ struct fyprt_context {
     int lastLaunches = 0;
     size_t queueStride = 0;                     // float4s per task queue
     size_t sortGroups = 0;                      // setup workgroups the sort scratch is sized for (per parity)
-    OccCache traceOcc, pathOcc, gi2Occ, queryOcc[2], hitsOcc;   // k_di_part2_trace, k_trace_rays, k_gi2_persistent, k_query_rays<kind, false>, k_query_hits<false>
+    OccCache traceOcc, pathOcc, gi2Occ, queryOcc[2], hitsOcc, pointsOcc;   // k_di_part2_trace, k_trace_rays, k_gi2_persistent, k_query_rays<kind, false>, k_query_hits<false>, k_query_points<false>
     int tuning[K_COUNT];                        // by TuningKey, defaults from kTuning
     int numCUs = 256;
     // wavefront path engine (rt_paths.h): two ray lists + results (ping-pong), per-pixel path state, pixel lists, list counters
@@ -226,6 +227,9 @@ struct fyprt_context {
     // multi-hit queries (fyprt_trace_ray_hits*, rt_query.h), allocated on the first one: their own counters (laid out as the batched
     // queries'), the host entry's staging (rays, `after` records, hit records, counts), grown on demand and kept, its two timing events
     DevBuf<unsigned long long> hitsCounters; DevBuf<float4> hitsRays, hitsAfter, hitsOut; DevBuf<uint32_t> hitsCounts; Event hitsEv[2];
+    // nearest-point queries (fyprt_nearest_points*, rt_points.h), allocated on the first one and kept, as the multi-hit queries': their own
+    // counters and queue head, the host entry's staging (points, `after` records, hit records, counts), its two timing events
+    DevBuf<unsigned long long> pointsCounters; DevBuf<float4> pointsIn, pointsAfter, pointsOut; DevBuf<uint32_t> pointsCounts; Event pointsEv[2];
     // radiance queries (fyprt_render_rays*, rt_query.h: k_render_rays_primary + the path stages), allocated on first use for
     // min(count, FYPRT_RENDER_RAYS_CHUNK) rays and kept: primary records, path state, ray / result lists, live lists, list counters + queue
     // heads; the host entry's staging (rays, pixel indices, radiance) and its two timing events
@@ -2324,6 +2328,88 @@ int fyprt_trace_ray_hits_device(fyprt_context* c, const void* rays, const void* 
     HIPCHK(c, hipSetDevice(c->device));
     return enqueue_ray_hits(c, static_cast<const float4*>(rays), static_cast<const float4*>(after), count, max_hits, static_cast<float4*>(hits),
                             static_cast<uint32_t*>(hit_counts), false);
+}
+
+// ---- nearest-point queries (rt_points.h: k_query_points / k_query_points_simple).  fyprt_trace_ray_hits clause for clause: the scene is
+// read, the query's own results and counters are written, no frame state moves.
+static int check_nearest_points(fyprt_context* c, const void* points, const void* after, uint32_t count, uint32_t maxHits, const void* hits, const void* hitCounts, bool device) {
+    const char* who = device ? "fyprt_nearest_points_device" : "fyprt_nearest_points";
+    if (!c) return FYPRT_EINVAL;
+    if (maxHits == 0 || maxHits > FYPRT_QUERY_MAX_HITS) return c->fail(FYPRT_EINVAL, std::string(who) + ": max_hits must be 1.." + std::to_string(FYPRT_QUERY_MAX_HITS));
+    if (count && (!points || !hits)) return c->fail(FYPRT_EINVAL, std::string(who) + ": NULL points / hits with a non-zero count");
+    if (device && (((uintptr_t)points & 15u) || ((uintptr_t)after & 15u) || ((uintptr_t)hits & 15u) || ((uintptr_t)hitCounts & 3u)))   // 16-byte loads and stores, 4-byte counts
+        return c->fail(FYPRT_EINVAL, std::string(who) + ": points, after and hits must be 16-byte and hit_counts 4-byte aligned");
+    if (c->hostOnly) return c->fail(FYPRT_ESTATE, std::string(who) + ": host-only context (device -1) cannot query");
+    if (!c->haveScene) return c->fail(FYPRT_ESTATE, std::string(who) + " before fyprt_upload_scene");
+    return FYPRT_OK;
+}
+// Enqueues one nearest-point launch on the context stream (device memory, count > 0, after / counts may be NULL); `timed` brackets it
+// with the query's events.  LDS and occupancy as enqueue_ray_hits: the stack plus 16 bytes per thread and list entry.
+static int enqueue_nearest_points(fyprt_context* c, const float4* points, const float4* after, uint32_t count, uint32_t maxHits, float4* hits, uint32_t* counts, bool timed) {
+    if (!c->pointsCounters.p) { HIPCHK(c, c->pointsCounters.alloc(8)); }
+    HIPCHK(c, hipMemsetAsync(c->pointsCounters.p, 0, 64, c->stream));
+    const StackLds stack = stack_lds(c, 0u);
+    DevScene qs = secondary_scene(c->dsc, (uint32_t)c->tuning[K_QUORUM_SECONDARY], c->countRays ? c->pointsCounters.p : nullptr);
+    qs.stackBudget = stack.budget;
+    const size_t ldsBytes = stack.bytes + (size_t)maxHits * 16u * kBlock;        // <= 32 KB + 32 KB
+    QueryPoints q{};
+    q.rays = points; q.after = after; q.hits = hits; q.counts = counts; q.count = count; q.maxHits = maxHits;
+    q.head = reinterpret_cast<uint32_t*>(c->pointsCounters.p + 5);
+    set_queue_params(c, q, K_REFILL_LANES);
+    const dim3 block(kBlock);
+    const uint32_t blocksForPoints = (uint32_t)(((size_t)count + kBlock - 1) / kBlock);
+    const bool simple = simple_ray_kernel(c);                     // tuning key 15 as for the other queries
+    dim3 grid;
+    if (simple) grid = dim3(std::max(1u, std::min<uint32_t>((uint32_t)c->numCUs * 16u, blocksForPoints)));
+    else {
+        const int occ = c->pointsOcc.get(k_query_points<false>, ldsBytes, 2), perCU = c->tuning[K_WG_PER_CU] > 0 ? std::min(c->tuning[K_WG_PER_CU], occ) : occ;
+        grid = dim3(std::max(1u, std::min<uint32_t>((uint32_t)(c->numCUs * perCU), blocksForPoints)));
+    }
+    if (timed) HIPCHK(c, hipEventRecord(c->pointsEv[0], c->stream));
+    static void (*const kPoints[2][2])(DevScene, QueryPoints) = {{k_query_points<false>, k_query_points<true>}, {k_query_points_simple<false>, k_query_points_simple<true>}};
+    hipLaunchKernelGGL(kPoints[simple ? 1 : 0][c->countRays ? 1 : 0], grid, block, ldsBytes, c->stream, qs, q);
+    HIPCHK(c, hipGetLastError());
+    if (timed) HIPCHK(c, hipEventRecord(c->pointsEv[1], c->stream));
+    return FYPRT_OK;
+}
+
+int fyprt_nearest_points(fyprt_context* c, const fyprt_point* points, const fyprt_point_hit* after, uint32_t count, uint32_t max_hits, fyprt_point_hit* hits,
+                         uint32_t* hit_counts, fyprt_frame_stats* stats) {
+    TRY(check_nearest_points(c, points, after, count, max_hits, hits, hit_counts, false));
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (count == 0) return FYPRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t pointBytes = (size_t)count * sizeof(fyprt_point), afterBytes = (size_t)count * sizeof(fyprt_point_hit), hitBytes = afterBytes * max_hits;
+    for (Event& e : c->pointsEv) HIPCHK(c, create(e));
+    if (c->pointsIn.n < (size_t)count) { HIPCHK(c, c->pointsIn.alloc(count)); }                          // staging grows, is kept
+    if (after && c->pointsAfter.n < (size_t)count) { HIPCHK(c, c->pointsAfter.alloc(count)); }
+    if (c->pointsOut.n < (size_t)count * max_hits) { HIPCHK(c, c->pointsOut.alloc((size_t)count * max_hits)); }
+    if (c->pointsCounts.n < (size_t)count) { HIPCHK(c, c->pointsCounts.alloc(count)); }
+    HIPCHK(c, hipMemcpyAsync(c->pointsIn.p, points, pointBytes, hipMemcpyHostToDevice, c->stream));
+    if (after) HIPCHK(c, hipMemcpyAsync(c->pointsAfter.p, after, afterBytes, hipMemcpyHostToDevice, c->stream));
+    TRY(enqueue_nearest_points(c, c->pointsIn.p, after ? c->pointsAfter.p : nullptr, count, max_hits, c->pointsOut.p, c->pointsCounts.p, true));
+    HIPCHK(c, hipMemcpyAsync(hits, c->pointsOut.p, hitBytes, hipMemcpyDeviceToHost, c->stream));
+    if (hit_counts) HIPCHK(c, hipMemcpyAsync(hit_counts, c->pointsCounts.p, (size_t)count * 4u, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (stats) {
+        float ms = 0.0f;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->pointsEv[0], c->pointsEv[1]));
+        stats->kernel_ms = ms; stats->kernel_ms_part[0] = ms; stats->launches = 1;
+        if (c->countRays) {
+            unsigned long long r[5] = {0, 0, 0, 0, 0};
+            HIPCHK(c, hipMemcpy(r, c->pointsCounters.p, sizeof r, hipMemcpyDeviceToHost));
+            add_ray_stats(stats, 0, r);
+        }
+    }
+    return FYPRT_OK;
+}
+
+int fyprt_nearest_points_device(fyprt_context* c, const void* points, const void* after, uint32_t count, uint32_t max_hits, void* hits, void* hit_counts) {
+    TRY(check_nearest_points(c, points, after, count, max_hits, hits, hit_counts, true));
+    if (count == 0) return FYPRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    return enqueue_nearest_points(c, static_cast<const float4*>(points), static_cast<const float4*>(after), count, max_hits, static_cast<float4*>(hits),
+                                  static_cast<uint32_t*>(hit_counts), false);
 }
 
 // ---- radiance queries (rt_query.h: k_render_rays_primary; rt_paths.h: the path stages with CAM = RaySource).  A frame's sample of

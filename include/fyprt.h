@@ -697,6 +697,58 @@ int fyprt_trace_ray_hits(fyprt_context* ctx, const fyprt_ray* rays, const fyprt_
 int fyprt_trace_ray_hits_device(fyprt_context* ctx, const void* rays, const void* after, uint32_t count, uint32_t max_hits, void* hits,
                                 void* hit_counts);
 
+/* Nearest-point query: the max_hits closest triangles to each point, in order ("Nearest-point queries") — snapping a mesh
+ * onto the surface next to it, clearance checks, the triangles within a brush radius, the unsigned distance to the scene.
+ * Every operation below is rounded on its own in IEEE binary32 (no contraction), dot(a,b) = (a.x*b.x + a.y*b.y) + a.z*b.z.
+ *   Distance    : for the point p and a leaf record (v0, e1, e2) as fyprt_export_bvh returns it (v1, v2 are never formed), Ericson's
+ *                 closest point on a triangle in this order:
+ *                   ap = p - v0;  d1 = dot(e1, ap);  d2 = dot(e2, ap)
+ *                   if d1 <= 0 and d2 <= 0:                       (u, v) = (0, 0)
+ *                   bp = ap - e1;  d3 = dot(e1, bp);  d4 = dot(e2, bp)
+ *                   elif d3 >= 0 and d4 <= d3:                    (u, v) = (1, 0)
+ *                   vc = d1*d4 - d3*d2
+ *                   elif vc <= 0 and d1 >= 0 and d3 <= 0:         (u, v) = (d1 / (d1 - d3), 0)
+ *                   cp = ap - e2;  d5 = dot(e1, cp);  d6 = dot(e2, cp)
+ *                   elif d6 >= 0 and d5 <= d6:                    (u, v) = (0, 1)
+ *                   vb = d5*d2 - d1*d6
+ *                   elif vb <= 0 and d2 >= 0 and d6 <= 0:         (u, v) = (0, d2 / (d2 - d6))
+ *                   va = d3*d6 - d5*d4;  a = d4 - d3;  b = d5 - d6
+ *                   elif va <= 0 and a >= 0 and b >= 0:           w = a / (a + b); (u, v) = (1 - w, w)
+ *                   else:                                         s = (va + vb) + vc; f = 1 / s; (u, v) = (vb * f, vc * f)
+ *                   u = u < 0 ? 0 : (u > 1 ? 1 : u);  m = 1 - u;  v = v < 0 ? 0 : (v > m ? m : v)      (selects: a NaN stays a NaN)
+ *                   diff = (ap - u*e1) - v*e2 per component;  distance2 = dot(diff, diff)
+ *                 The final clamp is part of the contract: it keeps the answered point inside the record's triangle up to rounding,
+ *                 whatever the region tests did on a sliver, and the traversal's conservative cull rests on that.
+ *   Acceptance  : distance2 <= r2, r2 = min(max_distance * max_distance, FLT_MAX); a NaN or infinite distance2 (a degenerate record) is
+ *                 therefore rejected.  With `after`, the key must also be greater than the key of after[i].
+ *   Order       : every accepted triangle has the 64-bit key (bits(distance2) << 32) | triangle; distance2 >= +0, so the bit pattern
+ *                 orders as the value.  The answer for a point is its max_hits smallest keys in ascending order: exact ties go to the
+ *                 lower triangle index.  The answer does not depend on the tree, the builder or the visiting order.
+ *   Record      : distance2, u, v as computed above — the closest point is (1-u-v) A + u B + v C of the caller's own vertices;
+ *                 triangle: the scene triangle index.  Unused records are {-1.0f, 0xFFFFFFFF, 0, 0}; hit_counts[i] = the number of used
+ *                 records of point i (hit_counts may be NULL).
+ *   Continuation: as the multi-hit query's — an after[i] with distance2 < 0 (the unused record) finishes the point: zero hits, no
+ *                 traversal.  Passing each pass's LAST record per point back in until every count is 0 enumerates every triangle within
+ *                 max_distance exactly once, ties included: the radius query.
+ *   Invalid points: a non-finite position component, a NaN max_distance or max_distance < 0 — zero hits without traversal, counted as a
+ *                 query with no tests.
+ * Errors, in this order: FYPRT_EINVAL for a NULL context, max_hits 0 or above FYPRT_QUERY_MAX_HITS, NULL points / hits with count > 0, and
+ * (device entry) points, after or hits not 16-byte or hit_counts not 4-byte aligned; FYPRT_ESTATE on a host-only context or before
+ * fyprt_upload_scene; count 0 returns FYPRT_OK and launches nothing.
+ * No frame state moves: the query has its own counters, queue head and events, and the host entry's staging buffers grow on demand and
+ * are kept.  The kernel follows tuning key 15 (and keys 4, 5, 6, 9, 10) as the other queries'; the per-lane list is the multi-hit
+ * query's.  With ray counting on, stats reports rays = points, box_tests = the valid child boxes tested, tri_tests, hits = points with at
+ * least one record, node_visits. */
+typedef struct fyprt_point     { float position[3]; float max_distance; } fyprt_point;      /* 16 B, 16-B aligned on the device */
+typedef struct fyprt_point_hit { float distance2; uint32_t triangle; float u, v; } fyprt_point_hit;   /* 16 B */
+/* Host memory, blocking.  `hits`: count x max_hits records, point-major.  `stats` may be NULL; it is filled as fyprt_trace_ray_hits fills it. */
+int fyprt_nearest_points(fyprt_context* ctx, const fyprt_point* points, const fyprt_point_hit* after /* NULL or count */, uint32_t count,
+                         uint32_t max_hits, fyprt_point_hit* hits /* count x max_hits */, uint32_t* hit_counts /* NULL or count */,
+                         fyprt_frame_stats* stats /* may be NULL */);
+/* Device memory of the context's GPU, asynchronous on the context stream (fyprt_stream). */
+int fyprt_nearest_points_device(fyprt_context* ctx, const void* points, const void* after, uint32_t count, uint32_t max_hits, void* hits,
+                                void* hit_counts);
+
 /* ================================================================================================= radiance queries
  * New (no reference counterpart): the renderer's sample of techniques 0-6 for the caller's own rays — other camera models, light probes,
  * surface bakes, re-rendering a few pixels ("Radiance queries").  Only an uploaded scene is needed (no resize, no camera).

@@ -11,7 +11,13 @@ With --hits K [K ...]: the multi-hit query (fyprt_trace_ray_hits) instead, on se
 their tmax): per set one line for FYPRT_QUERY_CLOSEST and one per K, timed in the same run on the same rays — median, minimum and
 maximum hipEvent ms over --calls calls after warm-up, Mrays/s, records (hits) per second, and the ratio to the closest-hit query.
 Written to profiles/query/hits_rate.jsonl unless --out names another file.
-  usage: python tools/query_rate.py --hits 1 2 4 8 [--calls 20] [--out FILE.jsonl]"""
+  usage: python tools/query_rate.py --hits 1 2 4 8 [--calls 20] [--out FILE.jsonl]
+With --points K [K ...]: the nearest-point query (fyprt_nearest_points) on three sets of 1920x1080 points — (a) the camera hits pushed
+1 % of the scene diameter along the normal, (b) uniform in the scene box, (c) uniform in a box three diameters wide: per set and K the
+median, minimum and maximum hipEvent ms, Mpoints/s, node visits, box and triangle tests per point (one counted call), and the ratio
+to the closest-hit query of the camera rays, timed in the same run.  Written to profiles/query/points_rate.jsonl unless --out names
+another file.
+  usage: python tools/query_rate.py --points 1 4 8 [--calls 20] [--out FILE.jsonl]"""
 import argparse
 import json
 import statistics
@@ -157,19 +163,79 @@ def main_hits(a):
     out.write_text("\n".join(lines) + "\n")
 
 
+def points_rate(ctx, name, p, ks, calls, med0):
+    """One point set: the nearest-point query per K, warmed up and timed over `calls` calls, then one counted call."""
+    rows = []
+    for k in ks:
+        for _ in range(3):
+            ctx.nearest_points(p, max_hits=k)
+        ms = [ctx.nearest_points(p, max_hits=k, with_stats=True)[2].kernel_ms for _ in range(calls)]
+        ctx.set_ray_counting(True)
+        st = ctx.nearest_points(p, max_hits=k, with_stats=True)[2]
+        ctx.set_ray_counting(False)
+        med = statistics.median(ms)
+        rows.append({"set": name, "scene": "hall_1M", "query": "points", "max_hits": k, "points": len(p), "ms_median": round(med, 4),
+                     "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4), "calls": calls, "mpoints_per_s": round(len(p) / med / 1e3, 1),
+                     "node_visits_per_point": round(st.node_visits / st.rays, 3), "box_tests_per_point": round(st.box_tests / st.rays, 3),
+                     "tri_tests_per_point": round(st.tri_tests / st.rays, 3), "ms_over_closest": round(med / med0, 3)})
+    return rows
+
+
+def main_points(a):
+    """Three sets of W x H points on the 1M hall: (a) the camera hits pushed 1 % of the scene diameter along the normal, (b) uniform in
+    the scene box, (c) uniform in a box three diameters wide; the closest-hit query of the camera rays is timed in the same run."""
+    W, H = 1920, 1080
+    n = W * H
+    rng = np.random.default_rng(2024)
+    hall, cam = scenes.hall_scene(), scenes.hall_camera(W, H)
+    ctx = capi.Context(0)
+    ctx.upload_scene(hall)
+    o, d = camera_rays(cam)
+    for _ in range(3):
+        ctx.trace_rays(o, d)
+    ms0 = [ctx.trace_rays(o, d, with_stats=True)[1].kernel_ms for _ in range(a.calls)]
+    med0 = statistics.median(ms0)
+    rows = [{"set": "a_camera", "scene": "hall_1M", "query": "closest", "rays": n, "ms_median": round(med0, 4), "ms_min": round(min(ms0), 4),
+             "ms_max": round(max(ms0), 4), "calls": a.calls, "mrays_per_s": round(n / med0 / 1e3, 1)}]
+    res = ctx.trace_rays(o, d)
+    pos = hall.world_vertices["position"].astype(np.float64)
+    lo, hi = pos.min(axis=0), pos.max(axis=0)
+    diam = float(np.linalg.norm(hi - lo))
+    hit = res["objectIndex"] >= 0
+    nrm = res["worldNormal"].astype(F32)
+    nrm = np.where((np.einsum("ij,ij->i", nrm, d) > 0)[:, None], -nrm, nrm)
+    near = np.where(hit[:, None], res["worldPosition"] + F32(0.01 * diam) * nrm, o + F32(0.5 * diam) * d).astype(F32)   # (a miss: a point half a diameter out)
+    box = rng.uniform(lo, hi, size=(n, 3)).astype(F32)
+    mid = (lo + hi) / 2
+    wide = rng.uniform(mid - 1.5 * diam, mid + 1.5 * diam, size=(n, 3)).astype(F32)
+    for name, p in (("a_near_surface", near), ("b_scene_box", box), ("c_wide_box", wide)):
+        rows += points_rate(ctx, name, p, a.points, a.calls, med0)
+    ctx.close()
+    lines = [json.dumps(r) for r in rows]
+    print("\n".join(lines))
+    out = Path(a.out) if a.out else ROOT / "profiles" / "query" / "points_rate.jsonl"
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--out", default=None)
     ap.add_argument("--hits", type=int, nargs="+", default=None, metavar="K", help="time the multi-hit query at these max_hits instead")
+    ap.add_argument("--points", type=int, nargs="+", default=None, metavar="K", help="time the nearest-point query at these max_hits instead")
     a = ap.parse_args()
     if a.hits and not all(1 <= k <= capi.QUERY_MAX_HITS for k in a.hits):
         raise SystemExit(f"--hits takes values in 1..{capi.QUERY_MAX_HITS}")
+    if a.points and not all(1 <= k <= capi.QUERY_MAX_HITS for k in a.points):
+        raise SystemExit(f"--points takes values in 1..{capi.QUERY_MAX_HITS}")
     if not torch.cuda.is_available():
         raise SystemExit("query_rate.py needs an MI355X")
     torch.cuda.set_device(0)
     if a.hits:
         return main_hits(a)
+    if a.points:
+        return main_points(a)
     W, H = 1920, 1080
     rows = []
     rng = np.random.default_rng(2024)
