@@ -5,6 +5,7 @@ this module raises, loudly.  Nothing here imports or touches oracle/.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from pathlib import Path
@@ -741,19 +742,98 @@ class Context:
         self._check(self.lib.fyprt_export_bvh(self.h, _ptr(nodes), C.byref(nn), _ptr(tris), C.byref(nt), C.byref(root), C.byref(depth)))
         return {"nodes": nodes, "tris": tris, "root": root.value, "max_stack": depth.value, "stack_budget": self.get_tuning(8), "skip_dead_rays": self.get_tuning(18)}
 
-    def trace_rays(self, origins, directions, tmin=0.0, tmax=np.inf, occluded=False, with_stats=False):
-        """Batched ray query against the uploaded scene (fyprt_trace_rays, blocking).  `origins` / `directions`: (N, 3); `tmin` /
-        `tmax`: scalars or (N,) arrays.  Returns the PAYLOAD_DTYPE records of the closest hits, or (occluded=True) a bool array that
-        is True where any triangle lies in (tmin, tmax); with `with_stats` also the FrameStats of the launch."""
+    # ---- what the query entry points share: record packing, argument checks, the torch stream hand-over, the continuation loop
+    @staticmethod
+    def _ray_records(who, origins, directions, tmin, tmax):
         o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
         d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
         if o.shape != d.shape:
-            raise ValueError(f"trace_rays: {len(o)} origins but {len(d)} directions")
+            raise ValueError(f"{who}: {len(o)} origins but {len(d)} directions")
         n = len(o)
         rays = np.empty(n, dtype=RAY_DTYPE)
         rays["origin"], rays["direction"] = o, d
         rays["tmin"] = np.broadcast_to(np.asarray(tmin, dtype=np.float32), (n,))
         rays["tmax"] = np.broadcast_to(np.asarray(tmax, dtype=np.float32), (n,))
+        return rays
+
+    @staticmethod
+    def _point_records(who, points, max_distance):
+        p = np.asarray(points, dtype=np.float32)
+        if p.ndim == 0 or p.size % 3 or (p.ndim > 1 and p.shape[-1] != 3):
+            raise ValueError(f"{who}: points must be (N, 3), got shape {p.shape}")
+        p = p.reshape(-1, 3)
+        n = len(p)
+        md = np.asarray(max_distance, dtype=np.float32)
+        if md.ndim > 1 or (md.ndim == 1 and len(md) != n):
+            raise ValueError(f"{who}: max_distance must be a scalar or {n} values")
+        rec = np.empty(n, dtype=POINT_DTYPE)
+        rec["position"], rec["max_distance"] = p, np.broadcast_to(md, (n,))
+        return rec
+
+    @staticmethod
+    def _check_max_hits(who, max_hits):
+        if not isinstance(max_hits, (int, np.integer)) or isinstance(max_hits, bool) or not 1 <= int(max_hits) <= QUERY_MAX_HITS:
+            raise ValueError(f"{who}: max_hits must be an integer in 1..{QUERY_MAX_HITS}, got {max_hits!r}")
+        return int(max_hits)
+
+    @staticmethod
+    def _after_records(who, after, n, dtype, dtype_name):
+        if after is None:
+            return None
+        aft = np.asarray(after)
+        if aft.dtype != dtype or aft.size != n:
+            raise ValueError(f"{who}: after must be {n} {dtype_name} records")
+        return np.ascontiguousarray(aft.reshape(-1))
+
+    def _check_record_tensor(self, who, name, t, width, after=None):
+        """`t`: the contiguous float32 (N, width) tensor of `name` on this context's GPU; `after`: None or (N, 4) beside it.  Returns N."""
+        import torch
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != width or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous float32 (N, {width}) tensor")
+        if t.device.type != "cuda" or (t.device.index if t.device.index is not None else torch.cuda.current_device()) != self.device:
+            raise ValueError(f"{who}: {name} must be on cuda:{self.device}, the context's GPU")
+        n = t.shape[0]
+        if after is not None and (after.dtype != torch.float32 or tuple(after.shape) != (n, 4) or not after.is_contiguous() or after.device != t.device):
+            raise ValueError(f"{who}: after must be a contiguous float32 (N, 4) tensor on the {name}' device")
+        return n
+
+    @contextlib.contextmanager
+    def _on_context_stream(self, device):
+        """The ordering of every *_tensor call (trace_rays_tensor's docstring): the context stream waits for torch's current stream, the
+        body enqueues on the context stream, torch's current stream waits for the context stream."""
+        import torch
+        cur = torch.cuda.current_stream(device)
+        ext = torch.cuda.ExternalStream(self.stream(), device=device)
+        ext.wait_stream(cur)                                           # inputs are written, outputs allocated before the query runs
+        yield
+        cur.wait_stream(ext)                                           # torch's later work (reads of the outputs, reuse of any block) follows it
+
+    @staticmethod
+    def _all_records(n, k, dtype, ask):
+        """Continuation passes of a list query until every record is finished: ask(live, after) -> (hits, counts) for the records `live`
+        (indices), each pass's last record per live entry passed back in as `after`.  Returns (flat records, offsets int64 (n + 1,))."""
+        live = np.arange(n)                                            # records not finished yet; only they are asked again
+        after = None
+        parts = [[] for _ in range(n)]
+        while len(live):
+            hits, counts = ask(live, after)
+            for j, i in enumerate(live):
+                if counts[j]:
+                    parts[i].append(hits[j, :counts[j]])
+            go = counts == k                                           # a short list has nothing further
+            live, after = live[go], np.ascontiguousarray(hits[go, k - 1])
+        total = np.array([sum(len(p) for p in ps) for ps in parts], dtype=np.int64)
+        offsets = np.concatenate([[0], np.cumsum(total)]).astype(np.int64)
+        flat = [p for ps in parts for p in ps]
+        records = np.concatenate(flat) if flat else np.empty(0, dtype=dtype)
+        return records, offsets
+
+    def trace_rays(self, origins, directions, tmin=0.0, tmax=np.inf, occluded=False, with_stats=False):
+        """Batched ray query against the uploaded scene (fyprt_trace_rays, blocking).  `origins` / `directions`: (N, 3); `tmin` /
+        `tmax`: scalars or (N,) arrays.  Returns the PAYLOAD_DTYPE records of the closest hits, or (occluded=True) a bool array that
+        is True where any triangle lies in (tmin, tmax); with `with_stats` also the FrameStats of the launch."""
+        rays = self._ray_records("trace_rays", origins, directions, tmin, tmax)
+        n = len(rays)
         out = np.empty(n, dtype=np.uint32 if occluded else PAYLOAD_DTYPE)
         st = FrameStats()
         self._check(self.lib.fyprt_trace_rays(self.h, QUERY_OCCLUDED if occluded else QUERY_CLOSEST, _ptr(rays), n, _ptr(out), C.byref(st)))
@@ -774,25 +854,30 @@ class Context:
         event on the context stream when a tensor is freed, and a tensor that outlives the context would then record on a destroyed
         stream."""
         import torch
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
-            raise ValueError("trace_rays_tensor: rays must be a contiguous float32 (N, 8) tensor")
-        if rays.device.type != "cuda" or (rays.device.index if rays.device.index is not None else torch.cuda.current_device()) != self.device:
-            raise ValueError(f"trace_rays_tensor: rays must be on cuda:{self.device}, the context's GPU")
-        n = rays.shape[0]
+        n = self._check_record_tensor("trace_rays_tensor", "rays", rays, 8)
         out = torch.empty((n,) if occluded else (n, 10), dtype=torch.int32 if occluded else torch.float32, device=rays.device)
-        cur = torch.cuda.current_stream(rays.device)
-        ext = torch.cuda.ExternalStream(self.stream(), device=rays.device)
-        ext.wait_stream(cur)                                           # the rays are written and `out` is allocated before the query runs
-        self._check(self.lib.fyprt_trace_rays_device(self.h, QUERY_OCCLUDED if occluded else QUERY_CLOSEST, C.c_void_p(rays.data_ptr()), n,
-                                                     C.c_void_p(out.data_ptr())))
-        cur.wait_stream(ext)                                           # torch's later work (reads of `out`, reuse of either block) follows it
+        with self._on_context_stream(rays.device):
+            self._check(self.lib.fyprt_trace_rays_device(self.h, QUERY_OCCLUDED if occluded else QUERY_CLOSEST, C.c_void_p(rays.data_ptr()), n,
+                                                         C.c_void_p(out.data_ptr())))
         return out
 
-    @staticmethod
-    def _check_max_hits(who, max_hits):
-        if not isinstance(max_hits, (int, np.integer)) or isinstance(max_hits, bool) or not 1 <= int(max_hits) <= QUERY_MAX_HITS:
-            raise ValueError(f"{who}: max_hits must be an integer in 1..{QUERY_MAX_HITS}, got {max_hits!r}")
-        return int(max_hits)
+    def _list_query(self, fn, rec, aft, k, hit_dtype, with_stats):
+        n = len(rec)
+        hits = np.empty((n, k), dtype=hit_dtype)
+        counts = np.empty(n, dtype=np.uint32)
+        st = FrameStats()
+        self._check(getattr(self.lib, fn)(self.h, _ptr(rec), _ptr(aft), n, k, _ptr(hits), _ptr(counts), C.byref(st)))
+        return (hits, counts, st) if with_stats else (hits, counts)
+
+    def _list_query_tensor(self, fn, who, name, rec, width, k, after):
+        import torch
+        n = self._check_record_tensor(who, name, rec, width, after)
+        hits = torch.empty((n, k, 4), dtype=torch.float32, device=rec.device)
+        counts = torch.empty((n,), dtype=torch.int32, device=rec.device)
+        with self._on_context_stream(rec.device):
+            self._check(getattr(self.lib, fn)(self.h, C.c_void_p(rec.data_ptr()), C.c_void_p(after.data_ptr()) if after is not None else None,
+                                            n, k, C.c_void_p(hits.data_ptr()), C.c_void_p(counts.data_ptr())))
+        return hits, counts
 
     def trace_ray_hits(self, origins, directions, tmin=0.0, tmax=np.inf, max_hits=QUERY_MAX_HITS, after=None, with_stats=False):
         """Ordered multi-hit query (fyprt_trace_ray_hits, blocking): the `max_hits` nearest accepted triangles per ray, ascending by
@@ -801,26 +886,9 @@ class Context:
         Returns (hits (N, K) RAY_HIT_DTYPE, counts (N,) uint32); unused records are (-1, 0xFFFFFFFF, 0, 0); with `with_stats` also
         the FrameStats of the launch."""
         k = self._check_max_hits("trace_ray_hits", max_hits)
-        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
-        d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
-        if o.shape != d.shape:
-            raise ValueError(f"trace_ray_hits: {len(o)} origins but {len(d)} directions")
-        n = len(o)
-        aft = None
-        if after is not None:
-            aft = np.asarray(after)
-            if aft.dtype != RAY_HIT_DTYPE or aft.size != n:
-                raise ValueError(f"trace_ray_hits: after must be {n} RAY_HIT_DTYPE records")
-            aft = np.ascontiguousarray(aft.reshape(-1))
-        rays = np.empty(n, dtype=RAY_DTYPE)
-        rays["origin"], rays["direction"] = o, d
-        rays["tmin"] = np.broadcast_to(np.asarray(tmin, dtype=np.float32), (n,))
-        rays["tmax"] = np.broadcast_to(np.asarray(tmax, dtype=np.float32), (n,))
-        hits = np.empty((n, k), dtype=RAY_HIT_DTYPE)
-        counts = np.empty(n, dtype=np.uint32)
-        st = FrameStats()
-        self._check(self.lib.fyprt_trace_ray_hits(self.h, _ptr(rays), _ptr(aft), n, k, _ptr(hits), _ptr(counts), C.byref(st)))
-        return (hits, counts, st) if with_stats else (hits, counts)
+        rays = self._ray_records("trace_ray_hits", origins, directions, tmin, tmax)
+        aft = self._after_records("trace_ray_hits", after, len(rays), RAY_HIT_DTYPE, "RAY_HIT_DTYPE")
+        return self._list_query("fyprt_trace_ray_hits", rays, aft, k, RAY_HIT_DTYPE, with_stats)
 
     def trace_ray_hits_tensor(self, rays, max_hits, after=None):
         """Multi-hit query on device tensors (fyprt_trace_ray_hits_device).  `rays`: contiguous float32 (N, 8) tensor on this context's
@@ -828,66 +896,17 @@ class Context:
         earlier call: `hits[:, -1].contiguous()`).  Returns a float32 (N, K, 4) tensor of records (t, triangle bits, u, v: the index is
         `hits[..., 1].contiguous().view(torch.int32)`) and an int32 (N,) tensor of counts.  Ordered against torch's current stream
         exactly as trace_rays_tensor is, without a host synchronisation and without record_stream."""
-        import torch
         k = self._check_max_hits("trace_ray_hits_tensor", max_hits)
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
-            raise ValueError("trace_ray_hits_tensor: rays must be a contiguous float32 (N, 8) tensor")
-        if rays.device.type != "cuda" or (rays.device.index if rays.device.index is not None else torch.cuda.current_device()) != self.device:
-            raise ValueError(f"trace_ray_hits_tensor: rays must be on cuda:{self.device}, the context's GPU")
-        n = rays.shape[0]
-        if after is not None and (after.dtype != torch.float32 or tuple(after.shape) != (n, 4) or not after.is_contiguous() or after.device != rays.device):
-            raise ValueError("trace_ray_hits_tensor: after must be a contiguous float32 (N, 4) tensor on the rays' device")
-        hits = torch.empty((n, k, 4), dtype=torch.float32, device=rays.device)
-        counts = torch.empty((n,), dtype=torch.int32, device=rays.device)
-        cur = torch.cuda.current_stream(rays.device)
-        ext = torch.cuda.ExternalStream(self.stream(), device=rays.device)
-        ext.wait_stream(cur)                                           # rays / after are written, the outputs allocated before the query runs
-        self._check(self.lib.fyprt_trace_ray_hits_device(self.h, C.c_void_p(rays.data_ptr()), C.c_void_p(after.data_ptr()) if after is not None else None,
-                                                         n, k, C.c_void_p(hits.data_ptr()), C.c_void_p(counts.data_ptr())))
-        cur.wait_stream(ext)                                           # torch's later work follows it
-        return hits, counts
+        return self._list_query_tensor("fyprt_trace_ray_hits_device", "trace_ray_hits_tensor", "rays", rays, 8, k, after)
 
     def trace_all_hits(self, origins, directions, tmin=0.0, tmax=np.inf, max_hits=QUERY_MAX_HITS):
         """Every accepted hit of every ray, in order: continuation passes of trace_ray_hits (each pass's last record per ray passed
         back in as `after`) until every ray is finished.  Returns (records, offsets): flat RAY_HIT_DTYPE records, ray i's in
         records[offsets[i]:offsets[i + 1]], offsets int64 (N + 1,)."""
         k = self._check_max_hits("trace_all_hits", max_hits)
-        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
-        d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
-        if o.shape != d.shape:
-            raise ValueError(f"trace_all_hits: {len(o)} origins but {len(d)} directions")
-        n = len(o)
-        lo = np.broadcast_to(np.asarray(tmin, dtype=np.float32), (n,))
-        hi = np.broadcast_to(np.asarray(tmax, dtype=np.float32), (n,))
-        live = np.arange(n)                                            # rays not finished yet; only they are traced again
-        after = None
-        parts = [[] for _ in range(n)]
-        while len(live):
-            hits, counts = self.trace_ray_hits(o[live], d[live], lo[live], hi[live], k, after)
-            for j, i in enumerate(live):
-                if counts[j]:
-                    parts[i].append(hits[j, :counts[j]])
-            go = counts == k                                           # a ray with a short list has no further hit
-            live, after = live[go], np.ascontiguousarray(hits[go, k - 1])
-        total = np.array([sum(len(p) for p in ps) for ps in parts], dtype=np.int64)
-        offsets = np.concatenate([[0], np.cumsum(total)]).astype(np.int64)
-        flat = [p for ps in parts for p in ps]
-        records = np.concatenate(flat) if flat else np.empty(0, dtype=RAY_HIT_DTYPE)
-        return records, offsets
-
-    @staticmethod
-    def _point_records(who, points, max_distance):
-        p = np.asarray(points, dtype=np.float32)
-        if p.ndim == 0 or p.size % 3 or (p.ndim > 1 and p.shape[-1] != 3):
-            raise ValueError(f"{who}: points must be (N, 3), got shape {p.shape}")
-        p = p.reshape(-1, 3)
-        n = len(p)
-        md = np.asarray(max_distance, dtype=np.float32)
-        if md.ndim > 1 or (md.ndim == 1 and len(md) != n):
-            raise ValueError(f"{who}: max_distance must be a scalar or {n} values")
-        rec = np.empty(n, dtype=POINT_DTYPE)
-        rec["position"], rec["max_distance"] = p, np.broadcast_to(md, (n,))
-        return rec
+        rays = self._ray_records("trace_all_hits", origins, directions, tmin, tmax)
+        return self._all_records(len(rays), k, RAY_HIT_DTYPE, lambda live, after: self.trace_ray_hits(
+            rays["origin"][live], rays["direction"][live], rays["tmin"][live], rays["tmax"][live], k, after))
 
     def nearest_points(self, points, max_distance=np.inf, max_hits=1, after=None, with_stats=False):
         """Nearest-point query (fyprt_nearest_points, blocking): the `max_hits` closest triangles to each point, ascending by
@@ -897,42 +916,16 @@ class Context:
         records are (-1, 0xFFFFFFFF, 0, 0); with `with_stats` also the FrameStats of the launch."""
         k = self._check_max_hits("nearest_points", max_hits)
         rec = self._point_records("nearest_points", points, max_distance)
-        n = len(rec)
-        aft = None
-        if after is not None:
-            aft = np.asarray(after)
-            if aft.dtype != POINT_HIT_DTYPE or aft.size != n:
-                raise ValueError(f"nearest_points: after must be {n} POINT_HIT_DTYPE records")
-            aft = np.ascontiguousarray(aft.reshape(-1))
-        hits = np.empty((n, k), dtype=POINT_HIT_DTYPE)
-        counts = np.empty(n, dtype=np.uint32)
-        st = FrameStats()
-        self._check(self.lib.fyprt_nearest_points(self.h, _ptr(rec), _ptr(aft), n, k, _ptr(hits), _ptr(counts), C.byref(st)))
-        return (hits, counts, st) if with_stats else (hits, counts)
+        aft = self._after_records("nearest_points", after, len(rec), POINT_HIT_DTYPE, "POINT_HIT_DTYPE")
+        return self._list_query("fyprt_nearest_points", rec, aft, k, POINT_HIT_DTYPE, with_stats)
 
     def nearest_points_tensor(self, points, max_hits, after=None):
         """Nearest-point query on device tensors (fyprt_nearest_points_device).  `points`: contiguous float32 (N, 4) tensor on this
         context's GPU, one fyprt_point per row (position, max_distance); `after`: None or a contiguous float32 (N, 4) tensor of hit
         records.  Returns a float32 (N, K, 4) tensor of records (distance2, triangle bits, u, v) and an int32 (N,) tensor of counts.
-        Ordered against torch's current stream exactly as trace_ray_hits_tensor is."""
-        import torch
+        Ordered against torch's current stream exactly as trace_rays_tensor is."""
         k = self._check_max_hits("nearest_points_tensor", max_hits)
-        if not isinstance(points, torch.Tensor) or points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous():
-            raise ValueError("nearest_points_tensor: points must be a contiguous float32 (N, 4) tensor")
-        if points.device.type != "cuda" or (points.device.index if points.device.index is not None else torch.cuda.current_device()) != self.device:
-            raise ValueError(f"nearest_points_tensor: points must be on cuda:{self.device}, the context's GPU")
-        n = points.shape[0]
-        if after is not None and (after.dtype != torch.float32 or tuple(after.shape) != (n, 4) or not after.is_contiguous() or after.device != points.device):
-            raise ValueError("nearest_points_tensor: after must be a contiguous float32 (N, 4) tensor on the points' device")
-        hits = torch.empty((n, k, 4), dtype=torch.float32, device=points.device)
-        counts = torch.empty((n,), dtype=torch.int32, device=points.device)
-        cur = torch.cuda.current_stream(points.device)
-        ext = torch.cuda.ExternalStream(self.stream(), device=points.device)
-        ext.wait_stream(cur)                                           # points / after are written, the outputs allocated before the query runs
-        self._check(self.lib.fyprt_nearest_points_device(self.h, C.c_void_p(points.data_ptr()), C.c_void_p(after.data_ptr()) if after is not None else None,
-                                                         n, k, C.c_void_p(hits.data_ptr()), C.c_void_p(counts.data_ptr())))
-        cur.wait_stream(ext)                                           # torch's later work follows it
-        return hits, counts
+        return self._list_query_tensor("fyprt_nearest_points_device", "nearest_points_tensor", "points", points, 4, k, after)
 
     def triangles_within(self, points, radius, max_hits=QUERY_MAX_HITS):
         """Every triangle within `radius` (a scalar or (N,) array) of every point, nearest first: continuation passes of nearest_points
@@ -940,22 +933,8 @@ class Context:
         records[offsets[i]:offsets[i + 1]], offsets int64 (N + 1,)."""
         k = self._check_max_hits("triangles_within", max_hits)
         rec = self._point_records("triangles_within", points, radius)
-        n = len(rec)
-        live = np.arange(n)                                            # points not finished yet; only they are asked again
-        after = None
-        parts = [[] for _ in range(n)]
-        while len(live):
-            hits, counts = self.nearest_points(rec["position"][live], rec["max_distance"][live], k, after)
-            for j, i in enumerate(live):
-                if counts[j]:
-                    parts[i].append(hits[j, :counts[j]])
-            go = counts == k                                           # a point with a short list has no further triangle
-            live, after = live[go], np.ascontiguousarray(hits[go, k - 1])
-        total = np.array([sum(len(p) for p in ps) for ps in parts], dtype=np.int64)
-        offsets = np.concatenate([[0], np.cumsum(total)]).astype(np.int64)
-        flat = [p for ps in parts for p in ps]
-        records = np.concatenate(flat) if flat else np.empty(0, dtype=POINT_HIT_DTYPE)
-        return records, offsets
+        return self._all_records(len(rec), k, POINT_HIT_DTYPE, lambda live, after: self.nearest_points(
+            rec["position"][live], rec["max_distance"][live], k, after))
 
     def render_rays(self, origins, directions, settings: Settings, frame_index=1, first_index=0, pixel_indices=None, tmin=0.0, tmax=np.inf,
                     want_payload=False, with_stats=False):
@@ -964,20 +943,13 @@ class Context:
         Ray k uses the random sequence of pixel `pixel_indices[k]` (or `first_index + k`) in frame `frame_index`.  Returns float32
         (N, 4): what a frame's epilogue would add to the accumulation; with `want_payload` also the PAYLOAD_DTYPE primary records, with
         `with_stats` also the FrameStats of the call."""
-        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
-        d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
-        if o.shape != d.shape:
-            raise ValueError(f"render_rays: {len(o)} origins but {len(d)} directions")
-        n = len(o)
+        rays = self._ray_records("render_rays", origins, directions, tmin, tmax)
+        n = len(rays)
         idx = None
         if pixel_indices is not None:
             idx = np.ascontiguousarray(np.asarray(pixel_indices).astype(np.uint32, copy=False).reshape(-1))
             if len(idx) != n:
                 raise ValueError(f"render_rays: {n} rays but {len(idx)} pixel indices")
-        rays = np.empty(n, dtype=RAY_DTYPE)
-        rays["origin"], rays["direction"] = o, d
-        rays["tmin"] = np.broadcast_to(np.asarray(tmin, dtype=np.float32), (n,))
-        rays["tmax"] = np.broadcast_to(np.asarray(tmax, dtype=np.float32), (n,))
         rad = np.empty((n, 4), dtype=np.float32)
         pay = np.empty(n, dtype=PAYLOAD_DTYPE) if want_payload else None
         st = FrameStats()
@@ -992,11 +964,7 @@ class Context:
         radiance, and with `want_payload` also a float32 (N, 10) tensor of primary records (as trace_rays_tensor).  Ordered against
         torch's current stream as trace_rays_tensor is, without a host synchronisation and without record_stream."""
         import torch
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
-            raise ValueError("render_rays_tensor: rays must be a contiguous float32 (N, 8) tensor")
-        if rays.device.type != "cuda" or (rays.device.index if rays.device.index is not None else torch.cuda.current_device()) != self.device:
-            raise ValueError(f"render_rays_tensor: rays must be on cuda:{self.device}, the context's GPU")
-        n = rays.shape[0]
+        n = self._check_record_tensor("render_rays_tensor", "rays", rays, 8)
         if pixel_indices is not None:
             if pixel_indices.dtype != torch.int32 or pixel_indices.dim() != 1 or pixel_indices.shape[0] != n or not pixel_indices.is_contiguous():
                 raise ValueError("render_rays_tensor: pixel_indices must be a contiguous int32 (N,) tensor, one per ray")
@@ -1004,14 +972,11 @@ class Context:
                 raise ValueError("render_rays_tensor: pixel_indices must be on the rays' GPU")
         rad = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
         pay = torch.empty((n, 10), dtype=torch.float32, device=rays.device) if want_payload else None
-        cur = torch.cuda.current_stream(rays.device)
-        ext = torch.cuda.ExternalStream(self.stream(), device=rays.device)
-        ext.wait_stream(cur)                                           # inputs written, outputs allocated before the query runs
-        self._check(self.lib.fyprt_render_rays_device(self.h, C.byref(settings), int(frame_index), C.c_void_p(rays.data_ptr()),
-                                                      C.c_void_p(pixel_indices.data_ptr()) if pixel_indices is not None else None,
-                                                      int(first_index), n, C.c_void_p(rad.data_ptr()),
-                                                      C.c_void_p(pay.data_ptr()) if pay is not None else None))
-        cur.wait_stream(ext)                                           # torch's later work follows the query
+        with self._on_context_stream(rays.device):
+            self._check(self.lib.fyprt_render_rays_device(self.h, C.byref(settings), int(frame_index), C.c_void_p(rays.data_ptr()),
+                                                          C.c_void_p(pixel_indices.data_ptr()) if pixel_indices is not None else None,
+                                                          int(first_index), n, C.c_void_p(rad.data_ptr()),
+                                                          C.c_void_p(pay.data_ptr()) if pay is not None else None))
         return (rad, pay) if want_payload else rad
 
     def denoise(self, params: DenoiseParams | None = None, want_radiance=True, with_stats=False):

@@ -214,22 +214,20 @@ struct fyprt_context {
     int lastLaunches = 0;
     size_t queueStride = 0;                     // float4s per task queue
     size_t sortGroups = 0;                      // setup workgroups the sort scratch is sized for (per parity)
-    OccCache traceOcc, pathOcc, gi2Occ, queryOcc[2], hitsOcc, pointsOcc;   // k_di_part2_trace, k_trace_rays, k_gi2_persistent, k_query_rays<kind, false>, k_query_hits<false>, k_query_points<false>
+    OccCache traceOcc, pathOcc, gi2Occ;        // k_di_part2_trace, k_trace_rays, k_gi2_persistent
     int tuning[K_COUNT];                        // by TuningKey, defaults from kTuning
     int numCUs = 256;
     // wavefront path engine (rt_paths.h): two ray lists + results (ping-pong), per-pixel path state, pixel lists, list counters
     DevBuf<float4> wfRays[2], wfHits[2], wfState; DevBuf<uint32_t> wfPixels, wfPixels2, wfCounters;
     DevBuf<uint32_t> refImage;                 // fyprt_compare_image's reference
     DevBuf<float4> shadowTasks; DevBuf<uint32_t> queueCounters, sortCounts, sortOffset, sortTotal, sortIndex; DevBuf<uint8_t> sortKeys; DevBuf<uint16_t> sortHist;
-    // batched ray queries (fyprt_trace_rays*, rt_query.h), all allocated on the first query: their own counters ([0..4] as a frame's
-    // launch, [5] low word = queue head of the persistent kernel), the host entry's staging buffers, its two timing events
-    DevBuf<unsigned long long> queryCounters; DevBuf<float4> queryRays; DevBuf<uint32_t> queryResults; Event queryEv[2];
-    // multi-hit queries (fyprt_trace_ray_hits*, rt_query.h), allocated on the first one: their own counters (laid out as the batched
-    // queries'), the host entry's staging (rays, `after` records, hit records, counts), grown on demand and kept, its two timing events
-    DevBuf<unsigned long long> hitsCounters; DevBuf<float4> hitsRays, hitsAfter, hitsOut; DevBuf<uint32_t> hitsCounts; Event hitsEv[2];
-    // nearest-point queries (fyprt_nearest_points*, rt_points.h), allocated on the first one and kept, as the multi-hit queries': their own
-    // counters and queue head, the host entry's staging (points, `after` records, hit records, counts), its two timing events
-    DevBuf<unsigned long long> pointsCounters; DevBuf<float4> pointsIn, pointsAfter, pointsOut; DevBuf<uint32_t> pointsCounts; Event pointsEv[2];
+    // One query family's state, allocated by its first query and kept: its own counters ([0..4] as a frame's launch, [5] low word = queue
+    // head of the persistent kernel), the host entry's staging (records in, `after` records, results in 4-byte words, counts), grown on
+    // demand, its two timing events, the occupancy of its persistent kernel (per kind for the ray query, [0] for the list queries)
+    struct QueryFamily {
+        DevBuf<unsigned long long> counters; DevBuf<float4> in, after; DevBuf<uint32_t> out, counts; Event ev[2]; OccCache occ[2];
+    };
+    QueryFamily rayQuery, hitsQuery, pointsQuery;      // fyprt_trace_rays* (and the primary segments of fyprt_render_rays*), fyprt_trace_ray_hits*, fyprt_nearest_points*
     // radiance queries (fyprt_render_rays*, rt_query.h: k_render_rays_primary + the path stages), allocated on first use for
     // min(count, FYPRT_RENDER_RAYS_CHUNK) rays and kept: primary records, path state, ray / result lists, live lists, list counters + queue
     // heads; the host entry's staging (rays, pixel indices, radiance) and its two timing events
@@ -383,6 +381,71 @@ template <class Q> static void set_queue_params(const fyprt_context* c, Q& q, in
 static void add_ray_stats(fyprt_frame_stats* s, int k, const unsigned long long* r) {
     s->part_rays[k] = r[0]; s->part_box_tests[k] = r[1]; s->part_tri_tests[k] = r[2]; s->part_hits[k] = r[3]; s->part_node_visits[k] = r[4];
     s->rays += r[0]; s->box_tests += r[1]; s->tri_tests += r[2]; s->hits += r[3]; s->node_visits += r[4];
+}
+
+// ---- what the query families share (the entry points: "batched ray queries" below)
+// Enqueues one query launch on the context stream (q: the record pointers in device memory and count > 0; kernels[simple][counted]);
+// `timed` brackets it with the family's events.  A workgroup's LDS is the stack plus `listBytes` per thread (the list queries' 16 bytes
+// per entry of this call's max_hits).  The families have always differed in how tuning key 2 and a failed occupancy query are taken,
+// and keep doing so: `clampWg` holds key 2 to the occupancy, `occFallback` stands in for an occupancy the runtime cannot give.
+template <class Q>
+static int launch_query(fyprt_context* c, fyprt_context::QueryFamily& f, OccCache& occ, Q q, void (*const kernels[2][2])(DevScene, Q), size_t listBytes,
+                        bool clampWg, int occFallback, bool timed) {
+    if (!f.counters.p) { HIPCHK(c, f.counters.alloc(8)); }
+    HIPCHK(c, hipMemsetAsync(f.counters.p, 0, 64, c->stream));
+    const StackLds stack = stack_lds(c, 0u);                      // the query kernels stage no top nodes (not even in a -DRT_TOPCACHE build)
+    // the path engine's ray kernels' quorum (incoherent rays in general), the family's own counters
+    DevScene qs = secondary_scene(c->dsc, (uint32_t)c->tuning[K_QUORUM_SECONDARY], c->countRays ? f.counters.p : nullptr);
+    qs.stackBudget = stack.budget;
+    const size_t ldsBytes = stack.bytes + listBytes * kBlock;     // <= 32 KB + 32 KB
+    q.head = reinterpret_cast<uint32_t*>(f.counters.p + 5);
+    set_queue_params(c, q, K_REFILL_LANES);
+    const uint32_t blocksForRecords = (uint32_t)(((size_t)q.count + kBlock - 1) / kBlock);
+    const bool simple = simple_ray_kernel(c);                     // tuning key 15 as in the path engine
+    int perCU = 16;
+    if (!simple) {
+        const int o = occ.get(kernels[0][0], ldsBytes, occFallback), wg = c->tuning[K_WG_PER_CU];
+        perCU = wg > 0 ? (clampWg ? std::min(wg, o) : wg) : o;
+    }
+    const dim3 grid(std::max(1u, std::min<uint32_t>((uint32_t)(c->numCUs * perCU), blocksForRecords)));   // no more workgroups than the records fill
+    if (timed) HIPCHK(c, hipEventRecord(f.ev[0], c->stream));
+    hipLaunchKernelGGL(kernels[simple ? 1 : 0][c->countRays ? 1 : 0], grid, dim3(kBlock), ldsBytes, c->stream, qs, q);
+    HIPCHK(c, hipGetLastError());
+    if (timed) HIPCHK(c, hipEventRecord(f.ev[1], c->stream));
+    return FYPRT_OK;
+}
+
+// A blocking entry point behind its checks: host records through the family's staging (which grows and is kept), one timed launch by
+// `enqueue(in, after, out, counts)` on the staging pointers, results back, the launch's time and ray counters into `stats`.
+// inQuads: float4s per input record; after / counts: the list queries' (counts is staged for them whether or not the caller wants it).
+struct HostQuery { const void* in; size_t inQuads; const void* after; void* out; size_t outBytes; uint32_t* counts; bool list; };
+template <class Enqueue>
+static int run_host_query(fyprt_context* c, fyprt_context::QueryFamily& f, const HostQuery& h, uint32_t count, fyprt_frame_stats* stats, Enqueue enqueue) {
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (count == 0) return FYPRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    for (Event& e : f.ev) HIPCHK(c, create(e));
+    if (f.in.n < (size_t)count * h.inQuads) { HIPCHK(c, f.in.alloc((size_t)count * h.inQuads)); }         // staging grows, is kept
+    if (h.after && f.after.n < (size_t)count) { HIPCHK(c, f.after.alloc(count)); }
+    if (f.out.bytes() < h.outBytes) { HIPCHK(c, f.out.alloc(h.outBytes / 4)); }
+    if (h.list && f.counts.n < (size_t)count) { HIPCHK(c, f.counts.alloc(count)); }
+    HIPCHK(c, hipMemcpyAsync(f.in.p, h.in, (size_t)count * h.inQuads * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    if (h.after) HIPCHK(c, hipMemcpyAsync(f.after.p, h.after, (size_t)count * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    TRY(enqueue(f.in.p, h.after ? f.after.p : nullptr, f.out.p, f.counts.p));
+    HIPCHK(c, hipMemcpyAsync(h.out, f.out.p, h.outBytes, hipMemcpyDeviceToHost, c->stream));
+    if (h.counts) HIPCHK(c, hipMemcpyAsync(h.counts, f.counts.p, (size_t)count * 4u, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (stats) {
+        float ms = 0.0f;
+        HIPCHK(c, hipEventElapsedTime(&ms, f.ev[0], f.ev[1]));
+        stats->kernel_ms = ms; stats->kernel_ms_part[0] = ms; stats->launches = 1;
+        if (c->countRays) {
+            unsigned long long r[5] = {0, 0, 0, 0, 0};
+            HIPCHK(c, hipMemcpy(r, f.counters.p, sizeof r, hipMemcpyDeviceToHost));
+            add_ray_stats(stats, 0, r);
+        }
+    }
+    return FYPRT_OK;
 }
 
 extern "C" {
@@ -2183,62 +2246,21 @@ static int check_query(fyprt_context* c, int query, const void* rays, uint32_t c
     if (!c->haveScene) return c->fail(FYPRT_ESTATE, std::string(who) + " before fyprt_upload_scene");
     return FYPRT_OK;
 }
-// Enqueues one query launch on the context stream (rays / results: device memory, count > 0); `timed` brackets it with the query events.
 static int enqueue_query(fyprt_context* c, int query, const float4* rays, uint32_t count, void* results, bool timed) {
-    const bool occluded = query == FYPRT_QUERY_OCCLUDED;
-    if (!c->queryCounters.p) { HIPCHK(c, c->queryCounters.alloc(8)); }
-    HIPCHK(c, hipMemsetAsync(c->queryCounters.p, 0, 64, c->stream));
-    const StackLds stack = stack_lds(c, 0u);                      // the query kernels stage no top nodes (not even in a -DRT_TOPCACHE build)
-    // the path engine's ray kernels' quorum (incoherent rays in general), the query's own counters
-    DevScene qs = secondary_scene(c->dsc, (uint32_t)c->tuning[K_QUORUM_SECONDARY], c->countRays ? c->queryCounters.p : nullptr);
-    qs.stackBudget = stack.budget;
-    const size_t ldsBytes = stack.bytes;
+    const int occluded = query == FYPRT_QUERY_OCCLUDED ? 1 : 0;
+    static void (*const kQuery[2][2][2])(DevScene, QueryRays) = {{{k_query_rays<false, false>, k_query_rays<false, true>}, {k_query_rays_simple<false, false>, k_query_rays_simple<false, true>}},
+                                                                {{k_query_rays<true, false>, k_query_rays<true, true>}, {k_query_rays_simple<true, false>, k_query_rays_simple<true, true>}}};
     QueryRays q{};
-    q.rays = rays; q.results = results; q.count = count; q.head = reinterpret_cast<uint32_t*>(c->queryCounters.p + 5);
-    set_queue_params(c, q, K_REFILL_LANES);
-    const dim3 block(kBlock);
-    const uint32_t blocksForRays = (uint32_t)(((size_t)count + kBlock - 1) / kBlock);
-    const bool simple = simple_ray_kernel(c);                     // tuning key 15 as in the path engine
-    dim3 grid;
-    if (simple) grid = dim3(std::max(1u, std::min<uint32_t>((uint32_t)c->numCUs * 16u, blocksForRays)));
-    else {
-        const int occ = c->queryOcc[occluded].get(occluded ? k_query_rays<true, false> : k_query_rays<false, false>, ldsBytes, 4), perCU = c->tuning[K_WG_PER_CU] > 0 ? c->tuning[K_WG_PER_CU] : occ;
-        grid = dim3(std::max(1u, std::min<uint32_t>((uint32_t)(c->numCUs * perCU), blocksForRays)));   // no more workgroups than the rays fill
-    }
-    if (timed) HIPCHK(c, hipEventRecord(c->queryEv[0], c->stream));
-    const int k = (occluded ? 2 : 0) + (c->countRays ? 1 : 0);
-    static void (*const kQuery[2][4])(DevScene, QueryRays) = {{k_query_rays<false, false>, k_query_rays<false, true>, k_query_rays<true, false>, k_query_rays<true, true>},
-        {k_query_rays_simple<false, false>, k_query_rays_simple<false, true>, k_query_rays_simple<true, false>, k_query_rays_simple<true, true>}};
-    hipLaunchKernelGGL(kQuery[simple ? 1 : 0][k], grid, block, ldsBytes, c->stream, qs, q);
-    HIPCHK(c, hipGetLastError());
-    if (timed) HIPCHK(c, hipEventRecord(c->queryEv[1], c->stream));
-    return FYPRT_OK;
+    q.rays = rays; q.results = results; q.count = count;
+    // key 2 taken as it is, 4 workgroups per CU without an occupancy, the occupancy cached per kind
+    return launch_query(c, c->rayQuery, c->rayQuery.occ[occluded], q, kQuery[occluded], 0u, false, 4, timed);
 }
 
 int fyprt_trace_rays(fyprt_context* c, int query, const fyprt_ray* rays, uint32_t count, void* results, fyprt_frame_stats* stats) {
     TRY(check_query(c, query, rays, count, results, false));
-    if (stats) std::memset(stats, 0, sizeof *stats);
-    if (count == 0) return FYPRT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t rayBytes = (size_t)count * sizeof(fyprt_ray), resultBytes = (size_t)count * (query == FYPRT_QUERY_OCCLUDED ? 4u : 40u);
-    for (Event& e : c->queryEv) HIPCHK(c, create(e));
-    if (c->queryRays.n < (size_t)count * 2) { HIPCHK(c, c->queryRays.alloc((size_t)count * 2)); }        // staging grows, is kept
-    if (c->queryResults.bytes() < resultBytes) { HIPCHK(c, c->queryResults.alloc(resultBytes / 4)); }
-    HIPCHK(c, hipMemcpyAsync(c->queryRays.p, rays, rayBytes, hipMemcpyHostToDevice, c->stream));
-    TRY(enqueue_query(c, query, c->queryRays.p, count, c->queryResults.p, true));
-    HIPCHK(c, hipMemcpyAsync(results, c->queryResults.p, resultBytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (stats) {
-        float ms = 0.0f;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->queryEv[0], c->queryEv[1]));
-        stats->kernel_ms = ms; stats->kernel_ms_part[0] = ms; stats->launches = 1;
-        if (c->countRays) {
-            unsigned long long r[5] = {0, 0, 0, 0, 0};
-            HIPCHK(c, hipMemcpy(r, c->queryCounters.p, sizeof r, hipMemcpyDeviceToHost));
-            add_ray_stats(stats, 0, r);
-        }
-    }
-    return FYPRT_OK;
+    const HostQuery h{rays, 2, nullptr, results, (size_t)count * (query == FYPRT_QUERY_OCCLUDED ? 4u : 40u), nullptr, false};
+    return run_host_query(c, c->rayQuery, h, count, stats, [&](const float4* in, const float4*, uint32_t* out, uint32_t*) {
+        return enqueue_query(c, query, in, count, out, true); });
 }
 
 int fyprt_trace_rays_device(fyprt_context* c, int query, const void* rays, uint32_t count, void* results) {
@@ -2248,168 +2270,62 @@ int fyprt_trace_rays_device(fyprt_context* c, int query, const void* rays, uint3
     return enqueue_query(c, query, static_cast<const float4*>(rays), count, results, false);
 }
 
-// ---- multi-hit queries (rt_query.h: k_query_hits / k_query_hits_simple).  As the batched queries: the scene is read, the query's own
-// results and counters are written, no frame state moves.
-static int check_ray_hits(fyprt_context* c, const void* rays, const void* after, uint32_t count, uint32_t maxHits, const void* hits, const void* hitCounts, bool device) {
-    const char* who = device ? "fyprt_trace_ray_hits_device" : "fyprt_trace_ray_hits";
+// ---- the list queries: multi-hit (rt_query.h: k_query_hits / k_query_hits_simple) and nearest points (rt_points.h: k_query_points /
+// k_query_points_simple).  As the batched queries: the scene is read, the query's own results and counters are written, no frame state
+// moves.  `who`: the entry point, `noun`: what its records are called, `verb`: what a host-only context is told it cannot do.
+static int check_list_query(fyprt_context* c, const char* who, const char* noun, const char* verb, const void* in, const void* after, uint32_t count,
+                            uint32_t maxHits, const void* hits, const void* hitCounts, bool device) {
     if (!c) return FYPRT_EINVAL;
     if (maxHits == 0 || maxHits > FYPRT_QUERY_MAX_HITS) return c->fail(FYPRT_EINVAL, std::string(who) + ": max_hits must be 1.." + std::to_string(FYPRT_QUERY_MAX_HITS));
-    if (count && (!rays || !hits)) return c->fail(FYPRT_EINVAL, std::string(who) + ": NULL rays / hits with a non-zero count");
-    if (device && (((uintptr_t)rays & 15u) || ((uintptr_t)after & 15u) || ((uintptr_t)hits & 15u) || ((uintptr_t)hitCounts & 3u)))   // 16-byte loads and stores, 4-byte counts
-        return c->fail(FYPRT_EINVAL, std::string(who) + ": rays, after and hits must be 16-byte and hit_counts 4-byte aligned");
-    if (c->hostOnly) return c->fail(FYPRT_ESTATE, std::string(who) + ": host-only context (device -1) cannot trace");
+    if (count && (!in || !hits)) return c->fail(FYPRT_EINVAL, std::string(who) + ": NULL " + noun + " / hits with a non-zero count");
+    if (device && (((uintptr_t)in & 15u) || ((uintptr_t)after & 15u) || ((uintptr_t)hits & 15u) || ((uintptr_t)hitCounts & 3u)))   // 16-byte loads and stores, 4-byte counts
+        return c->fail(FYPRT_EINVAL, std::string(who) + ": " + noun + ", after and hits must be 16-byte and hit_counts 4-byte aligned");
+    if (c->hostOnly) return c->fail(FYPRT_ESTATE, std::string(who) + ": host-only context (device -1) cannot " + verb);
     if (!c->haveScene) return c->fail(FYPRT_ESTATE, std::string(who) + " before fyprt_upload_scene");
     return FYPRT_OK;
 }
-// Enqueues one multi-hit launch on the context stream (device memory, count > 0, after / counts may be NULL); `timed` brackets it with
-// the query's events.  A workgroup's LDS is the stack plus 16 bytes per thread and list entry: the list is sized by this call's max_hits.
-static int enqueue_ray_hits(fyprt_context* c, const float4* rays, const float4* after, uint32_t count, uint32_t maxHits, float4* hits, uint32_t* counts, bool timed) {
-    if (!c->hitsCounters.p) { HIPCHK(c, c->hitsCounters.alloc(8)); }
-    HIPCHK(c, hipMemsetAsync(c->hitsCounters.p, 0, 64, c->stream));
-    const StackLds stack = stack_lds(c, 0u);
-    DevScene qs = secondary_scene(c->dsc, (uint32_t)c->tuning[K_QUORUM_SECONDARY], c->countRays ? c->hitsCounters.p : nullptr);
-    qs.stackBudget = stack.budget;
-    const size_t ldsBytes = stack.bytes + (size_t)maxHits * 16u * kBlock;        // <= 32 KB + 32 KB
+// The two families of list queries: state, kernels[simple][counted], float4s per input record
+struct ListQuery { fyprt_context::QueryFamily fyprt_context::* family; void (*kernels[2][2])(DevScene, QueryHits); size_t inQuads; };
+static const ListQuery kRayHits = {&fyprt_context::hitsQuery, {{k_query_hits<false>, k_query_hits<true>}, {k_query_hits_simple<false>, k_query_hits_simple<true>}}, 2};
+static const ListQuery kNearestPoints = {&fyprt_context::pointsQuery, {{k_query_points<false>, k_query_points<true>}, {k_query_points_simple<false>, k_query_points_simple<true>}}, 1};
+// (device memory, count > 0, after / counts may be NULL)
+static int enqueue_list_query(fyprt_context* c, const ListQuery& l, const float4* in, const float4* after, uint32_t count, uint32_t maxHits, float4* hits, uint32_t* counts, bool timed) {
+    fyprt_context::QueryFamily& f = c->*l.family;
     QueryHits q{};
-    q.rays = rays; q.after = after; q.hits = hits; q.counts = counts; q.count = count; q.maxHits = maxHits;
-    q.head = reinterpret_cast<uint32_t*>(c->hitsCounters.p + 5);
-    set_queue_params(c, q, K_REFILL_LANES);
-    const dim3 block(kBlock);
-    const uint32_t blocksForRays = (uint32_t)(((size_t)count + kBlock - 1) / kBlock);
-    const bool simple = simple_ray_kernel(c);                     // tuning key 15 as for the other queries
-    dim3 grid;
-    if (simple) grid = dim3(std::max(1u, std::min<uint32_t>((uint32_t)c->numCUs * 16u, blocksForRays)));
-    else {
-        const int occ = c->hitsOcc.get(k_query_hits<false>, ldsBytes, 2), perCU = c->tuning[K_WG_PER_CU] > 0 ? std::min(c->tuning[K_WG_PER_CU], occ) : occ;
-        grid = dim3(std::max(1u, std::min<uint32_t>((uint32_t)(c->numCUs * perCU), blocksForRays)));
-    }
-    if (timed) HIPCHK(c, hipEventRecord(c->hitsEv[0], c->stream));
-    static void (*const kHits[2][2])(DevScene, QueryHits) = {{k_query_hits<false>, k_query_hits<true>}, {k_query_hits_simple<false>, k_query_hits_simple<true>}};
-    hipLaunchKernelGGL(kHits[simple ? 1 : 0][c->countRays ? 1 : 0], grid, block, ldsBytes, c->stream, qs, q);
-    HIPCHK(c, hipGetLastError());
-    if (timed) HIPCHK(c, hipEventRecord(c->hitsEv[1], c->stream));
-    return FYPRT_OK;
+    q.rays = in; q.after = after; q.hits = hits; q.counts = counts; q.count = count; q.maxHits = maxHits;
+    // key 2 no higher than the occupancy, 2 workgroups per CU without one
+    return launch_query(c, f, f.occ[0], q, l.kernels, (size_t)maxHits * 16u, true, 2, timed);
+}
+static int host_list_query(fyprt_context* c, const ListQuery& l, const void* in, const void* after, uint32_t count, uint32_t maxHits, void* hits, uint32_t* hitCounts,
+                           fyprt_frame_stats* stats) {
+    const HostQuery h{in, l.inQuads, after, hits, (size_t)count * maxHits * sizeof(float4), hitCounts, true};
+    return run_host_query(c, c->*l.family, h, count, stats, [&](const float4* dIn, const float4* dAfter, uint32_t* dOut, uint32_t* dCounts) {
+        return enqueue_list_query(c, l, dIn, dAfter, count, maxHits, reinterpret_cast<float4*>(dOut), dCounts, true); });
+}
+static int device_list_query(fyprt_context* c, const ListQuery& l, const void* in, const void* after, uint32_t count, uint32_t maxHits, void* hits, void* hitCounts) {
+    if (count == 0) return FYPRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    return enqueue_list_query(c, l, static_cast<const float4*>(in), static_cast<const float4*>(after), count, maxHits, static_cast<float4*>(hits),
+                              static_cast<uint32_t*>(hitCounts), false);
 }
 
 int fyprt_trace_ray_hits(fyprt_context* c, const fyprt_ray* rays, const fyprt_ray_hit* after, uint32_t count, uint32_t max_hits, fyprt_ray_hit* hits,
                          uint32_t* hit_counts, fyprt_frame_stats* stats) {
-    TRY(check_ray_hits(c, rays, after, count, max_hits, hits, hit_counts, false));
-    if (stats) std::memset(stats, 0, sizeof *stats);
-    if (count == 0) return FYPRT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t rayBytes = (size_t)count * sizeof(fyprt_ray), afterBytes = (size_t)count * sizeof(fyprt_ray_hit), hitBytes = afterBytes * max_hits;
-    for (Event& e : c->hitsEv) HIPCHK(c, create(e));
-    if (c->hitsRays.n < (size_t)count * 2) { HIPCHK(c, c->hitsRays.alloc((size_t)count * 2)); }          // staging grows, is kept
-    if (after && c->hitsAfter.n < (size_t)count) { HIPCHK(c, c->hitsAfter.alloc(count)); }
-    if (c->hitsOut.n < (size_t)count * max_hits) { HIPCHK(c, c->hitsOut.alloc((size_t)count * max_hits)); }
-    if (c->hitsCounts.n < (size_t)count) { HIPCHK(c, c->hitsCounts.alloc(count)); }
-    HIPCHK(c, hipMemcpyAsync(c->hitsRays.p, rays, rayBytes, hipMemcpyHostToDevice, c->stream));
-    if (after) HIPCHK(c, hipMemcpyAsync(c->hitsAfter.p, after, afterBytes, hipMemcpyHostToDevice, c->stream));
-    TRY(enqueue_ray_hits(c, c->hitsRays.p, after ? c->hitsAfter.p : nullptr, count, max_hits, c->hitsOut.p, c->hitsCounts.p, true));
-    HIPCHK(c, hipMemcpyAsync(hits, c->hitsOut.p, hitBytes, hipMemcpyDeviceToHost, c->stream));
-    if (hit_counts) HIPCHK(c, hipMemcpyAsync(hit_counts, c->hitsCounts.p, (size_t)count * 4u, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (stats) {
-        float ms = 0.0f;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->hitsEv[0], c->hitsEv[1]));
-        stats->kernel_ms = ms; stats->kernel_ms_part[0] = ms; stats->launches = 1;
-        if (c->countRays) {
-            unsigned long long r[5] = {0, 0, 0, 0, 0};
-            HIPCHK(c, hipMemcpy(r, c->hitsCounters.p, sizeof r, hipMemcpyDeviceToHost));
-            add_ray_stats(stats, 0, r);
-        }
-    }
-    return FYPRT_OK;
+    TRY(check_list_query(c, "fyprt_trace_ray_hits", "rays", "trace", rays, after, count, max_hits, hits, hit_counts, false));
+    return host_list_query(c, kRayHits, rays, after, count, max_hits, hits, hit_counts, stats);
 }
-
 int fyprt_trace_ray_hits_device(fyprt_context* c, const void* rays, const void* after, uint32_t count, uint32_t max_hits, void* hits, void* hit_counts) {
-    TRY(check_ray_hits(c, rays, after, count, max_hits, hits, hit_counts, true));
-    if (count == 0) return FYPRT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    return enqueue_ray_hits(c, static_cast<const float4*>(rays), static_cast<const float4*>(after), count, max_hits, static_cast<float4*>(hits),
-                            static_cast<uint32_t*>(hit_counts), false);
+    TRY(check_list_query(c, "fyprt_trace_ray_hits_device", "rays", "trace", rays, after, count, max_hits, hits, hit_counts, true));
+    return device_list_query(c, kRayHits, rays, after, count, max_hits, hits, hit_counts);
 }
-
-// ---- nearest-point queries (rt_points.h: k_query_points / k_query_points_simple).  fyprt_trace_ray_hits clause for clause: the scene is
-// read, the query's own results and counters are written, no frame state moves.
-static int check_nearest_points(fyprt_context* c, const void* points, const void* after, uint32_t count, uint32_t maxHits, const void* hits, const void* hitCounts, bool device) {
-    const char* who = device ? "fyprt_nearest_points_device" : "fyprt_nearest_points";
-    if (!c) return FYPRT_EINVAL;
-    if (maxHits == 0 || maxHits > FYPRT_QUERY_MAX_HITS) return c->fail(FYPRT_EINVAL, std::string(who) + ": max_hits must be 1.." + std::to_string(FYPRT_QUERY_MAX_HITS));
-    if (count && (!points || !hits)) return c->fail(FYPRT_EINVAL, std::string(who) + ": NULL points / hits with a non-zero count");
-    if (device && (((uintptr_t)points & 15u) || ((uintptr_t)after & 15u) || ((uintptr_t)hits & 15u) || ((uintptr_t)hitCounts & 3u)))   // 16-byte loads and stores, 4-byte counts
-        return c->fail(FYPRT_EINVAL, std::string(who) + ": points, after and hits must be 16-byte and hit_counts 4-byte aligned");
-    if (c->hostOnly) return c->fail(FYPRT_ESTATE, std::string(who) + ": host-only context (device -1) cannot query");
-    if (!c->haveScene) return c->fail(FYPRT_ESTATE, std::string(who) + " before fyprt_upload_scene");
-    return FYPRT_OK;
-}
-// Enqueues one nearest-point launch on the context stream (device memory, count > 0, after / counts may be NULL); `timed` brackets it
-// with the query's events.  LDS and occupancy as enqueue_ray_hits: the stack plus 16 bytes per thread and list entry.
-static int enqueue_nearest_points(fyprt_context* c, const float4* points, const float4* after, uint32_t count, uint32_t maxHits, float4* hits, uint32_t* counts, bool timed) {
-    if (!c->pointsCounters.p) { HIPCHK(c, c->pointsCounters.alloc(8)); }
-    HIPCHK(c, hipMemsetAsync(c->pointsCounters.p, 0, 64, c->stream));
-    const StackLds stack = stack_lds(c, 0u);
-    DevScene qs = secondary_scene(c->dsc, (uint32_t)c->tuning[K_QUORUM_SECONDARY], c->countRays ? c->pointsCounters.p : nullptr);
-    qs.stackBudget = stack.budget;
-    const size_t ldsBytes = stack.bytes + (size_t)maxHits * 16u * kBlock;        // <= 32 KB + 32 KB
-    QueryPoints q{};
-    q.rays = points; q.after = after; q.hits = hits; q.counts = counts; q.count = count; q.maxHits = maxHits;
-    q.head = reinterpret_cast<uint32_t*>(c->pointsCounters.p + 5);
-    set_queue_params(c, q, K_REFILL_LANES);
-    const dim3 block(kBlock);
-    const uint32_t blocksForPoints = (uint32_t)(((size_t)count + kBlock - 1) / kBlock);
-    const bool simple = simple_ray_kernel(c);                     // tuning key 15 as for the other queries
-    dim3 grid;
-    if (simple) grid = dim3(std::max(1u, std::min<uint32_t>((uint32_t)c->numCUs * 16u, blocksForPoints)));
-    else {
-        const int occ = c->pointsOcc.get(k_query_points<false>, ldsBytes, 2), perCU = c->tuning[K_WG_PER_CU] > 0 ? std::min(c->tuning[K_WG_PER_CU], occ) : occ;
-        grid = dim3(std::max(1u, std::min<uint32_t>((uint32_t)(c->numCUs * perCU), blocksForPoints)));
-    }
-    if (timed) HIPCHK(c, hipEventRecord(c->pointsEv[0], c->stream));
-    static void (*const kPoints[2][2])(DevScene, QueryPoints) = {{k_query_points<false>, k_query_points<true>}, {k_query_points_simple<false>, k_query_points_simple<true>}};
-    hipLaunchKernelGGL(kPoints[simple ? 1 : 0][c->countRays ? 1 : 0], grid, block, ldsBytes, c->stream, qs, q);
-    HIPCHK(c, hipGetLastError());
-    if (timed) HIPCHK(c, hipEventRecord(c->pointsEv[1], c->stream));
-    return FYPRT_OK;
-}
-
 int fyprt_nearest_points(fyprt_context* c, const fyprt_point* points, const fyprt_point_hit* after, uint32_t count, uint32_t max_hits, fyprt_point_hit* hits,
                          uint32_t* hit_counts, fyprt_frame_stats* stats) {
-    TRY(check_nearest_points(c, points, after, count, max_hits, hits, hit_counts, false));
-    if (stats) std::memset(stats, 0, sizeof *stats);
-    if (count == 0) return FYPRT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t pointBytes = (size_t)count * sizeof(fyprt_point), afterBytes = (size_t)count * sizeof(fyprt_point_hit), hitBytes = afterBytes * max_hits;
-    for (Event& e : c->pointsEv) HIPCHK(c, create(e));
-    if (c->pointsIn.n < (size_t)count) { HIPCHK(c, c->pointsIn.alloc(count)); }                          // staging grows, is kept
-    if (after && c->pointsAfter.n < (size_t)count) { HIPCHK(c, c->pointsAfter.alloc(count)); }
-    if (c->pointsOut.n < (size_t)count * max_hits) { HIPCHK(c, c->pointsOut.alloc((size_t)count * max_hits)); }
-    if (c->pointsCounts.n < (size_t)count) { HIPCHK(c, c->pointsCounts.alloc(count)); }
-    HIPCHK(c, hipMemcpyAsync(c->pointsIn.p, points, pointBytes, hipMemcpyHostToDevice, c->stream));
-    if (after) HIPCHK(c, hipMemcpyAsync(c->pointsAfter.p, after, afterBytes, hipMemcpyHostToDevice, c->stream));
-    TRY(enqueue_nearest_points(c, c->pointsIn.p, after ? c->pointsAfter.p : nullptr, count, max_hits, c->pointsOut.p, c->pointsCounts.p, true));
-    HIPCHK(c, hipMemcpyAsync(hits, c->pointsOut.p, hitBytes, hipMemcpyDeviceToHost, c->stream));
-    if (hit_counts) HIPCHK(c, hipMemcpyAsync(hit_counts, c->pointsCounts.p, (size_t)count * 4u, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (stats) {
-        float ms = 0.0f;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->pointsEv[0], c->pointsEv[1]));
-        stats->kernel_ms = ms; stats->kernel_ms_part[0] = ms; stats->launches = 1;
-        if (c->countRays) {
-            unsigned long long r[5] = {0, 0, 0, 0, 0};
-            HIPCHK(c, hipMemcpy(r, c->pointsCounters.p, sizeof r, hipMemcpyDeviceToHost));
-            add_ray_stats(stats, 0, r);
-        }
-    }
-    return FYPRT_OK;
+    TRY(check_list_query(c, "fyprt_nearest_points", "points", "query", points, after, count, max_hits, hits, hit_counts, false));
+    return host_list_query(c, kNearestPoints, points, after, count, max_hits, hits, hit_counts, stats);
 }
-
 int fyprt_nearest_points_device(fyprt_context* c, const void* points, const void* after, uint32_t count, uint32_t max_hits, void* hits, void* hit_counts) {
-    TRY(check_nearest_points(c, points, after, count, max_hits, hits, hit_counts, true));
-    if (count == 0) return FYPRT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    return enqueue_nearest_points(c, static_cast<const float4*>(points), static_cast<const float4*>(after), count, max_hits, static_cast<float4*>(hits),
-                                  static_cast<uint32_t*>(hit_counts), false);
+    TRY(check_list_query(c, "fyprt_nearest_points_device", "points", "query", points, after, count, max_hits, hits, hit_counts, true));
+    return device_list_query(c, kNearestPoints, points, after, count, max_hits, hits, hit_counts);
 }
 
 // ---- radiance queries (rt_query.h: k_render_rays_primary; rt_paths.h: the path stages with CAM = RaySource).  A frame's sample of
@@ -2464,7 +2380,7 @@ static int enqueue_render_rays(fyprt_context* c, const fyprt_settings* s, uint32
     ++*launched;
     HIPCHK(c, hipGetLastError());
     const StageBufs b{{c->rrRays[0].p, c->rrRays[1].p}, {c->rrHits[0].p, c->rrHits[1].p}, c->rrState.p, c->rrPixels.p, c->rrPixels2.p,
-                      c->countRays ? c->queryCounters.p : nullptr};
+                      c->countRays ? c->rayQuery.counters.p : nullptr};
     TRY(run_stage(c, path_stage(tech, p, c->rrPixels.p, c->rrPixels2.p, c->rrCounters.p, count), b, qs, rs, fr, st, stack.bytes, blocking, launched));
     if (payloads) HIPCHK(c, hipMemcpyAsync(payloads, c->rrPayload.p, (size_t)count * sizeof(Payload), payloadKind, c->stream));
     return FYPRT_OK;
@@ -2496,7 +2412,7 @@ int fyprt_render_rays(fyprt_context* c, const fyprt_settings* s, uint32_t frame_
         ms += chunkMs;
         if (c->countRays) {
             unsigned long long r[5] = {0, 0, 0, 0, 0};
-            HIPCHK(c, hipMemcpy(r, c->queryCounters.p, sizeof r, hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(r, c->rayQuery.counters.p, sizeof r, hipMemcpyDeviceToHost));
             for (int k = 0; k < 5; ++k) totals[k] += r[k];
         }
     }

@@ -18,8 +18,8 @@
 // bound being r2 until the list is full and the worst entry's distance2 from then on: a child at exactly the bound is still visited,
 // a tie with a lower triangle index displaces the worst entry.
 //
-// Two kernels by tuning key 15, as the other queries: k_query_points (persistent waves: the refill, guided claims and node-loop quorum of
-// query_hits_body, keys 4, 5, 6, 9, 10) and k_query_points_simple (one thread per point).  The per-lane list is the multi-hit query's:
+// Two kernels by tuning key 15, as the other queries: k_query_points (persistent waves: query_body of rt_query.h with PointsLane, keys 4,
+// 5, 6, 9, 10) and k_query_points_simple (one thread per point: query_simple_body).  The per-lane list is the multi-hit query's:
 // HitList, hit_insert and store_hits, in LDS behind the stack, 16 B per entry; the query record is QueryHits with one float4 per point.
 #pragma once
 #include "rt_query.h"
@@ -166,130 +166,47 @@ RT_DEV float points_leaf(const DevScene& sc, const HitList& l, uint32_t maxHits,
     return bound;
 }
 
-// Persistent waves: query_hits_body with a point in place of the ray
-template <bool COUNT>
-RT_DEV void query_points_body(const DevScene& sc, const QueryPoints& q, int32_t* s_stack) {
-    int32_t* lds = s_stack + threadIdx.x;
-    const HitList list = hit_list(s_stack, sc.stackBudget, q.maxHits);
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t total = q.count;
-    const uint32_t nWaves = gridDim.x * (uint32_t)(kBlock / 64), myWave = blockIdx.x * (uint32_t)(kBlock / 64) + (threadIdx.x >> 6);
-    const uint32_t share = (total + nWaves - 1u) / nWaves;
-    const uint32_t chunk = q.chunk, want1 = chunk * q.staticChunks;
-    const uint32_t first = share < want1 ? (share < 16u ? 16u : share) : want1;
-    const uint32_t dynBase = nWaves * first;
-    const bool hasDyn = dynBase < total;
+// The point lane state: HitsLane with a point in place of the ray, the squared radius in place of the interval
+struct PointsLane {
+    using Query = QueryPoints;
+    const HitList list;
     f3 p = splat3(0.0f);
-    float r2 = 0.0f, bound = 0.0f; uint32_t task = 0, n = 0; int32_t cur = kExit; int top = 0;
+    float r2 = 0.0f, bound = 0.0f; uint32_t n = 0;
     unsigned long long worst = kNoWorstKey, lowKey = 0ull;
-    uint32_t nBox = 0, nTri = 0, nNode = 0;
-    bool active = false;
-    bool more = total != 0u;
-    uint32_t chunkNext = myWave * first < total ? myWave * first : total;
-    uint32_t chunkEnd = (myWave + 1u) * first < total ? (myWave + 1u) * first : total;
-    while (true) {
-        const unsigned long long idle = __ballot(!active);
-        if (more && (uint32_t)__popcll(idle) >= q.refillLanes) {
-            if (chunkNext >= chunkEnd && hasDyn) {
-                uint32_t base = 0;
-                uint32_t size = (total - chunkEnd) / nWaves;
-                size = size < q.minChunk ? q.minChunk : (size > chunk ? chunk : size);
-                if (lane == 0u) base = dynBase + atomicAdd(q.head, size);
-                base = (uint32_t)__shfl((int)base, 0);
-                chunkNext = base < total ? base : total;
-                chunkEnd = (base + size < total) ? base + size : total;
-            }
-            const uint32_t slot = chunkNext + (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
-            const uint32_t want = (uint32_t)__popcll(idle), avail = chunkEnd - chunkNext;
-            chunkNext += (want < avail) ? want : avail;
-            more = chunkNext < chunkEnd || (hasDyn && chunkEnd < total);
-            if (!active && slot < chunkEnd) {
-                task = slot;
-                const float4 r0 = q.rays[task];
-                p = mk3(r0.x, r0.y, r0.z);
-                r2 = point_r2(r0.w); bound = r2;
-                n = 0; worst = kNoWorstKey;
-                if (COUNT) { nBox = 0; nTri = 0; nNode = 0; }
-                top = 0; lane_push(lds, top, kExit);
-                const bool wanted = points_start(q, task, lowKey);
-                cur = (sc.triCount == 0 || !wanted || point_invalid(p, r0.w)) ? kExit : sc.rootRef;
-                active = true;
-            }
-        }
-        if (__ballot(active) == 0ull) { if (!more) break; else continue; }
-        while (true) {
-            bool walk = active && cur >= 0;
-            const uint32_t quorum = quorum_of(sc.nodeQuorum, (uint32_t)__popcll(__ballot(active)));
-            while (walk) {
-                { Stack st; st.lds = lds; st.top = top; cur = point_node_step<COUNT>(sc.nodes, sc.stackBudget, cur, p, bound, st, nBox, nNode); top = st.top; }
-                walk = cur >= 0;
-                if ((uint32_t)__popcll(__ballot(walk)) < quorum) break;
-            }
-            if (active && cur < 0 && cur != kExit) {
-                bound = points_leaf(sc, list, q.maxHits, cur, p, r2, lowKey, n, worst, bound, nTri, COUNT);
-                cur = lane_pop(lds, top);
-            }
-            if (active && cur == kExit) {
-                store_hits(q, list, task, n);
-                count_query_ray<COUNT>(sc, nBox, nTri, nNode, n != 0u);
-                active = false;
-            }
-            const unsigned long long act = __ballot(active);
-            if (act == 0ull) break;
-            if (more && (64u - (uint32_t)__popcll(act)) >= q.refillLanes) break;
-        }
+    RT_DEV PointsLane(const DevScene& sc, const QueryPoints& q, int32_t* s_stack) : list(hit_list(s_stack, sc.stackBudget, q.maxHits)) {}
+    RT_DEV int32_t start(const DevScene& sc, const QueryPoints& q, uint32_t i) {
+        const float4 r0 = q.rays[i];
+        p = mk3(r0.x, r0.y, r0.z);
+        r2 = point_r2(r0.w); bound = r2;
+        n = 0; worst = kNoWorstKey;
+        const bool wanted = points_start(q, i, lowKey);
+        return (sc.triCount == 0 || !wanted || point_invalid(p, r0.w)) ? kExit : sc.rootRef;
     }
-}
+    template <bool COUNT> RT_DEV int32_t visit(const DevScene& sc, int32_t cur, Stack& st, uint32_t& nBox, uint32_t& nNode) {
+        return point_node_step<COUNT>(sc.nodes, sc.stackBudget, cur, p, bound, st, nBox, nNode);
+    }
+    template <bool COUNT> RT_DEV bool leaf(const DevScene& sc, const QueryPoints& q, int32_t cur, uint32_t& nTri) {
+        bound = points_leaf(sc, list, q.maxHits, cur, p, r2, lowKey, n, worst, bound, nTri, COUNT);
+        return false;
+    }
+    RT_DEV bool finish(const DevScene&, const QueryPoints& q, uint32_t i) { store_hits(q, list, i, n); return n != 0u; }
+};
 
 template <bool COUNT> __global__ void k_query_points(DevScene sc, QueryPoints q);
 // 5 waves per SIMD as k_query_hits<false>: the list's LDS leaves room for no more workgroups from a 26-entry stack on
 template <> __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5))) void k_query_points<false>(DevScene sc, QueryPoints q) {
     extern __shared__ int32_t s_stack[];                         // (stackBudget + 1) x 4 B + maxHits x 16 B per thread, sized at launch
-    query_points_body<false>(sc, q, s_stack);
+    query_body<PointsLane, false>(sc, q, s_stack);
 }
 template <> __global__ __launch_bounds__(kBlock) void k_query_points<true>(DevScene sc, QueryPoints q) {      // instrumented: no register cap
     extern __shared__ int32_t s_stack[];
-    query_points_body<true>(sc, q, s_stack);
+    query_body<PointsLane, true>(sc, q, s_stack);
 }
 
-// One thread per point, as query_hits_one
-template <bool COUNT>
-RT_DEV void query_points_one(const DevScene& sc, const QueryPoints& q, uint32_t i, int32_t* ldsBase, const HitList& list) {
-    const float4 r0 = q.rays[i];
-    const f3 p = mk3(r0.x, r0.y, r0.z);
-    const float r2 = point_r2(r0.w);
-    float bound = r2;
-    uint32_t n = 0; unsigned long long worst = kNoWorstKey, lowKey;
-    uint32_t nBox = 0, nTri = 0, nNode = 0;
-    const bool wanted = points_start(q, i, lowKey);
-    if (!(sc.triCount == 0 || !wanted || point_invalid(p, r0.w))) {
-        Stack st; st.lds = ldsBase; st.top = 0; st.push(kExit);
-        int32_t cur = sc.rootRef;
-        while (true) {
-            bool walk = cur >= 0;
-            const uint32_t quorum = quorum_of(sc.nodeQuorum, (uint32_t)__popcll(__ballot(true)));
-            while (walk) {
-                cur = point_node_step<COUNT>(sc.nodes, sc.stackBudget, cur, p, bound, st, nBox, nNode);
-                walk = cur >= 0;
-                if ((uint32_t)__popcll(__ballot(walk)) < quorum) break;
-            }
-            if (cur >= 0) continue;
-            if (cur == kExit) break;
-            bound = points_leaf(sc, list, q.maxHits, cur, p, r2, lowKey, n, worst, bound, nTri, COUNT);
-            cur = st.pop();
-        }
-    }
-    store_hits(q, list, i, n);
-    count_query_ray<COUNT>(sc, nBox, nTri, nNode, n != 0u);
-}
 template <bool COUNT>
 __global__ __launch_bounds__(kBlock) void k_query_points_simple(DevScene sc, QueryPoints q) {
     extern __shared__ int32_t s_stack[];                         // (stackBudget + 1) x 4 B + maxHits x 16 B per thread, sized at launch
-    const HitList list = hit_list(s_stack, sc.stackBudget, q.maxHits);
-    for (uint32_t base = blockIdx.x * (uint32_t)kBlock; base < q.count; base += gridDim.x * (uint32_t)kBlock) {   // (block-uniform trips: the node visit's ballots see whole waves)
-        const uint32_t j = base + threadIdx.x;
-        if (j < q.count) query_points_one<COUNT>(sc, q, j, s_stack + threadIdx.x, list);
-    }
+    query_simple_body<PointsLane, COUNT>(sc, q, s_stack);
 }
 
 }  // namespace rt

@@ -18,7 +18,8 @@
 // The query kind is a template parameter: neither kernel carries the other kind's branches.  They only call the traversal core of
 // rt_device.h (node_step, tri_test, make_hit / make_miss, quorum_of, ray_not_finite); no frame kernel is touched.
 // The multi-hit query (fyprt_trace_ray_hits*: the K nearest hits per ray in order) has the same two forms, k_query_hits and
-// k_query_hits_simple, further down.
+// k_query_hits_simple, further down, and the nearest-point query (rt_points.h) has them too: all of them are query_body /
+// query_simple_body, written once below, around a per-query lane state.
 #pragma once
 #include "rt_paths.h"
 
@@ -54,9 +55,20 @@ RT_DEV void count_query_ray(const DevScene& sc, uint32_t nBox, uint32_t nTri, ui
     atomicAdd(sc.rayCounter + 4, (unsigned long long)nNode);
 }
 
-template <bool OCCLUDED, bool COUNT>
-RT_DEV void query_rays_body(const DevScene& sc, const QueryRays& q, int32_t* s_stack) {
+// ---- the scheduling every query family shares.  A lane state L carries the one record a lane has in flight:
+//   L(sc, q, s_stack)                          what a thread keeps for the whole launch (the list queries' LDS planes)
+//   start(sc, q, i)                            loads record i and initialises; sc.rootRef, or kExit for a record answered without traversal
+//   visit<COUNT>(sc, cur, st, nBox, nNode)     one node visit (node_step / point_node_step)
+//   leaf<COUNT>(sc, q, cur, nTri)              one leaf's triangles against the state; true when the record is finished by it
+//   finish(sc, q, i)                           stores the answer; whether it counts as a hit
+// Three of them: RayLane<OCCLUDED> here, HitsLane further down, PointsLane in rt_points.h.  The compiler replaces a lane state by its
+// scalars (tools/kernel_resources.py shows the registers of the hand-written bodies these replaced, profiles/query/).
+
+// Persistent waves: one in-flight record per lane, idle lanes refilled from the wave's claimed chunk.
+template <class L, bool COUNT>
+RT_DEV void query_body(const DevScene& sc, const typename L::Query& q, int32_t* s_stack) {
     int32_t* lds = s_stack + threadIdx.x;
+    L l(sc, q, s_stack);
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t total = q.count;
     // work distribution of trace_rays_body: static chunks per wave, then guided claims from the shared head
@@ -66,9 +78,7 @@ RT_DEV void query_rays_body(const DevScene& sc, const QueryRays& q, int32_t* s_s
     const uint32_t first = share < want1 ? (share < 16u ? 16u : share) : want1;
     const uint32_t dynBase = nWaves * first;
     const bool hasDyn = dynBase < total;
-    // (the origin lives in pk only: a separate copy of it costs three registers across the loop, and the closest-hit kernel spills)
-    f3 d = splat3(0.0f); RayPk pk = make_raypk(d, 1.0f, 1.0f, 1.0f);
-    float tmin = 0.0f, best = 0.0f, cut = 0.0f, hu = 0.0f, hv = 0.0f; uint32_t task = 0; int32_t cur = kExit, hitTri = -1; int top = 0;
+    uint32_t task = 0; int32_t cur = kExit; int top = 0;
     uint32_t nBox = 0, nTri = 0, nNode = 0;
     bool active = false;
     bool more = total != 0u;
@@ -92,15 +102,9 @@ RT_DEV void query_rays_body(const DevScene& sc, const QueryRays& q, int32_t* s_s
             more = chunkNext < chunkEnd || (hasDyn && chunkEnd < total);
             if (!active && slot < chunkEnd) {
                 task = slot;
-                const float4 r0 = q.rays[(size_t)task * 2], r1 = q.rays[(size_t)task * 2 + 1];
-                const f3 o = mk3(r0.x, r0.y, r0.z); d = mk3(r1.x, r1.y, r1.z); tmin = r0.w;
-                pk = make_raypk(o, safe_inv(d.x), safe_inv(d.y), safe_inv(d.z));
-                best = OCCLUDED ? r1.w : query_start(r1.w);
-                cut = best * 1.000001f;
-                hitTri = -1; hu = 0.0f; hv = 0.0f;
                 if (COUNT) { nBox = 0; nTri = 0; nNode = 0; }
                 top = 0; lane_push(lds, top, kExit);
-                cur = (sc.triCount == 0 || query_invalid(o, d, tmin, r1.w)) ? kExit : sc.rootRef;
+                cur = l.start(sc, q, task);
                 active = true;
             }
         }
@@ -109,26 +113,13 @@ RT_DEV void query_rays_body(const DevScene& sc, const QueryRays& q, int32_t* s_s
             bool walk = active && cur >= 0;
             const uint32_t quorum = quorum_of(sc.nodeQuorum, (uint32_t)__popcll(__ballot(active)));
             while (walk) {
-                { Stack st; st.lds = lds; st.top = top; cur = node_step<COUNT>(sc.nodes, sc.stackBudget, cur, pk, cut, st, nBox, nNode); top = st.top; }
+                { Stack st; st.lds = lds; st.top = top; cur = l.template visit<COUNT>(sc, cur, st, nBox, nNode); top = st.top; }
                 walk = cur >= 0;
                 if ((uint32_t)__popcll(__ballot(walk)) < quorum) break;
             }
-            if (active && cur < 0 && cur != kExit) {
-                const uint32_t code = (uint32_t)~cur, firstTri = code >> 2, cnt = (code & 3u) + 1u;
-                bool done = false;
-                for (uint32_t k = 0; k < cnt; ++k) {
-                    float t, u, v; uint32_t id;
-                    if (COUNT) nTri += 1;
-                    if (!tri_test(sc.leafTris + (size_t)(firstTri + k) * 3, mk3(pk.ox, pk.oy, pk.oz), d, t, u, v, id) || !(t > tmin) || !(t < best)) continue;
-                    hitTri = (int32_t)id;
-                    if (OCCLUDED) { done = true; break; }
-                    best = t; cut = t * 1.000001f; hu = u; hv = v;
-                }
-                cur = done ? kExit : lane_pop(lds, top);
-            }
+            if (active && cur < 0 && cur != kExit) cur = l.template leaf<COUNT>(sc, q, cur, nTri) ? kExit : lane_pop(lds, top);
             if (active && cur == kExit) {
-                store_query_result<OCCLUDED>(sc, q, task, mk3(pk.ox, pk.oy, pk.oz), d, best, hu, hv, hitTri);
-                count_query_ray<COUNT>(sc, nBox, nTri, nNode, hitTri >= 0);
+                count_query_ray<COUNT>(sc, nBox, nTri, nNode, l.finish(sc, q, task));
                 active = false;
             }
             const unsigned long long act = __ballot(active);
@@ -138,70 +129,90 @@ RT_DEV void query_rays_body(const DevScene& sc, const QueryRays& q, int32_t* s_s
     }
 }
 
-template <bool OCCLUDED, bool COUNT> __global__ void k_query_rays(DevScene sc, QueryRays q);
-template <> __global__ __launch_bounds__(kBlock) RT_TRACE_WAVES void k_query_rays<false, false>(DevScene sc, QueryRays q) {
-    extern __shared__ int32_t s_stack[];                         // (stackBudget + 1) entries x kBlock threads, sized at launch
-    query_rays_body<false, false>(sc, q, s_stack);
-}
-template <> __global__ __launch_bounds__(kBlock) RT_TRACE_WAVES void k_query_rays<true, false>(DevScene sc, QueryRays q) {
-    extern __shared__ int32_t s_stack[];
-    query_rays_body<true, false>(sc, q, s_stack);
-}
-template <> __global__ __launch_bounds__(kBlock) void k_query_rays<false, true>(DevScene sc, QueryRays q) {   // instrumented: no register cap
-    extern __shared__ int32_t s_stack[];
-    query_rays_body<false, true>(sc, q, s_stack);
-}
-template <> __global__ __launch_bounds__(kBlock) void k_query_rays<true, true>(DevScene sc, QueryRays q) {
-    extern __shared__ int32_t s_stack[];
-    query_rays_body<true, true>(sc, q, s_stack);
-}
-
-// One thread per ray: the interval form of trace_closest (or its any-hit variant), same traversal core.
-template <bool OCCLUDED, bool COUNT>
-RT_DEV void query_one(const DevScene& sc, const QueryRays& q, uint32_t i, int32_t* ldsBase) {
-    const float4 r0 = q.rays[(size_t)i * 2], r1 = q.rays[(size_t)i * 2 + 1];
-    const f3 o = mk3(r0.x, r0.y, r0.z), d = mk3(r1.x, r1.y, r1.z);
-    const float tmin = r0.w;
-    float best = OCCLUDED ? r1.w : query_start(r1.w), cut = best * 1.000001f, hu = 0.0f, hv = 0.0f;
-    int32_t hitTri = -1;
-    uint32_t nBox = 0, nTri = 0, nNode = 0;
-    if (!(sc.triCount == 0 || query_invalid(o, d, tmin, r1.w))) {
-        const RayPk pk = make_raypk(o, safe_inv(d.x), safe_inv(d.y), safe_inv(d.z));
-        Stack st; st.lds = ldsBase; st.top = 0; st.push(kExit);
-        int32_t cur = sc.rootRef;
-        bool done = false;
-        while (!done) {
+// One thread per record, grid-stride: the interval form of trace_closest around the same lane states.
+template <class L, bool COUNT>
+RT_DEV void query_simple_body(const DevScene& sc, const typename L::Query& q, int32_t* s_stack) {
+    L l(sc, q, s_stack);
+    for (uint32_t base = blockIdx.x * (uint32_t)kBlock; base < q.count; base += gridDim.x * (uint32_t)kBlock) {   // (block-uniform trips: the node visit's ballots see whole waves)
+        const uint32_t i = base + threadIdx.x;
+        if (i >= q.count) continue;
+        uint32_t nBox = 0, nTri = 0, nNode = 0;
+        Stack st; st.lds = s_stack + threadIdx.x; st.top = 0; st.push(kExit);
+        int32_t cur = l.start(sc, q, i);
+        while (cur != kExit) {
             bool walk = cur >= 0;
             const uint32_t quorum = quorum_of(sc.nodeQuorum, (uint32_t)__popcll(__ballot(true)));
             while (walk) {
-                cur = node_step<COUNT>(sc.nodes, sc.stackBudget, cur, pk, cut, st, nBox, nNode);
+                cur = l.template visit<COUNT>(sc, cur, st, nBox, nNode);
                 walk = cur >= 0;
                 if ((uint32_t)__popcll(__ballot(walk)) < quorum) break;
             }
-            if (cur >= 0) continue;
-            if (cur == kExit) break;
-            const uint32_t code = (uint32_t)~cur, firstTri = code >> 2, cnt = (code & 3u) + 1u;
-            for (uint32_t k = 0; k < cnt; ++k) {
-                float t, u, v; uint32_t id;
-                if (COUNT) nTri += 1;
-                if (!tri_test(sc.leafTris + (size_t)(firstTri + k) * 3, o, d, t, u, v, id) || !(t > tmin) || !(t < best)) continue;
-                hitTri = (int32_t)id;
-                if (OCCLUDED) { done = true; break; }
-                best = t; cut = t * 1.000001f; hu = u; hv = v;
-            }
-            cur = st.pop();
+            if (cur >= 0 || cur == kExit) continue;
+            cur = l.template leaf<COUNT>(sc, q, cur, nTri) ? kExit : st.pop();
         }
+        count_query_ray<COUNT>(sc, nBox, nTri, nNode, l.finish(sc, q, i));
     }
-    store_query_result<OCCLUDED>(sc, q, i, o, d, best, hu, hv, hitTri);
-    count_query_ray<COUNT>(sc, nBox, nTri, nNode, hitTri >= 0);
+}
+
+// The closest-hit / occlusion lane state
+template <bool OCCLUDED> struct RayLane {
+    using Query = QueryRays;
+    // (the origin lives in pk only: a separate copy of it costs three registers across the loop, and the closest-hit kernel spills)
+    f3 d = splat3(0.0f); RayPk pk = make_raypk(d, 1.0f, 1.0f, 1.0f);
+    float tmin = 0.0f, best = 0.0f, cut = 0.0f, hu = 0.0f, hv = 0.0f; int32_t hitTri = -1;
+    RT_DEV RayLane(const DevScene&, const QueryRays&, int32_t*) {}
+    // a refill is two 16-byte loads and three reciprocals
+    RT_DEV int32_t start(const DevScene& sc, const QueryRays& q, uint32_t i) {
+        const float4 r0 = q.rays[(size_t)i * 2], r1 = q.rays[(size_t)i * 2 + 1];
+        const f3 o = mk3(r0.x, r0.y, r0.z); d = mk3(r1.x, r1.y, r1.z); tmin = r0.w;
+        pk = make_raypk(o, safe_inv(d.x), safe_inv(d.y), safe_inv(d.z));
+        best = OCCLUDED ? r1.w : query_start(r1.w);
+        cut = best * 1.000001f;
+        hitTri = -1; hu = 0.0f; hv = 0.0f;
+        return (sc.triCount == 0 || query_invalid(o, d, tmin, r1.w)) ? kExit : sc.rootRef;
+    }
+    template <bool COUNT> RT_DEV int32_t visit(const DevScene& sc, int32_t cur, Stack& st, uint32_t& nBox, uint32_t& nNode) {
+        return node_step<COUNT>(sc.nodes, sc.stackBudget, cur, pk, cut, st, nBox, nNode);
+    }
+    template <bool COUNT> RT_DEV bool leaf(const DevScene& sc, const QueryRays&, int32_t cur, uint32_t& nTri) {
+        const uint32_t code = (uint32_t)~cur, firstTri = code >> 2, cnt = (code & 3u) + 1u;
+        for (uint32_t k = 0; k < cnt; ++k) {
+            float t, u, v; uint32_t id;
+            if (COUNT) nTri += 1;
+            if (!tri_test(sc.leafTris + (size_t)(firstTri + k) * 3, mk3(pk.ox, pk.oy, pk.oz), d, t, u, v, id) || !(t > tmin) || !(t < best)) continue;
+            hitTri = (int32_t)id;
+            if (OCCLUDED) return true;
+            best = t; cut = t * 1.000001f; hu = u; hv = v;
+        }
+        return false;
+    }
+    RT_DEV bool finish(const DevScene& sc, const QueryRays& q, uint32_t i) {
+        store_query_result<OCCLUDED>(sc, q, i, mk3(pk.ox, pk.oy, pk.oz), d, best, hu, hv, hitTri);
+        return hitTri >= 0;
+    }
+};
+
+template <bool OCCLUDED, bool COUNT> __global__ void k_query_rays(DevScene sc, QueryRays q);
+template <> __global__ __launch_bounds__(kBlock) RT_TRACE_WAVES void k_query_rays<false, false>(DevScene sc, QueryRays q) {
+    extern __shared__ int32_t s_stack[];                         // (stackBudget + 1) entries x kBlock threads, sized at launch
+    query_body<RayLane<false>, false>(sc, q, s_stack);
+}
+template <> __global__ __launch_bounds__(kBlock) RT_TRACE_WAVES void k_query_rays<true, false>(DevScene sc, QueryRays q) {
+    extern __shared__ int32_t s_stack[];
+    query_body<RayLane<true>, false>(sc, q, s_stack);
+}
+template <> __global__ __launch_bounds__(kBlock) void k_query_rays<false, true>(DevScene sc, QueryRays q) {   // instrumented: no register cap
+    extern __shared__ int32_t s_stack[];
+    query_body<RayLane<false>, true>(sc, q, s_stack);
+}
+template <> __global__ __launch_bounds__(kBlock) void k_query_rays<true, true>(DevScene sc, QueryRays q) {
+    extern __shared__ int32_t s_stack[];
+    query_body<RayLane<true>, true>(sc, q, s_stack);
 }
 template <bool OCCLUDED, bool COUNT>
 __global__ __launch_bounds__(kBlock) void k_query_rays_simple(DevScene sc, QueryRays q) {
     extern __shared__ int32_t s_stack[];                         // (stackBudget + 1) entries x kBlock threads, sized at launch
-    for (uint32_t base = blockIdx.x * (uint32_t)kBlock; base < q.count; base += gridDim.x * (uint32_t)kBlock) {   // (block-uniform trips: node_step's ballots see whole waves)
-        const uint32_t j = base + threadIdx.x;
-        if (j < q.count) query_one<OCCLUDED, COUNT>(sc, q, j, s_stack + threadIdx.x);
-    }
+    query_simple_body<RayLane<OCCLUDED>, COUNT>(sc, q, s_stack);
 }
 
 // ============================================================ multi-hit queries (fyprt_trace_ray_hits*): the K nearest hits per ray
@@ -288,83 +299,33 @@ RT_DEV void store_hits(const QueryHits& q, const HitList& l, uint32_t i, uint32_
     if (q.counts) q.counts[i] = n;
 }
 
-// Persistent waves: the scheduling of query_rays_body (refill, guided claims, node-loop quorum), the per-ray state of the list instead
-// of the closest hit's.
-template <bool COUNT>
-RT_DEV void query_hits_body(const DevScene& sc, const QueryHits& q, int32_t* s_stack) {
-    int32_t* lds = s_stack + threadIdx.x;
-    const HitList list = hit_list(s_stack, sc.stackBudget, q.maxHits);
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t total = q.count;
-    const uint32_t nWaves = gridDim.x * (uint32_t)(kBlock / 64), myWave = blockIdx.x * (uint32_t)(kBlock / 64) + (threadIdx.x >> 6);
-    const uint32_t share = (total + nWaves - 1u) / nWaves;
-    const uint32_t chunk = q.chunk, want1 = chunk * q.staticChunks;
-    const uint32_t first = share < want1 ? (share < 16u ? 16u : share) : want1;
-    const uint32_t dynBase = nWaves * first;
-    const bool hasDyn = dynBase < total;
+// The multi-hit lane state: the ray, and the list's length, worst key and `after` key in registers
+struct HitsLane {
+    using Query = QueryHits;
+    const HitList list;
     f3 d = splat3(0.0f); RayPk pk = make_raypk(d, 1.0f, 1.0f, 1.0f);
-    float tmin = 0.0f, hi = 0.0f, cut = 0.0f; uint32_t task = 0, n = 0; int32_t cur = kExit; int top = 0;
+    float tmin = 0.0f, hi = 0.0f, cut = 0.0f; uint32_t n = 0;
     unsigned long long worst = kNoWorstKey, afterKey = 0ull;
-    uint32_t nBox = 0, nTri = 0, nNode = 0;
-    bool active = false;
-    bool more = total != 0u;
-    uint32_t chunkNext = myWave * first < total ? myWave * first : total;
-    uint32_t chunkEnd = (myWave + 1u) * first < total ? (myWave + 1u) * first : total;
-    while (true) {
-        const unsigned long long idle = __ballot(!active);
-        if (more && (uint32_t)__popcll(idle) >= q.refillLanes) {
-            if (chunkNext >= chunkEnd && hasDyn) {
-                uint32_t base = 0;
-                uint32_t size = (total - chunkEnd) / nWaves;
-                size = size < q.minChunk ? q.minChunk : (size > chunk ? chunk : size);
-                if (lane == 0u) base = dynBase + atomicAdd(q.head, size);
-                base = (uint32_t)__shfl((int)base, 0);
-                chunkNext = base < total ? base : total;
-                chunkEnd = (base + size < total) ? base + size : total;
-            }
-            const uint32_t slot = chunkNext + (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
-            const uint32_t want = (uint32_t)__popcll(idle), avail = chunkEnd - chunkNext;
-            chunkNext += (want < avail) ? want : avail;
-            more = chunkNext < chunkEnd || (hasDyn && chunkEnd < total);
-            if (!active && slot < chunkEnd) {
-                task = slot;
-                const float4 r0 = q.rays[(size_t)task * 2], r1 = q.rays[(size_t)task * 2 + 1];
-                const f3 o = mk3(r0.x, r0.y, r0.z); d = mk3(r1.x, r1.y, r1.z); tmin = r0.w;
-                pk = make_raypk(o, safe_inv(d.x), safe_inv(d.y), safe_inv(d.z));
-                hi = query_start(r1.w);
-                cut = hi * 1.000001f;
-                n = 0; worst = kNoWorstKey;
-                if (COUNT) { nBox = 0; nTri = 0; nNode = 0; }
-                top = 0; lane_push(lds, top, kExit);
-                const bool wanted = hits_start(q, task, afterKey);
-                cur = (sc.triCount == 0 || !wanted || query_invalid(o, d, tmin, r1.w)) ? kExit : sc.rootRef;
-                active = true;
-            }
-        }
-        if (__ballot(active) == 0ull) { if (!more) break; else continue; }
-        while (true) {
-            bool walk = active && cur >= 0;
-            const uint32_t quorum = quorum_of(sc.nodeQuorum, (uint32_t)__popcll(__ballot(active)));
-            while (walk) {
-                { Stack st; st.lds = lds; st.top = top; cur = node_step<COUNT>(sc.nodes, sc.stackBudget, cur, pk, cut, st, nBox, nNode); top = st.top; }
-                walk = cur >= 0;
-                if ((uint32_t)__popcll(__ballot(walk)) < quorum) break;
-            }
-            if (active && cur < 0 && cur != kExit) {
-                cut = hits_leaf(sc, list, q.maxHits, cur, mk3(pk.ox, pk.oy, pk.oz), d, tmin, hi, afterKey, n, worst, cut, nTri, COUNT);
-                cur = lane_pop(lds, top);
-            }
-            if (active && cur == kExit) {
-                store_hits(q, list, task, n);
-                count_query_ray<COUNT>(sc, nBox, nTri, nNode, n != 0u);
-                active = false;
-            }
-            const unsigned long long act = __ballot(active);
-            if (act == 0ull) break;
-            if (more && (64u - (uint32_t)__popcll(act)) >= q.refillLanes) break;
-        }
+    RT_DEV HitsLane(const DevScene& sc, const QueryHits& q, int32_t* s_stack) : list(hit_list(s_stack, sc.stackBudget, q.maxHits)) {}
+    RT_DEV int32_t start(const DevScene& sc, const QueryHits& q, uint32_t i) {
+        const float4 r0 = q.rays[(size_t)i * 2], r1 = q.rays[(size_t)i * 2 + 1];
+        const f3 o = mk3(r0.x, r0.y, r0.z); d = mk3(r1.x, r1.y, r1.z); tmin = r0.w;
+        pk = make_raypk(o, safe_inv(d.x), safe_inv(d.y), safe_inv(d.z));
+        hi = query_start(r1.w);
+        cut = hi * 1.000001f;
+        n = 0; worst = kNoWorstKey;
+        const bool wanted = hits_start(q, i, afterKey);
+        return (sc.triCount == 0 || !wanted || query_invalid(o, d, tmin, r1.w)) ? kExit : sc.rootRef;
     }
-}
+    template <bool COUNT> RT_DEV int32_t visit(const DevScene& sc, int32_t cur, Stack& st, uint32_t& nBox, uint32_t& nNode) {
+        return node_step<COUNT>(sc.nodes, sc.stackBudget, cur, pk, cut, st, nBox, nNode);
+    }
+    template <bool COUNT> RT_DEV bool leaf(const DevScene& sc, const QueryHits& q, int32_t cur, uint32_t& nTri) {
+        cut = hits_leaf(sc, list, q.maxHits, cur, mk3(pk.ox, pk.oy, pk.oz), d, tmin, hi, afterKey, n, worst, cut, nTri, COUNT);
+        return false;
+    }
+    RT_DEV bool finish(const DevScene&, const QueryHits& q, uint32_t i) { store_hits(q, list, i, n); return n != 0u; }
+};
 
 template <bool COUNT> __global__ void k_query_hits(DevScene sc, QueryHits q);
 // Compiled for 5 waves per SIMD (96 VGPRs, 12 B of scratch as k_query_rays<false, false>), not the 6 of RT_TRACE_WAVES (80 VGPRs, 20 B: the
@@ -372,52 +333,17 @@ template <bool COUNT> __global__ void k_query_hits(DevScene sc, QueryHits q);
 // workgroups per CU from a 26-entry stack on (26 x 4 + 16 B per thread = 30 KB), so the sixth wave would be bought for small trees only.
 template <> __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5))) void k_query_hits<false>(DevScene sc, QueryHits q) {
     extern __shared__ int32_t s_stack[];                         // (stackBudget + 1) x 4 B + maxHits x 16 B per thread, sized at launch
-    query_hits_body<false>(sc, q, s_stack);
+    query_body<HitsLane, false>(sc, q, s_stack);
 }
 template <> __global__ __launch_bounds__(kBlock) void k_query_hits<true>(DevScene sc, QueryHits q) {          // instrumented: no register cap
     extern __shared__ int32_t s_stack[];
-    query_hits_body<true>(sc, q, s_stack);
+    query_body<HitsLane, true>(sc, q, s_stack);
 }
 
-// One thread per ray, as query_one
-template <bool COUNT>
-RT_DEV void query_hits_one(const DevScene& sc, const QueryHits& q, uint32_t i, int32_t* ldsBase, const HitList& list) {
-    const float4 r0 = q.rays[(size_t)i * 2], r1 = q.rays[(size_t)i * 2 + 1];
-    const f3 o = mk3(r0.x, r0.y, r0.z), d = mk3(r1.x, r1.y, r1.z);
-    const float tmin = r0.w, hi = query_start(r1.w);
-    float cut = hi * 1.000001f;
-    uint32_t n = 0; unsigned long long worst = kNoWorstKey, afterKey;
-    uint32_t nBox = 0, nTri = 0, nNode = 0;
-    const bool wanted = hits_start(q, i, afterKey);
-    if (!(sc.triCount == 0 || !wanted || query_invalid(o, d, tmin, r1.w))) {
-        const RayPk pk = make_raypk(o, safe_inv(d.x), safe_inv(d.y), safe_inv(d.z));
-        Stack st; st.lds = ldsBase; st.top = 0; st.push(kExit);
-        int32_t cur = sc.rootRef;
-        while (true) {
-            bool walk = cur >= 0;
-            const uint32_t quorum = quorum_of(sc.nodeQuorum, (uint32_t)__popcll(__ballot(true)));
-            while (walk) {
-                cur = node_step<COUNT>(sc.nodes, sc.stackBudget, cur, pk, cut, st, nBox, nNode);
-                walk = cur >= 0;
-                if ((uint32_t)__popcll(__ballot(walk)) < quorum) break;
-            }
-            if (cur >= 0) continue;
-            if (cur == kExit) break;
-            cut = hits_leaf(sc, list, q.maxHits, cur, o, d, tmin, hi, afterKey, n, worst, cut, nTri, COUNT);
-            cur = st.pop();
-        }
-    }
-    store_hits(q, list, i, n);
-    count_query_ray<COUNT>(sc, nBox, nTri, nNode, n != 0u);
-}
 template <bool COUNT>
 __global__ __launch_bounds__(kBlock) void k_query_hits_simple(DevScene sc, QueryHits q) {
     extern __shared__ int32_t s_stack[];                         // (stackBudget + 1) x 4 B + maxHits x 16 B per thread, sized at launch
-    const HitList list = hit_list(s_stack, sc.stackBudget, q.maxHits);
-    for (uint32_t base = blockIdx.x * (uint32_t)kBlock; base < q.count; base += gridDim.x * (uint32_t)kBlock) {   // (block-uniform trips: node_step's ballots see whole waves)
-        const uint32_t j = base + threadIdx.x;
-        if (j < q.count) query_hits_one<COUNT>(sc, q, j, s_stack + threadIdx.x, list);
-    }
+    query_simple_body<HitsLane, COUNT>(sc, q, s_stack);
 }
 
 // ============================================================ radiance queries (fyprt_render_rays*): the primary pass
