@@ -1,7 +1,9 @@
 """the device builders (tuning key 12; rt_lbvh.h): 1 = Morton sort + Karras radix tree, 2 = Morton sort + PLOC
 (parallel locally-ordered clustering), both followed by the wide collapse + refit.
 Same bars as for the host builder: structural invariants of the exported tree, bit-exact parity against the oracle traversing
-that exported tree, and the same picture as the host-built tree except for exact-t ties."""
+that exported tree, and the same picture as the host-built tree except for exact-t ties.
+Any valid tree passes these bars; WHICH tree the builders make (key, order, radix / PLOC tree, collapse, quantisation bytes) is held
+to a numpy restatement in test_gpu_builder_ref.py."""
 import numpy as np
 import pytest
 
