@@ -462,6 +462,40 @@ def make_camera_desc(cam) -> CameraDesc:
     return c
 
 
+def _denoise_blocking(owner, ctx, fn, args, scale, want_radiance, third, want_third):
+    """The blocking form of a denoiser call of `owner` (a Context or a Group: its library, handle and _check): entry `fn` with `args`,
+    then host outputs of `scale` times `ctx`'s frame (None: the frame itself), then `third` — a FrameStats, always passed, or a
+    band_ms array, passed when wanted.  Returns (image, radiance or None) reshaped, with `want_third` also the stats / the list of ms."""
+    s = scale or 1
+    h, w = ctx.height * s, ctx.width * s
+    n = max(h * w, 1) if scale else h * w
+    img = np.empty(n, dtype=np.uint32)
+    rad = np.empty((n, 4), dtype=np.float32) if want_radiance else None
+    stats = isinstance(third, FrameStats)
+    owner._check(getattr(owner.lib, fn)(owner.h, *args, _ptr(img), _ptr(rad), C.byref(third) if stats else third if want_third else None))
+    out = (img.reshape(h, w), rad.reshape(h, w, 4) if want_radiance else None)
+    return out + (third if stats else list(third),) if want_third else out
+
+
+def _denoise_tensor(owner, ctx, gpu, who, fn, args, scale, image_tensor, radiance_tensor):
+    """The device form of a denoiser call of `owner`: entry `fn` with `args`, then the output tensors, which are checked against `scale`
+    times the frame of `ctx` and its GPU (`gpu`: what the message calls it), on ctx's stream (Context._on_context_stream)."""
+    import torch
+    if image_tensor is None and radiance_tensor is None:
+        raise ValueError(f"{who}: at least one output tensor is needed")
+    h, w = ctx.height * scale, ctx.width * scale
+    for t, dt, shape, name in ((image_tensor, torch.int32, (h, w), "image_tensor"), (radiance_tensor, torch.float32, (h, w, 4), "radiance_tensor")):
+        if t is None:
+            continue
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous {dt} tensor of shape {shape}")
+        if t.device.type != "cuda" or (t.device.index if t.device.index is not None else torch.cuda.current_device()) != ctx.device:
+            raise ValueError(f"{who}: {name} must be on cuda:{ctx.device}, {gpu}")
+    with ctx._on_context_stream((image_tensor if image_tensor is not None else radiance_tensor).device):
+        owner._check(getattr(owner.lib, fn)(owner.h, *args, C.c_void_p(image_tensor.data_ptr()) if image_tensor is not None else None,
+                                            C.c_void_p(radiance_tensor.data_ptr()) if radiance_tensor is not None else None))
+
+
 class Context:
     """One renderer context on one GPU — the Python face of the reference's `Renderer`
     (Renderer.h:41-56): resize / upload_scene / set_camera / render / readback."""
@@ -984,73 +1018,26 @@ class Context:
         (image H x W uint32 ABGR8, radiance H x W x 4 float32 or None without `want_radiance`), with `with_stats` also the FrameStats of
         the call.  No frame state moves; read_buffer(BUF_ALBEDO) afterwards gives the albedo guide of that frame."""
         p = params if params is not None else DenoiseParams()
-        n = self.width * self.height
-        img = np.empty(n, dtype=np.uint32)
-        rad = np.empty((n, 4), dtype=np.float32) if want_radiance else None
-        st = FrameStats()
-        self._check(self.lib.fyprt_denoise(self.h, C.byref(p), _ptr(img), _ptr(rad), C.byref(st)))
-        out = (img.reshape(self.height, self.width), rad.reshape(self.height, self.width, 4) if want_radiance else None)
-        return out + (st,) if with_stats else out
+        return _denoise_blocking(self, self, "fyprt_denoise", (C.byref(p),), None, want_radiance, FrameStats(), with_stats)
 
     def denoise_tensor(self, image_tensor, radiance_tensor, params: DenoiseParams | None = None):
         """Denoise into device tensors (fyprt_denoise_device): `image_tensor` a contiguous int32 (H, W) tensor or None, `radiance_tensor`
         a contiguous float32 (H, W, 4) tensor or None, on this context's GPU.  Ordered against torch's current stream as
         trace_rays_tensor is, without a host synchronisation and without record_stream."""
-        import torch
         p = params if params is not None else DenoiseParams()
-        if image_tensor is None and radiance_tensor is None:
-            raise ValueError("denoise_tensor: at least one output tensor is needed")
-        for t, dt, shape, name in ((image_tensor, torch.int32, (self.height, self.width), "image_tensor"),
-                                   (radiance_tensor, torch.float32, (self.height, self.width, 4), "radiance_tensor")):
-            if t is None:
-                continue
-            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError(f"denoise_tensor: {name} must be a contiguous {dt} tensor of shape {shape}")
-            if t.device.type != "cuda" or (t.device.index if t.device.index is not None else torch.cuda.current_device()) != self.device:
-                raise ValueError(f"denoise_tensor: {name} must be on cuda:{self.device}, the context's GPU")
-        dev = (image_tensor if image_tensor is not None else radiance_tensor).device
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
-        ext.wait_stream(cur)                                           # the outputs are allocated (and their earlier uses done) before the kernels run
-        self._check(self.lib.fyprt_denoise_device(self.h, C.byref(p), C.c_void_p(image_tensor.data_ptr()) if image_tensor is not None else None,
-                                                  C.c_void_p(radiance_tensor.data_ptr()) if radiance_tensor is not None else None))
-        cur.wait_stream(ext)                                           # torch's later work follows the denoiser
+        _denoise_tensor(self, self, "the context's GPU", "denoise_tensor", "fyprt_denoise_device", (C.byref(p),), 1, image_tensor, radiance_tensor)
 
     def denoise_temporal(self, params: TemporalParams | None = None, want_radiance=True, with_stats=False):
         """Temporal denoise of the frame rendered last (fyprt_denoise_temporal, blocking; defaults when `params` is None): reprojected
         history, per-pixel variance, variance-guided a-trous.  Returns as denoise() does.  No frame state moves; the context's history
         advances (read_buffer(BUF_TEMPORAL) gives the record written, denoise_temporal_reset() drops it)."""
         p = params if params is not None else TemporalParams()
-        n = self.width * self.height
-        img = np.empty(n, dtype=np.uint32)
-        rad = np.empty((n, 4), dtype=np.float32) if want_radiance else None
-        st = FrameStats()
-        self._check(self.lib.fyprt_denoise_temporal(self.h, C.byref(p), _ptr(img), _ptr(rad), C.byref(st)))
-        out = (img.reshape(self.height, self.width), rad.reshape(self.height, self.width, 4) if want_radiance else None)
-        return out + (st,) if with_stats else out
+        return _denoise_blocking(self, self, "fyprt_denoise_temporal", (C.byref(p),), None, want_radiance, FrameStats(), with_stats)
 
     def denoise_temporal_tensor(self, image_tensor, radiance_tensor, params: TemporalParams | None = None):
         """denoise_temporal into device tensors (fyprt_denoise_temporal_device); tensors and stream ordering exactly as denoise_tensor."""
-        import torch
         p = params if params is not None else TemporalParams()
-        if image_tensor is None and radiance_tensor is None:
-            raise ValueError("denoise_temporal_tensor: at least one output tensor is needed")
-        for t, dt, shape, name in ((image_tensor, torch.int32, (self.height, self.width), "image_tensor"),
-                                   (radiance_tensor, torch.float32, (self.height, self.width, 4), "radiance_tensor")):
-            if t is None:
-                continue
-            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError(f"denoise_temporal_tensor: {name} must be a contiguous {dt} tensor of shape {shape}")
-            if t.device.type != "cuda" or (t.device.index if t.device.index is not None else torch.cuda.current_device()) != self.device:
-                raise ValueError(f"denoise_temporal_tensor: {name} must be on cuda:{self.device}, the context's GPU")
-        dev = (image_tensor if image_tensor is not None else radiance_tensor).device
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
-        ext.wait_stream(cur)                                           # the outputs are allocated (and their earlier uses done) before the kernels run
-        self._check(self.lib.fyprt_denoise_temporal_device(self.h, C.byref(p),
-                                                           C.c_void_p(image_tensor.data_ptr()) if image_tensor is not None else None,
-                                                           C.c_void_p(radiance_tensor.data_ptr()) if radiance_tensor is not None else None))
-        cur.wait_stream(ext)                                           # torch's later work follows the denoiser
+        _denoise_tensor(self, self, "the context's GPU", "denoise_temporal_tensor", "fyprt_denoise_temporal_device", (C.byref(p),), 1, image_tensor, radiance_tensor)
 
     def denoise_upscale(self, params: UpscaleParams | None = None, want_radiance=True, with_stats=False):
         """Denoise the frame rendered last at its own size and present it at scale x that size (fyprt_denoise_upscale, blocking; defaults
@@ -1059,41 +1046,16 @@ class Context:
         float32 or None), with `with_stats` also the FrameStats.  read_buffer(BUF_UPSCALE_GUIDE / BUF_UPSCALE_ALBEDO) afterwards gives the
         hi-res records (sH * sW of them)."""
         p = params if params is not None else UpscaleParams()
-        s = int(p.scale)
-        h, w = self.height * s, self.width * s
-        img = np.empty(max(h * w, 1), dtype=np.uint32)
-        rad = np.empty((max(h * w, 1), 4), dtype=np.float32) if want_radiance else None
-        st = FrameStats()
-        self._check(self.lib.fyprt_denoise_upscale(self.h, C.byref(p), _ptr(img), _ptr(rad), C.byref(st)))
-        self._upscale = s
-        out = (img.reshape(h, w), rad.reshape(h, w, 4) if want_radiance else None)
-        return out + (st,) if with_stats else out
+        out = _denoise_blocking(self, self, "fyprt_denoise_upscale", (C.byref(p),), int(p.scale), want_radiance, FrameStats(), with_stats)
+        self._upscale = int(p.scale)
+        return out
 
     def denoise_upscale_tensor(self, image_tensor, radiance_tensor, params: UpscaleParams | None = None):
         """denoise_upscale into device tensors of the hi-res size (fyprt_denoise_upscale_device): int32 (sH, sW) / float32 (sH, sW, 4);
         stream ordering exactly as denoise_tensor."""
-        import torch
         p = params if params is not None else UpscaleParams()
-        s = int(p.scale)
-        if image_tensor is None and radiance_tensor is None:
-            raise ValueError("denoise_upscale_tensor: at least one output tensor is needed")
-        for t, dt, shape, name in ((image_tensor, torch.int32, (self.height * s, self.width * s), "image_tensor"),
-                                   (radiance_tensor, torch.float32, (self.height * s, self.width * s, 4), "radiance_tensor")):
-            if t is None:
-                continue
-            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError(f"denoise_upscale_tensor: {name} must be a contiguous {dt} tensor of shape {shape}")
-            if t.device.type != "cuda" or (t.device.index if t.device.index is not None else torch.cuda.current_device()) != self.device:
-                raise ValueError(f"denoise_upscale_tensor: {name} must be on cuda:{self.device}, the context's GPU")
-        dev = (image_tensor if image_tensor is not None else radiance_tensor).device
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(self.stream(), device=dev)
-        ext.wait_stream(cur)                                           # the outputs are allocated (and their earlier uses done) before the kernels run
-        self._check(self.lib.fyprt_denoise_upscale_device(self.h, C.byref(p),
-                                                          C.c_void_p(image_tensor.data_ptr()) if image_tensor is not None else None,
-                                                          C.c_void_p(radiance_tensor.data_ptr()) if radiance_tensor is not None else None))
-        self._upscale = s
-        cur.wait_stream(ext)                                           # torch's later work follows the upscaler
+        _denoise_tensor(self, self, "the context's GPU", "denoise_upscale_tensor", "fyprt_denoise_upscale_device", (C.byref(p),), int(p.scale), image_tensor, radiance_tensor)
+        self._upscale = int(p.scale)
 
     def denoise_temporal_reset(self):
         """Drops the temporal history (fyprt_denoise_temporal_reset): the next denoise_temporal* call behaves as a first call."""
@@ -1163,80 +1125,32 @@ class Group:
         defaults when `params` is None).  Returns (image H x W uint32 ABGR8, radiance H x W x 4 float32 or None without `want_radiance`)
         of the WHOLE frame, bit for bit a single context's; with `with_band_ms` also the per-band milliseconds of the call."""
         p = params if params is not None else DenoiseParams()
-        H, W = self.contexts[0].height, self.contexts[0].width
-        img = np.empty(W * H, dtype=np.uint32)
-        rad = np.empty((W * H, 4), dtype=np.float32) if want_radiance else None
-        ms = (C.c_float * len(self.contexts))()
-        self._check(self.lib.fyprt_group_denoise(self.h, C.byref(p), _ptr(img), _ptr(rad), ms if with_band_ms else None))
-        out = (img.reshape(H, W), rad.reshape(H, W, 4) if want_radiance else None)
-        return out + (list(ms),) if with_band_ms else out
+        return _denoise_blocking(self, self.contexts[0], "fyprt_group_denoise", (C.byref(p),), None, want_radiance, (C.c_float * len(self.contexts))(), with_band_ms)
+
+    def _denoise_tensor(self, who, fn, args, scale, root, image_tensor, radiance_tensor):
+        if not 0 <= root < len(self.contexts):
+            raise ValueError(f"{who}: root out of range")
+        _denoise_tensor(self, self.contexts[root], "the root context's GPU", who, fn, args + (root,), scale, image_tensor, radiance_tensor)
 
     def denoise_tensor(self, image_tensor, radiance_tensor, params: DenoiseParams | None = None, root=0):
         """Context.denoise_tensor for the group (fyprt_group_denoise_device): the tensors live on the GPU of context `root`, and the call
         is ordered against torch's current stream through that context's stream, without a host synchronisation."""
-        import torch
         p = params if params is not None else DenoiseParams()
-        if not 0 <= root < len(self.contexts):
-            raise ValueError("denoise_tensor: root out of range")
-        ctx = self.contexts[root]
-        if image_tensor is None and radiance_tensor is None:
-            raise ValueError("denoise_tensor: at least one output tensor is needed")
-        for t, dt, shape, name in ((image_tensor, torch.int32, (ctx.height, ctx.width), "image_tensor"),
-                                   (radiance_tensor, torch.float32, (ctx.height, ctx.width, 4), "radiance_tensor")):
-            if t is None:
-                continue
-            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError(f"denoise_tensor: {name} must be a contiguous {dt} tensor of shape {shape}")
-            if t.device.type != "cuda" or (t.device.index if t.device.index is not None else torch.cuda.current_device()) != ctx.device:
-                raise ValueError(f"denoise_tensor: {name} must be on cuda:{ctx.device}, the root context's GPU")
-        dev = (image_tensor if image_tensor is not None else radiance_tensor).device
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(ctx.stream(), device=dev)
-        ext.wait_stream(cur)                                           # the outputs are allocated (and their earlier uses done) before root writes them
-        self._check(self.lib.fyprt_group_denoise_device(self.h, C.byref(p), root,
-                                                        C.c_void_p(image_tensor.data_ptr()) if image_tensor is not None else None,
-                                                        C.c_void_p(radiance_tensor.data_ptr()) if radiance_tensor is not None else None))
-        cur.wait_stream(ext)                                           # torch's later work follows the collect
+        self._denoise_tensor("denoise_tensor", "fyprt_group_denoise_device", (C.byref(p),), 1, root, image_tensor, radiance_tensor)
 
     def denoise_temporal(self, params: TemporalParams | None = None, history_rows=GROUP_HISTORY_ROWS, want_radiance=True, with_band_ms=False):
         """Context.denoise_temporal for the frame the group rendered last (fyprt_group_denoise_temporal, blocking; defaults when `params`
         is None): every band reprojects into the group's history — its own rows and `history_rows` rows either side, the band's history
         window — and filters its rows.  Returns as denoise() does.  With history_rows >= height the sequence is a single context's."""
         p = params if params is not None else TemporalParams()
-        H, W = self.contexts[0].height, self.contexts[0].width
-        img = np.empty(W * H, dtype=np.uint32)
-        rad = np.empty((W * H, 4), dtype=np.float32) if want_radiance else None
-        ms = (C.c_float * len(self.contexts))()
-        self._check(self.lib.fyprt_group_denoise_temporal(self.h, C.byref(p), int(history_rows), _ptr(img), _ptr(rad), ms if with_band_ms else None))
-        out = (img.reshape(H, W), rad.reshape(H, W, 4) if want_radiance else None)
-        return out + (list(ms),) if with_band_ms else out
+        return _denoise_blocking(self, self.contexts[0], "fyprt_group_denoise_temporal", (C.byref(p), int(history_rows)), None, want_radiance,
+                                 (C.c_float * len(self.contexts))(), with_band_ms)
 
     def denoise_temporal_tensor(self, image_tensor, radiance_tensor, params: TemporalParams | None = None, history_rows=GROUP_HISTORY_ROWS, root=0):
         """denoise_temporal into device tensors on the GPU of context `root` (fyprt_group_denoise_temporal_device); tensors and stream
         ordering exactly as denoise_tensor."""
-        import torch
         p = params if params is not None else TemporalParams()
-        if not 0 <= root < len(self.contexts):
-            raise ValueError("denoise_temporal_tensor: root out of range")
-        ctx = self.contexts[root]
-        if image_tensor is None and radiance_tensor is None:
-            raise ValueError("denoise_temporal_tensor: at least one output tensor is needed")
-        for t, dt, shape, name in ((image_tensor, torch.int32, (ctx.height, ctx.width), "image_tensor"),
-                                   (radiance_tensor, torch.float32, (ctx.height, ctx.width, 4), "radiance_tensor")):
-            if t is None:
-                continue
-            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError(f"denoise_temporal_tensor: {name} must be a contiguous {dt} tensor of shape {shape}")
-            if t.device.type != "cuda" or (t.device.index if t.device.index is not None else torch.cuda.current_device()) != ctx.device:
-                raise ValueError(f"denoise_temporal_tensor: {name} must be on cuda:{ctx.device}, the root context's GPU")
-        dev = (image_tensor if image_tensor is not None else radiance_tensor).device
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(ctx.stream(), device=dev)
-        ext.wait_stream(cur)                                           # the outputs are allocated (and their earlier uses done) before root writes them
-        self._check(self.lib.fyprt_group_denoise_temporal_device(self.h, C.byref(p), int(history_rows), root,
-                                                                 C.c_void_p(image_tensor.data_ptr()) if image_tensor is not None else None,
-                                                                 C.c_void_p(radiance_tensor.data_ptr()) if radiance_tensor is not None else None))
-        cur.wait_stream(ext)                                           # torch's later work follows the collect
+        self._denoise_tensor("denoise_temporal_tensor", "fyprt_group_denoise_temporal_device", (C.byref(p), int(history_rows)), 1, root, image_tensor, radiance_tensor)
 
     def denoise_upscale(self, params: UpscaleParams | None = None, history_rows=GROUP_HISTORY_ROWS, want_radiance=True, with_band_ms=False):
         """Context.denoise_upscale for the frame the group rendered last (fyprt_group_denoise_upscale, blocking; defaults when `params` is
@@ -1245,46 +1159,19 @@ class Group:
         WHOLE frame, with `with_band_ms` also the per-band milliseconds.  Afterwards read_buffer(BUF_UPSCALE_GUIDE / BUF_UPSCALE_ALBEDO)
         of a member gives its hi-res records, valid in the hi-res rows of its band."""
         p = params if params is not None else UpscaleParams()
-        s = int(p.scale)
-        H, W = self.contexts[0].height * s, self.contexts[0].width * s
-        img = np.empty(max(W * H, 1), dtype=np.uint32)
-        rad = np.empty((max(W * H, 1), 4), dtype=np.float32) if want_radiance else None
-        ms = (C.c_float * len(self.contexts))()
-        self._check(self.lib.fyprt_group_denoise_upscale(self.h, C.byref(p), int(history_rows), _ptr(img), _ptr(rad), ms if with_band_ms else None))
+        out = _denoise_blocking(self, self.contexts[0], "fyprt_group_denoise_upscale", (C.byref(p), int(history_rows)), int(p.scale), want_radiance,
+                                (C.c_float * len(self.contexts))(), with_band_ms)
         for c in self.contexts:
-            c._upscale = s
-        out = (img.reshape(H, W), rad.reshape(H, W, 4) if want_radiance else None)
-        return out + (list(ms),) if with_band_ms else out
+            c._upscale = int(p.scale)
+        return out
 
     def denoise_upscale_tensor(self, image_tensor, radiance_tensor, params: UpscaleParams | None = None, history_rows=GROUP_HISTORY_ROWS, root=0):
         """denoise_upscale into device tensors of the hi-res size on the GPU of context `root` (fyprt_group_denoise_upscale_device): int32
         (sH, sW) / float32 (sH, sW, 4); stream ordering exactly as denoise_tensor."""
-        import torch
         p = params if params is not None else UpscaleParams()
-        s = int(p.scale)
-        if not 0 <= root < len(self.contexts):
-            raise ValueError("denoise_upscale_tensor: root out of range")
-        ctx = self.contexts[root]
-        if image_tensor is None and radiance_tensor is None:
-            raise ValueError("denoise_upscale_tensor: at least one output tensor is needed")
-        for t, dt, shape, name in ((image_tensor, torch.int32, (ctx.height * s, ctx.width * s), "image_tensor"),
-                                   (radiance_tensor, torch.float32, (ctx.height * s, ctx.width * s, 4), "radiance_tensor")):
-            if t is None:
-                continue
-            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError(f"denoise_upscale_tensor: {name} must be a contiguous {dt} tensor of shape {shape}")
-            if t.device.type != "cuda" or (t.device.index if t.device.index is not None else torch.cuda.current_device()) != ctx.device:
-                raise ValueError(f"denoise_upscale_tensor: {name} must be on cuda:{ctx.device}, the root context's GPU")
-        dev = (image_tensor if image_tensor is not None else radiance_tensor).device
-        cur = torch.cuda.current_stream(dev)
-        ext = torch.cuda.ExternalStream(ctx.stream(), device=dev)
-        ext.wait_stream(cur)                                           # the outputs are allocated (and their earlier uses done) before root writes them
-        self._check(self.lib.fyprt_group_denoise_upscale_device(self.h, C.byref(p), int(history_rows), root,
-                                                                C.c_void_p(image_tensor.data_ptr()) if image_tensor is not None else None,
-                                                                C.c_void_p(radiance_tensor.data_ptr()) if radiance_tensor is not None else None))
+        self._denoise_tensor("denoise_upscale_tensor", "fyprt_group_denoise_upscale_device", (C.byref(p), int(history_rows)), int(p.scale), root, image_tensor, radiance_tensor)
         for c in self.contexts:
-            c._upscale = s
-        cur.wait_stream(ext)                                           # torch's later work follows the collect
+            c._upscale = int(p.scale)
 
     def denoise_temporal_reset(self):
         """Drops every member's temporal history (fyprt_group_denoise_temporal_reset): the next denoise_temporal* call is a first call."""
@@ -1337,41 +1224,32 @@ def halo_plan(row_bounds, halo, height, wrap_row=True, lib=None):
     return [tuple(out[4 * k: 4 * k + 4]) for k in range(cnt)]
 
 
+def _export_plan(lib, fn, row_bounds, *args):
+    """A fyprt_group_denoise*_plan entry `fn`: asked for the number of entries, then for the entries, as (stage, receiver, owner, first
+    row, end row) tuples."""
+    f = getattr(lib or load_library(), fn)
+    args = (_u32_array(row_bounds), len(row_bounds) - 1) + args
+    cnt = f(*args, None, 0)
+    if cnt < 0:
+        raise FyprtError(f"{fn} failed ({cnt})")
+    out = (C.c_uint32 * (5 * max(cnt, 1)))()
+    f(*args, out, cnt)
+    return [tuple(out[5 * k: 5 * k + 5]) for k in range(cnt)]
+
+
 def group_denoise_plan(row_bounds, height, iterations, lib=None):
     """fyprt_group_denoise_plan: [(stage, receiver, owner, first row, end row), ...] of one Group.denoise call, in issue order."""
-    lib = lib or load_library()
-    n = len(row_bounds) - 1
-    cnt = lib.fyprt_group_denoise_plan(_u32_array(row_bounds), n, height, iterations, None, 0)
-    if cnt < 0:
-        raise FyprtError(f"fyprt_group_denoise_plan failed ({cnt})")
-    out = (C.c_uint32 * (5 * max(cnt, 1)))()
-    lib.fyprt_group_denoise_plan(_u32_array(row_bounds), n, height, iterations, out, cnt)
-    return [tuple(out[5 * k: 5 * k + 5]) for k in range(cnt)]
+    return _export_plan(lib, "fyprt_group_denoise_plan", row_bounds, height, iterations)
 
 
 def group_denoise_temporal_plan(row_bounds, height, iterations, history_rows=GROUP_HISTORY_ROWS, lib=None):
     """fyprt_group_denoise_temporal_plan: [(stage, receiver, owner, first row, end row), ...] of one Group.denoise_temporal call that finds a
     history, in issue order (stage 0 guides, 1 prepared colour, 2 history, 3 + k colour and variance of iteration k)."""
-    lib = lib or load_library()
-    n = len(row_bounds) - 1
-    cnt = lib.fyprt_group_denoise_temporal_plan(_u32_array(row_bounds), n, height, iterations, history_rows, None, 0)
-    if cnt < 0:
-        raise FyprtError(f"fyprt_group_denoise_temporal_plan failed ({cnt})")
-    out = (C.c_uint32 * (5 * max(cnt, 1)))()
-    lib.fyprt_group_denoise_temporal_plan(_u32_array(row_bounds), n, height, iterations, history_rows, out, cnt)
-    return [tuple(out[5 * k: 5 * k + 5]) for k in range(cnt)]
+    return _export_plan(lib, "fyprt_group_denoise_temporal_plan", row_bounds, height, iterations, history_rows)
 
 
 def group_denoise_upscale_plan(row_bounds, height, iterations, temporal=False, history_rows=GROUP_HISTORY_ROWS, lib=None):
     """fyprt_group_denoise_upscale_plan: [(stage, receiver, owner, first row, end row), ...] of one Group.denoise_upscale call, in issue
     order: the plan of the low-res stage (group_denoise_plan, or with `temporal` group_denoise_temporal_plan), then the stage that brings
     every band but the last the colour row below it."""
-    lib = lib or load_library()
-    n = len(row_bounds) - 1
-    args = (_u32_array(row_bounds), n, height, iterations, 1 if temporal else 0, history_rows)
-    cnt = lib.fyprt_group_denoise_upscale_plan(*args, None, 0)
-    if cnt < 0:
-        raise FyprtError(f"fyprt_group_denoise_upscale_plan failed ({cnt})")
-    out = (C.c_uint32 * (5 * max(cnt, 1)))()
-    lib.fyprt_group_denoise_upscale_plan(*args, out, cnt)
-    return [tuple(out[5 * k: 5 * k + 5]) for k in range(cnt)]
+    return _export_plan(lib, "fyprt_group_denoise_upscale_plan", row_bounds, height, iterations, 1 if temporal else 0, history_rows)

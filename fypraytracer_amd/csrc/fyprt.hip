@@ -2525,9 +2525,10 @@ template <class Enqueue> static int denoise_blocking(fyprt_context* c, uint32_t*
 
 // ---- what fyprt_denoise*, fyprt_denoise_temporal* and fyprt_group_denoise* (fyprt_multi.h) enqueue with.
 // Iteration k.  scaled: sigma_luminance / 2^k (spatial); otherwise sigma_luminance itself (temporal: the variance carries the scale).
-static DnIter make_dn_iter(const fyprt_denoise_params& p, uint32_t k, bool scaled) {
+// keep: the last iteration writes its colour buffer as every other one does, not the outputs.
+static DnIter make_dn_iter(const fyprt_denoise_params& p, uint32_t k, bool scaled, bool keep) {
     return DnIter{1 << k, scaled ? p.sigma_luminance * (1.0f / (float)(1u << k)) : p.sigma_luminance, p.sigma_luminance > 0.0f ? 1u : 0u,
-                  p.sigma_plane, p.normal_power_log2, (k + 1 == p.iterations) ? 1u : 0u};
+                  p.sigma_plane, p.normal_power_log2, (!keep && k + 1 == p.iterations) ? 1u : 0u};
 }
 // The full-size guide, albedo and ping-pong colour buffers of a context and its dnDone event; the frame descriptor over them.
 static int ensure_dn_buffers(fyprt_context* c) {
@@ -2565,45 +2566,78 @@ static int dn_call_done(fyprt_context* c) {
     return FYPRT_OK;
 }
 
-// What both single-context denoisers start with: the shared buffers, the frame descriptor `fr`, the prepare launch (into dn.col[0]) between ev[0] and ev[1].
-static int begin_denoise(fyprt_context* c, const fyprt_denoise_params& sp, uint32_t* rgba8, float4* radiance4, const Event* ev, int* launched, DnFrame& fr) {
-    TRY(ensure_dn_buffers(c));
-    fr = dn_frame(c, sp.demodulate_albedo, rgba8, radiance4);
+// ---- A filter call is a list of steps, stated once per filter (spatial_steps, temporal_steps, upscale_steps) and run by filter_enqueue
+// on one context or by group_filter_enqueue (fyprt_multi.h) on a group's bands.  A step pulls a stage of the group's plan, launches, or both.
+struct XBuf { void* p; size_t bytesPerPixel; };
+constexpr size_t kDnGuideBytes = 2 * sizeof(float4), kDnColourBytes = sizeof(float4), kDtHistoryBytes = 4 * sizeof(float4), kDtVarianceBytes = sizeof(float);
+struct BandStep {
+    int pulls;                                                        // the plan stage every band pulls before the launch, or -1,
+    std::function<std::vector<XBuf>(fyprt_context*)> moved;           // and the buffers it moves: the receiver's and, in the same order, the owner's
+    bool overwritesPulled;                                            // the launch overwrites rows the neighbours pulled earlier
+    bool writesOutput;                                                // the launch writes the output rows
+    std::function<bool(fyprt_context*, const DnFrame&, DnBand)> launch;      // on a band's rows, on its context's stream: whether a kernel was launched; empty: the step only pulls
+    bool recordsDone;                                                 // `done` is recorded after the launch: a pull reads what it wrote
+    int part;                                                         // the kernel_ms_part of a context's blocking call the launch counts in
+};
+// (a launch captures at most 16 bytes — the parameters by address: they outlive the list — so that no step allocates)
+// The single-context runner: every launch of the list on the band [0, H) (a hi-res step scales it itself); what only concerns neighbours,
+// the pulls and their events, is skipped.  ev: the blocking form's timing events and launch count, or null — ev[k] where part k begins, one more at the end.
+static int filter_enqueue(fyprt_context* c, const std::vector<BandStep>& steps, uint32_t demodulate, uint32_t* rgba8, float4* radiance4, const Event* ev, int* launched) {
+    const DnFrame fr = dn_frame(c, demodulate, rgba8, radiance4);
+    int part = 0;
     if (ev) HIPCHK(c, hipEventRecord(ev[0], c->stream));
-    launch_dn_prepare(c, fr, DnBand{0, c->H});
-    ++*launched;
-    if (ev) HIPCHK(c, hipEventRecord(ev[1], c->stream));
-    return FYPRT_OK;
-}
-// ... and end with: the finish kernel on the unfiltered colour if no iteration ran, the last timing event, and dn_call_done.
-static int end_denoise(fyprt_context* c, const DnFrame& fr, uint32_t iterations, const float4* unfiltered, const Event* evLast, int* launched) {
-    if (iterations == 0) { launch_dn_finish(c, fr, DnBand{0, c->H}, unfiltered); ++*launched; }
+    for (const BandStep& st : steps) {
+        if (!st.launch) continue;
+        if (ev && st.part != part) HIPCHK(c, hipEventRecord(ev[part = st.part], c->stream));
+        if (st.launch(c, fr, DnBand{0, c->H}) && launched) ++*launched;
+    }
     HIPCHK(c, hipGetLastError());
-    if (evLast) HIPCHK(c, hipEventRecord(*evLast, c->stream));
+    if (ev) HIPCHK(c, hipEventRecord(ev[part + 1], c->stream));
     return dn_call_done(c);
 }
+// What both denoisers start with: prepare on the band's rows (into dn.col[0]), then the guide records of the halo rows (stage 0) ...
+static std::vector<BandStep> first_steps() {
+    std::vector<BandStep> steps;
+    steps.reserve(16);                                                // (the longest list: 8 iterations and 8 other steps)
+    steps.push_back({-1, nullptr, false, false, [](fyprt_context* c, const DnFrame& fr, DnBand band) { launch_dn_prepare(c, fr, band); return true; }, true, 0});
+    steps.push_back({0, [](fyprt_context* c) { return std::vector<XBuf>{{c->dn.guide.p, kDnGuideBytes}}; }, false, false, nullptr, false, 0});
+    return steps;
+}
+// ... and, without iterations, end with: the finish kernel on the unfiltered colour dn.col[col]
+static BandStep finish_step(int col, int part) {
+    return {-1, nullptr, false, true, [col](fyprt_context* c, const DnFrame& fr, DnBand band) { launch_dn_finish(c, fr, band, c->dn.col[col].p); return true; }, true, part};
+}
 
-// Enqueues prepare + iterations (+ finish) on the context stream, outputs in device memory.  ev: 3 timing events or null.
-// keep (fyprt_denoise_upscale*: its low-res stage): the call stops before the output — the last iteration writes its colour buffer as every
-// other one does (DnIter::last = 0), no finish kernel, no dn_call_done — and *keep is the buffer that holds e.
-static int enqueue_denoise(fyprt_context* c, const fyprt_denoise_params* p, uint32_t* rgba8, float4* radiance4, const Event* ev, int* launched,
-                           const float4** keep = nullptr) {
-    DnFrame fr;
-    TRY(begin_denoise(c, *p, rgba8, radiance4, ev, launched, fr));
-    for (uint32_t k = 0; k < p->iterations; ++k) {
-        DnIter it = make_dn_iter(*p, k, true);
-        if (keep) it.last = 0u;
-        launch_dn_iterate(c, fr, it, DnBand{0, c->H}, c->dn.col[k & 1u].p, c->dn.col[(k + 1u) & 1u].p);
-        ++*launched;
-    }
-    if (keep) { *keep = c->dn.col[p->iterations & 1u].p; return FYPRT_OK; }
-    return end_denoise(c, fr, p->iterations, c->dn.col[0].p, ev ? ev + 2 : nullptr, launched);
+// The spatial filter (the group's plan: group_denoise_plan): prepare; the guides; per iteration k the colour halo it reads (stage 1 + k:
+// dn.col[k & 1]) and the iteration dn.col[k & 1] -> dn.col[(k + 1) & 1]; without an iteration the finish kernel on dn.col[0].  Iteration 0
+// waits for no puller: it writes dn.col[1], which nothing pulled yet.  Parts: prepare | the iterations or the finish kernel.
+// keep (the low-res stage of the upscaler): the list stops before the output — the last iteration writes its colour buffer as every
+// other one does (DnIter::last = 0), no finish kernel — and *keep is the index of the dn.col that holds e.
+static std::vector<BandStep> spatial_steps(const fyprt_denoise_params& p, int* keep = nullptr) {
+    std::vector<BandStep> steps = first_steps();
+    const fyprt_denoise_params* pp = &p;
+    const bool kept = keep != nullptr;
+    for (uint32_t k = 0; k < p.iterations; ++k)
+        steps.push_back({1 + (int)k, [k](fyprt_context* c) { return std::vector<XBuf>{{c->dn.col[k & 1u].p, kDnColourBytes}}; }, k > 0, !kept && k + 1 == p.iterations,
+                         [pp, k, kept](fyprt_context* c, const DnFrame& fr, DnBand band) {
+                             launch_dn_iterate(c, fr, make_dn_iter(*pp, k, true, kept), band, c->dn.col[k & 1u].p, c->dn.col[(k + 1u) & 1u].p);
+                             return true;
+                         }, true, 1});
+    if (kept) *keep = (int)(p.iterations & 1u);
+    else if (p.iterations == 0) steps.push_back(finish_step(0, 1));
+    return steps;
+}
+
+// One spatial call on a context, outputs in device memory.  ev, launched: 3 timing events and the launch count of the blocking form, or null.
+static int denoise_call(fyprt_context* c, const fyprt_denoise_params* p, uint32_t* rgba8, float4* radiance4, const Event* ev, int* launched) {
+    TRY(ensure_dn_buffers(c));
+    return filter_enqueue(c, spatial_steps(*p), p->demodulate_albedo, rgba8, radiance4, ev, launched);
 }
 
 int fyprt_denoise(fyprt_context* c, const fyprt_denoise_params* p, uint32_t* rgba8, float* radiance4, fyprt_frame_stats* stats) {
     TRY(check_denoise(c, p, rgba8, radiance4, false));
     return denoise_blocking(c, rgba8, radiance4, stats, c->dnEv, 3,      // parts: prepare, the iterations (or the finish kernel)
-                            [&](uint32_t* img, float4* rad, int* launched) { return enqueue_denoise(c, p, img, rad, c->dnEv, launched); });
+                            [&](uint32_t* img, float4* rad, int* launched) { return denoise_call(c, p, img, rad, c->dnEv, launched); });
 }
 
 int fyprt_denoise_device(fyprt_context* c, const fyprt_denoise_params* p, void* rgba8, void* radiance4) {
@@ -2611,8 +2645,7 @@ int fyprt_denoise_device(fyprt_context* c, const fyprt_denoise_params* p, void* 
     HIPCHK(c, hipSetDevice(c->device));
     // every frame completes on the context stream (a pipelined frame's trace kernel waits there for its front part), so work enqueued on
     // it sees the last frame whole without a host wait
-    int launches = 0;
-    return enqueue_denoise(c, p, static_cast<uint32_t*>(rgba8), static_cast<float4*>(radiance4), nullptr, &launches);
+    return denoise_call(c, p, static_cast<uint32_t*>(rgba8), static_cast<float4*>(radiance4), nullptr, nullptr);
 }
 
 // ---- temporal denoiser (rt_temporal.h; the contract is include/fyprt.h's).  As the spatial one it reads the last frame's accumulation
@@ -2686,50 +2719,71 @@ static DtCall make_dt_call(const fyprt_context* c, const fyprt_temporal_params& 
     return tc;
 }
 
-// Enqueues prepare + reproject + iterations (+ finish) on the context stream.  ev: 4 timing events or null.  keep: as enqueue_denoise's —
-// the history advances as in any temporal call.
-static int enqueue_temporal(fyprt_context* c, const fyprt_temporal_params* p, uint32_t* rgba8, float4* radiance4, const Event* ev, int* launched,
-                            const float4** keep = nullptr) {
-    const fyprt_denoise_params& sp = p->spatial;
+// The temporal filter (the group's plan: group_temporal_plan, without stage 2 while there is no history): prepare; the guides; the
+// prepared colour the variance estimate reads (stage 1); with a history the moved flags of a pending edit — launched only while
+// dt_motion_pending, and nothing pulls what they are, so no `done` — and the history window (stage 2: dt.hist[dtCur]); the reprojection,
+// its taps within the band plus R rows either side, clipped to the frame (a context alone: R = H); per iteration k the colour and
+// variance it reads (stage 3 + k) and the iteration, colour dn.col[1] -> [0] -> [1] ..., variance dt.var[0] -> [1] -> [0] ..., iteration 0
+// feeding dt.hist[dtCur ^ 1] back; without an iteration the finish kernel on the integrated colour dn.col[1].  Every iteration waits
+// for its pullers: iteration 0 overwrites the prepared colour of stage 1.  Parts: prepare | moved flags + reprojection | the iterations
+// or the finish kernel.  keep: as spatial_steps' — the history advances as in any temporal call.  The callers advance the
+// bookkeeping (dt_advance) once everything is enqueued: the launches read dtCur as it was.
+static std::vector<BandStep> temporal_steps(const fyprt_temporal_params& p, bool history, uint32_t R, int* keep = nullptr) {
+    std::vector<BandStep> steps = first_steps();
+    const fyprt_temporal_params* pp = &p;
+    const fyprt_denoise_params& sp = p.spatial;
+    const bool kept = keep != nullptr;
+    steps.push_back({1, [](fyprt_context* c) { return std::vector<XBuf>{{c->dn.col[0].p, kDnColourBytes}}; }, false, false, nullptr, false, 1});
+    if (history) {
+        steps.push_back({-1, nullptr, false, false, [](fyprt_context* c, const DnFrame&, DnBand) {
+            if (!dt_motion_pending(c, true)) return false;
+            launch_dt_moved(c);
+            return true;
+        }, false, 1});
+        steps.push_back({2, [](fyprt_context* c) { return std::vector<XBuf>{{c->dt.hist[c->dtCur].p, kDtHistoryBytes}}; }, false, false, nullptr, false, 1});
+    }
+    steps.push_back({-1, nullptr, false, false, [pp, R, history](fyprt_context* c, const DnFrame& fr, DnBand band) {
+        const DnBand window{band.rowBegin > R ? band.rowBegin - R : 0u, std::min(fr.H, band.rowEnd + R)};
+        launch_dt_reproject(c, fr, make_dt_call(c, *pp, history), band, window, dt_motion_pending(c, history));
+        return true;
+    }, true, 1});
+    for (uint32_t k = 0; k < sp.iterations; ++k)
+        steps.push_back({3 + (int)k, [k](fyprt_context* c) { return std::vector<XBuf>{{c->dn.col[(k + 1u) & 1u].p, kDnColourBytes}, {c->dt.var[k & 1u].p, kDtVarianceBytes}}; },
+                         true, !kept && k + 1 == sp.iterations,
+                         [pp, k, kept](fyprt_context* c, const DnFrame& fr, DnBand band) {
+                             launch_dt_iterate(c, fr, make_dn_iter(pp->spatial, k, false, kept), band, c->dn.col[(k + 1u) & 1u].p, c->dn.col[k & 1u].p, c->dt.var[k & 1u].p,
+                                               c->dt.var[(k + 1u) & 1u].p, (k == 0 && pp->feedback) ? c->dt.hist[c->dtCur ^ 1].p : nullptr);
+                             return true;
+                         }, true, 2});
+    if (kept) *keep = (int)((sp.iterations + 1u) & 1u);      // (iteration k writes col[k & 1]; none: the integrated colour in col[1])
+    else if (sp.iterations == 0) steps.push_back(finish_step(1, 2));
+    return steps;
+}
+// After a temporal list is enqueued: the history it wrote is the current one, written by `group` (0: by the context alone)
+static void dt_advance(fyprt_context* c, uint64_t group) {
+    c->dtCur ^= 1; c->dtValid = true; c->dtGroup = group; c->dtSnapPending = false; std::memcpy(c->dtPV, c->framePV, 64);
+}
+
+// One temporal call on a context, outputs in device memory.  ev, launched: 4 timing events and the launch count of the blocking form, or null.
+static int temporal_call(fyprt_context* c, const fyprt_temporal_params* p, uint32_t* rgba8, float4* radiance4, const Event* ev, int* launched) {
     TRY(ensure_dt_buffers(c));
     if (c->dtGroup != 0) c->drop_history();      // a history a group wrote (fyprt_group_denoise_temporal*) covers the rows the context owned there
-    DnFrame fr;
-    TRY(begin_denoise(c, sp, rgba8, radiance4, ev, launched, fr));
-    const DtCall tc = make_dt_call(c, *p, c->dtValid);
-    const int next = c->dtCur ^ 1;
-    float4* hist = c->dt.hist[next].p;
-    const DnBand all{0, c->H};
-    const bool motion = dt_motion_pending(c, c->dtValid);      // object motion: the flags of the edited range, then the motion form
-    if (motion) { launch_dt_moved(c); ++*launched; }
-    launch_dt_reproject(c, fr, tc, all, all, motion);
-    ++*launched;
-    if (ev) HIPCHK(c, hipEventRecord(ev[2], c->stream));
-    for (uint32_t k = 0; k < sp.iterations; ++k) {           // colour: dn.col[1] -> [0] -> [1] ...; variance: dt.var[0] -> [1] -> [0] ...
-        DnIter it = make_dn_iter(sp, k, false);
-        if (keep) it.last = 0u;
-        const float4* in = c->dn.col[(k + 1u) & 1u].p; float4* out = c->dn.col[k & 1u].p;
-        const float* vin = c->dt.var[k & 1u].p; float* vout = c->dt.var[(k + 1u) & 1u].p;
-        float4* fb = (k == 0 && p->feedback) ? hist : nullptr;
-        launch_dt_iterate(c, fr, it, all, in, out, vin, vout, fb);
-        ++*launched;
-    }
-    if (keep) { *keep = c->dn.col[(sp.iterations + 1u) & 1u].p; HIPCHK(c, hipGetLastError()); }      // (iteration k writes col[k & 1]; none: the integrated colour in col[1])
-    else TRY(end_denoise(c, fr, sp.iterations, c->dn.col[1].p, ev ? ev + 3 : nullptr, launched));
-    c->dtCur = next; c->dtValid = true; c->dtGroup = 0; c->dtSnapPending = false; std::memcpy(c->dtPV, c->framePV, 64);
+    TRY(ensure_dn_buffers(c));
+    TRY(filter_enqueue(c, temporal_steps(*p, c->dtValid, c->H), p->spatial.demodulate_albedo, rgba8, radiance4, ev, launched));
+    dt_advance(c, 0);
     return FYPRT_OK;
 }
 
 int fyprt_denoise_temporal(fyprt_context* c, const fyprt_temporal_params* p, uint32_t* rgba8, float* radiance4, fyprt_frame_stats* stats) {
     TRY(check_temporal(c, p, rgba8, radiance4, false));
     return denoise_blocking(c, rgba8, radiance4, stats, c->dtEv, 4,      // parts: prepare, reproject, iterations
-                            [&](uint32_t* img, float4* rad, int* launched) { return enqueue_temporal(c, p, img, rad, c->dtEv, launched); });
+                            [&](uint32_t* img, float4* rad, int* launched) { return temporal_call(c, p, img, rad, c->dtEv, launched); });
 }
 
 int fyprt_denoise_temporal_device(fyprt_context* c, const fyprt_temporal_params* p, void* rgba8, void* radiance4) {
     TRY(check_temporal(c, p, rgba8, radiance4, true));
     HIPCHK(c, hipSetDevice(c->device));
-    int launches = 0;
-    return enqueue_temporal(c, p, static_cast<uint32_t*>(rgba8), static_cast<float4*>(radiance4), nullptr, &launches);
+    return temporal_call(c, p, static_cast<uint32_t*>(rgba8), static_cast<float4*>(radiance4), nullptr, nullptr);
 }
 
 int fyprt_denoise_temporal_reset(fyprt_context* c) {
@@ -2808,25 +2862,48 @@ static void launch_up_resolve(fyprt_context* c, const fyprt_denoise_params& sp, 
     }
 }
 
-// Enqueues the low-res stage, k_up_primary and k_up_resolve on the context stream (after ensure_up_buffers).  ev: 4 timing events or null.
-static int enqueue_upscale(fyprt_context* c, const fyprt_upscale_params* p, uint32_t* rgba8, float4* radiance4, const Event* ev, int* launched) {
-    const uint32_t s = p->scale;
-    const fyprt_denoise_params& sp = p->filter.spatial;
-    const DnBand all{0u, c->H * s};
-    if (ev) HIPCHK(c, hipEventRecord(ev[0], c->stream));
-    const float4* e = nullptr;
-    if (p->temporal) TRY(enqueue_temporal(c, &p->filter, nullptr, nullptr, nullptr, launched, &e));
-    else TRY(enqueue_denoise(c, &sp, nullptr, nullptr, nullptr, launched, &e));
-    if (ev) HIPCHK(c, hipEventRecord(ev[1], c->stream));
-    launch_up_primary(c, s, all);
-    ++*launched;
-    if (ev) HIPCHK(c, hipEventRecord(ev[2], c->stream));
-    launch_up_resolve(c, sp, s, e, rgba8, radiance4, all);
-    ++*launched;
-    HIPCHK(c, hipGetLastError());
-    if (ev) HIPCHK(c, hipEventRecord(ev[3], c->stream));
+// The upscaler at scale s: the low-res stage — either filter's list in its keep form, the colour e left in dn.col[col] —, then
+//   k_up_primary on the band's hi-res rows.  It reads the scene and the frame's camera only, so it may stand anywhere before the
+//   resolve; after the last iteration it runs, on a group, while the neighbour below finishes its last iteration, whose `done` the pull
+//   after it waits for — the one wait of the call that nothing else of the band's own could fill.  primaryEarly (the group's
+//   FYPRT_UP_PRIMARY_EARLY, fyprt_multi.h) puts it directly after prepare instead.  A launch-only step: it pulls nothing and records no
+//   `done`, because nothing pulls from it;
+//   then the pull of the plan's last stage (group_upscale_plan) — row e of dn.col[col], and its guide record where the plan has no
+//   stage 0 (spatial without an iteration) — and k_up_resolve on the band's hi-res rows, which writes the output rows and records `done`.
+// Parts: the low-res stage | k_up_primary | k_up_resolve.
+static std::vector<BandStep> upscale_steps(const fyprt_upscale_params& p, bool history, uint32_t R, bool primaryEarly) {
+    const fyprt_denoise_params* sp = &p.filter.spatial;
+    const uint32_t s = p.scale;
+    int col = 0;
+    std::vector<BandStep> steps = p.temporal ? temporal_steps(p.filter, history, R, &col) : spatial_steps(*sp, &col);
+    for (BandStep& st : steps) st.part = 0;
+    const bool withGuide = !p.temporal && sp->iterations == 0;
+    steps.insert(primaryEarly ? steps.begin() + 1 : steps.end(), BandStep{-1, nullptr, false, false, [s](fyprt_context* c, const DnFrame&, DnBand band) {
+        launch_up_primary(c, s, DnBand{band.rowBegin * s, band.rowEnd * s});
+        return true;
+    }, false, 1});
+    steps.push_back({(p.temporal ? 3 : 1) + (int)sp->iterations, [col, withGuide](fyprt_context* c) {
+        std::vector<XBuf> v{{c->dn.col[col].p, kDnColourBytes}};
+        if (withGuide) v.push_back({c->dn.guide.p, kDnGuideBytes});
+        return v;
+    }, false, true, [sp, s, col](fyprt_context* c, const DnFrame& fr, DnBand band) {
+        launch_up_resolve(c, *sp, s, c->dn.col[col].p, fr.rgba8, fr.radiance4, DnBand{band.rowBegin * s, band.rowEnd * s});
+        return true;
+    }, true, 2});
+    return steps;
+}
+
+// One upscale call on a context (after ensure_up_buffers), outputs in device memory.  ev, launched: 4 timing events and the launch count of the blocking form, or null.
+static int upscale_call(fyprt_context* c, const fyprt_upscale_params* p, uint32_t* rgba8, float4* radiance4, const Event* ev, int* launched) {
+    if (p->temporal) {
+        TRY(ensure_dt_buffers(c));
+        if (c->dtGroup != 0) c->drop_history();      // (as temporal_call)
+    }
+    TRY(ensure_dn_buffers(c));
+    TRY(filter_enqueue(c, upscale_steps(*p, c->dtValid, c->H, false), p->filter.spatial.demodulate_albedo, rgba8, radiance4, ev, launched));
+    if (p->temporal) dt_advance(c, 0);
     c->upValid = true;
-    return dn_call_done(c);
+    return FYPRT_OK;
 }
 
 int fyprt_denoise_upscale(fyprt_context* c, const fyprt_upscale_params* p, uint32_t* rgba8, float* radiance4, fyprt_frame_stats* stats) {
@@ -2835,15 +2912,14 @@ int fyprt_denoise_upscale(fyprt_context* c, const fyprt_upscale_params* p, uint3
     TRY(ensure_up_buffers(c, p->scale));
     const size_t n = (size_t)c->W * p->scale * ((size_t)c->H * p->scale);
     return staged_blocking(c, n, c->up.outImg, c->up.outRad, rgba8, radiance4, stats, c->upEv, 4,      // parts: the low-res stage, the hi-res primary rays, the resolve
-                           [&](uint32_t* img, float4* rad, int* launched) { return enqueue_upscale(c, p, img, rad, c->upEv, launched); });
+                           [&](uint32_t* img, float4* rad, int* launched) { return upscale_call(c, p, img, rad, c->upEv, launched); });
 }
 
 int fyprt_denoise_upscale_device(fyprt_context* c, const fyprt_upscale_params* p, void* rgba8, void* radiance4) {
     TRY(check_upscale(c, p, rgba8, radiance4, true));
     HIPCHK(c, hipSetDevice(c->device));
     TRY(ensure_up_buffers(c, p->scale));
-    int launches = 0;
-    return enqueue_upscale(c, p, static_cast<uint32_t*>(rgba8), static_cast<float4*>(radiance4), nullptr, &launches);
+    return upscale_call(c, p, static_cast<uint32_t*>(rgba8), static_cast<float4*>(radiance4), nullptr, nullptr);
 }
 
 #include "fyprt_multi.h"

@@ -20,7 +20,7 @@
 //   fyprt_comm_*    one process per GPU (torch.distributed.run, MPI, ...): RCCL — grouped ncclSend / ncclRecv for the halos, grouped
 //                   ncclBroadcast (one per band, in place in the full-size image) for the gather.  librccl.so.1 is opened on first use.
 // fyprt_group_denoise* and fyprt_group_denoise_temporal* (below fyprt_group_synchronize): the a-trous and the temporal denoiser on the same
-// bands, by the same peer copies and events — two lists of steps for one schedule, group_filter_enqueue.  The temporal history stays with
+// bands, by the same peer copies and events — the filters' lists of steps (fyprt.hip) on one schedule, group_filter_enqueue.  The temporal history stays with
 // the rows' owners, a band reads it inside its history window, and fyprt_group_set_rows moves it with the rows.
 #include <dlfcn.h>
 
@@ -57,7 +57,6 @@ std::vector<HaloXfer> halo_plan(const std::vector<uint32_t>& bounds, uint32_t ha
 // (the farthest tap of any iteration: 2 * 2^(iterations-1)); stage 1 + k = the colour | luminance buffer iteration k reads (16 B per
 // pixel), halo 2 * 2^k rows.  Clipped to the image, no wrap row; a halo higher than the neighbouring band has several owners.
 struct DnXfer { int stage; HaloXfer x; };
-constexpr size_t kDnGuideBytes = 2 * sizeof(float4), kDnColourBytes = sizeof(float4);
 std::vector<DnXfer> group_denoise_plan(const std::vector<uint32_t>& bounds, uint32_t H, uint32_t iterations) {
     std::vector<DnXfer> plan;
     if (iterations == 0) return plan;
@@ -71,7 +70,6 @@ std::vector<DnXfer> group_denoise_plan(const std::vector<uint32_t>& bounds, uint
 // guide records, max(2, 2^iterations) rows (the 5 x 5 variance estimate of k_dt_reproject reads 2 rows whatever the iterations); stage 1
 // = the prepared colour e0 | L that estimate reads, 2 rows; stage 2 = the history records (64 B per pixel), min(historyRows, H) rows:
 // the band's history window; stage 3 + k = the colour | luminance and the variance (4 B per pixel) iteration k reads, 2 * 2^k rows.
-constexpr size_t kDtHistoryBytes = 4 * sizeof(float4), kDtVarianceBytes = sizeof(float);
 std::vector<DnXfer> group_temporal_plan(const std::vector<uint32_t>& bounds, uint32_t H, uint32_t iterations, uint32_t historyRows) {
     std::vector<DnXfer> plan;
     for (const HaloXfer& x : halo_plan(bounds, std::max(2u, 1u << iterations), H, false)) plan.push_back({0, x});
@@ -85,23 +83,13 @@ std::vector<DnXfer> group_temporal_plan(const std::vector<uint32_t>& bounds, uin
 // last pulls the one low-res row below it, e_k, from its owner — the colour buffer that holds e after the last iteration (16 B per pixel).
 // The resolve of the last s - 1 hi-res rows of a band taps that row.  Its guide record needs no entry: stage 0 already brings at least one
 // guide row below the band (2^iterations >= 1 rows, temporal max(2, ...)) — except that the spatial plan has no stage 0 at all without an
-// iteration, and the call then moves the guide record of the row with its colour (48 B per pixel; group_upscale_steps).
+// iteration, and the call then moves the guide record of the row with its colour (48 B per pixel; upscale_steps).
 std::vector<DnXfer> group_upscale_plan(const std::vector<uint32_t>& bounds, uint32_t H, uint32_t iterations, bool temporal, uint32_t historyRows) {
     std::vector<DnXfer> plan = temporal ? group_temporal_plan(bounds, H, iterations, historyRows) : group_denoise_plan(bounds, H, iterations);
     const int n = (int)bounds.size() - 1, stage = (temporal ? 3 : 1) + (int)iterations;
     for (int k = 0; k + 1 < n; ++k) plan.push_back({stage, HaloXfer{k, k + 1, bounds[k + 1], bounds[k + 1] + 1u}});      // (no band is empty: row e_k is band k + 1's first)
     return plan;
 }
-// a plan as the _plan entries hand it out: (stage, receiver, owner, first row, end row) per entry; returns the number of entries
-int export_plan(const std::vector<DnXfer>& plan, uint32_t* out5, int capacity) {
-    for (int k = 0; k < (int)plan.size() && k < capacity && out5; ++k) {
-        const HaloXfer& x = plan[k].x;
-        out5[5 * k] = (uint32_t)plan[k].stage; out5[5 * k + 1] = (uint32_t)x.receiver; out5[5 * k + 2] = (uint32_t)x.owner; out5[5 * k + 3] = x.r0; out5[5 * k + 4] = x.r1;
-    }
-    return (int)plan.size();
-}
-
-struct XBuf { void* p; size_t bytesPerPixel; };
 // what crosses between Part 1 and Part 2 (kind 0) / before Part 1 (kind 1: temporal history), for the technique
 std::vector<XBuf> exchange_buffers(fyprt_context* c, int tech, int kind) {
     std::vector<XBuf> v;
@@ -144,6 +132,18 @@ const char* bad_bands(const uint32_t* b, int n, uint32_t H, int* at) {
     if (const char* t = bad_ends(b, n, H)) return t;
     for (; *at < n; ++*at) if (const char* t = bad_band(b, *at)) return t;
     return nullptr;
+}
+// What the three fyprt_group_denoise*_plan entries are: the check of the band table and the iterations, then `make(bounds)` as they hand
+// a plan out — (stage, receiver, owner, first row, end row) per entry, up to `capacity` entries; returns the number of entries.
+template <class Make> int export_checked_plan(const uint32_t* row_bounds, int n, uint32_t height, uint32_t iterations, uint32_t* out5, int capacity, Make&& make) {
+    int at;
+    if (!row_bounds || n <= 0 || iterations > 8u || bad_bands(row_bounds, n, height, &at)) return FYPRT_EINVAL;
+    const std::vector<DnXfer> plan = make(std::vector<uint32_t>(row_bounds, row_bounds + n + 1));
+    for (int k = 0; k < (int)plan.size() && k < capacity && out5; ++k) {
+        const HaloXfer& x = plan[k].x;
+        out5[5 * k] = (uint32_t)plan[k].stage; out5[5 * k + 1] = (uint32_t)x.receiver; out5[5 * k + 2] = (uint32_t)x.owner; out5[5 * k + 3] = x.r0; out5[5 * k + 4] = x.r1;
+    }
+    return (int)plan.size();
 }
 bool is_restir(const fyprt_settings* s) { return s->technique == FYPRT_RESTIR_DI || s->technique == FYPRT_RESTIR_GI; }
 // stripes of part `part` of an interleaved split, as (first row, end row) — the same walk as stripe_row_count
@@ -466,7 +466,7 @@ static int group_denoise_check(fyprt_group* g, const fyprt_denoise_params* p, in
 }
 
 // ---- group_filter_enqueue: one filter call on the group's bands, which both denoisers enqueue with.  A call is a plan — which rows a
-// band pulls from which owner at which stage — and a list of steps; the engine below runs the steps in order, each on every band
+// band pulls from which owner at which stage — and the filter's list of steps (BandStep, fyprt.hip); the engine below runs the steps in order, each on every band
 // before the next on any (the waits of a step resolve to the records of the step before, so the host's issue order is part of it):
 //   1. if the step's launch overwrites rows that neighbours pulled earlier: every band waits for the `pulled` of the bands that pull from it;
 //   2. if the step pulls a plan stage: every band copies that stage's rows from their owners, after the owner's `done`, and records `pulled`
@@ -506,14 +506,6 @@ static int group_denoise_check(fyprt_group* g, const fyprt_denoise_params* p, in
 //   the staging        the resolve writes the band's hi-res staging rows, which the earlier root's `collect` may still read: the
 //                      writesOutput wait, as for the low-res staging.  A staging or hi-res buffer reallocated for another scale is first
 //                      waited for on the host (group_ensure_up_buffers).
-struct BandStep {
-    int pulls;                                                        // the plan stage every band pulls before the launch, or -1,
-    std::function<std::vector<XBuf>(fyprt_context*)> moved;           // and the buffers it moves: the receiver's and, in the same order, the owner's
-    bool overwritesPulled;                                            // the launch overwrites rows the neighbours pulled earlier
-    bool writesOutput;                                                // the launch writes the output rows
-    std::function<void(fyprt_context*, const DnFrame&, DnBand)> launch;      // on a band's rows, on its context's stream; empty: the step only pulls
-    bool recordsDone;                                                 // `done` is recorded after the launch: a pull reads what it wrote
-};
 // The first step must not pull: the first-work wait goes with its launch (both denoisers start with prepare).
 static int group_filter_enqueue(fyprt_group* g, const std::vector<DnXfer>& plan, const std::vector<BandStep>& steps, uint32_t demodulate, int root,
                                 uint32_t* rgba8, float4* radiance4, bool timed, uint32_t scale = 1u) {
@@ -605,15 +597,6 @@ static int group_filter_enqueue(fyprt_group* g, const std::vector<DnXfer>& plan,
     g->dnCalled = true; g->dnRoot = root;
     return FYPRT_OK;
 }
-// What both lists of steps start with: prepare on the band's rows (into dn.col[0]), then the guide records of the halo rows (stage 0) ...
-static std::vector<BandStep> first_band_steps() {
-    return {{-1, nullptr, false, false, [](fyprt_context* c, const DnFrame& fr, DnBand band) { launch_dn_prepare(c, fr, band); }, true},
-            {0, [](fyprt_context* c) { return std::vector<XBuf>{{c->dn.guide.p, kDnGuideBytes}}; }, false, false, nullptr, false}};
-}
-// ... and, without iterations, end with: the finish kernel on the unfiltered colour dn.col[col]
-static BandStep finish_band_step(int col) {
-    return {-1, nullptr, false, true, [col](fyprt_context* c, const DnFrame& fr, DnBand band) { launch_dn_finish(c, fr, band, c->dn.col[col].p); }, true};
-}
 // The blocking form of either group call, as denoise_blocking is of a context's: the group synchronised (the last frame is complete on
 // every stream), the outputs staged at full size on member 0, `enqueue(rgba8, radiance4)` with member 0 as root and timed, copied back;
 // band_ms from every member's timing events.  scale > 1 (the upscale call): scale*W x scale*H pixels through member 0's upscale staging,
@@ -643,49 +626,16 @@ static int group_denoise_blocking(fyprt_group* g, uint32_t* rgba8, float* radian
     return FYPRT_OK;
 }
 
-// What the upscale call (scale s > 1) makes of a list of low-res steps in "keep" form (the last iteration as every other one, no finish
-// step: the colour e stays in dn.col[col]):
-//   k_up_primary on the band's hi-res rows after the last iteration.  It reads the scene and the frame's camera only, so it may stand
-//   anywhere before the resolve; there it runs while the neighbour below finishes its last iteration, whose `done` the pull after it
-//   waits for — the one wait of the call that nothing else of the band's own could fill.  Directly after prepare (FYPRT_UP_PRIMARY_EARLY)
-//   it was slower with 2, 4 and 8 bands sharing one GPU (profiles/upscale/group_upscale_rate.jsonl).  A launch-only step: it pulls
-//   nothing and records no `done`, because nothing pulls from it;
-//   then the pull of the plan's last stage `stage` — row e of dn.col[col], and its guide record where the plan has no stage 0
-//   (`withGuide`) — and k_up_resolve on the band's hi-res rows, which writes the output rows and records `done` for the collect.
+// The spatial call: the plan, the list (spatial_steps), the engine.  up: the call is the low-res stage of fyprt_group_denoise_upscale*
+// (group_upscale_plan, upscale_steps), at its scale.
 #ifndef FYPRT_UP_PRIMARY_EARLY
-#define FYPRT_UP_PRIMARY_EARLY 0     // 1: k_up_primary directly after prepare instead (the placement it was timed against)
+#define FYPRT_UP_PRIMARY_EARLY 0     // 1: a group's k_up_primary directly after prepare (the placement it was timed against); a context alone is not affected
 #endif
-static void group_upscale_steps(std::vector<BandStep>& steps, const fyprt_denoise_params& sp, uint32_t s, int stage, int col, bool withGuide) {
-    steps.insert(FYPRT_UP_PRIMARY_EARLY ? steps.begin() + 1 : steps.end(), BandStep{-1, nullptr, false, false, [s](fyprt_context* c, const DnFrame&, DnBand band) {
-        launch_up_primary(c, s, DnBand{band.rowBegin * s, band.rowEnd * s});
-    }, false});
-    steps.push_back({stage, [col, withGuide](fyprt_context* c) {
-        std::vector<XBuf> v{{c->dn.col[col].p, kDnColourBytes}};
-        if (withGuide) v.push_back({c->dn.guide.p, kDnGuideBytes});
-        return v;
-    }, false, true, [sp, s, col](fyprt_context* c, const DnFrame& fr, DnBand band) {
-        launch_up_resolve(c, sp, s, c->dn.col[col].p, fr.rgba8, fr.radiance4, DnBand{band.rowBegin * s, band.rowEnd * s});
-    }, true});
-}
-
-// The spatial call (group_denoise_plan): prepare; the guides; per iteration k the colour halo it reads (stage 1 + k: dn.col[k & 1]) and
-// the iteration dn.col[k & 1] -> dn.col[(k + 1) & 1].  Iteration 0 waits for no puller: it writes dn.col[1], which nothing pulled yet.
-// scale > 1: the low-res stage of fyprt_group_denoise_upscale* (group_upscale_plan, group_upscale_steps), e in dn.col[iterations & 1].
-static int group_spatial_call(fyprt_group* g, const fyprt_denoise_params* p, int root, uint32_t* rgba8, float4* radiance4, bool timed, uint32_t scale = 1u) {
-    std::vector<BandStep> steps = first_band_steps();
-    const bool keep = scale > 1u;
-    for (uint32_t k = 0; k < p->iterations; ++k) {
-        DnIter it = make_dn_iter(*p, k, true);
-        if (keep) it.last = 0u;
-        steps.push_back({1 + (int)k, [k](fyprt_context* c) { return std::vector<XBuf>{{c->dn.col[k & 1u].p, kDnColourBytes}}; }, k > 0, it.last != 0,
-                         [k, it](fyprt_context* c, const DnFrame& fr, DnBand band) { launch_dn_iterate(c, fr, it, band, c->dn.col[k & 1u].p, c->dn.col[(k + 1u) & 1u].p); }, true});
-    }
-    if (keep) {
-        group_upscale_steps(steps, *p, scale, 1 + (int)p->iterations, (int)(p->iterations & 1u), p->iterations == 0);
-        return group_filter_enqueue(g, group_upscale_plan(g->bounds, g->ctx[0]->H, p->iterations, false, 0u), steps, p->demodulate_albedo, root, rgba8, radiance4, timed, scale);
-    }
-    if (p->iterations == 0) steps.push_back(finish_band_step(0));
-    return group_filter_enqueue(g, group_denoise_plan(g->bounds, g->ctx[0]->H, p->iterations), steps, p->demodulate_albedo, root, rgba8, radiance4, timed);
+static int group_spatial_call(fyprt_group* g, const fyprt_denoise_params* p, int root, uint32_t* rgba8, float4* radiance4, bool timed, const fyprt_upscale_params* up = nullptr) {
+    const uint32_t H = g->ctx[0]->H;
+    const std::vector<DnXfer> plan = up ? group_upscale_plan(g->bounds, H, p->iterations, false, 0u) : group_denoise_plan(g->bounds, H, p->iterations);
+    const std::vector<BandStep> steps = up ? upscale_steps(*up, false, 0u, FYPRT_UP_PRIMARY_EARLY != 0) : spatial_steps(*p);
+    return group_filter_enqueue(g, plan, steps, p->demodulate_albedo, root, rgba8, radiance4, timed, up ? up->scale : 1u);
 }
 
 int fyprt_group_denoise(fyprt_group* g, const fyprt_denoise_params* p, uint32_t* rgba8, float* radiance4, float* band_ms) {
@@ -700,9 +650,7 @@ int fyprt_group_denoise_device(fyprt_group* g, const fyprt_denoise_params* p, in
 
 // The transfers of one fyprt_group_denoise* call in issue order: (stage, receiver, owner, first row, end row) per entry.
 int fyprt_group_denoise_plan(const uint32_t* row_bounds, int n, uint32_t height, uint32_t iterations, uint32_t* out5, int capacity) {
-    int at;
-    if (!row_bounds || n <= 0 || iterations > 8u || bad_bands(row_bounds, n, height, &at)) return FYPRT_EINVAL;
-    return export_plan(group_denoise_plan(std::vector<uint32_t>(row_bounds, row_bounds + n + 1), height, iterations), out5, capacity);
+    return export_checked_plan(row_bounds, n, height, iterations, out5, capacity, [&](const std::vector<uint32_t>& b) { return group_denoise_plan(b, height, iterations); });
 }
 
 // ---- fyprt_group_denoise_temporal*: the temporal denoiser (rt_temporal.h) on the group's bands, as fyprt_group_denoise* above: the band
@@ -731,54 +679,26 @@ static int group_temporal_check(fyprt_group* g, const fyprt_temporal_params* p, 
     return group_temporal_check_state(g, who);
 }
 
-// The temporal call (group_temporal_plan, without stage 2 while the group holds no history): prepare; the guides; the prepared colour
-// the variance estimate reads (stage 1); with a history the moved flags of a pending edit — nothing pulls what they are, so no `done` —
-// and the history window (stage 2: dt.hist[dtCur]); the reprojection, its taps within the band plus min(historyRows, H) rows either
-// side; per iteration k the colour and variance it reads (stage 3 + k) and the iteration, colour dn.col[1] -> [0] -> [1] ..., variance
-// dt.var[0] -> [1] -> [0] ..., iteration 0 feeding dt.hist[dtCur ^ 1] back.  Every iteration waits for its pullers: iteration 0
-// overwrites the prepared colour of stage 1.  The members' bookkeeping (dtCur, dtValid, dtGroup, dtPV, dtSnapPending) advances only
-// once everything is enqueued.
-// scale > 1: the low-res stage of fyprt_group_denoise_upscale* (group_upscale_plan, group_upscale_steps), e in dn.col[(iterations + 1) & 1].
+// The temporal call: the members' buffers; the plan (without stage 2 while the group holds no history); the list (temporal_steps), a
+// band's history window min(historyRows, H) rows either side of it; the engine; the members' bookkeeping, which advances only once
+// everything is enqueued.  up: as group_spatial_call's.
 static int group_temporal_call(fyprt_group* g, const fyprt_temporal_params* p, uint32_t historyRows, int root, uint32_t* rgba8, float4* radiance4, bool timed,
-                               uint32_t scale = 1u) {
-    const fyprt_denoise_params& sp = p->spatial;
-    const uint32_t H = g->ctx[0]->H, R = std::min(historyRows, H);
+                               const fyprt_upscale_params* up = nullptr) {
+    const uint32_t H = g->ctx[0]->H, R = std::min(historyRows, H), iterations = p->spatial.iterations;
     for (fyprt_context* c : g->ctx) { HIPCHK(c, hipSetDevice(c->device)); TRY(ensure_dt_buffers(c)); }      // (may drop the history)
-    const bool history = group_has_history(g), keep = scale > 1u;
+    const bool history = group_has_history(g);
     std::vector<DnXfer> plan;
-    for (const DnXfer& t : keep ? group_upscale_plan(g->bounds, H, sp.iterations, true, R) : group_temporal_plan(g->bounds, H, sp.iterations, R))
+    for (const DnXfer& t : up ? group_upscale_plan(g->bounds, H, iterations, true, R) : group_temporal_plan(g->bounds, H, iterations, R))
         if (t.stage != 2 || history) plan.push_back(t);
-    std::vector<BandStep> steps = first_band_steps();
-    steps.push_back({1, [](fyprt_context* c) { return std::vector<XBuf>{{c->dn.col[0].p, kDnColourBytes}}; }, false, false, nullptr, false});
-    if (history) {
-        steps.push_back({-1, nullptr, false, false, [](fyprt_context* c, const DnFrame&, DnBand) { if (dt_motion_pending(c, true)) launch_dt_moved(c); }, false});
-        steps.push_back({2, [](fyprt_context* c) { return std::vector<XBuf>{{c->dt.hist[c->dtCur].p, kDtHistoryBytes}}; }, false, false, nullptr, false});
-    }
-    steps.push_back({-1, nullptr, false, false, [=](fyprt_context* c, const DnFrame& fr, DnBand band) {
-        const DnBand window{band.rowBegin > R ? band.rowBegin - R : 0u, std::min(H, band.rowEnd + R)};
-        launch_dt_reproject(c, fr, make_dt_call(c, *p, history), band, window, dt_motion_pending(c, history));
-    }, true});
-    for (uint32_t k = 0; k < sp.iterations; ++k) {
-        DnIter it = make_dn_iter(sp, k, false);
-        if (keep) it.last = 0u;
-        const bool feedback = k == 0 && p->feedback;
-        steps.push_back({3 + (int)k, [k](fyprt_context* c) { return std::vector<XBuf>{{c->dn.col[(k + 1u) & 1u].p, kDnColourBytes}, {c->dt.var[k & 1u].p, kDtVarianceBytes}}; }, true, it.last != 0,
-                         [k, it, feedback](fyprt_context* c, const DnFrame& fr, DnBand band) {
-                             launch_dt_iterate(c, fr, it, band, c->dn.col[(k + 1u) & 1u].p, c->dn.col[k & 1u].p, c->dt.var[k & 1u].p, c->dt.var[(k + 1u) & 1u].p, feedback ? c->dt.hist[c->dtCur ^ 1].p : nullptr);
-                         }, true});
-    }
-    if (keep) group_upscale_steps(steps, sp, scale, 3 + (int)sp.iterations, (int)((sp.iterations + 1u) & 1u), false);
-    else if (sp.iterations == 0) steps.push_back(finish_band_step(1));
-    TRY(group_filter_enqueue(g, plan, steps, sp.demodulate_albedo, root, rgba8, radiance4, timed, scale));
-    for (fyprt_context* c : g->ctx) {
-        c->dtCur ^= 1; c->dtValid = true; c->dtGroup = g->id; c->dtSnapPending = false; std::memcpy(c->dtPV, c->framePV, 64);
-    }
+    const std::vector<BandStep> steps = up ? upscale_steps(*up, history, R, FYPRT_UP_PRIMARY_EARLY != 0) : temporal_steps(*p, history, R);
+    TRY(group_filter_enqueue(g, plan, steps, p->spatial.demodulate_albedo, root, rgba8, radiance4, timed, up ? up->scale : 1u));
+    for (fyprt_context* c : g->ctx) dt_advance(c, g->id);
     return FYPRT_OK;
 }
 // A failed enqueue leaves some bands' new history written and others' not: the group's history is dropped instead.
 static int group_temporal_call_or_drop(fyprt_group* g, const fyprt_temporal_params* p, uint32_t historyRows, int root, uint32_t* rgba8, float4* radiance4, bool timed,
-                                       uint32_t scale = 1u) {
-    const int rc = group_temporal_call(g, p, historyRows, root, rgba8, radiance4, timed, scale);
+                                       const fyprt_upscale_params* up = nullptr) {
+    const int rc = group_temporal_call(g, p, historyRows, root, rgba8, radiance4, timed, up);
     if (rc != FYPRT_OK) for (fyprt_context* c : g->ctx) c->drop_history();
     return rc;
 }
@@ -801,9 +721,7 @@ int fyprt_group_denoise_temporal_reset(fyprt_group* g) {
 
 // The transfers of one fyprt_group_denoise_temporal* call in issue order, entries as fyprt_group_denoise_plan's.
 int fyprt_group_denoise_temporal_plan(const uint32_t* row_bounds, int n, uint32_t height, uint32_t iterations, uint32_t history_rows, uint32_t* out5, int capacity) {
-    int at;
-    if (!row_bounds || n <= 0 || iterations > 8u || bad_bands(row_bounds, n, height, &at)) return FYPRT_EINVAL;
-    return export_plan(group_temporal_plan(std::vector<uint32_t>(row_bounds, row_bounds + n + 1), height, iterations, history_rows), out5, capacity);
+    return export_checked_plan(row_bounds, n, height, iterations, out5, capacity, [&](const std::vector<uint32_t>& b) { return group_temporal_plan(b, height, iterations, history_rows); });
 }
 
 // ---- fyprt_group_denoise_upscale*: the guided upscaler (rt_upscale.h) on the group's bands.  The low-res stage is the group's (either call
@@ -835,8 +753,8 @@ static int group_ensure_up_buffers(fyprt_group* g, uint32_t s) {
     return FYPRT_OK;
 }
 static int group_upscale_call(fyprt_group* g, const fyprt_upscale_params* p, uint32_t historyRows, int root, uint32_t* rgba8, float4* radiance4, bool timed) {
-    const int rc = p->temporal ? group_temporal_call_or_drop(g, &p->filter, historyRows, root, rgba8, radiance4, timed, p->scale)
-                               : group_spatial_call(g, &p->filter.spatial, root, rgba8, radiance4, timed, p->scale);
+    const int rc = p->temporal ? group_temporal_call_or_drop(g, &p->filter, historyRows, root, rgba8, radiance4, timed, p)
+                               : group_spatial_call(g, &p->filter.spatial, root, rgba8, radiance4, timed, p);
     if (rc == FYPRT_OK) for (fyprt_context* c : g->ctx) c->upValid = true;
     return rc;
 }
@@ -856,9 +774,8 @@ int fyprt_group_denoise_upscale_device(fyprt_group* g, const fyprt_upscale_param
 // The transfers of one fyprt_group_denoise_upscale* call in issue order, entries as fyprt_group_denoise_plan's.
 int fyprt_group_denoise_upscale_plan(const uint32_t* row_bounds, int n, uint32_t height, uint32_t iterations, uint32_t temporal, uint32_t history_rows, uint32_t* out5,
                                      int capacity) {
-    int at;
-    if (!row_bounds || n <= 0 || iterations > 8u || bad_bands(row_bounds, n, height, &at)) return FYPRT_EINVAL;
-    return export_plan(group_upscale_plan(std::vector<uint32_t>(row_bounds, row_bounds + n + 1), height, iterations, temporal != 0, history_rows), out5, capacity);
+    return export_checked_plan(row_bounds, n, height, iterations, out5, capacity,
+                               [&](const std::vector<uint32_t>& b) { return group_upscale_plan(b, height, iterations, temporal != 0, history_rows); });
 }
 
 // Cost-balanced bands: new boundaries from the time each band took last frame, assuming a band's cost is spread evenly over its rows
