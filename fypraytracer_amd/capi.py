@@ -71,6 +71,11 @@ QUERY_MAX_HITS = 8               # FYPRT_QUERY_MAX_HITS
 POINT_DTYPE = np.dtype([("position", "<f4", (3,)), ("max_distance", "<f4")])
 POINT_HIT_DTYPE = np.dtype([("distance2", "<f4"), ("triangle", "<u4"), ("u", "<f4"), ("v", "<f4")])
 assert POINT_DTYPE.itemsize == 16 and POINT_HIT_DTYPE.itemsize == 16
+# box-overlap queries (fyprt_overlap_boxes): fyprt_box (32 B; the pads are ignored); the answers are bare uint32 triangle indices
+BOX_DTYPE = np.dtype([("lo", "<f4", (3,)), ("pad0", "<u4"), ("hi", "<f4", (3,)), ("pad1", "<u4")])
+assert BOX_DTYPE.itemsize == 32
+OVERLAP_MAX_HITS = 32            # FYPRT_OVERLAP_MAX_HITS
+NO_TRIANGLE = 0xFFFFFFFF         # an unused slot of a box's answer; as `after`, a finished box
 RENDER_RAYS_CHUNK = 1 << 21      # FYPRT_RENDER_RAYS_CHUNK: rays per internal pass of fyprt_render_rays*
 BVH_NODE_DTYPE = np.dtype([("origin", "<f4", 3), ("ex", "u1", 3), ("meta", "u1"), ("child", "<i4", 4),
                            ("qlo", "u1", (3, 4)), ("qhi", "u1", (3, 4)), ("pad", "<u4", 2)])
@@ -252,6 +257,7 @@ EXPORTED_SYMBOLS = [
     "fyprt_regraft_meshes", "fyprt_tree_cost",
     "fyprt_kept_primary_frames",
     "fyprt_nearest_points", "fyprt_nearest_points_device",
+    "fyprt_overlap_boxes", "fyprt_overlap_boxes_device",
 ]
 # enum fyprt_probe (fyprt_selftest_functions) and the 32-bit words of one input / output record of each probe
 (PROBE_SINCOS, PROBE_ACOS, PROBE_POW5, PROBE_RND, PROBE_OCT_ENCODE, PROBE_OCT_DECODE, PROBE_PACK_ABGR, PROBE_UNPACK_ABGR, PROBE_EVAL_BRDF,
@@ -333,6 +339,9 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     if hasattr(lib, "fyprt_nearest_points"):   # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
         lib.fyprt_nearest_points.argtypes = [vp, vp, vp, u32, u32, vp, vp, C.POINTER(FrameStats)]
         lib.fyprt_nearest_points_device.argtypes = [vp, vp, vp, u32, u32, vp, vp]
+    if hasattr(lib, "fyprt_overlap_boxes"):
+        lib.fyprt_overlap_boxes.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp, C.POINTER(FrameStats)]
+        lib.fyprt_overlap_boxes_device.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp]
     if hasattr(lib, "fyprt_render_rays"):    # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
         lib.fyprt_render_rays.argtypes = [vp, C.POINTER(Settings), u32, vp, vp, u32, u32, vp, vp, C.POINTER(FrameStats)]
         lib.fyprt_render_rays_device.argtypes = [vp, C.POINTER(Settings), u32, vp, vp, u32, u32, vp, vp]
@@ -805,9 +814,22 @@ class Context:
         return rec
 
     @staticmethod
-    def _check_max_hits(who, max_hits):
-        if not isinstance(max_hits, (int, np.integer)) or isinstance(max_hits, bool) or not 1 <= int(max_hits) <= QUERY_MAX_HITS:
-            raise ValueError(f"{who}: max_hits must be an integer in 1..{QUERY_MAX_HITS}, got {max_hits!r}")
+    def _box_records(who, lo, hi):
+        l, h = np.asarray(lo, dtype=np.float32), np.asarray(hi, dtype=np.float32)
+        for name, a in (("lo", l), ("hi", h)):
+            if a.ndim == 0 or a.size % 3 or (a.ndim > 1 and a.shape[-1] != 3):
+                raise ValueError(f"{who}: {name} must be (N, 3), got shape {a.shape}")
+        l, h = l.reshape(-1, 3), h.reshape(-1, 3)
+        if len(l) != len(h):
+            raise ValueError(f"{who}: {len(l)} lower but {len(h)} upper corners")
+        rec = np.zeros(len(l), dtype=BOX_DTYPE)
+        rec["lo"], rec["hi"] = l, h
+        return rec
+
+    @staticmethod
+    def _check_max_hits(who, max_hits, cap=QUERY_MAX_HITS):
+        if not isinstance(max_hits, (int, np.integer)) or isinstance(max_hits, bool) or not 1 <= int(max_hits) <= cap:
+            raise ValueError(f"{who}: max_hits must be an integer in 1..{cap}, got {max_hits!r}")
         return int(max_hits)
 
     @staticmethod
@@ -819,15 +841,19 @@ class Context:
             raise ValueError(f"{who}: after must be {n} {dtype_name} records")
         return np.ascontiguousarray(aft.reshape(-1))
 
-    def _check_record_tensor(self, who, name, t, width, after=None):
-        """`t`: the contiguous float32 (N, width) tensor of `name` on this context's GPU; `after`: None or (N, 4) beside it.  Returns N."""
+    def _check_record_tensor(self, who, name, t, width, after=None, after_words=4):
+        """`t`: the contiguous float32 (N, width) tensor of `name` on this context's GPU; `after`: None or (N, 4) beside it — for
+        `after_words` 1, the box query's, an int32 (N,) tensor.  Returns N."""
         import torch
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != width or not t.is_contiguous():
             raise ValueError(f"{who}: {name} must be a contiguous float32 (N, {width}) tensor")
         if t.device.type != "cuda" or (t.device.index if t.device.index is not None else torch.cuda.current_device()) != self.device:
             raise ValueError(f"{who}: {name} must be on cuda:{self.device}, the context's GPU")
         n = t.shape[0]
-        if after is not None and (after.dtype != torch.float32 or tuple(after.shape) != (n, 4) or not after.is_contiguous() or after.device != t.device):
+        if after is not None and after_words == 1:
+            if not isinstance(after, torch.Tensor) or after.dtype != torch.int32 or tuple(after.shape) != (n,) or not after.is_contiguous() or after.device != t.device:
+                raise ValueError(f"{who}: after must be a contiguous int32 (N,) tensor on the {name}' device")
+        elif after is not None and (after.dtype != torch.float32 or tuple(after.shape) != (n, 4) or not after.is_contiguous() or after.device != t.device):
             raise ValueError(f"{who}: after must be a contiguous float32 (N, 4) tensor on the {name}' device")
         return n
 
@@ -895,23 +921,28 @@ class Context:
                                                          C.c_void_p(out.data_ptr())))
         return out
 
-    def _list_query(self, fn, rec, aft, k, hit_dtype, with_stats):
+    def _list_query(self, fn, rec, aft, k, hit_dtype, with_stats, totals=False):
+        """One blocking list query: (hits (N, K) of `hit_dtype`, counts[, totals][, stats]); `totals`: the entry point has the box
+        query's third result array."""
         n = len(rec)
         hits = np.empty((n, k), dtype=hit_dtype)
         counts = np.empty(n, dtype=np.uint32)
+        extra = [np.empty(n, dtype=np.uint32)] if totals else []
         st = FrameStats()
-        self._check(getattr(self.lib, fn)(self.h, _ptr(rec), _ptr(aft), n, k, _ptr(hits), _ptr(counts), C.byref(st)))
-        return (hits, counts, st) if with_stats else (hits, counts)
+        self._check(getattr(self.lib, fn)(self.h, _ptr(rec), _ptr(aft), n, k, _ptr(hits), _ptr(counts), *[_ptr(t) for t in extra], C.byref(st)))
+        return (hits, counts, *extra, st) if with_stats else (hits, counts, *extra)
 
-    def _list_query_tensor(self, fn, who, name, rec, width, k, after):
+    def _list_query_tensor(self, fn, who, name, rec, width, k, after, words=4):
+        """One list query on device tensors: float32 (N, K, 4) records and int32 counts; with `words` 1, the box query's, int32 (N, K)
+        indices, counts and totals."""
         import torch
-        n = self._check_record_tensor(who, name, rec, width, after)
-        hits = torch.empty((n, k, 4), dtype=torch.float32, device=rec.device)
-        counts = torch.empty((n,), dtype=torch.int32, device=rec.device)
+        n = self._check_record_tensor(who, name, rec, width, after, words)
+        hits = torch.empty((n, k, 4) if words == 4 else (n, k), dtype=torch.float32 if words == 4 else torch.int32, device=rec.device)
+        out = [torch.empty((n,), dtype=torch.int32, device=rec.device) for _ in range(1 if words == 4 else 2)]
         with self._on_context_stream(rec.device):
             self._check(getattr(self.lib, fn)(self.h, C.c_void_p(rec.data_ptr()), C.c_void_p(after.data_ptr()) if after is not None else None,
-                                            n, k, C.c_void_p(hits.data_ptr()), C.c_void_p(counts.data_ptr())))
-        return hits, counts
+                                            n, k, C.c_void_p(hits.data_ptr()), *[C.c_void_p(t.data_ptr()) for t in out]))
+        return (hits, *out)
 
     def trace_ray_hits(self, origins, directions, tmin=0.0, tmax=np.inf, max_hits=QUERY_MAX_HITS, after=None, with_stats=False):
         """Ordered multi-hit query (fyprt_trace_ray_hits, blocking): the `max_hits` nearest accepted triangles per ray, ascending by
@@ -969,6 +1000,37 @@ class Context:
         rec = self._point_records("triangles_within", points, radius)
         return self._all_records(len(rec), k, POINT_HIT_DTYPE, lambda live, after: self.nearest_points(
             rec["position"][live], rec["max_distance"][live], k, after))
+
+    def overlap_boxes(self, lo, hi, max_hits=OVERLAP_MAX_HITS, after=None, with_stats=False):
+        """Box-overlap query (fyprt_overlap_boxes, blocking): the `max_hits` lowest indices of the triangles that touch each closed box
+        [lo, hi].  `lo` / `hi`: (N, 3); `after`: None or N uint32 — only triangles with a greater index are returned, and NO_TRIANGLE
+        (an unused slot) finishes the box.  Returns (triangles (N, K) uint32 ascending, unused slots NO_TRIANGLE; counts (N,) uint32;
+        totals (N,) uint32: every accepted triangle, also those beyond K); with `with_stats` also the FrameStats of the launch."""
+        k = self._check_max_hits("overlap_boxes", max_hits, OVERLAP_MAX_HITS)
+        rec = self._box_records("overlap_boxes", lo, hi)
+        aft = None
+        if after is not None:
+            aft = np.asarray(after)
+            if aft.dtype != np.uint32 or aft.size != len(rec):
+                raise ValueError(f"overlap_boxes: after must be {len(rec)} uint32 triangle indices")
+            aft = np.ascontiguousarray(aft.reshape(-1))
+        return self._list_query("fyprt_overlap_boxes", rec, aft, k, np.uint32, with_stats, totals=True)
+
+    def overlap_boxes_tensor(self, boxes, max_hits, after=None):
+        """Box-overlap query on device tensors (fyprt_overlap_boxes_device).  `boxes`: contiguous float32 (N, 8) tensor on this context's
+        GPU, one fyprt_box per row (lo, pad, hi, pad); `after`: None or a contiguous int32 (N,) tensor of indices (the last column of an
+        earlier call: `triangles[:, -1].contiguous()`).  Returns int32 tensors: triangles (N, K) (unused slots -1), counts (N,), totals
+        (N,).  Ordered against torch's current stream exactly as trace_rays_tensor is."""
+        k = self._check_max_hits("overlap_boxes_tensor", max_hits, OVERLAP_MAX_HITS)
+        return self._list_query_tensor("fyprt_overlap_boxes_device", "overlap_boxes_tensor", "boxes", boxes, 8, k, after, words=1)
+
+    def triangles_in_boxes(self, lo, hi, max_hits=OVERLAP_MAX_HITS):
+        """Every triangle that touches every box, ascending by index: continuation passes of overlap_boxes until every box is
+        finished.  Returns (indices, offsets) shaped as triangles_within's: flat uint32 indices, box i's in
+        indices[offsets[i]:offsets[i + 1]], offsets int64 (N + 1,)."""
+        k = self._check_max_hits("triangles_in_boxes", max_hits, OVERLAP_MAX_HITS)
+        rec = self._box_records("triangles_in_boxes", lo, hi)
+        return self._all_records(len(rec), k, np.uint32, lambda live, after: self.overlap_boxes(rec["lo"][live], rec["hi"][live], k, after)[:2])
 
     def render_rays(self, origins, directions, settings: Settings, frame_index=1, first_index=0, pixel_indices=None, tmin=0.0, tmax=np.inf,
                     want_payload=False, with_stats=False):

@@ -18,6 +18,7 @@
 #include "rt_paths.h"
 #include "rt_query.h"
 #include "rt_points.h"
+#include "rt_boxes.h"
 #include "rt_denoise.h"
 #include "rt_temporal.h"
 #include "rt_upscale.h"
@@ -223,11 +224,13 @@ struct fyprt_context {
     DevBuf<float4> shadowTasks; DevBuf<uint32_t> queueCounters, sortCounts, sortOffset, sortTotal, sortIndex; DevBuf<uint8_t> sortKeys; DevBuf<uint16_t> sortHist;
     // One query family's state, allocated by its first query and kept: its own counters ([0..4] as a frame's launch, [5] low word = queue
     // head of the persistent kernel), the host entry's staging (records in, `after` records, results in 4-byte words, counts), grown on
-    // demand, its two timing events, the occupancy of its persistent kernel (per kind for the ray query, [0] for the list queries)
+    // demand, its two timing events, the occupancy of its persistent kernel (per kind for the ray query, [0] for the list queries).  The
+    // box query's `after` words share `after` (a quad holds four), its totals lie in `out` behind the triangle indices
     struct QueryFamily {
         DevBuf<unsigned long long> counters; DevBuf<float4> in, after; DevBuf<uint32_t> out, counts; Event ev[2]; OccCache occ[2];
     };
     QueryFamily rayQuery, hitsQuery, pointsQuery;      // fyprt_trace_rays* (and the primary segments of fyprt_render_rays*), fyprt_trace_ray_hits*, fyprt_nearest_points*
+    QueryFamily boxesQuery;                            // fyprt_overlap_boxes*
     // radiance queries (fyprt_render_rays*, rt_query.h: k_render_rays_primary + the path stages), allocated on first use for
     // min(count, FYPRT_RENDER_RAYS_CHUNK) rays and kept: primary records, path state, ray / result lists, live lists, list counters + queue
     // heads; the host entry's staging (rays, pixel indices, radiance) and its two timing events
@@ -385,8 +388,8 @@ static void add_ray_stats(fyprt_frame_stats* s, int k, const unsigned long long*
 
 // ---- what the query families share (the entry points: "batched ray queries" below)
 // Enqueues one query launch on the context stream (q: the record pointers in device memory and count > 0; kernels[simple][counted]);
-// `timed` brackets it with the family's events.  A workgroup's LDS is the stack plus `listBytes` per thread (the list queries' 16 bytes
-// per entry of this call's max_hits).  The families have always differed in how tuning key 2 and a failed occupancy query are taken,
+// `timed` brackets it with the family's events.  A workgroup's LDS is the stack plus `listBytes` per thread (the list queries' 16 bytes,
+// the box query's 4 bytes per entry of this call's max_hits).  The families have always differed in how tuning key 2 and a failed occupancy query are taken,
 // and keep doing so: `clampWg` holds key 2 to the occupancy, `occFallback` stands in for an occupancy the runtime cannot give.
 template <class Q>
 static int launch_query(fyprt_context* c, fyprt_context::QueryFamily& f, OccCache& occ, Q q, void (*const kernels[2][2])(DevScene, Q), size_t listBytes,
@@ -418,7 +421,12 @@ static int launch_query(fyprt_context* c, fyprt_context::QueryFamily& f, OccCach
 // A blocking entry point behind its checks: host records through the family's staging (which grows and is kept), one timed launch by
 // `enqueue(in, after, out, counts)` on the staging pointers, results back, the launch's time and ray counters into `stats`.
 // inQuads: float4s per input record; after / counts: the list queries' (counts is staged for them whether or not the caller wants it).
-struct HostQuery { const void* in; size_t inQuads; const void* after; void* out; size_t outBytes; uint32_t* counts; bool list; };
+// afterBytes: one `after` record; tailBytes: a second result array staged in `out` behind the first (the box query's totals), copied
+// back to `tail` if the caller wants it.
+struct HostQuery {
+    const void* in; size_t inQuads; const void* after; void* out; size_t outBytes; uint32_t* counts; bool list;
+    size_t afterBytes = sizeof(float4); void* tail = nullptr; size_t tailBytes = 0;
+};
 template <class Enqueue>
 static int run_host_query(fyprt_context* c, fyprt_context::QueryFamily& f, const HostQuery& h, uint32_t count, fyprt_frame_stats* stats, Enqueue enqueue) {
     if (stats) std::memset(stats, 0, sizeof *stats);
@@ -426,14 +434,16 @@ static int run_host_query(fyprt_context* c, fyprt_context::QueryFamily& f, const
     HIPCHK(c, hipSetDevice(c->device));
     for (Event& e : f.ev) HIPCHK(c, create(e));
     if (f.in.n < (size_t)count * h.inQuads) { HIPCHK(c, f.in.alloc((size_t)count * h.inQuads)); }         // staging grows, is kept
-    if (h.after && f.after.n < (size_t)count) { HIPCHK(c, f.after.alloc(count)); }
-    if (f.out.bytes() < h.outBytes) { HIPCHK(c, f.out.alloc(h.outBytes / 4)); }
+    const size_t afterQuads = ((size_t)count * h.afterBytes + sizeof(float4) - 1) / sizeof(float4);
+    if (h.after && f.after.n < afterQuads) { HIPCHK(c, f.after.alloc(afterQuads)); }
+    if (f.out.bytes() < h.outBytes + h.tailBytes) { HIPCHK(c, f.out.alloc((h.outBytes + h.tailBytes) / 4)); }
     if (h.list && f.counts.n < (size_t)count) { HIPCHK(c, f.counts.alloc(count)); }
     HIPCHK(c, hipMemcpyAsync(f.in.p, h.in, (size_t)count * h.inQuads * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    if (h.after) HIPCHK(c, hipMemcpyAsync(f.after.p, h.after, (size_t)count * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    if (h.after) HIPCHK(c, hipMemcpyAsync(f.after.p, h.after, (size_t)count * h.afterBytes, hipMemcpyHostToDevice, c->stream));
     TRY(enqueue(f.in.p, h.after ? f.after.p : nullptr, f.out.p, f.counts.p));
     HIPCHK(c, hipMemcpyAsync(h.out, f.out.p, h.outBytes, hipMemcpyDeviceToHost, c->stream));
     if (h.counts) HIPCHK(c, hipMemcpyAsync(h.counts, f.counts.p, (size_t)count * 4u, hipMemcpyDeviceToHost, c->stream));
+    if (h.tail) HIPCHK(c, hipMemcpyAsync(h.tail, f.out.p + h.outBytes / 4, h.tailBytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (stats) {
         float ms = 0.0f;
@@ -2326,6 +2336,47 @@ int fyprt_nearest_points(fyprt_context* c, const fyprt_point* points, const fypr
 int fyprt_nearest_points_device(fyprt_context* c, const void* points, const void* after, uint32_t count, uint32_t max_hits, void* hits, void* hit_counts) {
     TRY(check_list_query(c, "fyprt_nearest_points_device", "points", "query", points, after, count, max_hits, hits, hit_counts, true));
     return device_list_query(c, kNearestPoints, points, after, count, max_hits, hits, hit_counts);
+}
+
+// ---- box-overlap queries (rt_boxes.h: k_query_boxes / k_query_boxes_simple): a list query whose entries are bare triangle indices,
+// with a total beside the count.  The scene is read, the query's own results and counters are written, no frame state moves.
+static int check_overlap_boxes(fyprt_context* c, const char* who, const void* boxes, const void* after, uint32_t count, uint32_t maxHits, const void* triangles,
+                               const void* hitCounts, const void* totals, bool device) {
+    if (!c) return FYPRT_EINVAL;
+    if (maxHits == 0 || maxHits > FYPRT_OVERLAP_MAX_HITS) return c->fail(FYPRT_EINVAL, std::string(who) + ": max_hits must be 1.." + std::to_string(FYPRT_OVERLAP_MAX_HITS));
+    if (count && (!boxes || !triangles)) return c->fail(FYPRT_EINVAL, std::string(who) + ": NULL boxes / triangles with a non-zero count");
+    if (device && (((uintptr_t)boxes & 15u) || ((uintptr_t)after & 3u) || ((uintptr_t)triangles & 3u) || ((uintptr_t)hitCounts & 3u) || ((uintptr_t)totals & 3u)))   // 16-byte loads, 4-byte words
+        return c->fail(FYPRT_EINVAL, std::string(who) + ": boxes must be 16-byte and after, triangles, hit_counts and totals 4-byte aligned");
+    if (c->hostOnly) return c->fail(FYPRT_ESTATE, std::string(who) + ": host-only context (device -1) cannot query");
+    if (!c->haveScene) return c->fail(FYPRT_ESTATE, std::string(who) + " before fyprt_upload_scene");
+    return FYPRT_OK;
+}
+// (device memory, count > 0, after / counts / totals may be NULL)
+static int enqueue_overlap_boxes(fyprt_context* c, const float4* boxes, const uint32_t* after, uint32_t count, uint32_t maxHits, uint32_t* triangles, uint32_t* counts,
+                                 uint32_t* totals, bool timed) {
+    static void (*const kBoxes[2][2])(DevScene, QueryBoxes) = {{k_query_boxes<false>, k_query_boxes<true>}, {k_query_boxes_simple<false>, k_query_boxes_simple<true>}};
+    fyprt_context::QueryFamily& f = c->boxesQuery;
+    QueryBoxes q{};
+    q.boxes = boxes; q.after = after; q.triangles = triangles; q.counts = counts; q.totals = totals; q.count = count; q.maxHits = maxHits;
+    // as the list queries: key 2 no higher than the occupancy, 2 workgroups per CU without one
+    return launch_query(c, f, f.occ[0], q, kBoxes, (size_t)maxHits * 4u, true, 2, timed);
+}
+
+int fyprt_overlap_boxes(fyprt_context* c, const fyprt_box* boxes, const uint32_t* after, uint32_t count, uint32_t max_hits, uint32_t* triangles,
+                        uint32_t* hit_counts, uint32_t* totals, fyprt_frame_stats* stats) {
+    TRY(check_overlap_boxes(c, "fyprt_overlap_boxes", boxes, after, count, max_hits, triangles, hit_counts, totals, false));
+    HostQuery h{boxes, 2, after, triangles, (size_t)count * max_hits * 4u, hit_counts, true};
+    h.afterBytes = 4u; h.tail = totals; h.tailBytes = (size_t)count * 4u;
+    return run_host_query(c, c->boxesQuery, h, count, stats, [&](const float4* dIn, const float4* dAfter, uint32_t* dOut, uint32_t* dCounts) {
+        return enqueue_overlap_boxes(c, dIn, reinterpret_cast<const uint32_t*>(dAfter), count, max_hits, dOut, dCounts, dOut + (size_t)count * max_hits, true); });
+}
+int fyprt_overlap_boxes_device(fyprt_context* c, const void* boxes, const void* after, uint32_t count, uint32_t max_hits, void* triangles, void* hit_counts,
+                               void* totals) {
+    TRY(check_overlap_boxes(c, "fyprt_overlap_boxes_device", boxes, after, count, max_hits, triangles, hit_counts, totals, true));
+    if (count == 0) return FYPRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    return enqueue_overlap_boxes(c, static_cast<const float4*>(boxes), static_cast<const uint32_t*>(after), count, max_hits, static_cast<uint32_t*>(triangles),
+                                 static_cast<uint32_t*>(hit_counts), static_cast<uint32_t*>(totals), false);
 }
 
 // ---- radiance queries (rt_query.h: k_render_rays_primary; rt_paths.h: the path stages with CAM = RaySource).  A frame's sample of

@@ -749,6 +749,55 @@ int fyprt_nearest_points(fyprt_context* ctx, const fyprt_point* points, const fy
 int fyprt_nearest_points_device(fyprt_context* ctx, const void* points, const void* after, uint32_t count, uint32_t max_hits, void* hits,
                                 void* hit_counts);
 
+/* Box-overlap query: the triangles that touch each axis-aligned box [lo, hi], lowest indices first ("Box-overlap
+ * queries") — the triangles in a region for an editor's marquee, a physics broad phase, a voxeliser, a spatial cache.
+ * Every operation below is rounded on its own in IEEE binary32 (no contraction), dot(a,b) = (a.x*b.x + a.y*b.y) + a.z*b.z,
+ * cross(a,b) = (a.y*b.z - b.y*a.z, a.z*b.x - b.z*a.x, a.x*b.y - b.x*a.y).  min and max are selects, min(a,b) = a < b ? a : b and
+ * max(a,b) = a > b ? a : b, of three values min(min(x0, x1), x2); every comparison is written positively, so a NaN anywhere in a record
+ * rejects it.
+ *   Test        : for the box and a leaf record (v0, e1, e2) as fyprt_export_bvh returns it, the separating-axis test in this order:
+ *                   1. v1 = v0 + e1;  v2 = v0 + e2                                                  (per component)
+ *                   2. box axes, on the untranslated coordinates: for each axis a, mn / mx over v0.a, v1.a, v2.a:
+ *                        require mn <= hi.a and mx >= lo.a                                           (the box is closed)
+ *                   3. c = (lo + hi) * 0.5f;  h = (hi - lo) * 0.5f;  p_k = v_k - c
+ *                   4. nine edge axes: for each f in (e1, e2 - e1, e2), mn / mx over s_0, s_1, s_2:
+ *                        x: s_k = p_k.z*f.y - p_k.y*f.z;  r = h.y*|f.z| + h.z*|f.y|
+ *                        y: s_k = p_k.x*f.z - p_k.z*f.x;  r = h.x*|f.z| + h.z*|f.x|
+ *                        z: s_k = p_k.y*f.x - p_k.x*f.y;  r = h.x*|f.y| + h.y*|f.x|
+ *                        require mn <= r and mx >= -r
+ *                   5. plane: n = cross(e1, e2);  d = dot(n, p_0);  r = (h.x*|n.x| + h.y*|n.y|) + h.z*|n.z|
+ *                        require d <= r and d >= -r
+ *                 A zero-area record passes 4 and 5 with 0 <= 0: step 2 alone decides it.
+ *   Acceptance  : every requirement holds and, with `after`, the triangle index is greater than after[i].
+ *   Touching    : is decided by this rounded arithmetic.  A box that is the single point v0 of a record always accepts that record; a
+ *                 box at the caller's own second vertex V1 may not, because the record holds v0 + fl(V1 - V0), not V1.
+ *   Invalid box : on any axis !(lo <= hi), or lo + hi or hi - lo not finite — zero records without traversal, counted as a query with
+ *                 no tests.  The pads are ignored.
+ *   Order       : the records of box i are its max_hits smallest accepted triangle indices, ascending; unused slots are 0xFFFFFFFF.
+ *                 hit_counts[i] = the number of used slots, totals[i] = the number of ALL accepted triangles, also those beyond max_hits
+ *                 (the traversal visits them anyway).  Both may be NULL.  The answer does not depend on the tree, the builder or the
+ *                 visiting order.
+ *   Continuation: as the other list queries' — after[i] == 0xFFFFFFFF (the unused slot) finishes the box: zero records, total 0, no
+ *                 traversal.  Passing each pass's LAST slot per box back in lists every triangle exactly once; totals[i] tells how
+ *                 many are still to come, this pass included.
+ * Errors, in this order: FYPRT_EINVAL for a NULL context, max_hits 0 or above FYPRT_OVERLAP_MAX_HITS, NULL boxes / triangles with
+ * count > 0, and (device entry) boxes not 16-byte or after, triangles, hit_counts or totals not 4-byte aligned; FYPRT_ESTATE on a
+ * host-only context or before fyprt_upload_scene; count 0 returns FYPRT_OK and launches nothing.
+ * No frame state moves: the query has its own counters, queue head and events, and the host entry's staging buffers grow on demand and
+ * are kept.  The kernel follows tuning key 15 (and keys 4, 5, 6, 9, 10) as the other queries'; each lane keeps its sorted list in LDS
+ * behind the traversal stack, 4 bytes per entry — with the deepest stack, 32 entries fill the 64 KB a workgroup may have, which is why
+ * the cap is 32.  With ray counting on, stats reports rays = boxes, box_tests = the valid child boxes tested, tri_tests, hits = boxes
+ * with at least one record, node_visits. */
+#define FYPRT_OVERLAP_MAX_HITS 32
+typedef struct fyprt_box { float lo[3]; uint32_t pad0; float hi[3]; uint32_t pad1; } fyprt_box;   /* 32 B, 16-B aligned on the device */
+/* Host memory, blocking.  `triangles`: count x max_hits indices, box-major.  `stats` may be NULL; it is filled as fyprt_nearest_points fills it. */
+int fyprt_overlap_boxes(fyprt_context* ctx, const fyprt_box* boxes, const uint32_t* after /* NULL or count */, uint32_t count,
+                        uint32_t max_hits, uint32_t* triangles /* count x max_hits */, uint32_t* hit_counts /* NULL or count */,
+                        uint32_t* totals /* NULL or count */, fyprt_frame_stats* stats /* may be NULL */);
+/* Device memory of the context's GPU, asynchronous on the context stream (fyprt_stream). */
+int fyprt_overlap_boxes_device(fyprt_context* ctx, const void* boxes, const void* after, uint32_t count, uint32_t max_hits, void* triangles,
+                               void* hit_counts, void* totals);
+
 /* ================================================================================================= radiance queries
  * New (no reference counterpart): the renderer's sample of techniques 0-6 for the caller's own rays — other camera models, light probes,
  * surface bakes, re-rendering a few pixels ("Radiance queries").  Only an uploaded scene is needed (no resize, no camera).

@@ -17,7 +17,12 @@ With --points K [K ...]: the nearest-point query (fyprt_nearest_points) on three
 median, minimum and maximum hipEvent ms, Mpoints/s, node visits, box and triangle tests per point (one counted call), and the ratio
 to the closest-hit query of the camera rays, timed in the same run.  Written to profiles/query/points_rate.jsonl unless --out names
 another file.
-  usage: python tools/query_rate.py --points 1 4 8 [--calls 20] [--out FILE.jsonl]"""
+  usage: python tools/query_rate.py --points 1 4 8 [--calls 20] [--out FILE.jsonl]
+With --boxes K [K ...]: the box-overlap query (fyprt_overlap_boxes) on three sets of 1920x1080 boxes centred on the camera hits, with
+half extents of 0.1 %, 0.5 % and 2 % of the scene diameter: per set and K the median, minimum and maximum hipEvent ms, Mboxes/s, node
+visits, box and triangle tests and accepted triangles per box (one counted call), and the ratio to the closest-hit query of the camera
+rays, timed in the same run.  Written to profiles/query/boxes_rate.jsonl unless --out names another file.
+  usage: python tools/query_rate.py --boxes 1 8 32 [--calls 20] [--out FILE.jsonl]"""
 import argparse
 import json
 import statistics
@@ -218,13 +223,66 @@ def main_points(a):
     out.write_text("\n".join(lines) + "\n")
 
 
+def boxes_rate(ctx, name, lo, hi, ks, calls, med0):
+    """One box set: the box-overlap query per K, warmed up and timed over `calls` calls, then one counted call."""
+    rows = []
+    for k in ks:
+        for _ in range(3):
+            ctx.overlap_boxes(lo, hi, max_hits=k)
+        ms = [ctx.overlap_boxes(lo, hi, max_hits=k, with_stats=True)[3].kernel_ms for _ in range(calls)]
+        ctx.set_ray_counting(True)
+        _, counts, totals, st = ctx.overlap_boxes(lo, hi, max_hits=k, with_stats=True)
+        ctx.set_ray_counting(False)
+        med = statistics.median(ms)
+        rows.append({"set": name, "scene": "hall_1M", "query": "boxes", "max_hits": k, "boxes": len(lo), "ms_median": round(med, 4),
+                     "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4), "calls": calls, "mboxes_per_s": round(len(lo) / med / 1e3, 1),
+                     "node_visits_per_box": round(st.node_visits / st.rays, 3), "box_tests_per_box": round(st.box_tests / st.rays, 3),
+                     "tri_tests_per_box": round(st.tri_tests / st.rays, 3), "accepted_per_box": round(float(totals.mean()), 3),
+                     "records_per_box": round(float(counts.mean()), 3), "ms_over_closest": round(med / med0, 3)})
+    return rows
+
+
+def main_boxes(a):
+    """Three sets of W x H boxes on the 1M hall, centred on the camera hits (a miss: half a diameter out along the ray), with half
+    extents of 0.1 %, 0.5 % and 2 % of the scene diameter; the closest-hit query of the camera rays is timed in the same run."""
+    W, H = 1920, 1080
+    n = W * H
+    hall, cam = scenes.hall_scene(), scenes.hall_camera(W, H)
+    ctx = capi.Context(0)
+    ctx.upload_scene(hall)
+    o, d = camera_rays(cam)
+    for _ in range(3):
+        ctx.trace_rays(o, d)
+    ms0 = [ctx.trace_rays(o, d, with_stats=True)[1].kernel_ms for _ in range(a.calls)]
+    med0 = statistics.median(ms0)
+    rows = [{"set": "a_camera", "scene": "hall_1M", "query": "closest", "rays": n, "ms_median": round(med0, 4), "ms_min": round(min(ms0), 4),
+             "ms_max": round(max(ms0), 4), "calls": a.calls, "mrays_per_s": round(n / med0 / 1e3, 1)}]
+    res = ctx.trace_rays(o, d)
+    pos = hall.world_vertices["position"].astype(np.float64)
+    diam = float(np.linalg.norm(pos.max(axis=0) - pos.min(axis=0)))
+    hit = res["objectIndex"] >= 0
+    centre = np.where(hit[:, None], res["worldPosition"], o + F32(0.5 * diam) * d).astype(F32)
+    for name, frac in (("a_small_0.1pct", 0.001), ("b_medium_0.5pct", 0.005), ("c_large_2pct", 0.02)):
+        h = F32(frac * diam)
+        rows += boxes_rate(ctx, name, (centre - h).astype(F32), (centre + h).astype(F32), a.boxes, a.calls, med0)
+    ctx.close()
+    lines = [json.dumps(r) for r in rows]
+    print("\n".join(lines), flush=True)
+    out = Path(a.out) if a.out else ROOT / "profiles" / "query" / "boxes_rate.jsonl"
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--out", default=None)
     ap.add_argument("--hits", type=int, nargs="+", default=None, metavar="K", help="time the multi-hit query at these max_hits instead")
     ap.add_argument("--points", type=int, nargs="+", default=None, metavar="K", help="time the nearest-point query at these max_hits instead")
+    ap.add_argument("--boxes", type=int, nargs="+", default=None, metavar="K", help="time the box-overlap query at these max_hits instead")
     a = ap.parse_args()
+    if a.boxes and not all(1 <= k <= capi.OVERLAP_MAX_HITS for k in a.boxes):
+        raise SystemExit(f"--boxes takes values in 1..{capi.OVERLAP_MAX_HITS}")
     if a.hits and not all(1 <= k <= capi.QUERY_MAX_HITS for k in a.hits):
         raise SystemExit(f"--hits takes values in 1..{capi.QUERY_MAX_HITS}")
     if a.points and not all(1 <= k <= capi.QUERY_MAX_HITS for k in a.points):
@@ -236,6 +294,8 @@ def main():
         return main_hits(a)
     if a.points:
         return main_points(a)
+    if a.boxes:
+        return main_boxes(a)
     W, H = 1920, 1080
     rows = []
     rng = np.random.default_rng(2024)
