@@ -258,6 +258,7 @@ EXPORTED_SYMBOLS = [
     "fyprt_kept_primary_frames",
     "fyprt_nearest_points", "fyprt_nearest_points_device",
     "fyprt_overlap_boxes", "fyprt_overlap_boxes_device",
+    "fyprt_set_mesh_query_masks", "fyprt_set_query_mask", "fyprt_get_query_filter",
 ]
 # enum fyprt_probe (fyprt_selftest_functions) and the 32-bit words of one input / output record of each probe
 (PROBE_SINCOS, PROBE_ACOS, PROBE_POW5, PROBE_RND, PROBE_OCT_ENCODE, PROBE_OCT_DECODE, PROBE_PACK_ABGR, PROBE_UNPACK_ABGR, PROBE_EVAL_BRDF,
@@ -342,6 +343,10 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     if hasattr(lib, "fyprt_overlap_boxes"):
         lib.fyprt_overlap_boxes.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp, C.POINTER(FrameStats)]
         lib.fyprt_overlap_boxes_device.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp]
+    if hasattr(lib, "fyprt_set_mesh_query_masks"):
+        lib.fyprt_set_mesh_query_masks.argtypes = [vp, vp, u32]
+        lib.fyprt_set_query_mask.argtypes = [vp, u32]
+        lib.fyprt_get_query_filter.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_uint64)]
     if hasattr(lib, "fyprt_render_rays"):    # (absent only in older builds loaded through FYPRT_LIB for an A/B run)
         lib.fyprt_render_rays.argtypes = [vp, C.POINTER(Settings), u32, vp, vp, u32, u32, vp, vp, C.POINTER(FrameStats)]
         lib.fyprt_render_rays_device.argtypes = [vp, C.POINTER(Settings), u32, vp, vp, u32, u32, vp, vp]
@@ -771,6 +776,30 @@ class Context:
         n = C.c_uint64()
         self._check(self.lib.fyprt_kept_primary_frames(self.h, C.byref(n)))
         return n.value
+
+    # ---- query filters (fyprt_set_mesh_query_masks / fyprt_set_query_mask): they apply to the query methods below as they are
+    def set_mesh_query_masks(self, masks):
+        """One 32-bit group mask per mesh of the uploaded scene (fyprt_set_mesh_query_masks); None switches the filter off.  With a
+        table set the ray, multi-hit, nearest-point and box queries see the triangles of mesh m iff masks[m] & query mask != 0."""
+        if masks is None:
+            self._check(self.lib.fyprt_set_mesh_query_masks(self.h, None, 0))
+            return
+        m = np.ascontiguousarray(masks, dtype=np.uint32).reshape(-1)
+        self._check(self.lib.fyprt_set_mesh_query_masks(self.h, m.ctypes.data if len(m) else C.cast((C.c_uint32 * 1)(), C.c_void_p), len(m)))
+
+    def set_query_mask(self, mask: int):
+        """The mask of all later query calls (fyprt_set_query_mask); 0xFFFFFFFF by default."""
+        self._check(self.lib.fyprt_set_query_mask(self.h, int(mask) & 0xFFFFFFFF))
+
+    def query_filter(self):
+        """(table or None when the filter is off, query mask, builds of the device data since creation) — fyprt_get_query_filter."""
+        n, q, b = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        self._check(self.lib.fyprt_get_query_filter(self.h, None, C.byref(n), C.byref(q), C.byref(b)))
+        if n.value == 0:
+            return None, q.value, b.value
+        out = np.empty(n.value, dtype=np.uint32)
+        self._check(self.lib.fyprt_get_query_filter(self.h, out.ctypes.data, C.byref(n), C.byref(q), C.byref(b)))
+        return out, q.value, b.value
 
     def get_tuning(self, key: int) -> int:
         v = C.c_int()

@@ -228,9 +228,18 @@ struct fyprt_context {
     // box query's `after` words share `after` (a quad holds four), its totals lie in `out` behind the triangle indices
     struct QueryFamily {
         DevBuf<unsigned long long> counters; DevBuf<float4> in, after; DevBuf<uint32_t> out, counts; Event ev[2]; OccCache occ[2];
+        OccCache occFiltered[2];               // ... and of its filtered form, indexed as `occ`
     };
     QueryFamily rayQuery, hitsQuery, pointsQuery;      // fyprt_trace_rays* (and the primary segments of fyprt_render_rays*), fyprt_trace_ray_hits*, fyprt_nearest_points*
     QueryFamily boxesQuery;                            // fyprt_overlap_boxes*
+    // Query filter (fyprt_set_mesh_query_masks / fyprt_set_query_mask, rt_filter.h).  meshMasks: one word per mesh of the scene, empty =
+    // filter off.  The derived device data — the non-empty meshes' first triangles ascending and their masks (what the leaf pass searches),
+    // a word per leaf record, a word per node — is built on the context stream by the first filtered query after the table was set or
+    // the tree changed (ensure_query_filter; filterValid says it describes table and tree as they are) and released when the filter
+    // is switched off.  filterFirstHost / filterMaskHost: what the build uploads, kept while a copy may be in flight.
+    std::vector<uint32_t> meshMasks, filterFirstHost, filterMaskHost; uint32_t queryMask = 0xFFFFFFFFu; uint64_t filterBuilds = 0; bool filterValid = false;
+    DevBuf<uint32_t> filterFirst, filterMeshMask, leafMask, nodeMask;
+    void release_query_filter() { filterFirst.release(); filterMeshMask.release(); leafMask.release(); nodeMask.release(); filterValid = false; }
     // radiance queries (fyprt_render_rays*, rt_query.h: k_render_rays_primary + the path stages), allocated on first use for
     // min(count, FYPRT_RENDER_RAYS_CHUNK) rays and kept: primary records, path state, ray / result lists, live lists, list counters + queue
     // heads; the host entry's staging (rays, pixel indices, radiance) and its two timing events
@@ -392,8 +401,8 @@ static void add_ray_stats(fyprt_frame_stats* s, int k, const unsigned long long*
 // the box query's 4 bytes per entry of this call's max_hits).  The families have always differed in how tuning key 2 and a failed occupancy query are taken,
 // and keep doing so: `clampWg` holds key 2 to the occupancy, `occFallback` stands in for an occupancy the runtime cannot give.
 template <class Q>
-static int launch_query(fyprt_context* c, fyprt_context::QueryFamily& f, OccCache& occ, Q q, void (*const kernels[2][2])(DevScene, Q), size_t listBytes,
-                        bool clampWg, int occFallback, bool timed) {
+static int launch_query_kernels(fyprt_context* c, fyprt_context::QueryFamily& f, OccCache& occ, Q q, void (*const kernels[2][2])(DevScene, Q), size_t listBytes,
+                                bool clampWg, int occFallback, bool timed) {
     if (!f.counters.p) { HIPCHK(c, f.counters.alloc(8)); }
     HIPCHK(c, hipMemsetAsync(f.counters.p, 0, 64, c->stream));
     const StackLds stack = stack_lds(c, 0u);                      // the query kernels stage no top nodes (not even in a -DRT_TOPCACHE build)
@@ -416,6 +425,22 @@ static int launch_query(fyprt_context* c, fyprt_context::QueryFamily& f, OccCach
     HIPCHK(c, hipGetLastError());
     if (timed) HIPCHK(c, hipEventRecord(f.ev[1], c->stream));
     return FYPRT_OK;
+}
+// A family's kernels[simple][counted] in both forms, and the launch every query entry point ends in: the filtered form iff a mesh
+// mask table is set (`filterable`: the entry point is one the filter applies to — the radiance queries' primary pass is not), behind
+// the lazy build of the filter's device data; with the filter off the launch is the one it always was.  occIndex: which of the
+// family's occupancy entries (the ray query's kind).
+template <class Q> struct QueryKernels { void (*plain[2][2])(DevScene, Q); void (*filtered[2][2])(DevScene, Filtered<Q>); };
+static int ensure_query_filter(fyprt_context* c);
+template <class Q>
+static int launch_query(fyprt_context* c, fyprt_context::QueryFamily& f, int occIndex, const Q& q, const QueryKernels<Q>& k, size_t listBytes,
+                        bool clampWg, int occFallback, bool timed, bool filterable = true) {
+    if (!filterable || c->meshMasks.empty()) return launch_query_kernels(c, f, f.occ[occIndex], q, k.plain, listBytes, clampWg, occFallback, timed);
+    TRY(ensure_query_filter(c));
+    Filtered<Q> fq{};
+    static_cast<Q&>(fq) = q;
+    fq.flt.nodeMask = c->nodeMask.p; fq.flt.leafMask = c->leafMask.p; fq.flt.queryMask = c->queryMask;
+    return launch_query_kernels(c, f, f.occFiltered[occIndex], fq, k.filtered, listBytes, clampWg, occFallback, timed);
 }
 
 // A blocking entry point behind its checks: host records through the family's staging (which grows and is kept), one timed launch by
@@ -596,6 +621,39 @@ static int download_nodes(fyprt_context* c) {
 }  // extern "C"
 // what the builders below and the tree edits share
 #include "rt_tree_host.h"
+// The query filter's device data for the table and the tree as they are (rt_filter.h), enqueued on the context stream: the mesh table
+// up, one launch over the leaf records, one launch per level of the refit passes' grouping (bottom level first; the single-launch form
+// over parent links would need the partial refit's maps, which the same edits invalidate: DESIGN.md §4, "Query filters").  Buffers are
+// reallocated only when their size changes.  Whoever changes table or tree does so with the stream idle, so the host tables are free.
+static int ensure_query_filter(fyprt_context* c) {
+    if (c->filterValid) return FYPRT_OK;
+    if (c->meshMasks.size() != c->topoMeshes.size()) return c->fail(FYPRT_ESTATE, "query filter: the mask table does not match the scene's meshes");
+    std::vector<std::pair<uint32_t, uint32_t>> byFirst;
+    for (size_t m = 0; m < c->topoMeshes.size(); ++m) if (c->topoMeshes[m].triangle_count) byFirst.push_back({c->topoMeshes[m].first_triangle, c->meshMasks[m]});
+    std::sort(byFirst.begin(), byFirst.end());
+    c->filterFirstHost.clear(); c->filterMaskHost.clear();
+    for (const auto& e : byFirst) { c->filterFirstHost.push_back(e.first); c->filterMaskHost.push_back(e.second); }
+    const uint32_t nMesh = (uint32_t)byFirst.size(), nLeaf = (uint32_t)(c->leafTris.n / 3), nNodes = (uint32_t)(c->nodes.n / 4);
+    if (c->filterFirst.n != nMesh) { HIPCHK(c, c->filterFirst.alloc(nMesh)); HIPCHK(c, c->filterMeshMask.alloc(nMesh)); }
+    if (c->leafMask.n != nLeaf) HIPCHK(c, c->leafMask.alloc(nLeaf));
+    if (c->nodeMask.n != nNodes) HIPCHK(c, c->nodeMask.alloc(nNodes));
+    if (nMesh) {
+        HIPCHK(c, hipMemcpyAsync(c->filterFirst.p, c->filterFirstHost.data(), (size_t)nMesh * 4u, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->filterMeshMask.p, c->filterMaskHost.data(), (size_t)nMesh * 4u, hipMemcpyHostToDevice, c->stream));
+    }
+    if (nLeaf) hipLaunchKernelGGL(k_filter_leaf_masks, dim3((nLeaf + 255u) / 256u), dim3(256), 0, c->stream, (const float4*)c->leafTris.p, nLeaf,
+                                  (const uint32_t*)c->filterFirst.p, (const uint32_t*)c->filterMeshMask.p, nMesh, c->leafMask.p);
+    if (nNodes && (c->levelOffset.empty() || c->levelOffset.back() != nNodes || c->levelNodes.n < nNodes))
+        return c->fail(FYPRT_ESTATE, "query filter: the level grouping does not describe the node array");
+    if (nNodes)
+        for_each_level(c->levelOffset, [&](uint32_t first, uint32_t count, dim3 grid) {
+            hipLaunchKernelGGL(k_filter_level, grid, dim3(kLevelBlock), 0, c->stream, (const float4*)c->nodes.p, (const uint32_t*)(c->levelNodes.p + first), count, nNodes,
+                               (const uint32_t*)c->leafMask.p, nLeaf, c->nodeMask.p);
+        });
+    HIPCHK(c, hipGetLastError());
+    c->filterValid = true; ++c->filterBuilds;
+    return FYPRT_OK;
+}
 extern "C" {
 // the refit pass over the whole tree (rt_refit.h): leaf triangles from the per-triangle positions, then boxes + quantisation
 // level by level, bottom level first (the grouping's levels are the tree's: upload_level_grouping)
@@ -808,6 +866,7 @@ int fyprt_upload_scene(fyprt_context* c, const fyprt_scene_desc* s) {
     c->frameComplete = false;                  // the payload's triangle indices belong to the scene they were traced in (fyprt_denoise)
     c->drop_kept_primary();
     c->drop_history(); c->release_snapshot();  // world positions of another scene are not comparable (fyprt_denoise_temporal)
+    c->meshMasks.clear(); c->release_query_filter(); c->queryMask = 0xFFFFFFFFu;     // the query filter belongs to the scene it was set for
     const uint8_t* tb = (const uint8_t*)s->triangles;
     auto tri = [&](uint32_t i) { return reinterpret_cast<const uint32_t*>(tb + (size_t)i * s->triangle_stride); };
     for (uint32_t i = 0; i < s->triangle_count; ++i) {
@@ -1331,6 +1390,7 @@ int fyprt_append_meshes(fyprt_context* c, const fyprt_vertex* vertices, uint32_t
     c->topoTris.resize((size_t)T * 4);
     for (uint32_t i = 0; i < triangle_count; ++i) std::memcpy(&c->topoTris[(size_t)(T0 + i) * 4], tri(i), 16);
     c->topoMeshes.insert(c->topoMeshes.end(), meshes, meshes + mesh_count);
+    if (!c->meshMasks.empty()) { c->meshMasks.resize(M, 0xFFFFFFFFu); c->filterValid = false; }      // a new mesh is in every group (query filter)
     c->vertexCount = V; c->meshCount = M;
     // 2. the device's: vertices and triangle indices cross the bus, the per-triangle records are computed there
     static_assert(sizeof(DevVertex) == sizeof(fyprt_vertex), "vertex layout");
@@ -1506,6 +1566,7 @@ int fyprt_regraft_meshes(fyprt_context* c, const uint32_t* mesh_indices, uint32_
     size_t keptSize[7]; for (int i = 0; i < 7; ++i) keptSize[i] = kept[i]->n;
     const size_t placeOutSize = c->placeOut.n;
     c->drop_kept_primary();                    // hits at equal distance go by the tree's order — also of a tree a failed call leaves half moved
+    c->filterValid = false;                    // ... and so do the query filter's node and leaf words
     const int rc = regraft_meshes(c, mesh_indices, mesh_count, reports);
     c->placement = saved; c->linksValid = false;
     if (!c->hostOnly) {
@@ -2256,28 +2317,32 @@ static int check_query(fyprt_context* c, int query, const void* rays, uint32_t c
     if (!c->haveScene) return c->fail(FYPRT_ESTATE, std::string(who) + " before fyprt_upload_scene");
     return FYPRT_OK;
 }
-static int enqueue_query(fyprt_context* c, int query, const float4* rays, uint32_t count, void* results, bool timed) {
+// `filterable`: a ray query proper, which the query filter applies to; the radiance queries' primary pass is not
+static int enqueue_query(fyprt_context* c, int query, const float4* rays, uint32_t count, void* results, bool timed, bool filterable) {
     const int occluded = query == FYPRT_QUERY_OCCLUDED ? 1 : 0;
-    static void (*const kQuery[2][2][2])(DevScene, QueryRays) = {{{k_query_rays<false, false>, k_query_rays<false, true>}, {k_query_rays_simple<false, false>, k_query_rays_simple<false, true>}},
-                                                                {{k_query_rays<true, false>, k_query_rays<true, true>}, {k_query_rays_simple<true, false>, k_query_rays_simple<true, true>}}};
+    static const QueryKernels<QueryRays> kQuery[2] = {
+        {{{k_query_rays<false, false>, k_query_rays<false, true>}, {k_query_rays_simple<false, false>, k_query_rays_simple<false, true>}},
+         {{k_query_rays_filtered<false, false>, k_query_rays_filtered<false, true>}, {k_query_rays_simple_filtered<false, false>, k_query_rays_simple_filtered<false, true>}}},
+        {{{k_query_rays<true, false>, k_query_rays<true, true>}, {k_query_rays_simple<true, false>, k_query_rays_simple<true, true>}},
+         {{k_query_rays_filtered<true, false>, k_query_rays_filtered<true, true>}, {k_query_rays_simple_filtered<true, false>, k_query_rays_simple_filtered<true, true>}}}};
     QueryRays q{};
     q.rays = rays; q.results = results; q.count = count;
     // key 2 taken as it is, 4 workgroups per CU without an occupancy, the occupancy cached per kind
-    return launch_query(c, c->rayQuery, c->rayQuery.occ[occluded], q, kQuery[occluded], 0u, false, 4, timed);
+    return launch_query(c, c->rayQuery, occluded, q, kQuery[occluded], 0u, false, 4, timed, filterable);
 }
 
 int fyprt_trace_rays(fyprt_context* c, int query, const fyprt_ray* rays, uint32_t count, void* results, fyprt_frame_stats* stats) {
     TRY(check_query(c, query, rays, count, results, false));
     const HostQuery h{rays, 2, nullptr, results, (size_t)count * (query == FYPRT_QUERY_OCCLUDED ? 4u : 40u), nullptr, false};
     return run_host_query(c, c->rayQuery, h, count, stats, [&](const float4* in, const float4*, uint32_t* out, uint32_t*) {
-        return enqueue_query(c, query, in, count, out, true); });
+        return enqueue_query(c, query, in, count, out, true, true); });
 }
 
 int fyprt_trace_rays_device(fyprt_context* c, int query, const void* rays, uint32_t count, void* results) {
     TRY(check_query(c, query, rays, count, results, true));
     if (count == 0) return FYPRT_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    return enqueue_query(c, query, static_cast<const float4*>(rays), count, results, false);
+    return enqueue_query(c, query, static_cast<const float4*>(rays), count, results, false, true);
 }
 
 // ---- the list queries: multi-hit (rt_query.h: k_query_hits / k_query_hits_simple) and nearest points (rt_points.h: k_query_points /
@@ -2294,17 +2359,19 @@ static int check_list_query(fyprt_context* c, const char* who, const char* noun,
     if (!c->haveScene) return c->fail(FYPRT_ESTATE, std::string(who) + " before fyprt_upload_scene");
     return FYPRT_OK;
 }
-// The two families of list queries: state, kernels[simple][counted], float4s per input record
-struct ListQuery { fyprt_context::QueryFamily fyprt_context::* family; void (*kernels[2][2])(DevScene, QueryHits); size_t inQuads; };
-static const ListQuery kRayHits = {&fyprt_context::hitsQuery, {{k_query_hits<false>, k_query_hits<true>}, {k_query_hits_simple<false>, k_query_hits_simple<true>}}, 2};
-static const ListQuery kNearestPoints = {&fyprt_context::pointsQuery, {{k_query_points<false>, k_query_points<true>}, {k_query_points_simple<false>, k_query_points_simple<true>}}, 1};
+// The two families of list queries: state, kernels[simple][counted] in both forms, float4s per input record
+struct ListQuery { fyprt_context::QueryFamily fyprt_context::* family; QueryKernels<QueryHits> kernels; size_t inQuads; };
+static const ListQuery kRayHits = {&fyprt_context::hitsQuery, {{{k_query_hits<false>, k_query_hits<true>}, {k_query_hits_simple<false>, k_query_hits_simple<true>}},
+                                                               {{k_query_hits_filtered<false>, k_query_hits_filtered<true>}, {k_query_hits_simple_filtered<false>, k_query_hits_simple_filtered<true>}}}, 2};
+static const ListQuery kNearestPoints = {&fyprt_context::pointsQuery, {{{k_query_points<false>, k_query_points<true>}, {k_query_points_simple<false>, k_query_points_simple<true>}},
+                                                                       {{k_query_points_filtered<false>, k_query_points_filtered<true>}, {k_query_points_simple_filtered<false>, k_query_points_simple_filtered<true>}}}, 1};
 // (device memory, count > 0, after / counts may be NULL)
 static int enqueue_list_query(fyprt_context* c, const ListQuery& l, const float4* in, const float4* after, uint32_t count, uint32_t maxHits, float4* hits, uint32_t* counts, bool timed) {
     fyprt_context::QueryFamily& f = c->*l.family;
     QueryHits q{};
     q.rays = in; q.after = after; q.hits = hits; q.counts = counts; q.count = count; q.maxHits = maxHits;
     // key 2 no higher than the occupancy, 2 workgroups per CU without one
-    return launch_query(c, f, f.occ[0], q, l.kernels, (size_t)maxHits * 16u, true, 2, timed);
+    return launch_query(c, f, 0, q, l.kernels, (size_t)maxHits * 16u, true, 2, timed);
 }
 static int host_list_query(fyprt_context* c, const ListQuery& l, const void* in, const void* after, uint32_t count, uint32_t maxHits, void* hits, uint32_t* hitCounts,
                            fyprt_frame_stats* stats) {
@@ -2338,6 +2405,29 @@ int fyprt_nearest_points_device(fyprt_context* c, const void* points, const void
     return device_list_query(c, kNearestPoints, points, after, count, max_hits, hits, hit_counts);
 }
 
+// ---- query filters (rt_filter.h): the mesh mask table and the query mask.  Host state only; the device data is built by the next
+// filtered query (ensure_query_filter).  The table is replaced with the context stream idle: a build may still be copying the old one.
+int fyprt_set_mesh_query_masks(fyprt_context* c, const uint32_t* masks, uint32_t mesh_count) {
+    if (!c) return FYPRT_EINVAL;
+    if ((masks == nullptr) != (mesh_count == 0)) return c->fail(FYPRT_EINVAL, "fyprt_set_mesh_query_masks: NULL masks with a non-zero count, or masks with count 0");
+    if (!c->haveScene) return c->fail(FYPRT_ESTATE, "fyprt_set_mesh_query_masks before fyprt_upload_scene");
+    if (mesh_count && mesh_count != (uint32_t)c->topoMeshes.size()) return c->fail(FYPRT_EINVAL, "fyprt_set_mesh_query_masks: mesh_count differs from the scene's mesh count");
+    if (!c->hostOnly) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, hipStreamSynchronize(c->stream)); }
+    c->meshMasks.assign(masks, masks + mesh_count);
+    c->filterValid = false;
+    if (!mesh_count) c->release_query_filter();
+    return FYPRT_OK;
+}
+int fyprt_set_query_mask(fyprt_context* c, uint32_t query_mask) { if (!c) return FYPRT_EINVAL; c->queryMask = query_mask; return FYPRT_OK; }
+int fyprt_get_query_filter(fyprt_context* c, uint32_t* masks, uint32_t* mesh_count, uint32_t* query_mask, uint64_t* builds) {
+    if (!c || !mesh_count) return FYPRT_EINVAL;
+    *mesh_count = (uint32_t)c->meshMasks.size();
+    if (masks && !c->meshMasks.empty()) std::memcpy(masks, c->meshMasks.data(), c->meshMasks.size() * 4u);
+    if (query_mask) *query_mask = c->queryMask;
+    if (builds) *builds = c->filterBuilds;
+    return FYPRT_OK;
+}
+
 // ---- box-overlap queries (rt_boxes.h: k_query_boxes / k_query_boxes_simple): a list query whose entries are bare triangle indices,
 // with a total beside the count.  The scene is read, the query's own results and counters are written, no frame state moves.
 static int check_overlap_boxes(fyprt_context* c, const char* who, const void* boxes, const void* after, uint32_t count, uint32_t maxHits, const void* triangles,
@@ -2354,12 +2444,13 @@ static int check_overlap_boxes(fyprt_context* c, const char* who, const void* bo
 // (device memory, count > 0, after / counts / totals may be NULL)
 static int enqueue_overlap_boxes(fyprt_context* c, const float4* boxes, const uint32_t* after, uint32_t count, uint32_t maxHits, uint32_t* triangles, uint32_t* counts,
                                  uint32_t* totals, bool timed) {
-    static void (*const kBoxes[2][2])(DevScene, QueryBoxes) = {{k_query_boxes<false>, k_query_boxes<true>}, {k_query_boxes_simple<false>, k_query_boxes_simple<true>}};
+    static const QueryKernels<QueryBoxes> kBoxes = {{{k_query_boxes<false>, k_query_boxes<true>}, {k_query_boxes_simple<false>, k_query_boxes_simple<true>}},
+                                                    {{k_query_boxes_filtered<false>, k_query_boxes_filtered<true>}, {k_query_boxes_simple_filtered<false>, k_query_boxes_simple_filtered<true>}}};
     fyprt_context::QueryFamily& f = c->boxesQuery;
     QueryBoxes q{};
     q.boxes = boxes; q.after = after; q.triangles = triangles; q.counts = counts; q.totals = totals; q.count = count; q.maxHits = maxHits;
     // as the list queries: key 2 no higher than the occupancy, 2 workgroups per CU without one
-    return launch_query(c, f, f.occ[0], q, kBoxes, (size_t)maxHits * 4u, true, 2, timed);
+    return launch_query(c, f, 0, q, kBoxes, (size_t)maxHits * 4u, true, 2, timed);
 }
 
 int fyprt_overlap_boxes(fyprt_context* c, const fyprt_box* boxes, const uint32_t* after, uint32_t count, uint32_t max_hits, uint32_t* triangles,
@@ -2419,7 +2510,7 @@ static int enqueue_render_rays(fyprt_context* c, const fyprt_settings* s, uint32
     }
     HIPCHK(c, hipMemsetAsync(c->rrCounters.p, 0, 3 * p.L * sizeof(uint32_t), c->stream));
     // primary segments: the closest-hit query (its own counters and queue head; ray counts of the whole call land there too)
-    TRY(enqueue_query(c, FYPRT_QUERY_CLOSEST, rays, count, c->rrPayload.p, false));
+    TRY(enqueue_query(c, FYPRT_QUERY_CLOSEST, rays, count, c->rrPayload.p, false, false));      // unfiltered: the query filter does not touch radiance queries
     ++*launched;
     const StackLds stack = stack_lds(c, 0u);
     DevScene qs = c->dsc; qs.stackBudget = stack.budget;        // (run_stage sets quorum and counters of its trace launches)

@@ -141,15 +141,17 @@ RT_DEV void tri_insert(uint32_t* l, uint32_t maxHits, uint32_t& n, uint32_t& wor
     if (n == maxHits) worst = l[(size_t)(maxHits - 1u) * kBlock];
 }
 
-// The box lane state: the box, and the list's length, worst entry, lowest admissible index and the total in registers
-struct BoxLane {
-    using Query = QueryBoxes;
+// The box lane state: the box, and the list's length, worst entry, lowest admissible index and the total in registers.  FILTER as
+// RayLane's; the total then counts admitted triangles only.
+template <bool FILTER> struct BoxLaneT : LaneFilter<FILTER> {
+    using Query = typename std::conditional<FILTER, Filtered<QueryBoxes>, QueryBoxes>::type;
     uint32_t* const list;                       // &plane[threadIdx.x]; entry s at [s * kBlock]
     f3 lo = splat3(0.0f), hi = splat3(0.0f);
     uint32_t n = 0, worst = kNoTriangle, low = 0, total = 0;
-    RT_DEV BoxLane(const DevScene& sc, const QueryBoxes&, int32_t* s_stack)
+    RT_DEV BoxLaneT(const DevScene& sc, const Query&, int32_t* s_stack)
         : list(reinterpret_cast<uint32_t*>(s_stack + (size_t)(sc.stackBudget + 1) * kBlock) + threadIdx.x) {}
-    RT_DEV int32_t start(const DevScene& sc, const QueryBoxes& q, uint32_t i) {
+    RT_DEV int32_t start(const DevScene& sc, const Query& q, uint32_t i) {
+        this->load(q);
         const float4 b0 = q.boxes[(size_t)i * 2], b1 = q.boxes[(size_t)i * 2 + 1];
         lo = mk3(b0.x, b0.y, b0.z); hi = mk3(b1.x, b1.y, b1.z);
         n = 0; worst = kNoTriangle; low = 0; total = 0;
@@ -158,13 +160,15 @@ struct BoxLane {
         return (sc.triCount == 0 || !wanted || box_invalid(lo, hi)) ? kExit : sc.rootRef;
     }
     template <bool COUNT> RT_DEV int32_t visit(const DevScene& sc, int32_t cur, Stack& st, uint32_t& nBox, uint32_t& nNode) {
+        if (FILTER && !this->node(cur)) return st.pop();
         return box_node_step<COUNT>(sc.nodes, sc.stackBudget, cur, lo, hi, st, nBox, nNode);
     }
-    template <bool COUNT> RT_DEV bool leaf(const DevScene& sc, const QueryBoxes& q, int32_t cur, uint32_t& nTri) {
+    template <bool COUNT> RT_DEV bool leaf(const DevScene& sc, const Query& q, int32_t cur, uint32_t& nTri) {
         const uint32_t code = (uint32_t)~cur, firstTri = code >> 2, cnt = (code & 3u) + 1u;
         const f3 c = (lo + hi) * 0.5f, h = (hi - lo) * 0.5f;          // (six operations per leaf instead of six registers across the walk)
         for (uint32_t k = 0; k < cnt; ++k) {
             uint32_t id;
+            if (FILTER && !this->record(firstTri + k)) continue;
             if (COUNT) nTri += 1;
             if (!box_tri(sc.leafTris + (size_t)(firstTri + k) * 3, lo, hi, c, h, id) || id < low) continue;
             total += 1u;                                              // every accepted triangle, also those beyond maxHits
@@ -172,7 +176,7 @@ struct BoxLane {
         }
         return false;                                                 // a set query is never finished early
     }
-    RT_DEV bool finish(const DevScene&, const QueryBoxes& q, uint32_t i) {
+    RT_DEV bool finish(const DevScene&, const Query& q, uint32_t i) {
         uint32_t* dst = q.triangles + (size_t)i * q.maxHits;
         for (uint32_t s = 0; s < q.maxHits; ++s) dst[s] = s < n ? list[(size_t)s * kBlock] : kNoTriangle;
         if (q.counts) q.counts[i] = n;
@@ -180,6 +184,7 @@ struct BoxLane {
         return n != 0u;
     }
 };
+using BoxLane = BoxLaneT<false>;
 
 template <bool COUNT> __global__ void k_query_boxes(DevScene sc, QueryBoxes q);
 // 5 waves per SIMD (87 VGPRs, no scratch), as the other list queries: held to 6 (80 VGPRs) the kernel spills five registers to 16 B of
@@ -197,6 +202,21 @@ template <bool COUNT>
 __global__ __launch_bounds__(kBlock) void k_query_boxes_simple(DevScene sc, QueryBoxes q) {
     extern __shared__ int32_t s_stack[];                         // (stackBudget + 1) x 4 B + maxHits x 4 B per thread, sized at launch
     query_simple_body<BoxLane, COUNT>(sc, q, s_stack);
+}
+// ... and their filtered forms (BoxLaneT<true>)
+template <bool COUNT> __global__ void k_query_boxes_filtered(DevScene sc, Filtered<QueryBoxes> q);
+template <> __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5))) void k_query_boxes_filtered<false>(DevScene sc, Filtered<QueryBoxes> q) {
+    extern __shared__ int32_t s_stack[];
+    query_body<BoxLaneT<true>, false>(sc, q, s_stack);
+}
+template <> __global__ __launch_bounds__(kBlock) void k_query_boxes_filtered<true>(DevScene sc, Filtered<QueryBoxes> q) {        // instrumented: no register cap
+    extern __shared__ int32_t s_stack[];
+    query_body<BoxLaneT<true>, true>(sc, q, s_stack);
+}
+template <bool COUNT>
+__global__ __launch_bounds__(kBlock) void k_query_boxes_simple_filtered(DevScene sc, Filtered<QueryBoxes> q) {
+    extern __shared__ int32_t s_stack[];
+    query_simple_body<BoxLaneT<true>, COUNT>(sc, q, s_stack);
 }
 
 }  // namespace rt

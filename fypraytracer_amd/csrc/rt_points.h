@@ -150,11 +150,13 @@ RT_DEV int32_t point_node_step(const float4* nodes, int32_t budget, int32_t cur,
 }
 
 // One leaf's triangles against the list; returns the cull bound that holds afterwards
+template <class F>
 RT_DEV float points_leaf(const DevScene& sc, const HitList& l, uint32_t maxHits, int32_t cur, f3 p, float r2, unsigned long long lowKey,
-                         uint32_t& n, unsigned long long& worst, float bound, uint32_t& nTri, bool count) {
+                         uint32_t& n, unsigned long long& worst, float bound, uint32_t& nTri, bool count, const F& flt) {
     const uint32_t code = (uint32_t)~cur, firstTri = code >> 2, cnt = (code & 3u) + 1u;
     for (uint32_t k = 0; k < cnt; ++k) {
         float dist2, u, v; uint32_t id;
+        if (!flt.record(firstTri + k)) continue;
         if (count) nTri += 1;
         point_tri(sc.leafTris + (size_t)(firstTri + k) * 3, p, dist2, u, v, id);
         if (!(dist2 <= r2)) continue;
@@ -166,15 +168,17 @@ RT_DEV float points_leaf(const DevScene& sc, const HitList& l, uint32_t maxHits,
     return bound;
 }
 
-// The point lane state: HitsLane with a point in place of the ray, the squared radius in place of the interval
-struct PointsLane {
-    using Query = QueryPoints;
+// The point lane state: HitsLane with a point in place of the ray, the squared radius in place of the interval.  FILTER as RayLane's:
+// a masked sub-tree is never entered, so near an excluded mesh the list still fills from the admitted ones and the cull bound shrinks.
+template <bool FILTER> struct PointsLaneT : LaneFilter<FILTER> {
+    using Query = typename std::conditional<FILTER, Filtered<QueryPoints>, QueryPoints>::type;
     const HitList list;
     f3 p = splat3(0.0f);
     float r2 = 0.0f, bound = 0.0f; uint32_t n = 0;
     unsigned long long worst = kNoWorstKey, lowKey = 0ull;
-    RT_DEV PointsLane(const DevScene& sc, const QueryPoints& q, int32_t* s_stack) : list(hit_list(s_stack, sc.stackBudget, q.maxHits)) {}
-    RT_DEV int32_t start(const DevScene& sc, const QueryPoints& q, uint32_t i) {
+    RT_DEV PointsLaneT(const DevScene& sc, const Query& q, int32_t* s_stack) : list(hit_list(s_stack, sc.stackBudget, q.maxHits)) {}
+    RT_DEV int32_t start(const DevScene& sc, const Query& q, uint32_t i) {
+        this->load(q);
         const float4 r0 = q.rays[i];
         p = mk3(r0.x, r0.y, r0.z);
         r2 = point_r2(r0.w); bound = r2;
@@ -183,14 +187,16 @@ struct PointsLane {
         return (sc.triCount == 0 || !wanted || point_invalid(p, r0.w)) ? kExit : sc.rootRef;
     }
     template <bool COUNT> RT_DEV int32_t visit(const DevScene& sc, int32_t cur, Stack& st, uint32_t& nBox, uint32_t& nNode) {
+        if (FILTER && !this->node(cur)) return st.pop();
         return point_node_step<COUNT>(sc.nodes, sc.stackBudget, cur, p, bound, st, nBox, nNode);
     }
-    template <bool COUNT> RT_DEV bool leaf(const DevScene& sc, const QueryPoints& q, int32_t cur, uint32_t& nTri) {
-        bound = points_leaf(sc, list, q.maxHits, cur, p, r2, lowKey, n, worst, bound, nTri, COUNT);
+    template <bool COUNT> RT_DEV bool leaf(const DevScene& sc, const Query& q, int32_t cur, uint32_t& nTri) {
+        bound = points_leaf(sc, list, q.maxHits, cur, p, r2, lowKey, n, worst, bound, nTri, COUNT, static_cast<const LaneFilter<FILTER>&>(*this));
         return false;
     }
-    RT_DEV bool finish(const DevScene&, const QueryPoints& q, uint32_t i) { store_hits(q, list, i, n); return n != 0u; }
+    RT_DEV bool finish(const DevScene&, const Query& q, uint32_t i) { store_hits(q, list, i, n); return n != 0u; }
 };
+using PointsLane = PointsLaneT<false>;
 
 template <bool COUNT> __global__ void k_query_points(DevScene sc, QueryPoints q);
 // 5 waves per SIMD as k_query_hits<false>: the list's LDS leaves room for no more workgroups from a 26-entry stack on
@@ -207,6 +213,21 @@ template <bool COUNT>
 __global__ __launch_bounds__(kBlock) void k_query_points_simple(DevScene sc, QueryPoints q) {
     extern __shared__ int32_t s_stack[];                         // (stackBudget + 1) x 4 B + maxHits x 16 B per thread, sized at launch
     query_simple_body<PointsLane, COUNT>(sc, q, s_stack);
+}
+// ... and their filtered forms (PointsLaneT<true>)
+template <bool COUNT> __global__ void k_query_points_filtered(DevScene sc, Filtered<QueryPoints> q);
+template <> __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5))) void k_query_points_filtered<false>(DevScene sc, Filtered<QueryPoints> q) {
+    extern __shared__ int32_t s_stack[];
+    query_body<PointsLaneT<true>, false>(sc, q, s_stack);
+}
+template <> __global__ __launch_bounds__(kBlock) void k_query_points_filtered<true>(DevScene sc, Filtered<QueryPoints> q) {      // instrumented: no register cap
+    extern __shared__ int32_t s_stack[];
+    query_body<PointsLaneT<true>, true>(sc, q, s_stack);
+}
+template <bool COUNT>
+__global__ __launch_bounds__(kBlock) void k_query_points_simple_filtered(DevScene sc, Filtered<QueryPoints> q) {
+    extern __shared__ int32_t s_stack[];
+    query_simple_body<PointsLaneT<true>, COUNT>(sc, q, s_stack);
 }
 
 }  // namespace rt

@@ -409,9 +409,11 @@ static int prune_remove(fyprt_context* c, const PruneTable& tris, const PruneTab
             fyprt_mesh me = c->topoMeshes[m];
             me.first_triangle -= tris.before(me.first_triangle);
             if (copy) mfv.push_back(c->meshFirstVertex[m] - verts.before(c->meshFirstVertex[m]));
+            if (!c->meshMasks.empty()) c->meshMasks[w] = c->meshMasks[m];      // the query filter's table follows the meshes, in order
             c->topoMeshes[w++] = me;
         }
         c->topoMeshes.resize(w);
+        if (!c->meshMasks.empty()) { c->meshMasks.resize(w); c->filterValid = false; if (!w) c->release_query_filter(); }
         if (copy) { mfv.push_back(V); c->meshFirstVertex.swap(mfv); }
         c->vertexCount = V; c->meshCount = w;
     }

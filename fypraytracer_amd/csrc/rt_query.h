@@ -22,6 +22,7 @@
 // query_simple_body, written once below, around a per-query lane state.
 #pragma once
 #include "rt_paths.h"
+#include "rt_filter.h"
 
 namespace rt {
 
@@ -154,15 +155,17 @@ RT_DEV void query_simple_body(const DevScene& sc, const typename L::Query& q, in
     }
 }
 
-// The closest-hit / occlusion lane state
-template <bool OCCLUDED> struct RayLane {
-    using Query = QueryRays;
+// The closest-hit / occlusion lane state.  FILTER: the query filter's visit rule (rt_filter.h) around the same walk; the record is then
+// Filtered<QueryRays>.  Without it the base is empty and the lane is the code it was.
+template <bool OCCLUDED, bool FILTER = false> struct RayLane : LaneFilter<FILTER> {
+    using Query = typename std::conditional<FILTER, Filtered<QueryRays>, QueryRays>::type;
     // (the origin lives in pk only: a separate copy of it costs three registers across the loop, and the closest-hit kernel spills)
     f3 d = splat3(0.0f); RayPk pk = make_raypk(d, 1.0f, 1.0f, 1.0f);
     float tmin = 0.0f, best = 0.0f, cut = 0.0f, hu = 0.0f, hv = 0.0f; int32_t hitTri = -1;
-    RT_DEV RayLane(const DevScene&, const QueryRays&, int32_t*) {}
+    RT_DEV RayLane(const DevScene&, const Query&, int32_t*) {}
     // a refill is two 16-byte loads and three reciprocals
-    RT_DEV int32_t start(const DevScene& sc, const QueryRays& q, uint32_t i) {
+    RT_DEV int32_t start(const DevScene& sc, const Query& q, uint32_t i) {
+        this->load(q);
         const float4 r0 = q.rays[(size_t)i * 2], r1 = q.rays[(size_t)i * 2 + 1];
         const f3 o = mk3(r0.x, r0.y, r0.z); d = mk3(r1.x, r1.y, r1.z); tmin = r0.w;
         pk = make_raypk(o, safe_inv(d.x), safe_inv(d.y), safe_inv(d.z));
@@ -172,12 +175,14 @@ template <bool OCCLUDED> struct RayLane {
         return (sc.triCount == 0 || query_invalid(o, d, tmin, r1.w)) ? kExit : sc.rootRef;
     }
     template <bool COUNT> RT_DEV int32_t visit(const DevScene& sc, int32_t cur, Stack& st, uint32_t& nBox, uint32_t& nNode) {
+        if (FILTER && !this->node(cur)) return st.pop();
         return node_step<COUNT>(sc.nodes, sc.stackBudget, cur, pk, cut, st, nBox, nNode);
     }
-    template <bool COUNT> RT_DEV bool leaf(const DevScene& sc, const QueryRays&, int32_t cur, uint32_t& nTri) {
+    template <bool COUNT> RT_DEV bool leaf(const DevScene& sc, const Query&, int32_t cur, uint32_t& nTri) {
         const uint32_t code = (uint32_t)~cur, firstTri = code >> 2, cnt = (code & 3u) + 1u;
         for (uint32_t k = 0; k < cnt; ++k) {
             float t, u, v; uint32_t id;
+            if (FILTER && !this->record(firstTri + k)) continue;
             if (COUNT) nTri += 1;
             if (!tri_test(sc.leafTris + (size_t)(firstTri + k) * 3, mk3(pk.ox, pk.oy, pk.oz), d, t, u, v, id) || !(t > tmin) || !(t < best)) continue;
             hitTri = (int32_t)id;
@@ -186,7 +191,7 @@ template <bool OCCLUDED> struct RayLane {
         }
         return false;
     }
-    RT_DEV bool finish(const DevScene& sc, const QueryRays& q, uint32_t i) {
+    RT_DEV bool finish(const DevScene& sc, const Query& q, uint32_t i) {
         store_query_result<OCCLUDED>(sc, q, i, mk3(pk.ox, pk.oy, pk.oz), d, best, hu, hv, hitTri);
         return hitTri >= 0;
     }
@@ -213,6 +218,29 @@ template <bool OCCLUDED, bool COUNT>
 __global__ __launch_bounds__(kBlock) void k_query_rays_simple(DevScene sc, QueryRays q) {
     extern __shared__ int32_t s_stack[];                         // (stackBudget + 1) entries x kBlock threads, sized at launch
     query_simple_body<RayLane<OCCLUDED>, COUNT>(sc, q, s_stack);
+}
+// ... and their filtered forms (RayLane<OCCLUDED, true>), launched iff a mesh mask table is set
+template <bool OCCLUDED, bool COUNT> __global__ void k_query_rays_filtered(DevScene sc, Filtered<QueryRays> q);
+template <> __global__ __launch_bounds__(kBlock) RT_TRACE_WAVES void k_query_rays_filtered<false, false>(DevScene sc, Filtered<QueryRays> q) {
+    extern __shared__ int32_t s_stack[];
+    query_body<RayLane<false, true>, false>(sc, q, s_stack);
+}
+template <> __global__ __launch_bounds__(kBlock) RT_TRACE_WAVES void k_query_rays_filtered<true, false>(DevScene sc, Filtered<QueryRays> q) {
+    extern __shared__ int32_t s_stack[];
+    query_body<RayLane<true, true>, false>(sc, q, s_stack);
+}
+template <> __global__ __launch_bounds__(kBlock) void k_query_rays_filtered<false, true>(DevScene sc, Filtered<QueryRays> q) {   // instrumented: no register cap
+    extern __shared__ int32_t s_stack[];
+    query_body<RayLane<false, true>, true>(sc, q, s_stack);
+}
+template <> __global__ __launch_bounds__(kBlock) void k_query_rays_filtered<true, true>(DevScene sc, Filtered<QueryRays> q) {
+    extern __shared__ int32_t s_stack[];
+    query_body<RayLane<true, true>, true>(sc, q, s_stack);
+}
+template <bool OCCLUDED, bool COUNT>
+__global__ __launch_bounds__(kBlock) void k_query_rays_simple_filtered(DevScene sc, Filtered<QueryRays> q) {
+    extern __shared__ int32_t s_stack[];
+    query_simple_body<RayLane<OCCLUDED, true>, COUNT>(sc, q, s_stack);
 }
 
 // ============================================================ multi-hit queries (fyprt_trace_ray_hits*): the K nearest hits per ray
@@ -271,11 +299,13 @@ RT_DEV void hit_insert(const HitList& l, uint32_t maxHits, uint32_t& n, unsigned
     if (n == maxHits) worst = l.keys[(size_t)(maxHits - 1u) * kBlock];
 }
 // One leaf's triangles against the list; returns the box cut that holds afterwards
+template <class F>
 RT_DEV float hits_leaf(const DevScene& sc, const HitList& l, uint32_t maxHits, int32_t cur, f3 o, f3 d, float tmin, float hi, unsigned long long afterKey,
-                       uint32_t& n, unsigned long long& worst, float cut, uint32_t& nTri, bool count) {
+                       uint32_t& n, unsigned long long& worst, float cut, uint32_t& nTri, bool count, const F& flt) {
     const uint32_t code = (uint32_t)~cur, firstTri = code >> 2, cnt = (code & 3u) + 1u;
     for (uint32_t k = 0; k < cnt; ++k) {
         float t, u, v; uint32_t id;
+        if (!flt.record(firstTri + k)) continue;
         if (count) nTri += 1;
         if (!tri_test(sc.leafTris + (size_t)(firstTri + k) * 3, o, d, t, u, v, id) || !(t > tmin) || !(t < hi)) continue;
         const unsigned long long key = hit_key(t, id);
@@ -299,15 +329,16 @@ RT_DEV void store_hits(const QueryHits& q, const HitList& l, uint32_t i, uint32_
     if (q.counts) q.counts[i] = n;
 }
 
-// The multi-hit lane state: the ray, and the list's length, worst key and `after` key in registers
-struct HitsLane {
-    using Query = QueryHits;
+// The multi-hit lane state: the ray, and the list's length, worst key and `after` key in registers.  FILTER as RayLane's.
+template <bool FILTER> struct HitsLaneT : LaneFilter<FILTER> {
+    using Query = typename std::conditional<FILTER, Filtered<QueryHits>, QueryHits>::type;
     const HitList list;
     f3 d = splat3(0.0f); RayPk pk = make_raypk(d, 1.0f, 1.0f, 1.0f);
     float tmin = 0.0f, hi = 0.0f, cut = 0.0f; uint32_t n = 0;
     unsigned long long worst = kNoWorstKey, afterKey = 0ull;
-    RT_DEV HitsLane(const DevScene& sc, const QueryHits& q, int32_t* s_stack) : list(hit_list(s_stack, sc.stackBudget, q.maxHits)) {}
-    RT_DEV int32_t start(const DevScene& sc, const QueryHits& q, uint32_t i) {
+    RT_DEV HitsLaneT(const DevScene& sc, const Query& q, int32_t* s_stack) : list(hit_list(s_stack, sc.stackBudget, q.maxHits)) {}
+    RT_DEV int32_t start(const DevScene& sc, const Query& q, uint32_t i) {
+        this->load(q);
         const float4 r0 = q.rays[(size_t)i * 2], r1 = q.rays[(size_t)i * 2 + 1];
         const f3 o = mk3(r0.x, r0.y, r0.z); d = mk3(r1.x, r1.y, r1.z); tmin = r0.w;
         pk = make_raypk(o, safe_inv(d.x), safe_inv(d.y), safe_inv(d.z));
@@ -318,14 +349,16 @@ struct HitsLane {
         return (sc.triCount == 0 || !wanted || query_invalid(o, d, tmin, r1.w)) ? kExit : sc.rootRef;
     }
     template <bool COUNT> RT_DEV int32_t visit(const DevScene& sc, int32_t cur, Stack& st, uint32_t& nBox, uint32_t& nNode) {
+        if (FILTER && !this->node(cur)) return st.pop();
         return node_step<COUNT>(sc.nodes, sc.stackBudget, cur, pk, cut, st, nBox, nNode);
     }
-    template <bool COUNT> RT_DEV bool leaf(const DevScene& sc, const QueryHits& q, int32_t cur, uint32_t& nTri) {
-        cut = hits_leaf(sc, list, q.maxHits, cur, mk3(pk.ox, pk.oy, pk.oz), d, tmin, hi, afterKey, n, worst, cut, nTri, COUNT);
+    template <bool COUNT> RT_DEV bool leaf(const DevScene& sc, const Query& q, int32_t cur, uint32_t& nTri) {
+        cut = hits_leaf(sc, list, q.maxHits, cur, mk3(pk.ox, pk.oy, pk.oz), d, tmin, hi, afterKey, n, worst, cut, nTri, COUNT, static_cast<const LaneFilter<FILTER>&>(*this));
         return false;
     }
-    RT_DEV bool finish(const DevScene&, const QueryHits& q, uint32_t i) { store_hits(q, list, i, n); return n != 0u; }
+    RT_DEV bool finish(const DevScene&, const Query& q, uint32_t i) { store_hits(q, list, i, n); return n != 0u; }
 };
+using HitsLane = HitsLaneT<false>;
 
 template <bool COUNT> __global__ void k_query_hits(DevScene sc, QueryHits q);
 // Compiled for 5 waves per SIMD (96 VGPRs, 12 B of scratch as k_query_rays<false, false>), not the 6 of RT_TRACE_WAVES (80 VGPRs, 20 B: the
@@ -344,6 +377,21 @@ template <bool COUNT>
 __global__ __launch_bounds__(kBlock) void k_query_hits_simple(DevScene sc, QueryHits q) {
     extern __shared__ int32_t s_stack[];                         // (stackBudget + 1) x 4 B + maxHits x 16 B per thread, sized at launch
     query_simple_body<HitsLane, COUNT>(sc, q, s_stack);
+}
+// ... and their filtered forms (HitsLaneT<true>)
+template <bool COUNT> __global__ void k_query_hits_filtered(DevScene sc, Filtered<QueryHits> q);
+template <> __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5))) void k_query_hits_filtered<false>(DevScene sc, Filtered<QueryHits> q) {
+    extern __shared__ int32_t s_stack[];
+    query_body<HitsLaneT<true>, false>(sc, q, s_stack);
+}
+template <> __global__ __launch_bounds__(kBlock) void k_query_hits_filtered<true>(DevScene sc, Filtered<QueryHits> q) {          // instrumented: no register cap
+    extern __shared__ int32_t s_stack[];
+    query_body<HitsLaneT<true>, true>(sc, q, s_stack);
+}
+template <bool COUNT>
+__global__ __launch_bounds__(kBlock) void k_query_hits_simple_filtered(DevScene sc, Filtered<QueryHits> q) {
+    extern __shared__ int32_t s_stack[];
+    query_simple_body<HitsLaneT<true>, COUNT>(sc, q, s_stack);
 }
 
 // ============================================================ radiance queries (fyprt_render_rays*): the primary pass

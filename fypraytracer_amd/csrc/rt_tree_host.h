@@ -124,8 +124,9 @@ static int read_back_mesh_verts(fyprt_context* c, uint32_t m) {
 
 // ---- the scene descriptor's tree fields, and with them those of the per-triangle records of a scene of T triangles.  Every call that
 // builds, grafts, prunes or regrafts ends here, so here the kept primary hits go (fyprt_context::KeptPrimary): another tree visits the
-// triangles in another order, and hits at equal distance go by that order.
-static void set_scene_tree(fyprt_context* c) { c->drop_kept_primary(); c->dsc.nodes = c->nodes.p; c->dsc.leafTris = c->leafTris.p; c->dsc.rootRef = rth::device_ref(c->hostBvh.rootRef); }
+// triangles in another order, and hits at equal distance go by that order.  The query filter's node and leaf words describe the old
+// node array and leaf order: the next filtered query builds them again.
+static void set_scene_tree(fyprt_context* c) { c->drop_kept_primary(); c->filterValid = false; c->dsc.nodes = c->nodes.p; c->dsc.leafTris = c->leafTris.p; c->dsc.rootRef = rth::device_ref(c->hostBvh.rootRef); }
 static void set_scene_triangles(fyprt_context* c, uint32_t T) { set_scene_tree(c); c->dsc.triCount = T; c->dsc.triPos = c->triPos.p; c->dsc.triShade = c->triShade.p; }
 
 // ---- launches on the context stream

@@ -798,6 +798,43 @@ int fyprt_overlap_boxes(fyprt_context* ctx, const fyprt_box* boxes, const uint32
 int fyprt_overlap_boxes_device(fyprt_context* ctx, const void* boxes, const void* after, uint32_t count, uint32_t max_hits, void* triangles,
                                void* hit_counts, void* totals);
 
+/* ------------------------------------------------------------------------------------------------- query filters
+ * New (no reference counterpart): per-mesh group masks for the four query families above, so that a query can leave a mesh out (snapping
+ * a dragged mesh onto its neighbours, clearance around it, a broad phase against everything else) or look at one mesh alone (picking
+ * within the selection).  The meshes are the instances ("Query filters").
+ *   The mesh mask table M: one 32-bit word per mesh of the uploaded scene.  The query mask Q: one word per context, 0xFFFFFFFF by default.
+ *   The rule: the meshes partition the triangle list (upload and append enforce it); a triangle of mesh m is admitted iff (M[m] & Q) != 0.
+ *   With a table set, acceptance in the eight entry points fyprt_trace_rays, fyprt_trace_ray_hits, fyprt_nearest_points,
+ *   fyprt_overlap_boxes and their _device forms gets the extra condition "the triangle is admitted".  Nothing else changes: keys, order,
+ *   continuation (`after`), unused records, counts, invalid records and error order are as stated above, and the box query's totals count
+ *   admitted triangles only.  Each answer is the family's rule applied to the leaf records of the admitted triangles alone.  The
+ *   closest-hit query keeps its rule for exact-t ties (the first found in traversal order, among admitted triangles); the list queries stay
+ *   independent of the tree.
+ *   Not touched: frames of every technique, fyprt_render_rays* (its primary pass and the payloads it returns are unfiltered), the
+ *   upscaler's primary rays, every denoiser and every scene edit.  With no table set the kernels launched are the unfiltered ones.
+ *   Life of the table: fyprt_upload_scene drops it (filter off) and resets Q to all ones; fyprt_append_meshes extends it with 0xFFFFFFFF
+ *   per new mesh; fyprt_remove_meshes takes the removed meshes' entries out and moves the rest down in order (removing every mesh leaves
+ *   the filter off, as an upload does); a failed call changes nothing; fyprt_regraft_meshes and the geometry, material and texture edits
+ *   leave it alone.  The table is per context, as the scene is.
+ *   Device data: 4 bytes per leaf record and 4 bytes per node (the OR of the masks below it: a query never enters a sub-tree it does not
+ *   admit — an imported or regrafted mesh is one sub-tree), plus 8 bytes per mesh, built on the context stream by the first filtered
+ *   query after the table was set or the tree changed (append, removal, regraft and their rebuild fall-backs; not by vertex, transform,
+ *   material or texture edits, refits, or a new Q), counted by fyprt_live_device_bytes, released when the filter is switched off and
+ *   on destroy.  The device entries stay asynchronous.  With ray counting on a masked node is no node visit and a masked record no
+ *   triangle test.
+ * fyprt_set_mesh_query_masks: masks == NULL with mesh_count == 0 switches the filter off (the default).  Errors, in this order:
+ * FYPRT_EINVAL for a NULL context; FYPRT_EINVAL for a NULL array with a non-zero count or a non-NULL array with count 0; FYPRT_ESTATE
+ * before fyprt_upload_scene; FYPRT_EINVAL for a mesh_count different from the scene's mesh count.  Host-only contexts accept the call
+ * (the table is kept, there is nothing to build).  The call waits for the context stream. */
+int fyprt_set_mesh_query_masks(fyprt_context* ctx, const uint32_t* masks, uint32_t mesh_count);
+/* One mask for all later query calls of the context, in any state of the context, before or after the table.  A plain launch argument: a
+ * device-entry call uses the value in effect when it was enqueued.  FYPRT_EINVAL for a NULL context. */
+int fyprt_set_query_mask(fyprt_context* ctx, uint32_t query_mask);
+/* The filter as it is: *mesh_count = the table's length (0: the filter is off), masks (NULL: only the count is wanted) the table, builds
+ * the number of times the device data has been built since the context was created.  Any out-pointer but mesh_count may be NULL.
+ * FYPRT_EINVAL for a NULL context or mesh_count. */
+int fyprt_get_query_filter(fyprt_context* ctx, uint32_t* masks, uint32_t* mesh_count, uint32_t* query_mask, uint64_t* builds);
+
 /* ================================================================================================= radiance queries
  * New (no reference counterpart): the renderer's sample of techniques 0-6 for the caller's own rays — other camera models, light probes,
  * surface bakes, re-rendering a few pixels ("Radiance queries").  Only an uploaded scene is needed (no resize, no camera).

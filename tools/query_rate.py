@@ -22,7 +22,15 @@ With --boxes K [K ...]: the box-overlap query (fyprt_overlap_boxes) on three set
 half extents of 0.1 %, 0.5 % and 2 % of the scene diameter: per set and K the median, minimum and maximum hipEvent ms, Mboxes/s, node
 visits, box and triangle tests and accepted triangles per box (one counted call), and the ratio to the closest-hit query of the camera
 rays, timed in the same run.  Written to profiles/query/boxes_rate.jsonl unless --out names another file.
-  usage: python tools/query_rate.py --boxes 1 8 32 [--calls 20] [--out FILE.jsonl]"""
+  usage: python tools/query_rate.py --boxes 1 8 32 [--calls 20] [--out FILE.jsonl]
+With --filter: the query filter (fyprt_set_mesh_query_masks / fyprt_set_query_mask) on the bench hall.  Two contexts hold the scene, one
+with a mesh mask table and one without; per case the four families (closest hit, hits K = 4, nearest points, boxes K = 8) are timed on
+the same records, the two contexts' calls alternating: (1) a table and a query mask of all ones — the price of the checks; (2) one
+column excluded, nearest points at K = 1 placed on that column's own surface — the snap case; (3) only that column admitted, with the
+camera rays and whole-scene boxes.  Per row the median, minimum and maximum hipEvent ms of both launches, their ratio, and node visits
+and triangle tests per record of both (one counted call each).  Written to profiles/query/filter_rate.jsonl unless --out names
+another file.
+  usage: python tools/query_rate.py --filter [--calls 20] [--out FILE.jsonl]"""
 import argparse
 import json
 import statistics
@@ -273,6 +281,88 @@ def main_boxes(a):
     out.write_text("\n".join(lines) + "\n")
 
 
+def filter_rows(plain, filt, case, families, calls):
+    """The families of one case on both contexts: `families` maps a name to (records, call(ctx, with_stats) -> FrameStats)."""
+    rows = []
+    for name, (n, call) in families.items():
+        for _ in range(3):
+            call(plain), call(filt)
+        ms = {"unfiltered": [], "filtered": []}
+        for _ in range(calls):                                        # alternating: both see the same neighbours on the machine
+            ms["unfiltered"].append(call(plain).kernel_ms)
+            ms["filtered"].append(call(filt).kernel_ms)
+        row = {"case": case, "scene": "hall_1M", "query": name, "records": n, "calls": calls}
+        for which, ctx in (("unfiltered", plain), ("filtered", filt)):
+            ctx.set_ray_counting(True)
+            st = call(ctx)
+            ctx.set_ray_counting(False)
+            row.update({f"ms_median_{which}": round(statistics.median(ms[which]), 4), f"ms_min_{which}": round(min(ms[which]), 4),
+                        f"ms_max_{which}": round(max(ms[which]), 4), f"node_visits_per_record_{which}": round(st.node_visits / st.rays, 3),
+                        f"tri_tests_per_record_{which}": round(st.tri_tests / st.rays, 3), f"hit_fraction_{which}": round(st.hits / st.rays, 4)})
+        row["filtered_over_unfiltered"] = round(row["ms_median_filtered"] / row["ms_median_unfiltered"], 3)
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    return rows
+
+
+def main_filter(a):
+    W, H = 1920, 1080
+    rng = np.random.default_rng(2024)
+    hall, cam = scenes.hall_scene(), scenes.hall_camera(W, H)
+    plain, filt = capi.Context(0), capi.Context(0)
+    plain.upload_scene(hall)
+    filt.upload_scene(hall)
+    o, d = camera_rays(cam)
+    res = plain.trace_rays(o, d)
+    pos = hall.world_vertices["position"].astype(np.float64)
+    lo, hi = pos.min(axis=0), pos.max(axis=0)
+    diam = float(np.linalg.norm(hi - lo))
+    hit = res["objectIndex"] >= 0
+    centre = np.where(hit[:, None], res["worldPosition"], o + F32(0.5 * diam) * d).astype(F32)
+    h = F32(0.005 * diam)
+    blo, bhi = (centre - h).astype(F32), (centre + h).astype(F32)
+    # the column the camera sees most of: meshes 12 .. 75 are the columns (scenes.hall_scene)
+    first = np.array([m[0] for m in hall.meshes])
+    mesh_of_hit = np.searchsorted(first, res["objectIndex"][hit], side="right") - 1
+    seen = np.bincount(mesh_of_hit, minlength=len(hall.meshes))[12:76]
+    column = 12 + int(seen.argmax())
+    t0, nt = hall.meshes[column][0], hall.meshes[column][1]
+    # points on the column's own surface: uniform barycentrics on its triangles, drawn with replacement
+    tri = hall.triangles[t0 + rng.integers(0, nt, 1 << 18)]
+    r1, r2 = rng.random(len(tri)), rng.random(len(tri))
+    sq = np.sqrt(r1)
+    wp = hall.world_vertices["position"]
+    on_column = ((1 - sq)[:, None] * wp[tri["v0"]] + ((1 - r2) * sq)[:, None] * wp[tri["v1"]] + (r2 * sq)[:, None] * wp[tri["v2"]]).astype(F32)
+    whole = 64
+    wlo, whi = np.tile((lo - 1).astype(F32), (whole, 1)), np.tile((hi + 1).astype(F32), (whole, 1))
+
+    def families(points, k_points, boxes):
+        return {"closest": (len(o), lambda c: c.trace_rays(o, d, with_stats=True)[1]),
+                "hits_k4": (len(o), lambda c: c.trace_ray_hits(o, d, max_hits=4, with_stats=True)[2]),
+                f"points_k{k_points}": (len(points), lambda c: c.nearest_points(points, max_hits=k_points, with_stats=True)[2]),
+                "boxes_k8": (len(boxes[0]), lambda c: c.overlap_boxes(boxes[0], boxes[1], max_hits=8, with_stats=True)[3])}
+    nM = len(hall.meshes)
+    rows = []
+    filt.set_mesh_query_masks(np.full(nM, 0xFFFFFFFF, dtype=np.uint32))
+    rows += filter_rows(plain, filt, "1_all_ones", families(centre, 4, (blo, bhi)), a.calls)
+    M = np.ones(nM, dtype=np.uint32)
+    M[column] = 0
+    filt.set_mesh_query_masks(M)
+    rows += filter_rows(plain, filt, "2_column_excluded", families(on_column, 1, (blo, bhi)), a.calls)
+    M = np.zeros(nM, dtype=np.uint32)
+    M[column] = 1
+    filt.set_mesh_query_masks(M)
+    rows += filter_rows(plain, filt, "3_column_alone", families(centre, 1, (wlo, whi)), a.calls)
+    for r in rows:
+        r["column_mesh"], r["column_triangles"], r["filter_builds"] = column, int(nt), int(filt.query_filter()[2])
+    plain.close()
+    filt.close()
+    lines = [json.dumps(r) for r in rows]
+    out = Path(a.out) if a.out else ROOT / "profiles" / "query" / "filter_rate.jsonl"
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=20)
@@ -280,6 +370,7 @@ def main():
     ap.add_argument("--hits", type=int, nargs="+", default=None, metavar="K", help="time the multi-hit query at these max_hits instead")
     ap.add_argument("--points", type=int, nargs="+", default=None, metavar="K", help="time the nearest-point query at these max_hits instead")
     ap.add_argument("--boxes", type=int, nargs="+", default=None, metavar="K", help="time the box-overlap query at these max_hits instead")
+    ap.add_argument("--filter", action="store_true", help="time the four families with and without a query filter instead")
     a = ap.parse_args()
     if a.boxes and not all(1 <= k <= capi.OVERLAP_MAX_HITS for k in a.boxes):
         raise SystemExit(f"--boxes takes values in 1..{capi.OVERLAP_MAX_HITS}")
@@ -290,6 +381,8 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("query_rate.py needs an MI355X")
     torch.cuda.set_device(0)
+    if a.filter:
+        return main_filter(a)
     if a.hits:
         return main_hits(a)
     if a.points:
