@@ -305,6 +305,9 @@ static hipError_t sync_all(fyprt_context* c) {      // all three streams: `prim`
 // above the tree's level count, rounded DOWN to a stack size at which one more 256-thread workgroup fits the CU's 160 KB of
 // LDS (entries x 1 KB per workgroup: 32 -> 5 workgroups, 26 -> 6, 22 -> 7, 20 -> 8, 17 -> 9, 16 -> 10) as long as at least 4
 // entries of slack above the level count remain.  Never below the level count (the induction needs it), never above 31.
+// (k_di_part2_trace<false> adds 256 B of static LDS, the pair bytes of its cooperative leaf phase: the sizes 26, 22 and 17 keep their
+// residency, the exact fits 32, 20 and 16 hold one workgroup fewer for that kernel alone — which shows in unpipelined frames only,
+// pipelined ones cap the persistent grid at 4 per CU.  The table is not re-tuned for it: not measured.)
 static int effective_stack_budget(const fyprt_context* c) {
     const int levels = (int)c->hostBvh.levels;
     if (c->tuning[K_STACK_BUDGET] > 0) return std::min((int)rth::kStackBudget, std::max(levels, c->tuning[K_STACK_BUDGET]));
@@ -1951,6 +1954,14 @@ static int enqueue_di_wavefront_part2(FrameRun& f) {
     // multi-GPU band would otherwise park idle workgroups on the LDS / wave slots the next frame's Part 1 is waiting for
     const uint32_t traceGrid = std::max(8u, std::min((uint32_t)(c->numCUs * perCU), grid.x));
     hipLaunchKernelGGL(c->countRays ? k_di_part2_trace<true> : k_di_part2_trace<false>, dim3(traceGrid), block, f.ldsBytes, c->stream, f.sc, f.fr, q);
+#ifdef RT_DI_LEAF_STATS
+    {   // test build only (rt_wavefront.h): the kinds of leaf phase the production kernel ran in this frame
+        uint32_t kinds = 0;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpy(&kinds, q.counters + 3, sizeof kinds, hipMemcpyDeviceToHost));
+        std::fprintf(stderr, "fyprt leaf phases: grid %u, rays %s, kinds 0x%x (1 one round, 2 over 64 pairs, 4 single-triangle leaves, 8 closest-mode lane)\n", traceGrid, c->countRays ? "counted" : "production", kinds);
+    }
+#endif
     f.launches = 3;
     return FYPRT_OK;
 }

@@ -12,6 +12,7 @@
 //                     shadow rays differ 10x in length (lane utilisation of the one-thread-per-pixel Part 2: 35 %).
 //                     Chunks: the first one of every wave is static, the rest are stolen from a shared head and shrink
 //                     towards the end of the queue (see the kernel).  The ray-less list's epilogues run first, at full width.
+//                     A leaf phase tests the (lane, triangle) pairs of all lanes at a leaf spread over the wave's 64 lanes (production kernel).
 //
 // All epilogues of a wavefront frame run in the trace kernel, and Part 1 touches neither image nor accumulation
 // (DevFrame::p1Mode): that is what lets the host run Part 1 + setup of the next frame on a second stream beside it.
@@ -316,8 +317,43 @@ RT_DEV int32_t lane_pop(int32_t* lds, int& top) { --top; return lds[top * kBlock
 #ifndef RT_TRACE_WAVES
 #define RT_TRACE_WAVES __attribute__((amdgpu_waves_per_eu(6)))
 #endif
+// The leaf phase of the production kernel (COUNT == false) runs at the wave's full width: the (lane, triangle) pairs of the lanes at a leaf are
+// spread over all 64 lanes.  The instrumented kernel keeps the serial loop, which is also what -DRT_DI_COOP_LEAF=0 builds
+// (tools/build_variant.sh).  No operation on a ray changes.
+#ifndef RT_DI_COOP_LEAF
+#define RT_DI_COOP_LEAF 1
+#endif
+
+// One leaf triangle against a shadow ray for the cooperative leaf phase: the serial leaf loop's Möller–Trumbore, operation for operation.
+// Returns true and sets t when the loop's early-outs let the triangle through — written as the same comparisons, so a NaN u or v
+// (degenerate triangle: det == 0) passes exactly where `if (u < 0.0f || u > 1.0f) continue;` does not continue.
+RT_DEV bool leaf_tri_test(const float4 a, const float4 b, const float4 c, const f3 o, const f3 d, float& t) {
+    const f3 v0 = mk3(a.x, a.y, a.z), e1 = mk3(a.w, b.x, b.y), e2 = mk3(b.z, b.w, c.x);
+    const f3 hh = cross(d, e2);
+    const float det = dot(e1, hh), f = 1.0f / det;
+    const f3 s = o - v0;
+    const float u = f * dot(s, hh);
+    if (u < 0.0f || u > 1.0f) return false;
+    const f3 qq = cross(s, e1);
+    const float v = f * dot(d, qq);
+    if (v < 0.0f || (u + v) > 1.0f) return false;
+    t = f * dot(e2, qq);
+    return true;
+}
+// bits of a ballot below the calling lane (== __popcll(mask & ((1ull << lane) - 1)) without keeping that lane mask in two registers)
+RT_DEV uint32_t lanes_below(unsigned long long mask) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u)); }
+// between a wave's LDS writes and its reads of what OTHER lanes of the same wave wrote (and back): compiler ordering only
+RT_DEV void wave_lds_order() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); }
+RT_DEV float lane_read(int byteLane, float v) { return __int_as_float(__builtin_amdgcn_ds_bpermute(byteLane, __float_as_int(v))); }
+
 template <bool COUNT>
 RT_DEV void di_part2_trace_body(const DevScene& sc, const DevFrame& fr, const ShadowQueue& q, int32_t* s_stack) {
+    constexpr bool COOP = !COUNT && RT_DI_COOP_LEAF != 0;
+    // COOP: the wave's 64 pair BYTES (owner lane | k << 6) — 256 B of static LDS per workgroup beside the dynamic stack slab.  The slab sizes
+    // of effective_stack_budget that leave room (26, 22, 17 entries: 6, 7, 9 workgroups per CU) keep their residency; the exact fits
+    // (32, 20, 16 entries x their workgroups = 160 KB) lose one workgroup per CU to any static byte — DESIGN.md §4.
+    uint8_t* pairs = nullptr;
+    if constexpr (COOP) { __shared__ uint8_t s_pairs[kBlock]; pairs = s_pairs + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * 64u; }
     int32_t* lds = s_stack + threadIdx.x;
     const float4* top4 = stage_top_nodes(sc.nodes, sc.topCount, sc.stackBudget, s_stack);
     const uint32_t lane = threadIdx.x & 63u;
@@ -344,7 +380,9 @@ RT_DEV void di_part2_trace_body(const DevScene& sc, const DevFrame& fr, const Sh
     LaneRay r; r.cur = kExit; r.top = 0; r.nBox = 0; r.nTri = 0; r.nNode = 0;
     bool active = false;                                           // lane owns a ray that is still being traced
     bool pending = false;                                          // lane's ray is finished, its pixel epilogue not yet run
-    uint32_t outcome = 0;                                          // of the finished ray: 0 occluded, 1 light visible, 2 nothing hit (sky)
+    // of a finished ray: 0 occluded, 1 light visible (R.cu:2016-2027: Lvis), 2 nothing hit (R.cu:2028-2031: Lsky) — read off the lane's ray,
+    // which stays in place until the refill that follows the lane's epilogue
+    auto outcome_of = [](const LaneRay& x) -> uint32_t { return x.hitTri == (int32_t)x.lightTri ? 1u : (x.closestMode && x.hitTri < 0) ? 2u : 0u; };
     bool more = total != 0u;                                       // wave-uniform: tasks may remain (in the queue or in this wave's chunk)
     uint32_t chunkNext = myWave * first < total ? myWave * first : total;     // wave-uniform: this wave's claimed range of the queue
     uint32_t chunkEnd = (myWave + 1u) * first < total ? (myWave + 1u) * first : total;
@@ -355,6 +393,7 @@ RT_DEV void di_part2_trace_body(const DevScene& sc, const DevFrame& fr, const Sh
             // finished lanes run the fused epilogue together (accumulate, tonemap, pack) — batched here so that it
             // executes once per >= kRefillLanes rays instead of once per finished ray
             if (pending) {
+                const uint32_t outcome = outcome_of(r);
                 const float4 L = q.tasks[(size_t)r.task * 4 + (outcome == 2u ? 3 : 2)];
                 const uint32_t pixel = (uint32_t)__float_as_int(L.w);
                 const f3 radiance = (outcome != 0u) ? mk3(L.x, L.y, L.z) : splat3(0.0f);
@@ -370,11 +409,11 @@ RT_DEV void di_part2_trace_body(const DevScene& sc, const DevFrame& fr, const Sh
                 uint32_t size = (total - chunkEnd) / nWaves;
                 size = size < q.minChunk ? q.minChunk : (size > chunk ? chunk : size);
                 if (lane == 0u) base = dynBase + atomicAdd(q.counters + 2, size);
-                base = (uint32_t)__shfl((int)base, 0);
+                base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);       // (lane 0's: the claimed range stays in scalar registers)
                 chunkNext = base < total ? base : total;
                 chunkEnd = (base + size < total) ? base + size : total;
             }
-            const uint32_t slot = chunkNext + (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
+            const uint32_t slot = chunkNext + lanes_below(idle);
             const uint32_t want = (uint32_t)__popcll(idle), avail = chunkEnd - chunkNext;
             chunkNext += (want < avail) ? want : avail;
             more = chunkNext < chunkEnd || (hasDyn && chunkEnd < total);
@@ -408,7 +447,67 @@ RT_DEV void di_part2_trace_body(const DevScene& sc, const DevFrame& fr, const Sh
                 if ((uint32_t)__popcll(__ballot(walk)) < quorum) break;
             }
             // leaves
-            if (active && r.cur < 0 && r.cur != kExit) {
+            const bool atLeaf = active && r.cur < 0 && r.cur != kExit;
+            bool serialLeaves = true;                                      // wave-uniform
+            if constexpr (COOP) {
+                // COOPERATIVE LEAF PHASE.  A lane at a leaf has cnt = 1..4 triangles; tested one after the other the phase takes as many rounds
+                // as the fullest leaf, each with fewer lanes, while the lanes not at a leaf wait.  Here the (lane, k) pairs are numbered by an
+                // exclusive prefix of cnt over the lanes — four ballots (cnt >= 1..4), mbcnt prefix counts — and pair p is tested by lane p % 64 in
+                // round p / 64: the owner publishes (own lane | k << 6) in the wave's LDS byte p % 64, the helper reads it, fetches the owner's
+                // leaf and ray with cross-lane reads and runs the serial loop's test, operation for operation.  A ballot of "pair occludes"
+                // goes back to the owners.  Same-wave LDS traffic: DS operations of a wave execute in issue order, and wavefront-scope atomics +
+                // fences (no instruction on gfx950) keep the compiler from reordering them; no lane waits for anything but the wave's lock-step.
+                // The serial loop runs instead when a lane at a leaf is in closest mode (a shadow ray that missed its own light: it needs the
+                // running minimum with strict less, in triangle order) and when no leaf of the phase has a second triangle (nothing to gain).
+                const uint32_t cnt = atLeaf ? ((uint32_t)~r.cur & 3u) + 1u : 0u;
+                const unsigned long long m1 = __ballot(atLeaf), m2 = __ballot(cnt >= 2u);
+                serialLeaves = m2 == 0ull || __ballot(atLeaf && r.closestMode) != 0ull;
+#ifdef RT_DI_LEAF_STATS
+                // test build only: which kinds of leaf phase this frame ran, as flags in the spare word of the queue counters (the host prints them):
+                // 1 one cooperative round, 2 more than 64 pairs, 4 single-triangle leaves only (serial), 8 a closest-mode lane (serial)
+                {
+                    const uint32_t n = (uint32_t)(__popcll(m1) + __popcll(m2) + __popcll(__ballot(cnt >= 3u)) + __popcll(__ballot(cnt >= 4u)));
+                    if (m1 != 0ull && lane == 0u) atomicOr(q.counters + 3, m2 == 0ull ? 4u : serialLeaves ? 8u : n > 64u ? 2u : 1u);
+                }
+#endif
+                if (!serialLeaves) {
+                    const unsigned long long m3 = __ballot(cnt >= 3u), m4 = __ballot(cnt >= 4u);
+                    const uint32_t prefix = lanes_below(m1) + lanes_below(m2) + lanes_below(m3) + lanes_below(m4);
+                    const uint32_t nPairs = (uint32_t)(__popcll(m1) + __popcll(m2) + __popcll(m3) + __popcll(m4));     // wave-uniform, <= 256
+                    bool occluded = false;
+                    for (uint32_t base = 0; base < nPairs; base += 64u) {                // wave-uniform trip count
+#pragma unroll
+                        for (uint32_t k = 0; k < 4u; ++k)
+                            if (k < cnt && prefix + k - base < 64u) __hip_atomic_store(pairs + (prefix + k - base), (uint8_t)(lane | (k << 6)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                        wave_lds_order();
+                        const uint32_t word = __hip_atomic_load(pairs + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);   // (a lane past the last pair reads a stale byte and tests nothing)
+                        wave_lds_order();
+                        const bool helps = base + lane < nPairs;
+                        const int own = (int)(word & 63u) << 2;
+                        const uint32_t tri = ((uint32_t)~__builtin_amdgcn_ds_bpermute(own, r.cur) >> 2) + ((word >> 6) & 3u);
+                        const f3 o = mk3(lane_read(own, r.o.x), lane_read(own, r.o.y), lane_read(own, r.o.z));
+                        const f3 d = mk3(lane_read(own, r.d.x), lane_read(own, r.d.y), lane_read(own, r.d.z));
+                        const float tL = lane_read(own, r.tL);
+                        const uint32_t lightTri = (uint32_t)__builtin_amdgcn_ds_bpermute(own, (int)r.lightTri);
+                        bool hit = false;
+                        if (helps) {
+                            const float4* tp = sc.leafTris + (size_t)tri * 3;
+                            const float4 a = tp[0], b = tp[1], c = tp[2];
+                            float t;
+                            hit = (uint32_t)__float_as_int(c.y) != lightTri && leaf_tri_test(a, b, c, o, d, t) && t > 0.0001f && t < tL;
+                        }
+                        const unsigned long long hits = __ballot(hit);
+                        // the owner's pairs of this round: words [prefix - base, prefix + cnt - base) cut to [0, 64)
+                        const int lo = (int)prefix - (int)base, hi = lo + (int)cnt, lo0 = lo < 0 ? 0 : lo, hi0 = hi > 64 ? 64 : hi;
+                        if (hi0 > lo0) occluded = occluded || ((hits >> lo0) & (~0ull >> (64 - (hi0 - lo0)))) != 0ull;
+                    }
+                    // WHICH occluder is recorded does not matter.  A lane here is not in closest mode, so its outcome is (hitTri == lightTri) ? 1 : 0;
+                    // the light triangle itself is never tested (skipped above as in the serial loop), so every triangle the serial loop could
+                    // record as the occluder has an id other than lightTri, and all of them give outcome 0.  -1 is such an id too: no triangle's.
+                    if (atLeaf) { if (occluded) r.hitTri = -1; r.cur = occluded ? kExit : lane_pop(lds, r.top); }
+                }
+            }
+            if (serialLeaves && atLeaf) {
                 const uint32_t code = (uint32_t)~r.cur, first = code >> 2, cnt = (code & 3u) + 1u;
                 bool occluded = false;
                 for (uint32_t k = 0; k < cnt; ++k) {
@@ -437,9 +536,6 @@ RT_DEV void di_part2_trace_body(const DevScene& sc, const DevFrame& fr, const Sh
             }
             // finished lanes: select the pixel's radiance, park it until the next batched epilogue
             if (active && r.cur == kExit) {
-                outcome = 0u;
-                if (r.hitTri == (int32_t)r.lightTri) outcome = 1u;                      // R.cu:2016-2027: Lvis
-                else if (r.closestMode && r.hitTri < 0) outcome = 2u;                   // R.cu:2028-2031: Lsky
                 pending = true;
                 if (COUNT) {
                     // same totals as trace_shadow: the fallback counts its light test, then a full closest-hit ray

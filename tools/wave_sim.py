@@ -9,7 +9,17 @@ frame of the 1 M-triangle hall (single-threaded render), and this script replays
 kernel's refill rule.  Cost model (cycles of SIMD issue per wave, from the instruction mix of the ISA and the measured issue costs):
 node round 600, triangle round 230 (+40 per leaf phase), refill + epilogues 600.
 
-  usage: python tools/wave_sim.py [width height]      -> one JSON line per policy (total issue cycles, lane utilisation)"""
+Two policies model full-width parts of the production kernel (rt_wavefront.h: RT_DI_COOP_LEAF is in the tree, the epilogue pass was measured
+slower and is not — DESIGN.md §8 (10)):
+  cooperative leaf phase   a phase whose lanes hold P triangle tests costs ceil(P / 64) triangle rounds, each with an overhead (publish, read, nine
+                           cross-lane reads, ballot) swept over 100 / 200 / 300 cycles; a phase in which no lane has more than one logged test is priced as the one serial round.
+                           The log holds the tests the serial loop RAN, and a cooperative phase tests every triangle of a leaf, also behind the
+                           occluder the serial loop stopped at: priced twice, as logged (lower bound) and with the last leaf of every ray that ends
+                           on a leaf padded to the 4 triangles a leaf can hold (upper bound).
+  epilogues out of the refill   C_REFILL is split by the vector instructions of the two blocks in the kernel's ISA (epilogue 165, refill 108: 0.6 / 0.4);
+                           the epilogue share is charged once per 64 tasks instead of once per refill.
+
+  usage: python tools/wave_sim.py [width height [hall|hall_small]]   -> one JSON line per policy (total issue cycles, lane utilisation)"""
 import json
 import sys
 import time
@@ -26,10 +36,11 @@ from fypraytracer_amd import capi, scenes  # noqa: E402
 from oraclelib import Oracle  # noqa: E402
 
 C_NODE, C_TRI, C_LEAF_PHASE, C_REFILL = 600, 230, 40, 600
+EPILOGUE_SHARE = 165 / (165 + 108)          # of C_REFILL, by vector instructions
 
 
-def record(W, H):
-    sc = scenes.hall_scene()
+def record(W, H, scene="hall"):
+    sc = scenes.hall_scene() if scene == "hall" else scenes.hall_scene_small()
     cam = scenes.hall_camera(W, H)
     ctx = capi.Context(-1)
     ctx.upload_scene(sc)
@@ -82,8 +93,8 @@ def split_rays(buf):
 class Wave:
     """64 lanes x `slots` rays per lane; a ray = a row of the padded event matrix E (0 node visit, 100 + k leaf with k triangle tests, -1 end)"""
 
-    def __init__(self, E, first, count, slots=1, postpone=0):
-        self.E, self.next, self.end, self.slots = E, first, first + count, slots
+    def __init__(self, E, first, count, slots=1, postpone=0, refill_cost=C_REFILL):
+        self.E, self.next, self.end, self.slots, self.refill_cost = E, first, first + count, slots, refill_cost
         self.postpone = postpone            # leaves a lane may carry along while it keeps walking inner nodes ("speculative" traversal)
         self.held = np.zeros((64, slots), dtype=np.int64)
         self.task = np.full((64, slots), -1, dtype=np.int64)
@@ -137,6 +148,19 @@ class Wave:
         self.held = np.where(self.tri == 0, 0, self.held)
         self.cycles += C_TRI; self.lane_cycles += C_TRI * int(t.sum())
 
+    def coop_phase(self, t, overhead, hist):
+        """all pending triangle tests of the lanes in `t` in ceil(P / 64) rounds.  `single`: no lane has more than one LOGGED test left — priced as
+        the one serial round.  The log has no leaf sizes, so this is not the kernel's own rule (no leaf of the phase has a second triangle): a
+        larger leaf with one test run counts here too, and the figure is an upper bound of the phases that take the kernel's fallback."""
+        t = self.first_slot(t)
+        pairs = int(self.tri[t].sum())
+        single = int(self.tri[t].max()) <= 1
+        rounds = 1 if single else -(-pairs // 64)
+        self.tri = np.where(t, 0, self.tri)
+        self.held = np.where(self.tri == 0, 0, self.held)
+        self.cycles += rounds * (C_TRI + (0 if single else overhead)); self.lane_cycles += C_TRI * pairs
+        hist["phases"] += 1; hist["single"] += single; hist["over64"] += pairs > 64
+
     def idle_slots(self):
         return int((self.task < 0).sum())
 
@@ -147,12 +171,17 @@ class Wave:
             l, sl = free[k]
             self.task[l, sl] = self.next + k; self.pos[l, sl] = 0; self.tri[l, sl] = 0; self.held[l, sl] = 0
         self.next += got
-        self.cycles += C_REFILL; self.lane_cycles += C_REFILL * min(64, got)
+        self.cycles += self.refill_cost; self.lane_cycles += self.refill_cost * min(64, got)
 
 
-def run_kernel_policy(E, first, count, quorum=24, refill_lanes=24, slots=1, greedy=False, tri_weight=1.0, select_cost=0, select_cost_tri=None, postpone=0, leaf_quorum=0):
-    """the persistent kernel's loop (rt_wavefront.h) on one wave; greedy: every round is the kind with the larger (lanes / cost)"""
-    w = Wave(E, first, count, slots, postpone)
+def run_kernel_policy(E, first, count, quorum=24, refill_lanes=24, slots=1, greedy=False, tri_weight=1.0, select_cost=0, select_cost_tri=None, postpone=0, leaf_quorum=0,
+                      coop=None, defer_epilogue=False, hist=None):
+    """the persistent kernel's loop (rt_wavefront.h) on one wave; greedy: every round is the kind with the larger (lanes / cost);
+    coop: overhead cycles of a cooperative triangle round (None: serial leaf loop); defer_epilogue: epilogues once per 64 tasks, after the loop"""
+    w = Wave(E, first, count, slots, postpone, refill_cost=C_REFILL * (1.0 - EPILOGUE_SHARE) if defer_epilogue else C_REFILL)
+    if defer_epilogue:
+        w.cycles += C_REFILL * EPILOGUE_SHARE * -(-count // 64); w.lane_cycles += C_REFILL * EPILOGUE_SHARE * count
+    hist = hist if hist is not None else {"phases": 0, "single": 0, "over64": 0}
     while True:
         more = w.next < w.end
         if more and (w.idle_slots() >= refill_lanes * slots or not (w.task >= 0).any()):
@@ -181,6 +210,9 @@ def run_kernel_policy(E, first, count, quorum=24, refill_lanes=24, slots=1, gree
                         break
                 if t.any():
                     w.cycles += C_LEAF_PHASE
+                    if coop is not None:
+                        w.coop_phase(t, coop, hist)
+                        n, t = w.want()
                     while t.any():                               # leaf phase: every lane at a leaf tests all its triangles
                         w.tri_round(t)
                         n, t = w.want()
@@ -236,11 +268,12 @@ def run_workgroup_repack(E, first, count, repack_cost=0, refill_rays=96, lanes=2
 
 def main():
     W, H = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (256, 144)
-    cache = Path(f"/tmp/wave_sim_events2_{W}x{H}.npz")
+    scene = sys.argv[3] if len(sys.argv) > 3 else "hall"
+    cache = Path(f"/tmp/wave_sim_events2_{scene}_{W}x{H}.npz")
     if cache.exists():
         z = np.load(cache); buf, live_px = z["buf"], z["live"]
     else:
-        buf, live_px = record(W, H)
+        buf, live_px = record(W, H, scene)
         np.savez(cache, buf=buf, live=live_px)
     rays = split_rays(buf)
     shadow = [q for k, q, l in rays if k == 1]
@@ -266,7 +299,7 @@ def main():
                 ("two rays per lane, greedy r16, slot select +57 per node round, +100 per triangle round", dict(greedy=True, refill_lanes=16, slots=2, select_cost=57, select_cost_tri=100)),
                 ("two rays per lane, greedy r16, +57 / +100, triangle rounds weighted x0.7", dict(greedy=True, refill_lanes=16, slots=2, select_cost=57, select_cost_tri=100, tri_weight=0.7)),
                 ("three rays per lane, greedy r16", dict(greedy=True, refill_lanes=16, slots=3)), ("four rays per lane, greedy r16", dict(greedy=True, refill_lanes=16, slots=4))]
-    nwaves = 24
+    nwaves = 24 if len(shadow) >= 24 * chunk else max(1, len(shadow) // chunk)
     per = (len(shadow) // nwaves // chunk) * chunk
     L = max(len(q) for q in shadow) + 1
 
@@ -293,6 +326,28 @@ def main():
             c += cc; l += ll
         print(json.dumps({"queue_order": oname, "policy": "kernel q24 r24", "issue_cycles_per_ray": round(c / (nwaves * per), 1), "lane_utilisation": round(l / (c * 64), 3)}), flush=True)
     E = matrix(orders.get("tiles (the setup kernel's order: 16x16 workgroups, 8x8 waves)", orders["row-major"]))
+    # the full-width parts.  Epad: the last leaf of a ray that ends on one holds 4 triangles (a cooperative phase tests all of them)
+    Epad = E.copy()
+    last = (E >= 0).sum(axis=1) - 1
+    rows = np.flatnonzero((last >= 0) & (E[np.arange(len(E)), np.maximum(last, 0)] > 100))
+    Epad[rows, last[rows]] = 104
+    nr = nwaves * per
+    base_cyc = sum(run_kernel_policy(E, wv * per, per)[0] for wv in range(nwaves))
+    for name, kw, mats in [("epilogues out of the refill (once per 64 tasks)", dict(defer_epilogue=True), [("as logged", E)])] + \
+            [(f"cooperative leaf phase, +{o} cycles per round", dict(coop=o), [("as logged", E), ("last leaf padded to 4", Epad)]) for o in (100, 200, 300)] + \
+            [(f"both, +{o} cycles per round", dict(coop=o, defer_epilogue=True), [("as logged", E), ("last leaf padded to 4", Epad)]) for o in (100, 200, 300)]:
+        for mname, M in mats:
+            hist = {"phases": 0, "single": 0, "over64": 0}
+            cyc = lane = 0
+            for wv in range(nwaves):
+                c, l = run_kernel_policy(M, wv * per, per, hist=hist, **kw)
+                cyc += c; lane += l
+            out = {"policy": name, "triangle_tests": mname, "issue_cycles_per_ray": round(cyc / nr, 1), "vs_kernel_q24_r24": round(cyc / base_cyc, 4), "lane_utilisation": round(lane / (cyc * 64), 3)}
+            if "coop" in kw:
+                out.update(leaf_phases=hist["phases"], phases_with_at_most_one_logged_test_per_lane=hist["single"], phases_over_64_tests=hist["over64"])
+            print(json.dumps(out), flush=True)
+    if scene != "hall":
+        return
     # "Speculative" traversal: a lane that reaches a leaf carries it along and keeps walking inner nodes until its next leaf (or the end), so more
     # lanes share a node round.  A shadow ray that the carried leaf would have ended (occluded) walks on in vain until the leaf phase: priced by
     # appending the ray's mean node run between leaves to every ray that ends on a leaf (pessimistic: not every such ray is occluded).
