@@ -434,6 +434,11 @@ static int launch_query_kernels(fyprt_context* c, fyprt_context::QueryFamily& f,
 // the lazy build of the filter's device data; with the filter off the launch is the one it always was.  occIndex: which of the
 // family's occupancy entries (the ray query's kind).
 template <class Q> struct QueryKernels { void (*plain[2][2])(DevScene, Q); void (*filtered[2][2])(DevScene, Filtered<Q>); };
+// ... derived from the family's lane state LaneT<FILTER> (rt_query.h's three kernel templates): no cell is typed by hand
+template <template <bool> class LaneT> static constexpr QueryKernels<typename LaneT<false>::Query> query_kernels() {
+    return {{{k_query<LaneT<false>>, k_query_counted<LaneT<false>>}, {k_query_simple<LaneT<false>, false>, k_query_simple<LaneT<false>, true>}},
+            {{k_query<LaneT<true>>, k_query_counted<LaneT<true>>}, {k_query_simple<LaneT<true>, false>, k_query_simple<LaneT<true>, true>}}};
+}
 static int ensure_query_filter(fyprt_context* c);
 template <class Q>
 static int launch_query(fyprt_context* c, fyprt_context::QueryFamily& f, int occIndex, const Q& q, const QueryKernels<Q>& k, size_t listBytes,
@@ -484,6 +489,74 @@ static int run_host_query(fyprt_context* c, fyprt_context::QueryFamily& f, const
         }
     }
     return FYPRT_OK;
+}
+
+// ---- the list queries: multi-hit (rt_query.h), nearest points (rt_points.h) and box overlap (rt_boxes.h).  As the batched queries:
+// the scene is read, the query's own results and counters are written, no frame state moves.
+// A family: state, kernels[simple][counted] in both forms, and what differs between the families — float4s per input record, bytes per
+// `after` record and per list entry (16: a hit record; 4: a bare triangle index), the cap on max_hits, whether a totals array follows
+// the list; `noun` / `outNoun`: what its records and answers are called, `verb`: what a host-only context is told it cannot do.
+template <class Q> struct ListQuery {
+    fyprt_context::QueryFamily fyprt_context::* family; QueryKernels<Q> kernels;
+    size_t inQuads, afterBytes, entryBytes; uint32_t maxHitsCap; bool totals;
+    const char *noun, *outNoun, *verb;
+};
+static const ListQuery<QueryHits> kRayHits = {&fyprt_context::hitsQuery, query_kernels<HitsLaneT>(), 2, 16, 16, FYPRT_QUERY_MAX_HITS, false, "rays", "hits", "trace"};
+static const ListQuery<QueryHits> kNearestPoints = {&fyprt_context::pointsQuery, query_kernels<PointsLaneT>(), 1, 16, 16, FYPRT_QUERY_MAX_HITS, false, "points", "hits", "query"};
+static const ListQuery<QueryBoxes> kOverlapBoxes = {&fyprt_context::boxesQuery, query_kernels<BoxLaneT>(), 2, 4, 4, FYPRT_OVERLAP_MAX_HITS, true, "boxes", "triangles", "query"};
+
+// `who`: the entry point.  Input records are loaded as 16-byte quads; `after` and the list are loaded and stored in their own units.
+template <class Q>
+static int check_list_query(fyprt_context* c, const ListQuery<Q>& l, const char* who, const void* in, const void* after, uint32_t count, uint32_t maxHits, const void* out,
+                            const void* hitCounts, const void* totals, bool device) {
+    if (!c) return FYPRT_EINVAL;
+    if (maxHits == 0 || maxHits > l.maxHitsCap) return c->fail(FYPRT_EINVAL, std::string(who) + ": max_hits must be 1.." + std::to_string(l.maxHitsCap));
+    if (count && (!in || !out)) return c->fail(FYPRT_EINVAL, std::string(who) + ": NULL " + l.noun + " / " + l.outNoun + " with a non-zero count");
+    if (device && (((uintptr_t)in & 15u) || ((uintptr_t)after & (l.afterBytes - 1)) || ((uintptr_t)out & (l.entryBytes - 1)) || ((uintptr_t)hitCounts & 3u) || ((uintptr_t)totals & 3u))) {
+        std::vector<const char*> by[2] = {{l.noun}, {}};          // what must be 16-byte, what 4-byte aligned
+        by[l.afterBytes == 16 ? 0 : 1].push_back("after"); by[l.entryBytes == 16 ? 0 : 1].push_back(l.outNoun);
+        by[1].push_back("hit_counts"); if (l.totals) by[1].push_back("totals");
+        const auto join = [](const std::vector<const char*>& v) {
+            std::string s;
+            for (size_t i = 0; i < v.size(); ++i) s += std::string(i == 0 ? "" : i + 1 == v.size() ? " and " : ", ") + v[i];
+            return s;
+        };
+        return c->fail(FYPRT_EINVAL, std::string(who) + ": " + join(by[0]) + " must be 16-byte and " + join(by[1]) + " 4-byte aligned");
+    }
+    if (c->hostOnly) return c->fail(FYPRT_ESTATE, std::string(who) + ": host-only context (device -1) cannot " + l.verb);
+    if (!c->haveScene) return c->fail(FYPRT_ESTATE, std::string(who) + " before fyprt_upload_scene");
+    return FYPRT_OK;
+}
+static void list_record(QueryHits& q, const float4* in, const void* after, void* out, uint32_t* counts, uint32_t*) {
+    q.rays = in; q.after = static_cast<const float4*>(after); q.hits = static_cast<float4*>(out); q.counts = counts;
+}
+static void list_record(QueryBoxes& q, const float4* in, const void* after, void* out, uint32_t* counts, uint32_t* totals) {
+    q.boxes = in; q.after = static_cast<const uint32_t*>(after); q.triangles = static_cast<uint32_t*>(out); q.counts = counts; q.totals = totals;
+}
+// (device memory, count > 0, after / counts / totals may be NULL)
+template <class Q>
+static int enqueue_list_query(fyprt_context* c, const ListQuery<Q>& l, const float4* in, const void* after, uint32_t count, uint32_t maxHits, void* out, uint32_t* counts,
+                              uint32_t* totals, bool timed) {
+    Q q{};
+    list_record(q, in, after, out, counts, totals); q.count = count; q.maxHits = maxHits;
+    // key 2 no higher than the occupancy, 2 workgroups per CU without one
+    return launch_query(c, c->*l.family, 0, q, l.kernels, (size_t)maxHits * l.entryBytes, true, 2, timed);
+}
+template <class Q>
+static int host_list_query(fyprt_context* c, const ListQuery<Q>& l, const void* in, const void* after, uint32_t count, uint32_t maxHits, void* out, uint32_t* hitCounts,
+                           uint32_t* totals, fyprt_frame_stats* stats) {
+    HostQuery h{in, l.inQuads, after, out, (size_t)count * maxHits * l.entryBytes, hitCounts, true};
+    h.afterBytes = l.afterBytes;
+    if (l.totals) { h.tail = totals; h.tailBytes = (size_t)count * 4u; }       // staged behind the list whether or not the caller wants it
+    return run_host_query(c, c->*l.family, h, count, stats, [&](const float4* dIn, const float4* dAfter, uint32_t* dOut, uint32_t* dCounts) {
+        return enqueue_list_query(c, l, dIn, dAfter, count, maxHits, dOut, dCounts, l.totals ? dOut + h.outBytes / 4 : nullptr, true); });
+}
+template <class Q>
+static int device_list_query(fyprt_context* c, const ListQuery<Q>& l, const void* in, const void* after, uint32_t count, uint32_t maxHits, void* out, void* hitCounts,
+                             void* totals) {
+    if (count == 0) return FYPRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    return enqueue_list_query(c, l, static_cast<const float4*>(in), after, count, maxHits, out, static_cast<uint32_t*>(hitCounts), static_cast<uint32_t*>(totals), false);
 }
 
 extern "C" {
@@ -2331,11 +2404,7 @@ static int check_query(fyprt_context* c, int query, const void* rays, uint32_t c
 // `filterable`: a ray query proper, which the query filter applies to; the radiance queries' primary pass is not
 static int enqueue_query(fyprt_context* c, int query, const float4* rays, uint32_t count, void* results, bool timed, bool filterable) {
     const int occluded = query == FYPRT_QUERY_OCCLUDED ? 1 : 0;
-    static const QueryKernels<QueryRays> kQuery[2] = {
-        {{{k_query_rays<false, false>, k_query_rays<false, true>}, {k_query_rays_simple<false, false>, k_query_rays_simple<false, true>}},
-         {{k_query_rays_filtered<false, false>, k_query_rays_filtered<false, true>}, {k_query_rays_simple_filtered<false, false>, k_query_rays_simple_filtered<false, true>}}},
-        {{{k_query_rays<true, false>, k_query_rays<true, true>}, {k_query_rays_simple<true, false>, k_query_rays_simple<true, true>}},
-         {{k_query_rays_filtered<true, false>, k_query_rays_filtered<true, true>}, {k_query_rays_simple_filtered<true, false>, k_query_rays_simple_filtered<true, true>}}}};
+    static const QueryKernels<QueryRays> kQuery[2] = {query_kernels<ClosestLane>(), query_kernels<OccludedLane>()};
     QueryRays q{};
     q.rays = rays; q.results = results; q.count = count;
     // key 2 taken as it is, 4 workgroups per CU without an occupancy, the occupancy cached per kind
@@ -2356,64 +2425,24 @@ int fyprt_trace_rays_device(fyprt_context* c, int query, const void* rays, uint3
     return enqueue_query(c, query, static_cast<const float4*>(rays), count, results, false, true);
 }
 
-// ---- the list queries: multi-hit (rt_query.h: k_query_hits / k_query_hits_simple) and nearest points (rt_points.h: k_query_points /
-// k_query_points_simple).  As the batched queries: the scene is read, the query's own results and counters are written, no frame state
-// moves.  `who`: the entry point, `noun`: what its records are called, `verb`: what a host-only context is told it cannot do.
-static int check_list_query(fyprt_context* c, const char* who, const char* noun, const char* verb, const void* in, const void* after, uint32_t count,
-                            uint32_t maxHits, const void* hits, const void* hitCounts, bool device) {
-    if (!c) return FYPRT_EINVAL;
-    if (maxHits == 0 || maxHits > FYPRT_QUERY_MAX_HITS) return c->fail(FYPRT_EINVAL, std::string(who) + ": max_hits must be 1.." + std::to_string(FYPRT_QUERY_MAX_HITS));
-    if (count && (!in || !hits)) return c->fail(FYPRT_EINVAL, std::string(who) + ": NULL " + noun + " / hits with a non-zero count");
-    if (device && (((uintptr_t)in & 15u) || ((uintptr_t)after & 15u) || ((uintptr_t)hits & 15u) || ((uintptr_t)hitCounts & 3u)))   // 16-byte loads and stores, 4-byte counts
-        return c->fail(FYPRT_EINVAL, std::string(who) + ": " + noun + ", after and hits must be 16-byte and hit_counts 4-byte aligned");
-    if (c->hostOnly) return c->fail(FYPRT_ESTATE, std::string(who) + ": host-only context (device -1) cannot " + verb);
-    if (!c->haveScene) return c->fail(FYPRT_ESTATE, std::string(who) + " before fyprt_upload_scene");
-    return FYPRT_OK;
-}
-// The two families of list queries: state, kernels[simple][counted] in both forms, float4s per input record
-struct ListQuery { fyprt_context::QueryFamily fyprt_context::* family; QueryKernels<QueryHits> kernels; size_t inQuads; };
-static const ListQuery kRayHits = {&fyprt_context::hitsQuery, {{{k_query_hits<false>, k_query_hits<true>}, {k_query_hits_simple<false>, k_query_hits_simple<true>}},
-                                                               {{k_query_hits_filtered<false>, k_query_hits_filtered<true>}, {k_query_hits_simple_filtered<false>, k_query_hits_simple_filtered<true>}}}, 2};
-static const ListQuery kNearestPoints = {&fyprt_context::pointsQuery, {{{k_query_points<false>, k_query_points<true>}, {k_query_points_simple<false>, k_query_points_simple<true>}},
-                                                                       {{k_query_points_filtered<false>, k_query_points_filtered<true>}, {k_query_points_simple_filtered<false>, k_query_points_simple_filtered<true>}}}, 1};
-// (device memory, count > 0, after / counts may be NULL)
-static int enqueue_list_query(fyprt_context* c, const ListQuery& l, const float4* in, const float4* after, uint32_t count, uint32_t maxHits, float4* hits, uint32_t* counts, bool timed) {
-    fyprt_context::QueryFamily& f = c->*l.family;
-    QueryHits q{};
-    q.rays = in; q.after = after; q.hits = hits; q.counts = counts; q.count = count; q.maxHits = maxHits;
-    // key 2 no higher than the occupancy, 2 workgroups per CU without one
-    return launch_query(c, f, 0, q, l.kernels, (size_t)maxHits * 16u, true, 2, timed);
-}
-static int host_list_query(fyprt_context* c, const ListQuery& l, const void* in, const void* after, uint32_t count, uint32_t maxHits, void* hits, uint32_t* hitCounts,
-                           fyprt_frame_stats* stats) {
-    const HostQuery h{in, l.inQuads, after, hits, (size_t)count * maxHits * sizeof(float4), hitCounts, true};
-    return run_host_query(c, c->*l.family, h, count, stats, [&](const float4* dIn, const float4* dAfter, uint32_t* dOut, uint32_t* dCounts) {
-        return enqueue_list_query(c, l, dIn, dAfter, count, maxHits, reinterpret_cast<float4*>(dOut), dCounts, true); });
-}
-static int device_list_query(fyprt_context* c, const ListQuery& l, const void* in, const void* after, uint32_t count, uint32_t maxHits, void* hits, void* hitCounts) {
-    if (count == 0) return FYPRT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    return enqueue_list_query(c, l, static_cast<const float4*>(in), static_cast<const float4*>(after), count, maxHits, static_cast<float4*>(hits),
-                              static_cast<uint32_t*>(hitCounts), false);
-}
-
+// ---- the list queries' entry points (ListQuery and its helpers, templates, stand before the extern "C" block)
 int fyprt_trace_ray_hits(fyprt_context* c, const fyprt_ray* rays, const fyprt_ray_hit* after, uint32_t count, uint32_t max_hits, fyprt_ray_hit* hits,
                          uint32_t* hit_counts, fyprt_frame_stats* stats) {
-    TRY(check_list_query(c, "fyprt_trace_ray_hits", "rays", "trace", rays, after, count, max_hits, hits, hit_counts, false));
-    return host_list_query(c, kRayHits, rays, after, count, max_hits, hits, hit_counts, stats);
+    TRY(check_list_query(c, kRayHits, "fyprt_trace_ray_hits", rays, after, count, max_hits, hits, hit_counts, nullptr, false));
+    return host_list_query(c, kRayHits, rays, after, count, max_hits, hits, hit_counts, nullptr, stats);
 }
 int fyprt_trace_ray_hits_device(fyprt_context* c, const void* rays, const void* after, uint32_t count, uint32_t max_hits, void* hits, void* hit_counts) {
-    TRY(check_list_query(c, "fyprt_trace_ray_hits_device", "rays", "trace", rays, after, count, max_hits, hits, hit_counts, true));
-    return device_list_query(c, kRayHits, rays, after, count, max_hits, hits, hit_counts);
+    TRY(check_list_query(c, kRayHits, "fyprt_trace_ray_hits_device", rays, after, count, max_hits, hits, hit_counts, nullptr, true));
+    return device_list_query(c, kRayHits, rays, after, count, max_hits, hits, hit_counts, nullptr);
 }
 int fyprt_nearest_points(fyprt_context* c, const fyprt_point* points, const fyprt_point_hit* after, uint32_t count, uint32_t max_hits, fyprt_point_hit* hits,
                          uint32_t* hit_counts, fyprt_frame_stats* stats) {
-    TRY(check_list_query(c, "fyprt_nearest_points", "points", "query", points, after, count, max_hits, hits, hit_counts, false));
-    return host_list_query(c, kNearestPoints, points, after, count, max_hits, hits, hit_counts, stats);
+    TRY(check_list_query(c, kNearestPoints, "fyprt_nearest_points", points, after, count, max_hits, hits, hit_counts, nullptr, false));
+    return host_list_query(c, kNearestPoints, points, after, count, max_hits, hits, hit_counts, nullptr, stats);
 }
 int fyprt_nearest_points_device(fyprt_context* c, const void* points, const void* after, uint32_t count, uint32_t max_hits, void* hits, void* hit_counts) {
-    TRY(check_list_query(c, "fyprt_nearest_points_device", "points", "query", points, after, count, max_hits, hits, hit_counts, true));
-    return device_list_query(c, kNearestPoints, points, after, count, max_hits, hits, hit_counts);
+    TRY(check_list_query(c, kNearestPoints, "fyprt_nearest_points_device", points, after, count, max_hits, hits, hit_counts, nullptr, true));
+    return device_list_query(c, kNearestPoints, points, after, count, max_hits, hits, hit_counts, nullptr);
 }
 
 // ---- query filters (rt_filter.h): the mesh mask table and the query mask.  Host state only; the device data is built by the next
@@ -2439,46 +2468,16 @@ int fyprt_get_query_filter(fyprt_context* c, uint32_t* masks, uint32_t* mesh_cou
     return FYPRT_OK;
 }
 
-// ---- box-overlap queries (rt_boxes.h: k_query_boxes / k_query_boxes_simple): a list query whose entries are bare triangle indices,
-// with a total beside the count.  The scene is read, the query's own results and counters are written, no frame state moves.
-static int check_overlap_boxes(fyprt_context* c, const char* who, const void* boxes, const void* after, uint32_t count, uint32_t maxHits, const void* triangles,
-                               const void* hitCounts, const void* totals, bool device) {
-    if (!c) return FYPRT_EINVAL;
-    if (maxHits == 0 || maxHits > FYPRT_OVERLAP_MAX_HITS) return c->fail(FYPRT_EINVAL, std::string(who) + ": max_hits must be 1.." + std::to_string(FYPRT_OVERLAP_MAX_HITS));
-    if (count && (!boxes || !triangles)) return c->fail(FYPRT_EINVAL, std::string(who) + ": NULL boxes / triangles with a non-zero count");
-    if (device && (((uintptr_t)boxes & 15u) || ((uintptr_t)after & 3u) || ((uintptr_t)triangles & 3u) || ((uintptr_t)hitCounts & 3u) || ((uintptr_t)totals & 3u)))   // 16-byte loads, 4-byte words
-        return c->fail(FYPRT_EINVAL, std::string(who) + ": boxes must be 16-byte and after, triangles, hit_counts and totals 4-byte aligned");
-    if (c->hostOnly) return c->fail(FYPRT_ESTATE, std::string(who) + ": host-only context (device -1) cannot query");
-    if (!c->haveScene) return c->fail(FYPRT_ESTATE, std::string(who) + " before fyprt_upload_scene");
-    return FYPRT_OK;
-}
-// (device memory, count > 0, after / counts / totals may be NULL)
-static int enqueue_overlap_boxes(fyprt_context* c, const float4* boxes, const uint32_t* after, uint32_t count, uint32_t maxHits, uint32_t* triangles, uint32_t* counts,
-                                 uint32_t* totals, bool timed) {
-    static const QueryKernels<QueryBoxes> kBoxes = {{{k_query_boxes<false>, k_query_boxes<true>}, {k_query_boxes_simple<false>, k_query_boxes_simple<true>}},
-                                                    {{k_query_boxes_filtered<false>, k_query_boxes_filtered<true>}, {k_query_boxes_simple_filtered<false>, k_query_boxes_simple_filtered<true>}}};
-    fyprt_context::QueryFamily& f = c->boxesQuery;
-    QueryBoxes q{};
-    q.boxes = boxes; q.after = after; q.triangles = triangles; q.counts = counts; q.totals = totals; q.count = count; q.maxHits = maxHits;
-    // as the list queries: key 2 no higher than the occupancy, 2 workgroups per CU without one
-    return launch_query(c, f, 0, q, kBoxes, (size_t)maxHits * 4u, true, 2, timed);
-}
-
+// ---- box-overlap queries (rt_boxes.h): the list query whose entries are bare triangle indices, with a total beside the count
 int fyprt_overlap_boxes(fyprt_context* c, const fyprt_box* boxes, const uint32_t* after, uint32_t count, uint32_t max_hits, uint32_t* triangles,
                         uint32_t* hit_counts, uint32_t* totals, fyprt_frame_stats* stats) {
-    TRY(check_overlap_boxes(c, "fyprt_overlap_boxes", boxes, after, count, max_hits, triangles, hit_counts, totals, false));
-    HostQuery h{boxes, 2, after, triangles, (size_t)count * max_hits * 4u, hit_counts, true};
-    h.afterBytes = 4u; h.tail = totals; h.tailBytes = (size_t)count * 4u;
-    return run_host_query(c, c->boxesQuery, h, count, stats, [&](const float4* dIn, const float4* dAfter, uint32_t* dOut, uint32_t* dCounts) {
-        return enqueue_overlap_boxes(c, dIn, reinterpret_cast<const uint32_t*>(dAfter), count, max_hits, dOut, dCounts, dOut + (size_t)count * max_hits, true); });
+    TRY(check_list_query(c, kOverlapBoxes, "fyprt_overlap_boxes", boxes, after, count, max_hits, triangles, hit_counts, totals, false));
+    return host_list_query(c, kOverlapBoxes, boxes, after, count, max_hits, triangles, hit_counts, totals, stats);
 }
 int fyprt_overlap_boxes_device(fyprt_context* c, const void* boxes, const void* after, uint32_t count, uint32_t max_hits, void* triangles, void* hit_counts,
                                void* totals) {
-    TRY(check_overlap_boxes(c, "fyprt_overlap_boxes_device", boxes, after, count, max_hits, triangles, hit_counts, totals, true));
-    if (count == 0) return FYPRT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    return enqueue_overlap_boxes(c, static_cast<const float4*>(boxes), static_cast<const uint32_t*>(after), count, max_hits, static_cast<uint32_t*>(triangles),
-                                 static_cast<uint32_t*>(hit_counts), static_cast<uint32_t*>(totals), false);
+    TRY(check_list_query(c, kOverlapBoxes, "fyprt_overlap_boxes_device", boxes, after, count, max_hits, triangles, hit_counts, totals, true));
+    return device_list_query(c, kOverlapBoxes, boxes, after, count, max_hits, triangles, hit_counts, totals);
 }
 
 // ---- radiance queries (rt_query.h: k_render_rays_primary; rt_paths.h: the path stages with CAM = RaySource).  A frame's sample of

@@ -8,16 +8,16 @@
 // every comparison written positively so that a NaN rejects.  With `after` the index must also be greater than after[i].  The answer
 // is the maxHits smallest accepted indices: a function of the leaf records alone.
 //
-// The traversal (box_node_step, a sibling of point_node_step: neither that one nor node_step is touched) has no order network: every
+// The traversal (box_node_step, on point_node_step's node fetch, rt_points.h; node_step is not touched) has no order network: every
 // surviving child is visited, in slot order.  A child is skipped iff on some axis planeLo - s > hi or planeHi + s < lo with
 // s = k * max(|planeLo|, |planeHi|), k = 2^-20 (kPointSlack).  The slack is needed because the decoded planes bound the TRUE vertices
 // while box_tri's first step tests the ROUNDED v0 + e1, which lies up to 3 * 2^-24 * max(|V0|, |V1|) outside them (DESIGN.md §4,
 // "Box-overlap queries"); it changes only cost, never an answer.  A child box wholly inside the query box is still descended and its
 // records tested one by one: the contract is the rounded rule on every record.
 //
-// Two kernels by tuning key 15, as the other queries: k_query_boxes (persistent waves: query_body of rt_query.h with BoxLane, keys 4, 5,
-// 6, 9, 10) and k_query_boxes_simple (one thread per box: query_simple_body).  The per-lane list is one LDS plane of uint32 behind the
-// stack, lane-strided like it, kept sorted ascending; its length and its worst entry live in registers.
+// Two forms by tuning key 15, as the other queries: persistent waves (query_body of rt_query.h with BoxLaneT, keys 4, 5, 6, 9, 10) and
+// one thread per box (query_simple_body), behind rt_query.h's kernel templates.  The per-lane list is one LDS plane of uint32 behind
+// the stack, lane-strided like it, kept sorted ascending; its length and its worst entry live in registers.
 #pragma once
 #include "rt_points.h"
 
@@ -80,37 +80,24 @@ RT_DEV bool box_axis_apart(float pl, float ph, float lo, float hi) {
     return (pl - s > hi) || (ph + s < lo);
 }
 // Whether child i of a node is skipped; the planes are decoded as point_child_key decodes them (q * step exact, then one add)
-RT_DEV bool box_child_apart(uint32_t i, f3 lo, f3 hi, f3 org, f3 step, uint32_t lx, uint32_t ly, uint32_t lz, uint32_t hx, uint32_t hy, uint32_t hz) {
-    return box_axis_apart(ubyte_f(lx, i) * step.x + org.x, ubyte_f(hx, i) * step.x + org.x, lo.x, hi.x) ||
-           box_axis_apart(ubyte_f(ly, i) * step.y + org.y, ubyte_f(hy, i) * step.y + org.y, lo.y, hi.y) ||
-           box_axis_apart(ubyte_f(lz, i) * step.z + org.z, ubyte_f(hz, i) * step.z + org.z, lo.z, hi.z);
+RT_DEV bool box_child_apart(uint32_t i, f3 lo, f3 hi, const NodeBoxes& nd) {
+    return box_axis_apart(ubyte_f(nd.lx, i) * nd.step.x + nd.org.x, ubyte_f(nd.hx, i) * nd.step.x + nd.org.x, lo.x, hi.x) ||
+           box_axis_apart(ubyte_f(nd.ly, i) * nd.step.y + nd.org.y, ubyte_f(nd.hy, i) * nd.step.y + nd.org.y, lo.y, hi.y) ||
+           box_axis_apart(ubyte_f(nd.lz, i) * nd.step.z + nd.org.z, ubyte_f(nd.hz, i) * nd.step.z + nd.org.z, lo.z, hi.z);
 }
 
-// One visit of a 4-wide node for a box: point_node_step's fetch, child-count mask, stack rule and resume entries around the overlap
+// One visit of a 4-wide node for a box: point_node_step's fetch (fetch_node_boxes), stack rule and resume entries around the overlap
 // test, without the order network — the surviving child in the lowest slot is visited next, the others are pushed.
 // A resume entry carries the slots still owed; the slot descended into is taken out of it before it is pushed, and a resumed visit looks
 // at the owed slots only.  So every child of a node is entered at most once however often the node is fetched, every leaf is reached
 // once, and a record is tested once: the lane's total needs no memory of what it has counted.
 template <bool COUNT>
 RT_DEV int32_t box_node_step(const float4* nodes, int32_t budget, int32_t cur, f3 lo, f3 hi, Stack& st, uint32_t& nBox, uint32_t& nNode) {
-    const bool anyResumed = __ballot(cur >= kResumeBase) != 0ull;
-    const uint32_t off = (uint32_t)cur & kNodeOffsetMask;
-    uint32_t allow = 0xFu;
-    if (anyResumed) allow = (cur >= kResumeBase) ? ((uint32_t)cur & 0xFu) : 0xFu;
-    const float4* n = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(nodes) + off);     // uniform base + 32-bit lane offset
-    const float4 q0 = n[0], q1 = n[1], q2 = n[2]; const float2 q3 = *reinterpret_cast<const float2*>(n + 3);
-    const uint32_t ex = (uint32_t)__float_as_int(q0.w), cnt = (ex >> 24) & 7u, levels = ex >> 27;
-    allow &= (1u << cnt) - 1u;                                        // unused slots (qlo 255 / qhi 0) are a box like any other to this test
-    if (COUNT) { nBox += (uint32_t)__popc(allow); nNode += 1u; }
-    const f3 org = mk3(q0.x, q0.y, q0.z);
-    const f3 step = mk3(__int_as_float((int)((ex & 0xFFu) << 23)), __int_as_float((int)(((ex >> 8) & 0xFFu) << 23)), __int_as_float((int)(((ex >> 16) & 0xFFu) << 23)));
-    const uint32_t lx = (uint32_t)__float_as_int(q2.x), ly = (uint32_t)__float_as_int(q2.y), lz = (uint32_t)__float_as_int(q2.z),
-                   hx = (uint32_t)__float_as_int(q2.w), hy = (uint32_t)__float_as_int(q3.x), hz = (uint32_t)__float_as_int(q3.y);
-    const uint32_t hit = allow & ((box_child_apart(0, lo, hi, org, step, lx, ly, lz, hx, hy, hz) ? 0u : 1u) |
-                                  (box_child_apart(1, lo, hi, org, step, lx, ly, lz, hx, hy, hz) ? 0u : 2u) |
-                                  (box_child_apart(2, lo, hi, org, step, lx, ly, lz, hx, hy, hz) ? 0u : 4u) |
-                                  (box_child_apart(3, lo, hi, org, step, lx, ly, lz, hx, hy, hz) ? 0u : 8u));
-    const int32_t c0 = __float_as_int(q1.x), c1 = __float_as_int(q1.y), c2 = __float_as_int(q1.z), c3 = __float_as_int(q1.w);
+    const NodeBoxes nd = fetch_node_boxes<COUNT>(nodes, cur, nBox, nNode);
+    const uint32_t off = nd.off, allow = nd.allow, levels = nd.levels;
+    const uint32_t hit = allow & ((box_child_apart(0, lo, hi, nd) ? 0u : 1u) | (box_child_apart(1, lo, hi, nd) ? 0u : 2u) |
+                                  (box_child_apart(2, lo, hi, nd) ? 0u : 4u) | (box_child_apart(3, lo, hi, nd) ? 0u : 8u));
+    const int32_t c0 = nd.c0, c1 = nd.c1, c2 = nd.c2, c3 = nd.c3;
     const uint32_t first = hit & (0u - hit), rest = hit & ~first;     // the lowest surviving slot; slot 0 is never in `rest`
     const int32_t next = (first & 1u) ? c0 : (first & 2u) ? c1 : (first & 4u) ? c2 : c3;
     // node_step's stack rule: pushes while pending + 2 + levels <= budget (room for three entries), one resume entry otherwise
@@ -145,6 +132,9 @@ RT_DEV void tri_insert(uint32_t* l, uint32_t maxHits, uint32_t& n, uint32_t& wor
 // RayLane's; the total then counts admitted triangles only.
 template <bool FILTER> struct BoxLaneT : LaneFilter<FILTER> {
     using Query = typename std::conditional<FILTER, Filtered<QueryBoxes>, QueryBoxes>::type;
+    // 5 waves per SIMD (87 VGPRs, no scratch), as the other list queries: held to 6 (80 VGPRs) the kernel spills five registers to 16 B of
+    // scratch, and the LDS holds a sixth workgroup per CU only while stack and list together stay within 26 entries (1 KB each)
+    static constexpr int kWaves = 5;
     uint32_t* const list;                       // &plane[threadIdx.x]; entry s at [s * kBlock]
     f3 lo = splat3(0.0f), hi = splat3(0.0f);
     uint32_t n = 0, worst = kNoTriangle, low = 0, total = 0;
@@ -184,39 +174,5 @@ template <bool FILTER> struct BoxLaneT : LaneFilter<FILTER> {
         return n != 0u;
     }
 };
-using BoxLane = BoxLaneT<false>;
-
-template <bool COUNT> __global__ void k_query_boxes(DevScene sc, QueryBoxes q);
-// 5 waves per SIMD (87 VGPRs, no scratch), as the other list queries: held to 6 (80 VGPRs) the kernel spills five registers to 16 B of
-// scratch, and the LDS holds a sixth workgroup per CU only while stack and list together stay within 26 entries (1 KB each)
-template <> __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5))) void k_query_boxes<false>(DevScene sc, QueryBoxes q) {
-    extern __shared__ int32_t s_stack[];                         // (stackBudget + 1) x 4 B + maxHits x 4 B per thread, sized at launch
-    query_body<BoxLane, false>(sc, q, s_stack);
-}
-template <> __global__ __launch_bounds__(kBlock) void k_query_boxes<true>(DevScene sc, QueryBoxes q) {        // instrumented: no register cap
-    extern __shared__ int32_t s_stack[];
-    query_body<BoxLane, true>(sc, q, s_stack);
-}
-
-template <bool COUNT>
-__global__ __launch_bounds__(kBlock) void k_query_boxes_simple(DevScene sc, QueryBoxes q) {
-    extern __shared__ int32_t s_stack[];                         // (stackBudget + 1) x 4 B + maxHits x 4 B per thread, sized at launch
-    query_simple_body<BoxLane, COUNT>(sc, q, s_stack);
-}
-// ... and their filtered forms (BoxLaneT<true>)
-template <bool COUNT> __global__ void k_query_boxes_filtered(DevScene sc, Filtered<QueryBoxes> q);
-template <> __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5))) void k_query_boxes_filtered<false>(DevScene sc, Filtered<QueryBoxes> q) {
-    extern __shared__ int32_t s_stack[];
-    query_body<BoxLaneT<true>, false>(sc, q, s_stack);
-}
-template <> __global__ __launch_bounds__(kBlock) void k_query_boxes_filtered<true>(DevScene sc, Filtered<QueryBoxes> q) {        // instrumented: no register cap
-    extern __shared__ int32_t s_stack[];
-    query_body<BoxLaneT<true>, true>(sc, q, s_stack);
-}
-template <bool COUNT>
-__global__ __launch_bounds__(kBlock) void k_query_boxes_simple_filtered(DevScene sc, Filtered<QueryBoxes> q) {
-    extern __shared__ int32_t s_stack[];
-    query_simple_body<BoxLaneT<true>, COUNT>(sc, q, s_stack);
-}
 
 }  // namespace rt

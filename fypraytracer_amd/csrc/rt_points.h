@@ -18,8 +18,8 @@
 // bound being r2 until the list is full and the worst entry's distance2 from then on: a child at exactly the bound is still visited,
 // a tie with a lower triangle index displaces the worst entry.
 //
-// Two kernels by tuning key 15, as the other queries: k_query_points (persistent waves: query_body of rt_query.h with PointsLane, keys 4,
-// 5, 6, 9, 10) and k_query_points_simple (one thread per point: query_simple_body).  The per-lane list is the multi-hit query's:
+// Two forms by tuning key 15, as the other queries: persistent waves (query_body of rt_query.h with PointsLaneT, keys 4, 5, 6, 9, 10) and
+// one thread per point (query_simple_body), behind rt_query.h's kernel templates.  The per-lane list is the multi-hit query's:
 // HitList, hit_insert and store_hits, in LDS behind the stack, 16 B per entry; the query record is QueryHits with one float4 per point.
 #pragma once
 #include "rt_query.h"
@@ -85,6 +85,36 @@ RT_DEV void point_tri(const float4* tp, f3 p, float& dist2, float& u, float& v, 
     dist2 = dot(diff, diff);
 }
 
+// A node of the 4-wide tree as the point and box walks see it: fetched whole (64 bytes) and decoded, no test made yet.  `allow`: the
+// slots to look at — those of a resume entry, or all four, masked by the node's child count: unused slots (planes qlo 255 / qhi 0) are a
+// box like any other to a distance or overlap test.  `levels`: the height the stack rule needs; the planes stay packed, one word per
+// axis and side, and are decoded per child as the builders verify them (org + q * step).  Counts the visit and its box tests under COUNT.
+struct NodeBoxes {
+    uint32_t off, allow, levels; f3 org, step;
+    uint32_t lx, ly, lz, hx, hy, hz;
+    int32_t c0, c1, c2, c3;
+};
+template <bool COUNT>
+RT_DEV NodeBoxes fetch_node_boxes(const float4* nodes, int32_t cur, uint32_t& nBox, uint32_t& nNode) {
+    NodeBoxes nd;
+    const bool anyResumed = __ballot(cur >= kResumeBase) != 0ull;
+    nd.off = (uint32_t)cur & kNodeOffsetMask;
+    nd.allow = 0xFu;
+    if (anyResumed) nd.allow = (cur >= kResumeBase) ? ((uint32_t)cur & 0xFu) : 0xFu;
+    const float4* n = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(nodes) + nd.off);     // uniform base + 32-bit lane offset
+    const float4 q0 = n[0], q1 = n[1], q2 = n[2]; const float2 q3 = *reinterpret_cast<const float2*>(n + 3);
+    const uint32_t ex = (uint32_t)__float_as_int(q0.w), cnt = (ex >> 24) & 7u;
+    nd.levels = ex >> 27;
+    nd.allow &= (1u << cnt) - 1u;
+    if (COUNT) { nBox += (uint32_t)__popc(nd.allow); nNode += 1u; }
+    nd.org = mk3(q0.x, q0.y, q0.z);
+    nd.step = mk3(__int_as_float((int)((ex & 0xFFu) << 23)), __int_as_float((int)(((ex >> 8) & 0xFFu) << 23)), __int_as_float((int)(((ex >> 16) & 0xFFu) << 23)));
+    nd.lx = (uint32_t)__float_as_int(q2.x); nd.ly = (uint32_t)__float_as_int(q2.y); nd.lz = (uint32_t)__float_as_int(q2.z);
+    nd.hx = (uint32_t)__float_as_int(q2.w); nd.hy = (uint32_t)__float_as_int(q3.x); nd.hz = (uint32_t)__float_as_int(q3.y);
+    nd.c0 = __float_as_int(q1.x); nd.c1 = __float_as_int(q1.y); nd.c2 = __float_as_int(q1.z); nd.c3 = __float_as_int(q1.w);
+    return nd;
+}
+
 // One axis of a child's lower bound: the gap of p to [lo, hi], shrunk by k * max(|p|, |lo|, |hi|)
 RT_DEV float point_gap(float p, float lo, float hi) {
     const float g = __builtin_fmaxf(__builtin_fmaxf(lo - p, p - hi), 0.0f);
@@ -94,41 +124,26 @@ RT_DEV float point_gap(float p, float lo, float hi) {
 // Child i's planes decoded as the builders verify them (Collapser::quantise, refit_node: fma(q, step, origin) with q * step exact, so the
 // product and one add), its lower bound lb2, and the high word of its sort key: the bits of max(lb2, kNearClamp) if the child survives
 // the cull, the miss word otherwise.  Only the sort key is clamped, never the cull.
-RT_DEV uint32_t point_child_key(uint32_t i, f3 p, f3 org, f3 step, uint32_t lx, uint32_t ly, uint32_t lz, uint32_t hx, uint32_t hy, uint32_t hz,
-                                float bound, uint32_t missHi) {
-    const float gx = point_gap(p.x, ubyte_f(lx, i) * step.x + org.x, ubyte_f(hx, i) * step.x + org.x);
-    const float gy = point_gap(p.y, ubyte_f(ly, i) * step.y + org.y, ubyte_f(hy, i) * step.y + org.y);
-    const float gz = point_gap(p.z, ubyte_f(lz, i) * step.z + org.z, ubyte_f(hz, i) * step.z + org.z);
+RT_DEV uint32_t point_child_key(uint32_t i, f3 p, const NodeBoxes& nd, float bound, uint32_t missHi) {
+    const float gx = point_gap(p.x, ubyte_f(nd.lx, i) * nd.step.x + nd.org.x, ubyte_f(nd.hx, i) * nd.step.x + nd.org.x);
+    const float gy = point_gap(p.y, ubyte_f(nd.ly, i) * nd.step.y + nd.org.y, ubyte_f(nd.hy, i) * nd.step.y + nd.org.y);
+    const float gz = point_gap(p.z, ubyte_f(nd.lz, i) * nd.step.z + nd.org.z, ubyte_f(nd.hz, i) * nd.step.z + nd.org.z);
     const float lb2 = (gx * gx + gy * gy) + gz * gz;
     return (lb2 * kPointKeep > bound) ? missHi : __float_as_uint(__builtin_fmaxf(lb2, kNearClamp));
 }
 
-// One visit of a 4-wide node for a point: node_step's fetch, order network, stack rule and resume entries around the box-distance test.
-// Unused slots are masked by the node's child count (their planes, qlo 255 / qhi 0, are a box like any other to a distance test).
+// One visit of a 4-wide node for a point: node_step's order network, stack rule and resume entries around the box-distance test.
 template <bool COUNT>
 RT_DEV int32_t point_node_step(const float4* nodes, int32_t budget, int32_t cur, f3 p, float bound, Stack& st, uint32_t& nBox, uint32_t& nNode) {
-    const bool anyResumed = __ballot(cur >= kResumeBase) != 0ull;
-    const uint32_t off = (uint32_t)cur & kNodeOffsetMask;
-    uint32_t allow = 0xFu;
-    if (anyResumed) allow = (cur >= kResumeBase) ? ((uint32_t)cur & 0xFu) : 0xFu;
-    const float4* n = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(nodes) + off);     // uniform base + 32-bit lane offset
-    const float4 q0 = n[0], q1 = n[1], q2 = n[2]; const float2 q3 = *reinterpret_cast<const float2*>(n + 3);
-    const uint32_t ex = (uint32_t)__float_as_int(q0.w), cnt = (ex >> 24) & 7u, levels = ex >> 27;
-    allow &= (1u << cnt) - 1u;
-    if (COUNT) { nBox += (uint32_t)__popc(allow); nNode += 1u; }
-    const f3 org = mk3(q0.x, q0.y, q0.z);
-    const f3 step = mk3(__int_as_float((int)((ex & 0xFFu) << 23)), __int_as_float((int)(((ex >> 8) & 0xFFu) << 23)), __int_as_float((int)(((ex >> 16) & 0xFFu) << 23)));
-    const uint32_t lx = (uint32_t)__float_as_int(q2.x), ly = (uint32_t)__float_as_int(q2.y), lz = (uint32_t)__float_as_int(q2.z),
-                   hx = (uint32_t)__float_as_int(q2.w), hy = (uint32_t)__float_as_int(q3.x), hz = (uint32_t)__float_as_int(q3.y);
+    const NodeBoxes nd = fetch_node_boxes<COUNT>(nodes, cur, nBox, nNode);
+    const uint32_t off = nd.off, allow = nd.allow, levels = nd.levels;
     // the four (lower bound, child reference) pairs as 64-bit keys, ordered with v_min_f64 / v_max_f64 as node_step orders its entry
     // distances: the high word is >= 1e-30 (the clamp) and finite (an infinite lb2 exceeds every bound), a positive normal double
     constexpr uint32_t kMissHi = 0x7F900000u;
-    uint32_t h0 = point_child_key(0, p, org, step, lx, ly, lz, hx, hy, hz, bound, kMissHi);
-    uint32_t h1 = point_child_key(1, p, org, step, lx, ly, lz, hx, hy, hz, bound, kMissHi);
-    uint32_t h2 = point_child_key(2, p, org, step, lx, ly, lz, hx, hy, hz, bound, kMissHi);
-    uint32_t h3 = point_child_key(3, p, org, step, lx, ly, lz, hx, hy, hz, bound, kMissHi);
+    uint32_t h0 = point_child_key(0, p, nd, bound, kMissHi), h1 = point_child_key(1, p, nd, bound, kMissHi);
+    uint32_t h2 = point_child_key(2, p, nd, bound, kMissHi), h3 = point_child_key(3, p, nd, bound, kMissHi);
     h0 = (allow & 1u) ? h0 : kMissHi; h1 = (allow & 2u) ? h1 : kMissHi; h2 = (allow & 4u) ? h2 : kMissHi; h3 = (allow & 8u) ? h3 : kMissHi;
-    const int32_t c0 = __float_as_int(q1.x), c1 = __float_as_int(q1.y), c2 = __float_as_int(q1.z), c3 = __float_as_int(q1.w);
+    const int32_t c0 = nd.c0, c1 = nd.c1, c2 = nd.c2, c3 = nd.c3;
     double d0 = __hiloint2double((int)h0, c0), d1 = __hiloint2double((int)h1, c1), d2 = __hiloint2double((int)h2, c2), d3 = __hiloint2double((int)h3, c3);
     order_keys(d0, d1); order_keys(d2, d3); order_keys(d0, d2); order_keys(d1, d3); order_keys(d1, d2);
     const uint32_t s0h = (uint32_t)__double2hiint(d0), s1h = (uint32_t)__double2hiint(d1), s2h = (uint32_t)__double2hiint(d2), s3h = (uint32_t)__double2hiint(d3);
@@ -168,10 +183,11 @@ RT_DEV float points_leaf(const DevScene& sc, const HitList& l, uint32_t maxHits,
     return bound;
 }
 
-// The point lane state: HitsLane with a point in place of the ray, the squared radius in place of the interval.  FILTER as RayLane's:
+// The point lane state: HitsLaneT with a point in place of the ray, the squared radius in place of the interval.  FILTER as RayLane's:
 // a masked sub-tree is never entered, so near an excluded mesh the list still fills from the admitted ones and the cull bound shrinks.
 template <bool FILTER> struct PointsLaneT : LaneFilter<FILTER> {
     using Query = typename std::conditional<FILTER, Filtered<QueryPoints>, QueryPoints>::type;
+    static constexpr int kWaves = 5;            // as HitsLaneT: the list's LDS leaves room for no more workgroups from a 26-entry stack on
     const HitList list;
     f3 p = splat3(0.0f);
     float r2 = 0.0f, bound = 0.0f; uint32_t n = 0;
@@ -196,38 +212,5 @@ template <bool FILTER> struct PointsLaneT : LaneFilter<FILTER> {
     }
     RT_DEV bool finish(const DevScene&, const Query& q, uint32_t i) { store_hits(q, list, i, n); return n != 0u; }
 };
-using PointsLane = PointsLaneT<false>;
-
-template <bool COUNT> __global__ void k_query_points(DevScene sc, QueryPoints q);
-// 5 waves per SIMD as k_query_hits<false>: the list's LDS leaves room for no more workgroups from a 26-entry stack on
-template <> __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5))) void k_query_points<false>(DevScene sc, QueryPoints q) {
-    extern __shared__ int32_t s_stack[];                         // (stackBudget + 1) x 4 B + maxHits x 16 B per thread, sized at launch
-    query_body<PointsLane, false>(sc, q, s_stack);
-}
-template <> __global__ __launch_bounds__(kBlock) void k_query_points<true>(DevScene sc, QueryPoints q) {      // instrumented: no register cap
-    extern __shared__ int32_t s_stack[];
-    query_body<PointsLane, true>(sc, q, s_stack);
-}
-
-template <bool COUNT>
-__global__ __launch_bounds__(kBlock) void k_query_points_simple(DevScene sc, QueryPoints q) {
-    extern __shared__ int32_t s_stack[];                         // (stackBudget + 1) x 4 B + maxHits x 16 B per thread, sized at launch
-    query_simple_body<PointsLane, COUNT>(sc, q, s_stack);
-}
-// ... and their filtered forms (PointsLaneT<true>)
-template <bool COUNT> __global__ void k_query_points_filtered(DevScene sc, Filtered<QueryPoints> q);
-template <> __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5))) void k_query_points_filtered<false>(DevScene sc, Filtered<QueryPoints> q) {
-    extern __shared__ int32_t s_stack[];
-    query_body<PointsLaneT<true>, false>(sc, q, s_stack);
-}
-template <> __global__ __launch_bounds__(kBlock) void k_query_points_filtered<true>(DevScene sc, Filtered<QueryPoints> q) {      // instrumented: no register cap
-    extern __shared__ int32_t s_stack[];
-    query_body<PointsLaneT<true>, true>(sc, q, s_stack);
-}
-template <bool COUNT>
-__global__ __launch_bounds__(kBlock) void k_query_points_simple_filtered(DevScene sc, Filtered<QueryPoints> q) {
-    extern __shared__ int32_t s_stack[];
-    query_simple_body<PointsLaneT<true>, COUNT>(sc, q, s_stack);
-}
 
 }  // namespace rt

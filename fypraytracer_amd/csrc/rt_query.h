@@ -10,16 +10,17 @@
 // A ray with a non-finite origin / direction component, a NaN bound or !(tmin < tmax) is answered as a miss (0) without traversal
 // and counted as a ray with no tests.
 //
-// Two kernels, chosen by the host like the path engine's ray kernels (tuning key 15):
-//   k_query_rays         persistent waves, one in-flight ray per lane, idle lanes refilled from the wave's claimed chunk (the
-//                        guided self-scheduling of trace_rays_body, tuning keys 4, 5, 9, 10); a refill is two 16-byte loads and
-//                        three reciprocals, a finished closest-hit ray one triShade gather (make_hit) and a 40-byte store.
-//   k_query_rays_simple  one thread per ray, for small trees where rays are too cheap for the refill machinery to pay.
-// The query kind is a template parameter: neither kernel carries the other kind's branches.  They only call the traversal core of
+// Two forms, chosen by the host like the path engine's ray kernels (tuning key 15):
+//   persistent      waves that stay, one in-flight ray per lane, idle lanes refilled from the wave's claimed chunk (the guided
+//                   self-scheduling of trace_rays_body, tuning keys 4, 5, 9, 10); a refill is two 16-byte loads and three
+//                   reciprocals, a finished closest-hit ray one triShade gather (make_hit) and a 40-byte store.
+//   one thread      per ray, for small trees where rays are too cheap for the refill machinery to pay.
+// The query kind is a template parameter: neither form carries the other kind's branches.  They only call the traversal core of
 // rt_device.h (node_step, tri_test, make_hit / make_miss, quorum_of, ray_not_finite); no frame kernel is touched.
-// The multi-hit query (fyprt_trace_ray_hits*: the K nearest hits per ray in order) has the same two forms, k_query_hits and
-// k_query_hits_simple, further down, and the nearest-point query (rt_points.h) has them too: all of them are query_body /
-// query_simple_body, written once below, around a per-query lane state.
+// The multi-hit query (fyprt_trace_ray_hits*: the K nearest hits per ray in order) further down, the nearest-point query (rt_points.h)
+// and the box-overlap query (rt_boxes.h) have the same two forms: all of them are query_body / query_simple_body, written once below,
+// around a per-query lane state L, and every query kernel is one of the three entry points k_query<L>, k_query_counted<L> and
+// k_query_simple<L, COUNT> behind them.
 #pragma once
 #include "rt_paths.h"
 #include "rt_filter.h"
@@ -57,13 +58,15 @@ RT_DEV void count_query_ray(const DevScene& sc, uint32_t nBox, uint32_t nTri, ui
 }
 
 // ---- the scheduling every query family shares.  A lane state L carries the one record a lane has in flight:
+//   L::Query, L::kWaves                        the launch's record type; the waves per SIMD the uncounted persistent kernel is held to
 //   L(sc, q, s_stack)                          what a thread keeps for the whole launch (the list queries' LDS planes)
 //   start(sc, q, i)                            loads record i and initialises; sc.rootRef, or kExit for a record answered without traversal
 //   visit<COUNT>(sc, cur, st, nBox, nNode)     one node visit (node_step / point_node_step)
 //   leaf<COUNT>(sc, q, cur, nTri)              one leaf's triangles against the state; true when the record is finished by it
 //   finish(sc, q, i)                           stores the answer; whether it counts as a hit
-// Three of them: RayLane<OCCLUDED> here, HitsLane further down, PointsLane in rt_points.h.  The compiler replaces a lane state by its
-// scalars (tools/kernel_resources.py shows the registers of the hand-written bodies these replaced, profiles/query/).
+// Four of them, each plain and filtered: RayLane<OCCLUDED, FILTER> here, HitsLaneT<FILTER> further down, PointsLaneT in rt_points.h,
+// BoxLaneT in rt_boxes.h.  The compiler replaces a lane state by its scalars (tools/kernel_resources.py shows the registers of the
+// hand-written bodies these replaced, profiles/query/).
 
 // Persistent waves: one in-flight record per lane, idle lanes refilled from the wave's claimed chunk.
 template <class L, bool COUNT>
@@ -155,10 +158,26 @@ RT_DEV void query_simple_body(const DevScene& sc, const typename L::Query& q, in
     }
 }
 
+// The kernels of every query family, by lane state.  s_stack: (stackBudget + 1) entries x kBlock threads and behind them the lane state's
+// list planes (maxHits x 16 B or 4 B per thread), sized at launch.
+template <class L> __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(L::kWaves))) void k_query(DevScene sc, typename L::Query q) {
+    extern __shared__ int32_t s_stack[];
+    query_body<L, false>(sc, q, s_stack);
+}
+template <class L> __global__ __launch_bounds__(kBlock) void k_query_counted(DevScene sc, typename L::Query q) {   // instrumented: no register cap
+    extern __shared__ int32_t s_stack[];
+    query_body<L, true>(sc, q, s_stack);
+}
+template <class L, bool COUNT> __global__ __launch_bounds__(kBlock) void k_query_simple(DevScene sc, typename L::Query q) {
+    extern __shared__ int32_t s_stack[];
+    query_simple_body<L, COUNT>(sc, q, s_stack);
+}
+
 // The closest-hit / occlusion lane state.  FILTER: the query filter's visit rule (rt_filter.h) around the same walk; the record is then
 // Filtered<QueryRays>.  Without it the base is empty and the lane is the code it was.
 template <bool OCCLUDED, bool FILTER = false> struct RayLane : LaneFilter<FILTER> {
     using Query = typename std::conditional<FILTER, Filtered<QueryRays>, QueryRays>::type;
+    static constexpr int kWaves = RT_TRACE_WAVES_N;               // the register budget of the frames' persistent trace kernels (rt_wavefront.h)
     // (the origin lives in pk only: a separate copy of it costs three registers across the loop, and the closest-hit kernel spills)
     f3 d = splat3(0.0f); RayPk pk = make_raypk(d, 1.0f, 1.0f, 1.0f);
     float tmin = 0.0f, best = 0.0f, cut = 0.0f, hu = 0.0f, hv = 0.0f; int32_t hitTri = -1;
@@ -197,51 +216,8 @@ template <bool OCCLUDED, bool FILTER = false> struct RayLane : LaneFilter<FILTER
     }
 };
 
-template <bool OCCLUDED, bool COUNT> __global__ void k_query_rays(DevScene sc, QueryRays q);
-template <> __global__ __launch_bounds__(kBlock) RT_TRACE_WAVES void k_query_rays<false, false>(DevScene sc, QueryRays q) {
-    extern __shared__ int32_t s_stack[];                         // (stackBudget + 1) entries x kBlock threads, sized at launch
-    query_body<RayLane<false>, false>(sc, q, s_stack);
-}
-template <> __global__ __launch_bounds__(kBlock) RT_TRACE_WAVES void k_query_rays<true, false>(DevScene sc, QueryRays q) {
-    extern __shared__ int32_t s_stack[];
-    query_body<RayLane<true>, false>(sc, q, s_stack);
-}
-template <> __global__ __launch_bounds__(kBlock) void k_query_rays<false, true>(DevScene sc, QueryRays q) {   // instrumented: no register cap
-    extern __shared__ int32_t s_stack[];
-    query_body<RayLane<false>, true>(sc, q, s_stack);
-}
-template <> __global__ __launch_bounds__(kBlock) void k_query_rays<true, true>(DevScene sc, QueryRays q) {
-    extern __shared__ int32_t s_stack[];
-    query_body<RayLane<true>, true>(sc, q, s_stack);
-}
-template <bool OCCLUDED, bool COUNT>
-__global__ __launch_bounds__(kBlock) void k_query_rays_simple(DevScene sc, QueryRays q) {
-    extern __shared__ int32_t s_stack[];                         // (stackBudget + 1) entries x kBlock threads, sized at launch
-    query_simple_body<RayLane<OCCLUDED>, COUNT>(sc, q, s_stack);
-}
-// ... and their filtered forms (RayLane<OCCLUDED, true>), launched iff a mesh mask table is set
-template <bool OCCLUDED, bool COUNT> __global__ void k_query_rays_filtered(DevScene sc, Filtered<QueryRays> q);
-template <> __global__ __launch_bounds__(kBlock) RT_TRACE_WAVES void k_query_rays_filtered<false, false>(DevScene sc, Filtered<QueryRays> q) {
-    extern __shared__ int32_t s_stack[];
-    query_body<RayLane<false, true>, false>(sc, q, s_stack);
-}
-template <> __global__ __launch_bounds__(kBlock) RT_TRACE_WAVES void k_query_rays_filtered<true, false>(DevScene sc, Filtered<QueryRays> q) {
-    extern __shared__ int32_t s_stack[];
-    query_body<RayLane<true, true>, false>(sc, q, s_stack);
-}
-template <> __global__ __launch_bounds__(kBlock) void k_query_rays_filtered<false, true>(DevScene sc, Filtered<QueryRays> q) {   // instrumented: no register cap
-    extern __shared__ int32_t s_stack[];
-    query_body<RayLane<false, true>, true>(sc, q, s_stack);
-}
-template <> __global__ __launch_bounds__(kBlock) void k_query_rays_filtered<true, true>(DevScene sc, Filtered<QueryRays> q) {
-    extern __shared__ int32_t s_stack[];
-    query_body<RayLane<true, true>, true>(sc, q, s_stack);
-}
-template <bool OCCLUDED, bool COUNT>
-__global__ __launch_bounds__(kBlock) void k_query_rays_simple_filtered(DevScene sc, Filtered<QueryRays> q) {
-    extern __shared__ int32_t s_stack[];
-    query_simple_body<RayLane<OCCLUDED, true>, COUNT>(sc, q, s_stack);
-}
+template <bool FILTER> using ClosestLane = RayLane<false, FILTER>;
+template <bool FILTER> using OccludedLane = RayLane<true, FILTER>;
 
 // ============================================================ multi-hit queries (fyprt_trace_ray_hits*): the K nearest hits per ray
 // Every accepted hit (the closest-hit query's acceptance rule) has the 64-bit key (bits(t) << 32) | triangle: t > 1e-4, so the bit
@@ -332,6 +308,10 @@ RT_DEV void store_hits(const QueryHits& q, const HitList& l, uint32_t i, uint32_
 // The multi-hit lane state: the ray, and the list's length, worst key and `after` key in registers.  FILTER as RayLane's.
 template <bool FILTER> struct HitsLaneT : LaneFilter<FILTER> {
     using Query = typename std::conditional<FILTER, Filtered<QueryHits>, QueryHits>::type;
+    // 5 waves per SIMD (96 VGPRs, 12 B of scratch as the closest-hit kernel), not the 6 of RT_TRACE_WAVES (80 VGPRs, 20 B: the list's
+    // length, its worst key and the `after` key are five more live registers): the list's LDS leaves room for no more than 5 workgroups
+    // per CU from a 26-entry stack on (26 x 4 + 16 B per thread = 30 KB), so the sixth wave would be bought for small trees only.
+    static constexpr int kWaves = 5;
     const HitList list;
     f3 d = splat3(0.0f); RayPk pk = make_raypk(d, 1.0f, 1.0f, 1.0f);
     float tmin = 0.0f, hi = 0.0f, cut = 0.0f; uint32_t n = 0;
@@ -358,41 +338,6 @@ template <bool FILTER> struct HitsLaneT : LaneFilter<FILTER> {
     }
     RT_DEV bool finish(const DevScene&, const Query& q, uint32_t i) { store_hits(q, list, i, n); return n != 0u; }
 };
-using HitsLane = HitsLaneT<false>;
-
-template <bool COUNT> __global__ void k_query_hits(DevScene sc, QueryHits q);
-// Compiled for 5 waves per SIMD (96 VGPRs, 12 B of scratch as k_query_rays<false, false>), not the 6 of RT_TRACE_WAVES (80 VGPRs, 20 B: the
-// list's length, its worst key and the `after` key are five more live registers): the list's LDS leaves room for no more than 5
-// workgroups per CU from a 26-entry stack on (26 x 4 + 16 B per thread = 30 KB), so the sixth wave would be bought for small trees only.
-template <> __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5))) void k_query_hits<false>(DevScene sc, QueryHits q) {
-    extern __shared__ int32_t s_stack[];                         // (stackBudget + 1) x 4 B + maxHits x 16 B per thread, sized at launch
-    query_body<HitsLane, false>(sc, q, s_stack);
-}
-template <> __global__ __launch_bounds__(kBlock) void k_query_hits<true>(DevScene sc, QueryHits q) {          // instrumented: no register cap
-    extern __shared__ int32_t s_stack[];
-    query_body<HitsLane, true>(sc, q, s_stack);
-}
-
-template <bool COUNT>
-__global__ __launch_bounds__(kBlock) void k_query_hits_simple(DevScene sc, QueryHits q) {
-    extern __shared__ int32_t s_stack[];                         // (stackBudget + 1) x 4 B + maxHits x 16 B per thread, sized at launch
-    query_simple_body<HitsLane, COUNT>(sc, q, s_stack);
-}
-// ... and their filtered forms (HitsLaneT<true>)
-template <bool COUNT> __global__ void k_query_hits_filtered(DevScene sc, Filtered<QueryHits> q);
-template <> __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(5))) void k_query_hits_filtered<false>(DevScene sc, Filtered<QueryHits> q) {
-    extern __shared__ int32_t s_stack[];
-    query_body<HitsLaneT<true>, false>(sc, q, s_stack);
-}
-template <> __global__ __launch_bounds__(kBlock) void k_query_hits_filtered<true>(DevScene sc, Filtered<QueryHits> q) {          // instrumented: no register cap
-    extern __shared__ int32_t s_stack[];
-    query_body<HitsLaneT<true>, true>(sc, q, s_stack);
-}
-template <bool COUNT>
-__global__ __launch_bounds__(kBlock) void k_query_hits_simple_filtered(DevScene sc, Filtered<QueryHits> q) {
-    extern __shared__ int32_t s_stack[];
-    query_simple_body<HitsLaneT<true>, COUNT>(sc, q, s_stack);
-}
 
 // ============================================================ radiance queries (fyprt_render_rays*): the primary pass
 // The primary segments are traced by the closest-hit kernels above into the query's own payload records (the frame's primary record

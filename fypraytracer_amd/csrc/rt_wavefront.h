@@ -314,9 +314,15 @@ RT_DEV int32_t lane_pop(int32_t* lds, int& top) { --top; return lds[top * kBlock
 // register budget of the persistent trace kernels: 6 waves per SIMD (80 VGPRs); left alone the compiler lands a few registers above that
 // boundary and loses a resident workgroup per CU.  (The ReSTIR DI kernel also fits 72 VGPRs = 7 waves without a spill, and the 22 KB LDS
 // stack of the bench tree lets a CU hold 7 workgroups — measured slower, 0.458 vs 0.438 ms: profiles/README.md r02.)
-#ifndef RT_TRACE_WAVES
-#define RT_TRACE_WAVES __attribute__((amdgpu_waves_per_eu(6)))
+// RT_TRACE_WAVES_N is the number (-DRT_TRACE_WAVES_N=7 moves these kernels and the ray queries of rt_query.h together), RT_TRACE_WAVES the
+// attribute made of it.
+#ifdef RT_TRACE_WAVES
+#error "override RT_TRACE_WAVES_N (a number of waves), not RT_TRACE_WAVES"
 #endif
+#ifndef RT_TRACE_WAVES_N
+#define RT_TRACE_WAVES_N 6
+#endif
+#define RT_TRACE_WAVES __attribute__((amdgpu_waves_per_eu(RT_TRACE_WAVES_N)))
 // The leaf phase of the production kernel (COUNT == false) runs at the wave's full width: the (lane, triangle) pairs of the lanes at a leaf are
 // spread over all 64 lanes.  The instrumented kernel keeps the serial loop, which is also what -DRT_DI_COOP_LEAF=0 builds
 // (tools/build_variant.sh).  No operation on a ray changes.

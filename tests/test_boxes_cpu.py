@@ -71,6 +71,33 @@ def test_errors_in_the_headers_order_on_a_host_only_context():
     ctx.close()
 
 
+def test_argument_error_texts_of_the_three_list_queries():
+    """The list queries share one argument check; every entry point keeps its own text, byte for byte (callers may match them)."""
+    lib = capi.load_library()
+    ctx = capi.Context(-1)
+    dev = np.zeros(64, dtype=np.float32)                      # (never dereferenced: every call below fails before a launch)
+    base = dev.ctypes.data + (-dev.ctypes.data) % 16
+    families = (("fyprt_trace_ray_hits", "rays", "hits", 8, "trace", "rays, after and hits must be 16-byte and hit_counts 4-byte aligned", ()),
+                ("fyprt_nearest_points", "points", "hits", 8, "query", "points, after and hits must be 16-byte and hit_counts 4-byte aligned", ()),
+                ("fyprt_overlap_boxes", "boxes", "triangles", 32, "query",
+                 "boxes must be 16-byte and after, triangles, hit_counts and totals 4-byte aligned", (base,)))
+
+    def text(rc, code):
+        assert rc == code
+        return lib.fyprt_last_error(ctx.h).decode()
+
+    for name, noun, out, cap, verb, aligned, totals in families:
+        host, device = getattr(lib, name), getattr(lib, name + "_device")
+        for who, call in ((name, lambda r=base, n=4, k=4, h=base, c=base: host(ctx.h, r, None, n, k, h, c, *totals, None)),
+                          (name + "_device", lambda r=base, n=4, k=4, h=base, c=base: device(ctx.h, r, None, n, k, h, c, *totals))):
+            assert text(call(k=0), EINVAL) == text(call(k=cap + 1), EINVAL) == f"{who}: max_hits must be 1..{cap}"
+            assert text(call(r=None), EINVAL) == text(call(h=None), EINVAL) == f"{who}: NULL {noun} / {out} with a non-zero count"
+            assert text(call(), ESTATE) == f"{who}: host-only context (device -1) cannot {verb}"      # (comes before the scene's state)
+        assert text(device(ctx.h, base + 4, None, 4, 4, base, base, *totals), EINVAL) == f"{name}_device: {aligned}"
+        assert text(device(ctx.h, base, None, 4, 4, base, base + 2, *totals), EINVAL) == f"{name}_device: {aligned}"
+    ctx.close()
+
+
 class _NoLibrary:
     """Stands in for the loaded library: any call into it is a failure of the wrapper's own checks."""
 

@@ -1,4 +1,4 @@
-"""Box-overlap queries on the GPU (fyprt_overlap_boxes / fyprt_overlap_boxes_device, rt_boxes.h: k_query_boxes, k_query_boxes_simple).
+"""Box-overlap queries on the GPU (fyprt_overlap_boxes / fyprt_overlap_boxes_device, rt_boxes.h: BoxLaneT behind rt_query.h's kernel templates).
 Every comparison is bit for bit against tests/boxes_ref.py (every leaf record of ctx.export_bvh() tested, no tree): indices, unused
 slots, counts and totals.
   * the stack of coplanar layers: slabs of no thickness exactly on a layer, boxes across several layers, the whole scene; K from 1 to

@@ -1,4 +1,4 @@
-"""Multi-hit queries on the GPU (fyprt_trace_ray_hits / fyprt_trace_ray_hits_device, rt_query.h: k_query_hits, k_query_hits_simple).
+"""Multi-hit queries on the GPU (fyprt_trace_ray_hits / fyprt_trace_ray_hits_device, rt_query.h: HitsLaneT behind its kernel templates).
 Every comparison is bit for bit against tests/multihit_ref.py (every leaf record of ctx.export_bvh() tested, no tree): records, unused
 slots and counts.
   * a stack of coplanar layers with exact-t ties, K = 1..8, both kernels of tuning key 15, with its own coverage asserted;

@@ -1,5 +1,5 @@
-"""Nearest-point queries on the GPU (fyprt_nearest_points / fyprt_nearest_points_device, rt_points.h: k_query_points,
-k_query_points_simple).  Every comparison is bit for bit against tests/points_ref.py (every leaf record of ctx.export_bvh() measured, no
+"""Nearest-point queries on the GPU (fyprt_nearest_points / fyprt_nearest_points_device, rt_points.h: PointsLaneT behind rt_query.h's
+kernel templates).  Every comparison is bit for bit against tests/points_ref.py (every leaf record of ctx.export_bvh() measured, no
 tree): records, unused slots and counts.
   * the stack of coplanar layers, where every point has exact ties, K = 1..8, both kernels of tuning key 15;
   * hall_small under the three builders: points jittered off the surfaces the camera sees, uniform points in twice the scene box, points

@@ -28,15 +28,18 @@ def main():
             k, v = body.rsplit(":", 1)
             cur[k.strip()] = v.strip()
     names = subprocess.run(["c++filt"], input="\n".join(r["name"] for r in rows), capture_output=True, text=True).stdout.splitlines()
-    print(f"{'kernel':44s} {'VGPR':>5s} {'spill':>6s} {'scratch':>8s} {'waves':>6s} {'LDS':>6s}")
-    bad = 0
+    shown = []
     for r, n in zip(rows, names):
         n = re.sub(r"\(.*", "", n).replace("void ", "")
-        if not show_all and (not n.startswith("rt::k_") or "lbvh" in n):
-            continue
+        if show_all or (n.startswith("rt::k_") and "lbvh" not in n):
+            shown.append((r, n))
+    w = max([44] + [len(n) for _, n in shown])                 # (the query kernels carry their lane state's name: rt::k_query<rt::RayLane<false, false> >)
+    print(f"{'kernel':{w}s} {'VGPR':>5s} {'spill':>6s} {'scratch':>8s} {'waves':>6s} {'LDS':>6s}")
+    bad = 0
+    for r, n in shown:
         sc = int(r.get("ScratchSize [bytes/lane]", 0))
         bad += sc > 0
-        print(f"{n:44s} {r.get('VGPRs', '?'):>5s} {r.get('VGPRs Spill', r.get('VGPR Spill', '?')):>6s} {sc:8d} {r.get('Occupancy [waves/SIMD]', '?'):>6s} {r.get('LDS Size [bytes/block]', '?'):>6s}")
+        print(f"{n:{w}s} {r.get('VGPRs', '?'):>5s} {r.get('VGPRs Spill', r.get('VGPR Spill', '?')):>6s} {sc:8d} {r.get('Occupancy [waves/SIMD]', '?'):>6s} {r.get('LDS Size [bytes/block]', '?'):>6s}")
     print(f"kernels with scratch: {bad}")
 
 

@@ -6,7 +6,8 @@ the same process, for three edits —
   (iii) a column mesh (7 680 triangles) reassigned to a light material and back (reassignment kernel, list, records, all light trees).
 Wall time: medians over interleaved repetitions (update, upload, next case, ...).  Device time: the sum of the kernel times (and, apart,
 of the copies) of one update_materials call, from a rocprofv3 kernel + memory-copy trace of a child process that runs the same edits;
-the cases are separated in the trace by a one-ray query, whose kernel serves as a marker.
+the cases are separated in the trace by a one-ray query, whose kernel serves as a marker (MARKER matches the kernel names of the
+closest-hit lane state, rt::k_query<rt::RayLane<false, ...>> and k_query_simple of it, whichever tuning key 15 chooses).
   usage: material_edit_rate.py [--reps 7] [--no-trace] [--out profiles/materials/material_edit_rate.jsonl]
          material_edit_rate.py --child REPS          (what runs under rocprofv3)"""
 import argparse
@@ -28,7 +29,7 @@ from fypraytracer_amd import capi, scenes  # noqa: E402
 
 CASES = ("albedo", "emission_power", "reassign_column")
 UPDATE_KERNELS = ("k_set_mesh_material", "k_emissive_count", "k_emissive_scan", "k_emissive_scatter", "k_build_light_records")
-MARKER = "k_query_rays"
+MARKER = "RayLane<false"
 
 
 def make_scene():

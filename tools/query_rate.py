@@ -21,8 +21,10 @@ another file.
 With --boxes K [K ...]: the box-overlap query (fyprt_overlap_boxes) on three sets of 1920x1080 boxes centred on the camera hits, with
 half extents of 0.1 %, 0.5 % and 2 % of the scene diameter: per set and K the median, minimum and maximum hipEvent ms, Mboxes/s, node
 visits, box and triangle tests and accepted triangles per box (one counted call), and the ratio to the closest-hit query of the camera
-rays, timed in the same run.  Written to profiles/query/boxes_rate.jsonl unless --out names another file.
-  usage: python tools/query_rate.py --boxes 1 8 32 [--calls 20] [--out FILE.jsonl]
+rays, timed in the same run.  Written to profiles/query/boxes_rate.jsonl unless --out names another file.  --key15 V sets tuning key 15
+(1: persistent waves, 2: one thread per box) and --mask-table a mesh mask table of all ones (the filtered kernels, every triangle
+admitted) before anything is timed; both are noted in every row.  (FYPRT_LIB names another build of the library: A/B runs.)
+  usage: python tools/query_rate.py --boxes 1 8 32 [--key15 V] [--mask-table] [--calls 20] [--out FILE.jsonl]
 With --filter: the query filter (fyprt_set_mesh_query_masks / fyprt_set_query_mask) on the bench hall.  Two contexts hold the scene, one
 with a mesh mask table and one without; per case the four families (closest hit, hits K = 4, nearest points, boxes K = 8) are timed on
 the same records, the two contexts' calls alternating: (1) a table and a query mask of all ones — the price of the checks; (2) one
@@ -258,6 +260,10 @@ def main_boxes(a):
     hall, cam = scenes.hall_scene(), scenes.hall_camera(W, H)
     ctx = capi.Context(0)
     ctx.upload_scene(hall)
+    if a.key15:
+        ctx.set_tuning(15, a.key15)
+    if a.mask_table:
+        ctx.set_mesh_query_masks(np.full(len(hall.meshes), 0xFFFFFFFF, dtype=np.uint32))
     o, d = camera_rays(cam)
     for _ in range(3):
         ctx.trace_rays(o, d)
@@ -274,7 +280,7 @@ def main_boxes(a):
         h = F32(frac * diam)
         rows += boxes_rate(ctx, name, (centre - h).astype(F32), (centre + h).astype(F32), a.boxes, a.calls, med0)
     ctx.close()
-    lines = [json.dumps(r) for r in rows]
+    lines = [json.dumps({**r, "key15": a.key15, "mask_table": a.mask_table}) for r in rows]
     print("\n".join(lines), flush=True)
     out = Path(a.out) if a.out else ROOT / "profiles" / "query" / "boxes_rate.jsonl"
     out.parent.mkdir(parents=True, exist_ok=True)
@@ -370,6 +376,8 @@ def main():
     ap.add_argument("--hits", type=int, nargs="+", default=None, metavar="K", help="time the multi-hit query at these max_hits instead")
     ap.add_argument("--points", type=int, nargs="+", default=None, metavar="K", help="time the nearest-point query at these max_hits instead")
     ap.add_argument("--boxes", type=int, nargs="+", default=None, metavar="K", help="time the box-overlap query at these max_hits instead")
+    ap.add_argument("--key15", type=int, default=0, metavar="V", help="with --boxes: tuning key 15 (0: the library's choice)")
+    ap.add_argument("--mask-table", action="store_true", help="with --boxes: a mesh mask table of all ones, so that the filtered kernels run")
     ap.add_argument("--filter", action="store_true", help="time the four families with and without a query filter instead")
     a = ap.parse_args()
     if a.boxes and not all(1 <= k <= capi.OVERLAP_MAX_HITS for k in a.boxes):
