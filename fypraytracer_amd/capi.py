@@ -75,6 +75,10 @@ assert POINT_DTYPE.itemsize == 16 and POINT_HIT_DTYPE.itemsize == 16
 BOX_DTYPE = np.dtype([("lo", "<f4", (3,)), ("pad0", "<u4"), ("hi", "<f4", (3,)), ("pad1", "<u4")])
 assert BOX_DTYPE.itemsize == 32
 OVERLAP_MAX_HITS = 32            # FYPRT_OVERLAP_MAX_HITS
+# triangle-overlap queries (fyprt_overlap_triangles): fyprt_triangle (48 B; the pads are ignored); answers as the box query's
+# (TRIANGLE_DTYPE is the scene's index triangle above)
+QUERY_TRIANGLE_DTYPE = np.dtype([("v0", "<f4", (3,)), ("pad0", "<u4"), ("v1", "<f4", (3,)), ("pad1", "<u4"), ("v2", "<f4", (3,)), ("pad2", "<u4")])
+assert QUERY_TRIANGLE_DTYPE.itemsize == 48
 NO_TRIANGLE = 0xFFFFFFFF         # an unused slot of a box's answer; as `after`, a finished box
 RENDER_RAYS_CHUNK = 1 << 21      # FYPRT_RENDER_RAYS_CHUNK: rays per internal pass of fyprt_render_rays*
 BVH_NODE_DTYPE = np.dtype([("origin", "<f4", 3), ("ex", "u1", 3), ("meta", "u1"), ("child", "<i4", 4),
@@ -258,6 +262,7 @@ EXPORTED_SYMBOLS = [
     "fyprt_kept_primary_frames",
     "fyprt_nearest_points", "fyprt_nearest_points_device",
     "fyprt_overlap_boxes", "fyprt_overlap_boxes_device",
+    "fyprt_overlap_triangles", "fyprt_overlap_triangles_device",
     "fyprt_set_mesh_query_masks", "fyprt_set_query_mask", "fyprt_get_query_filter",
 ]
 # enum fyprt_probe (fyprt_selftest_functions) and the 32-bit words of one input / output record of each probe
@@ -343,6 +348,9 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     if hasattr(lib, "fyprt_overlap_boxes"):
         lib.fyprt_overlap_boxes.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp, C.POINTER(FrameStats)]
         lib.fyprt_overlap_boxes_device.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp]
+    if hasattr(lib, "fyprt_overlap_triangles"):
+        lib.fyprt_overlap_triangles.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp, C.POINTER(FrameStats)]
+        lib.fyprt_overlap_triangles_device.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp]
     if hasattr(lib, "fyprt_set_mesh_query_masks"):
         lib.fyprt_set_mesh_query_masks.argtypes = [vp, vp, u32]
         lib.fyprt_set_query_mask.argtypes = [vp, u32]
@@ -856,6 +864,36 @@ class Context:
         return rec
 
     @staticmethod
+    def _tri_records(who, tris):
+        """`tris`: (N, 3, 3) vertices, or three (N, 3) arrays (the first, second and third vertices)."""
+        if isinstance(tris, (tuple, list)) and len(tris) == 3 and all(np.ndim(t) >= 1 for t in tris):
+            parts = [np.asarray(t, dtype=np.float32) for t in tris]
+            for name, a in zip(("v0", "v1", "v2"), parts):
+                if a.size % 3 or (a.ndim > 1 and a.shape[-1] != 3) or a.ndim > 2:
+                    raise ValueError(f"{who}: {name} must be (N, 3), got shape {a.shape}")
+            parts = [a.reshape(-1, 3) for a in parts]
+            if not len(parts[0]) == len(parts[1]) == len(parts[2]):
+                raise ValueError(f"{who}: {len(parts[0])} first, {len(parts[1])} second and {len(parts[2])} third vertices")
+            t = np.stack(parts, axis=1)
+        else:
+            t = np.asarray(tris, dtype=np.float32)
+            if t.ndim not in (2, 3) or t.shape[-2:] != (3, 3):
+                raise ValueError(f"{who}: tris must be (N, 3, 3) or three (N, 3) arrays, got shape {t.shape}")
+            t = t.reshape(-1, 3, 3)
+        rec = np.zeros(len(t), dtype=QUERY_TRIANGLE_DTYPE)
+        rec["v0"], rec["v1"], rec["v2"] = t[:, 0], t[:, 1], t[:, 2]
+        return rec
+
+    @staticmethod
+    def _index_after(who, after, n):
+        if after is None:
+            return None
+        aft = np.asarray(after)
+        if aft.dtype != np.uint32 or aft.size != n:
+            raise ValueError(f"{who}: after must be {n} uint32 triangle indices")
+        return np.ascontiguousarray(aft.reshape(-1))
+
+    @staticmethod
     def _check_max_hits(who, max_hits, cap=QUERY_MAX_HITS):
         if not isinstance(max_hits, (int, np.integer)) or isinstance(max_hits, bool) or not 1 <= int(max_hits) <= cap:
             raise ValueError(f"{who}: max_hits must be an integer in 1..{cap}, got {max_hits!r}")
@@ -1037,12 +1075,7 @@ class Context:
         totals (N,) uint32: every accepted triangle, also those beyond K); with `with_stats` also the FrameStats of the launch."""
         k = self._check_max_hits("overlap_boxes", max_hits, OVERLAP_MAX_HITS)
         rec = self._box_records("overlap_boxes", lo, hi)
-        aft = None
-        if after is not None:
-            aft = np.asarray(after)
-            if aft.dtype != np.uint32 or aft.size != len(rec):
-                raise ValueError(f"overlap_boxes: after must be {len(rec)} uint32 triangle indices")
-            aft = np.ascontiguousarray(aft.reshape(-1))
+        aft = self._index_after("overlap_boxes", after, len(rec))
         return self._list_query("fyprt_overlap_boxes", rec, aft, k, np.uint32, with_stats, totals=True)
 
     def overlap_boxes_tensor(self, boxes, max_hits, after=None):
@@ -1060,6 +1093,33 @@ class Context:
         k = self._check_max_hits("triangles_in_boxes", max_hits, OVERLAP_MAX_HITS)
         rec = self._box_records("triangles_in_boxes", lo, hi)
         return self._all_records(len(rec), k, np.uint32, lambda live, after: self.overlap_boxes(rec["lo"][live], rec["hi"][live], k, after)[:2])
+
+    def overlap_triangles(self, tris, max_hits=OVERLAP_MAX_HITS, after=None, with_stats=False):
+        """Triangle-overlap query (fyprt_overlap_triangles, blocking): the `max_hits` lowest indices of the scene triangles that cut each
+        query triangle.  `tris`: (N, 3, 3), or three (N, 3) arrays; `after`: None or N uint32 — only triangles with a greater index are
+        returned, and NO_TRIANGLE (an unused slot) finishes the record.  Returns (triangles (N, K) uint32 ascending, unused slots
+        NO_TRIANGLE; counts (N,) uint32; totals (N,) uint32: every accepted triangle, also those beyond K); with `with_stats` also the
+        FrameStats of the launch."""
+        k = self._check_max_hits("overlap_triangles", max_hits, OVERLAP_MAX_HITS)
+        rec = self._tri_records("overlap_triangles", tris)
+        aft = self._index_after("overlap_triangles", after, len(rec))
+        return self._list_query("fyprt_overlap_triangles", rec, aft, k, np.uint32, with_stats, totals=True)
+
+    def overlap_triangles_tensor(self, tris, max_hits, after=None):
+        """Triangle-overlap query on device tensors (fyprt_overlap_triangles_device).  `tris`: contiguous float32 (N, 12) tensor on this
+        context's GPU, one fyprt_triangle per row (v0, pad, v1, pad, v2, pad); `after`: None or a contiguous int32 (N,) tensor of
+        indices.  Returns int32 tensors: triangles (N, K) (unused slots -1), counts (N,), totals (N,).  Ordered against torch's current
+        stream exactly as trace_rays_tensor is."""
+        k = self._check_max_hits("overlap_triangles_tensor", max_hits, OVERLAP_MAX_HITS)
+        return self._list_query_tensor("fyprt_overlap_triangles_device", "overlap_triangles_tensor", "tris", tris, 12, k, after, words=1)
+
+    def triangles_touching(self, tris, max_hits=OVERLAP_MAX_HITS):
+        """Every scene triangle that cuts every query triangle, ascending by index: continuation passes of overlap_triangles until every
+        record is finished.  Returns (indices, offsets) shaped as triangles_in_boxes'."""
+        k = self._check_max_hits("triangles_touching", max_hits, OVERLAP_MAX_HITS)
+        rec = self._tri_records("triangles_touching", tris)
+        q = np.stack([rec["v0"], rec["v1"], rec["v2"]], axis=1)
+        return self._all_records(len(rec), k, np.uint32, lambda live, after: self.overlap_triangles(q[live], k, after)[:2])
 
     def render_rays(self, origins, directions, settings: Settings, frame_index=1, first_index=0, pixel_indices=None, tmin=0.0, tmax=np.inf,
                     want_payload=False, with_stats=False):

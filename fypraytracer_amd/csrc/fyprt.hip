@@ -19,6 +19,7 @@
 #include "rt_query.h"
 #include "rt_points.h"
 #include "rt_boxes.h"
+#include "rt_triangles.h"
 #include "rt_denoise.h"
 #include "rt_temporal.h"
 #include "rt_upscale.h"
@@ -232,6 +233,7 @@ struct fyprt_context {
     };
     QueryFamily rayQuery, hitsQuery, pointsQuery;      // fyprt_trace_rays* (and the primary segments of fyprt_render_rays*), fyprt_trace_ray_hits*, fyprt_nearest_points*
     QueryFamily boxesQuery;                            // fyprt_overlap_boxes*
+    QueryFamily trianglesQuery;                        // fyprt_overlap_triangles*
     // Query filter (fyprt_set_mesh_query_masks / fyprt_set_query_mask, rt_filter.h).  meshMasks: one word per mesh of the scene, empty =
     // filter off.  The derived device data — the non-empty meshes' first triangles ascending and their masks (what the leaf pass searches),
     // a word per leaf record, a word per node — is built on the context stream by the first filtered query after the table was set or
@@ -491,7 +493,8 @@ static int run_host_query(fyprt_context* c, fyprt_context::QueryFamily& f, const
     return FYPRT_OK;
 }
 
-// ---- the list queries: multi-hit (rt_query.h), nearest points (rt_points.h) and box overlap (rt_boxes.h).  As the batched queries:
+// ---- the list queries: multi-hit (rt_query.h), nearest points (rt_points.h), box overlap (rt_boxes.h) and triangle overlap
+// (rt_triangles.h).  As the batched queries:
 // the scene is read, the query's own results and counters are written, no frame state moves.
 // A family: state, kernels[simple][counted] in both forms, and what differs between the families — float4s per input record, bytes per
 // `after` record and per list entry (16: a hit record; 4: a bare triangle index), the cap on max_hits, whether a totals array follows
@@ -504,6 +507,7 @@ template <class Q> struct ListQuery {
 static const ListQuery<QueryHits> kRayHits = {&fyprt_context::hitsQuery, query_kernels<HitsLaneT>(), 2, 16, 16, FYPRT_QUERY_MAX_HITS, false, "rays", "hits", "trace"};
 static const ListQuery<QueryHits> kNearestPoints = {&fyprt_context::pointsQuery, query_kernels<PointsLaneT>(), 1, 16, 16, FYPRT_QUERY_MAX_HITS, false, "points", "hits", "query"};
 static const ListQuery<QueryBoxes> kOverlapBoxes = {&fyprt_context::boxesQuery, query_kernels<BoxLaneT>(), 2, 4, 4, FYPRT_OVERLAP_MAX_HITS, true, "boxes", "triangles", "query"};
+static const ListQuery<QueryTriangles> kOverlapTriangles = {&fyprt_context::trianglesQuery, query_kernels<TriLaneT>(), 3, 4, 4, FYPRT_OVERLAP_MAX_HITS, true, "triangles", "triangles", "query"};
 
 // `who`: the entry point.  Input records are loaded as 16-byte quads; `after` and the list are loaded and stored in their own units.
 template <class Q>
@@ -532,6 +536,9 @@ static void list_record(QueryHits& q, const float4* in, const void* after, void*
 }
 static void list_record(QueryBoxes& q, const float4* in, const void* after, void* out, uint32_t* counts, uint32_t* totals) {
     q.boxes = in; q.after = static_cast<const uint32_t*>(after); q.triangles = static_cast<uint32_t*>(out); q.counts = counts; q.totals = totals;
+}
+static void list_record(QueryTriangles& q, const float4* in, const void* after, void* out, uint32_t* counts, uint32_t* totals) {
+    q.tris = in; q.after = static_cast<const uint32_t*>(after); q.triangles = static_cast<uint32_t*>(out); q.counts = counts; q.totals = totals;
 }
 // (device memory, count > 0, after / counts / totals may be NULL)
 template <class Q>
@@ -2478,6 +2485,18 @@ int fyprt_overlap_boxes_device(fyprt_context* c, const void* boxes, const void* 
                                void* totals) {
     TRY(check_list_query(c, kOverlapBoxes, "fyprt_overlap_boxes_device", boxes, after, count, max_hits, triangles, hit_counts, totals, true));
     return device_list_query(c, kOverlapBoxes, boxes, after, count, max_hits, triangles, hit_counts, totals);
+}
+
+// ---- triangle-overlap queries (rt_triangles.h): the box query's walk and list around a triangle / triangle leaf test
+int fyprt_overlap_triangles(fyprt_context* c, const fyprt_triangle* tris, const uint32_t* after, uint32_t count, uint32_t max_hits, uint32_t* triangles,
+                            uint32_t* hit_counts, uint32_t* totals, fyprt_frame_stats* stats) {
+    TRY(check_list_query(c, kOverlapTriangles, "fyprt_overlap_triangles", tris, after, count, max_hits, triangles, hit_counts, totals, false));
+    return host_list_query(c, kOverlapTriangles, tris, after, count, max_hits, triangles, hit_counts, totals, stats);
+}
+int fyprt_overlap_triangles_device(fyprt_context* c, const void* tris, const void* after, uint32_t count, uint32_t max_hits, void* triangles, void* hit_counts,
+                                   void* totals) {
+    TRY(check_list_query(c, kOverlapTriangles, "fyprt_overlap_triangles_device", tris, after, count, max_hits, triangles, hit_counts, totals, true));
+    return device_list_query(c, kOverlapTriangles, tris, after, count, max_hits, triangles, hit_counts, totals);
 }
 
 // ---- radiance queries (rt_query.h: k_render_rays_primary; rt_paths.h: the path stages with CAM = RaySource).  A frame's sample of

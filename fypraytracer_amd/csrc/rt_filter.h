@@ -1,5 +1,5 @@
 // Query filters (fyprt_set_mesh_query_masks / fyprt_set_query_mask): every mesh carries a 32-bit group mask M[m], a query call one mask
-// Q, and a triangle of mesh m is admitted iff (M[m] & Q) != 0.  The four query families (rt_query.h, rt_points.h, rt_boxes.h) run their
+// Q, and a triangle of mesh m is admitted iff (M[m] & Q) != 0.  The five query families (rt_query.h, rt_points.h, rt_boxes.h, rt_triangles.h) run their
 // existing rules over the admitted leaf records only; frames, radiance queries, denoisers and edits never look at a mask.
 //
 // Derived data, built lazily on the context stream by the first filtered query after the table was set or the tree changed:

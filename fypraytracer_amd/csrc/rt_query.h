@@ -64,8 +64,8 @@ RT_DEV void count_query_ray(const DevScene& sc, uint32_t nBox, uint32_t nTri, ui
 //   visit<COUNT>(sc, cur, st, nBox, nNode)     one node visit (node_step / point_node_step)
 //   leaf<COUNT>(sc, q, cur, nTri)              one leaf's triangles against the state; true when the record is finished by it
 //   finish(sc, q, i)                           stores the answer; whether it counts as a hit
-// Four of them, each plain and filtered: RayLane<OCCLUDED, FILTER> here, HitsLaneT<FILTER> further down, PointsLaneT in rt_points.h,
-// BoxLaneT in rt_boxes.h.  The compiler replaces a lane state by its scalars (tools/kernel_resources.py shows the registers of the
+// Five of them, each plain and filtered: RayLane<OCCLUDED, FILTER> here, HitsLaneT<FILTER> further down, PointsLaneT in rt_points.h,
+// BoxLaneT in rt_boxes.h, TriLaneT in rt_triangles.h.  The compiler replaces a lane state by its scalars (tools/kernel_resources.py shows the registers of the
 // hand-written bodies these replaced, profiles/query/).
 
 // Persistent waves: one in-flight record per lane, idle lanes refilled from the wave's claimed chunk.

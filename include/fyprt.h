@@ -798,16 +798,57 @@ int fyprt_overlap_boxes(fyprt_context* ctx, const fyprt_box* boxes, const uint32
 int fyprt_overlap_boxes_device(fyprt_context* ctx, const void* boxes, const void* after, uint32_t count, uint32_t max_hits, void* triangles,
                                void* hit_counts, void* totals);
 
+/* Triangle-overlap query: the scene triangles that cut each of the caller's triangles, lowest indices first (DESIGN.md §4,
+ * "Triangle-overlap queries") — the narrow phase behind fyprt_overlap_boxes' broad phase: collision checks, interpenetration
+ * highlighting, placement validation after an import, contact lists for a physics step.  Mask out the mesh in hand (query filters,
+ * below) and query its triangles.
+ * Every operation is rounded on its own in IEEE binary32 (no contraction); dot, cross, min / max as selects, min and max of three and
+ * the positively written comparisons are exactly those of the box query above, so a NaN anywhere in a scene record rejects it.
+ *   Test        : for the query triangle (q0, q1, q2) and a leaf record (v0, e1, e2) as fyprt_export_bvh returns it:
+ *                   1. v1 = v0 + e1;  v2 = v0 + e2;  lo.a = min(q0.a, q1.a, q2.a), hi.a = max(q0.a, q1.a, q2.a) per axis a
+ *                   2. coordinate axes, on the untranslated coordinates: for each axis a, mn / mx over v0.a, v1.a, v2.a:
+ *                        require mn <= hi.a and mx >= lo.a       (step 2 of the box rule with the query triangle's bounds as the box)
+ *                   3. f1 = q1 - q0;  f2 = q2 - q0;  p_k = v_k - q0
+ *                   4. for an axis a: t_k = dot(a, p_k), s1 = dot(a, f1), s2 = dot(a, f2);
+ *                        require min(t_0, t_1, t_2) <= max(0, s1, s2) and max(t_0, t_1, t_2) >= min(0, s1, s2)
+ *                      applied to 17 axes:
+ *                        the two normals n = cross(e1, e2) and m = cross(f1, f2);
+ *                        nine edge pairs cross(g, h), g in (e1, e2 - e1, e2) outer, h in (f1, f2 - f1, f2) inner;
+ *                        six in-plane edge normals cross(n, g) for the three g, then cross(m, h) for the three h
+ *                      (the in-plane axes decide coplanar pairs, where n, m are parallel and every edge pair is parallel to them).
+ *                 The result is the conjunction; the order in which the axes are evaluated does not matter.
+ *   Acceptance  : every requirement holds and, with `after`, the triangle index is greater than after[i].
+ *   Touching    : is decided by this rounded arithmetic.
+ *   Guaranteed  : with finite values, a query vertex that is bit-equal to a record's v0 always accepts that record.  For q0 == v0, p_0 is
+ *                 0 and lies in every interval that holds 0.  For q1 == v0, p_0 = fl(v0 - q0) is the very f1, so t_0 and s1 are the same
+ *                 bits on every axis; likewise q2 and f2.  Step 2 holds because v0.a lies in [lo.a, hi.a].
+ *   Degenerate  : a zero-area query triangle is valid, and a zero-area scene record is tested like any other; both are decided by the rule
+ *                 as written, which is complete (separates every disjoint pair in exact arithmetic) only for triangles with area.
+ *   Invalid     : a query triangle with a non-finite component of q0, q1, q2, f1 or f2 — zero records and total 0 without traversal,
+ *                 counted as a query with no tests.  The pads are ignored.
+ *   Order, continuation, errors, state, tuning keys, the max_hits cap and the counters are the box query's, word for word, with
+ *   "triangles" for the input and "triangles" for the output in the error texts (device entry: the query triangles 16-byte, the rest
+ *   4-byte aligned), and with ray counting on rays = query triangles.  The answer does not depend on the tree, the builder or the
+ *   visiting order: it is a function of the leaf records (of the admitted triangles, with a mask table set) alone. */
+typedef struct fyprt_triangle { float v0[3]; uint32_t pad0; float v1[3]; uint32_t pad1; float v2[3]; uint32_t pad2; } fyprt_triangle; /* 48 B, 16-B aligned on the device */
+/* Host memory, blocking.  `triangles`: count x max_hits scene-triangle indices, query-major.  `stats` as fyprt_overlap_boxes'. */
+int fyprt_overlap_triangles(fyprt_context* ctx, const fyprt_triangle* tris, const uint32_t* after /* NULL or count */, uint32_t count,
+                            uint32_t max_hits, uint32_t* triangles /* count x max_hits */, uint32_t* hit_counts /* NULL or count */,
+                            uint32_t* totals /* NULL or count */, fyprt_frame_stats* stats /* may be NULL */);
+/* Device memory of the context's GPU, asynchronous on the context stream (fyprt_stream). */
+int fyprt_overlap_triangles_device(fyprt_context* ctx, const void* tris, const void* after, uint32_t count, uint32_t max_hits,
+                                   void* triangles, void* hit_counts, void* totals);
+
 /* ------------------------------------------------------------------------------------------------- query filters
- * New (no reference counterpart): per-mesh group masks for the four query families above, so that a query can leave a mesh out (snapping
+ * New (no reference counterpart): per-mesh group masks for the five query families above, so that a query can leave a mesh out (snapping
  * a dragged mesh onto its neighbours, clearance around it, a broad phase against everything else) or look at one mesh alone (picking
  * within the selection).  The meshes are the instances ("Query filters").
  *   The mesh mask table M: one 32-bit word per mesh of the uploaded scene.  The query mask Q: one word per context, 0xFFFFFFFF by default.
  *   The rule: the meshes partition the triangle list (upload and append enforce it); a triangle of mesh m is admitted iff (M[m] & Q) != 0.
- *   With a table set, acceptance in the eight entry points fyprt_trace_rays, fyprt_trace_ray_hits, fyprt_nearest_points,
- *   fyprt_overlap_boxes and their _device forms gets the extra condition "the triangle is admitted".  Nothing else changes: keys, order,
- *   continuation (`after`), unused records, counts, invalid records and error order are as stated above, and the box query's totals count
- *   admitted triangles only.  Each answer is the family's rule applied to the leaf records of the admitted triangles alone.  The
+ *   With a table set, acceptance in the ten entry points fyprt_trace_rays, fyprt_trace_ray_hits, fyprt_nearest_points,
+ *   fyprt_overlap_boxes, fyprt_overlap_triangles and their _device forms gets the extra condition "the triangle is admitted".  Nothing
+ *   else changes: keys, order, continuation (`after`), unused records, counts, invalid records and error order are as stated above, and
+ *   the box and triangle queries' totals count admitted triangles only.  Each answer is the family's rule applied to the leaf records of the admitted triangles alone.  The
  *   closest-hit query keeps its rule for exact-t ties (the first found in traversal order, among admitted triangles); the list queries stay
  *   independent of the tree.
  *   Not touched: frames of every technique, fyprt_render_rays* (its primary pass and the payloads it returns are unfiltered), the

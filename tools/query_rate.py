@@ -25,6 +25,17 @@ rays, timed in the same run.  Written to profiles/query/boxes_rate.jsonl unless 
 (1: persistent waves, 2: one thread per box) and --mask-table a mesh mask table of all ones (the filtered kernels, every triangle
 admitted) before anything is timed; both are noted in every row.  (FYPRT_LIB names another build of the library: A/B runs.)
   usage: python tools/query_rate.py --boxes 1 8 32 [--key15 V] [--mask-table] [--calls 20] [--out FILE.jsonl]
+With --triangles K [K ...]: the triangle-overlap query (fyprt_overlap_triangles).  The query triangles are the triangles of the bench
+hall's largest mesh (at most 262 144 of them) under three offsets: (a) where the mesh lies, (b) moved by half its size along its longest
+axis, (c) moved two scene diameters away, clear of everything.  Per set and K the median, minimum and maximum hipEvent ms, Mtriangles/s,
+node visits, box and triangle tests and accepted triangles per query (one counted call); and, from the same process on the same
+triangles' bounding boxes at the same K, the box-overlap query's figures and the ratio of the two medians.  --key15 and --mask-table as
+for --boxes.  Written to profiles/query/triangles_rate.jsonl unless --out names another file.
+  usage: python tools/query_rate.py --triangles 1 8 32 [--key15 V] [--mask-table] [--calls 20] [--out FILE.jsonl]
+With --triangles-summary FILE [FILE ...]: no GPU; the files of several --triangles processes folded into one line per (key 15, mask
+table, set, K) — the median of the processes' medians for both queries, every process's median, their ratio and the counters — written
+to profiles/query/triangles_rate_summary.jsonl unless --out names another file, and printed as a table.
+  usage: python tools/query_rate.py --triangles-summary profiles/query/triangles_rate_key*_run*.jsonl
 With --filter: the query filter (fyprt_set_mesh_query_masks / fyprt_set_query_mask) on the bench hall.  Two contexts hold the scene, one
 with a mesh mask table and one without; per case the four families (closest hit, hits K = 4, nearest points, boxes K = 8) are timed on
 the same records, the two contexts' calls alternating: (1) a table and a query mask of all ones — the price of the checks; (2) one
@@ -287,6 +298,81 @@ def main_boxes(a):
     out.write_text("\n".join(lines) + "\n")
 
 
+def main_triangles(a):
+    """The triangles of the hall's largest mesh under three offsets against the hall, and the box query on their bounding boxes."""
+    hall = scenes.hall_scene()
+    ctx = capi.Context(0)
+    ctx.upload_scene(hall)
+    if a.key15:
+        ctx.set_tuning(15, a.key15)
+    if a.mask_table:
+        ctx.set_mesh_query_masks(np.full(len(hall.meshes), 0xFFFFFFFF, dtype=np.uint32))
+    mesh = int(np.argmax([m[1] for m in hall.meshes]))
+    first, count = int(hall.meshes[mesh][0]), min(int(hall.meshes[mesh][1]), 1 << 18)
+    t = hall.triangles[first:first + count]
+    pos = hall.world_vertices["position"]
+    q = np.stack([pos[t["v0"]], pos[t["v1"]], pos[t["v2"]]], axis=1).astype(F32)
+    allpos = pos.astype(np.float64)
+    diam = float(np.linalg.norm(allpos.max(axis=0) - allpos.min(axis=0)))
+    size = q.reshape(-1, 3).max(axis=0).astype(np.float64) - q.reshape(-1, 3).min(axis=0).astype(np.float64)
+    half = np.zeros(3)
+    half[int(np.argmax(size))] = 0.5 * size.max()
+    rows = []
+    for name, shift in (("a_in_place", np.zeros(3)), ("b_half_size", half), ("c_clear", np.array([0.0, 2.0 * diam, 0.0]))):
+        qs = (q + shift.astype(F32)).astype(F32)
+        lo, hi = qs.min(axis=1), qs.max(axis=1)
+        for k in a.triangles:
+            for _ in range(3):
+                ctx.overlap_triangles(qs, max_hits=k)
+                ctx.overlap_boxes(lo, hi, max_hits=k)
+            ms = [ctx.overlap_triangles(qs, max_hits=k, with_stats=True)[3].kernel_ms for _ in range(a.calls)]
+            msb = [ctx.overlap_boxes(lo, hi, max_hits=k, with_stats=True)[3].kernel_ms for _ in range(a.calls)]
+            ctx.set_ray_counting(True)
+            _, counts, totals, st = ctx.overlap_triangles(qs, max_hits=k, with_stats=True)
+            _, _, btotals, sb = ctx.overlap_boxes(lo, hi, max_hits=k, with_stats=True)
+            ctx.set_ray_counting(False)
+            med, medb = statistics.median(ms), statistics.median(msb)
+            rows.append({"set": name, "scene": "hall_1M", "query": "triangles", "mesh": mesh, "max_hits": k, "triangles": len(qs),
+                         "ms_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4), "calls": a.calls,
+                         "mtriangles_per_s": round(len(qs) / med / 1e3, 1), "node_visits_per_query": round(st.node_visits / st.rays, 3),
+                         "box_tests_per_query": round(st.box_tests / st.rays, 3), "tri_tests_per_query": round(st.tri_tests / st.rays, 3),
+                         "accepted_per_query": round(float(totals.mean()), 3), "records_per_query": round(float(counts.mean()), 3),
+                         "boxes_ms_median": round(medb, 4), "boxes_ms_min": round(min(msb), 4), "boxes_ms_max": round(max(msb), 4),
+                         "boxes_tri_tests_per_query": round(sb.tri_tests / sb.rays, 3), "boxes_accepted_per_query": round(float(btotals.mean()), 3),
+                         "ms_over_boxes": round(med / medb, 3)})
+    ctx.close()
+    lines = [json.dumps({**r, "key15": a.key15, "mask_table": a.mask_table}) for r in rows]
+    print("\n".join(lines), flush=True)
+    out = Path(a.out) if a.out else ROOT / "profiles" / "query" / "triangles_rate.jsonl"
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text("\n".join(lines) + "\n")
+
+
+def main_triangles_summary(a):
+    rows = [json.loads(l) for f in a.triangles_summary for l in Path(f).read_text().splitlines() if l.strip()]
+    keys = sorted({(r["key15"], r["mask_table"], r["set"], r["max_hits"]) for r in rows})
+    out = []
+    for key15, mask, name, k in keys:
+        rs = [r for r in rows if (r["key15"], r["mask_table"], r["set"], r["max_hits"]) == (key15, mask, name, k)]
+        t, b = [r["ms_median"] for r in rs], [r["boxes_ms_median"] for r in rs]
+        mt, mb = statistics.median(t), statistics.median(b)
+        out.append({"set": name, "key15": key15, "mask_table": mask, "max_hits": k, "processes": len(rs), "triangles": rs[0]["triangles"],
+                    "ms_median_of_medians": round(mt, 4), "ms_runs": t, "boxes_ms_median_of_medians": round(mb, 4), "boxes_ms_runs": b,
+                    "ms_over_boxes": round(mt / mb, 3), "tri_tests_per_query": rs[0]["tri_tests_per_query"],
+                    "node_visits_per_query": rs[0]["node_visits_per_query"], "accepted_per_query": rs[0]["accepted_per_query"],
+                    "boxes_accepted_per_query": rs[0]["boxes_accepted_per_query"]})
+    dest = Path(a.out) if a.out else ROOT / "profiles" / "query" / "triangles_rate_summary.jsonl"
+    dest.parent.mkdir(parents=True, exist_ok=True)
+    dest.write_text("\n".join(json.dumps(r) for r in out) + "\n")
+    print("| key 15 | mask table | set | K = 1 | K = 8 | K = 32 |\n|---|---|---|---|---|---|")
+    for key15, mask, name in sorted({k[:3] for k in keys}):
+        cells = []
+        for k in (1, 8, 32):
+            r = [x for x in out if (x["key15"], x["mask_table"], x["set"], x["max_hits"]) == (key15, mask, name, k)]
+            cells.append(f"{r[0]['ms_median_of_medians']:.3f} / {r[0]['boxes_ms_median_of_medians']:.3f} ({r[0]['ms_over_boxes']:.2f})" if r else "-")
+        print(f"| {key15} | {'yes' if mask else 'no'} | {name} | " + " | ".join(cells) + " |")
+
+
 def filter_rows(plain, filt, case, families, calls):
     """The families of one case on both contexts: `families` maps a name to (records, call(ctx, with_stats) -> FrameStats)."""
     rows = []
@@ -376,16 +462,22 @@ def main():
     ap.add_argument("--hits", type=int, nargs="+", default=None, metavar="K", help="time the multi-hit query at these max_hits instead")
     ap.add_argument("--points", type=int, nargs="+", default=None, metavar="K", help="time the nearest-point query at these max_hits instead")
     ap.add_argument("--boxes", type=int, nargs="+", default=None, metavar="K", help="time the box-overlap query at these max_hits instead")
-    ap.add_argument("--key15", type=int, default=0, metavar="V", help="with --boxes: tuning key 15 (0: the library's choice)")
-    ap.add_argument("--mask-table", action="store_true", help="with --boxes: a mesh mask table of all ones, so that the filtered kernels run")
+    ap.add_argument("--triangles", type=int, nargs="+", default=None, metavar="K", help="time the triangle-overlap query at these max_hits instead")
+    ap.add_argument("--triangles-summary", nargs="+", default=None, metavar="FILE", help="fold the files of several --triangles processes into one summary (no GPU)")
+    ap.add_argument("--key15", type=int, default=0, metavar="V", help="with --boxes / --triangles: tuning key 15 (0: the library's choice)")
+    ap.add_argument("--mask-table", action="store_true", help="with --boxes / --triangles: a mesh mask table of all ones, so that the filtered kernels run")
     ap.add_argument("--filter", action="store_true", help="time the four families with and without a query filter instead")
     a = ap.parse_args()
     if a.boxes and not all(1 <= k <= capi.OVERLAP_MAX_HITS for k in a.boxes):
         raise SystemExit(f"--boxes takes values in 1..{capi.OVERLAP_MAX_HITS}")
+    if a.triangles and not all(1 <= k <= capi.OVERLAP_MAX_HITS for k in a.triangles):
+        raise SystemExit(f"--triangles takes values in 1..{capi.OVERLAP_MAX_HITS}")
     if a.hits and not all(1 <= k <= capi.QUERY_MAX_HITS for k in a.hits):
         raise SystemExit(f"--hits takes values in 1..{capi.QUERY_MAX_HITS}")
     if a.points and not all(1 <= k <= capi.QUERY_MAX_HITS for k in a.points):
         raise SystemExit(f"--points takes values in 1..{capi.QUERY_MAX_HITS}")
+    if a.triangles_summary:
+        return main_triangles_summary(a)
     if not torch.cuda.is_available():
         raise SystemExit("query_rate.py needs an MI355X")
     torch.cuda.set_device(0)
@@ -397,6 +489,8 @@ def main():
         return main_points(a)
     if a.boxes:
         return main_boxes(a)
+    if a.triangles:
+        return main_triangles(a)
     W, H = 1920, 1080
     rows = []
     rng = np.random.default_rng(2024)
